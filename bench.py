@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
 """bench.py — QPS of RBAC-filtered exact k-NN on MI355X (BASELINE.json's metric), with the roofline of the dominant
-scan kernel and a CPU baseline timed beside it.
+scan kernel; with --full also the sibling legs, a CPU baseline timed beside them and the oracle parity checks.
 
   python bench.py [--gpus N --steps K --warmup W]          (N > 1: spawns its own ranks through torch.distributed.run)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+  python bench.py ... --full                               everything below, not only the headline leg
+  python bench.py ... --dump-outputs DIR                   the headline leg's last timed step as DIR/<name>.npy
+
+A plain run sets up, warms up, times the K steps of the headline leg and prints one JSON line.
 
 Workload (config.workload): synthetic SIFT10M-like corpus (10M x 128 fp32, integer-valued, 100 rows per document),
 tree RBAC (1000 users / 100 roles), k = 100, L2.  A step = one batch of `--queries` queries (uniform rows x
 uniform users, a fresh batch per step from the seeded stream) through the whole hot path: staging, threshold sample,
 shared-pass scan on the matrix cores (distance + permission + running top-k), selection, exact re-rank.  Two legs are
-timed with the same K steps each:
+timed with the same K steps each (the second with --full only):
 
   value / roofline      role-level filter applied as a PRE-filter: only the rows of the user's role partition are
                         scanned (BASELINE config 2's mode on the metric's SIFT10M corpus)
@@ -28,7 +32,12 @@ element: a rate for comparison with an fp32 scan, not an HBM fraction.  `traffic
 rocprofv3 PMC pass of this command (profiles/), when one is on file for the workload.
 
 No part of the timed path touches the CPU oracle; it is used only by the cpu_baseline leg (rank 0, N = 1) and for the
-parity spot-check of the GPU results on the same sample.
+parity spot-check of the GPU results on the same sample, both under --full.
+
+--dump-outputs DIR: rows, distances, counts, block_ids and doc_ids of the last timed step of the headline leg (the merged
+top-k when the corpus is split; under role placement every rank writes its own, suffixed _rank<r>), float64 ids and
+float32 distances, at most 64 MB in all.  The inputs depend only on the arguments (--seed), so two builds run with the
+same arguments can be compared output for output.
 """
 import argparse
 import ctypes
@@ -50,7 +59,7 @@ HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md); measur
 MFMA_F32_PEAK_TF = 157.3       # fp32 matrix peak (v_mfma_f32_16x16x4_f32), same guide
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -79,11 +88,38 @@ def parse():
     ap.add_argument("--index-rows", type=int, default=120_000, help="rows of the role partition the HNSW legs (CPU port and K4) index")
     ap.add_argument("--ivf-rows", type=int, default=1_000_000, help="rows of the IVFFlat leg's corpus (0: skip the leg)")
     ap.add_argument("--seed", type=int, default=20251121)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the other legs, cold start, sustained, sibling records, "
+                         "single-query / brute-force / 768-d / index legs, CPU baselines and the oracle parity checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline leg's last timed step returned as DIR/<name>.npy (float32 / float64)")
+    return ap.parse_args(argv)
 
 
 def ptr(t):
     return ctypes.c_void_p(t.data_ptr())
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def write_outputs(path, arrays, seed=0):
+    """--dump-outputs: the arrays a caller of the timed path received ({name: array, first axis = query}) as
+    path/<name>.npy.  float32 stays float32, everything else becomes float64 (ids are exact below 2**53).  Above
+    DUMP_LIMIT_BYTES in all, a fixed seeded sample of the queries is kept, and its indices go to sampled_queries.npy."""
+    os.makedirs(path, exist_ok=True)
+    conv = {name: np.ascontiguousarray(a, dtype=np.float32 if np.asarray(a).dtype == np.float32 else np.float64)
+            for name, a in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        nq = min(a.shape[0] for a in conv.values())
+        keep = max(1, int(nq * (DUMP_LIMIT_BYTES - 8 * nq - 4096) / total))      # (room for the index and the headers)
+        idx = np.sort(np.random.default_rng(seed).choice(nq, keep, replace=False))
+        conv = {name: a[idx] for name, a in conv.items()}
+        conv["sampled_queries"] = idx.astype(np.float64)
+    for name, a in conv.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(conv)
 
 
 def self_launch(args):
@@ -602,12 +638,19 @@ def placement_bench(args, torch, dist, vsrbac, rank, local_rank, world, dev, sim
         return {"dt": dt, "dt_this_rank": mine, "t_enq": t_enq, "stats": st, "flagged": flagged() - before,
                 "kernel": sessions[0].last_scan_kernel()}
 
-    results = {leg: timed_leg(leg, args.steps, args.warmup) for leg in legs}
+    results, dumped = {}, None
+    for leg in (legs if args.full else legs[:1]):
+        results[leg] = timed_leg(leg, args.steps, args.warmup)
+        if leg == legs[0] and args.dump_outputs:      # the last timed step's results, before another leg reuses the buffers
+            i = state["i"] - 1
+            o, nqb = outs[i % n_sess], len(batches[i % nb][0])
+            dumped = {name: o[key][:nqb].cpu().numpy() for name, key in
+                      (("rows", "row"), ("distances", "dist"), ("counts", "cnt"), ("block_ids", "blk"), ("doc_ids", "doc"))}
     if any(r["flagged"] for r in results.values()):
         raise SystemExit(f"screening flagged queries in the timed region: { {m: r['flagged'] for m, r in results.items()} }")
     head = results[legs[0]]
     sustained = None
-    if args.sustained_s > 0:
+    if args.full and args.sustained_s > 0:
         s_steps = max(args.steps, int(args.sustained_s / max(head["dt"] / args.steps, 1e-6)))
         s_steps = int(reduce(float(s_steps), dist.ReduceOp.MAX if world > 1 else None))      # the same count on every rank
         srun = timed_leg(legs[0], s_steps, 1)
@@ -617,7 +660,7 @@ def placement_bench(args, torch, dist, vsrbac, rank, local_rank, world, dev, sim
     # N = 1 step's own 1000 queries spread over the ranks (strong scaling: a rank's ~1000 / N-query call is mostly per-call
     # fixed cost, five launches for ~125 queries); under --scaling strong it is the N x 1000-query step.
     sibling = None
-    if parts > 1 and os.environ.get("VSR_BENCH_NO_SIBLING") != "1":
+    if args.full and parts > 1 and os.environ.get("VSR_BENCH_NO_SIBLING") != "1":
         nbs = max(1, min(4, nb))
         other = draw(1, nbs, 500) if weak else draw(parts, nbs, 500)
         saved = (batches, d_qs, filt, outs, nb)
@@ -643,12 +686,12 @@ def placement_bench(args, torch, dist, vsrbac, rank, local_rank, world, dev, sim
         finally:
             batches, d_qs, filt, outs, nb = saved
     # parity (default on): this rank's first queries of batch 0 against the oracle over the rows it holds -- by
-    # construction ALL rows those users may see; every rank checks its own, rank 0 reports the conjunction
-    from oracle.oracle import Oracle
-    orc = Oracle("pgflags")
-    m = min(8, len(batches[0][0]))
+    # construction ALL rows those users may see; every rank checks its own, rank 0 reports the conjunction (--full)
+    m = min(8, len(batches[0][0])) if args.full else 0
     ok = 1.0
     if m:
+        from oracle.oracle import Oracle
+        orc = Oracle("pgflags")
         o = outs[0]
         corpus.search_device(ptr(d_qs[0]), len(batches[0][0]), k, "l2", filt[legs[0]][0], ptr(o["blk"]), ptr(o["doc"]), ptr(o["row"]),
                              ptr(o["dist"]), ptr(o["cnt"]), None)
@@ -660,6 +703,9 @@ def placement_bench(args, torch, dist, vsrbac, rank, local_rank, world, dev, sim
     ok_all = reduce(ok, dist.ReduceOp.MIN if world > 1 else None)
     per_rank_q = [len(qr) for qr, _ in batches]
     mean_q = reduce(float(np.mean(per_rank_q)), dist.ReduceOp.SUM if world > 1 else None)
+    if dumped is not None:                            # every rank returns the results of its own roles' queries
+        write_outputs(args.dump_outputs, dumped if world == 1 else {f"{name}_rank{rank}": a for name, a in dumped.items()},
+                      seed=args.seed + rank)
     if rank == 0:
         roof = roofline_of(head["stats"], dim, head["kernel"], n_sess)
         roof["note"] = "rank 0's main scan launches (its roles' rows); " + roof.get("note", "")
@@ -677,7 +723,7 @@ def placement_bench(args, torch, dist, vsrbac, rank, local_rank, world, dev, sim
                        "rows": n, "dim": dim, "k": k, "queries_per_step": nq_step, "filter": legs[0],
                        "sharding": f"role placement x{parts}: every role (and all it can see) on one GPU, a query touches one "
                                    f"GPU, no exchange", "exchange": "none (no data-path collective)",
-                       "recall": 1.0 if ok_all else None, "batches_in_flight": n_sess,
+                       "recall": (1.0 if ok_all else None) if args.full else None, "batches_in_flight": n_sess,
                        "setup_pass": {"steps": state.get("setup_pass_steps", 0),
                                       "note": "untimed, before the warm-up steps: every session searches every distinct batch once"}},
             "roofline": roof,
@@ -687,13 +733,16 @@ def placement_bench(args, torch, dist, vsrbac, rank, local_rank, world, dev, sim
                           "queries_per_step_this_rank": {"min": int(min(per_rank_q)), "mean": round(float(np.mean(per_rank_q)), 1),
                                                          "max": int(max(per_rank_q))},
                           "queries_per_step_all_ranks": round(mean_q, 1) if world > 1 else None},
-            "multi_rank_parity": {"queries_per_rank": m, "ids_and_distances_identical": bool(ok_all),
-                                  "checked": "every rank: its first queries of batch 0 against the oracle over the rows it holds"},
             "setup_s": {"generate": round(t_gen, 1), "load": round(t_load, 1)},
             "host_enqueue_ms_per_step": round(head["t_enq"] / args.steps * 1e3, 4),
             "screening_flagged_queries": 0,
         }
+        if args.full:
+            out["multi_rank_parity"] = {"queries_per_rank": m, "ids_and_distances_identical": bool(ok_all),
+                                        "checked": "every rank: its first queries of batch 0 against the oracle over the rows it holds"}
         for leg in legs[1:]:
+            if leg not in results:
+                continue
             r = results[leg]
             out[leg] = {"value": round(nq_step * args.steps / r["dt"], 1), "unit": "queries/s", "ms_per_step": round(r["dt"] / args.steps * 1e3, 4),
                         "roofline": roofline_of(r["stats"], dim, r["kernel"], n_sess)}
@@ -1009,6 +1058,18 @@ def main():
         ctx.profiling(False)
         return a
 
+    def last_outputs():
+        """What the last step of the run returned to its caller: the merged top-k when the corpus is split into parts."""
+        i = state["i"] - 1
+        b = i % G if world > 1 and not state["overlap"] and not rehearsal else i % nbuf      # as step() picks it
+        _, blk_b, doc_b, dist_b = d_views[b]
+        if parts == 1:
+            got = {"rows": d_rows[b], "distances": dist_b, "counts": d_cnts[b], "block_ids": blk_b, "doc_ids": doc_b}
+        else:
+            sl = slice((b % G) * nq, (b % G + 1) * nq)
+            got = {"distances": m_dist[sl], "counts": m_cnt[sl], "block_ids": m_blk[sl], "doc_ids": m_doc[sl]}
+        return {name: t.cpu().numpy() for name, t in got.items()}
+
     def spot_check(leg, orc, m):
         """Batch 0 of the leg once more, then the first m queries against the oracle (ids AND distances)."""
         corpus.search_device(ptr(d_qs[0]), nq, k, "l2", filt[leg][0], ptr(d_views[0][1]), ptr(d_views[0][2]), ptr(d_rows[0]),
@@ -1029,7 +1090,7 @@ def main():
     # first the headline leg WITHOUT the setup pass, exactly as the driver's flags alone would run it (W warm-up steps behind an
     # idle GPU): reported beside the headline as `cold_start`, so that the line shows what the setup pass changes
     cold = None
-    if world == 1 and os.environ.get("VSR_BENCH_NO_SETUP_PASS") != "1":
+    if args.full and world == 1 and os.environ.get("VSR_BENCH_NO_SETUP_PASS") != "1":
         state["skip_setup_pass"] = True
         try:
             exp = os.environ.get("VSR_BENCH_COLD_EXPERIMENT", "")      # development: what the setup pass actually warms
@@ -1075,13 +1136,16 @@ def main():
                                 "behind seconds of host-side setup, then the K timed steps"}
         finally:
             state["skip_setup_pass"] = False
-    results = {}
-    for leg in legs:
+    # a plain run times the headline leg only; --full adds the other legs and everything below that is not the headline
+    results, dumped = {}, None
+    for leg in (legs if args.full else legs[:1]):
         r = timed_leg(leg, args.steps, args.warmup)
-        r["alone"] = alone_stats(leg)
+        if leg == legs[0] and args.dump_outputs and rank == 0:      # before anything else reuses the result buffers
+            dumped = last_outputs()
+        r["alone"] = alone_stats(leg) if args.full else None
         results[leg] = r
     # (the CPU port's HNSW build runs on a host thread from here on, under the remaining GPU legs -- not under the headline legs)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and int(os.environ.get("VSR_BENCH_SIM_WORLD", "0")) <= 1:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and int(os.environ.get("VSR_BENCH_SIM_WORLD", "0")) <= 1:
         from oracle.oracle import Oracle as _OracleEarly
         vis0 = rbac.visible_docs(int(batches[0][1][0])).astype(np.int64)
         part_rows = (((vis0 - 1) * 100)[:, None] + np.arange(100)[None, :]).reshape(-1)
@@ -1100,7 +1164,7 @@ def main():
 
     # ---- sustained leg (N = 1 and N > 1 alike): >= --sustained-s seconds of headline steps, clocks and thermals settled ----
     sustained = None
-    if args.sustained_s > 0:
+    if args.full and args.sustained_s > 0:
         per = head["dt"] / args.steps
         s_steps = max(args.steps, int(args.sustained_s / max(per, 1e-6)))
         s = timed_leg(legs[0], s_steps, 1)
@@ -1190,6 +1254,8 @@ def main():
     if cold:
         out["cold_start"] = cold
     for leg in legs[1:]:
+        if leg not in recs:
+            continue
         out[leg] = recs[leg]
         out[leg]["workload"] = (f"same corpus, users and queries; filter = per-user row-level-security bitmap tested in "
                                 f"the distance loop (BASELINE config 4's mode)" if leg == "postfilter" else leg)
@@ -1198,7 +1264,7 @@ def main():
 
     # ---- sibling record (N = 1): the headline leg's queries in batches four times as large -- what a caller that can wait for
     # 4000 queries gets (and the shape a rank of a weak-scaling job sees when its queue is deep): more queries share every pass
-    if world == 1 and sim_world <= 1 and nb >= 4 and os.environ.get("VSR_BENCH_NO_LARGE_BATCH") != "1":
+    if args.full and world == 1 and sim_world <= 1 and nb >= 4 and os.environ.get("VSR_BENCH_NO_LARGE_BATCH") != "1":
         try:
             mult = 4
             nbl = nb // mult
@@ -1239,7 +1305,7 @@ def main():
 
     # ---- sibling line (N = 1): the same headline leg with the int8 planes switched off (VSR_NO_INT8): hi-only bf16 planes,
     # 260 bytes per row instead of 132, fp32 accumulation, same exact results ----
-    if world == 1 and sim_world <= 1 and not args.no_bf16_line:
+    if args.full and world == 1 and sim_world <= 1 and not args.no_bf16_line:
         try:
             os.environ["VSR_NO_INT8"] = "1"
             try:
@@ -1267,7 +1333,7 @@ def main():
     d_keys, d_blk, d_doc, d_dist = d_views[0]         # slot 0 / session 0 from here on (everything above has drained)
     d_row, d_cnt = d_rows[0], d_cnts[0]
     # ---- latency mode (informational, N = 1): the harness's call shape, one query per call ----
-    if world == 1 and sim_world <= 1:
+    if args.full and world == 1 and sim_world <= 1:
         try:
             m1 = min(200, nq)
             singles = [corpus.pack_filters([filt[legs[0]][0]._keep[i]]) for i in range(m1)]
@@ -1346,7 +1412,7 @@ def main():
     #   pre-filter: ~100 permission classes, 10..330 queries each (K2w long rows, hi + mid planes)
     # Each leg: event-timed main launch (roofline, bound "mfma": products issued / dense bf16 peak), wall time per batch,
     # flagged queries (and the time with the tiered re-run when there are any), oracle spot check within 1e-4.
-    if world == 1 and sim_world <= 1 and args.wiki_rows > 0:
+    if args.full and world == 1 and sim_world <= 1 and args.wiki_rows > 0:
         try:
             wd, wk = 768, 100
             wn = int(args.wiki_rows)
@@ -1452,7 +1518,7 @@ def main():
             print(f"[bench] leg wiki768 failed: {exc!r}", file=sys.stderr, flush=True)
 
     # ---- CPU baseline (rank 0, N = 1): the oracle, pgvector's flags, one thread, bounded sample ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle.oracle import Oracle
         orc = Oracle("pgflags")
         m = min(args.cpu_queries, nq)
@@ -1514,7 +1580,7 @@ def main():
                                      "serial (rehearsal through host memory)" if rehearsal else "serial, one per batch")
     if sim_world > 1:
         out["sim_world"] = {"parts": parts, "merged_equals_local": bool(all(r["sim_ok"] for r in results.values()))}
-    if rank == 0 and world > 1 and os.environ.get("VSR_BENCH_VERIFY", "1") != "0":
+    if args.full and rank == 0 and world > 1 and os.environ.get("VSR_BENCH_VERIFY", "1") != "0":
         # default on: the merged multi-rank result of a few queries against the oracle on the full corpus (rank 0 regenerates it)
         from oracle.oracle import Oracle
         orc = Oracle("pgflags")
@@ -1528,6 +1594,8 @@ def main():
         ok = bool((m_blk[off:off + m].cpu().numpy() == blkf[rows_o]).all() and
                   (m_dist[off:off + m].cpu().numpy() == dist_o.astype(np.float32)).all())
         out["multi_rank_parity"] = {"queries": m, "ids_and_distances_identical": ok}
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped, seed=args.seed)
     if rank == 0:
         print(json.dumps(out), flush=True)
     corpus.free()

@@ -179,6 +179,37 @@ def test_bench_roofline_arithmetic():
     assert r["frac"] <= 1.0 and r["mfma"]["frac"] < 0.1
 
 
+def test_bench_options_and_output_dump(tmp_path):
+    """bench.py: a plain run is the headline only (--full off by default); --dump-outputs writes float32 / float64 .npy
+    files, and a set above the size limit is cut to the same seeded sample of queries every time."""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(os.path.dirname(os.path.dirname(__file__)), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path / "o")])
+    assert a.full and a.dump_outputs == str(tmp_path / "o")
+    rng = np.random.default_rng(3)
+    got = {"rows": rng.integers(-1, 1 << 40, (50, 10)), "distances": rng.random((50, 10), dtype=np.float32),
+           "counts": rng.integers(0, 11, 50).astype(np.int32)}
+    assert bench.write_outputs(str(tmp_path / "o"), got) == ["counts", "distances", "rows"]
+    for name, want in got.items():
+        back = np.load(tmp_path / "o" / f"{name}.npy")
+        assert back.dtype == (np.float32 if want.dtype == np.float32 else np.float64)
+        np.testing.assert_array_equal(back, want)
+    big = {"distances": np.arange(300_000 * 64, dtype=np.float32).reshape(300_000, 64),
+           "rows": np.arange(300_000 * 64, dtype=np.int64).reshape(300_000, 64)}
+    for d in ("s1", "s2"):
+        names = bench.write_outputs(str(tmp_path / d), big, seed=5)
+        assert "sampled_queries" in names
+        assert sum(os.path.getsize(tmp_path / d / f"{n}.npy") for n in names) <= bench.DUMP_LIMIT_BYTES
+    idx = np.load(tmp_path / "s1" / "sampled_queries.npy").astype(np.int64)
+    np.testing.assert_array_equal(idx, np.load(tmp_path / "s2" / "sampled_queries.npy"))
+    np.testing.assert_array_equal(np.load(tmp_path / "s1" / "rows.npy"), big["rows"][idx])
+
+
 def test_role_placement_covers_every_query_exactly_once():
     """bench.py's N > 1 placement (SURVEY 8e-ii): every role on one GPU with everything it can see; the ranks' query
     subsets partition every batch; the predicted load is balanced; the rows a rank holds are exactly what its roles see."""

@@ -15,7 +15,7 @@ sets=(
 i=0
 for s in "${sets[@]}"; do
   i=$((i+1))
-  rocprofv3 --pmc $s --kernel-trace --output-format csv -d "$out/pass$i" -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --sustained-s 0 "$@" > "$out/pass$i.log" 2>&1 || { echo "pass $i failed"; tail -5 "$out/pass$i.log"; }
+  rocprofv3 --pmc $s --kernel-trace --output-format csv -d "$out/pass$i" -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --sustained-s 0 "$@" > "$out/pass$i.log" 2>&1 || { echo "pass $i failed"; tail -5 "$out/pass$i.log"; }
   echo "pass $i done"
 done
 python3 tools/pmc_summary.py "$out/pmc.json" "$out"/pass* > "$out/pmc.txt"

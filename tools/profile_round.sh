@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round profile of the bench command, run on the GPU box in TWO gpurun calls (a call is limited to 20 minutes):
 #   tools/profile_round.sh stats <outdir>   rocprofv3 --kernel-trace --stats of the driver's command (python3 bench.py --gpus 1 --steps 20
-#                                           --warmup 5): per-kernel durations of every leg (SIFT10M, 768-d, hnsw, ivf, builds)
+#                                           --warmup 5 --full): per-kernel durations of every leg (SIFT10M, 768-d, hnsw, ivf, builds)
 #   tools/profile_round.sh pmc <outdir>     SQ / TCC counter passes of the headline leg (tools/pmc_run.sh: one rocprofv3 run per counter
 #                                           set, --kernel-trace only) + traffic.json (HBM bytes per launch, FETCH_SIZE / WRITE_SIZE passes),
 #                                           then the same passes for the 768-d GEMM kernel through tools/kbench.py
@@ -11,7 +11,7 @@ out=$2
 mkdir -p "$out"
 export TMPDIR=/tmp
 if [ "$what" = stats ]; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$out/bench_under_rocprof.json" 2> "$out/stats.log" || { echo "stats pass failed"; tail -5 "$out/stats.log"; }
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$out/bench_under_rocprof.json" 2> "$out/stats.log" || { echo "stats pass failed"; tail -5 "$out/stats.log"; }
   find "$out/stats" -name "*kernel_stats.csv" -exec cp {} "$out/bench_kernel_stats.csv" \;
   find "$out/stats" -name "*.csv" -size +3M -delete
   echo "stats done"

@@ -6,7 +6,7 @@ mkdir -p "$out"
 i=0
 for cfg in "$@"; do
   i=$((i+1))
-  env $cfg python3 bench.py --legs prefilter --steps 10 --warmup 3 --no-cpu-baseline --sustained-s 0 > "$out/cfg$i.json" 2> "$out/cfg$i.err"
+  env $cfg python3 bench.py --full --legs prefilter --steps 10 --warmup 3 --no-cpu-baseline --sustained-s 0 > "$out/cfg$i.json" 2> "$out/cfg$i.err"
   python3 - "$out/cfg$i.json" "$cfg" <<'PY'
 import json, sys
 try:
