@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "vsr_bounds.h"
 
 namespace vsr {
 
@@ -276,11 +277,10 @@ __host__ __device__ inline size_t coarse_row_offset(uint32_t row, uint32_t nks) 
     return ((size_t) (row >> 8) * nks) * COARSE_SLAB_U4 + (size_t) (row & 255u) * 4u;
 }
 inline size_t coarse_plane_u4(uint64_t n_rows, uint32_t cstride4) { return ((n_rows + 255) / 256) * 256 * (size_t) cstride4; }
-// relative error bound of the coarse product xh * qh accumulated in fp32: |dot_s - dot| <= g |x| |q|
-inline float coarse_err_g(int dim) { return 3.9138794e-3f + (float) (dim + 64) * 5.9604645e-8f; }     // 2^-8 (1 + 2^-9) + ...
+// relative error bound of the coarse product xh * qh accumulated in fp32: coarse_err_g (vsr_bounds.h)
 hipError_t launch_gemm(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s);
 hipError_t launch_split_coarse(const float4* rows, uint32_t n_rows, uint32_t stride4, uint4* scr_c, uint32_t cstride4, hipStream_t s);
-// Screening planes: element x = hi + mid + e with hi = bf16(x), mid = bf16(x - hi) (|e| <= 2^-18 |x|).  A plane row holds,
+// Screening planes: element x = hi + mid + e with hi = bf16(x), mid = bf16(x - hi) (|e| <= 2^-17 |x|).  A plane row holds,
 // for every 64-float stage s, 8 chunks of 8 hi values followed by 8 chunks of 8 mid values (16 bytes each, zero padded):
 // the same 256 bytes per row and stage as the fp32 image, but ready for v_mfma_f32_16x16x32_bf16 (16x the fp32 rate).
 // Hi-only layout (ho, every element exactly a bf16 value): 16 hi chunks per 128-float stage, half the bytes.  Query
@@ -289,8 +289,7 @@ inline uint32_t plane_stride4(int dim, bool ho) { return 16u * (uint32_t) (ho ? 
 hipError_t launch_check_bf16_exact(const float4* rows, uint32_t n_rows, uint32_t stride4, uint32_t* any_inexact, hipStream_t s);
 hipError_t launch_split_planes(const float4* rows, uint32_t n_rows, uint32_t stride4, uint4* scr, uint32_t pstride4, bool ho,
                                hipStream_t s);
-// relative error bound of the plane product  xh*qh + xh*qm + xm*qh  accumulated in fp32 over `dim` elements
-inline float plane_err_g(int dim) { return 3.0f * 3.8146973e-6f + (float) (3 * dim + 8) * 5.9604645e-8f; }
+// relative error bound of the plane product  xh*qh + xh*qm + xm*qh  accumulated in fp32: plane_err_g (vsr_bounds.h)
 hipError_t launch_rerank(const RerankParams& p, uint32_t n_queries, hipStream_t s);
 hipError_t launch_select_rerank(const RerankParams& p, uint32_t n_queries, hipStream_t s);
 // threshold seeds of K2w: per query the m-th smallest of its sampled keys (low word all ones), KEY_EMPTY if fewer;

@@ -16,8 +16,9 @@
 //     256 consecutive rows contribute to one K-step are one contiguous 16 KB slab, so an unfiltered tile streams whole
 //     slabs (row-major planes made every K-step a 64-byte-per-1536-byte column walk over HBM: measured 2.5 TB/s);
 //   * ONE product per element: the COARSE screening planes hold only hi = bf16(x) (vsr_corpus::d_scr_c), so a dot
-//     product is x.q ~ xh.qh with |error| <= g |x||q|, g = 2^-8 (1 + 2^-9) + (d + 64) 2^-24 (bf16 rounds to nearest:
-//     2^-9 relative per operand; fp32 accumulation).  That is 1/3 of K2w's products and 1/2 of its bytes.  The
+//     product is x.q ~ xh.qh with |error| <= g |x||q|, g = 2^-7 (1 + 2^-9) + (d + 64) 2^-24 (1 + 2^-5) (bf16 rounds to
+//     nearest: 2^-8 relative per operand; fp32 accumulation; coarse_err_g, vsr_bounds.h).  That is 1/3 of K2w's products
+//     and 1/2 of its bytes.  The
 //     screening only decides which kp candidates per query survive; select_rerank_kernel recomputes vector.c's exact
 //     arithmetic for them and FLAGS a query unless the kept / dropped gap exceeds the bound, exactly as for K2w -- a
 //     coarser screen needs a larger kp (the planner takes 4k) and flags sooner; a flagged query is re-run on the fine

@@ -11,7 +11,7 @@
 // so narrow passes (a leaf class seen by 10 queries) still use all four waves.
 //
 // Arithmetic: the tile is not the fp32 rows but their SCREENING PLANES (vsr_device.h, plane_stride4): every element
-// x = hi + mid (+ e, |e| <= 2^-18 |x|) as two bf16 values, so the dot products run on v_mfma_f32_16x16x32_bf16 at 16x
+// x = hi + mid (+ e, |e| <= 2^-17 |x|) as two bf16 values, so the dot products run on v_mfma_f32_16x16x32_bf16 at 16x
 // the fp32 MFMA rate:  x q ~ xh qh + xh qm + xm qh  (fp32 accumulation).  The result only SCREENS: it decides which
 // kp = 2k candidates per query survive; K5r recomputes the exact vector.c arithmetic for them from the fp32 rows and
 // flags a query whose kept / dropped gap is inside the screening's error bound (plane_err_g).  A corpus whose elements

@@ -2406,7 +2406,7 @@ static int search_impl(vsr_ctx* ctx, vsr_corpus* c, const float* h_queries, cons
         rr.out_dist = d_dist;
         rr.out_keys = d_keys;
         rr.out_count = d_cnt;
-        rr.err_g = (float) (c->dim + 8) * 5.9604645e-8f;    // K2's fp32 MFMA chain: (d + 8) * 2^-24
+        rr.err_g = k2_err_g(c->dim);                       // K2's fp32 MFMA chain (vsr_bounds.h)
         rr.seeded = seed ? 1 : 0;
         rr.tau_init = seed ? ctx->d_tau.as<uint64_t>() : nullptr;
         rr.out_flags = ctx->d_flags.as<int32_t>();
