@@ -233,7 +233,8 @@ int vsr_ivf_search_device(vsr_ivf* ivf, const float* d_queries, int nq, int dim,
  * addressed through up_slot[n_elem]).  vsr_hnsw_search = hnswgettuple's first call + the executor's filter and LIMIT:
  * greedy descent (ef = 1) from `entry`, HnswSearchLayer with ef_search on layer 0, then the TIDs of the result elements
  * nearest first, the permission test per row and the first k.  Equal distances are ordered by element id.  Like the
- * reference with hnsw.iterative_scan = off, a filtered query can return fewer than k rows.
+ * reference with hnsw.iterative_scan = off, a filtered query can return fewer than k rows (vsr_hnsw_search_iterative below
+ * runs pgvector's iterative scans).
  * out_visited (may be NULL): elements entered into the visited set by the layer-0 search, per query. */
 typedef struct vsr_hnsw vsr_hnsw;
 int vsr_hnsw_load(vsr_corpus* corpus, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
@@ -266,6 +267,41 @@ int vsr_hnsw_search_device(vsr_hnsw* index, const float* d_queries, int nq, int 
                            const vsr_filter* const* filters,
                            int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
                            int32_t* d_out_counts, int64_t* d_out_visited);
+
+/* Iterative index scans: hnsw.iterative_scan = relaxed_order | strict_order with hnsw.max_scan_tuples (hnswscan.c:47-76,
+ * 227-312; hnswutils.c:813-976; GUCs hnsw.c:21-31,90-102), i.e. hnswgettuple called until the executor's LIMIT is met.
+ * Per query: a visited set V that lasts the whole scan, a discarded set D ordered by (index distance, element id), a
+ * counter T (so->tuples) and P = -inf (so->previousDistance).
+ *   1. Round 0 is vsr_hnsw_search's walk.  T counts the layer-0 entry point plus the unvisited neighbours of every
+ *      expansion (= out_visited).  D receives every neighbour that fails admission and every element pushed out of W.
+ *   2. Emission: W nearest first, each element's heap TIDs newest first.  strict_order drops a TID whose element's index
+ *      distance is below P, else P takes that distance.  A TID the query's filter admits is a result; k results stop it.
+ *   3. W exhausted: if T >= max_scan_tuples, D's smallest element is the next W alone (stop when D is empty); otherwise
+ *      stop when D is empty, else the min(ef_search, |D|) smallest elements leave D and are the entry points of another
+ *      layer-0 search with ef_search (not marked or counted again; T grows by the unvisited neighbours of expansions, both
+ *      kinds of discard go to D again), whose W is the next batch.
+ *   4. Not modelled: pgvector's memory stop (work_mem x hnsw.scan_mem_multiplier): only max_scan_tuples ends the search.
+ * Rows come back in stream order, not re-sorted (relaxed_order can be out of order, as in pgvector).  The stream depends
+ * on neither k nor the filter, which only decide where it stops: the answer for k1 is a prefix of the answer for k2 > k1.
+ * mode VSR_HNSW_ITERATIVE_OFF is vsr_hnsw_search bit for bit (out_tuples = out_visited).  max_scan_tuples: 1 .. INT_MAX;
+ * anything else, or an unknown mode: VSR_ERR_INVALID.  A mode other than off on a predicate-aware index:
+ * VSR_ERR_UNSUPPORTED.  out_tuples (may be NULL): T when the query's scan stopped.  D lives in device memory with room
+ * for max_scan_tuples plus one round; a query that outgrows it is re-run by the host entry point with room for every
+ * element.  The _device variant (device pointers, one launch per chunk of queries on the corpus context's stream, no
+ * synchronisation) reports such a query with count -1 instead. */
+typedef enum {
+    VSR_HNSW_ITERATIVE_OFF = 0,
+    VSR_HNSW_ITERATIVE_RELAXED = 1,
+    VSR_HNSW_ITERATIVE_STRICT = 2
+} vsr_hnsw_iterative;
+int vsr_hnsw_search_iterative(vsr_hnsw* index, const float* queries, int nq, int dim, int k, int ef_search, int metric,
+                              const vsr_filter* const* filters, int mode, int64_t max_scan_tuples,
+                              int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows, float* out_dist,
+                              int32_t* out_counts, int64_t* out_tuples);
+int vsr_hnsw_search_iterative_device(vsr_hnsw* index, const float* d_queries, int nq, int dim, int k, int ef_search, int metric,
+                                     const vsr_filter* const* filters, int mode, int64_t max_scan_tuples,
+                                     int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
+                                     int32_t* d_out_counts, int64_t* d_out_tuples);
 
 /* opclass support functions for n vectors at once (host pointers): vector_norm (vector.c:756-769), l2_normalize
  * (vector.c:774-808; fails with "value out of range: overflow" like float_overflow_error) and

@@ -5,7 +5,8 @@
  * (GetScanItems, :15-45, :206-218) and every call hands out one heap TID in distance order (:278-311) with
  * xs_recheck = xs_recheckorderby = false.  The search itself is libvsrbac's exact filtered k-NN over the resident
  * corpus instead of HnswSearchLayer over index pages; hnsw.ef_search keeps its meaning as the number of candidates the
- * scan can return (:44).  With hnsw.iterative_scan (:227-276) a scan that runs dry asks for twice as many.
+ * scan can return (:44).  With hnsw.iterative_scan (:227-276) the in-process index-faithful scan is pgvector's iterative
+ * scan (vsr_hnsw_search_iterative); elsewhere a scan that runs dry asks for twice as many.
  */
 #include "vsr_pg.h"
 
@@ -33,6 +34,7 @@ hnswrescan(IndexScanDesc scan, ScanKey keys, int nkeys, ScanKey orderbys, int no
 
 	so->first = true;
 	so->nresults = so->next = 0;
+	so->iter_k = 0;
 	MemoryContextReset(so->tmpCtx);	/* :166 */
 	if (keys && scan->numberOfKeys > 0)
 		memmove(scan->keyData, keys, scan->numberOfKeys * sizeof(ScanKeyData));
@@ -52,15 +54,40 @@ hnswgettuple(IndexScanDesc scan, ScanDirection dir)
 			elog(ERROR, "non-MVCC snapshots are not supported with hnsw");	/* :203-204 */
 		/* the share lock pgvector takes around its page walk (:213-218) keeps vacuum's ordering with scans */
 		LockPage(scan->indexRelation, HNSW_SCAN_LOCK, ShareLock);
-		if (vsr_pg_index_faithful)
-			VsrRunIndexSearch(scan, so, true, hnsw_ef_search);	/* HnswSearchLayer over pgvector's own graph, on the GPU */
-		else
-			VsrRunSearch(scan, so, hnsw_ef_search);
+		so->iter_k = 0;
+		/* pgvector's iterative scan asks first for the ef_search rows its first batch can hold at most */
+		if (!(vsr_pg_index_faithful && hnsw_iterative_scan != HNSW_ITERATIVE_SCAN_OFF &&
+			  VsrRunHnswIterative(scan, so, Min(hnsw_ef_search, VSR_MAX_K))))
+		{
+			if (vsr_pg_index_faithful)
+				VsrRunIndexSearch(scan, so, true, hnsw_ef_search);	/* HnswSearchLayer over pgvector's own graph, on the GPU */
+			else
+				VsrRunSearch(scan, so, hnsw_ef_search);
+		}
 		UnlockPage(scan->indexRelation, HNSW_SCAN_LOCK, ShareLock);
 		so->first = false;
 	}
 	if (VsrNextTuple(scan, so))
 		return true;
+	if (so->iter_k > 0)
+	{
+		/*
+		 * vsr_hnsw_search_iterative's stream depends on neither k nor the filter: the first 2k rows begin with the k
+		 * handed out, so asking again for twice as many and skipping those is exact.  Fewer rows than asked: the
+		 * stream ended (hnsw.max_scan_tuples reached and the discarded candidates drained, or the graph exhausted).
+		 * One result list holds at most VSR_MAX_K rows: the scan ends there.
+		 */
+		int			had = so->nresults;
+
+		if (had < so->iter_k || so->iter_k >= VSR_MAX_K)
+			return false;
+		MemoryContextReset(so->tmpCtx);
+		LockPage(scan->indexRelation, HNSW_SCAN_LOCK, ShareLock);
+		(void) VsrRunHnswIterative(scan, so, Min(2 * so->iter_k, VSR_MAX_K));
+		UnlockPage(scan->indexRelation, HNSW_SCAN_LOCK, ShareLock);
+		so->next = Min(had, so->nresults);
+		return VsrNextTuple(scan, so);
+	}
 	if (hnsw_iterative_scan != HNSW_ITERATIVE_SCAN_OFF && so->nresults > 0 && so->nresults < VSR_MAX_K)
 	{
 		/*

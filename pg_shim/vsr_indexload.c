@@ -10,6 +10,9 @@
  *   ivfflat  the list pages (ivfflat.h:222-248: centre + start page per list) and the TIDs of every list's entry pages
  *            -> centres + row -> list map -> vsr_ivf_load; the scan is vsr_ivf_search
  *
+ * With hnsw.iterative_scan = relaxed_order | strict_order the in-process hnsw scan is pgvector's iterative scan,
+ * vsr_hnsw_search_iterative (VsrRunHnswIterative below).
+ *
  * Like the rest of pg_shim/ this file is written against postgres.h + pgvector's headers and is NOT compiled in the
  * authoring image.  The arrays it builds are exactly what tests/test_gpu_index.py feeds the same entry points from the
  * CPU restatement of pgvector's build (oracle/vsr_index_oracle.c).
@@ -414,4 +417,53 @@ emit:
 	so->nresults = count;
 	so->next = 0;
 	MemoryContextSwitchTo(old);
+}
+
+/*
+ * hnsw.iterative_scan != off on the in-process index-faithful path: the first k rows of the query's stream under
+ * vsr_hnsw_search_iterative (hnswscan.c:227-312 with hnsw.max_scan_tuples; pgvector's memory stop,
+ * hnsw.scan_mem_multiplier, is not modelled).  The stream depends on neither k nor the filter, so a caller that needs
+ * more rows asks again with a larger k and skips what it handed out: the answer for k is a prefix of the answer for 2k.
+ * false: not this path (the sidecar, the predicate-aware walk, an empty index); the caller keeps its ordinary search.
+ */
+bool
+VsrRunHnswIterative(IndexScanDesc scan, VsrPgScanOpaque so, int k)
+{
+	VsrPgCorpus *pc = so->pc;
+	MemoryContext old;
+	Vector	   *q;
+	const vsr_filter *filter;
+	int64	   *blk,
+			   *rowidx;
+	float	   *dist;
+	int32		count = 0;
+	int			mode = hnsw_iterative_scan == HNSW_ITERATIVE_SCAN_STRICT ? VSR_HNSW_ITERATIVE_STRICT : VSR_HNSW_ITERATIVE_RELAXED;
+
+	if (pc->sc_handle != 0 || vsr_pg_predicate_aware)
+		return false;
+	if (scan->orderByData == NULL)
+		elog(ERROR, "cannot scan hnsw index without order");
+	if (pc->graph == NULL)
+		pc->graph = VsrLoadHnswGraph(scan->indexRelation, pc);
+	if (pc->graph == NULL)
+		return false;
+	VsrCheck(vsr_hnsw_set_predicate_aware(pc->graph, 0));
+	old = MemoryContextSwitchTo(so->tmpCtx);
+	q = DatumGetVector(scan->orderByData->sk_argument);
+	filter = VsrFilterForCurrentUser(pc);
+	k = Max(1, Min(k, VSR_MAX_K));
+	blk = palloc(sizeof(int64) * k);
+	rowidx = palloc(sizeof(int64) * k);
+	dist = palloc(sizeof(float) * k);
+	VsrCheck(vsr_hnsw_search_iterative(pc->graph, q->x, 1, q->dim, k, hnsw_ef_search, VsrMetricOf(scan->indexRelation),
+									   filter ? &filter : NULL, mode, hnsw_max_scan_tuples, blk, NULL, rowidx, dist, &count,
+									   NULL));
+	so->result_tids = palloc(sizeof(ItemPointerData) * Max(count, 1));
+	for (int i = 0; i < count; i++)
+		so->result_tids[i] = pc->tids[rowidx[i]];
+	so->nresults = count;
+	so->next = 0;
+	so->iter_k = k;
+	MemoryContextSwitchTo(old);
+	return true;
 }

@@ -77,6 +77,7 @@ typedef struct VsrPgScanOpaqueData
 	int			nresults;
 	int			next;
 	int			probes_used;		/* ivfflat iterative scan: lists probed so far */
+	int			iter_k;			/* hnsw iterative scan through vsr_hnsw_search_iterative: rows asked for (0: not that path) */
 	ItemPointerData *result_tids;
 	MemoryContext tmpCtx;
 }			VsrPgScanOpaqueData;
@@ -98,5 +99,6 @@ extern bool VsrNextTuple(IndexScanDesc scan, VsrPgScanOpaque so);
 extern vsr_hnsw *VsrLoadHnswGraph(Relation index, VsrPgCorpus * pc);	/* index pages -> vsr_hnsw_load */
 extern vsr_ivf *VsrLoadIvfLists(Relation index, VsrPgCorpus * pc);	/* list pages -> vsr_ivf_load */
 extern void VsrRunIndexSearch(IndexScanDesc scan, VsrPgScanOpaque so, bool is_hnsw, int ef_or_probes);
+extern bool VsrRunHnswIterative(IndexScanDesc scan, VsrPgScanOpaque so, int k);	/* pgvector's iterative scan, first k rows */
 
 #endif							/* VSR_PG_H */

@@ -28,6 +28,28 @@
 // W and C hold permitted elements only; expanding c takes c's unvisited neighbours that are permitted, and for every
 // unvisited neighbour that is NOT permitted its permitted unvisited neighbours (two hops), in list order, up to HN_NBR
 // candidates per expansion.  The descent through the upper layers and the entry point are unfiltered.
+//
+// Iterative index scans (hnsw_iterative_kernel: hnsw.iterative_scan = relaxed_order / strict_order, hnsw.max_scan_tuples;
+// hnswscan.c:47-76,227-312, hnswutils.c:813-976 with a `discarded` heap).  Per query a visited set V that lasts the whole
+// scan, a discarded set D (keys as above), a counter T (so->tuples) and P = -inf (so->previousDistance):
+//   round 0   the search above.  T = the layer-0 entry point + the unvisited neighbours of every expansion (= out_visited).
+//             D receives every neighbour that fails admission and every element pushed out of W: S's entries at positions
+//             >= ef at the end of the round and every key insert() pushes off the end of S.
+//   emission  W nearest first, each element's TIDs newest first; strict_order drops a TID whose element is nearer than P,
+//             else P = its distance; a TID the query's filter admits is a result; the scan stops at k results.
+//   W empty   T >= max_scan_tuples: D's smallest key is the next W alone (the drain; taken here 64 keys at a time, in
+//             order: the same stream), stop when D is empty.  Otherwise stop when D is empty, else the min(ef, |D|)
+//             smallest keys leave D and are the entry points of another layer-0 search with ef (ResumeScanItems: entry
+//             points are neither marked nor counted again, T grows by the unvisited neighbours of expansions, both kinds
+//             of discard go to D again); its W is the next batch.
+// Not modelled: the memory stop (work_mem x hnsw.scan_mem_multiplier, hnswscan.c:244): only max_scan_tuples ends the
+// search phase.  Rows come back in stream order, not re-sorted (relaxed_order may be out of order, as in pgvector); the
+// stream depends on neither k nor the filter, so the answer for k1 is a prefix of the answer for k2 > k1.
+// D is one append buffer of keys per query in global memory (cap_d keys; a query that would overflow it reports status 1
+// and is re-run by the host entry point with cap_d = n_elem, which cannot overflow: an element is in at most one of D, W
+// and "already emitted").  Taking keys out of D: an MSB-first radix select of the threshold key over D (histogram in the
+// wave's LDS), a pass that moves the selected keys into S and compacts D in place, a bitonic sort of S.  The visited set
+// is the LDS bitmap when it fits and the global bitmap otherwise (the LDS hash is sized by ef, not by the scan).
 #pragma once
 #include "vsr_device.h"
 #include "vsr_topk.h"
@@ -65,6 +87,11 @@ struct HnswParams {
     int64_t*        out_visited = nullptr;   // optional [nq]: elements entered into the visited set on layer 0
     int32_t*        out_status = nullptr;    // optional [nq]: 0 = ok, 1 = the LDS hash overflowed (result not valid: re-run with VIS_GLOBAL)
     uint32_t*       err = nullptr;
+    // hnsw_iterative_kernel only (out_visited then reports T when the scan stopped; status 1 = D overflowed)
+    int             iter_mode = 0;           // VSR_HNSW_ITERATIVE_RELAXED = 1 / STRICT = 2
+    int64_t         max_scan = 0;            // hnsw.max_scan_tuples
+    uint64_t*       disc = nullptr;          // D: [nq][cap_d] keys
+    uint32_t        cap_d = 0;
 };
 
 constexpr int HN_UPPER_VISITED = 1024;     // visited list of an upper-layer (ef = 1) search, in LDS
@@ -78,7 +105,17 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_wave_barrier();
 }
 
-__global__ __launch_bounds__(256) void hnsw_search_kernel(const HnswParams p)
+constexpr int HN_HIST = 256;               // radix-select histogram of the iterative kernel (8-bit digits), in LDS
+
+// global-memory stores of the wave (D) visible to its later loads, and LDS as wave_sync
+__device__ __forceinline__ void wave_sync_global()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+template <bool ITER>
+__device__ __forceinline__ void hnsw_search_body(const HnswParams p)
 {
     extern __shared__ __align__(16) unsigned char smem_all[];
     const int lane = threadIdx.x & 63;
@@ -92,6 +129,11 @@ __global__ __launch_bounds__(256) void hnsw_search_kernel(const HnswParams p)
     float*    nd = reinterpret_cast<float*>(nb + HN_NBR);                    // [HN_NBR] their distances
     int32_t*  uv = reinterpret_cast<int32_t*>(nd + HN_NBR);                  // [HN_UPPER_VISITED] upper-layer visited list
     uint32_t* lv = reinterpret_cast<uint32_t*>(uv + HN_UPPER_VISITED);       // layer-0 visited set: bitmap words or hash slots
+    uint32_t* hist = nullptr;                                                // ITER: [HN_HIST] radix-select histogram
+    if constexpr (ITER) {
+        hist = lv;
+        lv += HN_HIST;
+    }
     const float* q = p.queries + (size_t) qi * p.q_stride;
     uint32_t* gvis = p.vis_mode == VIS_GLOBAL ? p.visited + (size_t) qi * p.vis_words : nullptr;
     const int half = lane >> 5, hl = lane & 31;
@@ -179,8 +221,10 @@ __global__ __launch_bounds__(256) void hnsw_search_kernel(const HnswParams p)
     uint32_t count = 0;                      // entries of S
     uint32_t pushed = 0;                     // wlen of the reference: pushes so far (never decremented)
     uint32_t first_open = 0;                 // every entry before this position is expanded
-    // insert (key, unexpanded) into S keeping it sorted; beyond caps the largest entry falls off
-    auto insert = [&](uint64_t key) {
+    // insert (key, unexpanded) into S keeping it sorted; beyond caps the largest entry falls off (ITER: returned, else
+    // KEY_EMPTY)
+    auto insert = [&](uint64_t key) -> uint64_t {
+        uint64_t dropped = KEY_EMPTY;
         // position = number of keys < key.  A binary search is a chain of log2(count) dependent LDS reads (eleven at ef_search
         // in the thousands: over a microsecond per insert); the wave does a 64-ary search instead: lane l compares the LAST key of
         // segment l (count / 64 keys, rounded up), the segments entirely below the key are a prefix, and the one segment that is
@@ -201,7 +245,12 @@ __global__ __launch_bounds__(256) void hnsw_search_kernel(const HnswParams p)
                 pos += (uint32_t) __popcll(__ballot(i < b1 && S[i] < key));
             }
         }
-        if (pos >= p.caps) return;
+        if (pos >= p.caps) {
+            if constexpr (ITER) dropped = key;
+            return dropped;
+        }
+        if constexpr (ITER)
+            if (count == p.caps) dropped = S[p.caps - 1];
         const uint32_t last = count < p.caps ? count : p.caps - 1;      // index the shifted tail ends at
         // the tail [pos, last) moves up by one, 256 entries per step from the end (four per lane: a step is two wave barriers
         // whatever it moves, and at ef_search in the thousands the tail is a thousand entries long)
@@ -228,18 +277,35 @@ __global__ __launch_bounds__(256) void hnsw_search_kernel(const HnswParams p)
         if (count < p.caps) ++count;
         if (pos < first_open) first_open = pos;
         wave_sync();
+        return dropped;
+    };
+
+    // ITER: D, the discarded keys of this query (global memory), n_disc of them
+    uint64_t* Dq = nullptr;
+    uint32_t n_disc = 0;
+    if constexpr (ITER) Dq = p.disc + (size_t) qi * p.cap_d;
+    // append the keys of the lanes with `pass` (one ballot-compacted write); beyond cap_d: overflow, nothing written
+    auto disc_append = [&](bool pass, uint64_t key) {
+        const uint64_t m = __ballot(pass);
+        const uint32_t add = (uint32_t) __popcll(m);
+        if (n_disc + add > p.cap_d) { overflow = true; return; }
+        if (pass) Dq[n_disc + (uint32_t) __popcll(m & ((1ull << lane) - 1ull))] = key;
+        n_disc += add;
     };
 
     int64_t visited_l0 = 0;
-    // Algorithm 2 on layer lc with beam ef_; S holds the entry points (unexpanded) on entry and W (sorted) on exit
-    auto search_layer = [&](int lc, uint32_t ef_) {
+    // Algorithm 2 on layer lc with beam ef_; S holds the entry points (unexpanded) on entry and W (sorted) on exit.
+    // mark_entries = false (ITER resume rounds): the entry points come from D, already visited and counted
+    auto search_layer = [&](int lc, uint32_t ef_, bool mark_entries) {
         const uint32_t lm = lc == 0 ? 2 * p.m : p.m;
         uint32_t n_uv = 0;
         // entry points count as visited
         if (lc == 0) {
-            for (uint32_t i = (uint32_t) lane; i < count; i += 64) (void) visit((uint32_t) S[i]);
-            visited_l0 += count;
-            hash_used += count;
+            if (!ITER || mark_entries) {
+                for (uint32_t i = (uint32_t) lane; i < count; i += 64) (void) visit((uint32_t) S[i]);
+                visited_l0 += count;
+                hash_used += count;
+            }
         } else {                             // (one entry point per upper layer)
             if (lane == 0) uv[0] = (int32_t) (uint32_t) S[0];
             n_uv = 1;
@@ -342,6 +408,7 @@ __global__ __launch_bounds__(256) void hnsw_search_kernel(const HnswParams p)
             }
             if (cnt == 0) continue;
             distances(cnt);
+            uint32_t admitted = 0;                   // ITER: bit i >> 6 of lane i & 63 = neighbour i entered W
             for (int i = 0; i < cnt; ++i) {                                  // the sequential admission of Algorithm 2
                 const uint32_t e = (uint32_t) nb[i];
                 const float ed = nd[i];
@@ -350,11 +417,32 @@ __global__ __launch_bounds__(256) void hnsw_search_kernel(const HnswParams p)
                 const float fd = mono_to_float((uint32_t) (S[(wl2 < count ? wl2 : count) - 1] >> 32));
                 if (!(ed < fd || always)) continue;
                 if (lc != 0 && p.level[e] < lc) continue;                    // (every element lives on layer 0)
-                insert(make_key(ed, e));
+                const uint64_t fell = insert(make_key(ed, e));
                 ++pushed;
+                if constexpr (ITER) {
+                    if (lane == (i & 63)) admitted |= 1u << (i >> 6);
+                    if (lc == 0 && fell != KEY_EMPTY) disc_append(lane == 0, fell);     // pushed out of W (and S)
+                }
+            }
+            if constexpr (ITER) {
+                if (lc == 0) {                                               // the neighbours admission rejected
+                    for (int c0 = 0; c0 < cnt; c0 += 64) {
+                        const int i = c0 + lane;
+                        const bool rej = i < cnt && !((admitted >> (c0 >> 6)) & 1u);
+                        disc_append(rej, rej ? make_key(nd[i], (uint32_t) nb[i]) : 0ull);
+                    }
+                    if (overflow) break;
+                }
             }
         }
         const uint32_t wl = pushed < ef_ ? pushed : ef_;
+        if constexpr (ITER) {
+            if (lc == 0 && !overflow)                                        // pushed out of W, still in S
+                for (uint32_t b = wl; b < count; b += 64) {
+                    const uint32_t i = b + (uint32_t) lane;
+                    disc_append(i < count, i < count ? S[i] : 0ull);
+                }
+        }
         count = wl < count ? wl : count;                                     // S = W, nearest first
     };
 
@@ -369,6 +457,8 @@ __global__ __launch_bounds__(256) void hnsw_search_kernel(const HnswParams p)
     if (p.out_status && lane == 0) p.out_status[qi] = 0;
     if (p.entry < 0) {
         if (lane == 0) p.out_count[qi] = 0;
+        if constexpr (ITER)
+            if (p.out_visited && lane == 0) p.out_visited[qi] = 0;
         write_empty(0);
         return;
     }
@@ -378,35 +468,53 @@ __global__ __launch_bounds__(256) void hnsw_search_kernel(const HnswParams p)
     distances(1);
     insert(make_key(nd[0], (uint32_t) p.entry));
     for (int lc = p.entry_level; lc >= 1; --lc) {
-        search_layer(lc, 1);
+        search_layer(lc, 1, true);
         if (lane == 0)
             for (uint32_t i = 0; i < count; ++i) X[i] = 0;                    // W becomes the next layer's entry points
         wave_sync();
     }
-    search_layer(0, p.ef);
-    if (p.out_visited && lane == 0) p.out_visited[qi] = visited_l0;
-    if (overflow) {                                                          // the visited table filled up: no result
+    search_layer(0, p.ef, true);
+    if constexpr (!ITER)
+        if (p.out_visited && lane == 0) p.out_visited[qi] = visited_l0;
+    auto fail_query = [&]() {                                                // status 1: no result
         if (lane == 0) {
             p.out_count[qi] = -1;
             if (p.out_status) p.out_status[qi] = 1;
         }
         write_empty(0);
+    };
+    if (overflow) {                                                          // the visited table filled up (ITER: D did)
+        if constexpr (ITER)
+            if (p.out_visited && lane == 0) p.out_visited[qi] = visited_l0;
+        fail_query();
         return;
     }
 
     // hnswgettuple: elements nearest first, their heap TIDs newest first, the permission bit, the first k
     uint32_t out = 0;
-    for (uint32_t base = 0; base < count && out < p.k; base += 64) {
+    float prev_d = -__builtin_inff();        // ITER strict_order: so->previousDistance (index distance)
+    // emit S[0, n) after what is out already
+    auto emit = [&](uint32_t n) {
+    for (uint32_t base = 0; base < n && out < p.k; base += 64) {
         const uint32_t i = base + (uint32_t) lane;
         uint32_t e = 0, nt = 0, okmask = 0;
         float d = 0.0f;
-        if (i < count) {
+        if (i < n) {
             e = (uint32_t) S[i];
             d = mono_to_float((uint32_t) (S[i] >> 32));
             nt = (uint32_t) p.tid_count[e];
+            if constexpr (ITER)
+                if (p.iter_mode == 2 && d < prev_d) nt = 0;                  // strict_order: nearer than the last one out
             for (uint32_t t = 0; t < nt; ++t) {                              // bit t: TID nt-1-t (newest first) is permitted
                 const uint32_t row = (uint32_t) p.tids[(size_t) e * 10 + (nt - 1 - t)];
                 if (!bm || ((bm[row >> 6] >> (row & 63)) & 1ull)) okmask |= 1u << t;
+            }
+        }
+        if constexpr (ITER) {
+            if (p.iter_mode == 2) {              // S is sorted: what passes is a suffix of the chunk, the last one sets P
+                float mx = nt > 0 ? d : -__builtin_inff();
+                for (int dd = 32; dd >= 1; dd >>= 1) mx = fmaxf(mx, __shfl_xor(mx, dd));
+                prev_d = fmaxf(prev_d, mx);
             }
         }
         uint32_t mine = (uint32_t) __popc(okmask), incl = mine;
@@ -437,10 +545,122 @@ __global__ __launch_bounds__(256) void hnsw_search_kernel(const HnswParams p)
             }
         out += (uint32_t) __shfl((int) incl, 63);
     }
+    };
+    emit(count);
+
+    if constexpr (ITER) {
+        // radix select: the key t such that exactly `want` (< n_disc) keys of D are <= t (keys are distinct)
+        auto threshold = [&](uint32_t want) -> uint64_t {
+            uint64_t prefix = 0, pmask = 0;
+            uint32_t need = want;
+            for (int shift = 56; shift >= 0; shift -= 8) {
+                for (uint32_t b = (uint32_t) lane; b < (uint32_t) HN_HIST; b += 64) hist[b] = 0u;
+                wave_sync();
+                for (uint32_t i = (uint32_t) lane; i < n_disc; i += 64) {
+                    const uint64_t key = Dq[i];
+                    if ((key & pmask) == prefix) atomicAdd(&hist[(uint32_t) (key >> shift) & 255u], 1u);
+                }
+                wave_sync();
+                uint32_t h[4], sum = 0;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { h[u] = hist[4 * lane + u]; sum += h[u]; }
+                uint32_t incl = sum;
+                for (int dd = 1; dd < 64; dd <<= 1) {
+                    const uint32_t o = (uint32_t) __shfl_up((int) incl, dd);
+                    if (lane >= dd) incl += o;
+                }
+                const uint32_t excl = incl - sum;
+                const int owner = __ffsll((unsigned long long) __ballot(excl < need && incl >= need)) - 1;
+                uint32_t below = excl, bin = 0, in_bin = 0;
+                bool found = false;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (!found && below + h[u] >= need) { found = true; bin = 4u * (uint32_t) lane + (uint32_t) u; in_bin = h[u]; }
+                    else if (!found) below += h[u];
+                }
+                bin = (uint32_t) __shfl((int) bin, owner);
+                in_bin = (uint32_t) __shfl((int) in_bin, owner);
+                below = (uint32_t) __shfl((int) below, owner);
+                prefix |= (uint64_t) bin << shift;
+                pmask |= 255ull << shift;
+                need -= below;
+                wave_sync();                                                 // (hist is cleared again below)
+                if (in_bin == need) break;                                   // the whole bin is taken
+            }
+            return prefix | ~pmask;
+        };
+        // the `want` smallest keys of D leave it and become S, sorted, unexpanded
+        auto take = [&](uint32_t want) {
+            wave_sync_global();
+            const uint64_t t = want < n_disc ? threshold(want) : KEY_EMPTY;
+            uint32_t kept = 0, sel = 0;
+            for (uint32_t base = 0; base < n_disc; base += 64) {             // (writes never pass the reads: in place)
+                const uint32_t i = base + (uint32_t) lane;
+                const uint64_t key = i < n_disc ? Dq[i] : KEY_EMPTY;
+                const bool s = i < n_disc && key <= t, kp = i < n_disc && key > t;
+                const uint64_t sm = __ballot(s), km = __ballot(kp);
+                const uint64_t below_me = (1ull << lane) - 1ull;
+                if (s) S[sel + (uint32_t) __popcll(sm & below_me)] = key;
+                if (kp) Dq[kept + (uint32_t) __popcll(km & below_me)] = key;
+                sel += (uint32_t) __popcll(sm);
+                kept += (uint32_t) __popcll(km);
+            }
+            n_disc = kept;
+            count = sel;
+            wave_sync_global();
+            // bitonic sort of S[0, count): positions >= count act as +inf and are never touched
+            uint32_t n2 = 1, lg = 0;
+            while (n2 < count) { n2 <<= 1; ++lg; }
+            for (uint32_t ls = 1; ls <= lg; ++ls) {
+                const uint32_t size = 1u << ls, half = size >> 1;
+                for (uint32_t tt = (uint32_t) lane; tt < n2 / 2; tt += 64) {  // flip: i against its mirror in the block
+                    const uint32_t i = ((tt >> (ls - 1)) << ls) + (tt & (half - 1)), j = i ^ (size - 1);
+                    if (j < count) {
+                        const uint64_t a = S[i], b = S[j];
+                        if (a > b) { S[i] = b; S[j] = a; }
+                    }
+                }
+                wave_sync();
+                for (uint32_t ld = ls - 1; ld >= 1; --ld) {
+                    const uint32_t stride = 1u << (ld - 1);
+                    for (uint32_t tt = (uint32_t) lane; tt < n2 / 2; tt += 64) {
+                        const uint32_t i = ((tt >> (ld - 1)) << ld) + (tt & (stride - 1)), j = i + stride;
+                        if (j < count) {
+                            const uint64_t a = S[i], b = S[j];
+                            if (a > b) { S[i] = b; S[j] = a; }
+                        }
+                    }
+                    wave_sync();
+                }
+            }
+            for (uint32_t i = (uint32_t) lane; i < count; i += 64) X[i] = 0;
+            wave_sync();
+        };
+        while (out < p.k && n_disc > 0) {
+            if (visited_l0 >= p.max_scan) {                                  // the drain: D in order, 64 keys at a time
+                take(n_disc < 64u ? n_disc : 64u);
+            } else {                                                         // ResumeScanItems
+                take(n_disc < p.ef ? n_disc : p.ef);
+                search_layer(0, p.ef, false);
+                if (overflow) break;
+            }
+            emit(count);
+        }
+        if (p.out_visited && lane == 0) p.out_visited[qi] = visited_l0;
+        if (overflow) {
+            fail_query();
+            return;
+        }
+    }
     if (out > p.k) out = p.k;
     write_empty(out);
     if (lane == 0) p.out_count[qi] = (int32_t) out;
 }
+
+__global__ __launch_bounds__(256) void hnsw_search_kernel(const HnswParams p) { hnsw_search_body<false>(p); }
+
+// pgvector's iterative index scan (see the header comment): every round of a query inside the one launch
+__global__ __launch_bounds__(256) void hnsw_iterative_kernel(const HnswParams p) { hnsw_search_body<true>(p); }
 
 constexpr size_t HN_LDS_BUDGET = 156 * 1024;   // of the CU's 160 KB (dynamic LDS of one workgroup)
 
@@ -485,17 +705,43 @@ inline bool hnsw_plan(HnswParams& p, bool force_global)
     return true;
 }
 
-inline hipError_t launch_hnsw_search(const HnswParams& p, hipStream_t s)
+// the iterative kernel: S and the rest as above plus the radix-select histogram; the layer-0 visited set is the LDS bitmap
+// when it fits and the global bitmap otherwise (force_global: always).  false: ef too large for the LDS
+inline bool hnsw_plan_iterative(HnswParams& p, bool force_global)
+{
+    const size_t fixed = hnsw_lds_fixed(p.caps) + (size_t) HN_HIST * 4;
+    if (fixed > HN_LDS_BUDGET) return false;
+    const size_t bitmap_bytes = (((size_t) p.n_elem + 31) / 32) * 4;
+    const size_t room = HN_LDS_BUDGET - fixed;
+    size_t vis_bytes = 0;
+    p.vis_words = (uint32_t) (bitmap_bytes / 4);
+    if (!force_global && bitmap_bytes <= room && bitmap_bytes <= 128 * 1024) {
+        p.vis_mode = VIS_LDS_BITMAP;
+        vis_bytes = bitmap_bytes;
+    } else
+        p.vis_mode = VIS_GLOBAL;
+    p.lds_per_query = (uint32_t) ((fixed + vis_bytes + 15) & ~(size_t) 15);
+    const size_t fit = HN_LDS_BUDGET / p.lds_per_query;
+    p.qpb = (uint32_t) (fit >= 4 && (size_t) p.lds_per_query * 4 <= 40 * 1024 ? 4 : fit >= 2 && (size_t) p.lds_per_query * 2 <= 40 * 1024 ? 2 : 1);
+    return true;
+}
+
+template <bool ITER>
+inline hipError_t launch_hnsw(const HnswParams& p, hipStream_t s)
 {
     if (p.nq == 0) return hipSuccess;
     const size_t lds = (size_t) p.lds_per_query * p.qpb;
     if (lds > HN_LDS_BUDGET || p.qpb < 1 || p.qpb > 4) return hipErrorInvalidValue;
+    const auto kernel = ITER ? hnsw_iterative_kernel : hnsw_search_kernel;
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_search_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(hnsw_search_kernel, dim3((p.nq + p.qpb - 1) / p.qpb), dim3(64 * p.qpb), lds, s, p);
+    hipLaunchKernelGGL(kernel, dim3((p.nq + p.qpb - 1) / p.qpb), dim3(64 * p.qpb), lds, s, p);
     return hipGetLastError();
 }
+
+inline hipError_t launch_hnsw_search(const HnswParams& p, hipStream_t s) { return launch_hnsw<false>(p, s); }
+inline hipError_t launch_hnsw_iterative(const HnswParams& p, hipStream_t s) { return launch_hnsw<true>(p, s); }
 
 }  // namespace vsr

@@ -6,6 +6,7 @@
 #include "vsr_hnsw_build.h"
 
 #include <algorithm>
+#include <climits>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -3082,7 +3083,7 @@ struct vsr_hnsw {
     int32_t *d_elem_row = nullptr, *d_level = nullptr, *d_nbr0 = nullptr, *d_up_slot = nullptr, *d_up_nbr = nullptr,
             *d_tid_count = nullptr, *d_tids = nullptr;
     std::map<uint64_t, uint64_t*> bitmaps;           // filters (by vsr_filter::id) without a full bitmap of their own, as one
-    DevBuf d_q, d_vis, d_out, d_bm;
+    DevBuf d_q, d_vis, d_out, d_bm, d_disc;
     PinBuf h_out, h_bm;
     int last_mode = -1;                              // visited form of the last launch (HnswVisited)
     int predicate_aware = 0;                         // vsr_hnsw_set_predicate_aware
@@ -3391,11 +3392,18 @@ static int hnsw_filter_bitmap(vsr_hnsw* h, const vsr_filter* f, const uint64_t**
     return VSR_OK;
 }
 
+// the iterative kernel's settings for one launch (hnsw_launch: nullptr = the plain search)
+struct HnswIterLaunch {
+    int mode = 0;
+    int64_t max_scan = 0;
+    uint32_t cap_d = 0;
+};
+
 // One launch over queries resident in device memory (rows of q_stride floats), results into device arrays; bitmaps: one
-// device pointer per query (d_bm, may be nullptr).  status_out / visited_out are optional device arrays.
+// device pointer per query (d_bm, may be nullptr).  status_out / visited_out are optional device arrays (iterative: T).
 static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const float* d_q, uint32_t q_stride, int nq, int k, int ef, int metric,
                        const uint64_t* const* d_bm, bool force_global, int64_t* d_blk, int32_t* d_doc, int64_t* d_row, float* d_dist,
-                       int32_t* d_cnt, int64_t* d_vis, int32_t* d_status)
+                       int32_t* d_cnt, int64_t* d_vis, int32_t* d_status, const HnswIterLaunch* iter = nullptr)
 {
     vsr_corpus* c = h->corpus;
     HnswParams p{};
@@ -3423,13 +3431,27 @@ static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const float* d_q, uint32_t q_s
     p.ef = (uint32_t) ef;
     p.k = (uint32_t) k;
     p.caps = (uint32_t) (2 * ef + 2 * h->m + 64);
-    if (!hnsw_plan(p, force_global)) {                      // S does not fit beside anything: a shorter tail behind W
+    if (iter) {                                             // (the LDS hash is sized by ef, not by the scan: never used here)
+        const char* env = getenv("VSR_HNSW_VISITED");
+        const bool glob = force_global || (env && !strcmp(env, "global"));
+        if (!hnsw_plan_iterative(p, glob)) {
+            p.caps = (uint32_t) (ef + 2 * h->m + 64);
+            if (!hnsw_plan_iterative(p, glob))
+                return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_search_iterative: ef_search = %d does not fit the LDS", ef);
+        }
+        int rc = h->d_disc.reserve((size_t) nq * iter->cap_d * sizeof(uint64_t));
+        if (rc) return rc;
+        p.iter_mode = iter->mode;
+        p.max_scan = iter->max_scan;
+        p.disc = h->d_disc.as<uint64_t>();
+        p.cap_d = iter->cap_d;
+    } else if (!hnsw_plan(p, force_global)) {               // S does not fit beside anything: a shorter tail behind W
         p.caps = (uint32_t) (ef + 2 * h->m + 64);
         if (!hnsw_plan(p, force_global)) return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_search: ef_search = %d does not fit the LDS", ef);
     }
     // development / tests: VSR_HNSW_VISITED=hash[:slots] forces the LDS hash table (with `slots` entries, a power of two) on a
     // graph small enough for the LDS bitmap, so that the table and its overflow re-run can be exercised on small graphs
-    if (!force_global) {
+    if (!force_global && !iter) {
         const char* env = getenv("VSR_HNSW_VISITED");
         if (env && !strncmp(env, "hash", 4)) {
             uint32_t slots = env[4] == ':' ? (uint32_t) atoi(env + 5) : 4096u;
@@ -3463,7 +3485,8 @@ static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const float* d_q, uint32_t q_s
     p.out_visited = d_vis;
     p.out_status = d_status;
     p.err = reinterpret_cast<uint32_t*>(ctx->d_flag_total) + 4;
-    HIPCHK(launch_hnsw_search(p, ctx->stream));
+    if (iter) HIPCHK(launch_hnsw_iterative(p, ctx->stream));
+    else HIPCHK(launch_hnsw_search(p, ctx->stream));
     h->last_mode = p.vis_mode;
     return VSR_OK;
 }
@@ -3584,6 +3607,152 @@ extern "C" int vsr_hnsw_search(vsr_hnsw* h, const float* queries, int nq, int di
             memcpy(out_dist + dst, reinterpret_cast<float*>(hh + o_dist) + src, (size_t) k * 4);
             out_cnt[redo[j]] = reinterpret_cast<int32_t*>(hh + o_cnt)[j];
             if (out_visited) out_visited[redo[j]] = reinterpret_cast<int64_t*>(hh + o_vis)[j];
+        }
+    }
+    return VSR_OK;
+}
+
+// ---- iterative index scans (hnsw.iterative_scan, hnsw.max_scan_tuples; vsr_hnsw.h's header comment) ----------------
+constexpr size_t HN_ITER_WORKSPACE = (size_t) 1 << 30;      // per launch: D + global visited bitmaps of its queries
+
+static int hnsw_iter_check(vsr_hnsw* h, const void* queries, int nq, int dim, int k, int ef, int metric,
+                           const vsr_filter* const* filters, int mode, int64_t max_scan_tuples, const char* who)
+{
+    int rc = hnsw_check(h, queries, nq, dim, k, ef, metric, filters, who);
+    if (rc) return rc;
+    if (mode < VSR_HNSW_ITERATIVE_OFF || mode > VSR_HNSW_ITERATIVE_STRICT) return fail(VSR_ERR_INVALID, "%s: iterative scan mode %d", who, mode);
+    if (max_scan_tuples < 1 || max_scan_tuples > INT_MAX)   /* hnsw.max_scan_tuples: 1 .. INT_MAX (hnsw.c:95-97) */
+        return fail(VSR_ERR_INVALID, "%s: max_scan_tuples must be between 1 and %d (got %lld)", who, INT_MAX, (long long) max_scan_tuples);
+    if (mode != VSR_HNSW_ITERATIVE_OFF && h->predicate_aware)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: iterative scans of the predicate-aware walk are not supported", who);
+    return VSR_OK;
+}
+
+// D's capacity: max_scan_tuples plus what one more round may visit beyond it (|D| <= T), at most every element.
+// VSR_HNSW_DISCARD_CAP=n (development / tests) forces n, so that the overflow re-run can be exercised on small graphs
+static uint32_t hnsw_discard_cap(const vsr_hnsw* h, int ef, int64_t max_scan_tuples)
+{
+    const int64_t slack = (int64_t) 4 * h->m * ef + 4096;    // (a round visits ~20 x ef elements at m = 16)
+    int64_t cap = std::min<int64_t>(h->n_elem, max_scan_tuples + slack);
+    if (const char* env = getenv("VSR_HNSW_DISCARD_CAP")) {
+        const long long forced = atoll(env);
+        if (forced > 0) cap = std::min<int64_t>(h->n_elem, forced);
+    }
+    return (uint32_t) std::max<int64_t>(cap, 1);
+}
+
+// the iterative kernel over queries resident on the device, one launch per chunk of queries whose workspace stays under
+// HN_ITER_WORKSPACE, on the context's stream without synchronisation
+static int hnsw_iter_run(vsr_hnsw* h, const float* d_q, int nq, int dim, int k, int ef, int metric, const vsr_filter* const* filters,
+                         int mode, int64_t max_scan_tuples, uint32_t cap_d, int64_t* d_blk, int32_t* d_doc, int64_t* d_row,
+                         float* d_dist, int32_t* d_cnt, int64_t* d_tuples, int32_t* d_status)
+{
+    vsr_ctx* ctx = h->corpus->ctx;
+    bool any_filter = false;
+    int rc;
+    if (h->h_bm.p) HIPCHK(hipStreamSynchronize(ctx->stream));            // the pinned pointer block of the previous call
+    if ((rc = hnsw_bitmaps(h, ctx, filters, 0, nq, any_filter))) return rc;
+    const size_t per_query = (size_t) cap_d * 8 + (((size_t) h->n_elem + 31) / 32) * 4;
+    const int chunk = (int) std::max<size_t>(1, std::min<size_t>((size_t) nq, HN_ITER_WORKSPACE / per_query));
+    HnswIterLaunch it;
+    it.mode = mode;
+    it.max_scan = max_scan_tuples;
+    it.cap_d = cap_d;
+    for (int q0 = 0; q0 < nq; q0 += chunk) {
+        const int n = std::min(chunk, nq - q0);
+        const size_t ok = (size_t) q0 * k;
+        if ((rc = hnsw_launch(h, ctx, d_q + (size_t) q0 * dim, (uint32_t) dim, n, k, ef, metric,
+                              any_filter ? h->d_bm.as<const uint64_t*>() + q0 : nullptr, false, d_blk + ok, d_doc + ok,
+                              d_row ? d_row + ok : nullptr, d_dist + ok, d_cnt + q0, d_tuples ? d_tuples + q0 : nullptr,
+                              d_status ? d_status + q0 : nullptr, &it)))
+            return rc;
+    }
+    return VSR_OK;
+}
+
+extern "C" int vsr_hnsw_search_iterative_device(vsr_hnsw* h, const float* d_queries, int nq, int dim, int k, int ef, int metric,
+                                                const vsr_filter* const* filters, int mode, int64_t max_scan_tuples,
+                                                int64_t* d_blk, int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt,
+                                                int64_t* d_tuples)
+{
+    int rc = hnsw_iter_check(h, d_queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples, "vsr_hnsw_search_iterative_device");
+    if (rc) return rc;
+    if (mode == VSR_HNSW_ITERATIVE_OFF)
+        return vsr_hnsw_search_device(h, d_queries, nq, dim, k, ef, metric, filters, d_blk, d_doc, d_row, d_dist, d_cnt, d_tuples);
+    if (nq == 0) return VSR_OK;
+    if (!d_blk || !d_dist || !d_cnt) return fail(VSR_ERR_INVALID, "vsr_hnsw_search_iterative_device: output is NULL");
+    vsr_ctx* ctx = h->corpus->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (!d_doc) {
+        if ((rc = h->d_out.reserve((size_t) nq * k * sizeof(int32_t)))) return rc;
+        d_doc = h->d_out.as<int32_t>();
+    }
+    return hnsw_iter_run(h, d_queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples, hnsw_discard_cap(h, ef, max_scan_tuples),
+                         d_blk, d_doc, d_row, d_dist, d_cnt, d_tuples, nullptr);
+}
+
+extern "C" int vsr_hnsw_search_iterative(vsr_hnsw* h, const float* queries, int nq, int dim, int k, int ef, int metric,
+                                         const vsr_filter* const* filters, int mode, int64_t max_scan_tuples, int64_t* out_blk,
+                                         int32_t* out_doc, int64_t* out_row, float* out_dist, int32_t* out_cnt, int64_t* out_tuples)
+{
+    int rc = hnsw_iter_check(h, queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples, "vsr_hnsw_search_iterative");
+    if (rc) return rc;
+    if (mode == VSR_HNSW_ITERATIVE_OFF)                      // hnsw.iterative_scan = off: the plain search, T = the visited count
+        return vsr_hnsw_search(h, queries, nq, dim, k, ef, metric, filters, out_blk, out_doc, out_row, out_dist, out_cnt, out_tuples);
+    if (nq == 0) return VSR_OK;
+    if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "vsr_hnsw_search_iterative: output is NULL");
+    vsr_ctx* ctx = h->corpus->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t nk = (size_t) nq * k;
+    const size_t o_blk = 0, o_row = align_up(o_blk + nk * 8, 256), o_doc = align_up(o_row + nk * 8, 256),
+                 o_dist = align_up(o_doc + nk * 4, 256), o_cnt = align_up(o_dist + nk * 4, 256),
+                 o_tup = align_up(o_cnt + (size_t) nq * 4, 256), o_st = align_up(o_tup + (size_t) nq * 8, 256),
+                 total = align_up(o_st + (size_t) nq * 4, 256);
+    if ((rc = h->d_q.reserve((size_t) nq * dim * sizeof(float)))) return rc;
+    if ((rc = h->d_out.reserve(total))) return rc;
+    if ((rc = h->h_out.reserve(total))) return rc;
+    char* d = h->d_out.as<char>();
+    char* hh = h->h_out.as<char>();
+    auto run = [&](const float* qs, int n, const vsr_filter* const* fs, uint32_t cap_d) -> int {
+        int r;
+        HIPCHK(hipMemcpyAsync(h->d_q.p, qs, (size_t) n * dim * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        if ((r = hnsw_iter_run(h, h->d_q.as<float>(), n, dim, k, ef, metric, fs, mode, max_scan_tuples, cap_d,
+                               reinterpret_cast<int64_t*>(d + o_blk), reinterpret_cast<int32_t*>(d + o_doc),
+                               reinterpret_cast<int64_t*>(d + o_row), reinterpret_cast<float*>(d + o_dist),
+                               reinterpret_cast<int32_t*>(d + o_cnt), reinterpret_cast<int64_t*>(d + o_tup),
+                               reinterpret_cast<int32_t*>(d + o_st))))
+            return r;
+        HIPCHK(hipMemcpyAsync(hh, d, total, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return VSR_OK;
+    };
+    if ((rc = run(queries, nq, filters, hnsw_discard_cap(h, ef, max_scan_tuples)))) return rc;
+    memcpy(out_blk, hh + o_blk, nk * 8);
+    if (out_row) memcpy(out_row, hh + o_row, nk * 8);
+    if (out_doc) memcpy(out_doc, hh + o_doc, nk * 4);
+    memcpy(out_dist, hh + o_dist, nk * 4);
+    memcpy(out_cnt, hh + o_cnt, (size_t) nq * 4);
+    if (out_tuples) memcpy(out_tuples, hh + o_tup, (size_t) nq * 8);
+    // queries whose D overflowed: again with room for every element (an element is in at most one of D, W, emitted)
+    std::vector<int> redo;
+    for (int i = 0; i < nq; ++i)
+        if (reinterpret_cast<const int32_t*>(hh + o_st)[i]) redo.push_back(i);
+    if (!redo.empty()) {
+        std::vector<float> q2(redo.size() * (size_t) dim);
+        std::vector<const vsr_filter*> f2(redo.size(), nullptr);
+        for (size_t j = 0; j < redo.size(); ++j) {
+            memcpy(&q2[j * (size_t) dim], queries + (size_t) redo[j] * dim, (size_t) dim * sizeof(float));
+            if (filters) f2[j] = filters[redo[j]];
+        }
+        if ((rc = run(q2.data(), (int) redo.size(), f2.data(), (uint32_t) std::max(h->n_elem, 1)))) return rc;
+        for (size_t j = 0; j < redo.size(); ++j) {
+            const size_t src = j * (size_t) k, dst = (size_t) redo[j] * k;
+            memcpy(out_blk + dst, reinterpret_cast<int64_t*>(hh + o_blk) + src, (size_t) k * 8);
+            if (out_row) memcpy(out_row + dst, reinterpret_cast<int64_t*>(hh + o_row) + src, (size_t) k * 8);
+            if (out_doc) memcpy(out_doc + dst, reinterpret_cast<int32_t*>(hh + o_doc) + src, (size_t) k * 4);
+            memcpy(out_dist + dst, reinterpret_cast<float*>(hh + o_dist) + src, (size_t) k * 4);
+            out_cnt[redo[j]] = reinterpret_cast<int32_t*>(hh + o_cnt)[j];
+            if (out_tuples) out_tuples[redo[j]] = reinterpret_cast<int64_t*>(hh + o_tup)[j];
         }
     }
     return VSR_OK;

@@ -18,6 +18,18 @@ def _metric(m):
     return METRICS[m] if isinstance(m, str) else int(m)
 
 
+# hnsw.iterative_scan's values (hnsw.c:21-31) -> vsr_hnsw_iterative
+ITERATIVE_MODES = {"off": 0, "relaxed_order": 1, "strict_order": 2}
+
+
+def _iterative_mode(m):
+    if isinstance(m, str):
+        if m not in ITERATIVE_MODES:
+            raise ValueError(f"invalid value for parameter \"hnsw.iterative_scan\": \"{m}\"")
+        return ITERATIVE_MODES[m]
+    return int(m)
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -488,3 +500,34 @@ class HnswIndex:
                                         _ptr(doc), _ptr(row), _ptr(dist), _ptr(cnt), _ptr(vis)))
         del keep
         return SearchResult(blk, doc, row, dist, cnt), vis
+
+    def search_iterative_device(self, d_queries, nq, k, ef_search, metric, filters, mode, max_scan_tuples, d_block, d_doc,
+                                d_rows, d_dist, d_counts, d_tuples=None):
+        """Device pointers (ints); launches on the corpus context's stream, no synchronisation
+        (vsr_hnsw_search_iterative_device).  A query whose discarded set outgrew its buffer reports count -1."""
+        farr, keep = self.corpus._filter_array(filters, nq)
+        check(self._lib.vsr_hnsw_search_iterative_device(self._h, d_queries, nq, self.corpus.dim, int(k), int(ef_search),
+                                                         _metric(metric), farr, _iterative_mode(mode), int(max_scan_tuples),
+                                                         d_block, d_doc, d_rows, d_dist, d_counts, d_tuples))
+        return keep
+
+    def search_iterative(self, queries, k, ef_search=40, metric="l2", filters=None, mode="relaxed_order",
+                         max_scan_tuples=20000):
+        """pgvector's iterative index scan (hnsw.iterative_scan = mode, hnsw.max_scan_tuples): rounds of the layer-0 search
+        resumed from the discarded candidates until k permitted rows are out.  SearchResult (rows in stream order) plus, as a
+        second value, the tuples each query's scan counted (so->tuples) when it stopped."""
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(queries, dtype=np.float32)))
+        nq, dim = q.shape
+        farr, keep = self.corpus._filter_array(filters, nq)
+        kk = max(int(k), 1)
+        blk = np.full((nq, kk), -1, dtype=np.int64)
+        doc = np.full((nq, kk), -1, dtype=np.int32)
+        row = np.full((nq, kk), -1, dtype=np.int64)
+        dist = np.full((nq, kk), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.int32)
+        tup = np.zeros(nq, dtype=np.int64)
+        check(self._lib.vsr_hnsw_search_iterative(self._h, _ptr(q), nq, dim, int(k), int(ef_search), _metric(metric), farr,
+                                                  _iterative_mode(mode), int(max_scan_tuples), _ptr(blk), _ptr(doc), _ptr(row),
+                                                  _ptr(dist), _ptr(cnt), _ptr(tup)))
+        del keep
+        return SearchResult(blk, doc, row, dist, cnt), tup
