@@ -174,7 +174,11 @@ int vsr_set_screening(vsr_ctx* ctx, int enable);           /* default: enabled; 
 int vsr_screening_check(vsr_ctx* ctx, int64_t* flagged_total, int32_t* flags_last_call, int nq);
 
 /* merge n_parts per-shard results (layout [n_parts][nq][k], as all-gathered from vsr_search_device) into the
- * global top-k: the client-side merge of search.py:347-364 done on the GPU. */
+ * global top-k: the client-side merge of search.py:347-364 done on the GPU.  Every part's list is sorted by key with
+ * KEY_EMPTY (all ones; payload -1 / -1 / +Inf) after its real entries.  Keys must be UNIQUE across the parts of a query
+ * (disjoint shards: the global row in the low 32 bits makes them so); the kernel does not remove duplicates -- replicated
+ * partitions are deduplicated on the host (vsrbac/placement.py).  n_parts * k <= 8192, else VSR_ERR_UNSUPPORTED.
+ * d_out_keys (nq*k, may be NULL) receives the merged keys, KEY_EMPTY past the count. */
 int vsr_merge_topk_device(vsr_ctx* ctx, const uint64_t* d_keys, const int64_t* d_block_ids,
                           const int32_t* d_doc_ids, const float* d_dist, int n_parts, int nq, int k,
                           int64_t* d_out_block_ids, int32_t* d_out_doc_ids, float* d_out_dist,

@@ -28,7 +28,8 @@ def assert_valid_topk(ids, dist, ref_all, k, tol, candidates=None):
     ok = (np.abs(dist - r) <= tol * scale) | (np.isnan(dist) & np.isnan(r))
     assert ok.all(), (dist[~ok], r[~ok])
     rr = np.where(np.isnan(r), np.inf, r)
-    assert (np.diff(rr) >= -tol * scale[1:]).all(), "not sorted"
+    fin = np.where(np.isnan(scale), 1.0, scale)         # (NaN rows rank as +inf; several may follow one another: inf - inf)
+    assert (rr[1:] >= rr[:-1] - tol * fin[1:]).all(), "not sorted"
     rest = np.setdiff1d(cand, ids)
     if rest.size:
         rest_d = np.where(np.isnan(ref_all[rest]), np.inf, ref_all[rest])

@@ -139,6 +139,80 @@ def test_index_scans_shard_like_exact_scans(ctx_free_gpu, oracle):
         c.close()
 
 
+def test_overflowed_hnsw_scans_are_rerun_before_the_merge(ctx_free_gpu, monkeypatch):
+    """vsr_hnsw_search_device reports count -1 for a query whose LDS visited table overflowed and leaves the re-run to the
+    caller.  GpuShardEngine.search_local_index is that caller: it must redo such queries (HnswIndex.search, global bitmap)
+    and patch them into the record, so the merged answer is bit-identical to the one without any overflow.  Before the
+    fix the -1 was read as "this rank found nothing": here every query of both shards overflows, and the merged lists came
+    back empty (every block id -1, every count 0).  The overflow is forced the tested way, with a tiny table
+    (VSR_HNSW_VISITED), no fault involved."""
+    import ctypes
+    import torch
+    import vsrbac
+    from vsrbac.sharded import GpuShardEngine, ShardedSearcher, shard_bounds
+    rng = np.random.default_rng(47)
+    n, dim, k, nq, ef = 8000, 64, 20, 16, 64
+    x = np.clip(np.rint(np.abs(rng.normal(0, 45, (n, dim)))), 0, 255).astype(np.float32)
+    blk = (np.arange(n) + 1).astype(np.int64)
+    doc = (np.arange(n) // 10 + 1).astype(np.int32)
+    mask = (rng.random(int(doc.max()) + 1) < 0.5)[doc].astype(np.uint8)
+    q = x[rng.integers(0, n, nq)] + rng.integers(0, 2, (nq, dim)).astype(np.float32)
+    dev = torch.device("cuda", 0)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    engines = []
+    for r in range(2):
+        lo, hi = shard_bounds(n, 2, r, align=10)
+        c = vsrbac.Context(0)
+        corpus = c.load_corpus(x[lo:hi], blk[lo:hi], doc[lo:hi], row_offset=lo)
+        e = GpuShardEngine(c, corpus, dev)
+        e.attach_index("hnsw", corpus.build_hnsw(16, 64, "l2", seed=5))
+        e.filters = [corpus.filter_from_bytemask(mask[lo:hi], vsrbac.BITMAP)] * nq
+        engines.append((e, c, corpus))
+
+    def merged():
+        locs = [e.search_local_index("hnsw", q, k, "l2", e.filters, ef_search=ef) for e, _, _ in engines]
+        torch.cuda.synchronize()
+        out = engines[0][0].merge_packed(torch.cat([l["pack"] for l in locs]), nq, k)
+        torch.cuda.synchronize()
+        return [t.cpu().numpy() for t in out]
+
+    def single():
+        out = ShardedSearcher(engines[0][0], 1, 0, None).search(q, k, "l2", engines[0][0].filters, index="hnsw", ef_search=ef)
+        torch.cuda.synchronize()
+        return [t.cpu().numpy() for t in out]
+
+    base, base1 = merged(), single()
+    assert (base[3] > 0).all() and (base1[3] > 0).all()
+    assert all(e.reruns == 0 for e, _, _ in engines)
+    monkeypatch.setenv("VSR_HNSW_VISITED", "hash:256")                  # read per call: the table now overflows
+    d_q = torch.from_numpy(q).to(dev)
+    overflowed = []
+    for e, c, corpus in engines:                                        # precondition: the raw device call does report -1
+        o = {"blk": torch.empty((nq, k), dtype=torch.int64, device=dev), "doc": torch.empty((nq, k), dtype=torch.int32, device=dev),
+             "row": torch.empty((nq, k), dtype=torch.int64, device=dev), "dist": torch.empty((nq, k), dtype=torch.float32, device=dev),
+             "cnt": torch.empty((nq,), dtype=torch.int32, device=dev)}
+        torch.cuda.synchronize()
+        keep = e.indexes["hnsw"].search_device(p(d_q), nq, k, ef, "l2", e.filters, p(o["blk"]), p(o["doc"]), p(o["row"]),
+                                               p(o["dist"]), p(o["cnt"]))
+        c.synchronize()
+        del keep
+        overflowed.append(int((o["cnt"].cpu().numpy() == -1).sum()))
+        assert overflowed[-1] >= 1, "the tiny visited table must overflow, or this test checks nothing"
+    again = merged()
+    for a, b in zip(again, base):                                       # block ids, doc ids, distances, counts
+        assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), (a, b)
+    for (e, _, _), lost in zip(engines, overflowed):
+        assert e.reruns >= lost
+    before = engines[0][0].reruns
+    for a, b in zip(single(), base1):
+        assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), (a, b)
+    assert engines[0][0].reruns - before >= overflowed[0]
+    for e, c, corpus in engines:
+        e.indexes["hnsw"].free()
+        corpus.free()
+        c.close()
+
+
 @pytest.fixture
 def ctx_free_gpu():
     yield None

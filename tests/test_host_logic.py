@@ -269,3 +269,80 @@ def test_device_keys_of_index_results_match_the_library_key():
     assert int(empty.numpy().view(np.uint64)[0]) == 0xFFFFFFFFFFFFFFFF
     order = np.argsort(got.numpy().view(np.uint64))
     assert list(dist[order][:2]) == [-np.inf, -2.25] and np.isnan(dist[order][-1])
+
+
+def test_rerun_rows_are_patched_into_the_record_before_the_keys():
+    """GpuShardEngine.patch_rerun / filters_of (the re-run of overflowed HNSW queries in search_local_index): the re-run
+    queries' rows replace theirs in the packed record and in the row array, other queries are untouched, the keys built
+    afterwards are the library's; a re-run that still reports a negative count raises instead of reaching the merge."""
+    import ctypes
+    import types
+    import torch
+    from vsrbac.engine import SearchResult
+    from vsrbac.sharded import GpuShardEngine, monotone_keys
+    eng = types.SimpleNamespace(torch=torch, device=torch.device("cpu"))
+    nq, k = 5, 4
+    nk = nq * k
+    rng = np.random.default_rng(9)
+    pack = torch.from_numpy(rng.integers(0, 256, nk * 24, dtype=np.uint8))
+    out = {"keys": pack[0:nk * 8].view(torch.int64).view(nq, k), "block": pack[nk * 8:nk * 16].view(torch.int64).view(nq, k),
+           "doc": pack[nk * 16:nk * 20].view(torch.int32).view(nq, k), "dist": pack[nk * 20:nk * 24].view(torch.float32).view(nq, k),
+           "counts": torch.tensor([4, -1, 2, -1, 0], dtype=torch.int32)}
+    rows = torch.from_numpy(rng.integers(0, 1000, (nq, k)))
+    out["dist"].copy_(torch.from_numpy(rng.random((nq, k), dtype=np.float32)))
+    keep = {name: t.clone() for name, t in out.items()}
+    keep_rows = rows.clone()
+    idx = np.array([1, 3])
+    res = SearchResult(block_ids=np.array([[11, 12, 13, -1], [-1, -1, -1, -1]], dtype=np.int64),
+                       doc_ids=np.array([[1, 1, 2, -1], [-1, -1, -1, -1]], dtype=np.int32),
+                       rows=np.array([[7, 3, 9, -1], [-1, -1, -1, -1]], dtype=np.int64),
+                       dist=np.array([[0.5, 0.5, -0.0, np.inf], [np.inf] * 4], dtype=np.float32),
+                       counts=np.array([3, 0], dtype=np.int32))
+    GpuShardEngine.patch_rerun(eng, out, rows, idx, res)
+    assert out["counts"].tolist() == [4, 3, 2, 0, 0]
+    for name, src in (("block", res.block_ids), ("doc", res.doc_ids), ("dist", res.dist)):
+        np.testing.assert_array_equal(out[name].numpy()[idx].view(np.uint8), src.view(np.uint8))
+        np.testing.assert_array_equal(out[name].numpy()[[0, 2, 4]], keep[name].numpy()[[0, 2, 4]])
+    np.testing.assert_array_equal(rows.numpy()[idx], res.rows)
+    np.testing.assert_array_equal(rows.numpy()[[0, 2, 4]], keep_rows.numpy()[[0, 2, 4]])
+    # the record itself (what the all-gather moves) holds the patched rows
+    np.testing.assert_array_equal(pack[nk * 8:nk * 16].view(torch.int64).view(nq, k).numpy()[1], res.block_ids[0])
+    # the step that follows in search_local_index: keys of the patched rows, empty slots last
+    valid = torch.arange(k)[None, :] < out["counts"][:, None]
+    keys = GpuShardEngine.device_keys(eng, out["dist"], torch.where(valid, rows, torch.full_like(rows, -1)), 1000)
+    np.testing.assert_array_equal(keys.numpy().view(np.uint64)[1, :3], monotone_keys(res.dist[0, :3], res.rows[0, :3] + 1000))
+    assert (keys.numpy().view(np.uint64)[1, 3:] == 0xFFFFFFFFFFFFFFFF).all() and (keys.numpy()[3] == -1).all()
+    for bad_counts in ([3, -1], [3]):
+        with pytest.raises(RuntimeError):
+            GpuShardEngine.patch_rerun(eng, out, rows, idx, res._replace(counts=np.array(bad_counts, dtype=np.int32)))
+    # the filters of the re-run queries, in every form a search takes them
+    one = object()
+    assert GpuShardEngine.filters_of(None, idx) is None and GpuShardEngine.filters_of(one, idx) is one
+    assert GpuShardEngine.filters_of(["a", "b", "c", "d", "e"], idx) == ["b", "d"]
+    arr = (ctypes.c_void_p * 5)(10, 20, None, 40, 50)
+    sub = GpuShardEngine.filters_of(arr, idx)
+    assert isinstance(sub, ctypes.Array) and len(sub) == 2 and list(sub) == [20, 40]
+
+
+@pytest.mark.parametrize("n_parts,k", [(2, 1), (3, 5), (3, 43), (8, 100), (64, 128), (8192, 1)])
+def test_merge_case_generator_and_its_reference(n_parts, k):
+    """tests/merge_model.py on its own: the forced conditions hold (asserted inside make_case), every part's list is
+    sorted with KEY_EMPTY last, and the reference is the k smallest real keys with the payload that came with each."""
+    import merge_model as mm
+    case = mm.make_case(n_parts, k, 7, 3)
+    keys, ref = case["keys"], case["ref"]
+    assert (keys[:, :, 1:] >= keys[:, :, :-1]).all()
+    empty = keys == mm.KEY_EMPTY
+    assert (case["block"][empty] == -1).all() and (case["doc"][empty] == -1).all() and np.isposinf(case["dist"][empty]).all()
+    if n_parts * k >= 100:                                  # (room for every kind of value)
+        assert np.isnan(case["dist"]).any() and (case["doc"][~empty] < 0).any() and (case["block"][~empty] > 2**32).any()
+    for q in range(7):
+        flat = {int(kk): (b, d, x) for kk, b, d, x in zip(keys[:, q].ravel(), case["block"][:, q].ravel(),
+                                                            case["doc"][:, q].ravel(), case["dist"][:, q].ravel().view(np.uint32))
+                if kk != mm.KEY_EMPTY}
+        want = sorted(flat)[:k]
+        m = ref["counts"][q]
+        assert m == len(want) and ref["keys"][q, :m].tolist() == want and (ref["keys"][q, m:] == mm.KEY_EMPTY).all()
+        for j, kk in enumerate(want):
+            assert (ref["block"][q, j], ref["doc"][q, j], ref["dist"][q, j].view(np.uint32)) == flat[kk]
+    assert mm.packed_records(case).size == n_parts * 7 * k * 24

@@ -370,13 +370,11 @@ __global__ __launch_bounds__(256) void merge_lists_kernel(const uint64_t* keys, 
         uint32_t pos = 0;
         if (i < total) {
             const uint32_t part = i / k, j = i % k;
-            if (part_stride) {
-                pos = i;                                     // position = (part, j); resolved again when reading
-                key = reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(keys) + part * part_stride)[q * k + j];
-            } else {
-                pos = (part * n_queries + q) * k + j;
-                key = keys[pos];
-            }
+            pos = i;                                         // position = (part, j); resolved again when reading
+            if (part_stride)
+                key = reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(keys) + part * part_stride)[(size_t) q * k + j];
+            else
+                key = keys[((size_t) part * n_queries + q) * k + j];   // (64-bit: n_parts * nq * k may pass 2^32)
         }
         skey[i] = key;
         spos[i] = pos;
@@ -404,14 +402,15 @@ __global__ __launch_bounds__(256) void merge_lists_kernel(const uint64_t* keys, 
             const uint32_t pos = spos[i];
             if (part_stride) {
                 const size_t off = (size_t) (pos / k) * part_stride;
-                const uint32_t e = q * k + pos % k;
+                const size_t e = (size_t) q * k + pos % k;
                 out_block[o] = reinterpret_cast<const int64_t*>(reinterpret_cast<const char*>(blocks) + off)[e];
                 out_doc[o] = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(docs) + off)[e];
                 out_dist[o] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(dist) + off)[e];
             } else {
-                out_block[o] = blocks[pos];
-                out_doc[o] = docs[pos];
-                out_dist[o] = dist[pos];
+                const size_t e = ((size_t) (pos / k) * n_queries + q) * k + pos % k;
+                out_block[o] = blocks[e];
+                out_doc[o] = docs[e];
+                out_dist[o] = dist[e];
             }
             if (out_keys) out_keys[o] = key;
         } else {

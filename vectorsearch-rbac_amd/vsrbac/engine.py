@@ -203,7 +203,7 @@ class Filter:
 
     def __del__(self):
         try:
-            if self.corpus._h:
+            if self.corpus._h and self.corpus.ctx._h:   # (vsr_filter_free reaches through the corpus to its context)
                 self.free()
         except Exception:
             pass
@@ -401,7 +401,7 @@ class IvfIndex:
 
     def __del__(self):
         try:
-            if self.corpus._h:
+            if self.corpus._h and self.corpus.ctx._h:
                 self.free()
         except Exception:
             pass
@@ -460,7 +460,7 @@ class HnswIndex:
 
     def __del__(self):
         try:
-            if self.corpus._h:
+            if self.corpus._h and self.corpus.ctx._h:
                 self.free()
         except Exception:
             pass

@@ -133,6 +133,30 @@ class GpuShardEngine:
         keys = (m << 32) | ((rows + int(row_offset)) & 0xFFFFFFFF)
         return torch.where(rows < 0, torch.full_like(keys, -1), keys)      # (-1 = 0xFFFF...: KEY_EMPTY)
 
+    @staticmethod
+    def filters_of(filters, idx):
+        """The filters of queries `idx` out of what a search takes: None, one Filter for all, a list, or a packed C array."""
+        if filters is None or not hasattr(filters, "__len__"):
+            return filters
+        if isinstance(filters, ctypes.Array):
+            sub = type(filters)._type_ * len(idx)
+            arr = sub(*[filters[int(i)] for i in idx])
+            arr._keep = filters                          # the handles must outlive the array
+            return arr
+        return [filters[int(i)] for i in idx]
+
+    def patch_rerun(self, out, rows, idx, res):
+        """Write the re-run queries' answers (`res`: host SearchResult, one entry per query of `idx`) over rows `idx` of the
+        record `out` and of `rows`, before the ordering keys are built.  A re-run that still has no answer is an error."""
+        torch = self.torch
+        counts = np.asarray(res.counts)
+        if counts.shape[0] != len(idx) or (counts < 0).any():
+            raise RuntimeError(f"re-run of {len(idx)} overflowed index queries left counts {counts.tolist()}")
+        at = torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(self.device)
+        for dst, src in ((out["block"], res.block_ids), (out["doc"], res.doc_ids), (out["dist"], res.dist),
+                         (out["counts"], res.counts), (rows, res.rows)):
+            dst[at] = torch.from_numpy(np.ascontiguousarray(src)).to(self.device, dst.dtype)
+
     def search_local_index(self, kind, queries, k, metric, filters, probes=None, ef_search=None):
         torch = self.torch
         index = getattr(self, "indexes", {}).get(kind)
@@ -153,9 +177,20 @@ class GpuShardEngine:
         if kind == "ivf":
             index.search_device(self._p(q), nq, k, int(probes if probes is not None else 1), metric, filters, *ptrs)
         else:
-            keep = index.search_device(self._p(q), nq, k, int(ef_search if ef_search is not None else 40), metric, filters, *ptrs)
+            ef = int(ef_search if ef_search is not None else 40)
+            keep = index.search_device(self._p(q), nq, k, ef, metric, filters, *ptrs)
             self.ctx.synchronize()                          # (one asynchronous launch: the filter array must outlive it)
             del keep
+            # a query whose LDS visited table overflowed reports count -1 and nothing else (vsr_hnsw_search_device): the
+            # host entry point redoes such queries with the global bitmap; its rows replace theirs in the record
+            bad = torch.nonzero(out["counts"] < 0).flatten().cpu().numpy()
+            if bad.size:
+                res, _ = index.search(q[torch.from_numpy(bad).to(self.device)].cpu().numpy(), k, ef, metric,
+                                      self.filters_of(filters, bad))
+                self.patch_rerun(out, rows, bad, res)
+                self.reruns += int(bad.size)
+        if bool((out["counts"] < 0).any()):                 # (the IVFFlat call returns proven-exact answers: never expected)
+            raise RuntimeError(f"{kind} index scan left a query without a result (negative count)")
         # slots past a query's count hold -1 / +inf already (the ABI's convention); their keys sort last
         valid = torch.arange(k, device=self.device)[None, :] < out["counts"][:, None]
         rows = torch.where(valid, rows, torch.full_like(rows, -1))
