@@ -1,4 +1,4 @@
-// vsr_hnsw_build.h -- parameters of the batched HNSW build (vsr_hnsw_build.hip), shared with the host loop in vsr_runtime.hip
+// vsr_hnsw_build.h -- parameters of the batched HNSW build (vsr_hnsw_build.hip), shared with the host loop in vsr_hnsw_rt.hip
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>

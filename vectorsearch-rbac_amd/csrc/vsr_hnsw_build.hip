@@ -369,7 +369,7 @@ __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildPar
 
 using namespace vsr;
 
-// host side: see vsr_runtime.hip (vsr_hnsw_build) for the batch loop; these are the two launches and the sort of a batch
+// host side: see vsr_hnsw_rt.hip (vsr_hnsw_build) for the batch loop; these are the two launches and the sort of a batch
 hipError_t vsr_hnsw_build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt, uint64_t* d_val_alt,
                                 hipStream_t s)
 {

@@ -1,0 +1,605 @@
+// vsr_hnsw_rt.hip — K4: HNSW graph load / build / search entry points.  The only unit that compiles vsr_hnsw.h's kernels.
+#include "vsr_runtime.h"
+#include "vsr_hnsw.h"
+#include "vsr_hnsw_build.h"
+
+#include <climits>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+
+// ---- K4: HNSW graph search (hnswscan.c:15-45, hnswutils.c:813-976) over a graph built elsewhere
+struct vsr_hnsw {
+    vsr_corpus* corpus = nullptr;
+    int32_t n_elem = 0, entry = -1, entry_level = -1, m = 0, max_level = 1;
+    int32_t *d_elem_row = nullptr, *d_level = nullptr, *d_nbr0 = nullptr, *d_up_slot = nullptr, *d_up_nbr = nullptr,
+            *d_tid_count = nullptr, *d_tids = nullptr;
+    std::map<uint64_t, uint64_t*> bitmaps;           // filters (by vsr_filter::id) without a full bitmap of their own, as one
+    DevBuf d_q, d_vis, d_out, d_bm, d_disc;
+    PinBuf h_out, h_bm;
+    int last_mode = -1;                              // visited form of the last launch (HnswVisited)
+    int predicate_aware = 0;                         // vsr_hnsw_set_predicate_aware
+};
+
+extern "C" int vsr_hnsw_free(vsr_hnsw* h)
+{
+    if (!h) return VSR_OK;
+    if (h->corpus) {
+        (void) hipSetDevice(h->corpus->ctx->device);
+        (void) hipStreamSynchronize(h->corpus->ctx->stream);
+    }
+    if (h->corpus) {
+        auto& reg = h->corpus->hnsw_indexes;
+        reg.erase(std::remove(reg.begin(), reg.end(), h), reg.end());
+    }
+    void* ptrs[] = {h->d_elem_row, h->d_level, h->d_nbr0, h->d_up_slot, h->d_up_nbr, h->d_tid_count, h->d_tids};
+    for (void* p : ptrs)
+        if (p) (void) hipFree(p);
+    for (auto& kv : h->bitmaps)
+        if (kv.second) (void) hipFree(kv.second);
+    delete h;
+    return VSR_OK;
+}
+
+static int upload_i32(int32_t** d, const int32_t* src, size_t count)          // a graph array into device memory of its own
+{
+    HIPCHK(hipMalloc(d, std::max<size_t>(4, count * sizeof(int32_t))));
+    if (count) HIPCHK(hipMemcpy(*d, src, count * sizeof(int32_t), hipMemcpyHostToDevice));
+    return VSR_OK;
+}
+
+extern "C" int vsr_hnsw_load(vsr_corpus* c, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
+                             const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
+                             int32_t n_upper, int32_t max_level, vsr_hnsw** out)
+{
+    if (!c || !out) return fail(VSR_ERR_INVALID, "vsr_hnsw_load: NULL argument");
+    *out = nullptr;
+    if (c->base) return fail(VSR_ERR_INVALID, "vsr_hnsw_load: the corpus is a view");
+    if (m < 2 || m > 100)        /* reloption m: 2 .. HNSW_MAX_M (hnsw.h:36-40) */
+        return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_load: m must be between 2 and 100 (got %d)", m);
+    if (n_elem < 0 || (n_elem > 0 && (!level || !nbr0 || !tid_count || !tids || !up_slot)) || max_level < 1 || n_upper < 0 ||
+        (n_upper > 0 && !up_nbr) || entry >= n_elem)
+        return fail(VSR_ERR_INVALID, "vsr_hnsw_load: bad graph arrays");
+    vsr_ctx* ctx = c->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    std::unique_ptr<vsr_hnsw> h(new vsr_hnsw());
+    h->corpus = c;
+    h->n_elem = n_elem;
+    h->entry = n_elem > 0 ? entry : -1;
+    h->m = m;
+    h->max_level = max_level;
+    // heap TIDs arrive as caller row indices; the kernels work on internal rows
+    std::vector<int32_t> inv((size_t) std::max<int64_t>(c->n, 1), -1);
+    for (int64_t r = 0; r < c->n; ++r) inv[(size_t) c->h_orig[(size_t) r]] = (int32_t) r;
+    std::vector<int32_t> itids((size_t) std::max(n_elem, 1) * 10, -1), erow((size_t) std::max(n_elem, 1), 0);
+    for (int32_t e = 0; e < n_elem; ++e) {
+        if (tid_count[e] < 1 || tid_count[e] > 10 || level[e] < 0 || level[e] > max_level)
+            return fail(VSR_ERR_INVALID, "vsr_hnsw_load: element %d has %d heap TIDs / level %d", e, tid_count[e], level[e]);
+        for (int t = 0; t < tid_count[e]; ++t) {
+            const int64_t row = tids[(size_t) e * 10 + t];
+            if (row < 0 || row >= c->n) return fail(VSR_ERR_INVALID, "vsr_hnsw_load: element %d points at row %lld", e, (long long) row);
+            itids[(size_t) e * 10 + t] = inv[(size_t) row];
+        }
+        erow[(size_t) e] = itids[(size_t) e * 10];
+        for (int j = 0; j < 2 * m; ++j)
+            if (nbr0[(size_t) e * 2 * m + j] >= n_elem) return fail(VSR_ERR_INVALID, "vsr_hnsw_load: neighbour out of range");
+    }
+    h->entry_level = h->entry >= 0 ? level[h->entry] : -1;
+    auto& up = upload_i32;
+    int rc;
+    if ((rc = up(&h->d_elem_row, erow.data(), (size_t) n_elem)) || (rc = up(&h->d_level, level, (size_t) n_elem)) ||
+        (rc = up(&h->d_nbr0, nbr0, (size_t) n_elem * 2 * m)) || (rc = up(&h->d_up_slot, up_slot, (size_t) n_elem)) ||
+        (rc = up(&h->d_up_nbr, up_nbr, (size_t) n_upper * max_level * m)) || (rc = up(&h->d_tid_count, tid_count, (size_t) n_elem)) ||
+        (rc = up(&h->d_tids, itids.data(), (size_t) n_elem * 10))) {
+        vsr_hnsw_free(h.release());
+        return rc;
+    }
+    c->hnsw_indexes.push_back(h.get());
+    *out = h.release();
+    return VSR_OK;
+}
+
+// CREATE INDEX ... USING hnsw on the GPU (vsr_hnsw_build.hip): batched insertion over the corpus's rows (element e = internal
+// row e), levels from a seeded xorshift64* stream.  Returns a loaded index, as vsr_hnsw_load would from the same graph.
+extern "C" int vsr_hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, vsr_hnsw** out)
+{
+    if (!c || !out) return fail(VSR_ERR_INVALID, "vsr_hnsw_build: NULL argument");
+    *out = nullptr;
+    if (c->base) return fail(VSR_ERR_INVALID, "vsr_hnsw_build: the corpus is a view");
+    if (m < 2 || m > 100) return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_build: m must be between 2 and 100 (got %d)", m);
+    if (ef_construction < 4 || ef_construction > 1000 || ef_construction < 2 * m)      /* hnsw.c:62-63, hnswbuild.c:677-679 */
+        return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_build: ef_construction must be between 4 and 1000 and at least 2 * m (got %d)",
+                    ef_construction);
+    if (metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)
+        return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_build: L2, inner product and cosine operator classes only");
+    vsr_ctx* ctx = c->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t n = c->n;
+    if (n > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_build: too many rows");
+    std::unique_ptr<vsr_hnsw> h(new vsr_hnsw());
+    h->corpus = c;
+    h->n_elem = (int32_t) n;
+    h->m = m;
+    // levels: level = floor(-ln(u) * ml), ml = 1 / ln(m) (hnswutils.c:243), capped like HnswGetMaxLevel (hnsw.h:89)
+    int cap = (8192 - 24 - 8 - 4 - 4) / 6 / m - 2;
+    cap = std::min(cap, 255);
+    uint64_t rs = seed * 0x9E3779B97F4A7C15ULL + 0x1234567ULL;               // xorshift64* (the serial CPU restatement draws the same stream)
+    if (!rs) rs = 1;
+    auto next = [&]() {
+        uint64_t x = rs;
+        x ^= x >> 12; x ^= x << 25; x ^= x >> 27;
+        rs = x;
+        return x * 0x2545F4914F6CDD1DULL;
+    };
+    (void) next();
+    const double ml = 1.0 / std::log((double) m);
+    std::vector<int32_t> level((size_t) std::max<int64_t>(n, 1), 0), up_slot((size_t) std::max<int64_t>(n, 1), -1);
+    int32_t max_level = 1, n_upper = 0;
+    for (int64_t e = 0; e < n; ++e) {
+        const double u = (double) (next() >> 11) * (1.0 / 9007199254740992.0);
+        int lv = (int) (-std::log(u) * ml);
+        lv = std::min(lv, cap);
+        level[(size_t) e] = lv;
+        if (lv >= 1) {
+            up_slot[(size_t) e] = n_upper++;
+            max_level = std::max(max_level, lv);
+        }
+    }
+    h->max_level = max_level;
+    const size_t alloc = (size_t) std::max<int64_t>(n, 1);
+    float *d_dist0 = nullptr, *d_up_dist = nullptr;
+    uint64_t *d_key[2] = {nullptr, nullptr}, *d_val[2] = {nullptr, nullptr};
+    uint32_t* d_cnt = nullptr;
+    void* d_tmp = nullptr;
+    auto cleanup = [&]() {
+        void* ptrs[] = {d_dist0, d_up_dist, d_key[0], d_key[1], d_val[0], d_val[1], d_cnt, d_tmp};
+        for (void* q : ptrs)
+            if (q) (void) hipFree(q);
+    };
+    auto bail = [&](int rc) {
+        cleanup();
+        vsr_hnsw_free(h.release());
+        return rc;
+    };
+#define HB_CHK(call)                                                                                         \
+    do {                                                                                                     \
+        hipError_t e_ = (call);                                                                              \
+        if (e_ != hipSuccess) return bail(fail(VSR_ERR_HIP, "vsr_hnsw_build: %s", hipGetErrorString(e_)));   \
+    } while (0)
+    const size_t up_words = (size_t) std::max(n_upper, 1) * max_level * m;
+    HB_CHK(hipMalloc(&h->d_level, alloc * 4));
+    HB_CHK(hipMalloc(&h->d_up_slot, alloc * 4));
+    HB_CHK(hipMalloc(&h->d_nbr0, alloc * 2 * m * 4));
+    HB_CHK(hipMalloc(&h->d_up_nbr, up_words * 4));
+    HB_CHK(hipMalloc(&d_dist0, alloc * 2 * m * 4));
+    HB_CHK(hipMalloc(&d_up_dist, up_words * 4));
+    HB_CHK(hipMemcpy(h->d_level, level.data(), alloc * 4, hipMemcpyHostToDevice));
+    HB_CHK(hipMemcpy(h->d_up_slot, up_slot.data(), alloc * 4, hipMemcpyHostToDevice));
+    HB_CHK(hipMemsetAsync(h->d_nbr0, 0xFF, alloc * 2 * m * 4, ctx->stream));
+    HB_CHK(hipMemsetAsync(h->d_up_nbr, 0xFF, up_words * 4, ctx->stream));
+
+    HnswBuildParams bp{};
+    bp.rows = c->d_rows;
+    bp.stride4 = c->stride4;
+    bp.metric = metric == VSR_METRIC_L2 ? M_L2 : M_IP;
+    bp.m = (uint32_t) m;
+    bp.efc = (uint32_t) ef_construction;
+    bp.max_level = (uint32_t) max_level;
+    bp.nbr0 = h->d_nbr0;
+    bp.dist0 = d_dist0;
+    bp.up_slot = h->d_up_slot;
+    bp.up_nbr = h->d_up_nbr;
+    bp.up_dist = d_up_dist;
+    bp.level = h->d_level;
+    bp.caps = (uint32_t) (ef_construction + 2 * m);
+    uint32_t slots = 4096;
+    while (slots < (uint32_t) ef_construction * 2u * (uint32_t) m * 2u && slots < 32768u) slots <<= 1;
+    bp.hash_slots = slots;
+    const size_t per = ((size_t) bp.caps * 8 + ((bp.caps + 15) & ~15u) + (size_t) HB_NBR * 12 + (size_t) bp.caps * 4 + (size_t) slots * 4 + 15) &
+                       ~(size_t) 15;
+    if (per > HN_LDS_BUDGET) return bail(fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_build: ef_construction = %d with m = %d does not fit the LDS", ef_construction, m));
+    bp.lds_per_wave = (uint32_t) per;
+    bp.wpb = (uint32_t) std::min<size_t>(4, HN_LDS_BUDGET / per);
+    bp.err = ctx->err_word();
+    const uint32_t batch_max = 4096;
+    bp.rec_cap = batch_max * (uint32_t) (2 * m + std::min(max_level, 4) * m);
+    HB_CHK(hipMalloc(&d_key[0], (size_t) bp.rec_cap * 8));
+    HB_CHK(hipMalloc(&d_key[1], (size_t) bp.rec_cap * 8));
+    HB_CHK(hipMalloc(&d_val[0], (size_t) bp.rec_cap * 8));
+    HB_CHK(hipMalloc(&d_val[1], (size_t) bp.rec_cap * 8));
+    HB_CHK(hipMalloc(&d_cnt, 64));
+    const size_t tmp_bytes = vsr_hnsw_build_sort_bytes(bp.rec_cap);
+    HB_CHK(hipMalloc(&d_tmp, std::max<size_t>(tmp_bytes, 256)));
+    bp.rec_count = d_cnt;
+
+    int32_t entry = -1, entry_level = -1;
+    for (int64_t done = 0; done < n;) {
+        // a batch never exceeds 1/8 of the graph it is inserted into: its elements do not see each other
+        const int64_t b = std::max<int64_t>(1, std::min<int64_t>({done / 8, (int64_t) batch_max, n - done}));
+        bp.entry = entry;
+        bp.entry_level = entry_level;
+        bp.first = (uint32_t) done;
+        bp.count = (uint32_t) b;
+        bp.rec_key = d_key[0];
+        bp.rec_val = d_val[0];
+        HB_CHK(vsr_hnsw_build_batch(bp, d_tmp, tmp_bytes, d_key[1], d_val[1], ctx->stream));
+        for (int64_t e = done; e < done + b; ++e)            // HnswUpdateGraphInMemory: a higher element becomes the entry point
+            if (entry < 0 || level[(size_t) e] > entry_level) {
+                entry = (int32_t) e;
+                entry_level = level[(size_t) e];
+            }
+        done += b;
+    }
+#undef HB_CHK
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    cleanup();
+    h->entry = n > 0 ? entry : -1;
+    h->entry_level = n > 0 ? entry_level : -1;
+    // element e holds internal row e alone
+    std::vector<int32_t> erow(alloc, 0), tcount(alloc, 1), itids(alloc * 10, -1);
+    for (int64_t e = 0; e < n; ++e) {
+        erow[(size_t) e] = (int32_t) e;
+        itids[(size_t) e * 10] = (int32_t) e;
+    }
+    auto& up = upload_i32;
+    int rc;
+    if ((rc = up(&h->d_elem_row, erow.data(), alloc)) || (rc = up(&h->d_tid_count, tcount.data(), alloc)) ||
+        (rc = up(&h->d_tids, itids.data(), alloc * 10))) {
+        vsr_hnsw_free(h.release());
+        return rc;
+    }
+    c->hnsw_indexes.push_back(h.get());
+    *out = h.release();
+    return VSR_OK;
+}
+
+// what a build left: elements, entry point, its level, the highest level (for reports and tests)
+extern "C" int vsr_hnsw_set_predicate_aware(vsr_hnsw* h, int on)
+{
+    if (!h) return fail(VSR_ERR_INVALID, "vsr_hnsw_set_predicate_aware: index is NULL");
+    h->predicate_aware = on ? 1 : 0;
+    return VSR_OK;
+}
+
+extern "C" int vsr_hnsw_info(const vsr_hnsw* h, int32_t* n_elem, int32_t* entry, int32_t* entry_level, int32_t* max_level)
+{
+    if (!h) return fail(VSR_ERR_INVALID, "vsr_hnsw_info: index is NULL");
+    if (n_elem) *n_elem = h->n_elem;
+    if (entry) *entry = h->entry;
+    if (entry_level) *entry_level = h->entry_level;
+    if (max_level) *max_level = h->max_level;
+    return VSR_OK;
+}
+
+void vsr::purge_hnsw_caches(vsr_corpus* c, const vsr_filter* f)
+{
+    for (vsr_hnsw* h : c->hnsw_indexes) {
+        for (auto it = h->bitmaps.begin(); it != h->bitmaps.end();) {
+            if (!f || it->first == f->id) {
+                if (it->second) (void) hipFree(it->second);
+                it = h->bitmaps.erase(it);
+            } else
+                ++it;
+        }
+    }
+}
+
+// the rows a filter admits as a bitmap over internal rows
+static int hnsw_filter_bitmap(vsr_hnsw* h, const vsr_filter* f, const uint64_t** out)
+{
+    vsr_corpus* c = h->corpus;
+    if (f->mode == VSR_FILTER_BITMAP && f->d_bitmap) {       // role / byte-mask filters in post-filter mode: already one
+        *out = f->d_bitmap;
+        return VSR_OK;
+    }
+    auto it = h->bitmaps.find(f->id);
+    if (it == h->bitmaps.end()) {
+        uint64_t* d = nullptr;
+        const size_t words = bitmap_words(c->n);
+        HIPCHK(hipMalloc(&d, words * sizeof(uint64_t)));
+        HIPCHK(hipMemsetAsync(d, 0, words * sizeof(uint64_t), c->ctx->stream));
+        HIPCHK(launch_view_bitmap(nullptr, (uint32_t) c->n, f->d_tiles, f->n_tiles, f->d_bitmap, d, c->ctx->stream));
+        it = h->bitmaps.emplace(f->id, d).first;
+    }
+    *out = it->second;
+    return VSR_OK;
+}
+
+// the iterative kernel's settings for one launch (hnsw_launch: nullptr = the plain search)
+struct HnswIterLaunch {
+    int mode;
+    int64_t max_scan;
+    uint32_t cap_d;
+};
+
+// One launch over queries resident in device memory (rows of q_stride floats), results into device arrays; bitmaps: one
+// device pointer per query (d_bm, may be nullptr).  d_status / d_vis are optional device arrays (iterative: T).
+static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const float* d_q, uint32_t q_stride, int nq, int k, int ef, int metric,
+                       const uint64_t* const* d_bm, bool force_global, const Outputs& out, int64_t* d_vis, int32_t* d_status,
+                       const HnswIterLaunch* iter = nullptr)
+{
+    vsr_corpus* c = h->corpus;
+    HnswParams p{};
+    p.rows = c->d_rows;
+    p.stride4 = c->stride4;
+    p.metric = metric;
+    p.queries = d_q;
+    p.q_stride = q_stride;
+    p.dim = (uint32_t) c->dim;
+    p.nq = (uint32_t) nq;
+    p.n_elem = (uint32_t) h->n_elem;
+    p.entry = h->entry;
+    p.entry_level = h->entry_level;
+    p.m = (uint32_t) h->m;
+    p.max_level = (uint32_t) h->max_level;
+    p.elem_row = h->d_elem_row;
+    p.nbr0 = h->d_nbr0;
+    p.up_slot = h->d_up_slot;
+    p.up_nbr = h->d_up_nbr;
+    p.level = h->d_level;
+    p.tid_count = h->d_tid_count;
+    p.tids = h->d_tids;
+    p.bitmaps = d_bm;
+    p.predicate_aware = h->predicate_aware;
+    p.ef = (uint32_t) ef;
+    p.k = (uint32_t) k;
+    p.caps = (uint32_t) (2 * ef + 2 * h->m + 64);
+    if (iter) {                                             // (the LDS hash is sized by ef, not by the scan: never used here)
+        const char* env = getenv("VSR_HNSW_VISITED");
+        const bool glob = force_global || (env && !strcmp(env, "global"));
+        if (!hnsw_plan_iterative(p, glob)) {
+            p.caps = (uint32_t) (ef + 2 * h->m + 64);
+            if (!hnsw_plan_iterative(p, glob))
+                return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_search_iterative: ef_search = %d does not fit the LDS", ef);
+        }
+        int rc = h->d_disc.reserve((size_t) nq * iter->cap_d * sizeof(uint64_t));
+        if (rc) return rc;
+        p.iter_mode = iter->mode;
+        p.max_scan = iter->max_scan;
+        p.disc = h->d_disc.as<uint64_t>();
+        p.cap_d = iter->cap_d;
+    } else if (!hnsw_plan(p, force_global)) {               // S does not fit beside anything: a shorter tail behind W
+        p.caps = (uint32_t) (ef + 2 * h->m + 64);
+        if (!hnsw_plan(p, force_global)) return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_search: ef_search = %d does not fit the LDS", ef);
+    }
+    // development / tests: VSR_HNSW_VISITED=hash[:slots] forces the LDS hash table (with `slots` entries, a power of two) on a
+    // graph small enough for the LDS bitmap, so that the table and its overflow re-run can be exercised on small graphs
+    if (!force_global && !iter) {
+        const char* env = getenv("VSR_HNSW_VISITED");
+        if (env && !strncmp(env, "hash", 4)) {
+            uint32_t slots = env[4] == ':' ? (uint32_t) atoi(env + 5) : 4096u;
+            while (slots & (slots - 1)) slots &= slots - 1;
+            slots = std::max(64u, slots);
+            const size_t fixed = hnsw_lds_fixed(p.caps);
+            if (fixed + (size_t) slots * 4 <= HN_LDS_BUDGET) {
+                p.vis_mode = VIS_LDS_HASH;
+                p.vis_words = slots;
+                p.lds_per_query = (uint32_t) ((fixed + (size_t) slots * 4 + 15) & ~(size_t) 15);
+                p.qpb = 1;
+            }
+        } else if (env && !strcmp(env, "global")) {
+            (void) hnsw_plan(p, true);
+        }
+    }
+    if (p.vis_mode == VIS_GLOBAL) {
+        int rc = h->d_vis.reserve((size_t) nq * p.vis_words * 4);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(h->d_vis.p, 0, (size_t) nq * p.vis_words * 4, ctx->stream));
+        p.visited = h->d_vis.as<uint32_t>();
+    }
+    set_results(p, c, out);
+    p.out_visited = d_vis;
+    p.out_status = d_status;
+    p.err = ctx->err_word();
+    if (iter) HIPCHK(launch_hnsw_iterative(p, ctx->stream));
+    else HIPCHK(launch_hnsw_search(p, ctx->stream));
+    h->last_mode = p.vis_mode;
+    return VSR_OK;
+}
+
+static int hnsw_check(vsr_hnsw* h, const void* queries, int nq, int dim, int k, int ef, int metric, const vsr_filter* const* filters,
+                      const char* who)
+{
+    if (!h) return fail(VSR_ERR_INVALID, "%s: index is NULL", who);
+    int rc = check_search_args(h->corpus, queries, nq, dim, k, metric, filters, who);
+    if (rc) return rc;
+    if (metric == VSR_METRIC_L1) return fail(VSR_ERR_UNSUPPORTED, "%s: L1 graphs are not supported", who);
+    if (ef < 1 || ef > 5000)      /* hnsw.ef_search: 1 .. HNSW_MAX_EF_SEARCH (hnsw.c:86-89, hnsw.h:44) */
+        return fail(VSR_ERR_INVALID, "%s: ef_search must be between 1 and 5000 (got %d)", who, ef);
+    return VSR_OK;
+}
+
+// per-query permission bitmaps as a device array of pointers (nullptr entries: no filter); any_filter = false: none at all
+static int hnsw_bitmaps(vsr_hnsw* h, vsr_ctx* ctx, const vsr_filter* const* filters, int n, bool& any_filter)
+{
+    any_filter = false;
+    std::vector<const uint64_t*> bms((size_t) n, nullptr);
+    int rc;
+    for (int i = 0; i < n; ++i)
+        if (filters && filters[i]) {
+            if ((rc = hnsw_filter_bitmap(h, filters[i], &bms[(size_t) i]))) return rc;
+            any_filter = true;
+        }
+    if (!any_filter) return VSR_OK;
+    if ((rc = h->d_bm.reserve((size_t) n * sizeof(uint64_t*)))) return rc;
+    if ((rc = h->h_bm.reserve((size_t) n * sizeof(uint64_t*)))) return rc;
+    memcpy(h->h_bm.p, bms.data(), (size_t) n * sizeof(uint64_t*));
+    HIPCHK(hipMemcpyAsync(h->d_bm.p, h->h_bm.p, (size_t) n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx->stream));
+    return VSR_OK;
+}
+
+// a device entry point's optional document array: the kernels always write one
+static int hnsw_doc_scratch(vsr_hnsw* h, int nq, int k, int32_t*& d_doc)
+{
+    if (d_doc) return VSR_OK;
+    int rc = h->d_out.reserve((size_t) nq * k * sizeof(int32_t));
+    if (rc) return rc;
+    d_doc = h->d_out.as<int32_t>();
+    return VSR_OK;
+}
+
+extern "C" int vsr_hnsw_search_device(vsr_hnsw* h, const float* d_queries, int nq, int dim, int k, int ef, int metric,
+                                      const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc, int64_t* d_row,
+                                      float* d_dist, int32_t* d_cnt, int64_t* d_visited)
+{
+    int rc = hnsw_check(h, d_queries, nq, dim, k, ef, metric, filters, "vsr_hnsw_search_device");
+    if (rc) return rc;
+    if (nq == 0) return VSR_OK;
+    if (!d_blk || !d_dist || !d_cnt) return fail(VSR_ERR_INVALID, "vsr_hnsw_search_device: output is NULL");
+    vsr_ctx* ctx = h->corpus->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    if ((rc = hnsw_doc_scratch(h, nq, k, d_doc))) return rc;
+    bool any_filter = false;
+    if (h->h_bm.p) HIPCHK(hipStreamSynchronize(ctx->stream));            // the pinned pointer block of the previous call
+    if ((rc = hnsw_bitmaps(h, ctx, filters, nq, any_filter))) return rc;
+    return hnsw_launch(h, ctx, d_queries, (uint32_t) dim, nq, k, ef, metric, any_filter ? h->d_bm.as<const uint64_t*>() : nullptr, false,
+                       {d_blk, d_doc, d_row, d_dist, d_cnt, nullptr}, d_visited, nullptr);
+}
+
+// The host form of a K4 search.  `launch(d_q, n, filters, tier, results, d_extra, d_status)` runs n device-resident queries
+// at re-run tier 0 or 1; the whole call is one launch and one copy back, then ONE re-run, a tier up, of the queries whose
+// status word says their first result is not valid (rare; big graphs or long scans only), patched into the caller's arrays.
+template <class Launch>
+static int hnsw_host_search(vsr_hnsw* h, const float* queries, int nq, int dim, int k, const vsr_filter* const* filters,
+                            const Outputs& out, int64_t* out_extra, Launch launch)
+{
+    vsr_ctx* ctx = h->corpus->ctx;
+    const ResultBlock rb(nq, k, true);
+    int rc;
+    if ((rc = h->d_q.reserve((size_t) nq * dim * sizeof(float)))) return rc;
+    if ((rc = h->d_out.reserve(rb.total))) return rc;
+    if ((rc = h->h_out.reserve(rb.total))) return rc;
+    char* d = h->d_out.as<char>();
+    char* hh = h->h_out.as<char>();
+    auto run = [&](const float* qs, int n, const vsr_filter* const* fs, int tier) -> int {
+        HIPCHK(hipMemcpyAsync(h->d_q.p, qs, (size_t) n * dim * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        int r = launch(h->d_q.as<float>(), n, fs, tier, rb.arrays(d), rb.column<int64_t>(d, rb.o_extra), rb.column<int32_t>(d, rb.o_status));
+        if (r) return r;
+        HIPCHK(hipMemcpyAsync(hh, d, rb.total, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return VSR_OK;
+    };
+    if ((rc = run(queries, nq, filters, 0))) return rc;
+    rb.copy_out_all(hh, out, out_extra);
+    const std::vector<int> redo = rb.flagged(hh, (size_t) nq);
+    if (redo.empty()) return VSR_OK;
+    std::vector<float> q2;
+    std::vector<const vsr_filter*> f2;
+    gather_subset(queries, dim, filters, redo, q2, f2);
+    if ((rc = run(q2.data(), (int) redo.size(), f2.data(), 1))) return rc;
+    for (size_t j = 0; j < redo.size(); ++j) rb.patch_one(hh, j, (size_t) redo[j], out, out_extra);
+    return VSR_OK;
+}
+
+extern "C" int vsr_hnsw_search(vsr_hnsw* h, const float* queries, int nq, int dim, int k, int ef, int metric,
+                               const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc, int64_t* out_row,
+                               float* out_dist, int32_t* out_cnt, int64_t* out_visited)
+{
+    int rc = hnsw_check(h, queries, nq, dim, k, ef, metric, filters, "vsr_hnsw_search");
+    if (rc) return rc;
+    if (nq == 0) return VSR_OK;
+    if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "vsr_hnsw_search: output is NULL");
+    vsr_ctx* ctx = h->corpus->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    // tier 1: queries whose LDS visited table overflowed (big graphs only) are re-run with the global bitmap
+    return hnsw_host_search(h, queries, nq, dim, k, filters, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr}, out_visited,
+                            [&](const float* d_q, int n, const vsr_filter* const* fs, int tier, const Outputs& res, int64_t* d_vis,
+                                int32_t* d_status) -> int {
+                                bool any_filter = false;
+                                int r = hnsw_bitmaps(h, ctx, fs, n, any_filter);
+                                if (r) return r;
+                                return hnsw_launch(h, ctx, d_q, (uint32_t) dim, n, k, ef, metric,
+                                                   any_filter ? h->d_bm.as<const uint64_t*>() : nullptr, tier == 1, res, d_vis, d_status);
+                            });
+}
+
+// ---- iterative index scans (hnsw.iterative_scan, hnsw.max_scan_tuples; vsr_hnsw.h's header comment) ----------------
+constexpr size_t HN_ITER_WORKSPACE = (size_t) 1 << 30;      // per launch: D + global visited bitmaps of its queries
+
+static int hnsw_iter_check(vsr_hnsw* h, const void* queries, int nq, int dim, int k, int ef, int metric,
+                           const vsr_filter* const* filters, int mode, int64_t max_scan_tuples, const char* who)
+{
+    int rc = hnsw_check(h, queries, nq, dim, k, ef, metric, filters, who);
+    if (rc) return rc;
+    if (mode < VSR_HNSW_ITERATIVE_OFF || mode > VSR_HNSW_ITERATIVE_STRICT) return fail(VSR_ERR_INVALID, "%s: iterative scan mode %d", who, mode);
+    if (max_scan_tuples < 1 || max_scan_tuples > INT_MAX)   /* hnsw.max_scan_tuples: 1 .. INT_MAX (hnsw.c:95-97) */
+        return fail(VSR_ERR_INVALID, "%s: max_scan_tuples must be between 1 and %d (got %lld)", who, INT_MAX, (long long) max_scan_tuples);
+    if (mode != VSR_HNSW_ITERATIVE_OFF && h->predicate_aware)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: iterative scans of the predicate-aware walk are not supported", who);
+    return VSR_OK;
+}
+
+// D's capacity: max_scan_tuples plus what one more round may visit beyond it (|D| <= T), at most every element.
+// VSR_HNSW_DISCARD_CAP=n (development / tests) forces n, so that the overflow re-run can be exercised on small graphs
+static uint32_t hnsw_discard_cap(const vsr_hnsw* h, int ef, int64_t max_scan_tuples)
+{
+    const int64_t slack = (int64_t) 4 * h->m * ef + 4096;    // (a round visits ~20 x ef elements at m = 16)
+    int64_t cap = std::min<int64_t>(h->n_elem, max_scan_tuples + slack);
+    if (const char* env = getenv("VSR_HNSW_DISCARD_CAP")) {
+        const long long forced = atoll(env);
+        if (forced > 0) cap = std::min<int64_t>(h->n_elem, forced);
+    }
+    return (uint32_t) std::max<int64_t>(cap, 1);
+}
+
+// the iterative kernel over queries resident on the device, one launch per chunk of queries whose workspace stays under
+// HN_ITER_WORKSPACE, on the context's stream without synchronisation
+static int hnsw_iter_run(vsr_hnsw* h, const float* d_q, int nq, int dim, int k, int ef, int metric, const vsr_filter* const* filters,
+                         int mode, int64_t max_scan_tuples, uint32_t cap_d, const Outputs& out, int64_t* d_tuples, int32_t* d_status)
+{
+    vsr_ctx* ctx = h->corpus->ctx;
+    bool any_filter = false;
+    int rc;
+    if (h->h_bm.p) HIPCHK(hipStreamSynchronize(ctx->stream));            // the pinned pointer block of the previous call
+    if ((rc = hnsw_bitmaps(h, ctx, filters, nq, any_filter))) return rc;
+    const size_t per_query = (size_t) cap_d * 8 + (((size_t) h->n_elem + 31) / 32) * 4;
+    const int chunk = (int) std::max<size_t>(1, std::min<size_t>((size_t) nq, HN_ITER_WORKSPACE / per_query));
+    const HnswIterLaunch it{mode, max_scan_tuples, cap_d};
+    for (int q0 = 0; q0 < nq; q0 += chunk) {
+        const int n = std::min(chunk, nq - q0);
+        if ((rc = hnsw_launch(h, ctx, d_q + (size_t) q0 * dim, (uint32_t) dim, n, k, ef, metric,
+                              any_filter ? h->d_bm.as<const uint64_t*>() + q0 : nullptr, false, out.from_query((size_t) q0, k),
+                              d_tuples ? d_tuples + q0 : nullptr, d_status ? d_status + q0 : nullptr, &it)))
+            return rc;
+    }
+    return VSR_OK;
+}
+
+extern "C" int vsr_hnsw_search_iterative_device(vsr_hnsw* h, const float* d_queries, int nq, int dim, int k, int ef, int metric,
+                                                const vsr_filter* const* filters, int mode, int64_t max_scan_tuples,
+                                                int64_t* d_blk, int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt,
+                                                int64_t* d_tuples)
+{
+    int rc = hnsw_iter_check(h, d_queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples, "vsr_hnsw_search_iterative_device");
+    if (rc) return rc;
+    if (mode == VSR_HNSW_ITERATIVE_OFF)
+        return vsr_hnsw_search_device(h, d_queries, nq, dim, k, ef, metric, filters, d_blk, d_doc, d_row, d_dist, d_cnt, d_tuples);
+    if (nq == 0) return VSR_OK;
+    if (!d_blk || !d_dist || !d_cnt) return fail(VSR_ERR_INVALID, "vsr_hnsw_search_iterative_device: output is NULL");
+    vsr_ctx* ctx = h->corpus->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    if ((rc = hnsw_doc_scratch(h, nq, k, d_doc))) return rc;
+    return hnsw_iter_run(h, d_queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples, hnsw_discard_cap(h, ef, max_scan_tuples),
+                         {d_blk, d_doc, d_row, d_dist, d_cnt, nullptr}, d_tuples, nullptr);
+}
+
+extern "C" int vsr_hnsw_search_iterative(vsr_hnsw* h, const float* queries, int nq, int dim, int k, int ef, int metric,
+                                         const vsr_filter* const* filters, int mode, int64_t max_scan_tuples, int64_t* out_blk,
+                                         int32_t* out_doc, int64_t* out_row, float* out_dist, int32_t* out_cnt, int64_t* out_tuples)
+{
+    int rc = hnsw_iter_check(h, queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples, "vsr_hnsw_search_iterative");
+    if (rc) return rc;
+    if (mode == VSR_HNSW_ITERATIVE_OFF)                      // hnsw.iterative_scan = off: the plain search, T = the visited count
+        return vsr_hnsw_search(h, queries, nq, dim, k, ef, metric, filters, out_blk, out_doc, out_row, out_dist, out_cnt, out_tuples);
+    if (nq == 0) return VSR_OK;
+    if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "vsr_hnsw_search_iterative: output is NULL");
+    HIPCHK(hipSetDevice(h->corpus->ctx->device));
+    // tier 1: queries whose D overflowed, again with room for every element (an element is in at most one of D, W, emitted)
+    const uint32_t cap_d[2] = {hnsw_discard_cap(h, ef, max_scan_tuples), (uint32_t) std::max(h->n_elem, 1)};
+    return hnsw_host_search(h, queries, nq, dim, k, filters, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr}, out_tuples,
+                            [&](const float* d_q, int n, const vsr_filter* const* fs, int tier, const Outputs& res, int64_t* d_tup,
+                                int32_t* d_status) -> int {
+                                return hnsw_iter_run(h, d_q, n, dim, k, ef, metric, fs, mode, max_scan_tuples, cap_d[tier], res, d_tup,
+                                                     d_status);
+                            });
+}

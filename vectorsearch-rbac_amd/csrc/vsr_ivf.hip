@@ -1,0 +1,326 @@
+// vsr_ivf.hip — K3: IVFFlat over a list-ordered view of the corpus (probe, per-list filter parts, assignment).
+#include "vsr_runtime.h"
+
+#include <cmath>
+
+// ---- K3: IVFFlat list probe (ivfscan.c:36-176, 339-389) over a list-ordered view of the corpus
+// [lists][dim] -> [dim][lists]: the layout ivf_probe_kernel reads (vsr_kernels.hip)
+static std::vector<float> transpose_centers(const float* centers, int lists, int dim)
+{
+    std::vector<float> t((size_t) lists * dim);
+    for (int c = 0; c < lists; ++c)
+        for (int j = 0; j < dim; ++j) t[(size_t) j * lists + c] = centers[(size_t) c * dim + j];
+    return t;
+}
+
+struct vsr_ivf {
+    vsr_corpus* main = nullptr;
+    vsr_corpus* view = nullptr;                      // list-ordered rows; view->base = main
+    int         lists = 0;
+    float*      d_centers = nullptr;
+    std::vector<uint32_t> list_start;                // lists + 1 offsets into the view
+    std::vector<vsr_filter*> list_filters;           // one RANGES filter per list (tiles over the view)
+    struct ViewBitmap { uint64_t* d = nullptr; std::vector<uint64_t> h; };
+    std::map<uint64_t, ViewBitmap> view_bitmaps;                          // a base filter (by vsr_filter::id) as a bitmap in view order
+    std::map<std::pair<uint64_t, int>, vsr_filter*> parts;                // (base filter id, list) -> part of a probe
+    DevBuf d_q, d_probe;
+};
+
+extern "C" int vsr_ivf_free(vsr_ivf* ivf)
+{
+    if (!ivf) return VSR_OK;
+    if (ivf->main) {
+        (void) hipSetDevice(ivf->main->ctx->device);
+        (void) hipStreamSynchronize(ivf->main->ctx->stream);
+    }
+    if (ivf->main) {
+        auto& reg = ivf->main->ivf_indexes;
+        reg.erase(std::remove(reg.begin(), reg.end(), ivf), reg.end());
+    }
+    for (auto& kv : ivf->parts) delete kv.second;    // tiles / bitmaps are borrowed
+    for (auto& kv : ivf->view_bitmaps)
+        if (kv.second.d) (void) hipFree(kv.second.d);
+    for (vsr_filter* f : ivf->list_filters) free_filter(f);
+    if (ivf->d_centers) (void) hipFree(ivf->d_centers);
+    ivf->d_q.release();
+    ivf->d_probe.release();
+    delete ivf->view;                                // frees the view's own arrays only
+    delete ivf;
+    return VSR_OK;
+}
+
+extern "C" int vsr_ivf_load(vsr_corpus* c, const float* centers, int lists, const int32_t* row_list, vsr_ivf** out)
+{
+    if (!c || !out || !centers || (c->n > 0 && !row_list)) return fail(VSR_ERR_INVALID, "vsr_ivf_load: NULL argument");
+    *out = nullptr;
+    if (c->base) return fail(VSR_ERR_INVALID, "vsr_ivf_load: the corpus is itself a view");
+    if (lists < 1 || lists > 32768)      /* reloption lists: 1 .. IVFFLAT_MAX_LISTS (ivfflat.h:42-44) */
+        return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_load: lists must be between 1 and 32768 (got %d)", lists);
+    vsr_ctx* ctx = c->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t n = c->n;
+    for (int64_t i = 0; i < n; ++i)
+        if (row_list[i] < 0 || row_list[i] >= lists) return fail(VSR_ERR_INVALID, "vsr_ivf_load: row %lld has list %d", (long long) i, row_list[i]);
+    std::unique_ptr<vsr_ivf> ivf(new vsr_ivf());
+    ivf->main = c;
+    ivf->lists = lists;
+    // view order: by list, then by base row (= (document_id, block_id) order inside a list)
+    std::vector<uint32_t> count((size_t) lists + 1, 0);
+    for (int64_t r = 0; r < n; ++r) count[(size_t) row_list[c->h_orig[(size_t) r]] + 1]++;
+    for (int l = 0; l < lists; ++l) count[(size_t) l + 1] += count[(size_t) l];
+    ivf->list_start = count;
+    std::vector<uint32_t> rank((size_t) std::max<int64_t>(n, 1));
+    {
+        std::vector<uint32_t> cur(count.begin(), count.end() - 1);
+        for (int64_t r = 0; r < n; ++r) rank[cur[(size_t) row_list[c->h_orig[(size_t) r]]]++] = (uint32_t) r;
+    }
+    std::unique_ptr<vsr_corpus> v(new vsr_corpus());
+    v->ctx = ctx;
+    v->n = n;
+    v->dim = c->dim;
+    v->stride4 = c->stride4;
+    v->row_offset = c->row_offset;
+    v->shape = c->shape;
+    v->base = c;
+    v->k2_safe = c->k2_safe;
+    const size_t alloc_rows = (size_t) std::max<int64_t>(n, 1), row_bytes = (size_t) c->stride4 * 16;
+    HIPCHK(hipMalloc(&v->d_rank, alloc_rows * sizeof(uint32_t)));
+    HIPCHK(hipMemcpy(v->d_rank, rank.data(), alloc_rows * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc(&v->d_rows, alloc_rows * row_bytes + 1024));
+    HIPCHK(hipMalloc(&v->d_norm2, alloc_rows * sizeof(float)));
+    HIPCHK(launch_gather_rows(c->d_rows, c->d_norm2, v->d_rank, (uint32_t) n, c->stride4, v->d_rows, v->d_norm2, ctx->stream));
+    if (c->d_scr) {                                  // the view's own screening planes, in its order
+        v->scr_has_mid = c->scr_has_mid;
+        v->pstride4 = c->pstride4;
+        HIPCHK(hipMalloc(&v->d_scr, alloc_rows * (size_t) v->pstride4 * 16 + 1024));
+        HIPCHK(launch_split_planes(v->d_rows, (uint32_t) n, v->stride4, v->d_scr, v->pstride4, !v->scr_has_mid, ctx->stream));
+        std::vector<uint2> all;
+        ranges_to_tiles({{0u, (uint32_t) n}}, v->shape.rw, all);
+        HIPCHK(hipMalloc(&v->d_all_tiles, std::max<size_t>(8, all.size() * sizeof(uint2))));
+        if (!all.empty()) HIPCHK(hipMemcpy(v->d_all_tiles, all.data(), all.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMalloc(&ivf->d_centers, (size_t) lists * c->dim * sizeof(float)));
+    {                                                       // transposed for the probe kernel: element j of every list contiguous
+        std::vector<float> ct = transpose_centers(centers, lists, c->dim);
+        HIPCHK(hipMemcpy(ivf->d_centers, ct.data(), ct.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ivf->view = v.release();
+    ivf->list_filters.assign((size_t) lists, nullptr);
+    for (int l = 0; l < lists; ++l) {
+        FilterPtr f = new_filter(ivf->view, VSR_FILTER_RANGES, true);
+        std::vector<uint2> tiles;
+        const uint32_t s0 = ivf->list_start[(size_t) l], s1 = ivf->list_start[(size_t) l + 1];
+        if (s1 > s0) ranges_to_tiles({{s0, s1}}, ivf->view->shape.rw, tiles);
+        int rc = upload_tiles(f.get(), tiles);
+        if (rc) { vsr_ivf_free(ivf.release()); return rc; }
+        f->allowed_rows = f->scanned_rows = s1 - s0;
+        ivf->list_filters[(size_t) l] = f.release();
+    }
+    c->ivf_indexes.push_back(ivf.get());
+    *out = ivf.release();
+    return VSR_OK;
+}
+
+void vsr::purge_ivf_caches(vsr_corpus* c, const vsr_filter* f)
+{
+    for (vsr_ivf* ivf : c->ivf_indexes) {
+        for (auto it = ivf->parts.begin(); it != ivf->parts.end();) {
+            if (!f || it->first.first == f->id) {
+                delete it->second;                           // tiles / bitmap are borrowed
+                it = ivf->parts.erase(it);
+            } else
+                ++it;
+        }
+        for (auto it = ivf->view_bitmaps.begin(); it != ivf->view_bitmaps.end();) {
+            if (!f || it->first == f->id) {
+                if (it->second.d) (void) hipFree(it->second.d);
+                it = ivf->view_bitmaps.erase(it);
+            } else
+                ++it;
+        }
+    }
+}
+
+// (base filter, list) as a filter of the view: the list's tiles and the base filter's bitmap in view order
+static int ivf_part(vsr_ivf* ivf, const vsr_filter* bf, int list, vsr_filter** out)
+{
+    if (!bf) {
+        *out = ivf->list_filters[(size_t) list];
+        return VSR_OK;
+    }
+    auto key = std::make_pair(bf->id, list);
+    auto it = ivf->parts.find(key);
+    if (it != ivf->parts.end()) {
+        *out = it->second;
+        return VSR_OK;
+    }
+    vsr_corpus* v = ivf->view;
+    vsr_ctx* ctx = v->ctx;
+    auto& vb = ivf->view_bitmaps[bf->id];
+    if (!vb.d) {
+        const size_t words = bitmap_words(v->n);
+        HIPCHK(hipMalloc(&vb.d, words * sizeof(uint64_t)));
+        HIPCHK(hipMemsetAsync(vb.d, 0, words * sizeof(uint64_t), ctx->stream));
+        HIPCHK(launch_view_bitmap(v->d_rank, (uint32_t) v->n, bf->d_tiles, bf->n_tiles, bf->d_bitmap, vb.d, ctx->stream));
+        vb.h.resize(words);
+        HIPCHK(hipMemcpyAsync(vb.h.data(), vb.d, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    const vsr_filter* lf = ivf->list_filters[(size_t) list];
+    std::unique_ptr<vsr_filter> f(new vsr_filter());
+    f->corpus = v;
+    f->mode = VSR_FILTER_BITMAP;
+    f->cached = true;
+    f->d_tiles = lf->d_tiles;
+    f->n_tiles = lf->n_tiles;
+    f->d_bitmap = vb.d;
+    f->owns_bitmap = false;
+    f->scanned_rows = lf->scanned_rows;
+    int64_t allowed = 0;
+    for (uint32_t p = ivf->list_start[(size_t) list]; p < ivf->list_start[(size_t) list + 1]; ++p)
+        allowed += (vb.h[p >> 6] >> (p & 63)) & 1ull;
+    f->allowed_rows = allowed;
+    *out = ivf->parts[key] = f.release();
+    return VSR_OK;
+}
+
+// the probe launch on device-resident queries; the probed list ids (nq x probes) back to the host, synchronised
+static int ivf_probe_lists(vsr_ivf* ivf, const float* d_queries, int nq, int dim, int probes, int metric, int32_t* out_lists)
+{
+    vsr_ctx* ctx = ivf->main->ctx;
+    int rc;
+    if ((rc = ivf->d_probe.reserve((size_t) nq * probes * sizeof(int32_t)))) return rc;
+    // cosine opclass: the caller passes normalised queries and the index distance is the negative inner product
+    // (vector.sql:323-327)
+    HIPCHK(launch_ivf_probe(d_queries, (uint32_t) dim, (uint32_t) nq, ivf->d_centers, dim, ivf->lists, probes,
+                            metric == VSR_METRIC_L2 ? M_L2 : M_IP, ivf->d_probe.as<int32_t>(), ctx->stream));
+    HIPCHK(hipMemcpyAsync(out_lists, ivf->d_probe.p, (size_t) nq * probes * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return VSR_OK;
+}
+
+// GetScanLists + the per-query filters of GetScanItems: the probe launch on device-resident queries, the probed list
+// ids back to the host (nq x probes x 4 bytes: the planner that groups queries by list is host code), one parts-only
+// filter of the view per query.
+static int ivf_plan(vsr_ivf* ivf, const float* d_queries, int nq, int dim, int probes, int metric,
+                    const vsr_filter* const* filters, std::vector<std::unique_ptr<vsr_filter>>& owned,
+                    std::vector<const vsr_filter*>& fl)
+{
+    int rc;
+    std::vector<int32_t> probe((size_t) nq * probes);
+    if ((rc = ivf_probe_lists(ivf, d_queries, nq, dim, probes, metric, probe.data()))) return rc;
+    owned.resize((size_t) nq);
+    fl.assign((size_t) nq, nullptr);
+    for (int q = 0; q < nq; ++q) {
+        std::unique_ptr<vsr_filter> f(new vsr_filter());
+        f->corpus = ivf->view;
+        f->mode = VSR_FILTER_RANGES;
+        f->parts_only = true;
+        for (int j = 0; j < probes; ++j) {
+            const int32_t l = probe[(size_t) q * probes + j];
+            if (l < 0) continue;
+            vsr_filter* part = nullptr;
+            if ((rc = ivf_part(ivf, filters ? filters[q] : nullptr, l, &part))) return rc;
+            if (part->n_tiles == 0) continue;
+            f->parts.push_back(part);
+            f->allowed_rows += part->allowed_rows;
+            f->scanned_rows += part->scanned_rows;
+        }
+        fl[(size_t) q] = f.get();
+        owned[(size_t) q] = std::move(f);
+    }
+    return VSR_OK;
+}
+
+static int ivf_check(vsr_ivf* ivf, const float* queries, int nq, int dim, int k, int& probes, int metric,
+                     const vsr_filter* const* filters, const void* o1, const void* o2, const void* o3, const char* who)
+{
+    if (!ivf) return fail(VSR_ERR_INVALID, "%s: index is NULL", who);
+    int rc = check_search_args(ivf->main, queries, nq, dim, k, metric, filters, who);
+    if (rc) return rc;
+    if (metric == VSR_METRIC_L1) return fail(VSR_ERR_UNSUPPORTED, "%s: ivfflat has no L1 operator class", who);
+    if (probes < 1) return fail(VSR_ERR_INVALID, "%s: probes must be >= 1 (got %d)", who, probes);   /* ivfflat.c:41-45 */
+    if (nq > 0 && (!o1 || !o2 || !o3)) return fail(VSR_ERR_INVALID, "%s: output is NULL", who);
+    probes = std::min(probes, ivf->lists);
+    return VSR_OK;
+}
+
+extern "C" int vsr_ivf_search(vsr_ivf* ivf, const float* queries, int nq, int dim, int k, int probes, int metric,
+                              const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc, int64_t* out_row,
+                              float* out_dist, int32_t* out_cnt)
+{
+    int rc = ivf_check(ivf, queries, nq, dim, k, probes, metric, filters, out_blk, out_dist, out_cnt, "vsr_ivf_search");
+    if (rc || nq == 0) return rc;
+    vsr_ctx* ctx = ivf->main->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    if ((rc = ivf->d_q.reserve((size_t) nq * dim * sizeof(float)))) return rc;
+    HIPCHK(hipMemcpyAsync(ivf->d_q.p, queries, (size_t) nq * dim * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    std::vector<std::unique_ptr<vsr_filter>> owned;
+    std::vector<const vsr_filter*> fl;
+    if ((rc = ivf_plan(ivf, ivf->d_q.as<float>(), nq, dim, probes, metric, filters, owned, fl))) return rc;
+    return host_search(ivf->view, queries, nq, dim, k, metric, fl.data(), {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr});
+}
+
+// The same with queries and results resident on the device.  Returns when every query is proven exact over its lists
+// (vsr_search_device_exact's contract); only the probed list ids cross PCIe.
+extern "C" int vsr_ivf_search_device(vsr_ivf* ivf, const float* d_queries, int nq, int dim, int k, int probes, int metric,
+                                     const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc, int64_t* d_row,
+                                     float* d_dist, int32_t* d_cnt)
+{
+    int rc = ivf_check(ivf, d_queries, nq, dim, k, probes, metric, filters, d_blk, d_dist, d_cnt, "vsr_ivf_search_device");
+    if (rc || nq == 0) return rc;
+    vsr_ctx* ctx = ivf->main->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    std::vector<std::unique_ptr<vsr_filter>> owned;
+    std::vector<const vsr_filter*> fl;
+    if ((rc = ivf_plan(ivf, d_queries, nq, dim, probes, metric, filters, owned, fl))) return rc;
+    return vsr_search_device_exact(nullptr, ivf->view, d_queries, nq, dim, k, metric, fl.data(), d_blk, d_doc, d_row, d_dist,
+                                   d_cnt, nullptr, nullptr);
+}
+
+extern "C" int vsr_ivf_probe(vsr_ivf* ivf, const float* queries, int nq, int dim, int probes, int metric, int32_t* out_lists)
+{
+    if (!ivf || !queries || !out_lists || nq < 0) return fail(VSR_ERR_INVALID, "vsr_ivf_probe: NULL argument");
+    if (dim != ivf->main->dim) return fail(VSR_ERR_DIM_MISMATCH, "different vector dimensions %d and %d", ivf->main->dim, dim);
+    if (probes < 1) return fail(VSR_ERR_INVALID, "vsr_ivf_probe: probes must be >= 1 (got %d)", probes);
+    if (nq == 0) return VSR_OK;
+    probes = std::min(probes, ivf->lists);
+    vsr_ctx* ctx = ivf->main->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = ivf->d_q.reserve((size_t) nq * dim * sizeof(float)))) return rc;
+    HIPCHK(hipMemcpyAsync(ivf->d_q.p, queries, (size_t) nq * dim * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    return ivf_probe_lists(ivf, ivf->d_q.as<float>(), nq, dim, probes, metric, out_lists);
+}
+
+// Index build, the part that touches every row (ivfbuild.c:141-227: InsertTuple finds the nearest list of each heap
+// row): all corpus rows against the centres, in the index's arithmetic, on the GPU.  The k-means that produces the
+// centres from the sampled rows (ivfbuild.c:404-445 ComputeCenters, ivfkmeans.c) is vsr_ivf_kmeans (vsr_kmeans.hip).
+extern "C" int vsr_ivf_assign(vsr_corpus* c, const float* centers, int lists, int metric, int32_t* out_row_list)
+{
+    if (!c || !centers || (c->n > 0 && !out_row_list)) return fail(VSR_ERR_INVALID, "vsr_ivf_assign: NULL argument");
+    if (c->base) return fail(VSR_ERR_INVALID, "vsr_ivf_assign: the corpus is a view");
+    if (lists < 1 || lists > 32768) return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_assign: lists must be between 1 and 32768 (got %d)", lists);
+    if (metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)
+        return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_assign: metric %d has no ivfflat opclass", metric);
+    vsr_ctx* ctx = c->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t n = c->n;
+    if (n == 0) return VSR_OK;
+    DevBuf d_centers, d_out;
+    int rc;
+    if ((rc = d_centers.reserve((size_t) lists * c->dim * sizeof(float)))) return rc;
+    if ((rc = d_out.reserve((size_t) n * sizeof(int32_t)))) return rc;
+    const std::vector<float> ct = transpose_centers(centers, lists, c->dim);      // (outlives the copy: synchronised below)
+    HIPCHK(hipMemcpyAsync(d_centers.p, ct.data(), ct.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    // cosine opclass: rows and centres are compared by the negative inner product (spherical k-means, vector.sql:323-327)
+    HIPCHK(launch_ivf_probe(reinterpret_cast<const float*>(c->d_rows), (uint32_t) c->stride4 * 4, (uint32_t) n,
+                            d_centers.as<float>(), c->dim, lists, 1, metric == VSR_METRIC_L2 ? M_L2 : M_IP, d_out.as<int32_t>(),
+                            ctx->stream));
+    std::vector<int32_t> by_internal((size_t) n);
+    HIPCHK(hipMemcpyAsync(by_internal.data(), d_out.p, (size_t) n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int64_t r = 0; r < n; ++r) out_row_list[c->h_orig[(size_t) r]] = by_internal[(size_t) r];     // caller's row order
+    return VSR_OK;
+}

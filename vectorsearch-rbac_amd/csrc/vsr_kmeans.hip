@@ -1,7 +1,7 @@
 // vsr_kmeans.hip — IVFFlat index build on the GPU: k-means++ seeding and Elkan's k-means over the sampled rows
 // (pgvector/src/ivfkmeans.c:21-93 InitCenters, :192-246 ComputeNewCenters, :259-498 ElkanKmeans; ivfbuild.c:404-445
 // ComputeCenters calls it on max(lists * 50, 10000) sampled rows).  The pass over every row that follows (row -> nearest
-// centre, ivfbuild.c:141-227) is vsr_ivf_assign (vsr_runtime.hip).
+// centre, ivfbuild.c:141-227) is vsr_ivf_assign (vsr_ivf.hip).
 //
 // Parity definition.  The reference's result depends on (a) its random stream (RandomDouble / RandomInt of a PostgreSQL
 // backend: not reproducible outside one; a seeded xorshift64* stands in here, the same one the CPU checker uses), (b) the
