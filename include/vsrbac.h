@@ -257,8 +257,33 @@ int vsr_hnsw_search(vsr_hnsw* index, const float* queries, int nq, int dim, int 
  * with m and ef_construction as the reloptions define them, levels from a seeded xorshift64* stream.  The
  * graph is not the serial build's graph -- neither is the reference's own parallel build's -- the guarantee is recall
  * (pgvector's test/t/012_hnsw_vector_build_recall.pl thresholds; tests/test_gpu_index.py).  Identical vectors are not merged
- * into one element (hnswbuild.c:329-351): every row is its own element.  Synchronises. */
+ * into one element (hnswbuild.c:329-351) by vsr_hnsw_build: every row is its own element (vsr_hnsw_build_ex merges them).
+ * Synchronises. */
 int vsr_hnsw_build(vsr_corpus* corpus, int m, int ef_construction, int metric, uint64_t seed, vsr_hnsw** out);
+/* vsr_hnsw_build with flags (unknown bits: VSR_ERR_INVALID).  flags = 0 is vsr_hnsw_build: the same graph for the same seed.
+ * VSR_HNSW_BUILD_MERGE_DUPLICATES folds identical rows into one element carrying up to 10 heap TIDs, as pgvector does
+ * (hnswbuild.c:309-355, called at :407).  ef_search bounds elements, not rows, so on a corpus with duplicates the merged graph
+ * returns up to 10 x ef_search rows where the unmerged one returns at most ef_search.
+ *   - Identical: the rows' dim fp32 values are byte-identical, on the rows as the corpus stores them (pgvector's
+ *     datumIsEqual: +0.0 and -0.0 differ).
+ *   - A group of g identical rows, in internal row order (the build's insertion order), becomes ceil(g / 10) elements.
+ *     Element i of the group holds members 10i .. 10i + 9 in insertion order; its vector is its first member's row.
+ *     Elements are numbered by their first member's position in insertion order.
+ *   - The level stream is drawn once per row in insertion order (pgvector draws before its duplicate check); an element takes
+ *     the level of its first row.  With the same seed, element e of the merged build is on the level the unmerged build
+ *     gives row tids[e][0].
+ *   - The grouping is exhaustive.  pgvector's is opportunistic (it compares a new element with its selected layer-0
+ *     neighbours only): the serial build can miss a merge and splits groups of more than 10 differently, so TID lists are
+ *     not comparable element by element; n_elem here <= n_elem there, and recall parity is the rest of the contract. */
+#define VSR_HNSW_BUILD_MERGE_DUPLICATES 1u
+int vsr_hnsw_build_ex(vsr_corpus* corpus, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out);
+/* The graph of any index, loaded or built, as the arrays vsr_hnsw_load takes (vsr_hnsw_load of an export answers bit for bit
+ * like the exported index).  vsr_hnsw_export_shape: what sizes them (any pointer may be NULL).  vsr_hnsw_export: host arrays
+ * level[n_elem], nbr0[n_elem][2m], tid_count[n_elem], tids[n_elem][10] (caller row indices, -1 padded), up_slot[n_elem],
+ * up_nbr[n_upper][max_level][m] (may be NULL when n_upper = 0).  Synchronises. */
+int vsr_hnsw_export_shape(const vsr_hnsw* index, int32_t* m, int32_t* n_elem, int32_t* entry, int32_t* n_upper, int32_t* max_level);
+int vsr_hnsw_export(const vsr_hnsw* index, int32_t* level, int32_t* nbr0, int32_t* tid_count, int64_t* tids, int32_t* up_slot,
+                    int32_t* up_nbr);
 int vsr_hnsw_info(const vsr_hnsw* index, int32_t* n_elem, int32_t* entry, int32_t* entry_level, int32_t* max_level);
 /* Predicate-aware walk (off by default: pgvector filters what the index returns, hnswscan.c + the executor's RLS qual).  On:
  * the layer-0 search of later vsr_hnsw_search* calls applies the query's filter while it walks, ACORN-1 style -- the result

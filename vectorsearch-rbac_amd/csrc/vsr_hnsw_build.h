@@ -7,6 +7,7 @@
 namespace vsr {
 
 constexpr int HB_NBR = 256;                // neighbour ids of one expansion / one list (2m <= 200)
+constexpr int HB_TIDS = 10;                // heap TIDs of one element (HNSW_HEAPTIDS, hnsw.h:37)
 
 struct HnswBuildParams {
     const float4*  rows = nullptr;           // corpus rows (internal order), zero padded to stride4 float4
@@ -19,6 +20,7 @@ struct HnswBuildParams {
     int32_t*       up_nbr = nullptr;         // [n_upper][max_level][m]
     float*         up_dist = nullptr;
     const int32_t* level = nullptr;          // element -> top level
+    const int32_t* elem_row = nullptr;       // element -> the row that holds its vector; nullptr: element e is row e
     int32_t        entry = -1, entry_level = -1;   // the graph's entry point when the batch begins
     uint32_t       first = 0, count = 0;     // the batch: elements first .. first + count - 1
     uint64_t*      rec_key = nullptr;        // reverse edges: (layer << 32) | target
@@ -32,8 +34,25 @@ struct HnswBuildParams {
     uint32_t*      err = nullptr;            // bit 16: a visited table filled up (the element keeps the candidates found so far)
 };
 
+// what the merging pre-pass (vsr_hnsw_dedup.hip) leaves: device arrays of n_elem entries, the caller's to hipFree
+struct HnswElemTable {
+    int32_t  n_elem = 0;
+    int32_t* elem_row = nullptr;             // the element's first member (internal row): its vector
+    int32_t* tid_count = nullptr;            // members, 1 .. HB_TIDS
+    int32_t* tids = nullptr;                 // [n_elem][HB_TIDS] internal rows in insertion order, -1 padded
+    int32_t* level = nullptr;                // the level drawn for the first member
+};
+struct HnswDedupTimes {                      // device-event times of the pre-pass's phases, summed over its rounds
+    float hash_ms = 0, sort_ms = 0, resolve_ms = 0, table_ms = 0;
+    int   rounds = 0;
+};
+
 }  // namespace vsr
 
+// byte-identical rows -> elements of up to HB_TIDS members (include/vsrbac.h, VSR_HNSW_BUILD_MERGE_DUPLICATES).  hash_bits:
+// 1 .. 64 bits of the row hash that take part; d_row_level: the level drawn for every row.  Synchronises s.
+hipError_t vsr_hnsw_dedup_elements(const float4* rows, uint32_t n, uint32_t stride4, int hash_bits, const int32_t* d_row_level,
+                                   vsr::HnswElemTable* out, vsr::HnswDedupTimes* times, hipStream_t s);
 // one batch: search + select + own lists, sort of the reverse edges, their application (all on stream s, no synchronisation)
 hipError_t vsr_hnsw_build_batch(vsr::HnswBuildParams& p, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt, uint64_t* d_val_alt,
                                 hipStream_t s);

@@ -15,8 +15,12 @@
 // another.  Elements of one batch do not see each other, so a batch is never larger than 1/8 of the graph it is inserted
 // into (the first elements go in one by one).  Levels come from the same seeded xorshift64* stream as the test suite's serial CPU restatement
 // (level = floor(-ln(u) / ln(m)), hnswutils.c:243), so both builds place the same elements on the same layers.
-// Not done: the merging of identical vectors into one element's heap TIDs (hnswbuild.c:329-351) -- every row is its own
-// element, which changes nothing a search returns.
+// Identical vectors: pgvector folds a row whose vector equals a selected layer-0 neighbour's into that element's heap TIDs
+// (up to 10, hnswbuild.c:309-355).  ef_search bounds ELEMENTS, so this changes what a search returns: on a corpus of
+// 8-fold duplicates a graph of one element per row emits at most ef_search rows where the merged graph emits 8 x as many.
+// vsr_hnsw_build keeps one element per row; vsr_hnsw_build_ex with VSR_HNSW_BUILD_MERGE_DUPLICATES runs
+// vsr_hnsw_dedup.hip's pre-pass first and the kernels below then insert ELEMENTS, reaching an element's vector through
+// HnswBuildParams::elem_row (template parameter IND; without it element e is row e and the gather is the plain one).
 //
 // Parity definition (tests/test_gpu_index.py): recall@20 at ef_search = 40 against the exact scan >= pgvector's TAP
 // thresholds on its own case (10 000 x 3-d: 0.99; inner product 0.97), and within 0.01 of that serial build's recall on
@@ -55,6 +59,14 @@ __device__ __forceinline__ int32_t* hb_list(const HnswBuildParams& p, uint32_t e
 
 // distance (the opclass's index distance: squared L2 or negative inner product) of row `a` to `cnt` elements listed in ids[]
 // -> out[]; two elements per wave instruction (32 lanes each), fp32 sums
+// the vector of element e (I: the id's own integer type, so that the direct form is the address arithmetic it always was)
+template <bool IND, class I>
+__device__ __forceinline__ const float4* hb_row(const HnswBuildParams& p, I e)
+{
+    return p.rows + (size_t) (IND ? (I) p.elem_row[e] : e) * p.stride4;
+}
+
+template <bool IND>
 __device__ __forceinline__ void hb_distances(const HnswBuildParams& p, const float4* a, const int32_t* ids, int cnt, float* out, int lane)
 {
     const int half = lane >> 5, hl = lane & 31;
@@ -65,7 +77,7 @@ __device__ __forceinline__ void hb_distances(const HnswBuildParams& p, const flo
         for (int u = 0; u < 4; ++u) {
             const int c = c0 + 2 * u + half;
             s[u] = 0.0f;
-            b[u] = p.rows + (size_t) (c < cnt ? ids[c] : ids[0]) * p.stride4;
+            b[u] = hb_row<IND>(p, c < cnt ? ids[c] : ids[0]);
         }
         for (uint32_t ch = (uint32_t) hl; ch < p.stride4; ch += 32) {
             const float4 av = a[ch];
@@ -95,6 +107,7 @@ __device__ __forceinline__ void hb_distances(const HnswBuildParams& p, const flo
 // neighbour already taken (CheckElementCloser); when fewer than lm pass, the passed-over ones fill up in order ("keep
 // pruned connections").  *pruned = index of the candidate pgvector would call pruned (only meaningful for n > lm).
 // scratch: ids[lm], nd[lm] in LDS.  Returns the number selected.
+template <bool IND>
 __device__ __forceinline__ int hb_select(const HnswBuildParams& p, const uint64_t* cand, int n, int lm, int32_t* sel, int32_t* wd,
                                          int32_t* ids, float* nd, int* pruned, int lane)
 {
@@ -111,7 +124,7 @@ __device__ __forceinline__ int hb_select(const HnswBuildParams& p, const uint64_
         const float de = mono_to_float((uint32_t) (cand[i] >> 32));
         bool closer = true;
         if (nsel > 0) {
-            hb_distances(p, p.rows + (size_t) e * p.stride4, ids, nsel, nd, lane);
+            hb_distances<IND>(p, hb_row<IND>(p, e), ids, nsel, nd, lane);
             bool bad = false;
             for (int j = lane; j < nsel; j += 64) bad |= nd[j] <= de;
             closer = __ballot(bad) == 0;
@@ -136,6 +149,7 @@ __device__ __forceinline__ int hb_select(const HnswBuildParams& p, const uint64_
 }
 
 // ---- phase 1: one wave per new element: search the frozen graph, select, write the element's own lists, emit reverse edges ----
+template <bool IND>
 __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildParams p)
 {
     extern __shared__ __align__(16) unsigned char smem_all[];
@@ -152,7 +166,7 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
     int32_t*  sel = reinterpret_cast<int32_t*>(nd + HB_NBR);                  // [HB_NBR] selected candidate indices
     int32_t*  wd = sel + HB_NBR;                                              // [caps] passed-over candidate indices
     uint32_t* lv = reinterpret_cast<uint32_t*>(wd + p.caps);                  // [hash_slots] visited set
-    const float4* q = p.rows + (size_t) me * p.stride4;
+    const float4* q = hb_row<IND>(p, me);
     const int my_level = p.level[me];
 
     // the element's own lists start empty
@@ -244,7 +258,7 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
             used += (uint32_t) cnt;
             if (used * 4u > p.hash_slots * 3u) { overflow = true; break; }
             if (cnt == 0) continue;
-            hb_distances(p, q, nb, cnt, nd, lane);
+            hb_distances<IND>(p, q, nb, cnt, nd, lane);
             for (int i = 0; i < cnt; ++i) {
                 const uint32_t e = (uint32_t) nb[i];
                 const float ed = nd[i];
@@ -263,7 +277,7 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
     // HnswFindElementNeighbors (hnswutils.c:1270-1346)
     if (lane == 0) nb[0] = p.entry;
     wave_sync();
-    hb_distances(p, q, nb, 1, nd, lane);
+    hb_distances<IND>(p, q, nb, 1, nd, lane);
     insert(make_key(nd[0], (uint32_t) p.entry));
     for (int lc = p.entry_level; lc >= my_level + 1; --lc) {
         search_layer(lc, 1);
@@ -275,7 +289,7 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
         search_layer(lc, p.efc);
         const int lm = (int) (lc == 0 ? 2 * p.m : p.m);
         int pruned;
-        const int ns = hb_select(p, S, (int) count, lm, sel, wd, nb, nd, &pruned, lane);
+        const int ns = hb_select<IND>(p, S, (int) count, lm, sel, wd, nb, nd, &pruned, lane);
         // AddConnections + the reverse edges HnswUpdateNeighborsInMemory will apply
         float* dl;
         int32_t* nl = hb_list(p, me, lc, &dl);
@@ -299,6 +313,7 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
 }
 
 // ---- phase 2: reverse edges, sorted by (layer, target): the wave of a run's first record applies the whole run ----
+template <bool IND>
 __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildParams p)
 {
     extern __shared__ __align__(16) unsigned char smem_all[];
@@ -355,7 +370,7 @@ __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildPar
         for (int j = lane; j < n; j += 64) cand[sel[j]] = mine[nm++];
         wave_sync();
         int pruned;
-        (void) hb_select(p, cand, n, lm, sel, wd, ids, nd, &pruned, lane);
+        (void) hb_select<IND>(p, cand, n, lm, sel, wd, ids, nd, &pruned, lane);
         const uint32_t pe = (uint32_t) cand[pruned];
         if (pe != e) {                                                        // the new element replaces the pruned one
             for (int j = lane; j < lm; j += 64)
@@ -370,8 +385,8 @@ __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildPar
 using namespace vsr;
 
 // host side: see vsr_hnsw_rt.hip (vsr_hnsw_build) for the batch loop; these are the two launches and the sort of a batch
-hipError_t vsr_hnsw_build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt, uint64_t* d_val_alt,
-                                hipStream_t s)
+template <bool IND>
+static hipError_t build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt, uint64_t* d_val_alt, hipStream_t s)
 {
     hipError_t e = hipMemsetAsync(p.rec_count, 0, sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
@@ -380,10 +395,10 @@ hipError_t vsr_hnsw_build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sor
     if (e != hipSuccess) return e;
     const size_t lds1 = (size_t) p.lds_per_wave * p.wpb;
     if (lds1 > 64 * 1024) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_build_search_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds1);
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_build_search_kernel<IND>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds1);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(hnsw_build_search_kernel, dim3((p.count + p.wpb - 1) / p.wpb), dim3(64 * p.wpb), lds1, s, p);
+    hipLaunchKernelGGL(hnsw_build_search_kernel<IND>, dim3((p.count + p.wpb - 1) / p.wpb), dim3(64 * p.wpb), lds1, s, p);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (p.entry < 0) return hipSuccess;                                       // the first element has nobody to link to
     hipcub::DoubleBuffer<uint64_t> keys(p.rec_key, d_key_alt), vals(p.rec_val, d_val_alt);
@@ -392,8 +407,15 @@ hipError_t vsr_hnsw_build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sor
     HnswBuildParams q = p;
     q.rec_key = keys.Current();
     q.rec_val = vals.Current();
-    hipLaunchKernelGGL(hnsw_build_link_kernel, dim3((p.rec_cap + 3) / 4), dim3(256), (size_t) 4 * HB_NBR * 32, s, q);
+    hipLaunchKernelGGL(hnsw_build_link_kernel<IND>, dim3((p.rec_cap + 3) / 4), dim3(256), (size_t) 4 * HB_NBR * 32, s, q);
     return hipGetLastError();
+}
+
+hipError_t vsr_hnsw_build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt, uint64_t* d_val_alt,
+                                hipStream_t s)
+{
+    return p.elem_row ? build_batch<true>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s)
+                      : build_batch<false>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
 }
 
 size_t vsr_hnsw_build_sort_bytes(uint32_t rec_cap)

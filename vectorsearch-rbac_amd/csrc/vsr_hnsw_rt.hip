@@ -11,7 +11,7 @@
 // ---- K4: HNSW graph search (hnswscan.c:15-45, hnswutils.c:813-976) over a graph built elsewhere
 struct vsr_hnsw {
     vsr_corpus* corpus = nullptr;
-    int32_t n_elem = 0, entry = -1, entry_level = -1, m = 0, max_level = 1;
+    int32_t n_elem = 0, entry = -1, entry_level = -1, m = 0, max_level = 1, n_upper = 0;
     int32_t *d_elem_row = nullptr, *d_level = nullptr, *d_nbr0 = nullptr, *d_up_slot = nullptr, *d_up_nbr = nullptr,
             *d_tid_count = nullptr, *d_tids = nullptr;
     std::map<uint64_t, uint64_t*> bitmaps;           // filters (by vsr_filter::id) without a full bitmap of their own, as one
@@ -68,6 +68,7 @@ extern "C" int vsr_hnsw_load(vsr_corpus* c, int m, int32_t n_elem, int32_t entry
     h->entry = n_elem > 0 ? entry : -1;
     h->m = m;
     h->max_level = max_level;
+    h->n_upper = n_upper;
     // heap TIDs arrive as caller row indices; the kernels work on internal rows
     std::vector<int32_t> inv((size_t) std::max<int64_t>(c->n, 1), -1);
     for (int64_t r = 0; r < c->n; ++r) inv[(size_t) c->h_orig[(size_t) r]] = (int32_t) r;
@@ -99,26 +100,27 @@ extern "C" int vsr_hnsw_load(vsr_corpus* c, int m, int32_t n_elem, int32_t entry
     return VSR_OK;
 }
 
-// CREATE INDEX ... USING hnsw on the GPU (vsr_hnsw_build.hip): batched insertion over the corpus's rows (element e = internal
-// row e), levels from a seeded xorshift64* stream.  Returns a loaded index, as vsr_hnsw_load would from the same graph.
-extern "C" int vsr_hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, vsr_hnsw** out)
+// CREATE INDEX ... USING hnsw on the GPU (vsr_hnsw_build.hip): batched insertion over the corpus's rows, levels from a seeded
+// xorshift64* stream drawn once per row.  flags = 0: element e = internal row e.  VSR_HNSW_BUILD_MERGE_DUPLICATES: the
+// elements come from vsr_hnsw_dedup.hip's table.  Returns a loaded index, as vsr_hnsw_load would from the same graph.
+static int hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out, const char* who)
 {
-    if (!c || !out) return fail(VSR_ERR_INVALID, "vsr_hnsw_build: NULL argument");
+    if (!c || !out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
     *out = nullptr;
-    if (c->base) return fail(VSR_ERR_INVALID, "vsr_hnsw_build: the corpus is a view");
-    if (m < 2 || m > 100) return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_build: m must be between 2 and 100 (got %d)", m);
+    if (flags & ~(uint32_t) VSR_HNSW_BUILD_MERGE_DUPLICATES) return fail(VSR_ERR_INVALID, "%s: unknown flag bits 0x%x", who, flags);
+    if (c->base) return fail(VSR_ERR_INVALID, "%s: the corpus is a view", who);
+    if (m < 2 || m > 100) return fail(VSR_ERR_UNSUPPORTED, "%s: m must be between 2 and 100 (got %d)", who, m);
     if (ef_construction < 4 || ef_construction > 1000 || ef_construction < 2 * m)      /* hnsw.c:62-63, hnswbuild.c:677-679 */
-        return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_build: ef_construction must be between 4 and 1000 and at least 2 * m (got %d)",
-                    ef_construction);
+        return fail(VSR_ERR_UNSUPPORTED, "%s: ef_construction must be between 4 and 1000 and at least 2 * m (got %d)", who, ef_construction);
     if (metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)
-        return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_build: L2, inner product and cosine operator classes only");
+        return fail(VSR_ERR_UNSUPPORTED, "%s: L2, inner product and cosine operator classes only", who);
     vsr_ctx* ctx = c->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     const int64_t n = c->n;
-    if (n > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_build: too many rows");
+    if (n > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "%s: too many rows", who);
+    const bool merge = (flags & VSR_HNSW_BUILD_MERGE_DUPLICATES) != 0 && n > 0;
     std::unique_ptr<vsr_hnsw> h(new vsr_hnsw());
     h->corpus = c;
-    h->n_elem = (int32_t) n;
     h->m = m;
     // levels: level = floor(-ln(u) * ml), ml = 1 / ln(m) (hnswutils.c:243), capped like HnswGetMaxLevel (hnsw.h:89)
     int cap = (8192 - 24 - 8 - 4 - 4) / 6 / m - 2;
@@ -133,26 +135,18 @@ extern "C" int vsr_hnsw_build(vsr_corpus* c, int m, int ef_construction, int met
     };
     (void) next();
     const double ml = 1.0 / std::log((double) m);
-    std::vector<int32_t> level((size_t) std::max<int64_t>(n, 1), 0), up_slot((size_t) std::max<int64_t>(n, 1), -1);
-    int32_t max_level = 1, n_upper = 0;
-    for (int64_t e = 0; e < n; ++e) {
+    std::vector<int32_t> level((size_t) std::max<int64_t>(n, 1), 0);         // per row, then (merging) per element
+    for (int64_t r = 0; r < n; ++r) {
         const double u = (double) (next() >> 11) * (1.0 / 9007199254740992.0);
-        int lv = (int) (-std::log(u) * ml);
-        lv = std::min(lv, cap);
-        level[(size_t) e] = lv;
-        if (lv >= 1) {
-            up_slot[(size_t) e] = n_upper++;
-            max_level = std::max(max_level, lv);
-        }
+        level[(size_t) r] = std::min((int) (-std::log(u) * ml), cap);
     }
-    h->max_level = max_level;
-    const size_t alloc = (size_t) std::max<int64_t>(n, 1);
     float *d_dist0 = nullptr, *d_up_dist = nullptr;
     uint64_t *d_key[2] = {nullptr, nullptr}, *d_val[2] = {nullptr, nullptr};
     uint32_t* d_cnt = nullptr;
     void* d_tmp = nullptr;
+    int32_t* d_row_level = nullptr;
     auto cleanup = [&]() {
-        void* ptrs[] = {d_dist0, d_up_dist, d_key[0], d_key[1], d_val[0], d_val[1], d_cnt, d_tmp};
+        void* ptrs[] = {d_dist0, d_up_dist, d_key[0], d_key[1], d_val[0], d_val[1], d_cnt, d_tmp, d_row_level};
         for (void* q : ptrs)
             if (q) (void) hipFree(q);
     };
@@ -164,16 +158,52 @@ extern "C" int vsr_hnsw_build(vsr_corpus* c, int m, int ef_construction, int met
 #define HB_CHK(call)                                                                                         \
     do {                                                                                                     \
         hipError_t e_ = (call);                                                                              \
-        if (e_ != hipSuccess) return bail(fail(VSR_ERR_HIP, "vsr_hnsw_build: %s", hipGetErrorString(e_)));   \
+        if (e_ != hipSuccess) return bail(fail(VSR_ERR_HIP, "%s: %s", who, hipGetErrorString(e_)));          \
     } while (0)
+    int64_t ne = n;                                                           // elements
+    if (merge) {
+        // development / tests: VSR_HNSW_DEDUP_HASH_BITS=b keeps the low b bits of the row hash (the collision path on a small
+        // corpus); VSR_HNSW_DEDUP_TIMING=1 prints the pre-pass's device-event times to stderr.  Both read at every call
+        int hash_bits = 64;
+        if (const char* env = getenv("VSR_HNSW_DEDUP_HASH_BITS")) hash_bits = std::max(1, std::min(64, atoi(env)));
+        const char* tenv = getenv("VSR_HNSW_DEDUP_TIMING");
+        const bool timing = tenv && atoi(tenv) > 0;
+        HnswDedupTimes times;
+        HnswElemTable t;
+        HB_CHK(hipMalloc(&d_row_level, (size_t) n * 4));
+        HB_CHK(hipMemcpyAsync(d_row_level, level.data(), (size_t) n * 4, hipMemcpyHostToDevice, ctx->stream));
+        HB_CHK(vsr_hnsw_dedup_elements(c->d_rows, (uint32_t) n, c->stride4, hash_bits, d_row_level, &t, timing ? &times : nullptr, ctx->stream));
+        h->d_elem_row = t.elem_row;
+        h->d_tid_count = t.tid_count;
+        h->d_tids = t.tids;
+        h->d_level = t.level;
+        ne = t.n_elem;
+        HB_CHK(hipMemcpy(level.data(), t.level, (size_t) ne * 4, hipMemcpyDeviceToHost));
+        if (timing)
+            fprintf(stderr, "vsr_hnsw_dedup: rows=%lld elements=%lld rounds=%d hash_ms=%.4f sort_ms=%.4f resolve_ms=%.4f table_ms=%.4f\n",
+                    (long long) n, (long long) ne, times.rounds, times.hash_ms, times.sort_ms, times.resolve_ms, times.table_ms);
+    }
+    h->n_elem = (int32_t) ne;
+    const size_t alloc = (size_t) std::max<int64_t>(ne, 1);
+    std::vector<int32_t> up_slot(alloc, -1);
+    int32_t max_level = 1, n_upper = 0;
+    for (int64_t e = 0; e < ne; ++e)
+        if (level[(size_t) e] >= 1) {
+            up_slot[(size_t) e] = n_upper++;
+            max_level = std::max(max_level, level[(size_t) e]);
+        }
+    h->max_level = max_level;
+    h->n_upper = n_upper;
     const size_t up_words = (size_t) std::max(n_upper, 1) * max_level * m;
-    HB_CHK(hipMalloc(&h->d_level, alloc * 4));
+    if (!merge) {
+        HB_CHK(hipMalloc(&h->d_level, alloc * 4));
+        HB_CHK(hipMemcpy(h->d_level, level.data(), alloc * 4, hipMemcpyHostToDevice));
+    }
     HB_CHK(hipMalloc(&h->d_up_slot, alloc * 4));
     HB_CHK(hipMalloc(&h->d_nbr0, alloc * 2 * m * 4));
     HB_CHK(hipMalloc(&h->d_up_nbr, up_words * 4));
     HB_CHK(hipMalloc(&d_dist0, alloc * 2 * m * 4));
     HB_CHK(hipMalloc(&d_up_dist, up_words * 4));
-    HB_CHK(hipMemcpy(h->d_level, level.data(), alloc * 4, hipMemcpyHostToDevice));
     HB_CHK(hipMemcpy(h->d_up_slot, up_slot.data(), alloc * 4, hipMemcpyHostToDevice));
     HB_CHK(hipMemsetAsync(h->d_nbr0, 0xFF, alloc * 2 * m * 4, ctx->stream));
     HB_CHK(hipMemsetAsync(h->d_up_nbr, 0xFF, up_words * 4, ctx->stream));
@@ -191,13 +221,14 @@ extern "C" int vsr_hnsw_build(vsr_corpus* c, int m, int ef_construction, int met
     bp.up_nbr = h->d_up_nbr;
     bp.up_dist = d_up_dist;
     bp.level = h->d_level;
+    bp.elem_row = merge ? h->d_elem_row : nullptr;
     bp.caps = (uint32_t) (ef_construction + 2 * m);
     uint32_t slots = 4096;
     while (slots < (uint32_t) ef_construction * 2u * (uint32_t) m * 2u && slots < 32768u) slots <<= 1;
     bp.hash_slots = slots;
     const size_t per = ((size_t) bp.caps * 8 + ((bp.caps + 15) & ~15u) + (size_t) HB_NBR * 12 + (size_t) bp.caps * 4 + (size_t) slots * 4 + 15) &
                        ~(size_t) 15;
-    if (per > HN_LDS_BUDGET) return bail(fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_build: ef_construction = %d with m = %d does not fit the LDS", ef_construction, m));
+    if (per > HN_LDS_BUDGET) return bail(fail(VSR_ERR_UNSUPPORTED, "%s: ef_construction = %d with m = %d does not fit the LDS", who, ef_construction, m));
     bp.lds_per_wave = (uint32_t) per;
     bp.wpb = (uint32_t) std::min<size_t>(4, HN_LDS_BUDGET / per);
     bp.err = ctx->err_word();
@@ -213,9 +244,9 @@ extern "C" int vsr_hnsw_build(vsr_corpus* c, int m, int ef_construction, int met
     bp.rec_count = d_cnt;
 
     int32_t entry = -1, entry_level = -1;
-    for (int64_t done = 0; done < n;) {
+    for (int64_t done = 0; done < ne;) {
         // a batch never exceeds 1/8 of the graph it is inserted into: its elements do not see each other
-        const int64_t b = std::max<int64_t>(1, std::min<int64_t>({done / 8, (int64_t) batch_max, n - done}));
+        const int64_t b = std::max<int64_t>(1, std::min<int64_t>({done / 8, (int64_t) batch_max, ne - done}));
         bp.entry = entry;
         bp.entry_level = entry_level;
         bp.first = (uint32_t) done;
@@ -230,26 +261,73 @@ extern "C" int vsr_hnsw_build(vsr_corpus* c, int m, int ef_construction, int met
             }
         done += b;
     }
+    HB_CHK(hipStreamSynchronize(ctx->stream));
 #undef HB_CHK
-    HIPCHK(hipStreamSynchronize(ctx->stream));
     cleanup();
-    h->entry = n > 0 ? entry : -1;
-    h->entry_level = n > 0 ? entry_level : -1;
-    // element e holds internal row e alone
-    std::vector<int32_t> erow(alloc, 0), tcount(alloc, 1), itids(alloc * 10, -1);
-    for (int64_t e = 0; e < n; ++e) {
-        erow[(size_t) e] = (int32_t) e;
-        itids[(size_t) e * 10] = (int32_t) e;
-    }
-    auto& up = upload_i32;
-    int rc;
-    if ((rc = up(&h->d_elem_row, erow.data(), alloc)) || (rc = up(&h->d_tid_count, tcount.data(), alloc)) ||
-        (rc = up(&h->d_tids, itids.data(), alloc * 10))) {
-        vsr_hnsw_free(h.release());
-        return rc;
+    h->entry = ne > 0 ? entry : -1;
+    h->entry_level = ne > 0 ? entry_level : -1;
+    if (!merge) {
+        // element e holds internal row e alone
+        std::vector<int32_t> erow(alloc, 0), tcount(alloc, 1), itids(alloc * 10, -1);
+        for (int64_t e = 0; e < n; ++e) {
+            erow[(size_t) e] = (int32_t) e;
+            itids[(size_t) e * 10] = (int32_t) e;
+        }
+        auto& up = upload_i32;
+        int rc;
+        if ((rc = up(&h->d_elem_row, erow.data(), alloc)) || (rc = up(&h->d_tid_count, tcount.data(), alloc)) ||
+            (rc = up(&h->d_tids, itids.data(), alloc * 10))) {
+            vsr_hnsw_free(h.release());
+            return rc;
+        }
     }
     c->hnsw_indexes.push_back(h.get());
     *out = h.release();
+    return VSR_OK;
+}
+
+extern "C" int vsr_hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, vsr_hnsw** out)
+{
+    return hnsw_build(c, m, ef_construction, metric, seed, 0u, out, "vsr_hnsw_build");
+}
+
+extern "C" int vsr_hnsw_build_ex(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out)
+{
+    return hnsw_build(c, m, ef_construction, metric, seed, flags, out, "vsr_hnsw_build_ex");
+}
+
+// the arrays vsr_hnsw_load takes, back from any index (loaded or built): shapes first, then the arrays into host memory
+extern "C" int vsr_hnsw_export_shape(const vsr_hnsw* h, int32_t* m, int32_t* n_elem, int32_t* entry, int32_t* n_upper, int32_t* max_level)
+{
+    if (!h) return fail(VSR_ERR_INVALID, "vsr_hnsw_export_shape: index is NULL");
+    if (m) *m = h->m;
+    if (n_elem) *n_elem = h->n_elem;
+    if (entry) *entry = h->entry;
+    if (n_upper) *n_upper = h->n_upper;
+    if (max_level) *max_level = h->max_level;
+    return VSR_OK;
+}
+
+extern "C" int vsr_hnsw_export(const vsr_hnsw* h, int32_t* level, int32_t* nbr0, int32_t* tid_count, int64_t* tids, int32_t* up_slot,
+                               int32_t* up_nbr)
+{
+    if (!h) return fail(VSR_ERR_INVALID, "vsr_hnsw_export: index is NULL");
+    if (!level || !nbr0 || !tid_count || !tids || !up_slot || (h->n_upper > 0 && !up_nbr))
+        return fail(VSR_ERR_INVALID, "vsr_hnsw_export: an output array is NULL");
+    const vsr_corpus* c = h->corpus;
+    HIPCHK(hipSetDevice(c->ctx->device));
+    HIPCHK(hipStreamSynchronize(c->ctx->stream));
+    const size_t ne = (size_t) h->n_elem;
+    if (ne == 0) return VSR_OK;
+    HIPCHK(hipMemcpy(level, h->d_level, ne * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(nbr0, h->d_nbr0, ne * 2 * h->m * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tid_count, h->d_tid_count, ne * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(up_slot, h->d_up_slot, ne * 4, hipMemcpyDeviceToHost));
+    if (h->n_upper > 0) HIPCHK(hipMemcpy(up_nbr, h->d_up_nbr, (size_t) h->n_upper * h->max_level * h->m * 4, hipMemcpyDeviceToHost));
+    std::vector<int32_t> itids(ne * 10);
+    HIPCHK(hipMemcpy(itids.data(), h->d_tids, ne * 10 * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < ne * 10; ++i)                                      // internal rows -> the caller's row indices
+        tids[i] = itids[i] >= 0 && (i % 10) < (size_t) tid_count[i / 10] ? c->h_orig[(size_t) itids[i]] : -1;
     return VSR_OK;
 }
 

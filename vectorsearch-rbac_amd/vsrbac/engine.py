@@ -10,6 +10,7 @@ from ._ffi import VsrError, check, load_library
 L2, IP, COSINE, L1 = 0, 1, 2, 3
 METRICS = {"l2": L2, "<->": L2, "ip": IP, "<#>": IP, "cosine": COSINE, "<=>": COSINE, "l1": L1, "<+>": L1}
 RANGES, BITMAP = 0, 1
+BUILD_MERGE_DUPLICATES = 1                           # VSR_HNSW_BUILD_MERGE_DUPLICATES
 
 SearchResult = namedtuple("SearchResult", "block_ids doc_ids rows dist counts")
 
@@ -300,10 +301,15 @@ class Corpus:
         row_list = self.ivf_assign(centers, metric)
         return IvfIndex(self, centers, row_list), centers, row_list
 
-    def build_hnsw(self, m=16, ef_construction=64, metric="l2", seed=1):
-        """CREATE INDEX ... USING hnsw on the GPU (vsr_hnsw_build): batched insertion, recall parity with the serial build."""
+    def build_hnsw(self, m=16, ef_construction=64, metric="l2", seed=1, merge_duplicates=False):
+        """CREATE INDEX ... USING hnsw on the GPU (vsr_hnsw_build): batched insertion, recall parity with the serial build.
+        merge_duplicates: byte-identical rows share an element of up to 10 heap TIDs, as in pgvector (vsr_hnsw_build_ex)."""
         h = C.c_void_p()
-        check(self._lib.vsr_hnsw_build(self._h, int(m), int(ef_construction), _metric(metric), int(seed), C.byref(h)))
+        if merge_duplicates:
+            check(self._lib.vsr_hnsw_build_ex(self._h, int(m), int(ef_construction), _metric(metric), int(seed),
+                                              BUILD_MERGE_DUPLICATES, C.byref(h)))
+        else:
+            check(self._lib.vsr_hnsw_build(self._h, int(m), int(ef_construction), _metric(metric), int(seed), C.byref(h)))
         return HnswIndex(self, h)
 
     def load_hnsw(self, graph):
@@ -475,6 +481,23 @@ class HnswIndex:
         v = [C.c_int32() for _ in range(4)]
         check(self._lib.vsr_hnsw_info(self._h, *[C.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
+
+    def export(self):
+        """The graph as the dict Corpus.load_hnsw takes (vsr_hnsw_export): level, nbr0 [n_elem][2m], tid_count,
+        tids [n_elem][10] (caller row indices), up_slot, up_nbr [n_upper][max_level][m], max_level, entry, m."""
+        v = [C.c_int32() for _ in range(5)]
+        check(self._lib.vsr_hnsw_export_shape(self._h, *[C.byref(x) for x in v]))
+        m, ne, entry, n_upper, max_level = (int(x.value) for x in v)
+        level = np.zeros(ne, dtype=np.int32)
+        nbr0 = np.zeros((ne, 2 * m), dtype=np.int32)
+        tid_count = np.zeros(ne, dtype=np.int32)
+        tids = np.zeros((ne, 10), dtype=np.int64)
+        up_slot = np.zeros(ne, dtype=np.int32)
+        up_nbr = np.zeros((max(n_upper, 1), max_level, m), dtype=np.int32)
+        check(self._lib.vsr_hnsw_export(self._h, _ptr(level), _ptr(nbr0), _ptr(tid_count), _ptr(tids), _ptr(up_slot),
+                                        _ptr(up_nbr)))
+        return {"level": level, "nbr0": nbr0, "tid_count": tid_count, "tids": tids, "up_slot": up_slot, "up_nbr": up_nbr,
+                "max_level": max_level, "entry": entry, "m": m}
 
     def search_device(self, d_queries, nq, k, ef_search, metric, filters, d_block, d_doc, d_rows, d_dist, d_counts,
                       d_visited=None):

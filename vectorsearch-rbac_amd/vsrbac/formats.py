@@ -198,3 +198,28 @@ def read_shared_vectors(path, mmap=True):
         raise ValueError(f"Malformed shared vector metadata: {path}.meta")
     ids = ids.reshape(n, 2)
     return rows, np.ascontiguousarray(ids[:, 0]), np.ascontiguousarray(ids[:, 1])
+
+
+# ---- an HNSW graph on disk: the dict Corpus.load_hnsw takes and HnswIndex.export returns, as one .npz ----
+_HNSW_ARRAYS = (("level", np.int32), ("nbr0", np.int32), ("tid_count", np.int32), ("tids", np.int64), ("up_slot", np.int32),
+                ("up_nbr", np.int32))
+_HNSW_SCALARS = ("max_level", "entry", "m")
+
+
+def save_hnsw(path, graph):
+    """Write an exported graph (HnswIndex.export, or any dict Corpus.load_hnsw takes) to `path` as one uncompressed .npz."""
+    fields = {name: np.ascontiguousarray(graph[name], dtype=dt) for name, dt in _HNSW_ARRAYS}
+    fields.update({name: np.asarray(int(graph[name]), dtype=np.int64) for name in _HNSW_SCALARS})
+    with open(path, "wb") as f:                         # (a file object: np.savez appends ".npz" to a bare name)
+        np.savez(f, **fields)
+
+
+def load_hnsw(path):
+    """The dict save_hnsw wrote: arrays with their dtypes and shapes, max_level / entry / m as ints."""
+    with np.load(path, allow_pickle=False) as z:
+        missing = [name for name, _ in _HNSW_ARRAYS if name not in z.files] + [name for name in _HNSW_SCALARS if name not in z.files]
+        if missing:
+            raise ValueError(f"{path}: not an HNSW graph file (missing {', '.join(missing)})")
+        graph = {name: np.ascontiguousarray(z[name], dtype=dt) for name, dt in _HNSW_ARRAYS}
+        graph.update({name: int(z[name]) for name in _HNSW_SCALARS})
+    return graph
