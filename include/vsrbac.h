@@ -229,6 +229,38 @@ int vsr_ivf_search_device(vsr_ivf* ivf, const float* d_queries, int nq, int dim,
                           const vsr_filter* const* filters,
                           int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
                           int32_t* d_out_counts);
+/* pgvector's iterative index scan for IVFFlat (ivfflat.iterative_scan = relaxed_order with ivfflat.max_probes: ivfscan.c:112-176
+ * GetScanItems, :249-272, and the refill loop of ivfflatgettuple at :375-381; GUCs ivfflat.c:20-51).  Per query:
+ *   1. List order.  P = min(probes, lists) and M = min(max(max_probes, probes), lists).  The M nearest centres are ordered
+ *      nearest first, equal distances to the lower list id (GetScanLists with so->maxProbes), in the arithmetic of
+ *      vsr_ivf_probe: the first P are exactly the lists vsr_ivf_probe(probes) returns.
+ *   2. Batches.  Batch b holds lists b*P .. min((b+1)*P, M) - 1 of that order; the last batch may be short.  A batch's rows
+ *      are ordered as vsr_ivf_search orders them: distance ascending, NaN last, then (document_id, block_id).
+ *   3. Stream.  Batch 0, then batch 1, and so on; it is NOT re-sorted across batches ("relaxed order": a later batch may
+ *      hold a nearer row).
+ *   4. Filter and stop.  The query's filter decides which rows count; the answer is the first k permitted rows of the
+ *      stream.  A batch is only begun while fewer than k have been found and lists remain; an empty batch does not stop the
+ *      scan; fewer than k rows come back only when all M lists are exhausted.
+ *   5. Prefix property.  The stream depends on neither k nor the filter's effect on the order: the answer for k1 is a
+ *      prefix of the answer for k2 > k1 (a caller that ran dry asks again for more rows and skips what it already has).
+ *   6. out_probes (may be NULL) = so->listIndex at the stop: the lists scanned, counted in whole batches.
+ * mode: VSR_IVF_ITERATIVE_OFF is vsr_ivf_search bit for bit (max_probes is ignored, as pgvector ignores it; out_probes =
+ * P); IVFFlat has no strict order; any other value is VSR_ERR_INVALID.  max_probes: 1 .. 32768 (the GUC's range), else
+ * VSR_ERR_INVALID.  Metrics, k limits, the dimension message and the L1 refusal are vsr_ivf_search's.  Entries past the
+ * count hold -1 / +Inf.  Batch 0 runs as vsr_ivf_search does; every later batch of every query runs in one further launch
+ * with nothing crossing PCIe in between.  An index whose lists x dimensions x k do not fit the launch's 160 KiB of
+ * on-chip memory (beyond ~2700 dimensions at 32768 lists) is VSR_ERR_UNSUPPORTED. */
+typedef enum { VSR_IVF_ITERATIVE_OFF = 0, VSR_IVF_ITERATIVE_RELAXED = 1 } vsr_ivf_iterative;
+int vsr_ivf_search_iterative(vsr_ivf* ivf, const float* queries, int nq, int dim, int k, int probes, int metric,
+                             const vsr_filter* const* filters, int mode, int max_probes,
+                             int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows, float* out_dist,
+                             int32_t* out_counts, int32_t* out_probes);
+/* same with queries and results resident on the device, on vsr_ivf_search_device's contract: enqueued on the corpus
+ * context's stream, returns when every query is proven exact.  d_out_doc_ids / d_out_rows / d_out_probes may be NULL. */
+int vsr_ivf_search_iterative_device(vsr_ivf* ivf, const float* d_queries, int nq, int dim, int k, int probes, int metric,
+                                    const vsr_filter* const* filters, int mode, int max_probes,
+                                    int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
+                                    int32_t* d_out_counts, int32_t* d_out_probes);
 
 /* ---- HNSW graph search (pgvector/src/hnswscan.c:15-45,179-316; hnswutils.c:813-976) -------------------------- */
 /* A graph as pgvector's in-memory build leaves it (hnswbuild.c:357-470): n_elem elements, each with a top level, up to 10

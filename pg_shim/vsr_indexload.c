@@ -11,7 +11,7 @@
  *            -> centres + row -> list map -> vsr_ivf_load; the scan is vsr_ivf_search
  *
  * With hnsw.iterative_scan = relaxed_order | strict_order the in-process hnsw scan is pgvector's iterative scan,
- * vsr_hnsw_search_iterative (VsrRunHnswIterative below).
+ * vsr_hnsw_search_iterative (VsrRunHnswIterative below); ivfflat's through vsr_ivf_search_iterative (VsrRunIvfIterative).
  *
  * Like the rest of pg_shim/ this file is written against postgres.h + pgvector's headers and is NOT compiled in the
  * authoring image.  The arrays it builds are exactly what tests/test_gpu_index.py feeds the same entry points from the
@@ -458,6 +458,53 @@ VsrRunHnswIterative(IndexScanDesc scan, VsrPgScanOpaque so, int k)
 	VsrCheck(vsr_hnsw_search_iterative(pc->graph, q->x, 1, q->dim, k, hnsw_ef_search, VsrMetricOf(scan->indexRelation),
 									   filter ? &filter : NULL, mode, hnsw_max_scan_tuples, blk, NULL, rowidx, dist, &count,
 									   NULL));
+	so->result_tids = palloc(sizeof(ItemPointerData) * Max(count, 1));
+	for (int i = 0; i < count; i++)
+		so->result_tids[i] = pc->tids[rowidx[i]];
+	so->nresults = count;
+	so->next = 0;
+	so->iter_k = k;
+	MemoryContextSwitchTo(old);
+	return true;
+}
+
+/*
+ * ivfflat.iterative_scan = relaxed_order on the in-process index-faithful path: the first k rows of the query's stream under
+ * vsr_ivf_search_iterative (ivfscan.c:112-176, 375-381 with ivfflat.max_probes): batches of `probes` lists, nearest lists
+ * first, each batch sorted, the stream not re-sorted across batches.  The stream depends on neither k nor the filter, so a
+ * caller that needs more rows asks again with a larger k and skips what it handed out: the answer for k is a prefix of
+ * the answer for 2k.  false: not this path (the sidecar, an empty index); the caller keeps its ordinary search.
+ */
+bool
+VsrRunIvfIterative(IndexScanDesc scan, VsrPgScanOpaque so, int k, int probes, int max_probes)
+{
+	VsrPgCorpus *pc = so->pc;
+	MemoryContext old;
+	Vector	   *q;
+	const vsr_filter *filter;
+	int64	   *blk,
+			   *rowidx;
+	float	   *dist;
+	int32		count = 0;
+
+	if (pc->sc_handle != 0)
+		return false;
+	if (scan->orderByData == NULL)
+		elog(ERROR, "cannot scan ivfflat index without order");
+	if (pc->ivf == NULL)
+		pc->ivf = VsrLoadIvfLists(scan->indexRelation, pc);
+	if (pc->ivf == NULL)
+		return false;
+	old = MemoryContextSwitchTo(so->tmpCtx);
+	q = DatumGetVector(scan->orderByData->sk_argument);
+	filter = VsrFilterForCurrentUser(pc);
+	k = Max(1, Min(k, VSR_MAX_K));
+	blk = palloc(sizeof(int64) * k);
+	rowidx = palloc(sizeof(int64) * k);
+	dist = palloc(sizeof(float) * k);
+	VsrCheck(vsr_ivf_search_iterative(pc->ivf, q->x, 1, q->dim, k, probes, VsrMetricOf(scan->indexRelation),
+									  filter ? &filter : NULL, VSR_IVF_ITERATIVE_RELAXED, max_probes, blk, NULL, rowidx, dist,
+									  &count, NULL));
 	so->result_tids = palloc(sizeof(ItemPointerData) * Max(count, 1));
 	for (int i = 0; i < count; i++)
 		so->result_tids[i] = pc->tids[rowidx[i]];

@@ -100,5 +100,6 @@ extern vsr_hnsw *VsrLoadHnswGraph(Relation index, VsrPgCorpus * pc);	/* index pa
 extern vsr_ivf *VsrLoadIvfLists(Relation index, VsrPgCorpus * pc);	/* list pages -> vsr_ivf_load */
 extern void VsrRunIndexSearch(IndexScanDesc scan, VsrPgScanOpaque so, bool is_hnsw, int ef_or_probes);
 extern bool VsrRunHnswIterative(IndexScanDesc scan, VsrPgScanOpaque so, int k);	/* pgvector's iterative scan, first k rows */
+extern bool VsrRunIvfIterative(IndexScanDesc scan, VsrPgScanOpaque so, int k, int probes, int max_probes);	/* the same for ivfflat */
 
 #endif							/* VSR_PG_H */

@@ -1,7 +1,25 @@
 // vsr_ivf.hip — K3: IVFFlat over a list-ordered view of the corpus (probe, per-list filter parts, assignment).
 #include "vsr_runtime.h"
+#include "vsr_ivf_iter.h"
 
 #include <cmath>
+
+namespace vsr {
+hipError_t launch_ivf_iterative(const IvfIterParams& p, uint32_t nq, hipStream_t s)
+{
+    if (nq == 0) return hipSuccess;
+    const size_t lds = ivf_iter_lds_bytes(p.lists, p.stride4, p.k);
+    // 160 KiB of LDS per CU; view rows are addressed in 32 bits with a step of 256 to spare
+    if (lds > 160 * 1024 || p.k < 1 || p.k > (uint32_t) MAX_K || p.n_rows > 0xFFFFFE00u) return hipErrorInvalidValue;
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_iterative_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(ivf_iterative_kernel, dim3(nq), dim3(256), lds, s, p);
+    return hipGetLastError();
+}
+}  // namespace vsr
 
 // ---- K3: IVFFlat list probe (ivfscan.c:36-176, 339-389) over a list-ordered view of the corpus
 // [lists][dim] -> [dim][lists]: the layout ivf_probe_kernel reads (vsr_kernels.hip)
@@ -24,6 +42,9 @@ struct vsr_ivf {
     std::map<uint64_t, ViewBitmap> view_bitmaps;                          // a base filter (by vsr_filter::id) as a bitmap in view order
     std::map<std::pair<uint64_t, int>, vsr_filter*> parts;                // (base filter id, list) -> part of a probe
     DevBuf d_q, d_probe;
+    uint32_t* d_list_start = nullptr;                // list_start on the device (the iterative scan walks lists there)
+    PinBuf h_vb;                                     // iterative scan: per query, its view bitmap's device address
+    DevBuf d_res;                                    // iterative scan, host form: the results before they go back
 };
 
 extern "C" int vsr_ivf_free(vsr_ivf* ivf)
@@ -42,6 +63,9 @@ extern "C" int vsr_ivf_free(vsr_ivf* ivf)
         if (kv.second.d) (void) hipFree(kv.second.d);
     for (vsr_filter* f : ivf->list_filters) free_filter(f);
     if (ivf->d_centers) (void) hipFree(ivf->d_centers);
+    if (ivf->d_list_start) (void) hipFree(ivf->d_list_start);
+    ivf->h_vb.release();
+    ivf->d_res.release();
     ivf->d_q.release();
     ivf->d_probe.release();
     delete ivf->view;                                // frees the view's own arrays only
@@ -104,6 +128,8 @@ extern "C" int vsr_ivf_load(vsr_corpus* c, const float* centers, int lists, cons
         std::vector<float> ct = transpose_centers(centers, lists, c->dim);
         HIPCHK(hipMemcpy(ivf->d_centers, ct.data(), ct.size() * sizeof(float), hipMemcpyHostToDevice));
     }
+    HIPCHK(hipMalloc(&ivf->d_list_start, ((size_t) lists + 1) * sizeof(uint32_t)));
+    HIPCHK(hipMemcpy(ivf->d_list_start, ivf->list_start.data(), ((size_t) lists + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ivf->view = v.release();
     ivf->list_filters.assign((size_t) lists, nullptr);
@@ -142,6 +168,25 @@ void vsr::purge_ivf_caches(vsr_corpus* c, const vsr_filter* f)
     }
 }
 
+// a filter of the base corpus as permission bits in view order (device and host copies), built on first use
+static int ivf_view_bitmap(vsr_ivf* ivf, const vsr_filter* bf, vsr_ivf::ViewBitmap** out)
+{
+    vsr_corpus* v = ivf->view;
+    vsr_ctx* ctx = v->ctx;
+    auto& vb = ivf->view_bitmaps[bf->id];
+    if (!vb.d) {
+        const size_t words = bitmap_words(v->n);
+        HIPCHK(hipMalloc(&vb.d, words * sizeof(uint64_t)));
+        HIPCHK(hipMemsetAsync(vb.d, 0, words * sizeof(uint64_t), ctx->stream));
+        HIPCHK(launch_view_bitmap(v->d_rank, (uint32_t) v->n, bf->d_tiles, bf->n_tiles, bf->d_bitmap, vb.d, ctx->stream));
+        vb.h.resize(words);
+        HIPCHK(hipMemcpyAsync(vb.h.data(), vb.d, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    *out = &vb;
+    return VSR_OK;
+}
+
 // (base filter, list) as a filter of the view: the list's tiles and the base filter's bitmap in view order
 static int ivf_part(vsr_ivf* ivf, const vsr_filter* bf, int list, vsr_filter** out)
 {
@@ -156,17 +201,10 @@ static int ivf_part(vsr_ivf* ivf, const vsr_filter* bf, int list, vsr_filter** o
         return VSR_OK;
     }
     vsr_corpus* v = ivf->view;
-    vsr_ctx* ctx = v->ctx;
-    auto& vb = ivf->view_bitmaps[bf->id];
-    if (!vb.d) {
-        const size_t words = bitmap_words(v->n);
-        HIPCHK(hipMalloc(&vb.d, words * sizeof(uint64_t)));
-        HIPCHK(hipMemsetAsync(vb.d, 0, words * sizeof(uint64_t), ctx->stream));
-        HIPCHK(launch_view_bitmap(v->d_rank, (uint32_t) v->n, bf->d_tiles, bf->n_tiles, bf->d_bitmap, vb.d, ctx->stream));
-        vb.h.resize(words);
-        HIPCHK(hipMemcpyAsync(vb.h.data(), vb.d, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-    }
+    vsr_ivf::ViewBitmap* vbp = nullptr;
+    int rc = ivf_view_bitmap(ivf, bf, &vbp);
+    if (rc) return rc;
+    vsr_ivf::ViewBitmap& vb = *vbp;
     const vsr_filter* lf = ivf->list_filters[(size_t) list];
     std::unique_ptr<vsr_filter> f(new vsr_filter());
     f->corpus = v;
@@ -246,6 +284,20 @@ static int ivf_check(vsr_ivf* ivf, const float* queries, int nq, int dim, int k,
     return VSR_OK;
 }
 
+// ... and the two arguments of the iterative form (GUC ranges: ivfflat.c:20-51)
+static int ivf_check(vsr_ivf* ivf, const float* queries, int nq, int dim, int k, int& probes, int metric,
+                     const vsr_filter* const* filters, int mode, int max_probes, const void* o1, const void* o2, const void* o3,
+                     const char* who)
+{
+    int rc = ivf_check(ivf, queries, nq, dim, k, probes, metric, filters, o1, o2, o3, who);
+    if (rc) return rc;
+    if (mode != VSR_IVF_ITERATIVE_OFF && mode != VSR_IVF_ITERATIVE_RELAXED)
+        return fail(VSR_ERR_INVALID, "%s: iterative scan mode %d (ivfflat has off and relaxed_order)", who, mode);
+    if (max_probes < 1 || max_probes > 32768)
+        return fail(VSR_ERR_INVALID, "%s: max_probes must be between 1 and 32768 (got %d)", who, max_probes);
+    return VSR_OK;
+}
+
 extern "C" int vsr_ivf_search(vsr_ivf* ivf, const float* queries, int nq, int dim, int k, int probes, int metric,
                               const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc, int64_t* out_row,
                               float* out_dist, int32_t* out_cnt)
@@ -277,6 +329,110 @@ extern "C" int vsr_ivf_search_device(vsr_ivf* ivf, const float* d_queries, int n
     if ((rc = ivf_plan(ivf, d_queries, nq, dim, probes, metric, filters, owned, fl))) return rc;
     return vsr_search_device_exact(nullptr, ivf->view, d_queries, nq, dim, k, metric, fl.data(), d_blk, d_doc, d_row, d_dist,
                                    d_cnt, nullptr, nullptr);
+}
+
+// ---- iterative index scans (ivfflat.iterative_scan = relaxed_order, ivfflat.max_probes) ----
+static int fill_probes(vsr_ctx* ctx, int32_t* d_probes, int nq, int value)
+{
+    if (d_probes) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_probes), value, (size_t) nq, ctx->stream));
+    return VSR_OK;
+}
+
+extern "C" int vsr_ivf_search_iterative_device(vsr_ivf* ivf, const float* d_queries, int nq, int dim, int k, int probes,
+                                               int metric, const vsr_filter* const* filters, int mode, int max_probes,
+                                               int64_t* d_blk, int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt,
+                                               int32_t* d_probes)
+{
+    int rc = ivf_check(ivf, d_queries, nq, dim, k, probes, metric, filters, mode, max_probes, d_blk, d_dist, d_cnt,
+                       "vsr_ivf_search_iterative_device");
+    if (rc || nq == 0) return rc;
+    vsr_ctx* ctx = ivf->main->ctx;
+    vsr_corpus* v = ivf->view;
+    HIPCHK(hipSetDevice(ctx->device));
+    // batch 0 = the scan without iteration: the shared matrix-core passes over the `probes` nearest lists, outputs written
+    std::vector<std::unique_ptr<vsr_filter>> owned;
+    std::vector<const vsr_filter*> fl;
+    if ((rc = ivf_plan(ivf, d_queries, nq, dim, probes, metric, filters, owned, fl))) return rc;
+    if ((rc = vsr_search_device_exact(nullptr, v, d_queries, nq, dim, k, metric, fl.data(), d_blk, d_doc, d_row, d_dist, d_cnt,
+                                      nullptr, nullptr)))
+        return rc;
+    const int max_lists = std::min(std::max(max_probes, probes), ivf->lists);
+    if (mode == VSR_IVF_ITERATIVE_OFF || max_lists <= probes) {            // pgvector ignores max_probes when the scan is off
+        if ((rc = fill_probes(ctx, d_probes, nq, probes))) return rc;
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return VSR_OK;
+    }
+    // every later batch in one launch; nothing comes back to the host in between.  Per query the address of its
+    // permission bits in view order (the bitmap exists even when batch 0's lists were all empty)
+    if ((rc = ivf->h_vb.reserve((size_t) nq * sizeof(uint64_t*)))) return rc;
+    const uint64_t** vbs = ivf->h_vb.as<const uint64_t*>();
+    for (int q = 0; q < nq; ++q) {
+        vbs[q] = nullptr;
+        if (filters && filters[q]) {
+            vsr_ivf::ViewBitmap* vb = nullptr;
+            if ((rc = ivf_view_bitmap(ivf, filters[q], &vb))) return rc;
+            vbs[q] = vb->d;
+        }
+    }
+    IvfIterParams p{};
+    p.queries = d_queries;
+    p.q_stride = (uint32_t) dim;
+    p.dim = (uint32_t) dim;
+    p.centers_t = ivf->d_centers;
+    p.lists = (uint32_t) ivf->lists;
+    p.center_metric = metric == VSR_METRIC_L2 ? M_L2 : M_IP;              // as the probe: cosine opclass = negative inner product
+    p.metric = metric;
+    p.probes = (uint32_t) probes;
+    p.max_lists = (uint32_t) max_lists;
+    p.k = (uint32_t) k;
+    p.list_start = ivf->d_list_start;
+    p.rows = v->d_rows;
+    p.stride4 = v->stride4;
+    p.n_rows = (uint32_t) v->n;
+    p.rank = v->d_rank;
+    p.bitmaps = reinterpret_cast<const uint64_t* const*>(ivf->h_vb.dp);
+    set_results(p, ivf->main, Outputs{d_blk, d_doc, d_row, d_dist, d_cnt, nullptr});
+    p.out_probes = d_probes;
+    hipError_t e = launch_ivf_iterative(p, (uint32_t) nq, ctx->stream);
+    if (e == hipErrorInvalidValue)
+        return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_search_iterative: %d lists x %d dimensions x k = %d need more than the 160 KiB of LDS",
+                    ivf->lists, dim, k);
+    HIPCHK(e);
+    HIPCHK(hipStreamSynchronize(ctx->stream));                             // (h_vb is reused by the next call)
+    return VSR_OK;
+}
+
+extern "C" int vsr_ivf_search_iterative(vsr_ivf* ivf, const float* queries, int nq, int dim, int k, int probes, int metric,
+                                        const vsr_filter* const* filters, int mode, int max_probes, int64_t* out_blk,
+                                        int32_t* out_doc, int64_t* out_row, float* out_dist, int32_t* out_cnt, int32_t* out_probes)
+{
+    int rc = ivf_check(ivf, queries, nq, dim, k, probes, metric, filters, mode, max_probes, out_blk, out_dist, out_cnt,
+                       "vsr_ivf_search_iterative");
+    if (rc || nq == 0) return rc;
+    if (mode == VSR_IVF_ITERATIVE_OFF || std::min(std::max(max_probes, probes), ivf->lists) <= probes) {
+        if ((rc = vsr_ivf_search(ivf, queries, nq, dim, k, probes, metric, filters, out_blk, out_doc, out_row, out_dist, out_cnt)))
+            return rc;
+        if (out_probes) std::fill(out_probes, out_probes + nq, (int32_t) probes);
+        return VSR_OK;
+    }
+    vsr_ctx* ctx = ivf->main->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    // queries up, the device form, results down
+    const ResultBlock rb(nq, k, true);                                     // (extra column: the lists scanned)
+    if ((rc = ivf->d_q.reserve((size_t) nq * dim * sizeof(float)))) return rc;
+    if ((rc = ivf->d_res.reserve(rb.total))) return rc;
+    HIPCHK(hipMemcpyAsync(ivf->d_q.p, queries, (size_t) nq * dim * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    char* d = ivf->d_res.as<char>();
+    const Outputs o = rb.arrays(d);
+    int32_t* d_probes = rb.column<int32_t>(d, rb.o_extra);
+    if ((rc = vsr_ivf_search_iterative_device(ivf, ivf->d_q.as<float>(), nq, dim, k, probes, metric, filters, mode, max_probes, o.blk,
+                                              o.doc, o.row, o.dist, o.cnt, d_probes)))
+        return rc;
+    std::vector<char> h(rb.o_status);
+    HIPCHK(hipMemcpy(h.data(), d, rb.o_status, hipMemcpyDeviceToHost));
+    rb.copy_out_all(h.data(), {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr}, nullptr);
+    if (out_probes) memcpy(out_probes, rb.column<int32_t>(h.data(), rb.o_extra), (size_t) nq * sizeof(int32_t));
+    return VSR_OK;
 }
 
 extern "C" int vsr_ivf_probe(vsr_ivf* ivf, const float* queries, int nq, int dim, int probes, int metric, int32_t* out_lists)

@@ -2,6 +2,7 @@
 #include <algorithm>
 #include "vsr_device.h"
 #include "vsr_topk.h"
+#include "vsr_exact.h"
 
 namespace vsr {
 
@@ -135,12 +136,7 @@ hipError_t launch_scan(const ScanParams& p, int metric, int dim, int qi, uint32_
 // Replaces the executor's top-N sort / the client-side merge of
 // controller/dynamic_partition/search.py:347-364 (no dedup needed: a row is scanned once).
 // -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float output_distance(int metric, float v)
-{
-    // L2 ranks by the fp32 sum; the operator value is sqrt((double) sum), vector.c:577
-    return metric == M_L2 ? (float) sqrt((double) v) : v;
-}
-
+// (output_distance: vsr_exact.h)
 // What a finished selection (count keys, ascending, in `keys`) turns into: a seed threshold, a partial list for the
 // next stage (level-2 K5 / K5r), or the caller's output rows.  Run by NT cooperating threads (a workgroup or a wave).
 template <int NT>
@@ -929,14 +925,7 @@ __device__ __forceinline__ void rerank_body(const RerankParams& p, uint32_t slot
     const uint32_t out_slot = p.queries[slot].out_slot;
     const float4* q = reinterpret_cast<const float4*>(p.queries_f) + (size_t) slot * p.stride4;
 
-    float qn_part = 0.0f;
-    for (uint32_t c = lane; c < p.stride4; c += 64) {
-        const float4 v = q[c];
-        qn_part = fmaf(v.x, v.x, qn_part); qn_part = fmaf(v.y, v.y, qn_part);
-        qn_part = fmaf(v.z, v.z, qn_part); qn_part = fmaf(v.w, v.w, qn_part);
-    }
-    for (int m = 32; m >= 1; m >>= 1) qn_part += __shfl_xor(qn_part, m);
-    const float qn = qn_part;
+    const float qn = wave_query_norm2(q, p.stride4, lane);
 
     // half a wave per candidate (32 lanes x float4 = 128 floats per step), U candidates per half-wave in flight:
     // 2U independent row gathers per wave hide the HBM/L2 latency of these scattered 512-byte reads.  The exact keys
@@ -947,53 +936,20 @@ __device__ __forceinline__ void rerank_body(const RerankParams& p, uint32_t slot
     // recompute and no gap to prove: the kp = k smallest screening keys are the answer)
     for (uint32_t c0 = p.exact_screen ? np2 : (uint32_t) wave * 2 * U; c0 < np2; c0 += 4 * 2 * U) {
         uint64_t sk[U];
+        uint32_t row[U];
         float s[U], nx[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) s[u] = nx[u] = 0.f;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t c = c0 + 2 * u + half;
             sk[u] = c < np2 ? keys[c] : KEY_EMPTY;
+            row[u] = sk[u] == KEY_EMPTY ? 0u : (uint32_t) sk[u];           // an empty slot reads row 0 and is dropped below
         }
-        for (uint32_t ch = hl; ch < p.stride4; ch += 32) {
-            const float4 b = q[ch];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                // no branch around the gather (an empty slot reads row 0 and is dropped below): the U loads of a half-
-                // wave must all be in flight before the first FMA waits
-                const f32x4 av = *reinterpret_cast<const f32x4*>(p.rows + (size_t) (sk[u] == KEY_EMPTY ? 0u : (uint32_t) sk[u]) * p.stride4 + ch);
-                const float4 a = make_float4(av[0], av[1], av[2], av[3]);
-                if (p.metric == M_L2) {
-                    const float d0 = a.x - b.x, d1 = a.y - b.y, d2 = a.z - b.z, d3 = a.w - b.w;
-                    s[u] = fmaf(d0, d0, s[u]); s[u] = fmaf(d1, d1, s[u]); s[u] = fmaf(d2, d2, s[u]); s[u] = fmaf(d3, d3, s[u]);
-                } else {
-                    s[u] = fmaf(a.x, b.x, s[u]); s[u] = fmaf(a.y, b.y, s[u]); s[u] = fmaf(a.z, b.z, s[u]); s[u] = fmaf(a.w, b.w, s[u]);
-                    if (p.metric == M_COSINE) {
-                        nx[u] = fmaf(a.x, a.x, nx[u]); nx[u] = fmaf(a.y, a.y, nx[u]);
-                        nx[u] = fmaf(a.z, a.z, nx[u]); nx[u] = fmaf(a.w, a.w, nx[u]);
-                    }
-                }
-            }
-        }
+        halfwave_row_sums<U>(p.rows, p.stride4, q, p.metric, row, hl, s, nx);     // the operator arithmetic: vsr_exact.h
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            for (int m = 16; m >= 1; m >>= 1) {                            // within the half-wave
-                s[u] += __shfl_xor(s[u], m);
-                nx[u] += __shfl_xor(nx[u], m);
-            }
             const uint32_t c = c0 + 2 * u + half;
             uint64_t out = KEY_EMPTY;
-            if (sk[u] != KEY_EMPTY) {
-                float v;
-                if (p.metric == M_L2) v = s[u];
-                else if (p.metric == M_IP) v = -s[u];
-                else {
-                    double sim = (double) s[u] / sqrt((double) nx[u] * (double) qn);
-                    if (sim > 1.0) sim = 1.0; else if (sim < -1.0) sim = -1.0;
-                    v = (float) (1.0 - sim);
-                }
-                out = make_key(v, (uint32_t) sk[u]);
-            }
+            if (sk[u] != KEY_EMPTY) out = make_key(exact_rank_value(p.metric, s[u], nx[u], qn), (uint32_t) sk[u]);
             if (hl == 0 && c < np2) keys[c] = out;
         }
     }
@@ -1178,13 +1134,16 @@ __global__ __launch_bounds__(256) void view_bitmap_kernel(const uint32_t* rank, 
     bool ok = p < n_rows;
     if (ok) {
         const uint32_t r = rank ? rank[p] : p;            // no rank map: the base corpus itself
-        if (tiles) {
+        // every filter carries a tile list; an empty one (a user without any permitted row: no list is allocated, the
+        // pointer is null) permits nothing
+        ok = n_tiles > 0 && tiles;
+        if (ok) {
             uint32_t lo = 0, hi = n_tiles;                   // last tile with start <= r
             while (hi - lo > 1) {
                 const uint32_t mid = (lo + hi) >> 1;
                 if (tiles[mid].x <= r) lo = mid; else hi = mid;
             }
-            ok = n_tiles > 0 && tiles[lo].x <= r && r - tiles[lo].x < tiles[lo].y;
+            ok = tiles[lo].x <= r && r - tiles[lo].x < tiles[lo].y;
         }
         if (ok && bitmap) ok = (bitmap[r >> 6] >> (r & 63)) & 1ull;
     }
@@ -1211,47 +1170,16 @@ __global__ __launch_bounds__(256) void ivf_probe_kernel(const float* queries, ui
     extern __shared__ __align__(16) unsigned char smem[];
     uint32_t* keys = reinterpret_cast<uint32_t*>(smem);     // [lists]; 0xFFFFFFFF = taken (above the canonical NaN's image)
     __shared__ uint64_t s_best[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const float* q = queries + (size_t) blockIdx.x * q_stride;         // (corpus rows as queries: the index build's assignment)
     // centers_t[j][c]: the centres TRANSPOSED (element j of all lists contiguous), so that the 64 lanes of a wave -- one centre
     // each -- read 256 contiguous bytes per element instead of 64 lines 4 * dim bytes apart; every lane still adds its own
     // centre's terms in element order (the reference's loop), and q[j] is one broadcast load
-    for (int c = tid; c < lists; c += 256) {
-        const float* x = centers_t + c;
-        float sum = 0.0f;
-        if (metric == M_L2) {
-            for (int j = 0; j < dim; ++j) {
-                const float d = __fsub_rn(x[(size_t) j * lists], q[j]);
-                sum = __fadd_rn(sum, __fmul_rn(d, d));
-            }
-        } else {
-            for (int j = 0; j < dim; ++j) sum = __fadd_rn(sum, __fmul_rn(x[(size_t) j * lists], q[j]));
-            sum = -sum;
-        }
-        keys[c] = mono_bits(sum);
-    }
+    for (int c = tid; c < lists; c += 256) keys[c] = ivf_center_key(centers_t, lists, dim, c, q, metric);    // vsr_exact.h
     __syncthreads();
     for (int pr = 0; pr < probes; ++pr) {
-        uint64_t best = KEY_EMPTY;
-        for (int c = tid; c < lists; c += 256) {
-            const uint32_t kc = keys[c];
-            const uint64_t cand = kc == 0xFFFFFFFFu ? KEY_EMPTY : (((uint64_t) kc << 32) | (uint32_t) c);
-            best = cand < best ? cand : best;
-        }
-        for (int m = 32; m >= 1; m >>= 1) {
-            const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) best, m), hi = (uint32_t) __shfl_xor((int) (uint32_t) (best >> 32), m);
-            const uint64_t o = ((uint64_t) hi << 32) | lo;
-            best = o < best ? o : best;
-        }
-        if (lane == 0) s_best[wave] = best;
-        __syncthreads();
-        uint64_t b = s_best[0];
-        for (int w = 1; w < 4; ++w) b = s_best[w] < b ? s_best[w] : b;
-        if (tid == 0) {
-            out[(size_t) blockIdx.x * probes + pr] = b == KEY_EMPTY ? -1 : (int32_t) (uint32_t) b;
-            if (b != KEY_EMPTY) keys[(uint32_t) b] = 0xFFFFFFFFu;
-        }
-        __syncthreads();
+        const uint64_t b = ivf_extract_nearest(keys, lists, s_best, tid);
+        if (tid == 0) out[(size_t) blockIdx.x * probes + pr] = b == KEY_EMPTY ? -1 : (int32_t) (uint32_t) b;
     }
 }
 

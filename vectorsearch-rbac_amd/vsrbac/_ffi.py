@@ -64,6 +64,8 @@ SYMBOLS = {
     "vsr_ivf_probe": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "vsr_ivf_search": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_ivf_search_device": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_ivf_search_iterative": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_ivf_search_iterative_device": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_hnsw_load": (_i, [_vp, _i, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(_vp)]),
     "vsr_hnsw_free": (_i, [_vp]),
     "vsr_hnsw_search": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

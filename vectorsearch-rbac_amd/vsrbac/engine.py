@@ -31,6 +31,18 @@ def _iterative_mode(m):
     return int(m)
 
 
+# ivfflat.iterative_scan's values (ivfflat.c:20-30) -> vsr_ivf_iterative; IVFFlat has no strict order
+IVF_ITERATIVE_MODES = {"off": 0, "relaxed_order": 1}
+
+
+def _ivf_iterative_mode(m):
+    if isinstance(m, str):
+        if m not in IVF_ITERATIVE_MODES:
+            raise ValueError(f"invalid value for parameter \"ivfflat.iterative_scan\": \"{m}\"")
+        return IVF_ITERATIVE_MODES[m]
+    return int(m)
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -440,6 +452,36 @@ class IvfIndex:
                                        _ptr(doc), _ptr(row), _ptr(dist), _ptr(cnt)))
         del keep
         return SearchResult(blk, doc, row, dist, cnt)
+
+    def search_iterative_device(self, d_queries, nq, k, probes, metric, filters, mode, max_probes, d_block, d_doc, d_rows,
+                                d_dist, d_counts, d_probes=None):
+        """Device pointers (ints); returns when every query is proven exact (vsr_ivf_search_iterative_device)."""
+        farr, keep = self.corpus._filter_array(filters, nq)
+        check(self._lib.vsr_ivf_search_iterative_device(self._h, d_queries, nq, self.corpus.dim, int(k), int(probes),
+                                                        _metric(metric), farr, _ivf_iterative_mode(mode), int(max_probes),
+                                                        d_block, d_doc, d_rows, d_dist, d_counts, d_probes))
+        del keep
+
+    def search_iterative(self, queries, k, probes, metric="l2", filters=None, mode="relaxed_order", max_probes=32768):
+        """pgvector's iterative index scan (ivfflat.iterative_scan = mode, ivfflat.max_probes): batches of `probes` lists,
+        nearest lists first, until k permitted rows are out or max_probes lists are scanned.  SearchResult (rows in stream
+        order: sorted inside a batch, not across batches) plus, as a second value, the lists each query's scan had taken
+        when it stopped (so->listIndex)."""
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(queries, dtype=np.float32)))
+        nq, dim = q.shape
+        farr, keep = self.corpus._filter_array(filters, nq)
+        kk = max(int(k), 1)
+        blk = np.full((nq, kk), -1, dtype=np.int64)
+        doc = np.full((nq, kk), -1, dtype=np.int32)
+        row = np.full((nq, kk), -1, dtype=np.int64)
+        dist = np.full((nq, kk), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.int32)
+        scanned = np.zeros(nq, dtype=np.int32)
+        check(self._lib.vsr_ivf_search_iterative(self._h, _ptr(q), nq, dim, int(k), int(probes), _metric(metric), farr,
+                                                 _ivf_iterative_mode(mode), int(max_probes), _ptr(blk), _ptr(doc), _ptr(row),
+                                                 _ptr(dist), _ptr(cnt), _ptr(scanned)))
+        del keep
+        return SearchResult(blk, doc, row, dist, cnt), scanned
 
 
 class HnswIndex:
