@@ -83,10 +83,10 @@ struct FusedTail {
 };
 
 struct ScanParams {
-    const float4*    rows;         // [n_rows][stride4] row-major, zero padded
+    const float4*    rows;         // [n_rows][stride4] row-major, zero padded (K1h: [n_rows][stride4 / 2] chunks of 8 halves)
     const float*     norm2;        // [n_rows] sum x^2 (cosine)
     uint32_t         n_rows;
-    uint32_t         stride4;      // float4 per row
+    uint32_t         stride4;      // float4 per row (K1h: per padded QUERY, two for every 16-byte row chunk)
     const float*     queries;      // [n_slots][stride4*4], zero padded
     const float*     q_norm2;      // [n_slots]
     const ScanGroup* groups;
@@ -211,13 +211,18 @@ struct KernelShape {
 
 // host-side launchers (vsr_kernels.hip)
 KernelShape scan_shape_for_dim(int dim);
+// K1h (halfvec corpus): the same classes by the row's 16-byte chunks, ceil(dim / 8) of 8 halves each; c counts those chunks
+KernelShape scan_shape_for_dim_half(int dim);
 uint32_t scan_cap_for_k(int k, int dim);
+uint32_t scan_cap_for_rw(int k, int rw);                  // ... from the tile rows of either kind of corpus
 int  scan_qmax(int dim, int k);    // queries per pass the LDS budget allows (1, or a multiple of 4 up to SCAN_QMAX)
+int  scan_qmax_half(int dim, int k);
 inline size_t scan_lds_bytes(uint32_t qmax, uint32_t cap, uint32_t stride4)
 {
     return (size_t) qmax * ((size_t) cap * 8 + 16 + (size_t) stride4 * 16 + 4) + 16;
 }
 hipError_t launch_scan(const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s);
+hipError_t launch_scan_half(const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s);   // K1h
 // one query per call over the int8 planes (vsr_scan8.h): K1's top-k and in-kernel merge, a quarter of the bytes per row
 hipError_t launch_scan8_fused(const ScanParams& p, uint32_t dim, uint32_t* q8_bad_host, uint32_t n_blocks, hipStream_t s);
 // K1m (vsr_mq.h): shared-pass kernel for 2..16 queries per pass; needs dim >= 61 (>= 16 float4 per row)
@@ -312,6 +317,7 @@ struct StageParams {
     uint32_t     q_stride;
     float*       q_dst;            // nq x qfloats, zero padded
     uint32_t     dim, qfloats, nq;
+    uint32_t     q_half;           // halfvec corpus: every query element is rounded to binary16 and widened again (Float4ToHalf)
     float*       q_norm2;          // [nq]
     uint4*       q_scr;            // [nq][q plane stride] bf16 hi / mid planes of the padded queries (nullptr: not needed)
     uint32_t     pstride4;         // corpus plane stride
@@ -334,6 +340,8 @@ hipError_t launch_check_u8_exact(const float4* rows, uint32_t n_rows, uint32_t s
 hipError_t launch_split_planes8(const float4* rows, uint32_t n_rows, uint32_t stride4, uint32_t dim, uint4* scr8, float* norm8,
                                 hipStream_t s);
 hipError_t launch_row_norms(const float4* rows, uint32_t n_rows, uint32_t stride4, float* norm2, hipStream_t s);
+// ... of a halfvec corpus: rows of `chunks` 16-byte chunks of 8 halves, widened to fp32 and summed in fp32 (halfutils.c:123-142)
+hipError_t launch_row_norms_half(const uint4* rows, uint32_t n_rows, uint32_t chunks, float* norm2, hipStream_t s);
 hipError_t launch_build_bitmap(const uint32_t* row_doc_idx, uint32_t n_rows, const uint64_t* doc_mask,
                                uint32_t words, const uint64_t* user_mask, uint64_t* bitmap, hipStream_t s);
 hipError_t launch_build_class_bitmap(const uint32_t* row_doc_idx, uint32_t n_rows, const uint32_t* doc_class, uint32_t cls,

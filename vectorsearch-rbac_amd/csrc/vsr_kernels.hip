@@ -11,6 +11,11 @@ hipError_t launch_scan_l2(const ScanParams&, int, int, uint32_t, hipStream_t);
 hipError_t launch_scan_ip(const ScanParams&, int, int, uint32_t, hipStream_t);
 hipError_t launch_scan_cosine(const ScanParams&, int, int, uint32_t, hipStream_t);
 hipError_t launch_scan_l1(const ScanParams&, int, int, uint32_t, hipStream_t);
+// ... and K1h's (vsr_scanh_*.hip)
+hipError_t launch_scanh_l2(const ScanParams&, int, int, uint32_t, hipStream_t);
+hipError_t launch_scanh_ip(const ScanParams&, int, int, uint32_t, hipStream_t);
+hipError_t launch_scanh_cosine(const ScanParams&, int, int, uint32_t, hipStream_t);
+hipError_t launch_scanh_l1(const ScanParams&, int, int, uint32_t, hipStream_t);
 
 hipError_t launch_mq_l2(const ScanParams&, uint32_t, hipStream_t);
 hipError_t launch_mq_ip(const ScanParams&, uint32_t, hipStream_t);
@@ -85,9 +90,9 @@ hipError_t launch_mq(const ScanParams& p, int metric, uint32_t n_blocks, hipStre
     }
 }
 
-KernelShape scan_shape_for_dim(int dim)
+// lanes per row, chunks per lane and row slots by the row's 16-byte chunks
+static KernelShape scan_shape_for_chunks(int d4)
 {
-    const int d4 = (dim + 3) / 4;
     if (d4 <= 1)   return {1, 1, 1, 64};
     if (d4 <= 4)   return {4, 1, 4, 64};
     if (d4 <= 16)  return {16, 1, 8, 32};
@@ -99,26 +104,39 @@ KernelShape scan_shape_for_dim(int dim)
     return {64, 0, 2, 2};
 }
 
-uint32_t scan_cap_for_k(int k, int dim)
+KernelShape scan_shape_for_dim(int dim) { return scan_shape_for_chunks((dim + 3) / 4); }
+// (a lane that widens 3 or 4 chunks of several rows for four queries runs out of registers: rows of more than 128 chunks,
+// d > 1024, stream chunk by chunk instead)
+KernelShape scan_shape_for_dim_half(int dim)
+{
+    const int d8 = (dim + 7) / 8;
+    return d8 <= 128 ? scan_shape_for_chunks(d8) : KernelShape{64, 0, 2, 2};
+}
+
+uint32_t scan_cap_for_rw(int k, int rw)
 {
     // room for k kept keys plus one check interval of new ones, trigger level >= 2k so compactions amortise
-    const int slack = scan_slack(scan_shape_for_dim(dim).rw);
+    const int slack = scan_slack(rw);
     uint32_t cap = 512;
     while (cap < (uint32_t) (2 * k + slack)) cap <<= 1;
     return cap;
 }
 
-int scan_qmax(int dim, int k)
+uint32_t scan_cap_for_k(int k, int dim) { return scan_cap_for_rw(k, scan_shape_for_dim(dim).rw); }
+
+// sh: the corpus's shape; stride4: float4 per padded query in LDS
+static int scan_qmax_for(const KernelShape& sh, uint32_t stride4, int k)
 {
-    const KernelShape sh = scan_shape_for_dim(dim);
-    const uint32_t stride4 = (uint32_t) ((dim + 3) / 4);
-    const size_t per_query = scan_lds_bytes(1, scan_cap_for_k(k, dim), stride4) - 16;
+    const size_t per_query = scan_lds_bytes(1, scan_cap_for_rw(k, sh.rw), stride4) - 16;
     int q = (int) (SCAN_LDS_BUDGET / per_query);
     if (sh.c == 0) q = q < 4 ? q : 4;            // runtime-chunk kernel: one sub-batch only
     if (q >= 4) q = (q < SCAN_QMAX ? q : SCAN_QMAX) / 4 * 4;
     else q = 1;
     return q;
 }
+
+int scan_qmax(int dim, int k) { return scan_qmax_for(scan_shape_for_dim(dim), (uint32_t) ((dim + 3) / 4), k); }
+int scan_qmax_half(int dim, int k) { return scan_qmax_for(scan_shape_for_dim_half(dim), 2u * (uint32_t) ((dim + 7) / 8), k); }
 
 hipError_t launch_scan(const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s)
 {
@@ -127,6 +145,17 @@ hipError_t launch_scan(const ScanParams& p, int metric, int dim, int qi, uint32_
     case M_IP:     return launch_scan_ip(p, dim, qi, n_blocks, s);
     case M_COSINE: return launch_scan_cosine(p, dim, qi, n_blocks, s);
     case M_L1:     return launch_scan_l1(p, dim, qi, n_blocks, s);
+    default:       return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_scan_half(const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s)
+{
+    switch (metric) {
+    case M_L2:     return launch_scanh_l2(p, dim, qi, n_blocks, s);
+    case M_IP:     return launch_scanh_ip(p, dim, qi, n_blocks, s);
+    case M_COSINE: return launch_scanh_cosine(p, dim, qi, n_blocks, s);
+    case M_L1:     return launch_scanh_l1(p, dim, qi, n_blocks, s);
     default:       return hipErrorInvalidValue;
     }
 }
@@ -477,6 +506,34 @@ hipError_t launch_row_norms(const float4* rows, uint32_t n_rows, uint32_t stride
     return hipGetLastError();
 }
 
+// halfvec rows: the norma accumulator of HalfvecCosineSimilarity (halfutils.c:123-142), fp32 over the widened elements
+__global__ __launch_bounds__(256) void row_norms_half_kernel(const uint4* rows, uint32_t n_rows, uint32_t chunks, float* norm2)
+{
+    using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
+    const uint32_t n_waves = (gridDim.x * 256) >> 6;
+    for (uint32_t r = wave; r < n_rows; r += n_waves) {
+        float s = 0.0f;
+        for (uint32_t c = lane; c < chunks; c += 64) {
+            const f16x8 x = __builtin_bit_cast(f16x8, rows[(size_t) r * chunks + c]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s = fmaf((float) x[j], (float) x[j], s);
+        }
+        for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+        if (lane == 0) norm2[r] = s;
+    }
+}
+
+hipError_t launch_row_norms_half(const uint4* rows, uint32_t n_rows, uint32_t chunks, float* norm2, hipStream_t s)
+{
+    if (n_rows == 0) return hipSuccess;
+    uint32_t blocks = (n_rows + 3) / 4;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(row_norms_half_kernel, dim3(blocks), dim3(256), 0, s, rows, n_rows, chunks, norm2);
+    return hipGetLastError();
+}
+
 // -------------------------------------------------------------------------------------------------
 // Screening planes (K2w): 8 consecutive floats -> one chunk of 8 bf16 "hi" values and one of 8 "mid" values
 // (hi = bf16(x), mid = bf16(x - hi); round to nearest even; x - hi is exact in fp32).
@@ -681,7 +738,10 @@ __global__ __launch_bounds__(256) void stage_kernel(const StageParams p)
     const uint32_t s = blockIdx.x;
     const float* src = p.q_src + (size_t) s * p.q_stride;
     float* dst = p.q_dst + (size_t) s * p.qfloats;
-    for (uint32_t j = (uint32_t) tid; j < p.qfloats; j += 256) dst[j] = j < p.dim ? src[j] : 0.0f;
+    for (uint32_t j = (uint32_t) tid; j < p.qfloats; j += 256) {
+        const float v = j < p.dim ? src[j] : 0.0f;
+        dst[j] = p.q_half ? (float) (_Float16) v : v;        // what `$1::halfvec` holds (Float4ToHalf, halfutils.h:146-261)
+    }
     if (tid == 0) {
         p.flags[s] = 0;
         p.tau[s] = KEY_EMPTY;

@@ -125,11 +125,12 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     const vsr_ctx* ctx = in.ctx;
     const vsr_corpus* c = in.c;
     Width w{};
-    w.mq_ok = mq_supported(c->dim) && mq_qmax(c->dim) >= 4 && !ctx->no_mq;
+    // (a halfvec corpus has fp16 rows only: K1h, never K1m or the screening kernels, which read fp32 rows and planes)
+    w.mq_ok = !c->half && mq_supported(c->dim) && mq_qmax(c->dim) >= 4 && !ctx->no_mq;
     // K2 / K2w: matrix-core screening keeps 2k (>= 32) candidates per query, K5r re-ranks them exactly
     w.keep = (uint32_t) std::max(2 * in.k, 32);
-    const bool k2_any = allow_screening && ctx->screening && c->k2_safe && in.metric != VSR_METRIC_L1 && mq_supported(c->dim) &&
-                        ctx->max_qb >= 16;
+    const bool k2_any = !c->half && allow_screening && ctx->screening && c->k2_safe && in.metric != VSR_METRIC_L1 &&
+                        mq_supported(c->dim) && ctx->max_qb >= 16;
     w.k2w_ok = k2_any && allow_wide && c->d_scr && w.keep <= GQ_MAX_KP && !ctx->no_wide && ctx->seeding;
     w.k2_ok = w.k2w_ok || (k2_any && mfma_cap_for_k(w.keep) <= 8192 && mfma_lds_bytes(c->stride4) <= 150 * 1024);
     w.wq = mfmaw_qmax(c->pstride4, !c->scr_has_mid);
@@ -154,7 +155,7 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     const int legacy_qb = ctx->max_qb_set ? ctx->max_qb : 16;
     if (w.k2w_ok) w.qmax = ctx->max_qb_set ? std::min(ctx->max_qb, w.wq) : w.wq;
     else if (w.k2_ok) w.qmax = std::min(legacy_qb, mfma_qmax(c->stride4));
-    else w.qmax = std::min(legacy_qb, w.mq_ok ? mq_qmax(c->dim) : scan_qmax(c->dim, in.k));
+    else w.qmax = std::min(legacy_qb, w.mq_ok ? mq_qmax(c->dim) : c->half ? scan_qmax_half(c->dim, in.k) : scan_qmax(c->dim, in.k));
     if (w.k2_ok && !w.k2w_ok && !ctx->max_qb_set && w.qmax >= 16 && c->stride4 > 64) {
         // long rows (d > 256): a pass costs mostly its row bytes, so two 16-query MFMA groups per pass (half the passes)
         // pay off -- but only when the query groups fill them (an unfiltered 1000-query batch: 17 % less time at
@@ -314,7 +315,7 @@ void emit_groups(const PlanIn& in, bool i8wide, const LaunchSize& ls, PlanScratc
         plan.n_partial_s += gs.n_blocks * p.q_count;
         plan.scan_rows += p.rows;
         plan.scan_pairs += p.rows * (int64_t) p.q_count;
-        plan.scan_bytes += p.rows * (int64_t) c->dim * 4 + (g.bitmap ? (p.rows + 7) / 8 : 0) + (int64_t) p.q_count * in.k * 12 +
+        plan.scan_bytes += p.rows * (int64_t) c->dim * (c->half ? 2 : 4) + (g.bitmap ? (p.rows + 7) / 8 : 0) + (int64_t) p.q_count * in.k * 12 +
                            (plan.k2 ? p.rows * 4 : 0);     // K2 also reads |row|^2
     }
     plan.n_scan_lists = plan.n_partial;
@@ -628,7 +629,7 @@ std::string vsr::scan_kernel_name(const Plan& plan, const vsr_corpus* c, int met
     else if (plan.mq)
         snprintf(buf, sizeof buf, "vsr::mq_scan_kernel<%s, SAMPLE=false> (K1m)", mname[metric]);
     else
-        snprintf(buf, sizeof buf, "vsr::scan_kernel<%s, LPR=%d, C=%d, R=%d, QI=%d> (K1)", mname[metric], c->shape.lpr,
-                 c->shape.c, c->shape.r, plan.qi);
+        snprintf(buf, sizeof buf, "vsr::scan_kernel<%s, LPR=%d, C=%d, R=%d, QI=%d%s", mname[metric], c->shape.lpr, c->shape.c,
+                 c->shape.r, plan.qi, c->half ? ", HALF=true> (K1h, half rows)" : "> (K1)");
     return buf;
 }

@@ -203,7 +203,9 @@ struct vsr_corpus {
     mutable hipStream_t scan_stream = nullptr;
     int64_t     n = 0;
     int         dim = 0;
-    uint32_t    stride4 = 0;
+    uint32_t    stride4 = 0;             // float4 per padded row (halfvec corpus: per padded QUERY, dim rounded up to 8 floats)
+    bool        half = false;            // halfvec corpus (vsr_corpus_load_half): d_rows holds stride4 / 2 16-byte chunks of 8
+                                         // binary16 values per row, no fp32 image, no screening planes; exact kernels only (K1h)
     int64_t     row_offset = 0;
     KernelShape shape{};
     float4*     d_rows = nullptr;

@@ -232,24 +232,31 @@ vsr_corpus::~vsr_corpus()
 extern "C" int64_t vsr_corpus_rows(const vsr_corpus* c) { return c ? c->n : 0; }
 extern "C" int vsr_corpus_dim(const vsr_corpus* c) { return c ? c->dim : 0; }
 
-extern "C" int vsr_corpus_load(vsr_ctx* ctx, const float* rows, int64_t n, int dim, const int64_t* block_ids,
-                               const int32_t* doc_ids, int64_t row_offset, vsr_corpus** out)
+// vsr_corpus_load (ELEM = float) and vsr_corpus_load_half (ELEM = uint16_t, binary16 bit patterns): the same identity
+// arrays and row order; a halfvec corpus keeps its rows as they came -- 2 bytes per element -- plus |row|^2, nothing else
+template <class ELEM>
+static int corpus_load(vsr_ctx* ctx, const ELEM* rows, int64_t n, int dim, const int64_t* block_ids, const int32_t* doc_ids,
+                       int64_t row_offset, vsr_corpus** out, const char* who)
 {
-    if (!ctx || !out) return fail(VSR_ERR_INVALID, "vsr_corpus_load: NULL argument");
+    constexpr bool HALF = sizeof(ELEM) == 2;
+    constexpr int PER16 = 16 / (int) sizeof(ELEM);          // elements per 16-byte chunk
+    if (!ctx || !out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
     *out = nullptr;
-    if (n < 0 || (n > 0 && !rows)) return fail(VSR_ERR_INVALID, "vsr_corpus_load: rows is NULL");
-    if (dim < 1 || dim > 16000)      // VECTOR_MAX_DIM, pgvector/src/vector.h:4
-        return fail(VSR_ERR_INVALID, "vsr_corpus_load: vector must have between 1 and 16000 dimensions (got %d)", dim);
-    if (n + row_offset >= 0xFFFFFFFFll) return fail(VSR_ERR_UNSUPPORTED, "vsr_corpus_load: more than 2^32-2 rows per shard");
+    if (n < 0 || (n > 0 && !rows)) return fail(VSR_ERR_INVALID, "%s: rows is NULL", who);
+    if (dim < 1 || dim > 16000)      // VECTOR_MAX_DIM, pgvector/src/vector.h:4; HALFVEC_MAX_DIM, halfvec.h
+        return fail(VSR_ERR_INVALID, "%s: %s must have between 1 and 16000 dimensions (got %d)", who, HALF ? "halfvec" : "vector", dim);
+    if (n + row_offset >= 0xFFFFFFFFll) return fail(VSR_ERR_UNSUPPORTED, "%s: more than 2^32-2 rows per shard", who);
     HIPCHK(hipSetDevice(ctx->device));
 
     std::unique_ptr<vsr_corpus> c(new vsr_corpus());
     c->ctx = ctx;
     c->n = n;
     c->dim = dim;
-    c->stride4 = (uint32_t) ((dim + 3) / 4);
+    c->half = HALF;
+    const uint32_t row_chunks = (uint32_t) ((dim + PER16 - 1) / PER16);   // 16-byte chunks per row
+    c->stride4 = HALF ? 2 * row_chunks : row_chunks;
     c->row_offset = row_offset;
-    c->shape = scan_shape_for_dim(dim);
+    c->shape = HALF ? scan_shape_for_dim_half(dim) : scan_shape_for_dim(dim);
 
     // internal order: (document_id, block_id); identity when the input is already sorted that way
     std::vector<int64_t> perm((size_t) n);
@@ -283,7 +290,7 @@ extern "C" int vsr_corpus_load(vsr_ctx* ctx, const float* rows, int64_t n, int d
     }
     c->doc_row_start.push_back((uint32_t) n);
 
-    const size_t row_bytes = (size_t) c->stride4 * 16;
+    const size_t row_bytes = (size_t) row_chunks * 16;
     const size_t alloc_rows = (size_t) std::max<int64_t>(n, 1);
     HIPCHK(hipMalloc(&c->d_rows, alloc_rows * row_bytes + 1024));
     HIPCHK(hipMalloc(&c->d_norm2, alloc_rows * sizeof(float)));
@@ -295,18 +302,19 @@ extern "C" int vsr_corpus_load(vsr_ctx* ctx, const float* rows, int64_t n, int d
     HIPCHK(hipMalloc(&c->d_row_docidx, alloc_rows * sizeof(uint32_t)));
 
     if (n > 0) {
-        if (sorted && dim % 4 == 0) {
+        if (sorted && dim % PER16 == 0) {
             HIPCHK(hipMemcpy(c->d_rows, rows, (size_t) n * row_bytes, hipMemcpyHostToDevice));
         } else {
             // permute + zero-pad through a bounded host staging buffer
             const size_t chunk_rows = std::max<size_t>(1, (64u << 20) / row_bytes);
-            std::vector<float> stage(chunk_rows * c->stride4 * 4);
+            const size_t row_elems = (size_t) row_chunks * PER16;
+            std::vector<ELEM> stage(chunk_rows * row_elems);
             for (int64_t base = 0; base < n; base += (int64_t) chunk_rows) {
                 const int64_t m = std::min<int64_t>((int64_t) chunk_rows, n - base);
-                std::fill(stage.begin(), stage.begin() + (size_t) m * c->stride4 * 4, 0.0f);
+                std::fill(stage.begin(), stage.begin() + (size_t) m * row_elems, ELEM(0));
                 for (int64_t i = 0; i < m; ++i)
-                    memcpy(&stage[(size_t) i * c->stride4 * 4], rows + (size_t) perm[(size_t) (base + i)] * dim,
-                           (size_t) dim * sizeof(float));
+                    memcpy(&stage[(size_t) i * row_elems], rows + (size_t) perm[(size_t) (base + i)] * dim,
+                           (size_t) dim * sizeof(ELEM));
                 HIPCHK(hipMemcpy(reinterpret_cast<char*>(c->d_rows) + (size_t) base * row_bytes, stage.data(),
                                  (size_t) m * row_bytes, hipMemcpyHostToDevice));
             }
@@ -315,6 +323,14 @@ extern "C" int vsr_corpus_load(vsr_ctx* ctx, const float* rows, int64_t n, int d
         HIPCHK(hipMemcpy(c->d_doc, h_doc.data(), (size_t) n * sizeof(int32_t), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(c->d_orig, perm.data(), (size_t) n * sizeof(int64_t), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(c->d_row_docidx, h_docidx.data(), (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (HALF) {
+            // the rows are the corpus: no fp32 image, no planes, exact kernels only
+            HIPCHK(launch_row_norms_half(reinterpret_cast<const uint4*>(c->d_rows), (uint32_t) n, row_chunks, c->d_norm2, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            c->k2_safe = false;
+            *out = c.release();
+            return VSR_OK;
+        }
         HIPCHK(launch_row_norms(c->d_rows, (uint32_t) n, c->stride4, c->d_norm2, ctx->stream));
         HIPCHK(launch_norm_max(c->d_norm2, (uint32_t) n, c->d_norm2_max, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -367,6 +383,34 @@ extern "C" int vsr_corpus_load(vsr_ctx* ctx, const float* rows, int64_t n, int d
     }
     *out = c.release();
     return VSR_OK;
+}
+
+extern "C" int vsr_corpus_load(vsr_ctx* ctx, const float* rows, int64_t n, int dim, const int64_t* block_ids,
+                               const int32_t* doc_ids, int64_t row_offset, vsr_corpus** out)
+{
+    return corpus_load(ctx, rows, n, dim, block_ids, doc_ids, row_offset, out, "vsr_corpus_load");
+}
+
+extern "C" int vsr_corpus_load_half(vsr_ctx* ctx, const uint16_t* rows, int64_t n, int dim, const int64_t* block_ids,
+                                    const int32_t* doc_ids, int64_t row_offset, vsr_corpus** out)
+{
+    return corpus_load(ctx, rows, n, dim, block_ids, doc_ids, row_offset, out, "vsr_corpus_load_half");
+}
+
+extern "C" int vsr_corpus_is_half(const vsr_corpus* c) { return c && c->half ? 1 : 0; }
+
+// rows, norms and every screening plane as allocated at load (a view's own image: its base is another corpus)
+extern "C" int64_t vsr_corpus_device_bytes(const vsr_corpus* c)
+{
+    if (!c) return 0;
+    const size_t rows = (size_t) std::max<int64_t>(c->n, 1);
+    size_t b = rows * (c->half ? c->stride4 / 2 : c->stride4) * 16 + 1024 + rows * sizeof(float);   // d_rows, d_norm2
+    if (c->d_norm2_max) b += 64;
+    if (c->d_scr) b += rows * (size_t) c->pstride4 * 16 + 1024;
+    if (c->d_scr_c) b += coarse_plane_u4((uint64_t) rows, c->cstride4) * 16 + 1024;
+    if (c->d_scr8) b += rows * (size_t) 128 + 4096;
+    if (c->d_norm2_8) b += (rows + 64) * sizeof(float);
+    return (int64_t) b;
 }
 
 extern "C" int vsr_last_scan_kernel(vsr_ctx* ctx, char* name, int name_len)

@@ -16,6 +16,13 @@
 // sums are combined with a halving butterfly (R registers over LPR lanes), after which lane
 // (l % D == 0) owns the finished value of row slot l / D.
 // HBM-bound: 3 flop per 4 bytes per query; no MFMA on purpose.
+//
+// K1h (HALF = true) is the same kernel over a halfvec corpus (pgvector/src/halfvec.c): a row is ceil(dim / 8) 16-byte
+// chunks of 8 IEEE binary16 values, so LPR, C and R count those chunks (scan_shape_for_dim_half) and a lane's load holds 8
+// elements.  Every chunk is widened to two float4 and goes through the same accum4 / rank_value against the fp32 query in
+// LDS -- pgvector computes every halfvec distance on the widened operands (halfutils.c) -- and the query is rounded to
+// binary16 and widened as it enters LDS, which is what `$1::halfvec` holds.  No fp16 arithmetic: x - q of two halves is
+// exact in fp32, not in fp16.  p.stride4 stays the QUERY's stride (float4 per padded query = two per row chunk).
 #pragma once
 #include "vsr_device.h"
 #include "vsr_topk.h"
@@ -37,6 +44,24 @@ __device__ __forceinline__ void accum4(float& p, const float4& x, const float4& 
         p = fmaf(x.x, q.x, p); p = fmaf(x.y, q.y, p); p = fmaf(x.z, q.z, p); p = fmaf(x.w, q.w, p);
     }
 }
+
+// K1h: 8 binary16 values (one 16-byte row chunk) -> two float4; every binary16 value, subnormals included, is an fp32 value
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+__device__ __forceinline__ void widen8(const uint4& h, float4& a, float4& b)
+{
+    const f16x8 v = __builtin_bit_cast(f16x8, h);
+    a = make_float4((float) v[0], (float) v[1], (float) v[2], (float) v[3]);
+    b = make_float4((float) v[4], (float) v[5], (float) v[6], (float) v[7]);
+}
+// Float4ToHalf (halfutils.h:146-261) and back: round to nearest even, |v| >= 65520 -> +-Inf, NaN stays NaN
+__device__ __forceinline__ float round_to_half(float v) { return (float) (_Float16) v; }
+__device__ __forceinline__ float4 round_to_half(const float4& v)
+{
+    return make_float4(round_to_half(v.x), round_to_half(v.y), round_to_half(v.z), round_to_half(v.w));
+}
+template <class X> __device__ __forceinline__ X zero_chunk();
+template <> __device__ __forceinline__ float4 zero_chunk<float4>() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+template <> __device__ __forceinline__ uint4 zero_chunk<uint4>() { return make_uint4(0u, 0u, 0u, 0u); }
 
 // fp32 ranking value, monotone in the SQL-level operator result:
 //   L2: the fp32 sum of squares (vector.c:584-594 ranks by it too); IP: -dot (vector.c:626-636);
@@ -100,12 +125,12 @@ struct ScanShape {
 };
 
 // One tile's worth of state: descriptor + the lane's share of its rows.
-template <int R, int CC>
+template <int R, int CC, class X = float4>                  // X: a 16-byte row chunk as loaded (K1h: uint4 = 8 halves)
 struct TileRegs {
     uint32_t start;
     uint64_t mask;       // rows of the tile to evaluate (row validity & permission bits); 0 = nothing to do
     float    rn;         // |row|^2 of the row this lane finishes (cosine)
-    float4   x[R][CC];
+    X        x[R][CC];
 };
 
 // ---- nq == 1: in-kernel merge tree (FusedTail, vsr_device.h) ----
@@ -328,12 +353,15 @@ __device__ __forceinline__ void fused_tail(const ScanParams& p, const ScanGroup&
 #define VSR_MINWAVES 2          // launch-bounds waves per SIMD the register allocator must allow
 #endif
 
-template <int METRIC, int LPR, int C, int R, int QI>
-__global__ __launch_bounds__(SCAN_THREADS, VSR_MINWAVES) void scan_kernel(const ScanParams p)
+// (K1h, one query per pass: widening needs no more than the 128 registers that let two workgroups share a CU, and says so;
+// with four queries per sub-batch it does, and is left the same room as K1)
+template <int METRIC, int LPR, int C, int R, int QI, bool HALF = false>
+__global__ __launch_bounds__(SCAN_THREADS, (HALF && QI == 1 ? 4 : VSR_MINWAVES)) void scan_kernel(const ScanParams p)
 {
     using S = ScanShape<LPR, R>;
     constexpr int G = S::G, RW = S::RW, D = S::D, XCHK = S::XCHK;
     constexpr int CC = C > 0 ? C : 1;
+    using Chunk = typename std::conditional<HALF, uint4, float4>::type;
 
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x;
@@ -358,6 +386,7 @@ __global__ __launch_bounds__(SCAN_THREADS, VSR_MINWAVES) void scan_kernel(const 
     const uint32_t t1 = (uint32_t) (((uint64_t) grp.n_tiles * (local_block + 1)) / grp.n_blocks);
 
     const uint32_t cap = p.cap, k = p.k, qmax = p.qmax, stride4 = p.stride4;
+    const uint32_t rstride = HALF ? stride4 / 2 : stride4;                     // 16-byte chunks per corpus row
     uint64_t* keys = reinterpret_cast<uint64_t*>(smem);                       // [qmax][cap]
     TopKCtrl* ctrl = reinterpret_cast<TopKCtrl*>(keys + (size_t) qmax * cap); // [qmax]
     float4*   qlds = reinterpret_cast<float4*>(ctrl + qmax);                  // [qmax][stride4]
@@ -376,7 +405,8 @@ __global__ __launch_bounds__(SCAN_THREADS, VSR_MINWAVES) void scan_kernel(const 
     for (uint32_t qi = 0; qi < n_sub * QI; ++qi) {                            // pad slots repeat query 0
         const uint32_t slot = fused ? 0u : p.q_slots[grp.q_begin + (qi < q_count ? qi : 0)];
         const float4* qsrc = reinterpret_cast<const float4*>(p.queries) + (size_t) slot * stride4;
-        for (uint32_t i = tid; i < stride4; i += SCAN_THREADS) qlds[(size_t) qi * stride4 + i] = qsrc[i];
+        for (uint32_t i = tid; i < stride4; i += SCAN_THREADS)
+            qlds[(size_t) qi * stride4 + i] = HALF ? round_to_half(qsrc[i]) : qsrc[i];
     }
     __syncthreads();
 
@@ -388,7 +418,7 @@ __global__ __launch_bounds__(SCAN_THREADS, VSR_MINWAVES) void scan_kernel(const 
     const uint32_t iters = ((t1 - t0 + ss - 1) / ss + SCAN_WAVES - 1) / SCAN_WAVES;
 
     // issue the loads of tile t (no waits): descriptor, permission bits, row chunks
-    auto fetch = [&](uint32_t t, TileRegs<R, CC>& tr) {
+    auto fetch = [&](uint32_t t, TileRegs<R, CC, Chunk>& tr) {
         tr.mask = 0;
         tr.start = 0;
         tr.rn = 0.0f;
@@ -411,7 +441,7 @@ __global__ __launch_bounds__(SCAN_THREADS, VSR_MINWAVES) void scan_kernel(const 
             if (own && ((mask >> row_own) & 1ull)) tr.rn = p.norm2[start + row_own];
         }
         if constexpr (C > 0) {
-            const float4* base = p.rows + (size_t) start * stride4;
+            const Chunk* base = reinterpret_cast<const Chunk*>(p.rows) + (size_t) start * rstride;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const int row = r * G + g;
@@ -419,16 +449,15 @@ __global__ __launch_bounds__(SCAN_THREADS, VSR_MINWAVES) void scan_kernel(const 
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
                     const uint32_t chunk = c * LPR + l;
-                    tr.x[r][c] = (ok && chunk < stride4) ? base[(size_t) row * stride4 + chunk]
-                                                         : make_float4(0.f, 0.f, 0.f, 0.f);
+                    tr.x[r][c] = (ok && chunk < rstride) ? base[(size_t) row * rstride + chunk] : zero_chunk<Chunk>();
                 }
             }
         }
     };
 
-    TileRegs<R, CC> cur;
+    TileRegs<R, CC, Chunk> cur;
 #if VSR_PREFETCH
-    TileRegs<R, CC> nxt;
+    TileRegs<R, CC, Chunk> nxt;
     fetch(t0 + wave * ss, cur);
 #endif
     uint32_t round = 0;
@@ -453,12 +482,33 @@ __global__ __launch_bounds__(SCAN_THREADS, VSR_MINWAVES) void scan_kernel(const 
 #pragma unroll
                     for (int c = 0; c < C; ++c) {
                         const uint32_t chunk = c * LPR + l;
+                        if constexpr (HALF) {
+                            // the sub-batch's query chunks first, then one row chunk at a time: 8 widened values live, not 8 R
+                            float4 qa[QI], qb[QI];
 #pragma unroll
-                        for (int qi = 0; qi < QI; ++qi) {
-                            const float4 qv = chunk < stride4 ? qlds[(size_t) (sb * QI + qi) * stride4 + chunk]
-                                                              : make_float4(0.f, 0.f, 0.f, 0.f);
+                            for (int qi = 0; qi < QI; ++qi) {
+                                const float4* qrow = qlds + (size_t) (sb * QI + qi) * stride4 + 2 * chunk;
+                                qa[qi] = chunk < rstride ? qrow[0] : make_float4(0.f, 0.f, 0.f, 0.f);
+                                qb[qi] = chunk < rstride ? qrow[1] : make_float4(0.f, 0.f, 0.f, 0.f);
+                            }
 #pragma unroll
-                            for (int r = 0; r < R; ++r) accum4<METRIC>(acc[qi][r], cur.x[r][c], qv);
+                            for (int r = 0; r < R; ++r) {
+                                float4 xa, xb;
+                                widen8(cur.x[r][c], xa, xb);
+#pragma unroll
+                                for (int qi = 0; qi < QI; ++qi) {
+                                    accum4<METRIC>(acc[qi][r], xa, qa[qi]);
+                                    accum4<METRIC>(acc[qi][r], xb, qb[qi]);
+                                }
+                            }
+                        } else {
+#pragma unroll
+                            for (int qi = 0; qi < QI; ++qi) {
+                                const float4 qv = chunk < stride4 ? qlds[(size_t) (sb * QI + qi) * stride4 + chunk]
+                                                                  : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                                for (int r = 0; r < R; ++r) accum4<METRIC>(acc[qi][r], cur.x[r][c], qv);
+                            }
                         }
                     }
 #pragma unroll
@@ -474,25 +524,45 @@ __global__ __launch_bounds__(SCAN_THREADS, VSR_MINWAVES) void scan_kernel(const 
                 }
             } else {
                 // any dimension: stream the rows chunk by chunk, all (<= QI) queries at once
-                const float4* base = p.rows + (size_t) start * stride4;
+                const Chunk* base = reinterpret_cast<const Chunk*>(p.rows) + (size_t) start * rstride;
                 float acc[QI][R];
 #pragma unroll
                 for (int qi = 0; qi < QI; ++qi)
 #pragma unroll
                     for (int r = 0; r < R; ++r) acc[qi][r] = 0.0f;
 #pragma unroll 4
-                for (uint32_t chunk = l; chunk < stride4; chunk += 64) {
-                    float4 x[R];
+                for (uint32_t chunk = l; chunk < rstride; chunk += 64) {
+                    Chunk x[R];
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         const bool ok = (cur.mask >> r) & 1ull;
-                        x[r] = ok ? base[(size_t) r * stride4 + chunk] : make_float4(0.f, 0.f, 0.f, 0.f);
+                        x[r] = ok ? base[(size_t) r * rstride + chunk] : zero_chunk<Chunk>();
                     }
+                    if constexpr (HALF) {
+                        float4 qa[QI], qb[QI];
 #pragma unroll
-                    for (int qi = 0; qi < QI; ++qi) {
-                        const float4 qv = qlds[(size_t) qi * stride4 + chunk];
+                        for (int qi = 0; qi < QI; ++qi) {
+                            const float4* qrow = qlds + (size_t) qi * stride4 + 2 * chunk;
+                            qa[qi] = qrow[0];
+                            qb[qi] = qrow[1];
+                        }
 #pragma unroll
-                        for (int r = 0; r < R; ++r) accum4<METRIC>(acc[qi][r], x[r], qv);
+                        for (int r = 0; r < R; ++r) {
+                            float4 xa, xb;
+                            widen8(x[r], xa, xb);
+#pragma unroll
+                            for (int qi = 0; qi < QI; ++qi) {
+                                accum4<METRIC>(acc[qi][r], xa, qa[qi]);
+                                accum4<METRIC>(acc[qi][r], xb, qb[qi]);
+                            }
+                        }
+                    } else {
+#pragma unroll
+                        for (int qi = 0; qi < QI; ++qi) {
+                            const float4 qv = qlds[(size_t) qi * stride4 + chunk];
+#pragma unroll
+                            for (int r = 0; r < R; ++r) accum4<METRIC>(acc[qi][r], x[r], qv);
+                        }
                     }
                 }
 #pragma unroll
@@ -556,11 +626,11 @@ __global__ __launch_bounds__(SCAN_THREADS, VSR_MINWAVES) void scan_kernel(const 
     }
 }
 
-template <int METRIC, int LPR, int C, int R, int QI>
+template <int METRIC, int LPR, int C, int R, int QI, bool HALF>
 hipError_t launch_scan_inst(const ScanParams& p, uint32_t n_blocks, hipStream_t s)
 {
     const size_t lds = scan_lds_bytes(p.qmax, p.cap, p.stride4);
-    auto kern = scan_kernel<METRIC, LPR, C, R, QI>;
+    auto kern = scan_kernel<METRIC, LPR, C, R, QI, HALF>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
@@ -571,14 +641,14 @@ hipError_t launch_scan_inst(const ScanParams& p, uint32_t n_blocks, hipStream_t 
 }
 
 // shape dispatch for one metric; instantiated once per metric in its own translation unit
-template <int METRIC>
+template <int METRIC, bool HALF = false>
 hipError_t launch_scan_metric(const ScanParams& p, int dim, int qi, uint32_t n_blocks, hipStream_t s)
 {
-    const KernelShape sh = scan_shape_for_dim(dim);
+    const KernelShape sh = HALF ? scan_shape_for_dim_half(dim) : scan_shape_for_dim(dim);
 #define VSR_CASE(LPR_, C_, R_)                                                             \
     if (sh.lpr == LPR_ && sh.c == C_) {                                                    \
-        if (qi == 1) return launch_scan_inst<METRIC, LPR_, C_, R_, 1>(p, n_blocks, s);     \
-        if (qi == 4) return launch_scan_inst<METRIC, LPR_, C_, R_, 4>(p, n_blocks, s);     \
+        if (qi == 1) return launch_scan_inst<METRIC, LPR_, C_, R_, 1, HALF>(p, n_blocks, s);     \
+        if (qi == 4) return launch_scan_inst<METRIC, LPR_, C_, R_, 4, HALF>(p, n_blocks, s);     \
         return hipErrorInvalidValue;                                                       \
     }
     VSR_CASE(1, 1, 1)
@@ -587,8 +657,10 @@ hipError_t launch_scan_metric(const ScanParams& p, int dim, int qi, uint32_t n_b
     VSR_CASE(32, 1, 8)
     VSR_CASE(64, 1, 8)
     VSR_CASE(64, 2, 4)
-    VSR_CASE(64, 3, 4)
-    VSR_CASE(64, 4, 2)
+    if constexpr (!HALF) {                                  // (scan_shape_for_dim_half: rows past 128 chunks stream, C = 0)
+        VSR_CASE(64, 3, 4)
+        VSR_CASE(64, 4, 2)
+    }
     VSR_CASE(64, 0, 2)
 #undef VSR_CASE
     return hipErrorInvalidValue;

@@ -346,11 +346,12 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
 
 // ---- one query, one pass -----------------------------------------------------------------------------------------
 // The whole search in ONE launch (FusedTail, vsr_device.h).  Conditions: the query already lies in device memory in the row
-// layout (d a multiple of 4: no padding to add), no |q|^2 needed (not cosine), one plain pass on K1, k small enough for the
+// layout (d a multiple of 4, of 8 over a halfvec corpus: no padding to add), no |q|^2 needed (not cosine), one plain pass on K1, k small enough for the
 // workgroup's LDS top-k buffer.  Returns the workgroups per first-level merge, 0: the call takes the general path.
-uint32_t fused_fan(const vsr_ctx* ctx, const Plan& plan, const Call& q)
+uint32_t fused_fan(const vsr_ctx* ctx, const vsr_corpus* c, const Plan& plan, const Call& q)
 {
-    if (!(q.nq == 1 && !ctx->no_fused && plan.groups.size() == 1 && plan.qi == 1 && !plan.k2 && !plan.mq && q.dim % 4 == 0 &&
+    // (K1h rounds the query to binary16 itself as it enters LDS: no staging kernel needed for that either)
+    if (!(q.nq == 1 && !ctx->no_fused && plan.groups.size() == 1 && plan.qi == 1 && !plan.k2 && !plan.mq && q.dim % (c->half ? 8 : 4) == 0 &&
           q.metric != VSR_METRIC_COSINE && plan.groups[0].n_blocks <= 64u * 64u && ctx->profiling != 1))
         return 0;
     const uint32_t kp = plan.keep;
@@ -385,7 +386,7 @@ int search_fused(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q, u
     ScanParams sp = scan_params(ctx, c, kp, 1);
     sp.queries = q_dev;
     sp.partial = ctx->d_partial.as<uint64_t>();
-    sp.cap = std::max<uint32_t>(4096, scan_cap_for_k((int) kp, c->dim));   // the merge's LDS layout (vsr_scan.h, FUSED_*)
+    sp.cap = std::max<uint32_t>(4096, scan_cap_for_rw((int) kp, c->shape.rw));   // the merge's LDS layout (vsr_scan.h, FUSED_*)
     sp.n_groups = 1;
     sp.fused.enable = 1;
     sp.fused.fan = fan;
@@ -423,7 +424,9 @@ int search_fused(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q, u
         sp.plane_ho = 2u;
         sp.fused.flag_total = ctx->d_flag_total;
         HIPCHK(launch_scan8_fused(sp, (uint32_t) dim, reinterpret_cast<uint32_t*>(ctx->h_q8.dp), g.n_blocks, ctx->stream));
-    } else
+    } else if (c->half)
+        HIPCHK(launch_scan_half(sp, metric, c->dim, 1, g.n_blocks, ctx->stream));
+    else
         HIPCHK(launch_scan(sp, metric, c->dim, 1, g.n_blocks, ctx->stream));
     if (!q.d_queries) {
         HIPCHK(hipEventRecord(ctx->desc_done, ctx->stream));
@@ -477,6 +480,7 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
 
     StageParams st{};                                       // (no query planes, no K2w counters on this path)
     RCCHK(stage_host_part(ctx, sb, off_qn, off_g, q.h_queries, q.d_queries, nq, q.dim, qfloats, st));
+    st.q_half = c->half ? 1u : 0u;
     RCCHK(ctx->d_partial.reserve(std::max<size_t>(8, (size_t) plan.n_partial * kp * sizeof(uint64_t))));
     char* ds = ctx->d_desc.as<char>();
     Timed whole(ctx, 5, ctx->stream);                       // the whole search on the device
@@ -486,7 +490,7 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
     sp.queries = reinterpret_cast<const float*>(ds);
     sp.q_norm2 = reinterpret_cast<const float*>(ds + off_qn);
     sp.partial = ctx->d_partial.as<uint64_t>();
-    sp.cap = plan.k2 ? mfma_cap_for_k(kp) : scan_cap_for_k((int) kp, c->dim);
+    sp.cap = plan.k2 ? mfma_cap_for_k(kp) : scan_cap_for_rw((int) kp, c->shape.rw);
     if (plan.mq || plan.k2) {
         RCCHK(ctx->d_cand.reserve(std::max<size_t>(8, (size_t) plan.n_scan_lists * cand_pitch(sp.cap) * sizeof(uint64_t))));
         sp.cand = ctx->d_cand.as<uint64_t>();
@@ -551,6 +555,7 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
         const uint32_t launch_blocks = sp.block_map ? plan.n_launch : plan.n_blocks;
         if (plan.k2) HIPCHK(launch_mfma(sp, metric, launch_blocks, ctx->stream));
         else if (plan.mq) HIPCHK(launch_mq(sp, metric, launch_blocks, ctx->stream));
+        else if (c->half) HIPCHK(launch_scan_half(sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream));
         else HIPCHK(launch_scan(sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream));
         HIPCHK(main.stop());
         ctx->last_kernel = scan_kernel_name(plan, c, metric);
@@ -616,7 +621,7 @@ int search_impl(vsr_ctx* ctx, vsr_corpus* c, const Call& q, const vsr_filter* co
     }
     ctx->last_coarse = plan.k2g;
     ctx->host_us[0] += us_since(h0);
-    const uint32_t fan = plan.k2w ? 0u : fused_fan(ctx, plan, q);
+    const uint32_t fan = plan.k2w ? 0u : fused_fan(ctx, c, plan, q);
     const int rc = plan.k2w ? search_wide(ctx, c, plan, q) : fan ? search_fused(ctx, c, plan, q, fan) : search_general(ctx, c, plan, q, allow_screening);
     const double spent = us_since(h0);
     ctx->host_us[2] += spent;
@@ -632,7 +637,8 @@ int vsr::check_search_args(const vsr_corpus* c, const void* queries, int nq, int
 {
     if (!c) return fail(VSR_ERR_INVALID, "%s: corpus is NULL", who);
     if (nq < 0 || (nq > 0 && !queries)) return fail(VSR_ERR_INVALID, "%s: queries is NULL", who);
-    if (dim != c->dim) return fail(VSR_ERR_DIM_MISMATCH, "different vector dimensions %d and %d", c->dim, dim);
+    if (dim != c->dim)                                      // CheckDims: vector.c:60-67, halfvec.c:60-67
+        return fail(VSR_ERR_DIM_MISMATCH, "different %s dimensions %d and %d", c->half ? "halfvec" : "vector", c->dim, dim);
     if (k < 1) return fail(VSR_ERR_INVALID, "%s: k must be >= 1 (got %d)", who, k);
     if (k > VSR_MAX_K) return fail(VSR_ERR_UNSUPPORTED, "%s: k = %d exceeds VSR_MAX_K = %d", who, k, VSR_MAX_K);
     if (metric < VSR_METRIC_L2 || metric > VSR_METRIC_L1) return fail(VSR_ERR_INVALID, "%s: metric %d", who, metric);
@@ -787,5 +793,13 @@ extern "C" int vsr_search(vsr_corpus* c, const float* queries, int nq, int dim, 
     if (c->base) return fail(VSR_ERR_INVALID, "vsr_search: this corpus is an index view; use the index's search function");
     if (nq == 0) return VSR_OK;
     if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "vsr_search: output is NULL");
+    if (c->half) {
+        // `$1::halfvec`: a finite element that rounds to +-Inf is an error (halfvec_in, halfvec.c:224-230); 65520 is
+        // the smallest magnitude that does.  (The device entry points do not look: the element becomes +-Inf.)
+        const size_t total = (size_t) nq * (size_t) dim;
+        for (size_t i = 0; i < total; ++i)
+            if (std::isfinite(queries[i]) && std::fabs(queries[i]) >= 65520.0f)
+                return fail(VSR_ERR_INVALID, "\"%.9g\" is out of range for type halfvec", (double) queries[i]);
+    }
     return host_search(c, queries, nq, dim, k, metric, filters, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr});
 }

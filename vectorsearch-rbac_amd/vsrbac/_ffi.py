@@ -35,6 +35,9 @@ SYMBOLS = {
     "vsr_synchronize": (_i, [_vp]),
     "vsr_device_info": (_i, [_vp, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_i64)]),
     "vsr_corpus_load": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i64, C.POINTER(_vp)]),
+    "vsr_corpus_load_half": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i64, C.POINTER(_vp)]),
+    "vsr_corpus_is_half": (_i, [_vp]),
+    "vsr_corpus_device_bytes": (_i64, [_vp]),
     "vsr_corpus_free": (_i, [_vp]),
     "vsr_corpus_rows": (_i64, [_vp]),
     "vsr_corpus_dim": (_i, [_vp]),

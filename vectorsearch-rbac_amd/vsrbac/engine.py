@@ -131,6 +131,20 @@ class Context:
     def load_corpus(self, rows, block_ids=None, doc_ids=None, row_offset=0):
         return Corpus(self, rows, block_ids, doc_ids, row_offset)
 
+    def load_corpus_half(self, rows, block_ids=None, doc_ids=None, row_offset=0):
+        """A halfvec corpus (vsr_corpus_load_half): `rows` np.float16, resident as they are -- 2 bytes per element.  An fp32
+        array is rounded to binary16 as Float4ToHalf does (round to nearest even); a finite element that would become
+        +-Inf raises VsrError('"<v>" is out of range for type halfvec').  Searches go through the same Corpus methods."""
+        rows = np.asarray(rows)
+        if rows.dtype != np.float16:
+            rows = np.ascontiguousarray(rows, dtype=np.float32)
+            bad = np.isfinite(rows) & (np.abs(rows) >= np.float32(65520.0))
+            if bad.any():
+                raise VsrError(_ffi.ERR_INVALID, f'"{float(rows[bad].ravel()[0]):.9g}" is out of range for type halfvec')
+            with np.errstate(over="ignore"):
+                rows = rows.astype(np.float16)
+        return Corpus(self, rows, block_ids, doc_ids, row_offset, half=True)
+
     def pair_distances(self, metric, a, b):
         """Operator value for pairs (a[i], b[i]); b may be a single vector (broadcast).
         Raises VsrError('different vector dimensions %d and %d') like pgvector's CheckDims."""
@@ -225,10 +239,10 @@ class Filter:
 class Corpus:
     """Rows resident in HBM, identified as (document_id, block_id) like the reference's documentblocks table."""
 
-    def __init__(self, ctx, rows, block_ids=None, doc_ids=None, row_offset=0):
+    def __init__(self, ctx, rows, block_ids=None, doc_ids=None, row_offset=0, half=False):
         self.ctx = ctx
         self._lib = ctx._lib
-        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        rows = np.ascontiguousarray(rows, dtype=np.float16 if half else np.float32)
         if rows.ndim != 2:
             raise ValueError("rows must be [n, dim]")
         n, dim = rows.shape
@@ -237,12 +251,21 @@ class Corpus:
         if (blk is not None and blk.size != n) or (doc is not None and doc.size != n):
             raise ValueError("block_ids / doc_ids must have one entry per row")
         h = C.c_void_p()
-        check(self._lib.vsr_corpus_load(ctx._h, _ptr(rows), n, dim, _ptr(blk), _ptr(doc), int(row_offset),
-                                        C.byref(h)))
+        load = self._lib.vsr_corpus_load_half if half else self._lib.vsr_corpus_load
+        check(load(ctx._h, _ptr(rows), n, dim, _ptr(blk), _ptr(doc), int(row_offset), C.byref(h)))
         self._h = h
         self.n, self.dim = n, dim
         self.row_offset = int(row_offset)
         self._user_filters = {}
+
+    @property
+    def is_half(self):
+        """True for a halfvec corpus (Context.load_corpus_half)."""
+        return bool(self._lib.vsr_corpus_is_half(self._h))
+
+    def device_bytes(self):
+        """Device bytes holding vector data: rows, norms and every screening plane (vsr_corpus_device_bytes)."""
+        return int(self._lib.vsr_corpus_device_bytes(self._h))
 
     def free(self):
         if getattr(self, "_h", None):

@@ -3,6 +3,8 @@
 
   * pgvector text form   `[a,b,...]`   vector_in / vector_out   (pgvector/src/vector.c:165-270, 278-315)
   * pgvector binary form  int16 dim, int16 unused (= 0), float4[dim] big-endian   vector_recv / vector_send  (:363-411)
+  * the same two forms of halfvec (pgvector/src/halfvec.c:165-320 text, :356-404 binary: big-endian uint16 binary16 elements);
+    arrays are np.float16, what Context.load_corpus_half takes
   * shared_vectors.bin (+ .meta) of the C++ benches   SharedVectorTable::save_vectors / load_vectors
     (logical_partition_benchmark/benchmark/src/shared_vector_table.cpp:169-201): int32 dim, int64 count, float32[count*dim];
     .meta = int32 dim, int64 count, (int32 document_id, int32 block_id)[count]
@@ -25,18 +27,18 @@ _libc.strtof.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p)]
 _ERANGE = 34
 
 
-def _check_element(v):
+def _check_element(v, kind="vector"):
     if math.isnan(v):
-        raise ValueError("NaN not allowed in vector")                         # vector.c:101-113
+        raise ValueError(f"NaN not allowed in {kind}")                        # vector.c:101-113, halfvec.c:101-113
     if math.isinf(v):
-        raise ValueError("infinite value not allowed in vector")
+        raise ValueError(f"infinite value not allowed in {kind}")
 
 
-def _check_dim(dim):
+def _check_dim(dim, kind="vector"):
     if dim < 1:
-        raise ValueError("vector must have at least 1 dimension")             # vector.c:85-96
+        raise ValueError(f"{kind} must have at least 1 dimension")            # vector.c:85-96, halfvec.c:84-96
     if dim > VECTOR_MAX_DIM:
-        raise ValueError(f"vector cannot have more than {VECTOR_MAX_DIM} dimensions")
+        raise ValueError(f"{kind} cannot have more than {VECTOR_MAX_DIM} dimensions")
 
 
 def _check_expected(expected_dim, dim):
@@ -46,10 +48,16 @@ def _check_expected(expected_dim, dim):
 
 def vector_from_text(lit, expected_dim=None):
     """vector_in: same grammar, same number parser (libc strtof: no double rounding), same error texts."""
+    return np.asarray(_elements_from_text(lit, expected_dim, "vector"), dtype=np.float32)
+
+
+def _elements_from_text(lit, expected_dim, kind):
+    """The grammar vector_in and halfvec_in share (vector.c:165-270, halfvec.c:165-271); kind: the type named in the errors.
+    halfvec: every element is the fp32 value of the binary16 it rounds to (Float4ToHalfUnchecked)."""
     if isinstance(lit, bytes):
         lit = lit.decode()
     raw = lit.encode()
-    bad = f'invalid input syntax for type vector: "{lit}"'
+    bad = f'invalid input syntax for type {kind}: "{lit}"'
     n = len(raw)
     pos = 0
 
@@ -63,13 +71,13 @@ def vector_from_text(lit, expected_dim=None):
         raise ValueError(bad + '\nDETAIL:  Vector contents must start with "[".')
     pos = skip(pos + 1)
     if raw[pos:pos + 1] == b"]":
-        raise ValueError("vector must have at least 1 dimension")
+        raise ValueError(f"{kind} must have at least 1 dimension")
     out = []
     buf = ctypes.create_string_buffer(raw + b"\0")
     base = ctypes.addressof(buf)
     while True:
         if len(out) == VECTOR_MAX_DIM:
-            raise ValueError(f"vector cannot have more than {VECTOR_MAX_DIM} dimensions")
+            raise ValueError(f"{kind} cannot have more than {VECTOR_MAX_DIM} dimensions")
         pos = skip(pos)
         if pos >= n:
             raise ValueError(bad)
@@ -79,9 +87,15 @@ def vector_from_text(lit, expected_dim=None):
         stop = ctypes.cast(end, ctypes.c_void_p).value - base
         if stop == pos:
             raise ValueError(bad)
-        if ctypes.get_errno() == _ERANGE and math.isinf(val):
-            raise ValueError(f'"{raw[pos:stop].decode()}" is out of range for type vector')
-        _check_element(val)
+        range_error = ctypes.get_errno() == _ERANGE and math.isinf(val)
+        if kind == "halfvec":
+            with np.errstate(over="ignore"):
+                h = float(np.float32(val).astype(np.float16))     # round to nearest even, |v| >= 65520 -> +-Inf
+            range_error = range_error or (math.isinf(h) and not math.isinf(val))
+            val = h
+        if range_error:
+            raise ValueError(f'"{raw[pos:stop].decode()}" is out of range for type {kind}')
+        _check_element(val, kind)
         out.append(val)
         pos = skip(stop)
         c = raw[pos:pos + 1]
@@ -95,9 +109,9 @@ def vector_from_text(lit, expected_dim=None):
     pos = skip(pos)
     if pos != n:
         raise ValueError(bad + "\nDETAIL:  Junk after closing right brace.")
-    _check_dim(len(out))
+    _check_dim(len(out), kind)
     _check_expected(expected_dim, len(out))
-    return np.asarray(out, dtype=np.float32)
+    return out
 
 
 def _float4_shortest(v):
@@ -156,6 +170,53 @@ def vector_to_binary(v):
     v = np.asarray(v, dtype=np.float32).ravel()
     _check_dim(v.size)
     return struct.pack(">hh", v.size, 0) + v.astype(">f4").tobytes()
+
+
+def _check_halfvec_typmod(expected_dim):
+    if expected_dim is None or expected_dim == -1:
+        return
+    if expected_dim < 1:
+        raise ValueError("dimensions for type halfvec must be at least 1")    # halfvec_typmod_in, halfvec.c:325-351
+    if expected_dim > VECTOR_MAX_DIM:                                         # (HALFVEC_MAX_DIM is 16000 too, halfvec.h)
+        raise ValueError(f"dimensions for type halfvec cannot exceed {VECTOR_MAX_DIM}")
+
+
+def halfvec_from_text(lit, expected_dim=None):
+    """halfvec_in (halfvec.c:165-271): vector_in's grammar; every element rounded to binary16 (round to nearest even), one
+    that overflows is `"<text>" is out of range for type halfvec`.  Returns np.float16."""
+    _check_halfvec_typmod(expected_dim)
+    return np.asarray(_elements_from_text(lit, expected_dim, "halfvec"), dtype=np.float16)
+
+
+def halfvec_to_text(v):
+    """halfvec_out (halfvec.c:279-320): the shortest float4 decimal of every widened element."""
+    v = np.asarray(v, dtype=np.float16).ravel()
+    return "[" + ",".join(_float4_shortest(np.float32(x)) for x in v) + "]"
+
+
+def halfvec_from_binary(b, expected_dim=None):
+    """halfvec_recv (halfvec.c:356-385): int16 dim, int16 unused (= 0), dim big-endian uint16 binary16 bit patterns."""
+    _check_halfvec_typmod(expected_dim)
+    if len(b) < 4:
+        raise ValueError("insufficient data left in message")
+    dim, unused = struct.unpack(">hh", b[:4])
+    _check_dim(dim, "halfvec")
+    _check_expected(expected_dim, dim)
+    if unused != 0:
+        raise ValueError(f"expected unused to be 0, not {unused}")
+    if len(b) != 4 + 2 * dim:
+        raise ValueError("insufficient data left in message" if len(b) < 4 + 2 * dim else "incorrect binary data format")
+    x = np.frombuffer(b, dtype=">u2", count=dim, offset=4).astype(np.uint16).view(np.float16)
+    for e in x:
+        _check_element(float(e), "halfvec")
+    return x
+
+
+def halfvec_to_binary(v):
+    """halfvec_send (halfvec.c:390-404)."""
+    v = np.ascontiguousarray(np.asarray(v, dtype=np.float16).ravel())
+    _check_dim(v.size, "halfvec")
+    return struct.pack(">hh", v.size, 0) + v.view(np.uint16).astype(">u2").tobytes()
 
 
 def write_shared_vectors(path, rows, doc_ids, block_ids):
