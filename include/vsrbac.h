@@ -96,15 +96,17 @@ int vsr_corpus_load(vsr_ctx* ctx, const float* rows, int64_t n, int dim,
                     const int64_t* block_ids, const int32_t* doc_ids, int64_t row_offset,
                     vsr_corpus** out);
 /* pgvector's halfvec (halfvec.h; HALFVEC_MAX_DIM 16000): rows[n][dim] IEEE binary16 bit patterns.  Everything else as
- * vsr_corpus_load.  The rows stay binary16 on the device (2 bytes per element, plus |row|^2 for cosine): no fp32 image, no
- * screening planes.  Every distance is pgvector's for the type (halfutils.c): both operands widened to fp32, then the
+ * vsr_corpus_load.  The rows stay binary16 on the device (2 bytes per element, plus |row|^2): no fp32 image, no
+ * screening planes -- the rows are their own (K2h).  Every distance is pgvector's for the type (halfutils.c): both operands widened to fp32, then the
  * arithmetic of vector.c -- so queries stay const float*, and the library rounds every query element to binary16 (round to
  * nearest even, Float4ToHalf) and widens it again first, which is what `ORDER BY col <-> $1::halfvec` computes.  vsr_search
  * refuses a finite query element that rounds to +-Inf (|v| >= 65520) with VSR_ERR_INVALID,
  * `"<v>" is out of range for type halfvec`; the device entry points do not look, the element becomes +-Inf.  A dimension
  * mismatch reads "different halfvec dimensions %d and %d".  All metrics, filters, RBAC, k <= VSR_MAX_K, raw keys and the
- * shard merge work as for any corpus; only exact kernels run (vsr_search_device_exact: n_rerun = 0; vsr_set_screening and
- * vsr_set_query_hint have no effect).  Non-finite rows are accepted as for fp32 (pgvector rejects them on input): NaN
+ * shard merge work as for any corpus.  Passes that several queries share (L2 / inner product / cosine, dim >= 61) are
+ * screened on the f16 matrix cores and re-ranked exactly, as over an fp32 corpus: vsr_search_device may return flagged
+ * queries (negative counts), vsr_search and vsr_search_device_exact re-run them, on the exact kernel over the half rows.
+ * vsr_set_screening(ctx, 0) keeps every search on that kernel; vsr_set_query_hint has no effect.  Non-finite rows are accepted as for fp32 (pgvector rejects them on input): NaN
  * distances sort last.  vsr_ivf_load, vsr_ivf_assign, vsr_hnsw_load and vsr_hnsw_build* over such a corpus:
  * VSR_ERR_UNSUPPORTED. */
 int vsr_corpus_load_half(vsr_ctx* ctx, const uint16_t* rows, int64_t n, int dim,

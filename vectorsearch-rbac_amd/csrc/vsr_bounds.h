@@ -1,4 +1,4 @@
-// vsr_bounds.h — relative error bounds of the three screening tiers: |dot_s - dot| <= g(d) |x| |q|.
+// vsr_bounds.h — relative error bounds of the screening tiers: |dot_s - dot| <= g(d) |x| |q|.
 //
 // Plain C++ (no HIP): the re-rank's flag test (vsr_kernels.hip, rerank_body) relies on these constants, and the CPU
 // suite compiles this header on its own to check them (tests/test_screening_bounds_cpu.py).
@@ -32,3 +32,14 @@ inline float plane_err_g(int dim)
 
 // K2, fp32 MFMA on the fp32 rows: every product rounded once (2^-24 relative), d of them accumulated in fp32
 inline float k2_err_g(int dim) { return (float) (dim + 8) * 5.9604645e-8f; }          // (d + 8) 2^-24
+
+// K2h, f16 MFMA on the binary16 rows of a halfvec corpus and the binary16-rounded query: nothing is rounded on the way in,
+// and a product of two halves (11 x 11 significand bits, exponents within +-32) is exact in fp32.  What remains is the
+// fp32 accumulation of the d products, in an order the hardware chooses.  Any order of n - 1 rounded additions is within
+// gamma = (n - 1) u / (1 - (n - 1) u) of the sum of |products|, u = 2^-24, and that sum is at most |x||q| (Cauchy-Schwarz).
+// The slack: up to VECTOR_MAX_DIM = 16000 the second-order part of gamma is (n - 1)^2 u^2 <= 15.3 u, and the zero padding
+// adds exactly.  ASSUMPTION, as for the bf16 MFMA chains above: the f16 MFMA adds its products with no more than one
+// fp32 rounding (to nearest) per product; the instruction's internal order and rounding are not documented, and
+// tests/test_gpu_halfvec_mfma.py checks the bound on the device.  Subnormal halves count like any other value: their
+// products are exact too (the same test checks that the hardware keeps them).
+inline float half_err_g(int dim) { return (float) (dim + 16) * 5.9604645e-8f; }       // (d + 16) 2^-24

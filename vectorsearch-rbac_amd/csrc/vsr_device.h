@@ -10,6 +10,7 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;   // native vector: loa
 using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 using i32x4 = __attribute__((ext_vector_type(4))) int;       // A / B fragment and accumulator of v_mfma_i32_16x16x64_i8
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16; // A / B fragment of v_mfma_f32_16x16x32_bf16
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16; // ... of v_mfma_f32_16x16x32_f16; one 16-byte chunk of a halfvec row
 
 // Explicit address spaces.  A pointer that comes out of a struct in memory (ScanGroup::tiles / bitmap) or an access the
 // compiler must not cache (volatile) is "generic" to hipcc and becomes a FLAT instruction, which counts on both the
@@ -105,7 +106,7 @@ struct ScanParams {
                                    // workgroup.  nullptr: groups own contiguous workgroup ranges (block_begin)
     // K2w screening planes (bf16 hi / mid split of every element, vsr_planes.h layout): corpus rows and query slots
     const uint4*     scr;          // [n_rows][pstride4] 16-byte chunks
-    const uint4*     q_scr;        // [n_slots][pstride4]
+    const uint4*     q_scr;        // [n_slots][pstride4] (K2h: [n_slots][stride4 / 2], the queries' binary16 image)
     uint32_t         pstride4;     // 16-byte chunks per corpus plane row (plane_stride4)
     // K2g coarse planes (vsr_gemm.h): hi = bf16(x) only, rows of cstride4 16-byte chunks (d padded to whole 64-element K-steps)
     const uint4*     scr_c;        // [n_rows][cstride4]
@@ -171,6 +172,7 @@ struct RerankParams {
     const uint64_t*    lists;          // [n_queries][kp] screening keys (ascending, KEY_EMPTY padded), by slot
     const SelectQuery* queries;        // out_slot per slot
     const float4*      rows;
+    uint32_t           rows_half;      // halfvec corpus: rows holds stride4 / 2 16-byte chunks of 8 halves per row
     uint32_t           stride4;
     const float*       queries_f;      // [n_slots][stride4*4] padded query vectors (slot order)
     uint32_t           kp, k;
@@ -231,6 +233,8 @@ int  mq_qmax(int dim);
 hipError_t launch_mq(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s);
 // K2 (vsr_mfma.h): fp32-MFMA screening for shared passes (L2 / IP / cosine), followed by K5r
 hipError_t launch_mfma(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s);
+// K2h (vsr_mfmah.h): the same over a halfvec corpus, f16 MFMA on the resident rows and p.q_scr; K2's cap, LDS and qmax
+hipError_t launch_mfmah(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s);
 inline size_t mfma_lds_bytes(uint32_t stride4, int nq = 16)
 {
     (void) stride4;                                        // the queries never sit in LDS (registers, or streamed per stage)
@@ -318,6 +322,7 @@ struct StageParams {
     float*       q_dst;            // nq x qfloats, zero padded
     uint32_t     dim, qfloats, nq;
     uint32_t     q_half;           // halfvec corpus: every query element is rounded to binary16 and widened again (Float4ToHalf)
+    _Float16*    q_h16;            // [nq][qfloats] the rounded queries as binary16 (K2h's B fragments), nullptr: not needed
     float*       q_norm2;          // [nq]
     uint4*       q_scr;            // [nq][q plane stride] bf16 hi / mid planes of the padded queries (nullptr: not needed)
     uint32_t     pstride4;         // corpus plane stride

@@ -32,26 +32,54 @@ __device__ __forceinline__ float wave_query_norm2(const float4* q, uint32_t stri
 // the half ends with s[u] = sum (a - b)^2 (L2) or sum a b (IP, cosine) and nx[u] = sum a^2 (cosine only).  Callers pass a
 // valid row (0) for an empty slot and drop its sums: there is no branch around the gather, the U loads of a half-wave are
 // all in flight before the first FMA waits.
-template <int U>
+// HALF: `rows` is a halfvec corpus -- stride4 / 2 16-byte chunks of 8 halves per row -- and a lane's step is one such chunk,
+// widened in registers and added element by element against the query's two float4 with the fmaf sequence K1h runs
+// (vsr_scan.h): on data whose sums do not depend on the order, the re-rank and K1h give the same bits.
+template <int U, bool HALF = false>
 __device__ __forceinline__ void halfwave_row_sums(const float4* rows, uint32_t stride4, const float4* q, int metric,
                                                   const uint32_t (&row)[U], int hl, float (&s)[U], float (&nx)[U])
 {
 #pragma unroll
     for (int u = 0; u < U; ++u) s[u] = nx[u] = 0.f;
-    for (uint32_t ch = hl; ch < stride4; ch += 32) {
-        const float4 b = q[ch];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const f32x4 av = *reinterpret_cast<const f32x4*>(rows + (size_t) row[u] * stride4 + ch);
-            const float4 a = make_float4(av[0], av[1], av[2], av[3]);
+    if constexpr (HALF) {
+        const uint32_t nchunk = stride4 / 2;
+        const u32x4* rows16 = reinterpret_cast<const u32x4*>(rows);
+        auto add4 = [&](float& su, float& nu, float a0, float a1, float a2, float a3, const float4& b) {
             if (metric == M_L2) {
-                const float d0 = a.x - b.x, d1 = a.y - b.y, d2 = a.z - b.z, d3 = a.w - b.w;
-                s[u] = fmaf(d0, d0, s[u]); s[u] = fmaf(d1, d1, s[u]); s[u] = fmaf(d2, d2, s[u]); s[u] = fmaf(d3, d3, s[u]);
+                const float d0 = a0 - b.x, d1 = a1 - b.y, d2 = a2 - b.z, d3 = a3 - b.w;
+                su = fmaf(d0, d0, su); su = fmaf(d1, d1, su); su = fmaf(d2, d2, su); su = fmaf(d3, d3, su);
             } else {
-                s[u] = fmaf(a.x, b.x, s[u]); s[u] = fmaf(a.y, b.y, s[u]); s[u] = fmaf(a.z, b.z, s[u]); s[u] = fmaf(a.w, b.w, s[u]);
+                su = fmaf(a0, b.x, su); su = fmaf(a1, b.y, su); su = fmaf(a2, b.z, su); su = fmaf(a3, b.w, su);
                 if (metric == M_COSINE) {
-                    nx[u] = fmaf(a.x, a.x, nx[u]); nx[u] = fmaf(a.y, a.y, nx[u]);
-                    nx[u] = fmaf(a.z, a.z, nx[u]); nx[u] = fmaf(a.w, a.w, nx[u]);
+                    nu = fmaf(a0, a0, nu); nu = fmaf(a1, a1, nu); nu = fmaf(a2, a2, nu); nu = fmaf(a3, a3, nu);
+                }
+            }
+        };
+        for (uint32_t ch = hl; ch < nchunk; ch += 32) {
+            const float4 b0 = q[2 * ch], b1 = q[2 * ch + 1];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const f16x8 a = __builtin_bit_cast(f16x8, rows16[(size_t) row[u] * nchunk + ch]);
+                add4(s[u], nx[u], (float) a[0], (float) a[1], (float) a[2], (float) a[3], b0);
+                add4(s[u], nx[u], (float) a[4], (float) a[5], (float) a[6], (float) a[7], b1);
+            }
+        }
+    } else {
+        for (uint32_t ch = hl; ch < stride4; ch += 32) {
+            const float4 b = q[ch];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const f32x4 av = *reinterpret_cast<const f32x4*>(rows + (size_t) row[u] * stride4 + ch);
+                const float4 a = make_float4(av[0], av[1], av[2], av[3]);
+                if (metric == M_L2) {
+                    const float d0 = a.x - b.x, d1 = a.y - b.y, d2 = a.z - b.z, d3 = a.w - b.w;
+                    s[u] = fmaf(d0, d0, s[u]); s[u] = fmaf(d1, d1, s[u]); s[u] = fmaf(d2, d2, s[u]); s[u] = fmaf(d3, d3, s[u]);
+                } else {
+                    s[u] = fmaf(a.x, b.x, s[u]); s[u] = fmaf(a.y, b.y, s[u]); s[u] = fmaf(a.z, b.z, s[u]); s[u] = fmaf(a.w, b.w, s[u]);
+                    if (metric == M_COSINE) {
+                        nx[u] = fmaf(a.x, a.x, nx[u]); nx[u] = fmaf(a.y, a.y, nx[u]);
+                        nx[u] = fmaf(a.z, a.z, nx[u]); nx[u] = fmaf(a.w, a.w, nx[u]);
+                    }
                 }
             }
         }

@@ -25,6 +25,9 @@ hipError_t launch_mq_l1(const ScanParams&, uint32_t, hipStream_t);
 hipError_t launch_mfma_l2(const ScanParams&, uint32_t, hipStream_t);
 hipError_t launch_mfma_ip(const ScanParams&, uint32_t, hipStream_t);
 hipError_t launch_mfma_cosine(const ScanParams&, uint32_t, hipStream_t);
+hipError_t launch_mfmah_l2(const ScanParams&, uint32_t, hipStream_t);
+hipError_t launch_mfmah_ip(const ScanParams&, uint32_t, hipStream_t);
+hipError_t launch_mfmah_cosine(const ScanParams&, uint32_t, hipStream_t);
 
 hipError_t launch_mfmaw_l2(const ScanParams&, uint32_t, hipStream_t);
 hipError_t launch_mfmaw_ip(const ScanParams&, uint32_t, hipStream_t);
@@ -60,6 +63,16 @@ hipError_t launch_mfma(const ScanParams& p, int metric, uint32_t n_blocks, hipSt
     case M_L2:     return launch_mfma_l2(p, n_blocks, s);
     case M_IP:     return launch_mfma_ip(p, n_blocks, s);
     case M_COSINE: return launch_mfma_cosine(p, n_blocks, s);
+    default:       return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_mfmah(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s)
+{
+    switch (metric) {
+    case M_L2:     return launch_mfmah_l2(p, n_blocks, s);
+    case M_IP:     return launch_mfmah_ip(p, n_blocks, s);
+    case M_COSINE: return launch_mfmah_cosine(p, n_blocks, s);
     default:       return hipErrorInvalidValue;
     }
 }
@@ -509,7 +522,6 @@ hipError_t launch_row_norms(const float4* rows, uint32_t n_rows, uint32_t stride
 // halfvec rows: the norma accumulator of HalfvecCosineSimilarity (halfutils.c:123-142), fp32 over the widened elements
 __global__ __launch_bounds__(256) void row_norms_half_kernel(const uint4* rows, uint32_t n_rows, uint32_t chunks, float* norm2)
 {
-    using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
     const int lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
     const uint32_t n_waves = (gridDim.x * 256) >> 6;
@@ -741,6 +753,7 @@ __global__ __launch_bounds__(256) void stage_kernel(const StageParams p)
     for (uint32_t j = (uint32_t) tid; j < p.qfloats; j += 256) {
         const float v = j < p.dim ? src[j] : 0.0f;
         dst[j] = p.q_half ? (float) (_Float16) v : v;        // what `$1::halfvec` holds (Float4ToHalf, halfutils.h:146-261)
+        if (p.q_h16) p.q_h16[(size_t) s * p.qfloats + j] = (_Float16) v;
     }
     if (tid == 0) {
         p.flags[s] = 0;
@@ -978,6 +991,8 @@ hipError_t launch_vector_fn(int mode, const float* a, const float* b, int64_t n,
 // -------------------------------------------------------------------------------------------------
 // keys[0 .. np2): the query's screening survivors (KEY_EMPTY padded) already in LDS; worst_kept: the largest kept
 // screening key when the survivor list is full, else KEY_EMPTY; force_flag: the caller already knows the result is unproven
+// HALF: p.rows is a halfvec corpus (p.rows_half): the half-row form of the operator arithmetic
+template <bool HALF = false>
 __device__ __forceinline__ void rerank_body(const RerankParams& p, uint32_t slot, uint64_t* keys, uint32_t np2,
                                             uint64_t worst_kept, bool force_flag)
 {
@@ -1004,7 +1019,7 @@ __device__ __forceinline__ void rerank_body(const RerankParams& p, uint32_t slot
             sk[u] = c < np2 ? keys[c] : KEY_EMPTY;
             row[u] = sk[u] == KEY_EMPTY ? 0u : (uint32_t) sk[u];           // an empty slot reads row 0 and is dropped below
         }
-        halfwave_row_sums<U>(p.rows, p.stride4, q, p.metric, row, hl, s, nx);     // the operator arithmetic: vsr_exact.h
+        halfwave_row_sums<U, HALF>(p.rows, p.stride4, q, p.metric, row, hl, s, nx);     // the operator arithmetic: vsr_exact.h
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t c = c0 + 2 * u + half;
@@ -1082,6 +1097,7 @@ __device__ __forceinline__ void rerank_body(const RerankParams& p, uint32_t slot
     if (tid == 0) p.out_count[out_slot] = s_flag ? -1 - (int32_t) m : (int32_t) m;    // flagged: -1 - count (see select_emit)
 }
 
+template <bool HALF>
 __global__ __launch_bounds__(256) void rerank_kernel(const RerankParams p)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1093,7 +1109,7 @@ __global__ __launch_bounds__(256) void rerank_kernel(const RerankParams p)
     // the survivors' screening keys first (one round trip for the whole list, not one per gather round)
     for (uint32_t c = threadIdx.x; c < np2; c += 256) keys[c] = c < p.kp ? list[c] : KEY_EMPTY;
     __syncthreads();
-    rerank_body(p, slot, keys, np2, list[p.kp - 1], false);              // K5 leaves the largest kept key last
+    rerank_body<HALF>(p, slot, keys, np2, list[p.kp - 1], false);        // K5 leaves the largest kept key last
 }
 
 // K2w: per query, the kp best of its candidate buffer (one wave, every key in registers, radix select) and then the
@@ -1262,7 +1278,8 @@ hipError_t launch_rerank(const RerankParams& p, uint32_t n_queries, hipStream_t 
 {
     uint32_t np2 = 2;
     while (np2 < p.kp) np2 <<= 1;
-    hipLaunchKernelGGL(rerank_kernel, dim3(n_queries), dim3(256), (size_t) np2 * sizeof(uint64_t), s, p);
+    if (p.rows_half) hipLaunchKernelGGL(rerank_kernel<true>, dim3(n_queries), dim3(256), (size_t) np2 * sizeof(uint64_t), s, p);
+    else hipLaunchKernelGGL(rerank_kernel<false>, dim3(n_queries), dim3(256), (size_t) np2 * sizeof(uint64_t), s, p);
     return hipGetLastError();
 }
 

@@ -125,13 +125,14 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     const vsr_ctx* ctx = in.ctx;
     const vsr_corpus* c = in.c;
     Width w{};
-    // (a halfvec corpus has fp16 rows only: K1h, never K1m or the screening kernels, which read fp32 rows and planes)
+    // (a halfvec corpus has fp16 rows only: K1h or, under K2's gates, K2h -- K2 on the f16 matrix cores, vsr_mfmah.h; never
+    // K1m, which reads fp32 rows, nor K2w / K2g / int8, which read planes it does not have)
     w.mq_ok = !c->half && mq_supported(c->dim) && mq_qmax(c->dim) >= 4 && !ctx->no_mq;
     // K2 / K2w: matrix-core screening keeps 2k (>= 32) candidates per query, K5r re-ranks them exactly
     w.keep = (uint32_t) std::max(2 * in.k, 32);
-    const bool k2_any = !c->half && allow_screening && ctx->screening && c->k2_safe && in.metric != VSR_METRIC_L1 &&
+    const bool k2_any = !(c->half && ctx->no_half_mfma) && allow_screening && ctx->screening && c->k2_safe && in.metric != VSR_METRIC_L1 &&
                         mq_supported(c->dim) && ctx->max_qb >= 16;
-    w.k2w_ok = k2_any && allow_wide && c->d_scr && w.keep <= GQ_MAX_KP && !ctx->no_wide && ctx->seeding;
+    w.k2w_ok = k2_any && !c->half && allow_wide && c->d_scr && w.keep <= GQ_MAX_KP && !ctx->no_wide && ctx->seeding;
     w.k2_ok = w.k2w_ok || (k2_any && mfma_cap_for_k(w.keep) <= 8192 && mfma_lds_bytes(c->stride4) <= 150 * 1024);
     w.wq = mfmaw_qmax(c->pstride4, !c->scr_has_mid);
     // K2g (coarse planes, 256-query passes): when nearly all (part, query) items sit in parts seen by more than 128
@@ -623,7 +624,12 @@ std::string vsr::scan_kernel_name(const Plan& plan, const vsr_corpus* c, int met
     else if (plan.k2w)
         snprintf(buf, sizeof buf, "vsr::mfma_wide_kernel<%s, NCH=%u, SAMPLE=false, HO=%s> (K2w, bf16 %s planes)", mname[metric],
                  c->pstride4 / 16, c->scr_has_mid ? "false" : "true", c->scr_has_mid ? "hi+mid" : "hi-only");
-    else if (plan.k2)
+    else if (plan.k2 && c->half) {
+        const uint32_t hstage = (c->stride4 / 2 + 15) / 16;    // launch_mfmah_metric's choice
+        const int ng = plan.qmax > 16 ? 2 : 1;
+        snprintf(buf, sizeof buf, "vsr::mfmah_scan_kernel<%s, NSTR=%u, SAMPLE=false, NG=%d> (K2h, half rows)", mname[metric],
+                 hstage <= 2 ? hstage : hstage <= 4 && ng == 1 ? 4u : 0u, ng);
+    } else if (plan.k2)
         snprintf(buf, sizeof buf, "vsr::mfma_scan_kernel<%s, NSTR=%d, SAMPLE=false, NG=%d> (K2)", mname[metric],
                  nstage > 4 ? 0 : 4, plan.qmax > 16 ? 2 : 1);
     else if (plan.mq)

@@ -147,6 +147,7 @@ struct vsr_ctx {
     bool no_mq = false;            // VSR_NO_MQ=1: keep shared passes on K1 (A/B measurements)
     bool no_wide = false;          // VSR_NO_WIDE=1: shared passes on K2 (wave-private tiles) instead of K2w (A/B)
     bool no_gemm = false;          // VSR_NO_GEMM=1: wide passes over long rows on K2w instead of K2g (A/B)
+    bool no_half_mfma = false;     // VSR_NO_HALF_MFMA=1: shared passes over a halfvec corpus on K1h instead of K2h (A/B)
     bool no_k2i = true;            // VSR_K2I=1: the int8 main launch as K2i's per-wave streams instead of K2w's workgroup tiles (A/B;
                                    // measured on the headline step: K2w 0.342 ms, K2i 0.366 ms -- K2w stays the default)
     bool last_k2i = false;         // the last main launch was eligible for K2i

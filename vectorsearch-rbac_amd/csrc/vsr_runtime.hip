@@ -82,6 +82,7 @@ extern "C" int vsr_open(int device, vsr_ctx** out)
     if ((env = getenv("VSR_NO_MQ"))) ctx->no_mq = atoi(env) != 0;
     if ((env = getenv("VSR_NO_WIDE"))) ctx->no_wide = atoi(env) != 0;
     if ((env = getenv("VSR_NO_GEMM"))) ctx->no_gemm = atoi(env) != 0;
+    if ((env = getenv("VSR_NO_HALF_MFMA"))) ctx->no_half_mfma = atoi(env) != 0;
     if ((env = getenv("VSR_K2I"))) ctx->no_k2i = atoi(env) == 0;
     if ((env = getenv("VSR_FORCE_EPI"))) ctx->force_epi = atoi(env) != 0;
     if ((env = getenv("VSR_K2I_WIDE"))) ctx->k2i_wide = atoi(env) != 0;
@@ -324,10 +325,14 @@ static int corpus_load(vsr_ctx* ctx, const ELEM* rows, int64_t n, int dim, const
         HIPCHK(hipMemcpy(c->d_orig, perm.data(), (size_t) n * sizeof(int64_t), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(c->d_row_docidx, h_docidx.data(), (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice));
         if (HALF) {
-            // the rows are the corpus: no fp32 image, no planes, exact kernels only
+            // the rows are the corpus and their own screening plane (K2h): no fp32 image, no planes.  As below, a corpus
+            // holding NaN / Inf (or norms that overflow) stays on the exact kernel, K1h
             HIPCHK(launch_row_norms_half(reinterpret_cast<const uint4*>(c->d_rows), (uint32_t) n, row_chunks, c->d_norm2, ctx->stream));
+            HIPCHK(launch_norm_max(c->d_norm2, (uint32_t) n, c->d_norm2_max, ctx->stream));
             HIPCHK(hipStreamSynchronize(ctx->stream));
-            c->k2_safe = false;
+            float nmax = 0.0f;
+            HIPCHK(hipMemcpy(&nmax, c->d_norm2_max, sizeof(float), hipMemcpyDeviceToHost));
+            c->k2_safe = std::isfinite(nmax);
             *out = c.release();
             return VSR_OK;
         }

@@ -46,7 +46,6 @@ __device__ __forceinline__ void accum4(float& p, const float4& x, const float4& 
 }
 
 // K1h: 8 binary16 values (one 16-byte row chunk) -> two float4; every binary16 value, subnormals included, is an fp32 value
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 __device__ __forceinline__ void widen8(const uint4& h, float4& a, float4& b)
 {
     const f16x8 v = __builtin_bit_cast(f16x8, h);

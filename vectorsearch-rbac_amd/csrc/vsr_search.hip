@@ -169,6 +169,7 @@ RerankParams rerank_params(const vsr_ctx* ctx, const vsr_corpus* c, const char* 
     RerankParams rr{};
     rr.queries = reinterpret_cast<const SelectQuery*>(ds + off_sq);
     rr.rows = idc->d_rows;
+    rr.rows_half = c->half ? 1u : 0u;
     rr.stride4 = c->stride4;
     rr.queries_f = reinterpret_cast<const float*>(ds);
     rr.kp = kp;
@@ -469,6 +470,8 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
     Staging sb;
     sb.add((size_t) nq * qfloats * sizeof(float));          // queries
     const size_t off_qn = sb.add((size_t) nq * sizeof(float));
+    const bool k2h = plan.k2 && c->half;                    // K2h: the queries also as binary16, its B fragments
+    const size_t off_qh = sb.add(k2h ? (size_t) nq * qfloats * sizeof(uint16_t) : 0);
     const size_t off_g = sb.add(plan.groups);               // copied from here on
     const size_t off_gs = sb.add(plan.groups_s);
     const size_t off_qs = sb.add(plan.q_slots);
@@ -481,6 +484,7 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
     StageParams st{};                                       // (no query planes, no K2w counters on this path)
     RCCHK(stage_host_part(ctx, sb, off_qn, off_g, q.h_queries, q.d_queries, nq, q.dim, qfloats, st));
     st.q_half = c->half ? 1u : 0u;
+    if (k2h) st.q_h16 = reinterpret_cast<_Float16*>(ctx->d_desc.as<char>() + off_qh);
     RCCHK(ctx->d_partial.reserve(std::max<size_t>(8, (size_t) plan.n_partial * kp * sizeof(uint64_t))));
     char* ds = ctx->d_desc.as<char>();
     Timed whole(ctx, 5, ctx->stream);                       // the whole search on the device
@@ -489,6 +493,7 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
     ScanParams sp = scan_params(ctx, c, kp, plan.qmax);
     sp.queries = reinterpret_cast<const float*>(ds);
     sp.q_norm2 = reinterpret_cast<const float*>(ds + off_qn);
+    if (k2h) sp.q_scr = reinterpret_cast<const uint4*>(ds + off_qh);
     sp.partial = ctx->d_partial.as<uint64_t>();
     sp.cap = plan.k2 ? mfma_cap_for_k(kp) : scan_cap_for_rw((int) kp, c->shape.rw);
     if (plan.mq || plan.k2) {
@@ -528,7 +533,8 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
         sp.n_groups = (uint32_t) plan.groups_s.size();
         Timed sample(ctx, 3, ctx->stream);
         sp.kp = sp.k = SEED_LIST;
-        if (plan.k2) HIPCHK(launch_mfma(sp, metric, plan.n_blocks_s, ctx->stream));
+        if (k2h) HIPCHK(launch_mfmah(sp, metric, plan.n_blocks_s, ctx->stream));
+        else if (plan.k2) HIPCHK(launch_mfma(sp, metric, plan.n_blocks_s, ctx->stream));
         else HIPCHK(launch_mq(sp, metric, plan.n_blocks_s, ctx->stream));
         sp.kp = sp.k = kp;
         HIPCHK(sample.stop());
@@ -553,7 +559,8 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
         Timed main(ctx, cls, ctx->stream);
         if (!plan.block_map.empty() && !ctx->no_xcd_map) sp.block_map = reinterpret_cast<const uint2*>(ds + off_bm);
         const uint32_t launch_blocks = sp.block_map ? plan.n_launch : plan.n_blocks;
-        if (plan.k2) HIPCHK(launch_mfma(sp, metric, launch_blocks, ctx->stream));
+        if (k2h) HIPCHK(launch_mfmah(sp, metric, launch_blocks, ctx->stream));
+        else if (plan.k2) HIPCHK(launch_mfma(sp, metric, launch_blocks, ctx->stream));
         else if (plan.mq) HIPCHK(launch_mq(sp, metric, launch_blocks, ctx->stream));
         else if (c->half) HIPCHK(launch_scan_half(sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream));
         else HIPCHK(launch_scan(sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream));
@@ -573,7 +580,7 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
     if (plan.k2) {
         RerankParams rr = rerank_params(ctx, c, ds, off_sq, kp, q.k, metric, q.out);
         rr.lists = ctx->d_partial.as<uint64_t>() + (size_t) plan.rerank_base * kp;
-        rr.err_g = k2_err_g(c->dim);                       // K2's fp32 MFMA chain (vsr_bounds.h)
+        rr.err_g = c->half ? half_err_g(c->dim) : k2_err_g(c->dim);   // K2h's / K2's fp32 accumulation (vsr_bounds.h)
         rr.seeded = seed ? 1 : 0;
         rr.tau_init = seed ? ctx->d_tau.as<uint64_t>() : nullptr;
         HIPCHK(launch_rerank(rr, (uint32_t) nq, ctx->stream));

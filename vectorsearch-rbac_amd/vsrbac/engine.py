@@ -115,7 +115,8 @@ class Context:
         return buf.value.decode()
 
     def set_screening(self, enable=True):
-        """Allow the MFMA screening + exact re-rank path (K2/K5r) for shared passes."""
+        """Allow the MFMA screening + exact re-rank path for shared passes (K2 / K2w / K2g over an fp32 corpus, K2h over a
+        halfvec corpus; K5r behind them).  False: exact kernels only (K1 / K1m, K1h), and no search of this context flags."""
         check(self._lib.vsr_set_screening(self._h, int(bool(enable))))
 
     def screening_check(self, nq=0):
