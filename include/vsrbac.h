@@ -113,14 +113,17 @@ int vsr_corpus_load_half(vsr_ctx* ctx, const uint16_t* rows, int64_t n, int dim,
                          const int64_t* block_ids, const int32_t* doc_ids, int64_t row_offset,
                          vsr_corpus** out);
 int     vsr_corpus_is_half(const vsr_corpus* corpus);        /* 1 / 0 */
-/* device bytes holding VECTOR data of any corpus: rows, norms, every screening plane; identity arrays, RBAC tables and
- * filters excluded */
+/* device bytes holding VECTOR data of any corpus: rows, norms, every screening plane and, once vsr_rbac_load has built it,
+ * the class-ordered copy of the int8 planes; identity arrays, RBAC tables and filters excluded */
 int64_t vsr_corpus_device_bytes(const vsr_corpus* corpus);
 int     vsr_corpus_free(vsr_corpus* corpus);
 int64_t vsr_corpus_rows(const vsr_corpus* corpus);
 int     vsr_corpus_dim(const vsr_corpus* corpus);
 
-/* ---- RBAC tables (UserRoles, PermissionAssignment of controller/initialize_main_tables.py:17-72) ---- */
+/* ---- RBAC tables (UserRoles, PermissionAssignment of controller/initialize_main_tables.py:17-72) ----
+ * Drops the filters the corpus cached for the previous tables.  A corpus with int8 planes (integer 0..255 rows, d <= 128) also gets a copy of those
+ * planes in permission-class order here (~137 bytes per row) unless its context was opened under VSR_NO_CLASS_VIEW=1 or the
+ * memory is not there; searches never depend on it. */
 int vsr_rbac_load(vsr_corpus* corpus,
                   const int32_t* ur_user, const int32_t* ur_role, int64_t n_user_roles,
                   const int32_t* pa_role, const int32_t* pa_doc, int64_t n_permissions);

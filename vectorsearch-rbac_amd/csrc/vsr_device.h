@@ -83,6 +83,10 @@ struct FusedTail {
     uint64_t*       dbg;           // development (VSR_FUSED_DBG=1): 100 MHz timestamps of the workgroup that finishes the call; nullptr otherwise
 };
 
+#ifndef VSR_MW_DENSE
+#define VSR_MW_DENSE 1     // K2w int8 main launch of a class-view plan: rows by arithmetic (vsr_mfmaw.h, DENSE); 0: the general
+#endif                     // row mapping (variant libraries for A/B measurements)
+
 struct ScanParams {
     const float4*    rows;         // [n_rows][stride4] row-major, zero padded (K1h: [n_rows][stride4 / 2] chunks of 8 halves)
     const float*     norm2;        // [n_rows] sum x^2 (cosine)
@@ -124,6 +128,8 @@ struct ScanParams {
     uint32_t*        err;          // bounds-guard word: 1 = row index out of range, 2 = candidate buffer overflow, 4 = tile index
     uint32_t         epi;          // K2w main launch, L2: 1 = few survivors expected per wave-tile (mask epilogue), 0 = rounds
     uint32_t         k2i;          // int8 planes: bit 0 = the main launch (epi == 1), bit 1 = the sample launch runs as per-wave streams (K2i, vsr_i8s.h)
+    uint32_t         dense;        // K2w int8 main launch: 1 = every group's tile list is an identity list over one contiguous run of
+                                   // rows (a class-view plan): rows by arithmetic (vsr_mfmaw.h, DENSE)
     FusedTail        fused;        // K1, nq == 1 only (enable = 0 otherwise)
 };
 
@@ -357,6 +363,8 @@ hipError_t launch_pair_distances(const float* a, const float* b, int64_t n_pairs
                                  int metric, double* out, hipStream_t s);
 hipError_t launch_gather_rows(const float4* src, const float* src_norm, const uint32_t* rank, uint32_t n_rows, uint32_t stride4,
                               float4* dst, float* dst_norm, hipStream_t s);
+hipError_t launch_gather_class_view(const uint4* src, const float* src_norm, uint32_t* rank, uint32_t n_rows, uint4* dst,
+                                    float* dst_norm, hipStream_t s);
 hipError_t launch_view_bitmap(const uint32_t* rank, uint32_t n_rows, const uint2* tiles, uint32_t n_tiles, const uint64_t* bitmap,
                               uint64_t* out, hipStream_t s);
 hipError_t launch_ivf_probe(const float* queries, uint32_t q_stride, uint32_t nq, const float* centers_t /* [dim][lists] */, int dim, int lists, int probes,

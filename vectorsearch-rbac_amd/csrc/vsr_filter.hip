@@ -13,6 +13,7 @@ static void purge_index_caches(vsr_corpus* c, const vsr_filter* f)
 void vsr::drop_cached_filters(vsr_corpus* c)
 {
     purge_index_caches(c, nullptr);                  // the indexes' view-order bitmaps and probe parts of every filter
+    c->class_view.reset();                           // (its order is the classes')
     for (vsr_filter* f : c->class_filters) free_filter(f);
     c->class_filters.clear();
     for (vsr_filter* f : c->class_bitmap_filters) free_filter(f);
@@ -22,6 +23,8 @@ void vsr::drop_cached_filters(vsr_corpus* c)
     for (auto& kv : c->cache) free_filter(kv.second);
     c->cache.clear();
 }
+
+static void build_class_view(vsr_corpus* c);
 
 extern "C" int vsr_rbac_load(vsr_corpus* c, const int32_t* ur_user, const int32_t* ur_role, int64_t n_ur,
                              const int32_t* pa_role, const int32_t* pa_doc, int64_t n_pa)
@@ -84,6 +87,7 @@ extern "C" int vsr_rbac_load(vsr_corpus* c, const int32_t* ur_user, const int32_
             HIPCHK(hipMemcpy(c->d_doc_class, c->doc_class.data(), c->doc_class.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     c->rbac = true;
+    build_class_view(c);
     return VSR_OK;
 }
 
@@ -214,6 +218,59 @@ static int upload_aligned_ranges(vsr_filter* f, const Ranges& ranges)
 constexpr size_t MAX_CLASSES = 4096;        // beyond this (e.g. random RBAC: a signature per document) filters stay whole
 constexpr size_t MAX_PARTS = 64;
 
+// The class view of the int8 planes (ClassView, vsr_runtime.h), rebuilt whenever the classes are (vsr_rbac_load).  The
+// corpus simply has none when it does not apply or cannot be allocated: every call is then planned on the base planes.
+// The int8 planes and their norms once more (classes padded to 64 rows) plus 4.5 bytes per row of rank and tile list
+// (10M x 128: 1.4 GB).
+static void build_class_view(vsr_corpus* c)
+{
+    c->class_view.reset();
+    vsr_ctx* ctx = c->ctx;
+    const size_t n_cls = c->class_sig.size();
+    if (!c->d_scr8 || !c->d_norm2_8 || c->base || ctx->no_class_view || c->shape.rw != 16 || c->n == 0 || n_cls == 0 ||
+        n_cls > MAX_CLASSES)
+        return;
+    std::unique_ptr<ClassView> v(new ClassView());
+    v->start.assign(n_cls, 0);
+    v->rows.assign(n_cls, 0);
+    for (size_t di = 0; di < c->docs.size(); ++di) v->rows[c->doc_class[di]] += c->doc_row_start[di + 1] - c->doc_row_start[di];
+    uint64_t total = 0;
+    for (size_t cls = 0; cls < n_cls; ++cls) {
+        v->start[cls] = (uint32_t) total;
+        total += align_up(v->rows[cls], 64);
+        if (total >= 0xFFFFFF00ull) return;
+    }
+    v->n_rows = (uint32_t) total;
+    // view row -> base row: documents in base order, each appended to its class; pads stay ~0u for the gather kernel
+    std::vector<uint32_t> rank((size_t) total, 0xFFFFFFFFu), at(v->start);
+    for (size_t di = 0; di < c->docs.size(); ++di) {
+        uint32_t& p = at[c->doc_class[di]];
+        for (uint32_t r = c->doc_row_start[di]; r < c->doc_row_start[di + 1]; ++r) rank[p++] = r;
+    }
+    // identity tile list; a tile counts only the rows of its class (the last one of a class fewer than 16, pad tiles none)
+    std::vector<uint2> tiles((size_t) (total / 16));
+    for (size_t cls = 0; cls < n_cls; ++cls)
+        for (uint32_t o = 0; o < (uint32_t) align_up(v->rows[cls], 64); o += 16)
+            tiles[(v->start[cls] + o) / 16] = make_uint2(v->start[cls] + o, o < v->rows[cls] ? std::min(16u, v->rows[cls] - o) : 0u);
+    const size_t scr_bytes = ((size_t) total + 32) * 128, norm_bytes = ((size_t) total + 64) * sizeof(float);
+    bool ok = hipSetDevice(ctx->device) == hipSuccess;
+    ok = ok && hipMalloc(&v->d_scr8, scr_bytes) == hipSuccess;
+    ok = ok && hipMalloc(&v->d_norm2_8, norm_bytes) == hipSuccess;
+    ok = ok && hipMalloc(&v->d_rank, (size_t) total * sizeof(uint32_t)) == hipSuccess;
+    ok = ok && hipMalloc(&v->d_tiles, tiles.size() * sizeof(uint2)) == hipSuccess;
+    ok = ok && hipMemcpy(v->d_rank, rank.data(), (size_t) total * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(v->d_tiles, tiles.data(), tiles.size() * sizeof(uint2), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemsetAsync(reinterpret_cast<char*>(v->d_scr8) + (size_t) total * 128, 0, 32 * 128, ctx->stream) == hipSuccess;
+    ok = ok && hipMemsetAsync(v->d_norm2_8 + total, 0xFF, 64 * sizeof(float), ctx->stream) == hipSuccess;     // (NaN)
+    ok = ok && launch_gather_class_view(c->d_scr8, c->d_norm2_8, v->d_rank, v->n_rows, v->d_scr8, v->d_norm2_8, ctx->stream) == hipSuccess;
+    ok = ok && hipStreamSynchronize(ctx->stream) == hipSuccess;
+    if (!ok) {
+        (void) hipGetLastError();                    // (out of memory: not an error of the load)
+        return;
+    }
+    c->class_view = std::move(v);
+}
+
 // the rows of one permission class as a RANGES filter (built once, owned by the corpus)
 static int class_filter(vsr_corpus* c, uint32_t cls, vsr_filter** out)
 {
@@ -227,6 +284,7 @@ static int class_filter(vsr_corpus* c, uint32_t cls, vsr_filter** out)
     int rc = upload_ranges(f.get(), ranges);
     if (rc) return rc;
     f->allowed_rows = f->scanned_rows = rows;
+    f->view_class = (int32_t) cls;
     c->class_filters[cls] = f.release();
     *out = c->class_filters[cls];
     return VSR_OK;
@@ -269,6 +327,7 @@ static int class_parts(vsr_corpus* c, const std::vector<uint64_t>& m, int (*make
         if (rc) return rc;
         if (part->n_tiles) f->parts.push_back(part);
     }
+    if (f->parts.size() == 1 && f->mode == VSR_FILTER_RANGES && !f->d_bitmap) f->view_class = f->parts[0]->view_class;   // its rows are that class
     if (f->parts.size() > MAX_PARTS || f->parts.size() < 2) f->parts.clear();
     return VSR_OK;
 }

@@ -1201,6 +1201,38 @@ hipError_t launch_gather_rows(const float4* src, const float* src_norm, const ui
     return hipGetLastError();
 }
 
+// the int8 planes in permission-class order (ClassView, vsr_runtime.h): view row p <- base row rank[p]; rank[p] == ~0u marks
+// a pad row: zero planes, |row|^2 = NaN, and its rank becomes 0 (no tile counts a pad row, so no key ever carries it)
+__global__ __launch_bounds__(256) void gather_class_view_kernel(const uint4* src, const float* src_norm, uint32_t* rank, uint32_t n_rows,
+                                                                uint4* dst, float* dst_norm)
+{
+    const uint64_t total = (uint64_t) n_rows * 8;
+    for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t) gridDim.x * 256) {
+        const uint32_t p = (uint32_t) (i >> 3), c = (uint32_t) (i & 7);
+        const uint32_t r = rank[p];
+        const bool pad = r == 0xFFFFFFFFu;
+        dst[i] = pad ? make_uint4(0u, 0u, 0u, 0u) : src[(size_t) r * 8 + c];
+        if (c == 0) dst_norm[p] = pad ? __builtin_nanf("") : src_norm[r];
+    }
+}
+
+__global__ __launch_bounds__(256) void clear_pad_ranks_kernel(uint32_t* rank, uint32_t n_rows)
+{
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (p < n_rows && rank[p] == 0xFFFFFFFFu) rank[p] = 0u;
+}
+
+hipError_t launch_gather_class_view(const uint4* src, const float* src_norm, uint32_t* rank, uint32_t n_rows, uint4* dst,
+                                    float* dst_norm, hipStream_t s)
+{
+    if (n_rows == 0) return hipSuccess;
+    const uint64_t total = (uint64_t) n_rows * 8;
+    hipLaunchKernelGGL(gather_class_view_kernel, dim3((uint32_t) std::min<uint64_t>((total + 255) / 256, 16384)), dim3(256), 0, s, src,
+                       src_norm, rank, n_rows, dst, dst_norm);
+    hipLaunchKernelGGL(clear_pad_ranks_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, s, rank, n_rows);   // (stream order: after the gather)
+    return hipGetLastError();
+}
+
 // a filter of the base corpus as a per-row bitmap in view order: bit(p) = base row rank[p] lies in one of the filter's
 // tiles (sorted by start) and, when the filter carries a bitmap, has its bit set
 __global__ __launch_bounds__(256) void view_bitmap_kernel(const uint32_t* rank, uint32_t n_rows, const uint2* tiles,

@@ -103,7 +103,11 @@ __device__ __forceinline__ void lds_barrier()
 // PL: plane kind of the corpus (ScanParams::plane_ho): 0 = bf16 hi + mid, 1 = bf16 hi only, 2 = int8 (u8-exact corpus and
 // queries, elements stored as x - 128; L2 only: |x' - q'|^2 = |x - q|^2, exact in int32 / fp32; 128 bytes per row, the
 // tile image has 8 chunks per row and v_mfma_i32_16x16x64_i8 covers d = 128 in two instructions).
-template <int METRIC, int NCH, bool SAMPLE, int PL, int DEPTH, int EPI = 0, int NGT = 1>
+// DENSE (int8 main launch of a class-view plan, ScanParams::dense): the pass's tile list is a slice of the view's identity
+// list over ONE contiguous run of rows, so the workgroup's rows are [row_lo, row_hi) and slot s of tile `it` is row
+// row_lo + 64 it + s: two descriptor loads in the prologue, then no descriptor, no bitmap word and no row index read in
+// front of the row loads -- their addresses are affine in the tile index -- and |row|^2 of a tile is one coalesced 256-byte read.
+template <int METRIC, int NCH, bool SAMPLE, int PL, int DEPTH, int EPI = 0, int NGT = 1, bool DENSE = false>
 __global__ __launch_bounds__(MW_THREADS, mw_occ(NCH, PL, SAMPLE)) void mfma_wide_kernel(const ScanParams p)
 {
     constexpr bool HO = PL == 1, I8 = PL == 2;
@@ -116,6 +120,7 @@ __global__ __launch_bounds__(MW_THREADS, mw_occ(NCH, PL, SAMPLE)) void mfma_wide
     constexpr int NU = I8 ? 2 : 4;                                             // chunks a thread stages per tile and stage
     static_assert(!I8 || (NCH == 1 && METRIC == M_L2), "int8 planes: one stage (d <= 128), L2 only");
     static_assert(!LONG || DEPTH == 1, "long rows: one stage ahead");
+    static_assert(!DENSE || (I8 && !SAMPLE), "dense rows: the int8 main launch only");
     static_assert(DEPTH >= 1 && DEPTH <= 4 && DEPTH + 2 <= MW_RING, "row-mapping ring too short");
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x;
@@ -272,6 +277,22 @@ __global__ __launch_bounds__(MW_THREADS, mw_occ(NCH, PL, SAMPLE)) void mfma_wide
         dsc_a[j] = make_uint2(0u, 0u);
     }
     bool bad_row = false;                                          // cannot happen; reported once at the end
+    uint32_t row_lo = 0, row_hi = 0;                               // DENSE: this workgroup's rows (wave-uniform)
+    if constexpr (DENSE) {
+        const uint2 da = load_tile(g_tiles, t0 < tile_last ? t0 : tile_last);
+        const uint2 db = load_tile(g_tiles, t1 > t0 && t1 - 1u < tile_last ? t1 - 1u : tile_last);
+        row_lo = (uint32_t) __builtin_amdgcn_readfirstlane((int) da.x);
+        row_hi = t1 > t0 ? (uint32_t) __builtin_amdgcn_readfirstlane((int) (db.x + db.y)) : row_lo;
+        bad_row = row_hi > p.n_rows || row_hi < row_lo;
+        row_hi = bad_row ? row_lo : row_hi;
+    }
+    auto start_dense = [&](uint32_t it_, int32_t& row, uint64_t& bw, float& nrm) {   // the lane's slot of tile it_
+        const uint32_t rr = row_lo + it_ * (uint32_t) MW_ROWS + (uint32_t) lane;
+        const bool ok = it_ < n_it && rr < row_hi;
+        row = ok ? (int32_t) rr : -1;
+        bw = ~0ull;
+        nrm = g_norm2[ok ? rr : 0u];
+    };
     auto start_rows = [&](uint2 d, int32_t& row, uint64_t& bw, float& nrm) {
         const uint32_t r = (uint32_t) lane % rw;
         const uint32_t rr = d.x + r;
@@ -294,7 +315,17 @@ __global__ __launch_bounds__(MW_THREADS, mw_occ(NCH, PL, SAMPLE)) void mfma_wide
             if constexpr (ITEST) rowthr[(it_ % MW_RING) * 64 + lane] = row >= 0 ? ((int32_t) nrm) >> 1 : 0x7FFFFFFF;
         }
     };
-    {
+    if constexpr (DENSE) {
+#pragma unroll
+        for (int j = 0; j < DEPTH; ++j) {
+            int32_t r0;
+            uint64_t b0;
+            float n0;
+            start_dense((uint32_t) j, r0, b0, n0);
+            finish_rows((uint32_t) j, r0, b0, n0);
+            start_dense((uint32_t) (DEPTH + j), pend_row[j], pend_bw[j], pend_nrm[j]);
+        }
+    } else {
         uint2 d[2 * DEPTH];
 #pragma unroll
         for (int j = 0; j < 2 * DEPTH; ++j) d[j] = fetch_desc((uint32_t) j);
@@ -327,8 +358,14 @@ __global__ __launch_bounds__(MW_THREADS, mw_occ(NCH, PL, SAMPLE)) void mfma_wide
         const int32_t* ridx = rowidx + (it_ % MW_RING) * 64;
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
-            const int32_t r = ridx[u * LROWS + lrow];
-            const uint32_t rc = (uint32_t) (r < 0 ? 0 : r);
+            uint32_t rc;
+            if constexpr (DENSE) {
+                const uint32_t rr = row_lo + it_ * (uint32_t) MW_ROWS + (uint32_t) (u * LROWS + lrow);
+                rc = it_ < n_it && rr < row_hi ? rr : 0u;
+            } else {
+                const int32_t r = ridx[u * LROWS + lrow];
+                rc = (uint32_t) (r < 0 ? 0 : r);
+            }
             if ((VSR_ABLATE & 8) && it_ > 0) continue;
             const u32x4 v = *reinterpret_cast<const u32x4*>(p.scr + (size_t) (rc < last_row ? rc : last_row) * pstride4 + chunk);
             X[D][S][u] = make_uint4(v[0], v[1], v[2], v[3]);
@@ -482,8 +519,11 @@ __global__ __launch_bounds__(MW_THREADS, mw_occ(NCH, PL, SAMPLE)) void mfma_wide
                     if (f_n) flush_store();                        // the image write above waited for this tile's rows, which
                                                                    // were issued after the atomics: their results are here
                     finish_rows(it + DEPTH, pend_row[D], pend_bw[D], pend_nrm[D]);
-                    start_rows(dsc_a[D], pend_row[D], pend_bw[D], pend_nrm[D]);
-                    dsc_a[D] = fetch_desc(it + 3 * DEPTH);
+                    if constexpr (DENSE) start_dense(it + 2 * DEPTH, pend_row[D], pend_bw[D], pend_nrm[D]);
+                    else {
+                        start_rows(dsc_a[D], pend_row[D], pend_bw[D], pend_nrm[D]);
+                        dsc_a[D] = fetch_desc(it + 3 * DEPTH);
+                    }
                 }
                 lds_barrier();
                 if constexpr (S == 0) {
@@ -815,6 +855,9 @@ hipError_t launch_mfmaw_metric(const ScanParams& p, uint32_t n_blocks, hipStream
         if (p.plane_ho == 2) {
             if constexpr (N == 1 && METRIC == M_L2) {                          // int8 planes: d <= 128, L2
                 if ((few && (p.k2i & 1u)) || (sample && (p.k2i & 2u))) return launch_i8_stream(p, n_blocks, s);   // per-wave streams (vsr_i8s.h)
+                if (p.dense && !sample)                                        // class view: rows by arithmetic
+                    return few ? launch(mfma_wide_kernel<METRIC, 1, false, 2, VSR_MW_DEPTH8, 1, 1, true>)
+                               : launch(mfma_wide_kernel<METRIC, 1, false, 2, VSR_MW_DEPTH8, 0, 1, true>);
                 return sample ? launch(mfma_wide_kernel<METRIC, 1, true, 2, mw_sample_depth(1, 2)>)
                               : few ? launch(mfma_wide_kernel<METRIC, 1, false, 2, VSR_MW_DEPTH8, 1>)
                                     : launch(mfma_wide_kernel<METRIC, 1, false, 2, VSR_MW_DEPTH8>);

@@ -16,6 +16,7 @@ struct PlanScalars {
     bool     k2 = false;          // shared passes run on K2 / K2w (MFMA screening) + K5r
     bool     k2w = false;         // ... on K2w: workgroup-shared row tiles, up to 128 queries per pass (vsr_mfmaw.h)
     bool     int8 = false;        // ... on the corpus's int8 planes (L2, integer 0..255 rows and queries)
+    bool     class_view = false;  // ... on the corpus's class view of the int8 planes (every pass a whole permission class)
     bool     k2g = false;         // ... on K2g: long rows, 256-query passes, coarse planes (vsr_gemm.h); implies k2w
     uint32_t keep = 0;            // partial list length kp (K2: 2k screening survivors; else k)
     uint32_t rerank_base = 0;     // K2: first partial list holding the per-query screening survivors

@@ -20,7 +20,10 @@ struct PlanIn {                              // what one make_plan call is asked
 };
 
 struct PassItem { const vsr_filter* part; uint32_t slot; };     // part: atomic filter scanned (nullptr = whole corpus)
-struct Pass { const vsr_filter* f; uint32_t q_off, q_count; int64_t rows; uint32_t n_tiles; int64_t cost; };
+struct Pass {
+    const vsr_filter* f; uint32_t q_off, q_count; int64_t rows; uint32_t n_tiles; int64_t cost;
+    const uint2* vtiles;                     // class view: the class's slice of the view's tile list (nullptr: the part's own list)
+};
 
 constexpr uint32_t XCDS = 8;
 
@@ -195,6 +198,7 @@ uint32_t cut_passes(const PlanIn& in, const Width& w, const std::vector<PassItem
             pd.q_count = cnt;
             pd.rows = f ? f->scanned_rows : c->n;
             pd.n_tiles = f ? f->n_tiles : (uint32_t) ((c->n + c->shape.rw - 1) / c->shape.rw);
+            pd.vtiles = nullptr;
             // relative cost of a row of this pass: K2w passes are bound by the row stream up to ~3 query groups and by
             // the matrix pipe beyond (a 64-row tile costs 4 * groups * d/4 MFMAs), so fat passes get more workgroups
             const int64_t groups = (cnt + 15) / 16;
@@ -224,6 +228,35 @@ void set_family(const PlanIn& in, const Width& w, uint32_t widest, Plan& plan)
     if (plan.int8) plan.keep = (uint32_t) std::max(in.k, 32);  // exact screening: no second half of survivors to re-rank
     plan.k2g = plan.k2w && w.k2g && !plan.int8;
     if (plan.k2g) plan.keep = w.keep_c;                     // coarse screening: a wider survivor list for the exact re-rank
+}
+
+// ---- stage 3b: the class view ------------------------------------------------------------------------------------
+// A call scans the corpus's class view (ClassView, vsr_runtime.h) when it screens on the int8 planes with K2w and EVERY pass's
+// part is one whole permission class: a class filter of the corpus, or a role filter that sees a single class (RANGES, no
+// bitmap, every scanned row permitted).  All or nothing: one unfiltered query, BITMAP part or ad-hoc filter and the call is
+// planned on the base planes exactly as before.  A pass's tile list becomes its class's slice of the view's identity list,
+// ceil(rows / 16) tiles without a dead slot except in the last; its rows -- and every count made of them -- stay rows.
+bool take_class_view(const PlanIn& in, const Plan& plan, std::vector<Pass>& passes)
+{
+    const ClassView* v = in.c->class_view.get();
+    if (!v || in.ctx->no_class_view || !plan.int8 || plan.k2g) return false;
+    bool any = false;
+    for (const Pass& p : passes) {
+        const vsr_filter* f = p.f;
+        if (f && f->scanned_rows == 0) continue;            // (a role that sees nothing: never launched)
+        if (!f || f->view_class < 0 || (size_t) f->view_class >= v->rows.size() || f->mode != VSR_FILTER_RANGES || f->d_bitmap ||
+            f->allowed_rows != f->scanned_rows || f->scanned_rows != (int64_t) v->rows[(size_t) f->view_class])
+            return false;
+        any = true;
+    }
+    if (!any) return false;
+    for (Pass& p : passes) {
+        if (!p.f || p.f->scanned_rows == 0) continue;
+        const size_t cls = (size_t) p.f->view_class;
+        p.vtiles = v->d_tiles + v->start[cls] / 16;
+        p.n_tiles = (v->rows[cls] + 15) / 16;
+    }
+    return true;
 }
 
 // ---- stage 4: workgroups of the launch ---------------------------------------------------------------------------
@@ -280,7 +313,7 @@ void emit_groups(const PlanIn& in, bool i8wide, const LaunchSize& ls, PlanScratc
         nb = std::min<int64_t>(nb, std::max<uint32_t>(1, p.n_tiles));
         nb = std::max<int64_t>(nb, 1);
         ScanGroup g;
-        g.tiles = p.f ? p.f->d_tiles : plan.k2w ? c->d_all_tiles : nullptr;
+        g.tiles = p.vtiles ? p.vtiles : p.f ? p.f->d_tiles : plan.k2w ? c->d_all_tiles : nullptr;
         g.bitmap = p.f ? p.f->d_bitmap : nullptr;
         g.n_tiles = p.n_tiles;
         g.q_begin = p.q_off;
@@ -602,6 +635,7 @@ bool vsr::make_plan(const vsr_ctx* ctx, const vsr_corpus* c, int nq, int k, int 
     const Width w = choose_width(in, s.gend, allow_screening, allow_wide, allow_gemm);
     const uint32_t widest = cut_passes(in, w, s.items, s.passes, plan.q_slots);
     set_family(in, w, widest, plan);
+    plan.class_view = take_class_view(in, plan, s.passes);
     const LaunchSize ls = size_launch(in, plan, s.passes);
     emit_groups(in, w.i8wide, ls, s, plan);
     if (plan.k2 || plan.mq) map_blocks_to_xcds(s.lane, plan);
@@ -637,5 +671,7 @@ std::string vsr::scan_kernel_name(const Plan& plan, const vsr_corpus* c, int met
     else
         snprintf(buf, sizeof buf, "vsr::scan_kernel<%s, LPR=%d, C=%d, R=%d, QI=%d%s", mname[metric], c->shape.lpr, c->shape.c,
                  c->shape.r, plan.qi, c->half ? ", HALF=true> (K1h, half rows)" : "> (K1)");
-    return buf;
+    std::string name = buf;
+    if (plan.class_view) name.insert(name.rfind(')'), ", class view");
+    return name;
 }

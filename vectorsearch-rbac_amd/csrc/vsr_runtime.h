@@ -155,6 +155,7 @@ struct vsr_ctx {
     bool no_scan8 = false;         // VSR_NO_SCAN8=1: one-query calls on the fp32 rows even when the int8 planes apply (A/B)
     bool k2i_wide = false;         // VSR_K2I_WIDE=1 (with VSR_K2I=1): 128-column passes on K2i
     int  force_epi = -1;           // VSR_FORCE_EPI=0|1: the main launch's survivor handling regardless of the estimate (tests)
+    bool no_class_view = false;    // VSR_NO_CLASS_VIEW=1: role pre-filters scan the base-order int8 planes, never the class view (A/B)
     int  screen_level = 2;         // search_impl -> make_plan: 2 = every screening tier, 1 = no coarse tier (K2g), 0 = exact only
     bool last_coarse = false;      // the last search screened on the coarse planes: its flagged queries go to the fine tier first
 
@@ -192,9 +193,32 @@ struct vsr_filter {
     // the planner scans class by class so that queries of different roles share the classes they have in common
     std::vector<vsr_filter*> parts;
     bool parts_only = false;               // the filter has no tile list of its own: always scanned part by part (IVF probes)
+    int32_t view_class = -1;               // RANGES filter whose rows are exactly one permission class (a corpus's class filter, or
+                                           // a role filter that sees a single class): that class, for the class view (ClassView)
     // planner scratch (one planner per context at a time): group id of this filter in the plan being built
     mutable uint64_t plan_epoch = 0;
     mutable uint32_t plan_group = 0;
+};
+
+// Class view: a second, derived copy of the int8 planes in permission-class order (vsr_filter.hip: build_class_view).
+// Class after class, rows inside a class in base order, every class starting at a multiple of 64 rows; pad rows are zero
+// planes with |row|^2 = NaN and no tile ever counts them.  A call whose passes are all whole classes scans a class as ONE
+// contiguous run of full 16-row tiles instead of one short range per document (make_plan, search_wide); candidate keys
+// carry base rows through `rank`, as the IVFFlat views' do.  Built by vsr_rbac_load, dropped with the classes.
+struct ClassView {
+    uint4*    d_scr8 = nullptr;          // [n_rows + 32][8] int8 planes (whole tiles may be read past the last row)
+    float*    d_norm2_8 = nullptr;       // [n_rows + 64]
+    uint32_t* d_rank = nullptr;          // [n_rows] view row -> base row (pads: 0, never emitted)
+    uint2*    d_tiles = nullptr;         // [n_rows / 16] (16 t, rows of the class that tile t holds: 16, fewer at a class's end, 0)
+    uint32_t  n_rows = 0;                // with the pads: a multiple of 64
+    std::vector<uint32_t> start, rows;   // per class: first view row, row count
+    size_t bytes() const { return ((size_t) n_rows + 32) * 128 + ((size_t) n_rows + 64) * 4 + (size_t) n_rows * 4 + (size_t) n_rows / 16 * 8; }
+    ~ClassView()
+    {
+        void* ptrs[] = {d_scr8, d_norm2_8, d_rank, d_tiles};
+        for (void* p : ptrs)
+            if (p) (void) hipFree(p);
+    }
 };
 
 struct vsr_corpus {
@@ -248,6 +272,8 @@ struct vsr_corpus {
     std::vector<vsr_filter*> class_filters;          // per class, built on first use (RANGES, owned by the corpus)
     std::vector<vsr_filter*> class_bitmap_filters;   // per class, BITMAP mode: aligned windows + the class's own bitmap
     uint32_t* d_doc_class = nullptr;                 // class of every document (device copy of doc_class)
+    std::unique_ptr<ClassView> class_view;           // the int8 planes in class order; none: no int8 planes, too many classes,
+                                                     // VSR_NO_CLASS_VIEW, or no memory for it
     // indexes loaded over this corpus: a filter that dies (vsr_filter_free, vsr_rbac_load) is purged from their caches
     std::vector<struct vsr_ivf*>  ivf_indexes;
     std::vector<struct vsr_hnsw*> hnsw_indexes;

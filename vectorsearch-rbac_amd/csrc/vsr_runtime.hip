@@ -89,6 +89,7 @@ extern "C" int vsr_open(int device, vsr_ctx** out)
     if ((env = getenv("VSR_NO_SCAN8"))) ctx->no_scan8 = atoi(env) != 0;
     if ((env = getenv("VSR_NO_K2I_SAMPLE"))) ctx->k2i_sample = atoi(env) == 0;
     if ((env = getenv("VSR_NO_CLASSES"))) ctx->no_classes = atoi(env) != 0;
+    if ((env = getenv("VSR_NO_CLASS_VIEW"))) ctx->no_class_view = atoi(env) != 0;
     if ((env = getenv("VSR_DEBUG"))) ctx->debug = (uint32_t) atoi(env);
     if ((env = getenv("VSR_NO_SEED"))) ctx->seeding = atoi(env) == 0;
     if ((env = getenv("VSR_NO_FUSED"))) ctx->no_fused = atoi(env) != 0;
@@ -415,6 +416,7 @@ extern "C" int64_t vsr_corpus_device_bytes(const vsr_corpus* c)
     if (c->d_scr_c) b += coarse_plane_u4((uint64_t) rows, c->cstride4) * 16 + 1024;
     if (c->d_scr8) b += rows * (size_t) 128 + 4096;
     if (c->d_norm2_8) b += (rows + 64) * sizeof(float);
+    if (c->class_view) b += c->class_view->bytes();         // (built by vsr_rbac_load, not at load)
     return (int64_t) b;
 }
 

@@ -260,6 +260,13 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
         sp.q_scr = reinterpret_cast<const uint4*>(ds + off_q8);
         sp.pstride4 = 8;
         sp.plane_ho = 2u;
+        if (plan.class_view) {                              // the same planes in class order; keys carry base rows through rank
+            const ClassView* v = c->class_view.get();
+            sp.scr = v->d_scr8;
+            sp.norm2 = v->d_norm2_8;
+            sp.rank = v->d_rank;
+            sp.n_rows = v->n_rows;
+        }
     }
     if (plan.k2g) {
         sp.scr_c = c->d_scr_c;
@@ -312,6 +319,7 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
         if (plan.int8 && plan.qmax > 64) sp.epi = 1u;       // 128-column passes exist on K2i only (its parking area takes bursts)
         sp.k2i = plan.int8 && !plan.k2g && sp.epi == 1 && !ctx->no_k2i && sp.rw == 16 && sp.qmax <= 128 ? 1u : 0u;
         ctx->last_k2i = sp.k2i != 0;
+        sp.dense = plan.class_view && VSR_MW_DENSE ? 1u : 0u;   // (the sample launch keeps the general row mapping)
         sp.tau_init = ctx->d_tau.as<uint64_t>();
         sp.qcand = ctx->d_cand.as<uint64_t>();
         sp.qcnt = qcnt;
