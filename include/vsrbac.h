@@ -420,7 +420,8 @@ typedef struct {
 int vsr_profiling(vsr_ctx* ctx, int enable);      /* HIP events on the launch stream: 1 = around every launch class (scan, sample, K5), 2 = around the main scan launch only, 0 = off */
 int vsr_stats_get(vsr_ctx* ctx, vsr_stats* out);  /* synchronises, accumulates pending events */
 int vsr_stats_reset(vsr_ctx* ctx);
-/* name of the kernel instantiation the main scan launch of the session's last search resolved to ("" before any) */
+/* name of the kernel instantiation the main scan launch of the session's last search resolved to ("" before any); searches
+   screened on the int8 planes append " + sample <kernel>", the instantiation of their sample launch */
 int vsr_last_scan_kernel(vsr_ctx* ctx, char* name, int name_len);
 
 /* launch-shape knobs (measurement only): blocks per launch budget, min rows per workgroup, queries per pass */

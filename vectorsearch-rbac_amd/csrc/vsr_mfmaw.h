@@ -44,6 +44,7 @@
 #include "vsr_topk.h"
 #include "vsr_mfma.h"
 #include "vsr_i8s.h"
+#include "vsr_i8r.h"
 
 namespace vsr {
 
@@ -854,6 +855,7 @@ hipError_t launch_mfmaw_metric(const ScanParams& p, uint32_t n_blocks, hipStream
         constexpr int D = mw_depth(N);
         if (p.plane_ho == 2) {
             if constexpr (N == 1 && METRIC == M_L2) {                          // int8 planes: d <= 128, L2
+                if (sample && (p.k2i & 4u)) return launch_i8_sample_reg(p, n_blocks, s);                          // class view: register-fed sample (vsr_i8r.h)
                 if ((few && (p.k2i & 1u)) || (sample && (p.k2i & 2u))) return launch_i8_stream(p, n_blocks, s);   // per-wave streams (vsr_i8s.h)
                 if (p.dense && !sample)                                        // class view: rows by arithmetic
                     return few ? launch(mfma_wide_kernel<METRIC, 1, false, 2, VSR_MW_DEPTH8, 1, 1, true>)

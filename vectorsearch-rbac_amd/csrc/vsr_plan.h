@@ -23,6 +23,7 @@ struct PlanScalars {
     uint32_t n_scan_lists = 0;
     uint32_t qmax = 1;            // query slots per workgroup
     bool     k2i_sample = false;  // int8 planes: the sample pass runs as K2i's per-wave streams (vsr_i8s.h, SAMPLE)
+    bool     k2r_sample = false;  // ... of a class-view plan: the same sample from the register-fed kernel (K2r, vsr_i8r.h)
     uint32_t n_blocks_s = 0;
     uint32_t n_partial_s = 0;
     uint32_t n_partial = 0;       // scan partial lists + level-1 K5 outputs (+ K2 survivor lists)

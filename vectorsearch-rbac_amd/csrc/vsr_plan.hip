@@ -292,7 +292,7 @@ LaunchSize size_launch(const PlanIn& in, const Plan& plan, const std::vector<Pas
         // the sample launch visits every ss-th tile: a workgroup of it is all prologue and memory latency, so it gets ONE
         // resident round of workgroups (each then walks ~12 tiles instead of three rounds walking 4: 72 -> ~45 us on the
         // 10M-row corpus); launches that fit one round anyway (a shard) keep the main launch's workgroups
-        const int64_t slots = (plan.k2g ? 1 : plan.int8 ? 4 : 3) * cus;
+        const int64_t slots = (plan.k2g ? 1 : plan.int8 ? 4 : 3) * cus * ctx->sample_rounds;   // (VSR_SAMPLE_ROUNDS: measurements only)
         ls.seed_div = (uint32_t) std::max<int64_t>(1, (ls.budget + slots - 1) / slots);
     }
     return ls;
@@ -639,7 +639,11 @@ bool vsr::make_plan(const vsr_ctx* ctx, const vsr_corpus* c, int nq, int k, int 
     const LaunchSize ls = size_launch(in, plan, s.passes);
     emit_groups(in, w.i8wide, ls, s, plan);
     if (plan.k2 || plan.mq) map_blocks_to_xcds(s.lane, plan);
-    if (plan.k2w) return plan_wide_sampling(in, s, plan);
+    if (plan.k2w) {
+        const bool ok = plan_wide_sampling(in, s, plan);
+        plan.k2r_sample = ok && plan.class_view && plan.k2i_sample && ctx->sample_reg;   // same geometry, same entries (vsr_i8r.h)
+        return ok;
+    }
     build_select_items(in, ls.seed_div, s, plan);
     return true;
 }

@@ -140,7 +140,7 @@ struct vsr_ctx {
     double extra_ms[2] = {0, 0};   // sample scan, seed select (profiling only)
     double host_us[3] = {0, 0, 0}; // VSR_DEBUG: host time in make_plan / waiting for the staging buffer / whole search_impl
     long   host_calls = 0;
-    std::string last_kernel;       // main scan kernel of the last search (vsr_last_scan_kernel)
+    std::string last_kernel;       // main scan kernel of the last search (vsr_last_scan_kernel); int8 K2w plans: " + sample <kernel>" appended
     bool no_classes = false;       // VSR_NO_CLASSES=1: scan role partitions whole (A/B measurements)
     bool max_qb_set = false;       // VSR_MAX_QB / vsr_tune chose the queries per pass: the planner does not override it
     bool no_xcd_map = false;       // VSR_NO_XCD_MAP=1: workgroups in pass order instead of XCD-aware bundles (A/B)
@@ -151,6 +151,8 @@ struct vsr_ctx {
     bool no_k2i = true;            // VSR_K2I=1: the int8 main launch as K2i's per-wave streams instead of K2w's workgroup tiles (A/B;
                                    // measured on the headline step: K2w 0.342 ms, K2i 0.366 ms -- K2w stays the default)
     bool last_k2i = false;         // the last main launch was eligible for K2i
+    uint32_t sample_rounds = 1;    // VSR_SAMPLE_ROUNDS=1..4: resident rounds of workgroups the K2w-family sample launch is cut into (A/B)
+    bool sample_reg = true;        // VSR_SAMPLE_REG=0: the int8 sample pass of a class-view plan on K2i's streams instead of K2r's registers (A/B)
     bool k2i_sample = true;        // VSR_NO_K2I_SAMPLE=1: the int8 sample pass on K2w's kernel instead of K2i's streams (A/B)
     bool no_scan8 = false;         // VSR_NO_SCAN8=1: one-query calls on the fp32 rows even when the int8 planes apply (A/B)
     bool k2i_wide = false;         // VSR_K2I_WIDE=1 (with VSR_K2I=1): 128-column passes on K2i

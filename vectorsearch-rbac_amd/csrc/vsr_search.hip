@@ -287,7 +287,7 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
         sp.qcand = ctx->d_samp.as<uint64_t>();
         sp.qcnt = scnt;
         sp.capq = GQ_SAMPLE_CAP;
-        sp.k2i = plan.k2i_sample ? 2u : 0u;                 // (bit 1: the sample launch on K2i; bit 0: the main launch)
+        sp.k2i = plan.k2r_sample ? 4u : plan.k2i_sample ? 2u : 0u;   // (bit 2: the sample launch on K2r; bit 1: on K2i; bit 0: the main launch)
         HIPCHK(launch_pass(plan.n_blocks_s, ctx->stream));
         HIPCHK(launch_seed_select(ctx->d_samp.as<uint64_t>(), scnt, GQ_SAMPLE_CAP, plan.kp_frac, ctx->d_tau.as<uint64_t>(),
                                   (uint32_t) nq, ctx->stream));
@@ -319,7 +319,7 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
         if (plan.int8 && plan.qmax > 64) sp.epi = 1u;       // 128-column passes exist on K2i only (its parking area takes bursts)
         sp.k2i = plan.int8 && !plan.k2g && sp.epi == 1 && !ctx->no_k2i && sp.rw == 16 && sp.qmax <= 128 ? 1u : 0u;
         ctx->last_k2i = sp.k2i != 0;
-        sp.dense = plan.class_view && VSR_MW_DENSE ? 1u : 0u;   // (the sample launch keeps the general row mapping)
+        sp.dense = plan.class_view && VSR_MW_DENSE ? 1u : 0u;   // (the sample launch: K2r, vsr_i8r.h, when the plan chose it)
         sp.tau_init = ctx->d_tau.as<uint64_t>();
         sp.qcand = ctx->d_cand.as<uint64_t>();
         sp.qcnt = qcnt;
@@ -332,6 +332,9 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
             HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->lane_out, 0));
         }
         ctx->last_kernel = scan_kernel_name(plan, c, metric, ctx->last_k2i);
+        if (plan.k2r_sample) ctx->last_kernel += " + sample vsr::i8_sample_reg_kernel<NQG=4> (K2r)";
+        else if (plan.k2i_sample) ctx->last_kernel += " + sample vsr::i8_stream_kernel<NQG=4, SAMPLE=true>";
+        else if (plan.int8) ctx->last_kernel += " + sample vsr::mfma_wide_kernel<L2, NCH=1, SAMPLE=true, PL=int8>";
         count_scan(ctx, plan, 1);
     }
 
