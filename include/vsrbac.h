@@ -61,7 +61,10 @@ typedef enum {
     VSR_METRIC_L2 = 0,          /* <->  sqrt(sum (a-b)^2)            */
     VSR_METRIC_IP = 1,          /* <#>  -sum a*b                     */
     VSR_METRIC_COSINE = 2,      /* <=>  1 - clamp(cos(a,b)), NaN for a zero vector (sorted last) */
-    VSR_METRIC_L1 = 3           /* <+>  sum |a-b|                    */
+    VSR_METRIC_L1 = 3,          /* <+>  sum |a-b|                    */
+    /* pgvector's type bit (sql/vector.sql: <~>, <%>); accepted by the *_bit entry points only */
+    VSR_METRIC_HAMMING = 4,     /* <~>  popcount(a ^ b)              */
+    VSR_METRIC_JACCARD = 5      /* <%>  |a&b| == 0 ? 1 : 1 - |a&b| / (double) (|a| + |b| - |a&b|)   (bitutils.c:96-129) */
 } vsr_metric;
 
 /* how a permission set is applied to the scan */
@@ -113,6 +116,38 @@ int vsr_corpus_load_half(vsr_ctx* ctx, const uint16_t* rows, int64_t n, int dim,
                          const int64_t* block_ids, const int32_t* doc_ids, int64_t row_offset,
                          vsr_corpus** out);
 int     vsr_corpus_is_half(const vsr_corpus* corpus);        /* 1 / 0 */
+/* pgvector's bit (bitvec.c, bitutils.c; what binary_quantize(vector | halfvec) returns, vector.c:941-968): rows[n][(dim + 7) / 8]
+ * bytes, tightly packed, in PostgreSQL's varbit order -- element i is bit 7 - i % 8 of byte i / 8.  dim counts bits, 1 .. 64000
+ * (HNSW_MAX_DIM * 32, the widest bit column a pgvector index takes, hnswutils.c:1403), anything else VSR_ERR_INVALID.  Bits past
+ * dim in the last byte are IGNORED: the library clears them on load and on query staging (varbit guarantees zero padding and
+ * pgvector relies on it; this library does not).  Everything else as vsr_corpus_load.  The rows stay packed on the device (16
+ * bytes per 128 bits, plus the row's popcount): no fp32 image, no norms, no planes, no class view.
+ * Searches go through vsr_search_bit / vsr_search_bit_device(_on), which are vsr_search / vsr_search_device(_on) with queries of
+ * (dim + 7) / 8 packed bytes (device queries need no alignment) and metric VSR_METRIC_HAMMING or VSR_METRIC_JACCARD.  out_dist is
+ * (float) of the operator's float8: a Hamming distance is an integer <= 64000 and exact in fp32; Jaccard is evaluated in double
+ * as bitutils.c does and then rounded, the way cosine is.  Order: ((float) distance ascending, document_id, block_id), as
+ * everywhere; keys are monotone(fp32) << 32 | global row, so vsr_merge_topk_* work untouched.  Rounding to fp32 is monotone: it
+ * can only merge two distinct float8 Jaccard values into a tie (then broken by the ids), never reorder them -- and not even
+ * that below 2049 dimensions, where two distinct fractions with denominators <= 2048 differ by more than an fp32 ulp.
+ * The scan is exact by construction (integer popcounts, K1b): nothing is screened, no query is ever flagged, counts are never
+ * negative, vsr_set_screening / vsr_set_query_hint have no effect.  All filters (vsr_rbac_load, the four vsr_filter_*
+ * constructors, both modes), k <= VSR_MAX_K, row_offset, sessions, raw keys, the shard merge, vsr_stats_get (scan_bytes counts
+ * (dim + 7) / 8 bytes per row) and vsr_corpus_device_bytes work as for any corpus.
+ * Errors.  A dimension mismatch is VSR_ERR_DIM_MISMATCH, "different bit lengths %u and %u" with the column's length first
+ * (CheckDims, bitvec.c:32-39).  vsr_search_bit* on a corpus that is not a bit corpus, or with a metric other than 4 / 5:
+ * VSR_ERR_INVALID.  vsr_search*, vsr_ivf_load, vsr_ivf_assign, vsr_hnsw_load and vsr_hnsw_build* over a bit corpus:
+ * VSR_ERR_UNSUPPORTED, the message names the bit corpus (the bit_hamming_ops / bit_jaccard_ops index opclasses are not built
+ * yet).  The float entry points keep rejecting metrics 4 / 5 with VSR_ERR_INVALID. */
+int vsr_corpus_load_bit(vsr_ctx* ctx, const uint8_t* rows, int64_t n, int dim,
+                        const int64_t* block_ids, const int32_t* doc_ids, int64_t row_offset,
+                        vsr_corpus** out);
+int     vsr_corpus_is_bit(const vsr_corpus* corpus);         /* 1 / 0 */
+/* binary_quantize over the RESIDENT rows of an fp32 or halfvec corpus, on the device: a new bit corpus of the same dim whose bit
+ * i is set where element i > 0 (a widened half is positive exactly when the half is).  Same context, same row identity
+ * (block / document ids, caller row indices, row_offset), same internal order.  RBAC tables are NOT inherited: run vsr_rbac_load
+ * on the new corpus.  The new corpus is independent of src (free either first).  src a bit corpus or an index view:
+ * VSR_ERR_INVALID. */
+int vsr_corpus_binary_quantize(vsr_corpus* src, vsr_corpus** out);
 /* device bytes holding VECTOR data of any corpus: rows, norms, every screening plane and, once vsr_rbac_load has built it,
  * the class-ordered copy of the int8 planes; identity arrays, RBAC tables and filters excluded */
 int64_t vsr_corpus_device_bytes(const vsr_corpus* corpus);
@@ -153,6 +188,13 @@ int vsr_search(vsr_corpus* corpus, const float* queries, int nq, int dim, int k,
                int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows,
                float* out_dist, int32_t* out_counts);
 
+/* vsr_search over a bit corpus (vsr_corpus_load_bit): queries[nq][(dim + 7) / 8] packed bytes, dim in bits, metric
+ * VSR_METRIC_HAMMING / VSR_METRIC_JACCARD */
+int vsr_search_bit(vsr_corpus* corpus, const uint8_t* queries, int nq, int dim, int k, int metric,
+                   const vsr_filter* const* filters,
+                   int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows,
+                   float* out_dist, int32_t* out_counts);
+
 /* same, queries and outputs in device memory, enqueued on the context's stream, no synchronisation.
  * out_keys (nq*k, may be NULL) receives the raw ordering keys (monotone fp32 distance << 32 | global row)
  * that vsr_merge_topk_device consumes. */
@@ -170,6 +212,16 @@ int vsr_search_device_on(vsr_ctx* session, vsr_corpus* corpus, const float* d_qu
                          const vsr_filter* const* filters,
                          int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows,
                          float* d_out_dist, int32_t* d_out_counts, uint64_t* d_out_keys);
+
+/* vsr_search_device / vsr_search_device_on over a bit corpus; d_queries needs no alignment.  Never flags. */
+int vsr_search_bit_device(vsr_corpus* corpus, const uint8_t* d_queries, int nq, int dim, int k, int metric,
+                          const vsr_filter* const* filters,
+                          int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows,
+                          float* d_out_dist, int32_t* d_out_counts, uint64_t* d_out_keys);
+int vsr_search_bit_device_on(vsr_ctx* session, vsr_corpus* corpus, const uint8_t* d_queries, int nq, int dim, int k, int metric,
+                             const vsr_filter* const* filters,
+                             int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows,
+                             float* d_out_dist, int32_t* d_out_counts, uint64_t* d_out_keys);
 
 /* same as vsr_search_device_on, but the call returns only when every query is PROVEN exact: it waits for the search,
  * and queries the screening flagged (below) are re-run on the exact path and patched into the outputs, all on the
@@ -220,6 +272,16 @@ int vsr_merge_topk_packed_device(vsr_ctx* ctx, const void* d_packed, int n_parts
  * what `SELECT a <-> b` evaluates per row (vector.c:568-578 etc.), batched.  Host pointers. */
 int vsr_pair_distances(vsr_ctx* ctx, int metric, const float* a, const float* b, int64_t n_pairs,
                        int dim_a, int dim_b, int b_broadcast, double* out);
+
+/* hamming_distance / jaccard_distance (bitvec.c:46-77) for n explicit pairs of bit strings, (dim + 7) / 8 packed bytes each
+ * (pad bits ignored), as vsr_pair_distances: metric 4 / 5, the operator's float8.  dim 0 is valid here:
+ * hamming_distance('', '') = 0, jaccard_distance('', '') = 1.  Unequal lengths: VSR_ERR_DIM_MISMATCH, "different bit lengths
+ * %u and %u".  Host pointers. */
+int vsr_bit_pair_distances(vsr_ctx* ctx, int metric, const uint8_t* a, const uint8_t* b, int64_t n_pairs,
+                           int dim_a, int dim_b, int b_broadcast, double* out);
+/* binary_quantize (vector.c:941-968) for n vectors: out[n][(dim + 7) / 8], bit i set where a[i] > 0 -- NaN, -0.0 and 0 give 0;
+ * pad bits zero.  Host pointers. */
+int vsr_binary_quantize(vsr_ctx* ctx, const float* a, int64_t n, int dim, uint8_t* out);
 
 /* ---- IVFFlat list probe (pgvector/src/ivfscan.c:36-176, 339-389) ------------------------------------------ */
 /* An index = `lists` centres (lists x dim floats) and the list of every corpus row (row_list[n], caller row order): what
@@ -401,7 +463,7 @@ typedef struct {
     /* K1 launches by kernel class: [0] = one query per pass, [1] = up to 4 queries sharing a pass */
     int64_t scan_launches[2];
     double  scan_ms[2];         /* sum of HIP-event durations of those launches          */
-    int64_t scan_bytes[2];      /* algorithmic bytes: rows*dim*4 (halfvec corpus: *2) + bitmap bytes + k*12 */
+    int64_t scan_bytes[2];      /* algorithmic bytes: rows*dim*4 (halfvec corpus: *2; bit corpus: rows*((dim+7)/8)) + bitmap bytes + k*12 */
     int64_t scan_rows[2];       /* rows scanned (per shared pass)                        */
     int64_t select_launches;    /* K5 */
     double  select_ms;

@@ -44,7 +44,7 @@ constexpr size_t   SCAN_LDS_BUDGET = 72 * 1024;   // per workgroup, so two workg
 // keys one workgroup may append per query between two overflow checks (tile rows x waves, >= 256)
 constexpr int scan_slack(int rw) { return SCAN_WAVES * rw > 256 ? SCAN_WAVES * rw : 256; }
 
-enum Metric : int { M_L2 = 0, M_IP = 1, M_COSINE = 2, M_L1 = 3 };
+enum Metric : int { M_L2 = 0, M_IP = 1, M_COSINE = 2, M_L1 = 3 };   // (bit corpora: MetricBit, vsr_scanb.h)
 
 // One unit of scan work: a (filter, <=QB queries) pair, spread over n_blocks workgroups.
 struct ScanGroup {
@@ -88,12 +88,13 @@ struct FusedTail {
 #endif                     // row mapping (variant libraries for A/B measurements)
 
 struct ScanParams {
-    const float4*    rows;         // [n_rows][stride4] row-major, zero padded (K1h: [n_rows][stride4 / 2] chunks of 8 halves)
-    const float*     norm2;        // [n_rows] sum x^2 (cosine)
+    const float4*    rows;         // [n_rows][stride4] row-major, zero padded (K1h: [n_rows][stride4 / 2] chunks of 8 halves;
+                                   // K1b: [n_rows][stride4] chunks of 128 packed bits)
+    const float*     norm2;        // [n_rows] sum x^2 (cosine; K1b: the row's popcount, Jaccard)
     uint32_t         n_rows;
-    uint32_t         stride4;      // float4 per row (K1h: per padded QUERY, two for every 16-byte row chunk)
-    const float*     queries;      // [n_slots][stride4*4], zero padded
-    const float*     q_norm2;      // [n_slots]
+    uint32_t         stride4;      // float4 per row (K1h: per padded QUERY, two for every 16-byte row chunk; K1b: 16-byte chunks)
+    const float*     queries;      // [n_slots][stride4*4], zero padded (K1b: [n_slots][stride4] chunks of packed bits)
+    const float*     q_norm2;      // [n_slots] (K1b: the query's popcount)
     const ScanGroup* groups;
     uint32_t         n_groups;
     const uint32_t*  q_slots;      // query slots of all passes, concatenated
@@ -222,16 +223,21 @@ struct KernelShape {
 KernelShape scan_shape_for_dim(int dim);
 // K1h (halfvec corpus): the same classes by the row's 16-byte chunks, ceil(dim / 8) of 8 halves each; c counts those chunks
 KernelShape scan_shape_for_dim_half(int dim);
+// K1b (bit corpus): ... by ceil(dim / 128) chunks of 128 packed bits
+KernelShape scan_shape_for_dim_bit(int dim);
 uint32_t scan_cap_for_k(int k, int dim);
 uint32_t scan_cap_for_rw(int k, int rw);                  // ... from the tile rows of either kind of corpus
 int  scan_qmax(int dim, int k);    // queries per pass the LDS budget allows (1, or a multiple of 4 up to SCAN_QMAX)
 int  scan_qmax_half(int dim, int k);
+int  scan_qmax_bit(int dim, int k);
 inline size_t scan_lds_bytes(uint32_t qmax, uint32_t cap, uint32_t stride4)
 {
     return (size_t) qmax * ((size_t) cap * 8 + 16 + (size_t) stride4 * 16 + 4) + 16;
 }
 hipError_t launch_scan(const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s);
 hipError_t launch_scan_half(const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s);   // K1h
+// K1b (vsr_scanb.h): Hamming (metric 4) / Jaccard (5) over a bit corpus; dim in bits
+hipError_t launch_scan_bit(const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s);
 // one query per call over the int8 planes (vsr_scan8.h): K1's top-k and in-kernel merge, a quarter of the bytes per row
 hipError_t launch_scan8_fused(const ScanParams& p, uint32_t dim, uint32_t* q8_bad_host, uint32_t n_blocks, hipStream_t s);
 // K1m (vsr_mq.h): shared-pass kernel for 2..16 queries per pass; needs dim >= 61 (>= 16 float4 per row)
@@ -328,6 +334,8 @@ struct StageParams {
     uint32_t     q_stride;
     float*       q_dst;            // nq x qfloats, zero padded
     uint32_t     dim, qfloats, nq;
+    uint32_t     q_bits;           // bit corpus (stage_bit_kernel, vsr_bit.hip): q_src holds nq x q_stride BYTES of packed bits, `dim` of them
+                                   // valid; q_dst receives nq x qfloats / 4 16-byte chunks, pad bits cleared; q_norm2 the popcounts
     uint32_t     q_half;           // halfvec corpus: every query element is rounded to binary16 and widened again (Float4ToHalf)
     _Float16*    q_h16;            // [nq][qfloats] the rounded queries as binary16 (K2h's B fragments), nullptr: not needed
     float*       q_norm2;          // [nq]
@@ -347,6 +355,16 @@ struct StageParams {
     uint32_t*    q8_bad_host;      // pinned host word <- 1 if any such query (the session then leaves the int8 path)
 };
 hipError_t launch_stage(const StageParams& p, hipStream_t s);
+hipError_t launch_stage_bit(const StageParams& p, hipStream_t s);      // p.q_bits != 0
+// bit corpora (vsr_bit.hip).  Popcount of every row of `chunks` 16-byte chunks, as fp32 (exact: <= 64000)
+hipError_t launch_row_popcounts(const uint4* rows, uint32_t n_rows, uint32_t chunks, float* pop, hipStream_t s);
+// binary_quantize (vector.c:941-968): bit = x > 0, element i -> bit 7 - i % 8 of byte i / 8.  src: n rows of src_stride elements
+// (fp32, or binary16 bit patterns when src_half), dim of them valid; dst: n rows of dst_bytes bytes, everything past dim zero
+hipError_t launch_binary_quantize(const void* src, int src_half, uint64_t n_rows, uint32_t dim, uint32_t src_stride, uint8_t* dst,
+                                  uint32_t dst_bytes, hipStream_t s);
+// hamming_distance / jaccard_distance (bitvec.c:46-77) for n explicit pairs of ceil(dim / 8) bytes; pad bits are ignored
+hipError_t launch_bit_pair_distances(const uint8_t* a, const uint8_t* b, int64_t n_pairs, int dim, int b_broadcast, int metric,
+                                     double* out, hipStream_t s);
 // int8 planes of a u8-exact corpus (d <= 128): scr8[row][8 chunks of 16 elements x - 128, zero padded], norm8 = sum (x-128)^2
 hipError_t launch_check_u8_exact(const float4* rows, uint32_t n_rows, uint32_t stride4, uint32_t* any_inexact, hipStream_t s);
 hipError_t launch_split_planes8(const float4* rows, uint32_t n_rows, uint32_t stride4, uint32_t dim, uint4* scr8, float* norm8,

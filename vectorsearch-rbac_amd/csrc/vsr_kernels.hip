@@ -16,6 +16,9 @@ hipError_t launch_scanh_l2(const ScanParams&, int, int, uint32_t, hipStream_t);
 hipError_t launch_scanh_ip(const ScanParams&, int, int, uint32_t, hipStream_t);
 hipError_t launch_scanh_cosine(const ScanParams&, int, int, uint32_t, hipStream_t);
 hipError_t launch_scanh_l1(const ScanParams&, int, int, uint32_t, hipStream_t);
+// ... and K1b (vsr_scanb_*.hip)
+hipError_t launch_scanb_hamming(const ScanParams&, int, int, uint32_t, hipStream_t);
+hipError_t launch_scanb_jaccard(const ScanParams&, int, int, uint32_t, hipStream_t);
 
 hipError_t launch_mq_l2(const ScanParams&, uint32_t, hipStream_t);
 hipError_t launch_mq_ip(const ScanParams&, uint32_t, hipStream_t);
@@ -126,6 +129,13 @@ KernelShape scan_shape_for_dim_half(int dim)
     return d8 <= 128 ? scan_shape_for_chunks(d8) : KernelShape{64, 0, 2, 2};
 }
 
+// (K1b: the same rule by chunks of 128 bits; 64000 bits are 500 chunks)
+KernelShape scan_shape_for_dim_bit(int dim)
+{
+    const int d128 = (dim + 127) / 128;
+    return d128 <= 128 ? scan_shape_for_chunks(d128) : KernelShape{64, 0, 2, 2};
+}
+
 uint32_t scan_cap_for_rw(int k, int rw)
 {
     // room for k kept keys plus one check interval of new ones, trigger level >= 2k so compactions amortise
@@ -150,6 +160,18 @@ static int scan_qmax_for(const KernelShape& sh, uint32_t stride4, int k)
 
 int scan_qmax(int dim, int k) { return scan_qmax_for(scan_shape_for_dim(dim), (uint32_t) ((dim + 3) / 4), k); }
 int scan_qmax_half(int dim, int k) { return scan_qmax_for(scan_shape_for_dim_half(dim), 2u * (uint32_t) ((dim + 7) / 8), k); }
+
+// (queries are a few chunks: the candidate buffers bound the queries per pass)
+int scan_qmax_bit(int dim, int k) { return scan_qmax_for(scan_shape_for_dim_bit(dim), (uint32_t) ((dim + 127) / 128), k); }
+
+hipError_t launch_scan_bit(const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s)
+{
+    switch (metric) {
+    case 4:  return launch_scanb_hamming(p, dim, qi, n_blocks, s);
+    case 5:  return launch_scanb_jaccard(p, dim, qi, n_blocks, s);
+    default: return hipErrorInvalidValue;
+    }
+}
 
 hipError_t launch_scan(const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s)
 {

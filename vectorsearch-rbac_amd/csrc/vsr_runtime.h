@@ -233,6 +233,9 @@ struct vsr_corpus {
     uint32_t    stride4 = 0;             // float4 per padded row (halfvec corpus: per padded QUERY, dim rounded up to 8 floats)
     bool        half = false;            // halfvec corpus (vsr_corpus_load_half): d_rows holds stride4 / 2 16-byte chunks of 8
                                          // binary16 values per row, no fp32 image, no screening planes; exact kernels only (K1h)
+    bool        bit = false;             // bit corpus (vsr_corpus_load_bit, vsr_corpus_binary_quantize): dim counts BITS, d_rows holds stride4
+                                         // 16-byte chunks of packed bits per row (pad bits zero), d_norm2 the rows' popcounts; no norms-max, no
+                                         // planes, no class view; exact kernel only (K1b)
     int64_t     row_offset = 0;
     KernelShape shape{};
     float4*     d_rows = nullptr;
@@ -396,8 +399,9 @@ inline size_t bitmap_words(int64_t n) { return (size_t) ((n + 63) / 64) + 2; }  
 void   purge_ivf_caches(vsr_corpus* c, const vsr_filter* f);
 void   purge_hnsw_caches(vsr_corpus* c, const vsr_filter* f);
 // vsr_search.hip
+// bit_entry: the caller is a vsr_search_bit* entry point (bit corpus, metrics 4 / 5); every other caller is refused a bit corpus
 int    check_search_args(const vsr_corpus* c, const void* queries, int nq, int dim, int k, int metric,
-                         const vsr_filter* const* filters, const char* who);
+                         const vsr_filter* const* filters, const char* who, bool bit_entry = false);
 int    host_search(vsr_corpus* c, const float* queries, int nq, int dim, int k, int metric, const vsr_filter* const* filters,
                    const Outputs& out);
 

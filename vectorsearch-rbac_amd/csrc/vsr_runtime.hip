@@ -236,18 +236,23 @@ vsr_corpus::~vsr_corpus()
 extern "C" int64_t vsr_corpus_rows(const vsr_corpus* c) { return c ? c->n : 0; }
 extern "C" int vsr_corpus_dim(const vsr_corpus* c) { return c ? c->dim : 0; }
 
-// vsr_corpus_load (ELEM = float) and vsr_corpus_load_half (ELEM = uint16_t, binary16 bit patterns): the same identity
-// arrays and row order; a halfvec corpus keeps its rows as they came -- 2 bytes per element -- plus |row|^2, nothing else
+// vsr_corpus_load (ELEM = float), vsr_corpus_load_half (ELEM = uint16_t, binary16 bit patterns) and vsr_corpus_load_bit
+// (ELEM = uint8_t, ceil(dim / 8) bytes of packed bits): the same identity arrays and row order; a halfvec corpus keeps its rows
+// as they came -- 2 bytes per element -- plus |row|^2, a bit corpus its bytes (pad bits cleared) plus the rows' popcounts,
+// nothing else
 template <class ELEM>
 static int corpus_load(vsr_ctx* ctx, const ELEM* rows, int64_t n, int dim, const int64_t* block_ids, const int32_t* doc_ids,
                        int64_t row_offset, vsr_corpus** out, const char* who)
 {
     constexpr bool HALF = sizeof(ELEM) == 2;
-    constexpr int PER16 = 16 / (int) sizeof(ELEM);          // elements per 16-byte chunk
+    constexpr bool BIT = sizeof(ELEM) == 1;
+    constexpr int PER16 = 16 / (int) sizeof(ELEM);          // elements per 16-byte chunk (bit corpus: bytes)
     if (!ctx || !out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
     *out = nullptr;
     if (n < 0 || (n > 0 && !rows)) return fail(VSR_ERR_INVALID, "%s: rows is NULL", who);
-    if (dim < 1 || dim > 16000)      // VECTOR_MAX_DIM, pgvector/src/vector.h:4; HALFVEC_MAX_DIM, halfvec.h
+    if (BIT && (dim < 1 || dim > 64000))   // HNSW_MAX_DIM * 32, the widest bit column an index takes (hnswutils.c:1403)
+        return fail(VSR_ERR_INVALID, "%s: bit must have between 1 and 64000 dimensions (got %d)", who, dim);
+    if (!BIT && (dim < 1 || dim > 16000))  // VECTOR_MAX_DIM, pgvector/src/vector.h:4; HALFVEC_MAX_DIM, halfvec.h
         return fail(VSR_ERR_INVALID, "%s: %s must have between 1 and 16000 dimensions (got %d)", who, HALF ? "halfvec" : "vector", dim);
     if (n + row_offset >= 0xFFFFFFFFll) return fail(VSR_ERR_UNSUPPORTED, "%s: more than 2^32-2 rows per shard", who);
     HIPCHK(hipSetDevice(ctx->device));
@@ -257,10 +262,12 @@ static int corpus_load(vsr_ctx* ctx, const ELEM* rows, int64_t n, int dim, const
     c->n = n;
     c->dim = dim;
     c->half = HALF;
-    const uint32_t row_chunks = (uint32_t) ((dim + PER16 - 1) / PER16);   // 16-byte chunks per row
+    c->bit = BIT;
+    const int in_elems = BIT ? (dim + 7) / 8 : dim;         // elements per row as the caller holds them
+    const uint32_t row_chunks = (uint32_t) ((in_elems + PER16 - 1) / PER16);   // 16-byte chunks per row
     c->stride4 = HALF ? 2 * row_chunks : row_chunks;
     c->row_offset = row_offset;
-    c->shape = HALF ? scan_shape_for_dim_half(dim) : scan_shape_for_dim(dim);
+    c->shape = BIT ? scan_shape_for_dim_bit(dim) : HALF ? scan_shape_for_dim_half(dim) : scan_shape_for_dim(dim);
 
     // internal order: (document_id, block_id); identity when the input is already sorted that way
     std::vector<int64_t> perm((size_t) n);
@@ -298,15 +305,17 @@ static int corpus_load(vsr_ctx* ctx, const ELEM* rows, int64_t n, int dim, const
     const size_t alloc_rows = (size_t) std::max<int64_t>(n, 1);
     HIPCHK(hipMalloc(&c->d_rows, alloc_rows * row_bytes + 1024));
     HIPCHK(hipMalloc(&c->d_norm2, alloc_rows * sizeof(float)));
-    HIPCHK(hipMalloc(&c->d_norm2_max, 64));
-    HIPCHK(hipMemset(c->d_norm2_max, 0, 64));
+    if (!BIT) {
+        HIPCHK(hipMalloc(&c->d_norm2_max, 64));
+        HIPCHK(hipMemset(c->d_norm2_max, 0, 64));
+    }
     HIPCHK(hipMalloc(&c->d_block, alloc_rows * sizeof(int64_t)));
     HIPCHK(hipMalloc(&c->d_doc, alloc_rows * sizeof(int32_t)));
     HIPCHK(hipMalloc(&c->d_orig, alloc_rows * sizeof(int64_t)));
     HIPCHK(hipMalloc(&c->d_row_docidx, alloc_rows * sizeof(uint32_t)));
 
     if (n > 0) {
-        if (sorted && dim % PER16 == 0) {
+        if (sorted && in_elems % PER16 == 0 && !(BIT && dim % 8)) {
             HIPCHK(hipMemcpy(c->d_rows, rows, (size_t) n * row_bytes, hipMemcpyHostToDevice));
         } else {
             // permute + zero-pad through a bounded host staging buffer
@@ -316,9 +325,13 @@ static int corpus_load(vsr_ctx* ctx, const ELEM* rows, int64_t n, int dim, const
             for (int64_t base = 0; base < n; base += (int64_t) chunk_rows) {
                 const int64_t m = std::min<int64_t>((int64_t) chunk_rows, n - base);
                 std::fill(stage.begin(), stage.begin() + (size_t) m * row_elems, ELEM(0));
-                for (int64_t i = 0; i < m; ++i)
-                    memcpy(&stage[(size_t) i * row_elems], rows + (size_t) perm[(size_t) (base + i)] * dim,
-                           (size_t) dim * sizeof(ELEM));
+                for (int64_t i = 0; i < m; ++i) {
+                    memcpy(&stage[(size_t) i * row_elems], rows + (size_t) perm[(size_t) (base + i)] * in_elems,
+                           (size_t) in_elems * sizeof(ELEM));
+                    // varbit guarantees zero pad bits and pgvector relies on it; this library clears them
+                    if constexpr (BIT)
+                        if (dim % 8) stage[(size_t) i * row_elems + (size_t) in_elems - 1] &= (ELEM) (0xFF00u >> (dim % 8));
+                }
                 HIPCHK(hipMemcpy(reinterpret_cast<char*>(c->d_rows) + (size_t) base * row_bytes, stage.data(),
                                  (size_t) m * row_bytes, hipMemcpyHostToDevice));
             }
@@ -327,6 +340,12 @@ static int corpus_load(vsr_ctx* ctx, const ELEM* rows, int64_t n, int dim, const
         HIPCHK(hipMemcpy(c->d_doc, h_doc.data(), (size_t) n * sizeof(int32_t), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(c->d_orig, perm.data(), (size_t) n * sizeof(int64_t), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(c->d_row_docidx, h_docidx.data(), (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (BIT) {                                          // the rows' popcounts (Jaccard), exact in fp32; nothing else
+            HIPCHK(launch_row_popcounts(reinterpret_cast<const uint4*>(c->d_rows), (uint32_t) n, row_chunks, c->d_norm2, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            *out = c.release();
+            return VSR_OK;
+        }
         if (HALF) {
             // the rows are the corpus and their own screening plane (K2h): no fp32 image, no planes.  As below, a corpus
             // holding NaN / Inf (or norms that overflow) stays on the exact kernel, K1h
@@ -406,6 +425,104 @@ extern "C" int vsr_corpus_load_half(vsr_ctx* ctx, const uint16_t* rows, int64_t 
 }
 
 extern "C" int vsr_corpus_is_half(const vsr_corpus* c) { return c && c->half ? 1 : 0; }
+
+extern "C" int vsr_corpus_load_bit(vsr_ctx* ctx, const uint8_t* rows, int64_t n, int dim, const int64_t* block_ids,
+                                   const int32_t* doc_ids, int64_t row_offset, vsr_corpus** out)
+{
+    return corpus_load(ctx, rows, n, dim, block_ids, doc_ids, row_offset, out, "vsr_corpus_load_bit");
+}
+
+extern "C" int vsr_corpus_is_bit(const vsr_corpus* c) { return c && c->bit ? 1 : 0; }
+
+// binary_quantize over the resident rows: a bit corpus with the source's context, row identity and internal order.  RBAC
+// tables are not inherited (filters belong to one corpus): the caller runs vsr_rbac_load on the new corpus.
+extern "C" int vsr_corpus_binary_quantize(vsr_corpus* src, vsr_corpus** out)
+{
+    if (!src || !out) return fail(VSR_ERR_INVALID, "vsr_corpus_binary_quantize: NULL argument");
+    *out = nullptr;
+    if (src->bit) return fail(VSR_ERR_INVALID, "vsr_corpus_binary_quantize: the corpus is a bit corpus already");
+    if (src->base) return fail(VSR_ERR_INVALID, "vsr_corpus_binary_quantize: this corpus is an index view");
+    vsr_ctx* ctx = src->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    std::unique_ptr<vsr_corpus> c(new vsr_corpus());
+    c->ctx = ctx;
+    c->n = src->n;
+    c->dim = src->dim;
+    c->bit = true;
+    const uint32_t row_chunks = (uint32_t) ((src->dim + 127) / 128);
+    c->stride4 = row_chunks;
+    c->row_offset = src->row_offset;
+    c->shape = scan_shape_for_dim_bit(src->dim);
+    c->h_orig = src->h_orig;
+    c->docs = src->docs;
+    c->doc_row_start = src->doc_row_start;
+    const size_t rows = (size_t) std::max<int64_t>(src->n, 1), n = (size_t) src->n;
+    HIPCHK(hipMalloc(&c->d_rows, rows * row_chunks * 16 + 1024));
+    HIPCHK(hipMalloc(&c->d_norm2, rows * sizeof(float)));
+    HIPCHK(hipMalloc(&c->d_block, rows * sizeof(int64_t)));
+    HIPCHK(hipMalloc(&c->d_doc, rows * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&c->d_orig, rows * sizeof(int64_t)));
+    HIPCHK(hipMalloc(&c->d_row_docidx, rows * sizeof(uint32_t)));
+    if (n > 0) {
+        HIPCHK(hipMemcpyAsync(c->d_block, src->d_block, n * sizeof(int64_t), hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(c->d_doc, src->d_doc, n * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(c->d_orig, src->d_orig, n * sizeof(int64_t), hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(c->d_row_docidx, src->d_row_docidx, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        // (both kinds of source row hold stride4 * 4 elements: fp32 rows stride4 float4, half rows stride4 / 2 chunks of 8)
+        HIPCHK(launch_binary_quantize(src->d_rows, src->half ? 1 : 0, (uint64_t) n, (uint32_t) src->dim, src->stride4 * 4u,
+                                      reinterpret_cast<uint8_t*>(c->d_rows), row_chunks * 16u, ctx->stream));
+        HIPCHK(launch_row_popcounts(reinterpret_cast<const uint4*>(c->d_rows), (uint32_t) n, row_chunks, c->d_norm2, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    *out = c.release();
+    return VSR_OK;
+}
+
+// binary_quantize (vector.c:941-968) for n host vectors -> n x ceil(dim / 8) bytes
+extern "C" int vsr_binary_quantize(vsr_ctx* ctx, const float* a, int64_t n, int dim, uint8_t* out)
+{
+    if (!ctx || n < 0 || (n > 0 && (!a || !out))) return fail(VSR_ERR_INVALID, "vsr_binary_quantize: NULL argument");
+    if (dim < 1) return fail(VSR_ERR_INVALID, "vsr_binary_quantize: dim %d", dim);
+    if (n == 0) return VSR_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t a_bytes = (size_t) n * dim * sizeof(float), o_bytes = (size_t) n * (size_t) ((dim + 7) / 8);
+    const size_t o_out = align_up(a_bytes, 256);
+    int rc = ctx->d_misc.reserve(o_out + o_bytes);
+    if (rc) return rc;
+    char* d = ctx->d_misc.as<char>();
+    HIPCHK(hipMemcpyAsync(d, a, a_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(launch_binary_quantize(d, 0, (uint64_t) n, (uint32_t) dim, (uint32_t) dim, reinterpret_cast<uint8_t*>(d + o_out),
+                                  (uint32_t) ((dim + 7) / 8), ctx->stream));
+    HIPCHK(hipMemcpyAsync(out, d + o_out, o_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return VSR_OK;
+}
+
+// hamming_distance / jaccard_distance for n explicit pairs (bitvec.c:46-77); dim 0 is a valid bit string
+extern "C" int vsr_bit_pair_distances(vsr_ctx* ctx, int metric, const uint8_t* a, const uint8_t* b, int64_t n_pairs, int dim_a,
+                                      int dim_b, int b_broadcast, double* out)
+{
+    if (!ctx || n_pairs < 0 || (n_pairs > 0 && !out)) return fail(VSR_ERR_INVALID, "vsr_bit_pair_distances: NULL argument");
+    if (dim_a < 0 || dim_b < 0) return fail(VSR_ERR_INVALID, "vsr_bit_pair_distances: negative bit length");
+    if (dim_a != dim_b) return fail(VSR_ERR_DIM_MISMATCH, "different bit lengths %u and %u", (unsigned) dim_a, (unsigned) dim_b);   // CheckDims, bitvec.c:32-39
+    if (dim_a > 0 && n_pairs > 0 && (!a || !b)) return fail(VSR_ERR_INVALID, "vsr_bit_pair_distances: NULL argument");
+    if (metric != VSR_METRIC_HAMMING && metric != VSR_METRIC_JACCARD) return fail(VSR_ERR_INVALID, "vsr_bit_pair_distances: metric %d", metric);
+    if (n_pairs == 0) return VSR_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t) ((dim_a + 7) / 8);
+    const size_t a_bytes = (size_t) n_pairs * bytes, b_bytes = (size_t) (b_broadcast ? 1 : n_pairs) * bytes;
+    const size_t o_b = align_up(a_bytes, 256), o_out = align_up(o_b + b_bytes, 256);
+    int rc = ctx->d_misc.reserve(o_out + (size_t) n_pairs * sizeof(double));
+    if (rc) return rc;
+    char* d = ctx->d_misc.as<char>();
+    if (a_bytes) HIPCHK(hipMemcpyAsync(d, a, a_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (b_bytes) HIPCHK(hipMemcpyAsync(d + o_b, b, b_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(launch_bit_pair_distances(reinterpret_cast<uint8_t*>(d), reinterpret_cast<uint8_t*>(d + o_b), n_pairs, dim_a, b_broadcast,
+                                     metric, reinterpret_cast<double*>(d + o_out), ctx->stream));
+    HIPCHK(hipMemcpyAsync(out, d + o_out, (size_t) n_pairs * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return VSR_OK;
+}
 
 // rows, norms and every screening plane as allocated at load (a view's own image: its base is another corpus)
 extern "C" int64_t vsr_corpus_device_bytes(const vsr_corpus* c)

@@ -89,10 +89,12 @@ int wait_for_staging_block(vsr_ctx* ctx)
 // copy + gather + norm + two fills: it pulls the descriptor block out of the pinned host buffer, pads the queries to the row
 // stride (from the caller's device buffer, or from the staged host copy), computes |q|^2 with the arithmetic of the row
 // norms, clears the per-query flags and seeds.  The queries' section is the block's first, |q|^2 lies at off_qn.
+// (bits: the queries are packed bit strings -- a bit corpus: `dim` bits = ceil(dim / 8) bytes per query, padded to qfloats * 4 bytes)
 int stage_host_part(vsr_ctx* ctx, const Staging& sb, size_t off_qn, size_t off_g, const float* h_queries, const float* d_queries,
-                    int nq, int dim, size_t qfloats, StageParams& st)
+                    int nq, int dim, size_t qfloats, StageParams& st, bool bits = false)
 {
     const size_t h_q_bytes = h_queries ? align_up((size_t) nq * qfloats * sizeof(float), 256) : 0;
+    const size_t src_bytes = bits ? (size_t) (dim + 7) / 8 : (size_t) dim * sizeof(float);
     RCCHK(wait_for_staging_block(ctx));
     RCCHK(ctx->h_desc.reserve(h_q_bytes + (sb.total - off_g)));
     RCCHK(ctx->d_desc.reserve(sb.total));
@@ -101,11 +103,11 @@ int stage_host_part(vsr_ctx* ctx, const Staging& sb, size_t off_qn, size_t off_g
     char* hs = ctx->h_desc.as<char>();
     char* ds = ctx->d_desc.as<char>();
     if (h_queries) {
-        float* hq = reinterpret_cast<float*>(hs);
+        const size_t slot_bytes = qfloats * sizeof(float);
         for (int s = 0; s < nq; ++s) {
-            float* dst = hq + (size_t) s * qfloats;
-            memcpy(dst, h_queries + (size_t) s * dim, (size_t) dim * sizeof(float));
-            for (size_t j = (size_t) dim; j < qfloats; ++j) dst[j] = 0.0f;
+            char* dst = hs + (size_t) s * slot_bytes;
+            memcpy(dst, reinterpret_cast<const char*>(h_queries) + (size_t) s * src_bytes, src_bytes);
+            memset(dst + src_bytes, 0, slot_bytes - src_bytes);
         }
     }
     sb.fill(hs + h_q_bytes, off_g);
@@ -115,6 +117,10 @@ int stage_host_part(vsr_ctx* ctx, const Staging& sb, size_t off_qn, size_t off_g
     st.n16 = (uint32_t) ((sb.total - off_g) / 16);
     st.q_src = d_queries ? d_queries : reinterpret_cast<const float*>(hd);
     st.q_stride = d_queries ? (uint32_t) dim : (uint32_t) qfloats;
+    if (bits) {                                             // byte strides; stage_bit_kernel clears the pad bits and counts the ones
+        st.q_stride = d_queries ? (uint32_t) src_bytes : (uint32_t) (qfloats * sizeof(float));
+        st.q_bits = 1u;
+    }
     st.q_dst = reinterpret_cast<float*>(ds);
     st.dim = (uint32_t) dim;
     st.qfloats = (uint32_t) qfloats;
@@ -127,7 +133,7 @@ int stage_host_part(vsr_ctx* ctx, const Staging& sb, size_t off_qn, size_t off_g
 
 int launch_staging(vsr_ctx* ctx, const StageParams& st)
 {
-    HIPCHK(launch_stage(st, ctx->stream));
+    HIPCHK(st.q_bits ? launch_stage_bit(st, ctx->stream) : launch_stage(st, ctx->stream));
     HIPCHK(hipEventRecord(ctx->desc_done, ctx->stream));
     ctx->desc_pending = true;
     return VSR_OK;
@@ -192,6 +198,7 @@ void count_scan(vsr_ctx* ctx, const Plan& plan, int cls)    // cls: 0 = one quer
 }
 
 // one search call as the launch sequences see it.  d_queries == nullptr: queries come from `h_queries`.
+// (bit corpus: the query pointers address packed bit strings, ceil(dim / 8) bytes each)
 struct Call { const float *h_queries, *d_queries; int nq, dim, k, metric; Outputs out; };
 
 // ---- K2w / K2g ---------------------------------------------------------------------------------------------------
@@ -363,6 +370,7 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
 uint32_t fused_fan(const vsr_ctx* ctx, const vsr_corpus* c, const Plan& plan, const Call& q)
 {
     // (K1h rounds the query to binary16 itself as it enters LDS: no staging kernel needed for that either)
+    if (c->bit) return 0;                                   // K1b does not instantiate the in-kernel merge: staging + K1b + K5
     if (!(q.nq == 1 && !ctx->no_fused && plan.groups.size() == 1 && plan.qi == 1 && !plan.k2 && !plan.mq && q.dim % (c->half ? 8 : 4) == 0 &&
           q.metric != VSR_METRIC_COSINE && plan.groups[0].n_blocks <= 64u * 64u && ctx->profiling != 1))
         return 0;
@@ -493,7 +501,7 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
     const size_t off_bm = sb.add(plan.block_map);
 
     StageParams st{};                                       // (no query planes, no K2w counters on this path)
-    RCCHK(stage_host_part(ctx, sb, off_qn, off_g, q.h_queries, q.d_queries, nq, q.dim, qfloats, st));
+    RCCHK(stage_host_part(ctx, sb, off_qn, off_g, q.h_queries, q.d_queries, nq, q.dim, qfloats, st, c->bit));
     st.q_half = c->half ? 1u : 0u;
     if (k2h) st.q_h16 = reinterpret_cast<_Float16*>(ctx->d_desc.as<char>() + off_qh);
     RCCHK(ctx->d_partial.reserve(std::max<size_t>(8, (size_t) plan.n_partial * kp * sizeof(uint64_t))));
@@ -574,6 +582,7 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
         else if (plan.k2) HIPCHK(launch_mfma(sp, metric, launch_blocks, ctx->stream));
         else if (plan.mq) HIPCHK(launch_mq(sp, metric, launch_blocks, ctx->stream));
         else if (c->half) HIPCHK(launch_scan_half(sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream));
+        else if (c->bit) HIPCHK(launch_scan_bit(sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream));
         else HIPCHK(launch_scan(sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream));
         HIPCHK(main.stop());
         ctx->last_kernel = scan_kernel_name(plan, c, metric);
@@ -651,26 +660,33 @@ int search_impl(vsr_ctx* ctx, vsr_corpus* c, const Call& q, const vsr_filter* co
 }  // namespace
 
 int vsr::check_search_args(const vsr_corpus* c, const void* queries, int nq, int dim, int k, int metric,
-                           const vsr_filter* const* filters, const char* who)
+                           const vsr_filter* const* filters, const char* who, bool bit_entry)
 {
     if (!c) return fail(VSR_ERR_INVALID, "%s: corpus is NULL", who);
+    if (bit_entry && !c->bit) return fail(VSR_ERR_INVALID, "%s: the corpus is not a bit corpus", who);
+    if (c->bit && !bit_entry)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: a bit corpus is searched with vsr_search_bit* (<~> / <%%>) and has no index path yet", who);
     if (nq < 0 || (nq > 0 && !queries)) return fail(VSR_ERR_INVALID, "%s: queries is NULL", who);
+    if (dim != c->dim && c->bit)                            // CheckDims, bitvec.c:32-39: the column's length first
+        return fail(VSR_ERR_DIM_MISMATCH, "different bit lengths %u and %u", (unsigned) c->dim, (unsigned) dim);
     if (dim != c->dim)                                      // CheckDims: vector.c:60-67, halfvec.c:60-67
         return fail(VSR_ERR_DIM_MISMATCH, "different %s dimensions %d and %d", c->half ? "halfvec" : "vector", c->dim, dim);
     if (k < 1) return fail(VSR_ERR_INVALID, "%s: k must be >= 1 (got %d)", who, k);
     if (k > VSR_MAX_K) return fail(VSR_ERR_UNSUPPORTED, "%s: k = %d exceeds VSR_MAX_K = %d", who, k, VSR_MAX_K);
-    if (metric < VSR_METRIC_L2 || metric > VSR_METRIC_L1) return fail(VSR_ERR_INVALID, "%s: metric %d", who, metric);
+    if (bit_entry ? metric != VSR_METRIC_HAMMING && metric != VSR_METRIC_JACCARD : metric < VSR_METRIC_L2 || metric > VSR_METRIC_L1)
+        return fail(VSR_ERR_INVALID, "%s: metric %d", who, metric);
     if (filters)
         for (int i = 0; i < nq; ++i)
             if (filters[i] && filters[i]->corpus != c) return fail(VSR_ERR_INVALID, "%s: filter %d belongs to another corpus", who, i);
     return VSR_OK;
 }
 
-extern "C" int vsr_search_device_on(vsr_ctx* session, vsr_corpus* c, const float* d_queries, int nq, int dim, int k,
-                                    int metric, const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc,
-                                    int64_t* d_row, float* d_dist, int32_t* d_cnt, uint64_t* d_keys)
+// vsr_search_device_on and vsr_search_bit_device_on (bit_entry: d_queries addresses packed bit strings)
+static int search_device_on(vsr_ctx* session, vsr_corpus* c, const float* d_queries, int nq, int dim, int k, int metric,
+                            const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc, int64_t* d_row, float* d_dist,
+                            int32_t* d_cnt, uint64_t* d_keys, bool bit_entry)
 {
-    int rc = check_search_args(c, d_queries, nq, dim, k, metric, filters, "vsr_search_device");
+    int rc = check_search_args(c, d_queries, nq, dim, k, metric, filters, bit_entry ? "vsr_search_bit_device" : "vsr_search_device", bit_entry);
     if (rc) return rc;
     vsr_ctx* ctx = session ? session : c->ctx;
     if (ctx->device != c->ctx->device) return fail(VSR_ERR_INVALID, "vsr_search_device_on: session and corpus are on different devices");
@@ -682,6 +698,28 @@ extern "C" int vsr_search_device_on(vsr_ctx* session, vsr_corpus* c, const float
         d_doc = ctx->d_misc.as<int32_t>();
     }
     return search_impl(ctx, c, {nullptr, d_queries, nq, dim, k, metric, {d_blk, d_doc, d_row, d_dist, d_cnt, d_keys}}, filters, 2);
+}
+
+extern "C" int vsr_search_device_on(vsr_ctx* session, vsr_corpus* c, const float* d_queries, int nq, int dim, int k,
+                                    int metric, const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc,
+                                    int64_t* d_row, float* d_dist, int32_t* d_cnt, uint64_t* d_keys)
+{
+    return search_device_on(session, c, d_queries, nq, dim, k, metric, filters, d_blk, d_doc, d_row, d_dist, d_cnt, d_keys, false);
+}
+
+extern "C" int vsr_search_bit_device_on(vsr_ctx* session, vsr_corpus* c, const uint8_t* d_queries, int nq, int dim, int k,
+                                        int metric, const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc,
+                                        int64_t* d_row, float* d_dist, int32_t* d_cnt, uint64_t* d_keys)
+{
+    return search_device_on(session, c, reinterpret_cast<const float*>(d_queries), nq, dim, k, metric, filters, d_blk, d_doc, d_row,
+                            d_dist, d_cnt, d_keys, true);
+}
+
+extern "C" int vsr_search_bit_device(vsr_corpus* c, const uint8_t* d_queries, int nq, int dim, int k, int metric,
+                                     const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc, int64_t* d_row,
+                                     float* d_dist, int32_t* d_cnt, uint64_t* d_keys)
+{
+    return vsr_search_bit_device_on(nullptr, c, d_queries, nq, dim, k, metric, filters, d_blk, d_doc, d_row, d_dist, d_cnt, d_keys);
 }
 
 extern "C" int vsr_search_device(vsr_corpus* c, const float* d_queries, int nq, int dim, int k, int metric,
@@ -820,4 +858,17 @@ extern "C" int vsr_search(vsr_corpus* c, const float* queries, int nq, int dim, 
                 return fail(VSR_ERR_INVALID, "\"%.9g\" is out of range for type halfvec", (double) queries[i]);
     }
     return host_search(c, queries, nq, dim, k, metric, filters, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr});
+}
+
+// ORDER BY col <~> $1 / col <%> $1 LIMIT k over a bit corpus.  Exact by construction: nothing flags, nothing is re-run.
+extern "C" int vsr_search_bit(vsr_corpus* c, const uint8_t* queries, int nq, int dim, int k, int metric,
+                              const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc, int64_t* out_row,
+                              float* out_dist, int32_t* out_cnt)
+{
+    int rc = check_search_args(c, queries, nq, dim, k, metric, filters, "vsr_search_bit", true);
+    if (rc) return rc;
+    if (nq == 0) return VSR_OK;
+    if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "vsr_search_bit: output is NULL");
+    return host_search(c, reinterpret_cast<const float*>(queries), nq, dim, k, metric, filters,
+                       {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr});
 }

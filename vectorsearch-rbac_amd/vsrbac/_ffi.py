@@ -37,6 +37,9 @@ SYMBOLS = {
     "vsr_corpus_load": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i64, C.POINTER(_vp)]),
     "vsr_corpus_load_half": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i64, C.POINTER(_vp)]),
     "vsr_corpus_is_half": (_i, [_vp]),
+    "vsr_corpus_load_bit": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i64, C.POINTER(_vp)]),
+    "vsr_corpus_is_bit": (_i, [_vp]),
+    "vsr_corpus_binary_quantize": (_i, [_vp, C.POINTER(_vp)]),
     "vsr_corpus_device_bytes": (_i64, [_vp]),
     "vsr_corpus_free": (_i, [_vp]),
     "vsr_corpus_rows": (_i64, [_vp]),
@@ -50,6 +53,9 @@ SYMBOLS = {
     "vsr_filter_allowed_rows": (_i64, [_vp]),
     "vsr_filter_scanned_rows": (_i64, [_vp]),
     "vsr_search": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_search_bit": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_search_bit_device": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_search_bit_device_on": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_search_device": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_search_device_on": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_search_device_exact": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -60,6 +66,8 @@ SYMBOLS = {
     "vsr_packed_result_bytes": (_i64, [_i, _i]),
     "vsr_merge_topk_packed_device": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "vsr_pair_distances": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "vsr_bit_pair_distances": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "vsr_binary_quantize": (_i, [_vp, _vp, _i64, _i, _vp]),
     "vsr_ivf_load": (_i, [_vp, _vp, _i, _vp, C.POINTER(_vp)]),
     "vsr_ivf_free": (_i, [_vp]),
     "vsr_ivf_assign": (_i, [_vp, _vp, _i, _i, _vp]),

@@ -8,7 +8,9 @@ from . import _ffi
 from ._ffi import VsrError, check, load_library
 
 L2, IP, COSINE, L1 = 0, 1, 2, 3
-METRICS = {"l2": L2, "<->": L2, "ip": IP, "<#>": IP, "cosine": COSINE, "<=>": COSINE, "l1": L1, "<+>": L1}
+HAMMING, JACCARD = 4, 5                              # bit corpora only (Corpus.search_bit)
+METRICS = {"l2": L2, "<->": L2, "ip": IP, "<#>": IP, "cosine": COSINE, "<=>": COSINE, "l1": L1, "<+>": L1,
+           "hamming": HAMMING, "<~>": HAMMING, "jaccard": JACCARD, "<%>": JACCARD}
 RANGES, BITMAP = 0, 1
 BUILD_MERGE_DUPLICATES = 1                           # VSR_HNSW_BUILD_MERGE_DUPLICATES
 
@@ -45,6 +47,27 @@ def _ivf_iterative_mode(m):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _packed_bits(a, dim, what):
+    """`a` as packed uint8 [n, (dim + 7) // 8] in varbit order: a bool [n, dim] array is packed with np.packbits (element i
+    -> bit 7 - i % 8 of byte i // 8); a uint8 array is taken as packed already, then `dim` must be given."""
+    a = np.asarray(a)
+    if a.dtype == np.bool_:
+        a = np.atleast_2d(a)
+        if dim is not None and int(dim) != a.shape[1]:
+            raise ValueError(f"{what}: a bool array of {a.shape[1]} columns cannot have dim {dim}")
+        dim = a.shape[1]
+        packed = np.packbits(a, axis=1) if dim else np.zeros((a.shape[0], 0), dtype=np.uint8)
+        return np.ascontiguousarray(packed), int(dim)
+    if a.dtype != np.uint8:
+        raise ValueError(f"{what}: bit strings are bool [n, dim] or packed uint8 [n, (dim + 7) // 8] arrays")
+    if dim is None:
+        raise ValueError(f"{what}: packed uint8 rows need dim (the bit length)")
+    a = np.ascontiguousarray(a.reshape(1, -1) if a.ndim == 1 else a)
+    if a.ndim != 2 or a.shape[1] != (int(dim) + 7) // 8:
+        raise ValueError(f"{what}: packed rows of {int(dim)} bits are [n, {(int(dim) + 7) // 8}] bytes")
+    return a, int(dim)
 
 
 class Context:
@@ -146,6 +169,31 @@ class Context:
                 rows = rows.astype(np.float16)
         return Corpus(self, rows, block_ids, doc_ids, row_offset, half=True)
 
+    def load_corpus_bit(self, rows, dim=None, block_ids=None, doc_ids=None, row_offset=0):
+        """A bit corpus (vsr_corpus_load_bit): `rows` packed uint8 [n, (dim + 7) // 8] in varbit order, or a bool [n, dim]
+        array (packed here with np.packbits; dim may then be omitted).  Searches go through Corpus.search_bit."""
+        packed, dim = _packed_bits(rows, dim, "load_corpus_bit")
+        return Corpus(self, packed, block_ids, doc_ids, row_offset, bit_dim=dim)
+
+    def bit_pair_distances(self, metric, a, b, dim=None, dim_b=None):
+        """hamming_distance / jaccard_distance for pairs (a[i], b[i]) of bit strings, bool or packed uint8 (then with `dim`;
+        `dim_b` when b's length differs); b may be a single string (broadcast).  Raises VsrError('different bit lengths %u
+        and %u') like pgvector's CheckDims."""
+        bcast = np.asarray(b).ndim == 1
+        pa, da = _packed_bits(a, dim, "bit_pair_distances")
+        pb, db = _packed_bits(b, dim if dim_b is None else dim_b, "bit_pair_distances")
+        out = np.empty(pa.shape[0], dtype=np.float64)
+        check(self._lib.vsr_bit_pair_distances(self._h, _metric(metric), _ptr(pa), _ptr(pb), pa.shape[0], da, db, int(bcast),
+                                               _ptr(out)))
+        return out
+
+    def binary_quantize(self, a):
+        """binary_quantize of every row (vector.c:941-968): packed uint8 [n, (dim + 7) // 8], bit set where the element > 0."""
+        a = np.ascontiguousarray(np.atleast_2d(np.asarray(a, dtype=np.float32)))
+        out = np.zeros((a.shape[0], (a.shape[1] + 7) // 8), dtype=np.uint8)
+        check(self._lib.vsr_binary_quantize(self._h, _ptr(a), a.shape[0], a.shape[1], _ptr(out)))
+        return out
+
     def pair_distances(self, metric, a, b):
         """Operator value for pairs (a[i], b[i]); b may be a single vector (broadcast).
         Raises VsrError('different vector dimensions %d and %d') like pgvector's CheckDims."""
@@ -240,19 +288,22 @@ class Filter:
 class Corpus:
     """Rows resident in HBM, identified as (document_id, block_id) like the reference's documentblocks table."""
 
-    def __init__(self, ctx, rows, block_ids=None, doc_ids=None, row_offset=0, half=False):
+    def __init__(self, ctx, rows, block_ids=None, doc_ids=None, row_offset=0, half=False, bit_dim=None):
         self.ctx = ctx
         self._lib = ctx._lib
-        rows = np.ascontiguousarray(rows, dtype=np.float16 if half else np.float32)
+        bit = bit_dim is not None                    # rows: packed uint8 [n, (bit_dim + 7) // 8] (Context.load_corpus_bit)
+        rows = np.ascontiguousarray(rows, dtype=np.uint8 if bit else np.float16 if half else np.float32)
         if rows.ndim != 2:
             raise ValueError("rows must be [n, dim]")
         n, dim = rows.shape
+        if bit:
+            dim = int(bit_dim)
         blk = None if block_ids is None else np.ascontiguousarray(block_ids, dtype=np.int64)
         doc = None if doc_ids is None else np.ascontiguousarray(doc_ids, dtype=np.int32)
         if (blk is not None and blk.size != n) or (doc is not None and doc.size != n):
             raise ValueError("block_ids / doc_ids must have one entry per row")
         h = C.c_void_p()
-        load = self._lib.vsr_corpus_load_half if half else self._lib.vsr_corpus_load
+        load = self._lib.vsr_corpus_load_bit if bit else self._lib.vsr_corpus_load_half if half else self._lib.vsr_corpus_load
         check(load(ctx._h, _ptr(rows), n, dim, _ptr(blk), _ptr(doc), int(row_offset), C.byref(h)))
         self._h = h
         self.n, self.dim = n, dim
@@ -263,6 +314,22 @@ class Corpus:
     def is_half(self):
         """True for a halfvec corpus (Context.load_corpus_half)."""
         return bool(self._lib.vsr_corpus_is_half(self._h))
+
+    @property
+    def is_bit(self):
+        """True for a bit corpus (Context.load_corpus_bit, Corpus.binary_quantize)."""
+        return bool(self._lib.vsr_corpus_is_bit(self._h))
+
+    def binary_quantize(self):
+        """A bit corpus of this corpus's resident rows, quantized on the device (vsr_corpus_binary_quantize): same context,
+        row identity and internal order.  RBAC tables are not inherited: call load_rbac on the result."""
+        h = C.c_void_p()
+        check(self._lib.vsr_corpus_binary_quantize(self._h, C.byref(h)))
+        out = Corpus.__new__(Corpus)
+        out.ctx, out._lib, out._h = self.ctx, self._lib, h
+        out.n, out.dim, out.row_offset = self.n, self.dim, self.row_offset
+        out._user_filters = {}
+        return out
 
     def device_bytes(self):
         """Device bytes holding vector data: rows, norms and every screening plane (vsr_corpus_device_bytes)."""
@@ -389,6 +456,33 @@ class Corpus:
                                    _ptr(row), _ptr(dist), _ptr(cnt)))
         del keep
         return SearchResult(blk, doc, row, dist, cnt)
+
+    def search_bit(self, queries, k, metric="hamming", filters=None, dim=None):
+        """Corpus.search over a bit corpus: `queries` bool [nq, dim] or packed uint8 [nq, (dim + 7) // 8] (dim: the corpus's
+        unless given), metric "hamming" / "<~>" or "jaccard" / "<%>".  Exact; never flags."""
+        q, qdim = _packed_bits(queries, self.dim if dim is None else dim, "search_bit")
+        nq = q.shape[0]
+        farr, keep = self._filter_array(filters, nq)
+        kk = max(int(k), 1)
+        blk = np.full((nq, kk), -1, dtype=np.int64)
+        doc = np.full((nq, kk), -1, dtype=np.int32)
+        row = np.full((nq, kk), -1, dtype=np.int64)
+        dist = np.full((nq, kk), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.int32)
+        check(self._lib.vsr_search_bit(self._h, _ptr(q), nq, qdim, int(k), _metric(metric), farr, _ptr(blk), _ptr(doc),
+                                       _ptr(row), _ptr(dist), _ptr(cnt)))
+        del keep
+        return SearchResult(blk, doc, row, dist, cnt)
+
+    def search_bit_device(self, d_queries, nq, k, metric, filters, d_block, d_doc, d_rows, d_dist, d_counts, d_keys=None,
+                          dim=None, session=None):
+        """search_device over a bit corpus (vsr_search_bit_device_on): d_queries addresses nq x (dim + 7) // 8 packed bytes,
+        any alignment."""
+        farr, keep = self._filter_array(filters, nq)
+        check(self._lib.vsr_search_bit_device_on(session._h if session is not None else None, self._h, d_queries, nq,
+                                                 self.dim if dim is None else dim, int(k), _metric(metric), farr, d_block,
+                                                 d_doc, d_rows, d_dist, d_counts, d_keys))
+        return keep
 
     def search_device(self, d_queries, nq, k, metric, filters, d_block, d_doc, d_rows, d_dist, d_counts, d_keys=None,
                       dim=None, session=None):

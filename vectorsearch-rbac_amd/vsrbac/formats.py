@@ -5,6 +5,8 @@
   * pgvector binary form  int16 dim, int16 unused (= 0), float4[dim] big-endian   vector_recv / vector_send  (:363-411)
   * the same two forms of halfvec (pgvector/src/halfvec.c:165-320 text, :356-404 binary: big-endian uint16 binary16 elements);
     arrays are np.float16, what Context.load_corpus_half takes
+  * PostgreSQL's bit / varbit, the operand type of pgvector's <~> and <%> (bitvec.c): '0' / '1' digit text; binary form int32
+    bit length, big-endian, then the packed bytes.  Values are bool arrays, what Context.load_corpus_bit packs
   * shared_vectors.bin (+ .meta) of the C++ benches   SharedVectorTable::save_vectors / load_vectors
     (logical_partition_benchmark/benchmark/src/shared_vector_table.cpp:169-201): int32 dim, int64 count, float32[count*dim];
     .meta = int32 dim, int64 count, (int32 document_id, int32 block_id)[count]
@@ -217,6 +219,44 @@ def halfvec_to_binary(v):
     v = np.ascontiguousarray(np.asarray(v, dtype=np.float16).ravel())
     _check_dim(v.size, "halfvec")
     return struct.pack(">hh", v.size, 0) + v.view(np.uint16).astype(">u2").tobytes()
+
+
+# ---- PostgreSQL's bit / varbit, the type pgvector's <~> and <%> take (bitvec.c).  A value here is a bool array: element i is
+# bit i of the string; on the wire and in a corpus it is bit 7 - i % 8 of byte i // 8, pad bits zero (np.packbits' order).
+def bit_from_text(lit):
+    """bit_in / varbit_in for binary digits: '0' / '1' characters with an optional B (or b) prefix, any length including 0.
+    (The hexadecimal X form is not taken.)  Returns a bool array."""
+    s = lit[1:] if lit[:1] in ("B", "b") else lit
+    for ch in s:
+        if ch not in "01":
+            raise ValueError(f'"{ch}" is not a valid binary digit')
+    return np.frombuffer(s.encode("ascii"), dtype=np.uint8) == ord("1")
+
+
+def bit_to_text(v):
+    """bit_out / varbit_out: one '0' / '1' digit per element, no prefix."""
+    return "".join("1" if x else "0" for x in np.asarray(v, dtype=np.bool_).ravel())
+
+
+def bit_from_binary(b):
+    """varbit_recv: int32 bit length, big-endian, then (length + 7) // 8 bytes; pad bits in the last byte are dropped, as
+    varbit_recv clears them.  Returns a bool array."""
+    if len(b) < 4:
+        raise ValueError("insufficient data left in message")
+    (bitlen,) = struct.unpack(">i", b[:4])
+    if bitlen < 0:
+        raise ValueError("invalid length in external bit string")
+    nbytes = (bitlen + 7) // 8
+    if len(b) != 4 + nbytes:
+        raise ValueError("insufficient data left in message" if len(b) < 4 + nbytes else "incorrect binary data format")
+    bits = np.unpackbits(np.frombuffer(b, dtype=np.uint8, count=nbytes, offset=4))
+    return bits[:bitlen].astype(np.bool_)
+
+
+def bit_to_binary(v):
+    """varbit_send: int32 bit length, big-endian, then the packed bytes with zero pad bits."""
+    v = np.asarray(v, dtype=np.bool_).ravel()
+    return struct.pack(">i", v.size) + np.packbits(v).tobytes()
 
 
 def write_shared_vectors(path, rows, doc_ids, block_ids):
