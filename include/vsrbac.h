@@ -223,6 +223,43 @@ int vsr_search_bit_device_on(vsr_ctx* session, vsr_corpus* corpus, const uint8_t
                              int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows,
                              float* d_out_dist, int32_t* d_out_counts, uint64_t* d_out_keys);
 
+/* ---- two-stage search: Hamming shortlist on the bits, exact re-rank on the source rows ------------------------------
+ *   SELECT * FROM (SELECT * FROM items ORDER BY binary_quantize(embedding)::bit(n) <~> binary_quantize($1) LIMIT shortlist)
+ *   ORDER BY embedding <op> $1 LIMIT k;             (pgvector README, "Re-rank by the original vectors for better recall")
+ * `bits` must be the corpus vsr_corpus_binary_quantize made from `source` (fp32 or halfvec; either may still be freed first,
+ * and a source freed and loaded again is another corpus).  Per query q of `dim` floats:
+ *   1. qb = binary_quantize(q): bit i set where q[i] > 0, from the fp32 value as given, also for a halfvec source;
+ *   2. S = the answer of vsr_search_bit(bits, qb, k = shortlist, VSR_METRIC_HAMMING, filters[i]): the `shortlist` nearest
+ *      permitted rows by (Hamming, document_id, block_id), fewer if the filter admits fewer.  The filters are filters of
+ *      `bits`, the corpus that is scanned (RBAC tables are not inherited by a quantized corpus);
+ *   3. the exact operator distance of q to the SOURCE rows of S, in the arithmetic vsr_search reports (halfvec source: q
+ *      rounded to binary16 and widened); the first min(k, |S|) by (distance asc, NaN last, document_id, block_id) are the
+ *      answer, entries past out_counts[i] hold -1 / +Inf (out_keys: all ones).
+ * So a filter admitting at most `shortlist` rows gives exactly vsr_search(source) over the same rows, and the shortlists of one
+ * query are nested: recall against the exact search never decreases as `shortlist` grows.  Deterministic; no query is ever
+ * flagged, counts are never negative, vsr_set_screening and vsr_set_query_hint have no effect.  out_rows and out_doc_ids may be
+ * NULL.  k <= shortlist <= VSR_MAX_K; metric L2, inner product or cosine.
+ * Errors.  VSR_ERR_INVALID: source a bit corpus or an index view, bits not a bit corpus, bits not made from source (the message
+ * names both corpora), k < 1, shortlist < k, shortlist > VSR_MAX_K, a metric other than 0 .. 3, a filter of another corpus
+ * (source's included), and -- host entry point, halfvec source -- a finite query element that overflows binary16, as vsr_search.
+ * VSR_ERR_UNSUPPORTED: VSR_METRIC_L1.  VSR_ERR_DIM_MISMATCH: dim is not the source's, in vsr_search's words for that corpus. */
+int vsr_search_quantized(vsr_corpus* source, vsr_corpus* bits, const float* queries, int nq, int dim, int k, int shortlist,
+                         int metric, const vsr_filter* const* filters,
+                         int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows,
+                         float* out_dist, int32_t* out_counts);
+/* same, queries (nq x dim floats, row stride dim, 4-byte aligned) and outputs in device memory: both stages are enqueued on
+ * the stream of `session` (NULL, or vsr_search_quantized_device: the bits corpus's own context; the session must be on the
+ * corpora's device) with no synchronisation and no host round trip in between.  d_out_keys (nq*k, may be NULL): monotone
+ * fp32 distance << 32 | global row (row_offset included), as vsr_search_device's.  Query elements are not range-checked. */
+int vsr_search_quantized_device(vsr_corpus* source, vsr_corpus* bits, const float* d_queries, int nq, int dim, int k,
+                                int shortlist, int metric, const vsr_filter* const* filters,
+                                int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows,
+                                float* d_out_dist, int32_t* d_out_counts, uint64_t* d_out_keys);
+int vsr_search_quantized_device_on(vsr_ctx* session, vsr_corpus* source, vsr_corpus* bits, const float* d_queries, int nq,
+                                   int dim, int k, int shortlist, int metric, const vsr_filter* const* filters,
+                                   int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows,
+                                   float* d_out_dist, int32_t* d_out_counts, uint64_t* d_out_keys);
+
 /* same as vsr_search_device_on, but the call returns only when every query is PROVEN exact: it waits for the search,
  * and queries the screening flagged (below) are re-run on the exact path and patched into the outputs, all on the
  * session's stream.  n_rerun (may be NULL) receives how many queries that took.  Synchronises the session's stream. */

@@ -68,6 +68,7 @@ using DevBuf = Buf<false>;
 using PinBuf = Buf<true>;
 
 inline std::atomic<uint64_t> g_filter_id{0};
+inline std::atomic<uint64_t> g_corpus_serial{0};
 
 }  // namespace vsr
 
@@ -117,6 +118,7 @@ struct vsr_ctx {
     PinBuf h_dbg;
     DevBuf d_done;                // nq == 1 fused path: arrival counters of the in-kernel merge tree (zero between calls)
     DevBuf d_redo;                // vsr_search_device_exact: queries and results of the flagged queries
+    DevBuf d_short;               // vsr_search_quantized*: bit queries, the stage-1 answer, the re-rank keys
     PinBuf h_desc;
     PinBuf h_out;
     hipEvent_t desc_done = nullptr;   // staging buffer reuse guard
@@ -225,6 +227,10 @@ struct ClassView {
 
 struct vsr_corpus {
     vsr_ctx*    ctx = nullptr;
+    // identity of this corpus among all the process ever created: never reused, unlike the address.  A quantized corpus
+    // records its source's, which is how vsr_search_quantized* knows that the two hold the same rows in the same order
+    const uint64_t serial = g_corpus_serial.fetch_add(1, std::memory_order_relaxed) + 1;
+    uint64_t    quantized_from = 0;      // vsr_corpus_binary_quantize: the source's serial; 0: not a quantized corpus
     // the corpus's scan lane (VSR_SCAN_LANE=1): the main scan launches of ALL sessions over this corpus queue up on this one
     // stream, so two of them never share the GPU (their short kernels still run beside the other sessions' scans)
     mutable hipStream_t scan_stream = nullptr;

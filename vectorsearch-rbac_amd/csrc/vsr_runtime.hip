@@ -449,6 +449,7 @@ extern "C" int vsr_corpus_binary_quantize(vsr_corpus* src, vsr_corpus** out)
     c->n = src->n;
     c->dim = src->dim;
     c->bit = true;
+    c->quantized_from = src->serial;
     const uint32_t row_chunks = (uint32_t) ((src->dim + 127) / 128);
     c->stride4 = row_chunks;
     c->row_offset = src->row_offset;

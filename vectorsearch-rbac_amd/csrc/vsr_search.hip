@@ -1,6 +1,8 @@
 // vsr_search.hip — the brute-force search: the three launch sequences a plan resolves to (K2w / K2g wide passes, the
-// one-query fused launch, the general K1 / K1m / K2 path), the vsr_search* entry points and their flag re-run ladders.
+// one-query fused launch, the general K1 / K1m / K2 path), the vsr_search* entry points and their flag re-run ladders, and the
+// two-stage search (vsr_search_quantized*: K1b shortlist, then the exact re-rank of vsr_shortlist.h).
 #include "vsr_plan.h"
+#include "vsr_shortlist.h"
 
 #include <chrono>
 #include <cmath>
@@ -871,4 +873,149 @@ extern "C" int vsr_search_bit(vsr_corpus* c, const uint8_t* queries, int nq, int
     if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "vsr_search_bit: output is NULL");
     return host_search(c, reinterpret_cast<const float*>(queries), nq, dim, k, metric, filters,
                        {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr});
+}
+
+// ---- two-stage search: Hamming shortlist on the bits (K1b), exact re-rank on the source rows ------------------------
+// What the three vsr_search_quantized* entry points share.  Exactly one of h_queries / d_queries is set; `out` addresses
+// device memory either way (the host entry point hands in its result block).  Everything is enqueued on ctx->stream:
+//   binary_quantize of the queries -> stage 1 = the internal search over `bits` with k = shortlist, its keys into the
+//   session's scratch -> shortlist_rerank_kernel over the source rows -> shortlist_emit_kernel.
+static const char* corpus_kind(const vsr_corpus* c) { return c->bit ? "bit" : c->half ? "halfvec" : "vector"; }
+
+static int check_quantized_args(const vsr_ctx* session, const vsr_corpus* src, const vsr_corpus* bits, const void* queries, int nq,
+                                int dim, int k, int shortlist, int metric, const vsr_filter* const* filters, const char* who)
+{
+    if (!src || !bits) return fail(VSR_ERR_INVALID, "%s: corpus is NULL", who);
+    if (src->bit) return fail(VSR_ERR_INVALID, "%s: the source corpus is a bit corpus (the re-rank needs the fp32 or halfvec rows)", who);
+    if (src->base) return fail(VSR_ERR_INVALID, "%s: the source corpus is an index view", who);
+    if (!bits->bit) return fail(VSR_ERR_INVALID, "%s: the bits corpus is not a bit corpus", who);
+    if (bits->quantized_from != src->serial) {
+        char from[64] = "it was loaded with vsr_corpus_load_bit";
+        if (bits->quantized_from) snprintf(from, sizeof from, "it was made from corpus #%llu", (unsigned long long) bits->quantized_from);
+        return fail(VSR_ERR_INVALID, "%s: bits corpus #%llu (%lld rows of %d bits) was not made from source corpus #%llu (%s, %lld rows "
+                    "of %d dimensions) by vsr_corpus_binary_quantize: %s", who, (unsigned long long) bits->serial, (long long) bits->n,
+                    bits->dim, (unsigned long long) src->serial, corpus_kind(src), (long long) src->n, src->dim, from);
+    }
+    if (nq < 0 || (nq > 0 && !queries)) return fail(VSR_ERR_INVALID, "%s: queries is NULL", who);
+    if (dim != src->dim)                                    // CheckDims: vector.c:60-67, halfvec.c:60-67
+        return fail(VSR_ERR_DIM_MISMATCH, "different %s dimensions %d and %d", src->half ? "halfvec" : "vector", src->dim, dim);
+    if (k < 1) return fail(VSR_ERR_INVALID, "%s: k must be >= 1 (got %d)", who, k);
+    if (shortlist < k) return fail(VSR_ERR_INVALID, "%s: shortlist = %d is shorter than k = %d", who, shortlist, k);
+    if (shortlist > VSR_MAX_K) return fail(VSR_ERR_INVALID, "%s: shortlist = %d exceeds VSR_MAX_K = %d", who, shortlist, VSR_MAX_K);
+    if (metric == VSR_METRIC_L1) return fail(VSR_ERR_UNSUPPORTED, "%s: the re-rank has no L1 form (metric 3)", who);
+    if (metric < VSR_METRIC_L2 || metric > VSR_METRIC_L1) return fail(VSR_ERR_INVALID, "%s: metric %d", who, metric);
+    if (filters)
+        for (int i = 0; i < nq; ++i)
+            if (filters[i] && filters[i]->corpus != bits)
+                return fail(VSR_ERR_INVALID, "%s: filter %d belongs to another corpus (the bits corpus is the one scanned: it owns the filters)", who, i);
+    if (src->ctx->device != bits->ctx->device || (session && session->device != bits->ctx->device))
+        return fail(VSR_ERR_INVALID, "%s: session and corpora are on different devices", who);
+    return VSR_OK;
+}
+
+static int search_quantized_impl(vsr_ctx* ctx, vsr_corpus* src, vsr_corpus* bits, const float* h_queries, const float* d_queries,
+                                 int nq, int dim, int k, int shortlist, int metric, const vsr_filter* const* filters, const Outputs& out)
+{
+    const size_t ns = (size_t) nq * (size_t) shortlist, qbytes = (size_t) (dim + 7) / 8;
+    // scratch: [fp32 queries of a host call | bit queries | stage-1 keys | stage-1 block ids, then the re-rank keys | doc | dist | counts]
+    // (nobody reads stage 1's id columns: the re-rank keys take the block ids' place once stage 1 has run)
+    const size_t o_q = 0, o_qb = align_up(o_q + (h_queries ? (size_t) nq * dim * sizeof(float) : 0), 256),
+                 o_key = align_up(o_qb + (size_t) nq * qbytes, 256), o_blk = align_up(o_key + ns * 8, 256),
+                 o_doc = align_up(o_blk + ns * 8, 256), o_dist = align_up(o_doc + ns * 4, 256),
+                 o_cnt = align_up(o_dist + ns * 4, 256), total = align_up(o_cnt + (size_t) nq * 4, 256);
+    RCCHK(ctx->d_short.reserve(total));
+    char* w = ctx->d_short.as<char>();
+    if (h_queries) {
+        HIPCHK(hipMemcpyAsync(w + o_q, h_queries, (size_t) nq * dim * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        d_queries = reinterpret_cast<const float*>(w + o_q);
+    }
+    uint8_t* d_qb = reinterpret_cast<uint8_t*>(w + o_qb);
+    uint64_t* s1_keys = reinterpret_cast<uint64_t*>(w + o_key);
+    HIPCHK(launch_binary_quantize(d_queries, 0, (uint64_t) nq, (uint32_t) dim, (uint32_t) dim, d_qb, (uint32_t) qbytes, ctx->stream));
+    const Outputs s1{reinterpret_cast<int64_t*>(w + o_blk), reinterpret_cast<int32_t*>(w + o_doc), nullptr,
+                     reinterpret_cast<float*>(w + o_dist), reinterpret_cast<int32_t*>(w + o_cnt), s1_keys};
+    RCCHK(search_impl(ctx, bits, {nullptr, reinterpret_cast<const float*>(d_qb), nq, dim, shortlist, VSR_METRIC_HAMMING, s1}, filters, 2));
+
+    ShortlistParams sl{};
+    sl.s1_keys = s1_keys;
+    sl.shortlist = (uint32_t) shortlist;
+    sl.s1_row_offset = (uint32_t) bits->row_offset;
+    sl.q_src = d_queries;
+    sl.dim = (uint32_t) dim;
+    sl.rows = src->d_rows;
+    sl.stride4 = src->stride4;
+    sl.n_rows = (uint32_t) src->n;
+    sl.metric = metric;
+    sl.rr_keys = reinterpret_cast<uint64_t*>(w + o_blk);
+    sl.err = ctx->err_word();
+    sl.k = (uint32_t) k;
+    sl.row_offset = (uint32_t) src->row_offset;
+    sl.block_ids = src->d_block;
+    sl.doc_ids = src->d_doc;
+    sl.orig_rows = src->d_orig;
+    sl.out_block = out.blk;
+    sl.out_doc = out.doc;
+    sl.out_row = out.row;
+    sl.out_dist = out.dist;
+    sl.out_keys = out.keys;
+    sl.out_count = out.cnt;
+    Timed rerank(ctx, 2, ctx->stream);                      // counted with the selections
+    HIPCHK(launch_shortlist_rerank(sl, src->half, (uint32_t) nq, ctx->stream));
+    HIPCHK(launch_shortlist_emit(sl, (uint32_t) nq, ctx->stream));
+    HIPCHK(rerank.stop());
+    ctx->last_kernel += " + shortlist re-rank";
+    return VSR_OK;
+}
+
+extern "C" int vsr_search_quantized_device_on(vsr_ctx* session, vsr_corpus* src, vsr_corpus* bits, const float* d_queries, int nq,
+                                              int dim, int k, int shortlist, int metric, const vsr_filter* const* filters,
+                                              int64_t* d_blk, int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt,
+                                              uint64_t* d_keys)
+{
+    const char* who = "vsr_search_quantized_device";
+    int rc = check_quantized_args(session, src, bits, d_queries, nq, dim, k, shortlist, metric, filters, who);
+    if (rc) return rc;
+    if (nq == 0) return VSR_OK;
+    if (!d_blk || !d_dist || !d_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", who);
+    vsr_ctx* ctx = session ? session : bits->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    return search_quantized_impl(ctx, src, bits, nullptr, d_queries, nq, dim, k, shortlist, metric, filters,
+                                 {d_blk, d_doc, d_row, d_dist, d_cnt, d_keys});
+}
+
+extern "C" int vsr_search_quantized_device(vsr_corpus* src, vsr_corpus* bits, const float* d_queries, int nq, int dim, int k,
+                                           int shortlist, int metric, const vsr_filter* const* filters, int64_t* d_blk,
+                                           int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt, uint64_t* d_keys)
+{
+    return vsr_search_quantized_device_on(nullptr, src, bits, d_queries, nq, dim, k, shortlist, metric, filters, d_blk, d_doc, d_row,
+                                          d_dist, d_cnt, d_keys);
+}
+
+extern "C" int vsr_search_quantized(vsr_corpus* src, vsr_corpus* bits, const float* queries, int nq, int dim, int k, int shortlist,
+                                    int metric, const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc,
+                                    int64_t* out_row, float* out_dist, int32_t* out_cnt)
+{
+    const char* who = "vsr_search_quantized";
+    int rc = check_quantized_args(nullptr, src, bits, queries, nq, dim, k, shortlist, metric, filters, who);
+    if (rc) return rc;
+    if (nq == 0) return VSR_OK;
+    if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", who);
+    if (src->half) {                                        // `$1::halfvec`, as vsr_search refuses it
+        const size_t total = (size_t) nq * (size_t) dim;
+        for (size_t i = 0; i < total; ++i)
+            if (std::isfinite(queries[i]) && std::fabs(queries[i]) >= 65520.0f)
+                return fail(VSR_ERR_INVALID, "\"%.9g\" is out of range for type halfvec", (double) queries[i]);
+    }
+    vsr_ctx* ctx = bits->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    const ResultBlock rb(nq, k, false);                     // results in device memory, one packed copy back, one wait
+    if ((rc = ctx->d_out.reserve(rb.o_status))) return rc;
+    if ((rc = ctx->h_out.reserve(rb.total))) return rc;
+    char* d = ctx->d_out.as<char>();
+    char* h = ctx->h_out.as<char>();
+    if ((rc = search_quantized_impl(ctx, src, bits, queries, nullptr, nq, dim, k, shortlist, metric, filters, rb.arrays(d)))) return rc;
+    HIPCHK(hipMemcpyAsync(h, d, rb.o_status, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    rb.copy_out_all(h, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr}, nullptr);
+    return VSR_OK;
 }

@@ -12,6 +12,7 @@ HAMMING, JACCARD = 4, 5                              # bit corpora only (Corpus.
 METRICS = {"l2": L2, "<->": L2, "ip": IP, "<#>": IP, "cosine": COSINE, "<=>": COSINE, "l1": L1, "<+>": L1,
            "hamming": HAMMING, "<~>": HAMMING, "jaccard": JACCARD, "<%>": JACCARD}
 RANGES, BITMAP = 0, 1
+MAX_K = 2048                                         # VSR_MAX_K: the largest k, and the longest shortlist of search_quantized
 BUILD_MERGE_DUPLICATES = 1                           # VSR_HNSW_BUILD_MERGE_DUPLICATES
 
 SearchResult = namedtuple("SearchResult", "block_ids doc_ids rows dist counts")
@@ -492,6 +493,34 @@ class Corpus:
         check(self._lib.vsr_search_device_on(session._h if session is not None else None, self._h, d_queries, nq,
                                              self.dim if dim is None else dim, int(k), _metric(metric), farr, d_block,
                                              d_doc, d_rows, d_dist, d_counts, d_keys))
+        return keep
+
+    def search_quantized(self, bits, queries, k, shortlist, metric="l2", filters=None):
+        """Two-stage search (vsr_search_quantized): the `shortlist` nearest permitted rows of `bits` -- this corpus's
+        binary_quantize() -- by Hamming distance to binary_quantize(query), re-ranked by the exact `metric` distance to this
+        corpus's rows; the first k.  `filters` are filters of `bits`.  k <= shortlist <= MAX_K; "l2", "ip" or "cosine"."""
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(queries, dtype=np.float32)))
+        nq, dim = q.shape
+        farr, keep = bits._filter_array(filters, nq)
+        kk = max(int(k), 1)
+        blk = np.full((nq, kk), -1, dtype=np.int64)
+        doc = np.full((nq, kk), -1, dtype=np.int32)
+        row = np.full((nq, kk), -1, dtype=np.int64)
+        dist = np.full((nq, kk), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.int32)
+        check(self._lib.vsr_search_quantized(self._h, bits._h, _ptr(q), nq, dim, int(k), int(shortlist), _metric(metric), farr,
+                                             _ptr(blk), _ptr(doc), _ptr(row), _ptr(dist), _ptr(cnt)))
+        del keep
+        return SearchResult(blk, doc, row, dist, cnt)
+
+    def search_quantized_device(self, bits, d_queries, nq, k, shortlist, metric, filters, d_block, d_doc, d_rows, d_dist,
+                                d_counts, d_keys=None, session=None):
+        """search_quantized with device pointers (ints): d_queries addresses nq x dim floats.  Both stages are enqueued on the
+        stream of `session` (None: the context of `bits`); nothing synchronises (vsr_search_quantized_device_on)."""
+        farr, keep = bits._filter_array(filters, nq)
+        check(self._lib.vsr_search_quantized_device_on(session._h if session is not None else None, self._h, bits._h, d_queries,
+                                                       nq, self.dim, int(k), int(shortlist),
+                                                       _metric(metric), farr, d_block, d_doc, d_rows, d_dist, d_counts, d_keys))
         return keep
 
     def ivf_assign(self, centers, metric="l2"):
