@@ -148,6 +148,23 @@ int     vsr_corpus_is_bit(const vsr_corpus* corpus);         /* 1 / 0 */
  * on the new corpus.  The new corpus is independent of src (free either first).  src a bit corpus or an index view:
  * VSR_ERR_INVALID. */
 int vsr_corpus_binary_quantize(vsr_corpus* src, vsr_corpus** out);
+/* pgvector's sparsevec (sparsevec.c, sparsevec.h): n rows as CSR -- indptr[n + 1] (row i owns entries indptr[i] .. indptr[i + 1]),
+ * indices[nnz] zero-based, values[nnz] fp32.  Validated as sparsevec_recv validates a value (sparsevec.c:53-133, 493-539), every
+ * refusal VSR_ERR_INVALID in pgvector's words: dim 1 .. 1000000000; at most 16000 non-zeros per row and no more than dim; indices in
+ * range, ascending, no duplicates; no NaN, no Inf, no stored zero.  Empty rows are legal.  Identity arrays, row_offset and the
+ * (document_id, block_id) internal order are vsr_corpus_load's; the CSR rows are permuted on the host.  Resident form: interleaved
+ * (index, value) entries of 8 bytes (rows padded to an even entry count), 8 bytes of row offset and |row|^2 per row: no dense
+ * image, no planes, no class view.
+ * Searches go through vsr_search_sparse / vsr_search_sparse_device(_on): metrics VSR_METRIC_L2 .. VSR_METRIC_L1, the operators <->,
+ * <#>, <=>, <+> of sparsevec.c:803-1037, exact (nothing is screened, nothing flags), ordered as every search is.  Sums are fp32 as
+ * pgvector's are, in another order; the query terms no row entry meets enter as (float) of a double difference.
+ * vsr_search*, vsr_search_bit*, vsr_search_quantized*, vsr_corpus_binary_quantize, vsr_ivf_load, vsr_ivf_assign, vsr_hnsw_load
+ * and vsr_hnsw_build* over a sparse corpus: VSR_ERR_UNSUPPORTED, the message names sparsevec (the sparsevec_*_ops HNSW opclasses
+ * are not built yet). */
+int vsr_corpus_load_sparse(vsr_ctx* ctx, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n, int dim,
+                           const int64_t* block_ids, const int32_t* doc_ids, int64_t row_offset,
+                           vsr_corpus** out);
+int     vsr_corpus_is_sparse(const vsr_corpus* corpus);      /* 1 / 0 */
 /* device bytes holding VECTOR data of any corpus: rows, norms, every screening plane and, once vsr_rbac_load has built it,
  * the class-ordered copy of the int8 planes; identity arrays, RBAC tables and filters excluded */
 int64_t vsr_corpus_device_bytes(const vsr_corpus* corpus);
@@ -222,6 +239,29 @@ int vsr_search_bit_device_on(vsr_ctx* session, vsr_corpus* corpus, const uint8_t
                              const vsr_filter* const* filters,
                              int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows,
                              float* d_out_dist, int32_t* d_out_counts, uint64_t* d_out_keys);
+
+/* vsr_search over a sparse corpus (vsr_corpus_load_sparse): nq queries as CSR (q_indptr[nq + 1], q_indices zero-based, q_values),
+ * validated as rows are (VSR_ERR_INVALID, pgvector's words); an empty query is legal.  dim other than the corpus's:
+ * VSR_ERR_DIM_MISMATCH, "different sparsevec dimensions %d and %d" (CheckDims, sparsevec.c), the column's first.  A corpus that is
+ * not sparse: VSR_ERR_INVALID. */
+int vsr_search_sparse(vsr_corpus* corpus, const int64_t* q_indptr, const int32_t* q_indices, const float* q_values, int nq,
+                      int dim, int k, int metric, const vsr_filter* const* filters,
+                      int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows,
+                      float* out_dist, int32_t* out_counts);
+/* vsr_search_device / vsr_search_device_on over a sparse corpus: the three CSR arrays of the queries in device memory.  They are
+ * not read on the host, so the caller states max_query_nnz, the largest number of non-zeros of any query of the call
+ * (0 .. 16000): it sizes the queries' lookup tables.  A query with more entries than that (or with a negative count) is not
+ * staged -- it is searched as an empty query -- and sets a bit of the session's guard word: vsr_screening_check then fails.
+ * Entries whose index is not in 0 .. dim - 1 are dropped the same way.  Never flags. */
+int vsr_search_sparse_device(vsr_corpus* corpus, const int64_t* d_q_indptr, const int32_t* d_q_indices, const float* d_q_values,
+                             int nq, int dim, int max_query_nnz, int k, int metric, const vsr_filter* const* filters,
+                             int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows,
+                             float* d_out_dist, int32_t* d_out_counts, uint64_t* d_out_keys);
+int vsr_search_sparse_device_on(vsr_ctx* session, vsr_corpus* corpus, const int64_t* d_q_indptr, const int32_t* d_q_indices,
+                                const float* d_q_values, int nq, int dim, int max_query_nnz, int k, int metric,
+                                const vsr_filter* const* filters,
+                                int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows,
+                                float* d_out_dist, int32_t* d_out_counts, uint64_t* d_out_keys);
 
 /* ---- two-stage search: Hamming shortlist on the bits, exact re-rank on the source rows ------------------------------
  *   SELECT * FROM (SELECT * FROM items ORDER BY binary_quantize(embedding)::bit(n) <~> binary_quantize($1) LIMIT shortlist)
@@ -319,6 +359,14 @@ int vsr_bit_pair_distances(vsr_ctx* ctx, int metric, const uint8_t* a, const uin
 /* binary_quantize (vector.c:941-968) for n vectors: out[n][(dim + 7) / 8], bit i set where a[i] > 0 -- NaN, -0.0 and 0 give 0;
  * pad bits zero.  Host pointers. */
 int vsr_binary_quantize(vsr_ctx* ctx, const float* a, int64_t n, int dim, uint8_t* out);
+/* sparsevec's l2_distance / negative inner product / cosine_distance / l1_distance (sparsevec.c:803-1037) for n explicit pairs:
+ * pair i is row i of the CSR triple a against row i of the CSR triple b (both validated as vsr_corpus_load_sparse validates rows).
+ * One thread per pair runs pgvector's own sequential merge in pgvector's order, so out[i] is the operator's float8 bit for bit on
+ * any data.  metric 0 .. 3.  dim_a != dim_b: VSR_ERR_DIM_MISMATCH, "different sparsevec dimensions %d and %d".  Host pointers. */
+int vsr_sparse_pair_distances(vsr_ctx* ctx, int metric,
+                              const int64_t* a_indptr, const int32_t* a_indices, const float* a_values,
+                              const int64_t* b_indptr, const int32_t* b_indices, const float* b_values,
+                              int64_t n_pairs, int dim_a, int dim_b, double* out);
 
 /* ---- IVFFlat list probe (pgvector/src/ivfscan.c:36-176, 339-389) ------------------------------------------ */
 /* An index = `lists` centres (lists x dim floats) and the list of every corpus row (row_list[n], caller row order): what
@@ -500,7 +548,7 @@ typedef struct {
     /* K1 launches by kernel class: [0] = one query per pass, [1] = up to 4 queries sharing a pass */
     int64_t scan_launches[2];
     double  scan_ms[2];         /* sum of HIP-event durations of those launches          */
-    int64_t scan_bytes[2];      /* algorithmic bytes: rows*dim*4 (halfvec corpus: *2; bit corpus: rows*((dim+7)/8)) + bitmap bytes + k*12 */
+    int64_t scan_bytes[2];      /* algorithmic bytes: rows*dim*4 (halfvec corpus: *2; bit corpus: rows*((dim+7)/8); sparse corpus: 8 per stored entry) + bitmap bytes + k*12 */
     int64_t scan_rows[2];       /* rows scanned (per shared pass)                        */
     int64_t select_launches;    /* K5 */
     double  select_ms;

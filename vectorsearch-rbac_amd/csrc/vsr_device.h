@@ -133,6 +133,12 @@ struct ScanParams {
     uint32_t         dense;        // K2w int8 main launch: 1 = every group's tile list is an identity list over one contiguous run of
                                    // rows (a class-view plan): rows by arithmetic (vsr_mfmaw.h, DENSE)
     FusedTail        fused;        // K1, nq == 1 only (enable = 0 otherwise)
+    // K1s (vsr_scans.h, sparse corpus): rows = interleaved (index, value) entries of 8 bytes, row r owns entries
+    // sp_off[r] .. sp_off[r + 1] (an even count: 16-byte loads); the queries are open-addressing tables (SparseStageParams)
+    const uint64_t*  sp_off;       // [n_rows + 1]
+    const uint2*     sp_tab;       // [n_slots][sp_slots] (index, value bits); empty slot: index SPARSE_EMPTY, value 0
+    uint32_t         sp_slots;     // slots per table, a power of two >= 2
+    const double*    sp_qtot;      // [n_slots][2] sum q^2, sum |q| of the staged query, in double
 };
 
 // Per query: which partial lists to merge and where to put the result.
@@ -355,6 +361,52 @@ struct StageParams {
     uint32_t*    q8_bad_host;      // pinned host word <- 1 if any such query (the session then leaves the int8 path)
 };
 hipError_t launch_stage(const StageParams& p, hipStream_t s);
+// Per-batch staging of a sparse search (stage_sparse_kernel, vsr_sparse.hip): the descriptor block as above, and per query (one
+// wave each) an open-addressing table of `slots` (index, value) slots -- a power of two >= 2 x the call's largest query nnz, the
+// same for every query of the call; multiplicative hash, linear probing, insertion by atomic compare-and-swap; load factor
+// <= 1/2, so every lookup ends at an empty slot -- plus sum q^2 and sum |q| in double and sum q^2 in fp32 (cosine).
+constexpr uint32_t SPARSE_EMPTY = 0xFFFFFFFFu;
+constexpr uint32_t SPARSE_HASH_MUL = 2654435761u;        // slot = (index * SPARSE_HASH_MUL) >> (32 - log2 slots)
+constexpr uint32_t SPARSE_ERR_QUERY = 8u;                // guard-word bit: a device query longer than max_nnz / malformed
+constexpr int      SPARSE_MAX_NNZ = 16000;               // SPARSEVEC_MAX_NNZ, sparsevec.h
+constexpr int      SPARSE_MAX_DIM = 1000000000;          // SPARSEVEC_MAX_DIM
+struct SparseStageParams {
+    const uint4*   src16;          // descriptor block: pinned host memory as the device sees it
+    uint4*         dst16;
+    uint32_t       n16;
+    const int64_t* indptr;         // [nq + 1]  the queries' CSR arrays (the caller's device buffers, or the staged host copy)
+    const int32_t* indices;
+    const float*   values;
+    uint32_t       nq, dim, max_nnz;
+    uint32_t       slots, shift;   // shift = 32 - log2 slots
+    uint2*         tab;            // [nq][slots]
+    double*        qtot;           // [nq][2]
+    float*         q_norm2;        // [nq]
+    int32_t*       flags;          // [nq] <- 0
+    uint64_t*      tau;            // [nq] <- KEY_EMPTY
+    uint32_t*      err;            // the session's guard word
+};
+hipError_t launch_stage_sparse(const SparseStageParams& p, hipStream_t s);
+// K1s: LPR in {4, 16, 64} lanes per row (sparse_lpr_for_mean_nnz), qi in {1, 4}; global_tab: the tables are read where staging
+// wrote them instead of from an LDS copy (a table that does not fit the LDS budget beside the candidate lists)
+int  sparse_lpr_for_mean_nnz(double mean_nnz);
+inline uint32_t sparse_slots_for_nnz(uint32_t max_nnz)
+{
+    uint32_t slots = 2;
+    while (slots < 2u * max_nnz) slots <<= 1;
+    return slots;
+}
+inline size_t scans_lds_bytes(uint32_t qmax, uint32_t cap, uint32_t lds_slots)
+{
+    return (size_t) qmax * ((size_t) cap * 8 + 16 + (size_t) lds_slots * 8 + 8 + 4) + 16;
+}
+bool scan_sparse_table_in_lds(uint32_t slots, int k);     // one query's table fits beside its candidate list
+int  scan_qmax_sparse(uint32_t slots, int k);             // queries per pass: 1, or a multiple of 4 up to SCAN_QMAX (table in LDS); 4 or 1 (global)
+hipError_t launch_scan_sparse(const ScanParams& p, int metric, int lpr, int qi, bool global_tab, uint32_t n_blocks, hipStream_t s);
+// sparsevec.c:803-1037 for n explicit pairs, one thread per pair, pgvector's sequential merge; out: the operator's float8
+hipError_t launch_sparse_pair_distances(const int64_t* a_ptr, const int32_t* a_idx, const float* a_val, const int64_t* b_ptr,
+                                        const int32_t* b_idx, const float* b_val, int64_t n_pairs, int metric, double* out,
+                                        hipStream_t s);
 hipError_t launch_stage_bit(const StageParams& p, hipStream_t s);      // p.q_bits != 0
 // bit corpora (vsr_bit.hip).  Popcount of every row of `chunks` 16-byte chunks, as fp32 (exact: <= 64000)
 hipError_t launch_row_popcounts(const uint4* rows, uint32_t n_rows, uint32_t chunks, float* pop, hipStream_t s);

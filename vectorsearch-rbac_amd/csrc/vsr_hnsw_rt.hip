@@ -56,6 +56,7 @@ extern "C" int vsr_hnsw_load(vsr_corpus* c, int m, int32_t n_elem, int32_t entry
     *out = nullptr;
     if (c->base) return fail(VSR_ERR_INVALID, "vsr_hnsw_load: the corpus is a view");
     if (c->half) return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_load: a halfvec corpus has no index path yet (the halfvec_*_ops opclasses)");
+    if (c->sparse) return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_load: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)");
     if (c->bit) return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_load: a bit corpus has no index path yet (the bit_hamming_ops / bit_jaccard_ops opclasses)");
     if (m < 2 || m > 100)        /* reloption m: 2 .. HNSW_MAX_M (hnsw.h:36-40) */
         return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_load: m must be between 2 and 100 (got %d)", m);
@@ -112,6 +113,7 @@ static int hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uin
     if (flags & ~(uint32_t) VSR_HNSW_BUILD_MERGE_DUPLICATES) return fail(VSR_ERR_INVALID, "%s: unknown flag bits 0x%x", who, flags);
     if (c->base) return fail(VSR_ERR_INVALID, "%s: the corpus is a view", who);
     if (c->half) return fail(VSR_ERR_UNSUPPORTED, "%s: a halfvec corpus has no index path yet (the halfvec_*_ops opclasses)", who);
+    if (c->sparse) return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
     if (c->bit) return fail(VSR_ERR_UNSUPPORTED, "%s: a bit corpus has no index path yet (the bit_hamming_ops / bit_jaccard_ops opclasses)", who);
     if (m < 2 || m > 100) return fail(VSR_ERR_UNSUPPORTED, "%s: m must be between 2 and 100 (got %d)", who, m);
     if (ef_construction < 4 || ef_construction > 1000 || ef_construction < 2 * m)      /* hnsw.c:62-63, hnswbuild.c:677-679 */

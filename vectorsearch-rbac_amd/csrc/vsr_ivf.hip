@@ -79,6 +79,7 @@ extern "C" int vsr_ivf_load(vsr_corpus* c, const float* centers, int lists, cons
     *out = nullptr;
     if (c->base) return fail(VSR_ERR_INVALID, "vsr_ivf_load: the corpus is itself a view");
     if (c->half) return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_load: a halfvec corpus has no index path yet (the halfvec_*_ops opclasses)");
+    if (c->sparse) return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_load: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)");
     if (c->bit) return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_load: a bit corpus has no index path yet (the bit_hamming_ops / bit_jaccard_ops opclasses)");
     if (lists < 1 || lists > 32768)      /* reloption lists: 1 .. IVFFLAT_MAX_LISTS (ivfflat.h:42-44) */
         return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_load: lists must be between 1 and 32768 (got %d)", lists);
@@ -460,6 +461,7 @@ extern "C" int vsr_ivf_assign(vsr_corpus* c, const float* centers, int lists, in
     if (!c || !centers || (c->n > 0 && !out_row_list)) return fail(VSR_ERR_INVALID, "vsr_ivf_assign: NULL argument");
     if (c->base) return fail(VSR_ERR_INVALID, "vsr_ivf_assign: the corpus is a view");
     if (c->half) return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_assign: a halfvec corpus has no index path yet (the halfvec_*_ops opclasses)");
+    if (c->sparse) return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_assign: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)");
     if (c->bit) return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_assign: a bit corpus has no index path yet (the bit_hamming_ops / bit_jaccard_ops opclasses)");
     if (lists < 1 || lists > 32768) return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_assign: lists must be between 1 and 32768 (got %d)", lists);
     if (metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)

@@ -18,6 +18,7 @@ struct PlanScalars {
     bool     int8 = false;        // ... on the corpus's int8 planes (L2, integer 0..255 rows and queries)
     bool     class_view = false;  // ... on the corpus's class view of the int8 planes (every pass a whole permission class)
     bool     k2g = false;         // ... on K2g: long rows, 256-query passes, coarse planes (vsr_gemm.h); implies k2w
+    bool     sparse_global = false;   // K1s (sparse corpus): the query tables stay in global memory (vsr_scans.h, GLOBAL_TAB)
     uint32_t keep = 0;            // partial list length kp (K2: 2k screening survivors; else k)
     uint32_t rerank_base = 0;     // K2: first partial list holding the per-query screening survivors
     uint32_t n_scan_lists = 0;

@@ -94,6 +94,7 @@ struct vsr_ctx {
     DevBuf d_qcnt;       // K2w: [candidate counts | sample counts]
     bool   hint_u8 = false;       // vsr_set_query_hint: the caller's DEVICE-resident queries are integers 0..255
     bool   int8_this_call = false;   // search_impl -> make_plan: the queries of this call qualify for the int8 planes
+    uint32_t sparse_slots = 2;       // ... (sparse corpus) slots of this call's query tables: sizes the passes (scan_qmax_sparse)
     bool   q8_ok = true;          // ... and every hinted query so far really was (else the hint is dropped)
     PinBuf h_q8;                  // one word the staging kernel sets when a query is not (read without synchronising)
     bool   no_fused = false;      // VSR_NO_FUSED: nq == 1 takes the general path (staging, K1, K5)
@@ -242,6 +243,12 @@ struct vsr_corpus {
     bool        bit = false;             // bit corpus (vsr_corpus_load_bit, vsr_corpus_binary_quantize): dim counts BITS, d_rows holds stride4
                                          // 16-byte chunks of packed bits per row (pad bits zero), d_norm2 the rows' popcounts; no norms-max, no
                                          // planes, no class view; exact kernel only (K1b)
+    bool        sparse = false;          // sparse corpus (vsr_corpus_load_sparse): d_rows holds sp_entries interleaved (index, value) entries of 8
+                                         // bytes, d_sp_off the rows' first entries (n + 1 of them, all even), d_norm2 the rows' |row|^2;
+                                         // stride4 = 0, shape = {LPR by the mean entry count, 0, LPR, 64}; no planes, no class view; exact
+                                         // kernel only (K1s)
+    uint64_t*   d_sp_off = nullptr;
+    uint64_t    sp_entries = 0;          // stored entries, pad entries included
     int64_t     row_offset = 0;
     KernelShape shape{};
     float4*     d_rows = nullptr;
@@ -406,8 +413,13 @@ void   purge_ivf_caches(vsr_corpus* c, const vsr_filter* f);
 void   purge_hnsw_caches(vsr_corpus* c, const vsr_filter* f);
 // vsr_search.hip
 // bit_entry: the caller is a vsr_search_bit* entry point (bit corpus, metrics 4 / 5); every other caller is refused a bit corpus
+// sparse_entry: ... a vsr_search_sparse* entry point (sparse corpus, metrics 0 .. 3); every other caller is refused a sparse corpus
 int    check_search_args(const vsr_corpus* c, const void* queries, int nq, int dim, int k, int metric,
-                         const vsr_filter* const* filters, const char* who, bool bit_entry = false);
+                         const vsr_filter* const* filters, const char* who, bool bit_entry = false, bool sparse_entry = false);
+// vsr_runtime.hip: n sparsevec values as CSR, checked as sparsevec_recv checks one (sparsevec.c:53-133, 493-539); max_nnz (may be
+// nullptr) receives the longest row's entry count
+int    check_sparse_rows(const char* who, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n, int dim,
+                         uint32_t* max_nnz);
 int    host_search(vsr_corpus* c, const float* queries, int nq, int dim, int k, int metric, const vsr_filter* const* filters,
                    const Outputs& out);
 

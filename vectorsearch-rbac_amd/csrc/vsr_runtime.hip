@@ -228,7 +228,7 @@ vsr_corpus::~vsr_corpus()
 {
     if (scan_stream) { (void) hipStreamSynchronize(scan_stream); (void) hipStreamDestroy(scan_stream); }
     drop_cached_filters(this);
-    void* ptrs[] = {d_rows, d_scr, d_scr_c, d_scr8, d_norm2_8, d_all_tiles, d_doc_class, d_rank, d_norm2, d_norm2_max, d_block, d_doc, d_orig, d_row_docidx, d_doc_mask};
+    void* ptrs[] = {d_rows, d_sp_off, d_scr, d_scr_c, d_scr8, d_norm2_8, d_all_tiles, d_doc_class, d_rank, d_norm2, d_norm2_max, d_block, d_doc, d_orig, d_row_docidx, d_doc_mask};
     for (void* p : ptrs)
         if (p) (void) hipFree(p);
 }
@@ -434,6 +434,199 @@ extern "C" int vsr_corpus_load_bit(vsr_ctx* ctx, const uint8_t* rows, int64_t n,
 
 extern "C" int vsr_corpus_is_bit(const vsr_corpus* c) { return c && c->bit ? 1 : 0; }
 
+// ---- sparse corpora (pgvector's sparsevec) ----
+int vsr::check_sparse_rows(const char* who, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n, int dim,
+                           uint32_t* max_nnz)
+{
+    if (max_nnz) *max_nnz = 0;
+    // CheckDim, sparsevec.c:53-65
+    if (dim < 1) return fail(VSR_ERR_INVALID, "sparsevec must have at least 1 dimension");
+    if (dim > SPARSE_MAX_DIM) return fail(VSR_ERR_INVALID, "sparsevec cannot have more than %d dimensions", SPARSE_MAX_DIM);
+    if (n < 0 || (n > 0 && !indptr)) return fail(VSR_ERR_INVALID, "%s: indptr is NULL", who);
+    for (int64_t r = 0; r < n; ++r) {
+        const int64_t beg = indptr[r], nnz = indptr[r + 1] - beg;
+        // CheckNnz, :70-87
+        if (nnz < 0 || beg < 0) return fail(VSR_ERR_INVALID, "sparsevec cannot have negative number of elements");
+        if (nnz > SPARSE_MAX_NNZ) return fail(VSR_ERR_INVALID, "sparsevec cannot have more than %d non-zero elements", SPARSE_MAX_NNZ);
+        if (nnz > dim) return fail(VSR_ERR_INVALID, "sparsevec cannot have more elements than dimensions");
+        if (nnz > 0 && (!indices || !values)) return fail(VSR_ERR_INVALID, "%s: indices / values is NULL", who);
+        for (int64_t i = 0; i < nnz; ++i) {                  // CheckIndex, :92-116
+            const int32_t index = indices[beg + i];
+            if (index < 0 || index >= dim) return fail(VSR_ERR_INVALID, "sparsevec index out of bounds");
+            if (i > 0 && index < indices[beg + i - 1]) return fail(VSR_ERR_INVALID, "sparsevec indices must be in ascending order");
+            if (i > 0 && index == indices[beg + i - 1]) return fail(VSR_ERR_INVALID, "sparsevec indices must not contain duplicates");
+        }
+        for (int64_t i = 0; i < nnz; ++i) {                  // CheckElement, :121-133; sparsevec_recv, :527-536
+            const float v = values[beg + i];
+            if (std::isnan(v)) return fail(VSR_ERR_INVALID, "NaN not allowed in sparsevec");
+            if (std::isinf(v)) return fail(VSR_ERR_INVALID, "infinite value not allowed in sparsevec");
+            if (v == 0) return fail(VSR_ERR_INVALID, "binary representation of sparsevec cannot contain zero values");
+        }
+        if (max_nnz && (uint32_t) nnz > *max_nnz) *max_nnz = (uint32_t) nnz;
+    }
+    return VSR_OK;
+}
+
+extern "C" int vsr_corpus_load_sparse(vsr_ctx* ctx, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n,
+                                      int dim, const int64_t* block_ids, const int32_t* doc_ids, int64_t row_offset, vsr_corpus** out)
+{
+    const char* who = "vsr_corpus_load_sparse";
+    if (!ctx || !out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    int rc = check_sparse_rows(who, indptr, indices, values, n, dim, nullptr);
+    if (rc) return rc;
+    if (n + row_offset >= 0xFFFFFFFFll) return fail(VSR_ERR_UNSUPPORTED, "%s: more than 2^32-2 rows per shard", who);
+    HIPCHK(hipSetDevice(ctx->device));
+
+    std::unique_ptr<vsr_corpus> c(new vsr_corpus());
+    c->ctx = ctx;
+    c->n = n;
+    c->dim = dim;
+    c->sparse = true;
+    c->stride4 = 0;
+    c->row_offset = row_offset;
+
+    // internal order: (document_id, block_id), as corpus_load
+    std::vector<int64_t> perm((size_t) n);
+    std::iota(perm.begin(), perm.end(), (int64_t) 0);
+    auto doc_of = [&](int64_t r) { return doc_ids ? doc_ids[r] : 0; };
+    auto blk_of = [&](int64_t r) { return block_ids ? block_ids[r] : r; };
+    bool sorted = true;
+    for (int64_t i = 1; i < n && sorted; ++i) {
+        const int32_t da = doc_of(i - 1), db = doc_of(i);
+        if (da > db || (da == db && blk_of(i - 1) > blk_of(i))) sorted = false;
+    }
+    if (!sorted)
+        std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) {
+            const int32_t da = doc_of(a), db = doc_of(b);
+            if (da != db) return da < db;
+            return blk_of(a) < blk_of(b);
+        });
+    c->h_orig = perm;
+    std::vector<int32_t> h_doc((size_t) n);
+    std::vector<int64_t> h_blk((size_t) n);
+    std::vector<uint32_t> h_docidx((size_t) n);
+    for (int64_t i = 0; i < n; ++i) {
+        h_doc[(size_t) i] = doc_of(perm[(size_t) i]);
+        h_blk[(size_t) i] = blk_of(perm[(size_t) i]);
+        if (i == 0 || h_doc[(size_t) i] != h_doc[(size_t) i - 1]) {
+            c->docs.push_back(h_doc[(size_t) i]);
+            c->doc_row_start.push_back((uint32_t) i);
+        }
+        h_docidx[(size_t) i] = (uint32_t) (c->docs.size() - 1);
+    }
+    c->doc_row_start.push_back((uint32_t) n);
+
+    // the rows in internal order: offsets (every row an even number of entries), |row|^2 as sparsevec_cosine_distance sums it
+    // (fp32, in order, :964-966)
+    std::vector<uint64_t> off((size_t) n + 1, 0);
+    std::vector<float> norm2((size_t) n);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t r = perm[(size_t) i], nnz = indptr[r + 1] - indptr[r];
+        off[(size_t) i + 1] = off[(size_t) i] + (uint64_t) ((nnz + 1) / 2 * 2);
+        float na = 0.0f;
+        for (int64_t e = 0; e < nnz; ++e) {
+            const float v = values[indptr[r] + e];
+            const float sq = v * v;
+            na = na + sq;
+        }
+        norm2[(size_t) i] = na;
+    }
+    c->sp_entries = off[(size_t) n];
+    const double mean = n > 0 ? (double) c->sp_entries / (double) n : 0.0;
+    const int lpr = sparse_lpr_for_mean_nnz(mean);
+    c->shape = KernelShape{lpr, 0, lpr, 64};
+
+    const size_t alloc_rows = (size_t) std::max<int64_t>(n, 1);
+    HIPCHK(hipMalloc(&c->d_rows, (size_t) c->sp_entries * 8 + 1024));
+    HIPCHK(hipMalloc(&c->d_sp_off, (alloc_rows + 1) * sizeof(uint64_t)));
+    HIPCHK(hipMalloc(&c->d_norm2, alloc_rows * sizeof(float)));
+    HIPCHK(hipMalloc(&c->d_block, alloc_rows * sizeof(int64_t)));
+    HIPCHK(hipMalloc(&c->d_doc, alloc_rows * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&c->d_orig, alloc_rows * sizeof(int64_t)));
+    HIPCHK(hipMalloc(&c->d_row_docidx, alloc_rows * sizeof(uint32_t)));
+    if (n > 0) {
+        // interleave through a bounded host staging buffer (whole rows per piece)
+        const size_t piece = (size_t) 8 << 20;               // entries
+        std::vector<uint2> stage;
+        for (int64_t i0 = 0; i0 < n;) {
+            int64_t i1 = i0 + 1;
+            while (i1 < n && off[(size_t) i1 + 1] - off[(size_t) i0] <= piece) ++i1;
+            stage.assign((size_t) (off[(size_t) i1] - off[(size_t) i0]), make_uint2(SPARSE_EMPTY, 0u));
+            for (int64_t i = i0; i < i1; ++i) {
+                const int64_t r = perm[(size_t) i], nnz = indptr[r + 1] - indptr[r];
+                uint2* dst = stage.data() + (off[(size_t) i] - off[(size_t) i0]);
+                for (int64_t e = 0; e < nnz; ++e) {
+                    uint32_t bits;
+                    memcpy(&bits, &values[indptr[r] + e], 4);
+                    dst[e] = make_uint2((uint32_t) indices[indptr[r] + e], bits);
+                }
+            }
+            if (!stage.empty())
+                HIPCHK(hipMemcpy(reinterpret_cast<uint2*>(c->d_rows) + off[(size_t) i0], stage.data(), stage.size() * sizeof(uint2),
+                                 hipMemcpyHostToDevice));
+            i0 = i1;
+        }
+        HIPCHK(hipMemcpy(c->d_norm2, norm2.data(), (size_t) n * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(c->d_block, h_blk.data(), (size_t) n * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(c->d_doc, h_doc.data(), (size_t) n * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(c->d_orig, perm.data(), (size_t) n * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(c->d_row_docidx, h_docidx.data(), (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpy(c->d_sp_off, off.data(), off.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    *out = c.release();
+    return VSR_OK;
+}
+
+extern "C" int vsr_corpus_is_sparse(const vsr_corpus* c) { return c && c->sparse ? 1 : 0; }
+
+// sparsevec.c:803-1037 for n explicit pairs (host CSR triples)
+extern "C" int vsr_sparse_pair_distances(vsr_ctx* ctx, int metric, const int64_t* a_indptr, const int32_t* a_indices,
+                                         const float* a_values, const int64_t* b_indptr, const int32_t* b_indices,
+                                         const float* b_values, int64_t n_pairs, int dim_a, int dim_b, double* out)
+{
+    const char* who = "vsr_sparse_pair_distances";
+    if (!ctx || n_pairs < 0 || (n_pairs > 0 && (!a_indptr || !b_indptr || !out))) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
+    int rc = check_sparse_rows(who, a_indptr, a_indices, a_values, n_pairs, dim_a, nullptr);
+    if (rc) return rc;
+    if ((rc = check_sparse_rows(who, b_indptr, b_indices, b_values, n_pairs, dim_b, nullptr))) return rc;
+    if (dim_a != dim_b) return fail(VSR_ERR_DIM_MISMATCH, "different sparsevec dimensions %d and %d", dim_a, dim_b);   // CheckDims
+    if (metric < VSR_METRIC_L2 || metric > VSR_METRIC_L1) return fail(VSR_ERR_INVALID, "%s: metric %d", who, metric);
+    if (n_pairs == 0) return VSR_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    // the pairs' entries, rebased to 0
+    const int64_t a0 = a_indptr[0], b0 = b_indptr[0];
+    const size_t a_nnz = (size_t) (a_indptr[n_pairs] - a0), b_nnz = (size_t) (b_indptr[n_pairs] - b0);
+    std::vector<int64_t> ptr(2 * ((size_t) n_pairs + 1));
+    for (int64_t i = 0; i <= n_pairs; ++i) {
+        ptr[(size_t) i] = a_indptr[i] - a0;
+        ptr[(size_t) n_pairs + 1 + (size_t) i] = b_indptr[i] - b0;
+    }
+    const size_t ptr_bytes = ptr.size() * sizeof(int64_t);
+    const size_t o_ai = align_up(ptr_bytes, 256), o_av = align_up(o_ai + a_nnz * 4, 256), o_bi = align_up(o_av + a_nnz * 4, 256),
+                 o_bv = align_up(o_bi + b_nnz * 4, 256), o_out = align_up(o_bv + b_nnz * 4, 256);
+    if ((rc = ctx->d_misc.reserve(o_out + (size_t) n_pairs * sizeof(double)))) return rc;
+    char* d = ctx->d_misc.as<char>();
+    HIPCHK(hipMemcpyAsync(d, ptr.data(), ptr_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (a_nnz) {
+        HIPCHK(hipMemcpyAsync(d + o_ai, a_indices + a0, a_nnz * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(d + o_av, a_values + a0, a_nnz * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (b_nnz) {
+        HIPCHK(hipMemcpyAsync(d + o_bi, b_indices + b0, b_nnz * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(d + o_bv, b_values + b0, b_nnz * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));               // (ptr is a local: the copy must have left it)
+    const int64_t* d_ptr = reinterpret_cast<const int64_t*>(d);
+    HIPCHK(launch_sparse_pair_distances(d_ptr, reinterpret_cast<const int32_t*>(d + o_ai), reinterpret_cast<const float*>(d + o_av),
+                                        d_ptr + n_pairs + 1, reinterpret_cast<const int32_t*>(d + o_bi),
+                                        reinterpret_cast<const float*>(d + o_bv), n_pairs, metric, reinterpret_cast<double*>(d + o_out),
+                                        ctx->stream));
+    HIPCHK(hipMemcpyAsync(out, d + o_out, (size_t) n_pairs * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return VSR_OK;
+}
+
 // binary_quantize over the resident rows: a bit corpus with the source's context, row identity and internal order.  RBAC
 // tables are not inherited (filters belong to one corpus): the caller runs vsr_rbac_load on the new corpus.
 extern "C" int vsr_corpus_binary_quantize(vsr_corpus* src, vsr_corpus** out)
@@ -441,6 +634,7 @@ extern "C" int vsr_corpus_binary_quantize(vsr_corpus* src, vsr_corpus** out)
     if (!src || !out) return fail(VSR_ERR_INVALID, "vsr_corpus_binary_quantize: NULL argument");
     *out = nullptr;
     if (src->bit) return fail(VSR_ERR_INVALID, "vsr_corpus_binary_quantize: the corpus is a bit corpus already");
+    if (src->sparse) return fail(VSR_ERR_UNSUPPORTED, "vsr_corpus_binary_quantize: a sparsevec corpus has no binary_quantize (pgvector defines none)");
     if (src->base) return fail(VSR_ERR_INVALID, "vsr_corpus_binary_quantize: this corpus is an index view");
     vsr_ctx* ctx = src->ctx;
     HIPCHK(hipSetDevice(ctx->device));
@@ -530,6 +724,8 @@ extern "C" int64_t vsr_corpus_device_bytes(const vsr_corpus* c)
 {
     if (!c) return 0;
     const size_t rows = (size_t) std::max<int64_t>(c->n, 1);
+    if (c->sparse)                                           // entries, row offsets, |row|^2
+        return (int64_t) ((size_t) c->sp_entries * 8 + 1024 + (rows + 1) * sizeof(uint64_t) + rows * sizeof(float));
     size_t b = rows * (c->half ? c->stride4 / 2 : c->stride4) * 16 + 1024 + rows * sizeof(float);   // d_rows, d_norm2
     if (c->d_norm2_max) b += 64;
     if (c->d_scr) b += rows * (size_t) c->pstride4 * 16 + 1024;

@@ -50,6 +50,13 @@ struct Timed {
 };
 #define RCCHK(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
 
+// the queries of a sparse search
+struct SparseQueries {                                      // nq queries as CSR
+    const int64_t* indptr; const int32_t* indices; const float* values;
+    bool     host;                                          // the arrays are host memory (validated; copied through the pinned block)
+    uint32_t max_nnz;                                       // the longest query: sizes the tables
+};
+
 // ---- staging block -----------------------------------------------------------------------------------------------
 // The per-batch block in device memory, sections appended in order, each 256-byte aligned: [what the staging kernel
 // computes: padded queries, |q|^2, query planes || what the host writes (and the pinned block holds): the plan's descriptors]
@@ -133,6 +140,59 @@ int stage_host_part(vsr_ctx* ctx, const Staging& sb, size_t off_qn, size_t off_g
     return VSR_OK;
 }
 
+// ... of a sparse search: the host's part as above; a host call's CSR arrays travel in front of it in the pinned block.  The
+// staging block's first section is the queries' tables, `off_qt` their double totals, `off_qn` their fp32 |q|^2.
+int stage_sparse(vsr_ctx* ctx, const Staging& sb, size_t off_qt, size_t off_qn, size_t off_g, const SparseQueries& sq, int nq, int dim,
+                 uint32_t slots)
+{
+    const size_t nnz = sq.host ? (size_t) (sq.indptr[nq] - sq.indptr[0]) : 0;
+    const size_t h_ptr = 0, h_idx = align_up(h_ptr + ((size_t) nq + 1) * 8, 256), h_val = align_up(h_idx + nnz * 4, 256),
+                 h_q_bytes = sq.host ? align_up(h_val + nnz * 4, 256) : 0;
+    RCCHK(wait_for_staging_block(ctx));
+    RCCHK(ctx->h_desc.reserve(h_q_bytes + (sb.total - off_g)));
+    RCCHK(ctx->d_desc.reserve(sb.total));
+    RCCHK(ctx->d_flags.reserve((size_t) nq * sizeof(int32_t)));
+    RCCHK(ctx->d_tau.reserve((size_t) nq * sizeof(uint64_t)));
+    char* hs = ctx->h_desc.as<char>();
+    char* ds = ctx->d_desc.as<char>();
+    const char* hd = reinterpret_cast<const char*>(ctx->h_desc.dp);
+    SparseStageParams st{};
+    if (sq.host) {
+        int64_t* ptr = reinterpret_cast<int64_t*>(hs + h_ptr);
+        for (int i = 0; i <= nq; ++i) ptr[i] = sq.indptr[i] - sq.indptr[0];
+        if (nnz) {
+            memcpy(hs + h_idx, sq.indices + sq.indptr[0], nnz * 4);
+            memcpy(hs + h_val, sq.values + sq.indptr[0], nnz * 4);
+        }
+        st.indptr = reinterpret_cast<const int64_t*>(hd + h_ptr);
+        st.indices = reinterpret_cast<const int32_t*>(hd + h_idx);
+        st.values = reinterpret_cast<const float*>(hd + h_val);
+    } else {
+        st.indptr = sq.indptr;
+        st.indices = sq.indices;
+        st.values = sq.values;
+    }
+    sb.fill(hs + h_q_bytes, off_g);
+    st.src16 = reinterpret_cast<const uint4*>(hd + h_q_bytes);
+    st.dst16 = reinterpret_cast<uint4*>(ds + off_g);
+    st.n16 = (uint32_t) ((sb.total - off_g) / 16);
+    st.nq = (uint32_t) nq;
+    st.dim = (uint32_t) dim;
+    st.max_nnz = sq.max_nnz;
+    st.slots = slots;
+    st.shift = 32u - (uint32_t) __builtin_ctz(slots);
+    st.tab = reinterpret_cast<uint2*>(ds);
+    st.qtot = reinterpret_cast<double*>(ds + off_qt);
+    st.q_norm2 = reinterpret_cast<float*>(ds + off_qn);
+    st.flags = ctx->d_flags.as<int32_t>();
+    st.tau = ctx->d_tau.as<uint64_t>();
+    st.err = ctx->err_word();
+    HIPCHK(launch_stage_sparse(st, ctx->stream));
+    HIPCHK(hipEventRecord(ctx->desc_done, ctx->stream));
+    ctx->desc_pending = true;
+    return VSR_OK;
+}
+
 int launch_staging(vsr_ctx* ctx, const StageParams& st)
 {
     HIPCHK(st.q_bits ? launch_stage_bit(st, ctx->stream) : launch_stage(st, ctx->stream));
@@ -201,7 +261,8 @@ void count_scan(vsr_ctx* ctx, const Plan& plan, int cls)    // cls: 0 = one quer
 
 // one search call as the launch sequences see it.  d_queries == nullptr: queries come from `h_queries`.
 // (bit corpus: the query pointers address packed bit strings, ceil(dim / 8) bytes each)
-struct Call { const float *h_queries, *d_queries; int nq, dim, k, metric; Outputs out; };
+// (sparse corpus: `sparse` is set and the query pointers are not used)
+struct Call { const float *h_queries, *d_queries; int nq, dim, k, metric; Outputs out; const SparseQueries* sparse = nullptr; };
 
 // ---- K2w / K2g ---------------------------------------------------------------------------------------------------
 // K2w launch sequence (plan.k2w): staging -> sample pass -> threshold seeds -> main pass -> select + exact re-rank.
@@ -372,7 +433,7 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
 uint32_t fused_fan(const vsr_ctx* ctx, const vsr_corpus* c, const Plan& plan, const Call& q)
 {
     // (K1h rounds the query to binary16 itself as it enters LDS: no staging kernel needed for that either)
-    if (c->bit) return 0;                                   // K1b does not instantiate the in-kernel merge: staging + K1b + K5
+    if (c->bit || c->sparse) return 0;                      // K1b / K1s do not instantiate the in-kernel merge: staging + scan + K5
     if (!(q.nq == 1 && !ctx->no_fused && plan.groups.size() == 1 && plan.qi == 1 && !plan.k2 && !plan.mq && q.dim % (c->half ? 8 : 4) == 0 &&
           q.metric != VSR_METRIC_COSINE && plan.groups[0].n_blocks <= 64u * 64u && ctx->profiling != 1))
         return 0;
@@ -489,8 +550,10 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
     const vsr_corpus* idc = c->base ? c->base : c;          // identity arrays and re-rank rows (c may be a list-ordered view)
     const size_t qfloats = (size_t) c->stride4 * 4;
     Staging sb;
-    sb.add((size_t) nq * qfloats * sizeof(float));          // queries
+    const uint32_t sp_slots = c->sparse ? ctx->sparse_slots : 0u;
+    sb.add(c->sparse ? (size_t) nq * sp_slots * sizeof(uint2) : (size_t) nq * qfloats * sizeof(float));   // queries (sparse: their tables)
     const size_t off_qn = sb.add((size_t) nq * sizeof(float));
+    const size_t off_qt = sb.add(c->sparse ? (size_t) nq * 2 * sizeof(double) : 0);   // K1s: sum q^2, sum |q| in double
     const bool k2h = plan.k2 && c->half;                    // K2h: the queries also as binary16, its B fragments
     const size_t off_qh = sb.add(k2h ? (size_t) nq * qfloats * sizeof(uint16_t) : 0);
     const size_t off_g = sb.add(plan.groups);               // copied from here on
@@ -503,18 +566,27 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
     const size_t off_bm = sb.add(plan.block_map);
 
     StageParams st{};                                       // (no query planes, no K2w counters on this path)
-    RCCHK(stage_host_part(ctx, sb, off_qn, off_g, q.h_queries, q.d_queries, nq, q.dim, qfloats, st, c->bit));
-    st.q_half = c->half ? 1u : 0u;
-    if (k2h) st.q_h16 = reinterpret_cast<_Float16*>(ctx->d_desc.as<char>() + off_qh);
+    if (!c->sparse) {
+        RCCHK(stage_host_part(ctx, sb, off_qn, off_g, q.h_queries, q.d_queries, nq, q.dim, qfloats, st, c->bit));
+        st.q_half = c->half ? 1u : 0u;
+        if (k2h) st.q_h16 = reinterpret_cast<_Float16*>(ctx->d_desc.as<char>() + off_qh);
+    }
     RCCHK(ctx->d_partial.reserve(std::max<size_t>(8, (size_t) plan.n_partial * kp * sizeof(uint64_t))));
-    char* ds = ctx->d_desc.as<char>();
     Timed whole(ctx, 5, ctx->stream);                       // the whole search on the device
-    RCCHK(launch_staging(ctx, st));
+    if (c->sparse) RCCHK(stage_sparse(ctx, sb, off_qt, off_qn, off_g, *q.sparse, nq, q.dim, sp_slots));
+    else RCCHK(launch_staging(ctx, st));
+    char* ds = ctx->d_desc.as<char>();
 
     ScanParams sp = scan_params(ctx, c, kp, plan.qmax);
     sp.queries = reinterpret_cast<const float*>(ds);
     sp.q_norm2 = reinterpret_cast<const float*>(ds + off_qn);
     if (k2h) sp.q_scr = reinterpret_cast<const uint4*>(ds + off_qh);
+    if (c->sparse) {
+        sp.sp_off = c->d_sp_off;
+        sp.sp_tab = reinterpret_cast<const uint2*>(ds);
+        sp.sp_slots = sp_slots;
+        sp.sp_qtot = reinterpret_cast<const double*>(ds + off_qt);
+    }
     sp.partial = ctx->d_partial.as<uint64_t>();
     sp.cap = plan.k2 ? mfma_cap_for_k(kp) : scan_cap_for_rw((int) kp, c->shape.rw);
     if (plan.mq || plan.k2) {
@@ -585,6 +657,7 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
         else if (plan.mq) HIPCHK(launch_mq(sp, metric, launch_blocks, ctx->stream));
         else if (c->half) HIPCHK(launch_scan_half(sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream));
         else if (c->bit) HIPCHK(launch_scan_bit(sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream));
+        else if (c->sparse) HIPCHK(launch_scan_sparse(sp, metric, c->shape.lpr, plan.qi, plan.sparse_global, plan.n_blocks, ctx->stream));
         else HIPCHK(launch_scan(sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream));
         HIPCHK(main.stop());
         ctx->last_kernel = scan_kernel_name(plan, c, metric);
@@ -642,6 +715,7 @@ int search_impl(vsr_ctx* ctx, vsr_corpus* c, const Call& q, const vsr_filter* co
     ctx->screen_level = level;
     const auto h0 = Clock::now();
     ctx->int8_this_call = queries_are_u8(ctx, c, q, allow_screening);
+    if (q.sparse) ctx->sparse_slots = sparse_slots_for_nnz(q.sparse->max_nnz);
     static thread_local Plan plan;
     if (!make_plan(ctx, c, q.nq, q.k, q.metric, allow_screening, true, true, filters, plan)) {
         // K2g could not be seeded safely: K2w; K2w neither: legacy shared passes
@@ -662,13 +736,18 @@ int search_impl(vsr_ctx* ctx, vsr_corpus* c, const Call& q, const vsr_filter* co
 }  // namespace
 
 int vsr::check_search_args(const vsr_corpus* c, const void* queries, int nq, int dim, int k, int metric,
-                           const vsr_filter* const* filters, const char* who, bool bit_entry)
+                           const vsr_filter* const* filters, const char* who, bool bit_entry, bool sparse_entry)
 {
     if (!c) return fail(VSR_ERR_INVALID, "%s: corpus is NULL", who);
+    if (sparse_entry && !c->sparse) return fail(VSR_ERR_INVALID, "%s: the corpus is not a sparse corpus", who);
+    if (c->sparse && !sparse_entry)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus is searched with vsr_search_sparse* (<->, <#>, <=>, <+>) and has no index path yet", who);
     if (bit_entry && !c->bit) return fail(VSR_ERR_INVALID, "%s: the corpus is not a bit corpus", who);
     if (c->bit && !bit_entry)
         return fail(VSR_ERR_UNSUPPORTED, "%s: a bit corpus is searched with vsr_search_bit* (<~> / <%%>) and has no index path yet", who);
     if (nq < 0 || (nq > 0 && !queries)) return fail(VSR_ERR_INVALID, "%s: queries is NULL", who);
+    if (dim != c->dim && c->sparse)                         // CheckDims, sparsevec.c
+        return fail(VSR_ERR_DIM_MISMATCH, "different sparsevec dimensions %d and %d", c->dim, dim);
     if (dim != c->dim && c->bit)                            // CheckDims, bitvec.c:32-39: the column's length first
         return fail(VSR_ERR_DIM_MISMATCH, "different bit lengths %u and %u", (unsigned) c->dim, (unsigned) dim);
     if (dim != c->dim)                                      // CheckDims: vector.c:60-67, halfvec.c:60-67
@@ -875,17 +954,86 @@ extern "C" int vsr_search_bit(vsr_corpus* c, const uint8_t* queries, int nq, int
                        {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr});
 }
 
+// ORDER BY col <op> $1 LIMIT k over a sparse corpus (sparsevec.c:803-1037).  Exact by construction: nothing flags.
+static int search_sparse_device_on(vsr_ctx* session, vsr_corpus* c, const int64_t* d_indptr, const int32_t* d_indices, const float* d_values,
+                                   int nq, int dim, int max_query_nnz, int k, int metric, const vsr_filter* const* filters, int64_t* d_blk,
+                                   int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt, uint64_t* d_keys)
+{
+    const char* who = "vsr_search_sparse_device";
+    int rc = check_search_args(c, d_indptr, nq, dim, k, metric, filters, who, false, true);
+    if (rc) return rc;
+    if (max_query_nnz < 0 || max_query_nnz > SPARSE_MAX_NNZ)
+        return fail(VSR_ERR_INVALID, "%s: max_query_nnz must be between 0 and %d (got %d)", who, SPARSE_MAX_NNZ, max_query_nnz);
+    if (nq > 0 && max_query_nnz > 0 && (!d_indices || !d_values)) return fail(VSR_ERR_INVALID, "%s: queries is NULL", who);
+    vsr_ctx* ctx = session ? session : c->ctx;
+    if (ctx->device != c->ctx->device) return fail(VSR_ERR_INVALID, "vsr_search_sparse_device_on: session and corpus are on different devices");
+    if (nq == 0) return VSR_OK;
+    if (!d_blk || !d_dist || !d_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", who);
+    HIPCHK(hipSetDevice(ctx->device));
+    if (!d_doc) {
+        if ((rc = ctx->d_misc.reserve((size_t) nq * k * sizeof(int32_t)))) return rc;
+        d_doc = ctx->d_misc.as<int32_t>();
+    }
+    const SparseQueries sq{d_indptr, d_indices, d_values, false, (uint32_t) max_query_nnz};
+    return search_impl(ctx, c, {nullptr, nullptr, nq, dim, k, metric, {d_blk, d_doc, d_row, d_dist, d_cnt, d_keys}, &sq}, filters, 0);
+}
+
+extern "C" int vsr_search_sparse_device_on(vsr_ctx* session, vsr_corpus* c, const int64_t* d_indptr, const int32_t* d_indices,
+                                           const float* d_values, int nq, int dim, int max_query_nnz, int k, int metric,
+                                           const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc, int64_t* d_row,
+                                           float* d_dist, int32_t* d_cnt, uint64_t* d_keys)
+{
+    return search_sparse_device_on(session, c, d_indptr, d_indices, d_values, nq, dim, max_query_nnz, k, metric, filters, d_blk, d_doc,
+                                   d_row, d_dist, d_cnt, d_keys);
+}
+
+extern "C" int vsr_search_sparse_device(vsr_corpus* c, const int64_t* d_indptr, const int32_t* d_indices, const float* d_values, int nq,
+                                        int dim, int max_query_nnz, int k, int metric, const vsr_filter* const* filters, int64_t* d_blk,
+                                        int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt, uint64_t* d_keys)
+{
+    return search_sparse_device_on(nullptr, c, d_indptr, d_indices, d_values, nq, dim, max_query_nnz, k, metric, filters, d_blk, d_doc,
+                                   d_row, d_dist, d_cnt, d_keys);
+}
+
+extern "C" int vsr_search_sparse(vsr_corpus* c, const int64_t* q_indptr, const int32_t* q_indices, const float* q_values, int nq, int dim,
+                                 int k, int metric, const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc,
+                                 int64_t* out_row, float* out_dist, int32_t* out_cnt)
+{
+    const char* who = "vsr_search_sparse";
+    int rc = check_search_args(c, q_indptr, nq, dim, k, metric, filters, who, false, true);
+    if (rc) return rc;
+    uint32_t max_nnz = 0;
+    if ((rc = check_sparse_rows(who, q_indptr, q_indices, q_values, nq, dim, &max_nnz))) return rc;
+    if (nq == 0) return VSR_OK;
+    if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", who);
+    vsr_ctx* ctx = c->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    const ResultBlock rb(nq, k, false);                     // results in device memory, one packed copy back, one wait
+    if ((rc = ctx->d_out.reserve(rb.o_status))) return rc;
+    if ((rc = ctx->h_out.reserve(rb.total))) return rc;
+    char* d = ctx->d_out.as<char>();
+    char* h = ctx->h_out.as<char>();
+    const SparseQueries sq{q_indptr, q_indices, q_values, true, max_nnz};
+    if ((rc = search_impl(ctx, c, {nullptr, nullptr, nq, dim, k, metric, rb.arrays(d), &sq}, filters, 0))) return rc;
+    HIPCHK(hipMemcpyAsync(h, d, rb.o_status, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    rb.copy_out_all(h, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr}, nullptr);
+    return VSR_OK;
+}
+
 // ---- two-stage search: Hamming shortlist on the bits (K1b), exact re-rank on the source rows ------------------------
 // What the three vsr_search_quantized* entry points share.  Exactly one of h_queries / d_queries is set; `out` addresses
 // device memory either way (the host entry point hands in its result block).  Everything is enqueued on ctx->stream:
 //   binary_quantize of the queries -> stage 1 = the internal search over `bits` with k = shortlist, its keys into the
 //   session's scratch -> shortlist_rerank_kernel over the source rows -> shortlist_emit_kernel.
-static const char* corpus_kind(const vsr_corpus* c) { return c->bit ? "bit" : c->half ? "halfvec" : "vector"; }
+static const char* corpus_kind(const vsr_corpus* c) { return c->sparse ? "sparsevec" : c->bit ? "bit" : c->half ? "halfvec" : "vector"; }
 
 static int check_quantized_args(const vsr_ctx* session, const vsr_corpus* src, const vsr_corpus* bits, const void* queries, int nq,
                                 int dim, int k, int shortlist, int metric, const vsr_filter* const* filters, const char* who)
 {
     if (!src || !bits) return fail(VSR_ERR_INVALID, "%s: corpus is NULL", who);
+    if (src->sparse || bits->sparse)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no two-stage search (pgvector defines no binary_quantize for sparsevec)", who);
     if (src->bit) return fail(VSR_ERR_INVALID, "%s: the source corpus is a bit corpus (the re-rank needs the fp32 or halfvec rows)", who);
     if (src->base) return fail(VSR_ERR_INVALID, "%s: the source corpus is an index view", who);
     if (!bits->bit) return fail(VSR_ERR_INVALID, "%s: the bits corpus is not a bit corpus", who);

@@ -40,6 +40,8 @@ SYMBOLS = {
     "vsr_corpus_load_bit": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i64, C.POINTER(_vp)]),
     "vsr_corpus_is_bit": (_i, [_vp]),
     "vsr_corpus_binary_quantize": (_i, [_vp, C.POINTER(_vp)]),
+    "vsr_corpus_load_sparse": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _i64, C.POINTER(_vp)]),
+    "vsr_corpus_is_sparse": (_i, [_vp]),
     "vsr_corpus_device_bytes": (_i64, [_vp]),
     "vsr_corpus_free": (_i, [_vp]),
     "vsr_corpus_rows": (_i64, [_vp]),
@@ -56,6 +58,9 @@ SYMBOLS = {
     "vsr_search_bit": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_search_bit_device": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_search_bit_device_on": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_search_sparse": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_search_sparse_device": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_search_sparse_device_on": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_search_quantized": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_search_quantized_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_search_quantized_device_on": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -71,6 +76,7 @@ SYMBOLS = {
     "vsr_pair_distances": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp]),
     "vsr_bit_pair_distances": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp]),
     "vsr_binary_quantize": (_i, [_vp, _vp, _i64, _i, _vp]),
+    "vsr_sparse_pair_distances": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
     "vsr_ivf_load": (_i, [_vp, _vp, _i, _vp, C.POINTER(_vp)]),
     "vsr_ivf_free": (_i, [_vp]),
     "vsr_ivf_assign": (_i, [_vp, _vp, _i, _i, _vp]),

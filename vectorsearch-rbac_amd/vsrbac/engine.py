@@ -71,6 +71,24 @@ def _packed_bits(a, dim, what):
     return a, int(dim)
 
 
+def _csr(indptr, indices=None, values=None, dim=None, what="sparse rows"):
+    """Sparse rows as (indptr int64 [n + 1], indices int32 [nnz] zero-based, values float32 [nnz], dim): three arrays plus `dim`,
+    or any object with .indptr / .indices / .data / .shape (a scipy.sparse CSR matrix; scipy itself is not needed)."""
+    if indices is None and values is None and hasattr(indptr, "indptr"):
+        m = indptr
+        indptr, indices, values = m.indptr, m.indices, m.data
+        if dim is None:
+            dim = m.shape[1]
+    if indices is None or values is None or dim is None:
+        raise ValueError(f"{what}: give indptr, indices, values and dim, or an object with .indptr / .indices / .data / .shape")
+    ip = np.ascontiguousarray(indptr, dtype=np.int64).reshape(-1)
+    ix = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+    vx = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+    if ip.size < 1 or ix.size != vx.size or (ip.size > 1 and (int(ip.max()) > ix.size or int(ip.min()) < 0)):
+        raise ValueError(f"{what}: indptr has n + 1 entries addressing indices / values of equal length")
+    return ip, ix, vx, int(dim)
+
+
 class Context:
     """One MI355X.  Fails loudly (VsrError) when there is no gfx950 device."""
 
@@ -175,6 +193,27 @@ class Context:
         array (packed here with np.packbits; dim may then be omitted).  Searches go through Corpus.search_bit."""
         packed, dim = _packed_bits(rows, dim, "load_corpus_bit")
         return Corpus(self, packed, block_ids, doc_ids, row_offset, bit_dim=dim)
+
+    def load_corpus_sparse(self, indptr, indices=None, values=None, dim=None, block_ids=None, doc_ids=None, row_offset=0):
+        """A sparse corpus (vsr_corpus_load_sparse, pgvector's sparsevec): CSR rows as three arrays plus `dim` (zero-based
+        indices), or any object with .indptr / .indices / .data / .shape.  Rows are validated as sparsevec_recv validates a
+        value (VsrError in pgvector's words).  Searches go through Corpus.search_sparse."""
+        ip, ix, vx, dim = _csr(indptr, indices, values, dim, "load_corpus_sparse")
+        return Corpus(self, None, block_ids, doc_ids, row_offset, sparse=(ip, ix, vx, dim))
+
+    def sparse_pair_distances(self, metric, a, b):
+        """sparsevec's <->, <#>, <=>, <+> for pairs (a[i], b[i]): a, b are (indptr, indices, values, dim) tuples or objects with
+        .indptr / .indices / .data / .shape, of equally many rows.  The operator's float8, bit for bit (one thread per pair runs
+        sparsevec.c's own merge).  Raises VsrError('different sparsevec dimensions %d and %d') on a mismatch."""
+        pa = _csr(*a, what="sparse_pair_distances") if isinstance(a, (tuple, list)) else _csr(a, what="sparse_pair_distances")
+        pb = _csr(*b, what="sparse_pair_distances") if isinstance(b, (tuple, list)) else _csr(b, what="sparse_pair_distances")
+        n = pa[0].size - 1
+        if pb[0].size - 1 != n:
+            raise ValueError("sparse_pair_distances: a and b must hold equally many rows")
+        out = np.empty(n, dtype=np.float64)
+        check(self._lib.vsr_sparse_pair_distances(self._h, _metric(metric), _ptr(pa[0]), _ptr(pa[1]), _ptr(pa[2]), _ptr(pb[0]),
+                                                  _ptr(pb[1]), _ptr(pb[2]), n, pa[3], pb[3], _ptr(out)))
+        return out
 
     def bit_pair_distances(self, metric, a, b, dim=None, dim_b=None):
         """hamming_distance / jaccard_distance for pairs (a[i], b[i]) of bit strings, bool or packed uint8 (then with `dim`;
@@ -289,9 +328,24 @@ class Filter:
 class Corpus:
     """Rows resident in HBM, identified as (document_id, block_id) like the reference's documentblocks table."""
 
-    def __init__(self, ctx, rows, block_ids=None, doc_ids=None, row_offset=0, half=False, bit_dim=None):
+    def __init__(self, ctx, rows, block_ids=None, doc_ids=None, row_offset=0, half=False, bit_dim=None, sparse=None):
         self.ctx = ctx
         self._lib = ctx._lib
+        if sparse is not None:                       # (indptr, indices, values, dim) as _csr returns them (Context.load_corpus_sparse)
+            ip, ix, vx, dim = sparse
+            n = ip.size - 1
+            blk = None if block_ids is None else np.ascontiguousarray(block_ids, dtype=np.int64)
+            doc = None if doc_ids is None else np.ascontiguousarray(doc_ids, dtype=np.int32)
+            if (blk is not None and blk.size != n) or (doc is not None and doc.size != n):
+                raise ValueError("block_ids / doc_ids must have one entry per row")
+            h = C.c_void_p()
+            check(self._lib.vsr_corpus_load_sparse(ctx._h, _ptr(ip), _ptr(ix), _ptr(vx), n, dim, _ptr(blk), _ptr(doc),
+                                                   int(row_offset), C.byref(h)))
+            self._h = h
+            self.n, self.dim = n, dim
+            self.row_offset = int(row_offset)
+            self._user_filters = {}
+            return
         bit = bit_dim is not None                    # rows: packed uint8 [n, (bit_dim + 7) // 8] (Context.load_corpus_bit)
         rows = np.ascontiguousarray(rows, dtype=np.uint8 if bit else np.float16 if half else np.float32)
         if rows.ndim != 2:
@@ -320,6 +374,11 @@ class Corpus:
     def is_bit(self):
         """True for a bit corpus (Context.load_corpus_bit, Corpus.binary_quantize)."""
         return bool(self._lib.vsr_corpus_is_bit(self._h))
+
+    @property
+    def is_sparse(self):
+        """True for a sparse corpus (Context.load_corpus_sparse)."""
+        return bool(self._lib.vsr_corpus_is_sparse(self._h))
 
     def binary_quantize(self):
         """A bit corpus of this corpus's resident rows, quantized on the device (vsr_corpus_binary_quantize): same context,
@@ -474,6 +533,37 @@ class Corpus:
                                        _ptr(row), _ptr(dist), _ptr(cnt)))
         del keep
         return SearchResult(blk, doc, row, dist, cnt)
+
+    def search_sparse(self, queries, k, metric="l2", filters=None, indices=None, values=None, dim=None):
+        """Corpus.search over a sparse corpus: `queries` as CSR -- an object with .indptr / .indices / .data / .shape, or the
+        indptr array with `indices`, `values` (dim: the corpus's unless given).  metric "l2", "ip", "cosine" or "l1".
+        Exact; never flags."""
+        if indices is None and hasattr(queries, "indptr"):
+            ip, ix, vx, qdim = _csr(queries, dim=dim, what="search_sparse")
+        else:
+            ip, ix, vx, qdim = _csr(queries, indices, values, self.dim if dim is None else dim, "search_sparse")
+        nq = ip.size - 1
+        farr, keep = self._filter_array(filters, nq)
+        kk = max(int(k), 1)
+        blk = np.full((nq, kk), -1, dtype=np.int64)
+        doc = np.full((nq, kk), -1, dtype=np.int32)
+        row = np.full((nq, kk), -1, dtype=np.int64)
+        dist = np.full((nq, kk), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.int32)
+        check(self._lib.vsr_search_sparse(self._h, _ptr(ip), _ptr(ix), _ptr(vx), nq, qdim, int(k), _metric(metric), farr,
+                                          _ptr(blk), _ptr(doc), _ptr(row), _ptr(dist), _ptr(cnt)))
+        del keep
+        return SearchResult(blk, doc, row, dist, cnt)
+
+    def search_sparse_device(self, d_indptr, d_indices, d_values, nq, max_query_nnz, k, metric, filters, d_block, d_doc, d_rows,
+                             d_dist, d_counts, d_keys=None, dim=None, session=None):
+        """search_device over a sparse corpus (vsr_search_sparse_device_on): the queries' CSR arrays in device memory (int64,
+        int32, float32) and the largest non-zero count of any of them; a longer query fails screening_check."""
+        farr, keep = self._filter_array(filters, nq)
+        check(self._lib.vsr_search_sparse_device_on(session._h if session is not None else None, self._h, d_indptr, d_indices,
+                                                    d_values, nq, self.dim if dim is None else dim, int(max_query_nnz), int(k),
+                                                    _metric(metric), farr, d_block, d_doc, d_rows, d_dist, d_counts, d_keys))
+        return keep
 
     def search_bit_device(self, d_queries, nq, k, metric, filters, d_block, d_doc, d_rows, d_dist, d_counts, d_keys=None,
                           dim=None, session=None):

@@ -7,6 +7,8 @@
     arrays are np.float16, what Context.load_corpus_half takes
   * PostgreSQL's bit / varbit, the operand type of pgvector's <~> and <%> (bitvec.c): '0' / '1' digit text; binary form int32
     bit length, big-endian, then the packed bytes.  Values are bool arrays, what Context.load_corpus_bit packs
+  * pgvector's sparsevec (sparsevec.c:187-565): text `{i:v,...}/dim` with one-based indices; binary int32 dim, nnz, unused,
+    then the zero-based indices and the float4 values.  Values are (indices, values, dim) rows of a CSR corpus
   * shared_vectors.bin (+ .meta) of the C++ benches   SharedVectorTable::save_vectors / load_vectors
     (logical_partition_benchmark/benchmark/src/shared_vector_table.cpp:169-201): int32 dim, int64 count, float32[count*dim];
     .meta = int32 dim, int64 count, (int32 document_id, int32 block_id)[count]
@@ -257,6 +259,177 @@ def bit_to_binary(v):
     """varbit_send: int32 bit length, big-endian, then the packed bytes with zero pad bits."""
     v = np.asarray(v, dtype=np.bool_).ravel()
     return struct.pack(">i", v.size) + np.packbits(v).tobytes()
+
+
+# ---- pgvector's sparsevec (sparsevec.c).  A value here is (indices int32 zero-based ascending, values float32, dim): one row of
+# the CSR arrays Context.load_corpus_sparse takes.  Text is `{i:v,...}/dim` with ONE-based indices; the binary form is
+# sparsevec_send's: int32 dim, int32 nnz, int32 unused (= 0), nnz int32 zero-based indices, nnz float4, all big-endian.
+SPARSEVEC_MAX_DIM = 1000000000                            # sparsevec.h
+SPARSEVEC_MAX_NNZ = 16000
+_INT_MAX, _INT_MIN = 2147483647, -2147483648
+
+
+def _check_sparsevec_dim(dim):
+    if dim < 1:
+        raise ValueError("sparsevec must have at least 1 dimension")          # CheckDim, sparsevec.c:53-65
+    if dim > SPARSEVEC_MAX_DIM:
+        raise ValueError(f"sparsevec cannot have more than {SPARSEVEC_MAX_DIM} dimensions")
+
+
+def _check_sparsevec_typmod(expected_dim):
+    if expected_dim is None or expected_dim == -1:
+        return
+    if expected_dim < 1:
+        raise ValueError("dimensions for type sparsevec must be at least 1")  # sparsevec_typmod_in, sparsevec.c:461-487
+    if expected_dim > SPARSEVEC_MAX_DIM:
+        raise ValueError(f"dimensions for type sparsevec cannot exceed {SPARSEVEC_MAX_DIM}")
+
+
+def _check_sparsevec_indices(indices, dim):
+    for i, index in enumerate(indices):                                       # CheckIndex, sparsevec.c:92-116
+        if index < 0 or index >= dim:
+            raise ValueError("sparsevec index out of bounds")
+        if i > 0 and index < indices[i - 1]:
+            raise ValueError("sparsevec indices must be in ascending order")
+        if i > 0 and index == indices[i - 1]:
+            raise ValueError("sparsevec indices must not contain duplicates")
+
+
+def _strtol(raw, pos):
+    """strtol(base 10) at raw[pos:]: (value, end), end == pos when no digits were read."""
+    p, n = pos, len(raw)
+    while p < n and chr(raw[p]) in _SPACE:
+        p += 1
+    q = p + 1 if raw[p:p + 1] in (b"+", b"-") else p
+    e = q
+    while e < n and 48 <= raw[e] <= 57:
+        e += 1
+    if e == q:
+        return 0, pos
+    return int(raw[p:e]), e
+
+
+def sparsevec_from_text(lit, expected_dim=None):
+    """sparsevec_in (sparsevec.c:187-389): same grammar, same number parsers, same error texts; zero values are dropped, the
+    entries sorted by index.  Returns (indices int32 zero-based, values float32, dim)."""
+    _check_sparsevec_typmod(expected_dim)
+    if isinstance(lit, bytes):
+        lit = lit.decode()
+    raw = lit.encode()
+    bad = f'invalid input syntax for type sparsevec: "{lit}"'
+    n = len(raw)
+    if raw.count(b",") + 1 > SPARSEVEC_MAX_NNZ:
+        raise ValueError(f"sparsevec cannot have more than {SPARSEVEC_MAX_NNZ} non-zero elements")
+
+    def skip(p):
+        while p < n and chr(raw[p]) in _SPACE:
+            p += 1
+        return p
+
+    pos = skip(0)
+    if raw[pos:pos + 1] != b"{":
+        raise ValueError(bad + '\nDETAIL:  Vector contents must start with "{".')
+    pos = skip(pos + 1)
+    elements = []
+    if raw[pos:pos + 1] == b"}":
+        pos += 1
+    else:
+        buf = ctypes.create_string_buffer(raw + b"\0")
+        base = ctypes.addressof(buf)
+        while True:
+            pos = skip(pos)
+            if pos >= n:
+                raise ValueError(bad)
+            index, stop = _strtol(raw, pos)
+            if stop == pos:
+                raise ValueError(bad)
+            index = min(max(index, _INT_MIN + 1), _INT_MAX)               # "keep in int range for correct error message later"
+            pos = skip(stop)
+            if raw[pos:pos + 1] != b":":
+                raise ValueError(bad)
+            pos = skip(pos + 1)
+            end = ctypes.c_char_p()
+            ctypes.set_errno(0)
+            val = _libc.strtof(ctypes.c_char_p(base + pos), ctypes.byref(end))
+            stop = ctypes.cast(end, ctypes.c_void_p).value - base
+            if stop == pos:
+                raise ValueError(bad)
+            if ctypes.get_errno() == _ERANGE and (val == 0 or math.isinf(val)):
+                raise ValueError(f'"{raw[pos:stop].decode()}" is out of range for type sparsevec')
+            _check_element(val, "sparsevec")
+            if val != 0:                                                      # zero values are not stored
+                elements.append((index - 1, val))                             # 1-based (SQL) -> 0-based
+            pos = skip(stop)
+            c = raw[pos:pos + 1]
+            if c == b",":
+                pos += 1
+            elif c == b"}":
+                pos += 1
+                break
+            else:
+                raise ValueError(bad)
+    pos = skip(pos)
+    if raw[pos:pos + 1] != b"/":
+        raise ValueError(bad + "\nDETAIL:  Unexpected end of input.")
+    pos = skip(pos + 1)
+    dim, stop = _strtol(raw, pos)
+    if stop == pos:
+        raise ValueError(bad)
+    dim = min(max(dim, _INT_MIN), _INT_MAX)
+    pos = skip(stop)
+    if pos != n:
+        raise ValueError(bad + "\nDETAIL:  Junk after closing.")
+    _check_sparsevec_dim(dim)
+    _check_expected(expected_dim, dim)
+    elements.sort(key=lambda e: e[0])
+    _check_sparsevec_indices([e[0] for e in elements], dim)
+    return (np.asarray([e[0] for e in elements], dtype=np.int32), np.asarray([e[1] for e in elements], dtype=np.float32), dim)
+
+
+def sparsevec_to_text(indices, values, dim):
+    """sparsevec_out (sparsevec.c:408-456): one-based indices, the shortest float4 decimal of every value."""
+    indices = np.asarray(indices, dtype=np.int64).ravel()
+    values = np.asarray(values, dtype=np.float32).ravel()
+    return "{" + ",".join(f"{int(i) + 1}:{_float4_shortest(v)}" for i, v in zip(indices, values)) + "}/" + str(int(dim))
+
+
+def sparsevec_from_binary(b, expected_dim=None):
+    """sparsevec_recv (sparsevec.c:492-539).  Returns (indices int32 zero-based, values float32, dim)."""
+    _check_sparsevec_typmod(expected_dim)
+    if len(b) < 12:
+        raise ValueError("insufficient data left in message")
+    dim, nnz, unused = struct.unpack(">iii", b[:12])
+    _check_sparsevec_dim(dim)
+    if nnz < 0:                                                               # CheckNnz, sparsevec.c:70-87
+        raise ValueError("sparsevec cannot have negative number of elements")
+    if nnz > SPARSEVEC_MAX_NNZ:
+        raise ValueError(f"sparsevec cannot have more than {SPARSEVEC_MAX_NNZ} non-zero elements")
+    if nnz > dim:
+        raise ValueError("sparsevec cannot have more elements than dimensions")
+    _check_expected(expected_dim, dim)
+    if unused != 0:
+        raise ValueError(f"expected unused to be 0, not {unused}")
+    if len(b) < 12 + 4 * nnz:
+        raise ValueError("insufficient data left in message")
+    indices = np.frombuffer(b, dtype=">i4", count=nnz, offset=12).astype(np.int32)
+    _check_sparsevec_indices([int(i) for i in indices], dim)
+    if len(b) != 12 + 8 * nnz:
+        raise ValueError("insufficient data left in message" if len(b) < 12 + 8 * nnz else "incorrect binary data format")
+    values = np.frombuffer(b, dtype=">f4", count=nnz, offset=12 + 4 * nnz).astype(np.float32)
+    for v in values:
+        _check_element(float(v), "sparsevec")
+        if v == 0:
+            raise ValueError("binary representation of sparsevec cannot contain zero values")
+    return indices, values, dim
+
+
+def sparsevec_to_binary(indices, values, dim):
+    """sparsevec_send (sparsevec.c:544-565)."""
+    indices = np.asarray(indices, dtype=np.int32).ravel()
+    values = np.asarray(values, dtype=np.float32).ravel()
+    if indices.size != values.size:
+        raise ValueError("sparsevec: one value per index")
+    return struct.pack(">iii", int(dim), indices.size, 0) + indices.astype(">i4").tobytes() + values.astype(">f4").tobytes()
 
 
 def write_shared_vectors(path, rows, doc_ids, block_ids):
