@@ -324,6 +324,32 @@ hipError_t launch_select_rerank(const RerankParams& p, uint32_t n_queries, hipSt
 // m = lambda + 6 sqrt(lambda) + 4 with lambda = kp * frac * (kept / sampled): frac = the densest pass's sampling fraction
 hipError_t launch_seed_select(const uint64_t* samp, const uint32_t* samp_cnt, uint32_t cap, float kp_frac, uint64_t* tau,
                               uint32_t n_queries, hipStream_t s);
+// One wave per query for both selections of an exact_screen plan (int8 planes): 64-thread workgroups inside what four
+// resident int8 main workgroups leave of a CU -- 96 VGPRs and a wave slot per SIMD, 32 KB of LDS (vsr_kernels.hip).
+// vsr_ctx::select_wave (VSR_SELECT_WAVE=0) keeps seed_select_kernel / select_rerank_kernel instead.
+constexpr int SELW_THREADS = 64;
+constexpr int SELW_OCC = 5;                              // waves per SIMD the register allocation aims at: 512 / 5 -> 96 VGPRs
+constexpr uint32_t SEED_MAX_M = 1024;                   // a seed needs m < SEED_MAX_M sampled keys kept (one select chunk of 64 x 16)
+__host__ __device__ inline uint32_t seed_rank_of(float lambda) { return (uint32_t) ceilf(lambda + 6.0f * sqrtf(lambda)) + 4u; }
+// kept keys a seed launch needs room for: m grows with lambda and lambda <= kp_frac.  One key more than the host's own m: the
+// device may contract lambda + 6 sqrt(lambda) into one rounding, which moves the sum by an ulp and m by at most one
+inline uint32_t seed_wave_keep_cap(float kp_frac)
+{
+    const float m = ceilf(kp_frac + 6.0f * sqrtf(kp_frac)) + 5.0f;
+    return m < (float) (SEED_MAX_M - 1) ? (uint32_t) m : SEED_MAX_M - 1;
+}
+inline size_t seed_wave_lds_bytes(uint32_t keep_cap) { return (size_t) keep_cap * 8; }          // + 1 KB of histogram (static)
+inline size_t select_emit_wave_lds_bytes(uint32_t kp)                                            // np2 keys; + 1 KB of histogram (static)
+{
+    uint32_t np2 = 2;
+    while (np2 < kp) np2 <<= 1;
+    return (size_t) np2 * 8;
+}
+hipError_t launch_seed_select_wave(const uint64_t* samp, const uint32_t* samp_cnt, uint32_t cap, float kp_frac, uint64_t* tau,
+                                   uint32_t n_queries, hipStream_t s);
+// the final selection of an exact_screen plan (kp = k <= GQ_MAX_KP): select, sort, count / flag rules and outputs of
+// select_rerank_kernel's exact_screen path, without its re-rank waves and without reading the fp32 query
+hipError_t launch_select_emit_wave(const RerankParams& p, uint32_t n_queries, hipStream_t s);
 hipError_t launch_norm_max(const float* norm2, uint32_t n, float* out_max, hipStream_t s);
 hipError_t launch_select(const SelectParams& p, uint32_t n_queries, int threads, hipStream_t s);   // threads: 64 (one wave per query) | 256 | 1024
 uint32_t select_wave_fanin(uint32_t kp);

@@ -1169,6 +1169,94 @@ hipError_t launch_select_rerank(const RerankParams& p, uint32_t n_queries, hipSt
     return hipGetLastError();
 }
 
+// K2w / K2i over the int8 planes (exact_screen): the final selection as ONE wave per query.  The screening values are the
+// exact distances, so there is no re-rank and nothing for three more waves to do: the kp = k smallest keys of the query's
+// buffer (stream select), a wave-level sort, then rerank_body's count and flag rules of the exact_screen path and the
+// outputs.  A 64-thread workgroup inside 96 VGPRs and ~5 KB of LDS takes any free wave slot beside four resident main
+// workgroups (104 VGPRs per wave, 32 KB of LDS each), so the 1000 queries of a batch are one resident round of four per
+// CU.  Neither the fp32 query nor the fp32 rows are read.
+__global__ __launch_bounds__(SELW_THREADS, SELW_OCC) void select_emit_wave_kernel(const RerankParams p)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    uint64_t* keys = reinterpret_cast<uint64_t*>(smem);                   // [np2]
+    __shared__ uint32_t hist[256];
+    // Everything after the select -- seventeen pointers and a few words -- is read from the kernel-argument segment (the
+    // explicit arguments start at its offset 0) where it is used: held in SGPRs across the stream select, those ~40
+    // registers push the kernel past the 102 a wave has, and the compiler parks the rest in VGPR lanes.
+    const auto* late = (const __attribute__((address_space(4))) RerankParams*) __builtin_amdgcn_kernarg_segment_ptr();
+    const int lane = threadIdx.x;
+    const uint32_t slot = blockIdx.x;
+    const uint32_t np2 = next_pow2(p.kp);
+    const uint32_t cnt = p.qcnt[slot];
+    const uint32_t n = cnt < p.capq ? cnt : p.capq;
+    uint64_t kth;
+    const uint32_t want = wave_select_stream<16>(p.qcand + (size_t) slot * p.capq, n, p.kp, keys, hist, lane, kth);
+    for (uint32_t i = want + (uint32_t) lane; i < np2; i += 64) keys[i] = KEY_EMPTY;
+    const uint64_t worst_kept = n >= p.kp ? kth : KEY_EMPTY;              // (kth: the same value in every lane)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    bitonic_sort_wave(keys, np2, lane);
+
+    // how many keys exist, and the flag: every lane computes both (LDS broadcasts), lane 0 reports them
+    const uint32_t k = late->k;
+    uint32_t lo = 0, hi = p.kp < np2 ? p.kp : np2;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (keys[mid] != KEY_EMPTY) lo = mid + 1; else hi = mid;
+    }
+    const uint32_t* qbad = late->qbad;
+    int flag = (cnt > p.capq || (qbad && qbad[slot])) ? 1 : 0;           // a buffer that overflowed lost candidates
+    // every row outside the kept set ranks at or after `bound`: the worst kept candidate when the list is full, else the
+    // seeded threshold (if any), else there is no outside row at all
+    const SelectQuery sq = late->queries[slot];
+    uint64_t bound = worst_kept;
+    if (bound == KEY_EMPTY && late->seeded) bound = late->tau_init[slot];
+    if (bound != KEY_EMPTY && lo < k && lo < sq.allowed) flag = 1;        // the threshold cut below the k-th result
+    const uint32_t out_slot = sq.out_slot;
+    const uint32_t m = lo < k ? lo : k;
+    if (lane == 0) {
+        late->out_flags[out_slot] = flag;
+        if (flag) atomicAdd(late->flagged_total, 1);
+        late->out_count[out_slot] = flag ? -1 - (int32_t) m : (int32_t) m;    // flagged: -1 - count (see select_emit)
+    }
+    const size_t o = (size_t) out_slot * k;
+    const int metric = late->metric;
+    const uint32_t row_offset = late->row_offset;
+    const int64_t* block_ids = late->block_ids;
+    const int32_t* doc_ids = late->doc_ids;
+    const int64_t* orig_rows = late->orig_rows;
+    int64_t* out_block = late->out_block + o;
+    int32_t* out_doc = late->out_doc + o;
+    int64_t* out_row = late->out_row ? late->out_row + o : nullptr;
+    float* out_dist = late->out_dist + o;
+    uint64_t* out_keys = late->out_keys ? late->out_keys + o : nullptr;
+    for (uint32_t i = (uint32_t) lane; i < k; i += 64) {
+        if (i < m) {
+            const uint64_t key = keys[i];
+            const uint32_t row = (uint32_t) key;
+            const float v = mono_to_float((uint32_t) (key >> 32));
+            out_block[i] = block_ids[row];
+            out_doc[i] = doc_ids[row];
+            if (out_row) out_row[i] = orig_rows[row];
+            out_dist[i] = output_distance(metric, v);
+            if (out_keys) out_keys[i] = (key & 0xFFFFFFFF00000000ull) | (uint64_t) (row + row_offset);
+        } else {
+            out_block[i] = -1;
+            out_doc[i] = -1;
+            if (out_row) out_row[i] = -1;
+            out_dist[i] = __builtin_inff();
+            if (out_keys) out_keys[i] = KEY_EMPTY;
+        }
+    }
+}
+
+hipError_t launch_select_emit_wave(const RerankParams& p, uint32_t n_queries, hipStream_t s)
+{
+    if (p.capq != GQ_CAP || p.kp > GQ_MAX_KP || p.kp == 0 || !p.exact_screen) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(select_emit_wave_kernel, dim3(n_queries), dim3(SELW_THREADS), select_emit_wave_lds_bytes(p.kp), s, p);
+    return hipGetLastError();
+}
+
 // Threshold seeds of K2w: per query, the m-th smallest of its sampled keys; every row ranking at or before it stays
 // eligible in the main pass (low word all ones: ties of that distance included); too few samples: no threshold.
 __global__ __launch_bounds__(256) void seed_select_kernel(const uint64_t* samp, const uint32_t* samp_cnt, uint32_t cap,
@@ -1194,6 +1282,42 @@ hipError_t launch_seed_select(const uint64_t* samp, const uint32_t* samp_cnt, ui
 {
     if (cap != GQ_SAMPLE_CAP || !(kp_frac > 0.0f)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(seed_select_kernel, dim3((n_queries + 3) / 4), dim3(256), 0, s, samp, samp_cnt, cap, kp_frac, tau, n_queries);
+    return hipGetLastError();
+}
+
+// The same seeds, one query per 64-thread workgroup.  seed_select_kernel reserves 1024 kept keys per wave (36 KB per
+// workgroup) and 104 VGPRs: beside four resident int8 main workgroups it is not resident at all and runs in the gaps they
+// leave.  Here the survivor list is dynamic LDS for the launch's largest m (`keep_cap` keys; m grows with lambda, and
+// lambda <= kp_frac), so a workgroup is 1 KB of histogram + 8 m bytes (~26 keys at the headline's shape) inside 96 VGPRs: it
+// takes any free wave slot, and a 1000-query batch is one resident round.
+__global__ __launch_bounds__(SELW_THREADS, SELW_OCC) void seed_select_wave_kernel(const uint64_t* samp, const uint32_t* samp_cnt, uint32_t cap,
+                                                                                  float kp_frac, uint64_t* tau, uint32_t keep_cap)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    uint64_t* keep = reinterpret_cast<uint64_t*>(smem);      // [keep_cap]
+    __shared__ uint32_t hist[256];
+    const int lane = threadIdx.x;
+    const uint32_t q = blockIdx.x;
+    const uint32_t cnt = samp_cnt[q];
+    const uint32_t n = cnt < cap ? cnt : cap;
+    // a buffer that overflowed holds a subset of the sample: the effective sampling fraction shrinks with it
+    const float lambda = kp_frac * (cnt > n ? (float) n / (float) cnt : 1.0f);
+    const uint32_t m = seed_rank_of(lambda);
+    // (m <= keep_cap always holds -- the launcher sized the list from kp_frac; it is tested because it bounds the LDS writes)
+    const bool seeded = n >= m && m < SEED_MAX_M && m <= keep_cap;
+    uint64_t kth = KEY_EMPTY;
+    if (seeded) (void) wave_select_stream<16>(samp + (size_t) q * cap, n, m, keep, hist, lane, kth);
+    if (lane == 0) tau[q] = seeded ? (kth | 0xFFFFFFFFull) : KEY_EMPTY;
+}
+
+hipError_t launch_seed_select_wave(const uint64_t* samp, const uint32_t* samp_cnt, uint32_t cap, float kp_frac, uint64_t* tau,
+                                   uint32_t n_queries, hipStream_t s)
+{
+    if (cap != GQ_SAMPLE_CAP || !(kp_frac > 0.0f)) return hipErrorInvalidValue;
+    if (n_queries == 0) return hipSuccess;
+    const uint32_t keep_cap = seed_wave_keep_cap(kp_frac);
+    hipLaunchKernelGGL(seed_select_wave_kernel, dim3(n_queries), dim3(SELW_THREADS), seed_wave_lds_bytes(keep_cap), s, samp, samp_cnt, cap,
+                       kp_frac, tau, keep_cap);
     return hipGetLastError();
 }
 

@@ -156,6 +156,8 @@ struct vsr_ctx {
     bool last_k2i = false;         // the last main launch was eligible for K2i
     uint32_t sample_rounds = 1;    // VSR_SAMPLE_ROUNDS=1..4: resident rounds of workgroups the K2w-family sample launch is cut into (A/B)
     bool sample_reg = true;        // VSR_SAMPLE_REG=0: the int8 sample pass of a class-view plan on K2i's streams instead of K2r's registers (A/B)
+    bool select_wave = true;       // VSR_SELECT_WAVE=0: seed and final selection of an int8 (exact_screen) plan on seed_select_kernel /
+                                   // select_rerank_kernel instead of the one-wave-per-query kernels (A/B, tests)
     bool k2i_sample = true;        // VSR_NO_K2I_SAMPLE=1: the int8 sample pass on K2w's kernel instead of K2i's streams (A/B)
     bool no_scan8 = false;         // VSR_NO_SCAN8=1: one-query calls on the fp32 rows even when the int8 planes apply (A/B)
     bool k2i_wide = false;         // VSR_K2I_WIDE=1 (with VSR_K2I=1): 128-column passes on K2i

@@ -346,6 +346,8 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
     auto launch_pass = [&](uint32_t blocks, hipStream_t s) { return plan.k2g ? launch_gemm(sp, metric, blocks, s) : launch_mfmaw(sp, metric, blocks, s); };
     sp.q_slots = reinterpret_cast<const uint32_t*>(ds + off_qs);
 
+    // int8 planes (exact_screen): seed and final selection as one wave per query, resident beside the main launches
+    const bool wave_select = plan.int8 && ctx->select_wave;
     if (plan.n_blocks) {
         // ---- sample pass: every sample_stride-th tile, open threshold, into the queries' sample buffers ----
         Timed sample(ctx, 3, ctx->stream);                  // sample pass + seed select together
@@ -359,8 +361,8 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
         sp.capq = GQ_SAMPLE_CAP;
         sp.k2i = plan.k2r_sample ? 4u : plan.k2i_sample ? 2u : 0u;   // (bit 2: the sample launch on K2r; bit 1: on K2i; bit 0: the main launch)
         HIPCHK(launch_pass(plan.n_blocks_s, ctx->stream));
-        HIPCHK(launch_seed_select(ctx->d_samp.as<uint64_t>(), scnt, GQ_SAMPLE_CAP, plan.kp_frac, ctx->d_tau.as<uint64_t>(),
-                                  (uint32_t) nq, ctx->stream));
+        HIPCHK((wave_select ? launch_seed_select_wave : launch_seed_select)(ctx->d_samp.as<uint64_t>(), scnt, GQ_SAMPLE_CAP, plan.kp_frac,
+                                                                            ctx->d_tau.as<uint64_t>(), (uint32_t) nq, ctx->stream));
         HIPCHK(sample.stop());
         // ---- main pass ----
         hipStream_t main_stream = ctx->stream;
@@ -419,7 +421,8 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
     rr.exact_screen = plan.int8 ? 1u : 0u;
     rr.seeded = 1;
     rr.tau_init = ctx->d_tau.as<uint64_t>();
-    HIPCHK(launch_select_rerank(rr, (uint32_t) nq, ctx->stream));
+    HIPCHK((wave_select ? launch_select_emit_wave : launch_select_rerank)(rr, (uint32_t) nq, ctx->stream));
+    if (plan.n_blocks) ctx->last_kernel += wave_select ? " + select vsr::select_emit_wave_kernel" : " + select vsr::select_rerank_kernel";
     HIPCHK(select.stop());
     HIPCHK(whole.stop());
     ctx->stats.queries += nq;
