@@ -111,7 +111,8 @@ int vsr_corpus_load(vsr_ctx* ctx, const float* rows, int64_t n, int dim,
  * queries (negative counts), vsr_search and vsr_search_device_exact re-run them, on the exact kernel over the half rows.
  * vsr_set_screening(ctx, 0) keeps every search on that kernel; vsr_set_query_hint has no effect.  Non-finite rows are accepted as for fp32 (pgvector rejects them on input): NaN
  * distances sort last.  vsr_ivf_load, vsr_ivf_assign, vsr_hnsw_load and vsr_hnsw_build* over such a corpus:
- * VSR_ERR_UNSUPPORTED. */
+ * VSR_ERR_UNSUPPORTED (the halfvec_*_ops index opclasses are not built yet; of pgvector's other column types only bit has an
+ * index path, vsr_hnsw_*_bit). */
 int vsr_corpus_load_half(vsr_ctx* ctx, const uint16_t* rows, int64_t n, int dim,
                          const int64_t* block_ids, const int32_t* doc_ids, int64_t row_offset,
                          vsr_corpus** out);
@@ -136,8 +137,9 @@ int     vsr_corpus_is_half(const vsr_corpus* corpus);        /* 1 / 0 */
  * Errors.  A dimension mismatch is VSR_ERR_DIM_MISMATCH, "different bit lengths %u and %u" with the column's length first
  * (CheckDims, bitvec.c:32-39).  vsr_search_bit* on a corpus that is not a bit corpus, or with a metric other than 4 / 5:
  * VSR_ERR_INVALID.  vsr_search*, vsr_ivf_load, vsr_ivf_assign, vsr_hnsw_load and vsr_hnsw_build* over a bit corpus:
- * VSR_ERR_UNSUPPORTED, the message names the bit corpus (the bit_hamming_ops / bit_jaccard_ops index opclasses are not built
- * yet).  The float entry points keep rejecting metrics 4 / 5 with VSR_ERR_INVALID. */
+ * VSR_ERR_UNSUPPORTED, the message names the bit corpus.  The HNSW opclasses bit_hamming_ops / bit_jaccard_ops are
+ * vsr_hnsw_load_bit / vsr_hnsw_build_bit / vsr_hnsw_search_bit* below; IVFFlat over bits is not built yet.  The float entry
+ * points keep rejecting metrics 4 / 5 with VSR_ERR_INVALID. */
 int vsr_corpus_load_bit(vsr_ctx* ctx, const uint8_t* rows, int64_t n, int dim,
                         const int64_t* block_ids, const int32_t* doc_ids, int64_t row_offset,
                         vsr_corpus** out);
@@ -534,6 +536,72 @@ int vsr_hnsw_search_iterative_device(vsr_hnsw* index, const float* d_queries, in
                                      const vsr_filter* const* filters, int mode, int64_t max_scan_tuples,
                                      int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
                                      int32_t* d_out_counts, int64_t* d_out_tuples);
+
+/* ---- HNSW over a bit corpus: bit_hamming_ops / bit_jaccard_ops (hnsw_bit_support, hnswutils.c:1398-1410; test/sql/hnsw_bit.sql,
+ * test/t/020_hnsw_bit_build_recall.pl, 023_hnsw_bit_duplicates.pl) --------------------------------------------------------------
+ * An HNSW index belongs to one opclass: the graph is built for one distance, so `metric` (VSR_METRIC_HAMMING or
+ * VSR_METRIC_JACCARD) is fixed when the index is made, by vsr_hnsw_load_bit (the arrays of vsr_hnsw_load) or vsr_hnsw_build_bit.
+ * vsr_hnsw_load / vsr_hnsw_build* keep refusing a bit corpus (VSR_ERR_UNSUPPORTED, the message names the bit corpus and these
+ * entry points); these refuse a corpus that is not a bit corpus and a metric other than 4 / 5 with VSR_ERR_INVALID.
+ *   - Queries: (dim + 7) / 8 packed bytes each, varbit order; device queries need no alignment.  Bits past dim are ignored:
+ *     staging clears them, as vsr_search_bit's does.
+ *   - dim must be the corpus's bit length, else VSR_ERR_DIM_MISMATCH, "different bit lengths %u and %u", the column's first
+ *     (CheckDims, bitvec.c:32-39).
+ *   - metric must be the index's; a mismatch is VSR_ERR_INVALID naming both.  It catches misuse, it selects nothing.
+ *   - The float vsr_hnsw_search* on a bit index: VSR_ERR_UNSUPPORTED, the message names the bit corpus.  vsr_hnsw_search_bit* on
+ *     an index over any other corpus: VSR_ERR_INVALID.
+ *   - Index distance: Hamming is the integer count, exact in fp32; Jaccard is evaluated in double as bitutils.c:96-129 does (no
+ *     common bit: 1) and rounded to fp32, exactly the value vsr_search_bit reports.  Candidate keys are monotone(fp32) << 32 |
+ *     element id as in vsr_hnsw_search: equal distances -- the rule among Hamming distances -- are ordered by element id.
+ *     out_dist is that fp32 value (no square root).
+ *   - Everything else is vsr_hnsw_search's, unchanged: vsr_hnsw_set_predicate_aware, the iterative modes (relaxed, strict,
+ *     max_scan_tuples, the re-run of a query whose discarded set overflowed), the visited-set forms and the re-run of a query
+ *     whose LDS table overflowed (the device entry points report it with count -1), vsr_hnsw_export*, vsr_hnsw_info,
+ *     vsr_hnsw_free, the filters of the bit corpus, row_offset, up to 10 TIDs per element, m 2 .. 100, ef_search 1 .. 5000.
+ *   - The device entry points enqueue the query staging and ONE search launch (iterative: one per chunk of queries) on the
+ *     corpus context's stream and do not synchronise.
+ * vsr_hnsw_build_bit is vsr_hnsw_build_ex over bit rows: the same batched insertion, the same seeded level stream, flags 0 or
+ * VSR_HNSW_BUILD_MERGE_DUPLICATES with exactly the grouping contract written there.  Identical means the packed bytes are
+ * identical; pad bits are zero on load, so this is datumIsEqual on a bit(n).  Quantized corpora are full of duplicates: the
+ * merging build is the one to use.  The guarantee is recall, as for the float build (020_hnsw_bit_build_recall.pl's floors). */
+int vsr_hnsw_load_bit(vsr_corpus* bits, int metric, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
+                      const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
+                      int32_t n_upper, int32_t max_level, vsr_hnsw** out);
+int vsr_hnsw_build_bit(vsr_corpus* bits, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out);
+int vsr_hnsw_search_bit(vsr_hnsw* index, const uint8_t* queries, int nq, int dim, int k, int ef_search, int metric,
+                        const vsr_filter* const* filters,
+                        int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows, float* out_dist, int32_t* out_counts,
+                        int64_t* out_visited);
+int vsr_hnsw_search_bit_device(vsr_hnsw* index, const uint8_t* d_queries, int nq, int dim, int k, int ef_search, int metric,
+                               const vsr_filter* const* filters,
+                               int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
+                               int32_t* d_out_counts, int64_t* d_out_visited);
+int vsr_hnsw_search_bit_iterative(vsr_hnsw* index, const uint8_t* queries, int nq, int dim, int k, int ef_search, int metric,
+                                  const vsr_filter* const* filters, int mode, int64_t max_scan_tuples,
+                                  int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows, float* out_dist,
+                                  int32_t* out_counts, int64_t* out_tuples);
+int vsr_hnsw_search_bit_iterative_device(vsr_hnsw* index, const uint8_t* d_queries, int nq, int dim, int k, int ef_search, int metric,
+                                         const vsr_filter* const* filters, int mode, int64_t max_scan_tuples,
+                                         int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
+                                         int32_t* d_out_counts, int64_t* d_out_tuples);
+/* The indexed two-stage search -- pgvector's documented use of binary_quantize: CREATE INDEX ... USING hnsw
+ * ((binary_quantize(embedding)::bit(n)) bit_hamming_ops), ORDER BY ... <~> ... LIMIT shortlist, then the re-rank on the original
+ * vectors.  It is vsr_search_quantized with stage 1 replaced by the index: qb = binary_quantize(q); S = the answer of
+ * vsr_hnsw_search_bit(bit_index, qb, k = shortlist, ef_search, VSR_METRIC_HAMMING, filters), which may hold fewer than
+ * `shortlist` rows, as any HNSW scan may; stage 2 is vsr_search_quantized's exact re-rank on `source`, unchanged.  bit_index must
+ * be a Hamming index over the corpus vsr_corpus_binary_quantize(source) made, else VSR_ERR_INVALID in vsr_search_quantized's
+ * words.  Plain walk or predicate-aware as the index is set; no iterative mode.  k <= shortlist <= VSR_MAX_K; L2, inner product
+ * and cosine; L1 is VSR_ERR_UNSUPPORTED.  Both stages run on the bit corpus context's stream with no host round trip; the
+ * _device form does not synchronise, d_out_keys (may be NULL) receives the raw keys as vsr_search_quantized_device's does, and a
+ * query whose LDS visited table overflowed (graphs beyond ~1M elements) has an empty shortlist there: count 0.  The host form
+ * runs the call again with the global visited bitmap when that happens. */
+int vsr_hnsw_search_quantized(vsr_corpus* source, vsr_hnsw* bit_index, const float* queries, int nq, int dim, int k, int shortlist,
+                              int ef_search, int metric, const vsr_filter* const* filters,
+                              int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows, float* out_dist, int32_t* out_counts);
+int vsr_hnsw_search_quantized_device(vsr_corpus* source, vsr_hnsw* bit_index, const float* d_queries, int nq, int dim, int k,
+                                     int shortlist, int ef_search, int metric, const vsr_filter* const* filters,
+                                     int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
+                                     int32_t* d_out_counts, uint64_t* d_out_keys);
 
 /* opclass support functions for n vectors at once (host pointers): vector_norm (vector.c:756-769), l2_normalize
  * (vector.c:774-808; fails with "value out of range: overflow" like float_overflow_error) and

@@ -53,15 +53,17 @@
 #pragma once
 #include "vsr_device.h"
 #include "vsr_topk.h"
+#include "vsr_bitops.h"
 
 namespace vsr {
 
 enum HnswVisited : int { VIS_LDS_BITMAP = 0, VIS_LDS_HASH = 1, VIS_GLOBAL = 2 };
+// (HnswRows, the row format the search body is instantiated for: vsr_bitops.h; ROWS_BIT is K4b, see above hnsw_search_body)
 
 struct HnswParams {
     const float4*   rows = nullptr;          // base corpus rows (internal order)
     uint32_t        stride4 = 0;
-    int             metric = 0;              // M_L2 / M_IP / M_COSINE (unit rows: ranked by negative inner product)
+    int             metric = 0;              // M_L2 / M_IP / M_COSINE (unit rows: ranked by negative inner product); ROWS_BIT: M_HAMMING / M_JACCARD
     const float*    queries = nullptr;       // [nq][q_stride] floats (q_stride >= dim; elements past dim are not read)
     uint32_t        q_stride = 0, dim = 0, nq = 0;
     uint32_t        n_elem = 0;
@@ -87,6 +89,13 @@ struct HnswParams {
     int64_t*        out_visited = nullptr;   // optional [nq]: elements entered into the visited set on layer 0
     int32_t*        out_status = nullptr;    // optional [nq]: 0 = ok, 1 = the LDS hash overflowed (result not valid: re-run with VIS_GLOBAL)
     uint32_t*       err = nullptr;
+    // ROWS_BIT only.  rows: stride4 16-byte chunks of packed bits per row (pad bits zero); queries: the STAGED queries, q_stride / 4
+    // = stride4 chunks each, pad bits cleared (stage_bit_kernel)
+    const float*    row_pop = nullptr;       // popcount of every row (the corpus's d_norm2), Jaccard
+    const float*    q_pop = nullptr;         // [nq] popcount of every staged query
+    uint64_t*       out_keys = nullptr;      // optional [nq][k]: make_key(distance, internal row + key_row_offset) of every result,
+                                             // KEY_EMPTY past the count: the stage-1 keys of the two-stage search (ShortlistParams::s1_keys)
+    uint32_t        key_row_offset = 0;
     // hnsw_iterative_kernel only (out_visited then reports T when the scan stopped; status 1 = D overflowed)
     int             iter_mode = 0;           // VSR_HNSW_ITERATIVE_RELAXED = 1 / STRICT = 2
     int64_t         max_scan = 0;            // hnsw.max_scan_tuples
@@ -114,7 +123,14 @@ __device__ __forceinline__ void wave_sync_global()
     __builtin_amdgcn_wave_barrier();
 }
 
-template <bool ITER>
+// K4b, ROWS = ROWS_BIT: the graph of a bit corpus (bit_hamming_ops / bit_jaccard_ops, hnswutils.c:1398-1410).  K4 gives half a
+// wave to each gathered row; a 128-bit row is ONE 16-byte chunk, which would leave 31 of 32 lanes idle.  The bit distance stage
+// (bit_graph_distances, vsr_bitops.h) gives a row G lanes, G the smallest power of two >= its chunks (at most 64): 64 neighbours
+// per wave step at 128 bits, 8 at 1024 bits, and beyond 8192 bits the 64 lanes loop over the chunks.  The lane keeps its chunk
+// of the staged query in a register across expansions (re-read from the staged copy when a row has more than 64 chunks);
+// partials are integer popcounts, reduced by shuffles inside the lane group, converted once with K1b's own expression
+// (rank_value_bits: Hamming the count, Jaccard in double then rounded).  The reported distance is that fp32 value (no sqrt).
+template <bool ITER, int ROWS = ROWS_F32>
 __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
 {
     extern __shared__ __align__(16) unsigned char smem_all[];
@@ -165,8 +181,28 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
         return false;                                                        // table full: reported through `overflow` below
     };
 
+    // ROWS_BIT: lanes per row, this lane's chunk of the staged query, the query's popcount
+    uint32_t bit_g = 1;
+    uint4 qreg = make_uint4(0u, 0u, 0u, 0u);
+    float q_pop = 0.0f;
+    if constexpr (ROWS == ROWS_BIT) {
+        bit_g = bit_graph_lanes(p.stride4);
+        const uint32_t gl = (uint32_t) lane & (bit_g - 1u);
+        if (p.stride4 <= 64u && gl < p.stride4) qreg = reinterpret_cast<const uint4*>(q)[gl];
+        q_pop = p.q_pop[qi];
+    }
     // distance of the query to `cnt` elements listed in nb[] -> nd[] (fp32 sum; exact on integer-valued data in any order)
     auto distances = [&](int cnt) {
+        if constexpr (ROWS == ROWS_BIT) {
+            const uint4* brows = reinterpret_cast<const uint4*>(p.rows);
+            const uint4* qs = reinterpret_cast<const uint4*>(q);
+            if (p.metric == M_JACCARD)
+                bit_graph_distances<true>(brows, p.stride4, bit_g, p.elem_row, p.row_pop, qs, qreg, q_pop, nb, cnt, nd, lane);
+            else
+                bit_graph_distances<false>(brows, p.stride4, bit_g, p.elem_row, p.row_pop, qs, qreg, q_pop, nb, cnt, nd, lane);
+            wave_sync();
+            return;
+        } else {
         constexpr int U = 4;
         for (int c0 = 0; c0 < cnt; c0 += 2 * U) {
             float s[U];
@@ -205,6 +241,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
             }
         }
         wave_sync();
+        }
     };
 
     const uint64_t* bm = p.bitmaps ? p.bitmaps[qi] : nullptr;
@@ -452,6 +489,8 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
             p.out_block[o] = -1; p.out_doc[o] = -1;
             if (p.out_row) p.out_row[o] = -1;
             p.out_dist[o] = __builtin_inff();
+            if constexpr (ROWS == ROWS_BIT)
+                if (p.out_keys) p.out_keys[o] = KEY_EMPTY;
         }
     };
     if (p.out_status && lane == 0) p.out_status[qi] = 0;
@@ -532,6 +571,10 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
                     p.out_doc[o] = p.doc_ids[row];
                     if (p.out_row) p.out_row[o] = p.orig_rows[row];
                     float v;
+                    if constexpr (ROWS == ROWS_BIT) {                        // <~> / <%>: the index distance is the operator's value
+                        v = d;
+                        if (p.out_keys) p.out_keys[o] = make_key(d, row + p.key_row_offset);
+                    } else
                     if (p.metric == M_L2) v = (float) sqrt((double) d);       // l2_distance, vector.c:577
                     else if (p.metric == M_IP) v = d;                        // <#> = negative inner product
                     else {                                                   // unit rows: cosine distance = 1 - dot
@@ -658,9 +701,11 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
 }
 
 __global__ __launch_bounds__(256) void hnsw_search_kernel(const HnswParams p) { hnsw_search_body<false>(p); }
+__global__ __launch_bounds__(256) void hnsw_bit_search_kernel(const HnswParams p) { hnsw_search_body<false, ROWS_BIT>(p); }
 
 // pgvector's iterative index scan (see the header comment): every round of a query inside the one launch
 __global__ __launch_bounds__(256) void hnsw_iterative_kernel(const HnswParams p) { hnsw_search_body<true>(p); }
+__global__ __launch_bounds__(256) void hnsw_bit_iterative_kernel(const HnswParams p) { hnsw_search_body<true, ROWS_BIT>(p); }
 
 constexpr size_t HN_LDS_BUDGET = 156 * 1024;   // of the CU's 160 KB (dynamic LDS of one workgroup)
 
@@ -726,13 +771,14 @@ inline bool hnsw_plan_iterative(HnswParams& p, bool force_global)
     return true;
 }
 
-template <bool ITER>
+template <bool ITER, int ROWS = ROWS_F32>
 inline hipError_t launch_hnsw(const HnswParams& p, hipStream_t s)
 {
     if (p.nq == 0) return hipSuccess;
     const size_t lds = (size_t) p.lds_per_query * p.qpb;
     if (lds > HN_LDS_BUDGET || p.qpb < 1 || p.qpb > 4) return hipErrorInvalidValue;
-    const auto kernel = ITER ? hnsw_iterative_kernel : hnsw_search_kernel;
+    const auto kernel = ROWS == ROWS_BIT ? (ITER ? hnsw_bit_iterative_kernel : hnsw_bit_search_kernel)
+                                         : (ITER ? hnsw_iterative_kernel : hnsw_search_kernel);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         if (e != hipSuccess) return e;
@@ -743,5 +789,7 @@ inline hipError_t launch_hnsw(const HnswParams& p, hipStream_t s)
 
 inline hipError_t launch_hnsw_search(const HnswParams& p, hipStream_t s) { return launch_hnsw<false>(p, s); }
 inline hipError_t launch_hnsw_iterative(const HnswParams& p, hipStream_t s) { return launch_hnsw<true>(p, s); }
+inline hipError_t launch_hnsw_bit_search(const HnswParams& p, hipStream_t s) { return launch_hnsw<false, ROWS_BIT>(p, s); }
+inline hipError_t launch_hnsw_bit_iterative(const HnswParams& p, hipStream_t s) { return launch_hnsw<true, ROWS_BIT>(p, s); }
 
 }  // namespace vsr

@@ -22,6 +22,12 @@
 // vsr_hnsw_dedup.hip's pre-pass first and the kernels below then insert ELEMENTS, reaching an element's vector through
 // HnswBuildParams::elem_row (template parameter IND; without it element e is row e and the gather is the plain one).
 //
+// Bit corpora (vsr_hnsw_build_bit, bit_hamming_ops / bit_jaccard_ops): template parameter ROWS = ROWS_BIT gives hb_distances --
+// the one place that reads row values -- K4b's lane mapping and integer arithmetic (bit_graph_distances, vsr_bitops.h);
+// SelectNeighbors, the reverse-edge pass, the batching and the level stream do not know the row format.  The pre-pass of the
+// merging build compares rows as 16-byte chunks and serves packed bits as it stands.  Parity: pgvector's
+// test/t/020_hnsw_bit_build_recall.pl floors (tests/test_gpu_hnsw_bit.py).
+//
 // Parity definition (tests/test_gpu_index.py): recall@20 at ef_search = 40 against the exact scan >= pgvector's TAP
 // thresholds on its own case (10 000 x 3-d: 0.99; inner product 0.97), and within 0.01 of that serial build's recall on
 // the same rows.
@@ -35,6 +41,7 @@
 
 #include "vsr_device.h"
 #include "vsr_topk.h"
+#include "vsr_bitops.h"
 #include "vsr_hnsw_build.h"
 
 namespace vsr {
@@ -66,9 +73,24 @@ __device__ __forceinline__ const float4* hb_row(const HnswBuildParams& p, I e)
     return p.rows + (size_t) (IND ? (I) p.elem_row[e] : e) * p.stride4;
 }
 
-template <bool IND>
+// ROWS_BIT (a bit corpus, metric M_HAMMING / M_JACCARD): the lane mapping and arithmetic of K4b (bit_graph_distances, vsr_bitops.h)
+template <bool IND, int ROWS>
 __device__ __forceinline__ void hb_distances(const HnswBuildParams& p, const float4* a, const int32_t* ids, int cnt, float* out, int lane)
 {
+    if constexpr (ROWS == ROWS_BIT) {
+        const uint32_t G = bit_graph_lanes(p.stride4), gl = (uint32_t) lane & (G - 1u);
+        const uint4* rows = reinterpret_cast<const uint4*>(p.rows);
+        const uint4* qs = reinterpret_cast<const uint4*>(a);
+        uint4 qreg = make_uint4(0u, 0u, 0u, 0u);
+        if (p.stride4 <= 64u && gl < p.stride4) qreg = qs[gl];
+        const int32_t* er = IND ? p.elem_row : nullptr;
+        if (p.metric == M_JACCARD)
+            bit_graph_distances<true>(rows, p.stride4, G, er, p.row_pop, qs, qreg, p.row_pop[(size_t) (a - p.rows) / p.stride4], ids, cnt, out, lane);
+        else
+            bit_graph_distances<false>(rows, p.stride4, G, er, p.row_pop, qs, qreg, 0.0f, ids, cnt, out, lane);
+        wave_sync();
+        return;
+    } else {
     const int half = lane >> 5, hl = lane & 31;
     for (int c0 = 0; c0 < cnt; c0 += 8) {
         float s[4];
@@ -100,6 +122,7 @@ __device__ __forceinline__ void hb_distances(const HnswBuildParams& p, const flo
         }
     }
     wave_sync();
+    }
 }
 
 // SelectNeighbors (hnswutils.c:1053-1154): cand[0 .. n) = (distance to the owner, element) nearest first; keeps up to lm of them
@@ -107,7 +130,7 @@ __device__ __forceinline__ void hb_distances(const HnswBuildParams& p, const flo
 // neighbour already taken (CheckElementCloser); when fewer than lm pass, the passed-over ones fill up in order ("keep
 // pruned connections").  *pruned = index of the candidate pgvector would call pruned (only meaningful for n > lm).
 // scratch: ids[lm], nd[lm] in LDS.  Returns the number selected.
-template <bool IND>
+template <bool IND, int ROWS>
 __device__ __forceinline__ int hb_select(const HnswBuildParams& p, const uint64_t* cand, int n, int lm, int32_t* sel, int32_t* wd,
                                          int32_t* ids, float* nd, int* pruned, int lane)
 {
@@ -124,7 +147,7 @@ __device__ __forceinline__ int hb_select(const HnswBuildParams& p, const uint64_
         const float de = mono_to_float((uint32_t) (cand[i] >> 32));
         bool closer = true;
         if (nsel > 0) {
-            hb_distances<IND>(p, hb_row<IND>(p, e), ids, nsel, nd, lane);
+            hb_distances<IND, ROWS>(p, hb_row<IND>(p, e), ids, nsel, nd, lane);
             bool bad = false;
             for (int j = lane; j < nsel; j += 64) bad |= nd[j] <= de;
             closer = __ballot(bad) == 0;
@@ -149,7 +172,7 @@ __device__ __forceinline__ int hb_select(const HnswBuildParams& p, const uint64_
 }
 
 // ---- phase 1: one wave per new element: search the frozen graph, select, write the element's own lists, emit reverse edges ----
-template <bool IND>
+template <bool IND, int ROWS>
 __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildParams p)
 {
     extern __shared__ __align__(16) unsigned char smem_all[];
@@ -258,7 +281,7 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
             used += (uint32_t) cnt;
             if (used * 4u > p.hash_slots * 3u) { overflow = true; break; }
             if (cnt == 0) continue;
-            hb_distances<IND>(p, q, nb, cnt, nd, lane);
+            hb_distances<IND, ROWS>(p, q, nb, cnt, nd, lane);
             for (int i = 0; i < cnt; ++i) {
                 const uint32_t e = (uint32_t) nb[i];
                 const float ed = nd[i];
@@ -277,7 +300,7 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
     // HnswFindElementNeighbors (hnswutils.c:1270-1346)
     if (lane == 0) nb[0] = p.entry;
     wave_sync();
-    hb_distances<IND>(p, q, nb, 1, nd, lane);
+    hb_distances<IND, ROWS>(p, q, nb, 1, nd, lane);
     insert(make_key(nd[0], (uint32_t) p.entry));
     for (int lc = p.entry_level; lc >= my_level + 1; --lc) {
         search_layer(lc, 1);
@@ -289,7 +312,7 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
         search_layer(lc, p.efc);
         const int lm = (int) (lc == 0 ? 2 * p.m : p.m);
         int pruned;
-        const int ns = hb_select<IND>(p, S, (int) count, lm, sel, wd, nb, nd, &pruned, lane);
+        const int ns = hb_select<IND, ROWS>(p, S, (int) count, lm, sel, wd, nb, nd, &pruned, lane);
         // AddConnections + the reverse edges HnswUpdateNeighborsInMemory will apply
         float* dl;
         int32_t* nl = hb_list(p, me, lc, &dl);
@@ -313,7 +336,7 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
 }
 
 // ---- phase 2: reverse edges, sorted by (layer, target): the wave of a run's first record applies the whole run ----
-template <bool IND>
+template <bool IND, int ROWS>
 __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildParams p)
 {
     extern __shared__ __align__(16) unsigned char smem_all[];
@@ -370,7 +393,7 @@ __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildPar
         for (int j = lane; j < n; j += 64) cand[sel[j]] = mine[nm++];
         wave_sync();
         int pruned;
-        (void) hb_select<IND>(p, cand, n, lm, sel, wd, ids, nd, &pruned, lane);
+        (void) hb_select<IND, ROWS>(p, cand, n, lm, sel, wd, ids, nd, &pruned, lane);
         const uint32_t pe = (uint32_t) cand[pruned];
         if (pe != e) {                                                        // the new element replaces the pruned one
             for (int j = lane; j < lm; j += 64)
@@ -385,7 +408,7 @@ __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildPar
 using namespace vsr;
 
 // host side: see vsr_hnsw_rt.hip (vsr_hnsw_build) for the batch loop; these are the two launches and the sort of a batch
-template <bool IND>
+template <bool IND, int ROWS>
 static hipError_t build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt, uint64_t* d_val_alt, hipStream_t s)
 {
     hipError_t e = hipMemsetAsync(p.rec_count, 0, sizeof(uint32_t), s);
@@ -395,10 +418,10 @@ static hipError_t build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sort_
     if (e != hipSuccess) return e;
     const size_t lds1 = (size_t) p.lds_per_wave * p.wpb;
     if (lds1 > 64 * 1024) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_build_search_kernel<IND>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds1);
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_build_search_kernel<IND, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds1);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(hnsw_build_search_kernel<IND>, dim3((p.count + p.wpb - 1) / p.wpb), dim3(64 * p.wpb), lds1, s, p);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_build_search_kernel<IND, ROWS>), dim3((p.count + p.wpb - 1) / p.wpb), dim3(64 * p.wpb), lds1, s, p);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (p.entry < 0) return hipSuccess;                                       // the first element has nobody to link to
     hipcub::DoubleBuffer<uint64_t> keys(p.rec_key, d_key_alt), vals(p.rec_val, d_val_alt);
@@ -407,15 +430,18 @@ static hipError_t build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sort_
     HnswBuildParams q = p;
     q.rec_key = keys.Current();
     q.rec_val = vals.Current();
-    hipLaunchKernelGGL(hnsw_build_link_kernel<IND>, dim3((p.rec_cap + 3) / 4), dim3(256), (size_t) 4 * HB_NBR * 32, s, q);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_build_link_kernel<IND, ROWS>), dim3((p.rec_cap + 3) / 4), dim3(256), (size_t) 4 * HB_NBR * 32, s, q);
     return hipGetLastError();
 }
 
 hipError_t vsr_hnsw_build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt, uint64_t* d_val_alt,
                                 hipStream_t s)
 {
-    return p.elem_row ? build_batch<true>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s)
-                      : build_batch<false>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
+    if (p.bits)
+        return p.elem_row ? build_batch<true, ROWS_BIT>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s)
+                          : build_batch<false, ROWS_BIT>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
+    return p.elem_row ? build_batch<true, ROWS_F32>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s)
+                      : build_batch<false, ROWS_F32>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
 }
 
 size_t vsr_hnsw_build_sort_bytes(uint32_t rec_cap)

@@ -1,7 +1,9 @@
-// vsr_hnsw_rt.hip — K4: HNSW graph load / build / search entry points.  The only unit that compiles vsr_hnsw.h's kernels.
+// vsr_hnsw_rt.hip — K4 / K4b: HNSW graph load / build / search entry points, over fp32 corpora (vsr_hnsw_*) and bit corpora
+// (vsr_hnsw_*_bit, vsr_hnsw_search_quantized*).  The only unit that compiles vsr_hnsw.h's kernels.
 #include "vsr_runtime.h"
 #include "vsr_hnsw.h"
 #include "vsr_hnsw_build.h"
+#include "vsr_shortlist.h"
 
 #include <climits>
 #include <cmath>
@@ -16,6 +18,9 @@ struct vsr_hnsw {
             *d_tid_count = nullptr, *d_tids = nullptr;
     std::map<uint64_t, uint64_t*> bitmaps;           // filters (by vsr_filter::id) without a full bitmap of their own, as one
     DevBuf d_q, d_vis, d_out, d_bm, d_disc;
+    DevBuf d_qb;                                     // bit index: [staged queries | their popcounts | the staging kernel's flag and seed words]
+    int bit_metric = 0;                              // 0: an index over fp32 rows; VSR_METRIC_HAMMING / VSR_METRIC_JACCARD: the opclass of a
+                                                     // bit index (fixed when the index is made: the graph is built for one distance)
     PinBuf h_out, h_bm;
     int last_mode = -1;                              // visited form of the last launch (HnswVisited)
     int predicate_aware = 0;                         // vsr_hnsw_set_predicate_aware
@@ -48,25 +53,41 @@ static int upload_i32(int32_t** d, const int32_t* src, size_t count)          //
     return VSR_OK;
 }
 
-extern "C" int vsr_hnsw_load(vsr_corpus* c, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
-                             const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
-                             int32_t n_upper, int32_t max_level, vsr_hnsw** out)
+// what a bit entry point asks of its corpus and opclass (who: the entry point)
+static int hnsw_bit_opclass(const vsr_corpus* c, int metric, const char* who)
 {
-    if (!c || !out) return fail(VSR_ERR_INVALID, "vsr_hnsw_load: NULL argument");
+    if (!c->bit) return fail(VSR_ERR_INVALID, "%s: the corpus is not a bit corpus", who);
+    if (metric != VSR_METRIC_HAMMING && metric != VSR_METRIC_JACCARD)
+        return fail(VSR_ERR_INVALID, "%s: metric %d is not an operator class of bit (4: bit_hamming_ops, 5: bit_jaccard_ops)", who, metric);
+    return VSR_OK;
+}
+
+// vsr_hnsw_load (bit_metric = 0) and vsr_hnsw_load_bit (the opclass)
+static int hnsw_load(vsr_corpus* c, int bit_metric, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
+                     const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
+                     int32_t n_upper, int32_t max_level, vsr_hnsw** out, const char* who)
+{
+    if (!c || !out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
     *out = nullptr;
-    if (c->base) return fail(VSR_ERR_INVALID, "vsr_hnsw_load: the corpus is a view");
-    if (c->half) return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_load: a halfvec corpus has no index path yet (the halfvec_*_ops opclasses)");
-    if (c->sparse) return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_load: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)");
-    if (c->bit) return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_load: a bit corpus has no index path yet (the bit_hamming_ops / bit_jaccard_ops opclasses)");
+    if (c->base) return fail(VSR_ERR_INVALID, "%s: the corpus is a view", who);
+    if (bit_metric) {
+        int rc = hnsw_bit_opclass(c, bit_metric, who);
+        if (rc) return rc;
+    }
+    if (c->half) return fail(VSR_ERR_UNSUPPORTED, "%s: a halfvec corpus has no index path yet (the halfvec_*_ops opclasses)", who);
+    if (c->sparse) return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
+    if (c->bit && !bit_metric)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: the graph of a bit corpus is loaded with vsr_hnsw_load_bit (the bit_hamming_ops / bit_jaccard_ops opclasses)", who);
     if (m < 2 || m > 100)        /* reloption m: 2 .. HNSW_MAX_M (hnsw.h:36-40) */
-        return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_load: m must be between 2 and 100 (got %d)", m);
+        return fail(VSR_ERR_UNSUPPORTED, "%s: m must be between 2 and 100 (got %d)", who, m);
     if (n_elem < 0 || (n_elem > 0 && (!level || !nbr0 || !tid_count || !tids || !up_slot)) || max_level < 1 || n_upper < 0 ||
         (n_upper > 0 && !up_nbr) || entry >= n_elem)
-        return fail(VSR_ERR_INVALID, "vsr_hnsw_load: bad graph arrays");
+        return fail(VSR_ERR_INVALID, "%s: bad graph arrays", who);
     vsr_ctx* ctx = c->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     std::unique_ptr<vsr_hnsw> h(new vsr_hnsw());
     h->corpus = c;
+    h->bit_metric = bit_metric;
     h->n_elem = n_elem;
     h->entry = n_elem > 0 ? entry : -1;
     h->m = m;
@@ -78,15 +99,15 @@ extern "C" int vsr_hnsw_load(vsr_corpus* c, int m, int32_t n_elem, int32_t entry
     std::vector<int32_t> itids((size_t) std::max(n_elem, 1) * 10, -1), erow((size_t) std::max(n_elem, 1), 0);
     for (int32_t e = 0; e < n_elem; ++e) {
         if (tid_count[e] < 1 || tid_count[e] > 10 || level[e] < 0 || level[e] > max_level)
-            return fail(VSR_ERR_INVALID, "vsr_hnsw_load: element %d has %d heap TIDs / level %d", e, tid_count[e], level[e]);
+            return fail(VSR_ERR_INVALID, "%s: element %d has %d heap TIDs / level %d", who, e, tid_count[e], level[e]);
         for (int t = 0; t < tid_count[e]; ++t) {
             const int64_t row = tids[(size_t) e * 10 + t];
-            if (row < 0 || row >= c->n) return fail(VSR_ERR_INVALID, "vsr_hnsw_load: element %d points at row %lld", e, (long long) row);
+            if (row < 0 || row >= c->n) return fail(VSR_ERR_INVALID, "%s: element %d points at row %lld", who, e, (long long) row);
             itids[(size_t) e * 10 + t] = inv[(size_t) row];
         }
         erow[(size_t) e] = itids[(size_t) e * 10];
         for (int j = 0; j < 2 * m; ++j)
-            if (nbr0[(size_t) e * 2 * m + j] >= n_elem) return fail(VSR_ERR_INVALID, "vsr_hnsw_load: neighbour out of range");
+            if (nbr0[(size_t) e * 2 * m + j] >= n_elem) return fail(VSR_ERR_INVALID, "%s: neighbour out of range", who);
     }
     h->entry_level = h->entry >= 0 ? level[h->entry] : -1;
     auto& up = upload_i32;
@@ -103,22 +124,47 @@ extern "C" int vsr_hnsw_load(vsr_corpus* c, int m, int32_t n_elem, int32_t entry
     return VSR_OK;
 }
 
+extern "C" int vsr_hnsw_load(vsr_corpus* c, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
+                             const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
+                             int32_t n_upper, int32_t max_level, vsr_hnsw** out)
+{
+    return hnsw_load(c, 0, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, out, "vsr_hnsw_load");
+}
+
+extern "C" int vsr_hnsw_load_bit(vsr_corpus* c, int metric, int m, int32_t n_elem, int32_t entry, const int32_t* level,
+                                 const int32_t* nbr0, const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot,
+                                 const int32_t* up_nbr, int32_t n_upper, int32_t max_level, vsr_hnsw** out)
+{
+    if (!c || !out) return fail(VSR_ERR_INVALID, "vsr_hnsw_load_bit: NULL argument");
+    *out = nullptr;
+    int rc = hnsw_bit_opclass(c, metric, "vsr_hnsw_load_bit");
+    if (rc) return rc;
+    return hnsw_load(c, metric, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, out, "vsr_hnsw_load_bit");
+}
+
 // CREATE INDEX ... USING hnsw on the GPU (vsr_hnsw_build.hip): batched insertion over the corpus's rows, levels from a seeded
 // xorshift64* stream drawn once per row.  flags = 0: element e = internal row e.  VSR_HNSW_BUILD_MERGE_DUPLICATES: the
 // elements come from vsr_hnsw_dedup.hip's table.  Returns a loaded index, as vsr_hnsw_load would from the same graph.
-static int hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out, const char* who)
+// bit_entry (vsr_hnsw_build_bit): the corpus is a bit corpus, metric its opclass; the kernels take the bit row format
+static int hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out, const char* who,
+                      bool bit_entry = false)
 {
     if (!c || !out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
     *out = nullptr;
+    if (bit_entry) {
+        int rc = hnsw_bit_opclass(c, metric, who);
+        if (rc) return rc;
+    }
     if (flags & ~(uint32_t) VSR_HNSW_BUILD_MERGE_DUPLICATES) return fail(VSR_ERR_INVALID, "%s: unknown flag bits 0x%x", who, flags);
     if (c->base) return fail(VSR_ERR_INVALID, "%s: the corpus is a view", who);
     if (c->half) return fail(VSR_ERR_UNSUPPORTED, "%s: a halfvec corpus has no index path yet (the halfvec_*_ops opclasses)", who);
     if (c->sparse) return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
-    if (c->bit) return fail(VSR_ERR_UNSUPPORTED, "%s: a bit corpus has no index path yet (the bit_hamming_ops / bit_jaccard_ops opclasses)", who);
+    if (c->bit && !bit_entry)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: the graph of a bit corpus is built with vsr_hnsw_build_bit (the bit_hamming_ops / bit_jaccard_ops opclasses)", who);
     if (m < 2 || m > 100) return fail(VSR_ERR_UNSUPPORTED, "%s: m must be between 2 and 100 (got %d)", who, m);
     if (ef_construction < 4 || ef_construction > 1000 || ef_construction < 2 * m)      /* hnsw.c:62-63, hnswbuild.c:677-679 */
         return fail(VSR_ERR_UNSUPPORTED, "%s: ef_construction must be between 4 and 1000 and at least 2 * m (got %d)", who, ef_construction);
-    if (metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)
+    if (!bit_entry && metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)
         return fail(VSR_ERR_UNSUPPORTED, "%s: L2, inner product and cosine operator classes only", who);
     vsr_ctx* ctx = c->ctx;
     HIPCHK(hipSetDevice(ctx->device));
@@ -127,6 +173,7 @@ static int hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uin
     const bool merge = (flags & VSR_HNSW_BUILD_MERGE_DUPLICATES) != 0 && n > 0;
     std::unique_ptr<vsr_hnsw> h(new vsr_hnsw());
     h->corpus = c;
+    h->bit_metric = bit_entry ? metric : 0;
     h->m = m;
     // levels: level = floor(-ln(u) * ml), ml = 1 / ln(m) (hnswutils.c:243), capped like HnswGetMaxLevel (hnsw.h:89)
     int cap = (8192 - 24 - 8 - 4 - 4) / 6 / m - 2;
@@ -218,6 +265,11 @@ static int hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uin
     bp.rows = c->d_rows;
     bp.stride4 = c->stride4;
     bp.metric = metric == VSR_METRIC_L2 ? M_L2 : M_IP;
+    if (bit_entry) {
+        bp.bits = 1;
+        bp.metric = metric == VSR_METRIC_JACCARD ? M_JACCARD : M_HAMMING;
+        bp.row_pop = c->d_norm2;
+    }
     bp.m = (uint32_t) m;
     bp.efc = (uint32_t) ef_construction;
     bp.max_level = (uint32_t) max_level;
@@ -300,6 +352,11 @@ extern "C" int vsr_hnsw_build(vsr_corpus* c, int m, int ef_construction, int met
 extern "C" int vsr_hnsw_build_ex(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out)
 {
     return hnsw_build(c, m, ef_construction, metric, seed, flags, out, "vsr_hnsw_build_ex");
+}
+
+extern "C" int vsr_hnsw_build_bit(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out)
+{
+    return hnsw_build(c, m, ef_construction, metric, seed, flags, out, "vsr_hnsw_build_bit", true);
 }
 
 // the arrays vsr_hnsw_load takes, back from any index (loaded or built): shapes first, then the arrays into host memory
@@ -396,9 +453,19 @@ struct HnswIterLaunch {
     uint32_t cap_d;
 };
 
-// One launch over queries resident in device memory (rows of q_stride floats), results into device arrays; bitmaps: one
-// device pointer per query (d_bm, may be nullptr).  d_status / d_vis are optional device arrays (iterative: T).
-static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const float* d_q, uint32_t q_stride, int nq, int k, int ef, int metric,
+// The queries of a launch in device memory: rows of `stride` floats.  A bit index: the STAGED bit strings (hnsw_stage_bits),
+// stride / 4 16-byte chunks each, and their popcounts.
+struct HnswQueries {
+    const float* q;
+    uint32_t     stride;
+    const float* pop;
+    HnswQueries from_query(size_t q0) const { return {q + q0 * stride, stride, pop ? pop + q0 : nullptr}; }
+};
+
+// One launch over queries resident in device memory, results into device arrays (out.keys: a bit index only, the raw keys of
+// the results); bitmaps: one device pointer per query (d_bm, may be nullptr).  d_status / d_vis are optional device arrays
+// (iterative: T).  The kernel is K4b when the index is over a bit corpus.
+static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const HnswQueries& qs, int nq, int k, int ef, int metric,
                        const uint64_t* const* d_bm, bool force_global, const Outputs& out, int64_t* d_vis, int32_t* d_status,
                        const HnswIterLaunch* iter = nullptr)
 {
@@ -407,8 +474,15 @@ static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const float* d_q, uint32_t q_s
     p.rows = c->d_rows;
     p.stride4 = c->stride4;
     p.metric = metric;
-    p.queries = d_q;
-    p.q_stride = q_stride;
+    p.queries = qs.q;
+    p.q_stride = qs.stride;
+    if (h->bit_metric) {
+        p.metric = h->bit_metric == VSR_METRIC_JACCARD ? M_JACCARD : M_HAMMING;
+        p.row_pop = c->d_norm2;
+        p.q_pop = qs.pop;
+        p.out_keys = out.keys;
+        p.key_row_offset = (uint32_t) c->row_offset;
+    }
     p.dim = (uint32_t) c->dim;
     p.nq = (uint32_t) nq;
     p.n_elem = (uint32_t) h->n_elem;
@@ -475,21 +549,60 @@ static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const float* d_q, uint32_t q_s
     p.out_visited = d_vis;
     p.out_status = d_status;
     p.err = ctx->err_word();
-    if (iter) HIPCHK(launch_hnsw_iterative(p, ctx->stream));
+    if (h->bit_metric) HIPCHK(iter ? launch_hnsw_bit_iterative(p, ctx->stream) : launch_hnsw_bit_search(p, ctx->stream));
+    else if (iter) HIPCHK(launch_hnsw_iterative(p, ctx->stream));
     else HIPCHK(launch_hnsw_search(p, ctx->stream));
     h->last_mode = p.vis_mode;
     return VSR_OK;
 }
 
+static const char* bit_metric_name(int metric) { return metric == VSR_METRIC_JACCARD ? "Jaccard (5, bit_jaccard_ops)" : "Hamming (4, bit_hamming_ops)"; }
+
+// bit_entry: the caller is a vsr_hnsw_search_bit* entry point (a bit index, `dim` bits, the index's own metric)
 static int hnsw_check(vsr_hnsw* h, const void* queries, int nq, int dim, int k, int ef, int metric, const vsr_filter* const* filters,
-                      const char* who)
+                      const char* who, bool bit_entry = false)
 {
     if (!h) return fail(VSR_ERR_INVALID, "%s: index is NULL", who);
-    int rc = check_search_args(h->corpus, queries, nq, dim, k, metric, filters, who);
+    if (bit_entry && !h->bit_metric)
+        return fail(VSR_ERR_INVALID, "%s: the index is not over a bit corpus (it is searched with vsr_hnsw_search*)", who);
+    if (!bit_entry && h->bit_metric)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: the index is over a bit corpus: it is searched with vsr_hnsw_search_bit* (<~> / <%%>)", who);
+    int rc = check_search_args(h->corpus, queries, nq, dim, k, metric, filters, who, bit_entry);
     if (rc) return rc;
+    if (bit_entry && metric != h->bit_metric)               // an index belongs to one opclass: the metric only catches misuse
+        return fail(VSR_ERR_INVALID, "%s: the index was made for %s, the search asks for %s", who, bit_metric_name(h->bit_metric),
+                    bit_metric_name(metric));
     if (metric == VSR_METRIC_L1) return fail(VSR_ERR_UNSUPPORTED, "%s: L1 graphs are not supported", who);
     if (ef < 1 || ef > 5000)      /* hnsw.ef_search: 1 .. HNSW_MAX_EF_SEARCH (hnsw.c:86-89, hnsw.h:44) */
         return fail(VSR_ERR_INVALID, "%s: ef_search must be between 1 and 5000 (got %d)", who, ef);
+    return VSR_OK;
+}
+
+// Query staging of a bit index: nq packed strings of (dim + 7) / 8 bytes at d_src (any alignment) -> 16-byte chunks with the
+// pad bits cleared, and their popcounts, in h->d_qb (stage_bit_kernel, vsr_bit.hip: the staging of vsr_search_bit).  One launch
+// on the context's stream.
+static int hnsw_stage_bits(vsr_hnsw* h, vsr_ctx* ctx, const uint8_t* d_src, int nq, HnswQueries& qs)
+{
+    const vsr_corpus* c = h->corpus;
+    const size_t slot = (size_t) c->stride4 * 16;
+    const size_t o_pop = align_up((size_t) nq * slot, 256), o_flags = align_up(o_pop + (size_t) nq * 4, 256),
+                 o_tau = align_up(o_flags + (size_t) nq * 4, 256), total = o_tau + (size_t) nq * 8;
+    int rc = h->d_qb.reserve(total);
+    if (rc) return rc;
+    char* w = h->d_qb.as<char>();
+    StageParams st{};
+    st.q_src = reinterpret_cast<const float*>(d_src);
+    st.q_stride = (uint32_t) ((c->dim + 7) / 8);            // bytes
+    st.q_dst = reinterpret_cast<float*>(w);
+    st.dim = (uint32_t) c->dim;
+    st.qfloats = c->stride4 * 4u;
+    st.nq = (uint32_t) nq;
+    st.q_bits = 1u;
+    st.q_norm2 = reinterpret_cast<float*>(w + o_pop);
+    st.flags = reinterpret_cast<int32_t*>(w + o_flags);     // (the staging kernel clears a flag and a seed word per query: unused here)
+    st.tau = reinterpret_cast<uint64_t*>(w + o_tau);
+    HIPCHK(launch_stage_bit(st, ctx->stream));
+    qs = {reinterpret_cast<const float*>(w), c->stride4 * 4u, reinterpret_cast<const float*>(w + o_pop)};
     return VSR_OK;
 }
 
@@ -522,42 +635,76 @@ static int hnsw_doc_scratch(vsr_hnsw* h, int nq, int k, int32_t*& d_doc)
     return VSR_OK;
 }
 
-extern "C" int vsr_hnsw_search_device(vsr_hnsw* h, const float* d_queries, int nq, int dim, int k, int ef, int metric,
-                                      const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc, int64_t* d_row,
-                                      float* d_dist, int32_t* d_cnt, int64_t* d_visited)
+// The queries of a search entry point, fp32 or bit.  Float: rows of `dim` floats.  Bit: packed strings of (dim + 7) / 8 bytes,
+// staged (hnsw_stage_bits) in front of every launch.
+struct HnswEntry {
+    const char* who;
+    bool        bit;
+    size_t bytes(int dim) const { return bit ? (size_t) (dim + 7) / 8 : (size_t) dim * sizeof(float); }
+    // queries resident at d_q -> what hnsw_launch takes (bit: one staging launch on the stream)
+    int resident(vsr_hnsw* h, vsr_ctx* ctx, const void* d_q, int nq, int dim, HnswQueries& qs) const
+    {
+        qs = {static_cast<const float*>(d_q), (uint32_t) dim, nullptr};
+        return bit ? hnsw_stage_bits(h, ctx, static_cast<const uint8_t*>(d_q), nq, qs) : VSR_OK;
+    }
+};
+
+// vsr_hnsw_search_device / vsr_hnsw_search_bit_device: (bit: query staging plus) ONE search launch, no synchronisation
+static int hnsw_search_device(const HnswEntry& en, vsr_hnsw* h, const void* d_queries, int nq, int dim, int k, int ef, int metric,
+                              const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc, int64_t* d_row, float* d_dist,
+                              int32_t* d_cnt, int64_t* d_visited)
 {
-    int rc = hnsw_check(h, d_queries, nq, dim, k, ef, metric, filters, "vsr_hnsw_search_device");
+    int rc = hnsw_check(h, d_queries, nq, dim, k, ef, metric, filters, en.who, en.bit);
     if (rc) return rc;
     if (nq == 0) return VSR_OK;
-    if (!d_blk || !d_dist || !d_cnt) return fail(VSR_ERR_INVALID, "vsr_hnsw_search_device: output is NULL");
+    if (!d_blk || !d_dist || !d_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", en.who);
     vsr_ctx* ctx = h->corpus->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     if ((rc = hnsw_doc_scratch(h, nq, k, d_doc))) return rc;
     bool any_filter = false;
     if (h->h_bm.p) HIPCHK(hipStreamSynchronize(ctx->stream));            // the pinned pointer block of the previous call
     if ((rc = hnsw_bitmaps(h, ctx, filters, nq, any_filter))) return rc;
-    return hnsw_launch(h, ctx, d_queries, (uint32_t) dim, nq, k, ef, metric, any_filter ? h->d_bm.as<const uint64_t*>() : nullptr, false,
+    HnswQueries qs;
+    if ((rc = en.resident(h, ctx, d_queries, nq, dim, qs))) return rc;
+    return hnsw_launch(h, ctx, qs, nq, k, ef, metric, any_filter ? h->d_bm.as<const uint64_t*>() : nullptr, false,
                        {d_blk, d_doc, d_row, d_dist, d_cnt, nullptr}, d_visited, nullptr);
 }
 
+extern "C" int vsr_hnsw_search_device(vsr_hnsw* h, const float* d_queries, int nq, int dim, int k, int ef, int metric,
+                                      const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc, int64_t* d_row,
+                                      float* d_dist, int32_t* d_cnt, int64_t* d_visited)
+{
+    return hnsw_search_device({"vsr_hnsw_search_device", false}, h, d_queries, nq, dim, k, ef, metric, filters, d_blk, d_doc, d_row, d_dist,
+                              d_cnt, d_visited);
+}
+
+extern "C" int vsr_hnsw_search_bit_device(vsr_hnsw* h, const uint8_t* d_queries, int nq, int dim, int k, int ef, int metric,
+                                          const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc, int64_t* d_row,
+                                          float* d_dist, int32_t* d_cnt, int64_t* d_visited)
+{
+    return hnsw_search_device({"vsr_hnsw_search_bit_device", true}, h, d_queries, nq, dim, k, ef, metric, filters, d_blk, d_doc, d_row,
+                              d_dist, d_cnt, d_visited);
+}
+
 // The host form of a K4 search.  `launch(d_q, n, filters, tier, results, d_extra, d_status)` runs n device-resident queries
-// at re-run tier 0 or 1; the whole call is one launch and one copy back, then ONE re-run, a tier up, of the queries whose
-// status word says their first result is not valid (rare; big graphs or long scans only), patched into the caller's arrays.
+// (qbytes bytes each, as the caller holds them) at re-run tier 0 or 1; the whole call is one launch and one copy back, then
+// ONE re-run, a tier up, of the queries whose status word says their first result is not valid (rare; big graphs or long
+// scans only), patched into the caller's arrays.
 template <class Launch>
-static int hnsw_host_search(vsr_hnsw* h, const float* queries, int nq, int dim, int k, const vsr_filter* const* filters,
+static int hnsw_host_search(vsr_hnsw* h, const void* queries, size_t qbytes, int nq, int k, const vsr_filter* const* filters,
                             const Outputs& out, int64_t* out_extra, Launch launch)
 {
     vsr_ctx* ctx = h->corpus->ctx;
     const ResultBlock rb(nq, k, true);
     int rc;
-    if ((rc = h->d_q.reserve((size_t) nq * dim * sizeof(float)))) return rc;
+    if ((rc = h->d_q.reserve((size_t) nq * qbytes))) return rc;
     if ((rc = h->d_out.reserve(rb.total))) return rc;
     if ((rc = h->h_out.reserve(rb.total))) return rc;
     char* d = h->d_out.as<char>();
     char* hh = h->h_out.as<char>();
-    auto run = [&](const float* qs, int n, const vsr_filter* const* fs, int tier) -> int {
-        HIPCHK(hipMemcpyAsync(h->d_q.p, qs, (size_t) n * dim * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        int r = launch(h->d_q.as<float>(), n, fs, tier, rb.arrays(d), rb.column<int64_t>(d, rb.o_extra), rb.column<int32_t>(d, rb.o_status));
+    auto run = [&](const void* qs, int n, const vsr_filter* const* fs, int tier) -> int {
+        HIPCHK(hipMemcpyAsync(h->d_q.p, qs, (size_t) n * qbytes, hipMemcpyHostToDevice, ctx->stream));
+        int r = launch(h->d_q.p, n, fs, tier, rb.arrays(d), rb.column<int64_t>(d, rb.o_extra), rb.column<int32_t>(d, rb.o_status));
         if (r) return r;
         HIPCHK(hipMemcpyAsync(hh, d, rb.total, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -567,43 +714,66 @@ static int hnsw_host_search(vsr_hnsw* h, const float* queries, int nq, int dim, 
     rb.copy_out_all(hh, out, out_extra);
     const std::vector<int> redo = rb.flagged(hh, (size_t) nq);
     if (redo.empty()) return VSR_OK;
-    std::vector<float> q2;
-    std::vector<const vsr_filter*> f2;
-    gather_subset(queries, dim, filters, redo, q2, f2);
+    std::vector<char> q2(redo.size() * qbytes);
+    std::vector<const vsr_filter*> f2(redo.size(), nullptr);
+    for (size_t j = 0; j < redo.size(); ++j) {
+        memcpy(&q2[j * qbytes], static_cast<const char*>(queries) + (size_t) redo[j] * qbytes, qbytes);
+        if (filters) f2[j] = filters[redo[j]];
+    }
     if ((rc = run(q2.data(), (int) redo.size(), f2.data(), 1))) return rc;
     for (size_t j = 0; j < redo.size(); ++j) rb.patch_one(hh, j, (size_t) redo[j], out, out_extra);
     return VSR_OK;
+}
+
+// vsr_hnsw_search / vsr_hnsw_search_bit
+static int hnsw_search_host(const HnswEntry& en, vsr_hnsw* h, const void* queries, int nq, int dim, int k, int ef, int metric,
+                            const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc, int64_t* out_row, float* out_dist,
+                            int32_t* out_cnt, int64_t* out_visited)
+{
+    int rc = hnsw_check(h, queries, nq, dim, k, ef, metric, filters, en.who, en.bit);
+    if (rc) return rc;
+    if (nq == 0) return VSR_OK;
+    if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", en.who);
+    vsr_ctx* ctx = h->corpus->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    // tier 1: queries whose LDS visited table overflowed (big graphs only) are re-run with the global bitmap
+    return hnsw_host_search(h, queries, en.bytes(dim), nq, k, filters, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr}, out_visited,
+                            [&](const void* d_q, int n, const vsr_filter* const* fs, int tier, const Outputs& res, int64_t* d_vis,
+                                int32_t* d_status) -> int {
+                                bool any_filter = false;
+                                int r = hnsw_bitmaps(h, ctx, fs, n, any_filter);
+                                if (r) return r;
+                                HnswQueries qs;
+                                if ((r = en.resident(h, ctx, d_q, n, dim, qs))) return r;
+                                return hnsw_launch(h, ctx, qs, n, k, ef, metric, any_filter ? h->d_bm.as<const uint64_t*>() : nullptr,
+                                                   tier == 1, res, d_vis, d_status);
+                            });
 }
 
 extern "C" int vsr_hnsw_search(vsr_hnsw* h, const float* queries, int nq, int dim, int k, int ef, int metric,
                                const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc, int64_t* out_row,
                                float* out_dist, int32_t* out_cnt, int64_t* out_visited)
 {
-    int rc = hnsw_check(h, queries, nq, dim, k, ef, metric, filters, "vsr_hnsw_search");
-    if (rc) return rc;
-    if (nq == 0) return VSR_OK;
-    if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "vsr_hnsw_search: output is NULL");
-    vsr_ctx* ctx = h->corpus->ctx;
-    HIPCHK(hipSetDevice(ctx->device));
-    // tier 1: queries whose LDS visited table overflowed (big graphs only) are re-run with the global bitmap
-    return hnsw_host_search(h, queries, nq, dim, k, filters, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr}, out_visited,
-                            [&](const float* d_q, int n, const vsr_filter* const* fs, int tier, const Outputs& res, int64_t* d_vis,
-                                int32_t* d_status) -> int {
-                                bool any_filter = false;
-                                int r = hnsw_bitmaps(h, ctx, fs, n, any_filter);
-                                if (r) return r;
-                                return hnsw_launch(h, ctx, d_q, (uint32_t) dim, n, k, ef, metric,
-                                                   any_filter ? h->d_bm.as<const uint64_t*>() : nullptr, tier == 1, res, d_vis, d_status);
-                            });
+    return hnsw_search_host({"vsr_hnsw_search", false}, h, queries, nq, dim, k, ef, metric, filters, out_blk, out_doc, out_row, out_dist,
+                            out_cnt, out_visited);
+}
+
+extern "C" int vsr_hnsw_search_bit(vsr_hnsw* h, const uint8_t* queries, int nq, int dim, int k, int ef, int metric,
+                                   const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc, int64_t* out_row,
+                                   float* out_dist, int32_t* out_cnt, int64_t* out_visited)
+{
+    return hnsw_search_host({"vsr_hnsw_search_bit", true}, h, queries, nq, dim, k, ef, metric, filters, out_blk, out_doc, out_row, out_dist,
+                            out_cnt, out_visited);
 }
 
 // ---- iterative index scans (hnsw.iterative_scan, hnsw.max_scan_tuples; vsr_hnsw.h's header comment) ----------------
 constexpr size_t HN_ITER_WORKSPACE = (size_t) 1 << 30;      // per launch: D + global visited bitmaps of its queries
 
 static int hnsw_iter_check(vsr_hnsw* h, const void* queries, int nq, int dim, int k, int ef, int metric,
-                           const vsr_filter* const* filters, int mode, int64_t max_scan_tuples, const char* who)
+                           const vsr_filter* const* filters, int mode, int64_t max_scan_tuples, const HnswEntry& en)
 {
-    int rc = hnsw_check(h, queries, nq, dim, k, ef, metric, filters, who);
+    const char* who = en.who;
+    int rc = hnsw_check(h, queries, nq, dim, k, ef, metric, filters, who, en.bit);
     if (rc) return rc;
     if (mode < VSR_HNSW_ITERATIVE_OFF || mode > VSR_HNSW_ITERATIVE_STRICT) return fail(VSR_ERR_INVALID, "%s: iterative scan mode %d", who, mode);
     if (max_scan_tuples < 1 || max_scan_tuples > INT_MAX)   /* hnsw.max_scan_tuples: 1 .. INT_MAX (hnsw.c:95-97) */
@@ -628,7 +798,7 @@ static uint32_t hnsw_discard_cap(const vsr_hnsw* h, int ef, int64_t max_scan_tup
 
 // the iterative kernel over queries resident on the device, one launch per chunk of queries whose workspace stays under
 // HN_ITER_WORKSPACE, on the context's stream without synchronisation
-static int hnsw_iter_run(vsr_hnsw* h, const float* d_q, int nq, int dim, int k, int ef, int metric, const vsr_filter* const* filters,
+static int hnsw_iter_run(vsr_hnsw* h, const HnswQueries& qs, int nq, int k, int ef, int metric, const vsr_filter* const* filters,
                          int mode, int64_t max_scan_tuples, uint32_t cap_d, const Outputs& out, int64_t* d_tuples, int32_t* d_status)
 {
     vsr_ctx* ctx = h->corpus->ctx;
@@ -641,7 +811,7 @@ static int hnsw_iter_run(vsr_hnsw* h, const float* d_q, int nq, int dim, int k, 
     const HnswIterLaunch it{mode, max_scan_tuples, cap_d};
     for (int q0 = 0; q0 < nq; q0 += chunk) {
         const int n = std::min(chunk, nq - q0);
-        if ((rc = hnsw_launch(h, ctx, d_q + (size_t) q0 * dim, (uint32_t) dim, n, k, ef, metric,
+        if ((rc = hnsw_launch(h, ctx, qs.from_query((size_t) q0), n, k, ef, metric,
                               any_filter ? h->d_bm.as<const uint64_t*>() + q0 : nullptr, false, out.from_query((size_t) q0, k),
                               d_tuples ? d_tuples + q0 : nullptr, d_status ? d_status + q0 : nullptr, &it)))
             return rc;
@@ -649,41 +819,184 @@ static int hnsw_iter_run(vsr_hnsw* h, const float* d_q, int nq, int dim, int k, 
     return VSR_OK;
 }
 
+// vsr_hnsw_search_iterative_device / vsr_hnsw_search_bit_iterative_device
+static int hnsw_iterative_device(const HnswEntry& en, vsr_hnsw* h, const void* d_queries, int nq, int dim, int k, int ef, int metric,
+                                 const vsr_filter* const* filters, int mode, int64_t max_scan_tuples, int64_t* d_blk, int32_t* d_doc,
+                                 int64_t* d_row, float* d_dist, int32_t* d_cnt, int64_t* d_tuples)
+{
+    int rc = hnsw_iter_check(h, d_queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples, en);
+    if (rc) return rc;
+    if (mode == VSR_HNSW_ITERATIVE_OFF)
+        return hnsw_search_device(en, h, d_queries, nq, dim, k, ef, metric, filters, d_blk, d_doc, d_row, d_dist, d_cnt, d_tuples);
+    if (nq == 0) return VSR_OK;
+    if (!d_blk || !d_dist || !d_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", en.who);
+    vsr_ctx* ctx = h->corpus->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    if ((rc = hnsw_doc_scratch(h, nq, k, d_doc))) return rc;
+    HnswQueries qs;
+    if ((rc = en.resident(h, ctx, d_queries, nq, dim, qs))) return rc;
+    return hnsw_iter_run(h, qs, nq, k, ef, metric, filters, mode, max_scan_tuples, hnsw_discard_cap(h, ef, max_scan_tuples),
+                         {d_blk, d_doc, d_row, d_dist, d_cnt, nullptr}, d_tuples, nullptr);
+}
+
 extern "C" int vsr_hnsw_search_iterative_device(vsr_hnsw* h, const float* d_queries, int nq, int dim, int k, int ef, int metric,
                                                 const vsr_filter* const* filters, int mode, int64_t max_scan_tuples,
                                                 int64_t* d_blk, int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt,
                                                 int64_t* d_tuples)
 {
-    int rc = hnsw_iter_check(h, d_queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples, "vsr_hnsw_search_iterative_device");
+    return hnsw_iterative_device({"vsr_hnsw_search_iterative_device", false}, h, d_queries, nq, dim, k, ef, metric, filters, mode,
+                                 max_scan_tuples, d_blk, d_doc, d_row, d_dist, d_cnt, d_tuples);
+}
+
+extern "C" int vsr_hnsw_search_bit_iterative_device(vsr_hnsw* h, const uint8_t* d_queries, int nq, int dim, int k, int ef, int metric,
+                                                    const vsr_filter* const* filters, int mode, int64_t max_scan_tuples,
+                                                    int64_t* d_blk, int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt,
+                                                    int64_t* d_tuples)
+{
+    return hnsw_iterative_device({"vsr_hnsw_search_bit_iterative_device", true}, h, d_queries, nq, dim, k, ef, metric, filters, mode,
+                                 max_scan_tuples, d_blk, d_doc, d_row, d_dist, d_cnt, d_tuples);
+}
+
+// vsr_hnsw_search_iterative / vsr_hnsw_search_bit_iterative
+static int hnsw_iterative_host(const HnswEntry& en, vsr_hnsw* h, const void* queries, int nq, int dim, int k, int ef, int metric,
+                               const vsr_filter* const* filters, int mode, int64_t max_scan_tuples, int64_t* out_blk, int32_t* out_doc,
+                               int64_t* out_row, float* out_dist, int32_t* out_cnt, int64_t* out_tuples)
+{
+    int rc = hnsw_iter_check(h, queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples, en);
     if (rc) return rc;
-    if (mode == VSR_HNSW_ITERATIVE_OFF)
-        return vsr_hnsw_search_device(h, d_queries, nq, dim, k, ef, metric, filters, d_blk, d_doc, d_row, d_dist, d_cnt, d_tuples);
+    if (mode == VSR_HNSW_ITERATIVE_OFF)                      // hnsw.iterative_scan = off: the plain search, T = the visited count
+        return hnsw_search_host(en, h, queries, nq, dim, k, ef, metric, filters, out_blk, out_doc, out_row, out_dist, out_cnt, out_tuples);
     if (nq == 0) return VSR_OK;
-    if (!d_blk || !d_dist || !d_cnt) return fail(VSR_ERR_INVALID, "vsr_hnsw_search_iterative_device: output is NULL");
+    if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", en.who);
     vsr_ctx* ctx = h->corpus->ctx;
     HIPCHK(hipSetDevice(ctx->device));
-    if ((rc = hnsw_doc_scratch(h, nq, k, d_doc))) return rc;
-    return hnsw_iter_run(h, d_queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples, hnsw_discard_cap(h, ef, max_scan_tuples),
-                         {d_blk, d_doc, d_row, d_dist, d_cnt, nullptr}, d_tuples, nullptr);
+    // tier 1: queries whose D overflowed, again with room for every element (an element is in at most one of D, W, emitted)
+    const uint32_t cap_d[2] = {hnsw_discard_cap(h, ef, max_scan_tuples), (uint32_t) std::max(h->n_elem, 1)};
+    return hnsw_host_search(h, queries, en.bytes(dim), nq, k, filters, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr}, out_tuples,
+                            [&](const void* d_q, int n, const vsr_filter* const* fs, int tier, const Outputs& res, int64_t* d_tup,
+                                int32_t* d_status) -> int {
+                                HnswQueries qs;
+                                int r = en.resident(h, ctx, d_q, n, dim, qs);
+                                if (r) return r;
+                                return hnsw_iter_run(h, qs, n, k, ef, metric, fs, mode, max_scan_tuples, cap_d[tier], res, d_tup, d_status);
+                            });
 }
 
 extern "C" int vsr_hnsw_search_iterative(vsr_hnsw* h, const float* queries, int nq, int dim, int k, int ef, int metric,
                                          const vsr_filter* const* filters, int mode, int64_t max_scan_tuples, int64_t* out_blk,
                                          int32_t* out_doc, int64_t* out_row, float* out_dist, int32_t* out_cnt, int64_t* out_tuples)
 {
-    int rc = hnsw_iter_check(h, queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples, "vsr_hnsw_search_iterative");
+    return hnsw_iterative_host({"vsr_hnsw_search_iterative", false}, h, queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples,
+                               out_blk, out_doc, out_row, out_dist, out_cnt, out_tuples);
+}
+
+extern "C" int vsr_hnsw_search_bit_iterative(vsr_hnsw* h, const uint8_t* queries, int nq, int dim, int k, int ef, int metric,
+                                             const vsr_filter* const* filters, int mode, int64_t max_scan_tuples, int64_t* out_blk,
+                                             int32_t* out_doc, int64_t* out_row, float* out_dist, int32_t* out_cnt, int64_t* out_tuples)
+{
+    return hnsw_iterative_host({"vsr_hnsw_search_bit_iterative", true}, h, queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples,
+                               out_blk, out_doc, out_row, out_dist, out_cnt, out_tuples);
+}
+
+// ---- indexed two-stage search: the Hamming shortlist from the bit graph (K4b), the exact re-rank on the source rows ----
+// vsr_search_quantized with stage 1 replaced by the index: binary_quantize of the queries -> query staging -> ONE K4b launch
+// with k = shortlist whose epilogue writes the stage-1 keys -> the re-rank and emit launches of vsr_shortlist.h
+// (quantized_rerank, vsr_search.hip).  Everything on the bit corpus context's stream, no host round trip.  d_status: optional
+// [nq] status words of stage 1 (1: the LDS visited table overflowed; that query's shortlist is empty).
+static int hnsw_quantized_impl(vsr_corpus* src, vsr_hnsw* h, const float* h_queries, const float* d_queries, int nq, int dim, int k,
+                               int shortlist, int ef, int metric, const vsr_filter* const* filters, bool force_global,
+                               const Outputs& out, int32_t* d_status)
+{
+    vsr_corpus* bits = h->corpus;
+    vsr_ctx* ctx = bits->ctx;
+    const size_t ns = (size_t) nq * (size_t) shortlist, qbytes = (size_t) (dim + 7) / 8;
+    // scratch: [fp32 queries of a host call | bit queries | stage-1 keys | stage-1 block ids, then the re-rank keys | doc | dist | counts]
+    const size_t o_q = 0, o_qb = align_up(o_q + (h_queries ? (size_t) nq * dim * sizeof(float) : 0), 256),
+                 o_key = align_up(o_qb + (size_t) nq * qbytes, 256), o_blk = align_up(o_key + ns * 8, 256),
+                 o_doc = align_up(o_blk + ns * 8, 256), o_dist = align_up(o_doc + ns * 4, 256),
+                 o_cnt = align_up(o_dist + ns * 4, 256), total = align_up(o_cnt + (size_t) nq * 4, 256);
+    int rc = ctx->d_short.reserve(total);
     if (rc) return rc;
-    if (mode == VSR_HNSW_ITERATIVE_OFF)                      // hnsw.iterative_scan = off: the plain search, T = the visited count
-        return vsr_hnsw_search(h, queries, nq, dim, k, ef, metric, filters, out_blk, out_doc, out_row, out_dist, out_cnt, out_tuples);
+    char* w = ctx->d_short.as<char>();
+    if (h_queries) {
+        HIPCHK(hipMemcpyAsync(w + o_q, h_queries, (size_t) nq * dim * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        d_queries = reinterpret_cast<const float*>(w + o_q);
+    }
+    uint8_t* d_qb = reinterpret_cast<uint8_t*>(w + o_qb);
+    uint64_t* s1_keys = reinterpret_cast<uint64_t*>(w + o_key);
+    HIPCHK(launch_binary_quantize(d_queries, 0, (uint64_t) nq, (uint32_t) dim, (uint32_t) dim, d_qb, (uint32_t) qbytes, ctx->stream));
+    bool any_filter = false;
+    if (h->h_bm.p) HIPCHK(hipStreamSynchronize(ctx->stream));            // the pinned pointer block of the previous call
+    if ((rc = hnsw_bitmaps(h, ctx, filters, nq, any_filter))) return rc;
+    HnswQueries qs;
+    if ((rc = hnsw_stage_bits(h, ctx, d_qb, nq, qs))) return rc;
+    const Outputs s1{reinterpret_cast<int64_t*>(w + o_blk), reinterpret_cast<int32_t*>(w + o_doc), nullptr,
+                     reinterpret_cast<float*>(w + o_dist), reinterpret_cast<int32_t*>(w + o_cnt), s1_keys};
+    if ((rc = hnsw_launch(h, ctx, qs, nq, shortlist, ef, VSR_METRIC_HAMMING, any_filter ? h->d_bm.as<const uint64_t*>() : nullptr,
+                          force_global, s1, nullptr, d_status)))
+        return rc;
+    return quantized_rerank(ctx, src, s1_keys, (uint32_t) bits->row_offset, reinterpret_cast<uint64_t*>(w + o_blk), d_queries, nq, dim, k,
+                            shortlist, metric, out);
+}
+
+static int hnsw_quantized_check(vsr_corpus* src, vsr_hnsw* h, const void* queries, int nq, int dim, int k, int shortlist, int ef,
+                                int metric, const vsr_filter* const* filters, const char* who)
+{
+    if (!h) return fail(VSR_ERR_INVALID, "%s: index is NULL", who);
+    int rc = check_quantized_args(nullptr, src, h->corpus, queries, nq, dim, k, shortlist, metric, filters, who);
+    if (rc) return rc;
+    if (h->bit_metric != VSR_METRIC_HAMMING)
+        return fail(VSR_ERR_INVALID, "%s: the index was made for %s: the shortlist of binary_quantize needs a Hamming index", who,
+                    h->bit_metric ? bit_metric_name(h->bit_metric) : "a corpus that is not a bit corpus");
+    if (ef < 1 || ef > 5000) return fail(VSR_ERR_INVALID, "%s: ef_search must be between 1 and 5000 (got %d)", who, ef);
+    return VSR_OK;
+}
+
+extern "C" int vsr_hnsw_search_quantized_device(vsr_corpus* src, vsr_hnsw* h, const float* d_queries, int nq, int dim, int k,
+                                                int shortlist, int ef, int metric, const vsr_filter* const* filters, int64_t* d_blk,
+                                                int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt, uint64_t* d_keys)
+{
+    const char* who = "vsr_hnsw_search_quantized_device";
+    int rc = hnsw_quantized_check(src, h, d_queries, nq, dim, k, shortlist, ef, metric, filters, who);
+    if (rc) return rc;
     if (nq == 0) return VSR_OK;
-    if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "vsr_hnsw_search_iterative: output is NULL");
+    if (!d_blk || !d_dist || !d_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", who);
     HIPCHK(hipSetDevice(h->corpus->ctx->device));
-    // tier 1: queries whose D overflowed, again with room for every element (an element is in at most one of D, W, emitted)
-    const uint32_t cap_d[2] = {hnsw_discard_cap(h, ef, max_scan_tuples), (uint32_t) std::max(h->n_elem, 1)};
-    return hnsw_host_search(h, queries, nq, dim, k, filters, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr}, out_tuples,
-                            [&](const float* d_q, int n, const vsr_filter* const* fs, int tier, const Outputs& res, int64_t* d_tup,
-                                int32_t* d_status) -> int {
-                                return hnsw_iter_run(h, d_q, n, dim, k, ef, metric, fs, mode, max_scan_tuples, cap_d[tier], res, d_tup,
-                                                     d_status);
-                            });
+    return hnsw_quantized_impl(src, h, nullptr, d_queries, nq, dim, k, shortlist, ef, metric, filters, false,
+                               {d_blk, d_doc, d_row, d_dist, d_cnt, d_keys}, nullptr);
+}
+
+extern "C" int vsr_hnsw_search_quantized(vsr_corpus* src, vsr_hnsw* h, const float* queries, int nq, int dim, int k, int shortlist,
+                                         int ef, int metric, const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc,
+                                         int64_t* out_row, float* out_dist, int32_t* out_cnt)
+{
+    const char* who = "vsr_hnsw_search_quantized";
+    int rc = hnsw_quantized_check(src, h, queries, nq, dim, k, shortlist, ef, metric, filters, who);
+    if (rc) return rc;
+    if (nq == 0) return VSR_OK;
+    if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", who);
+    if (src->half) {                                        // `$1::halfvec`, as vsr_search refuses it
+        const size_t total = (size_t) nq * (size_t) dim;
+        for (size_t i = 0; i < total; ++i)
+            if (std::isfinite(queries[i]) && std::fabs(queries[i]) >= 65520.0f)
+                return fail(VSR_ERR_INVALID, "\"%.9g\" is out of range for type halfvec", (double) queries[i]);
+    }
+    vsr_ctx* ctx = h->corpus->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    const ResultBlock rb(nq, k, false);                     // results and stage 1's status words: one packed copy back, one wait
+    if ((rc = h->d_out.reserve(rb.total))) return rc;
+    if ((rc = h->h_out.reserve(rb.total))) return rc;
+    char* d = h->d_out.as<char>();
+    char* hh = h->h_out.as<char>();
+    // tier 1: a query's LDS visited table overflowed (big graphs only): the call again with the global bitmap
+    for (int tier = 0; tier < 2; ++tier) {
+        if ((rc = hnsw_quantized_impl(src, h, queries, nullptr, nq, dim, k, shortlist, ef, metric, filters, tier == 1, rb.arrays(d),
+                                      rb.column<int32_t>(d, rb.o_status))))
+            return rc;
+        HIPCHK(hipMemcpyAsync(hh, d, rb.total, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (rb.flagged(hh, (size_t) nq).empty()) break;
+    }
+    rb.copy_out_all(hh, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr}, nullptr);
+    return VSR_OK;
 }

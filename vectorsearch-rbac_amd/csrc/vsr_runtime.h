@@ -424,5 +424,11 @@ int    check_sparse_rows(const char* who, const int64_t* indptr, const int32_t* 
                          uint32_t* max_nnz);
 int    host_search(vsr_corpus* c, const float* queries, int nq, int dim, int k, int metric, const vsr_filter* const* filters,
                    const Outputs& out);
+// the two-stage searches (vsr_search_quantized*, and vsr_hnsw_search_quantized* in vsr_hnsw_rt.hip): the argument checks they share
+// (session may be nullptr) and stage 2, the exact re-rank of stage-1 keys on the source rows
+int    check_quantized_args(const vsr_ctx* session, const vsr_corpus* src, const vsr_corpus* bits, const void* queries, int nq,
+                            int dim, int k, int shortlist, int metric, const vsr_filter* const* filters, const char* who);
+int    quantized_rerank(vsr_ctx* ctx, vsr_corpus* src, const uint64_t* s1_keys, uint32_t s1_row_offset, uint64_t* rr_keys,
+                        const float* d_queries, int nq, int dim, int k, int shortlist, int metric, const Outputs& out);
 
 }  // namespace vsr

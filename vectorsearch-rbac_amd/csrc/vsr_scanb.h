@@ -21,35 +21,11 @@
 // one-query in-kernel merge, FusedTail, is not instantiated here).
 #pragma once
 #include "vsr_scan.h"
+#include "vsr_bitops.h"
 
 namespace vsr {
 
-enum MetricBit : int { M_HAMMING = 4, M_JACCARD = 5 };
-
-template <bool JACCARD>
-__device__ __forceinline__ void accum_bits(uint32_t& p, const uint4& x, const uint4& q)
-{
-    if constexpr (JACCARD) {
-        p += (uint32_t) __popc(x.x & q.x); p += (uint32_t) __popc(x.y & q.y);
-        p += (uint32_t) __popc(x.z & q.z); p += (uint32_t) __popc(x.w & q.w);
-    } else {
-        p += (uint32_t) __popc(x.x ^ q.x); p += (uint32_t) __popc(x.y ^ q.y);
-        p += (uint32_t) __popc(x.z ^ q.z); p += (uint32_t) __popc(x.w ^ q.w);
-    }
-}
-
-// (float) of the operator's float8.  Hamming: the count.  Jaccard (bitutils.c:125-128): ab == 0 ? 1 : 1 - ab / (double) (aa + bb - ab)
-template <bool JACCARD>
-__device__ __forceinline__ float rank_value_bits(uint32_t p, float row_pop, float q_pop)
-{
-    if constexpr (JACCARD) {
-        if (p == 0) return 1.0f;
-        const double uni = (double) row_pop + (double) q_pop - (double) p;      // integers < 2^17: exact
-        return (float) (1.0 - (double) p / uni);
-    } else {
-        return (float) p;
-    }
-}
+// MetricBit, accum_bits and rank_value_bits: vsr_bitops.h (shared with the graph kernels)
 
 // reduce_slots (vsr_scan.h) over uint32 partials: N live registers over lanes differing in bit M (and below)
 template <int M, int N>

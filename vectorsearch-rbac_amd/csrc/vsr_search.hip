@@ -747,7 +747,7 @@ int vsr::check_search_args(const vsr_corpus* c, const void* queries, int nq, int
         return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus is searched with vsr_search_sparse* (<->, <#>, <=>, <+>) and has no index path yet", who);
     if (bit_entry && !c->bit) return fail(VSR_ERR_INVALID, "%s: the corpus is not a bit corpus", who);
     if (c->bit && !bit_entry)
-        return fail(VSR_ERR_UNSUPPORTED, "%s: a bit corpus is searched with vsr_search_bit* (<~> / <%%>) and has no index path yet", who);
+        return fail(VSR_ERR_UNSUPPORTED, "%s: a bit corpus is searched with vsr_search_bit* (<~> / <%%>), its graphs with vsr_hnsw_search_bit*", who);
     if (nq < 0 || (nq > 0 && !queries)) return fail(VSR_ERR_INVALID, "%s: queries is NULL", who);
     if (dim != c->dim && c->sparse)                         // CheckDims, sparsevec.c
         return fail(VSR_ERR_DIM_MISMATCH, "different sparsevec dimensions %d and %d", c->dim, dim);
@@ -1031,7 +1031,7 @@ extern "C" int vsr_search_sparse(vsr_corpus* c, const int64_t* q_indptr, const i
 //   session's scratch -> shortlist_rerank_kernel over the source rows -> shortlist_emit_kernel.
 static const char* corpus_kind(const vsr_corpus* c) { return c->sparse ? "sparsevec" : c->bit ? "bit" : c->half ? "halfvec" : "vector"; }
 
-static int check_quantized_args(const vsr_ctx* session, const vsr_corpus* src, const vsr_corpus* bits, const void* queries, int nq,
+int vsr::check_quantized_args(const vsr_ctx* session, const vsr_corpus* src, const vsr_corpus* bits, const void* queries, int nq,
                                 int dim, int k, int shortlist, int metric, const vsr_filter* const* filters, const char* who)
 {
     if (!src || !bits) return fail(VSR_ERR_INVALID, "%s: corpus is NULL", who);
@@ -1086,18 +1086,27 @@ static int search_quantized_impl(vsr_ctx* ctx, vsr_corpus* src, vsr_corpus* bits
     const Outputs s1{reinterpret_cast<int64_t*>(w + o_blk), reinterpret_cast<int32_t*>(w + o_doc), nullptr,
                      reinterpret_cast<float*>(w + o_dist), reinterpret_cast<int32_t*>(w + o_cnt), s1_keys};
     RCCHK(search_impl(ctx, bits, {nullptr, reinterpret_cast<const float*>(d_qb), nq, dim, shortlist, VSR_METRIC_HAMMING, s1}, filters, 2));
+    return quantized_rerank(ctx, src, s1_keys, (uint32_t) bits->row_offset, reinterpret_cast<uint64_t*>(w + o_blk), d_queries, nq, dim, k,
+                            shortlist, metric, out);
+}
 
+// Stage 2 of a two-stage search, whoever made the shortlist (K1b here, the bit graph in vsr_hnsw_rt.hip): the re-rank and emit
+// launches of vsr_shortlist.h on ctx->stream.  s1_keys: [nq][shortlist] stage-1 keys, ascending with KEY_EMPTY last, whose rows carry
+// s1_row_offset; rr_keys: [nq][shortlist] scratch; d_queries: the fp32 queries in device memory.
+int vsr::quantized_rerank(vsr_ctx* ctx, vsr_corpus* src, const uint64_t* s1_keys, uint32_t s1_row_offset, uint64_t* rr_keys,
+                          const float* d_queries, int nq, int dim, int k, int shortlist, int metric, const Outputs& out)
+{
     ShortlistParams sl{};
     sl.s1_keys = s1_keys;
     sl.shortlist = (uint32_t) shortlist;
-    sl.s1_row_offset = (uint32_t) bits->row_offset;
+    sl.s1_row_offset = s1_row_offset;
     sl.q_src = d_queries;
     sl.dim = (uint32_t) dim;
     sl.rows = src->d_rows;
     sl.stride4 = src->stride4;
     sl.n_rows = (uint32_t) src->n;
     sl.metric = metric;
-    sl.rr_keys = reinterpret_cast<uint64_t*>(w + o_blk);
+    sl.rr_keys = rr_keys;
     sl.err = ctx->err_word();
     sl.k = (uint32_t) k;
     sl.row_offset = (uint32_t) src->row_offset;

@@ -1,6 +1,7 @@
 // vsr_shortlist.h — stage 2 of the two-stage search (vsr_search_quantized*): the exact re-rank of a Hamming shortlist.
-// Stage 1 is K1b over the bit corpus with k = shortlist (vsr_search.hip); its keys (ascending, KEY_EMPTY padded) name the
-// rows whose SOURCE image -- fp32 or halfvec -- is gathered here.  Kernels: vsr_shortlist.hip.
+// Stage 1 is K1b over the bit corpus with k = shortlist (vsr_search.hip), or K4b over its Hamming graph (vsr_hnsw_rt.hip:
+// vsr_hnsw_search_quantized*); its keys (KEY_EMPTY padded: every real key before the first empty one) name the rows whose
+// SOURCE image -- fp32 or halfvec -- is gathered here.  Kernels: vsr_shortlist.hip.
 #pragma once
 #include "vsr_device.h"
 

@@ -480,6 +480,20 @@ class Corpus:
         max_level (include/vsrbac.h, vsr_hnsw_load: what a dump of pgvector's in-memory build holds)."""
         return HnswIndex(self, graph)
 
+    def build_hnsw_bit(self, m=16, ef_construction=64, metric="hamming", seed=1, merge_duplicates=False):
+        """CREATE INDEX ... USING hnsw (col bit_hamming_ops | bit_jaccard_ops) over this bit corpus (vsr_hnsw_build_bit):
+        build_hnsw's batched insertion on the packed rows.  merge_duplicates: byte-identical rows share an element -- the
+        build to use on a quantized corpus, which is full of duplicates."""
+        h = C.c_void_p()
+        check(self._lib.vsr_hnsw_build_bit(self._h, int(m), int(ef_construction), _metric(metric), int(seed),
+                                           BUILD_MERGE_DUPLICATES if merge_duplicates else 0, C.byref(h)))
+        return HnswIndex(self, h)
+
+    def load_hnsw_bit(self, graph, metric="hamming"):
+        """load_hnsw over this bit corpus (vsr_hnsw_load_bit): `metric` is the opclass the graph was built for, "hamming" or
+        "jaccard"; the index then answers HnswIndex.search_bit* with that metric only."""
+        return HnswIndex(self, graph, bit_metric=_metric(metric))
+
     # ---- search ------------------------------------------------------------------------------
     def pack_filters(self, filters):
         """One filter per query as a reusable C array (build it once when the same batch shape repeats)."""
@@ -613,6 +627,35 @@ class Corpus:
                                                        _metric(metric), farr, d_block, d_doc, d_rows, d_dist, d_counts, d_keys))
         return keep
 
+    def search_quantized_hnsw(self, bit_index, queries, k, shortlist, ef_search=40, metric="l2", filters=None):
+        """search_quantized with the shortlist taken from an index (vsr_hnsw_search_quantized): `bit_index` is a Hamming
+        HnswIndex over this corpus's binary_quantize(); the shortlist is its search_bit answer for k = shortlist and
+        ef_search (it may be shorter than `shortlist`), the re-rank is search_quantized's.  `filters` are filters of the bit
+        corpus."""
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(queries, dtype=np.float32)))
+        nq, dim = q.shape
+        farr, keep = bit_index.corpus._filter_array(filters, nq)
+        kk = max(int(k), 1)
+        blk = np.full((nq, kk), -1, dtype=np.int64)
+        doc = np.full((nq, kk), -1, dtype=np.int32)
+        row = np.full((nq, kk), -1, dtype=np.int64)
+        dist = np.full((nq, kk), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.int32)
+        check(self._lib.vsr_hnsw_search_quantized(self._h, bit_index._h, _ptr(q), nq, dim, int(k), int(shortlist), int(ef_search),
+                                                  _metric(metric), farr, _ptr(blk), _ptr(doc), _ptr(row), _ptr(dist), _ptr(cnt)))
+        del keep
+        return SearchResult(blk, doc, row, dist, cnt)
+
+    def search_quantized_hnsw_device(self, bit_index, d_queries, nq, k, shortlist, ef_search, metric, filters, d_block, d_doc,
+                                     d_rows, d_dist, d_counts, d_keys=None):
+        """search_quantized_hnsw with device pointers (ints): d_queries addresses nq x dim floats.  Both stages are enqueued on
+        the bit corpus context's stream; nothing synchronises (vsr_hnsw_search_quantized_device)."""
+        farr, keep = bit_index.corpus._filter_array(filters, nq)
+        check(self._lib.vsr_hnsw_search_quantized_device(self._h, bit_index._h, d_queries, nq, self.dim, int(k), int(shortlist),
+                                                         int(ef_search), _metric(metric), farr, d_block, d_doc, d_rows, d_dist,
+                                                         d_counts, d_keys))
+        return keep
+
     def ivf_assign(self, centers, metric="l2"):
         """The pass of the ivfflat build that touches every row (ivfbuild.c:404-445): the nearest centre of each row, in
         the caller's row order -- the `row_list` IvfIndex / vsr_ivf_load take."""
@@ -724,9 +767,9 @@ class IvfIndex:
 class HnswIndex:
     """pgvector's hnsw scan (hnswscan.c) on the GPU: greedy descent, ef_search beam on layer 0, TIDs, filter, LIMIT."""
 
-    def __init__(self, corpus, g):
+    def __init__(self, corpus, g, bit_metric=None):
         self.corpus, self._lib = corpus, corpus._lib
-        if isinstance(g, C.c_void_p):                # a handle vsr_hnsw_build returned (Corpus.build_hnsw)
+        if isinstance(g, C.c_void_p):                # a handle vsr_hnsw_build* returned (Corpus.build_hnsw, build_hnsw_bit)
             self._h = g
             return
         a = lambda name, dt: np.ascontiguousarray(g[name], dtype=dt)
@@ -734,8 +777,13 @@ class HnswIndex:
         up_slot, up_nbr = a("up_slot", np.int32), a("up_nbr", np.int32)
         n_upper = int((up_slot >= 0).sum())
         h = C.c_void_p()
-        check(self._lib.vsr_hnsw_load(corpus._h, int(g["m"]), level.size, int(g["entry"]), _ptr(level), _ptr(nbr0), _ptr(tc),
-                                      _ptr(tids), _ptr(up_slot), _ptr(up_nbr), n_upper, int(g["max_level"]), C.byref(h)))
+        if bit_metric is not None:                   # Corpus.load_hnsw_bit: the opclass travels with the graph
+            check(self._lib.vsr_hnsw_load_bit(corpus._h, int(bit_metric), int(g["m"]), level.size, int(g["entry"]), _ptr(level),
+                                              _ptr(nbr0), _ptr(tc), _ptr(tids), _ptr(up_slot), _ptr(up_nbr), n_upper,
+                                              int(g["max_level"]), C.byref(h)))
+        else:
+            check(self._lib.vsr_hnsw_load(corpus._h, int(g["m"]), level.size, int(g["entry"]), _ptr(level), _ptr(nbr0), _ptr(tc),
+                                          _ptr(tids), _ptr(up_slot), _ptr(up_nbr), n_upper, int(g["max_level"]), C.byref(h)))
         self._h = h
 
     def free(self):
@@ -833,3 +881,59 @@ class HnswIndex:
                                                   _ptr(dist), _ptr(cnt), _ptr(tup)))
         del keep
         return SearchResult(blk, doc, row, dist, cnt), tup
+
+    # ---- a bit index (Corpus.load_hnsw_bit / build_hnsw_bit): queries are bit strings, the metric is the index's -------------
+    def _results(self, nq, k):
+        kk = max(int(k), 1)
+        return (np.full((nq, kk), -1, dtype=np.int64), np.full((nq, kk), -1, dtype=np.int32), np.full((nq, kk), -1, dtype=np.int64),
+                np.full((nq, kk), np.inf, dtype=np.float32), np.zeros(nq, dtype=np.int32))
+
+    def search_bit(self, queries, k, ef_search=40, metric="hamming", filters=None, dim=None):
+        """HnswIndex.search over a bit index (vsr_hnsw_search_bit): `queries` bool [nq, dim] or packed uint8
+        [nq, (dim + 7) // 8] (dim: the corpus's unless given), as Corpus.search_bit takes them; `metric` must be the index's.
+        SearchResult (dist: the Hamming count or the Jaccard distance) plus the elements each query visited on layer 0."""
+        q, qdim = _packed_bits(queries, self.corpus.dim if dim is None else dim, "search_bit")
+        nq = q.shape[0]
+        farr, keep = self.corpus._filter_array(filters, nq)
+        blk, doc, row, dist, cnt = self._results(nq, k)
+        vis = np.zeros(nq, dtype=np.int64)
+        check(self._lib.vsr_hnsw_search_bit(self._h, _ptr(q), nq, qdim, int(k), int(ef_search), _metric(metric), farr, _ptr(blk),
+                                            _ptr(doc), _ptr(row), _ptr(dist), _ptr(cnt), _ptr(vis)))
+        del keep
+        return SearchResult(blk, doc, row, dist, cnt), vis
+
+    def search_bit_device(self, d_queries, nq, k, ef_search, metric, filters, d_block, d_doc, d_rows, d_dist, d_counts,
+                          d_visited=None, dim=None):
+        """Device pointers (ints): d_queries addresses nq x (dim + 7) // 8 packed bytes, any alignment; query staging and ONE
+        search launch on the corpus context's stream, no synchronisation (vsr_hnsw_search_bit_device)."""
+        farr, keep = self.corpus._filter_array(filters, nq)
+        check(self._lib.vsr_hnsw_search_bit_device(self._h, d_queries, nq, self.corpus.dim if dim is None else dim, int(k),
+                                                   int(ef_search), _metric(metric), farr, d_block, d_doc, d_rows, d_dist, d_counts,
+                                                   d_visited))
+        return keep
+
+    def search_bit_iterative(self, queries, k, ef_search=40, metric="hamming", filters=None, mode="relaxed_order",
+                             max_scan_tuples=20000, dim=None):
+        """search_iterative over a bit index (vsr_hnsw_search_bit_iterative): SearchResult in stream order plus the tuples
+        each query's scan counted when it stopped."""
+        q, qdim = _packed_bits(queries, self.corpus.dim if dim is None else dim, "search_bit_iterative")
+        nq = q.shape[0]
+        farr, keep = self.corpus._filter_array(filters, nq)
+        blk, doc, row, dist, cnt = self._results(nq, k)
+        tup = np.zeros(nq, dtype=np.int64)
+        check(self._lib.vsr_hnsw_search_bit_iterative(self._h, _ptr(q), nq, qdim, int(k), int(ef_search), _metric(metric), farr,
+                                                      _iterative_mode(mode), int(max_scan_tuples), _ptr(blk), _ptr(doc), _ptr(row),
+                                                      _ptr(dist), _ptr(cnt), _ptr(tup)))
+        del keep
+        return SearchResult(blk, doc, row, dist, cnt), tup
+
+    def search_bit_iterative_device(self, d_queries, nq, k, ef_search, metric, filters, mode, max_scan_tuples, d_block, d_doc,
+                                    d_rows, d_dist, d_counts, d_tuples=None, dim=None):
+        """Device pointers (ints); no synchronisation (vsr_hnsw_search_bit_iterative_device).  A query whose discarded set
+        outgrew its buffer reports count -1."""
+        farr, keep = self.corpus._filter_array(filters, nq)
+        check(self._lib.vsr_hnsw_search_bit_iterative_device(self._h, d_queries, nq, self.corpus.dim if dim is None else dim,
+                                                             int(k), int(ef_search), _metric(metric), farr, _iterative_mode(mode),
+                                                             int(max_scan_tuples), d_block, d_doc, d_rows, d_dist, d_counts,
+                                                             d_tuples))
+        return keep
