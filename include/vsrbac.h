@@ -110,9 +110,10 @@ int vsr_corpus_load(vsr_ctx* ctx, const float* rows, int64_t n, int dim,
  * screened on the f16 matrix cores and re-ranked exactly, as over an fp32 corpus: vsr_search_device may return flagged
  * queries (negative counts), vsr_search and vsr_search_device_exact re-run them, on the exact kernel over the half rows.
  * vsr_set_screening(ctx, 0) keeps every search on that kernel; vsr_set_query_hint has no effect.  Non-finite rows are accepted as for fp32 (pgvector rejects them on input): NaN
- * distances sort last.  vsr_ivf_load, vsr_ivf_assign, vsr_hnsw_load and vsr_hnsw_build* over such a corpus:
- * VSR_ERR_UNSUPPORTED (the halfvec_*_ops index opclasses are not built yet; of pgvector's other column types only bit has an
- * index path, vsr_hnsw_*_bit). */
+ * distances sort last.  The HNSW opclasses halfvec_l2_ops / halfvec_ip_ops / halfvec_cosine_ops are vsr_hnsw_load_half /
+ * vsr_hnsw_build_half below, searched by the float vsr_hnsw_search* entry points (K4h); vsr_hnsw_load and vsr_hnsw_build* over
+ * such a corpus keep answering VSR_ERR_UNSUPPORTED, the message names the halfvec corpus and those entry points.  vsr_ivf_load and
+ * vsr_ivf_assign over such a corpus: VSR_ERR_UNSUPPORTED (IVFFlat over halfvec is not built yet). */
 int vsr_corpus_load_half(vsr_ctx* ctx, const uint16_t* rows, int64_t n, int dim,
                          const int64_t* block_ids, const int32_t* doc_ids, int64_t row_offset,
                          vsr_corpus** out);
@@ -536,6 +537,39 @@ int vsr_hnsw_search_iterative_device(vsr_hnsw* index, const float* d_queries, in
                                      const vsr_filter* const* filters, int mode, int64_t max_scan_tuples,
                                      int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
                                      int32_t* d_out_counts, int64_t* d_out_tuples);
+
+/* device memory of an index's graph arrays, in bytes (the corpus: vsr_corpus_device_bytes).  Any index; the row format of the
+ * corpus does not enter, so an index over halfvec rows and one over their fp32 image loaded from the same arrays agree. */
+int64_t vsr_hnsw_device_bytes(const vsr_hnsw* index);
+
+/* ---- HNSW over a halfvec corpus: halfvec_l2_ops / halfvec_ip_ops / halfvec_cosine_ops (hnsw_halfvec_support,
+ * hnswutils.c:1385-1396; test/sql/hnsw_halfvec.sql, test/t/024_hnsw_halfvec_build_recall.pl) ------------------------------------
+ * vsr_hnsw_load_half takes the arrays of vsr_hnsw_load, vsr_hnsw_build_half the arguments of vsr_hnsw_build_ex; both return an
+ * index that EVERY float search entry point above takes: vsr_hnsw_search, vsr_hnsw_search_device,
+ * vsr_hnsw_search_iterative(_device), metric per call (L2, inner product, cosine over unit rows rounded to binary16; L1:
+ * VSR_ERR_UNSUPPORTED, as for fp32 graphs).  The graph kernels gather the binary16 rows themselves (K4h): no fp32 image of the
+ * rows is made anywhere, and vsr_hnsw_device_bytes equals that of an fp32 index loaded from the same arrays.
+ *   - Arithmetic: pgvector's for the type (halfutils.c) -- both operands widened to fp32, fp32 sums.  Queries stay
+ *     const float*; the search kernel rounds every query element to binary16 (Float4ToHalf, round to nearest even) as it loads
+ *     the query.  There is no staging launch: vsr_hnsw_search_device stays ONE launch, the iterative form one per chunk of queries.
+ *   - Reported distances follow vsr_hnsw_search's rule for fp32 indexes.
+ *   - The host entry points refuse a finite query element that rounds to +-Inf (|v| >= 65520) with VSR_ERR_INVALID,
+ *     `"<v>" is out of range for type halfvec`, as vsr_search does; the device entry points do not look.  A dimension mismatch is
+ *     VSR_ERR_DIM_MISMATCH, "different halfvec dimensions %d and %d".
+ *   - A corpus that is not a halfvec corpus: VSR_ERR_INVALID.  More than 4000 dimensions (HNSW_MAX_DIM * 2, hnswutils.c:1390):
+ *     VSR_ERR_UNSUPPORTED, "column cannot have more than 4000 dimensions for hnsw index".  m, ef_construction, flags and metrics
+ *     are checked exactly as vsr_hnsw_build_ex checks them.
+ *   - vsr_hnsw_load / vsr_hnsw_build / vsr_hnsw_build_ex keep refusing a halfvec corpus (VSR_ERR_UNSUPPORTED, the message names
+ *     the halfvec corpus and these entry points).  vsr_hnsw_search_bit* on a half index: VSR_ERR_INVALID, as on any non-bit index.
+ *   - Everything else is vsr_hnsw_search's, unchanged: vsr_hnsw_set_predicate_aware, the iterative modes, the visited-set forms
+ *     and both re-runs, vsr_hnsw_export*, vsr_hnsw_info, vsr_hnsw_free, filters, row_offset, up to 10 TIDs per element.
+ * The merging build (VSR_HNSW_BUILD_MERGE_DUPLICATES) keeps vsr_hnsw_build_ex's grouping contract; identical means the binary16
+ * bytes are identical, so +0.0 and -0.0 differ: datumIsEqual on a halfvec.  The guarantee is recall, as for the float build
+ * (024_hnsw_halfvec_build_recall.pl's floor, 0.98 for all three opclasses).  halfvec_l1_ops and IVFFlat over halfvec are not built. */
+int vsr_hnsw_load_half(vsr_corpus* half_corpus, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
+                       const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
+                       int32_t n_upper, int32_t max_level, vsr_hnsw** out);
+int vsr_hnsw_build_half(vsr_corpus* half_corpus, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out);
 
 /* ---- HNSW over a bit corpus: bit_hamming_ops / bit_jaccard_ops (hnsw_bit_support, hnswutils.c:1398-1410; test/sql/hnsw_bit.sql,
  * test/t/020_hnsw_bit_build_recall.pl, 023_hnsw_bit_duplicates.pl) --------------------------------------------------------------

@@ -54,6 +54,7 @@
 #include "vsr_device.h"
 #include "vsr_topk.h"
 #include "vsr_bitops.h"
+#include "vsr_halfops.h"
 
 namespace vsr {
 
@@ -96,6 +97,9 @@ struct HnswParams {
     uint64_t*       out_keys = nullptr;      // optional [nq][k]: make_key(distance, internal row + key_row_offset) of every result,
                                              // KEY_EMPTY past the count: the stage-1 keys of the two-stage search (ShortlistParams::s1_keys)
     uint32_t        key_row_offset = 0;
+    // ROWS_HALF only.  rows: stride4 16-byte chunks of 8 binary16 values per row (elements past dim zero); queries: fp32, as for ROWS_F32
+    uint32_t        q_chunks = 0;            // 16-byte chunks of the wave's LDS that hold the rounded query: stride4 when stride4 > 64
+                                             // (set before hnsw_plan*, which count it), else 0 -- the query lives in registers
     // hnsw_iterative_kernel only (out_visited then reports T when the scan stopped; status 1 = D overflowed)
     int             iter_mode = 0;           // VSR_HNSW_ITERATIVE_RELAXED = 1 / STRICT = 2
     int64_t         max_scan = 0;            // hnsw.max_scan_tuples
@@ -106,8 +110,7 @@ struct HnswParams {
 constexpr int HN_UPPER_VISITED = 1024;     // visited list of an upper-layer (ef = 1) search, in LDS
 constexpr int HN_NBR = 256;                // neighbour ids of one expansion (2m <= 200)
 
-__device__ __forceinline__ float hnsw_rank_value(int metric, float s) { return metric == M_L2 ? s : -s; }
-
+// (hnsw_rank_value: vsr_halfops.h)
 __device__ __forceinline__ void wave_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -130,6 +133,14 @@ __device__ __forceinline__ void wave_sync_global()
 // of the staged query in a register across expansions (re-read from the staged copy when a row has more than 64 chunks);
 // partials are integer popcounts, reduced by shuffles inside the lane group, converted once with K1b's own expression
 // (rank_value_bits: Hamming the count, Jaccard in double then rounded).  The reported distance is that fp32 value (no sqrt).
+//
+// K4h, ROWS = ROWS_HALF: the graph of a halfvec corpus (halfvec_l2_ops / halfvec_ip_ops / halfvec_cosine_ops, hnswutils.c:1385-1396).
+// A row is C = ceil(dim / 8) 16-byte chunks of 8 binary16 values, half the bytes K4 gathers.  The half distance stage
+// (half_graph_distances, vsr_halfops.h) gives a row G lanes as K4b does: 4 neighbours per wave step at 128 dimensions, 32 at 10,
+// and beyond 512 dimensions the 64 lanes loop over the chunks.  The query arrives as fp32 and is rounded to binary16 once, when
+// the wave loads it (`$1::halfvec`): the lane keeps its chunk in a register when C <= 64, otherwise the wave keeps the rounded
+// query in its LDS (q_chunks chunks in front of the visited set); both last across expansions and there is no staging launch.
+// Arithmetic: both operands widened to fp32, fmaf sums (halfutils.c), ranked and reported exactly as K4 does.
 template <bool ITER, int ROWS = ROWS_F32>
 __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
 {
@@ -145,6 +156,11 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
     float*    nd = reinterpret_cast<float*>(nb + HN_NBR);                    // [HN_NBR] their distances
     int32_t*  uv = reinterpret_cast<int32_t*>(nd + HN_NBR);                  // [HN_UPPER_VISITED] upper-layer visited list
     uint32_t* lv = reinterpret_cast<uint32_t*>(uv + HN_UPPER_VISITED);       // layer-0 visited set: bitmap words or hash slots
+    uint4*    qh = nullptr;                                                  // ROWS_HALF: [q_chunks] the rounded query
+    if constexpr (ROWS == ROWS_HALF) {
+        qh = reinterpret_cast<uint4*>(lv);
+        lv += 4u * p.q_chunks;
+    }
     uint32_t* hist = nullptr;                                                // ITER: [HN_HIST] radix-select histogram
     if constexpr (ITER) {
         hist = lv;
@@ -191,6 +207,17 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
         if (p.stride4 <= 64u && gl < p.stride4) qreg = reinterpret_cast<const uint4*>(q)[gl];
         q_pop = p.q_pop[qi];
     }
+    // ROWS_HALF: the same lane groups; the query rounded to binary16 once, this lane's chunk of it or the copy in LDS
+    if constexpr (ROWS == ROWS_HALF) {
+        bit_g = bit_graph_lanes(p.stride4);
+        const uint32_t gl = (uint32_t) lane & (bit_g - 1u);
+        if (p.stride4 <= 64u) {
+            if (gl < p.stride4) qreg = half_query_chunk(q, p.dim, gl);
+        } else {
+            for (uint32_t ch = (uint32_t) lane; ch < p.q_chunks; ch += 64) qh[ch] = half_query_chunk(q, p.dim, ch);
+            wave_sync();
+        }
+    }
     // distance of the query to `cnt` elements listed in nb[] -> nd[] (fp32 sum; exact on integer-valued data in any order)
     auto distances = [&](int cnt) {
         if constexpr (ROWS == ROWS_BIT) {
@@ -200,6 +227,12 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
                 bit_graph_distances<true>(brows, p.stride4, bit_g, p.elem_row, p.row_pop, qs, qreg, q_pop, nb, cnt, nd, lane);
             else
                 bit_graph_distances<false>(brows, p.stride4, bit_g, p.elem_row, p.row_pop, qs, qreg, q_pop, nb, cnt, nd, lane);
+            wave_sync();
+            return;
+        } else if constexpr (ROWS == ROWS_HALF) {
+            const uint4* hrows = reinterpret_cast<const uint4*>(p.rows);
+            if (p.metric == M_L2) half_graph_distances<true>(hrows, p.stride4, bit_g, p.elem_row, qh, qreg, nb, cnt, nd, lane);
+            else half_graph_distances<false>(hrows, p.stride4, bit_g, p.elem_row, qh, qreg, nb, cnt, nd, lane);
             wave_sync();
             return;
         } else {
@@ -702,23 +735,27 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
 
 __global__ __launch_bounds__(256) void hnsw_search_kernel(const HnswParams p) { hnsw_search_body<false>(p); }
 __global__ __launch_bounds__(256) void hnsw_bit_search_kernel(const HnswParams p) { hnsw_search_body<false, ROWS_BIT>(p); }
+__global__ __launch_bounds__(256) void hnsw_half_search_kernel(const HnswParams p) { hnsw_search_body<false, ROWS_HALF>(p); }
 
 // pgvector's iterative index scan (see the header comment): every round of a query inside the one launch
 __global__ __launch_bounds__(256) void hnsw_iterative_kernel(const HnswParams p) { hnsw_search_body<true>(p); }
 __global__ __launch_bounds__(256) void hnsw_bit_iterative_kernel(const HnswParams p) { hnsw_search_body<true, ROWS_BIT>(p); }
+__global__ __launch_bounds__(256) void hnsw_half_iterative_kernel(const HnswParams p) { hnsw_search_body<true, ROWS_HALF>(p); }
 
 constexpr size_t HN_LDS_BUDGET = 156 * 1024;   // of the CU's 160 KB (dynamic LDS of one workgroup)
 
-inline size_t hnsw_lds_fixed(uint32_t caps)
+// (q_chunks: HnswParams::q_chunks, the rounded query of a K4h wave; 0 for every other kernel)
+inline size_t hnsw_lds_fixed(uint32_t caps, uint32_t q_chunks = 0)
 {
-    return (((size_t) caps * 8 + ((caps + 15) & ~15u) + (size_t) HN_NBR * 8 + (size_t) HN_UPPER_VISITED * 4) + 15) & ~(size_t) 15;
+    return ((((size_t) caps * 8 + ((caps + 15) & ~15u) + (size_t) HN_NBR * 8 + (size_t) HN_UPPER_VISITED * 4) + 15) & ~(size_t) 15) +
+           (size_t) q_chunks * 16;
 }
 
 // visited form, table size, queries per workgroup for a graph of n_elem elements searched with ef (see the header comment);
 // force_global: the re-run of queries whose LDS hash overflowed.  false: ef too large for the LDS
 inline bool hnsw_plan(HnswParams& p, bool force_global)
 {
-    const size_t fixed = hnsw_lds_fixed(p.caps);
+    const size_t fixed = hnsw_lds_fixed(p.caps, p.q_chunks);
     if (fixed > HN_LDS_BUDGET) return false;
     const size_t bitmap_bytes = (((size_t) p.n_elem + 31) / 32) * 4;
     const size_t room = HN_LDS_BUDGET - fixed;
@@ -754,7 +791,7 @@ inline bool hnsw_plan(HnswParams& p, bool force_global)
 // when it fits and the global bitmap otherwise (force_global: always).  false: ef too large for the LDS
 inline bool hnsw_plan_iterative(HnswParams& p, bool force_global)
 {
-    const size_t fixed = hnsw_lds_fixed(p.caps) + (size_t) HN_HIST * 4;
+    const size_t fixed = hnsw_lds_fixed(p.caps, p.q_chunks) + (size_t) HN_HIST * 4;
     if (fixed > HN_LDS_BUDGET) return false;
     const size_t bitmap_bytes = (((size_t) p.n_elem + 31) / 32) * 4;
     const size_t room = HN_LDS_BUDGET - fixed;
@@ -777,8 +814,9 @@ inline hipError_t launch_hnsw(const HnswParams& p, hipStream_t s)
     if (p.nq == 0) return hipSuccess;
     const size_t lds = (size_t) p.lds_per_query * p.qpb;
     if (lds > HN_LDS_BUDGET || p.qpb < 1 || p.qpb > 4) return hipErrorInvalidValue;
-    const auto kernel = ROWS == ROWS_BIT ? (ITER ? hnsw_bit_iterative_kernel : hnsw_bit_search_kernel)
-                                         : (ITER ? hnsw_iterative_kernel : hnsw_search_kernel);
+    const auto kernel = ROWS == ROWS_BIT    ? (ITER ? hnsw_bit_iterative_kernel : hnsw_bit_search_kernel)
+                        : ROWS == ROWS_HALF ? (ITER ? hnsw_half_iterative_kernel : hnsw_half_search_kernel)
+                                            : (ITER ? hnsw_iterative_kernel : hnsw_search_kernel);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         if (e != hipSuccess) return e;
@@ -791,5 +829,7 @@ inline hipError_t launch_hnsw_search(const HnswParams& p, hipStream_t s) { retur
 inline hipError_t launch_hnsw_iterative(const HnswParams& p, hipStream_t s) { return launch_hnsw<true>(p, s); }
 inline hipError_t launch_hnsw_bit_search(const HnswParams& p, hipStream_t s) { return launch_hnsw<false, ROWS_BIT>(p, s); }
 inline hipError_t launch_hnsw_bit_iterative(const HnswParams& p, hipStream_t s) { return launch_hnsw<true, ROWS_BIT>(p, s); }
+inline hipError_t launch_hnsw_half_search(const HnswParams& p, hipStream_t s) { return launch_hnsw<false, ROWS_HALF>(p, s); }
+inline hipError_t launch_hnsw_half_iterative(const HnswParams& p, hipStream_t s) { return launch_hnsw<true, ROWS_HALF>(p, s); }
 
 }  // namespace vsr

@@ -15,6 +15,7 @@ struct HnswBuildParams {
     int            metric = 0;               // M_L2 / M_IP (cosine opclass: unit rows, negative inner product)
     int            bits = 0;                 // 1: a bit corpus -- rows are stride4 16-byte chunks of packed bits, metric M_HAMMING / M_JACCARD
     const float*   row_pop = nullptr;        // bits: popcount of every row (Jaccard)
+    int            halves = 0;               // 1: a halfvec corpus -- rows are stride4 16-byte chunks of 8 binary16 values, metric M_L2 / M_IP
     uint32_t       m = 0, efc = 0, max_level = 1;
     int32_t*       nbr0 = nullptr;           // [n][2m] neighbour ids, -1 padded
     float*         dist0 = nullptr;          // [n][2m] their distances to the owner

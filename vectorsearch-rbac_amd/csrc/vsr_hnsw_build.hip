@@ -28,6 +28,11 @@
 // merging build compares rows as 16-byte chunks and serves packed bits as it stands.  Parity: pgvector's
 // test/t/020_hnsw_bit_build_recall.pl floors (tests/test_gpu_hnsw_bit.py).
 //
+// Halfvec corpora (vsr_hnsw_build_half, halfvec_l2_ops / halfvec_ip_ops / halfvec_cosine_ops): ROWS = ROWS_HALF gives hb_distances
+// K4h's lane mapping and arithmetic (half_graph_distances, vsr_halfops.h: both rows widened to fp32, fmaf sums); the inserted
+// element's row is the "query" and is binary16 already.  The pre-pass compares the binary16 bytes, so +0.0 and -0.0 differ
+// (datumIsEqual on a halfvec).  Parity: pgvector's test/t/024_hnsw_halfvec_build_recall.pl floors (tests/test_gpu_hnsw_half.py).
+//
 // Parity definition (tests/test_gpu_index.py): recall@20 at ef_search = 40 against the exact scan >= pgvector's TAP
 // thresholds on its own case (10 000 x 3-d: 0.99; inner product 0.97), and within 0.01 of that serial build's recall on
 // the same rows.
@@ -42,11 +47,12 @@
 #include "vsr_device.h"
 #include "vsr_topk.h"
 #include "vsr_bitops.h"
+#include "vsr_halfops.h"
 #include "vsr_hnsw_build.h"
 
 namespace vsr {
 
-__device__ __forceinline__ float hnsw_rank_value(int metric, float s) { return metric == M_L2 ? s : -s; }
+// (hnsw_rank_value: vsr_halfops.h)
 __device__ __forceinline__ void wave_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -74,6 +80,7 @@ __device__ __forceinline__ const float4* hb_row(const HnswBuildParams& p, I e)
 }
 
 // ROWS_BIT (a bit corpus, metric M_HAMMING / M_JACCARD): the lane mapping and arithmetic of K4b (bit_graph_distances, vsr_bitops.h)
+// ROWS_HALF (a halfvec corpus, metric M_L2 / M_IP): those of K4h (half_graph_distances, vsr_halfops.h)
 template <bool IND, int ROWS>
 __device__ __forceinline__ void hb_distances(const HnswBuildParams& p, const float4* a, const int32_t* ids, int cnt, float* out, int lane)
 {
@@ -88,6 +95,18 @@ __device__ __forceinline__ void hb_distances(const HnswBuildParams& p, const flo
             bit_graph_distances<true>(rows, p.stride4, G, er, p.row_pop, qs, qreg, p.row_pop[(size_t) (a - p.rows) / p.stride4], ids, cnt, out, lane);
         else
             bit_graph_distances<false>(rows, p.stride4, G, er, p.row_pop, qs, qreg, 0.0f, ids, cnt, out, lane);
+        wave_sync();
+        return;
+    } else if constexpr (ROWS == ROWS_HALF) {
+        // (rows are stride4 16-byte chunks of 8 binary16 values; `a` is such a row)
+        const uint32_t G = bit_graph_lanes(p.stride4), gl = (uint32_t) lane & (G - 1u);
+        const uint4* rows = reinterpret_cast<const uint4*>(p.rows);
+        const uint4* qs = reinterpret_cast<const uint4*>(a);
+        uint4 qreg = make_uint4(0u, 0u, 0u, 0u);
+        if (p.stride4 <= 64u && gl < p.stride4) qreg = qs[gl];
+        const int32_t* er = IND ? p.elem_row : nullptr;
+        if (p.metric == M_L2) half_graph_distances<true>(rows, p.stride4, G, er, qs, qreg, ids, cnt, out, lane);
+        else half_graph_distances<false>(rows, p.stride4, G, er, qs, qreg, ids, cnt, out, lane);
         wave_sync();
         return;
     } else {
@@ -440,6 +459,9 @@ hipError_t vsr_hnsw_build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sor
     if (p.bits)
         return p.elem_row ? build_batch<true, ROWS_BIT>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s)
                           : build_batch<false, ROWS_BIT>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
+    if (p.halves)
+        return p.elem_row ? build_batch<true, ROWS_HALF>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s)
+                          : build_batch<false, ROWS_HALF>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
     return p.elem_row ? build_batch<true, ROWS_F32>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s)
                       : build_batch<false, ROWS_F32>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
 }

@@ -1,5 +1,6 @@
-// vsr_hnsw_rt.hip — K4 / K4b: HNSW graph load / build / search entry points, over fp32 corpora (vsr_hnsw_*) and bit corpora
-// (vsr_hnsw_*_bit, vsr_hnsw_search_quantized*).  The only unit that compiles vsr_hnsw.h's kernels.
+// vsr_hnsw_rt.hip — K4 / K4b / K4h: HNSW graph load / build / search entry points, over fp32 corpora (vsr_hnsw_*), bit corpora
+// (vsr_hnsw_*_bit, vsr_hnsw_search_quantized*) and halfvec corpora (vsr_hnsw_load_half / vsr_hnsw_build_half, searched by the
+// float entry points).  The only unit that compiles vsr_hnsw.h's kernels.
 #include "vsr_runtime.h"
 #include "vsr_hnsw.h"
 #include "vsr_hnsw_build.h"
@@ -21,6 +22,7 @@ struct vsr_hnsw {
     DevBuf d_qb;                                     // bit index: [staged queries | their popcounts | the staging kernel's flag and seed words]
     int bit_metric = 0;                              // 0: an index over fp32 rows; VSR_METRIC_HAMMING / VSR_METRIC_JACCARD: the opclass of a
                                                      // bit index (fixed when the index is made: the graph is built for one distance)
+    bool half = false;                               // an index over a halfvec corpus (vsr_hnsw_load_half / vsr_hnsw_build_half): K4h
     PinBuf h_out, h_bm;
     int last_mode = -1;                              // visited form of the last launch (HnswVisited)
     int predicate_aware = 0;                         // vsr_hnsw_set_predicate_aware
@@ -62,10 +64,22 @@ static int hnsw_bit_opclass(const vsr_corpus* c, int metric, const char* who)
     return VSR_OK;
 }
 
-// vsr_hnsw_load (bit_metric = 0) and vsr_hnsw_load_bit (the opclass)
+// what a halfvec entry point asks of its corpus (who: the entry point)
+static int hnsw_half_opclass(const vsr_corpus* c, const char* who)
+{
+    if (!c->half) return fail(VSR_ERR_INVALID, "%s: the corpus is not a halfvec corpus", who);
+    if (c->dim > 4000)           /* HNSW_MAX_DIM * 2, hnswutils.c:1390 */
+        return fail(VSR_ERR_UNSUPPORTED, "%s: column cannot have more than 4000 dimensions for hnsw index", who);
+    return VSR_OK;
+}
+static const char* const HNSW_HALF_ENTRY =
+    "the graph of a halfvec corpus is loaded with vsr_hnsw_load_half and built with vsr_hnsw_build_half (the halfvec_l2_ops / halfvec_ip_ops / "
+    "halfvec_cosine_ops opclasses)";
+
+// vsr_hnsw_load (bit_metric = 0), vsr_hnsw_load_bit (the opclass) and vsr_hnsw_load_half (half_entry)
 static int hnsw_load(vsr_corpus* c, int bit_metric, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
                      const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
-                     int32_t n_upper, int32_t max_level, vsr_hnsw** out, const char* who)
+                     int32_t n_upper, int32_t max_level, vsr_hnsw** out, const char* who, bool half_entry = false)
 {
     if (!c || !out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
     *out = nullptr;
@@ -74,7 +88,11 @@ static int hnsw_load(vsr_corpus* c, int bit_metric, int m, int32_t n_elem, int32
         int rc = hnsw_bit_opclass(c, bit_metric, who);
         if (rc) return rc;
     }
-    if (c->half) return fail(VSR_ERR_UNSUPPORTED, "%s: a halfvec corpus has no index path yet (the halfvec_*_ops opclasses)", who);
+    if (half_entry) {
+        int rc = hnsw_half_opclass(c, who);
+        if (rc) return rc;
+    }
+    if (c->half && !half_entry) return fail(VSR_ERR_UNSUPPORTED, "%s: %s", who, HNSW_HALF_ENTRY);
     if (c->sparse) return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
     if (c->bit && !bit_metric)
         return fail(VSR_ERR_UNSUPPORTED, "%s: the graph of a bit corpus is loaded with vsr_hnsw_load_bit (the bit_hamming_ops / bit_jaccard_ops opclasses)", who);
@@ -88,6 +106,7 @@ static int hnsw_load(vsr_corpus* c, int bit_metric, int m, int32_t n_elem, int32
     std::unique_ptr<vsr_hnsw> h(new vsr_hnsw());
     h->corpus = c;
     h->bit_metric = bit_metric;
+    h->half = half_entry;
     h->n_elem = n_elem;
     h->entry = n_elem > 0 ? entry : -1;
     h->m = m;
@@ -142,12 +161,20 @@ extern "C" int vsr_hnsw_load_bit(vsr_corpus* c, int metric, int m, int32_t n_ele
     return hnsw_load(c, metric, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, out, "vsr_hnsw_load_bit");
 }
 
+extern "C" int vsr_hnsw_load_half(vsr_corpus* c, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
+                                  const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
+                                  int32_t n_upper, int32_t max_level, vsr_hnsw** out)
+{
+    return hnsw_load(c, 0, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, out, "vsr_hnsw_load_half", true);
+}
+
 // CREATE INDEX ... USING hnsw on the GPU (vsr_hnsw_build.hip): batched insertion over the corpus's rows, levels from a seeded
 // xorshift64* stream drawn once per row.  flags = 0: element e = internal row e.  VSR_HNSW_BUILD_MERGE_DUPLICATES: the
 // elements come from vsr_hnsw_dedup.hip's table.  Returns a loaded index, as vsr_hnsw_load would from the same graph.
 // bit_entry (vsr_hnsw_build_bit): the corpus is a bit corpus, metric its opclass; the kernels take the bit row format
+// half_entry (vsr_hnsw_build_half): the corpus is a halfvec corpus; the kernels take the half row format
 static int hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out, const char* who,
-                      bool bit_entry = false)
+                      bool bit_entry = false, bool half_entry = false)
 {
     if (!c || !out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
     *out = nullptr;
@@ -155,9 +182,13 @@ static int hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uin
         int rc = hnsw_bit_opclass(c, metric, who);
         if (rc) return rc;
     }
+    if (half_entry) {
+        int rc = hnsw_half_opclass(c, who);
+        if (rc) return rc;
+    }
     if (flags & ~(uint32_t) VSR_HNSW_BUILD_MERGE_DUPLICATES) return fail(VSR_ERR_INVALID, "%s: unknown flag bits 0x%x", who, flags);
     if (c->base) return fail(VSR_ERR_INVALID, "%s: the corpus is a view", who);
-    if (c->half) return fail(VSR_ERR_UNSUPPORTED, "%s: a halfvec corpus has no index path yet (the halfvec_*_ops opclasses)", who);
+    if (c->half && !half_entry) return fail(VSR_ERR_UNSUPPORTED, "%s: %s", who, HNSW_HALF_ENTRY);
     if (c->sparse) return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
     if (c->bit && !bit_entry)
         return fail(VSR_ERR_UNSUPPORTED, "%s: the graph of a bit corpus is built with vsr_hnsw_build_bit (the bit_hamming_ops / bit_jaccard_ops opclasses)", who);
@@ -171,9 +202,11 @@ static int hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uin
     const int64_t n = c->n;
     if (n > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "%s: too many rows", who);
     const bool merge = (flags & VSR_HNSW_BUILD_MERGE_DUPLICATES) != 0 && n > 0;
+    const uint32_t row_chunks = half_entry ? c->stride4 / 2 : c->stride4;    // 16-byte chunks per resident row
     std::unique_ptr<vsr_hnsw> h(new vsr_hnsw());
     h->corpus = c;
     h->bit_metric = bit_entry ? metric : 0;
+    h->half = half_entry;
     h->m = m;
     // levels: level = floor(-ln(u) * ml), ml = 1 / ln(m) (hnswutils.c:243), capped like HnswGetMaxLevel (hnsw.h:89)
     int cap = (8192 - 24 - 8 - 4 - 4) / 6 / m - 2;
@@ -225,7 +258,7 @@ static int hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uin
         HnswElemTable t;
         HB_CHK(hipMalloc(&d_row_level, (size_t) n * 4));
         HB_CHK(hipMemcpyAsync(d_row_level, level.data(), (size_t) n * 4, hipMemcpyHostToDevice, ctx->stream));
-        HB_CHK(vsr_hnsw_dedup_elements(c->d_rows, (uint32_t) n, c->stride4, hash_bits, d_row_level, &t, timing ? &times : nullptr, ctx->stream));
+        HB_CHK(vsr_hnsw_dedup_elements(c->d_rows, (uint32_t) n, row_chunks, hash_bits, d_row_level, &t, timing ? &times : nullptr, ctx->stream));
         h->d_elem_row = t.elem_row;
         h->d_tid_count = t.tid_count;
         h->d_tids = t.tids;
@@ -263,8 +296,9 @@ static int hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uin
 
     HnswBuildParams bp{};
     bp.rows = c->d_rows;
-    bp.stride4 = c->stride4;
+    bp.stride4 = row_chunks;
     bp.metric = metric == VSR_METRIC_L2 ? M_L2 : M_IP;
+    bp.halves = half_entry ? 1 : 0;
     if (bit_entry) {
         bp.bits = 1;
         bp.metric = metric == VSR_METRIC_JACCARD ? M_JACCARD : M_HAMMING;
@@ -357,6 +391,22 @@ extern "C" int vsr_hnsw_build_ex(vsr_corpus* c, int m, int ef_construction, int 
 extern "C" int vsr_hnsw_build_bit(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out)
 {
     return hnsw_build(c, m, ef_construction, metric, seed, flags, out, "vsr_hnsw_build_bit", true);
+}
+
+extern "C" int vsr_hnsw_build_half(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out)
+{
+    return hnsw_build(c, m, ef_construction, metric, seed, flags, out, "vsr_hnsw_build_half", false, true);
+}
+
+// device memory of the graph arrays of an index (the corpus is counted by vsr_corpus_device_bytes); any index.  The row format
+// of the corpus does not enter: an index over halfvec rows and one over their fp32 image loaded from the same arrays agree
+extern "C" int64_t vsr_hnsw_device_bytes(const vsr_hnsw* h)
+{
+    if (!h) return 0;
+    const size_t ne = (size_t) std::max(h->n_elem, 0);
+    const size_t words = ne * 4 /* elem_row, level, up_slot, tid_count */ + ne * 2 * (size_t) h->m + ne * 10 +
+                         (size_t) h->n_upper * (size_t) h->max_level * (size_t) h->m;
+    return (int64_t) (words * sizeof(int32_t));
 }
 
 // the arrays vsr_hnsw_load takes, back from any index (loaded or built): shapes first, then the arrays into host memory
@@ -464,7 +514,7 @@ struct HnswQueries {
 
 // One launch over queries resident in device memory, results into device arrays (out.keys: a bit index only, the raw keys of
 // the results); bitmaps: one device pointer per query (d_bm, may be nullptr).  d_status / d_vis are optional device arrays
-// (iterative: T).  The kernel is K4b when the index is over a bit corpus.
+// (iterative: T).  The kernel is K4b when the index is over a bit corpus, K4h when it is over a halfvec corpus.
 static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const HnswQueries& qs, int nq, int k, int ef, int metric,
                        const uint64_t* const* d_bm, bool force_global, const Outputs& out, int64_t* d_vis, int32_t* d_status,
                        const HnswIterLaunch* iter = nullptr)
@@ -482,6 +532,10 @@ static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const HnswQueries& qs, int nq,
         p.q_pop = qs.pop;
         p.out_keys = out.keys;
         p.key_row_offset = (uint32_t) c->row_offset;
+    }
+    if (h->half) {                                          // K4h: 16-byte chunks per row; rows past 64 chunks keep the query in LDS
+        p.stride4 = c->stride4 / 2;
+        p.q_chunks = p.stride4 > 64u ? p.stride4 : 0u;
     }
     p.dim = (uint32_t) c->dim;
     p.nq = (uint32_t) nq;
@@ -528,7 +582,7 @@ static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const HnswQueries& qs, int nq,
             uint32_t slots = env[4] == ':' ? (uint32_t) atoi(env + 5) : 4096u;
             while (slots & (slots - 1)) slots &= slots - 1;
             slots = std::max(64u, slots);
-            const size_t fixed = hnsw_lds_fixed(p.caps);
+            const size_t fixed = hnsw_lds_fixed(p.caps, p.q_chunks);
             if (fixed + (size_t) slots * 4 <= HN_LDS_BUDGET) {
                 p.vis_mode = VIS_LDS_HASH;
                 p.vis_words = slots;
@@ -550,6 +604,7 @@ static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const HnswQueries& qs, int nq,
     p.out_status = d_status;
     p.err = ctx->err_word();
     if (h->bit_metric) HIPCHK(iter ? launch_hnsw_bit_iterative(p, ctx->stream) : launch_hnsw_bit_search(p, ctx->stream));
+    else if (h->half) HIPCHK(iter ? launch_hnsw_half_iterative(p, ctx->stream) : launch_hnsw_half_search(p, ctx->stream));
     else if (iter) HIPCHK(launch_hnsw_iterative(p, ctx->stream));
     else HIPCHK(launch_hnsw_search(p, ctx->stream));
     h->last_mode = p.vis_mode;
@@ -575,6 +630,18 @@ static int hnsw_check(vsr_hnsw* h, const void* queries, int nq, int dim, int k, 
     if (metric == VSR_METRIC_L1) return fail(VSR_ERR_UNSUPPORTED, "%s: L1 graphs are not supported", who);
     if (ef < 1 || ef > 5000)      /* hnsw.ef_search: 1 .. HNSW_MAX_EF_SEARCH (hnsw.c:86-89, hnsw.h:44) */
         return fail(VSR_ERR_INVALID, "%s: ef_search must be between 1 and 5000 (got %d)", who, ef);
+    return VSR_OK;
+}
+
+// The host entry points over halfvec rows refuse what `$1::halfvec` refuses (halfutils.h:146-261: a finite value that rounds
+// to +-Inf), as vsr_search does; the device entry points do not look
+static int half_query_range(const void* queries, int nq, int dim)
+{
+    const float* q = static_cast<const float*>(queries);
+    const size_t total = (size_t) nq * (size_t) dim;
+    for (size_t i = 0; i < total; ++i)
+        if (std::isfinite(q[i]) && std::fabs(q[i]) >= 65520.0f)
+            return fail(VSR_ERR_INVALID, "\"%.9g\" is out of range for type halfvec", (double) q[i]);
     return VSR_OK;
 }
 
@@ -734,6 +801,7 @@ static int hnsw_search_host(const HnswEntry& en, vsr_hnsw* h, const void* querie
     if (rc) return rc;
     if (nq == 0) return VSR_OK;
     if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", en.who);
+    if (h->half && (rc = half_query_range(queries, nq, dim))) return rc;
     vsr_ctx* ctx = h->corpus->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     // tier 1: queries whose LDS visited table overflowed (big graphs only) are re-run with the global bitmap
@@ -868,6 +936,7 @@ static int hnsw_iterative_host(const HnswEntry& en, vsr_hnsw* h, const void* que
         return hnsw_search_host(en, h, queries, nq, dim, k, ef, metric, filters, out_blk, out_doc, out_row, out_dist, out_cnt, out_tuples);
     if (nq == 0) return VSR_OK;
     if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", en.who);
+    if (h->half && (rc = half_query_range(queries, nq, dim))) return rc;
     vsr_ctx* ctx = h->corpus->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     // tier 1: queries whose D overflowed, again with room for every element (an element is in at most one of D, W, emitted)
@@ -975,12 +1044,7 @@ extern "C" int vsr_hnsw_search_quantized(vsr_corpus* src, vsr_hnsw* h, const flo
     if (rc) return rc;
     if (nq == 0) return VSR_OK;
     if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", who);
-    if (src->half) {                                        // `$1::halfvec`, as vsr_search refuses it
-        const size_t total = (size_t) nq * (size_t) dim;
-        for (size_t i = 0; i < total; ++i)
-            if (std::isfinite(queries[i]) && std::fabs(queries[i]) >= 65520.0f)
-                return fail(VSR_ERR_INVALID, "\"%.9g\" is out of range for type halfvec", (double) queries[i]);
-    }
+    if (src->half && (rc = half_query_range(queries, nq, dim))) return rc;     // `$1::halfvec`, as vsr_search refuses it
     vsr_ctx* ctx = h->corpus->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     const ResultBlock rb(nq, k, false);                     // results and stage 1's status words: one packed copy back, one wait

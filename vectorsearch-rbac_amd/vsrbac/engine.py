@@ -494,6 +494,19 @@ class Corpus:
         "jaccard"; the index then answers HnswIndex.search_bit* with that metric only."""
         return HnswIndex(self, graph, bit_metric=_metric(metric))
 
+    def build_hnsw_half(self, m=16, ef_construction=64, metric="l2", seed=1, merge_duplicates=False):
+        """CREATE INDEX ... USING hnsw (col halfvec_l2_ops | halfvec_ip_ops | halfvec_cosine_ops) over this halfvec corpus
+        (vsr_hnsw_build_half): build_hnsw's batched insertion on the binary16 rows.  merge_duplicates: rows whose binary16 bytes
+        are identical share an element.  The index answers HnswIndex.search* like any float index."""
+        h = C.c_void_p()
+        check(self._lib.vsr_hnsw_build_half(self._h, int(m), int(ef_construction), _metric(metric), int(seed),
+                                            BUILD_MERGE_DUPLICATES if merge_duplicates else 0, C.byref(h)))
+        return HnswIndex(self, h)
+
+    def load_hnsw_half(self, graph):
+        """load_hnsw over this halfvec corpus (vsr_hnsw_load_half): the graph kernels read the binary16 rows themselves."""
+        return HnswIndex(self, graph, half=True)
+
     # ---- search ------------------------------------------------------------------------------
     def pack_filters(self, filters):
         """One filter per query as a reusable C array (build it once when the same batch shape repeats)."""
@@ -767,7 +780,7 @@ class IvfIndex:
 class HnswIndex:
     """pgvector's hnsw scan (hnswscan.c) on the GPU: greedy descent, ef_search beam on layer 0, TIDs, filter, LIMIT."""
 
-    def __init__(self, corpus, g, bit_metric=None):
+    def __init__(self, corpus, g, bit_metric=None, half=False):
         self.corpus, self._lib = corpus, corpus._lib
         if isinstance(g, C.c_void_p):                # a handle vsr_hnsw_build* returned (Corpus.build_hnsw, build_hnsw_bit)
             self._h = g
@@ -781,6 +794,10 @@ class HnswIndex:
             check(self._lib.vsr_hnsw_load_bit(corpus._h, int(bit_metric), int(g["m"]), level.size, int(g["entry"]), _ptr(level),
                                               _ptr(nbr0), _ptr(tc), _ptr(tids), _ptr(up_slot), _ptr(up_nbr), n_upper,
                                               int(g["max_level"]), C.byref(h)))
+        elif half:                                   # Corpus.load_hnsw_half
+            check(self._lib.vsr_hnsw_load_half(corpus._h, int(g["m"]), level.size, int(g["entry"]), _ptr(level), _ptr(nbr0),
+                                               _ptr(tc), _ptr(tids), _ptr(up_slot), _ptr(up_nbr), n_upper, int(g["max_level"]),
+                                               C.byref(h)))
         else:
             check(self._lib.vsr_hnsw_load(corpus._h, int(g["m"]), level.size, int(g["entry"]), _ptr(level), _ptr(nbr0), _ptr(tc),
                                           _ptr(tids), _ptr(up_slot), _ptr(up_nbr), n_upper, int(g["max_level"]), C.byref(h)))
@@ -808,6 +825,10 @@ class HnswIndex:
         v = [C.c_int32() for _ in range(4)]
         check(self._lib.vsr_hnsw_info(self._h, *[C.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
+
+    def device_bytes(self):
+        """Device memory of the graph arrays in bytes (vsr_hnsw_device_bytes); the corpus: Corpus.device_bytes."""
+        return int(self._lib.vsr_hnsw_device_bytes(self._h))
 
     def export(self):
         """The graph as the dict Corpus.load_hnsw takes (vsr_hnsw_export): level, nbr0 [n_elem][2m], tid_count,
