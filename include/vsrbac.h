@@ -112,8 +112,9 @@ int vsr_corpus_load(vsr_ctx* ctx, const float* rows, int64_t n, int dim,
  * vsr_set_screening(ctx, 0) keeps every search on that kernel; vsr_set_query_hint has no effect.  Non-finite rows are accepted as for fp32 (pgvector rejects them on input): NaN
  * distances sort last.  The HNSW opclasses halfvec_l2_ops / halfvec_ip_ops / halfvec_cosine_ops are vsr_hnsw_load_half /
  * vsr_hnsw_build_half below, searched by the float vsr_hnsw_search* entry points (K4h); vsr_hnsw_load and vsr_hnsw_build* over
- * such a corpus keep answering VSR_ERR_UNSUPPORTED, the message names the halfvec corpus and those entry points.  vsr_ivf_load and
- * vsr_ivf_assign over such a corpus: VSR_ERR_UNSUPPORTED (IVFFlat over halfvec is not built yet). */
+ * such a corpus keep answering VSR_ERR_UNSUPPORTED, the message names the halfvec corpus and those entry points.  The IVFFlat
+ * opclasses are vsr_ivf_kmeans_half / vsr_ivf_assign_half / vsr_ivf_load_half below (K3h); vsr_ivf_load and vsr_ivf_assign over such
+ * a corpus keep answering VSR_ERR_UNSUPPORTED, the message names the halfvec corpus and the _half entry points. */
 int vsr_corpus_load_half(vsr_ctx* ctx, const uint16_t* rows, int64_t n, int dim,
                          const int64_t* block_ids, const int32_t* doc_ids, int64_t row_offset,
                          vsr_corpus** out);
@@ -436,6 +437,44 @@ int vsr_ivf_search_iterative_device(vsr_ivf* ivf, const float* d_queries, int nq
                                     int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
                                     int32_t* d_out_counts, int32_t* d_out_probes);
 
+/* device memory of an index in bytes (the corpus: vsr_corpus_device_bytes).  Any index.  Counted: the list-ordered view's rows,
+ * norms and rank map (and its screening planes where the fp32 corpus has them), the centres, the list offsets.  Not counted: what
+ * is cached per filter (bitmaps in view order, per-list parts) and the lists' tile lists, as vsr_hnsw_device_bytes leaves out its
+ * per-filter bitmaps. */
+int64_t vsr_ivf_device_bytes(const vsr_ivf* ivf);
+
+/* ---- IVFFlat over a halfvec corpus: halfvec_l2_ops / halfvec_ip_ops / halfvec_cosine_ops (ivfflat_halfvec_support, ivfutils.c:
+ * 266-276, 305-314, 349-361; test/sql/ivfflat_halfvec.sql, test/t/032_ivfflat_halfvec_build_recall.pl) -----------------------------
+ * vsr_ivf_kmeans_half, vsr_ivf_assign_half and vsr_ivf_load_half are vsr_ivf_kmeans, vsr_ivf_assign and vsr_ivf_load with every
+ * float array -- samples, centres -- as binary16 bit patterns; vsr_ivf_load_half returns an index that EVERY float entry point above
+ * takes: vsr_ivf_probe, vsr_ivf_search, vsr_ivf_search_device, vsr_ivf_search_iterative(_device), metric per call (L2, inner
+ * product, cosine over unit rows rounded to binary16; L1: VSR_ERR_UNSUPPORTED, as for fp32 indexes).  The list-ordered image holds
+ * the rows as the corpus does, 2 bytes per element, and the centres stay binary16 (K3h): no fp32 image of rows or centres exists on
+ * the device, and vsr_ivf_device_bytes is about half that of the fp32 index over the widened rows (a quarter where that one
+ * carries screening planes).
+ *   - Centres are halfvec values.  A centre distance is the fp32 sum in element order, without contraction, of the widened centre
+ *     against the query rounded to binary16 (Float4ToHalf, round to nearest even) and widened: what `$1::halfvec` computes
+ *     (halfutils.c:27-40, 79-90).  Queries stay const float*; the probe and the iterative scan round as they load.  The assignment
+ *     reads the corpus's binary16 rows where they lie.  Equal distances go to the lower list id.
+ *   - Rows rank inside the lists exactly as vsr_search ranks a halfvec corpus.
+ *   - k-means (vsr_ivf_kmeans_half): pgvector's for the type.  Sums and distances run in fp32 over the widened samples, and every
+ *     value stored into a centre is rounded to binary16 (HalfvecUpdateCenter): the means, the random fill of an empty centre and of
+ *     the no-sample case, the quotients of halfvec_l2_normalize (norm in double over the widened elements; overflow is looked for
+ *     in the binary16 result).  Same seed and samples => the same centres as the float build with those roundings.
+ *   - The host entry points refuse a finite query element that rounds to +-Inf (|v| >= 65520) with VSR_ERR_INVALID,
+ *     `"<v>" is out of range for type halfvec`, as vsr_search does; the device entry points do not look.  A dimension mismatch is
+ *     VSR_ERR_DIM_MISMATCH, "different halfvec dimensions %d and %d".
+ *   - A corpus that is not a halfvec corpus: VSR_ERR_INVALID, "the corpus is not a halfvec corpus".  vsr_ivf_load / vsr_ivf_assign
+ *     keep refusing a halfvec corpus (VSR_ERR_UNSUPPORTED, the message names the halfvec corpus and these entry points).
+ *   - Everything else is the fp32 index's, unchanged: lists 1 .. 32768, probes, max_probes, the modes, the outputs, the prefix
+ *     property, out_probes, filters, caller order against storage order, empty lists, n = 0, vsr_ivf_free.
+ * The guarantee of the build is recall (032_ivfflat_halfvec_build_recall.pl's floors).  halfvec_l1_ops is not built. */
+int vsr_ivf_load_half(vsr_corpus* half_corpus, const uint16_t* centers /* [lists][dim] binary16 bits */, int lists,
+                      const int32_t* row_list, vsr_ivf** out);
+int vsr_ivf_assign_half(vsr_corpus* half_corpus, const uint16_t* centers, int lists, int metric, int32_t* out_row_list);
+int vsr_ivf_kmeans_half(vsr_ctx* ctx, int metric, int dim, const uint16_t* samples, int64_t n_samples, int lists, uint64_t seed,
+                        uint16_t* out_centers, int* out_iterations);
+
 /* ---- HNSW graph search (pgvector/src/hnswscan.c:15-45,179-316; hnswutils.c:813-976) -------------------------- */
 /* A graph as pgvector's in-memory build leaves it (hnswbuild.c:357-470): n_elem elements, each with a top level, up to 10
  * heap TIDs (tids: caller row indices, -1 padded; identical vectors share an element), 2m neighbours on layer 0
@@ -565,7 +604,7 @@ int64_t vsr_hnsw_device_bytes(const vsr_hnsw* index);
  *     and both re-runs, vsr_hnsw_export*, vsr_hnsw_info, vsr_hnsw_free, filters, row_offset, up to 10 TIDs per element.
  * The merging build (VSR_HNSW_BUILD_MERGE_DUPLICATES) keeps vsr_hnsw_build_ex's grouping contract; identical means the binary16
  * bytes are identical, so +0.0 and -0.0 differ: datumIsEqual on a halfvec.  The guarantee is recall, as for the float build
- * (024_hnsw_halfvec_build_recall.pl's floor, 0.98 for all three opclasses).  halfvec_l1_ops and IVFFlat over halfvec are not built. */
+ * (024_hnsw_halfvec_build_recall.pl's floor, 0.98 for all three opclasses).  halfvec_l1_ops is not built. */
 int vsr_hnsw_load_half(vsr_corpus* half_corpus, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
                        const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
                        int32_t n_upper, int32_t max_level, vsr_hnsw** out);

@@ -464,8 +464,10 @@ hipError_t launch_gather_class_view(const uint4* src, const float* src_norm, uin
                                     float* dst_norm, hipStream_t s);
 hipError_t launch_view_bitmap(const uint32_t* rank, uint32_t n_rows, const uint2* tiles, uint32_t n_tiles, const uint64_t* bitmap,
                               uint64_t* out, hipStream_t s);
-hipError_t launch_ivf_probe(const float* queries, uint32_t q_stride, uint32_t nq, const float* centers_t /* [dim][lists] */, int dim, int lists, int probes,
-                            int metric, int32_t* out, hipStream_t s);
+// form: IVF_F32 (fp32 queries and centres), IVF_HALF_Q32 / IVF_HALF_ROW (binary16 centres; fp32 queries rounded on load / binary16
+// rows in place): vsr_exact.h.  q_stride counts elements of the query side's type.
+hipError_t launch_ivf_probe(const void* queries, uint32_t q_stride, uint32_t nq, const void* centers_t /* [dim][lists] */, int dim, int lists, int probes,
+                            int metric, int32_t* out, hipStream_t s, int form = 0);
 hipError_t launch_vector_fn(int mode, const float* a, const float* b, int64_t n, int dim, int b_broadcast, double* out_d,
                             float* out_f, int* overflow, hipStream_t s);
 hipError_t launch_merge_lists(const uint64_t* keys, const int64_t* blocks, const int32_t* docs, const float* dist,

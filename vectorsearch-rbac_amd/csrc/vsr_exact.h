@@ -6,6 +6,8 @@
 #pragma once
 #include "vsr_topk.h"
 
+#include <type_traits>
+
 namespace vsr {
 
 __device__ __forceinline__ float output_distance(int metric, float v)
@@ -107,17 +109,36 @@ __device__ __forceinline__ float exact_rank_value(int metric, float s, float nx,
 // centers_t[j][c]: the centres TRANSPOSED (element j of all lists contiguous), so that the 64 lanes of a wave -- one centre
 // each -- read 256 contiguous bytes per element instead of 64 lines 4 * dim bytes apart; every lane adds its own centre's
 // terms in element order, in the order and rounding of vector.c's loops compiled without contraction.
-__device__ __forceinline__ uint32_t ivf_center_key(const float* centers_t, int lists, int dim, int c, const float* q, int metric)
+//
+// FORM says what the two sides hold (K3h: the halfvec opclasses, halfutils.c:27-40, 79-90 on the widened values):
+//   IVF_F32      fp32 centres, fp32 query: the vector opclasses;
+//   IVF_HALF_Q32 binary16 centres (a wave's element step is 128 contiguous bytes), an fp32 query whose every element is rounded
+//                to binary16 (Float4ToHalf, nearest even) as it is loaded and widened again: `$1::halfvec` (probe, iterative scan);
+//   IVF_HALF_ROW binary16 centres, the query is a binary16 row read in place (the build's assignment over a halfvec corpus).
+// The two half forms run the same fp32 sequence on the same widened values: a (query, centre) pair has one key.
+enum { IVF_F32 = 0, IVF_HALF_Q32 = 1, IVF_HALF_ROW = 2 };
+
+template <int FORM>
+__device__ __forceinline__ float ivf_query_element(const void* q, int j)
 {
-    const float* x = centers_t + c;
+    if constexpr (FORM == IVF_F32) return static_cast<const float*>(q)[j];
+    else if constexpr (FORM == IVF_HALF_Q32) return (float) (_Float16) static_cast<const float*>(q)[j];
+    else return (float) static_cast<const _Float16*>(q)[j];
+}
+
+template <int FORM = IVF_F32>
+__device__ __forceinline__ uint32_t ivf_center_key(const void* centers_t, int lists, int dim, int c, const void* q, int metric)
+{
+    using CT = typename std::conditional<FORM == IVF_F32, float, _Float16>::type;
+    const CT* x = static_cast<const CT*>(centers_t) + c;
     float sum = 0.0f;
     if (metric == M_L2) {
         for (int j = 0; j < dim; ++j) {
-            const float d = __fsub_rn(x[(size_t) j * lists], q[j]);
+            const float d = __fsub_rn((float) x[(size_t) j * lists], ivf_query_element<FORM>(q, j));
             sum = __fadd_rn(sum, __fmul_rn(d, d));
         }
     } else {
-        for (int j = 0; j < dim; ++j) sum = __fadd_rn(sum, __fmul_rn(x[(size_t) j * lists], q[j]));
+        for (int j = 0; j < dim; ++j) sum = __fadd_rn(sum, __fmul_rn((float) x[(size_t) j * lists], ivf_query_element<FORM>(q, j)));
         sum = -sum;
     }
     return mono_bits(sum);

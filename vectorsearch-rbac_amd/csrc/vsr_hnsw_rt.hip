@@ -634,8 +634,8 @@ static int hnsw_check(vsr_hnsw* h, const void* queries, int nq, int dim, int k, 
 }
 
 // The host entry points over halfvec rows refuse what `$1::halfvec` refuses (halfutils.h:146-261: a finite value that rounds
-// to +-Inf), as vsr_search does; the device entry points do not look
-static int half_query_range(const void* queries, int nq, int dim)
+// to +-Inf), as vsr_search does; the device entry points do not look.  (Also the IVFFlat entry points': vsr_ivf.hip.)
+int vsr::half_query_range(const void* queries, int nq, int dim)
 {
     const float* q = static_cast<const float*>(queries);
     const size_t total = (size_t) nq * (size_t) dim;

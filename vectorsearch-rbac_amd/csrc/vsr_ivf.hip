@@ -1,4 +1,5 @@
 // vsr_ivf.hip — K3: IVFFlat over a list-ordered view of the corpus (probe, per-list filter parts, assignment).
+// K3h: the same over a halfvec corpus (the _half entry points): binary16 rows in the view, binary16 centres, nothing widened.
 #include "vsr_runtime.h"
 #include "vsr_ivf_iter.h"
 
@@ -11,21 +12,22 @@ hipError_t launch_ivf_iterative(const IvfIterParams& p, uint32_t nq, hipStream_t
     const size_t lds = ivf_iter_lds_bytes(p.lists, p.stride4, p.k);
     // 160 KiB of LDS per CU; view rows are addressed in 32 bits with a step of 256 to spare
     if (lds > 160 * 1024 || p.k < 1 || p.k > (uint32_t) MAX_K || p.n_rows > 0xFFFFFE00u) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_iterative_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+    auto* kernel = p.rows_half ? ivf_iterative_kernel<true> : ivf_iterative_kernel<false>;
+    if (lds > 64 * 1024) {                                 // (per instantiation: each is a kernel of its own)
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(ivf_iterative_kernel, dim3(nq), dim3(256), lds, s, p);
+    hipLaunchKernelGGL(kernel, dim3(nq), dim3(256), lds, s, p);
     return hipGetLastError();
 }
 }  // namespace vsr
 
 // ---- K3: IVFFlat list probe (ivfscan.c:36-176, 339-389) over a list-ordered view of the corpus
 // [lists][dim] -> [dim][lists]: the layout ivf_probe_kernel reads (vsr_kernels.hip)
-static std::vector<float> transpose_centers(const float* centers, int lists, int dim)
+// (T = float, or uint16_t: the binary16 centres of a halfvec index)
+template <class T> static std::vector<T> transpose_centers(const T* centers, int lists, int dim)
 {
-    std::vector<float> t((size_t) lists * dim);
+    std::vector<T> t((size_t) lists * dim);
     for (int c = 0; c < lists; ++c)
         for (int j = 0; j < dim; ++j) t[(size_t) j * lists + c] = centers[(size_t) c * dim + j];
     return t;
@@ -35,7 +37,8 @@ struct vsr_ivf {
     vsr_corpus* main = nullptr;
     vsr_corpus* view = nullptr;                      // list-ordered rows; view->base = main
     int         lists = 0;
-    float*      d_centers = nullptr;
+    bool        half = false;                        // vsr_ivf_load_half: binary16 rows (the view's) and binary16 centres (K3h)
+    void*       d_centers = nullptr;                 // [dim][lists] fp32, or binary16 when half
     std::vector<uint32_t> list_start;                // lists + 1 offsets into the view
     std::vector<vsr_filter*> list_filters;           // one RANGES filter per list (tiles over the view)
     struct ViewBitmap { uint64_t* d = nullptr; std::vector<uint64_t> h; };
@@ -73,24 +76,40 @@ extern "C" int vsr_ivf_free(vsr_ivf* ivf)
     return VSR_OK;
 }
 
-extern "C" int vsr_ivf_load(vsr_corpus* c, const float* centers, int lists, const int32_t* row_list, vsr_ivf** out)
+// what vsr_ivf_load / vsr_ivf_assign and their _half forms refuse alike (half_entry: the caller is a _half entry point)
+static int ivf_check_corpus(const vsr_corpus* c, bool half_entry, int lists, const char* who)
 {
-    if (!c || !out || !centers || (c->n > 0 && !row_list)) return fail(VSR_ERR_INVALID, "vsr_ivf_load: NULL argument");
-    *out = nullptr;
-    if (c->base) return fail(VSR_ERR_INVALID, "vsr_ivf_load: the corpus is itself a view");
-    if (c->half) return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_load: a halfvec corpus has no index path yet (the halfvec_*_ops opclasses)");
-    if (c->sparse) return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_load: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)");
-    if (c->bit) return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_load: a bit corpus has no index path yet (the bit_hamming_ops / bit_jaccard_ops opclasses)");
+    if (c->base) return fail(VSR_ERR_INVALID, "%s: the corpus is a view", who);
+    if (half_entry && !c->half) return fail(VSR_ERR_INVALID, "%s: the corpus is not a halfvec corpus", who);
+    if (c->half && !half_entry)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: a halfvec corpus is indexed with vsr_ivf_kmeans_half / vsr_ivf_assign_half / vsr_ivf_load_half "
+                    "(the halfvec_*_ops opclasses)", who);
+    if (c->sparse) return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
+    if (c->bit) return fail(VSR_ERR_UNSUPPORTED, "%s: a bit corpus has no index path yet (the bit_hamming_ops / bit_jaccard_ops opclasses)", who);
     if (lists < 1 || lists > 32768)      /* reloption lists: 1 .. IVFFLAT_MAX_LISTS (ivfflat.h:42-44) */
-        return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_load: lists must be between 1 and 32768 (got %d)", lists);
+        return fail(VSR_ERR_UNSUPPORTED, "%s: lists must be between 1 and 32768 (got %d)", who, lists);
+    return VSR_OK;
+}
+
+// vsr_ivf_load (T = float) and vsr_ivf_load_half (T = uint16_t: binary16 centres over a halfvec corpus, K3h).  The half view
+// holds the rows as the corpus does, stride4 / 2 chunks of 8 binary16 values, and no planes: nothing is widened.
+template <class T>
+static int ivf_load(vsr_corpus* c, const T* centers, int lists, const int32_t* row_list, vsr_ivf** out, const char* who)
+{
+    constexpr bool HALF = std::is_same<T, uint16_t>::value;
+    if (!c || !out || !centers || (c->n > 0 && !row_list)) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    int rc = ivf_check_corpus(c, HALF, lists, who);
+    if (rc) return rc;
     vsr_ctx* ctx = c->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     const int64_t n = c->n;
     for (int64_t i = 0; i < n; ++i)
-        if (row_list[i] < 0 || row_list[i] >= lists) return fail(VSR_ERR_INVALID, "vsr_ivf_load: row %lld has list %d", (long long) i, row_list[i]);
+        if (row_list[i] < 0 || row_list[i] >= lists) return fail(VSR_ERR_INVALID, "%s: row %lld has list %d", who, (long long) i, row_list[i]);
     std::unique_ptr<vsr_ivf> ivf(new vsr_ivf());
     ivf->main = c;
     ivf->lists = lists;
+    ivf->half = HALF;
     // view order: by list, then by base row (= (document_id, block_id) order inside a list)
     std::vector<uint32_t> count((size_t) lists + 1, 0);
     for (int64_t r = 0; r < n; ++r) count[(size_t) row_list[c->h_orig[(size_t) r]] + 1]++;
@@ -110,12 +129,15 @@ extern "C" int vsr_ivf_load(vsr_corpus* c, const float* centers, int lists, cons
     v->shape = c->shape;
     v->base = c;
     v->k2_safe = c->k2_safe;
-    const size_t alloc_rows = (size_t) std::max<int64_t>(n, 1), row_bytes = (size_t) c->stride4 * 16;
+    v->half = HALF;
+    // 16-byte chunks per stored row: a halfvec row is stride4 / 2 chunks of 8 halves (the gather moves chunks, whatever they hold)
+    const uint32_t row_chunks = HALF ? c->stride4 / 2 : c->stride4;
+    const size_t alloc_rows = (size_t) std::max<int64_t>(n, 1), row_bytes = (size_t) row_chunks * 16;
     HIPCHK(hipMalloc(&v->d_rank, alloc_rows * sizeof(uint32_t)));
     HIPCHK(hipMemcpy(v->d_rank, rank.data(), alloc_rows * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIPCHK(hipMalloc(&v->d_rows, alloc_rows * row_bytes + 1024));
     HIPCHK(hipMalloc(&v->d_norm2, alloc_rows * sizeof(float)));
-    HIPCHK(launch_gather_rows(c->d_rows, c->d_norm2, v->d_rank, (uint32_t) n, c->stride4, v->d_rows, v->d_norm2, ctx->stream));
+    HIPCHK(launch_gather_rows(c->d_rows, c->d_norm2, v->d_rank, (uint32_t) n, row_chunks, v->d_rows, v->d_norm2, ctx->stream));
     if (c->d_scr) {                                  // the view's own screening planes, in its order
         v->scr_has_mid = c->scr_has_mid;
         v->pstride4 = c->pstride4;
@@ -126,10 +148,10 @@ extern "C" int vsr_ivf_load(vsr_corpus* c, const float* centers, int lists, cons
         HIPCHK(hipMalloc(&v->d_all_tiles, std::max<size_t>(8, all.size() * sizeof(uint2))));
         if (!all.empty()) HIPCHK(hipMemcpy(v->d_all_tiles, all.data(), all.size() * sizeof(uint2), hipMemcpyHostToDevice));
     }
-    HIPCHK(hipMalloc(&ivf->d_centers, (size_t) lists * c->dim * sizeof(float)));
+    HIPCHK(hipMalloc(&ivf->d_centers, (size_t) lists * c->dim * sizeof(T)));
     {                                                       // transposed for the probe kernel: element j of every list contiguous
-        std::vector<float> ct = transpose_centers(centers, lists, c->dim);
-        HIPCHK(hipMemcpy(ivf->d_centers, ct.data(), ct.size() * sizeof(float), hipMemcpyHostToDevice));
+        std::vector<T> ct = transpose_centers(centers, lists, c->dim);
+        HIPCHK(hipMemcpy(ivf->d_centers, ct.data(), ct.size() * sizeof(T), hipMemcpyHostToDevice));
     }
     HIPCHK(hipMalloc(&ivf->d_list_start, ((size_t) lists + 1) * sizeof(uint32_t)));
     HIPCHK(hipMemcpy(ivf->d_list_start, ivf->list_start.data(), ((size_t) lists + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -149,6 +171,28 @@ extern "C" int vsr_ivf_load(vsr_corpus* c, const float* centers, int lists, cons
     c->ivf_indexes.push_back(ivf.get());
     *out = ivf.release();
     return VSR_OK;
+}
+
+extern "C" int vsr_ivf_load(vsr_corpus* c, const float* centers, int lists, const int32_t* row_list, vsr_ivf** out)
+{
+    return ivf_load(c, centers, lists, row_list, out, "vsr_ivf_load");
+}
+
+extern "C" int vsr_ivf_load_half(vsr_corpus* c, const uint16_t* centers, int lists, const int32_t* row_list, vsr_ivf** out)
+{
+    return ivf_load(c, centers, lists, row_list, out, "vsr_ivf_load_half");
+}
+
+// the view's rows, norms and rank, the centres and the list offsets (cached per-filter bitmaps and tile lists are not counted)
+extern "C" int64_t vsr_ivf_device_bytes(const vsr_ivf* ivf)
+{
+    if (!ivf) return 0;
+    const vsr_corpus* v = ivf->view;
+    const size_t rows = (size_t) std::max<int64_t>(v->n, 1);
+    size_t b = rows * (v->half ? v->stride4 / 2 : v->stride4) * 16 + 1024 + rows * sizeof(float) + rows * sizeof(uint32_t);
+    if (v->d_scr) b += rows * (size_t) v->pstride4 * 16 + 1024;
+    b += (size_t) ivf->lists * v->dim * (ivf->half ? 2 : 4) + ((size_t) ivf->lists + 1) * sizeof(uint32_t);
+    return (int64_t) b;
 }
 
 void vsr::purge_ivf_caches(vsr_corpus* c, const vsr_filter* f)
@@ -235,7 +279,8 @@ static int ivf_probe_lists(vsr_ivf* ivf, const float* d_queries, int nq, int dim
     // cosine opclass: the caller passes normalised queries and the index distance is the negative inner product
     // (vector.sql:323-327)
     HIPCHK(launch_ivf_probe(d_queries, (uint32_t) dim, (uint32_t) nq, ivf->d_centers, dim, ivf->lists, probes,
-                            metric == VSR_METRIC_L2 ? M_L2 : M_IP, ivf->d_probe.as<int32_t>(), ctx->stream));
+                            metric == VSR_METRIC_L2 ? M_L2 : M_IP, ivf->d_probe.as<int32_t>(), ctx->stream,
+                            ivf->half ? IVF_HALF_Q32 : IVF_F32));
     HIPCHK(hipMemcpyAsync(out_lists, ivf->d_probe.p, (size_t) nq * probes * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return VSR_OK;
@@ -307,6 +352,7 @@ extern "C" int vsr_ivf_search(vsr_ivf* ivf, const float* queries, int nq, int di
 {
     int rc = ivf_check(ivf, queries, nq, dim, k, probes, metric, filters, out_blk, out_dist, out_cnt, "vsr_ivf_search");
     if (rc || nq == 0) return rc;
+    if (ivf->half && (rc = half_query_range(queries, nq, dim))) return rc;     // `$1::halfvec`, as vsr_search refuses it
     vsr_ctx* ctx = ivf->main->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     if ((rc = ivf->d_q.reserve((size_t) nq * dim * sizeof(float)))) return rc;
@@ -390,6 +436,7 @@ extern "C" int vsr_ivf_search_iterative_device(vsr_ivf* ivf, const float* d_quer
     p.k = (uint32_t) k;
     p.list_start = ivf->d_list_start;
     p.rows = v->d_rows;
+    p.rows_half = ivf->half ? 1u : 0u;
     p.stride4 = v->stride4;
     p.n_rows = (uint32_t) v->n;
     p.rank = v->d_rank;
@@ -418,6 +465,7 @@ extern "C" int vsr_ivf_search_iterative(vsr_ivf* ivf, const float* queries, int 
         if (out_probes) std::fill(out_probes, out_probes + nq, (int32_t) probes);
         return VSR_OK;
     }
+    if (ivf->half && (rc = half_query_range(queries, nq, dim))) return rc;
     vsr_ctx* ctx = ivf->main->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     // queries up, the device form, results down
@@ -441,9 +489,14 @@ extern "C" int vsr_ivf_search_iterative(vsr_ivf* ivf, const float* queries, int 
 extern "C" int vsr_ivf_probe(vsr_ivf* ivf, const float* queries, int nq, int dim, int probes, int metric, int32_t* out_lists)
 {
     if (!ivf || !queries || !out_lists || nq < 0) return fail(VSR_ERR_INVALID, "vsr_ivf_probe: NULL argument");
-    if (dim != ivf->main->dim) return fail(VSR_ERR_DIM_MISMATCH, "different vector dimensions %d and %d", ivf->main->dim, dim);
+    if (dim != ivf->main->dim)
+        return fail(VSR_ERR_DIM_MISMATCH, "different %s dimensions %d and %d", ivf->half ? "halfvec" : "vector", ivf->main->dim, dim);
     if (probes < 1) return fail(VSR_ERR_INVALID, "vsr_ivf_probe: probes must be >= 1 (got %d)", probes);
     if (nq == 0) return VSR_OK;
+    if (ivf->half) {
+        int rr = half_query_range(queries, nq, dim);
+        if (rr) return rr;
+    }
     probes = std::min(probes, ivf->lists);
     vsr_ctx* ctx = ivf->main->ctx;
     HIPCHK(hipSetDevice(ctx->device));
@@ -456,33 +509,42 @@ extern "C" int vsr_ivf_probe(vsr_ivf* ivf, const float* queries, int nq, int dim
 // Index build, the part that touches every row (ivfbuild.c:141-227: InsertTuple finds the nearest list of each heap
 // row): all corpus rows against the centres, in the index's arithmetic, on the GPU.  The k-means that produces the
 // centres from the sampled rows (ivfbuild.c:404-445 ComputeCenters, ivfkmeans.c) is vsr_ivf_kmeans (vsr_kmeans.hip).
-extern "C" int vsr_ivf_assign(vsr_corpus* c, const float* centers, int lists, int metric, int32_t* out_row_list)
+// (T = uint16_t, vsr_ivf_assign_half: binary16 centres against the binary16 rows where they lie -- a stored row holds stride4 * 4
+// elements in either format -- and no widened copy of the corpus.)
+template <class T>
+static int ivf_assign(vsr_corpus* c, const T* centers, int lists, int metric, int32_t* out_row_list, const char* who)
 {
-    if (!c || !centers || (c->n > 0 && !out_row_list)) return fail(VSR_ERR_INVALID, "vsr_ivf_assign: NULL argument");
-    if (c->base) return fail(VSR_ERR_INVALID, "vsr_ivf_assign: the corpus is a view");
-    if (c->half) return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_assign: a halfvec corpus has no index path yet (the halfvec_*_ops opclasses)");
-    if (c->sparse) return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_assign: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)");
-    if (c->bit) return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_assign: a bit corpus has no index path yet (the bit_hamming_ops / bit_jaccard_ops opclasses)");
-    if (lists < 1 || lists > 32768) return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_assign: lists must be between 1 and 32768 (got %d)", lists);
+    constexpr bool HALF = std::is_same<T, uint16_t>::value;
+    if (!c || !centers || (c->n > 0 && !out_row_list)) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
+    int rc = ivf_check_corpus(c, HALF, lists, who);
+    if (rc) return rc;
     if (metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)
-        return fail(VSR_ERR_UNSUPPORTED, "vsr_ivf_assign: metric %d has no ivfflat opclass", metric);
+        return fail(VSR_ERR_UNSUPPORTED, "%s: metric %d has no ivfflat opclass", who, metric);
     vsr_ctx* ctx = c->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     const int64_t n = c->n;
     if (n == 0) return VSR_OK;
     DevBuf d_centers, d_out;
-    int rc;
-    if ((rc = d_centers.reserve((size_t) lists * c->dim * sizeof(float)))) return rc;
+    if ((rc = d_centers.reserve((size_t) lists * c->dim * sizeof(T)))) return rc;
     if ((rc = d_out.reserve((size_t) n * sizeof(int32_t)))) return rc;
-    const std::vector<float> ct = transpose_centers(centers, lists, c->dim);      // (outlives the copy: synchronised below)
-    HIPCHK(hipMemcpyAsync(d_centers.p, ct.data(), ct.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    const std::vector<T> ct = transpose_centers(centers, lists, c->dim);      // (outlives the copy: synchronised below)
+    HIPCHK(hipMemcpyAsync(d_centers.p, ct.data(), ct.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     // cosine opclass: rows and centres are compared by the negative inner product (spherical k-means, vector.sql:323-327)
-    HIPCHK(launch_ivf_probe(reinterpret_cast<const float*>(c->d_rows), (uint32_t) c->stride4 * 4, (uint32_t) n,
-                            d_centers.as<float>(), c->dim, lists, 1, metric == VSR_METRIC_L2 ? M_L2 : M_IP, d_out.as<int32_t>(),
-                            ctx->stream));
+    HIPCHK(launch_ivf_probe(c->d_rows, (uint32_t) c->stride4 * 4, (uint32_t) n, d_centers.p, c->dim, lists, 1,
+                            metric == VSR_METRIC_L2 ? M_L2 : M_IP, d_out.as<int32_t>(), ctx->stream, HALF ? IVF_HALF_ROW : IVF_F32));
     std::vector<int32_t> by_internal((size_t) n);
     HIPCHK(hipMemcpyAsync(by_internal.data(), d_out.p, (size_t) n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     for (int64_t r = 0; r < n; ++r) out_row_list[c->h_orig[(size_t) r]] = by_internal[(size_t) r];     // caller's row order
     return VSR_OK;
+}
+
+extern "C" int vsr_ivf_assign(vsr_corpus* c, const float* centers, int lists, int metric, int32_t* out_row_list)
+{
+    return ivf_assign(c, centers, lists, metric, out_row_list, "vsr_ivf_assign");
+}
+
+extern "C" int vsr_ivf_assign_half(vsr_corpus* c, const uint16_t* centers, int lists, int metric, int32_t* out_row_list)
+{
+    return ivf_assign(c, centers, lists, metric, out_row_list, "vsr_ivf_assign_half");
 }

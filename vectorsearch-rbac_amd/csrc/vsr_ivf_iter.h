@@ -41,7 +41,7 @@ struct IvfIterParams {
     const float*           queries;          // [nq][q_stride] (device)
     uint32_t               q_stride;
     uint32_t               dim;
-    const float*           centers_t;        // [dim][lists]
+    const void*            centers_t;        // [dim][lists]: fp32, or binary16 when rows_half (K3h)
     uint32_t               lists;
     int                    center_metric;    // M_L2, or M_IP for the inner-product and cosine opclasses
     int                    metric;           // the operator the rows rank by
@@ -50,6 +50,7 @@ struct IvfIterParams {
     uint32_t               k;
     const uint32_t*        list_start;       // [lists + 1] offsets into the view
     const float4*          rows;             // the view's rows, [n_rows][stride4], zero padded
+    uint32_t               rows_half;        // 1: the view of a halfvec corpus, [n_rows][stride4 / 2] chunks of 8 binary16 values
     uint32_t               stride4;
     uint32_t               n_rows;
     const uint32_t*        rank;             // view row -> base row (what keys carry)
@@ -108,6 +109,10 @@ __device__ __forceinline__ void ivf_iter_fold(uint64_t* kept, uint32_t sk, uint6
     __syncthreads();
 }
 
+// HALF (K3h): rows and centres are binary16.  The query is rounded to binary16 as it is loaded (`$1::halfvec`) and kept in LDS
+// widened, as fp32 -- the LDS formula does not change -- so the row sums (halfwave_row_sums<U, true>), cosine's |q|^2 and the
+// centre keys (IVF_HALF_Q32, from the query in global memory, rounded the same way) all see the same values.
+template <bool HALF>
 __global__ __launch_bounds__(256) void ivf_iterative_kernel(const IvfIterParams p)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -135,10 +140,10 @@ __global__ __launch_bounds__(256) void ivf_iterative_kernel(const IvfIterParams 
     const float* qg = p.queries + (size_t) qi * p.q_stride;
     {
         float* qf = reinterpret_cast<float*>(q4);
-        for (uint32_t j = tid; j < p.stride4 * 4; j += 256) qf[j] = j < p.dim ? qg[j] : 0.0f;
+        for (uint32_t j = tid; j < p.stride4 * 4; j += 256) qf[j] = j < p.dim ? (HALF ? (float) (_Float16) qg[j] : qg[j]) : 0.0f;
     }
     for (int c = tid; c < (int) p.lists; c += 256)
-        ckeys[c] = ivf_center_key(p.centers_t, (int) p.lists, (int) p.dim, c, qg, p.center_metric);
+        ckeys[c] = ivf_center_key<HALF ? IVF_HALF_Q32 : IVF_F32>(p.centers_t, (int) p.lists, (int) p.dim, c, qg, p.center_metric);
     if (tid == 0) ctrl->bad = 0;
     __syncthreads();
     const float qn = p.metric == M_COSINE ? wave_query_norm2(q4, p.stride4, lane) : 0.0f;
@@ -205,7 +210,7 @@ __global__ __launch_bounds__(256) void ivf_iterative_kernel(const IvfIterParams 
                         const uint32_t j = j0 + 2 * u + half;
                         row[u] = j < n_ok ? rowsel[j] : s0;                // an empty slot reads a row of the list and is dropped
                     }
-                    halfwave_row_sums<U>(p.rows, p.stride4, q4, p.metric, row, hl, s, nx);     // vsr_exact.h
+                    halfwave_row_sums<U, HALF>(p.rows, p.stride4, q4, p.metric, row, hl, s, nx);     // vsr_exact.h
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         const uint32_t j = j0 + 2 * u + half;

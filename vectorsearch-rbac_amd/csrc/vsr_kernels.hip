@@ -1416,7 +1416,10 @@ hipError_t launch_view_bitmap(const uint32_t* rank, uint32_t n_rows, const uint2
 // GetScanLists (ivfscan.c:36-107): per query the `probes` nearest of `lists` centres under the opclass distance (L2
 // squared, or negative inner product), nearest first, the lower list id first among equals.  One workgroup per query.
 // The sums run in the order and rounding of vector.c's loops compiled without contraction (one lane per centre).
-__global__ __launch_bounds__(256) void ivf_probe_kernel(const float* queries, uint32_t q_stride, const float* centers_t, int dim,
+// FORM (vsr_exact.h): IVF_F32; IVF_HALF_Q32 / IVF_HALF_ROW = K3h, binary16 centres against fp32 queries rounded on load or
+// against the binary16 rows of a halfvec corpus in place.  q_stride counts elements of the query side's type.
+template <int FORM>
+__global__ __launch_bounds__(256) void ivf_probe_kernel(const void* queries, uint32_t q_stride, const void* centers_t, int dim,
                                                         int lists, int probes, int metric, int32_t* out)
 {
     // one 32-bit monotone image of the distance per list (the list id is the slot): 32768 lists, the reloption's maximum
@@ -1425,11 +1428,12 @@ __global__ __launch_bounds__(256) void ivf_probe_kernel(const float* queries, ui
     uint32_t* keys = reinterpret_cast<uint32_t*>(smem);     // [lists]; 0xFFFFFFFF = taken (above the canonical NaN's image)
     __shared__ uint64_t s_best[4];
     const int tid = threadIdx.x;
-    const float* q = queries + (size_t) blockIdx.x * q_stride;         // (corpus rows as queries: the index build's assignment)
+    // (corpus rows as queries: the index build's assignment)
+    const void* q = static_cast<const char*>(queries) + (size_t) blockIdx.x * q_stride * (FORM == IVF_HALF_ROW ? 2 : 4);
     // centers_t[j][c]: the centres TRANSPOSED (element j of all lists contiguous), so that the 64 lanes of a wave -- one centre
     // each -- read 256 contiguous bytes per element instead of 64 lines 4 * dim bytes apart; every lane still adds its own
     // centre's terms in element order (the reference's loop), and q[j] is one broadcast load
-    for (int c = tid; c < lists; c += 256) keys[c] = ivf_center_key(centers_t, lists, dim, c, q, metric);    // vsr_exact.h
+    for (int c = tid; c < lists; c += 256) keys[c] = ivf_center_key<FORM>(centers_t, lists, dim, c, q, metric);    // vsr_exact.h
     __syncthreads();
     for (int pr = 0; pr < probes; ++pr) {
         const uint64_t b = ivf_extract_nearest(keys, lists, s_best, tid);
@@ -1437,19 +1441,31 @@ __global__ __launch_bounds__(256) void ivf_probe_kernel(const float* queries, ui
     }
 }
 
-hipError_t launch_ivf_probe(const float* queries, uint32_t q_stride, uint32_t nq, const float* centers_t, int dim, int lists, int probes,
-                            int metric, int32_t* out, hipStream_t s)
+template <int FORM>
+static hipError_t launch_ivf_probe_form(const void* queries, uint32_t q_stride, uint32_t nq, const void* centers_t, int dim, int lists,
+                                        int probes, int metric, int32_t* out, hipStream_t s)
 {
-    if (nq == 0) return hipSuccess;
     const size_t lds = (size_t) lists * sizeof(uint32_t);
-    if (lds > 128 * 1024) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_probe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int) lds);
+    if (lds > 64 * 1024) {                                 // (per instantiation: each is a kernel of its own)
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_probe_kernel<FORM>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(ivf_probe_kernel, dim3(nq), dim3(256), lds, s, queries, q_stride, centers_t, dim, lists, probes, metric, out);
+    hipLaunchKernelGGL(ivf_probe_kernel<FORM>, dim3(nq), dim3(256), lds, s, queries, q_stride, centers_t, dim, lists, probes, metric, out);
     return hipGetLastError();
+}
+
+hipError_t launch_ivf_probe(const void* queries, uint32_t q_stride, uint32_t nq, const void* centers_t, int dim, int lists, int probes,
+                            int metric, int32_t* out, hipStream_t s, int form)
+{
+    if (nq == 0) return hipSuccess;
+    if ((size_t) lists * sizeof(uint32_t) > 128 * 1024) return hipErrorInvalidValue;
+    switch (form) {
+    case IVF_F32: return launch_ivf_probe_form<IVF_F32>(queries, q_stride, nq, centers_t, dim, lists, probes, metric, out, s);
+    case IVF_HALF_Q32: return launch_ivf_probe_form<IVF_HALF_Q32>(queries, q_stride, nq, centers_t, dim, lists, probes, metric, out, s);
+    case IVF_HALF_ROW: return launch_ivf_probe_form<IVF_HALF_ROW>(queries, q_stride, nq, centers_t, dim, lists, probes, metric, out, s);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 hipError_t launch_rerank(const RerankParams& p, uint32_t n_queries, hipStream_t s)

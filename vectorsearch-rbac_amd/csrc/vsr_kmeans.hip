@@ -55,21 +55,28 @@ __device__ __forceinline__ double km_distance(int metric, int dim, const float* 
     return acos(d) / 3.14159265358979323846;
 }
 
-// l2_normalize of one centre in place (vector.c:774-808; a centre that overflows stays as it is, like NormCenters)
-__device__ inline void km_norm_center(int dim, float* c)
+// a value on its way into a centre of a halfvec index: HalfvecUpdateCenter (ivfutils.c:266-276) stores Float4ToHalfUnchecked(x),
+// round to nearest even, and everything downstream reads it widened again
+__device__ __forceinline__ float km_center_value(int round_half, float v) { return round_half ? (float) (_Float16) v : v; }
+
+// l2_normalize of one centre in place (vector.c:774-808; a centre that overflows stays as it is, like NormCenters).
+// round_half: halfvec_l2_normalize (halfvec.c:712-744) -- the elements are binary16 values already, the norm is the same double
+// over the widened elements, the quotient is rounded to binary16 and the overflow check looks at that binary16 result
+__device__ inline void km_norm_center(int dim, float* c, int round_half)
 {
     double norm = 0;
     for (int i = 0; i < dim; ++i) norm += (double) c[i] * (double) c[i];
     norm = sqrt(norm);
     if (!(norm > 0)) { for (int i = 0; i < dim; ++i) c[i] = 0.0f; return; }
     bool inf = false;
-    for (int i = 0; i < dim; ++i) inf |= isinf((float) (c[i] / norm));
+    for (int i = 0; i < dim; ++i) inf |= isinf(km_center_value(round_half, (float) (c[i] / norm)));
     if (inf) return;
-    for (int i = 0; i < dim; ++i) c[i] = (float) (c[i] / norm);
+    for (int i = 0; i < dim; ++i) c[i] = km_center_value(round_half, (float) (c[i] / norm));
 }
 
 struct KmState {
     int metric, dim, nc;
+    int round_half;            // vsr_ivf_kmeans_half: every value written into centers / newc is rounded to binary16 and widened again
     int64_t ns;
     const float* samples;      // [ns][dim]
     float* centers;            // [nc][dim]
@@ -276,7 +283,7 @@ __global__ __launch_bounds__(256) void km_sum_kernel(KmState k)
     for (int m = 0; m < n; ++m) sum = __fadd_rn(sum, k.samples[(size_t) members[m] * k.dim + t]);
     if (n > 0) {
         if (isinf(sum)) sum = sum > 0 ? FLT_MAX : -FLT_MAX;
-        sum = __fdiv_rn(sum, (float) n);
+        sum = km_center_value(k.round_half, __fdiv_rn(sum, (float) n));
     }
     k.newc[i] = sum;
 }
@@ -287,8 +294,8 @@ __global__ __launch_bounds__(1) void km_fix_centers_kernel(KmState k)
     for (int c = 0; c < k.nc; ++c) {
         float* x = k.newc + (size_t) c * k.dim;
         if (k.counts[c] == 0)
-            for (int t = 0; t < k.dim; ++t) x[t] = (float) km_double(k.rng);
-        if (k.metric != M_L2) km_norm_center(k.dim, x);
+            for (int t = 0; t < k.dim; ++t) x[t] = km_center_value(k.round_half, (float) km_double(k.rng));
+        if (k.metric != M_L2) km_norm_center(k.dim, x, k.round_half);
     }
 }
 
@@ -313,9 +320,23 @@ __global__ __launch_bounds__(256) void km_bounds_kernel(KmState k)           // 
 __global__ __launch_bounds__(256) void km_random_centers_kernel(KmState k)   // RandomCenters, ivfkmeans.c:124-147 (no samples)
 {
     if (blockIdx.x || threadIdx.x) return;
-    for (int64_t i = 0; i < (int64_t) k.nc * k.dim; ++i) k.centers[i] = (float) km_double(k.rng);
+    for (int64_t i = 0; i < (int64_t) k.nc * k.dim; ++i) k.centers[i] = km_center_value(k.round_half, (float) km_double(k.rng));
     if (k.metric != M_L2)
-        for (int c = 0; c < k.nc; ++c) km_norm_center(k.dim, k.centers + (size_t) c * k.dim);
+        for (int c = 0; c < k.nc; ++c) km_norm_center(k.dim, k.centers + (size_t) c * k.dim, k.round_half);
+}
+
+// vsr_ivf_kmeans_half: the binary16 samples widened once into the build's fp32 scratch (HalfvecSumCenter and the distance
+// functions of halfutils.c read HalfToFloat4 of every element), and the finished centres -- binary16 values by then -- narrowed
+__global__ __launch_bounds__(256) void km_widen_kernel(const _Float16* src, float* dst, int64_t n)
+{
+    const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = (float) src[i];
+}
+
+__global__ __launch_bounds__(256) void km_narrow_kernel(const float* src, _Float16* dst, int64_t n)
+{
+    const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = (_Float16) src[i];
 }
 
 }  // namespace vsr
@@ -331,17 +352,18 @@ using namespace vsr;
 int vsr_kmeans_fail(const char* what, const char* why, bool oom);     // vsr_runtime.hip: sets vsr_last_error
 int vsr_ctx_device(const vsr_ctx* ctx, hipStream_t* stream);          // vsr_runtime.hip
 
-extern "C" int vsr_ivf_kmeans(vsr_ctx* ctx, int metric, int dim, const float* samples, int64_t n_samples, int lists, uint64_t seed,
-                              float* out_centers, int* out_iterations)
+// vsr_ivf_kmeans (samples and out_centers fp32) and vsr_ivf_kmeans_half (round_half: both binary16 bit patterns)
+static int km_run(vsr_ctx* ctx, int metric, int dim, const void* samples, int64_t n_samples, int lists, uint64_t seed, void* out_centers,
+                  int* out_iterations, bool round_half, const char* who)
 {
     int rc = VSR_OK;
     hipStream_t st = nullptr;
     if (!ctx || !out_centers || n_samples < 0 || (n_samples > 0 && !samples))
-        return vsr_kmeans_fail("vsr_ivf_kmeans", "NULL argument", false), VSR_ERR_INVALID;
+        return vsr_kmeans_fail(who, "NULL argument", false), VSR_ERR_INVALID;
     if (dim < 1 || dim > 16000 || lists < 1 || lists > 32768)      /* IVFFLAT_MAX_LISTS, ivfflat.h:44 */
-        return vsr_kmeans_fail("vsr_ivf_kmeans", "dim must be 1..16000 and lists 1..32768", false), VSR_ERR_INVALID;
+        return vsr_kmeans_fail(who, "dim must be 1..16000 and lists 1..32768", false), VSR_ERR_INVALID;
     if (metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)
-        return vsr_kmeans_fail("vsr_ivf_kmeans", "metric has no ivfflat operator class", false), VSR_ERR_UNSUPPORTED;
+        return vsr_kmeans_fail(who, "metric has no ivfflat operator class", false), VSR_ERR_UNSUPPORTED;
     if (out_iterations) *out_iterations = 0;
     const int dev = vsr_ctx_device(ctx, &st);
     if (hipSetDevice(dev) != hipSuccess) return vsr_kmeans_fail("hipSetDevice", "failed", false), VSR_ERR_HIP;
@@ -352,6 +374,7 @@ extern "C" int vsr_ivf_kmeans(vsr_ctx* ctx, int metric, int dim, const float* sa
     k.dim = dim;
     k.nc = nc;
     k.ns = ns;
+    k.round_half = round_half ? 1 : 0;
     void* bufs[32] = {nullptr};
     int nb = 0;
     auto alloc = [&](size_t bytes) -> void* {
@@ -386,16 +409,22 @@ extern "C" int vsr_ivf_kmeans(vsr_ctx* ctx, int metric, int dim, const float* sa
         k.changes = (int*) alloc(16);
         k.rng = (KmRng*) alloc(16);
         k.samples = d_samples;
-        if (!d_samples || !k.centers || !k.newc || !k.lower || !k.upper || !k.weight || !k.s || !k.half || !k.newcdist || !k.counts ||
+        // the binary16 side of the half form: the samples as uploaded, later the centres on their way out (whichever is larger)
+        _Float16* d_h16 = round_half ? (_Float16*) alloc((size_t) std::max<int64_t>(ns, nc) * dim * 2) : nullptr;
+        if ((round_half && !d_h16) || !d_samples || !k.centers || !k.newc || !k.lower || !k.upper || !k.weight || !k.s || !k.half || !k.newcdist || !k.counts ||
             !k.closest || !k.changes || !k.rng || !k.closest_sorted || !k.order_val_in || !k.order_val || !k.starts || !d_sort_tmp) {
-            rc = vsr_kmeans_fail("vsr_ivf_kmeans", "out of device memory", true);
+            rc = vsr_kmeans_fail(who, "out of device memory", true);
             goto done;
         }
         KM_HIP(hipMemcpyAsync(k.rng, &h_rng, sizeof h_rng, hipMemcpyHostToDevice, st));
         if (ns == 0) {
             hipLaunchKernelGGL(km_random_centers_kernel, dim3(1), dim3(64), 0, st, k);
         } else {
-            KM_HIP(hipMemcpyAsync(d_samples, samples, (size_t) ns * dim * 4, hipMemcpyHostToDevice, st));
+            if (round_half) {
+                KM_HIP(hipMemcpyAsync(d_h16, samples, (size_t) ns * dim * 2, hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL(km_widen_kernel, dim3((unsigned) ((ns * dim + 255) / 256)), dim3(256), 0, st, d_h16, d_samples, ns * dim);
+            } else
+                KM_HIP(hipMemcpyAsync(d_samples, samples, (size_t) ns * dim * 4, hipMemcpyHostToDevice, st));
             const unsigned gs = (unsigned) ((ns + 255) / 256), gc = (unsigned) ((nc + 255) / 256);
             hipLaunchKernelGGL(km_first_center_kernel, dim3(1), dim3(1), 0, st, k);
             for (int i = 0; i < nc; ++i) {
@@ -428,11 +457,32 @@ extern "C" int vsr_ivf_kmeans(vsr_ctx* ctx, int metric, int dim, const float* sa
             }
         }
         KM_HIP(hipGetLastError());
-        KM_HIP(hipMemcpyAsync(out_centers, k.centers, (size_t) nc * dim * 4, hipMemcpyDeviceToHost, st));
+        if (round_half) {
+            hipLaunchKernelGGL(km_narrow_kernel, dim3((unsigned) (((int64_t) nc * dim + 255) / 256)), dim3(256), 0, st, k.centers, d_h16,
+                               (int64_t) nc * dim);
+            KM_HIP(hipGetLastError());
+            KM_HIP(hipMemcpyAsync(out_centers, d_h16, (size_t) nc * dim * 2, hipMemcpyDeviceToHost, st));
+        } else
+            KM_HIP(hipMemcpyAsync(out_centers, k.centers, (size_t) nc * dim * 4, hipMemcpyDeviceToHost, st));
         KM_HIP(hipStreamSynchronize(st));
         if (out_iterations) *out_iterations = iterations;
     }
 done:
     for (int i = 0; i < nb; ++i) (void) hipFree(bufs[i]);
     return rc;
+}
+
+extern "C" int vsr_ivf_kmeans(vsr_ctx* ctx, int metric, int dim, const float* samples, int64_t n_samples, int lists, uint64_t seed,
+                              float* out_centers, int* out_iterations)
+{
+    return km_run(ctx, metric, dim, samples, n_samples, lists, seed, out_centers, out_iterations, false, "vsr_ivf_kmeans");
+}
+
+// CREATE INDEX ... USING ivfflat (col halfvec_*_ops), step 1: pgvector's k-means for the type (ivfutils.c:266-276, 305-314) -- the
+// sums and distances run in fp32 on the widened samples, as above, and every centre is a halfvec value: rounded to binary16 wherever
+// the float build stores an fp32 centre.  Seeded centres are samples and need no rounding.
+extern "C" int vsr_ivf_kmeans_half(vsr_ctx* ctx, int metric, int dim, const uint16_t* samples, int64_t n_samples, int lists, uint64_t seed,
+                                   uint16_t* out_centers, int* out_iterations)
+{
+    return km_run(ctx, metric, dim, samples, n_samples, lists, seed, out_centers, out_iterations, true, "vsr_ivf_kmeans_half");
 }

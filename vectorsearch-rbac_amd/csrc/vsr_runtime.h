@@ -413,6 +413,8 @@ inline size_t bitmap_words(int64_t n) { return (size_t) ((n + 63) / 64) + 2; }  
 // vsr_rbac_load, corpus teardown): the indexes forget what they derived from it.  The caller has synchronised the stream.
 void   purge_ivf_caches(vsr_corpus* c, const vsr_filter* f);
 void   purge_hnsw_caches(vsr_corpus* c, const vsr_filter* f);
+// vsr_hnsw_rt.hip: host queries bound for halfvec rows: a finite element that rounds to +-Inf in binary16 is refused (`$1::halfvec`)
+int    half_query_range(const void* queries, int nq, int dim);
 // vsr_search.hip
 // bit_entry: the caller is a vsr_search_bit* entry point (bit corpus, metrics 4 / 5); every other caller is refused a bit corpus
 // sparse_entry: ... a vsr_search_sparse* entry point (sparse corpus, metrics 0 .. 3); every other caller is refused a sparse corpus

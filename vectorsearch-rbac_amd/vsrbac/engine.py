@@ -50,6 +50,15 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _as_f16(a, what):
+    """`a` as np.float16.  The halfvec index entry points take halfvec values: an array of another type is refused rather than
+    rounded silently (round it with astype(np.float16), as load_corpus_half documents)."""
+    a = np.asarray(a)
+    if a.dtype != np.float16:
+        raise ValueError(f"{what} must be a np.float16 array (halfvec values), got {a.dtype}")
+    return a
+
+
 def _packed_bits(a, dim, what):
     """`a` as packed uint8 [n, (dim + 7) // 8] in varbit order: a bool [n, dim] array is packed with np.packbits (element i
     -> bit 7 - i % 8 of byte i // 8); a uint8 array is taken as packed already, then `dim` must be given."""
@@ -282,6 +291,17 @@ class Context:
                                        C.byref(it)))
         return out, it.value
 
+    def ivf_kmeans_half(self, samples_f16, lists, metric="l2", seed=1):
+        """ivf_kmeans for the halfvec opclasses (vsr_ivf_kmeans_half): `samples_f16` np.float16; the centres are halfvec
+        values, rounded to binary16 wherever the float build stores one.  Returns (centers[lists, dim] np.float16, iterations)."""
+        s = np.ascontiguousarray(np.atleast_2d(_as_f16(samples_f16, "samples")))
+        ns, dim = (0, s.shape[1]) if s.size == 0 else s.shape
+        out = np.zeros((int(lists), dim), dtype=np.float16)
+        it = C.c_int(0)
+        check(self._lib.vsr_ivf_kmeans_half(self._h, _metric(metric), dim, _ptr(s), ns, int(lists), C.c_uint64(int(seed)),
+                                            _ptr(out), C.byref(it)))
+        return out, it.value
+
     def merge_topk_device(self, keys, block_ids, doc_ids, dist, n_parts, nq, k, out_block, out_doc, out_dist,
                           out_keys, out_counts):
         """Device pointers (ints).  Layout [n_parts][nq][k]."""
@@ -463,6 +483,24 @@ class Corpus:
         centers, _ = self.ctx.ivf_kmeans(rows[pick], lists, metric, seed)
         row_list = self.ivf_assign(centers, metric)
         return IvfIndex(self, centers, row_list), centers, row_list
+
+    def load_ivf_half(self, centers_f16, row_list):
+        """load_ivf over this halfvec corpus (vsr_ivf_load_half): centres np.float16 [lists, dim]; the list-ordered image and the
+        centres stay binary16 on the device.  The index answers IvfIndex.search* / probe like any float index."""
+        return IvfIndex(self, centers_f16, row_list, half=True)
+
+    def build_ivf_half(self, rows_f16, lists=100, metric="l2", seed=1, sample=None):
+        """CREATE INDEX ... USING ivfflat (col halfvec_l2_ops | halfvec_ip_ops | halfvec_cosine_ops) over this halfvec corpus:
+        build_ivf's sampling rule on `rows_f16` (this corpus's rows in the caller's order, np.float16), vsr_ivf_kmeans_half,
+        vsr_ivf_assign_half, vsr_ivf_load_half.  Returns (IvfIndex, centers np.float16, row_list)."""
+        rows = np.ascontiguousarray(_as_f16(rows_f16, "rows"))
+        n = rows.shape[0]
+        want = max(int(lists) * 50, 10000) if sample is None else int(sample)
+        rng = np.random.default_rng(seed)
+        pick = np.sort(rng.choice(n, size=min(n, want), replace=False)) if n else np.zeros(0, dtype=np.int64)
+        centers, _ = self.ctx.ivf_kmeans_half(rows[pick], lists, metric, seed)
+        row_list = self.ivf_assign_half(centers, metric)
+        return IvfIndex(self, centers, row_list, half=True), centers, row_list
 
     def build_hnsw(self, m=16, ef_construction=64, metric="l2", seed=1, merge_duplicates=False):
         """CREATE INDEX ... USING hnsw on the GPU (vsr_hnsw_build): batched insertion, recall parity with the serial build.
@@ -679,6 +717,16 @@ class Corpus:
         check(self._lib.vsr_ivf_assign(self._h, _ptr(c), int(c.shape[0]), _metric(metric), _ptr(out)))
         return out
 
+    def ivf_assign_half(self, centers_f16, metric="l2"):
+        """ivf_assign over this halfvec corpus (vsr_ivf_assign_half): centres np.float16, compared with the binary16 rows where
+        they lie."""
+        c = np.ascontiguousarray(_as_f16(centers_f16, "centers"))
+        if c.ndim != 2 or c.shape[1] != self.dim:
+            raise VsrError(_ffi.ERR_INVALID, f"centers must be (lists, {self.dim})")
+        out = np.zeros(self.n, dtype=np.int32)
+        check(self._lib.vsr_ivf_assign_half(self._h, _ptr(c), int(c.shape[0]), _metric(metric), _ptr(out)))
+        return out
+
     def search_device_exact(self, d_queries, nq, k, metric, filters, d_block, d_doc, d_rows, d_dist, d_counts, d_keys=None,
                             dim=None, session=None):
         """search_device + wait + exact re-run of whatever the screening flagged (vsr_search_device_exact): returns the
@@ -695,15 +743,21 @@ class Corpus:
 class IvfIndex:
     """pgvector's ivfflat scan (ivfscan.c) on the GPU: probe the nearest lists, scan them, keep the permitted top-k."""
 
-    def __init__(self, corpus, centers, row_list):
+    def __init__(self, corpus, centers, row_list, half=False):
         self.corpus, self._lib = corpus, corpus._lib
-        c = np.ascontiguousarray(centers, dtype=np.float32)
+        c = np.ascontiguousarray(_as_f16(centers, "centers")) if half else np.ascontiguousarray(centers, dtype=np.float32)
         rl = np.ascontiguousarray(row_list, dtype=np.int32)
         if c.ndim != 2 or c.shape[1] != corpus.dim or rl.size != corpus.n:
             raise ValueError("centers must be [lists, dim] and row_list must have one entry per row")
         h = C.c_void_p()
-        check(self._lib.vsr_ivf_load(corpus._h, _ptr(c), c.shape[0], _ptr(rl), C.byref(h)))
+        load = self._lib.vsr_ivf_load_half if half else self._lib.vsr_ivf_load     # (half: Corpus.load_ivf_half)
+        check(load(corpus._h, _ptr(c), c.shape[0], _ptr(rl), C.byref(h)))
         self._h, self.lists = h, c.shape[0]
+
+    def device_bytes(self):
+        """Device memory of the index in bytes (vsr_ivf_device_bytes): the list-ordered image of the rows with norms and rank
+        map, the centres, the list offsets; the corpus itself: Corpus.device_bytes."""
+        return int(self._lib.vsr_ivf_device_bytes(self._h))
 
     def free(self):
         if getattr(self, "_h", None):
