@@ -131,7 +131,7 @@ def test_known_answers(ctx, known):
 # ---------------------------------------------------------------------------------------------
 # 2. every row shape
 # ---------------------------------------------------------------------------------------------
-# (at and around every byte and 128-bit chunk boundary; 1024 | 4099: LPR 16 | 32 of scan_shape_for_dim_bit; 64000: the
+# (at and around every byte and 128-bit chunk boundary; 1024 | 4099: LPR 16 | 32 of scan_shape(RowFormat::BIT, dim); 64000: the
 # widest column, 500 chunks, the streaming instantiation)
 SHAPE_DIMS = [1, 7, 8, 9, 64, 127, 128, 129, 255, 1000, 1024, 4099, 64000]
 

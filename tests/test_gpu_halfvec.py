@@ -185,7 +185,7 @@ def test_randomized_shapes_exact(ctx, oracle, seed):
 # ---------------------------------------------------------------------------------------------
 # 4. every row-layout class on real-valued rows
 # ---------------------------------------------------------------------------------------------
-# (8 | 9, 32 | 33, 128 | 129, 256 | 257, 512 | 513, 1024 | 1025: the boundaries of scan_shape_for_dim_half)
+# (8 | 9, 32 | 33, 128 | 129, 256 | 257, 512 | 513, 1024 | 1025: the boundaries of scan_shape(RowFormat::HALF, dim))
 LAYOUT_DIMS = [1, 3, 7, 8, 9, 15, 17, 32, 33, 64, 100, 128, 129, 255, 256, 257, 512, 513, 768, 1024, 1025, 1536, 2000, 4100]
 
 

@@ -225,25 +225,78 @@ struct KernelShape {
     int rw;      // rows per wave iteration = r * (64 / lpr)
 };
 
+// What a stored row holds; said once per object (vsr_corpus::format, vsr_hnsw::format; an index's view corpus carries the
+// index's) and mapped to the kernels' own switches (HALF / ROWS template arguments, rows_half, q_bits, q_half) where a launch is
+// made.  The small facts that follow from it:
+enum class RowFormat : uint8_t {
+    F32,        // fp32 elements, stride4 float4 per row, zero padded
+    HALF,       // binary16 elements, 16-byte chunks of 8; stride4 still counts float4 per padded (fp32) QUERY, two per row chunk
+    BIT,        // packed bits, 16-byte chunks of 128; dim counts bits
+    SPARSE,     // interleaved (index, value) entries of 8 bytes behind row offsets (CSR); stride4 = 0
+};
+// 16-byte chunks per stored row (SPARSE: rows have no common length)
+inline uint32_t format_row_chunks(RowFormat f, int dim)
+{
+    switch (f) {
+    case RowFormat::F32:  return (uint32_t) ((dim + 3) / 4);
+    case RowFormat::HALF: return (uint32_t) ((dim + 7) / 8);
+    case RowFormat::BIT:  return (uint32_t) ((dim + 127) / 128);
+    default:              return 0;
+    }
+}
+// bytes of a row's `dim` elements, for the byte accounting of a scan (SPARSE: 8 per stored entry, counted by the caller)
+inline int64_t format_row_bytes(RowFormat f, int dim)
+{
+    return f == RowFormat::BIT ? (dim + 7) / 8 : (int64_t) dim * (f == RowFormat::HALF ? 2 : 4);
+}
+// bytes of one query as the caller holds it: fp32 elements (a halfvec corpus or index takes fp32 queries too), or a packed bit
+// string (SPARSE: the queries arrive as CSR arrays)
+inline size_t format_query_bytes(RowFormat f, int dim)
+{
+    return f == RowFormat::BIT ? (size_t) (dim + 7) / 8 : (size_t) dim * sizeof(float);
+}
+// pgvector's name of the type, as the messages spell it
+inline const char* format_name(RowFormat f)
+{
+    switch (f) {
+    case RowFormat::HALF:   return "halfvec";
+    case RowFormat::BIT:    return "bit";
+    case RowFormat::SPARSE: return "sparsevec";
+    default:                return "vector";
+    }
+}
+
 // host-side launchers (vsr_kernels.hip)
-KernelShape scan_shape_for_dim(int dim);
-// K1h (halfvec corpus): the same classes by the row's 16-byte chunks, ceil(dim / 8) of 8 halves each; c counts those chunks
-KernelShape scan_shape_for_dim_half(int dim);
-// K1b (bit corpus): ... by ceil(dim / 128) chunks of 128 packed bits
-KernelShape scan_shape_for_dim_bit(int dim);
+// K1 / K1h / K1b: lanes per row, chunks per lane and row slots by the row's 16-byte chunks (K1s: by the mean entry count,
+// sparse_lpr_for_mean_nnz)
+KernelShape scan_shape(RowFormat f, int dim);
 uint32_t scan_cap_for_k(int k, int dim);
 uint32_t scan_cap_for_rw(int k, int rw);                  // ... from the tile rows of either kind of corpus
-int  scan_qmax(int dim, int k);    // queries per pass the LDS budget allows (1, or a multiple of 4 up to SCAN_QMAX)
-int  scan_qmax_half(int dim, int k);
-int  scan_qmax_bit(int dim, int k);
+// queries per pass the LDS budget allows (1, or a multiple of 4 up to SCAN_QMAX); K1s: scan_qmax_sparse, by the table slots
+int  scan_qmax(RowFormat f, int dim, int k);
 inline size_t scan_lds_bytes(uint32_t qmax, uint32_t cap, uint32_t stride4)
 {
     return (size_t) qmax * ((size_t) cap * 8 + 16 + (size_t) stride4 * 16 + 4) + 16;
 }
-hipError_t launch_scan(const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s);
-hipError_t launch_scan_half(const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s);   // K1h
-// K1b (vsr_scanb.h): Hamming (metric 4) / Jaccard (5) over a bit corpus; dim in bits
-hipError_t launch_scan_bit(const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s);
+// K1 (vsr_scan.h), K1h (the same kernels, HALF), K1b (vsr_scanb.h: metric 4 Hamming / 5 Jaccard, dim in bits) or K1s
+// (vsr_scans.h; dim unused; lpr in {4, 16, 64} lanes per row, global_tab: the query tables are read where staging wrote them
+// instead of from an LDS copy -- a table that does not fit the LDS budget beside the candidate lists).  qi in {1, 4}
+hipError_t launch_scan(RowFormat f, const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s,
+                       int sparse_lpr = 0, bool sparse_global_tab = false);
+// ... and the per-metric launchers behind the family launchers of this header (launch_scan, launch_mq, launch_mfma,
+// launch_mfmah, launch_mfmaw, launch_gemm): one translation unit per metric, for parallel builds
+using ScanLaunch   = hipError_t(const ScanParams& p, int dim, int qi, uint32_t n_blocks, hipStream_t s);
+using SparseLaunch = hipError_t(const ScanParams& p, int lpr, int qi, bool global_tab, uint32_t n_blocks, hipStream_t s);
+using PassLaunch   = hipError_t(const ScanParams& p, uint32_t n_blocks, hipStream_t s);
+ScanLaunch   launch_scan_l2, launch_scan_ip, launch_scan_cosine, launch_scan_l1;         // vsr_scan_*.hip (with K1m's and K2's)
+ScanLaunch   launch_scanh_l2, launch_scanh_ip, launch_scanh_cosine, launch_scanh_l1;     // vsr_scanh_*.hip
+ScanLaunch   launch_scanb_hamming, launch_scanb_jaccard;                                 // vsr_scanb_*.hip
+SparseLaunch launch_scans_l2, launch_scans_ip, launch_scans_cosine, launch_scans_l1;     // vsr_scans_*.hip
+PassLaunch   launch_mq_l2, launch_mq_ip, launch_mq_cosine, launch_mq_l1;
+PassLaunch   launch_mfma_l2, launch_mfma_ip, launch_mfma_cosine;
+PassLaunch   launch_mfmah_l2, launch_mfmah_ip, launch_mfmah_cosine;                      // vsr_mfmah_*.hip
+PassLaunch   launch_mfmaw_l2, launch_mfmaw_ip, launch_mfmaw_cosine;                      // vsr_mfmaw_*.hip
+PassLaunch   launch_gemm_l2, launch_gemm_ip, launch_gemm_cosine;                         // vsr_gemm_*.hip
 // one query per call over the int8 planes (vsr_scan8.h): K1's top-k and in-kernel merge, a quarter of the bytes per row
 hipError_t launch_scan8_fused(const ScanParams& p, uint32_t dim, uint32_t* q8_bad_host, uint32_t n_blocks, hipStream_t s);
 // K1m (vsr_mq.h): shared-pass kernel for 2..16 queries per pass; needs dim >= 61 (>= 16 float4 per row)
@@ -413,8 +466,7 @@ struct SparseStageParams {
     uint32_t*      err;            // the session's guard word
 };
 hipError_t launch_stage_sparse(const SparseStageParams& p, hipStream_t s);
-// K1s: LPR in {4, 16, 64} lanes per row (sparse_lpr_for_mean_nnz), qi in {1, 4}; global_tab: the tables are read where staging
-// wrote them instead of from an LDS copy (a table that does not fit the LDS budget beside the candidate lists)
+// K1s: LPR in {4, 16, 64} lanes per row
 int  sparse_lpr_for_mean_nnz(double mean_nnz);
 inline uint32_t sparse_slots_for_nnz(uint32_t max_nnz)
 {
@@ -428,7 +480,6 @@ inline size_t scans_lds_bytes(uint32_t qmax, uint32_t cap, uint32_t lds_slots)
 }
 bool scan_sparse_table_in_lds(uint32_t slots, int k);     // one query's table fits beside its candidate list
 int  scan_qmax_sparse(uint32_t slots, int k);             // queries per pass: 1, or a multiple of 4 up to SCAN_QMAX (table in LDS); 4 or 1 (global)
-hipError_t launch_scan_sparse(const ScanParams& p, int metric, int lpr, int qi, bool global_tab, uint32_t n_blocks, hipStream_t s);
 // sparsevec.c:803-1037 for n explicit pairs, one thread per pair, pgvector's sequential merge; out: the operator's float8
 hipError_t launch_sparse_pair_distances(const int64_t* a_ptr, const int32_t* a_idx, const float* a_val, const int64_t* b_ptr,
                                         const int32_t* b_idx, const float* b_val, int64_t n_pairs, int metric, double* out,

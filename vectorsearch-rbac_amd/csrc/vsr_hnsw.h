@@ -808,8 +808,8 @@ inline bool hnsw_plan_iterative(HnswParams& p, bool force_global)
     return true;
 }
 
-template <bool ITER, int ROWS = ROWS_F32>
-inline hipError_t launch_hnsw(const HnswParams& p, hipStream_t s)
+template <bool ITER, int ROWS>
+inline hipError_t launch_hnsw_rows(const HnswParams& p, hipStream_t s)
 {
     if (p.nq == 0) return hipSuccess;
     const size_t lds = (size_t) p.lds_per_query * p.qpb;
@@ -825,11 +825,15 @@ inline hipError_t launch_hnsw(const HnswParams& p, hipStream_t s)
     return hipGetLastError();
 }
 
-inline hipError_t launch_hnsw_search(const HnswParams& p, hipStream_t s) { return launch_hnsw<false>(p, s); }
-inline hipError_t launch_hnsw_iterative(const HnswParams& p, hipStream_t s) { return launch_hnsw<true>(p, s); }
-inline hipError_t launch_hnsw_bit_search(const HnswParams& p, hipStream_t s) { return launch_hnsw<false, ROWS_BIT>(p, s); }
-inline hipError_t launch_hnsw_bit_iterative(const HnswParams& p, hipStream_t s) { return launch_hnsw<true, ROWS_BIT>(p, s); }
-inline hipError_t launch_hnsw_half_search(const HnswParams& p, hipStream_t s) { return launch_hnsw<false, ROWS_HALF>(p, s); }
-inline hipError_t launch_hnsw_half_iterative(const HnswParams& p, hipStream_t s) { return launch_hnsw<true, ROWS_HALF>(p, s); }
+// K4 (F32), K4h (HALF) or K4b (BIT); iterative: the iterative-scan kernel of that row format
+inline hipError_t launch_hnsw(RowFormat f, bool iterative, const HnswParams& p, hipStream_t s)
+{
+    switch (f) {
+    case RowFormat::F32:  return iterative ? launch_hnsw_rows<true, ROWS_F32>(p, s) : launch_hnsw_rows<false, ROWS_F32>(p, s);
+    case RowFormat::HALF: return iterative ? launch_hnsw_rows<true, ROWS_HALF>(p, s) : launch_hnsw_rows<false, ROWS_HALF>(p, s);
+    case RowFormat::BIT:  return iterative ? launch_hnsw_rows<true, ROWS_BIT>(p, s) : launch_hnsw_rows<false, ROWS_BIT>(p, s);
+    default:              return hipErrorInvalidValue;
+    }
+}
 
 }  // namespace vsr

@@ -20,9 +20,9 @@ struct vsr_hnsw {
     std::map<uint64_t, uint64_t*> bitmaps;           // filters (by vsr_filter::id) without a full bitmap of their own, as one
     DevBuf d_q, d_vis, d_out, d_bm, d_disc;
     DevBuf d_qb;                                     // bit index: [staged queries | their popcounts | the staging kernel's flag and seed words]
-    int bit_metric = 0;                              // 0: an index over fp32 rows; VSR_METRIC_HAMMING / VSR_METRIC_JACCARD: the opclass of a
-                                                     // bit index (fixed when the index is made: the graph is built for one distance)
-    bool half = false;                               // an index over a halfvec corpus (vsr_hnsw_load_half / vsr_hnsw_build_half): K4h
+    RowFormat format = RowFormat::F32;               // the corpus's rows: F32 (K4), HALF (vsr_hnsw_load_half / vsr_hnsw_build_half: K4h) or BIT (K4b)
+    int bit_metric = 0;                              // BIT only: the opclass, VSR_METRIC_HAMMING / VSR_METRIC_JACCARD (fixed when the index
+                                                     // is made: the graph is built for one distance)
     PinBuf h_out, h_bm;
     int last_mode = -1;                              // visited form of the last launch (HnswVisited)
     int predicate_aware = 0;                         // vsr_hnsw_set_predicate_aware
@@ -58,7 +58,7 @@ static int upload_i32(int32_t** d, const int32_t* src, size_t count)          //
 // what a bit entry point asks of its corpus and opclass (who: the entry point)
 static int hnsw_bit_opclass(const vsr_corpus* c, int metric, const char* who)
 {
-    if (!c->bit) return fail(VSR_ERR_INVALID, "%s: the corpus is not a bit corpus", who);
+    if (c->format != RowFormat::BIT) return fail(VSR_ERR_INVALID, "%s: the corpus is not a bit corpus", who);
     if (metric != VSR_METRIC_HAMMING && metric != VSR_METRIC_JACCARD)
         return fail(VSR_ERR_INVALID, "%s: metric %d is not an operator class of bit (4: bit_hamming_ops, 5: bit_jaccard_ops)", who, metric);
     return VSR_OK;
@@ -67,7 +67,7 @@ static int hnsw_bit_opclass(const vsr_corpus* c, int metric, const char* who)
 // what a halfvec entry point asks of its corpus (who: the entry point)
 static int hnsw_half_opclass(const vsr_corpus* c, const char* who)
 {
-    if (!c->half) return fail(VSR_ERR_INVALID, "%s: the corpus is not a halfvec corpus", who);
+    if (c->format != RowFormat::HALF) return fail(VSR_ERR_INVALID, "%s: the corpus is not a halfvec corpus", who);
     if (c->dim > 4000)           /* HNSW_MAX_DIM * 2, hnswutils.c:1390 */
         return fail(VSR_ERR_UNSUPPORTED, "%s: column cannot have more than 4000 dimensions for hnsw index", who);
     return VSR_OK;
@@ -76,25 +76,26 @@ static const char* const HNSW_HALF_ENTRY =
     "the graph of a halfvec corpus is loaded with vsr_hnsw_load_half and built with vsr_hnsw_build_half (the halfvec_l2_ops / halfvec_ip_ops / "
     "halfvec_cosine_ops opclasses)";
 
-// vsr_hnsw_load (bit_metric = 0), vsr_hnsw_load_bit (the opclass) and vsr_hnsw_load_half (half_entry)
-static int hnsw_load(vsr_corpus* c, int bit_metric, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
+// vsr_hnsw_load (expect = F32), vsr_hnsw_load_half (HALF) and vsr_hnsw_load_bit (BIT; bit_metric: the opclass): `expect` is the
+// corpus format the entry point is for
+static int hnsw_load(vsr_corpus* c, RowFormat expect, int bit_metric, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
                      const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
-                     int32_t n_upper, int32_t max_level, vsr_hnsw** out, const char* who, bool half_entry = false)
+                     int32_t n_upper, int32_t max_level, vsr_hnsw** out, const char* who)
 {
     if (!c || !out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
     *out = nullptr;
     if (c->base) return fail(VSR_ERR_INVALID, "%s: the corpus is a view", who);
-    if (bit_metric) {
+    if (expect == RowFormat::BIT) {
         int rc = hnsw_bit_opclass(c, bit_metric, who);
         if (rc) return rc;
     }
-    if (half_entry) {
+    if (expect == RowFormat::HALF) {
         int rc = hnsw_half_opclass(c, who);
         if (rc) return rc;
     }
-    if (c->half && !half_entry) return fail(VSR_ERR_UNSUPPORTED, "%s: %s", who, HNSW_HALF_ENTRY);
-    if (c->sparse) return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
-    if (c->bit && !bit_metric)
+    if (c->format == RowFormat::HALF && expect != RowFormat::HALF) return fail(VSR_ERR_UNSUPPORTED, "%s: %s", who, HNSW_HALF_ENTRY);
+    if (c->format == RowFormat::SPARSE) return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
+    if (c->format == RowFormat::BIT && expect != RowFormat::BIT)
         return fail(VSR_ERR_UNSUPPORTED, "%s: the graph of a bit corpus is loaded with vsr_hnsw_load_bit (the bit_hamming_ops / bit_jaccard_ops opclasses)", who);
     if (m < 2 || m > 100)        /* reloption m: 2 .. HNSW_MAX_M (hnsw.h:36-40) */
         return fail(VSR_ERR_UNSUPPORTED, "%s: m must be between 2 and 100 (got %d)", who, m);
@@ -105,8 +106,8 @@ static int hnsw_load(vsr_corpus* c, int bit_metric, int m, int32_t n_elem, int32
     HIPCHK(hipSetDevice(ctx->device));
     std::unique_ptr<vsr_hnsw> h(new vsr_hnsw());
     h->corpus = c;
+    h->format = expect;
     h->bit_metric = bit_metric;
-    h->half = half_entry;
     h->n_elem = n_elem;
     h->entry = n_elem > 0 ? entry : -1;
     h->m = m;
@@ -147,7 +148,7 @@ extern "C" int vsr_hnsw_load(vsr_corpus* c, int m, int32_t n_elem, int32_t entry
                              const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
                              int32_t n_upper, int32_t max_level, vsr_hnsw** out)
 {
-    return hnsw_load(c, 0, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, out, "vsr_hnsw_load");
+    return hnsw_load(c, RowFormat::F32, 0, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, out, "vsr_hnsw_load");
 }
 
 extern "C" int vsr_hnsw_load_bit(vsr_corpus* c, int metric, int m, int32_t n_elem, int32_t entry, const int32_t* level,
@@ -158,55 +159,55 @@ extern "C" int vsr_hnsw_load_bit(vsr_corpus* c, int metric, int m, int32_t n_ele
     *out = nullptr;
     int rc = hnsw_bit_opclass(c, metric, "vsr_hnsw_load_bit");
     if (rc) return rc;
-    return hnsw_load(c, metric, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, out, "vsr_hnsw_load_bit");
+    return hnsw_load(c, RowFormat::BIT, metric, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, out, "vsr_hnsw_load_bit");
 }
 
 extern "C" int vsr_hnsw_load_half(vsr_corpus* c, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
                                   const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
                                   int32_t n_upper, int32_t max_level, vsr_hnsw** out)
 {
-    return hnsw_load(c, 0, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, out, "vsr_hnsw_load_half", true);
+    return hnsw_load(c, RowFormat::HALF, 0, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, out, "vsr_hnsw_load_half");
 }
 
 // CREATE INDEX ... USING hnsw on the GPU (vsr_hnsw_build.hip): batched insertion over the corpus's rows, levels from a seeded
 // xorshift64* stream drawn once per row.  flags = 0: element e = internal row e.  VSR_HNSW_BUILD_MERGE_DUPLICATES: the
 // elements come from vsr_hnsw_dedup.hip's table.  Returns a loaded index, as vsr_hnsw_load would from the same graph.
-// bit_entry (vsr_hnsw_build_bit): the corpus is a bit corpus, metric its opclass; the kernels take the bit row format
-// half_entry (vsr_hnsw_build_half): the corpus is a halfvec corpus; the kernels take the half row format
-static int hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out, const char* who,
-                      bool bit_entry = false, bool half_entry = false)
+// expect: the corpus format the entry point is for -- BIT (vsr_hnsw_build_bit; metric is the opclass), HALF (vsr_hnsw_build_half) or
+// F32; the kernels take that row format
+static int hnsw_build(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out,
+                      const char* who)
 {
     if (!c || !out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
     *out = nullptr;
-    if (bit_entry) {
+    if (expect == RowFormat::BIT) {
         int rc = hnsw_bit_opclass(c, metric, who);
         if (rc) return rc;
     }
-    if (half_entry) {
+    if (expect == RowFormat::HALF) {
         int rc = hnsw_half_opclass(c, who);
         if (rc) return rc;
     }
     if (flags & ~(uint32_t) VSR_HNSW_BUILD_MERGE_DUPLICATES) return fail(VSR_ERR_INVALID, "%s: unknown flag bits 0x%x", who, flags);
     if (c->base) return fail(VSR_ERR_INVALID, "%s: the corpus is a view", who);
-    if (c->half && !half_entry) return fail(VSR_ERR_UNSUPPORTED, "%s: %s", who, HNSW_HALF_ENTRY);
-    if (c->sparse) return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
-    if (c->bit && !bit_entry)
+    if (c->format == RowFormat::HALF && expect != RowFormat::HALF) return fail(VSR_ERR_UNSUPPORTED, "%s: %s", who, HNSW_HALF_ENTRY);
+    if (c->format == RowFormat::SPARSE) return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
+    if (c->format == RowFormat::BIT && expect != RowFormat::BIT)
         return fail(VSR_ERR_UNSUPPORTED, "%s: the graph of a bit corpus is built with vsr_hnsw_build_bit (the bit_hamming_ops / bit_jaccard_ops opclasses)", who);
     if (m < 2 || m > 100) return fail(VSR_ERR_UNSUPPORTED, "%s: m must be between 2 and 100 (got %d)", who, m);
     if (ef_construction < 4 || ef_construction > 1000 || ef_construction < 2 * m)      /* hnsw.c:62-63, hnswbuild.c:677-679 */
         return fail(VSR_ERR_UNSUPPORTED, "%s: ef_construction must be between 4 and 1000 and at least 2 * m (got %d)", who, ef_construction);
-    if (!bit_entry && metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)
+    if (expect != RowFormat::BIT && metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)
         return fail(VSR_ERR_UNSUPPORTED, "%s: L2, inner product and cosine operator classes only", who);
     vsr_ctx* ctx = c->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     const int64_t n = c->n;
     if (n > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "%s: too many rows", who);
     const bool merge = (flags & VSR_HNSW_BUILD_MERGE_DUPLICATES) != 0 && n > 0;
-    const uint32_t row_chunks = half_entry ? c->stride4 / 2 : c->stride4;    // 16-byte chunks per resident row
+    const uint32_t row_chunks = format_row_chunks(expect, c->dim);
     std::unique_ptr<vsr_hnsw> h(new vsr_hnsw());
     h->corpus = c;
-    h->bit_metric = bit_entry ? metric : 0;
-    h->half = half_entry;
+    h->format = expect;
+    h->bit_metric = expect == RowFormat::BIT ? metric : 0;
     h->m = m;
     // levels: level = floor(-ln(u) * ml), ml = 1 / ln(m) (hnswutils.c:243), capped like HnswGetMaxLevel (hnsw.h:89)
     int cap = (8192 - 24 - 8 - 4 - 4) / 6 / m - 2;
@@ -298,8 +299,8 @@ static int hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uin
     bp.rows = c->d_rows;
     bp.stride4 = row_chunks;
     bp.metric = metric == VSR_METRIC_L2 ? M_L2 : M_IP;
-    bp.halves = half_entry ? 1 : 0;
-    if (bit_entry) {
+    bp.halves = expect == RowFormat::HALF ? 1 : 0;
+    if (expect == RowFormat::BIT) {
         bp.bits = 1;
         bp.metric = metric == VSR_METRIC_JACCARD ? M_JACCARD : M_HAMMING;
         bp.row_pop = c->d_norm2;
@@ -380,22 +381,22 @@ static int hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uin
 
 extern "C" int vsr_hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, vsr_hnsw** out)
 {
-    return hnsw_build(c, m, ef_construction, metric, seed, 0u, out, "vsr_hnsw_build");
+    return hnsw_build(c, RowFormat::F32, m, ef_construction, metric, seed, 0u, out, "vsr_hnsw_build");
 }
 
 extern "C" int vsr_hnsw_build_ex(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out)
 {
-    return hnsw_build(c, m, ef_construction, metric, seed, flags, out, "vsr_hnsw_build_ex");
+    return hnsw_build(c, RowFormat::F32, m, ef_construction, metric, seed, flags, out, "vsr_hnsw_build_ex");
 }
 
 extern "C" int vsr_hnsw_build_bit(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out)
 {
-    return hnsw_build(c, m, ef_construction, metric, seed, flags, out, "vsr_hnsw_build_bit", true);
+    return hnsw_build(c, RowFormat::BIT, m, ef_construction, metric, seed, flags, out, "vsr_hnsw_build_bit");
 }
 
 extern "C" int vsr_hnsw_build_half(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out)
 {
-    return hnsw_build(c, m, ef_construction, metric, seed, flags, out, "vsr_hnsw_build_half", false, true);
+    return hnsw_build(c, RowFormat::HALF, m, ef_construction, metric, seed, flags, out, "vsr_hnsw_build_half");
 }
 
 // device memory of the graph arrays of an index (the corpus is counted by vsr_corpus_device_bytes); any index.  The row format
@@ -522,21 +523,18 @@ static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const HnswQueries& qs, int nq,
     vsr_corpus* c = h->corpus;
     HnswParams p{};
     p.rows = c->d_rows;
-    p.stride4 = c->stride4;
+    p.stride4 = format_row_chunks(h->format, c->dim);       // 16-byte chunks per row
     p.metric = metric;
     p.queries = qs.q;
     p.q_stride = qs.stride;
-    if (h->bit_metric) {
+    if (h->format == RowFormat::BIT) {
         p.metric = h->bit_metric == VSR_METRIC_JACCARD ? M_JACCARD : M_HAMMING;
         p.row_pop = c->d_norm2;
         p.q_pop = qs.pop;
         p.out_keys = out.keys;
         p.key_row_offset = (uint32_t) c->row_offset;
     }
-    if (h->half) {                                          // K4h: 16-byte chunks per row; rows past 64 chunks keep the query in LDS
-        p.stride4 = c->stride4 / 2;
-        p.q_chunks = p.stride4 > 64u ? p.stride4 : 0u;
-    }
+    if (h->format == RowFormat::HALF) p.q_chunks = p.stride4 > 64u ? p.stride4 : 0u;   // K4h: rows past 64 chunks keep the query in LDS
     p.dim = (uint32_t) c->dim;
     p.nq = (uint32_t) nq;
     p.n_elem = (uint32_t) h->n_elem;
@@ -603,28 +601,27 @@ static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const HnswQueries& qs, int nq,
     p.out_visited = d_vis;
     p.out_status = d_status;
     p.err = ctx->err_word();
-    if (h->bit_metric) HIPCHK(iter ? launch_hnsw_bit_iterative(p, ctx->stream) : launch_hnsw_bit_search(p, ctx->stream));
-    else if (h->half) HIPCHK(iter ? launch_hnsw_half_iterative(p, ctx->stream) : launch_hnsw_half_search(p, ctx->stream));
-    else if (iter) HIPCHK(launch_hnsw_iterative(p, ctx->stream));
-    else HIPCHK(launch_hnsw_search(p, ctx->stream));
+    HIPCHK(launch_hnsw(h->format, iter != nullptr, p, ctx->stream));
     h->last_mode = p.vis_mode;
     return VSR_OK;
 }
 
 static const char* bit_metric_name(int metric) { return metric == VSR_METRIC_JACCARD ? "Jaccard (5, bit_jaccard_ops)" : "Hamming (4, bit_hamming_ops)"; }
 
-// bit_entry: the caller is a vsr_hnsw_search_bit* entry point (a bit index, `dim` bits, the index's own metric)
+// entry: the queries the entry point takes -- BIT: a vsr_hnsw_search_bit* one (a bit index, `dim` bits, the index's own metric); F32
+// otherwise
 static int hnsw_check(vsr_hnsw* h, const void* queries, int nq, int dim, int k, int ef, int metric, const vsr_filter* const* filters,
-                      const char* who, bool bit_entry = false)
+                      const char* who, RowFormat entry)
 {
     if (!h) return fail(VSR_ERR_INVALID, "%s: index is NULL", who);
-    if (bit_entry && !h->bit_metric)
+    const bool bit_index = h->format == RowFormat::BIT;
+    if (entry == RowFormat::BIT && !bit_index)
         return fail(VSR_ERR_INVALID, "%s: the index is not over a bit corpus (it is searched with vsr_hnsw_search*)", who);
-    if (!bit_entry && h->bit_metric)
+    if (entry != RowFormat::BIT && bit_index)
         return fail(VSR_ERR_UNSUPPORTED, "%s: the index is over a bit corpus: it is searched with vsr_hnsw_search_bit* (<~> / <%%>)", who);
-    int rc = check_search_args(h->corpus, queries, nq, dim, k, metric, filters, who, bit_entry);
+    int rc = check_search_args(h->corpus, queries, nq, dim, k, metric, filters, who, entry);
     if (rc) return rc;
-    if (bit_entry && metric != h->bit_metric)               // an index belongs to one opclass: the metric only catches misuse
+    if (bit_index && metric != h->bit_metric)               // an index belongs to one opclass: the metric only catches misuse
         return fail(VSR_ERR_INVALID, "%s: the index was made for %s, the search asks for %s", who, bit_metric_name(h->bit_metric),
                     bit_metric_name(metric));
     if (metric == VSR_METRIC_L1) return fail(VSR_ERR_UNSUPPORTED, "%s: L1 graphs are not supported", who);
@@ -706,13 +703,13 @@ static int hnsw_doc_scratch(vsr_hnsw* h, int nq, int k, int32_t*& d_doc)
 // staged (hnsw_stage_bits) in front of every launch.
 struct HnswEntry {
     const char* who;
-    bool        bit;
-    size_t bytes(int dim) const { return bit ? (size_t) (dim + 7) / 8 : (size_t) dim * sizeof(float); }
+    RowFormat   queries;                                    // F32 or BIT
+    size_t bytes(int dim) const { return format_query_bytes(queries, dim); }
     // queries resident at d_q -> what hnsw_launch takes (bit: one staging launch on the stream)
     int resident(vsr_hnsw* h, vsr_ctx* ctx, const void* d_q, int nq, int dim, HnswQueries& qs) const
     {
         qs = {static_cast<const float*>(d_q), (uint32_t) dim, nullptr};
-        return bit ? hnsw_stage_bits(h, ctx, static_cast<const uint8_t*>(d_q), nq, qs) : VSR_OK;
+        return queries == RowFormat::BIT ? hnsw_stage_bits(h, ctx, static_cast<const uint8_t*>(d_q), nq, qs) : VSR_OK;
     }
 };
 
@@ -721,7 +718,7 @@ static int hnsw_search_device(const HnswEntry& en, vsr_hnsw* h, const void* d_qu
                               const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc, int64_t* d_row, float* d_dist,
                               int32_t* d_cnt, int64_t* d_visited)
 {
-    int rc = hnsw_check(h, d_queries, nq, dim, k, ef, metric, filters, en.who, en.bit);
+    int rc = hnsw_check(h, d_queries, nq, dim, k, ef, metric, filters, en.who, en.queries);
     if (rc) return rc;
     if (nq == 0) return VSR_OK;
     if (!d_blk || !d_dist || !d_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", en.who);
@@ -741,7 +738,7 @@ extern "C" int vsr_hnsw_search_device(vsr_hnsw* h, const float* d_queries, int n
                                       const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc, int64_t* d_row,
                                       float* d_dist, int32_t* d_cnt, int64_t* d_visited)
 {
-    return hnsw_search_device({"vsr_hnsw_search_device", false}, h, d_queries, nq, dim, k, ef, metric, filters, d_blk, d_doc, d_row, d_dist,
+    return hnsw_search_device({"vsr_hnsw_search_device", RowFormat::F32}, h, d_queries, nq, dim, k, ef, metric, filters, d_blk, d_doc, d_row, d_dist,
                               d_cnt, d_visited);
 }
 
@@ -749,7 +746,7 @@ extern "C" int vsr_hnsw_search_bit_device(vsr_hnsw* h, const uint8_t* d_queries,
                                           const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc, int64_t* d_row,
                                           float* d_dist, int32_t* d_cnt, int64_t* d_visited)
 {
-    return hnsw_search_device({"vsr_hnsw_search_bit_device", true}, h, d_queries, nq, dim, k, ef, metric, filters, d_blk, d_doc, d_row,
+    return hnsw_search_device({"vsr_hnsw_search_bit_device", RowFormat::BIT}, h, d_queries, nq, dim, k, ef, metric, filters, d_blk, d_doc, d_row,
                               d_dist, d_cnt, d_visited);
 }
 
@@ -797,11 +794,11 @@ static int hnsw_search_host(const HnswEntry& en, vsr_hnsw* h, const void* querie
                             const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc, int64_t* out_row, float* out_dist,
                             int32_t* out_cnt, int64_t* out_visited)
 {
-    int rc = hnsw_check(h, queries, nq, dim, k, ef, metric, filters, en.who, en.bit);
+    int rc = hnsw_check(h, queries, nq, dim, k, ef, metric, filters, en.who, en.queries);
     if (rc) return rc;
     if (nq == 0) return VSR_OK;
     if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", en.who);
-    if (h->half && (rc = half_query_range(queries, nq, dim))) return rc;
+    if (h->format == RowFormat::HALF && (rc = half_query_range(queries, nq, dim))) return rc;
     vsr_ctx* ctx = h->corpus->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     // tier 1: queries whose LDS visited table overflowed (big graphs only) are re-run with the global bitmap
@@ -822,7 +819,7 @@ extern "C" int vsr_hnsw_search(vsr_hnsw* h, const float* queries, int nq, int di
                                const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc, int64_t* out_row,
                                float* out_dist, int32_t* out_cnt, int64_t* out_visited)
 {
-    return hnsw_search_host({"vsr_hnsw_search", false}, h, queries, nq, dim, k, ef, metric, filters, out_blk, out_doc, out_row, out_dist,
+    return hnsw_search_host({"vsr_hnsw_search", RowFormat::F32}, h, queries, nq, dim, k, ef, metric, filters, out_blk, out_doc, out_row, out_dist,
                             out_cnt, out_visited);
 }
 
@@ -830,7 +827,7 @@ extern "C" int vsr_hnsw_search_bit(vsr_hnsw* h, const uint8_t* queries, int nq, 
                                    const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc, int64_t* out_row,
                                    float* out_dist, int32_t* out_cnt, int64_t* out_visited)
 {
-    return hnsw_search_host({"vsr_hnsw_search_bit", true}, h, queries, nq, dim, k, ef, metric, filters, out_blk, out_doc, out_row, out_dist,
+    return hnsw_search_host({"vsr_hnsw_search_bit", RowFormat::BIT}, h, queries, nq, dim, k, ef, metric, filters, out_blk, out_doc, out_row, out_dist,
                             out_cnt, out_visited);
 }
 
@@ -841,7 +838,7 @@ static int hnsw_iter_check(vsr_hnsw* h, const void* queries, int nq, int dim, in
                            const vsr_filter* const* filters, int mode, int64_t max_scan_tuples, const HnswEntry& en)
 {
     const char* who = en.who;
-    int rc = hnsw_check(h, queries, nq, dim, k, ef, metric, filters, who, en.bit);
+    int rc = hnsw_check(h, queries, nq, dim, k, ef, metric, filters, who, en.queries);
     if (rc) return rc;
     if (mode < VSR_HNSW_ITERATIVE_OFF || mode > VSR_HNSW_ITERATIVE_STRICT) return fail(VSR_ERR_INVALID, "%s: iterative scan mode %d", who, mode);
     if (max_scan_tuples < 1 || max_scan_tuples > INT_MAX)   /* hnsw.max_scan_tuples: 1 .. INT_MAX (hnsw.c:95-97) */
@@ -912,7 +909,7 @@ extern "C" int vsr_hnsw_search_iterative_device(vsr_hnsw* h, const float* d_quer
                                                 int64_t* d_blk, int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt,
                                                 int64_t* d_tuples)
 {
-    return hnsw_iterative_device({"vsr_hnsw_search_iterative_device", false}, h, d_queries, nq, dim, k, ef, metric, filters, mode,
+    return hnsw_iterative_device({"vsr_hnsw_search_iterative_device", RowFormat::F32}, h, d_queries, nq, dim, k, ef, metric, filters, mode,
                                  max_scan_tuples, d_blk, d_doc, d_row, d_dist, d_cnt, d_tuples);
 }
 
@@ -921,7 +918,7 @@ extern "C" int vsr_hnsw_search_bit_iterative_device(vsr_hnsw* h, const uint8_t* 
                                                     int64_t* d_blk, int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt,
                                                     int64_t* d_tuples)
 {
-    return hnsw_iterative_device({"vsr_hnsw_search_bit_iterative_device", true}, h, d_queries, nq, dim, k, ef, metric, filters, mode,
+    return hnsw_iterative_device({"vsr_hnsw_search_bit_iterative_device", RowFormat::BIT}, h, d_queries, nq, dim, k, ef, metric, filters, mode,
                                  max_scan_tuples, d_blk, d_doc, d_row, d_dist, d_cnt, d_tuples);
 }
 
@@ -936,7 +933,7 @@ static int hnsw_iterative_host(const HnswEntry& en, vsr_hnsw* h, const void* que
         return hnsw_search_host(en, h, queries, nq, dim, k, ef, metric, filters, out_blk, out_doc, out_row, out_dist, out_cnt, out_tuples);
     if (nq == 0) return VSR_OK;
     if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", en.who);
-    if (h->half && (rc = half_query_range(queries, nq, dim))) return rc;
+    if (h->format == RowFormat::HALF && (rc = half_query_range(queries, nq, dim))) return rc;
     vsr_ctx* ctx = h->corpus->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     // tier 1: queries whose D overflowed, again with room for every element (an element is in at most one of D, W, emitted)
@@ -955,7 +952,7 @@ extern "C" int vsr_hnsw_search_iterative(vsr_hnsw* h, const float* queries, int 
                                          const vsr_filter* const* filters, int mode, int64_t max_scan_tuples, int64_t* out_blk,
                                          int32_t* out_doc, int64_t* out_row, float* out_dist, int32_t* out_cnt, int64_t* out_tuples)
 {
-    return hnsw_iterative_host({"vsr_hnsw_search_iterative", false}, h, queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples,
+    return hnsw_iterative_host({"vsr_hnsw_search_iterative", RowFormat::F32}, h, queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples,
                                out_blk, out_doc, out_row, out_dist, out_cnt, out_tuples);
 }
 
@@ -963,7 +960,7 @@ extern "C" int vsr_hnsw_search_bit_iterative(vsr_hnsw* h, const uint8_t* queries
                                              const vsr_filter* const* filters, int mode, int64_t max_scan_tuples, int64_t* out_blk,
                                              int32_t* out_doc, int64_t* out_row, float* out_dist, int32_t* out_cnt, int64_t* out_tuples)
 {
-    return hnsw_iterative_host({"vsr_hnsw_search_bit_iterative", true}, h, queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples,
+    return hnsw_iterative_host({"vsr_hnsw_search_bit_iterative", RowFormat::BIT}, h, queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples,
                                out_blk, out_doc, out_row, out_dist, out_cnt, out_tuples);
 }
 
@@ -1014,9 +1011,9 @@ static int hnsw_quantized_check(vsr_corpus* src, vsr_hnsw* h, const void* querie
     if (!h) return fail(VSR_ERR_INVALID, "%s: index is NULL", who);
     int rc = check_quantized_args(nullptr, src, h->corpus, queries, nq, dim, k, shortlist, metric, filters, who);
     if (rc) return rc;
-    if (h->bit_metric != VSR_METRIC_HAMMING)
+    if (h->format != RowFormat::BIT || h->bit_metric != VSR_METRIC_HAMMING)
         return fail(VSR_ERR_INVALID, "%s: the index was made for %s: the shortlist of binary_quantize needs a Hamming index", who,
-                    h->bit_metric ? bit_metric_name(h->bit_metric) : "a corpus that is not a bit corpus");
+                    h->format == RowFormat::BIT ? bit_metric_name(h->bit_metric) : "a corpus that is not a bit corpus");
     if (ef < 1 || ef > 5000) return fail(VSR_ERR_INVALID, "%s: ef_search must be between 1 and 5000 (got %d)", who, ef);
     return VSR_OK;
 }
@@ -1044,7 +1041,7 @@ extern "C" int vsr_hnsw_search_quantized(vsr_corpus* src, vsr_hnsw* h, const flo
     if (rc) return rc;
     if (nq == 0) return VSR_OK;
     if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", who);
-    if (src->half && (rc = half_query_range(queries, nq, dim))) return rc;     // `$1::halfvec`, as vsr_search refuses it
+    if (src->format == RowFormat::HALF && (rc = half_query_range(queries, nq, dim))) return rc;   // `$1::halfvec`, as vsr_search refuses it
     vsr_ctx* ctx = h->corpus->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     const ResultBlock rb(nq, k, false);                     // results and stage 1's status words: one packed copy back, one wait

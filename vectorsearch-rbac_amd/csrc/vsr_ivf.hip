@@ -37,8 +37,7 @@ struct vsr_ivf {
     vsr_corpus* main = nullptr;
     vsr_corpus* view = nullptr;                      // list-ordered rows; view->base = main
     int         lists = 0;
-    bool        half = false;                        // vsr_ivf_load_half: binary16 rows (the view's) and binary16 centres (K3h)
-    void*       d_centers = nullptr;                 // [dim][lists] fp32, or binary16 when half
+    void*       d_centers = nullptr;                 // [dim][lists] fp32; binary16 when the view's rows are (vsr_ivf_load_half, K3h)
     std::vector<uint32_t> list_start;                // lists + 1 offsets into the view
     std::vector<vsr_filter*> list_filters;           // one RANGES filter per list (tiles over the view)
     struct ViewBitmap { uint64_t* d = nullptr; std::vector<uint64_t> h; };
@@ -49,6 +48,8 @@ struct vsr_ivf {
     PinBuf h_vb;                                     // iterative scan: per query, its view bitmap's device address
     DevBuf d_res;                                    // iterative scan, host form: the results before they go back
 };
+
+static bool ivf_half(const vsr_ivf* ivf) { return ivf->view->format == RowFormat::HALF; }
 
 extern "C" int vsr_ivf_free(vsr_ivf* ivf)
 {
@@ -76,16 +77,16 @@ extern "C" int vsr_ivf_free(vsr_ivf* ivf)
     return VSR_OK;
 }
 
-// what vsr_ivf_load / vsr_ivf_assign and their _half forms refuse alike (half_entry: the caller is a _half entry point)
-static int ivf_check_corpus(const vsr_corpus* c, bool half_entry, int lists, const char* who)
+// what vsr_ivf_load / vsr_ivf_assign (expect = F32) and their _half forms (HALF) refuse alike
+static int ivf_check_corpus(const vsr_corpus* c, RowFormat expect, int lists, const char* who)
 {
     if (c->base) return fail(VSR_ERR_INVALID, "%s: the corpus is a view", who);
-    if (half_entry && !c->half) return fail(VSR_ERR_INVALID, "%s: the corpus is not a halfvec corpus", who);
-    if (c->half && !half_entry)
+    if (expect == RowFormat::HALF && c->format != RowFormat::HALF) return fail(VSR_ERR_INVALID, "%s: the corpus is not a halfvec corpus", who);
+    if (c->format == RowFormat::HALF && expect != RowFormat::HALF)
         return fail(VSR_ERR_UNSUPPORTED, "%s: a halfvec corpus is indexed with vsr_ivf_kmeans_half / vsr_ivf_assign_half / vsr_ivf_load_half "
                     "(the halfvec_*_ops opclasses)", who);
-    if (c->sparse) return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
-    if (c->bit) return fail(VSR_ERR_UNSUPPORTED, "%s: a bit corpus has no index path yet (the bit_hamming_ops / bit_jaccard_ops opclasses)", who);
+    if (c->format == RowFormat::SPARSE) return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
+    if (c->format == RowFormat::BIT) return fail(VSR_ERR_UNSUPPORTED, "%s: a bit corpus has no index path yet (the bit_hamming_ops / bit_jaccard_ops opclasses)", who);
     if (lists < 1 || lists > 32768)      /* reloption lists: 1 .. IVFFLAT_MAX_LISTS (ivfflat.h:42-44) */
         return fail(VSR_ERR_UNSUPPORTED, "%s: lists must be between 1 and 32768 (got %d)", who, lists);
     return VSR_OK;
@@ -96,10 +97,10 @@ static int ivf_check_corpus(const vsr_corpus* c, bool half_entry, int lists, con
 template <class T>
 static int ivf_load(vsr_corpus* c, const T* centers, int lists, const int32_t* row_list, vsr_ivf** out, const char* who)
 {
-    constexpr bool HALF = std::is_same<T, uint16_t>::value;
+    constexpr RowFormat FMT = std::is_same<T, uint16_t>::value ? RowFormat::HALF : RowFormat::F32;
     if (!c || !out || !centers || (c->n > 0 && !row_list)) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
     *out = nullptr;
-    int rc = ivf_check_corpus(c, HALF, lists, who);
+    int rc = ivf_check_corpus(c, FMT, lists, who);
     if (rc) return rc;
     vsr_ctx* ctx = c->ctx;
     HIPCHK(hipSetDevice(ctx->device));
@@ -109,7 +110,6 @@ static int ivf_load(vsr_corpus* c, const T* centers, int lists, const int32_t* r
     std::unique_ptr<vsr_ivf> ivf(new vsr_ivf());
     ivf->main = c;
     ivf->lists = lists;
-    ivf->half = HALF;
     // view order: by list, then by base row (= (document_id, block_id) order inside a list)
     std::vector<uint32_t> count((size_t) lists + 1, 0);
     for (int64_t r = 0; r < n; ++r) count[(size_t) row_list[c->h_orig[(size_t) r]] + 1]++;
@@ -129,9 +129,8 @@ static int ivf_load(vsr_corpus* c, const T* centers, int lists, const int32_t* r
     v->shape = c->shape;
     v->base = c;
     v->k2_safe = c->k2_safe;
-    v->half = HALF;
-    // 16-byte chunks per stored row: a halfvec row is stride4 / 2 chunks of 8 halves (the gather moves chunks, whatever they hold)
-    const uint32_t row_chunks = HALF ? c->stride4 / 2 : c->stride4;
+    v->format = FMT;
+    const uint32_t row_chunks = format_row_chunks(FMT, c->dim);   // (the gather moves 16-byte chunks, whatever they hold)
     const size_t alloc_rows = (size_t) std::max<int64_t>(n, 1), row_bytes = (size_t) row_chunks * 16;
     HIPCHK(hipMalloc(&v->d_rank, alloc_rows * sizeof(uint32_t)));
     HIPCHK(hipMemcpy(v->d_rank, rank.data(), alloc_rows * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -189,9 +188,9 @@ extern "C" int64_t vsr_ivf_device_bytes(const vsr_ivf* ivf)
     if (!ivf) return 0;
     const vsr_corpus* v = ivf->view;
     const size_t rows = (size_t) std::max<int64_t>(v->n, 1);
-    size_t b = rows * (v->half ? v->stride4 / 2 : v->stride4) * 16 + 1024 + rows * sizeof(float) + rows * sizeof(uint32_t);
+    size_t b = rows * format_row_chunks(v->format, v->dim) * 16 + 1024 + rows * sizeof(float) + rows * sizeof(uint32_t);
     if (v->d_scr) b += rows * (size_t) v->pstride4 * 16 + 1024;
-    b += (size_t) ivf->lists * v->dim * (ivf->half ? 2 : 4) + ((size_t) ivf->lists + 1) * sizeof(uint32_t);
+    b += (size_t) ivf->lists * v->dim * (ivf_half(ivf) ? 2 : 4) + ((size_t) ivf->lists + 1) * sizeof(uint32_t);
     return (int64_t) b;
 }
 
@@ -280,7 +279,7 @@ static int ivf_probe_lists(vsr_ivf* ivf, const float* d_queries, int nq, int dim
     // (vector.sql:323-327)
     HIPCHK(launch_ivf_probe(d_queries, (uint32_t) dim, (uint32_t) nq, ivf->d_centers, dim, ivf->lists, probes,
                             metric == VSR_METRIC_L2 ? M_L2 : M_IP, ivf->d_probe.as<int32_t>(), ctx->stream,
-                            ivf->half ? IVF_HALF_Q32 : IVF_F32));
+                            ivf_half(ivf) ? IVF_HALF_Q32 : IVF_F32));
     HIPCHK(hipMemcpyAsync(out_lists, ivf->d_probe.p, (size_t) nq * probes * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return VSR_OK;
@@ -352,7 +351,7 @@ extern "C" int vsr_ivf_search(vsr_ivf* ivf, const float* queries, int nq, int di
 {
     int rc = ivf_check(ivf, queries, nq, dim, k, probes, metric, filters, out_blk, out_dist, out_cnt, "vsr_ivf_search");
     if (rc || nq == 0) return rc;
-    if (ivf->half && (rc = half_query_range(queries, nq, dim))) return rc;     // `$1::halfvec`, as vsr_search refuses it
+    if (ivf_half(ivf) && (rc = half_query_range(queries, nq, dim))) return rc;   // `$1::halfvec`, as vsr_search refuses it
     vsr_ctx* ctx = ivf->main->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     if ((rc = ivf->d_q.reserve((size_t) nq * dim * sizeof(float)))) return rc;
@@ -436,7 +435,7 @@ extern "C" int vsr_ivf_search_iterative_device(vsr_ivf* ivf, const float* d_quer
     p.k = (uint32_t) k;
     p.list_start = ivf->d_list_start;
     p.rows = v->d_rows;
-    p.rows_half = ivf->half ? 1u : 0u;
+    p.rows_half = ivf_half(ivf) ? 1u : 0u;
     p.stride4 = v->stride4;
     p.n_rows = (uint32_t) v->n;
     p.rank = v->d_rank;
@@ -465,7 +464,7 @@ extern "C" int vsr_ivf_search_iterative(vsr_ivf* ivf, const float* queries, int 
         if (out_probes) std::fill(out_probes, out_probes + nq, (int32_t) probes);
         return VSR_OK;
     }
-    if (ivf->half && (rc = half_query_range(queries, nq, dim))) return rc;
+    if (ivf_half(ivf) && (rc = half_query_range(queries, nq, dim))) return rc;
     vsr_ctx* ctx = ivf->main->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     // queries up, the device form, results down
@@ -490,10 +489,10 @@ extern "C" int vsr_ivf_probe(vsr_ivf* ivf, const float* queries, int nq, int dim
 {
     if (!ivf || !queries || !out_lists || nq < 0) return fail(VSR_ERR_INVALID, "vsr_ivf_probe: NULL argument");
     if (dim != ivf->main->dim)
-        return fail(VSR_ERR_DIM_MISMATCH, "different %s dimensions %d and %d", ivf->half ? "halfvec" : "vector", ivf->main->dim, dim);
+        return fail(VSR_ERR_DIM_MISMATCH, "different %s dimensions %d and %d", format_name(ivf->main->format), ivf->main->dim, dim);
     if (probes < 1) return fail(VSR_ERR_INVALID, "vsr_ivf_probe: probes must be >= 1 (got %d)", probes);
     if (nq == 0) return VSR_OK;
-    if (ivf->half) {
+    if (ivf_half(ivf)) {
         int rr = half_query_range(queries, nq, dim);
         if (rr) return rr;
     }
@@ -514,9 +513,9 @@ extern "C" int vsr_ivf_probe(vsr_ivf* ivf, const float* queries, int nq, int dim
 template <class T>
 static int ivf_assign(vsr_corpus* c, const T* centers, int lists, int metric, int32_t* out_row_list, const char* who)
 {
-    constexpr bool HALF = std::is_same<T, uint16_t>::value;
+    constexpr RowFormat FMT = std::is_same<T, uint16_t>::value ? RowFormat::HALF : RowFormat::F32;
     if (!c || !centers || (c->n > 0 && !out_row_list)) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
-    int rc = ivf_check_corpus(c, HALF, lists, who);
+    int rc = ivf_check_corpus(c, FMT, lists, who);
     if (rc) return rc;
     if (metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)
         return fail(VSR_ERR_UNSUPPORTED, "%s: metric %d has no ivfflat opclass", who, metric);
@@ -531,7 +530,7 @@ static int ivf_assign(vsr_corpus* c, const T* centers, int lists, int metric, in
     HIPCHK(hipMemcpyAsync(d_centers.p, ct.data(), ct.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     // cosine opclass: rows and centres are compared by the negative inner product (spherical k-means, vector.sql:323-327)
     HIPCHK(launch_ivf_probe(c->d_rows, (uint32_t) c->stride4 * 4, (uint32_t) n, d_centers.p, c->dim, lists, 1,
-                            metric == VSR_METRIC_L2 ? M_L2 : M_IP, d_out.as<int32_t>(), ctx->stream, HALF ? IVF_HALF_ROW : IVF_F32));
+                            metric == VSR_METRIC_L2 ? M_L2 : M_IP, d_out.as<int32_t>(), ctx->stream, FMT == RowFormat::HALF ? IVF_HALF_ROW : IVF_F32));
     std::vector<int32_t> by_internal((size_t) n);
     HIPCHK(hipMemcpyAsync(by_internal.data(), d_out.p, (size_t) n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));

@@ -6,78 +6,41 @@
 
 namespace vsr {
 
-// per-metric scan launchers live in their own translation units (vsr_scan_*.hip)
-hipError_t launch_scan_l2(const ScanParams&, int, int, uint32_t, hipStream_t);
-hipError_t launch_scan_ip(const ScanParams&, int, int, uint32_t, hipStream_t);
-hipError_t launch_scan_cosine(const ScanParams&, int, int, uint32_t, hipStream_t);
-hipError_t launch_scan_l1(const ScanParams&, int, int, uint32_t, hipStream_t);
-// ... and K1h's (vsr_scanh_*.hip)
-hipError_t launch_scanh_l2(const ScanParams&, int, int, uint32_t, hipStream_t);
-hipError_t launch_scanh_ip(const ScanParams&, int, int, uint32_t, hipStream_t);
-hipError_t launch_scanh_cosine(const ScanParams&, int, int, uint32_t, hipStream_t);
-hipError_t launch_scanh_l1(const ScanParams&, int, int, uint32_t, hipStream_t);
-// ... and K1b (vsr_scanb_*.hip)
-hipError_t launch_scanb_hamming(const ScanParams&, int, int, uint32_t, hipStream_t);
-hipError_t launch_scanb_jaccard(const ScanParams&, int, int, uint32_t, hipStream_t);
+// the launcher of `metric` among a family's per-metric ones (vsr_device.h); nullptr: the family has no such form
+template <class F> static F* by_metric(int metric, F* l2, F* ip, F* cosine, F* l1 = nullptr)
+{
+    switch (metric) {
+    case M_L2:     return l2;
+    case M_IP:     return ip;
+    case M_COSINE: return cosine;
+    case M_L1:     return l1;
+    default:       return nullptr;
+    }
+}
 
-hipError_t launch_mq_l2(const ScanParams&, uint32_t, hipStream_t);
-hipError_t launch_mq_ip(const ScanParams&, uint32_t, hipStream_t);
-hipError_t launch_mq_cosine(const ScanParams&, uint32_t, hipStream_t);
-hipError_t launch_mq_l1(const ScanParams&, uint32_t, hipStream_t);
-
-hipError_t launch_mfma_l2(const ScanParams&, uint32_t, hipStream_t);
-hipError_t launch_mfma_ip(const ScanParams&, uint32_t, hipStream_t);
-hipError_t launch_mfma_cosine(const ScanParams&, uint32_t, hipStream_t);
-hipError_t launch_mfmah_l2(const ScanParams&, uint32_t, hipStream_t);
-hipError_t launch_mfmah_ip(const ScanParams&, uint32_t, hipStream_t);
-hipError_t launch_mfmah_cosine(const ScanParams&, uint32_t, hipStream_t);
-
-hipError_t launch_mfmaw_l2(const ScanParams&, uint32_t, hipStream_t);
-hipError_t launch_mfmaw_ip(const ScanParams&, uint32_t, hipStream_t);
-hipError_t launch_mfmaw_cosine(const ScanParams&, uint32_t, hipStream_t);
-
-hipError_t launch_gemm_l2(const ScanParams&, uint32_t, hipStream_t);
-hipError_t launch_gemm_ip(const ScanParams&, uint32_t, hipStream_t);
-hipError_t launch_gemm_cosine(const ScanParams&, uint32_t, hipStream_t);
+static hipError_t launch_pass(PassLaunch* f, const ScanParams& p, uint32_t n_blocks, hipStream_t s)
+{
+    return f ? f(p, n_blocks, s) : hipErrorInvalidValue;
+}
 
 hipError_t launch_gemm(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s)
 {
-    switch (metric) {
-    case M_L2:     return launch_gemm_l2(p, n_blocks, s);
-    case M_IP:     return launch_gemm_ip(p, n_blocks, s);
-    case M_COSINE: return launch_gemm_cosine(p, n_blocks, s);
-    default:       return hipErrorInvalidValue;
-    }
+    return launch_pass(by_metric(metric, launch_gemm_l2, launch_gemm_ip, launch_gemm_cosine), p, n_blocks, s);
 }
 
 hipError_t launch_mfmaw(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s)
 {
-    switch (metric) {
-    case M_L2:     return launch_mfmaw_l2(p, n_blocks, s);
-    case M_IP:     return launch_mfmaw_ip(p, n_blocks, s);
-    case M_COSINE: return launch_mfmaw_cosine(p, n_blocks, s);
-    default:       return hipErrorInvalidValue;
-    }
+    return launch_pass(by_metric(metric, launch_mfmaw_l2, launch_mfmaw_ip, launch_mfmaw_cosine), p, n_blocks, s);
 }
 
 hipError_t launch_mfma(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s)
 {
-    switch (metric) {
-    case M_L2:     return launch_mfma_l2(p, n_blocks, s);
-    case M_IP:     return launch_mfma_ip(p, n_blocks, s);
-    case M_COSINE: return launch_mfma_cosine(p, n_blocks, s);
-    default:       return hipErrorInvalidValue;
-    }
+    return launch_pass(by_metric(metric, launch_mfma_l2, launch_mfma_ip, launch_mfma_cosine), p, n_blocks, s);
 }
 
 hipError_t launch_mfmah(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s)
 {
-    switch (metric) {
-    case M_L2:     return launch_mfmah_l2(p, n_blocks, s);
-    case M_IP:     return launch_mfmah_ip(p, n_blocks, s);
-    case M_COSINE: return launch_mfmah_cosine(p, n_blocks, s);
-    default:       return hipErrorInvalidValue;
-    }
+    return launch_pass(by_metric(metric, launch_mfmah_l2, launch_mfmah_ip, launch_mfmah_cosine), p, n_blocks, s);
 }
 
 bool mq_supported(int dim) { return (dim + 3) / 4 >= 16; }
@@ -97,17 +60,11 @@ int mq_qmax(int dim)
 
 hipError_t launch_mq(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s)
 {
-    switch (metric) {
-    case M_L2:     return launch_mq_l2(p, n_blocks, s);
-    case M_IP:     return launch_mq_ip(p, n_blocks, s);
-    case M_COSINE: return launch_mq_cosine(p, n_blocks, s);
-    case M_L1:     return launch_mq_l1(p, n_blocks, s);
-    default:       return hipErrorInvalidValue;
-    }
+    return launch_pass(by_metric(metric, launch_mq_l2, launch_mq_ip, launch_mq_cosine, launch_mq_l1), p, n_blocks, s);
 }
 
 // lanes per row, chunks per lane and row slots by the row's 16-byte chunks
-static KernelShape scan_shape_for_chunks(int d4)
+static KernelShape scan_shape_for_chunks(uint32_t d4)
 {
     if (d4 <= 1)   return {1, 1, 1, 64};
     if (d4 <= 4)   return {4, 1, 4, 64};
@@ -120,20 +77,12 @@ static KernelShape scan_shape_for_chunks(int d4)
     return {64, 0, 2, 2};
 }
 
-KernelShape scan_shape_for_dim(int dim) { return scan_shape_for_chunks((dim + 3) / 4); }
-// (a lane that widens 3 or 4 chunks of several rows for four queries runs out of registers: rows of more than 128 chunks,
-// d > 1024, stream chunk by chunk instead)
-KernelShape scan_shape_for_dim_half(int dim)
+// K1h: a lane that widens 3 or 4 chunks of several rows for four queries runs out of registers: rows of more than 128 chunks,
+// d > 1024, stream chunk by chunk instead.  K1b: the same rule by chunks of 128 bits; 64000 bits are 500 chunks
+KernelShape scan_shape(RowFormat f, int dim)
 {
-    const int d8 = (dim + 7) / 8;
-    return d8 <= 128 ? scan_shape_for_chunks(d8) : KernelShape{64, 0, 2, 2};
-}
-
-// (K1b: the same rule by chunks of 128 bits; 64000 bits are 500 chunks)
-KernelShape scan_shape_for_dim_bit(int dim)
-{
-    const int d128 = (dim + 127) / 128;
-    return d128 <= 128 ? scan_shape_for_chunks(d128) : KernelShape{64, 0, 2, 2};
+    const uint32_t chunks = format_row_chunks(f, dim);
+    return f == RowFormat::F32 || chunks <= 128 ? scan_shape_for_chunks(chunks) : KernelShape{64, 0, 2, 2};
 }
 
 uint32_t scan_cap_for_rw(int k, int rw)
@@ -145,11 +94,14 @@ uint32_t scan_cap_for_rw(int k, int rw)
     return cap;
 }
 
-uint32_t scan_cap_for_k(int k, int dim) { return scan_cap_for_rw(k, scan_shape_for_dim(dim).rw); }
+uint32_t scan_cap_for_k(int k, int dim) { return scan_cap_for_rw(k, scan_shape(RowFormat::F32, dim).rw); }
 
-// sh: the corpus's shape; stride4: float4 per padded query in LDS
-static int scan_qmax_for(const KernelShape& sh, uint32_t stride4, int k)
+int scan_qmax(RowFormat f, int dim, int k)
 {
+    const KernelShape sh = scan_shape(f, dim);
+    // float4 per padded query in LDS: K1h keeps fp32 queries, two float4 for every row chunk of 8 halves (K1b: queries are a few
+    // chunks, the candidate buffers bound the queries per pass)
+    const uint32_t stride4 = (f == RowFormat::HALF ? 2u : 1u) * format_row_chunks(f, dim);
     const size_t per_query = scan_lds_bytes(1, scan_cap_for_rw(k, sh.rw), stride4) - 16;
     int q = (int) (SCAN_LDS_BUDGET / per_query);
     if (sh.c == 0) q = q < 4 ? q : 4;            // runtime-chunk kernel: one sub-batch only
@@ -158,41 +110,17 @@ static int scan_qmax_for(const KernelShape& sh, uint32_t stride4, int k)
     return q;
 }
 
-int scan_qmax(int dim, int k) { return scan_qmax_for(scan_shape_for_dim(dim), (uint32_t) ((dim + 3) / 4), k); }
-int scan_qmax_half(int dim, int k) { return scan_qmax_for(scan_shape_for_dim_half(dim), 2u * (uint32_t) ((dim + 7) / 8), k); }
-
-// (queries are a few chunks: the candidate buffers bound the queries per pass)
-int scan_qmax_bit(int dim, int k) { return scan_qmax_for(scan_shape_for_dim_bit(dim), (uint32_t) ((dim + 127) / 128), k); }
-
-hipError_t launch_scan_bit(const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s)
+hipError_t launch_scan(RowFormat f, const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s, int sparse_lpr,
+                       bool sparse_global_tab)
 {
-    switch (metric) {
-    case 4:  return launch_scanb_hamming(p, dim, qi, n_blocks, s);
-    case 5:  return launch_scanb_jaccard(p, dim, qi, n_blocks, s);
-    default: return hipErrorInvalidValue;
+    if (f == RowFormat::SPARSE) {
+        SparseLaunch* k1s = by_metric(metric, launch_scans_l2, launch_scans_ip, launch_scans_cosine, launch_scans_l1);
+        return k1s ? k1s(p, sparse_lpr, qi, sparse_global_tab, n_blocks, s) : hipErrorInvalidValue;
     }
-}
-
-hipError_t launch_scan(const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s)
-{
-    switch (metric) {
-    case M_L2:     return launch_scan_l2(p, dim, qi, n_blocks, s);
-    case M_IP:     return launch_scan_ip(p, dim, qi, n_blocks, s);
-    case M_COSINE: return launch_scan_cosine(p, dim, qi, n_blocks, s);
-    case M_L1:     return launch_scan_l1(p, dim, qi, n_blocks, s);
-    default:       return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_scan_half(const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s)
-{
-    switch (metric) {
-    case M_L2:     return launch_scanh_l2(p, dim, qi, n_blocks, s);
-    case M_IP:     return launch_scanh_ip(p, dim, qi, n_blocks, s);
-    case M_COSINE: return launch_scanh_cosine(p, dim, qi, n_blocks, s);
-    case M_L1:     return launch_scanh_l1(p, dim, qi, n_blocks, s);
-    default:       return hipErrorInvalidValue;
-    }
+    ScanLaunch* k1 = f == RowFormat::BIT    ? (metric == 4 ? launch_scanb_hamming : metric == 5 ? launch_scanb_jaccard : nullptr)
+                     : f == RowFormat::HALF ? by_metric(metric, launch_scanh_l2, launch_scanh_ip, launch_scanh_cosine, launch_scanh_l1)
+                                            : by_metric(metric, launch_scan_l2, launch_scan_ip, launch_scan_cosine, launch_scan_l1);
+    return k1 ? k1(p, dim, qi, n_blocks, s) : hipErrorInvalidValue;
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -132,12 +132,13 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     // K1m, which reads fp32 rows, nor K2w / K2g / int8, which read planes it does not have)
     // (a bit corpus has packed bits only and an exact integer kernel, K1b: as with screening off, nothing else applies)
     // (a sparse corpus has CSR rows only and an exact kernel, K1s: planned like a bit corpus; the call's table size bounds the pass)
-    w.mq_ok = !c->half && !c->bit && !c->sparse && mq_supported(c->dim) && mq_qmax(c->dim) >= 4 && !ctx->no_mq;
+    const bool f32 = c->format == RowFormat::F32, half = c->format == RowFormat::HALF;
+    w.mq_ok = f32 && mq_supported(c->dim) && mq_qmax(c->dim) >= 4 && !ctx->no_mq;
     // K2 / K2w: matrix-core screening keeps 2k (>= 32) candidates per query, K5r re-ranks them exactly
     w.keep = (uint32_t) std::max(2 * in.k, 32);
-    const bool k2_any = !c->bit && !c->sparse && !(c->half && ctx->no_half_mfma) && allow_screening && ctx->screening && c->k2_safe && in.metric != VSR_METRIC_L1 &&
+    const bool k2_any = (f32 || (half && !ctx->no_half_mfma)) && allow_screening && ctx->screening && c->k2_safe && in.metric != VSR_METRIC_L1 &&
                         mq_supported(c->dim) && ctx->max_qb >= 16;
-    w.k2w_ok = k2_any && !c->half && allow_wide && c->d_scr && w.keep <= GQ_MAX_KP && !ctx->no_wide && ctx->seeding;
+    w.k2w_ok = k2_any && f32 && allow_wide && c->d_scr && w.keep <= GQ_MAX_KP && !ctx->no_wide && ctx->seeding;
     w.k2_ok = w.k2w_ok || (k2_any && mfma_cap_for_k(w.keep) <= 8192 && mfma_lds_bytes(c->stride4) <= 150 * 1024);
     w.wq = mfmaw_qmax(c->pstride4, !c->scr_has_mid);
     // K2g (coarse planes, 256-query passes): when nearly all (part, query) items sit in parts seen by more than 128
@@ -161,9 +162,12 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     const int legacy_qb = ctx->max_qb_set ? ctx->max_qb : 16;
     if (w.k2w_ok) w.qmax = ctx->max_qb_set ? std::min(ctx->max_qb, w.wq) : w.wq;
     else if (w.k2_ok) w.qmax = std::min(legacy_qb, mfma_qmax(c->stride4));
-    else w.qmax = std::min(legacy_qb, w.mq_ok ? mq_qmax(c->dim) : c->sparse ? scan_qmax_sparse(ctx->sparse_slots, in.k) :
-                                     c->bit ? scan_qmax_bit(c->dim, in.k) :
-                                     c->half ? scan_qmax_half(c->dim, in.k) : scan_qmax(c->dim, in.k));
+    else if (w.mq_ok) w.qmax = std::min(legacy_qb, mq_qmax(c->dim));
+    else
+        switch (c->format) {
+        case RowFormat::SPARSE: w.qmax = std::min(legacy_qb, scan_qmax_sparse(ctx->sparse_slots, in.k)); break;
+        default:                w.qmax = std::min(legacy_qb, scan_qmax(c->format, c->dim, in.k));
+        }
     if (w.k2_ok && !w.k2w_ok && !ctx->max_qb_set && w.qmax >= 16 && c->stride4 > 64) {
         // long rows (d > 256): a pass costs mostly its row bytes, so two 16-query MFMA groups per pass (half the passes)
         // pay off -- but only when the query groups fill them (an unfiltered 1000-query batch: 17 % less time at
@@ -227,7 +231,7 @@ void set_family(const PlanIn& in, const Width& w, uint32_t widest, Plan& plan)
     plan.mq = plan.qi == 4 && w.mq_ok && !plan.k2;
     plan.keep = plan.k2 ? w.keep : (uint32_t) in.k;
     // K1s: a table that does not fit LDS beside one candidate list is read from global memory, and then qmax = QI
-    plan.sparse_global = in.c->sparse && !scan_sparse_table_in_lds(in.ctx->sparse_slots, in.k);
+    plan.sparse_global = in.c->format == RowFormat::SPARSE && !scan_sparse_table_in_lds(in.ctx->sparse_slots, in.k);
     if (plan.k2w) plan.qmax = (uint32_t) w.wq;              // query slots per workgroup: one (long rows: two) 16-query groups per wave
     else if (plan.k2) plan.qmax = plan.qmax > 16 ? 32 : 16;
     plan.int8 = plan.k2w && in.c->d_scr8 && in.metric == VSR_METRIC_L2 && in.ctx->int8_this_call;
@@ -355,10 +359,10 @@ void emit_groups(const PlanIn& in, bool i8wide, const LaunchSize& ls, PlanScratc
         plan.n_partial_s += gs.n_blocks * p.q_count;
         plan.scan_rows += p.rows;
         plan.scan_pairs += p.rows * (int64_t) p.q_count;
-        const int64_t row_bytes = c->bit ? (c->dim + 7) / 8 : (int64_t) c->dim * (c->half ? 2 : 4);
         // (sparse corpus: 8 bytes per stored entry -- a filter part's rows at the corpus's mean entry count)
-        const int64_t rows_bytes = c->sparse ? (int64_t) ((__int128) p.rows * (__int128) c->sp_entries * 8 / std::max<int64_t>(c->n, 1))
-                                             : p.rows * row_bytes;
+        const int64_t rows_bytes = c->format == RowFormat::SPARSE
+                                       ? (int64_t) ((__int128) p.rows * (__int128) c->sp_entries * 8 / std::max<int64_t>(c->n, 1))
+                                       : p.rows * format_row_bytes(c->format, c->dim);
         plan.scan_bytes += rows_bytes + (g.bitmap ? (p.rows + 7) / 8 : 0) + (int64_t) p.q_count * in.k * 12 +
                            (plan.k2 ? p.rows * 4 : 0);     // K2 also reads |row|^2
     }
@@ -672,7 +676,7 @@ std::string vsr::scan_kernel_name(const Plan& plan, const vsr_corpus* c, int met
     else if (plan.k2w)
         snprintf(buf, sizeof buf, "vsr::mfma_wide_kernel<%s, NCH=%u, SAMPLE=false, HO=%s> (K2w, bf16 %s planes)", mname[metric],
                  c->pstride4 / 16, c->scr_has_mid ? "false" : "true", c->scr_has_mid ? "hi+mid" : "hi-only");
-    else if (plan.k2 && c->half) {
+    else if (plan.k2 && c->format == RowFormat::HALF) {
         const uint32_t hstage = (c->stride4 / 2 + 15) / 16;    // launch_mfmah_metric's choice
         const int ng = plan.qmax > 16 ? 2 : 1;
         snprintf(buf, sizeof buf, "vsr::mfmah_scan_kernel<%s, NSTR=%u, SAMPLE=false, NG=%d> (K2h, half rows)", mname[metric],
@@ -680,17 +684,22 @@ std::string vsr::scan_kernel_name(const Plan& plan, const vsr_corpus* c, int met
     } else if (plan.k2)
         snprintf(buf, sizeof buf, "vsr::mfma_scan_kernel<%s, NSTR=%d, SAMPLE=false, NG=%d> (K2)", mname[metric],
                  nstage > 4 ? 0 : 4, plan.qmax > 16 ? 2 : 1);
-    else if (c->sparse)
-        snprintf(buf, sizeof buf, "vsr::scans_kernel<%s, LPR=%d, QI=%d, TAB=%s> (K1s, sparse rows)", mname[metric], c->shape.lpr, plan.qi,
-                 plan.sparse_global ? "global" : "lds");
-    else if (c->bit)
-        snprintf(buf, sizeof buf, "vsr::scanb_kernel<%s, LPR=%d, C=%d, R=%d, QI=%d> (K1b, bit rows)", mname[metric], c->shape.lpr,
-                 c->shape.c, c->shape.r, plan.qi);
     else if (plan.mq)
         snprintf(buf, sizeof buf, "vsr::mq_scan_kernel<%s, SAMPLE=false> (K1m)", mname[metric]);
     else
-        snprintf(buf, sizeof buf, "vsr::scan_kernel<%s, LPR=%d, C=%d, R=%d, QI=%d%s", mname[metric], c->shape.lpr, c->shape.c,
-                 c->shape.r, plan.qi, c->half ? ", HALF=true> (K1h, half rows)" : "> (K1)");
+        switch (c->format) {
+        case RowFormat::SPARSE:
+            snprintf(buf, sizeof buf, "vsr::scans_kernel<%s, LPR=%d, QI=%d, TAB=%s> (K1s, sparse rows)", mname[metric], c->shape.lpr, plan.qi,
+                     plan.sparse_global ? "global" : "lds");
+            break;
+        case RowFormat::BIT:
+            snprintf(buf, sizeof buf, "vsr::scanb_kernel<%s, LPR=%d, C=%d, R=%d, QI=%d> (K1b, bit rows)", mname[metric], c->shape.lpr,
+                     c->shape.c, c->shape.r, plan.qi);
+            break;
+        default:
+            snprintf(buf, sizeof buf, "vsr::scan_kernel<%s, LPR=%d, C=%d, R=%d, QI=%d%s", mname[metric], c->shape.lpr, c->shape.c,
+                     c->shape.r, plan.qi, c->format == RowFormat::HALF ? ", HALF=true> (K1h, half rows)" : "> (K1)");
+        }
     std::string name = buf;
     if (plan.class_view) name.insert(name.rfind(')'), ", class view");
     return name;

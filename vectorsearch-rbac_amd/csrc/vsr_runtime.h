@@ -240,15 +240,14 @@ struct vsr_corpus {
     int64_t     n = 0;
     int         dim = 0;
     uint32_t    stride4 = 0;             // float4 per padded row (halfvec corpus: per padded QUERY, dim rounded up to 8 floats)
-    bool        half = false;            // halfvec corpus (vsr_corpus_load_half): d_rows holds stride4 / 2 16-byte chunks of 8
-                                         // binary16 values per row, no fp32 image, no screening planes; exact kernels only (K1h)
-    bool        bit = false;             // bit corpus (vsr_corpus_load_bit, vsr_corpus_binary_quantize): dim counts BITS, d_rows holds stride4
-                                         // 16-byte chunks of packed bits per row (pad bits zero), d_norm2 the rows' popcounts; no norms-max, no
-                                         // planes, no class view; exact kernel only (K1b)
-    bool        sparse = false;          // sparse corpus (vsr_corpus_load_sparse): d_rows holds sp_entries interleaved (index, value) entries of 8
-                                         // bytes, d_sp_off the rows' first entries (n + 1 of them, all even), d_norm2 the rows' |row|^2;
-                                         // stride4 = 0, shape = {LPR by the mean entry count, 0, LPR, 64}; no planes, no class view; exact
-                                         // kernel only (K1s)
+    // What d_rows holds (RowFormat, vsr_device.h; format_row_chunks 16-byte chunks per row):
+    // HALF (vsr_corpus_load_half): chunks of 8 binary16 values, no fp32 image, no screening planes; K1h, or K2h on the rows themselves
+    // BIT (vsr_corpus_load_bit, vsr_corpus_binary_quantize): dim counts BITS, chunks of packed bits (pad bits zero), d_norm2 the
+    //   rows' popcounts; no norms-max, no planes, no class view; exact kernel only (K1b)
+    // SPARSE (vsr_corpus_load_sparse): sp_entries interleaved (index, value) entries of 8 bytes, d_sp_off the rows' first entries
+    //   (n + 1 of them, all even), d_norm2 the rows' |row|^2; stride4 = 0, shape = {LPR by the mean entry count, 0, LPR, 64}; no
+    //   planes, no class view; exact kernel only (K1s)
+    RowFormat   format = RowFormat::F32;
     uint64_t*   d_sp_off = nullptr;
     uint64_t    sp_entries = 0;          // stored entries, pad entries included
     int64_t     row_offset = 0;
@@ -416,15 +415,17 @@ void   purge_hnsw_caches(vsr_corpus* c, const vsr_filter* f);
 // vsr_hnsw_rt.hip: host queries bound for halfvec rows: a finite element that rounds to +-Inf in binary16 is refused (`$1::halfvec`)
 int    half_query_range(const void* queries, int nq, int dim);
 // vsr_search.hip
-// bit_entry: the caller is a vsr_search_bit* entry point (bit corpus, metrics 4 / 5); every other caller is refused a bit corpus
-// sparse_entry: ... a vsr_search_sparse* entry point (sparse corpus, metrics 0 .. 3); every other caller is refused a sparse corpus
+// entry: the queries the calling entry point takes -- F32 (fp32 vectors: a vector or a halfvec corpus, metrics 0 .. 3), BIT (a
+// vsr_search_bit* / vsr_hnsw_search_bit* entry point: bit corpus, metrics 4 / 5) or SPARSE (vsr_search_sparse*: sparse corpus,
+// metrics 0 .. 3).  A bit or a sparse corpus is refused to every other entry point
 int    check_search_args(const vsr_corpus* c, const void* queries, int nq, int dim, int k, int metric,
-                         const vsr_filter* const* filters, const char* who, bool bit_entry = false, bool sparse_entry = false);
+                         const vsr_filter* const* filters, const char* who, RowFormat entry = RowFormat::F32);
 // vsr_runtime.hip: n sparsevec values as CSR, checked as sparsevec_recv checks one (sparsevec.c:53-133, 493-539); max_nnz (may be
 // nullptr) receives the longest row's entry count
 int    check_sparse_rows(const char* who, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n, int dim,
                          uint32_t* max_nnz);
-int    host_search(vsr_corpus* c, const float* queries, int nq, int dim, int k, int metric, const vsr_filter* const* filters,
+// queries: format_query_bytes(c->format, dim) bytes each
+int    host_search(vsr_corpus* c, const void* queries, int nq, int dim, int k, int metric, const vsr_filter* const* filters,
                    const Outputs& out);
 // the two-stage searches (vsr_search_quantized*, and vsr_hnsw_search_quantized* in vsr_hnsw_rt.hip): the argument checks they share
 // (session may be nullptr) and stage 2, the exact re-rank of stage-1 keys on the source rows

@@ -262,13 +262,12 @@ static int corpus_load(vsr_ctx* ctx, const ELEM* rows, int64_t n, int dim, const
     c->ctx = ctx;
     c->n = n;
     c->dim = dim;
-    c->half = HALF;
-    c->bit = BIT;
+    c->format = BIT ? RowFormat::BIT : HALF ? RowFormat::HALF : RowFormat::F32;
     const int in_elems = BIT ? (dim + 7) / 8 : dim;         // elements per row as the caller holds them
-    const uint32_t row_chunks = (uint32_t) ((in_elems + PER16 - 1) / PER16);   // 16-byte chunks per row
+    const uint32_t row_chunks = format_row_chunks(c->format, dim);
     c->stride4 = HALF ? 2 * row_chunks : row_chunks;
     c->row_offset = row_offset;
-    c->shape = BIT ? scan_shape_for_dim_bit(dim) : HALF ? scan_shape_for_dim_half(dim) : scan_shape_for_dim(dim);
+    c->shape = scan_shape(c->format, dim);
 
     // internal order: (document_id, block_id); identity when the input is already sorted that way
     std::vector<int64_t> perm((size_t) n);
@@ -425,7 +424,7 @@ extern "C" int vsr_corpus_load_half(vsr_ctx* ctx, const uint16_t* rows, int64_t 
     return corpus_load(ctx, rows, n, dim, block_ids, doc_ids, row_offset, out, "vsr_corpus_load_half");
 }
 
-extern "C" int vsr_corpus_is_half(const vsr_corpus* c) { return c && c->half ? 1 : 0; }
+extern "C" int vsr_corpus_is_half(const vsr_corpus* c) { return c && c->format == RowFormat::HALF ? 1 : 0; }
 
 extern "C" int vsr_corpus_load_bit(vsr_ctx* ctx, const uint8_t* rows, int64_t n, int dim, const int64_t* block_ids,
                                    const int32_t* doc_ids, int64_t row_offset, vsr_corpus** out)
@@ -433,7 +432,7 @@ extern "C" int vsr_corpus_load_bit(vsr_ctx* ctx, const uint8_t* rows, int64_t n,
     return corpus_load(ctx, rows, n, dim, block_ids, doc_ids, row_offset, out, "vsr_corpus_load_bit");
 }
 
-extern "C" int vsr_corpus_is_bit(const vsr_corpus* c) { return c && c->bit ? 1 : 0; }
+extern "C" int vsr_corpus_is_bit(const vsr_corpus* c) { return c && c->format == RowFormat::BIT ? 1 : 0; }
 
 // ---- sparse corpora (pgvector's sparsevec) ----
 int vsr::check_sparse_rows(const char* who, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n, int dim,
@@ -483,7 +482,7 @@ extern "C" int vsr_corpus_load_sparse(vsr_ctx* ctx, const int64_t* indptr, const
     c->ctx = ctx;
     c->n = n;
     c->dim = dim;
-    c->sparse = true;
+    c->format = RowFormat::SPARSE;
     c->stride4 = 0;
     c->row_offset = row_offset;
 
@@ -579,7 +578,7 @@ extern "C" int vsr_corpus_load_sparse(vsr_ctx* ctx, const int64_t* indptr, const
     return VSR_OK;
 }
 
-extern "C" int vsr_corpus_is_sparse(const vsr_corpus* c) { return c && c->sparse ? 1 : 0; }
+extern "C" int vsr_corpus_is_sparse(const vsr_corpus* c) { return c && c->format == RowFormat::SPARSE ? 1 : 0; }
 
 // sparsevec.c:803-1037 for n explicit pairs (host CSR triples)
 extern "C" int vsr_sparse_pair_distances(vsr_ctx* ctx, int metric, const int64_t* a_indptr, const int32_t* a_indices,
@@ -634,8 +633,8 @@ extern "C" int vsr_corpus_binary_quantize(vsr_corpus* src, vsr_corpus** out)
 {
     if (!src || !out) return fail(VSR_ERR_INVALID, "vsr_corpus_binary_quantize: NULL argument");
     *out = nullptr;
-    if (src->bit) return fail(VSR_ERR_INVALID, "vsr_corpus_binary_quantize: the corpus is a bit corpus already");
-    if (src->sparse) return fail(VSR_ERR_UNSUPPORTED, "vsr_corpus_binary_quantize: a sparsevec corpus has no binary_quantize (pgvector defines none)");
+    if (src->format == RowFormat::BIT) return fail(VSR_ERR_INVALID, "vsr_corpus_binary_quantize: the corpus is a bit corpus already");
+    if (src->format == RowFormat::SPARSE) return fail(VSR_ERR_UNSUPPORTED, "vsr_corpus_binary_quantize: a sparsevec corpus has no binary_quantize (pgvector defines none)");
     if (src->base) return fail(VSR_ERR_INVALID, "vsr_corpus_binary_quantize: this corpus is an index view");
     vsr_ctx* ctx = src->ctx;
     HIPCHK(hipSetDevice(ctx->device));
@@ -643,12 +642,12 @@ extern "C" int vsr_corpus_binary_quantize(vsr_corpus* src, vsr_corpus** out)
     c->ctx = ctx;
     c->n = src->n;
     c->dim = src->dim;
-    c->bit = true;
+    c->format = RowFormat::BIT;
     c->quantized_from = src->serial;
-    const uint32_t row_chunks = (uint32_t) ((src->dim + 127) / 128);
+    const uint32_t row_chunks = format_row_chunks(RowFormat::BIT, src->dim);
     c->stride4 = row_chunks;
     c->row_offset = src->row_offset;
-    c->shape = scan_shape_for_dim_bit(src->dim);
+    c->shape = scan_shape(RowFormat::BIT, src->dim);
     c->h_orig = src->h_orig;
     c->docs = src->docs;
     c->doc_row_start = src->doc_row_start;
@@ -665,7 +664,7 @@ extern "C" int vsr_corpus_binary_quantize(vsr_corpus* src, vsr_corpus** out)
         HIPCHK(hipMemcpyAsync(c->d_orig, src->d_orig, n * sizeof(int64_t), hipMemcpyDeviceToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(c->d_row_docidx, src->d_row_docidx, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
         // (both kinds of source row hold stride4 * 4 elements: fp32 rows stride4 float4, half rows stride4 / 2 chunks of 8)
-        HIPCHK(launch_binary_quantize(src->d_rows, src->half ? 1 : 0, (uint64_t) n, (uint32_t) src->dim, src->stride4 * 4u,
+        HIPCHK(launch_binary_quantize(src->d_rows, src->format == RowFormat::HALF ? 1 : 0, (uint64_t) n, (uint32_t) src->dim, src->stride4 * 4u,
                                       reinterpret_cast<uint8_t*>(c->d_rows), row_chunks * 16u, ctx->stream));
         HIPCHK(launch_row_popcounts(reinterpret_cast<const uint4*>(c->d_rows), (uint32_t) n, row_chunks, c->d_norm2, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -725,9 +724,9 @@ extern "C" int64_t vsr_corpus_device_bytes(const vsr_corpus* c)
 {
     if (!c) return 0;
     const size_t rows = (size_t) std::max<int64_t>(c->n, 1);
-    if (c->sparse)                                           // entries, row offsets, |row|^2
+    if (c->format == RowFormat::SPARSE)                      // entries, row offsets, |row|^2
         return (int64_t) ((size_t) c->sp_entries * 8 + 1024 + (rows + 1) * sizeof(uint64_t) + rows * sizeof(float));
-    size_t b = rows * (c->half ? c->stride4 / 2 : c->stride4) * 16 + 1024 + rows * sizeof(float);   // d_rows, d_norm2
+    size_t b = rows * format_row_chunks(c->format, c->dim) * 16 + 1024 + rows * sizeof(float);   // d_rows, d_norm2
     if (c->d_norm2_max) b += 64;
     if (c->d_scr) b += rows * (size_t) c->pstride4 * 16 + 1024;
     if (c->d_scr_c) b += coarse_plane_u4((uint64_t) rows, c->cstride4) * 16 + 1024;

@@ -18,7 +18,7 @@
 // HBM-bound: 3 flop per 4 bytes per query; no MFMA on purpose.
 //
 // K1h (HALF = true) is the same kernel over a halfvec corpus (pgvector/src/halfvec.c): a row is ceil(dim / 8) 16-byte
-// chunks of 8 IEEE binary16 values, so LPR, C and R count those chunks (scan_shape_for_dim_half) and a lane's load holds 8
+// chunks of 8 IEEE binary16 values, so LPR, C and R count those chunks (scan_shape, HALF) and a lane's load holds 8
 // elements.  Every chunk is widened to two float4 and goes through the same accum4 / rank_value against the fp32 query in
 // LDS -- pgvector computes every halfvec distance on the widened operands (halfutils.c) -- and the query is rounded to
 // binary16 and widened as it enters LDS, which is what `$1::halfvec` holds.  No fp16 arithmetic: x - q of two halves is
@@ -643,7 +643,7 @@ hipError_t launch_scan_inst(const ScanParams& p, uint32_t n_blocks, hipStream_t 
 template <int METRIC, bool HALF = false>
 hipError_t launch_scan_metric(const ScanParams& p, int dim, int qi, uint32_t n_blocks, hipStream_t s)
 {
-    const KernelShape sh = HALF ? scan_shape_for_dim_half(dim) : scan_shape_for_dim(dim);
+    const KernelShape sh = scan_shape(HALF ? RowFormat::HALF : RowFormat::F32, dim);
 #define VSR_CASE(LPR_, C_, R_)                                                             \
     if (sh.lpr == LPR_ && sh.c == C_) {                                                    \
         if (qi == 1) return launch_scan_inst<METRIC, LPR_, C_, R_, 1, HALF>(p, n_blocks, s);     \
@@ -656,7 +656,7 @@ hipError_t launch_scan_metric(const ScanParams& p, int dim, int qi, uint32_t n_b
     VSR_CASE(32, 1, 8)
     VSR_CASE(64, 1, 8)
     VSR_CASE(64, 2, 4)
-    if constexpr (!HALF) {                                  // (scan_shape_for_dim_half: rows past 128 chunks stream, C = 0)
+    if constexpr (!HALF) {                                  // (scan_shape, HALF: rows past 128 chunks stream, C = 0)
         VSR_CASE(64, 3, 4)
         VSR_CASE(64, 4, 2)
     }

@@ -8,7 +8,7 @@
 // up to qmax queries of a pass in LDS applied in sub-batches of QI to the register-resident tile, the LDS candidate list with a
 // running threshold (vsr_topk.h) and partial lists of kp keys for K5.  A row is ceil(dim / 128) 16-byte chunks of packed
 // bits, zero padded (bits past dim are cleared at load and at query staging), so the shape classes count those chunks
-// (scan_shape_for_dim_bit): at dim <= 128 LPR = 1 and one load instruction reads 64 rows as 1 KiB.  p.stride4 is the chunks
+// (scan_shape, BIT): at dim <= 128 LPR = 1 and one load instruction reads 64 rows as 1 KiB.  p.stride4 is the chunks
 // per row AND per query slot.
 // The arithmetic is integer: per (row chunk, query) four xor (Hamming) or and (Jaccard) and four popcount-accumulates into a
 // uint32 partial; the butterfly over the LPR lanes is reduce_slots in uint32.  Jaccard takes |row| from p.norm2 (the popcounts
@@ -262,7 +262,7 @@ hipError_t launch_scanb_inst(const ScanParams& p, uint32_t n_blocks, hipStream_t
 template <bool JACCARD>
 hipError_t launch_scanb_metric(const ScanParams& p, int dim, int qi, uint32_t n_blocks, hipStream_t s)
 {
-    const KernelShape sh = scan_shape_for_dim_bit(dim);
+    const KernelShape sh = scan_shape(RowFormat::BIT, dim);
 #define VSR_CASE(LPR_, C_, R_)                                                             \
     if (sh.lpr == LPR_ && sh.c == C_) {                                                    \
         if (qi == 1) return launch_scanb_inst<JACCARD, LPR_, C_, R_, 1>(p, n_blocks, s);   \

@@ -98,12 +98,12 @@ int wait_for_staging_block(vsr_ctx* ctx)
 // copy + gather + norm + two fills: it pulls the descriptor block out of the pinned host buffer, pads the queries to the row
 // stride (from the caller's device buffer, or from the staged host copy), computes |q|^2 with the arithmetic of the row
 // norms, clears the per-query flags and seeds.  The queries' section is the block's first, |q|^2 lies at off_qn.
-// (bits: the queries are packed bit strings -- a bit corpus: `dim` bits = ceil(dim / 8) bytes per query, padded to qfloats * 4 bytes)
-int stage_host_part(vsr_ctx* ctx, const Staging& sb, size_t off_qn, size_t off_g, const float* h_queries, const float* d_queries,
-                    int nq, int dim, size_t qfloats, StageParams& st, bool bits = false)
+// (fmt, the corpus's: BIT queries are packed bit strings, `dim` bits = ceil(dim / 8) bytes per query, padded to qfloats * 4 bytes)
+int stage_host_part(vsr_ctx* ctx, const Staging& sb, size_t off_qn, size_t off_g, RowFormat fmt, const void* h_queries, const void* d_queries,
+                    int nq, int dim, size_t qfloats, StageParams& st)
 {
     const size_t h_q_bytes = h_queries ? align_up((size_t) nq * qfloats * sizeof(float), 256) : 0;
-    const size_t src_bytes = bits ? (size_t) (dim + 7) / 8 : (size_t) dim * sizeof(float);
+    const size_t src_bytes = format_query_bytes(fmt, dim);
     RCCHK(wait_for_staging_block(ctx));
     RCCHK(ctx->h_desc.reserve(h_q_bytes + (sb.total - off_g)));
     RCCHK(ctx->d_desc.reserve(sb.total));
@@ -115,7 +115,7 @@ int stage_host_part(vsr_ctx* ctx, const Staging& sb, size_t off_qn, size_t off_g
         const size_t slot_bytes = qfloats * sizeof(float);
         for (int s = 0; s < nq; ++s) {
             char* dst = hs + (size_t) s * slot_bytes;
-            memcpy(dst, reinterpret_cast<const char*>(h_queries) + (size_t) s * src_bytes, src_bytes);
+            memcpy(dst, static_cast<const char*>(h_queries) + (size_t) s * src_bytes, src_bytes);
             memset(dst + src_bytes, 0, slot_bytes - src_bytes);
         }
     }
@@ -124,9 +124,9 @@ int stage_host_part(vsr_ctx* ctx, const Staging& sb, size_t off_qn, size_t off_g
     st.src16 = reinterpret_cast<const uint4*>(hd + h_q_bytes);
     st.dst16 = reinterpret_cast<uint4*>(ds + off_g);
     st.n16 = (uint32_t) ((sb.total - off_g) / 16);
-    st.q_src = d_queries ? d_queries : reinterpret_cast<const float*>(hd);
+    st.q_src = d_queries ? static_cast<const float*>(d_queries) : reinterpret_cast<const float*>(hd);
     st.q_stride = d_queries ? (uint32_t) dim : (uint32_t) qfloats;
-    if (bits) {                                             // byte strides; stage_bit_kernel clears the pad bits and counts the ones
+    if (fmt == RowFormat::BIT) {                                           // byte strides; stage_bit_kernel clears the pad bits and counts the ones
         st.q_stride = d_queries ? (uint32_t) src_bytes : (uint32_t) (qfloats * sizeof(float));
         st.q_bits = 1u;
     }
@@ -237,7 +237,7 @@ RerankParams rerank_params(const vsr_ctx* ctx, const vsr_corpus* c, const char* 
     RerankParams rr{};
     rr.queries = reinterpret_cast<const SelectQuery*>(ds + off_sq);
     rr.rows = idc->d_rows;
-    rr.rows_half = c->half ? 1u : 0u;
+    rr.rows_half = c->format == RowFormat::HALF ? 1u : 0u;
     rr.stride4 = c->stride4;
     rr.queries_f = reinterpret_cast<const float*>(ds);
     rr.kp = kp;
@@ -259,10 +259,10 @@ void count_scan(vsr_ctx* ctx, const Plan& plan, int cls)    // cls: 0 = one quer
     ctx->stats.unique_rows[cls] += plan.unique_rows;
 }
 
-// one search call as the launch sequences see it.  d_queries == nullptr: queries come from `h_queries`.
-// (bit corpus: the query pointers address packed bit strings, ceil(dim / 8) bytes each)
-// (sparse corpus: `sparse` is set and the query pointers are not used)
-struct Call { const float *h_queries, *d_queries; int nq, dim, k, metric; Outputs out; const SparseQueries* sparse = nullptr; };
+// one search call as the launch sequences see it.  d_queries == nullptr: queries come from `h_queries`.  The corpus's format says
+// what the query pointers address: fp32 vectors, or (BIT) packed bit strings, format_query_bytes each; SPARSE: `sparse` is set
+// and the query pointers are not used
+struct Call { const void *h_queries, *d_queries; int nq, dim, k, metric; Outputs out; const SparseQueries* sparse = nullptr; };
 
 // ---- K2w / K2g ---------------------------------------------------------------------------------------------------
 // K2w launch sequence (plan.k2w): staging -> sample pass -> threshold seeds -> main pass -> select + exact re-rank.
@@ -288,7 +288,7 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
     const size_t off_bm = sb.add(plan.block_map);
 
     StageParams st{};
-    RCCHK(stage_host_part(ctx, sb, off_qn, off_g, q.h_queries, q.d_queries, nq, q.dim, qfloats, st));
+    RCCHK(stage_host_part(ctx, sb, off_qn, off_g, c->format, q.h_queries, q.d_queries, nq, q.dim, qfloats, st));
     RCCHK(ctx->d_cand.reserve((size_t) nq * GQ_CAP * sizeof(uint64_t)));
     RCCHK(ctx->d_samp.reserve((size_t) nq * GQ_SAMPLE_CAP * sizeof(uint64_t)));
     RCCHK(ctx->d_qcnt.reserve((size_t) 2 * nq * sizeof(uint32_t)));
@@ -436,8 +436,8 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
 uint32_t fused_fan(const vsr_ctx* ctx, const vsr_corpus* c, const Plan& plan, const Call& q)
 {
     // (K1h rounds the query to binary16 itself as it enters LDS: no staging kernel needed for that either)
-    if (c->bit || c->sparse) return 0;                      // K1b / K1s do not instantiate the in-kernel merge: staging + scan + K5
-    if (!(q.nq == 1 && !ctx->no_fused && plan.groups.size() == 1 && plan.qi == 1 && !plan.k2 && !plan.mq && q.dim % (c->half ? 8 : 4) == 0 &&
+    if (c->format == RowFormat::BIT || c->format == RowFormat::SPARSE) return 0;   // K1b / K1s do not instantiate the in-kernel merge: staging + scan + K5
+    if (!(q.nq == 1 && !ctx->no_fused && plan.groups.size() == 1 && plan.qi == 1 && !plan.k2 && !plan.mq && q.dim % (c->format == RowFormat::HALF ? 8 : 4) == 0 &&
           q.metric != VSR_METRIC_COSINE && plan.groups[0].n_blocks <= 64u * 64u && ctx->profiling != 1))
         return 0;
     const uint32_t kp = plan.keep;
@@ -460,7 +460,7 @@ int search_fused(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q, u
         RCCHK(ctx->d_done.reserve((size_t) (1 + 4096 / 16 + 64) * sizeof(uint32_t)));
         HIPCHK(hipMemsetAsync(ctx->d_done.p, 0, ctx->d_done.cap, ctx->stream));
     }
-    const float* q_dev = q.d_queries;
+    const float* q_dev = static_cast<const float*>(q.d_queries);   // (F32 or HALF corpus: fused_fan)
     if (!q_dev) {
         // host query: the kernel reads it straight out of the pinned staging block (512 bytes, cached after the
         // first workgroup), which the previous call's kernel must have left
@@ -510,10 +510,8 @@ int search_fused(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q, u
         sp.plane_ho = 2u;
         sp.fused.flag_total = ctx->d_flag_total;
         HIPCHK(launch_scan8_fused(sp, (uint32_t) dim, reinterpret_cast<uint32_t*>(ctx->h_q8.dp), g.n_blocks, ctx->stream));
-    } else if (c->half)
-        HIPCHK(launch_scan_half(sp, metric, c->dim, 1, g.n_blocks, ctx->stream));
-    else
-        HIPCHK(launch_scan(sp, metric, c->dim, 1, g.n_blocks, ctx->stream));
+    } else
+        HIPCHK(launch_scan(c->format, sp, metric, c->dim, 1, g.n_blocks, ctx->stream));
     if (!q.d_queries) {
         HIPCHK(hipEventRecord(ctx->desc_done, ctx->stream));
         ctx->desc_pending = true;
@@ -553,11 +551,12 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
     const vsr_corpus* idc = c->base ? c->base : c;          // identity arrays and re-rank rows (c may be a list-ordered view)
     const size_t qfloats = (size_t) c->stride4 * 4;
     Staging sb;
-    const uint32_t sp_slots = c->sparse ? ctx->sparse_slots : 0u;
-    sb.add(c->sparse ? (size_t) nq * sp_slots * sizeof(uint2) : (size_t) nq * qfloats * sizeof(float));   // queries (sparse: their tables)
+    const bool sparse = c->format == RowFormat::SPARSE, half = c->format == RowFormat::HALF;
+    const uint32_t sp_slots = sparse ? ctx->sparse_slots : 0u;
+    sb.add(sparse ? (size_t) nq * sp_slots * sizeof(uint2) : (size_t) nq * qfloats * sizeof(float));   // queries (sparse: their tables)
     const size_t off_qn = sb.add((size_t) nq * sizeof(float));
-    const size_t off_qt = sb.add(c->sparse ? (size_t) nq * 2 * sizeof(double) : 0);   // K1s: sum q^2, sum |q| in double
-    const bool k2h = plan.k2 && c->half;                    // K2h: the queries also as binary16, its B fragments
+    const size_t off_qt = sb.add(sparse ? (size_t) nq * 2 * sizeof(double) : 0);   // K1s: sum q^2, sum |q| in double
+    const bool k2h = plan.k2 && half;                       // K2h: the queries also as binary16, its B fragments
     const size_t off_qh = sb.add(k2h ? (size_t) nq * qfloats * sizeof(uint16_t) : 0);
     const size_t off_g = sb.add(plan.groups);               // copied from here on
     const size_t off_gs = sb.add(plan.groups_s);
@@ -569,14 +568,14 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
     const size_t off_bm = sb.add(plan.block_map);
 
     StageParams st{};                                       // (no query planes, no K2w counters on this path)
-    if (!c->sparse) {
-        RCCHK(stage_host_part(ctx, sb, off_qn, off_g, q.h_queries, q.d_queries, nq, q.dim, qfloats, st, c->bit));
-        st.q_half = c->half ? 1u : 0u;
+    if (!sparse) {
+        RCCHK(stage_host_part(ctx, sb, off_qn, off_g, c->format, q.h_queries, q.d_queries, nq, q.dim, qfloats, st));
+        st.q_half = half ? 1u : 0u;
         if (k2h) st.q_h16 = reinterpret_cast<_Float16*>(ctx->d_desc.as<char>() + off_qh);
     }
     RCCHK(ctx->d_partial.reserve(std::max<size_t>(8, (size_t) plan.n_partial * kp * sizeof(uint64_t))));
     Timed whole(ctx, 5, ctx->stream);                       // the whole search on the device
-    if (c->sparse) RCCHK(stage_sparse(ctx, sb, off_qt, off_qn, off_g, *q.sparse, nq, q.dim, sp_slots));
+    if (sparse) RCCHK(stage_sparse(ctx, sb, off_qt, off_qn, off_g, *q.sparse, nq, q.dim, sp_slots));
     else RCCHK(launch_staging(ctx, st));
     char* ds = ctx->d_desc.as<char>();
 
@@ -584,7 +583,7 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
     sp.queries = reinterpret_cast<const float*>(ds);
     sp.q_norm2 = reinterpret_cast<const float*>(ds + off_qn);
     if (k2h) sp.q_scr = reinterpret_cast<const uint4*>(ds + off_qh);
-    if (c->sparse) {
+    if (sparse) {
         sp.sp_off = c->d_sp_off;
         sp.sp_tab = reinterpret_cast<const uint2*>(ds);
         sp.sp_slots = sp_slots;
@@ -658,10 +657,7 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
         if (k2h) HIPCHK(launch_mfmah(sp, metric, launch_blocks, ctx->stream));
         else if (plan.k2) HIPCHK(launch_mfma(sp, metric, launch_blocks, ctx->stream));
         else if (plan.mq) HIPCHK(launch_mq(sp, metric, launch_blocks, ctx->stream));
-        else if (c->half) HIPCHK(launch_scan_half(sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream));
-        else if (c->bit) HIPCHK(launch_scan_bit(sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream));
-        else if (c->sparse) HIPCHK(launch_scan_sparse(sp, metric, c->shape.lpr, plan.qi, plan.sparse_global, plan.n_blocks, ctx->stream));
-        else HIPCHK(launch_scan(sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream));
+        else HIPCHK(launch_scan(c->format, sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream, c->shape.lpr, plan.sparse_global));
         HIPCHK(main.stop());
         ctx->last_kernel = scan_kernel_name(plan, c, metric);
         count_scan(ctx, plan, cls);
@@ -678,7 +674,7 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
     if (plan.k2) {
         RerankParams rr = rerank_params(ctx, c, ds, off_sq, kp, q.k, metric, q.out);
         rr.lists = ctx->d_partial.as<uint64_t>() + (size_t) plan.rerank_base * kp;
-        rr.err_g = c->half ? half_err_g(c->dim) : k2_err_g(c->dim);   // K2h's / K2's fp32 accumulation (vsr_bounds.h)
+        rr.err_g = half ? half_err_g(c->dim) : k2_err_g(c->dim);   // K2h's / K2's fp32 accumulation (vsr_bounds.h)
         rr.seeded = seed ? 1 : 0;
         rr.tau_init = seed ? ctx->d_tau.as<uint64_t>() : nullptr;
         HIPCHK(launch_rerank(rr, (uint32_t) nq, ctx->stream));
@@ -698,9 +694,10 @@ bool queries_are_u8(vsr_ctx* ctx, const vsr_corpus* c, const Call& q, bool allow
     if (!(c->d_scr8 && q.metric == VSR_METRIC_L2 && allow_screening)) return false;
     if (!q.h_queries) return ctx->hint_u8 && ctx->q8_ok;
     bool ok = true;
+    const float* hq = static_cast<const float*>(q.h_queries);   // (int8 planes: an F32 corpus)
     const size_t total = (size_t) q.nq * q.dim;
     for (size_t i = 0; i < total && ok; ++i) {
-        const float v = q.h_queries[i];
+        const float v = hq[i];
         ok = v >= 0.0f && v <= 255.0f && v == floorf(v);
     }
     return ok;
@@ -739,25 +736,26 @@ int search_impl(vsr_ctx* ctx, vsr_corpus* c, const Call& q, const vsr_filter* co
 }  // namespace
 
 int vsr::check_search_args(const vsr_corpus* c, const void* queries, int nq, int dim, int k, int metric,
-                           const vsr_filter* const* filters, const char* who, bool bit_entry, bool sparse_entry)
+                           const vsr_filter* const* filters, const char* who, RowFormat entry)
 {
     if (!c) return fail(VSR_ERR_INVALID, "%s: corpus is NULL", who);
-    if (sparse_entry && !c->sparse) return fail(VSR_ERR_INVALID, "%s: the corpus is not a sparse corpus", who);
-    if (c->sparse && !sparse_entry)
+    const bool bit = c->format == RowFormat::BIT, sparse = c->format == RowFormat::SPARSE;
+    if (entry == RowFormat::SPARSE && !sparse) return fail(VSR_ERR_INVALID, "%s: the corpus is not a sparse corpus", who);
+    if (sparse && entry != RowFormat::SPARSE)
         return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus is searched with vsr_search_sparse* (<->, <#>, <=>, <+>) and has no index path yet", who);
-    if (bit_entry && !c->bit) return fail(VSR_ERR_INVALID, "%s: the corpus is not a bit corpus", who);
-    if (c->bit && !bit_entry)
+    if (entry == RowFormat::BIT && !bit) return fail(VSR_ERR_INVALID, "%s: the corpus is not a bit corpus", who);
+    if (bit && entry != RowFormat::BIT)
         return fail(VSR_ERR_UNSUPPORTED, "%s: a bit corpus is searched with vsr_search_bit* (<~> / <%%>), its graphs with vsr_hnsw_search_bit*", who);
     if (nq < 0 || (nq > 0 && !queries)) return fail(VSR_ERR_INVALID, "%s: queries is NULL", who);
-    if (dim != c->dim && c->sparse)                         // CheckDims, sparsevec.c
+    if (dim != c->dim && sparse)                            // CheckDims, sparsevec.c
         return fail(VSR_ERR_DIM_MISMATCH, "different sparsevec dimensions %d and %d", c->dim, dim);
-    if (dim != c->dim && c->bit)                            // CheckDims, bitvec.c:32-39: the column's length first
+    if (dim != c->dim && bit)                               // CheckDims, bitvec.c:32-39: the column's length first
         return fail(VSR_ERR_DIM_MISMATCH, "different bit lengths %u and %u", (unsigned) c->dim, (unsigned) dim);
     if (dim != c->dim)                                      // CheckDims: vector.c:60-67, halfvec.c:60-67
-        return fail(VSR_ERR_DIM_MISMATCH, "different %s dimensions %d and %d", c->half ? "halfvec" : "vector", c->dim, dim);
+        return fail(VSR_ERR_DIM_MISMATCH, "different %s dimensions %d and %d", format_name(c->format), c->dim, dim);
     if (k < 1) return fail(VSR_ERR_INVALID, "%s: k must be >= 1 (got %d)", who, k);
     if (k > VSR_MAX_K) return fail(VSR_ERR_UNSUPPORTED, "%s: k = %d exceeds VSR_MAX_K = %d", who, k, VSR_MAX_K);
-    if (bit_entry ? metric != VSR_METRIC_HAMMING && metric != VSR_METRIC_JACCARD : metric < VSR_METRIC_L2 || metric > VSR_METRIC_L1)
+    if (entry == RowFormat::BIT ? metric != VSR_METRIC_HAMMING && metric != VSR_METRIC_JACCARD : metric < VSR_METRIC_L2 || metric > VSR_METRIC_L1)
         return fail(VSR_ERR_INVALID, "%s: metric %d", who, metric);
     if (filters)
         for (int i = 0; i < nq; ++i)
@@ -765,12 +763,12 @@ int vsr::check_search_args(const vsr_corpus* c, const void* queries, int nq, int
     return VSR_OK;
 }
 
-// vsr_search_device_on and vsr_search_bit_device_on (bit_entry: d_queries addresses packed bit strings)
-static int search_device_on(vsr_ctx* session, vsr_corpus* c, const float* d_queries, int nq, int dim, int k, int metric,
+// vsr_search_device_on (entry = F32) and vsr_search_bit_device_on (BIT: d_queries addresses packed bit strings)
+static int search_device_on(vsr_ctx* session, vsr_corpus* c, RowFormat entry, const void* d_queries, int nq, int dim, int k, int metric,
                             const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc, int64_t* d_row, float* d_dist,
-                            int32_t* d_cnt, uint64_t* d_keys, bool bit_entry)
+                            int32_t* d_cnt, uint64_t* d_keys)
 {
-    int rc = check_search_args(c, d_queries, nq, dim, k, metric, filters, bit_entry ? "vsr_search_bit_device" : "vsr_search_device", bit_entry);
+    int rc = check_search_args(c, d_queries, nq, dim, k, metric, filters, entry == RowFormat::BIT ? "vsr_search_bit_device" : "vsr_search_device", entry);
     if (rc) return rc;
     vsr_ctx* ctx = session ? session : c->ctx;
     if (ctx->device != c->ctx->device) return fail(VSR_ERR_INVALID, "vsr_search_device_on: session and corpus are on different devices");
@@ -788,15 +786,14 @@ extern "C" int vsr_search_device_on(vsr_ctx* session, vsr_corpus* c, const float
                                     int metric, const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc,
                                     int64_t* d_row, float* d_dist, int32_t* d_cnt, uint64_t* d_keys)
 {
-    return search_device_on(session, c, d_queries, nq, dim, k, metric, filters, d_blk, d_doc, d_row, d_dist, d_cnt, d_keys, false);
+    return search_device_on(session, c, RowFormat::F32, d_queries, nq, dim, k, metric, filters, d_blk, d_doc, d_row, d_dist, d_cnt, d_keys);
 }
 
 extern "C" int vsr_search_bit_device_on(vsr_ctx* session, vsr_corpus* c, const uint8_t* d_queries, int nq, int dim, int k,
                                         int metric, const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc,
                                         int64_t* d_row, float* d_dist, int32_t* d_cnt, uint64_t* d_keys)
 {
-    return search_device_on(session, c, reinterpret_cast<const float*>(d_queries), nq, dim, k, metric, filters, d_blk, d_doc, d_row,
-                            d_dist, d_cnt, d_keys, true);
+    return search_device_on(session, c, RowFormat::BIT, d_queries, nq, dim, k, metric, filters, d_blk, d_doc, d_row, d_dist, d_cnt, d_keys);
 }
 
 extern "C" int vsr_search_bit_device(vsr_corpus* c, const uint8_t* d_queries, int nq, int dim, int k, int metric,
@@ -851,7 +848,7 @@ extern "C" int vsr_search_device_exact(vsr_ctx* session, vsr_corpus* c, const fl
                                   hipMemcpyDeviceToDevice, ctx->stream));
             if (filters) f2[j] = filters[redo[j]];
         }
-        rc = search_impl(ctx, c, {nullptr, reinterpret_cast<const float*>(w + o_q), (int) nr, dim, k, metric, redone}, f2.data(), level);
+        rc = search_impl(ctx, c, {nullptr, w + o_q, (int) nr, dim, k, metric, redone}, f2.data(), level);
         if (rc) return rc;
         const Outputs all{d_blk, d_doc, d_row, d_dist, d_cnt, d_keys};
         for (size_t j = 0; j < nr; ++j) {
@@ -881,7 +878,7 @@ extern "C" int vsr_search_device_exact(vsr_ctx* session, vsr_corpus* c, const fl
 
 // Host-buffer search on a corpus or on a list-ordered view of one: the search, then the re-run of the (rare) flagged
 // queries one tier down -- coarse planes -> fine planes -> exact kernels.
-int vsr::host_search(vsr_corpus* c, const float* queries, int nq, int dim, int k, int metric, const vsr_filter* const* filters,
+int vsr::host_search(vsr_corpus* c, const void* queries, int nq, int dim, int k, int metric, const vsr_filter* const* filters,
                      const Outputs& out)
 {
     int rc;
@@ -897,7 +894,7 @@ int vsr::host_search(vsr_corpus* c, const float* queries, int nq, int dim, int k
     if ((rc = ctx->h_out.reserve(rb.total))) return rc;
     char* d = direct ? static_cast<char*>(ctx->h_out.dp) : ctx->d_out.as<char>();
     char* h = ctx->h_out.as<char>();
-    auto run = [&](const float* qs, int n, const vsr_filter* const* fs, int level) -> int {
+    auto run = [&](const void* qs, int n, const vsr_filter* const* fs, int level) -> int {
         int r = search_impl(ctx, c, {qs, nullptr, n, dim, k, metric, rb.arrays(d)}, fs, level);
         if (r) return r;
         if (!direct) HIPCHK(hipMemcpyAsync(h, d, results, hipMemcpyDeviceToHost, ctx->stream));
@@ -912,7 +909,7 @@ int vsr::host_search(vsr_corpus* c, const float* queries, int nq, int dim, int k
     std::vector<float> q2;
     std::vector<const vsr_filter*> f2;
     for (int level = ctx->last_coarse ? 1 : 0; level >= 0 && !redo.empty(); --level) {
-        gather_subset(queries, dim, filters, redo, q2, f2);
+        gather_subset(static_cast<const float*>(queries), dim, filters, redo, q2, f2);   // (only screening flags: fp32 queries)
         if ((rc = run(q2.data(), (int) redo.size(), f2.data(), level))) return rc;
         std::vector<int> still;
         for (size_t j = 0; j < redo.size(); ++j) {
@@ -933,14 +930,9 @@ extern "C" int vsr_search(vsr_corpus* c, const float* queries, int nq, int dim, 
     if (c->base) return fail(VSR_ERR_INVALID, "vsr_search: this corpus is an index view; use the index's search function");
     if (nq == 0) return VSR_OK;
     if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "vsr_search: output is NULL");
-    if (c->half) {
-        // `$1::halfvec`: a finite element that rounds to +-Inf is an error (halfvec_in, halfvec.c:224-230); 65520 is
-        // the smallest magnitude that does.  (The device entry points do not look: the element becomes +-Inf.)
-        const size_t total = (size_t) nq * (size_t) dim;
-        for (size_t i = 0; i < total; ++i)
-            if (std::isfinite(queries[i]) && std::fabs(queries[i]) >= 65520.0f)
-                return fail(VSR_ERR_INVALID, "\"%.9g\" is out of range for type halfvec", (double) queries[i]);
-    }
+    // `$1::halfvec`: a finite element that rounds to +-Inf is an error (halfvec_in, halfvec.c:224-230); 65520 is the smallest
+    // magnitude that does.  (The device entry points do not look: the element becomes +-Inf.)
+    if (c->format == RowFormat::HALF && (rc = half_query_range(queries, nq, dim))) return rc;
     return host_search(c, queries, nq, dim, k, metric, filters, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr});
 }
 
@@ -949,12 +941,11 @@ extern "C" int vsr_search_bit(vsr_corpus* c, const uint8_t* queries, int nq, int
                               const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc, int64_t* out_row,
                               float* out_dist, int32_t* out_cnt)
 {
-    int rc = check_search_args(c, queries, nq, dim, k, metric, filters, "vsr_search_bit", true);
+    int rc = check_search_args(c, queries, nq, dim, k, metric, filters, "vsr_search_bit", RowFormat::BIT);
     if (rc) return rc;
     if (nq == 0) return VSR_OK;
     if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "vsr_search_bit: output is NULL");
-    return host_search(c, reinterpret_cast<const float*>(queries), nq, dim, k, metric, filters,
-                       {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr});
+    return host_search(c, queries, nq, dim, k, metric, filters, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr});
 }
 
 // ORDER BY col <op> $1 LIMIT k over a sparse corpus (sparsevec.c:803-1037).  Exact by construction: nothing flags.
@@ -963,7 +954,7 @@ static int search_sparse_device_on(vsr_ctx* session, vsr_corpus* c, const int64_
                                    int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt, uint64_t* d_keys)
 {
     const char* who = "vsr_search_sparse_device";
-    int rc = check_search_args(c, d_indptr, nq, dim, k, metric, filters, who, false, true);
+    int rc = check_search_args(c, d_indptr, nq, dim, k, metric, filters, who, RowFormat::SPARSE);
     if (rc) return rc;
     if (max_query_nnz < 0 || max_query_nnz > SPARSE_MAX_NNZ)
         return fail(VSR_ERR_INVALID, "%s: max_query_nnz must be between 0 and %d (got %d)", who, SPARSE_MAX_NNZ, max_query_nnz);
@@ -1003,7 +994,7 @@ extern "C" int vsr_search_sparse(vsr_corpus* c, const int64_t* q_indptr, const i
                                  int64_t* out_row, float* out_dist, int32_t* out_cnt)
 {
     const char* who = "vsr_search_sparse";
-    int rc = check_search_args(c, q_indptr, nq, dim, k, metric, filters, who, false, true);
+    int rc = check_search_args(c, q_indptr, nq, dim, k, metric, filters, who, RowFormat::SPARSE);
     if (rc) return rc;
     uint32_t max_nnz = 0;
     if ((rc = check_sparse_rows(who, q_indptr, q_indices, q_values, nq, dim, &max_nnz))) return rc;
@@ -1029,27 +1020,25 @@ extern "C" int vsr_search_sparse(vsr_corpus* c, const int64_t* q_indptr, const i
 // device memory either way (the host entry point hands in its result block).  Everything is enqueued on ctx->stream:
 //   binary_quantize of the queries -> stage 1 = the internal search over `bits` with k = shortlist, its keys into the
 //   session's scratch -> shortlist_rerank_kernel over the source rows -> shortlist_emit_kernel.
-static const char* corpus_kind(const vsr_corpus* c) { return c->sparse ? "sparsevec" : c->bit ? "bit" : c->half ? "halfvec" : "vector"; }
-
 int vsr::check_quantized_args(const vsr_ctx* session, const vsr_corpus* src, const vsr_corpus* bits, const void* queries, int nq,
                                 int dim, int k, int shortlist, int metric, const vsr_filter* const* filters, const char* who)
 {
     if (!src || !bits) return fail(VSR_ERR_INVALID, "%s: corpus is NULL", who);
-    if (src->sparse || bits->sparse)
+    if (src->format == RowFormat::SPARSE || bits->format == RowFormat::SPARSE)
         return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no two-stage search (pgvector defines no binary_quantize for sparsevec)", who);
-    if (src->bit) return fail(VSR_ERR_INVALID, "%s: the source corpus is a bit corpus (the re-rank needs the fp32 or halfvec rows)", who);
+    if (src->format == RowFormat::BIT) return fail(VSR_ERR_INVALID, "%s: the source corpus is a bit corpus (the re-rank needs the fp32 or halfvec rows)", who);
     if (src->base) return fail(VSR_ERR_INVALID, "%s: the source corpus is an index view", who);
-    if (!bits->bit) return fail(VSR_ERR_INVALID, "%s: the bits corpus is not a bit corpus", who);
+    if (bits->format != RowFormat::BIT) return fail(VSR_ERR_INVALID, "%s: the bits corpus is not a bit corpus", who);
     if (bits->quantized_from != src->serial) {
         char from[64] = "it was loaded with vsr_corpus_load_bit";
         if (bits->quantized_from) snprintf(from, sizeof from, "it was made from corpus #%llu", (unsigned long long) bits->quantized_from);
         return fail(VSR_ERR_INVALID, "%s: bits corpus #%llu (%lld rows of %d bits) was not made from source corpus #%llu (%s, %lld rows "
                     "of %d dimensions) by vsr_corpus_binary_quantize: %s", who, (unsigned long long) bits->serial, (long long) bits->n,
-                    bits->dim, (unsigned long long) src->serial, corpus_kind(src), (long long) src->n, src->dim, from);
+                    bits->dim, (unsigned long long) src->serial, format_name(src->format), (long long) src->n, src->dim, from);
     }
     if (nq < 0 || (nq > 0 && !queries)) return fail(VSR_ERR_INVALID, "%s: queries is NULL", who);
     if (dim != src->dim)                                    // CheckDims: vector.c:60-67, halfvec.c:60-67
-        return fail(VSR_ERR_DIM_MISMATCH, "different %s dimensions %d and %d", src->half ? "halfvec" : "vector", src->dim, dim);
+        return fail(VSR_ERR_DIM_MISMATCH, "different %s dimensions %d and %d", format_name(src->format), src->dim, dim);
     if (k < 1) return fail(VSR_ERR_INVALID, "%s: k must be >= 1 (got %d)", who, k);
     if (shortlist < k) return fail(VSR_ERR_INVALID, "%s: shortlist = %d is shorter than k = %d", who, shortlist, k);
     if (shortlist > VSR_MAX_K) return fail(VSR_ERR_INVALID, "%s: shortlist = %d exceeds VSR_MAX_K = %d", who, shortlist, VSR_MAX_K);
@@ -1085,7 +1074,7 @@ static int search_quantized_impl(vsr_ctx* ctx, vsr_corpus* src, vsr_corpus* bits
     HIPCHK(launch_binary_quantize(d_queries, 0, (uint64_t) nq, (uint32_t) dim, (uint32_t) dim, d_qb, (uint32_t) qbytes, ctx->stream));
     const Outputs s1{reinterpret_cast<int64_t*>(w + o_blk), reinterpret_cast<int32_t*>(w + o_doc), nullptr,
                      reinterpret_cast<float*>(w + o_dist), reinterpret_cast<int32_t*>(w + o_cnt), s1_keys};
-    RCCHK(search_impl(ctx, bits, {nullptr, reinterpret_cast<const float*>(d_qb), nq, dim, shortlist, VSR_METRIC_HAMMING, s1}, filters, 2));
+    RCCHK(search_impl(ctx, bits, {nullptr, d_qb, nq, dim, shortlist, VSR_METRIC_HAMMING, s1}, filters, 2));
     return quantized_rerank(ctx, src, s1_keys, (uint32_t) bits->row_offset, reinterpret_cast<uint64_t*>(w + o_blk), d_queries, nq, dim, k,
                             shortlist, metric, out);
 }
@@ -1120,7 +1109,7 @@ int vsr::quantized_rerank(vsr_ctx* ctx, vsr_corpus* src, const uint64_t* s1_keys
     sl.out_keys = out.keys;
     sl.out_count = out.cnt;
     Timed rerank(ctx, 2, ctx->stream);                      // counted with the selections
-    HIPCHK(launch_shortlist_rerank(sl, src->half, (uint32_t) nq, ctx->stream));
+    HIPCHK(launch_shortlist_rerank(sl, src->format, (uint32_t) nq, ctx->stream));
     HIPCHK(launch_shortlist_emit(sl, (uint32_t) nq, ctx->stream));
     HIPCHK(rerank.stop());
     ctx->last_kernel += " + shortlist re-rank";
@@ -1160,12 +1149,7 @@ extern "C" int vsr_search_quantized(vsr_corpus* src, vsr_corpus* bits, const flo
     if (rc) return rc;
     if (nq == 0) return VSR_OK;
     if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", who);
-    if (src->half) {                                        // `$1::halfvec`, as vsr_search refuses it
-        const size_t total = (size_t) nq * (size_t) dim;
-        for (size_t i = 0; i < total; ++i)
-            if (std::isfinite(queries[i]) && std::fabs(queries[i]) >= 65520.0f)
-                return fail(VSR_ERR_INVALID, "\"%.9g\" is out of range for type halfvec", (double) queries[i]);
-    }
+    if (src->format == RowFormat::HALF && (rc = half_query_range(queries, nq, dim))) return rc;   // `$1::halfvec`, as vsr_search refuses it
     vsr_ctx* ctx = bits->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     const ResultBlock rb(nq, k, false);                     // results in device memory, one packed copy back, one wait

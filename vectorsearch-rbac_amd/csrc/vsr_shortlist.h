@@ -37,7 +37,7 @@ struct ShortlistParams {
 };
 
 inline size_t shortlist_rerank_lds(uint32_t stride4) { return (size_t) stride4 * 16; }   // the padded query
-hipError_t launch_shortlist_rerank(const ShortlistParams& p, bool half, uint32_t nq, hipStream_t s);
+hipError_t launch_shortlist_rerank(const ShortlistParams& p, RowFormat src, uint32_t nq, hipStream_t s);   // src: the source rows, F32 or HALF
 hipError_t launch_shortlist_emit(const ShortlistParams& p, uint32_t nq, hipStream_t s);
 
 }  // namespace vsr

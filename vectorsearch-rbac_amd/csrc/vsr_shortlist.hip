@@ -112,13 +112,13 @@ __global__ __launch_bounds__(256) void shortlist_emit_kernel(const ShortlistPara
     if (tid == 0) p.out_count[qi] = (int32_t) m;
 }
 
-hipError_t launch_shortlist_rerank(const ShortlistParams& p, bool half, uint32_t nq, hipStream_t s)
+hipError_t launch_shortlist_rerank(const ShortlistParams& p, RowFormat src, uint32_t nq, hipStream_t s)
 {
     if (nq == 0) return hipSuccess;
     if (p.shortlist < 1 || p.shortlist > (uint32_t) MAX_K) return hipErrorInvalidValue;
     const dim3 grid(nq * ((p.shortlist + SL_CHUNK - 1) / SL_CHUNK));      // nq <= 2^31 / 8
     const size_t lds = shortlist_rerank_lds(p.stride4);                    // <= 64000 bytes (16000 dimensions)
-    if (half) hipLaunchKernelGGL(shortlist_rerank_kernel<true>, grid, dim3(256), lds, s, p);
+    if (src == RowFormat::HALF) hipLaunchKernelGGL(shortlist_rerank_kernel<true>, grid, dim3(256), lds, s, p);
     else hipLaunchKernelGGL(shortlist_rerank_kernel<false>, grid, dim3(256), lds, s, p);
     return hipGetLastError();
 }

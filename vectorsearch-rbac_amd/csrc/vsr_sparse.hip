@@ -164,20 +164,4 @@ int scan_qmax_sparse(uint32_t slots, int k)
     return (q < SCAN_QMAX ? q : SCAN_QMAX) / 4 * 4;
 }
 
-hipError_t launch_scans_l2(const ScanParams& p, int lpr, int qi, bool global_tab, uint32_t n_blocks, hipStream_t s);
-hipError_t launch_scans_ip(const ScanParams& p, int lpr, int qi, bool global_tab, uint32_t n_blocks, hipStream_t s);
-hipError_t launch_scans_cosine(const ScanParams& p, int lpr, int qi, bool global_tab, uint32_t n_blocks, hipStream_t s);
-hipError_t launch_scans_l1(const ScanParams& p, int lpr, int qi, bool global_tab, uint32_t n_blocks, hipStream_t s);
-
-hipError_t launch_scan_sparse(const ScanParams& p, int metric, int lpr, int qi, bool global_tab, uint32_t n_blocks, hipStream_t s)
-{
-    switch (metric) {
-    case M_L2:     return launch_scans_l2(p, lpr, qi, global_tab, n_blocks, s);
-    case M_IP:     return launch_scans_ip(p, lpr, qi, global_tab, n_blocks, s);
-    case M_COSINE: return launch_scans_cosine(p, lpr, qi, global_tab, n_blocks, s);
-    case M_L1:     return launch_scans_l1(p, lpr, qi, global_tab, n_blocks, s);
-    default:       return hipErrorInvalidValue;
-    }
-}
-
 }  // namespace vsr
