@@ -27,7 +27,7 @@ query from below m (no seed) past m to more than 1024 (two chunks of the seed's 
 import numpy as np
 import pytest
 
-from helpers import sift_like
+from edge_world import World
 
 pytestmark = pytest.mark.gpu
 
@@ -52,71 +52,9 @@ def _ctx(monkeypatch, **env):
     return c
 
 
-class World:
-    """classes: (allowed rows, queries) per child role, the root last; role 1 = the root, role 2 + c = child c, user u holds
-    role u."""
-
-    def __init__(self, classes, d=128, seed=20261019):
-        rng = np.random.default_rng(seed)
-        self.classes = classes
-        root = len(classes) - 1
-        assert classes[root][0] == 1
-        sizes = [a - 1 for a, _ in classes[:root]] + [1]
-        doc_rows, doc_class = [], []
-        for cls, size in enumerate(sizes):
-            parts = [100] * (size // 100) + ([size % 100] if size % 100 else [])
-            doc_rows += parts
-            doc_class += [cls] * len(parts)
-        order = rng.permutation(len(doc_rows))                         # every class scattered over the whole corpus
-        self.doc_rows = np.asarray(doc_rows)[order]
-        self.doc_class = np.asarray(doc_class)[order]
-        self.doc = np.repeat(np.arange(1, len(order) + 1), self.doc_rows).astype(np.int32)
-        self.n = int(self.doc.size)
-        assert self.n == sum(sizes)
-        self.blk = (np.arange(self.n) + 1).astype(np.int64)
-        row_class = np.repeat(self.doc_class, self.doc_rows)
-        self.x = np.empty((self.n, d), dtype=np.float32)
-        for cls, size in enumerate(sizes):                             # every vector one to three times, at scattered rows
-            base = sift_like(rng, size, d)
-            copies = np.repeat(np.arange(size), rng.integers(1, 4, size))[:size]
-            self.x[row_class == cls] = base[rng.permutation(copies)]
-        self.role_of_class = [2 + c for c in range(root)] + [1]
-        self.quser = np.concatenate([np.full(w, self.role_of_class[c]) for c, (_, w) in enumerate(classes)])
-        rng.shuffle(self.quser)
-        self.nq = int(self.quser.size)
-        q = self.x[rng.integers(0, self.n, self.nq)].copy()
-        q[:, :5] = rng.integers(0, 256, (self.nq, 5)).astype(np.float32)
-        self.q = q
-        self._ref = {}
-        self._rows = {}
-
-    def rbac(self):
-        perms = []
-        for d, cls in enumerate(self.doc_class):
-            role = self.role_of_class[int(cls)]
-            perms += [(role, d + 1)] if role != 1 else [(r, d + 1) for r in range(1, len(self.classes) + 1)]
-        user_roles = [(r, r) for r in range(1, len(self.classes) + 1)]
-        return np.asarray(user_roles, dtype=np.int32), np.asarray(perms, dtype=np.int32)
-
-    def allowed_rows(self, oracle, user):
-        if user not in self._rows:
-            ur, perms = self.rbac()
-            self._rows[user] = np.flatnonzero(oracle.user_row_mask(user, ur, perms, self.doc))
-        return self._rows[user]
-
-    def ref(self, oracle, i):
-        """The oracle's top K_REF of query i (computed once; a smaller k is its head: same order), over the allowed rows only."""
-        i = int(i)
-        if i not in self._ref:
-            rows = self.allowed_rows(oracle, int(self.quser[i]))
-            idx, dist = oracle.filtered_topk("l2", self.x[rows], self.q[i], K_REF, self.doc[rows], self.blk[rows])
-            self._ref[i] = (rows[idx], dist)
-        return self._ref[i]
-
-
 @pytest.fixture(scope="module")
 def world():
-    return World(CLASSES)
+    return World(CLASSES, k_ref=K_REF)
 
 
 def _calls(w, ki):
