@@ -1,6 +1,7 @@
 // vsr_plan.h — the plan of one search batch: which passes scan which filter parts for which queries, on which kernel family,
 // in how many workgroups, seeded and merged how.  Written by make_plan (vsr_plan.hip), read by vsr_search.hip.
 #pragma once
+#include <cmath>
 #include "vsr_runtime.h"
 
 namespace vsr {
@@ -66,6 +67,19 @@ bool make_plan(const vsr_ctx* ctx, const vsr_corpus* c, int nq, int k, int metri
 // sample has probability ~1e-8, so the m-th smallest sampled key ranks behind the kp-th row.
 inline double seed_lambda(uint32_t kp, double frac) { return (double) kp * frac; }
 uint32_t seed_rank(uint32_t kp, double frac);
+
+// Survivors a wave-tile (64 rows x 16 queries) of the K2w main launch can expect: what a query admits over the rows it scans
+// (kp + 6 sqrt(kp / f) + 4 / f at the plan's sampling fraction f) x 1024 pairs per wave-tile / the pairs of an average query.
+// Up to MASK_EPI_SURVIVORS the mask epilogue wins (vsr_mfmaw.h, EPI = 1); the planner keeps a thinner sample below it too.
+constexpr double MASK_EPI_SURVIVORS = 4.0;
+inline double survivors_per_wave_tile(const Plan& plan, int nq)
+{
+    const double kp = plan.keep;
+    const double f = plan.kp_frac > 0 ? plan.kp_frac / kp : 1.0 / 16;
+    const double admitted = kp + 6.0 * std::sqrt(kp / f) + 4.0 / f;
+    const double rows_per_query = (double) plan.scan_pairs / std::max(1, nq);
+    return rows_per_query > 0 ? 1024.0 * admitted / rows_per_query : 2.0 * MASK_EPI_SURVIVORS;
+}
 
 // the instantiation the main scan launch of a plan resolves to (bench.py reports it beside the roofline)
 std::string scan_kernel_name(const Plan& plan, const vsr_corpus* c, int metric, bool k2i = false);

@@ -16,8 +16,15 @@ struct PlanIn {                              // what one make_plan call is asked
     const vsr_corpus*        c;
     int                      nq, k, metric;
     const vsr_filter* const* filters;
+    bool                     thin_sample;    // make_plan's first attempt: an int8 class-view plan may sample at VIEW_SAMPLE_STRIDE
     const vsr_filter* filter(uint32_t q) const { return filters ? filters[q] : nullptr; }
 };
+
+// The sample stride of int8 class-view plans whose sample launch is K2r.  The context's stride (16) dates from plans that
+// re-ranked every admitted row; on these plans a candidate costs an LDS park, a share of a column atomic and an 8-byte key,
+// and the seed admits (kp f + 6 sqrt(kp f) + 4) / f rows per query: 404 at f = 1/16, 568 at 1/32, 836 at 1/64 (kp = 100).
+// Measured on the headline step (profiles/r7): 32 beats 16 by more than the session's spread, 64 loses.
+constexpr uint32_t VIEW_SAMPLE_STRIDE = 32;
 
 struct PassItem { const vsr_filter* part; uint32_t slot; };     // part: atomic filter scanned (nullptr = whole corpus)
 struct Pass {
@@ -269,6 +276,16 @@ bool take_class_view(const PlanIn& in, const Plan& plan, std::vector<Pass>& pass
     return true;
 }
 
+// The stride the plan's sampling starts from: VIEW_SAMPLE_STRIDE for an int8 class-view plan that can sample on K2r (the
+// first planning attempt only: make_plan), else the context's.  An explicit VSR_SAMPLE_STRIDE always wins.
+uint32_t first_stride(const PlanIn& in, const Plan& plan)
+{
+    const vsr_ctx* ctx = in.ctx;
+    const bool thin = in.thin_sample && !ctx->sample_stride_set && plan.int8 && plan.class_view && ctx->k2i_sample && ctx->sample_reg &&
+                      in.c->shape.rw == 16 && ctx->sample_stride < VIEW_SAMPLE_STRIDE;
+    return thin ? VIEW_SAMPLE_STRIDE : ctx->sample_stride;
+}
+
 // ---- stage 4: workgroups of the launch ---------------------------------------------------------------------------
 // Workgroups per launch: 4 per CU (two resident at a time), and for big shared-pass launches one per ~13k scanned
 // rows up to 16 per CU -- finer blocks even out the passes' very different lengths over the chip (10M rows, 1000
@@ -304,6 +321,8 @@ LaunchSize size_launch(const PlanIn& in, const Plan& plan, const std::vector<Pas
         // 10M-row corpus); launches that fit one round anyway (a shard) keep the main launch's workgroups
         const int64_t slots = (plan.k2g ? 1 : plan.int8 ? 4 : 3) * cus * ctx->sample_rounds;   // (VSR_SAMPLE_ROUNDS: measurements only)
         ls.seed_div = (uint32_t) std::max<int64_t>(1, (ls.budget + slots - 1) / slots);
+        // a thinner sample: fewer, not shorter, workgroups -- each still walks about as many stages of a longer range
+        ls.seed_div = ls.seed_div * first_stride(in, plan) / ctx->sample_stride;
     }
     return ls;
 }
@@ -429,7 +448,8 @@ double densest_fraction(const std::vector<ScanGroup>& groups, int rw, double til
 bool try_k2i_sample(const PlanIn& in, PlanScratch& s, Plan& plan)
 {
     const vsr_corpus* c = in.c;
-    const double ss = in.ctx->sample_stride;
+    const uint32_t stride = first_stride(in, plan);
+    const double ss = stride;
     const double frac = densest_fraction(plan.groups_s, c->shape.rw, 32.0, ss);
     const uint32_t seed_m = seed_rank(plan.keep, frac);
     s.est.assign((size_t) in.nq, 0.0);
@@ -450,7 +470,7 @@ bool try_k2i_sample(const PlanIn& in, PlanScratch& s, Plan& plan)
     }
     if (!thick) return false;
     plan.k2i_sample = true;
-    plan.sample_stride = in.ctx->sample_stride;
+    plan.sample_stride = stride;
     plan.kp_frac = (float) seed_lambda(plan.keep, frac);
     for (ScanGroup& gs : plan.groups_s) gs.partial_begin = 0u;
     return true;
@@ -515,6 +535,8 @@ bool evaluate_stride(const PlanIn& in, uint32_t stride, PlanScratch& s, Plan& pl
 bool plan_wide_sampling(const PlanIn& in, PlanScratch& s, Plan& plan)
 {
     bool ok = plan.int8 && in.ctx->k2i_sample && in.c->shape.rw == 16 && try_k2i_sample(in, s, plan);
+    // (the thinner sample of a class-view plan is K2r's or nobody's: make_plan plans the call again at the context's stride)
+    if (!ok && first_stride(in, plan) != in.ctx->sample_stride) return false;
     // A sample too thin for some query at the configured stride is taken more densely (8, 4, 2) before the plan is given up:
     // K2g's 256-row tiles on a small corpus, and K2w over many small parts (IVFFlat lists: probes x ~1000 rows per query
     // used to fall back to the legacy kernels as soon as one query's lists added up to more than its candidate buffer).
@@ -643,23 +665,33 @@ bool vsr::make_plan(const vsr_ctx* ctx, const vsr_corpus* c, int nq, int k, int 
                     bool allow_gemm, const vsr_filter* const* filters, Plan& plan)
 {
     static thread_local PlanScratch s;
-    const PlanIn in{ctx, c, nq, k, metric, filters};
-    plan.reset();
-    plan.unique_rows = group_items(in, s);
-    const Width w = choose_width(in, s.gend, allow_screening, allow_wide, allow_gemm);
-    const uint32_t widest = cut_passes(in, w, s.items, s.passes, plan.q_slots);
-    set_family(in, w, widest, plan);
-    plan.class_view = take_class_view(in, plan, s.passes);
-    const LaunchSize ls = size_launch(in, plan, s.passes);
-    emit_groups(in, w.i8wide, ls, s, plan);
-    if (plan.k2 || plan.mq) map_blocks_to_xcds(s.lane, plan);
-    if (plan.k2w) {
-        const bool ok = plan_wide_sampling(in, s, plan);
-        plan.k2r_sample = ok && plan.class_view && plan.k2i_sample && ctx->sample_reg;   // same geometry, same entries (vsr_i8r.h)
-        return ok;
+    // An int8 class-view plan is first planned with the thinner sample (VIEW_SAMPLE_STRIDE: sample workgroups and seed rank
+    // follow from the stride, so the whole plan does).  It stands when everything that protects a seed holds at that stride --
+    // try_k2i_sample's thickness and buffer-capacity checks for every query, K2r as the sample kernel -- and the main launch
+    // keeps the mask epilogue under the looser seeds.  Otherwise (a query whose sample gets too thin, a small corpus) the call
+    // is planned again exactly as before: the context's stride, stepped down by plan_wide_sampling until the checks hold.
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        const PlanIn in{ctx, c, nq, k, metric, filters, attempt == 0};
+        plan.reset();
+        plan.unique_rows = group_items(in, s);
+        const Width w = choose_width(in, s.gend, allow_screening, allow_wide, allow_gemm);
+        const uint32_t widest = cut_passes(in, w, s.items, s.passes, plan.q_slots);
+        set_family(in, w, widest, plan);
+        plan.class_view = take_class_view(in, plan, s.passes);
+        const bool thin = first_stride(in, plan) != ctx->sample_stride;
+        const LaunchSize ls = size_launch(in, plan, s.passes);
+        emit_groups(in, w.i8wide, ls, s, plan);
+        if (plan.k2 || plan.mq) map_blocks_to_xcds(s.lane, plan);
+        if (plan.k2w) {
+            const bool ok = plan_wide_sampling(in, s, plan);
+            plan.k2r_sample = ok && plan.class_view && plan.k2i_sample && ctx->sample_reg;   // same geometry, same entries (vsr_i8r.h)
+            if (thin && !(plan.k2r_sample && survivors_per_wave_tile(plan, nq) <= MASK_EPI_SURVIVORS)) continue;
+            return ok;
+        }
+        build_select_items(in, ls.seed_div, s, plan);
+        return true;
     }
-    build_select_items(in, ls.seed_div, s, plan);
-    return true;
+    return false;                                              // (not reached: the second attempt never samples thin)
 }
 
 std::string vsr::scan_kernel_name(const Plan& plan, const vsr_corpus* c, int metric, bool k2i)

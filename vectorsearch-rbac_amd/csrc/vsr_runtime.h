@@ -101,6 +101,7 @@ struct vsr_ctx {
     bool   seeding = true;        // seed thresholds of big shared passes from a 1/32 sample pass
     int64_t seed_min_rows = 2000000;
     uint32_t sample_stride = 16;  // K2w sample launch: every 16th tile of a workgroup (VSR_SAMPLE_STRIDE)
+    bool   sample_stride_set = false;   // ... given explicitly: the planner's own choice for int8 class-view plans (every 32nd) stands back
     // threshold seeding of the K2 / K1m shared passes (vsr_search.hip): the sample pass visits every seed_stride-th tile with
     // 1/seed_block_div of the workgroups (measured on MI355X: 256 / 1 is the cheapest sample that still seeds tightly)
     uint32_t seed_stride = 256;   // VSR_SEED_STRIDE

@@ -96,7 +96,10 @@ extern "C" int vsr_open(int device, vsr_ctx** out)
     if ((env = getenv("VSR_NO_XCD_MAP"))) ctx->no_xcd_map = atoi(env) != 0;
     if ((env = getenv("VSR_MIN_SHARED_ROWS"))) ctx->min_shared_rows = std::max(64, atoi(env));
     if ((env = getenv("VSR_SEED_MIN_PASS"))) ctx->seed_min_pass_rows = atoll(env);
-    if ((env = getenv("VSR_SAMPLE_STRIDE"))) ctx->sample_stride = (uint32_t) std::min(512, std::max(2, atoi(env)));
+    if ((env = getenv("VSR_SAMPLE_STRIDE"))) {
+        ctx->sample_stride = (uint32_t) std::min(512, std::max(2, atoi(env)));
+        ctx->sample_stride_set = true;
+    }
     if ((env = getenv("VSR_SAMPLE_REG"))) ctx->sample_reg = atoi(env) != 0;
     if ((env = getenv("VSR_SELECT_WAVE"))) ctx->select_wave = atoi(env) != 0;
     if ((env = getenv("VSR_SAMPLE_ROUNDS"))) ctx->sample_rounds = (uint32_t) std::min(4, std::max(1, atoi(env)));

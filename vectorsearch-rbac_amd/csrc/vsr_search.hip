@@ -380,13 +380,7 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
         sp.groups = reinterpret_cast<const ScanGroup*>(ds + off_g);
         sp.n_groups = (uint32_t) plan.groups.size();
         sp.sample_stride = 1;
-        {
-            // survivors a wave-tile (64 rows x 16 queries) can expect: what a query admits over the rows it scans
-            const double f = plan.kp_frac > 0 ? plan.kp_frac / kp : 1.0 / 16;
-            const double admitted = kp + 6.0 * std::sqrt(kp / f) + 4.0 / f;
-            const double rows_per_query = (double) plan.scan_pairs / std::max(1, nq);
-            sp.epi = rows_per_query > 0 && 1024.0 * admitted / rows_per_query <= 4.0 ? 1u : 0u;
-        }
+        sp.epi = survivors_per_wave_tile(plan, nq) <= MASK_EPI_SURVIVORS ? 1u : 0u;
         if (ctx->force_epi >= 0) sp.epi = (uint32_t) ctx->force_epi;
         if (plan.int8 && plan.qmax > 64) sp.epi = 1u;       // 128-column passes exist on K2i only (its parking area takes bursts)
         sp.k2i = plan.int8 && !plan.k2g && sp.epi == 1 && !ctx->no_k2i && sp.rw == 16 && sp.qmax <= 128 ? 1u : 0u;
@@ -404,7 +398,8 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
             HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->lane_out, 0));
         }
         ctx->last_kernel = scan_kernel_name(plan, c, metric, ctx->last_k2i);
-        if (plan.k2r_sample) ctx->last_kernel += " + sample vsr::i8_sample_reg_kernel<NQG=4> (K2r)";
+        if (plan.k2r_sample)
+            ctx->last_kernel += " + sample vsr::i8_sample_reg_kernel<NQG=4> (K2r, stride " + std::to_string(plan.sample_stride) + ")";
         else if (plan.k2i_sample) ctx->last_kernel += " + sample vsr::i8_stream_kernel<NQG=4, SAMPLE=true>";
         else if (plan.int8) ctx->last_kernel += " + sample vsr::mfma_wide_kernel<L2, NCH=1, SAMPLE=true, PL=int8>";
         count_scan(ctx, plan, 1);
