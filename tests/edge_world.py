@@ -1,6 +1,7 @@
 """Corpora whose permission classes put the number of allowed rows of a query on the edges of the final selection
 (vsr_kernels.hip: select_emit_wave_kernel, select_rerank_kernel, K5 + rerank_kernel, rerank_body).  Shared by
-test_gpu_select_wave.py (the int8 planes) and test_screen_edges.py (the bf16, fp32-MFMA and f16 screening tiers).
+test_gpu_select_wave.py (the int8 planes), test_screen_edges.py (the bf16, fp32-MFMA and f16 screening tiers) and
+test_gpu_exact_shared.py (K1m, whose edges are those of its candidate buffers).
 
 A World is ~n rows x d in documents of at most 100 rows, dealt in random order over the classes.  The RBAC is a tree as
 vsrbac.datasets.tree_rbac makes it (a role is permitted its own documents and its ancestors'; a user holds one role): the
@@ -101,13 +102,20 @@ class World:
             self._ref[(metric, i)] = (rows[idx], dist)
         return self._ref[(metric, i)]
 
-    def exact_bound(self):
+    def exact_bound(self, l1=False):
         """max over rows and queries of (|x| + |q|)^2: bounds every partial sum of |x - q|^2, of |x|^2 + |q|^2 - 2 x.q and of
-        x.q.  Asserts that the values are integers and the bound is below 2^24."""
+        x.q -- and with them the three sums of a cosine distance, x.q, |x|^2 and |q|^2.  l1: also |x|_1 + |q|_1, which bounds
+        every partial sum of sum |x_i - q_i|; the larger of the two is returned.  Asserts that the values are integers and the
+        bound is below 2^24."""
         q = np.stack([self.rq(v) for v in self.q])
         assert (self.x == np.rint(self.x)).all() and (q == np.rint(q)).all()
         nx = float((self.x.astype(np.float64) ** 2).sum(1).max())
         nq = float((q.astype(np.float64) ** 2).sum(1).max())
         bound = (np.sqrt(nx) + np.sqrt(nq)) ** 2
         assert bound < 2 ** 24, (nx, nq, bound)
+        if l1:
+            ax = float(np.abs(self.x.astype(np.float64)).sum(1).max())
+            aq = float(np.abs(q.astype(np.float64)).sum(1).max())
+            assert ax + aq < 2 ** 24, (ax, aq)
+            bound = max(bound, ax + aq)
         return bound
