@@ -140,8 +140,10 @@ int     vsr_corpus_is_half(const vsr_corpus* corpus);        /* 1 / 0 */
  * (CheckDims, bitvec.c:32-39).  vsr_search_bit* on a corpus that is not a bit corpus, or with a metric other than 4 / 5:
  * VSR_ERR_INVALID.  vsr_search*, vsr_ivf_load, vsr_ivf_assign, vsr_hnsw_load and vsr_hnsw_build* over a bit corpus:
  * VSR_ERR_UNSUPPORTED, the message names the bit corpus.  The HNSW opclasses bit_hamming_ops / bit_jaccard_ops are
- * vsr_hnsw_load_bit / vsr_hnsw_build_bit / vsr_hnsw_search_bit* below; IVFFlat over bits is not built yet.  The float entry
- * points keep rejecting metrics 4 / 5 with VSR_ERR_INVALID. */
+ * vsr_hnsw_load_bit / vsr_hnsw_build_bit / vsr_hnsw_search_bit* below; the IVFFlat opclass bit_hamming_ops is vsr_ivf_kmeans_bit /
+ * vsr_ivf_assign_bit / vsr_ivf_load_bit / vsr_ivf_probe_bit / vsr_ivf_search_bit* below (K3b) -- vsr_ivf_load and vsr_ivf_assign keep
+ * their refusal of a bit corpus, whose message predates those entry points.  The float entry points keep rejecting metrics 4 / 5
+ * with VSR_ERR_INVALID. */
 int vsr_corpus_load_bit(vsr_ctx* ctx, const uint8_t* rows, int64_t n, int dim,
                         const int64_t* block_ids, const int32_t* doc_ids, int64_t row_offset,
                         vsr_corpus** out);
@@ -474,6 +476,54 @@ int vsr_ivf_load_half(vsr_corpus* half_corpus, const uint16_t* centers /* [lists
 int vsr_ivf_assign_half(vsr_corpus* half_corpus, const uint16_t* centers, int lists, int metric, int32_t* out_row_list);
 int vsr_ivf_kmeans_half(vsr_ctx* ctx, int metric, int dim, const uint16_t* samples, int64_t n_samples, int lists, uint64_t seed,
                         uint16_t* out_centers, int* out_iterations);
+
+/* ---- IVFFlat over a bit corpus: bit_hamming_ops (ivfflat_bit_support, ivfutils.c:248-252, 278-292, 316-323, 364-377;
+ * test/sql/ivfflat_bit.sql, test/t/035_ivfflat_bit_build_recall.pl, test/t/036_ivfflat_bit_centers.pl) (K3b) ----------------------
+ * The one ivfflat opclass of the type: list, row and k-means distance are all hamming_distance; there is no Jaccard opclass, no
+ * norm procedure, nothing spherical.  dim counts bits, 1 .. 64000; lists 1 .. 32768.
+ *   - Packed bit strings everywhere -- rows, queries, samples, centres: varbit order (vsr_corpus_load_bit's), ceil(dim / 8) bytes
+ *     each; bits past dim in the last byte are ignored on every input, centres included, and clear on every output.
+ *   - Centres are bit strings.  k-means (vsr_ivf_kmeans_bit) is pgvector's for the type: k-means++ and Elkan's bounds as in
+ *     vsr_ivf_kmeans, the distance the Hamming count as a double; a new centre has bit i set where the fp32 quotient (members with
+ *     bit i) / (members) > 0.5; an empty centre draws one value per bit from the serial stream, in (centre, bit) order, and takes
+ *     the same > 0.5.  Every quantity is an integer or half-integer exact in fp32 and double, so the same seed and samples give the
+ *     same centres and iteration count as a restatement on any host, bit for bit.  Samples and centres stay packed on the device.
+ *   - Centre order: (Hamming count, list id), the lower list id first among equals -- one key for a (row or query, centre) pair in
+ *     the probe, the assignment and the iterative scan.
+ *   - Rows inside the lists rank as vsr_search_bit ranks them: ((float) Hamming count, document_id, block_id).
+ *   - The list-ordered image holds the packed rows (16-byte chunks, as the corpus), their popcounts and the rank map; the centres
+ *     stay packed: no fp32 image of anything.  The searches run K1b over the image: all filter modes, k <= VSR_MAX_K, the -1 / +Inf
+ *     fill and vsr_stats_get as for vsr_search_bit; nothing is screened, nothing flags.
+ *   - vsr_ivf_search_bit(_device) and vsr_ivf_search_bit_iterative(_device) have the contracts of vsr_ivf_search(_device) and
+ *     vsr_ivf_search_iterative(_device) with packed queries; metric is VSR_METRIC_HAMMING.  vsr_ivf_free and vsr_ivf_device_bytes
+ *     take the index as they take any.
+ *   - Errors.  A corpus that is not a bit corpus: VSR_ERR_INVALID, "the corpus is not a bit corpus".  vsr_ivf_probe_bit /
+ *     vsr_ivf_search_bit* on an index that is not over a bit corpus: VSR_ERR_INVALID, "the index is not over a bit corpus (it is
+ *     searched with vsr_ivf_search*)".  vsr_ivf_probe, vsr_ivf_search* and vsr_ivf_search_iterative* on a bit index:
+ *     VSR_ERR_UNSUPPORTED, "the index is over a bit corpus: it is searched with vsr_ivf_search_bit* (<~>)".  VSR_METRIC_JACCARD:
+ *     VSR_ERR_UNSUPPORTED, "ivfflat has no bit_jaccard_ops operator class"; any other metric VSR_ERR_INVALID.  A dimension mismatch
+ *     is VSR_ERR_DIM_MISMATCH, "different bit lengths %u and %u"; the format refusal wins over it.  probes, max_probes, mode, k,
+ *     NULL and list-id checks are those of the float entry points. */
+int vsr_ivf_kmeans_bit(vsr_ctx* ctx, int dim_bits, const uint8_t* samples /* [n][(dim+7)/8] */, int64_t n_samples, int lists,
+                       uint64_t seed, uint8_t* out_centers /* [lists][(dim+7)/8] */, int* out_iterations);
+int vsr_ivf_assign_bit(vsr_corpus* bit_corpus, const uint8_t* centers, int lists, int32_t* out_row_list);
+int vsr_ivf_load_bit(vsr_corpus* bit_corpus, const uint8_t* centers, int lists, const int32_t* row_list, vsr_ivf** out);
+int vsr_ivf_probe_bit(vsr_ivf* ivf, const uint8_t* queries, int nq, int dim, int probes, int32_t* out_lists /* nq*probes */);
+int vsr_ivf_search_bit(vsr_ivf* ivf, const uint8_t* queries, int nq, int dim, int k, int probes, int metric,
+                       const vsr_filter* const* filters,
+                       int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows, float* out_dist, int32_t* out_counts);
+int vsr_ivf_search_bit_device(vsr_ivf* ivf, const uint8_t* d_queries, int nq, int dim, int k, int probes, int metric,
+                              const vsr_filter* const* filters,
+                              int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
+                              int32_t* d_out_counts);
+int vsr_ivf_search_bit_iterative(vsr_ivf* ivf, const uint8_t* queries, int nq, int dim, int k, int probes, int metric,
+                                 const vsr_filter* const* filters, int mode, int max_probes,
+                                 int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows, float* out_dist,
+                                 int32_t* out_counts, int32_t* out_probes);
+int vsr_ivf_search_bit_iterative_device(vsr_ivf* ivf, const uint8_t* d_queries, int nq, int dim, int k, int probes, int metric,
+                                        const vsr_filter* const* filters, int mode, int max_probes,
+                                        int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
+                                        int32_t* d_out_counts, int32_t* d_out_probes);
 
 /* ---- HNSW graph search (pgvector/src/hnswscan.c:15-45,179-316; hnswutils.c:813-976) -------------------------- */
 /* A graph as pgvector's in-memory build leaves it (hnswbuild.c:357-470): n_elem elements, each with a top level, up to 10

@@ -56,6 +56,28 @@ hipError_t launch_stage_bit(const StageParams& p, hipStream_t s)
     return hipGetLastError();
 }
 
+// one thread per output byte
+__global__ __launch_bounds__(256) void pack_bits_kernel(const uint8_t* src, uint32_t src_stride, uint32_t n, uint32_t dim, uint8_t* dst,
+                                                        uint32_t dst_bytes)
+{
+    const uint32_t src_bytes = (dim + 7u) / 8u;
+    const uint64_t total = (uint64_t) n * dst_bytes;
+    for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t) gridDim.x * 256) {
+        const uint32_t s = (uint32_t) (i / dst_bytes), j = (uint32_t) (i % dst_bytes);
+        dst[i] = j < src_bytes ? (uint8_t) ((uint32_t) src[(size_t) s * src_stride + j] & bit_byte_mask(j, dim)) : (uint8_t) 0;
+    }
+}
+
+hipError_t launch_pack_bits(const uint8_t* src, uint32_t src_stride, uint32_t n, uint32_t dim, uint8_t* dst, uint32_t dst_bytes,
+                            hipStream_t s)
+{
+    const uint64_t total = (uint64_t) n * dst_bytes;
+    if (total == 0) return hipSuccess;
+    hipLaunchKernelGGL(pack_bits_kernel, dim3((uint32_t) std::min<uint64_t>((total + 255) / 256, 16384)), dim3(256), 0, s, src, src_stride, n,
+                       dim, dst, dst_bytes);
+    return hipGetLastError();
+}
+
 // one wave per row
 __global__ __launch_bounds__(256) void row_popcounts_kernel(const uint4* rows, uint32_t n_rows, uint32_t chunks, float* pop)
 {

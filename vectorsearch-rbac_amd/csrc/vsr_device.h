@@ -487,6 +487,10 @@ hipError_t launch_sparse_pair_distances(const int64_t* a_ptr, const int32_t* a_i
 hipError_t launch_stage_bit(const StageParams& p, hipStream_t s);      // p.q_bits != 0
 // bit corpora (vsr_bit.hip).  Popcount of every row of `chunks` 16-byte chunks, as fp32 (exact: <= 64000)
 hipError_t launch_row_popcounts(const uint4* rows, uint32_t n_rows, uint32_t chunks, float* pop, hipStream_t s);
+// n bit strings of ceil(dim / 8) bytes, src_stride bytes apart (any alignment), as rows of dst_bytes bytes (a multiple of 4) with
+// the pad bits and everything behind them clear: the query side of the bit centre key (IVF_BIT, vsr_exact.h)
+hipError_t launch_pack_bits(const uint8_t* src, uint32_t src_stride, uint32_t n, uint32_t dim, uint8_t* dst, uint32_t dst_bytes,
+                            hipStream_t s);
 // binary_quantize (vector.c:941-968): bit = x > 0, element i -> bit 7 - i % 8 of byte i / 8.  src: n rows of src_stride elements
 // (fp32, or binary16 bit patterns when src_half), dim of them valid; dst: n rows of dst_bytes bytes, everything past dim zero
 hipError_t launch_binary_quantize(const void* src, int src_half, uint64_t n_rows, uint32_t dim, uint32_t src_stride, uint8_t* dst,
@@ -516,7 +520,8 @@ hipError_t launch_gather_class_view(const uint4* src, const float* src_norm, uin
 hipError_t launch_view_bitmap(const uint32_t* rank, uint32_t n_rows, const uint2* tiles, uint32_t n_tiles, const uint64_t* bitmap,
                               uint64_t* out, hipStream_t s);
 // form: IVF_F32 (fp32 queries and centres), IVF_HALF_Q32 / IVF_HALF_ROW (binary16 centres; fp32 queries rounded on load / binary16
-// rows in place): vsr_exact.h.  q_stride counts elements of the query side's type.
+// rows in place): vsr_exact.h.  q_stride counts elements of the query side's type.  IVF_BIT (K3b): packed centres [words][lists],
+// packed queries or bit rows; `dim` and q_stride count 32-bit words.
 hipError_t launch_ivf_probe(const void* queries, uint32_t q_stride, uint32_t nq, const void* centers_t /* [dim][lists] */, int dim, int lists, int probes,
                             int metric, int32_t* out, hipStream_t s, int form = 0);
 hipError_t launch_vector_fn(int mode, const float* a, const float* b, int64_t n, int dim, int b_broadcast, double* out_d,

@@ -116,7 +116,12 @@ __device__ __forceinline__ float exact_rank_value(int metric, float s, float nx,
 //                to binary16 (Float4ToHalf, nearest even) as it is loaded and widened again: `$1::halfvec` (probe, iterative scan);
 //   IVF_HALF_ROW binary16 centres, the query is a binary16 row read in place (the build's assignment over a halfvec corpus).
 // The two half forms run the same fp32 sequence on the same widened values: a (query, centre) pair has one key.
-enum { IVF_F32 = 0, IVF_HALF_Q32 = 1, IVF_HALF_ROW = 2 };
+//   IVF_BIT      K3b, bit_hamming_ops (ivfutils.c:364-377: FUNCTION 1 is hamming_distance): the centres are packed bit strings,
+//                transposed by 32-bit word -- centers_t[w][c], `dim` counts WORDS here -- so a wave's word step is again 256
+//                contiguous bytes; the query side is packed words with the pad bits clear (a staged query, the query in LDS of
+//                the iterative scan, or a corpus row in place: rows are zero padded to whole 16-byte chunks >= the words).  The
+//                key is the popcount sum itself: monotone already, at most 64000, never the `taken` mark.  `metric` is not read.
+enum { IVF_F32 = 0, IVF_HALF_Q32 = 1, IVF_HALF_ROW = 2, IVF_BIT = 3 };
 
 template <int FORM>
 __device__ __forceinline__ float ivf_query_element(const void* q, int j)
@@ -129,6 +134,13 @@ __device__ __forceinline__ float ivf_query_element(const void* q, int j)
 template <int FORM = IVF_F32>
 __device__ __forceinline__ uint32_t ivf_center_key(const void* centers_t, int lists, int dim, int c, const void* q, int metric)
 {
+    if constexpr (FORM == IVF_BIT) {
+        const uint32_t* x = static_cast<const uint32_t*>(centers_t) + c;
+        const uint32_t* qw = static_cast<const uint32_t*>(q);
+        uint32_t count = 0;
+        for (int w = 0; w < dim; ++w) count += (uint32_t) __popc(x[(size_t) w * lists] ^ qw[w]);
+        return count;
+    }
     using CT = typename std::conditional<FORM == IVF_F32, float, _Float16>::type;
     const CT* x = static_cast<const CT*>(centers_t) + c;
     float sum = 0.0f;

@@ -30,6 +30,7 @@
 #pragma once
 #include "vsr_device.h"
 #include "vsr_exact.h"
+#include "vsr_bitops.h"
 #include "vsr_topk.h"
 
 namespace vsr {
@@ -38,10 +39,10 @@ constexpr uint32_t IVI_CHUNK = 512;          // appended keys between two folds 
 constexpr uint32_t IVI_MIN_KEPT = 512;       // the fold reads kept[SK - 1 - j], j < IVI_CHUNK
 
 struct IvfIterParams {
-    const float*           queries;          // [nq][q_stride] (device)
+    const float*           queries;          // [nq][q_stride] (device); rows_bit: packed bit strings, q_stride BYTES apart
     uint32_t               q_stride;
     uint32_t               dim;
-    const void*            centers_t;        // [dim][lists]: fp32, or binary16 when rows_half (K3h)
+    const void*            centers_t;        // [dim][lists]: fp32, or binary16 when rows_half (K3h); rows_bit: packed, [words][lists]
     uint32_t               lists;
     int                    center_metric;    // M_L2, or M_IP for the inner-product and cosine opclasses
     int                    metric;           // the operator the rows rank by
@@ -51,6 +52,7 @@ struct IvfIterParams {
     const uint32_t*        list_start;       // [lists + 1] offsets into the view
     const float4*          rows;             // the view's rows, [n_rows][stride4], zero padded
     uint32_t               rows_half;        // 1: the view of a halfvec corpus, [n_rows][stride4 / 2] chunks of 8 binary16 values
+    uint32_t               rows_bit;         // 1: the view of a bit corpus (K3b), [n_rows][stride4] chunks of packed bits, pad bits clear
     uint32_t               stride4;
     uint32_t               n_rows;
     const uint32_t*        rank;             // view row -> base row (what keys carry)
@@ -72,9 +74,10 @@ __host__ __device__ inline uint32_t ivf_iter_kept(uint32_t k)
     while (sk < k) sk <<= 1;
     return sk;
 }
-inline size_t ivf_iter_lds_bytes(uint32_t lists, uint32_t stride4, uint32_t k)
+// (bit: the view of a bit corpus -- stride4 is its chunks per row -- whose waves also keep the 64 counts of a step)
+inline size_t ivf_iter_lds_bytes(uint32_t lists, uint32_t stride4, uint32_t k, bool bit = false)
 {
-    return (((size_t) lists * 4 + 15) & ~(size_t) 15) + (size_t) stride4 * 16 + 4 * 64 * 4 + (size_t) (ivf_iter_kept(k) + IVI_CHUNK) * 8 + 64;
+    return (((size_t) lists * 4 + 15) & ~(size_t) 15) + (size_t) stride4 * 16 + (bit ? 2 : 1) * 4 * 64 * 4 + (size_t) (ivf_iter_kept(k) + IVI_CHUNK) * 8 + 64;
 }
 
 #ifdef __HIPCC__
@@ -112,9 +115,18 @@ __device__ __forceinline__ void ivf_iter_fold(uint64_t* kept, uint32_t sk, uint6
 // HALF (K3h): rows and centres are binary16.  The query is rounded to binary16 as it is loaded (`$1::halfvec`) and kept in LDS
 // widened, as fp32 -- the LDS formula does not change -- so the row sums (halfwave_row_sums<U, true>), cosine's |q|^2 and the
 // centre keys (IVF_HALF_Q32, from the query in global memory, rounded the same way) all see the same values.
-template <bool HALF>
+//
+// IVI_BIT (K3b, bit_hamming_ops): rows, centres and the query are packed bits.  The query goes into LDS byte by byte (device
+// queries need no alignment) with the pad bits and the rest of its stride4 chunks cleared; the centre keys are IVF_BIT's Hamming
+// counts of that LDS image -- the probe's key of the same pair; a step's permitted rows are gathered by lane groups and counted
+// by bit_graph_distances (vsr_bitops.h), 64 counts per wave step into LDS, and lane j makes the key of row j: the value is the
+// count as fp32, as K1b's.  Selection, folding, bounds checks and out_probes are the code below, unchanged.
+enum { IVI_F32 = 0, IVI_HALF = 1, IVI_BIT = 2 };
+
+template <int FORM>
 __global__ __launch_bounds__(256) void ivf_iterative_kernel(const IvfIterParams p)
 {
+    constexpr bool HALF = FORM == IVI_HALF, BIT = FORM == IVI_BIT;
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t qi = blockIdx.x;
@@ -131,19 +143,36 @@ __global__ __launch_bounds__(256) void ivf_iterative_kernel(const IvfIterParams 
     off += (size_t) p.stride4 * 16;
     uint32_t* rowsel = reinterpret_cast<uint32_t*>(smem + off) + wave * 64;   // this wave's compacted rows of a step
     off += 4 * 64 * 4;
+    float* counts = reinterpret_cast<float*>(smem + off) + wave * 64;        // BIT: this wave's Hamming counts of a step
+    if (BIT) off += 4 * 64 * 4;
     uint64_t* kept = reinterpret_cast<uint64_t*>(smem + off);             // [sk]
     off += (size_t) sk * 8;
     uint64_t* chunk = reinterpret_cast<uint64_t*>(smem + off);            // [IVI_CHUNK]
     off += (size_t) IVI_CHUNK * 8;
     IvfIterCtrl* ctrl = reinterpret_cast<IvfIterCtrl*>(smem + off);
 
-    const float* qg = p.queries + (size_t) qi * p.q_stride;
-    {
+    if constexpr (BIT) {
+        const uint8_t* qb = reinterpret_cast<const uint8_t*>(p.queries) + (size_t) qi * p.q_stride;
+        uint8_t* ql = reinterpret_cast<uint8_t*>(q4);
+        const uint32_t src_bytes = (p.dim + 7u) / 8u;
+        for (uint32_t j = tid; j < p.stride4 * 16; j += 256) {
+            uint32_t v = 0;
+            if (j < src_bytes) {
+                const uint32_t live = p.dim - j * 8u;                        // >= 1: the valid bits of byte j from its top
+                v = (uint32_t) qb[j] & (live >= 8u ? 0xFFu : (0xFF00u >> live) & 0xFFu);
+            }
+            ql[j] = (uint8_t) v;
+        }
+        __syncthreads();                                                   // the centre keys read the whole query
+        for (int c = tid; c < (int) p.lists; c += 256)
+            ckeys[c] = ivf_center_key<IVF_BIT>(p.centers_t, (int) p.lists, (int) ((p.dim + 31u) / 32u), c, q4, p.center_metric);
+    } else {
+        const float* qg = p.queries + (size_t) qi * p.q_stride;
         float* qf = reinterpret_cast<float*>(q4);
         for (uint32_t j = tid; j < p.stride4 * 4; j += 256) qf[j] = j < p.dim ? (HALF ? (float) (_Float16) qg[j] : qg[j]) : 0.0f;
+        for (int c = tid; c < (int) p.lists; c += 256)
+            ckeys[c] = ivf_center_key<HALF ? IVF_HALF_Q32 : IVF_F32>(p.centers_t, (int) p.lists, (int) p.dim, c, qg, p.center_metric);
     }
-    for (int c = tid; c < (int) p.lists; c += 256)
-        ckeys[c] = ivf_center_key<HALF ? IVF_HALF_Q32 : IVF_F32>(p.centers_t, (int) p.lists, (int) p.dim, c, qg, p.center_metric);
     if (tid == 0) ctrl->bad = 0;
     __syncthreads();
     const float qn = p.metric == M_COSINE ? wave_query_norm2(q4, p.stride4, lane) : 0.0f;
@@ -202,7 +231,34 @@ __global__ __launch_bounds__(256) void ivf_iterative_kernel(const IvfIterParams 
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 const uint64_t tau = lds_peek(&ctrl->tau);                 // a stale (larger) tau only admits extra keys
-                for (uint32_t j0 = 0; j0 < n_ok; j0 += 2 * U) {
+                if constexpr (BIT) {
+                    if (n_ok) {                                            // (wave-uniform)
+                        const uint4* rows16 = reinterpret_cast<const uint4*>(p.rows);
+                        const uint4* qs = reinterpret_cast<const uint4*>(q4);
+                        const uint32_t G = bit_graph_lanes(p.stride4), gl = (uint32_t) lane & (G - 1u);
+                        const uint4 qreg = gl < p.stride4 ? qs[gl] : make_uint4(0u, 0u, 0u, 0u);
+                        // rowsel[j] < s1 <= n_rows < 2^31 (launcher): a row id of the view as the gather takes it
+                        bit_graph_distances<false>(rows16, p.stride4, G, nullptr, nullptr, qs, qreg, 0.0f,
+                                                   reinterpret_cast<const int32_t*>(rowsel), (int) n_ok, counts, lane);
+                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                        const bool mine = (uint32_t) lane < n_ok;
+                        const uint32_t br = mine ? p.rank[rowsel[lane]] : 0u;
+                        const bool in_range = br < p.n_rows;
+                        if (mine && !in_range) ctrl->bad = 1;              // never a key, never an address
+                        const uint64_t key = make_key(mine ? counts[lane] : 0.0f, br);
+                        const bool pass = mine && in_range && key < tau;
+                        const uint64_t pm = __ballot(pass);
+                        if (pm) {
+                            const int leader = __ffsll((unsigned long long) pm) - 1;
+                            uint32_t at = 0;
+                            if (lane == leader) at = atomicAdd(&ctrl->count, (uint32_t) __popcll(pm));
+                            at = (uint32_t) __shfl((int) at, leader) + (uint32_t) __popcll(pm & ((1ull << lane) - 1ull));
+                            if (pass && at < IVI_CHUNK) chunk[at] = key;
+                        }
+                    }
+                }
+                for (uint32_t j0 = 0; !BIT && j0 < n_ok; j0 += 2 * U) {          // fp32 / binary16 rows
                     uint32_t row[U];
                     float s[U], nx[U];
 #pragma unroll

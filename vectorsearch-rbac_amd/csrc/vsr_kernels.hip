@@ -1346,6 +1346,8 @@ hipError_t launch_view_bitmap(const uint32_t* rank, uint32_t n_rows, const uint2
 // The sums run in the order and rounding of vector.c's loops compiled without contraction (one lane per centre).
 // FORM (vsr_exact.h): IVF_F32; IVF_HALF_Q32 / IVF_HALF_ROW = K3h, binary16 centres against fp32 queries rounded on load or
 // against the binary16 rows of a halfvec corpus in place.  q_stride counts elements of the query side's type.
+// IVF_BIT = K3b: packed centres [words][lists] against packed queries or bit rows; `dim` and q_stride count 32-bit words and the
+// key is the Hamming count.
 template <int FORM>
 __global__ __launch_bounds__(256) void ivf_probe_kernel(const void* queries, uint32_t q_stride, const void* centers_t, int dim,
                                                         int lists, int probes, int metric, int32_t* out)
@@ -1392,6 +1394,7 @@ hipError_t launch_ivf_probe(const void* queries, uint32_t q_stride, uint32_t nq,
     case IVF_F32: return launch_ivf_probe_form<IVF_F32>(queries, q_stride, nq, centers_t, dim, lists, probes, metric, out, s);
     case IVF_HALF_Q32: return launch_ivf_probe_form<IVF_HALF_Q32>(queries, q_stride, nq, centers_t, dim, lists, probes, metric, out, s);
     case IVF_HALF_ROW: return launch_ivf_probe_form<IVF_HALF_ROW>(queries, q_stride, nq, centers_t, dim, lists, probes, metric, out, s);
+    case IVF_BIT: return launch_ivf_probe_form<IVF_BIT>(queries, q_stride, nq, centers_t, dim, lists, probes, metric, out, s);
     default: return hipErrorInvalidValue;
     }
 }

@@ -13,12 +13,23 @@
 // kernel (the distance sweep before it is parallel).  Same seed and samples => the same centres as the checker bit for bit
 // for L2; the spherical variant (inner product / cosine opclasses) goes through acos(), whose last bit may differ between
 // the device's and the host's libm: there the centres agree within 1e-6 and the assignments are checked instead.
+//
+// K3b, bit_hamming_ops (vsr_ivf_kmeans_bit; ivfutils.c:278-292 BitUpdateCenter, :316-323 BitSumCenter, :364-377): the same
+// algorithm with two substitutions.  The distance is hamming_distance, the count as a double.  A new centre is a bit string: the
+// reference adds each member's bits into an fp32 vector, divides by the member count in fp32 and sets bit i where x[i] > 0.5.
+// Samples and centres stay PACKED here (KmState::bits: 32-bit words, pad bits clear; no fp32 image of either): the distance is
+// a xor + popcount loop, the per-(centre, bit) sum an integer count over the centre's sorted members -- an fp32 sum of at most
+// 2^24 ones is that integer -- and the update `(float) count / (float) n > 0.5f`, written as the reference computes it.  Every
+// distance, half-distance and squared weight is an integer or half-integer that fp32 and double hold exactly, so the result equals
+// a restatement on any host bit for bit, on any data.
 #include "../../include/vsrbac.h"
 #include "vsr_device.h"
 
 #include <hipcub/hipcub.hpp>
 #include <cfloat>
 #include <cstdio>
+#include <cstring>
+#include <vector>
 
 namespace vsr {
 
@@ -55,6 +66,17 @@ __device__ __forceinline__ double km_distance(int metric, int dim, const float* 
     return acos(d) / 3.14159265358979323846;
 }
 
+// hamming_distance (bitvec.c:46-60) of two packed strings whose pad bits are clear
+__device__ __forceinline__ double km_bit_distance(int words, const uint32_t* a, const uint32_t* b)
+{
+    uint32_t count = 0;
+    for (int w = 0; w < words; ++w) count += (uint32_t) __popc(a[w] ^ b[w]);
+    return (double) count;
+}
+
+// element e of a bit string in varbit order: bit 7 - e % 8 of byte e / 8, bytes little-endian in the 32-bit word
+__host__ __device__ inline uint32_t km_bit_of_element(int e) { return 1u << (8 * ((e & 31) >> 3) + 7 - (e & 7)); }
+
 // a value on its way into a centre of a halfvec index: HalfvecUpdateCenter (ivfutils.c:266-276) stores Float4ToHalfUnchecked(x),
 // round to nearest even, and everything downstream reads it widened again
 __device__ __forceinline__ float km_center_value(int round_half, float v) { return round_half ? (float) (_Float16) v : v; }
@@ -77,6 +99,11 @@ __device__ inline void km_norm_center(int dim, float* c, int round_half)
 struct KmState {
     int metric, dim, nc;
     int round_half;            // vsr_ivf_kmeans_half: every value written into centers / newc is rounded to binary16 and widened again
+    int bits;                  // vsr_ivf_kmeans_bit: dim counts bits; bsamples / bcenters / bnewc replace samples / centers / newc
+    int words;                 // ... 32-bit words per packed string
+    const uint32_t* bsamples;  // [ns][words]
+    uint32_t* bcenters;        // [nc][words]
+    uint32_t* bnewc;           // [nc][words]
     int64_t ns;
     const float* samples;      // [ns][dim]
     float* centers;            // [nc][dim]
@@ -97,10 +124,35 @@ struct KmState {
     KmRng* rng;                // [1]
 };
 
+// the k-means distance by the form of the samples: sample j to centre c, centre a to centre b, centre c to its successor
+__device__ __forceinline__ double km_sample_distance(const KmState& k, int64_t j, int c)
+{
+    if (k.bits) return km_bit_distance(k.words, k.bsamples + (size_t) j * k.words, k.bcenters + (size_t) c * k.words);
+    return km_distance(k.metric, k.dim, k.samples + (size_t) j * k.dim, k.centers + (size_t) c * k.dim);
+}
+__device__ __forceinline__ double km_center_distance(const KmState& k, int a, int b)
+{
+    if (k.bits) return km_bit_distance(k.words, k.bcenters + (size_t) a * k.words, k.bcenters + (size_t) b * k.words);
+    return km_distance(k.metric, k.dim, k.centers + (size_t) a * k.dim, k.centers + (size_t) b * k.dim);
+}
+__device__ __forceinline__ double km_moved_distance(const KmState& k, int c)
+{
+    if (k.bits) return km_bit_distance(k.words, k.bcenters + (size_t) c * k.words, k.bnewc + (size_t) c * k.words);
+    return km_distance(k.metric, k.dim, k.centers + (size_t) c * k.dim, k.newc + (size_t) c * k.dim);
+}
+// sample j becomes centre c, by threads t, t + step, ...
+__device__ __forceinline__ void km_take_sample(const KmState& k, int64_t j, int c, int t, int step)
+{
+    if (k.bits)
+        for (int w = t; w < k.words; w += step) k.bcenters[(size_t) c * k.words + w] = k.bsamples[(size_t) j * k.words + w];
+    else
+        for (int d = t; d < k.dim; d += step) k.centers[(size_t) c * k.dim + d] = k.samples[(size_t) j * k.dim + d];
+}
+
 __global__ __launch_bounds__(1) void km_first_center_kernel(KmState k)
 {
     const int64_t j = (int64_t) (km_next(k.rng) % (uint64_t) k.ns);
-    for (int t = 0; t < k.dim; ++t) k.centers[t] = k.samples[(size_t) j * k.dim + t];
+    km_take_sample(k, j, 0, 0, 1);
 }
 
 // k-means++: distances of every sample to centre i, running minimum of their squares (ivfkmeans.c:45-63)
@@ -108,7 +160,7 @@ __global__ __launch_bounds__(256) void km_seed_sweep_kernel(KmState k, int i)
 {
     const int64_t j = (int64_t) blockIdx.x * 256 + threadIdx.x;
     if (j >= k.ns) return;
-    double d = km_distance(k.metric, k.dim, k.samples + (size_t) j * k.dim, k.centers + (size_t) i * k.dim);
+    double d = km_sample_distance(k, j, i);
     k.lower[(size_t) i * k.ns + j] = (float) d;
     d *= d;
     if (i == 0) k.weight[j] = FLT_MAX;
@@ -159,7 +211,7 @@ __global__ __launch_bounds__(KM_PICK_THREADS) void km_seed_pick_kernel(KmState k
     __syncthreads();
     long long j = s_pick;
     if (j < 0 || j > k.ns - 1) j = k.ns - 1;                 // the reference's loop stops at ns - 1 whatever is left of choice
-    for (int d = t; d < k.dim; d += KM_PICK_THREADS) k.centers[(size_t) (i + 1) * k.dim + d] = k.samples[(size_t) j * k.dim + d];
+    km_take_sample(k, j, i + 1, t, KM_PICK_THREADS);
 }
 
 __global__ __launch_bounds__(256) void km_init_assign_kernel(KmState k)      // ivfkmeans.c:325-345
@@ -180,7 +232,7 @@ __global__ __launch_bounds__(256) void km_half_kernel(KmState k)             // 
     if (i >= (int64_t) k.nc * k.nc) return;
     const int a = (int) (i / k.nc), b = (int) (i % k.nc);
     if (a >= b) return;
-    const float d = (float) (0.5 * km_distance(k.metric, k.dim, k.centers + (size_t) a * k.dim, k.centers + (size_t) b * k.dim));
+    const float d = (float) (0.5 * km_center_distance(k, a, b));
     k.half[(size_t) a * k.nc + b] = d;
     k.half[(size_t) b * k.nc + a] = d;
 }
@@ -201,7 +253,6 @@ __global__ __launch_bounds__(256) void km_assign_kernel(KmState k, int rjreset)
 {
     const int64_t j = (int64_t) blockIdx.x * 256 + threadIdx.x;
     if (j >= k.ns) return;
-    const float* x = k.samples + (size_t) j * k.dim;
     float* lo = k.lower + j;                                  // lo[c * ns]: this sample's bound on centre c
     const size_t ls = (size_t) k.ns;
     float up = k.upper[j];
@@ -215,14 +266,14 @@ __global__ __launch_bounds__(256) void km_assign_kernel(KmState k, int rjreset)
             if (up <= lo[c * ls]) continue;
             if (up <= k.half[(size_t) cl * k.nc + c]) continue;
             if (rj) {
-                dxcx = (float) km_distance(k.metric, k.dim, x, k.centers + (size_t) cl * k.dim);
+                dxcx = (float) km_sample_distance(k, j, cl);
                 lo[cl * ls] = dxcx;
                 up = dxcx;
                 rj = 0;
             } else
                 dxcx = up;
             if (dxcx > lo[c * ls] || dxcx > k.half[(size_t) cl * k.nc + c]) {
-                const float dxc = (float) km_distance(k.metric, k.dim, x, k.centers + (size_t) c * k.dim);
+                const float dxc = (float) km_sample_distance(k, j, c);
                 lo[c * ls] = dxc;
                 if (dxc < dxcx) {
                     cl = c;
@@ -288,6 +339,54 @@ __global__ __launch_bounds__(256) void km_sum_kernel(KmState k)
     k.newc[i] = sum;
 }
 
+// BitSumCenter + ComputeNewCenters' division + BitUpdateCenter for one 32-bit word of one centre: the members' bits counted per
+// position (the reference's fp32 sum of ones, an integer below 2^24), then bit i of the new centre = x[i] > 0.5 with
+// x[i] = (float) count / (float) n.  Pad positions stay clear; an empty centre's word is zero until km_fix_centers_bit_kernel.
+__global__ __launch_bounds__(256) void km_sum_bit_kernel(KmState k)
+{
+    const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t) k.nc * k.words) return;
+    const int c = (int) (i / k.words), w = (int) (i % k.words);
+    const int n = k.counts[c];
+    const int* members = k.order_val + k.starts[c];
+    uint32_t count[32];
+#pragma unroll
+    for (int b = 0; b < 32; ++b) count[b] = 0u;
+    for (int m = 0; m < n; ++m) {
+        const uint32_t x = k.bsamples[(size_t) members[m] * k.words + w];
+#pragma unroll
+        for (int b = 0; b < 32; ++b) count[b] += (x >> b) & 1u;
+    }
+    uint32_t out = 0u;
+    if (n > 0) {
+#pragma unroll
+        for (int b = 0; b < 32; ++b) {
+            const int e = w * 32 + 8 * (b >> 3) + 7 - (b & 7);                  // the element bit b of this word holds
+            if (e < k.dim && __fdiv_rn((float) count[b], (float) n) > 0.5f) out |= 1u << b;
+        }
+    }
+    k.bnewc[i] = out;
+}
+
+// an empty centre: x[i] = RandomDouble() stored as fp32, in (centre, element) order from the serial stream, then the same > 0.5
+__device__ inline void km_random_bits(const KmState& k, uint32_t* center)
+{
+    for (int w = 0; w < k.words; ++w) center[w] = 0u;
+    for (int e = 0; e < k.dim; ++e)
+        if ((float) km_double(k.rng) > 0.5f) center[e >> 5] |= km_bit_of_element(e);
+}
+
+__global__ __launch_bounds__(1) void km_fix_centers_bit_kernel(KmState k)
+{
+    for (int c = 0; c < k.nc; ++c)
+        if (k.counts[c] == 0) km_random_bits(k, k.bnewc + (size_t) c * k.words);
+}
+
+__global__ __launch_bounds__(1) void km_random_centers_bit_kernel(KmState k)   // RandomCenters over bits
+{
+    for (int c = 0; c < k.nc; ++c) km_random_bits(k, k.bcenters + (size_t) c * k.words);
+}
+
 // empty centres get random values, in centre order (the stream is serial); spherical variant: centres normalised
 __global__ __launch_bounds__(1) void km_fix_centers_kernel(KmState k)
 {
@@ -303,7 +402,7 @@ __global__ __launch_bounds__(256) void km_newcdist_kernel(KmState k)         // 
 {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= k.nc) return;
-    k.newcdist[c] = (float) km_distance(k.metric, k.dim, k.centers + (size_t) c * k.dim, k.newc + (size_t) c * k.dim);
+    k.newcdist[c] = (float) km_moved_distance(k, c);
 }
 
 __global__ __launch_bounds__(256) void km_bounds_kernel(KmState k)           // ivfkmeans.c:464-487
@@ -352,17 +451,20 @@ using namespace vsr;
 int vsr_kmeans_fail(const char* what, const char* why, bool oom);     // vsr_runtime.hip: sets vsr_last_error
 int vsr_ctx_device(const vsr_ctx* ctx, hipStream_t* stream);          // vsr_runtime.hip
 
-// vsr_ivf_kmeans (samples and out_centers fp32) and vsr_ivf_kmeans_half (round_half: both binary16 bit patterns)
+// vsr_ivf_kmeans (samples and out_centers fp32), vsr_ivf_kmeans_half (round_half: both binary16 bit patterns) and
+// vsr_ivf_kmeans_bit (bits: both packed bit strings of ceil(dim / 8) bytes, dim up to 64000; metric is not read)
 static int km_run(vsr_ctx* ctx, int metric, int dim, const void* samples, int64_t n_samples, int lists, uint64_t seed, void* out_centers,
-                  int* out_iterations, bool round_half, const char* who)
+                  int* out_iterations, bool round_half, const char* who, bool bits = false)
 {
     int rc = VSR_OK;
     hipStream_t st = nullptr;
     if (!ctx || !out_centers || n_samples < 0 || (n_samples > 0 && !samples))
         return vsr_kmeans_fail(who, "NULL argument", false), VSR_ERR_INVALID;
-    if (dim < 1 || dim > 16000 || lists < 1 || lists > 32768)      /* IVFFLAT_MAX_LISTS, ivfflat.h:44 */
+    if (bits && (dim < 1 || dim > 64000 || lists < 1 || lists > 32768))   /* IVFFLAT_MAX_DIM * 32 bits, ivfutils.c:364-377 */
+        return vsr_kmeans_fail(who, "dim must be 1..64000 bits and lists 1..32768", false), VSR_ERR_INVALID;
+    if (!bits && (dim < 1 || dim > 16000 || lists < 1 || lists > 32768))      /* IVFFLAT_MAX_LISTS, ivfflat.h:44 */
         return vsr_kmeans_fail(who, "dim must be 1..16000 and lists 1..32768", false), VSR_ERR_INVALID;
-    if (metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)
+    if (!bits && metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)
         return vsr_kmeans_fail(who, "metric has no ivfflat operator class", false), VSR_ERR_UNSUPPORTED;
     if (out_iterations) *out_iterations = 0;
     const int dev = vsr_ctx_device(ctx, &st);
@@ -375,6 +477,11 @@ static int km_run(vsr_ctx* ctx, int metric, int dim, const void* samples, int64_
     k.nc = nc;
     k.ns = ns;
     k.round_half = round_half ? 1 : 0;
+    k.bits = bits ? 1 : 0;
+    k.words = bits ? (dim + 31) / 32 : 0;
+    const size_t words = (size_t) k.words, src_bytes = ((size_t) dim + 7) / 8;
+    const size_t elem_bytes = bits ? words * 4 : (size_t) dim * 4;      // one sample / centre as the kernels hold it
+    std::vector<uint32_t> h_bits;                                       // bits: samples on their way in, centres on their way out
     void* bufs[32] = {nullptr};
     int nb = 0;
     auto alloc = [&](size_t bytes) -> void* {
@@ -387,9 +494,9 @@ static int km_run(vsr_ctx* ctx, int metric, int dim, const void* samples, int64_
     km_seed(&h_rng, seed);
     int iterations = 0;
     {
-        float* d_samples = (float*) alloc((size_t) ns * dim * 4);
-        k.centers = (float*) alloc((size_t) nc * dim * 4);
-        k.newc = (float*) alloc((size_t) nc * dim * 4);
+        float* d_samples = (float*) alloc((size_t) ns * elem_bytes);
+        k.centers = (float*) alloc((size_t) nc * elem_bytes);
+        k.newc = (float*) alloc((size_t) nc * elem_bytes);
         k.lower = (float*) alloc((size_t) ns * nc * 4);
         k.upper = (float*) alloc((size_t) ns * 4);
         k.weight = (float*) alloc((size_t) ns * 4);
@@ -409,6 +516,11 @@ static int km_run(vsr_ctx* ctx, int metric, int dim, const void* samples, int64_
         k.changes = (int*) alloc(16);
         k.rng = (KmRng*) alloc(16);
         k.samples = d_samples;
+        if (bits) {                                                     // the same three buffers, read as packed words
+            k.bsamples = reinterpret_cast<const uint32_t*>(d_samples);
+            k.bcenters = reinterpret_cast<uint32_t*>(k.centers);
+            k.bnewc = reinterpret_cast<uint32_t*>(k.newc);
+        }
         // the binary16 side of the half form: the samples as uploaded, later the centres on their way out (whichever is larger)
         _Float16* d_h16 = round_half ? (_Float16*) alloc((size_t) std::max<int64_t>(ns, nc) * dim * 2) : nullptr;
         if ((round_half && !d_h16) || !d_samples || !k.centers || !k.newc || !k.lower || !k.upper || !k.weight || !k.s || !k.half || !k.newcdist || !k.counts ||
@@ -418,9 +530,19 @@ static int km_run(vsr_ctx* ctx, int metric, int dim, const void* samples, int64_
         }
         KM_HIP(hipMemcpyAsync(k.rng, &h_rng, sizeof h_rng, hipMemcpyHostToDevice, st));
         if (ns == 0) {
-            hipLaunchKernelGGL(km_random_centers_kernel, dim3(1), dim3(64), 0, st, k);
+            if (bits) hipLaunchKernelGGL(km_random_centers_bit_kernel, dim3(1), dim3(1), 0, st, k);
+            else hipLaunchKernelGGL(km_random_centers_kernel, dim3(1), dim3(64), 0, st, k);
         } else {
-            if (round_half) {
+            if (bits) {                                                 // whole words per sample, pad bits clear
+                h_bits.assign((size_t) ns * words, 0u);
+                const uint8_t last = (dim & 7) ? (uint8_t) (0xFF00u >> (dim & 7)) : (uint8_t) 0xFF;
+                for (int64_t j = 0; j < ns; ++j) {
+                    uint8_t* dst = reinterpret_cast<uint8_t*>(h_bits.data() + (size_t) j * words);
+                    memcpy(dst, static_cast<const uint8_t*>(samples) + (size_t) j * src_bytes, src_bytes);
+                    dst[src_bytes - 1] &= last;
+                }
+                KM_HIP(hipMemcpyAsync(d_samples, h_bits.data(), (size_t) ns * words * 4, hipMemcpyHostToDevice, st));
+            } else if (round_half) {
                 KM_HIP(hipMemcpyAsync(d_h16, samples, (size_t) ns * dim * 2, hipMemcpyHostToDevice, st));
                 hipLaunchKernelGGL(km_widen_kernel, dim3((unsigned) ((ns * dim + 255) / 256)), dim3(256), 0, st, d_h16, d_samples, ns * dim);
             } else
@@ -444,11 +566,16 @@ static int km_run(vsr_ctx* ctx, int metric, int dim, const void* samples, int64_
                     KM_HIP(hipcub::DeviceRadixSort::SortPairs(d_sort_tmp, sb, (const int*) k.closest, k.closest_sorted,
                                                               (const int*) k.order_val_in, k.order_val, (int) ns, 0, 16, st));
                 }
-                hipLaunchKernelGGL(km_sum_kernel, dim3((unsigned) (((int64_t) nc * dim + 255) / 256)), dim3(256), 0, st, k);
-                hipLaunchKernelGGL(km_fix_centers_kernel, dim3(1), dim3(1), 0, st, k);
+                if (bits) {
+                    hipLaunchKernelGGL(km_sum_bit_kernel, dim3((unsigned) (((int64_t) nc * k.words + 255) / 256)), dim3(256), 0, st, k);
+                    hipLaunchKernelGGL(km_fix_centers_bit_kernel, dim3(1), dim3(1), 0, st, k);
+                } else {
+                    hipLaunchKernelGGL(km_sum_kernel, dim3((unsigned) (((int64_t) nc * dim + 255) / 256)), dim3(256), 0, st, k);
+                    hipLaunchKernelGGL(km_fix_centers_kernel, dim3(1), dim3(1), 0, st, k);
+                }
                 hipLaunchKernelGGL(km_newcdist_kernel, dim3(gc), dim3(256), 0, st, k);
                 hipLaunchKernelGGL(km_bounds_kernel, dim3(gs), dim3(256), 0, st, k);
-                KM_HIP(hipMemcpyAsync(k.centers, k.newc, (size_t) nc * dim * 4, hipMemcpyDeviceToDevice, st));
+                KM_HIP(hipMemcpyAsync(k.centers, k.newc, (size_t) nc * elem_bytes, hipMemcpyDeviceToDevice, st));
                 int changes = 0;
                 KM_HIP(hipMemcpyAsync(&changes, k.changes, sizeof changes, hipMemcpyDeviceToHost, st));
                 KM_HIP(hipStreamSynchronize(st));
@@ -457,7 +584,13 @@ static int km_run(vsr_ctx* ctx, int metric, int dim, const void* samples, int64_
             }
         }
         KM_HIP(hipGetLastError());
-        if (round_half) {
+        if (bits) {
+            h_bits.assign((size_t) nc * words, 0u);
+            KM_HIP(hipMemcpyAsync(h_bits.data(), k.centers, (size_t) nc * words * 4, hipMemcpyDeviceToHost, st));
+            KM_HIP(hipStreamSynchronize(st));
+            for (int c = 0; c < nc; ++c)
+                memcpy(static_cast<uint8_t*>(out_centers) + (size_t) c * src_bytes, h_bits.data() + (size_t) c * words, src_bytes);
+        } else if (round_half) {
             hipLaunchKernelGGL(km_narrow_kernel, dim3((unsigned) (((int64_t) nc * dim + 255) / 256)), dim3(256), 0, st, k.centers, d_h16,
                                (int64_t) nc * dim);
             KM_HIP(hipGetLastError());
@@ -485,4 +618,13 @@ extern "C" int vsr_ivf_kmeans_half(vsr_ctx* ctx, int metric, int dim, const uint
                                    uint16_t* out_centers, int* out_iterations)
 {
     return km_run(ctx, metric, dim, samples, n_samples, lists, seed, out_centers, out_iterations, true, "vsr_ivf_kmeans_half");
+}
+
+// CREATE INDEX ... USING ivfflat (col bit_hamming_ops), step 1 (K3b): samples and centres are packed bit strings in varbit order,
+// ceil(dim_bits / 8) bytes each; pad bits are ignored on the way in and clear on the way out.
+extern "C" int vsr_ivf_kmeans_bit(vsr_ctx* ctx, int dim_bits, const uint8_t* samples, int64_t n_samples, int lists, uint64_t seed,
+                                  uint8_t* out_centers, int* out_iterations)
+{
+    return km_run(ctx, VSR_METRIC_HAMMING, dim_bits, samples, n_samples, lists, seed, out_centers, out_iterations, false,
+                  "vsr_ivf_kmeans_bit", true);
 }

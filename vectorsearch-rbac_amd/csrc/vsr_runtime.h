@@ -428,6 +428,9 @@ int    check_sparse_rows(const char* who, const int64_t* indptr, const int32_t* 
 // queries: format_query_bytes(c->format, dim) bytes each
 int    host_search(vsr_corpus* c, const void* queries, int nq, int dim, int k, int metric, const vsr_filter* const* filters,
                    const Outputs& out);
+// the same with queries and results on the device, enqueued and not waited for; a bit corpus or a view of one: nothing flags
+int    device_search(vsr_corpus* c, const void* d_queries, int nq, int dim, int k, int metric, const vsr_filter* const* filters,
+                     const Outputs& out);
 // the two-stage searches (vsr_search_quantized*, and vsr_hnsw_search_quantized* in vsr_hnsw_rt.hip): the argument checks they share
 // (session may be nullptr) and stage 2, the exact re-rank of stage-1 keys on the source rows
 int    check_quantized_args(const vsr_ctx* session, const vsr_corpus* src, const vsr_corpus* bits, const void* queries, int nq,

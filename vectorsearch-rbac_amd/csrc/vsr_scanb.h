@@ -17,8 +17,13 @@
 // in fp32, rounding a Jaccard value is monotone.  Nothing is screened: every result is exact by construction.
 // No matrix cores: CDNA4 has no 1-bit MFMA.
 // Not carried over from scan_kernel (this is a second kernel body: a fix to K1's top-k or overflow protocol belongs in both):
-// p.tau_init (no seeded thresholds), p.sample_stride (no sample pass), p.rank (no list-ordered views) and p.fused (the
-// one-query in-kernel merge, FusedTail, is not instantiated here).
+// p.tau_init (no seeded thresholds), p.sample_stride (no sample pass) and p.fused (the one-query in-kernel merge, FusedTail, is
+// not instantiated here).  p.rank IS carried, by the VIEW instantiations (K3b, the list-ordered view of an IVFFlat index over a bit
+// corpus): a finished row's key holds p.rank[view row], the base row, on both the compile-time-chunk and the runtime-chunk path --
+// read for permitted rows only, so never past the view -- and the view's p.norm2 holds the popcounts gathered with the rows.
+// VIEW is a template argument, not a test of p.rank in the kernel: the runtime test cost the 1000-query RBAC leg of
+// tools/bit_probe.py 3.5 - 4 % (profiles/ivf_bit.json), outside the parent kernel's own spread, so a corpus scanned directly
+// (p.rank == nullptr) runs the kernel it ran before.  Only Hamming has VIEW instantiations: ivfflat has no Jaccard opclass.
 #pragma once
 #include "vsr_scan.h"
 #include "vsr_bitops.h"
@@ -49,7 +54,7 @@ __device__ __forceinline__ void reduce_slots_u32(uint32_t* p, int lane)
 }
 
 // C > 0: compile-time chunk count.  C == 0: runtime chunk loop (rows of more than 128 chunks; LPR = 64, qmax <= QI).
-template <bool JACCARD, int LPR, int C, int R, int QI>
+template <bool JACCARD, int LPR, int C, int R, int QI, bool VIEW = false>
 __global__ __launch_bounds__(SCAN_THREADS, VSR_MINWAVES) void scanb_kernel(const ScanParams p)
 {
     using S = ScanShape<LPR, R>;
@@ -72,6 +77,7 @@ __global__ __launch_bounds__(SCAN_THREADS, VSR_MINWAVES) void scanb_kernel(const
     const ScanGroup grp = p.groups[lo];
     const auto g_tiles = as_global(grp.tiles);
     const auto g_bitmap = as_global(grp.bitmap);
+    const auto g_rank = as_global(p.rank);                                     // VIEW: keys carry the base row
     const uint32_t local_block = blockIdx.x - grp.block_begin;
     const uint32_t t0 = (uint32_t) (((uint64_t) grp.n_tiles * local_block) / grp.n_blocks);
     const uint32_t t1 = (uint32_t) (((uint64_t) grp.n_tiles * (local_block + 1)) / grp.n_blocks);
@@ -176,7 +182,9 @@ __global__ __launch_bounds__(SCAN_THREADS, VSR_MINWAVES) void scanb_kernel(const
                         reduce_slots_u32<LPR / 2, R>(acc[qi], lane);
                         const bool live = own && ok_own && qs < q_count;
                         const float v = live ? rank_value_bits<JACCARD>(acc[qi][0], cur.rn, qnl[qs]) : 0.0f;   // the division: permitted pairs only
-                        const uint64_t key = make_key(v, start + row_own);
+                        uint32_t key_row = start + row_own;
+                        if constexpr (VIEW) key_row = live ? g_rank[key_row] : key_row;
+                        const uint64_t key = make_key(v, key_row);
                         const uint64_t tau = lds_peek(&ctrl[qs].tau);
                         topk_append(keys + (size_t) qs * cap, &ctrl[qs], live && key < tau, key);
                     }
@@ -209,7 +217,9 @@ __global__ __launch_bounds__(SCAN_THREADS, VSR_MINWAVES) void scanb_kernel(const
                     reduce_slots_u32<LPR / 2, R>(acc[qi], lane);
                     const bool live = own && ok_own && (uint32_t) qi < q_count;
                     const float v = live ? rank_value_bits<JACCARD>(acc[qi][0], cur.rn, qnl[qi]) : 0.0f;
-                    const uint64_t key = make_key(v, start + row_own);
+                    uint32_t key_row = start + row_own;
+                    if constexpr (VIEW) key_row = live ? g_rank[key_row] : key_row;
+                    const uint64_t key = make_key(v, key_row);
                     const uint64_t tau = lds_peek(&ctrl[qi].tau);
                     topk_append(keys + (size_t) qi * cap, &ctrl[qi], live && key < tau, key);
                 }
@@ -245,11 +255,11 @@ __global__ __launch_bounds__(SCAN_THREADS, VSR_MINWAVES) void scanb_kernel(const
     }
 }
 
-template <bool JACCARD, int LPR, int C, int R, int QI>
+template <bool JACCARD, int LPR, int C, int R, int QI, bool VIEW = false>
 hipError_t launch_scanb_inst(const ScanParams& p, uint32_t n_blocks, hipStream_t s)
 {
     const size_t lds = scan_lds_bytes(p.qmax, p.cap, p.stride4);
-    auto kern = scanb_kernel<JACCARD, LPR, C, R, QI>;
+    auto kern = scanb_kernel<JACCARD, LPR, C, R, QI, VIEW>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         if (e != hipSuccess) return e;
@@ -263,8 +273,14 @@ template <bool JACCARD>
 hipError_t launch_scanb_metric(const ScanParams& p, int dim, int qi, uint32_t n_blocks, hipStream_t s)
 {
     const KernelShape sh = scan_shape(RowFormat::BIT, dim);
+    const bool view = p.rank != nullptr;                   // a list-ordered view (K3b): the VIEW instantiations, Hamming only
+    if (view && JACCARD) return hipErrorInvalidValue;
 #define VSR_CASE(LPR_, C_, R_)                                                             \
     if (sh.lpr == LPR_ && sh.c == C_) {                                                    \
+        if constexpr (!JACCARD) {                                                          \
+            if (view && qi == 1) return launch_scanb_inst<false, LPR_, C_, R_, 1, true>(p, n_blocks, s);   \
+            if (view && qi == 4) return launch_scanb_inst<false, LPR_, C_, R_, 4, true>(p, n_blocks, s);   \
+        }                                                                                  \
         if (qi == 1) return launch_scanb_inst<JACCARD, LPR_, C_, R_, 1>(p, n_blocks, s);   \
         if (qi == 4) return launch_scanb_inst<JACCARD, LPR_, C_, R_, 4>(p, n_blocks, s);   \
         return hipErrorInvalidValue;                                                       \

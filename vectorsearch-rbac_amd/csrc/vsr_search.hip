@@ -806,6 +806,24 @@ extern "C" int vsr_search_device(vsr_corpus* c, const float* d_queries, int nq, 
                                 d_keys);
 }
 
+// The search of vsr_search_bit_device over a corpus or a list-ordered view of one (vsr_ivf_search_bit_device, K3b), arguments
+// already checked by the caller: enqueued on the corpus context's stream, not waited for.  Bit corpora only: K1b is exact by
+// construction, so there is nothing to flag or re-run (fp32 / halfvec views: vsr_search_device_exact).
+int vsr::device_search(vsr_corpus* c, const void* d_queries, int nq, int dim, int k, int metric, const vsr_filter* const* filters,
+                       const Outputs& out)
+{
+    vsr_ctx* ctx = c->ctx;
+    if (nq == 0) return VSR_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    Outputs o = out;
+    if (!o.doc) {
+        int rc = ctx->d_misc.reserve((size_t) nq * k * sizeof(int32_t));
+        if (rc) return rc;
+        o.doc = ctx->d_misc.as<int32_t>();
+    }
+    return search_impl(ctx, c, {nullptr, d_queries, nq, dim, k, metric, o}, filters, 2);
+}
+
 // The device API for callers that cannot tolerate an unproven row: search, wait, re-run what was flagged, patch.
 extern "C" int vsr_search_device_exact(vsr_ctx* session, vsr_corpus* c, const float* d_queries, int nq, int dim, int k,
                                        int metric, const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc,

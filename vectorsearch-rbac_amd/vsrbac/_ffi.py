@@ -90,6 +90,14 @@ SYMBOLS = {
     "vsr_ivf_load_half": (_i, [_vp, _vp, _i, _vp, C.POINTER(_vp)]),
     "vsr_ivf_assign_half": (_i, [_vp, _vp, _i, _i, _vp]),
     "vsr_ivf_kmeans_half": (_i, [_vp, _i, _i, _vp, _i64, _i, C.c_uint64, _vp, C.POINTER(_i)]),
+    "vsr_ivf_kmeans_bit": (_i, [_vp, _i, _vp, _i64, _i, C.c_uint64, _vp, C.POINTER(_i)]),
+    "vsr_ivf_assign_bit": (_i, [_vp, _vp, _i, _vp]),
+    "vsr_ivf_load_bit": (_i, [_vp, _vp, _i, _vp, C.POINTER(_vp)]),
+    "vsr_ivf_probe_bit": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "vsr_ivf_search_bit": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_ivf_search_bit_device": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_ivf_search_bit_iterative": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_ivf_search_bit_iterative_device": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_hnsw_load": (_i, [_vp, _i, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(_vp)]),
     "vsr_hnsw_free": (_i, [_vp]),
     "vsr_hnsw_search": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

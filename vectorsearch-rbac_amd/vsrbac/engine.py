@@ -302,6 +302,17 @@ class Context:
                                             _ptr(out), C.byref(it)))
         return out, it.value
 
+    def ivf_kmeans_bit(self, samples, lists, dim=None, seed=1):
+        """ivf_kmeans for bit_hamming_ops (vsr_ivf_kmeans_bit): `samples` bool [n, dim] or packed uint8 [n, (dim + 7) // 8] with
+        `dim`; the distance is the Hamming count and the centres are bit strings (bit i set where more than half of a centre's
+        members have it).  Returns (centers packed uint8 [lists, (dim + 7) // 8], iterations)."""
+        s, dim = _packed_bits(samples, dim, "ivf_kmeans_bit")
+        out = np.zeros((int(lists), (dim + 7) // 8), dtype=np.uint8)
+        it = C.c_int(0)
+        check(self._lib.vsr_ivf_kmeans_bit(self._h, dim, _ptr(s), s.shape[0], int(lists), C.c_uint64(int(seed)), _ptr(out),
+                                           C.byref(it)))
+        return out, it.value
+
     def merge_topk_device(self, keys, block_ids, doc_ids, dist, n_parts, nq, k, out_block, out_doc, out_dist,
                           out_keys, out_counts):
         """Device pointers (ints).  Layout [n_parts][nq][k]."""
@@ -501,6 +512,25 @@ class Corpus:
         centers, _ = self.ctx.ivf_kmeans_half(rows[pick], lists, metric, seed)
         row_list = self.ivf_assign_half(centers, metric)
         return IvfIndex(self, centers, row_list, half=True), centers, row_list
+
+    def load_ivf_bit(self, centers, row_list):
+        """load_ivf over this bit corpus (vsr_ivf_load_bit, bit_hamming_ops): centres bool [lists, dim] or packed uint8
+        [lists, (dim + 7) // 8]; image and centres stay packed on the device.  The index answers IvfIndex.probe_bit /
+        search_bit*."""
+        return IvfIndex(self, centers, row_list, bit=True)
+
+    def build_ivf_bit(self, rows, lists=100, seed=1, sample=None):
+        """CREATE INDEX ... USING ivfflat (col bit_hamming_ops) over this bit corpus: build_ivf's sampling rule on `rows` (this
+        corpus's rows in the caller's order, bool or packed uint8), vsr_ivf_kmeans_bit, vsr_ivf_assign_bit, vsr_ivf_load_bit.
+        Returns (IvfIndex, centers packed uint8, row_list)."""
+        rows, dim = _packed_bits(rows, self.dim, "build_ivf_bit")
+        n = rows.shape[0]
+        want = max(int(lists) * 50, 10000) if sample is None else int(sample)
+        rng = np.random.default_rng(seed)
+        pick = np.sort(rng.choice(n, size=min(n, want), replace=False)) if n else np.zeros(0, dtype=np.int64)
+        centers, _ = self.ctx.ivf_kmeans_bit(rows[pick], lists, dim, seed)
+        row_list = self.ivf_assign_bit(centers)
+        return IvfIndex(self, centers, row_list, bit=True), centers, row_list
 
     def build_hnsw(self, m=16, ef_construction=64, metric="l2", seed=1, merge_duplicates=False):
         """CREATE INDEX ... USING hnsw on the GPU (vsr_hnsw_build): batched insertion, recall parity with the serial build.
@@ -727,6 +757,13 @@ class Corpus:
         check(self._lib.vsr_ivf_assign_half(self._h, _ptr(c), int(c.shape[0]), _metric(metric), _ptr(out)))
         return out
 
+    def ivf_assign_bit(self, centers):
+        """ivf_assign over this bit corpus (vsr_ivf_assign_bit): the centre of the lowest (Hamming count, list id) for each row."""
+        c, _ = _packed_bits(centers, self.dim, "ivf_assign_bit")
+        out = np.zeros(self.n, dtype=np.int32)
+        check(self._lib.vsr_ivf_assign_bit(self._h, _ptr(c), int(c.shape[0]), _ptr(out)))
+        return out
+
     def search_device_exact(self, d_queries, nq, k, metric, filters, d_block, d_doc, d_rows, d_dist, d_counts, d_keys=None,
                             dim=None, session=None):
         """search_device + wait + exact re-run of whatever the screening flagged (vsr_search_device_exact): returns the
@@ -743,14 +780,19 @@ class Corpus:
 class IvfIndex:
     """pgvector's ivfflat scan (ivfscan.c) on the GPU: probe the nearest lists, scan them, keep the permitted top-k."""
 
-    def __init__(self, corpus, centers, row_list, half=False):
+    def __init__(self, corpus, centers, row_list, half=False, bit=False):
         self.corpus, self._lib = corpus, corpus._lib
-        c = np.ascontiguousarray(_as_f16(centers, "centers")) if half else np.ascontiguousarray(centers, dtype=np.float32)
         rl = np.ascontiguousarray(row_list, dtype=np.int32)
-        if c.ndim != 2 or c.shape[1] != corpus.dim or rl.size != corpus.n:
-            raise ValueError("centers must be [lists, dim] and row_list must have one entry per row")
+        if bit:                                                                     # (Corpus.load_ivf_bit)
+            c, _ = _packed_bits(centers, corpus.dim, "centers")
+            if rl.size != corpus.n:
+                raise ValueError("row_list must have one entry per row")
+        else:
+            c = np.ascontiguousarray(_as_f16(centers, "centers")) if half else np.ascontiguousarray(centers, dtype=np.float32)
+            if c.ndim != 2 or c.shape[1] != corpus.dim or rl.size != corpus.n:
+                raise ValueError("centers must be [lists, dim] and row_list must have one entry per row")
         h = C.c_void_p()
-        load = self._lib.vsr_ivf_load_half if half else self._lib.vsr_ivf_load     # (half: Corpus.load_ivf_half)
+        load = self._lib.vsr_ivf_load_bit if bit else self._lib.vsr_ivf_load_half if half else self._lib.vsr_ivf_load   # (half: Corpus.load_ivf_half)
         check(load(corpus._h, _ptr(c), c.shape[0], _ptr(rl), C.byref(h)))
         self._h, self.lists = h, c.shape[0]
 
@@ -829,6 +871,65 @@ class IvfIndex:
                                                  _ptr(dist), _ptr(cnt), _ptr(scanned)))
         del keep
         return SearchResult(blk, doc, row, dist, cnt), scanned
+
+    # ---- an index over a bit corpus (Corpus.load_ivf_bit / build_ivf_bit, bit_hamming_ops) ----
+    def probe_bit(self, queries, probes, dim=None):
+        """IvfIndex.probe for a bit index (vsr_ivf_probe_bit): `queries` bool [nq, dim] or packed uint8 [nq, (dim + 7) // 8]; the
+        lists in (Hamming count to the centre, list id) order."""
+        q, qdim = _packed_bits(queries, self.corpus.dim if dim is None else dim, "probe_bit")
+        p = min(int(probes), self.lists)
+        out = np.zeros((q.shape[0], p), dtype=np.int32)
+        check(self._lib.vsr_ivf_probe_bit(self._h, _ptr(q), q.shape[0], qdim, int(probes), _ptr(out)))
+        return out
+
+    def _results(self, nq, k):
+        kk = max(int(k), 1)
+        return (np.full((nq, kk), -1, dtype=np.int64), np.full((nq, kk), -1, dtype=np.int32), np.full((nq, kk), -1, dtype=np.int64),
+                np.full((nq, kk), np.inf, dtype=np.float32), np.zeros(nq, dtype=np.int32))
+
+    def search_bit(self, queries, k, probes, metric="hamming", filters=None, dim=None):
+        """IvfIndex.search for a bit index (vsr_ivf_search_bit): queries as in probe_bit, metric "hamming" / "<~>"; rows rank as
+        Corpus.search_bit ranks them."""
+        q, qdim = _packed_bits(queries, self.corpus.dim if dim is None else dim, "search_bit")
+        nq = q.shape[0]
+        farr, keep = self.corpus._filter_array(filters, nq)
+        blk, doc, row, dist, cnt = self._results(nq, k)
+        check(self._lib.vsr_ivf_search_bit(self._h, _ptr(q), nq, qdim, int(k), int(probes), _metric(metric), farr, _ptr(blk),
+                                           _ptr(doc), _ptr(row), _ptr(dist), _ptr(cnt)))
+        del keep
+        return SearchResult(blk, doc, row, dist, cnt)
+
+    def search_bit_device(self, d_queries, nq, k, probes, metric, filters, d_block, d_doc, d_rows, d_dist, d_counts, dim=None):
+        """search_device for a bit index (vsr_ivf_search_bit_device): d_queries addresses nq x (dim + 7) // 8 packed bytes, any
+        alignment; returns when the results are complete."""
+        farr, keep = self.corpus._filter_array(filters, nq)
+        check(self._lib.vsr_ivf_search_bit_device(self._h, d_queries, nq, self.corpus.dim if dim is None else dim, int(k),
+                                                  int(probes), _metric(metric), farr, d_block, d_doc, d_rows, d_dist, d_counts))
+        del keep
+
+    def search_bit_iterative(self, queries, k, probes, metric="hamming", filters=None, mode="relaxed_order", max_probes=32768,
+                             dim=None):
+        """search_iterative for a bit index (vsr_ivf_search_bit_iterative): SearchResult and the lists each scan had taken."""
+        q, qdim = _packed_bits(queries, self.corpus.dim if dim is None else dim, "search_bit_iterative")
+        nq = q.shape[0]
+        farr, keep = self.corpus._filter_array(filters, nq)
+        blk, doc, row, dist, cnt = self._results(nq, k)
+        scanned = np.zeros(nq, dtype=np.int32)
+        check(self._lib.vsr_ivf_search_bit_iterative(self._h, _ptr(q), nq, qdim, int(k), int(probes), _metric(metric), farr,
+                                                     _ivf_iterative_mode(mode), int(max_probes), _ptr(blk), _ptr(doc),
+                                                     _ptr(row), _ptr(dist), _ptr(cnt), _ptr(scanned)))
+        del keep
+        return SearchResult(blk, doc, row, dist, cnt), scanned
+
+    def search_bit_iterative_device(self, d_queries, nq, k, probes, metric, filters, mode, max_probes, d_block, d_doc, d_rows,
+                                    d_dist, d_counts, d_probes=None, dim=None):
+        """search_iterative_device for a bit index (vsr_ivf_search_bit_iterative_device)."""
+        farr, keep = self.corpus._filter_array(filters, nq)
+        check(self._lib.vsr_ivf_search_bit_iterative_device(self._h, d_queries, nq, self.corpus.dim if dim is None else dim,
+                                                            int(k), int(probes), _metric(metric), farr,
+                                                            _ivf_iterative_mode(mode), int(max_probes), d_block, d_doc, d_rows,
+                                                            d_dist, d_counts, d_probes))
+        del keep
 
 
 class HnswIndex:
