@@ -550,10 +550,18 @@ int vsr_hnsw_search(vsr_hnsw* index, const float* queries, int nq, int dim, int 
  * query that outgrows it reports count -1 (never a partial result): vsr_hnsw_search re-runs such queries itself. */
 /* index build (hnswbuild.c:357-470 in-memory build; hnswutils.c:1053-1346): batched insertion on the GPU over the corpus's rows
  * with m and ef_construction as the reloptions define them, levels from a seeded xorshift64* stream.  The
- * graph is not the serial build's graph -- neither is the reference's own parallel build's -- the guarantee is recall
- * (pgvector's test/t/012_hnsw_vector_build_recall.pl thresholds; tests/test_gpu_index.py).  Identical vectors are not merged
- * into one element (hnswbuild.c:329-351) by vsr_hnsw_build: every row is its own element (vsr_hnsw_build_ex merges them).
- * Synchronises. */
+ * graph is not the serial build's graph -- neither is the reference's own parallel build's -- so against pgvector the
+ * guarantee is recall (its test/t/012_hnsw_vector_build_recall.pl thresholds; tests/test_gpu_index.py).  The build itself is
+ * deterministic: the same rows, seed, m, ef_construction and flags give the same graph, run to run -- the elements of a batch
+ * search the graph as it stood when the batch began, candidates of equal distance are ordered by element id, and a
+ * neighbour's reverse edges of one batch are applied in ascending source element.  On integer-valued rows (fp32 sums that do
+ * not depend on their order) that graph is the one a serial restatement of the batched algorithm builds, array for array
+ * (oracle/vsr_index_oracle.c: orc_hnsw_build_batched; tests/test_gpu_hnsw_build_model.py).
+ * Never a thinner graph in silence: when a layer search fills its visited table (LDS, sized from m and ef_construction) the
+ * build starts again with a table twice as large; VSR_ERR_UNSUPPORTED, naming ef_construction and m, when no larger one fits
+ * or when reverse edges had to be dropped.  The session's guard word (vsr_screening_check) is left as it was found.
+ * Identical vectors are not merged into one element (hnswbuild.c:329-351) by vsr_hnsw_build: every row is its own element
+ * (vsr_hnsw_build_ex merges them).  Synchronises. */
 int vsr_hnsw_build(vsr_corpus* corpus, int m, int ef_construction, int metric, uint64_t seed, vsr_hnsw** out);
 /* vsr_hnsw_build with flags (unknown bits: VSR_ERR_INVALID).  flags = 0 is vsr_hnsw_build: the same graph for the same seed.
  * VSR_HNSW_BUILD_MERGE_DUPLICATES folds identical rows into one element carrying up to 10 heap TIDs, as pgvector does

@@ -12,7 +12,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 L2, IP, COSINE, L1 = 0, 1, 2, 3
-METRICS = {"l2": L2, "ip": IP, "cosine": COSINE, "l1": L1}
+JACCARD = 4                      # index paths only: bit_jaccard_ops over rows unpacked to 0 / 1 (HnswIndex.batched)
+METRICS = {"l2": L2, "ip": IP, "cosine": COSINE, "l1": L1, "jaccard": JACCARD}
 
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
@@ -75,6 +76,7 @@ def _bind(lib):
         "orc_ivf_assign": (None, [i, i, _f32p, i64, _f32p, i, _i32p]),
         "orc_ivf_probe": (i, [i, i, _f32p, i, _f32p, i, _i32p]),
         "orc_hnsw_build": (vp, [i, _f32p, i64, i, i, i, C.c_uint64]),
+        "orc_hnsw_build_batched": (vp, [i, _f32p, i64, i, i, i, C.c_uint64, C.c_int32, _i32p, _i32p, _i64p, i]),
         "orc_hnsw_free": (None, [vp]),
         "orc_hnsw_info": (None, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "orc_hnsw_export": (None, [vp, _i32p, _i32p, _i32p, _i64p, _i32p, _i32p, C.c_int32]),
@@ -267,9 +269,36 @@ class HnswIndex:
         self.rows = np.ascontiguousarray(rows, dtype=np.float32)
         n, dim = self.rows.shape
         self._h = oracle.lib.orc_hnsw_build(METRICS[metric], self.rows, n, dim, int(m), int(ef_construction), int(seed))
+        self._read_info()
+
+    def _read_info(self):
         a, b, c, d = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
-        oracle.lib.orc_hnsw_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+        self.orc.lib.orc_hnsw_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
         self.n_elem, self.entry, self.entry_level, self.n_upper = a.value, b.value, c.value, d.value
+
+    @classmethod
+    def batched(cls, oracle, metric, rows, m=16, ef_construction=64, seed=1, elements=None, batch_limit=0):
+        """The GPU's batched build restated serially (vsr_index_oracle.c: orc_hnsw_build_batched).  elements: None -- element e
+        is row e -- or a list of row tuples, one per element in element order (an element's vector is its first row's; the
+        merging build's canonical grouping).  metric may be "jaccard" (rows unpacked to 0 / 1; "l2" on such rows is Hamming).
+        batch_limit > 0 caps every batch (1: the serial build)."""
+        self = cls.__new__(cls)
+        self.orc, self.metric, self.m = oracle, metric, int(m)
+        self.rows = np.ascontiguousarray(rows, dtype=np.float32)
+        n, dim = self.rows.shape
+        if elements is None:
+            elements = [(r,) for r in range(n)]
+        ne = len(elements)
+        elem_row = np.array([t[0] for t in elements] + [0], dtype=np.int32)
+        tid_count = np.array([len(t) for t in elements] + [0], dtype=np.int32)
+        tids = np.full((ne + 1, 10), -1, dtype=np.int64)
+        for e, t in enumerate(elements):
+            tids[e, :len(t)] = t
+        assert tid_count[:ne].min(initial=1) >= 1 and tid_count.max(initial=1) <= 10
+        self._h = oracle.lib.orc_hnsw_build_batched(METRICS[metric], self.rows, n, dim, int(m), int(ef_construction), int(seed),
+                                                    ne, elem_row, tid_count, tids.reshape(-1), int(batch_limit))
+        self._read_info()
+        return self
 
     def __del__(self):
         try:

@@ -50,7 +50,15 @@ static double index_distance(int metric, int dim, const float *a, const float *b
     switch (metric) {
     case ORC_L2: return orc_l2_squared_distance(dim, a, b);           /* vector_l2_squared_distance */
     case ORC_L1: return orc_l1_distance(dim, a, b);
-    default:     return orc_negative_inner_product(dim, a, b);        /* ip and cosine (rows normalised by the caller) */
+    case ORC_JACCARD: {                                               /* bit_jaccard_ops on rows unpacked to 0 / 1 */
+        /* jaccard_distance, bitutils.c:96-129: ab == 0 ? 1 : 1 - ab / (double) (aa + bb - ab); the index keeps it as float4 */
+        /* 0 / 1 values: a * b is a & b and a + b - a * b is a | b; counts below 2^24 are exact in float, without a branch */
+        float ab = 0.0f, un = 0.0f;
+        for (int i = 0; i < dim; i++) { const float p = a[i] * b[i]; ab += p; un += a[i] + b[i] - p; }
+        if (ab == 0.0f) return 1.0;
+        return (double) (float) (1.0 - (double) ab / (double) un);
+    }
+    default:    return orc_negative_inner_product(dim, a, b);        /* ip and cosine (rows normalised by the caller) */
     }
 }
 /* k-means distance proc 3 (ivfflat.h IVFFLAT_KMEANS_DISTANCE_PROC): L2 for l2_ops, angular for ip / cosine */
@@ -589,6 +597,105 @@ void *orc_hnsw_build(int metric, const float *rows, int64_t n, int dim, int m, i
     hcand **sel = (hcand **) malloc(sizeof(hcand *) * (size_t) (ef_construction + 2));
     for (int64_t i = 0; i < n; i++) hnsw_insert(g, i, &rng, visited, wbuf, lw, lwp, sel);
     free(visited); free(wbuf); free(lw); free(lwp); free(sel);
+    return g;
+}
+
+/* ---- the GPU's BATCHED build restated serially (vectorsearch-rbac_amd/csrc/vsr_hnsw_build.hip, the loop of hnsw_build in
+ * vsr_hnsw_rt.hip).  Every piece is pgvector's, as above; what differs from orc_hnsw_build is the schedule:
+ *   elements   given by elem_row[n_elem] (element -> the row that holds its vector, ascending), with their heap TIDs; no
+ *              opportunistic duplicate fold.  Levels: one draw per ROW in insertion order, an element takes its first row's.
+ *   batches    max(1, min(done / 8, 4096, n_elem - done)) elements (batch_limit > 0: at most that many)
+ *   phase 1    every element of a batch runs HnswFindElementNeighbors against the graph, entry point and entry level as
+ *              they stood when the batch began, and writes its own lists in selection order
+ *   phase 2    the batch's reverse edges are HnswUpdateConnection calls, in ascending source element within a
+ *              (layer, target); different (layer, target) pairs touch different lists, so their order does not matter
+ *   entry      after the batch, HnswUpdateGraphInMemory's rule over the batch's elements in order
+ * With batch_limit = 1 and rows without duplicates this IS orc_hnsw_build (tests/test_hnsw_build_model_cpu.py). */
+void *orc_hnsw_build_batched(int metric, const float *rows, int64_t n_rows, int dim, int m, int ef_construction, uint64_t seed,
+                             int32_t n_elem, const int32_t *elem_row, const int32_t *tid_count, const int64_t *tids,
+                             int batch_limit)
+{
+    orc_hnsw *g = (orc_hnsw *) calloc(1, sizeof(orc_hnsw));
+    g->metric = metric; g->dim = dim; g->m = m; g->efc = ef_construction; g->n_rows = n_rows; g->rows = rows; g->entry = -1;
+    int cap = (8192 - 24 - 8 - 4 - 4) / 6 / m - 2;
+    g->max_level_cap = cap > 255 ? 255 : cap;
+    const size_t ne = (size_t) n_elem;
+    g->elem_row = (int32_t *) malloc(sizeof(int32_t) * (ne + 1));
+    g->elem_level = (int32_t *) malloc(sizeof(int32_t) * (ne + 1));
+    g->tid_count = (int32_t *) malloc(sizeof(int32_t) * (ne + 1));
+    g->tids = malloc(sizeof(int64_t[HNSW_HEAPTIDS]) * (ne + 1));
+    g->nbr = (hcand **) calloc(ne + 1, sizeof(hcand *));
+    g->nbr_len = (int32_t **) calloc(ne + 1, sizeof(int32_t *));
+    orc_rng rng;
+    rng_seed(&rng, seed);
+    const double ml = 1.0 / log((double) m);
+    int32_t *row_level = (int32_t *) malloc(sizeof(int32_t) * (size_t) (n_rows + 1));
+    for (int64_t r = 0; r < n_rows; r++) {
+        int level = (int) (-log(rng_double(&rng)) * ml);
+        row_level[r] = level > g->max_level_cap ? g->max_level_cap : level;
+    }
+    for (int32_t e = 0; e < n_elem; e++) {
+        g->elem_row[e] = elem_row[e];
+        g->elem_level[e] = row_level[elem_row[e]];
+        g->tid_count[e] = tid_count ? tid_count[e] : 1;
+        for (int t = 0; t < g->tid_count[e]; t++) g->tids[e][t] = tids ? tids[(size_t) e * HNSW_HEAPTIDS + t] : elem_row[e];
+        int total = 0;
+        for (int l = 0; l <= g->elem_level[e]; l++) total += layer_m(m, l);
+        g->nbr[e] = (hcand *) calloc((size_t) total, sizeof(hcand));
+        g->nbr_len[e] = (int32_t *) calloc((size_t) g->elem_level[e] + 1, sizeof(int32_t));
+    }
+    free(row_level);
+    uint8_t *visited = (uint8_t *) malloc(ne + 1);
+    scand *wbuf = (scand *) malloc(sizeof(scand) * (size_t) (ef_construction + 2));
+    scand *cur = (scand *) malloc(sizeof(scand) * (size_t) (ef_construction + 2));
+    hcand *lw = (hcand *) malloc(sizeof(hcand) * (size_t) (ef_construction + 2));
+    hcand **lwp = (hcand **) malloc(sizeof(hcand *) * (size_t) (ef_construction + 2));
+    hcand **sel = (hcand **) malloc(sizeof(hcand *) * (size_t) (ef_construction + 2));
+    for (int32_t done = 0; done < n_elem;) {
+        int32_t b = done / 8;
+        if (b > 4096) b = 4096;
+        if (b > n_elem - done) b = n_elem - done;
+        if (batch_limit > 0 && b > batch_limit) b = batch_limit;
+        if (b < 1) b = 1;
+        const int32_t entry = g->entry;
+        const int entry_level = entry >= 0 ? g->elem_level[entry] : -1;
+        g->n_elem = done;                              /* the frozen graph: what a search can reach (and clears) */
+        for (int32_t e = done; e < done + b && entry >= 0; e++) {      /* phase 1: HnswFindElementNeighbors, :1270-1346 */
+            const float *q = evec(g, e);
+            const int level = g->elem_level[e];
+            scand ep[1] = {{index_distance(metric, dim, q, evec(g, entry)), entry}};
+            const scand *epv = ep;
+            int n_ep = 1;
+            for (int lc = entry_level; lc >= level + 1; lc--) {
+                n_ep = search_layer(g, q, epv, n_ep, 1, lc, wbuf, visited, NULL);
+                memcpy(cur, wbuf, sizeof(scand) * (size_t) n_ep);
+                epv = cur;
+            }
+            if (epv != cur) memcpy(cur, epv, sizeof(scand) * (size_t) n_ep);
+            for (int lc = level < entry_level ? level : entry_level; lc >= 0; lc--) {
+                const int nw = search_layer(g, q, cur, n_ep, ef_construction, lc, wbuf, visited, NULL);
+                for (int i = 0; i < nw; i++) { lw[i].elem = wbuf[i].elem; lw[i].dist = (float) wbuf[i].dist; lwp[i] = &lw[i]; }
+                const int ns = select_neighbors(g, lwp, nw, layer_m(m, lc), sel, NULL);
+                int32_t *len;
+                hcand *nb = nbrs(g, e, lc, &len);
+                for (int i = 0; i < ns; i++) nb[(*len)++] = *sel[i];               /* AddConnections */
+                memcpy(cur, wbuf, sizeof(scand) * (size_t) nw);
+                n_ep = nw;
+            }
+        }
+        g->n_elem = done + b;
+        for (int32_t e = done; e < done + b; e++) {    /* phase 2: ascending source element */
+            for (int lc = g->elem_level[e]; lc >= 0; lc--) {
+                int32_t *len;
+                hcand *nb = nbrs(g, e, lc, &len);
+                for (int i = 0; i < *len; i++) update_connection(g, nb[i].elem, lc, e, nb[i].dist);
+            }
+            if (g->entry < 0 || g->elem_level[e] > g->elem_level[g->entry]) g->entry = e;
+        }
+        done += b;
+    }
+    g->n_elem = n_elem;
+    free(visited); free(wbuf); free(cur); free(lw); free(lwp); free(sel);
     return g;
 }
 

@@ -24,7 +24,8 @@
 extern "C" {
 #endif
 
-enum { ORC_L2 = 0, ORC_IP = 1, ORC_COSINE = 2, ORC_L1 = 3 };
+enum { ORC_L2 = 0, ORC_IP = 1, ORC_COSINE = 2, ORC_L1 = 3,
+       ORC_JACCARD = 4 };   /* index paths only (vsr_index_oracle.c): bit_jaccard_ops over rows unpacked to 0 / 1 */
 
 /* pgvector/src/vector.c:549-563 VectorL2SquaredDistance (fp32 accumulate) */
 float  orc_l2_squared(int dim, const float *a, const float *b);
@@ -116,6 +117,10 @@ int     orc_ivf_kmeans(int metric, int dim, const float *samples, int64_t ns, in
 void    orc_ivf_assign(int metric, int dim, const float *rows, int64_t n, const float *centers, int lists, int32_t *assign);
 int     orc_ivf_probe(int metric, int dim, const float *centers, int lists, const float *q, int probes, int32_t *out_lists);
 void   *orc_hnsw_build(int metric, const float *rows, int64_t n, int dim, int m, int ef_construction, uint64_t seed);
+/* the GPU's batched build restated serially; metric may be ORC_JACCARD (rows unpacked to 0 / 1) */
+void   *orc_hnsw_build_batched(int metric, const float *rows, int64_t n_rows, int dim, int m, int ef_construction, uint64_t seed,
+                               int32_t n_elem, const int32_t *elem_row, const int32_t *tid_count, const int64_t *tids,
+                               int batch_limit);
 void    orc_hnsw_free(void *h);
 void    orc_hnsw_info(const void *h, int32_t *n_elem, int32_t *entry, int32_t *entry_level, int32_t *n_upper);
 void    orc_hnsw_export(const void *h, int32_t *level, int32_t *nbr0, int32_t *tid_count, int64_t *tids, int32_t *up_slot,

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from helpers import check_graph as _check_graph, same_graph as _same_graph
 from oracle.oracle import HnswIndex as OracleHnsw
 
 pytestmark = pytest.mark.gpu
@@ -70,32 +71,6 @@ def _canonical(x):
 
 def _tid_tuples(g):
     return [tuple(int(t) for t in g["tids"][e, :g["tid_count"][e]]) for e in range(len(g["level"]))]
-
-
-def _check_lists(lists, owner, n_elem):
-    """lists [rows][width] of neighbour ids owned by owner[rows]: in range, -1 only as trailing padding, no self-loop, no
-    repeated id."""
-    assert lists.min(initial=-1) >= -1 and lists.max(initial=-1) < n_elem
-    valid = lists >= 0
-    assert (valid[:, 1:] <= valid[:, :-1]).all(), "-1 before a neighbour"
-    assert not (lists == owner[:, None]).any(), "self-loop"
-    s = np.sort(lists, axis=1)
-    assert not ((s[:, 1:] == s[:, :-1]) & (s[:, 1:] >= 0)).any(), "an id twice in one list"
-
-
-def _check_graph(g):
-    level, up_slot, up_nbr = g["level"], g["up_slot"], g["up_nbr"]
-    ne = len(level)
-    _check_lists(g["nbr0"], np.arange(ne), ne)
-    assert ((up_slot >= 0) == (level >= 1)).all()
-    upper = np.flatnonzero(up_slot >= 0)
-    assert sorted(up_slot[upper].tolist()) == list(range(len(upper)))
-    for lc in range(1, g["max_level"] + 1):
-        lists = up_nbr[up_slot[upper], lc - 1]
-        assert (lists[level[upper] < lc] == -1).all(), "an upper list above the element's level"
-        _check_lists(lists, upper, ne)
-    assert level.max() <= g["max_level"]
-    assert level[g["entry"]] == level.max()
 
 
 _EXPORTS = {}
@@ -199,16 +174,6 @@ def test_merged_build_returns_k_rows_where_the_unmerged_one_cannot(ctx, oracle):
 
 
 # ---- 3. export and load round trip ---------------------------------------------------------------------------------
-def _same_graph(a, b):
-    assert sorted(a) == sorted(b)
-    for key in a:
-        if isinstance(a[key], np.ndarray):
-            assert a[key].dtype == b[key].dtype and a[key].shape == b[key].shape, key
-            np.testing.assert_array_equal(a[key], b[key], err_msg=key)
-        else:
-            assert a[key] == b[key], key
-
-
 def test_export_of_a_loaded_graph_is_the_graph(ctx, dup4000):
     x, ref = dup4000
     want = ref.export()

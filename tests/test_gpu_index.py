@@ -7,6 +7,7 @@ distances are compared bit for bit."""
 import numpy as np
 import pytest
 
+from helpers import check_built_graph
 from oracle.oracle import HnswIndex as OracleHnsw
 from oracle.oracle import IvfIndex as OracleIvf
 
@@ -491,7 +492,8 @@ def test_ivf_kmeans_spherical_variant(ctx, oracle):
 
 # ---------------------------------------------------------------------------------------------
 # f2: HNSW build on the GPU (vsr_hnsw_build: batched insertion).  Graph identity is not reproducible even in the reference
-# (its parallel build races), so parity = recall: pgvector's own TAP case and thresholds
+# (its parallel build races), so parity WITH PGVECTOR = recall (graph identity with the serial model of the batched build:
+# tests/test_gpu_hnsw_build_model.py): pgvector's own TAP case and thresholds
 # (pgvector/test/t/012_hnsw_vector_build_recall.pl: 10 000 rows of 3-d random() * random(), 20 queries, LIMIT 20, default m,
 # ef_construction, ef_search; >= 0.99, inner product >= 0.97), and recall within 0.01 of the index oracle's serial build.
 # ---------------------------------------------------------------------------------------------
@@ -521,13 +523,15 @@ def test_hnsw_build_on_the_gpu_recall_parity_tap_case(ctx, oracle, metric, floor
     print(f"hnsw build {metric}: recall@20 GPU batched {r_gpu:.4f}, serial port {r_ref:.4f}")
     assert r_gpu >= floor, (r_gpu, r_ref)
     assert r_gpu >= r_ref - 0.01, (r_gpu, r_ref)
+    check_built_graph(gpu.export(), 16)
     gpu.free()
     corpus.free()
 
 
 def test_hnsw_build_on_the_gpu_128d(ctx, oracle):
     """SIFT-like 128-d rows: the batched build's graph answers like the serial port's at the same ef_search (recall within
-    0.02), its lists respect m / 2m, and every element but the first is reachable from layer 0 lists (no orphan lists)."""
+    0.02), and the exported graph is well formed: lists of 2m / m at most, neighbours that live on their layer, no element but
+    the first without a layer-0 neighbour, the first element of the highest level as entry point (helpers.check_built_graph)."""
     rng = np.random.default_rng(1202)
     n, dim, k = 20_000, 128, 10
     x = np.clip(np.rint(np.abs(rng.normal(0, 45, (n, dim)))), 0, 255).astype(np.float32)
@@ -542,5 +546,6 @@ def test_hnsw_build_on_the_gpu_128d(ctx, oracle):
         r_ref = _recall([ref.search(q[i], ef)[0][:k] for i in range(len(q))], exact)
         print(f"hnsw build 128-d ef={ef}: recall@10 GPU batched {r_gpu:.4f}, serial port {r_ref:.4f}")
         assert r_gpu >= r_ref - 0.02, (ef, r_gpu, r_ref)
+    check_built_graph(gpu.export(), 16)
     gpu.free()
     corpus.free()

@@ -8,6 +8,11 @@ namespace vsr {
 
 constexpr int HB_NBR = 256;                // neighbour ids of one expansion / one list (2m <= 200)
 constexpr int HB_TIDS = 10;                // heap TIDs of one element (HNSW_HEAPTIDS, hnsw.h:37)
+constexpr uint32_t HB_BATCH_MAX = 4096;    // elements of one batch
+constexpr int HB_SRC_BITS = 12;            // a reverse edge's sort key ends in its source's index in the batch (< HB_BATCH_MAX)
+constexpr int HB_KEY_BITS = 8 + 32 + HB_SRC_BITS;   // layer (<= 255) | target | source index: the bits the sort looks at
+constexpr uint32_t HB_ERR_VISITED = 16u;   // guard-word bit: a visited table filled up (hnsw_build restarts with a larger one)
+constexpr uint32_t HB_ERR_RECORDS = 32u;   // guard-word bit: reverse edges past rec_cap were dropped
 
 struct HnswBuildParams {
     const float4*  rows = nullptr;           // corpus rows (internal order), zero padded to stride4 float4
@@ -26,15 +31,15 @@ struct HnswBuildParams {
     const int32_t* elem_row = nullptr;       // element -> the row that holds its vector; nullptr: element e is row e
     int32_t        entry = -1, entry_level = -1;   // the graph's entry point when the batch begins
     uint32_t       first = 0, count = 0;     // the batch: elements first .. first + count - 1
-    uint64_t*      rec_key = nullptr;        // reverse edges: (layer << 32) | target
+    uint64_t*      rec_key = nullptr;        // reverse edges: (layer << 44) | (target << 12) | the new element's index in the batch
     uint64_t*      rec_val = nullptr;        //                (new element << 32) | distance bits
     uint32_t*      rec_count = nullptr;
-    uint32_t       rec_cap = 0;
+    uint32_t       rec_cap = 0;              // record slots of this batch: what its elements can emit at most (from their levels)
     uint32_t       caps = 0;                 // entries of the sorted candidate array (ef_construction + 2m)
     uint32_t       hash_slots = 0;           // visited set of a layer search: open-addressing table in LDS (power of two)
     uint32_t       lds_per_wave = 0;
     uint32_t       wpb = 1;                  // waves (elements) per workgroup
-    uint32_t*      err = nullptr;            // bit 16: a visited table filled up (the element keeps the candidates found so far)
+    uint32_t*      err = nullptr;            // the session's guard word: HB_ERR_VISITED / HB_ERR_RECORDS, read by hnsw_build after the last batch
 };
 
 // what the merging pre-pass (vsr_hnsw_dedup.hip) leaves: device arrays of n_elem entries, the caller's to hipFree

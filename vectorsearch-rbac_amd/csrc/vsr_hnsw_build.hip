@@ -11,9 +11,20 @@
 //
 // The GPU build inserts BATCHES: every element of a batch searches the graph as it stood when the batch began (one wave per
 // element, vsr_hnsw.h's search machinery), selects its neighbours and writes its own lists; the reverse edges of the whole
-// batch are then sorted by (layer, target) and one wave per target applies its run of HnswUpdateConnection calls one after
-// another.  Elements of one batch do not see each other, so a batch is never larger than 1/8 of the graph it is inserted
-// into (the first elements go in one by one).  Levels come from the same seeded xorshift64* stream as the test suite's serial CPU restatement
+// batch are then sorted by (layer, target, source's index in the batch) and one wave per (layer, target) applies its run of
+// HnswUpdateConnection calls one after another, in ascending source element.  Elements of one batch do not see each other, so
+// a batch is never larger than 1/8 of the graph it is inserted into (the first elements go in one by one).
+// Nothing in this depends on timing -- the record slots are claimed in wave arrival order, which is why the source index is part
+// of the sort key -- so the same rows, seed, m, ef_construction and flags give the same graph, run to run, and on integer-valued
+// rows (fp32 sums independent of their order) that graph is the one the serial restatement of THIS algorithm builds
+// (the test suite's orc_hnsw_build_batched; tests/test_gpu_hnsw_build_model.py compares the exported arrays).
+// Tie rules: where pgvector leaves an order open (equal distances in a heap) keys are (distance, element id), lower id first,
+// in S, in hb_select's input and in the full-list sort of the link kernel; where it is definite the kernels follow it
+// (CheckElementCloser's <=, keep-pruned-connections, which candidate counts as pruned, replace in place or append, and
+// SelectNeighbors returning a short candidate list as it came: furthest first).
+// A visited table that fills up ends the element's search early and sets HB_ERR_VISITED in the guard word; records past rec_cap
+// set HB_ERR_RECORDS.  hnsw_build (vsr_hnsw_rt.hip) reads the word after the last batch: it never returns such a graph.
+// Levels come from the same seeded xorshift64* stream as the test suite's serial CPU restatement
 // (level = floor(-ln(u) / ln(m)), hnswutils.c:243), so both builds place the same elements on the same layers.
 // Identical vectors: pgvector folds a row whose vector equals a selected layer-0 neighbour's into that element's heap TIDs
 // (up to 10, hnswbuild.c:309-355).  ef_search bounds ELEMENTS, so this changes what a search returns: on a corpus of
@@ -35,7 +46,7 @@
 //
 // Parity definition (tests/test_gpu_index.py): recall@20 at ef_search = 40 against the exact scan >= pgvector's TAP
 // thresholds on its own case (10 000 x 3-d: 0.99; inner product 0.97), and within 0.01 of that serial build's recall on
-// the same rows.
+// the same rows; and (tests/test_gpu_hnsw_build_model.py) graph identity with the batched model, as above.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -154,8 +165,8 @@ __device__ __forceinline__ int hb_select(const HnswBuildParams& p, const uint64_
                                          int32_t* ids, float* nd, int* pruned, int lane)
 {
     if (n <= lm) {
-        if (lane < n) sel[lane] = lane;
-        for (int i = 64 + lane; i < n; i += 64) sel[i] = i;
+        // "return c" (hnswutils.c:1071-1072): the candidates as HnswSearchLayer's w lists them, FURTHEST first
+        for (int i = lane; i < n; i += 64) sel[i] = n - 1 - i;
         *pruned = -1;
         wave_sync();
         return n;
@@ -343,18 +354,22 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
             nl[j] = (int32_t) (uint32_t) key;
             dl[j] = mono_to_float((uint32_t) (key >> 32));
             if (base + (uint32_t) j < p.rec_cap) {
-                p.rec_key[base + j] = ((uint64_t) (uint32_t) lc << 32) | (uint32_t) key;
+                // slots are claimed in wave arrival order; the sort key carries the index in the batch (< 4096 = 2^HB_SRC_BITS),
+                // so that a (layer, target) run comes out in ascending source element whatever the arrival order was
+                p.rec_key[base + j] = ((uint64_t) (uint32_t) lc << (32 + HB_SRC_BITS)) | ((uint64_t) (uint32_t) key << HB_SRC_BITS) | bi;
                 p.rec_val[base + j] = ((uint64_t) me << 32) | __float_as_uint(mono_to_float((uint32_t) (key >> 32)));
             }
         }
+        if (lane == 0 && ns > 0 && base + (uint32_t) ns > p.rec_cap) atomicOr(p.err, HB_ERR_RECORDS);   // (cannot happen: the host sizes rec_cap from the levels)
         if (lane == 0)
             for (uint32_t i = 0; i < count; ++i) X[i] = 0;                    // W is the next layer's entry set
         wave_sync();
     }
-    if (overflow && lane == 0) atomicOr(p.err, 16u);
+    if (overflow && lane == 0) atomicOr(p.err, HB_ERR_VISITED);
 }
 
-// ---- phase 2: reverse edges, sorted by (layer, target): the wave of a run's first record applies the whole run ----
+// ---- phase 2: reverse edges, sorted by (layer, target, source): the wave of a run's first record applies the whole
+// (layer, target) run, sources in ascending element id ----
 template <bool IND, int ROWS>
 __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildParams p)
 {
@@ -364,8 +379,8 @@ __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildPar
     const uint32_t ri = blockIdx.x * 4 + wave;
     const uint32_t n_rec = *p.rec_count < p.rec_cap ? *p.rec_count : p.rec_cap;
     if (ri >= n_rec) return;
-    const uint64_t key = p.rec_key[ri];
-    if (ri > 0 && p.rec_key[ri - 1] == key) return;                           // not the first of its run
+    const uint64_t key = p.rec_key[ri] >> HB_SRC_BITS;                        // (layer, target)
+    if (ri > 0 && (p.rec_key[ri - 1] >> HB_SRC_BITS) == key) return;          // not the first of its run
     const int lc = (int) (key >> 32);
     const uint32_t owner = (uint32_t) key;
     const int lm = (int) (lc == 0 ? 2 * p.m : p.m);
@@ -377,7 +392,7 @@ __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildPar
     float*    nd = reinterpret_cast<float*>(ids + HB_NBR);
     float* dl;
     int32_t* nl = hb_list(p, owner, lc, &dl);
-    for (uint32_t r = ri; r < n_rec && p.rec_key[r] == key; ++r) {            // HnswUpdateConnection, one after another
+    for (uint32_t r = ri; r < n_rec && (p.rec_key[r] >> HB_SRC_BITS) == key; ++r) {   // HnswUpdateConnection, one after another
         const uint32_t e = (uint32_t) (p.rec_val[r] >> 32);
         const float de = __uint_as_float((uint32_t) p.rec_val[r]);
         // current length of the list (-1 padded)
@@ -444,7 +459,7 @@ static hipError_t build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sort_
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (p.entry < 0) return hipSuccess;                                       // the first element has nobody to link to
     hipcub::DoubleBuffer<uint64_t> keys(p.rec_key, d_key_alt), vals(p.rec_val, d_val_alt);
-    e = hipcub::DeviceRadixSort::SortPairs(d_sort_tmp, sort_tmp_bytes, keys, vals, (int) p.rec_cap, 0, 40, s);
+    e = hipcub::DeviceRadixSort::SortPairs(d_sort_tmp, sort_tmp_bytes, keys, vals, (int) p.rec_cap, 0, HB_KEY_BITS, s);
     if (e != hipSuccess) return e;
     HnswBuildParams q = p;
     q.rec_key = keys.Current();
@@ -470,6 +485,6 @@ size_t vsr_hnsw_build_sort_bytes(uint32_t rec_cap)
 {
     size_t bytes = 0;
     hipcub::DoubleBuffer<uint64_t> keys(nullptr, nullptr), vals(nullptr, nullptr);
-    (void) hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, keys, vals, (int) rec_cap, 0, 40, (hipStream_t) 0);
+    (void) hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, keys, vals, (int) rec_cap, 0, HB_KEY_BITS, (hipStream_t) 0);
     return bytes;
 }

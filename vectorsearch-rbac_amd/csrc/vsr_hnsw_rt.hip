@@ -169,13 +169,22 @@ extern "C" int vsr_hnsw_load_half(vsr_corpus* c, int m, int32_t n_elem, int32_t 
     return hnsw_load(c, RowFormat::HALF, 0, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, out, "vsr_hnsw_load_half");
 }
 
+// per-wave LDS of the build's search kernel (hnsw_build_search_kernel's carve-up) with `slots` visited-table entries
+static size_t hnsw_build_lds_per_wave(uint32_t caps, uint32_t slots)
+{
+    return ((size_t) caps * 8 + ((caps + 15) & ~15u) + (size_t) HB_NBR * 12 + (size_t) caps * 4 + (size_t) slots * 4 + 15) & ~(size_t) 15;
+}
+
 // CREATE INDEX ... USING hnsw on the GPU (vsr_hnsw_build.hip): batched insertion over the corpus's rows, levels from a seeded
 // xorshift64* stream drawn once per row.  flags = 0: element e = internal row e.  VSR_HNSW_BUILD_MERGE_DUPLICATES: the
 // elements come from vsr_hnsw_dedup.hip's table.  Returns a loaded index, as vsr_hnsw_load would from the same graph.
 // expect: the corpus format the entry point is for -- BIT (vsr_hnsw_build_bit; metric is the opclass), HALF (vsr_hnsw_build_half) or
-// F32; the kernels take that row format
-static int hnsw_build(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out,
-                      const char* who)
+// F32; the kernels take that row format.
+// One attempt with a visited table of *slots entries (0: the default for m and ef_construction, written back).  *guard: the
+// build's guard-word bits (HB_ERR_VISITED / HB_ERR_RECORDS) when a kernel set one; the partial index is then freed, the bits
+// are cleared from the session's word, *out stays NULL and the return value is VSR_OK: hnsw_build decides what follows.
+static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out,
+                           const char* who, uint32_t* slots_io, uint32_t* guard)
 {
     if (!c || !out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
     *out = nullptr;
@@ -316,45 +325,76 @@ static int hnsw_build(vsr_corpus* c, RowFormat expect, int m, int ef_constructio
     bp.level = h->d_level;
     bp.elem_row = merge ? h->d_elem_row : nullptr;
     bp.caps = (uint32_t) (ef_construction + 2 * m);
-    uint32_t slots = 4096;
-    while (slots < (uint32_t) ef_construction * 2u * (uint32_t) m * 2u && slots < 32768u) slots <<= 1;
+    uint32_t slots = *slots_io;
+    if (slots == 0) {
+        slots = 4096;
+        while (slots < (uint32_t) ef_construction * 2u * (uint32_t) m * 2u && slots < 32768u) slots <<= 1;
+        *slots_io = slots;
+    }
     bp.hash_slots = slots;
-    const size_t per = ((size_t) bp.caps * 8 + ((bp.caps + 15) & ~15u) + (size_t) HB_NBR * 12 + (size_t) bp.caps * 4 + (size_t) slots * 4 + 15) &
-                       ~(size_t) 15;
+    const size_t per = hnsw_build_lds_per_wave(bp.caps, slots);
     if (per > HN_LDS_BUDGET) return bail(fail(VSR_ERR_UNSUPPORTED, "%s: ef_construction = %d with m = %d does not fit the LDS", who, ef_construction, m));
     bp.lds_per_wave = (uint32_t) per;
     bp.wpb = (uint32_t) std::min<size_t>(4, HN_LDS_BUDGET / per);
     bp.err = ctx->err_word();
-    const uint32_t batch_max = 4096;
-    bp.rec_cap = batch_max * (uint32_t) (2 * m + std::min(max_level, 4) * m);
-    HB_CHK(hipMalloc(&d_key[0], (size_t) bp.rec_cap * 8));
-    HB_CHK(hipMalloc(&d_key[1], (size_t) bp.rec_cap * 8));
-    HB_CHK(hipMalloc(&d_val[0], (size_t) bp.rec_cap * 8));
-    HB_CHK(hipMalloc(&d_val[1], (size_t) bp.rec_cap * 8));
+    // the schedule: a batch never exceeds 1/8 of the graph it is inserted into (its elements do not see each other).  An element
+    // of level l emits at most 2m + l * m reverse edges, so a batch's record slots are known here: the sort and the link
+    // launch cover those, not the largest batch's
+    struct Batch { uint32_t first, count, rec_cap; };
+    std::vector<Batch> batches;
+    uint32_t rec_cap_max = 1;
+    size_t tmp_bytes = 0;
+    for (int64_t done = 0; done < ne;) {
+        const int64_t b = std::max<int64_t>(1, std::min<int64_t>({done / 8, (int64_t) HB_BATCH_MAX, ne - done}));
+        uint64_t cap = 0;
+        for (int64_t e = done; e < done + b; ++e) cap += (uint64_t) (2 * m + level[(size_t) e] * m);
+        if (cap > 0x7FFFFFFFull) return bail(fail(VSR_ERR_UNSUPPORTED, "%s: a batch of %lld elements with m = %d has too many reverse edges", who, (long long) b, m));
+        batches.push_back({(uint32_t) done, (uint32_t) b, (uint32_t) cap});
+        rec_cap_max = std::max(rec_cap_max, (uint32_t) cap);
+        done += b;
+    }
+    {
+        std::vector<uint32_t> caps;                                           // the sort's scratch: the most any batch's size asks for
+        for (const Batch& bt : batches) caps.push_back(bt.rec_cap);
+        std::sort(caps.begin(), caps.end());
+        caps.erase(std::unique(caps.begin(), caps.end()), caps.end());
+        for (uint32_t cap : caps) tmp_bytes = std::max(tmp_bytes, vsr_hnsw_build_sort_bytes(cap));
+    }
+    HB_CHK(hipMalloc(&d_key[0], (size_t) rec_cap_max * 8));
+    HB_CHK(hipMalloc(&d_key[1], (size_t) rec_cap_max * 8));
+    HB_CHK(hipMalloc(&d_val[0], (size_t) rec_cap_max * 8));
+    HB_CHK(hipMalloc(&d_val[1], (size_t) rec_cap_max * 8));
     HB_CHK(hipMalloc(&d_cnt, 64));
-    const size_t tmp_bytes = vsr_hnsw_build_sort_bytes(bp.rec_cap);
     HB_CHK(hipMalloc(&d_tmp, std::max<size_t>(tmp_bytes, 256)));
     bp.rec_count = d_cnt;
 
     int32_t entry = -1, entry_level = -1;
-    for (int64_t done = 0; done < ne;) {
-        // a batch never exceeds 1/8 of the graph it is inserted into: its elements do not see each other
-        const int64_t b = std::max<int64_t>(1, std::min<int64_t>({done / 8, (int64_t) batch_max, ne - done}));
+    for (const Batch& bt : batches) {
         bp.entry = entry;
         bp.entry_level = entry_level;
-        bp.first = (uint32_t) done;
-        bp.count = (uint32_t) b;
+        bp.first = bt.first;
+        bp.count = bt.count;
+        bp.rec_cap = bt.rec_cap;
         bp.rec_key = d_key[0];
         bp.rec_val = d_val[0];
         HB_CHK(vsr_hnsw_build_batch(bp, d_tmp, tmp_bytes, d_key[1], d_val[1], ctx->stream));
-        for (int64_t e = done; e < done + b; ++e)            // HnswUpdateGraphInMemory: a higher element becomes the entry point
+        for (uint32_t e = bt.first; e < bt.first + bt.count; ++e)   // HnswUpdateGraphInMemory: a higher element becomes the entry point
             if (entry < 0 || level[(size_t) e] > entry_level) {
                 entry = (int32_t) e;
                 entry_level = level[(size_t) e];
             }
-        done += b;
     }
     HB_CHK(hipStreamSynchronize(ctx->stream));
+    // no silent degradation: a full visited table made a search stop early, records past rec_cap were dropped.  The bits are
+    // this build's: they leave the session's guard word here, so that a later vsr_screening_check is not poisoned
+    uint32_t word = 0;
+    HB_CHK(hipMemcpy(&word, bp.err, sizeof word, hipMemcpyDeviceToHost));
+    if (word & (HB_ERR_VISITED | HB_ERR_RECORDS)) {
+        *guard = word & (HB_ERR_VISITED | HB_ERR_RECORDS);
+        word &= ~(HB_ERR_VISITED | HB_ERR_RECORDS);
+        HB_CHK(hipMemcpy(bp.err, &word, sizeof word, hipMemcpyHostToDevice));
+        return bail(VSR_OK);
+    }
 #undef HB_CHK
     cleanup();
     h->entry = ne > 0 ? entry : -1;
@@ -377,6 +417,40 @@ static int hnsw_build(vsr_corpus* c, RowFormat expect, int m, int ef_constructio
     c->hnsw_indexes.push_back(h.get());
     *out = h.release();
     return VSR_OK;
+}
+
+// The build never returns a thinner graph than it was asked for: when a layer search filled its visited table the build is
+// run again with a table twice as large, as long as one fits the LDS; dropped reverse edges are an error.
+// VSR_HNSW_BUILD_VISITED_SLOTS=n (development / tests; a power of two, 256 .. 32768; read at every call) sets the INITIAL table
+// size, so that the restart can be exercised on a small corpus.
+static int hnsw_build(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out,
+                      const char* who)
+{
+    uint32_t slots = 0;
+    if (const char* env = getenv("VSR_HNSW_BUILD_VISITED_SLOTS")) {
+        char* end = nullptr;
+        const long v = strtol(env, &end, 10);
+        if (end == env || *end != '\0' || v < 256 || v > 32768 || (v & (v - 1)) != 0) {
+            if (out) *out = nullptr;
+            return fail(VSR_ERR_INVALID, "%s: VSR_HNSW_BUILD_VISITED_SLOTS must be a power of two from 256 to 32768 (got \"%s\")", who, env);
+        }
+        slots = (uint32_t) v;
+    }
+    for (;;) {
+        uint32_t guard = 0;
+        const int rc = hnsw_build_once(c, expect, m, ef_construction, metric, seed, flags, out, who, &slots, &guard);
+        if (rc != VSR_OK || guard == 0) return rc;
+        if (guard & HB_ERR_RECORDS)
+            return fail(VSR_ERR_UNSUPPORTED, "%s: reverse edges were dropped at ef_construction = %d with m = %d: the graph would be incomplete", who,
+                        ef_construction, m);
+        // HB_ERR_VISITED
+        const uint32_t caps = (uint32_t) (ef_construction + 2 * m);
+        if (slots >= 32768u || hnsw_build_lds_per_wave(caps, slots * 2u) > HN_LDS_BUDGET)
+            return fail(VSR_ERR_UNSUPPORTED,
+                        "%s: a layer search at ef_construction = %d with m = %d fills its visited table of %u entries and no larger one fits the LDS",
+                        who, ef_construction, m, slots);
+        slots *= 2u;
+    }
 }
 
 extern "C" int vsr_hnsw_build(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, vsr_hnsw** out)
