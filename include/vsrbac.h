@@ -165,8 +165,10 @@ int vsr_corpus_binary_quantize(vsr_corpus* src, vsr_corpus** out);
  * <#>, <=>, <+> of sparsevec.c:803-1037, exact (nothing is screened, nothing flags), ordered as every search is.  Sums are fp32 as
  * pgvector's are, in another order; the query terms no row entry meets enter as (float) of a double difference.
  * vsr_search*, vsr_search_bit*, vsr_search_quantized*, vsr_corpus_binary_quantize, vsr_ivf_load, vsr_ivf_assign, vsr_hnsw_load
- * and vsr_hnsw_build* over a sparse corpus: VSR_ERR_UNSUPPORTED, the message names sparsevec (the sparsevec_*_ops HNSW opclasses
- * are not built yet). */
+ * and vsr_hnsw_build(_ex) over a sparse corpus: VSR_ERR_UNSUPPORTED, the message names sparsevec.  The HNSW opclasses
+ * sparsevec_l2_ops / sparsevec_ip_ops / sparsevec_cosine_ops / sparsevec_l1_ops are vsr_hnsw_load_sparse / vsr_hnsw_build_sparse /
+ * vsr_hnsw_search_sparse* below (K4s); pgvector has no IVFFlat opclass for sparsevec.  (The text of vsr_hnsw_load's and
+ * vsr_hnsw_build's refusal still says the type "has no index path yet": it is kept as it was.) */
 int vsr_corpus_load_sparse(vsr_ctx* ctx, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n, int dim,
                            const int64_t* block_ids, const int32_t* doc_ids, int64_t row_offset,
                            vsr_corpus** out);
@@ -715,6 +717,59 @@ int vsr_hnsw_search_bit_iterative_device(vsr_hnsw* index, const uint8_t* d_queri
                                          const vsr_filter* const* filters, int mode, int64_t max_scan_tuples,
                                          int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
                                          int32_t* d_out_counts, int64_t* d_out_tuples);
+/* K4s -- HNSW over a sparse corpus (vsr_corpus_load_sparse): pgvector's sparsevec_l2_ops / sparsevec_ip_ops /
+ * sparsevec_cosine_ops / sparsevec_l1_ops (hnswutils.c:1352-1361, 1411-1422), the type's whole index story (it has no IVFFlat
+ * opclass).  vsr_hnsw_load_sparse takes the arrays of vsr_hnsw_load, vsr_hnsw_build_sparse the arguments of vsr_hnsw_build_ex with
+ * metric VSR_METRIC_L2 .. VSR_METRIC_L1; the metric of a search is given per call, as for the float indexes, L1 included.  Cosine
+ * follows K4's convention: the caller loads unit rows (vsr_sparse_l2_normalize) and passes unit queries.
+ *   - Refusals of load and build: a corpus that is not sparse, VSR_ERR_INVALID "<entry point>: the corpus is not a sparse corpus";
+ *     a corpus with a row of more than 1000 non-zeros (HNSW_MAX_NNZ, checkValue of the opclasses), VSR_ERR_UNSUPPORTED
+ *     "sparsevec cannot have more than 1000 non-zero elements for hnsw index"; VSR_HNSW_BUILD_MERGE_DUPLICATES,
+ *     VSR_ERR_UNSUPPORTED (the pre-pass compares fixed-stride rows).  m, ef_construction, seed: vsr_hnsw_build_ex's rules.
+ *   - Queries are CSR, as vsr_search_sparse takes them and validated as it validates them (host forms); pgvector checks only
+ *     indexed values, so a query may carry up to 16000 non-zeros.  The _device forms take the three arrays in device memory and
+ *     max_query_nnz, which sizes the staged tables: a longer (or malformed) query becomes an empty table and sets bit value 8 of the
+ *     guard word (vsr_screening_check), exactly as in vsr_search_sparse_device.  Query staging and the search are launches on the
+ *     corpus context's stream with no host round trip.
+ *   - Index distance: squared L2, the L1 sum, the negated inner product (inner product and cosine opclasses); ties by element id.
+ *     Reported distances: vsr_hnsw_search's rule, and <+> reports the sum itself.  Arithmetic is vsr_search_sparse's: fp32 over
+ *     a row's entries, the query entries no row entry meets as (float) of a double difference.
+ *   - The float and bit search entry points on a sparse index: VSR_ERR_UNSUPPORTED, the message names these entry points; these
+ *     entry points on another index: VSR_ERR_INVALID.
+ *   - Everything else is vsr_hnsw_search's, unchanged: vsr_hnsw_set_predicate_aware, the iterative modes with max_scan_tuples, the
+ *     visited-set forms and both re-runs, vsr_hnsw_export*, vsr_hnsw_info, vsr_hnsw_device_bytes, vsr_hnsw_free, filters, row_offset,
+ *     up to 10 TIDs per element. */
+int vsr_hnsw_load_sparse(vsr_corpus* sparse_corpus, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
+                         const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
+                         int32_t n_upper, int32_t max_level, vsr_hnsw** out);
+int vsr_hnsw_build_sparse(vsr_corpus* sparse_corpus, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out);
+int vsr_hnsw_search_sparse(vsr_hnsw* index, const int64_t* q_indptr, const int32_t* q_indices, const float* q_values, int nq, int dim,
+                           int k, int ef_search, int metric, const vsr_filter* const* filters,
+                           int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows, float* out_dist, int32_t* out_counts,
+                           int64_t* out_visited);
+int vsr_hnsw_search_sparse_device(vsr_hnsw* index, const int64_t* d_q_indptr, const int32_t* d_q_indices, const float* d_q_values,
+                                  int nq, int dim, int max_query_nnz, int k, int ef_search, int metric,
+                                  const vsr_filter* const* filters,
+                                  int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
+                                  int32_t* d_out_counts, int64_t* d_out_visited);
+int vsr_hnsw_search_sparse_iterative(vsr_hnsw* index, const int64_t* q_indptr, const int32_t* q_indices, const float* q_values, int nq,
+                                     int dim, int k, int ef_search, int metric, const vsr_filter* const* filters, int mode,
+                                     int64_t max_scan_tuples,
+                                     int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows, float* out_dist,
+                                     int32_t* out_counts, int64_t* out_tuples);
+int vsr_hnsw_search_sparse_iterative_device(vsr_hnsw* index, const int64_t* d_q_indptr, const int32_t* d_q_indices,
+                                            const float* d_q_values, int nq, int dim, int max_query_nnz, int k, int ef_search,
+                                            int metric, const vsr_filter* const* filters, int mode, int64_t max_scan_tuples,
+                                            int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
+                                            int32_t* d_out_counts, int64_t* d_out_tuples);
+/* The two vector functions the cosine opclass needs, for n sparse vectors at once (host pointers; only the offsets and the values
+ * enter): sparsevec_l2_norm (sparsevec.c:1044-1055: a double sum of double products, then sqrt) and sparsevec_l2_normalize
+ * (sparsevec.c:1060-1120: (float) (v / norm) per entry with the norm in double; a zero norm leaves the row as it is; an infinite
+ * result fails with "value out of range: overflow").  out_values has one value per input entry; *out_zeros (may be NULL) counts
+ * the entries that became 0 -- the caller drops them, as pgvector does, so that the result is a legal sparsevec. */
+int vsr_sparse_norms(vsr_ctx* ctx, const int64_t* indptr, const float* values, int64_t n, double* out);
+int vsr_sparse_l2_normalize(vsr_ctx* ctx, const int64_t* indptr, const float* values, int64_t n, float* out_values, int64_t* out_zeros);
+
 /* The indexed two-stage search -- pgvector's documented use of binary_quantize: CREATE INDEX ... USING hnsw
  * ((binary_quantize(embedding)::bit(n)) bit_hamming_ops), ORDER BY ... <~> ... LIMIT shortlist, then the re-rank on the original
  * vectors.  It is vsr_search_quantized with stage 1 replaced by the index: qb = binary_quantize(q); S = the answer of

@@ -11,7 +11,7 @@ enum MetricBit : int { M_HAMMING = 4, M_JACCARD = 5 };
 // row format of the corpus under an HNSW graph: a template parameter of the search body (vsr_hnsw.h) and of the build kernels
 // (vsr_hnsw_build.hip).  Everything but the distance stage and the reported distance is shared between the two
 // (ROWS_HALF: a halfvec corpus, vsr_halfops.h)
-enum HnswRows : int { ROWS_F32 = 0, ROWS_BIT = 1, ROWS_HALF = 2 };
+enum HnswRows : int { ROWS_F32 = 0, ROWS_BIT = 1, ROWS_HALF = 2, ROWS_SPARSE = 3 };
 
 template <bool JACCARD>
 __device__ __forceinline__ void accum_bits(uint32_t& p, const uint4& x, const uint4& q)

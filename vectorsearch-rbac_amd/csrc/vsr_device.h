@@ -484,6 +484,10 @@ int  scan_qmax_sparse(uint32_t slots, int k);             // queries per pass: 1
 hipError_t launch_sparse_pair_distances(const int64_t* a_ptr, const int32_t* a_idx, const float* a_val, const int64_t* b_ptr,
                                         const int32_t* b_idx, const float* b_val, int64_t n_pairs, int metric, double* out,
                                         hipStream_t s);
+// sparsevec_l2_norm / sparsevec_l2_normalize (sparsevec.c:1044-1120) of n CSR rows, one thread per row; out_values == nullptr:
+// norms only; *overflow |= 1 for an infinite result, *zeros += the entries that became 0
+hipError_t launch_sparse_norms(const int64_t* ptr, const float* val, int64_t n, double* out_norm, float* out_values, int* overflow,
+                               unsigned long long* zeros, hipStream_t s);
 hipError_t launch_stage_bit(const StageParams& p, hipStream_t s);      // p.q_bits != 0
 // bit corpora (vsr_bit.hip).  Popcount of every row of `chunks` 16-byte chunks, as fp32 (exact: <= 64000)
 hipError_t launch_row_popcounts(const uint4* rows, uint32_t n_rows, uint32_t chunks, float* pop, hipStream_t s);

@@ -10,8 +10,9 @@
 
 namespace vsr {
 
-// the index distance the graph ranks by: squared L2, or the negative inner product (cosine opclass: unit rows)
-__device__ __forceinline__ float hnsw_rank_value(int metric, float s) { return metric == M_L2 ? s : -s; }
+// the index distance the graph ranks by: squared L2, the L1 sum (sparsevec_l1_ops), or the negative inner product (cosine opclass:
+// unit rows)
+__device__ __forceinline__ float hnsw_rank_value(int metric, float s) { return metric == M_L2 || metric == M_L1 ? s : -s; }
 
 // 8 floats (elements past `dim` zero) starting at element 8 * ch of a query -> one chunk of binary16 values: Float4ToHalf,
 // round to nearest even, which is what `$1::halfvec` holds

@@ -55,6 +55,7 @@
 #include "vsr_topk.h"
 #include "vsr_bitops.h"
 #include "vsr_halfops.h"
+#include "vsr_sparseops.h"
 
 namespace vsr {
 
@@ -100,6 +101,15 @@ struct HnswParams {
     // ROWS_HALF only.  rows: stride4 16-byte chunks of 8 binary16 values per row (elements past dim zero); queries: fp32, as for ROWS_F32
     uint32_t        q_chunks = 0;            // 16-byte chunks of the wave's LDS that hold the rounded query: stride4 when stride4 > 64
                                              // (set before hnsw_plan*, which count it), else 0 -- the query lives in registers
+    // ROWS_SPARSE only.  rows: the corpus's interleaved (index, value) entries, row r owns entries sp_off[r] .. sp_off[r + 1]; queries is
+    // not read: query qi is the table sp_tab + qi * sp_slots that stage_sparse_kernel made, with its double totals sp_qtot[2 qi] (Q2)
+    // and sp_qtot[2 qi + 1] (Q1).  q_chunks = sp_slots / 2 when the wave keeps a copy of the table in its LDS, 0 when it reads it where
+    // staging wrote it; metric may be M_L1
+    const uint64_t* sp_off = nullptr;        // [rows + 1]
+    const uint2*    sp_tab = nullptr;        // [nq][sp_slots]
+    const double*   sp_qtot = nullptr;       // [nq][2]
+    uint32_t        sp_slots = 0;            // a power of two >= 2
+    uint32_t        sp_lanes = 0;            // lanes per row: 4, 16 or 64 (the corpus's entry-count class)
     // hnsw_iterative_kernel only (out_visited then reports T when the scan stopped; status 1 = D overflowed)
     int             iter_mode = 0;           // VSR_HNSW_ITERATIVE_RELAXED = 1 / STRICT = 2
     int64_t         max_scan = 0;            // hnsw.max_scan_tuples
@@ -141,6 +151,15 @@ __device__ __forceinline__ void wave_sync_global()
 // the wave loads it (`$1::halfvec`): the lane keeps its chunk in a register when C <= 64, otherwise the wave keeps the rounded
 // query in its LDS (q_chunks chunks in front of the visited set); both last across expansions and there is no staging launch.
 // Arithmetic: both operands widened to fp32, fmaf sums (halfutils.c), ranked and reported exactly as K4 does.
+//
+// K4s, ROWS = ROWS_SPARSE: the graph of a sparse corpus (sparsevec_l2_ops / sparsevec_ip_ops / sparsevec_cosine_ops /
+// sparsevec_l1_ops, hnswutils.c:1352-1361, 1411-1422).  A row is a CSR run of (index, value) entries of any length up to 1000; the
+// query is K1s's open-addressing table (stage_sparse_kernel: one launch in front of the search, on the same stream).  The wave
+// copies its query's table once into its LDS, into the q_chunks area in front of the visited set (sp_slots / 2 chunks: 16 KB at 1000
+// non-zeros); a table that does not fit beside S at one query per workgroup is read where staging wrote it.  The sparse distance
+// stage (sparse_graph_distances, vsr_sparseops.h) gives a row 4, 16 or 64 lanes by the corpus's entry-count class.  Arithmetic:
+// K1s's (fp32 sum over the row's entries, double sum over the hits, the rest term of L2 and L1); ranked by squared L2, the L1 sum or
+// the negated inner product; reported as K4 reports, L1 as the sum itself.
 template <bool ITER, int ROWS = ROWS_F32>
 __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
 {
@@ -161,7 +180,12 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
         qh = reinterpret_cast<uint4*>(lv);
         lv += 4u * p.q_chunks;
     }
-    uint32_t* hist = nullptr;                                                // ITER: [HN_HIST] radix-select histogram
+    uint64_t* qt = nullptr;                                                  // ROWS_SPARSE: [sp_slots] the query's table (q_chunks != 0)
+    if constexpr (ROWS == ROWS_SPARSE) {
+        qt = reinterpret_cast<uint64_t*>(lv);
+        lv += 4u * p.q_chunks;
+    }
+    uint32_t* hist = nullptr;                                               // ITER: [HN_HIST] radix-select histogram
     if constexpr (ITER) {
         hist = lv;
         lv += HN_HIST;
@@ -218,6 +242,21 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
             wave_sync();
         }
     }
+    // ROWS_SPARSE: the staged table of the query, copied into the wave's LDS when the plan gave it room; its double totals
+    const uint64_t* sp_gtab = nullptr;
+    uint32_t sp_mask = 0, sp_shift = 0;
+    double sp_q2 = 0.0, sp_q1 = 0.0;
+    if constexpr (ROWS == ROWS_SPARSE) {
+        sp_gtab = reinterpret_cast<const uint64_t*>(p.sp_tab) + (size_t) qi * p.sp_slots;
+        sp_mask = p.sp_slots - 1u;
+        sp_shift = (uint32_t) __clz((int) p.sp_slots) + 1u;                   // 32 - log2 slots
+        sp_q2 = p.sp_qtot[2 * (size_t) qi];
+        sp_q1 = p.sp_qtot[2 * (size_t) qi + 1];
+        if (p.q_chunks) {
+            for (uint32_t i = (uint32_t) lane; i < p.sp_slots; i += 64) qt[i] = sp_gtab[i];
+            wave_sync();
+        }
+    }
     // distance of the query to `cnt` elements listed in nb[] -> nd[] (fp32 sum; exact on integer-valued data in any order)
     auto distances = [&](int cnt) {
         if constexpr (ROWS == ROWS_BIT) {
@@ -233,6 +272,15 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
             const uint4* hrows = reinterpret_cast<const uint4*>(p.rows);
             if (p.metric == M_L2) half_graph_distances<true>(hrows, p.stride4, bit_g, p.elem_row, qh, qreg, nb, cnt, nd, lane);
             else half_graph_distances<false>(hrows, p.stride4, bit_g, p.elem_row, qh, qreg, nb, cnt, nd, lane);
+            wave_sync();
+            return;
+        } else if constexpr (ROWS == ROWS_SPARSE) {
+            if (p.q_chunks)
+                sparse_graph_distances_metric(p.metric, p.rows, p.sp_off, p.sp_lanes, p.elem_row, (lds_u64) qt, sp_mask, sp_shift, sp_q2, sp_q1,
+                                              nb, cnt, nd, lane);
+            else
+                sparse_graph_distances_metric(p.metric, p.rows, p.sp_off, p.sp_lanes, p.elem_row, as_global(sp_gtab), sp_mask, sp_shift, sp_q2,
+                                              sp_q1, nb, cnt, nd, lane);
             wave_sync();
             return;
         } else {
@@ -608,7 +656,9 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
                         v = d;
                         if (p.out_keys) p.out_keys[o] = make_key(d, row + p.key_row_offset);
                     } else
-                    if (p.metric == M_L2) v = (float) sqrt((double) d);       // l2_distance, vector.c:577
+                    if (ROWS == ROWS_SPARSE && p.metric == M_L1) v = d;      // <+>: the index distance is the operator's value
+                    else
+                    if (p.metric == M_L2) v = (float) sqrt((double) d);      // l2_distance, vector.c:577
                     else if (p.metric == M_IP) v = d;                        // <#> = negative inner product
                     else {                                                   // unit rows: cosine distance = 1 - dot
                         double sim = -(double) d;
@@ -742,6 +792,10 @@ __global__ __launch_bounds__(256) void hnsw_iterative_kernel(const HnswParams p)
 __global__ __launch_bounds__(256) void hnsw_bit_iterative_kernel(const HnswParams p) { hnsw_search_body<true, ROWS_BIT>(p); }
 __global__ __launch_bounds__(256) void hnsw_half_iterative_kernel(const HnswParams p) { hnsw_search_body<true, ROWS_HALF>(p); }
 
+// K4s: the search and the iterative scan over a sparse corpus
+__global__ __launch_bounds__(256) void hnsw_sparse_search_kernel(const HnswParams p) { hnsw_search_body<false, ROWS_SPARSE>(p); }
+__global__ __launch_bounds__(256) void hnsw_sparse_iterative_kernel(const HnswParams p) { hnsw_search_body<true, ROWS_SPARSE>(p); }
+
 constexpr size_t HN_LDS_BUDGET = 156 * 1024;   // of the CU's 160 KB (dynamic LDS of one workgroup)
 
 // (q_chunks: HnswParams::q_chunks, the rounded query of a K4h wave; 0 for every other kernel)
@@ -816,6 +870,7 @@ inline hipError_t launch_hnsw_rows(const HnswParams& p, hipStream_t s)
     if (lds > HN_LDS_BUDGET || p.qpb < 1 || p.qpb > 4) return hipErrorInvalidValue;
     const auto kernel = ROWS == ROWS_BIT    ? (ITER ? hnsw_bit_iterative_kernel : hnsw_bit_search_kernel)
                         : ROWS == ROWS_HALF ? (ITER ? hnsw_half_iterative_kernel : hnsw_half_search_kernel)
+                        : ROWS == ROWS_SPARSE ? (ITER ? hnsw_sparse_iterative_kernel : hnsw_sparse_search_kernel)
                                             : (ITER ? hnsw_iterative_kernel : hnsw_search_kernel);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
@@ -832,6 +887,11 @@ inline hipError_t launch_hnsw(RowFormat f, bool iterative, const HnswParams& p, 
     case RowFormat::F32:  return iterative ? launch_hnsw_rows<true, ROWS_F32>(p, s) : launch_hnsw_rows<false, ROWS_F32>(p, s);
     case RowFormat::HALF: return iterative ? launch_hnsw_rows<true, ROWS_HALF>(p, s) : launch_hnsw_rows<false, ROWS_HALF>(p, s);
     case RowFormat::BIT:  return iterative ? launch_hnsw_rows<true, ROWS_BIT>(p, s) : launch_hnsw_rows<false, ROWS_BIT>(p, s);
+    case RowFormat::SPARSE:
+        if (p.sp_slots < 2 || (p.sp_slots & (p.sp_slots - 1)) != 0 || (p.q_chunks != 0 && p.q_chunks != p.sp_slots / 2) ||
+            (p.sp_lanes != 4 && p.sp_lanes != 16 && p.sp_lanes != 64))
+            return hipErrorInvalidValue;
+        return iterative ? launch_hnsw_rows<true, ROWS_SPARSE>(p, s) : launch_hnsw_rows<false, ROWS_SPARSE>(p, s);
     default:              return hipErrorInvalidValue;
     }
 }

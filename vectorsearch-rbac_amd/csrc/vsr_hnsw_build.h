@@ -13,6 +13,9 @@ constexpr int HB_SRC_BITS = 12;            // a reverse edge's sort key ends in 
 constexpr int HB_KEY_BITS = 8 + 32 + HB_SRC_BITS;   // layer (<= 255) | target | source index: the bits the sort looks at
 constexpr uint32_t HB_ERR_VISITED = 16u;   // guard-word bit: a visited table filled up (hnsw_build restarts with a larger one)
 constexpr uint32_t HB_ERR_RECORDS = 32u;   // guard-word bit: reverse edges past rec_cap were dropped
+constexpr uint32_t HB_ERR_CANDIDATES = 64u;   // guard-word bit (sparse build): the candidate array dropped an unexpanded candidate as near as
+                                              // the furthest of W, which pgvector's unbounded heap would still expand (hnsw_build restarts
+                                              // with a longer array)
 
 struct HnswBuildParams {
     const float4*  rows = nullptr;           // corpus rows (internal order), zero padded to stride4 float4
@@ -21,6 +24,11 @@ struct HnswBuildParams {
     int            bits = 0;                 // 1: a bit corpus -- rows are stride4 16-byte chunks of packed bits, metric M_HAMMING / M_JACCARD
     const float*   row_pop = nullptr;        // bits: popcount of every row (Jaccard)
     int            halves = 0;               // 1: a halfvec corpus -- rows are stride4 16-byte chunks of 8 binary16 values, metric M_L2 / M_IP
+    int            sparse = 0;               // 1: a sparse corpus -- rows are interleaved (index, value) entries, row r owns entries sp_off[r] ..
+                                             // sp_off[r + 1]; stride4 = 1, so that rows + r NAMES row r (never dereferenced); metric M_L2 / M_IP / M_L1
+    const uint64_t* sp_off = nullptr;        // sparse: [rows + 1]
+    uint32_t       sp_slots = 0;             // sparse: slots of a wave's left-hand table in LDS, a power of two >= 2 x the largest row
+    uint32_t       sp_lanes = 0;             // sparse: lanes per row, 4 / 16 / 64 (the corpus's entry-count class)
     uint32_t       m = 0, efc = 0, max_level = 1;
     int32_t*       nbr0 = nullptr;           // [n][2m] neighbour ids, -1 padded
     float*         dist0 = nullptr;          // [n][2m] their distances to the owner

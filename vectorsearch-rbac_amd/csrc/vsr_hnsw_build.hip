@@ -44,6 +44,14 @@
 // element's row is the "query" and is binary16 already.  The pre-pass compares the binary16 bytes, so +0.0 and -0.0 differ
 // (datumIsEqual on a halfvec).  Parity: pgvector's test/t/024_hnsw_halfvec_build_recall.pl floors (tests/test_gpu_hnsw_half.py).
 //
+// Sparse corpora (vsr_hnsw_build_sparse, sparsevec_l2_ops / sparsevec_ip_ops / sparsevec_cosine_ops / sparsevec_l1_ops): ROWS =
+// ROWS_SPARSE gives hb_distances K4s's lane mapping and arithmetic (sparse_graph_distances, vsr_sparseops.h).  The left-hand vector
+// -- the inserted element in the search, a candidate in hb_select, a target's neighbour in the link kernel -- is a hash table in the
+// wave's LDS that the wave rebuilds from the left-hand row whenever that row changes (sparse_left_load: sized once per build from
+// the corpus's largest row, at most 2048 slots = 16 KB).  Which slot an entry lands in may depend on lane timing; what a lookup
+// returns and the order of every sum do not, so the build stays deterministic.  No merging build: the pre-pass compares
+// fixed-stride rows.  Parity: pgvector's test/t/028_hnsw_sparsevec_build_recall.pl floors (tests/test_gpu_hnsw_sparse.py).
+//
 // Parity definition (tests/test_gpu_index.py): recall@20 at ef_search = 40 against the exact scan >= pgvector's TAP
 // thresholds on its own case (10 000 x 3-d: 0.99; inner product 0.97), and within 0.01 of that serial build's recall on
 // the same rows; and (tests/test_gpu_hnsw_build_model.py) graph identity with the batched model, as above.
@@ -59,6 +67,7 @@
 #include "vsr_topk.h"
 #include "vsr_bitops.h"
 #include "vsr_halfops.h"
+#include "vsr_sparseops.h"
 #include "vsr_hnsw_build.h"
 
 namespace vsr {
@@ -92,10 +101,20 @@ __device__ __forceinline__ const float4* hb_row(const HnswBuildParams& p, I e)
 
 // ROWS_BIT (a bit corpus, metric M_HAMMING / M_JACCARD): the lane mapping and arithmetic of K4b (bit_graph_distances, vsr_bitops.h)
 // ROWS_HALF (a halfvec corpus, metric M_L2 / M_IP): those of K4h (half_graph_distances, vsr_halfops.h)
+// ROWS_SPARSE (a sparse corpus, metric M_L2 / M_IP / M_L1): those of K4s (sparse_graph_distances, vsr_sparseops.h).  The left-hand
+// operand is a table in the wave's LDS (left: which row it holds), rebuilt here whenever `a` names another row
 template <bool IND, int ROWS>
-__device__ __forceinline__ void hb_distances(const HnswBuildParams& p, const float4* a, const int32_t* ids, int cnt, float* out, int lane)
+__device__ __forceinline__ void hb_distances(const HnswBuildParams& p, const float4* a, const int32_t* ids, int cnt, float* out, int lane,
+                                             SparseLeft* left = nullptr)
 {
-    if constexpr (ROWS == ROWS_BIT) {
+    if constexpr (ROWS == ROWS_SPARSE) {
+        sparse_left_load(*left, p.rows, p.sp_off, (int64_t) (a - p.rows), lane);      // (stride4 = 1: a names the row)
+        const uint32_t mask = p.sp_slots - 1u, shift = (uint32_t) __clz((int) p.sp_slots) + 1u;
+        sparse_graph_distances_metric(p.metric, p.rows, p.sp_off, p.sp_lanes, IND ? p.elem_row : nullptr, (lds_u64) left->tab, mask, shift,
+                                      left->q2, left->q1, ids, cnt, out, lane);
+        wave_sync();
+        return;
+    } else if constexpr (ROWS == ROWS_BIT) {
         const uint32_t G = bit_graph_lanes(p.stride4), gl = (uint32_t) lane & (G - 1u);
         const uint4* rows = reinterpret_cast<const uint4*>(p.rows);
         const uint4* qs = reinterpret_cast<const uint4*>(a);
@@ -162,7 +181,7 @@ __device__ __forceinline__ void hb_distances(const HnswBuildParams& p, const flo
 // scratch: ids[lm], nd[lm] in LDS.  Returns the number selected.
 template <bool IND, int ROWS>
 __device__ __forceinline__ int hb_select(const HnswBuildParams& p, const uint64_t* cand, int n, int lm, int32_t* sel, int32_t* wd,
-                                         int32_t* ids, float* nd, int* pruned, int lane)
+                                         int32_t* ids, float* nd, int* pruned, int lane, SparseLeft* left = nullptr)
 {
     if (n <= lm) {
         // "return c" (hnswutils.c:1071-1072): the candidates as HnswSearchLayer's w lists them, FURTHEST first
@@ -177,7 +196,7 @@ __device__ __forceinline__ int hb_select(const HnswBuildParams& p, const uint64_
         const float de = mono_to_float((uint32_t) (cand[i] >> 32));
         bool closer = true;
         if (nsel > 0) {
-            hb_distances<IND, ROWS>(p, hb_row<IND>(p, e), ids, nsel, nd, lane);
+            hb_distances<IND, ROWS>(p, hb_row<IND>(p, e), ids, nsel, nd, lane, left);
             bool bad = false;
             for (int j = lane; j < nsel; j += 64) bad |= nd[j] <= de;
             closer = __ballot(bad) == 0;
@@ -221,6 +240,11 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
     uint32_t* lv = reinterpret_cast<uint32_t*>(wd + p.caps);                  // [hash_slots] visited set
     const float4* q = hb_row<IND>(p, me);
     const int my_level = p.level[me];
+    SparseLeft left;                                                          // ROWS_SPARSE: the left-hand table, the last sp_slots * 8 bytes
+    if constexpr (ROWS == ROWS_SPARSE) {
+        left.tab = reinterpret_cast<uint64_t*>(smem + p.lds_per_wave - (size_t) p.sp_slots * 8);
+        left.slots = p.sp_slots;
+    }
 
     // the element's own lists start empty
     for (int lc = 0; lc <= my_level; ++lc) {
@@ -249,6 +273,17 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
         return false;
     };
     uint32_t count = 0, pushed = 0, first_open = 0;
+    // ROWS_SPARSE: S is bounded where pgvector's candidate heap is not.  A key that does not enter S, or falls off its end
+    // unexpanded, is lost for good only when it is as near as the furthest of W -- then the heap would still expand it (c.dist >
+    // f.dist is what ends the search).  Sparse rows make that common: every pair without a common index has inner product 0.
+    // Such a loss is reported (HB_ERR_CANDIDATES) and hnsw_build runs the build again with a longer S.  cur_ef: the beam of the
+    // layer search in progress
+    uint32_t cur_ef = 1;
+    bool lost = false;
+    auto as_near_as_w = [&](uint64_t key) -> bool {
+        const uint32_t wl = pushed < cur_ef ? pushed : cur_ef;
+        return mono_to_float((uint32_t) (key >> 32)) <= mono_to_float((uint32_t) (S[(wl < count ? wl : count) - 1] >> 32));
+    };
     auto insert = [&](uint64_t key) {
         uint32_t lo = 0, hi = count;
         while (lo < hi) {
@@ -256,6 +291,10 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
             if (S[mid] < key) lo = mid + 1; else hi = mid;
         }
         const uint32_t pos = lo;
+        if constexpr (ROWS == ROWS_SPARSE) {
+            if (pos >= p.caps) lost |= as_near_as_w(key);
+            else if (count == p.caps && X[p.caps - 1] == 0) lost |= as_near_as_w(S[p.caps - 1]);
+        }
         if (pos >= p.caps) return;
         const uint32_t last = count < p.caps ? count : p.caps - 1;
         for (int64_t base = (int64_t) ((last - 1) & ~63u); last > pos && base >= (int64_t) (pos & ~63u); base -= 64) {
@@ -275,6 +314,7 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
     // HnswSearchLayer (hnswutils.c:813-976) on layer lc with beam ef_: S holds the entry points on entry, W on exit
     auto search_layer = [&](int lc, uint32_t ef_) {
         const uint32_t lm = lc == 0 ? 2 * p.m : p.m;
+        cur_ef = ef_;
         clear_visited();
         for (uint32_t i = (uint32_t) lane; i < count; i += 64) (void) visit((uint32_t) S[i]);
         used = count;
@@ -311,7 +351,7 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
             used += (uint32_t) cnt;
             if (used * 4u > p.hash_slots * 3u) { overflow = true; break; }
             if (cnt == 0) continue;
-            hb_distances<IND, ROWS>(p, q, nb, cnt, nd, lane);
+            hb_distances<IND, ROWS>(p, q, nb, cnt, nd, lane, &left);
             for (int i = 0; i < cnt; ++i) {
                 const uint32_t e = (uint32_t) nb[i];
                 const float ed = nd[i];
@@ -330,7 +370,7 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
     // HnswFindElementNeighbors (hnswutils.c:1270-1346)
     if (lane == 0) nb[0] = p.entry;
     wave_sync();
-    hb_distances<IND, ROWS>(p, q, nb, 1, nd, lane);
+    hb_distances<IND, ROWS>(p, q, nb, 1, nd, lane, &left);
     insert(make_key(nd[0], (uint32_t) p.entry));
     for (int lc = p.entry_level; lc >= my_level + 1; --lc) {
         search_layer(lc, 1);
@@ -342,7 +382,7 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
         search_layer(lc, p.efc);
         const int lm = (int) (lc == 0 ? 2 * p.m : p.m);
         int pruned;
-        const int ns = hb_select<IND, ROWS>(p, S, (int) count, lm, sel, wd, nb, nd, &pruned, lane);
+        const int ns = hb_select<IND, ROWS>(p, S, (int) count, lm, sel, wd, nb, nd, &pruned, lane, &left);
         // AddConnections + the reverse edges HnswUpdateNeighborsInMemory will apply
         float* dl;
         int32_t* nl = hb_list(p, me, lc, &dl);
@@ -366,6 +406,8 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
         wave_sync();
     }
     if (overflow && lane == 0) atomicOr(p.err, HB_ERR_VISITED);
+    if constexpr (ROWS == ROWS_SPARSE)
+        if (lost && lane == 0) atomicOr(p.err, HB_ERR_CANDIDATES);
 }
 
 // ---- phase 2: reverse edges, sorted by (layer, target, source): the wave of a run's first record applies the whole
@@ -385,6 +427,11 @@ __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildPar
     const uint32_t owner = (uint32_t) key;
     const int lm = (int) (lc == 0 ? 2 * p.m : p.m);
     unsigned char* smem = smem_all + (size_t) wave * (HB_NBR * 32);
+    SparseLeft left;                                                          // ROWS_SPARSE: the waves' left-hand tables lie behind the four lists
+    if constexpr (ROWS == ROWS_SPARSE) {
+        left.tab = reinterpret_cast<uint64_t*>(smem_all + (size_t) 4 * (HB_NBR * 32) + (size_t) wave * p.sp_slots * 8);
+        left.slots = p.sp_slots;
+    }
     uint64_t* cand = reinterpret_cast<uint64_t*>(smem);                       // [lm + 1] (distance, element), sorted
     int32_t*  sel = reinterpret_cast<int32_t*>(cand + HB_NBR);
     int32_t*  wd = sel + HB_NBR;
@@ -427,7 +474,7 @@ __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildPar
         for (int j = lane; j < n; j += 64) cand[sel[j]] = mine[nm++];
         wave_sync();
         int pruned;
-        (void) hb_select<IND, ROWS>(p, cand, n, lm, sel, wd, ids, nd, &pruned, lane);
+        (void) hb_select<IND, ROWS>(p, cand, n, lm, sel, wd, ids, nd, &pruned, lane, &left);
         const uint32_t pe = (uint32_t) cand[pruned];
         if (pe != e) {                                                        // the new element replaces the pruned one
             for (int j = lane; j < lm; j += 64)
@@ -464,13 +511,24 @@ static hipError_t build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sort_
     HnswBuildParams q = p;
     q.rec_key = keys.Current();
     q.rec_val = vals.Current();
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_build_link_kernel<IND, ROWS>), dim3((p.rec_cap + 3) / 4), dim3(256), (size_t) 4 * HB_NBR * 32, s, q);
+    const size_t lds2 = (size_t) 4 * HB_NBR * 32 + (ROWS == ROWS_SPARSE ? (size_t) 4 * p.sp_slots * 8 : 0);
+    if (lds2 > 64 * 1024) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_build_link_kernel<IND, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds2);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_build_link_kernel<IND, ROWS>), dim3((p.rec_cap + 3) / 4), dim3(256), lds2, s, q);
     return hipGetLastError();
 }
 
 hipError_t vsr_hnsw_build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt, uint64_t* d_val_alt,
                                 hipStream_t s)
 {
+    if (p.sparse) {                                                           // (no merging build over sparse rows: element e is row e)
+        if (p.elem_row || p.stride4 != 1 || p.sp_slots < 2 || (p.sp_slots & (p.sp_slots - 1)) != 0 ||
+            (p.sp_lanes != 4 && p.sp_lanes != 16 && p.sp_lanes != 64))
+            return hipErrorInvalidValue;
+        return build_batch<false, ROWS_SPARSE>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
+    }
     if (p.bits)
         return p.elem_row ? build_batch<true, ROWS_BIT>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s)
                           : build_batch<false, ROWS_BIT>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);

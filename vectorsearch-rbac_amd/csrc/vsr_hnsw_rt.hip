@@ -76,8 +76,17 @@ static const char* const HNSW_HALF_ENTRY =
     "the graph of a halfvec corpus is loaded with vsr_hnsw_load_half and built with vsr_hnsw_build_half (the halfvec_l2_ops / halfvec_ip_ops / "
     "halfvec_cosine_ops opclasses)";
 
-// vsr_hnsw_load (expect = F32), vsr_hnsw_load_half (HALF) and vsr_hnsw_load_bit (BIT; bit_metric: the opclass): `expect` is the
-// corpus format the entry point is for
+// what a sparsevec entry point asks of its corpus (who: the entry point): checkValue of the sparsevec opclasses, hnswutils.c:1352-1361
+static int hnsw_sparse_opclass(const vsr_corpus* c, const char* who)
+{
+    if (c->format != RowFormat::SPARSE) return fail(VSR_ERR_INVALID, "%s: the corpus is not a sparse corpus", who);
+    if (c->sp_max_nnz > (uint32_t) HNSW_SPARSE_MAX_NNZ)
+        return fail(VSR_ERR_UNSUPPORTED, "sparsevec cannot have more than %d non-zero elements for hnsw index", HNSW_SPARSE_MAX_NNZ);
+    return VSR_OK;
+}
+
+// vsr_hnsw_load (expect = F32), vsr_hnsw_load_half (HALF), vsr_hnsw_load_bit (BIT; bit_metric: the opclass) and
+// vsr_hnsw_load_sparse (SPARSE): `expect` is the corpus format the entry point is for
 static int hnsw_load(vsr_corpus* c, RowFormat expect, int bit_metric, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
                      const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
                      int32_t n_upper, int32_t max_level, vsr_hnsw** out, const char* who)
@@ -93,8 +102,14 @@ static int hnsw_load(vsr_corpus* c, RowFormat expect, int bit_metric, int m, int
         int rc = hnsw_half_opclass(c, who);
         if (rc) return rc;
     }
+    if (expect == RowFormat::SPARSE) {
+        int rc = hnsw_sparse_opclass(c, who);
+        if (rc) return rc;
+    }
     if (c->format == RowFormat::HALF && expect != RowFormat::HALF) return fail(VSR_ERR_UNSUPPORTED, "%s: %s", who, HNSW_HALF_ENTRY);
-    if (c->format == RowFormat::SPARSE) return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
+    // (stale since K4s: the graph of a sparse corpus is loaded with vsr_hnsw_load_sparse; the text is pinned by tests)
+    if (c->format == RowFormat::SPARSE && expect != RowFormat::SPARSE)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
     if (c->format == RowFormat::BIT && expect != RowFormat::BIT)
         return fail(VSR_ERR_UNSUPPORTED, "%s: the graph of a bit corpus is loaded with vsr_hnsw_load_bit (the bit_hamming_ops / bit_jaccard_ops opclasses)", who);
     if (m < 2 || m > 100)        /* reloption m: 2 .. HNSW_MAX_M (hnsw.h:36-40) */
@@ -169,10 +184,24 @@ extern "C" int vsr_hnsw_load_half(vsr_corpus* c, int m, int32_t n_elem, int32_t 
     return hnsw_load(c, RowFormat::HALF, 0, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, out, "vsr_hnsw_load_half");
 }
 
-// per-wave LDS of the build's search kernel (hnsw_build_search_kernel's carve-up) with `slots` visited-table entries
-static size_t hnsw_build_lds_per_wave(uint32_t caps, uint32_t slots)
+extern "C" int vsr_hnsw_load_sparse(vsr_corpus* c, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
+                                    const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
+                                    int32_t n_upper, int32_t max_level, vsr_hnsw** out)
 {
-    return ((size_t) caps * 8 + ((caps + 15) & ~15u) + (size_t) HB_NBR * 12 + (size_t) caps * 4 + (size_t) slots * 4 + 15) & ~(size_t) 15;
+    return hnsw_load(c, RowFormat::SPARSE, 0, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, out, "vsr_hnsw_load_sparse");
+}
+
+// per-wave LDS of the build's search kernel (hnsw_build_search_kernel's carve-up) with `slots` visited-table entries and, a sparse
+// build, the wave's left-hand table of sp_slots (index, value) slots behind them
+static size_t hnsw_build_lds_per_wave(uint32_t caps, uint32_t slots, uint32_t sp_slots = 0)
+{
+    return (((size_t) caps * 8 + ((caps + 15) & ~15u) + (size_t) HB_NBR * 12 + (size_t) caps * 4 + (size_t) slots * 4 + 15) & ~(size_t) 15) +
+           (size_t) sp_slots * 8;
+}
+// slots of a sparse build's left-hand tables: sized once from the corpus's largest row (<= 1000 non-zeros: <= 2048 slots, 16 KB)
+static uint32_t hnsw_build_sparse_slots(const vsr_corpus* c, RowFormat expect)
+{
+    return c && expect == RowFormat::SPARSE && c->format == RowFormat::SPARSE ? sparse_slots_for_nnz(c->sp_max_nnz) : 0u;
 }
 
 // CREATE INDEX ... USING hnsw on the GPU (vsr_hnsw_build.hip): batched insertion over the corpus's rows, levels from a seeded
@@ -181,10 +210,11 @@ static size_t hnsw_build_lds_per_wave(uint32_t caps, uint32_t slots)
 // expect: the corpus format the entry point is for -- BIT (vsr_hnsw_build_bit; metric is the opclass), HALF (vsr_hnsw_build_half) or
 // F32; the kernels take that row format.
 // One attempt with a visited table of *slots entries (0: the default for m and ef_construction, written back).  *guard: the
-// build's guard-word bits (HB_ERR_VISITED / HB_ERR_RECORDS) when a kernel set one; the partial index is then freed, the bits
+// build's guard-word bits (HB_ERR_VISITED / HB_ERR_RECORDS / HB_ERR_CANDIDATES) when a kernel set one (caps: entries of the sorted
+// candidate array, at least ef_construction + 2 m); the partial index is then freed, the bits
 // are cleared from the session's word, *out stays NULL and the return value is VSR_OK: hnsw_build decides what follows.
 static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out,
-                           const char* who, uint32_t* slots_io, uint32_t* guard)
+                           const char* who, uint32_t* slots_io, uint32_t caps, uint32_t* guard)
 {
     if (!c || !out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
     *out = nullptr;
@@ -196,16 +226,26 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
         int rc = hnsw_half_opclass(c, who);
         if (rc) return rc;
     }
+    if (expect == RowFormat::SPARSE) {
+        int rc = hnsw_sparse_opclass(c, who);
+        if (rc) return rc;
+    }
     if (flags & ~(uint32_t) VSR_HNSW_BUILD_MERGE_DUPLICATES) return fail(VSR_ERR_INVALID, "%s: unknown flag bits 0x%x", who, flags);
+    if (expect == RowFormat::SPARSE && (flags & VSR_HNSW_BUILD_MERGE_DUPLICATES))
+        return fail(VSR_ERR_UNSUPPORTED, "%s: VSR_HNSW_BUILD_MERGE_DUPLICATES is not supported over a sparse corpus (the pre-pass compares fixed-stride rows)", who);
     if (c->base) return fail(VSR_ERR_INVALID, "%s: the corpus is a view", who);
     if (c->format == RowFormat::HALF && expect != RowFormat::HALF) return fail(VSR_ERR_UNSUPPORTED, "%s: %s", who, HNSW_HALF_ENTRY);
-    if (c->format == RowFormat::SPARSE) return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
+    // (stale since K4s: the graph of a sparse corpus is built with vsr_hnsw_build_sparse; the text is pinned by tests)
+    if (c->format == RowFormat::SPARSE && expect != RowFormat::SPARSE)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: a sparsevec corpus has no index path yet (the sparsevec_*_ops HNSW opclasses)", who);
     if (c->format == RowFormat::BIT && expect != RowFormat::BIT)
         return fail(VSR_ERR_UNSUPPORTED, "%s: the graph of a bit corpus is built with vsr_hnsw_build_bit (the bit_hamming_ops / bit_jaccard_ops opclasses)", who);
     if (m < 2 || m > 100) return fail(VSR_ERR_UNSUPPORTED, "%s: m must be between 2 and 100 (got %d)", who, m);
     if (ef_construction < 4 || ef_construction > 1000 || ef_construction < 2 * m)      /* hnsw.c:62-63, hnswbuild.c:677-679 */
         return fail(VSR_ERR_UNSUPPORTED, "%s: ef_construction must be between 4 and 1000 and at least 2 * m (got %d)", who, ef_construction);
-    if (expect != RowFormat::BIT && metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)
+    if (expect == RowFormat::SPARSE && (metric < VSR_METRIC_L2 || metric > VSR_METRIC_L1))
+        return fail(VSR_ERR_INVALID, "%s: metric %d is not an operator class of sparsevec (0: sparsevec_l2_ops, 1: sparsevec_ip_ops, 2: sparsevec_cosine_ops, 3: sparsevec_l1_ops)", who, metric);
+    if (expect != RowFormat::BIT && expect != RowFormat::SPARSE && metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)
         return fail(VSR_ERR_UNSUPPORTED, "%s: L2, inner product and cosine operator classes only", who);
     vsr_ctx* ctx = c->ctx;
     HIPCHK(hipSetDevice(ctx->device));
@@ -314,6 +354,14 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
         bp.metric = metric == VSR_METRIC_JACCARD ? M_JACCARD : M_HAMMING;
         bp.row_pop = c->d_norm2;
     }
+    if (expect == RowFormat::SPARSE) {
+        bp.sparse = 1;
+        bp.stride4 = 1;                                       // rows + r names row r (vsr_hnsw_build.h)
+        bp.metric = metric == VSR_METRIC_L2 ? M_L2 : metric == VSR_METRIC_L1 ? M_L1 : M_IP;
+        bp.sp_off = c->d_sp_off;
+        bp.sp_slots = hnsw_build_sparse_slots(c, expect);
+        bp.sp_lanes = (uint32_t) c->shape.lpr;
+    }
     bp.m = (uint32_t) m;
     bp.efc = (uint32_t) ef_construction;
     bp.max_level = (uint32_t) max_level;
@@ -324,7 +372,7 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
     bp.up_dist = d_up_dist;
     bp.level = h->d_level;
     bp.elem_row = merge ? h->d_elem_row : nullptr;
-    bp.caps = (uint32_t) (ef_construction + 2 * m);
+    bp.caps = std::max(caps, (uint32_t) (ef_construction + 2 * m));
     uint32_t slots = *slots_io;
     if (slots == 0) {
         slots = 4096;
@@ -332,7 +380,7 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
         *slots_io = slots;
     }
     bp.hash_slots = slots;
-    const size_t per = hnsw_build_lds_per_wave(bp.caps, slots);
+    const size_t per = hnsw_build_lds_per_wave(bp.caps, slots, bp.sp_slots);
     if (per > HN_LDS_BUDGET) return bail(fail(VSR_ERR_UNSUPPORTED, "%s: ef_construction = %d with m = %d does not fit the LDS", who, ef_construction, m));
     bp.lds_per_wave = (uint32_t) per;
     bp.wpb = (uint32_t) std::min<size_t>(4, HN_LDS_BUDGET / per);
@@ -389,9 +437,9 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
     // this build's: they leave the session's guard word here, so that a later vsr_screening_check is not poisoned
     uint32_t word = 0;
     HB_CHK(hipMemcpy(&word, bp.err, sizeof word, hipMemcpyDeviceToHost));
-    if (word & (HB_ERR_VISITED | HB_ERR_RECORDS)) {
-        *guard = word & (HB_ERR_VISITED | HB_ERR_RECORDS);
-        word &= ~(HB_ERR_VISITED | HB_ERR_RECORDS);
+    if (word & (HB_ERR_VISITED | HB_ERR_RECORDS | HB_ERR_CANDIDATES)) {
+        *guard = word & (HB_ERR_VISITED | HB_ERR_RECORDS | HB_ERR_CANDIDATES);
+        word &= ~(HB_ERR_VISITED | HB_ERR_RECORDS | HB_ERR_CANDIDATES);
         HB_CHK(hipMemcpy(bp.err, &word, sizeof word, hipMemcpyHostToDevice));
         return bail(VSR_OK);
     }
@@ -423,6 +471,9 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
 // run again with a table twice as large, as long as one fits the LDS; dropped reverse edges are an error.
 // VSR_HNSW_BUILD_VISITED_SLOTS=n (development / tests; a power of two, 256 .. 32768; read at every call) sets the INITIAL table
 // size, so that the restart can be exercised on a small corpus.
+// A sparse build also restarts, with a candidate array twice as long, when a layer search lost an unexpanded candidate as near as
+// the furthest of W (HB_ERR_CANDIDATES, vsr_hnsw_build.hip): pgvector's candidate heap has no bound, and rows without a common
+// index all have inner product 0, so such ties outgrow ef_construction + 2 m entries.
 static int hnsw_build(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out,
                       const char* who)
 {
@@ -436,16 +487,24 @@ static int hnsw_build(vsr_corpus* c, RowFormat expect, int m, int ef_constructio
         }
         slots = (uint32_t) v;
     }
+    uint32_t caps = (uint32_t) (ef_construction + 2 * m);
     for (;;) {
         uint32_t guard = 0;
-        const int rc = hnsw_build_once(c, expect, m, ef_construction, metric, seed, flags, out, who, &slots, &guard);
+        const int rc = hnsw_build_once(c, expect, m, ef_construction, metric, seed, flags, out, who, &slots, caps, &guard);
         if (rc != VSR_OK || guard == 0) return rc;
         if (guard & HB_ERR_RECORDS)
             return fail(VSR_ERR_UNSUPPORTED, "%s: reverse edges were dropped at ef_construction = %d with m = %d: the graph would be incomplete", who,
                         ef_construction, m);
+        if (guard & HB_ERR_CANDIDATES) {
+            if (hnsw_build_lds_per_wave(caps * 2u, slots, hnsw_build_sparse_slots(c, expect)) > HN_LDS_BUDGET)
+                return fail(VSR_ERR_UNSUPPORTED,
+                            "%s: a layer search at ef_construction = %d with m = %d holds more than %u candidates of equal distance and no longer "
+                            "candidate array fits the LDS", who, ef_construction, m, caps);
+            caps *= 2u;
+            if (!(guard & HB_ERR_VISITED)) continue;
+        }
         // HB_ERR_VISITED
-        const uint32_t caps = (uint32_t) (ef_construction + 2 * m);
-        if (slots >= 32768u || hnsw_build_lds_per_wave(caps, slots * 2u) > HN_LDS_BUDGET)
+        if (slots >= 32768u || hnsw_build_lds_per_wave(caps, slots * 2u, hnsw_build_sparse_slots(c, expect)) > HN_LDS_BUDGET)
             return fail(VSR_ERR_UNSUPPORTED,
                         "%s: a layer search at ef_construction = %d with m = %d fills its visited table of %u entries and no larger one fits the LDS",
                         who, ef_construction, m, slots);
@@ -471,6 +530,11 @@ extern "C" int vsr_hnsw_build_bit(vsr_corpus* c, int m, int ef_construction, int
 extern "C" int vsr_hnsw_build_half(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out)
 {
     return hnsw_build(c, RowFormat::HALF, m, ef_construction, metric, seed, flags, out, "vsr_hnsw_build_half");
+}
+
+extern "C" int vsr_hnsw_build_sparse(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out)
+{
+    return hnsw_build(c, RowFormat::SPARSE, m, ef_construction, metric, seed, flags, out, "vsr_hnsw_build_sparse");
 }
 
 // device memory of the graph arrays of an index (the corpus is counted by vsr_corpus_device_bytes); any index.  The row format
@@ -580,11 +644,27 @@ struct HnswIterLaunch {
 
 // The queries of a launch in device memory: rows of `stride` floats.  A bit index: the STAGED bit strings (hnsw_stage_bits),
 // stride / 4 16-byte chunks each, and their popcounts.
+// A sparse index: the STAGED tables (hnsw_stage_sparse) of sp_slots slots each and their double totals; q is not read.
 struct HnswQueries {
     const float* q;
     uint32_t     stride;
     const float* pop;
-    HnswQueries from_query(size_t q0) const { return {q + q0 * stride, stride, pop ? pop + q0 : nullptr}; }
+    const uint2*  sp_tab = nullptr;
+    const double* sp_qtot = nullptr;
+    uint32_t      sp_slots = 0;
+    HnswQueries from_query(size_t q0) const
+    {
+        return {q ? q + q0 * stride : nullptr, stride, pop ? pop + q0 : nullptr, sp_tab ? sp_tab + q0 * sp_slots : nullptr,
+                sp_qtot ? sp_qtot + 2 * q0 : nullptr, sp_slots};
+    }
+};
+
+// the queries of a sparse entry point as the caller holds them: CSR arrays in host or in device memory, and the longest of them
+struct SparseCsr {
+    const int64_t* indptr;
+    const int32_t* indices;
+    const float*   values;
+    uint32_t       max_nnz;
 };
 
 // One launch over queries resident in device memory, results into device arrays (out.keys: a bit index only, the raw keys of
@@ -609,6 +689,13 @@ static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const HnswQueries& qs, int nq,
         p.key_row_offset = (uint32_t) c->row_offset;
     }
     if (h->format == RowFormat::HALF) p.q_chunks = p.stride4 > 64u ? p.stride4 : 0u;   // K4h: rows past 64 chunks keep the query in LDS
+    if (h->format == RowFormat::SPARSE) {                   // K4s
+        p.sp_off = c->d_sp_off;
+        p.sp_tab = qs.sp_tab;
+        p.sp_qtot = qs.sp_qtot;
+        p.sp_slots = qs.sp_slots;
+        p.sp_lanes = (uint32_t) c->shape.lpr;
+    }
     p.dim = (uint32_t) c->dim;
     p.nq = (uint32_t) nq;
     p.n_elem = (uint32_t) h->n_elem;
@@ -628,11 +715,20 @@ static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const HnswQueries& qs, int nq,
     p.ef = (uint32_t) ef;
     p.k = (uint32_t) k;
     p.caps = (uint32_t) (2 * ef + 2 * h->m + 64);
+    // K4s: the wave keeps its query's table in LDS (sp_slots / 2 chunks in front of the visited set) when the table fits beside S at
+    // one query per workgroup; otherwise the table is read where staging wrote it (K1s's GLOBAL_TAB choice)
+    auto sparse_table = [&]() {
+        if (h->format != RowFormat::SPARSE) return;
+        p.q_chunks = p.sp_slots / 2u;
+        if (hnsw_lds_fixed(p.caps, p.q_chunks) + (iter ? (size_t) HN_HIST * 4 : 0) > HN_LDS_BUDGET) p.q_chunks = 0u;
+    };
+    sparse_table();
     if (iter) {                                             // (the LDS hash is sized by ef, not by the scan: never used here)
         const char* env = getenv("VSR_HNSW_VISITED");
         const bool glob = force_global || (env && !strcmp(env, "global"));
         if (!hnsw_plan_iterative(p, glob)) {
             p.caps = (uint32_t) (ef + 2 * h->m + 64);
+            sparse_table();
             if (!hnsw_plan_iterative(p, glob))
                 return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_search_iterative: ef_search = %d does not fit the LDS", ef);
         }
@@ -644,6 +740,7 @@ static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const HnswQueries& qs, int nq,
         p.cap_d = iter->cap_d;
     } else if (!hnsw_plan(p, force_global)) {               // S does not fit beside anything: a shorter tail behind W
         p.caps = (uint32_t) (ef + 2 * h->m + 64);
+        sparse_table();
         if (!hnsw_plan(p, force_global)) return fail(VSR_ERR_UNSUPPORTED, "vsr_hnsw_search: ef_search = %d does not fit the LDS", ef);
     }
     // development / tests: VSR_HNSW_VISITED=hash[:slots] forces the LDS hash table (with `slots` entries, a power of two) on a
@@ -688,7 +785,13 @@ static int hnsw_check(vsr_hnsw* h, const void* queries, int nq, int dim, int k, 
                       const char* who, RowFormat entry)
 {
     if (!h) return fail(VSR_ERR_INVALID, "%s: index is NULL", who);
-    const bool bit_index = h->format == RowFormat::BIT;
+    const bool bit_index = h->format == RowFormat::BIT, sparse_index = h->format == RowFormat::SPARSE;
+    if (entry == RowFormat::SPARSE && !sparse_index)
+        return fail(VSR_ERR_INVALID, "%s: the index is not over a sparse corpus (it is searched with vsr_hnsw_search* or vsr_hnsw_search_bit*)", who);
+    if (entry != RowFormat::SPARSE && sparse_index)
+        return fail(VSR_ERR_UNSUPPORTED,
+                    "%s: the index is over a sparsevec corpus: it is searched with vsr_hnsw_search_sparse* (vsr_hnsw_search_sparse, "
+                    "vsr_hnsw_search_sparse_device, vsr_hnsw_search_sparse_iterative, vsr_hnsw_search_sparse_iterative_device)", who);
     if (entry == RowFormat::BIT && !bit_index)
         return fail(VSR_ERR_INVALID, "%s: the index is not over a bit corpus (it is searched with vsr_hnsw_search*)", who);
     if (entry != RowFormat::BIT && bit_index)
@@ -698,7 +801,8 @@ static int hnsw_check(vsr_hnsw* h, const void* queries, int nq, int dim, int k, 
     if (bit_index && metric != h->bit_metric)               // an index belongs to one opclass: the metric only catches misuse
         return fail(VSR_ERR_INVALID, "%s: the index was made for %s, the search asks for %s", who, bit_metric_name(h->bit_metric),
                     bit_metric_name(metric));
-    if (metric == VSR_METRIC_L1) return fail(VSR_ERR_UNSUPPORTED, "%s: L1 graphs are not supported", who);
+    if (metric == VSR_METRIC_L1 && !sparse_index)           // (sparsevec_l1_ops is the one L1 opclass of hnsw)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: L1 graphs are not supported", who);
     if (ef < 1 || ef > 5000)      /* hnsw.ef_search: 1 .. HNSW_MAX_EF_SEARCH (hnsw.c:86-89, hnsw.h:44) */
         return fail(VSR_ERR_INVALID, "%s: ef_search must be between 1 and 5000 (got %d)", who, ef);
     return VSR_OK;
@@ -744,6 +848,40 @@ static int hnsw_stage_bits(vsr_hnsw* h, vsr_ctx* ctx, const uint8_t* d_src, int 
     return VSR_OK;
 }
 
+// Query staging of a sparse index: nq queries as CSR arrays in device memory -> one open-addressing table of `slots` (index, value)
+// slots per query (slots: a power of two >= 2 x max_nnz, the same for every query of the call), their double totals Q2 / Q1 and
+// |q|^2, in h->d_qb (stage_sparse_kernel, vsr_sparse.hip: the staging of vsr_search_sparse).  A query longer than max_nnz becomes an
+// empty table and sets SPARSE_ERR_QUERY in the session's guard word.  One launch on the context's stream.
+static int hnsw_stage_sparse(vsr_hnsw* h, vsr_ctx* ctx, const SparseCsr& d, int nq, HnswQueries& qs)
+{
+    const vsr_corpus* c = h->corpus;
+    const uint32_t slots = sparse_slots_for_nnz(d.max_nnz);
+    const size_t o_tot = align_up((size_t) nq * slots * sizeof(uint2), 256), o_norm = align_up(o_tot + (size_t) nq * 2 * sizeof(double), 256),
+                 o_flags = align_up(o_norm + (size_t) nq * 4, 256), o_tau = align_up(o_flags + (size_t) nq * 4, 256),
+                 total = o_tau + (size_t) nq * 8;
+    int rc = h->d_qb.reserve(total);
+    if (rc) return rc;
+    char* w = h->d_qb.as<char>();
+    SparseStageParams st{};
+    st.indptr = d.indptr;
+    st.indices = d.indices;
+    st.values = d.values;
+    st.nq = (uint32_t) nq;
+    st.dim = (uint32_t) c->dim;
+    st.max_nnz = d.max_nnz;
+    st.slots = slots;
+    st.shift = 32u - (uint32_t) __builtin_ctz(slots);
+    st.tab = reinterpret_cast<uint2*>(w);
+    st.qtot = reinterpret_cast<double*>(w + o_tot);
+    st.q_norm2 = reinterpret_cast<float*>(w + o_norm);
+    st.flags = reinterpret_cast<int32_t*>(w + o_flags);     // (the staging kernel clears a flag and a seed word per query: unused here)
+    st.tau = reinterpret_cast<uint64_t*>(w + o_tau);
+    st.err = ctx->err_word();
+    HIPCHK(launch_stage_sparse(st, ctx->stream));
+    qs = {nullptr, 0u, nullptr, reinterpret_cast<const uint2*>(w), reinterpret_cast<const double*>(w + o_tot), slots};
+    return VSR_OK;
+}
+
 // per-query permission bitmaps as a device array of pointers (nullptr entries: no filter); any_filter = false: none at all
 static int hnsw_bitmaps(vsr_hnsw* h, vsr_ctx* ctx, const vsr_filter* const* filters, int n, bool& any_filter)
 {
@@ -777,11 +915,12 @@ static int hnsw_doc_scratch(vsr_hnsw* h, int nq, int k, int32_t*& d_doc)
 // staged (hnsw_stage_bits) in front of every launch.
 struct HnswEntry {
     const char* who;
-    RowFormat   queries;                                    // F32 or BIT
+    RowFormat   queries;                                    // F32, BIT or SPARSE (then the query pointer addresses a SparseCsr)
     size_t bytes(int dim) const { return format_query_bytes(queries, dim); }
-    // queries resident at d_q -> what hnsw_launch takes (bit: one staging launch on the stream)
+    // queries resident at d_q -> what hnsw_launch takes (bit, sparse: one staging launch on the stream)
     int resident(vsr_hnsw* h, vsr_ctx* ctx, const void* d_q, int nq, int dim, HnswQueries& qs) const
     {
+        if (queries == RowFormat::SPARSE) return hnsw_stage_sparse(h, ctx, *static_cast<const SparseCsr*>(d_q), nq, qs);
         qs = {static_cast<const float*>(d_q), (uint32_t) dim, nullptr};
         return queries == RowFormat::BIT ? hnsw_stage_bits(h, ctx, static_cast<const uint8_t*>(d_q), nq, qs) : VSR_OK;
     }
@@ -863,7 +1002,62 @@ static int hnsw_host_search(vsr_hnsw* h, const void* queries, size_t qbytes, int
     return VSR_OK;
 }
 
-// vsr_hnsw_search / vsr_hnsw_search_bit
+// hnsw_host_search over CSR queries in host memory (validated by the entry point): the three arrays travel to h->d_q, `launch`
+// takes a SparseCsr of device pointers; the re-run's queries are the flagged ones gathered into a CSR triple of their own.
+template <class Launch>
+static int hnsw_host_search_sparse(vsr_hnsw* h, const SparseCsr& q, int nq, int k, const vsr_filter* const* filters, const Outputs& out,
+                                   int64_t* out_extra, Launch launch)
+{
+    vsr_ctx* ctx = h->corpus->ctx;
+    const ResultBlock rb(nq, k, true);
+    int rc;
+    if ((rc = h->d_out.reserve(rb.total))) return rc;
+    if ((rc = h->h_out.reserve(rb.total))) return rc;
+    char* d = h->d_out.as<char>();
+    char* hh = h->h_out.as<char>();
+    // ptr: n + 1 offsets starting at 0; idx / val: the entries they address
+    auto run = [&](const int64_t* ptr, const int32_t* idx, const float* val, int n, const vsr_filter* const* fs, int tier) -> int {
+        const size_t nnz = (size_t) ptr[n];
+        const size_t o_idx = align_up(((size_t) n + 1) * 8, 256), o_val = align_up(o_idx + nnz * 4, 256), total = o_val + nnz * 4;
+        int r = h->d_q.reserve(total);
+        if (r) return r;
+        char* dq = h->d_q.as<char>();
+        HIPCHK(hipMemcpyAsync(dq, ptr, ((size_t) n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (nnz) {
+            HIPCHK(hipMemcpyAsync(dq + o_idx, idx, nnz * 4, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(hipMemcpyAsync(dq + o_val, val, nnz * 4, hipMemcpyHostToDevice, ctx->stream));
+        }
+        const SparseCsr dev{reinterpret_cast<const int64_t*>(dq), reinterpret_cast<const int32_t*>(dq + o_idx),
+                            reinterpret_cast<const float*>(dq + o_val), q.max_nnz};
+        r = launch(&dev, n, fs, tier, rb.arrays(d), rb.column<int64_t>(d, rb.o_extra), rb.column<int32_t>(d, rb.o_status));
+        if (r) return r;
+        HIPCHK(hipMemcpyAsync(hh, d, rb.total, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return VSR_OK;
+    };
+    std::vector<int64_t> ptr((size_t) nq + 1);
+    for (int i = 0; i <= nq; ++i) ptr[(size_t) i] = q.indptr[i] - q.indptr[0];
+    if ((rc = run(ptr.data(), q.indices + q.indptr[0], q.values + q.indptr[0], nq, filters, 0))) return rc;
+    rb.copy_out_all(hh, out, out_extra);
+    const std::vector<int> redo = rb.flagged(hh, (size_t) nq);
+    if (redo.empty()) return VSR_OK;
+    std::vector<int64_t> ptr2(redo.size() + 1, 0);
+    std::vector<int32_t> idx2;
+    std::vector<float> val2;
+    std::vector<const vsr_filter*> f2(redo.size(), nullptr);
+    for (size_t j = 0; j < redo.size(); ++j) {
+        const int64_t b = q.indptr[redo[j]], e = q.indptr[redo[j] + 1];
+        idx2.insert(idx2.end(), q.indices + b, q.indices + e);
+        val2.insert(val2.end(), q.values + b, q.values + e);
+        ptr2[j + 1] = ptr2[j] + (e - b);
+        if (filters) f2[j] = filters[redo[j]];
+    }
+    if ((rc = run(ptr2.data(), idx2.data(), val2.data(), (int) redo.size(), f2.data(), 1))) return rc;
+    for (size_t j = 0; j < redo.size(); ++j) rb.patch_one(hh, j, (size_t) redo[j], out, out_extra);
+    return VSR_OK;
+}
+
+// vsr_hnsw_search / vsr_hnsw_search_bit / vsr_hnsw_search_sparse (then `queries` addresses a SparseCsr of host arrays)
 static int hnsw_search_host(const HnswEntry& en, vsr_hnsw* h, const void* queries, int nq, int dim, int k, int ef, int metric,
                             const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc, int64_t* out_row, float* out_dist,
                             int32_t* out_cnt, int64_t* out_visited)
@@ -876,17 +1070,19 @@ static int hnsw_search_host(const HnswEntry& en, vsr_hnsw* h, const void* querie
     vsr_ctx* ctx = h->corpus->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     // tier 1: queries whose LDS visited table overflowed (big graphs only) are re-run with the global bitmap
-    return hnsw_host_search(h, queries, en.bytes(dim), nq, k, filters, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr}, out_visited,
-                            [&](const void* d_q, int n, const vsr_filter* const* fs, int tier, const Outputs& res, int64_t* d_vis,
-                                int32_t* d_status) -> int {
-                                bool any_filter = false;
-                                int r = hnsw_bitmaps(h, ctx, fs, n, any_filter);
-                                if (r) return r;
-                                HnswQueries qs;
-                                if ((r = en.resident(h, ctx, d_q, n, dim, qs))) return r;
-                                return hnsw_launch(h, ctx, qs, n, k, ef, metric, any_filter ? h->d_bm.as<const uint64_t*>() : nullptr,
-                                                   tier == 1, res, d_vis, d_status);
-                            });
+    const auto launch = [&](const void* d_q, int n, const vsr_filter* const* fs, int tier, const Outputs& res, int64_t* d_vis,
+                            int32_t* d_status) -> int {
+        bool any_filter = false;
+        int r = hnsw_bitmaps(h, ctx, fs, n, any_filter);
+        if (r) return r;
+        HnswQueries qs;
+        if ((r = en.resident(h, ctx, d_q, n, dim, qs))) return r;
+        return hnsw_launch(h, ctx, qs, n, k, ef, metric, any_filter ? h->d_bm.as<const uint64_t*>() : nullptr, tier == 1, res, d_vis, d_status);
+    };
+    const Outputs out{out_blk, out_doc, out_row, out_dist, out_cnt, nullptr};
+    if (en.queries == RowFormat::SPARSE)
+        return hnsw_host_search_sparse(h, *static_cast<const SparseCsr*>(queries), nq, k, filters, out, out_visited, launch);
+    return hnsw_host_search(h, queries, en.bytes(dim), nq, k, filters, out, out_visited, launch);
 }
 
 extern "C" int vsr_hnsw_search(vsr_hnsw* h, const float* queries, int nq, int dim, int k, int ef, int metric,
@@ -1012,14 +1208,17 @@ static int hnsw_iterative_host(const HnswEntry& en, vsr_hnsw* h, const void* que
     HIPCHK(hipSetDevice(ctx->device));
     // tier 1: queries whose D overflowed, again with room for every element (an element is in at most one of D, W, emitted)
     const uint32_t cap_d[2] = {hnsw_discard_cap(h, ef, max_scan_tuples), (uint32_t) std::max(h->n_elem, 1)};
-    return hnsw_host_search(h, queries, en.bytes(dim), nq, k, filters, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr}, out_tuples,
-                            [&](const void* d_q, int n, const vsr_filter* const* fs, int tier, const Outputs& res, int64_t* d_tup,
-                                int32_t* d_status) -> int {
-                                HnswQueries qs;
-                                int r = en.resident(h, ctx, d_q, n, dim, qs);
-                                if (r) return r;
-                                return hnsw_iter_run(h, qs, n, k, ef, metric, fs, mode, max_scan_tuples, cap_d[tier], res, d_tup, d_status);
-                            });
+    const auto launch = [&](const void* d_q, int n, const vsr_filter* const* fs, int tier, const Outputs& res, int64_t* d_tup,
+                            int32_t* d_status) -> int {
+        HnswQueries qs;
+        int r = en.resident(h, ctx, d_q, n, dim, qs);
+        if (r) return r;
+        return hnsw_iter_run(h, qs, n, k, ef, metric, fs, mode, max_scan_tuples, cap_d[tier], res, d_tup, d_status);
+    };
+    const Outputs out{out_blk, out_doc, out_row, out_dist, out_cnt, nullptr};
+    if (en.queries == RowFormat::SPARSE)
+        return hnsw_host_search_sparse(h, *static_cast<const SparseCsr*>(queries), nq, k, filters, out, out_tuples, launch);
+    return hnsw_host_search(h, queries, en.bytes(dim), nq, k, filters, out, out_tuples, launch);
 }
 
 extern "C" int vsr_hnsw_search_iterative(vsr_hnsw* h, const float* queries, int nq, int dim, int k, int ef, int metric,
@@ -1036,6 +1235,84 @@ extern "C" int vsr_hnsw_search_bit_iterative(vsr_hnsw* h, const uint8_t* queries
 {
     return hnsw_iterative_host({"vsr_hnsw_search_bit_iterative", RowFormat::BIT}, h, queries, nq, dim, k, ef, metric, filters, mode, max_scan_tuples,
                                out_blk, out_doc, out_row, out_dist, out_cnt, out_tuples);
+}
+
+// ---- K4s: the entry points of an index over a sparse corpus.  Queries are CSR; the metric is given per call, L2 .. L1 -----------
+// a host entry point's queries, validated as vsr_search_sparse validates them
+static int hnsw_sparse_host_queries(const char* who, vsr_hnsw* h, const int64_t* q_indptr, const int32_t* q_indices, const float* q_values,
+                                    int nq, int dim, int k, int metric, const vsr_filter* const* filters, SparseCsr& out)
+{
+    if (!h) return fail(VSR_ERR_INVALID, "%s: index is NULL", who);
+    if (h->format != RowFormat::SPARSE)
+        return fail(VSR_ERR_INVALID, "%s: the index is not over a sparse corpus (it is searched with vsr_hnsw_search* or vsr_hnsw_search_bit*)", who);
+    int rc = check_search_args(h->corpus, q_indptr, nq, dim, k, metric, filters, who, RowFormat::SPARSE);
+    if (rc) return rc;
+    uint32_t max_nnz = 0;
+    if ((rc = check_sparse_rows(who, q_indptr, q_indices, q_values, nq, dim, &max_nnz))) return rc;
+    out = {q_indptr, q_indices, q_values, max_nnz};
+    return VSR_OK;
+}
+
+// a device entry point's queries: nothing is read here; max_query_nnz sizes the tables (a longer query: an empty table and the guard bit)
+static int hnsw_sparse_device_queries(const char* who, vsr_hnsw* h, const int64_t* d_indptr, const int32_t* d_indices, const float* d_values,
+                                      int nq, int max_query_nnz, SparseCsr& out)
+{
+    if (!h) return fail(VSR_ERR_INVALID, "%s: index is NULL", who);
+    if (nq < 0 || (nq > 0 && !d_indptr)) return fail(VSR_ERR_INVALID, "%s: queries is NULL", who);
+    if (max_query_nnz < 0 || max_query_nnz > SPARSE_MAX_NNZ)
+        return fail(VSR_ERR_INVALID, "%s: max_query_nnz must be between 0 and %d (got %d)", who, SPARSE_MAX_NNZ, max_query_nnz);
+    if (nq > 0 && max_query_nnz > 0 && (!d_indices || !d_values)) return fail(VSR_ERR_INVALID, "%s: queries is NULL", who);
+    out = {d_indptr, d_indices, d_values, (uint32_t) max_query_nnz};
+    return VSR_OK;
+}
+
+extern "C" int vsr_hnsw_search_sparse(vsr_hnsw* h, const int64_t* q_indptr, const int32_t* q_indices, const float* q_values, int nq, int dim,
+                                      int k, int ef, int metric, const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc,
+                                      int64_t* out_row, float* out_dist, int32_t* out_cnt, int64_t* out_visited)
+{
+    const char* who = "vsr_hnsw_search_sparse";
+    SparseCsr q{};
+    int rc = hnsw_sparse_host_queries(who, h, q_indptr, q_indices, q_values, nq, dim, k, metric, filters, q);
+    if (rc) return rc;
+    return hnsw_search_host({who, RowFormat::SPARSE}, h, &q, nq, dim, k, ef, metric, filters, out_blk, out_doc, out_row, out_dist, out_cnt,
+                            out_visited);
+}
+
+extern "C" int vsr_hnsw_search_sparse_device(vsr_hnsw* h, const int64_t* d_indptr, const int32_t* d_indices, const float* d_values, int nq,
+                                             int dim, int max_query_nnz, int k, int ef, int metric, const vsr_filter* const* filters,
+                                             int64_t* d_blk, int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt, int64_t* d_visited)
+{
+    const char* who = "vsr_hnsw_search_sparse_device";
+    SparseCsr q{};
+    int rc = hnsw_sparse_device_queries(who, h, d_indptr, d_indices, d_values, nq, max_query_nnz, q);
+    if (rc) return rc;
+    return hnsw_search_device({who, RowFormat::SPARSE}, h, &q, nq, dim, k, ef, metric, filters, d_blk, d_doc, d_row, d_dist, d_cnt, d_visited);
+}
+
+extern "C" int vsr_hnsw_search_sparse_iterative(vsr_hnsw* h, const int64_t* q_indptr, const int32_t* q_indices, const float* q_values, int nq,
+                                                int dim, int k, int ef, int metric, const vsr_filter* const* filters, int mode,
+                                                int64_t max_scan_tuples, int64_t* out_blk, int32_t* out_doc, int64_t* out_row, float* out_dist,
+                                                int32_t* out_cnt, int64_t* out_tuples)
+{
+    const char* who = "vsr_hnsw_search_sparse_iterative";
+    SparseCsr q{};
+    int rc = hnsw_sparse_host_queries(who, h, q_indptr, q_indices, q_values, nq, dim, k, metric, filters, q);
+    if (rc) return rc;
+    return hnsw_iterative_host({who, RowFormat::SPARSE}, h, &q, nq, dim, k, ef, metric, filters, mode, max_scan_tuples, out_blk, out_doc, out_row,
+                               out_dist, out_cnt, out_tuples);
+}
+
+extern "C" int vsr_hnsw_search_sparse_iterative_device(vsr_hnsw* h, const int64_t* d_indptr, const int32_t* d_indices, const float* d_values,
+                                                       int nq, int dim, int max_query_nnz, int k, int ef, int metric,
+                                                       const vsr_filter* const* filters, int mode, int64_t max_scan_tuples, int64_t* d_blk,
+                                                       int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt, int64_t* d_tuples)
+{
+    const char* who = "vsr_hnsw_search_sparse_iterative_device";
+    SparseCsr q{};
+    int rc = hnsw_sparse_device_queries(who, h, d_indptr, d_indices, d_values, nq, max_query_nnz, q);
+    if (rc) return rc;
+    return hnsw_iterative_device({who, RowFormat::SPARSE}, h, &q, nq, dim, k, ef, metric, filters, mode, max_scan_tuples, d_blk, d_doc, d_row,
+                                 d_dist, d_cnt, d_tuples);
 }
 
 // ---- indexed two-stage search: the Hamming shortlist from the bit graph (K4b), the exact re-rank on the source rows ----

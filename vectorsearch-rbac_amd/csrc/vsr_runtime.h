@@ -251,6 +251,7 @@ struct vsr_corpus {
     RowFormat   format = RowFormat::F32;
     uint64_t*   d_sp_off = nullptr;
     uint64_t    sp_entries = 0;          // stored entries, pad entries included
+    uint32_t    sp_max_nnz = 0;          // non-zeros of the longest row (the HNSW entry points take at most HNSW_MAX_NNZ = 1000)
     int64_t     row_offset = 0;
     KernelShape shape{};
     float4*     d_rows = nullptr;

@@ -527,6 +527,7 @@ extern "C" int vsr_corpus_load_sparse(vsr_ctx* ctx, const int64_t* indptr, const
     for (int64_t i = 0; i < n; ++i) {
         const int64_t r = perm[(size_t) i], nnz = indptr[r + 1] - indptr[r];
         off[(size_t) i + 1] = off[(size_t) i] + (uint64_t) ((nnz + 1) / 2 * 2);
+        c->sp_max_nnz = std::max(c->sp_max_nnz, (uint32_t) nnz);
         float na = 0.0f;
         for (int64_t e = 0; e < nnz; ++e) {
             const float v = values[indptr[r] + e];
@@ -628,6 +629,54 @@ extern "C" int vsr_sparse_pair_distances(vsr_ctx* ctx, int metric, const int64_t
     HIPCHK(hipMemcpyAsync(out, d + o_out, (size_t) n_pairs * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return VSR_OK;
+}
+
+// sparsevec_l2_norm (out_norm) or sparsevec_l2_normalize (out_values, out_zeros) of n CSR rows: only the offsets and the values enter
+static int sparse_norm_fn(vsr_ctx* ctx, const int64_t* indptr, const float* values, int64_t n, double* out_norm, float* out_values,
+                          int64_t* out_zeros, bool normalize, const char* who)
+{
+    if (!ctx || n < 0 || (n > 0 && !indptr) || (n > 0 && !normalize && !out_norm)) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
+    if (out_zeros) *out_zeros = 0;
+    if (n == 0) return VSR_OK;
+    const int64_t b0 = indptr[0];
+    for (int64_t i = 0; i < n; ++i)
+        if (indptr[i + 1] < indptr[i] || indptr[i] < 0) return fail(VSR_ERR_INVALID, "sparsevec cannot have negative number of elements");
+    const size_t nnz = (size_t) (indptr[n] - b0);
+    if (nnz > 0 && (!values || (normalize && !out_values))) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
+    HIPCHK(hipSetDevice(ctx->device));
+    std::vector<int64_t> ptr((size_t) n + 1);
+    for (int64_t i = 0; i <= n; ++i) ptr[(size_t) i] = indptr[i] - b0;
+    const size_t o_val = align_up(ptr.size() * 8, 256), o_norm = align_up(o_val + nnz * 4, 256), o_out = align_up(o_norm + (size_t) n * 8, 256),
+                 o_flag = align_up(o_out + nnz * 4, 256);
+    int rc = ctx->d_misc.reserve(o_flag + 64);
+    if (rc) return rc;
+    char* d = ctx->d_misc.as<char>();
+    HIPCHK(hipMemcpyAsync(d, ptr.data(), ptr.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (nnz) HIPCHK(hipMemcpyAsync(d + o_val, values + b0, nnz * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(d + o_flag, 0, 16, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));               // (ptr is a local: the copy must have left it)
+    HIPCHK(launch_sparse_norms(reinterpret_cast<const int64_t*>(d), reinterpret_cast<const float*>(d + o_val), n,
+                               reinterpret_cast<double*>(d + o_norm), normalize ? reinterpret_cast<float*>(d + o_out) : nullptr,
+                               reinterpret_cast<int*>(d + o_flag), reinterpret_cast<unsigned long long*>(d + o_flag + 8), ctx->stream));
+    struct { int overflow; int pad; unsigned long long zeros; } flag = {0, 0, 0};
+    if (out_norm) HIPCHK(hipMemcpyAsync(out_norm, d + o_norm, (size_t) n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (normalize && nnz) HIPCHK(hipMemcpyAsync(out_values, d + o_out, nnz * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&flag, d + o_flag, 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (flag.overflow) return fail(VSR_ERR_INVALID, "value out of range: overflow");     // float_overflow_error(), sparsevec.c:1088
+    if (out_zeros) *out_zeros = (int64_t) flag.zeros;
+    return VSR_OK;
+}
+
+extern "C" int vsr_sparse_norms(vsr_ctx* ctx, const int64_t* indptr, const float* values, int64_t n, double* out)
+{
+    return sparse_norm_fn(ctx, indptr, values, n, out, nullptr, nullptr, false, "vsr_sparse_norms");
+}
+
+extern "C" int vsr_sparse_l2_normalize(vsr_ctx* ctx, const int64_t* indptr, const float* values, int64_t n, float* out_values,
+                                       int64_t* out_zeros)
+{
+    return sparse_norm_fn(ctx, indptr, values, n, nullptr, out_values, out_zeros, true, "vsr_sparse_l2_normalize");
 }
 
 // binary_quantize over the resident rows: a bit corpus with the source's context, row identity and internal order.  RBAC

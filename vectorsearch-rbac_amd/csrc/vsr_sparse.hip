@@ -144,6 +144,47 @@ hipError_t launch_sparse_pair_distances(const int64_t* a_ptr, const int32_t* a_i
     return hipGetLastError();
 }
 
+// Support functions of the cosine opclass, batched, one thread per vector with sparsevec.c's loops as they stand: sparsevec_l2_norm
+// (:1044-1055: a double sum of double products in entry order, then sqrt) and sparsevec_l2_normalize (:1060-1120: (float) (v / norm)
+// with the norm in double; a zero norm leaves the values as they are; an infinite result is reported; entries that became 0 are
+// counted -- the caller drops them).  out_values == nullptr: norms only.
+__global__ __launch_bounds__(256) void sparse_norm_kernel(const int64_t* ptr, const float* val, int64_t n, double* out_norm, float* out_values,
+                                                          int* overflow, unsigned long long* zeros)
+{
+    const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int64_t beg = ptr[i], end = ptr[i + 1];
+        double norm = 0.0;
+        for (int64_t e = beg; e < end; ++e) norm += (double) val[e] * (double) val[e];
+        norm = sqrt(norm);
+        if (out_norm) out_norm[i] = norm;
+        if (!out_values) continue;
+        unsigned long long z = 0;
+        bool inf = false;
+        for (int64_t e = beg; e < end; ++e) {
+            float r = val[e];
+            if (norm > 0) {
+                r = (float) ((double) val[e] / norm);
+                inf |= isinf(r);
+                z += r == 0.0f ? 1ull : 0ull;
+            }
+            out_values[e] = r;
+        }
+        if (inf) atomicOr(overflow, 1);
+        if (z) atomicAdd(zeros, z);
+    }
+}
+
+hipError_t launch_sparse_norms(const int64_t* ptr, const float* val, int64_t n, double* out_norm, float* out_values, int* overflow,
+                               unsigned long long* zeros, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(sparse_norm_kernel, dim3((uint32_t) blocks), dim3(256), 0, s, ptr, val, n, out_norm, out_values, overflow, zeros);
+    return hipGetLastError();
+}
+
 // ---- K1s capacity rules (host) ----
 // A lane group of LPR lanes takes 2 LPR entries of a row per step (16-byte loads): 4 lanes up to a dozen stored entries per row
 // on average, 16 up to about a hundred, a whole wave beyond.

@@ -118,6 +118,15 @@ SYMBOLS = {
     "vsr_hnsw_search_bit_iterative_device": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_hnsw_load_half": (_i, [_vp, _i, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(_vp)]),
     "vsr_hnsw_build_half": (_i, [_vp, _i, _i, _i, C.c_uint64, C.c_uint32, _vp]),
+    "vsr_hnsw_load_sparse": (_i, [_vp, _i, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(_vp)]),
+    "vsr_hnsw_build_sparse": (_i, [_vp, _i, _i, _i, C.c_uint64, C.c_uint32, _vp]),
+    "vsr_hnsw_search_sparse": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_hnsw_search_sparse_device": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_hnsw_search_sparse_iterative": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_hnsw_search_sparse_iterative_device": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp,
+                                                     _vp]),
+    "vsr_sparse_norms": (_i, [_vp, _vp, _vp, _i64, _vp]),
+    "vsr_sparse_l2_normalize": (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "vsr_hnsw_device_bytes": (_i64, [_vp]),
     "vsr_hnsw_search_quantized": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_hnsw_search_quantized_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -224,6 +224,31 @@ class Context:
                                                   _ptr(pb[1]), _ptr(pb[2]), n, pa[3], pb[3], _ptr(out)))
         return out
 
+    def sparse_norms(self, a, indices=None, values=None, dim=None):
+        """l2_norm of every sparse row (sparsevec.c:1044-1055): `a` as load_corpus_sparse takes rows.  float64 [n]."""
+        ip, _, vx, _ = _csr(a, indices, values, dim, "sparse_norms")
+        n = ip.size - 1
+        out = np.empty(n, dtype=np.float64)
+        check(self._lib.vsr_sparse_norms(self._h, _ptr(ip), _ptr(vx), n, _ptr(out)))
+        return out
+
+    def sparse_l2_normalize(self, a, indices=None, values=None, dim=None):
+        """l2_normalize of every sparse row (sparsevec.c:1060-1120): (indptr, indices, values, dim) of the unit rows.  An entry
+        whose quotient rounds to 0 is dropped, as pgvector drops it, so the result is a legal sparsevec; a row of zero norm stays
+        as it is; raises VsrError('value out of range: overflow')."""
+        ip, ix, vx, dim = _csr(a, indices, values, dim, "sparse_l2_normalize")
+        n = ip.size - 1
+        out = np.empty_like(vx)
+        zeros = C.c_int64(0)
+        check(self._lib.vsr_sparse_l2_normalize(self._h, _ptr(ip), _ptr(vx), n, _ptr(out), C.byref(zeros)))
+        lo, hi = int(ip[0]), int(ip[-1])
+        ix, out, ip = ix[lo:hi], out[:hi - lo], ip - lo     # (the library writes the entries it read, rebased to 0)
+        if zeros.value:
+            keep = out != 0
+            kept = np.concatenate([[0], np.cumsum(keep)]).astype(np.int64)
+            ix, out, ip = ix[keep], out[keep], kept[ip]
+        return ip, np.ascontiguousarray(ix), np.ascontiguousarray(out), dim
+
     def bit_pair_distances(self, metric, a, b, dim=None, dim_b=None):
         """hamming_distance / jaccard_distance for pairs (a[i], b[i]) of bit strings, bool or packed uint8 (then with `dim`;
         `dim_b` when b's length differs); b may be a single string (broadcast).  Raises VsrError('different bit lengths %u
@@ -574,6 +599,20 @@ class Corpus:
     def load_hnsw_half(self, graph):
         """load_hnsw over this halfvec corpus (vsr_hnsw_load_half): the graph kernels read the binary16 rows themselves."""
         return HnswIndex(self, graph, half=True)
+
+    def build_hnsw_sparse(self, m=16, ef_construction=64, metric="l2", seed=1, merge_duplicates=False):
+        """CREATE INDEX ... USING hnsw (col sparsevec_l2_ops | sparsevec_ip_ops | sparsevec_cosine_ops | sparsevec_l1_ops) over
+        this sparse corpus (vsr_hnsw_build_sparse): build_hnsw's batched insertion on the CSR rows, at most 1000 non-zeros per
+        row.  Cosine: load unit rows (Context.sparse_l2_normalize).  merge_duplicates is refused (VsrError).  The index answers
+        HnswIndex.search_sparse*."""
+        h = C.c_void_p()
+        check(self._lib.vsr_hnsw_build_sparse(self._h, int(m), int(ef_construction), _metric(metric), int(seed),
+                                              BUILD_MERGE_DUPLICATES if merge_duplicates else 0, C.byref(h)))
+        return HnswIndex(self, h)
+
+    def load_hnsw_sparse(self, graph):
+        """load_hnsw over this sparse corpus (vsr_hnsw_load_sparse); the index answers HnswIndex.search_sparse*, metric per call."""
+        return HnswIndex(self, graph, sparse=True)
 
     # ---- search ------------------------------------------------------------------------------
     def pack_filters(self, filters):
@@ -935,7 +974,7 @@ class IvfIndex:
 class HnswIndex:
     """pgvector's hnsw scan (hnswscan.c) on the GPU: greedy descent, ef_search beam on layer 0, TIDs, filter, LIMIT."""
 
-    def __init__(self, corpus, g, bit_metric=None, half=False):
+    def __init__(self, corpus, g, bit_metric=None, half=False, sparse=False):
         self.corpus, self._lib = corpus, corpus._lib
         if isinstance(g, C.c_void_p):                # a handle vsr_hnsw_build* returned (Corpus.build_hnsw, build_hnsw_bit)
             self._h = g
@@ -953,6 +992,10 @@ class HnswIndex:
             check(self._lib.vsr_hnsw_load_half(corpus._h, int(g["m"]), level.size, int(g["entry"]), _ptr(level), _ptr(nbr0),
                                                _ptr(tc), _ptr(tids), _ptr(up_slot), _ptr(up_nbr), n_upper, int(g["max_level"]),
                                                C.byref(h)))
+        elif sparse:                                 # Corpus.load_hnsw_sparse
+            check(self._lib.vsr_hnsw_load_sparse(corpus._h, int(g["m"]), level.size, int(g["entry"]), _ptr(level), _ptr(nbr0),
+                                                 _ptr(tc), _ptr(tids), _ptr(up_slot), _ptr(up_nbr), n_upper, int(g["max_level"]),
+                                                 C.byref(h)))
         else:
             check(self._lib.vsr_hnsw_load(corpus._h, int(g["m"]), level.size, int(g["entry"]), _ptr(level), _ptr(nbr0), _ptr(tc),
                                           _ptr(tids), _ptr(up_slot), _ptr(up_nbr), n_upper, int(g["max_level"]), C.byref(h)))
@@ -1102,6 +1145,67 @@ class HnswIndex:
                                                       _ptr(dist), _ptr(cnt), _ptr(tup)))
         del keep
         return SearchResult(blk, doc, row, dist, cnt), tup
+
+    # ---- a sparse index (Corpus.load_hnsw_sparse / build_hnsw_sparse): queries are CSR, the metric is given per call -----------
+    def _csr_queries(self, queries, indices, values, dim, what):
+        """The forms Corpus.search_sparse accepts: an object with .indptr / .indices / .data / .shape, or three arrays."""
+        if indices is None and hasattr(queries, "indptr"):
+            return _csr(queries, dim=dim, what=what)
+        return _csr(queries, indices, values, self.corpus.dim if dim is None else dim, what)
+
+    def search_sparse(self, queries, k, ef_search=40, metric="l2", filters=None, indices=None, values=None, dim=None):
+        """HnswIndex.search over a sparse index (vsr_hnsw_search_sparse): `queries` as Corpus.search_sparse takes them (up to
+        16000 non-zeros each), metric "l2", "ip", "cosine" (unit rows and unit queries) or "l1".  SearchResult plus the
+        elements each query visited on layer 0."""
+        ip, ix, vx, qdim = self._csr_queries(queries, indices, values, dim, "search_sparse")
+        nq = ip.size - 1
+        farr, keep = self.corpus._filter_array(filters, nq)
+        blk, doc, row, dist, cnt = self._results(nq, k)
+        vis = np.zeros(nq, dtype=np.int64)
+        check(self._lib.vsr_hnsw_search_sparse(self._h, _ptr(ip), _ptr(ix), _ptr(vx), nq, qdim, int(k), int(ef_search),
+                                               _metric(metric), farr, _ptr(blk), _ptr(doc), _ptr(row), _ptr(dist), _ptr(cnt),
+                                               _ptr(vis)))
+        del keep
+        return SearchResult(blk, doc, row, dist, cnt), vis
+
+    def search_sparse_device(self, d_indptr, d_indices, d_values, nq, max_query_nnz, k, ef_search, metric, filters, d_block, d_doc,
+                             d_rows, d_dist, d_counts, d_visited=None, dim=None):
+        """Device pointers (ints): the queries' CSR arrays in device memory (int64, int32, float32) and the largest non-zero
+        count of any of them (a longer query fails screening_check); query staging and ONE search launch on the corpus
+        context's stream, no synchronisation (vsr_hnsw_search_sparse_device)."""
+        farr, keep = self.corpus._filter_array(filters, nq)
+        check(self._lib.vsr_hnsw_search_sparse_device(self._h, d_indptr, d_indices, d_values, nq,
+                                                      self.corpus.dim if dim is None else dim, int(max_query_nnz), int(k),
+                                                      int(ef_search), _metric(metric), farr, d_block, d_doc, d_rows, d_dist,
+                                                      d_counts, d_visited))
+        return keep
+
+    def search_sparse_iterative(self, queries, k, ef_search=40, metric="l2", filters=None, mode="relaxed_order",
+                                max_scan_tuples=20000, indices=None, values=None, dim=None):
+        """search_iterative over a sparse index (vsr_hnsw_search_sparse_iterative): SearchResult in stream order plus the
+        tuples each query's scan counted when it stopped."""
+        ip, ix, vx, qdim = self._csr_queries(queries, indices, values, dim, "search_sparse_iterative")
+        nq = ip.size - 1
+        farr, keep = self.corpus._filter_array(filters, nq)
+        blk, doc, row, dist, cnt = self._results(nq, k)
+        tup = np.zeros(nq, dtype=np.int64)
+        check(self._lib.vsr_hnsw_search_sparse_iterative(self._h, _ptr(ip), _ptr(ix), _ptr(vx), nq, qdim, int(k), int(ef_search),
+                                                         _metric(metric), farr, _iterative_mode(mode), int(max_scan_tuples),
+                                                         _ptr(blk), _ptr(doc), _ptr(row), _ptr(dist), _ptr(cnt), _ptr(tup)))
+        del keep
+        return SearchResult(blk, doc, row, dist, cnt), tup
+
+    def search_sparse_iterative_device(self, d_indptr, d_indices, d_values, nq, max_query_nnz, k, ef_search, metric, filters, mode,
+                                       max_scan_tuples, d_block, d_doc, d_rows, d_dist, d_counts, d_tuples=None, dim=None):
+        """Device pointers (ints); no synchronisation (vsr_hnsw_search_sparse_iterative_device).  A query whose discarded set
+        outgrew its buffer reports count -1."""
+        farr, keep = self.corpus._filter_array(filters, nq)
+        check(self._lib.vsr_hnsw_search_sparse_iterative_device(self._h, d_indptr, d_indices, d_values, nq,
+                                                                self.corpus.dim if dim is None else dim, int(max_query_nnz),
+                                                                int(k), int(ef_search), _metric(metric), farr,
+                                                                _iterative_mode(mode), int(max_scan_tuples), d_block, d_doc,
+                                                                d_rows, d_dist, d_counts, d_tuples))
+        return keep
 
     def search_bit_iterative_device(self, d_queries, nq, k, ef_search, metric, filters, mode, max_scan_tuples, d_block, d_doc,
                                     d_rows, d_dist, d_counts, d_tuples=None, dim=None):
