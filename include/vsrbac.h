@@ -789,6 +789,40 @@ int vsr_hnsw_search_quantized_device(vsr_corpus* source, vsr_hnsw* bit_index, co
                                      int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
                                      int32_t* d_out_counts, uint64_t* d_out_keys);
 
+/* The two-stage search through the IVFFlat index of the bits: CREATE INDEX ... USING ivfflat
+ * ((binary_quantize(embedding)::bit(n)) bit_hamming_ops), ORDER BY ... <~> ... LIMIT shortlist under ivfflat.probes (and
+ * ivfflat.iterative_scan / ivfflat.max_probes), then the re-rank on the original vectors.  bit_index is a vsr_ivf_load_bit index
+ * over the corpus vsr_corpus_binary_quantize(source) made; source is fp32 or halfvec; the filters are filters of that bit corpus.
+ * Per query q of `dim` floats:
+ *   1. qb = binary_quantize(q), from the fp32 value as given: bit i is set where q[i] > 0 (NaN, 0 and -0.0 give 0);
+ *   2. S = exactly the rows vsr_ivf_search_bit_iterative(bit_index, qb, k = shortlist, probes, VSR_METRIC_HAMMING, filters, mode,
+ *      max_probes) returns: batches of `probes` lists in (Hamming count, list id) centre order, each batch contributing its
+ *      (shortlist - have) smallest ((float) Hamming, document_id, block_id) keys, until `shortlist` rows are found or
+ *      max(max_probes, probes) lists are scanned.  mode == VSR_IVF_ITERATIVE_OFF ignores max_probes and is vsr_ivf_search_bit's
+ *      answer.  Stage 1 is one launch (K3q) that quantizes the queries itself and starts at the first list: no host planning;
+ *   3. stage 2 is vsr_search_quantized's, unchanged: the exact operator distance on the source rows of S, the first
+ *      min(k, |S|) returned, the same -1 / +Inf fill past out_counts[i].
+ * out_probes (nq, may be NULL) receives the lists scanned, whole batches, as vsr_ivf_search_bit_iterative's.  out_rows and
+ * out_doc_ids may be NULL.  k <= shortlist <= VSR_MAX_K; L2, inner product and cosine; L1 is VSR_ERR_UNSUPPORTED.
+ * Consequences: with probes >= lists the call equals vsr_search_quantized(source, bits, ...); with a filter that admits at most
+ * `shortlist` rows, VSR_IVF_ITERATIVE_RELAXED and max_probes >= lists it equals vsr_search(source) over those rows.
+ * The _device form (queries nq x dim floats, row stride dim, 4-byte aligned, and all outputs in device memory) enqueues
+ * everything on the bit corpus context's stream and does not synchronise; a filter's view-order bitmap is built, and waited
+ * for, on its first use with this index only.  d_out_keys (nq*k, may be NULL) is as vsr_search_quantized_device's.  The host form
+ * copies up, calls the device form's launches and copies down.
+ * Errors.  bit_index not over a bit corpus: VSR_ERR_INVALID, "the index is not over a bit corpus (it is searched with
+ * vsr_ivf_search*)".  Then vsr_search_quantized's checks against bit_index's corpus, in its words (bits not made from source,
+ * shortlist < k, shortlist > VSR_MAX_K, L1, a filter of another corpus -- source's included --, VSR_ERR_DIM_MISMATCH).  probes,
+ * mode and max_probes as vsr_ivf_search_iterative.  A shape whose LDS does not fit a compute unit: VSR_ERR_UNSUPPORTED. */
+int vsr_ivf_search_quantized(vsr_corpus* source, vsr_ivf* bit_index, const float* queries, int nq, int dim, int k, int shortlist,
+                             int probes, int metric, const vsr_filter* const* filters, int mode, int max_probes,
+                             int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows, float* out_dist,
+                             int32_t* out_counts, int32_t* out_probes);
+int vsr_ivf_search_quantized_device(vsr_corpus* source, vsr_ivf* bit_index, const float* d_queries, int nq, int dim, int k,
+                                    int shortlist, int probes, int metric, const vsr_filter* const* filters, int mode,
+                                    int max_probes, int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows,
+                                    float* d_out_dist, int32_t* d_out_counts, int32_t* d_out_probes, uint64_t* d_out_keys);
+
 /* opclass support functions for n vectors at once (host pointers): vector_norm (vector.c:756-769), l2_normalize
  * (vector.c:774-808; fails with "value out of range: overflow" like float_overflow_error) and
  * vector_spherical_distance (vector.c:692-711; unit vectors assumed, as IVFFlat's spherical k-means uses it) */

@@ -3,6 +3,7 @@
 // K3b: the same over a bit corpus (the _bit entry points, bit_hamming_ops): packed rows in the view, packed centres, K1b scans.
 #include "vsr_runtime.h"
 #include "vsr_ivf_iter.h"
+#include "vsr_ivf_shortlist.h"
 
 #include <cmath>
 
@@ -31,6 +32,21 @@ hipError_t launch_ivf_iterative(const IvfIterParams& p, uint32_t nq, hipStream_t
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(kernel, dim3(nq), dim3(256), lds, s, p);
+    return hipGetLastError();
+}
+
+// K3q (vsr_ivf_shortlist.h): one workgroup per query; what does not fit the CU's LDS is refused, as above
+hipError_t launch_ivf_bit_shortlist(const IvfShortlistParams& p, uint32_t nq, hipStream_t s)
+{
+    if (nq == 0) return hipSuccess;
+    const size_t lds = ivf_shortlist_lds_bytes(p.lists, p.stride4, p.shortlist);
+    if (lds > 160 * 1024 || p.shortlist < 1 || p.shortlist > (uint32_t) MAX_K || p.n_rows > 0x7FFFFE00u) return hipErrorInvalidValue;
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_bit_shortlist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int) lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(ivf_bit_shortlist_kernel, dim3(nq), dim3(256), lds, s, p);
     return hipGetLastError();
 }
 }  // namespace vsr
@@ -62,6 +78,11 @@ struct vsr_ivf {
     uint32_t* d_list_start = nullptr;                // list_start on the device (the iterative scan walks lists there)
     PinBuf h_vb;                                     // iterative scan: per query, its view bitmap's device address
     DevBuf d_res;                                    // iterative scan, host form: the results before they go back
+    // vsr_ivf_search_quantized*: the per-query view-bitmap addresses on their way into the context's scratch.  The kernel reads the
+    // scratch copy; the event guards the pinned block against the next call's rewrite until that copy has run
+    PinBuf h_vbq;
+    hipEvent_t vbq_done = nullptr;
+    bool vbq_pending = false;
 };
 
 static bool ivf_half(const vsr_ivf* ivf) { return ivf->view->format == RowFormat::HALF; }
@@ -103,6 +124,8 @@ extern "C" int vsr_ivf_free(vsr_ivf* ivf)
     if (ivf->d_centers) (void) hipFree(ivf->d_centers);
     if (ivf->d_list_start) (void) hipFree(ivf->d_list_start);
     ivf->h_vb.release();
+    ivf->h_vbq.release();
+    if (ivf->vbq_done) (void) hipEventDestroy(ivf->vbq_done);
     ivf->d_res.release();
     ivf->d_q.release();
     ivf->d_qwords.release();
@@ -398,6 +421,22 @@ static int ivf_check_entry(const vsr_ivf* ivf, RowFormat entry, const char* who)
     return VSR_OK;
 }
 
+static int ivf_check_probes(int probes, const char* who)
+{
+    if (probes < 1) return fail(VSR_ERR_INVALID, "%s: probes must be >= 1 (got %d)", who, probes);   /* ivfflat.c:41-45 */
+    return VSR_OK;
+}
+
+// the two arguments of the iterative forms (GUC ranges: ivfflat.c:20-51)
+static int ivf_check_iterative(int mode, int max_probes, const char* who)
+{
+    if (mode != VSR_IVF_ITERATIVE_OFF && mode != VSR_IVF_ITERATIVE_RELAXED)
+        return fail(VSR_ERR_INVALID, "%s: iterative scan mode %d (ivfflat has off and relaxed_order)", who, mode);
+    if (max_probes < 1 || max_probes > 32768)
+        return fail(VSR_ERR_INVALID, "%s: max_probes must be between 1 and 32768 (got %d)", who, max_probes);
+    return VSR_OK;
+}
+
 static int ivf_check(vsr_ivf* ivf, RowFormat entry, const void* queries, int nq, int dim, int k, int& probes, int metric,
                      const vsr_filter* const* filters, const void* o1, const void* o2, const void* o3, const char* who)
 {
@@ -406,24 +445,20 @@ static int ivf_check(vsr_ivf* ivf, RowFormat entry, const void* queries, int nq,
     if ((rc = check_search_args(ivf->main, queries, nq, dim, k, metric, filters, who, entry))) return rc;
     if (metric == VSR_METRIC_JACCARD) return fail(VSR_ERR_UNSUPPORTED, "%s: ivfflat has no bit_jaccard_ops operator class", who);
     if (metric == VSR_METRIC_L1) return fail(VSR_ERR_UNSUPPORTED, "%s: ivfflat has no L1 operator class", who);
-    if (probes < 1) return fail(VSR_ERR_INVALID, "%s: probes must be >= 1 (got %d)", who, probes);   /* ivfflat.c:41-45 */
+    if ((rc = ivf_check_probes(probes, who))) return rc;
     if (nq > 0 && (!o1 || !o2 || !o3)) return fail(VSR_ERR_INVALID, "%s: output is NULL", who);
     probes = std::min(probes, ivf->lists);
     return VSR_OK;
 }
 
-// ... and the two arguments of the iterative form (GUC ranges: ivfflat.c:20-51)
+// ... and the two arguments of the iterative form
 static int ivf_check(vsr_ivf* ivf, RowFormat entry, const void* queries, int nq, int dim, int k, int& probes, int metric,
                      const vsr_filter* const* filters, int mode, int max_probes, const void* o1, const void* o2, const void* o3,
                      const char* who)
 {
     int rc = ivf_check(ivf, entry, queries, nq, dim, k, probes, metric, filters, o1, o2, o3, who);
     if (rc) return rc;
-    if (mode != VSR_IVF_ITERATIVE_OFF && mode != VSR_IVF_ITERATIVE_RELAXED)
-        return fail(VSR_ERR_INVALID, "%s: iterative scan mode %d (ivfflat has off and relaxed_order)", who, mode);
-    if (max_probes < 1 || max_probes > 32768)
-        return fail(VSR_ERR_INVALID, "%s: max_probes must be between 1 and 32768 (got %d)", who, max_probes);
-    return VSR_OK;
+    return ivf_check_iterative(mode, max_probes, who);
 }
 
 // vsr_ivf_search (entry = F32) and vsr_ivf_search_bit (BIT: packed queries)
@@ -641,6 +676,140 @@ extern "C" int vsr_ivf_search_bit_iterative(vsr_ivf* ivf, const uint8_t* queries
 {
     return ivf_iterative(ivf, RowFormat::BIT, queries, nq, dim, k, probes, metric, filters, mode, max_probes, out_blk, out_doc, out_row,
                          out_dist, out_cnt, out_probes, "vsr_ivf_search_bit_iterative");
+}
+
+// ---- two-stage search through the bit index: the Hamming shortlist from the lists (K3q), the exact re-rank on the source rows ----
+// vsr_search_quantized with stage 1 replaced by the index, everything on the bit corpus context's stream with no host round trip:
+// the per-query table of view-order bitmap addresses (a stream-ordered copy into the context's scratch: the kernel never reads
+// the pinned block, which the next call rewrites) -> ONE K3q launch, which quantizes the queries itself and starts at the first
+// list -> the re-rank and emit launches of vsr_shortlist.h (quantized_rerank, vsr_search.hip).  Exactly one of h_queries /
+// d_queries is set; `out` and d_probes address device memory either way.
+static int ivf_quantized_impl(vsr_corpus* src, vsr_ivf* ivf, const float* h_queries, const float* d_queries, int nq, int dim, int k,
+                              int shortlist, int probes, int metric, const vsr_filter* const* filters, int mode, int max_probes,
+                              const Outputs& out, int32_t* d_probes, const char* who)
+{
+    vsr_corpus* bits = ivf->main;
+    vsr_corpus* v = ivf->view;
+    vsr_ctx* ctx = bits->ctx;
+    int rc;
+    const size_t ns = (size_t) nq * (size_t) shortlist;
+    // scratch: [fp32 queries of a host call | bitmap addresses | stage-1 keys | re-rank keys | stage-1 counts]
+    const size_t o_q = 0, o_vb = align_up(o_q + (h_queries ? (size_t) nq * dim * sizeof(float) : 0), 256),
+                 o_key = align_up(o_vb + (size_t) nq * sizeof(uint64_t*), 256), o_rr = align_up(o_key + ns * 8, 256),
+                 o_cnt = align_up(o_rr + ns * 8, 256), total = align_up(o_cnt + (size_t) nq * 4, 256);
+    if ((rc = ctx->d_short.reserve(total))) return rc;
+    char* w = ctx->d_short.as<char>();
+    if (h_queries) {
+        HIPCHK(hipMemcpyAsync(w + o_q, h_queries, (size_t) nq * dim * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        d_queries = reinterpret_cast<const float*>(w + o_q);
+    }
+    bool any_filter = false;
+    if (filters)
+        for (int q = 0; q < nq && !any_filter; ++q) any_filter = filters[q] != nullptr;
+    if (any_filter) {
+        if (ivf->vbq_pending) {                                            // the previous call's copy still owns the pinned block
+            HIPCHK(hipEventSynchronize(ivf->vbq_done));
+            ivf->vbq_pending = false;
+        }
+        if (!ivf->vbq_done) HIPCHK(hipEventCreateWithFlags(&ivf->vbq_done, hipEventDisableTiming));
+        if ((rc = ivf->h_vbq.reserve((size_t) nq * sizeof(uint64_t*)))) return rc;
+        const uint64_t** vbs = ivf->h_vbq.as<const uint64_t*>();
+        for (int q = 0; q < nq; ++q) {
+            vbs[q] = nullptr;
+            if (filters[q]) {
+                vsr_ivf::ViewBitmap* vb = nullptr;
+                if ((rc = ivf_view_bitmap(ivf, filters[q], &vb))) return rc;    // (built, and waited for, on a filter's first use)
+                vbs[q] = vb->d;
+            }
+        }
+        HIPCHK(hipMemcpyAsync(w + o_vb, vbs, (size_t) nq * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipEventRecord(ivf->vbq_done, ctx->stream));
+        ivf->vbq_pending = true;
+    }
+    uint64_t* s1_keys = reinterpret_cast<uint64_t*>(w + o_key);
+    IvfShortlistParams p{};
+    p.queries = d_queries;
+    p.dim = (uint32_t) dim;
+    p.centers_t = ivf->d_centers;
+    p.lists = (uint32_t) ivf->lists;
+    p.probes = (uint32_t) probes;
+    // pgvector ignores max_probes when the scan is off
+    p.max_lists = (uint32_t) (mode == VSR_IVF_ITERATIVE_OFF ? probes : std::min(std::max(max_probes, probes), ivf->lists));
+    p.shortlist = (uint32_t) shortlist;
+    p.list_start = ivf->d_list_start;
+    p.rows = reinterpret_cast<const uint4*>(v->d_rows);
+    p.stride4 = v->stride4;
+    p.n_rows = (uint32_t) v->n;
+    p.rank = v->d_rank;
+    p.bitmaps = any_filter ? reinterpret_cast<const uint64_t* const*>(w + o_vb) : nullptr;
+    p.row_offset = (uint32_t) bits->row_offset;
+    p.s1_keys = s1_keys;
+    p.out_count = reinterpret_cast<int32_t*>(w + o_cnt);
+    p.out_probes = d_probes;
+    hipError_t e = launch_ivf_bit_shortlist(p, (uint32_t) nq, ctx->stream);
+    if (e == hipErrorInvalidValue)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: %d lists x %d bits x shortlist = %d need more than the 160 KiB of LDS", who, ivf->lists, dim, shortlist);
+    HIPCHK(e);
+    ctx->last_kernel = "ivf_bit_shortlist_kernel";
+    return quantized_rerank(ctx, src, s1_keys, (uint32_t) bits->row_offset, reinterpret_cast<uint64_t*>(w + o_rr), d_queries, nq, dim, k,
+                            shortlist, metric, out);
+}
+
+static int ivf_quantized_check(vsr_corpus* src, vsr_ivf* ivf, const void* queries, int nq, int dim, int k, int shortlist, int& probes,
+                               int metric, const vsr_filter* const* filters, int mode, int max_probes, const char* who)
+{
+    int rc = ivf_check_entry(ivf, RowFormat::BIT, who);
+    if (rc) return rc;
+    if ((rc = check_quantized_args(nullptr, src, ivf->main, queries, nq, dim, k, shortlist, metric, filters, who))) return rc;
+    if ((rc = ivf_check_probes(probes, who))) return rc;
+    if ((rc = ivf_check_iterative(mode, max_probes, who))) return rc;
+    probes = std::min(probes, ivf->lists);
+    return VSR_OK;
+}
+
+extern "C" int vsr_ivf_search_quantized_device(vsr_corpus* src, vsr_ivf* ivf, const float* d_queries, int nq, int dim, int k,
+                                               int shortlist, int probes, int metric, const vsr_filter* const* filters, int mode,
+                                               int max_probes, int64_t* d_blk, int32_t* d_doc, int64_t* d_row, float* d_dist,
+                                               int32_t* d_cnt, int32_t* d_probes, uint64_t* d_keys)
+{
+    const char* who = "vsr_ivf_search_quantized_device";
+    int rc = ivf_quantized_check(src, ivf, d_queries, nq, dim, k, shortlist, probes, metric, filters, mode, max_probes, who);
+    if (rc) return rc;
+    if (nq == 0) return VSR_OK;
+    if (!d_blk || !d_dist || !d_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", who);
+    HIPCHK(hipSetDevice(ivf->main->ctx->device));
+    return ivf_quantized_impl(src, ivf, nullptr, d_queries, nq, dim, k, shortlist, probes, metric, filters, mode, max_probes,
+                              {d_blk, d_doc, d_row, d_dist, d_cnt, d_keys}, d_probes, who);
+}
+
+extern "C" int vsr_ivf_search_quantized(vsr_corpus* src, vsr_ivf* ivf, const float* queries, int nq, int dim, int k, int shortlist,
+                                        int probes, int metric, const vsr_filter* const* filters, int mode, int max_probes,
+                                        int64_t* out_blk, int32_t* out_doc, int64_t* out_row, float* out_dist, int32_t* out_cnt,
+                                        int32_t* out_probes)
+{
+    const char* who = "vsr_ivf_search_quantized";
+    int rc = ivf_quantized_check(src, ivf, queries, nq, dim, k, shortlist, probes, metric, filters, mode, max_probes, who);
+    if (rc) return rc;
+    if (nq == 0) return VSR_OK;
+    if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", who);
+    if (src->format == RowFormat::HALF && (rc = half_query_range(queries, nq, dim))) return rc;   // `$1::halfvec`, as vsr_search refuses it
+    vsr_ctx* ctx = ivf->main->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    // queries up, the device form's launches, results down: one packed copy back, one wait
+    const ResultBlock rb(nq, k, true);                                     // (extra column: the lists scanned)
+    if ((rc = ctx->d_out.reserve(rb.o_status))) return rc;
+    if ((rc = ctx->h_out.reserve(rb.total))) return rc;
+    char* d = ctx->d_out.as<char>();
+    char* h = ctx->h_out.as<char>();
+    int32_t* d_probes = rb.column<int32_t>(d, rb.o_extra);
+    if ((rc = ivf_quantized_impl(src, ivf, queries, nullptr, nq, dim, k, shortlist, probes, metric, filters, mode, max_probes, rb.arrays(d),
+                                 d_probes, who)))
+        return rc;
+    HIPCHK(hipMemcpyAsync(h, d, rb.o_status, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    rb.copy_out_all(h, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr}, nullptr);
+    if (out_probes) memcpy(out_probes, rb.column<int32_t>(h, rb.o_extra), (size_t) nq * sizeof(int32_t));
+    return VSR_OK;
 }
 
 extern "C" int vsr_ivf_probe(vsr_ivf* ivf, const float* queries, int nq, int dim, int probes, int metric, int32_t* out_lists)

@@ -32,11 +32,9 @@
 #include "vsr_exact.h"
 #include "vsr_bitops.h"
 #include "vsr_topk.h"
+#include "vsr_ivf_lds.h"     // IVI_CHUNK, ivf_iter_kept, ivf_iter_lds_bytes
 
 namespace vsr {
-
-constexpr uint32_t IVI_CHUNK = 512;          // appended keys between two folds (>= 2 x the 256 a workgroup step can append)
-constexpr uint32_t IVI_MIN_KEPT = 512;       // the fold reads kept[SK - 1 - j], j < IVI_CHUNK
 
 struct IvfIterParams {
     const float*           queries;          // [nq][q_stride] (device); rows_bit: packed bit strings, q_stride BYTES apart
@@ -68,18 +66,6 @@ struct IvfIterParams {
     int32_t*               out_probes;       // [nq] lists scanned, whole batches; may be nullptr
 };
 
-__host__ __device__ inline uint32_t ivf_iter_kept(uint32_t k)
-{
-    uint32_t sk = IVI_MIN_KEPT;
-    while (sk < k) sk <<= 1;
-    return sk;
-}
-// (bit: the view of a bit corpus -- stride4 is its chunks per row -- whose waves also keep the 64 counts of a step)
-inline size_t ivf_iter_lds_bytes(uint32_t lists, uint32_t stride4, uint32_t k, bool bit = false)
-{
-    return (((size_t) lists * 4 + 15) & ~(size_t) 15) + (size_t) stride4 * 16 + (bit ? 2 : 1) * 4 * 64 * 4 + (size_t) (ivf_iter_kept(k) + IVI_CHUNK) * 8 + 64;
-}
-
 #ifdef __HIPCC__
 struct IvfIterCtrl {                         // 64 bytes
     uint64_t tau;                            // keys >= tau cannot enter the batch's result
@@ -110,6 +96,60 @@ __device__ __forceinline__ void ivf_iter_fold(uint64_t* kept, uint32_t sk, uint6
         ctrl->tau = kept[need - 1];                                        // KEY_EMPTY until `need` keys exist
     }
     __syncthreads();
+}
+
+// The permitted rows of one workgroup step -- the 256 view rows from `base` (a multiple of 64), one word of the bitmap per
+// wave -- of the list [s0, s1): this wave's word into m, the workgroup's count returned (the same in every thread).  Shared
+// with K3q (vsr_ivf_shortlist.h).
+__device__ __forceinline__ uint32_t ivf_iter_step_masks(uint32_t base, uint32_t s0, uint32_t s1, const uint64_t* bm, int wave, uint64_t& m)
+{
+    uint32_t step_n = 0;
+    m = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const uint32_t w0 = base + (uint32_t) w * 64;
+        uint64_t mw = 0;
+        if (w0 < s1) {
+            const uint32_t lo = s0 > w0 ? s0 - w0 : 0u;        // < 64: w0 >= s0 & ~63
+            const uint32_t hi = s1 - w0 < 64u ? s1 - w0 : 64u;
+            mw = (hi == 64u ? ~0ull : (1ull << hi) - 1ull) & ~((1ull << lo) - 1ull);
+            if (bm) mw &= bm[w0 >> 6];                         // w0 < s1 <= n_rows: inside the bitmap
+        }
+        step_n += (uint32_t) __popcll(mw);
+        if (w == wave) m = mw;
+    }
+    return step_n;
+}
+
+// A wave's step over a bit view: the n_ok (>= 1, wave-uniform) compacted view rows of rowsel are gathered by lane groups and
+// counted against the packed query in LDS (bit_graph_distances, vsr_bitops.h), 64 counts into `counts`; lane j makes the key of
+// row j -- make_key((float) count, base row), the value the count as fp32, as K1b's -- and keys below tau are appended to the
+// chunk.  A base row outside the corpus sets ctrl->bad and becomes neither a key nor an address.  Shared by K3i's bit form and K3q.
+__device__ __forceinline__ void ivf_iter_bit_rows(const uint4* rows16, uint32_t stride4, const uint4* qs, uint32_t* rowsel, uint32_t n_ok,
+                                                  float* counts, const uint32_t* rank, uint32_t n_rows, uint64_t tau,
+                                                  IvfIterCtrl* ctrl, uint64_t* chunk, int lane)
+{
+    const uint32_t G = bit_graph_lanes(stride4), gl = (uint32_t) lane & (G - 1u);
+    const uint4 qreg = gl < stride4 ? qs[gl] : make_uint4(0u, 0u, 0u, 0u);
+    // rowsel[j] < s1 <= n_rows < 2^31 (launcher): a row id of the view as the gather takes it
+    bit_graph_distances<false>(rows16, stride4, G, nullptr, nullptr, qs, qreg, 0.0f, reinterpret_cast<const int32_t*>(rowsel), (int) n_ok,
+                               counts, lane);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const bool mine = (uint32_t) lane < n_ok;
+    const uint32_t br = mine ? rank[rowsel[lane]] : 0u;
+    const bool in_range = br < n_rows;
+    if (mine && !in_range) ctrl->bad = 1;              // never a key, never an address
+    const uint64_t key = make_key(mine ? counts[lane] : 0.0f, br);
+    const bool pass = mine && in_range && key < tau;
+    const uint64_t pm = __ballot(pass);
+    if (pm) {
+        const int leader = __ffsll((unsigned long long) pm) - 1;
+        uint32_t at = 0;
+        if (lane == leader) at = atomicAdd(&ctrl->count, (uint32_t) __popcll(pm));
+        at = (uint32_t) __shfl((int) at, leader) + (uint32_t) __popcll(pm & ((1ull << lane) - 1ull));
+        if (pass && at < IVI_CHUNK) chunk[at] = key;
+    }
 }
 
 // HALF (K3h): rows and centres are binary16.  The query is rounded to binary16 as it is loaded (`$1::halfvec`) and kept in LDS
@@ -204,21 +244,8 @@ __global__ __launch_bounds__(256) void ivf_iterative_kernel(const IvfIterParams 
             // workgroup steps of 256 view rows (64 per wave) from the 64-row boundary at or below s0: a wave's step is one
             // word of the bitmap, the rows of the word outside the list masked out
             for (uint32_t base = s0 & ~63u; base < s1; base += 256) {
-                uint64_t m = 0;                                            // this wave's permitted rows of the step
-                uint32_t step_n = 0;                                       // ... and the workgroup's count of them
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const uint32_t w0 = base + (uint32_t) w * 64;
-                    uint64_t mw = 0;
-                    if (w0 < s1) {
-                        const uint32_t lo = s0 > w0 ? s0 - w0 : 0u;        // < 64: w0 >= s0 & ~63
-                        const uint32_t hi = s1 - w0 < 64u ? s1 - w0 : 64u;
-                        mw = (hi == 64u ? ~0ull : (1ull << hi) - 1ull) & ~((1ull << lo) - 1ull);
-                        if (bm) mw &= bm[w0 >> 6];                         // w0 < s1 <= n_rows: inside the bitmap
-                    }
-                    step_n += (uint32_t) __popcll(mw);
-                    if (w == wave) m = mw;
-                }
+                uint64_t m;                                                // this wave's permitted rows of the step
+                const uint32_t step_n = ivf_iter_step_masks(base, s0, s1, bm, wave, m);   // ... and the workgroup's count of them
                 if (ub + step_n > IVI_CHUNK) {                             // (uniform) the chunk could overflow: fold it first
                     __syncthreads();                                       // every append so far is in the chunk
                     ivf_iter_fold(kept, sk, chunk, ctrl, need, tid);
@@ -232,31 +259,9 @@ __global__ __launch_bounds__(256) void ivf_iterative_kernel(const IvfIterParams 
                 __builtin_amdgcn_wave_barrier();
                 const uint64_t tau = lds_peek(&ctrl->tau);                 // a stale (larger) tau only admits extra keys
                 if constexpr (BIT) {
-                    if (n_ok) {                                            // (wave-uniform)
-                        const uint4* rows16 = reinterpret_cast<const uint4*>(p.rows);
-                        const uint4* qs = reinterpret_cast<const uint4*>(q4);
-                        const uint32_t G = bit_graph_lanes(p.stride4), gl = (uint32_t) lane & (G - 1u);
-                        const uint4 qreg = gl < p.stride4 ? qs[gl] : make_uint4(0u, 0u, 0u, 0u);
-                        // rowsel[j] < s1 <= n_rows < 2^31 (launcher): a row id of the view as the gather takes it
-                        bit_graph_distances<false>(rows16, p.stride4, G, nullptr, nullptr, qs, qreg, 0.0f,
-                                                   reinterpret_cast<const int32_t*>(rowsel), (int) n_ok, counts, lane);
-                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                        const bool mine = (uint32_t) lane < n_ok;
-                        const uint32_t br = mine ? p.rank[rowsel[lane]] : 0u;
-                        const bool in_range = br < p.n_rows;
-                        if (mine && !in_range) ctrl->bad = 1;              // never a key, never an address
-                        const uint64_t key = make_key(mine ? counts[lane] : 0.0f, br);
-                        const bool pass = mine && in_range && key < tau;
-                        const uint64_t pm = __ballot(pass);
-                        if (pm) {
-                            const int leader = __ffsll((unsigned long long) pm) - 1;
-                            uint32_t at = 0;
-                            if (lane == leader) at = atomicAdd(&ctrl->count, (uint32_t) __popcll(pm));
-                            at = (uint32_t) __shfl((int) at, leader) + (uint32_t) __popcll(pm & ((1ull << lane) - 1ull));
-                            if (pass && at < IVI_CHUNK) chunk[at] = key;
-                        }
-                    }
+                    if (n_ok)                                              // (wave-uniform)
+                        ivf_iter_bit_rows(reinterpret_cast<const uint4*>(p.rows), p.stride4, reinterpret_cast<const uint4*>(q4), rowsel, n_ok,
+                                          counts, p.rank, p.n_rows, tau, ctrl, chunk, lane);
                 }
                 for (uint32_t j0 = 0; !BIT && j0 < n_ok; j0 += 2 * U) {          // fp32 / binary16 rows
                     uint32_t row[U];

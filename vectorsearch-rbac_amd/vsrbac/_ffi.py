@@ -130,6 +130,8 @@ SYMBOLS = {
     "vsr_hnsw_device_bytes": (_i64, [_vp]),
     "vsr_hnsw_search_quantized": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_hnsw_search_quantized_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_ivf_search_quantized": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_ivf_search_quantized_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_vector_norms": (_i, [_vp, _vp, _i64, _i, _vp]),
     "vsr_l2_normalize": (_i, [_vp, _vp, _i64, _i, _vp]),
     "vsr_spherical_distances": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp]),

@@ -776,6 +776,39 @@ class Corpus:
                                                          d_counts, d_keys))
         return keep
 
+    def search_quantized_ivf(self, bit_index, queries, k, shortlist, probes=1, metric="l2", filters=None, mode="off",
+                             max_probes=32768):
+        """search_quantized with the shortlist taken from the lists of an index (vsr_ivf_search_quantized): `bit_index` is an
+        IvfIndex over this corpus's binary_quantize() (load_ivf_bit / build_ivf_bit); the shortlist is its search_bit_iterative
+        answer for k = shortlist, `probes`, `mode` ("off": search_bit's, max_probes ignored) and `max_probes`, the re-rank is
+        search_quantized's.  `filters` are filters of the bit corpus.  Returns SearchResult and the lists each scan had taken."""
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(queries, dtype=np.float32)))
+        nq, dim = q.shape
+        farr, keep = bit_index.corpus._filter_array(filters, nq)
+        kk = max(int(k), 1)
+        blk = np.full((nq, kk), -1, dtype=np.int64)
+        doc = np.full((nq, kk), -1, dtype=np.int32)
+        row = np.full((nq, kk), -1, dtype=np.int64)
+        dist = np.full((nq, kk), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.int32)
+        scanned = np.zeros(nq, dtype=np.int32)
+        check(self._lib.vsr_ivf_search_quantized(self._h, bit_index._h, _ptr(q), nq, dim, int(k), int(shortlist), int(probes),
+                                                 _metric(metric), farr, _ivf_iterative_mode(mode), int(max_probes), _ptr(blk),
+                                                 _ptr(doc), _ptr(row), _ptr(dist), _ptr(cnt), _ptr(scanned)))
+        del keep
+        return SearchResult(blk, doc, row, dist, cnt), scanned
+
+    def search_quantized_ivf_device(self, bit_index, d_queries, nq, k, shortlist, probes, metric, filters, mode, max_probes,
+                                    d_block, d_doc, d_rows, d_dist, d_counts, d_probes=None, d_keys=None):
+        """search_quantized_ivf with device pointers (ints): d_queries addresses nq x dim floats.  Both stages are enqueued on
+        the bit corpus context's stream; nothing synchronises (vsr_ivf_search_quantized_device)."""
+        farr, keep = bit_index.corpus._filter_array(filters, nq)
+        check(self._lib.vsr_ivf_search_quantized_device(self._h, bit_index._h, d_queries, nq, self.dim, int(k), int(shortlist),
+                                                        int(probes), _metric(metric), farr, _ivf_iterative_mode(mode),
+                                                        int(max_probes), d_block, d_doc, d_rows, d_dist, d_counts, d_probes,
+                                                        d_keys))
+        return keep
+
     def ivf_assign(self, centers, metric="l2"):
         """The pass of the ivfflat build that touches every row (ivfbuild.c:404-445): the nearest centre of each row, in
         the caller's row order -- the `row_list` IvfIndex / vsr_ivf_load take."""
