@@ -132,6 +132,9 @@ struct ScanParams {
                                    // bit 2 = the sample launch of a class-view plan runs register-fed (K2r, vsr_i8r.h)
     uint32_t         dense;        // K2w int8 main launch: 1 = every group's tile list is an identity list over one contiguous run of
                                    // rows (a class-view plan): rows by arithmetic (vsr_mfmaw.h, DENSE)
+    // walk alignment (WalkHint below; DENSE main launch with a block_map only, nullptr otherwise)
+    const uint32_t*  walk_rot;     // the session's rotation word: workgroup b takes block_map[(b + rot) mod gridDim.x]
+    uint32_t*        walk_pos;     // the class view's position word: every workgroup stores its first view row >> 6
     FusedTail        fused;        // K1, nq == 1 only (enable = 0 otherwise)
     // K1s (vsr_scans.h, sparse corpus): rows = interleaved (index, value) entries of 8 bytes, row r owns entries
     // sp_off[r] .. sp_off[r + 1] (an even count: 16-byte loads); the queries are open-addressing tables (SparseStageParams)
@@ -375,8 +378,35 @@ hipError_t launch_rerank(const RerankParams& p, uint32_t n_queries, hipStream_t 
 hipError_t launch_select_rerank(const RerankParams& p, uint32_t n_queries, hipStream_t s);
 // threshold seeds of K2w: per query the m-th smallest of its sampled keys (low word all ones), KEY_EMPTY if fewer;
 // m = lambda + 6 sqrt(lambda) + 4 with lambda = kp * frac * (kept / sampled): frac = the densest pass's sampling fraction
+// Walk alignment: DENSE int8 main launches over one class view start where the launches in flight are reading, so that rows
+// one of them pulled into the Infinity Cache serve the others.  A hint and nothing else: every DENSE main workgroup stores its
+// first view row >> 6 into the view's position word (plain store, last writer wins, any value is acceptable); the seed
+// selection in front of a main launch -- one thread of its block 0 -- translates the word through the plan's table (position
+// slice -> dispatch slot at which THIS launch's block_map reaches those rows) into the session's rotation word, and the main
+// kernel takes block_map[(blockIdx.x + rot) mod n_launch].  rot is a multiple of 8, so padding entries and XCD lanes keep
+// their places; it is written by a completed predecessor in stream order, so a launch's workgroups all see one value.
+struct WalkHint {
+    uint32_t*       rot;           // out: the session's rotation word; nullptr: no hint (every other plan)
+    const uint32_t* pos;           // the class view's position word
+    const uint32_t* table;         // [((n_pos - 1) >> shift) + 1] slots, each a multiple of 8 below n_launch
+    uint32_t        n_pos;         // 64-row units of the view: a position at or past it maps to slot 0
+    uint32_t        shift;         // slice of a position: pos >> shift
+    uint32_t        n_launch;
+    uint32_t        mode;          // 0: the word; 1: `value` in its place (VSR_WALK_POS); 2: `value` is the rotation (VSR_WALK_ROT)
+    uint32_t        value;
+};
+__device__ inline void walk_hint_publish(const WalkHint& w)
+{
+    if (!w.rot) return;
+    uint32_t r = w.value;
+    if (w.mode != 2u) {
+        const uint32_t pos = w.mode == 1u ? w.value : *w.pos;
+        r = pos < w.n_pos ? w.table[pos >> w.shift] : 0u;
+    }
+    *w.rot = r < w.n_launch ? r & ~7u : 0u;
+}
 hipError_t launch_seed_select(const uint64_t* samp, const uint32_t* samp_cnt, uint32_t cap, float kp_frac, uint64_t* tau,
-                              uint32_t n_queries, hipStream_t s);
+                              uint32_t n_queries, hipStream_t s, const WalkHint& walk = WalkHint{});
 // One wave per query for both selections of an exact_screen plan (int8 planes): 64-thread workgroups inside what four
 // resident int8 main workgroups leave of a CU -- 96 VGPRs and a wave slot per SIMD, 32 KB of LDS (vsr_kernels.hip).
 // vsr_ctx::select_wave (VSR_SELECT_WAVE=0) keeps seed_select_kernel / select_rerank_kernel instead.
@@ -399,7 +429,7 @@ inline size_t select_emit_wave_lds_bytes(uint32_t kp)                           
     return (size_t) np2 * 8;
 }
 hipError_t launch_seed_select_wave(const uint64_t* samp, const uint32_t* samp_cnt, uint32_t cap, float kp_frac, uint64_t* tau,
-                                   uint32_t n_queries, hipStream_t s);
+                                   uint32_t n_queries, hipStream_t s, const WalkHint& walk = WalkHint{});
 // the final selection of an exact_screen plan (kp = k <= GQ_MAX_KP): select, sort, count / flag rules and outputs of
 // select_rerank_kernel's exact_screen path, without its re-rank waves and without reading the fp32 query
 hipError_t launch_select_emit_wave(const RerankParams& p, uint32_t n_queries, hipStream_t s);

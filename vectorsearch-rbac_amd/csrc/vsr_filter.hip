@@ -258,6 +258,8 @@ static void build_class_view(vsr_corpus* c)
     ok = ok && hipMalloc(&v->d_norm2_8, norm_bytes) == hipSuccess;
     ok = ok && hipMalloc(&v->d_rank, (size_t) total * sizeof(uint32_t)) == hipSuccess;
     ok = ok && hipMalloc(&v->d_tiles, tiles.size() * sizeof(uint2)) == hipSuccess;
+    ok = ok && hipMalloc(&v->d_walk_pos, 64) == hipSuccess;
+    ok = ok && hipMemsetAsync(v->d_walk_pos, 0, 64, ctx->stream) == hipSuccess;
     ok = ok && hipMemcpy(v->d_rank, rank.data(), (size_t) total * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemcpy(v->d_tiles, tiles.data(), tiles.size() * sizeof(uint2), hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemsetAsync(reinterpret_cast<char*>(v->d_scr8) + (size_t) total * 128, 0, 32 * 128, ctx->stream) == hipSuccess;

@@ -1188,10 +1188,11 @@ hipError_t launch_select_emit_wave(const RerankParams& p, uint32_t n_queries, hi
 // Threshold seeds of K2w: per query, the m-th smallest of its sampled keys; every row ranking at or before it stays
 // eligible in the main pass (low word all ones: ties of that distance included); too few samples: no threshold.
 __global__ __launch_bounds__(256) void seed_select_kernel(const uint64_t* samp, const uint32_t* samp_cnt, uint32_t cap,
-                                                          float kp_frac, uint64_t* tau, uint32_t n_queries)
+                                                          float kp_frac, uint64_t* tau, uint32_t n_queries, const WalkHint walk)
 {
     __shared__ uint32_t sm_hist[4][256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (blockIdx.x == 0 && threadIdx.x == 0) walk_hint_publish(walk);   // the rotation of the main launch that follows (vsr_device.h)
     const uint32_t q = blockIdx.x * 4 + (uint32_t) wave;
     if (q >= n_queries) return;                              // wave-uniform; no workgroup barrier below
     __shared__ uint64_t sm_keep[4][GQ_SAMPLE_CAP / 4];
@@ -1206,10 +1207,10 @@ __global__ __launch_bounds__(256) void seed_select_kernel(const uint64_t* samp, 
 }
 
 hipError_t launch_seed_select(const uint64_t* samp, const uint32_t* samp_cnt, uint32_t cap, float kp_frac, uint64_t* tau,
-                              uint32_t n_queries, hipStream_t s)
+                              uint32_t n_queries, hipStream_t s, const WalkHint& walk)
 {
     if (cap != GQ_SAMPLE_CAP || !(kp_frac > 0.0f)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(seed_select_kernel, dim3((n_queries + 3) / 4), dim3(256), 0, s, samp, samp_cnt, cap, kp_frac, tau, n_queries);
+    hipLaunchKernelGGL(seed_select_kernel, dim3((n_queries + 3) / 4), dim3(256), 0, s, samp, samp_cnt, cap, kp_frac, tau, n_queries, walk);
     return hipGetLastError();
 }
 
@@ -1219,13 +1220,14 @@ hipError_t launch_seed_select(const uint64_t* samp, const uint32_t* samp_cnt, ui
 // lambda <= kp_frac), so a workgroup is 1 KB of histogram + 8 m bytes (~26 keys at the headline's shape) inside 96 VGPRs: it
 // takes any free wave slot, and a 1000-query batch is one resident round.
 __global__ __launch_bounds__(SELW_THREADS, SELW_OCC) void seed_select_wave_kernel(const uint64_t* samp, const uint32_t* samp_cnt, uint32_t cap,
-                                                                                  float kp_frac, uint64_t* tau, uint32_t keep_cap)
+                                                                                  float kp_frac, uint64_t* tau, uint32_t keep_cap, const WalkHint walk)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     uint64_t* keep = reinterpret_cast<uint64_t*>(smem);      // [keep_cap]
     __shared__ uint32_t hist[256];
     const int lane = threadIdx.x;
     const uint32_t q = blockIdx.x;
+    if (q == 0 && lane == 0) walk_hint_publish(walk);        // the rotation of the main launch that follows (vsr_device.h)
     const uint32_t cnt = samp_cnt[q];
     const uint32_t n = cnt < cap ? cnt : cap;
     // a buffer that overflowed holds a subset of the sample: the effective sampling fraction shrinks with it
@@ -1239,13 +1241,13 @@ __global__ __launch_bounds__(SELW_THREADS, SELW_OCC) void seed_select_wave_kerne
 }
 
 hipError_t launch_seed_select_wave(const uint64_t* samp, const uint32_t* samp_cnt, uint32_t cap, float kp_frac, uint64_t* tau,
-                                   uint32_t n_queries, hipStream_t s)
+                                   uint32_t n_queries, hipStream_t s, const WalkHint& walk)
 {
     if (cap != GQ_SAMPLE_CAP || !(kp_frac > 0.0f)) return hipErrorInvalidValue;
     if (n_queries == 0) return hipSuccess;
     const uint32_t keep_cap = seed_wave_keep_cap(kp_frac);
     hipLaunchKernelGGL(seed_select_wave_kernel, dim3(n_queries), dim3(SELW_THREADS), seed_wave_lds_bytes(keep_cap), s, samp, samp_cnt, cap,
-                       kp_frac, tau, keep_cap);
+                       kp_frac, tau, keep_cap, walk);
     return hipGetLastError();
 }
 

@@ -130,7 +130,17 @@ __global__ __launch_bounds__(MW_THREADS, mw_occ(NCH, PL, SAMPLE)) void mfma_wide
 
     uint32_t lo = 0, mapped_block = 0;
     if (p.block_map) {
-        const uint2 m = p.block_map[blockIdx.x];
+        uint32_t map_slot = blockIdx.x;
+        if constexpr (DENSE) {
+            // walk alignment (WalkHint, vsr_device.h): the map rotated by what the seed selection in front of this launch wrote --
+            // one value for the whole launch, a multiple of 8 (XCD lanes and padding entries keep their places), bounded here
+            if (p.walk_rot) {
+                const uint32_t rot = *p.walk_rot;
+                map_slot += rot < gridDim.x ? rot & ~7u : 0u;
+                map_slot -= map_slot >= gridDim.x ? gridDim.x : 0u;
+            }
+        }
+        const uint2 m = p.block_map[map_slot];
         if (m.x == 0xFFFFFFFFu) return;                                        // padding workgroup of a short XCD lane
         lo = m.x;
         mapped_block = m.y;
@@ -286,6 +296,7 @@ __global__ __launch_bounds__(MW_THREADS, mw_occ(NCH, PL, SAMPLE)) void mfma_wide
         row_hi = t1 > t0 ? (uint32_t) __builtin_amdgcn_readfirstlane((int) (db.x + db.y)) : row_lo;
         bad_row = row_hi > p.n_rows || row_hi < row_lo;
         row_hi = bad_row ? row_lo : row_hi;
+        if (p.walk_pos && tid == 0) *p.walk_pos = row_lo >> 6;     // where this launch is reading: a hint for the next one (benign race)
     }
     auto start_dense = [&](uint32_t it_, int32_t& row, uint64_t& bw, float& nrm) {   // the lane's slot of tile it_
         const uint32_t rr = row_lo + it_ * (uint32_t) MW_ROWS + (uint32_t) lane;

@@ -18,6 +18,9 @@ struct PlanScalars {
     bool     k2w = false;         // ... on K2w: workgroup-shared row tiles, up to 128 queries per pass (vsr_mfmaw.h)
     bool     int8 = false;        // ... on the corpus's int8 planes (L2, integer 0..255 rows and queries)
     bool     class_view = false;  // ... on the corpus's class view of the int8 planes (every pass a whole permission class)
+    bool     walk = false;        // ... with the main launch's block_map rotated to where the launches in flight are reading (walk_table)
+    uint32_t walk_n_pos = 0;      // 64-row units of the view
+    uint32_t walk_shift = 0;      // walk_table's slice of a position p: p >> walk_shift
     bool     k2g = false;         // ... on K2g: long rows, 256-query passes, coarse planes (vsr_gemm.h); implies k2w
     bool     sparse_global = false;   // K1s (sparse corpus): the query tables stay in global memory (vsr_scans.h, GLOBAL_TAB)
     uint32_t keep = 0;            // partial list length kp (K2: 2k screening survivors; else k)
@@ -49,11 +52,13 @@ struct Plan : PlanScalars {
     std::vector<ScanGroup>   groups_s;       // sample pass (threshold seeding): same passes, fewer workgroups
     std::vector<SelectQuery> seedq;          // per query: merge the sample pass's lists into a seed threshold
     std::vector<uint2>       block_map;      // shared-pass launches: workgroup -> (group, block), XCD-aware (vsr_plan.hip)
+    std::vector<uint32_t>    walk_table;     // walk: position slice -> slot (a multiple of 8) at which block_map reaches its rows (WalkHint)
 
     void reset()                             // keeps the vectors' capacity: one plan per batch, no allocation once warm
     {
         static_cast<PlanScalars&>(*this) = PlanScalars{};
         q_slots.clear(); groups.clear(); list_ids.clear(); sel1.clear(); selq.clear(); groups_s.clear(); seedq.clear(); block_map.clear();
+        walk_table.clear();
     }
 };
 

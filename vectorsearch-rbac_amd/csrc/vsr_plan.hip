@@ -6,6 +6,7 @@
 // PlanScratch and keep their capacity, so a warm planner allocates nothing.
 #include "vsr_plan.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 
@@ -274,6 +275,55 @@ bool take_class_view(const PlanIn& in, const Plan& plan, std::vector<Pass>& pass
         p.n_tiles = (v->rows[cls] + 15) / 16;
     }
     return true;
+}
+
+// ---- stage 3c: walk alignment (WalkHint, vsr_device.h) -------------------------------------------------------------
+// ONE canonical walk order: the passes of a class-view plan in ascending view position, so that every launch over a corpus
+// visits the classes in the same order whichever query of the batch named a class first (cut_passes emits parts in first-seen
+// order).  The passes of one class stay adjacent and in their order (q_off ascends with it).  Results do not depend on it.
+#ifndef VSR_WALK_SLICES
+#define VSR_WALK_SLICES 512        // slices of the view in a plan's walk table (2 KB of the staging block)
+#endif
+#ifndef VSR_WALK_LEAD
+#define VSR_WALK_LEAD 8            // rows of 8 dispatch slots a launch starts ahead of (< 0: behind) the published position: the word is
+#endif                             // a seed selection and a launch old when the first workgroups start.  Measured on the headline step
+                                   // (profiles/r8): +8 beats 0 in five adjacent pairs of five, -8 equals 0; variant libraries only
+
+bool takes_walk(const vsr_ctx* ctx, const Plan& plan)
+{
+    return plan.class_view && ctx->walk_align && !ctx->no_xcd_map && ctx->no_k2i && VSR_MW_DENSE;
+}
+
+void order_walk(const ClassView* v, std::vector<Pass>& passes)
+{
+    auto key = [v](const Pass& p) { return p.f && p.f->scanned_rows > 0 ? v->start[(size_t) p.f->view_class] : 0xFFFFFFFFu; };
+    auto before = [&](const Pass& a, const Pass& b) { return key(a) != key(b) ? key(a) < key(b) : a.q_off < b.q_off; };
+    if (!std::is_sorted(passes.begin(), passes.end(), before)) std::sort(passes.begin(), passes.end(), before);
+}
+
+// The table of a plan: slice s of the view (positions s << shift ..., a position = 64 rows) -> the first row of 8 dispatch
+// slots at which the mapped launch has a workgroup reaching past the slice's first row.  A row in a class this batch does
+// not scan maps to the next class it does scan; rows behind the last scanned class map to slot 0.
+void build_walk_table(const ClassView* v, Plan& plan)
+{
+    plan.walk_n_pos = v->n_rows >> 6;
+    plan.walk_shift = 0;
+    while (((plan.walk_n_pos - 1) >> plan.walk_shift) + 1 > (uint32_t) VSR_WALK_SLICES) ++plan.walk_shift;
+    const uint32_t n_slices = ((plan.walk_n_pos - 1) >> plan.walk_shift) + 1;
+    plan.walk_table.assign(n_slices, 0u);
+    const uint32_t n_t = plan.n_launch / XCDS;
+    const uint32_t lead = (uint32_t) (((int64_t) VSR_WALK_LEAD % (int64_t) n_t + (int64_t) n_t) % (int64_t) n_t);
+    uint64_t reach = 0;                                     // first view row no workgroup of slots [0, 8 t + 8) reaches
+    for (uint32_t t = 0, s = 0; t < n_t && s < n_slices; ++t) {
+        for (uint32_t l = 0; l < XCDS; ++l) {
+            const uint2 m = plan.block_map[(size_t) t * XCDS + l];
+            if (m.x == 0xFFFFFFFFu) continue;
+            const ScanGroup& g = plan.groups[m.x];
+            const uint64_t first = (uint64_t) (g.tiles - v->d_tiles) * 16;
+            reach = std::max(reach, first + 16 * ((uint64_t) g.n_tiles * (m.y + 1) / g.n_blocks));
+        }
+        for (; s < n_slices && ((uint64_t) s << (plan.walk_shift + 6)) < reach; ++s) plan.walk_table[s] = (t + lead) % n_t * XCDS;
+    }
 }
 
 // The stride the plan's sampling starts from: VIEW_SAMPLE_STRIDE for an int8 class-view plan that can sample on K2r (the
@@ -678,10 +728,14 @@ bool vsr::make_plan(const vsr_ctx* ctx, const vsr_corpus* c, int nq, int k, int 
         const uint32_t widest = cut_passes(in, w, s.items, s.passes, plan.q_slots);
         set_family(in, w, widest, plan);
         plan.class_view = take_class_view(in, plan, s.passes);
+        plan.walk = takes_walk(ctx, plan);
+        if (plan.walk) order_walk(c->class_view.get(), s.passes);
         const bool thin = first_stride(in, plan) != ctx->sample_stride;
         const LaunchSize ls = size_launch(in, plan, s.passes);
         emit_groups(in, w.i8wide, ls, s, plan);
         if (plan.k2 || plan.mq) map_blocks_to_xcds(s.lane, plan);
+        plan.walk = plan.walk && !plan.block_map.empty();
+        if (plan.walk) build_walk_table(c->class_view.get(), plan);
         if (plan.k2w) {
             const bool ok = plan_wide_sampling(in, s, plan);
             plan.k2r_sample = ok && plan.class_view && plan.k2i_sample && ctx->sample_reg;   // same geometry, same entries (vsr_i8r.h)
@@ -734,5 +788,6 @@ std::string vsr::scan_kernel_name(const Plan& plan, const vsr_corpus* c, int met
         }
     std::string name = buf;
     if (plan.class_view) name.insert(name.rfind(')'), ", class view");
+    if (plan.walk) name.insert(name.rfind(')'), ", walk-aligned over " + std::to_string(plan.n_launch) + " slots");
     return name;
 }

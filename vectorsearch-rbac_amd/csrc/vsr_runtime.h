@@ -108,7 +108,8 @@ struct vsr_ctx {
     uint32_t seed_block_div = 1;  // VSR_SEED_DIV
     int64_t seed_min_pass_rows = 2048;   // average rows per pass below which the warm-up it removes is too small to pay
     // 64 bytes of device words: [0] running count of flagged queries; byte 16: the kernels' bounds-guard word (checked by
-    // vsr_screening_check); byte 32: one all-ones 64-bit word, the "bitmap" of passes without a permission bitmap
+    // vsr_screening_check); byte 32: one all-ones 64-bit word, the "bitmap" of passes without a permission bitmap; byte 48: the
+    // session's walk rotation (walk_rot_word)
     int32_t* d_flag_total = nullptr;
     uint32_t* err_word() const { return reinterpret_cast<uint32_t*>(d_flag_total) + 4; }
     const uint64_t* ones_word() const { return reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(d_flag_total) + 32); }
@@ -164,6 +165,14 @@ struct vsr_ctx {
     bool k2i_wide = false;         // VSR_K2I_WIDE=1 (with VSR_K2I=1): 128-column passes on K2i
     int  force_epi = -1;           // VSR_FORCE_EPI=0|1: the main launch's survivor handling regardless of the estimate (tests)
     bool no_class_view = false;    // VSR_NO_CLASS_VIEW=1: role pre-filters scan the base-order int8 planes, never the class view (A/B)
+    // walk alignment of the DENSE int8 main launches of class-view plans (WalkHint, vsr_device.h)
+    bool walk_align = true;        // VSR_WALK_ALIGN=0: no rotation, no position word, passes in first-seen order (A/B: the code before it)
+    bool walk_pos_set = false, walk_rot_set = false, walk_spread = false;
+    uint32_t walk_pos = 0;         // VSR_WALK_POS=<n>: the seed selection translates n instead of the position word (tests)
+    uint64_t walk_rot = 0;         // VSR_WALK_ROT=<n>: rot = (8 n) mod n_launch, bypassing the word (tests);
+                                   // VSR_WALK_ROT=spread: the i-th context of the process starts i/3 of the map in (A/B: misaligned on purpose)
+    uint32_t ordinal = 0;          // this context is the process's ordinal-th
+    uint32_t* walk_rot_word() const { return reinterpret_cast<uint32_t*>(d_flag_total) + 12; }   // byte 48 of d_flag_total's block
     int  screen_level = 2;         // search_impl -> make_plan: 2 = every screening tier, 1 = no coarse tier (K2g), 0 = exact only
     bool last_coarse = false;      // the last search screened on the coarse planes: its flagged queries go to the fine tier first
 
@@ -218,12 +227,14 @@ struct ClassView {
     float*    d_norm2_8 = nullptr;       // [n_rows + 64]
     uint32_t* d_rank = nullptr;          // [n_rows] view row -> base row (pads: 0, never emitted)
     uint2*    d_tiles = nullptr;         // [n_rows / 16] (16 t, rows of the class that tile t holds: 16, fewer at a class's end, 0)
+    uint32_t* d_walk_pos = nullptr;      // one word, zero at creation: first view row >> 6 of the DENSE main workgroup that started
+                                         // last, whichever session launched it (walk alignment: WalkHint, vsr_device.h)
     uint32_t  n_rows = 0;                // with the pads: a multiple of 64
     std::vector<uint32_t> start, rows;   // per class: first view row, row count
     size_t bytes() const { return ((size_t) n_rows + 32) * 128 + ((size_t) n_rows + 64) * 4 + (size_t) n_rows * 4 + (size_t) n_rows / 16 * 8; }
     ~ClassView()
     {
-        void* ptrs[] = {d_scr8, d_norm2_8, d_rank, d_tiles};
+        void* ptrs[] = {d_scr8, d_norm2_8, d_rank, d_tiles, d_walk_pos};
         for (void* p : ptrs)
             if (p) (void) hipFree(p);
     }

@@ -106,6 +106,18 @@ extern "C" int vsr_open(int device, vsr_ctx** out)
     if ((env = getenv("VSR_SEED_STRIDE"))) ctx->seed_stride = (uint32_t) std::max(2, atoi(env));
     if ((env = getenv("VSR_SEED_DIV"))) ctx->seed_block_div = (uint32_t) std::max(1, atoi(env));
     if ((env = getenv("VSR_NO_SCREENING"))) ctx->screening = atoi(env) == 0;
+    static std::atomic<uint32_t> g_ctx_ordinal{0};
+    ctx->ordinal = g_ctx_ordinal.fetch_add(1, std::memory_order_relaxed);
+    if ((env = getenv("VSR_WALK_ALIGN"))) ctx->walk_align = atoi(env) != 0;
+    if ((env = getenv("VSR_WALK_POS"))) {
+        ctx->walk_pos = (uint32_t) std::min<unsigned long long>(strtoull(env, nullptr, 0), 0xFFFFFFFFull);
+        ctx->walk_pos_set = true;
+    }
+    if ((env = getenv("VSR_WALK_ROT"))) {
+        ctx->walk_spread = strcmp(env, "spread") == 0;
+        ctx->walk_rot_set = !ctx->walk_spread;
+        ctx->walk_rot = ctx->walk_spread ? 0 : strtoull(env, nullptr, 0);
+    }
     *out = ctx.release();
     return VSR_OK;
 }

@@ -286,6 +286,7 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
     const size_t off_qs = sb.add(plan.q_slots);
     const size_t off_sq = sb.add(plan.selq);
     const size_t off_bm = sb.add(plan.block_map);
+    const size_t off_wt = sb.add(plan.walk_table);
 
     StageParams st{};
     RCCHK(stage_host_part(ctx, sb, off_qn, off_g, c->format, q.h_queries, q.d_queries, nq, q.dim, qfloats, st));
@@ -361,8 +362,26 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
         sp.capq = GQ_SAMPLE_CAP;
         sp.k2i = plan.k2r_sample ? 4u : plan.k2i_sample ? 2u : 0u;   // (bit 2: the sample launch on K2r; bit 1: on K2i; bit 0: the main launch)
         HIPCHK(launch_pass(plan.n_blocks_s, ctx->stream));
+        // walk alignment: the seed selection also turns the view's position word into this session's rotation of the main launch
+        WalkHint walk{};
+        if (plan.walk) {
+            const uint32_t n_rows8 = plan.n_launch / 8;     // rotations are whole rows of 8 slots: one per XCD
+            walk.rot = ctx->walk_rot_word();
+            walk.pos = c->class_view->d_walk_pos;
+            walk.table = reinterpret_cast<const uint32_t*>(ds + off_wt);
+            walk.n_pos = plan.walk_n_pos;
+            walk.shift = plan.walk_shift;
+            walk.n_launch = plan.n_launch;
+            if (ctx->walk_rot_set || ctx->walk_spread) {
+                walk.mode = 2u;
+                walk.value = 8u * (uint32_t) (ctx->walk_spread ? (uint64_t) (ctx->ordinal % 3u) * n_rows8 / 3u : ctx->walk_rot % n_rows8);
+            } else if (ctx->walk_pos_set) {
+                walk.mode = 1u;
+                walk.value = ctx->walk_pos;
+            }
+        }
         HIPCHK((wave_select ? launch_seed_select_wave : launch_seed_select)(ctx->d_samp.as<uint64_t>(), scnt, GQ_SAMPLE_CAP, plan.kp_frac,
-                                                                            ctx->d_tau.as<uint64_t>(), (uint32_t) nq, ctx->stream));
+                                                                            ctx->d_tau.as<uint64_t>(), (uint32_t) nq, ctx->stream, walk));
         HIPCHK(sample.stop());
         // ---- main pass ----
         hipStream_t main_stream = ctx->stream;
@@ -391,6 +410,10 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
         sp.qcnt = qcnt;
         sp.capq = GQ_CAP;
         if (!plan.block_map.empty() && !ctx->no_xcd_map) sp.block_map = reinterpret_cast<const uint2*>(ds + off_bm);
+        if (plan.walk && sp.block_map && sp.dense) {        // (the sample launch above knows neither word)
+            sp.walk_rot = walk.rot;
+            sp.walk_pos = c->class_view->d_walk_pos;
+        }
         HIPCHK(launch_pass(sp.block_map ? plan.n_launch : plan.n_blocks, main_stream));
         HIPCHK(main.stop());
         if (ctx->scan_lane) {                               // the selection waits for the lane

@@ -161,8 +161,8 @@ class Context:
 
     def last_scan_kernel(self):
         """Kernel instantiation the main scan launch of this session's last search resolved to."""
-        buf = C.create_string_buffer(200)
-        check(self._lib.vsr_last_scan_kernel(self._h, buf, 200))
+        buf = C.create_string_buffer(512)                # (a class-view int8 plan names three kernels and their variants: > 200 characters)
+        check(self._lib.vsr_last_scan_kernel(self._h, buf, 512))
         return buf.value.decode()
 
     def set_screening(self, enable=True):
