@@ -590,6 +590,37 @@ int vsr_hnsw_export_shape(const vsr_hnsw* index, int32_t* m, int32_t* n_elem, in
 int vsr_hnsw_export(const vsr_hnsw* index, int32_t* level, int32_t* nbr0, int32_t* tid_count, int64_t* tids, int32_t* up_slot,
                     int32_t* up_nbr);
 int vsr_hnsw_info(const vsr_hnsw* index, int32_t* n_elem, int32_t* entry, int32_t* entry_level, int32_t* max_level);
+/* INSERT into an indexed table (hnswinsert.c), for a batch of rows: extends a graph that exists instead of rebuilding it.  Takes
+ * the arrays vsr_hnsw_load takes; the row format (fp32, halfvec or bit) comes from the corpus.
+ *   - `corpus` holds the rows the prior graph was made over plus new rows.  The prior graph's heap TIDs are caller row indices
+ *     of `corpus`, each covered row named once (n0 of them); that those rows ARE the vectors the graph was built on is the
+ *     caller's contract and cannot be checked.
+ *   - The new rows are the caller rows no TID names.  They are inserted in ascending internal row order, (document_id, block_id),
+ *     the order vsr_hnsw_build inserts in: the i-th becomes element n_elem + i with that one TID.  Prior elements keep their ids,
+ *     TID lists, levels and up_slot; new upper elements take slots n_upper, n_upper + 1, ... in element order; when a new element's
+ *     level exceeds max_level the upper arrays are re-strided to the new max_level.
+ *   - Levels: the seeded xorshift64* stream of vsr_hnsw_build, one draw per row; the i-th new row takes draw n0 + i.  Batches: the
+ *     build's schedule max(1, min(done / 8, 4096, left)) with done starting at n_elem, its two phases, its entry-point rule, its
+ *     visited-table restart (which begins again from the caller's arrays).  The per-edge distances the re-selection of a full list
+ *     reads are not part of an export: they are recomputed from the rows on the GPU before the first batch.
+ *     The schedule depends on done alone, so vsr_hnsw_build* of a prefix that ends at one of the full build's batch boundaries,
+ *     extended over all rows with the build's seed, IS the full build's graph wherever that build is reproducible (integer-valued
+ *     rows: tests/test_gpu_hnsw_extend.py compares array for array).  Off a boundary the graph is deterministic and a valid
+ *     graph of the same batched algorithm, parity with pgvector being recall (test/t/013_hnsw_vector_insert_recall.pl's floors).
+ *   - metric as for the matching build call: L2 / IP / cosine over unit rows (fp32, halfvec); Hamming / Jaccard over a bit
+ *     corpus, where it is also the index's opclass.  m, ef_construction, halfvec dimension, a view corpus: the build's refusals.
+ *   - flags must be 0: VSR_HNSW_BUILD_MERGE_DUPLICATES is VSR_ERR_UNSUPPORTED (an inserted row is never folded into an element,
+ *     where pgvector would); a prior graph that HAS multi-TID elements is accepted and extended.
+ *   - A sparse corpus: VSR_ERR_UNSUPPORTED, the message names sparsevec (the sparse build has no element -> row form).
+ *   - The prior graph is written through, so it is checked on the host beyond vsr_hnsw_load's checks, VSR_ERR_INVALID naming the
+ *     element: neighbour ids in [-1, n_elem); lists packed (no id after a -1); a neighbour on layer lc has level >= lc; up_slot in
+ *     [0, n_upper) and distinct exactly where level >= 1, -1 elsewhere; entry on the highest level; no row under two TIDs.
+ *   - n_elem = 0 (entry -1) is vsr_hnsw_build* with flags 0, the same graph; no new rows is vsr_hnsw_load*.
+ * The result is an ordinary index (search, export, info, device_bytes, set_predicate_aware).  Synchronises. */
+int vsr_hnsw_extend(vsr_corpus* corpus, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
+                    const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
+                    int32_t n_upper, int32_t max_level,
+                    int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out);
 /* Predicate-aware walk (off by default: pgvector filters what the index returns, hnswscan.c + the executor's RLS qual).  On:
  * the layer-0 search of later vsr_hnsw_search* calls applies the query's filter while it walks, ACORN-1 style -- the result
  * set and the candidate set hold permitted elements only, and an expansion also takes the permitted neighbours of its

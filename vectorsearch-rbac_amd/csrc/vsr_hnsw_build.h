@@ -73,3 +73,8 @@ hipError_t vsr_hnsw_dedup_elements(const float4* rows, uint32_t n, uint32_t stri
 hipError_t vsr_hnsw_build_batch(vsr::HnswBuildParams& p, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt, uint64_t* d_val_alt,
                                 hipStream_t s);
 size_t vsr_hnsw_build_sort_bytes(uint32_t rec_cap);
+// vsr_hnsw_extend: fills p.dist0 / p.up_dist for the lists of elements 0 .. n_prior - 1 from the ids p.nbr0 / p.up_nbr hold (one
+// launch on s, no synchronisation).  d_up_owner[n_upper_prior]: upper slot -> its element, -1 for a slot no element names.  Every
+// id in those lists is in [-1, n_prior), lists are packed, and a neighbour on layer lc has an upper slot: the caller checked.
+hipError_t vsr_hnsw_edge_distances(const vsr::HnswBuildParams& p, uint32_t n_prior, const int32_t* d_up_owner, uint32_t n_upper_prior,
+                                   hipStream_t s);

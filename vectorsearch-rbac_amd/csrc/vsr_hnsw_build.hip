@@ -52,6 +52,11 @@
 // returns and the order of every sum do not, so the build stays deterministic.  No merging build: the pre-pass compares
 // fixed-stride rows.  Parity: pgvector's test/t/028_hnsw_sparsevec_build_recall.pl floors (tests/test_gpu_hnsw_sparse.py).
 //
+// Extension (vsr_hnsw_extend): the same batches inserted into a graph that arrived as arrays.  The one piece of state such a graph
+// lacks, the distance of every edge (dist0 / up_dist, read when a full list is re-selected), is filled in by hnsw_edge_dist_kernel
+// before the first batch; elements reach their rows through elem_row whenever element != internal row (a merged prior graph, new
+// rows that sort between old ones).  fp32, halfvec and bit rows; tests/test_gpu_hnsw_extend.py.
+//
 // Parity definition (tests/test_gpu_index.py): recall@20 at ef_search = 40 against the exact scan >= pgvector's TAP
 // thresholds on its own case (10 000 x 3-d: 0.99; inner product 0.97), and within 0.01 of that serial build's recall on
 // the same rows; and (tests/test_gpu_hnsw_build_model.py) graph identity with the batched model, as above.
@@ -484,9 +489,82 @@ __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildPar
     }
 }
 
+// ---- extension (vsr_hnsw_extend): the per-edge distances of a graph that arrived without them.  One wave per (element, layer)
+// list of the prior graph: lists 0 .. n_prior - 1 are the layer-0 lists, the rest (slot, layer) pairs of the upper arrays, whose
+// owner comes from up_owner[slot] (-1: a slot no element names).  The ids go to the wave's LDS, hb_distances takes the owner's row
+// as the left operand, and the rank values land where phase 1 and the link kernel would have left them.  The host has bounded every
+// id the gather goes through (hnsw_extend_prepare, vsr_hnsw_rt.hip); waves are independent: no workgroup barrier ----
+template <bool IND, int ROWS>
+__global__ __launch_bounds__(256) void hnsw_edge_dist_kernel(const HnswBuildParams p, const uint32_t n_prior, const int32_t* __restrict__ up_owner,
+                                                             const uint32_t n_upper_prior)
+{
+    __shared__ __align__(16) int32_t ids_all[4][HB_NBR];
+    __shared__ __align__(16) float nd_all[4][HB_NBR];
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const uint64_t li = (uint64_t) blockIdx.x * 4 + wave;
+    uint32_t e;
+    int lc = 0;
+    if (li < n_prior) {
+        e = (uint32_t) li;
+    } else {
+        const uint64_t u = li - n_prior, slot = u / p.max_level;
+        if (slot >= n_upper_prior) return;
+        const int32_t owner = up_owner[slot];
+        lc = (int) (u % p.max_level) + 1;
+        if (owner < 0 || lc > p.level[owner]) return;
+        e = (uint32_t) owner;
+    }
+    int32_t* ids = ids_all[wave];
+    float* nd = nd_all[wave];
+    const uint32_t lm = lc == 0 ? 2 * p.m : p.m;                              // (<= 200 < HB_NBR)
+    float* dl;
+    const int32_t* nl = hb_list(p, e, lc, &dl);
+    int cnt = 0;
+    bool open = true;                                                         // the valid prefix: lists are packed
+    for (uint32_t j0 = 0; j0 < lm; j0 += 64) {
+        const uint32_t j = j0 + (uint32_t) lane;
+        const int32_t my = j < lm ? nl[j] : -1;
+        ids[j] = my;
+        const uint64_t gap = __ballot(my < 0);
+        if (open) {
+            if (gap == 0) cnt += 64;
+            else { cnt += __ffsll((unsigned long long) gap) - 1; open = false; }
+        }
+    }
+    wave_sync();
+    if (cnt == 0) return;
+    hb_distances<IND, ROWS>(p, hb_row<IND>(p, e), ids, cnt, nd, lane);
+    for (int j = lane; j < cnt; j += 64) dl[j] = mono_to_float(mono_bits(nd[j]));   // as a key carries it (-0 -> +0)
+}
+
 }  // namespace vsr
 
 using namespace vsr;
+
+template <bool IND, int ROWS>
+static hipError_t edge_distances(const HnswBuildParams& p, uint32_t n_prior, const int32_t* d_up_owner, uint32_t n_upper_prior, hipStream_t s)
+{
+    const uint64_t lists = (uint64_t) n_prior + (uint64_t) n_upper_prior * p.max_level;
+    if (lists == 0) return hipSuccess;
+    if ((lists + 3) / 4 > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_edge_dist_kernel<IND, ROWS>), dim3((uint32_t) ((lists + 3) / 4)), dim3(256), 0, s, p, n_prior, d_up_owner,
+                       n_upper_prior);
+    return hipGetLastError();
+}
+
+hipError_t vsr_hnsw_edge_distances(const HnswBuildParams& p, uint32_t n_prior, const int32_t* d_up_owner, uint32_t n_upper_prior, hipStream_t s)
+{
+    if (p.sparse || 2 * p.m > (uint32_t) HB_NBR) return hipErrorInvalidValue;   // (no element -> row instantiation over sparse rows)
+    if (p.bits)
+        return p.elem_row ? edge_distances<true, ROWS_BIT>(p, n_prior, d_up_owner, n_upper_prior, s)
+                          : edge_distances<false, ROWS_BIT>(p, n_prior, d_up_owner, n_upper_prior, s);
+    if (p.halves)
+        return p.elem_row ? edge_distances<true, ROWS_HALF>(p, n_prior, d_up_owner, n_upper_prior, s)
+                          : edge_distances<false, ROWS_HALF>(p, n_prior, d_up_owner, n_upper_prior, s);
+    return p.elem_row ? edge_distances<true, ROWS_F32>(p, n_prior, d_up_owner, n_upper_prior, s)
+                      : edge_distances<false, ROWS_F32>(p, n_prior, d_up_owner, n_upper_prior, s);
+}
 
 // host side: see vsr_hnsw_rt.hip (vsr_hnsw_build) for the batch loop; these are the two launches and the sort of a batch
 template <bool IND, int ROWS>

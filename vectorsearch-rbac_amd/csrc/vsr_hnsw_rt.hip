@@ -213,8 +213,22 @@ static uint32_t hnsw_build_sparse_slots(const vsr_corpus* c, RowFormat expect)
 // build's guard-word bits (HB_ERR_VISITED / HB_ERR_RECORDS / HB_ERR_CANDIDATES) when a kernel set one (caps: entries of the sorted
 // candidate array, at least ef_construction + 2 m); the partial index is then freed, the bits
 // are cleared from the session's word, *out stays NULL and the return value is VSR_OK: hnsw_build decides what follows.
-static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out,
-                           const char* who, uint32_t* slots_io, uint32_t caps, uint32_t* guard)
+//
+// prior (vsr_hnsw_extend; nullptr: a build): the graph the batches are inserted into.  A build is the extension of nothing: no
+// prior elements, no draws skipped, the schedule from done = 0, distances all zero.  Everything an attempt changes is a device copy,
+// so a restart begins again from the caller's arrays.
+struct HnswPrior {
+    int32_t n_elem = 0, entry = -1, n_upper = 0, max_level = 1;
+    const int32_t *level = nullptr, *nbr0 = nullptr, *tid_count = nullptr, *up_slot = nullptr, *up_nbr = nullptr;   // the caller's arrays, checked
+    std::vector<int32_t> itids;              // [n_elem][10] heap TIDs as internal rows, -1 padded
+    std::vector<int32_t> elem_row;           // [n_elem + n_new] element -> internal row: first TIDs, then the rows no TID names, ascending
+    std::vector<int32_t> up_owner;           // [n_upper] upper slot -> its element, -1: no element names the slot
+    int64_t n0 = 0, n_new = 0;               // rows the prior graph covers (level draws to skip) / rows to insert
+    bool identity = true;                    // element e is internal row e throughout: the direct kernels serve
+};
+
+// what every build entry point asks of its corpus and arguments, in the order and words the build has always used
+static int hnsw_build_check(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, uint32_t flags, vsr_hnsw** out, const char* who)
 {
     if (!c || !out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
     *out = nullptr;
@@ -247,11 +261,24 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
         return fail(VSR_ERR_INVALID, "%s: metric %d is not an operator class of sparsevec (0: sparsevec_l2_ops, 1: sparsevec_ip_ops, 2: sparsevec_cosine_ops, 3: sparsevec_l1_ops)", who, metric);
     if (expect != RowFormat::BIT && expect != RowFormat::SPARSE && metric != VSR_METRIC_L2 && metric != VSR_METRIC_IP && metric != VSR_METRIC_COSINE)
         return fail(VSR_ERR_UNSUPPORTED, "%s: L2, inner product and cosine operator classes only", who);
+    return VSR_OK;
+}
+
+static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out,
+                           const char* who, uint32_t* slots_io, uint32_t caps, uint32_t* guard, const HnswPrior* prior = nullptr)
+{
+    {
+        const int rc = hnsw_build_check(c, expect, m, ef_construction, metric, flags, out, who);
+        if (rc) return rc;
+    }
     vsr_ctx* ctx = c->ctx;
     HIPCHK(hipSetDevice(ctx->device));
     const int64_t n = c->n;
     if (n > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "%s: too many rows", who);
-    const bool merge = (flags & VSR_HNSW_BUILD_MERGE_DUPLICATES) != 0 && n > 0;
+    const bool merge = !prior && (flags & VSR_HNSW_BUILD_MERGE_DUPLICATES) != 0 && n > 0;
+    const int64_t n_prior = prior ? prior->n_elem : 0;                        // elements that are there already
+    const int64_t n_new = prior ? prior->n_new : n;                           // rows to insert, one element each unless merging
+    if (n_prior + n_new > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "%s: too many elements", who);
     const uint32_t row_chunks = format_row_chunks(expect, c->dim);
     std::unique_ptr<vsr_hnsw> h(new vsr_hnsw());
     h->corpus = c;
@@ -271,18 +298,25 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
     };
     (void) next();
     const double ml = 1.0 / std::log((double) m);
-    std::vector<int32_t> level((size_t) std::max<int64_t>(n, 1), 0);         // per row, then (merging) per element
-    for (int64_t r = 0; r < n; ++r) {
+    // per element: the prior graph's levels, then one draw per inserted row (merging: per row, then per element).  The i-th
+    // inserted row takes draw n0 + i, so a prefix build extended with the build's seed draws what the one-shot build draws
+    std::vector<int32_t> level((size_t) std::max<int64_t>(n_prior + n_new, 1), 0);
+    if (n_prior > 0) std::copy(prior->level, prior->level + n_prior, level.begin());
+    for (int64_t r = 0; r < (prior ? prior->n0 : 0); ++r) (void) next();
+    for (int64_t r = 0; r < n_new; ++r) {
         const double u = (double) (next() >> 11) * (1.0 / 9007199254740992.0);
-        level[(size_t) r] = std::min((int) (-std::log(u) * ml), cap);
+        level[(size_t) (n_prior + r)] = std::min((int) (-std::log(u) * ml), cap);
     }
     float *d_dist0 = nullptr, *d_up_dist = nullptr;
     uint64_t *d_key[2] = {nullptr, nullptr}, *d_val[2] = {nullptr, nullptr};
     uint32_t* d_cnt = nullptr;
     void* d_tmp = nullptr;
-    int32_t* d_row_level = nullptr;
+    int32_t *d_row_level = nullptr, *d_up_owner = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};                                    // VSR_HNSW_EXTEND_TIMING: around the edge-distance launch
     auto cleanup = [&]() {
-        void* ptrs[] = {d_dist0, d_up_dist, d_key[0], d_key[1], d_val[0], d_val[1], d_cnt, d_tmp, d_row_level};
+        for (hipEvent_t e : ev)
+            if (e) (void) hipEventDestroy(e);
+        void* ptrs[] = {d_dist0, d_up_dist, d_key[0], d_key[1], d_val[0], d_val[1], d_cnt, d_tmp, d_row_level, d_up_owner};
         for (void* q : ptrs)
             if (q) (void) hipFree(q);
     };
@@ -296,7 +330,7 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
         hipError_t e_ = (call);                                                                              \
         if (e_ != hipSuccess) return bail(fail(VSR_ERR_HIP, "%s: %s", who, hipGetErrorString(e_)));          \
     } while (0)
-    int64_t ne = n;                                                           // elements
+    int64_t ne = n_prior + n_new;                                             // elements
     if (merge) {
         // development / tests: VSR_HNSW_DEDUP_HASH_BITS=b keeps the low b bits of the row hash (the collision path on a small
         // corpus); VSR_HNSW_DEDUP_TIMING=1 prints the pre-pass's device-event times to stderr.  Both read at every call
@@ -321,9 +355,11 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
     }
     h->n_elem = (int32_t) ne;
     const size_t alloc = (size_t) std::max<int64_t>(ne, 1);
+    // prior elements keep their upper slots; new upper elements take the next ones in element order
     std::vector<int32_t> up_slot(alloc, -1);
-    int32_t max_level = 1, n_upper = 0;
-    for (int64_t e = 0; e < ne; ++e)
+    int32_t max_level = prior ? prior->max_level : 1, n_upper = prior ? prior->n_upper : 0;
+    if (n_prior > 0) std::copy(prior->up_slot, prior->up_slot + n_prior, up_slot.begin());
+    for (int64_t e = n_prior; e < ne; ++e)
         if (level[(size_t) e] >= 1) {
             up_slot[(size_t) e] = n_upper++;
             max_level = std::max(max_level, level[(size_t) e]);
@@ -343,6 +379,31 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
     HB_CHK(hipMemcpy(h->d_up_slot, up_slot.data(), alloc * 4, hipMemcpyHostToDevice));
     HB_CHK(hipMemsetAsync(h->d_nbr0, 0xFF, alloc * 2 * m * 4, ctx->stream));
     HB_CHK(hipMemsetAsync(h->d_up_nbr, 0xFF, up_words * 4, ctx->stream));
+    HB_CHK(hipMemsetAsync(d_dist0, 0, alloc * 2 * m * 4, ctx->stream));
+    HB_CHK(hipMemsetAsync(d_up_dist, 0, up_words * 4, ctx->stream));
+    // the prior graph's lists, behind the memsets on the same stream; the upper arrays at this graph's max_level (a new element
+    // above the prior top re-strides them).  The host arrays outlive the stream's work: it is synchronised below and in bail
+    std::vector<int32_t> prior_up;
+    if (n_prior > 0) {
+        HB_CHK(hipMemcpyAsync(h->d_nbr0, prior->nbr0, (size_t) n_prior * 2 * m * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (prior->n_upper > 0) {
+            const int32_t* src = prior->up_nbr;
+            if (max_level != prior->max_level) {
+                prior_up.assign((size_t) prior->n_upper * max_level * m, -1);
+                for (int32_t s = 0; s < prior->n_upper; ++s)
+                    std::copy(src + (size_t) s * prior->max_level * m, src + (size_t) (s + 1) * prior->max_level * m,
+                              prior_up.begin() + (size_t) s * max_level * m);
+                src = prior_up.data();
+            }
+            HB_CHK(hipMemcpyAsync(h->d_up_nbr, src, (size_t) prior->n_upper * max_level * m * 4, hipMemcpyHostToDevice, ctx->stream));
+            HB_CHK(hipMalloc(&d_up_owner, (size_t) prior->n_upper * 4));
+            HB_CHK(hipMemcpyAsync(d_up_owner, prior->up_owner.data(), (size_t) prior->n_upper * 4, hipMemcpyHostToDevice, ctx->stream));
+        }
+        if (!prior->identity) {
+            const int rc = upload_i32(&h->d_elem_row, prior->elem_row.data(), (size_t) ne);
+            if (rc) return bail(rc);
+        }
+    }
 
     HnswBuildParams bp{};
     bp.rows = c->d_rows;
@@ -371,7 +432,8 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
     bp.up_nbr = h->d_up_nbr;
     bp.up_dist = d_up_dist;
     bp.level = h->d_level;
-    bp.elem_row = merge ? h->d_elem_row : nullptr;
+    bp.elem_row = h->d_elem_row;                                              // the merging build's table / an extension whose elements are
+                                                                              // not its rows in order; nullptr: element e is row e
     bp.caps = std::max(caps, (uint32_t) (ef_construction + 2 * m));
     uint32_t slots = *slots_io;
     if (slots == 0) {
@@ -392,7 +454,7 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
     std::vector<Batch> batches;
     uint32_t rec_cap_max = 1;
     size_t tmp_bytes = 0;
-    for (int64_t done = 0; done < ne;) {
+    for (int64_t done = n_prior; done < ne;) {
         const int64_t b = std::max<int64_t>(1, std::min<int64_t>({done / 8, (int64_t) HB_BATCH_MAX, ne - done}));
         uint64_t cap = 0;
         for (int64_t e = done; e < done + b; ++e) cap += (uint64_t) (2 * m + level[(size_t) e] * m);
@@ -417,6 +479,20 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
     bp.rec_count = d_cnt;
 
     int32_t entry = -1, entry_level = -1;
+    const char* tenv = getenv("VSR_HNSW_EXTEND_TIMING");                      // development: 1 prints the edge-distance launch's device time
+    const bool edge_timing = n_prior > 0 && tenv && atoi(tenv) > 0;
+    if (n_prior > 0) {
+        // the one piece of build state the arrays do not carry: the distance of every edge, which the link kernel's re-selection reads
+        entry = prior->entry;
+        entry_level = level[(size_t) entry];
+        if (edge_timing) {
+            HB_CHK(hipEventCreate(&ev[0]));
+            HB_CHK(hipEventCreate(&ev[1]));
+            HB_CHK(hipEventRecord(ev[0], ctx->stream));
+        }
+        HB_CHK(vsr_hnsw_edge_distances(bp, (uint32_t) n_prior, d_up_owner, (uint32_t) prior->n_upper, ctx->stream));
+        if (edge_timing) HB_CHK(hipEventRecord(ev[1], ctx->stream));
+    }
     for (const Batch& bt : batches) {
         bp.entry = entry;
         bp.entry_level = entry_level;
@@ -433,6 +509,12 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
             }
     }
     HB_CHK(hipStreamSynchronize(ctx->stream));
+    if (edge_timing) {
+        float ms = 0.0f;
+        HB_CHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        fprintf(stderr, "vsr_hnsw_extend: prior_elements=%lld new_elements=%lld batches=%zu edge_dist_ms=%.4f\n", (long long) n_prior,
+                (long long) (ne - n_prior), batches.size(), ms);
+    }
     // no silent degradation: a full visited table made a search stop early, records past rec_cap were dropped.  The bits are
     // this build's: they leave the session's guard word here, so that a later vsr_screening_check is not poisoned
     uint32_t word = 0;
@@ -448,15 +530,19 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
     h->entry = ne > 0 ? entry : -1;
     h->entry_level = ne > 0 ? entry_level : -1;
     if (!merge) {
-        // element e holds internal row e alone
+        // an inserted element holds its row alone (a build: element e is internal row e); prior elements keep their TID lists
         std::vector<int32_t> erow(alloc, 0), tcount(alloc, 1), itids(alloc * 10, -1);
-        for (int64_t e = 0; e < n; ++e) {
-            erow[(size_t) e] = (int32_t) e;
-            itids[(size_t) e * 10] = (int32_t) e;
+        if (n_prior > 0) {
+            std::copy(prior->tid_count, prior->tid_count + n_prior, tcount.begin());
+            std::copy(prior->itids.begin(), prior->itids.begin() + (size_t) n_prior * 10, itids.begin());
+        }
+        for (int64_t e = 0; e < ne; ++e) {
+            erow[(size_t) e] = prior ? prior->elem_row[(size_t) e] : (int32_t) e;
+            if (e >= n_prior) itids[(size_t) e * 10] = erow[(size_t) e];
         }
         auto& up = upload_i32;
-        int rc;
-        if ((rc = up(&h->d_elem_row, erow.data(), alloc)) || (rc = up(&h->d_tid_count, tcount.data(), alloc)) ||
+        int rc = VSR_OK;
+        if ((!h->d_elem_row && (rc = up(&h->d_elem_row, erow.data(), alloc))) || (rc = up(&h->d_tid_count, tcount.data(), alloc)) ||
             (rc = up(&h->d_tids, itids.data(), alloc * 10))) {
             vsr_hnsw_free(h.release());
             return rc;
@@ -475,7 +561,7 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
 // the furthest of W (HB_ERR_CANDIDATES, vsr_hnsw_build.hip): pgvector's candidate heap has no bound, and rows without a common
 // index all have inner product 0, so such ties outgrow ef_construction + 2 m entries.
 static int hnsw_build(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out,
-                      const char* who)
+                      const char* who, const HnswPrior* prior = nullptr)
 {
     uint32_t slots = 0;
     if (const char* env = getenv("VSR_HNSW_BUILD_VISITED_SLOTS")) {
@@ -490,7 +576,7 @@ static int hnsw_build(vsr_corpus* c, RowFormat expect, int m, int ef_constructio
     uint32_t caps = (uint32_t) (ef_construction + 2 * m);
     for (;;) {
         uint32_t guard = 0;
-        const int rc = hnsw_build_once(c, expect, m, ef_construction, metric, seed, flags, out, who, &slots, caps, &guard);
+        const int rc = hnsw_build_once(c, expect, m, ef_construction, metric, seed, flags, out, who, &slots, caps, &guard, prior);
         if (rc != VSR_OK || guard == 0) return rc;
         if (guard & HB_ERR_RECORDS)
             return fail(VSR_ERR_UNSUPPORTED, "%s: reverse edges were dropped at ef_construction = %d with m = %d: the graph would be incomplete", who,
@@ -535,6 +621,109 @@ extern "C" int vsr_hnsw_build_half(vsr_corpus* c, int m, int ef_construction, in
 extern "C" int vsr_hnsw_build_sparse(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out)
 {
     return hnsw_build(c, RowFormat::SPARSE, m, ef_construction, metric, seed, flags, out, "vsr_hnsw_build_sparse");
+}
+
+// vsr_hnsw_extend's host pass over the caller's graph, before anything is uploaded.  The extension WRITES through these lists
+// (phase 2 updates the lists of old elements, the edge-distance launch gathers rows through every id), so it asks more than
+// hnsw_load: ids in [-1, n_elem), packed lists, a neighbour on layer lc living on layer lc (else its up_slot is -1 and the
+// reverse-edge pass would write out of bounds), upper slots distinct exactly where level >= 1, the entry on the top level, no row
+// under two TIDs.  Leaves in pr what hnsw_build_once needs: TIDs as internal rows, element -> row with the rows no TID names
+// appended in ascending internal order (the build's insertion order), slot -> element.
+static int hnsw_extend_prepare(const vsr_corpus* c, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
+                               const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr, int32_t n_upper,
+                               int32_t max_level, HnswPrior& pr, const char* who)
+{
+    if (c->n > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "%s: too many rows", who);
+    if (n_elem < 0 || (n_elem > 0 && (!level || !nbr0 || !tid_count || !tids || !up_slot || entry < 0)) || max_level < 1 || n_upper < 0 ||
+        (n_upper > 0 && !up_nbr) || entry >= n_elem)
+        return fail(VSR_ERR_INVALID, "%s: bad graph arrays", who);
+    pr.n_elem = n_elem;
+    pr.entry = n_elem > 0 ? entry : -1;
+    pr.n_upper = n_elem > 0 ? n_upper : 0;
+    pr.max_level = n_elem > 0 ? max_level : 1;
+    pr.level = level; pr.nbr0 = nbr0; pr.tid_count = tid_count; pr.up_slot = up_slot; pr.up_nbr = up_nbr;
+    const size_t rows = (size_t) c->n;
+    std::vector<int32_t> inv(std::max<size_t>(rows, 1), -1);
+    for (size_t r = 0; r < rows; ++r) inv[(size_t) c->h_orig[r]] = (int32_t) r;
+    std::vector<uint8_t> covered(std::max<size_t>(rows, 1), 0);
+    pr.itids.assign((size_t) std::max(n_elem, 1) * 10, -1);
+    pr.up_owner.assign((size_t) std::max(pr.n_upper, 1), -1);
+    int32_t top = 0;
+    for (int32_t e = 0; e < n_elem; ++e) {
+        if (tid_count[e] < 1 || tid_count[e] > 10 || level[e] < 0 || level[e] > max_level)
+            return fail(VSR_ERR_INVALID, "%s: element %d has %d heap TIDs / level %d", who, e, tid_count[e], level[e]);
+        for (int t = 0; t < tid_count[e]; ++t) {
+            const int64_t row = tids[(size_t) e * 10 + t];
+            if (row < 0 || row >= c->n) return fail(VSR_ERR_INVALID, "%s: element %d points at row %lld", who, e, (long long) row);
+            const int32_t r = inv[(size_t) row];
+            if (covered[(size_t) r]) return fail(VSR_ERR_INVALID, "%s: element %d names row %lld, which another heap TID names already", who, e, (long long) row);
+            covered[(size_t) r] = 1;
+            pr.itids[(size_t) e * 10 + t] = r;
+        }
+        pr.n0 += tid_count[e];
+        const int32_t s = up_slot[e];
+        if (level[e] >= 1) {
+            if (s < 0 || s >= n_upper) return fail(VSR_ERR_INVALID, "%s: element %d of level %d has upper slot %d, outside [0, %d)", who, e, level[e], s, n_upper);
+            if (pr.up_owner[(size_t) s] >= 0)
+                return fail(VSR_ERR_INVALID, "%s: element %d shares upper slot %d with element %d", who, e, s, pr.up_owner[(size_t) s]);
+            pr.up_owner[(size_t) s] = e;
+        } else if (s != -1)
+            return fail(VSR_ERR_INVALID, "%s: element %d of level 0 has upper slot %d (must be -1)", who, e, s);
+        top = std::max(top, level[e]);
+    }
+    if (n_elem > 0 && level[entry] != top)
+        return fail(VSR_ERR_INVALID, "%s: entry element %d has level %d, below the highest level %d", who, entry, level[entry], top);
+    for (int32_t e = 0; e < n_elem; ++e)
+        for (int lc = 0; lc <= level[e]; ++lc) {
+            const int lm = lc == 0 ? 2 * m : m;
+            const int32_t* nl = lc == 0 ? nbr0 + (size_t) e * 2 * m : up_nbr + ((size_t) up_slot[e] * max_level + (size_t) (lc - 1)) * m;
+            bool gap = false;
+            for (int j = 0; j < lm; ++j) {
+                const int32_t id = nl[j];
+                if (id < -1 || id >= n_elem)
+                    return fail(VSR_ERR_INVALID, "%s: element %d lists neighbour %d on layer %d, outside [-1, %d)", who, e, id, lc, n_elem);
+                if (id < 0) { gap = true; continue; }
+                if (gap) return fail(VSR_ERR_INVALID, "%s: element %d: the layer %d list is not packed (neighbour %d follows a -1)", who, e, lc, id);
+                if (level[id] < lc)
+                    return fail(VSR_ERR_INVALID, "%s: element %d lists neighbour %d on layer %d, above that element's level %d", who, e, id, lc, level[id]);
+            }
+        }
+    pr.n_new = c->n - pr.n0;
+    pr.elem_row.assign((size_t) std::max<int64_t>(n_elem + pr.n_new, 1), 0);
+    for (int32_t e = 0; e < n_elem; ++e) pr.elem_row[(size_t) e] = pr.itids[(size_t) e * 10];
+    size_t at = (size_t) n_elem;
+    for (size_t r = 0; r < rows; ++r)
+        if (!covered[r]) pr.elem_row[at++] = (int32_t) r;
+    pr.identity = true;
+    for (size_t e = 0; e < (size_t) (n_elem + pr.n_new); ++e) pr.identity = pr.identity && pr.elem_row[e] == (int32_t) e;
+    return VSR_OK;
+}
+
+// INSERT into a table that has an hnsw index (hnswinsert.c), for a batch of rows: the arrays vsr_hnsw_load takes, over a corpus
+// that holds the rows they were built on plus new ones; the new rows go in by the build's own batches (hnsw_build_once with a prior).
+extern "C" int vsr_hnsw_extend(vsr_corpus* c, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
+                               const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr, int32_t n_upper,
+                               int32_t max_level, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out)
+{
+    const char* who = "vsr_hnsw_extend";
+    if (!c || !out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    if (c->format == RowFormat::SPARSE)
+        return fail(VSR_ERR_UNSUPPORTED,
+                    "%s: the graph of a sparsevec corpus cannot be extended yet (the sparse build has no element -> row form): rebuild it with "
+                    "vsr_hnsw_build_sparse", who);
+    const RowFormat expect = c->format;
+    int rc = hnsw_build_check(c, expect, m, ef_construction, metric, flags, out, who);
+    if (rc) return rc;
+    if (flags & VSR_HNSW_BUILD_MERGE_DUPLICATES)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: VSR_HNSW_BUILD_MERGE_DUPLICATES is not supported: an inserted row is never folded into an existing element", who);
+    HnswPrior pr;
+    rc = hnsw_extend_prepare(c, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, pr, who);
+    if (rc) return rc;
+    if (pr.n_new == 0)                                                        // nothing to insert: the graph as it is
+        return hnsw_load(c, expect, expect == RowFormat::BIT ? metric : 0, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper,
+                         max_level, out, who);
+    return hnsw_build(c, expect, m, ef_construction, metric, seed, 0u, out, who, &pr);
 }
 
 // device memory of the graph arrays of an index (the corpus is counted by vsr_corpus_device_bytes); any index.  The row format

@@ -104,7 +104,9 @@ SYMBOLS = {
     "vsr_hnsw_search_device": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_hnsw_build": (_i, [_vp, _i, _i, _i, C.c_uint64, _vp]),
     "vsr_hnsw_build_ex": (_i, [_vp, _i, _i, _i, C.c_uint64, C.c_uint32, _vp]),
-    "vsr_hnsw_export_shape": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "vsr_hnsw_extend": (_i, [_vp, _i, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i, _i, C.c_uint64, C.c_uint32,
+                             C.POINTER(_vp)]),
+    "vsr_hnsw_export_shape":(_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_hnsw_export": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_hnsw_info": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "vsr_hnsw_set_predicate_aware": (_i, [_vp, _i]),

@@ -573,6 +573,26 @@ class Corpus:
         max_level (include/vsrbac.h, vsr_hnsw_load: what a dump of pgvector's in-memory build holds)."""
         return HnswIndex(self, graph)
 
+    def extend_hnsw(self, graph, ef_construction=64, metric=None, seed=1):
+        """INSERT for a batch of rows (vsr_hnsw_extend): `graph` is the dict HnswIndex.export() returns for a graph over SOME of
+        this corpus's rows -- its TIDs are row indices of this corpus -- and the rows no TID names are inserted by build_hnsw's own
+        batches, in internal row order, with levels from the build's seeded stream (the i-th new row takes the draw after those of
+        the covered rows).  fp32, halfvec and bit corpora; metric: None is "l2", or "hamming" on a bit corpus, where it also becomes
+        the index's opclass.  Extending a prefix build at one of the build's batch boundaries gives the one-shot build's graph.
+        Recipe: load the corpus again with the new rows (old rows at their old indices, or map the TIDs), extend_hnsw(old.export()),
+        then free the old index and the old corpus."""
+        if metric is None:
+            metric = "hamming" if self.is_bit else "l2"
+        a = lambda name, dt: np.ascontiguousarray(graph[name], dtype=dt)
+        level, nbr0, tc, tids = a("level", np.int32), a("nbr0", np.int32), a("tid_count", np.int32), a("tids", np.int64)
+        up_slot, up_nbr = a("up_slot", np.int32), a("up_nbr", np.int32)
+        n_upper = int((up_slot >= 0).sum())
+        h = C.c_void_p()
+        check(self._lib.vsr_hnsw_extend(self._h, int(graph["m"]), level.size, int(graph["entry"]), _ptr(level), _ptr(nbr0), _ptr(tc),
+                                        _ptr(tids), _ptr(up_slot), _ptr(up_nbr), n_upper, int(graph["max_level"]),
+                                        int(ef_construction), _metric(metric), int(seed), 0, C.byref(h)))
+        return HnswIndex(self, h)
+
     def build_hnsw_bit(self, m=16, ef_construction=64, metric="hamming", seed=1, merge_duplicates=False):
         """CREATE INDEX ... USING hnsw (col bit_hamming_ops | bit_jaccard_ops) over this bit corpus (vsr_hnsw_build_bit):
         build_hnsw's batched insertion on the packed rows.  merge_duplicates: byte-identical rows share an element -- the
@@ -1077,6 +1097,12 @@ class HnswIndex:
                                         _ptr(up_nbr)))
         return {"level": level, "nbr0": nbr0, "tid_count": tid_count, "tids": tids, "up_slot": up_slot, "up_nbr": up_nbr,
                 "max_level": max_level, "entry": entry, "m": m}
+
+    def extended_over(self, corpus, ef_construction=64, metric=None, seed=1):
+        """A new index over `corpus` -- this index's rows at their row indices plus new rows -- made by export() and
+        Corpus.extend_hnsw: the graph is kept, only the new rows are inserted.  This index and its corpus stay as they are: free
+        the old pair once the new one serves."""
+        return corpus.extend_hnsw(self.export(), ef_construction, metric, seed)
 
     def search_device(self, d_queries, nq, k, ef_search, metric, filters, d_block, d_doc, d_rows, d_dist, d_counts,
                       d_visited=None):
