@@ -621,6 +621,52 @@ int vsr_hnsw_extend(vsr_corpus* corpus, int m, int32_t n_elem, int32_t entry, co
                     const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
                     int32_t n_upper, int32_t max_level,
                     int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out);
+/* VACUUM of an indexed table after DELETE (hnswvacuum.c): removes rows from a graph that exists, repairs every element that pointed
+ * at a deleted one on the GPU and returns the compacted graph.  Takes the arrays vsr_hnsw_load takes, over the SAME corpus: the
+ * deleted rows stay in it, because the repair walks through deleted elements and reads their vectors.  fp32, halfvec and bit corpora.
+ *   - dead_rows[n_dead]: caller row indices.  A value outside [0, rows) is VSR_ERR_INVALID; duplicates are allowed; rows no heap TID
+ *     names are ignored.  flags must be 0.
+ *   - Pass 1 (host): the deleted TIDs leave their elements; an element lives while it has a TID left.  `highest` is the live element
+ *     other than the entry with the greatest level, the lowest id among equals.
+ *   - needs(e): a list of e names a deleted element, or e's layer-0 list is not full (NeedsUpdated).
+ *   - Entry phase (RepairGraphEntryPoint), batches of one: highest is repaired from the entry, deleted or not, if needs(highest); a
+ *     deleted entry is replaced by highest (none: the index is empty); a live entry is repaired from highest if needs(entry) (no
+ *     highest: its lists become empty).
+ *   - Main phase: every live e != entry with needs(e), ascending, computed ONCE after the entry phase, in batches of min(4096, left).
+ *     pgvector re-evaluates NeedsUpdated as it goes; computing it once can only add repairs.
+ *   - The repair of e is the build's search and selection against the graph as the batch found it, with beam ef_construction + 1:
+ *     deleted elements and e itself are walked and stay in the working set, only live elements (e among them) count towards the beam,
+ *     and both leave the candidates before the selection.  The batch's new lists are staged and installed together; the reverse
+ *     edges are the build's records in the build's order, applied with UpdateNeighborOnDisk's cases: a source the list names already
+ *     is skipped, a list that is not full takes it at its end, a full list gives up the first slot that names a deleted element,
+ *     any other full list is re-selected (HnswUpdateConnection).
+ *   - The result is compacted: live elements renumbered in ascending old id, upper slots in ascending old slot, max_level =
+ *     max(1, level of the new entry) with the upper arrays at that stride, every list rewritten.  A live element keeps its surviving
+ *     TIDs in their old order, moved to the front; its vector is the first survivor's row.  Everything deleted: the index
+ *     vsr_hnsw_load makes of n_elem = 0, whose searches return count 0.
+ *   - out_elem_map[n_elem] (may be NULL): the new id of every old element, -1 for a deleted one.  out_stats (may be NULL).
+ *   - n_dead = 0 is vsr_hnsw_load* (a departure: pgvector would still repair lists that are not full).
+ *   - Refusals: those of vsr_hnsw_extend -- a sparse corpus (VSR_ERR_UNSUPPORTED, the message names sparsevec), a view corpus, the
+ *     build's limits on m, ef_construction, metric and halfvec dimension, and its host checks of the prior graph (written through).
+ *   - A search that cannot find ef_construction live elements admits every candidate, so the working set of a mostly deleted graph
+ *     outgrows the kernel's arrays: the call then runs again with a visited table / candidate array twice as large, from the
+ *     caller's arrays, and when nothing larger fits the LDS it is VSR_ERR_UNSUPPORTED (rebuild over the live rows), never a
+ *     thinner graph.  The result does not depend on the initial sizes.
+ * To drop the deleted rows from the corpus too: export the result, remap its TIDs, load a corpus without them and vsr_hnsw_load.
+ * UPDATE is vacuum followed by vsr_hnsw_extend.  The result is an ordinary index.  Synchronises. */
+typedef struct {
+    int64_t tuples_removed, tuples_kept;   /* heap TIDs deleted / left */
+    int32_t elements_removed;              /* elements whose last TID went */
+    int32_t elements_repaired;             /* repairs run (entry phase included) */
+    int32_t batches;                       /* repair batches of the attempt that succeeded (entry phase included) */
+    int32_t attempts;                      /* 1 + restarts with larger arrays; 0: nothing ran on the GPU */
+} vsr_hnsw_vacuum_stats;
+int vsr_hnsw_vacuum(vsr_corpus* corpus, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
+                    const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr,
+                    int32_t n_upper, int32_t max_level, int ef_construction, int metric,
+                    const int64_t* dead_rows, int64_t n_dead, uint32_t flags,
+                    int32_t* out_elem_map /* [n_elem] new id or -1, may be NULL */, vsr_hnsw_vacuum_stats* out_stats /* may be NULL */,
+                    vsr_hnsw** out);
 /* Predicate-aware walk (off by default: pgvector filters what the index returns, hnswscan.c + the executor's RLS qual).  On:
  * the layer-0 search of later vsr_hnsw_search* calls applies the query's filter while it walks, ACORN-1 style -- the result
  * set and the candidate set hold permitted elements only, and an expansion also takes the permitted neighbours of its

@@ -50,6 +50,16 @@ struct HnswBuildParams {
     uint32_t*      err = nullptr;            // the session's guard word: HB_ERR_VISITED / HB_ERR_RECORDS, read by hnsw_build after the last batch
 };
 
+// vsr_hnsw_vacuum: what the repair forms of the two build kernels take beside HnswBuildParams (a second kernel argument, so that the
+// build's own launches keep theirs).  The batch is elems[0 .. p.count), not p.first ..; p.efc is ef_construction + 1
+struct HnswVacuumParams {
+    const int32_t* live = nullptr;           // [n_elem] 1: the element has a heap TID left
+    const int32_t* elems = nullptr;          // [p.count] the elements this batch repairs, ascending
+    int32_t*       stage_nbr = nullptr;      // [p.count][stage_stride] the new lists: layer 0 (2m), then layers 1 .. max_level (m each)
+    float*         stage_dist = nullptr;     // their distances
+    uint32_t       stage_stride = 0;         // 2m + max_level * m
+};
+
 // what the merging pre-pass (vsr_hnsw_dedup.hip) leaves: device arrays of n_elem entries, the caller's to hipFree
 struct HnswElemTable {
     int32_t  n_elem = 0;
@@ -73,6 +83,19 @@ hipError_t vsr_hnsw_dedup_elements(const float4* rows, uint32_t n, uint32_t stri
 hipError_t vsr_hnsw_build_batch(vsr::HnswBuildParams& p, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt, uint64_t* d_val_alt,
                                 hipStream_t s);
 size_t vsr_hnsw_build_sort_bytes(uint32_t rec_cap);
+// vsr_hnsw_vacuum.  One repair batch (p.count <= HB_BATCH_MAX elements, v.elems): the searches into v.stage_*, the install launch,
+// the sort and the link launch, all on s.  The selection's scratch lies over the visited table (hash_slots / 3 candidates).
+hipError_t vsr_hnsw_vacuum_batch(vsr::HnswBuildParams& p, const vsr::HnswVacuumParams& v, void* d_sort_tmp, size_t sort_tmp_bytes,
+                                 uint64_t* d_key_alt, uint64_t* d_val_alt, hipStream_t s);
+// scratch of the compaction and the scan below, for n_elem elements
+size_t vsr_hnsw_vacuum_tmp_bytes(uint32_t n_elem);
+// d_flag[e] = NeedsUpdated(e) for every live e != skip; d_list (may be nullptr): the flagged elements ascending, *d_num of them
+hipError_t vsr_hnsw_vacuum_mark(const vsr::HnswBuildParams& p, const int32_t* d_live, uint32_t n_elem, int32_t skip, uint8_t* d_flag,
+                                int32_t* d_list, int32_t* d_num, void* d_tmp, size_t tmp_bytes, hipStream_t s);
+// d_map = exclusive scan of d_live; the live elements' lists, renumbered, into the compacted arrays (memset to -1 by the caller)
+hipError_t vsr_hnsw_vacuum_renumber(const vsr::HnswBuildParams& p, const int32_t* d_live, int32_t* d_map, const int32_t* d_slot_map,
+                                    uint32_t n_elem, int32_t* d_new_nbr0, int32_t* d_new_up_nbr, uint32_t new_max_level, void* d_tmp,
+                                    size_t tmp_bytes, hipStream_t s);
 // vsr_hnsw_extend: fills p.dist0 / p.up_dist for the lists of elements 0 .. n_prior - 1 from the ids p.nbr0 / p.up_nbr hold (one
 // launch on s, no synchronisation).  d_up_owner[n_upper_prior]: upper slot -> its element, -1 for a slot no element names.  Every
 // id in those lists is in [-1, n_prior), lists are packed, and a neighbour on layer lc has an upper slot: the caller checked.

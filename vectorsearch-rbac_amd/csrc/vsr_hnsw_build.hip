@@ -226,15 +226,27 @@ __device__ __forceinline__ int hb_select(const HnswBuildParams& p, const uint64_
 }
 
 // ---- phase 1: one wave per new element: search the frozen graph, select, write the element's own lists, emit reverse edges ----
-template <bool IND, int ROWS>
-__global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildParams p)
+// VAC (vsr_hnsw_vacuum): the REPAIR of an element that is in the graph already -- HnswFindElementNeighbors with existing = true
+// (hnswvacuum.c's RepairGraphElement).  The batch is v.elems[]; deleted elements (v.live[e] == 0) and the element itself are walked
+// and stay in W, but only live elements count towards the beam (CountElement): a live push that takes the live count beyond ef
+// takes the furthest entry, deleted or live, off W.  The count starts at the live entry points and is never taken back, so a layer
+// entered with more than ef live entry points loses one entry per live push from the start.  Every push after the first loss is
+// nearer than W's furthest, so W is the nearest pushed - popped entries of everything pushed: still a prefix of S.
+// Before the selection the deleted elements
+// and the element itself leave the candidates (RemoveElements); the new lists go to v.stage_* and not to the graph, which the
+// other waves of the batch are reading.  S can outgrow any bound here (a graph with few live elements admits everything), so the
+// loss check of the sparse build is on, and so is one for a W longer than S.
+template <bool IND, int ROWS, bool VAC>
+__device__ __forceinline__ void hb_search_body(const HnswBuildParams& p, const HnswVacuumParams& v)
 {
     extern __shared__ __align__(16) unsigned char smem_all[];
     const int lane = threadIdx.x & 63;
     const uint32_t wave = (uint32_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
     const uint32_t bi = blockIdx.x * p.wpb + wave;
     if (wave >= p.wpb || bi >= p.count) return;                               // (waves are independent: no workgroup barrier)
-    const uint32_t me = p.first + bi;
+    uint32_t me_;
+    if constexpr (VAC) me_ = (uint32_t) v.elems[bi]; else me_ = p.first + bi;
+    const uint32_t me = me_;
     unsigned char* smem = smem_all + (size_t) wave * p.lds_per_wave;
     uint64_t* S = reinterpret_cast<uint64_t*>(smem);                          // [caps] candidates, sorted, nearest first
     uint8_t*  X = reinterpret_cast<uint8_t*>(S + p.caps);                     // [caps] expanded flags
@@ -243,6 +255,17 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
     int32_t*  sel = reinterpret_cast<int32_t*>(nd + HB_NBR);                  // [HB_NBR] selected candidate indices
     int32_t*  wd = sel + HB_NBR;                                              // [caps] passed-over candidate indices
     uint32_t* lv = reinterpret_cast<uint32_t*>(wd + p.caps);                  // [hash_slots] visited set
+    // VAC: S can be thousands of entries long, so the selection's scratch does not get arrays of caps entries of its own.  T[tcap],
+    // the candidates without the deleted elements and `me`, and wd[tcap] lie over the visited table, which no one reads between the
+    // end of a layer search and the clear_visited() of the next: 12 bytes a candidate, tcap = hash_slots / 3
+    uint64_t* T = nullptr;
+    uint32_t tcap = 0;
+    if constexpr (VAC) {
+        lv = reinterpret_cast<uint32_t*>(sel + HB_NBR);
+        T = reinterpret_cast<uint64_t*>(lv);
+        tcap = p.hash_slots / 3u;
+        wd = reinterpret_cast<int32_t*>(T + tcap);
+    }
     const float4* q = hb_row<IND>(p, me);
     const int my_level = p.level[me];
     SparseLeft left;                                                          // ROWS_SPARSE: the left-hand table, the last sp_slots * 8 bytes
@@ -251,14 +274,31 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
         left.slots = p.sp_slots;
     }
 
+    // VAC: the staged lists of `me`
+    int32_t* st_n = nullptr;
+    float* st_d = nullptr;
+    if constexpr (VAC) {
+        st_n = v.stage_nbr + (size_t) bi * v.stage_stride;
+        st_d = v.stage_dist + (size_t) bi * v.stage_stride;
+    }
+    auto own_list = [&](int lc, float** dist) -> int32_t* {
+        if constexpr (VAC) {
+            const uint32_t at = lc == 0 ? 0u : (uint32_t) (lc + 1) * p.m;     // 2m + (lc - 1) m
+            *dist = st_d + at;
+            return st_n + at;
+        } else {
+            return hb_list(p, me, lc, dist);
+        }
+    };
+
     // the element's own lists start empty
     for (int lc = 0; lc <= my_level; ++lc) {
         float* dl;
-        int32_t* nl = hb_list(p, me, lc, &dl);
+        int32_t* nl = own_list(lc, &dl);
         const uint32_t lm = lc == 0 ? 2 * p.m : p.m;
         for (uint32_t j = (uint32_t) lane; j < lm; j += 64) { nl[j] = -1; dl[j] = 0.0f; }
     }
-    if (p.entry < 0) return;                                                  // the very first element
+    if (p.entry < 0) return;                                                  // the very first element (VAC: nobody else is left)
 
     bool overflow = false;
     uint32_t used = 0;
@@ -285,8 +325,14 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
     // layer search in progress
     uint32_t cur_ef = 1;
     bool lost = false;
+    uint32_t live_pushed = 0, popped = 0;                                     // VAC: the live elements among `pushed`; entries W lost
+    // entries of W: min(pushed, ef); VAC: every live push beyond ef took the furthest entry, deleted or live, off W
+    auto w_len = [&](uint32_t ef_) -> uint32_t {
+        if constexpr (VAC) return pushed - popped;
+        else return pushed < ef_ ? pushed : ef_;
+    };
     auto as_near_as_w = [&](uint64_t key) -> bool {
-        const uint32_t wl = pushed < cur_ef ? pushed : cur_ef;
+        const uint32_t wl = w_len(cur_ef);
         return mono_to_float((uint32_t) (key >> 32)) <= mono_to_float((uint32_t) (S[(wl < count ? wl : count) - 1] >> 32));
     };
     auto insert = [&](uint64_t key) {
@@ -296,7 +342,7 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
             if (S[mid] < key) lo = mid + 1; else hi = mid;
         }
         const uint32_t pos = lo;
-        if constexpr (ROWS == ROWS_SPARSE) {
+        if constexpr (ROWS == ROWS_SPARSE || VAC) {
             if (pos >= p.caps) lost |= as_near_as_w(key);
             else if (count == p.caps && X[p.caps - 1] == 0) lost |= as_near_as_w(S[p.caps - 1]);
         }
@@ -325,6 +371,14 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
         used = count;
         pushed = count;
         first_open = 0;
+        if constexpr (VAC) {                                                  // the entry points' live count
+            live_pushed = 0;
+            popped = 0;
+            for (uint32_t base = 0; base < count; base += 64) {
+                const uint32_t i = base + (uint32_t) lane;
+                live_pushed += (uint32_t) __popcll(__ballot(i < count && v.live[(uint32_t) S[i]] != 0));
+            }
+        }
         wave_sync();
         for (;;) {
             uint32_t cpos = 0xFFFFFFFFu;
@@ -336,7 +390,7 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
             if (cpos == 0xFFFFFFFFu) break;
             first_open = cpos + 1;
             const uint64_t ckey = S[cpos];
-            const uint32_t wl = pushed < ef_ ? pushed : ef_;
+            const uint32_t wl = w_len(ef_);
             const uint64_t fkey = S[(wl < count ? wl : count) - 1];
             if (mono_to_float((uint32_t) (ckey >> 32)) > mono_to_float((uint32_t) (fkey >> 32))) break;
             if (lane == 0) X[cpos] = 1;
@@ -360,15 +414,21 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
             for (int i = 0; i < cnt; ++i) {
                 const uint32_t e = (uint32_t) nb[i];
                 const float ed = nd[i];
-                const bool always = pushed < ef_;
-                const uint32_t wl2 = pushed < ef_ ? pushed : ef_;
+                bool always_;
+                if constexpr (VAC) always_ = live_pushed < ef_; else always_ = pushed < ef_;
+                const bool always = always_;
+                const uint32_t wl2 = w_len(ef_);
                 const float fd = mono_to_float((uint32_t) (S[(wl2 < count ? wl2 : count) - 1] >> 32));
                 if (!(ed < fd || always)) continue;
                 insert(make_key(ed, e));
                 ++pushed;
+                if constexpr (VAC) {
+                    if (v.live[e] != 0 && ++live_pushed > ef_) ++popped;
+                    lost |= w_len(ef_) > p.caps;                              // W no longer fits S
+                }
             }
         }
-        const uint32_t wl = pushed < ef_ ? pushed : ef_;
+        const uint32_t wl = w_len(ef_);
         count = wl < count ? wl : count;
     };
 
@@ -387,15 +447,35 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
         search_layer(lc, p.efc);
         const int lm = (int) (lc == 0 ? 2 * p.m : p.m);
         int pruned;
-        const int ns = hb_select<IND, ROWS>(p, S, (int) count, lm, sel, wd, nb, nd, &pruned, lane, &left);
+        const uint64_t* C = S;                                                // the candidates of the selection, nearest first
+        int nc = (int) count;
+        if constexpr (VAC) {                                                  // RemoveElements: without the deleted ones and `me`, order kept
+            nc = 0;
+            for (uint32_t base = 0; base < count; base += 64) {
+                const uint32_t i = base + (uint32_t) lane;
+                const uint64_t kk = i < count ? S[i] : 0;
+                const bool keep = i < count && (uint32_t) kk != me && v.live[(uint32_t) kk] != 0;
+                const uint64_t km = __ballot(keep);
+                const uint32_t at = (uint32_t) nc + (uint32_t) __popcll(km & ((1ull << lane) - 1ull));
+                if (keep && at < tcap) T[at] = kk;
+                nc += __popcll(km);
+            }
+            if ((uint32_t) nc > tcap) {                                       // more live candidates than the table's bytes hold: a larger table
+                overflow = true;
+                nc = (int) tcap;
+            }
+            wave_sync();
+            C = T;
+        }
+        const int ns = hb_select<IND, ROWS>(p, C, nc, lm, sel, wd, nb, nd, &pruned, lane, &left);
         // AddConnections + the reverse edges HnswUpdateNeighborsInMemory will apply
         float* dl;
-        int32_t* nl = hb_list(p, me, lc, &dl);
+        int32_t* nl = own_list(lc, &dl);
         uint32_t base = 0;
         if (lane == 0 && ns > 0) base = atomicAdd(p.rec_count, (uint32_t) ns);
         base = (uint32_t) __shfl((int) base, 0);
         for (int j = lane; j < ns; j += 64) {
-            const uint64_t key = S[sel[j]];
+            const uint64_t key = C[sel[j]];
             nl[j] = (int32_t) (uint32_t) key;
             dl[j] = mono_to_float((uint32_t) (key >> 32));
             if (base + (uint32_t) j < p.rec_cap) {
@@ -411,14 +491,29 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
         wave_sync();
     }
     if (overflow && lane == 0) atomicOr(p.err, HB_ERR_VISITED);
-    if constexpr (ROWS == ROWS_SPARSE)
+    if constexpr (ROWS == ROWS_SPARSE || VAC)
         if (lost && lane == 0) atomicOr(p.err, HB_ERR_CANDIDATES);
+}
+
+template <bool IND, int ROWS>
+__global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildParams p)
+{
+    hb_search_body<IND, ROWS, false>(p, HnswVacuumParams{});
+}
+
+template <bool IND, int ROWS>
+__global__ __launch_bounds__(256) void hnsw_vacuum_search_kernel(const HnswBuildParams p, const HnswVacuumParams v)
+{
+    hb_search_body<IND, ROWS, true>(p, v);
 }
 
 // ---- phase 2: reverse edges, sorted by (layer, target, source): the wave of a run's first record applies the whole
 // (layer, target) run, sources in ascending element id ----
-template <bool IND, int ROWS>
-__global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildParams p)
+// VAC (vsr_hnsw_vacuum): UpdateNeighborOnDisk's cases come first (hnswinsert.c:470-560): a source the list names already is
+// skipped, a list that is not full takes it at its end, a full list that names a deleted element (live[] == 0) gives the first such
+// slot away (LoadElementsForInsert); only then HnswUpdateConnection's re-selection
+template <bool IND, int ROWS, bool VAC>
+__device__ __forceinline__ void hb_link_body(const HnswBuildParams& p, const int32_t* __restrict__ live)
 {
     extern __shared__ __align__(16) unsigned char smem_all[];
     const int lane = threadIdx.x & 63;
@@ -447,6 +542,20 @@ __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildPar
     for (uint32_t r = ri; r < n_rec && (p.rec_key[r] >> HB_SRC_BITS) == key; ++r) {   // HnswUpdateConnection, one after another
         const uint32_t e = (uint32_t) (p.rec_val[r] >> 32);
         const float de = __uint_as_float((uint32_t) p.rec_val[r]);
+        int dead_at = 0x7FFFFFFF;                                             // VAC: the first slot that names a deleted element
+        if constexpr (VAC) {
+            bool has = false;
+            for (int j = lane; j < lm; j += 64) {
+                const int32_t id = nl[j];
+                has |= id == (int32_t) e;
+                if (id >= 0 && live[id] == 0 && j < dead_at) dead_at = j;
+            }
+            if (__ballot(has) != 0) continue;
+            for (int mm = 32; mm >= 1; mm >>= 1) {
+                const int o = __shfl_xor(dead_at, mm);
+                dead_at = o < dead_at ? o : dead_at;
+            }
+        }
         // current length of the list (-1 padded)
         int len = 0;
         for (int j0 = 0; j0 < lm; j0 += 64) {
@@ -457,6 +566,13 @@ __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildPar
             if (lane == 0) { nl[len] = (int32_t) e; dl[len] = de; }
             wave_sync();
             continue;
+        }
+        if constexpr (VAC) {
+            if (dead_at < lm) {
+                if (lane == 0) { nl[dead_at] = (int32_t) e; dl[dead_at] = de; }
+                wave_sync();
+                continue;
+            }
         }
         // full: the list and the new element, nearest first (ties: the lower element id first, the order list_sort leaves
         // with CompareCandidateDistances read from the tail)
@@ -487,6 +603,92 @@ __global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildPar
         }
         wave_sync();
     }
+}
+
+template <bool IND, int ROWS>
+__global__ __launch_bounds__(256) void hnsw_build_link_kernel(const HnswBuildParams p)
+{
+    hb_link_body<IND, ROWS, false>(p, nullptr);
+}
+
+template <bool IND, int ROWS>
+__global__ __launch_bounds__(256) void hnsw_vacuum_link_kernel(const HnswBuildParams p, const int32_t* __restrict__ live)
+{
+    hb_link_body<IND, ROWS, true>(p, live);
+}
+
+// ---- vacuum (vsr_hnsw_vacuum): the small kernels around the two repair forms above ----
+// the staged lists of a batch become the elements' lists: after every search of the batch has ended, before the link kernel.
+// One wave per batch element
+__global__ __launch_bounds__(256) void hnsw_vacuum_install_kernel(const HnswBuildParams p, const HnswVacuumParams v)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t bi = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (bi >= p.count) return;
+    const uint32_t me = (uint32_t) v.elems[bi];
+    const int my_level = p.level[me];
+    for (int lc = 0; lc <= my_level; ++lc) {
+        float* dl;
+        int32_t* nl = hb_list(p, me, lc, &dl);
+        const uint32_t lm = lc == 0 ? 2 * p.m : p.m;
+        const size_t at = (size_t) bi * v.stage_stride + (lc == 0 ? 0u : (uint32_t) (lc + 1) * p.m);
+        for (uint32_t j = (uint32_t) lane; j < lm; j += 64) { nl[j] = v.stage_nbr[at + j]; dl[j] = v.stage_dist[at + j]; }
+    }
+}
+
+// NeedsUpdated (hnswvacuum.c:190-235): flag[e] = 1 when live element e (other than `skip`, the entry point; -1: none) has a list that
+// names a deleted element, or a layer-0 list that is not full.  Lists are packed: the first -1 ends one.  One thread per element
+__global__ __launch_bounds__(256) void hnsw_vacuum_mark_kernel(const HnswBuildParams p, const int32_t* __restrict__ live, const uint32_t n_elem,
+                                                               const int32_t skip, uint8_t* __restrict__ flag)
+{
+    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+    if (e >= n_elem) return;
+    uint8_t f = 0;
+    if (live[e] != 0 && (int32_t) e != skip) {
+        const int my_level = p.level[e];
+        for (int lc = 0; lc <= my_level; ++lc) {
+            float* dl;
+            const int32_t* nl = hb_list(p, e, lc, &dl);
+            const uint32_t lm = lc == 0 ? 2 * p.m : p.m;
+            uint32_t j = 0;
+            for (; j < lm; ++j) {
+                const int32_t id = nl[j];
+                if (id < 0) break;
+                if (live[id] == 0) f = 1;
+            }
+            if (lc == 0 && j < lm) f = 1;
+        }
+    }
+    flag[e] = f;
+}
+
+// pass 3: the lists of the live elements into the compacted arrays, ids through map[] (the exclusive scan of live[]), upper slots
+// through slot_map[], the upper arrays at the new graph's max_level.  A list of a live element that still names a deleted one would
+// be a fault of the repair: HB_ERR_RECORDS, never a thinner list in silence.  One wave per element
+__global__ __launch_bounds__(256) void hnsw_vacuum_renumber_kernel(const HnswBuildParams p, const int32_t* __restrict__ live,
+                                                                   const int32_t* __restrict__ map, const int32_t* __restrict__ slot_map,
+                                                                   const uint32_t n_elem, int32_t* __restrict__ new_nbr0,
+                                                                   int32_t* __restrict__ new_up_nbr, const uint32_t new_max_level)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t e = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (e >= n_elem || live[e] == 0) return;
+    const uint32_t ne = (uint32_t) map[e];
+    const int my_level = p.level[e];                                          // (<= new_max_level: the new entry is on the top live level)
+    bool bad = false;
+    for (int lc = 0; lc <= my_level && lc <= (int) new_max_level; ++lc) {
+        float* dl;
+        const int32_t* nl = hb_list(p, e, lc, &dl);
+        const uint32_t lm = lc == 0 ? 2 * p.m : p.m;
+        int32_t* out = lc == 0 ? new_nbr0 + (size_t) ne * 2 * p.m
+                               : new_up_nbr + ((size_t) slot_map[p.up_slot[e]] * new_max_level + (uint32_t) (lc - 1)) * p.m;
+        for (uint32_t j = (uint32_t) lane; j < lm; j += 64) {
+            const int32_t id = nl[j];
+            bad |= id >= 0 && live[id] == 0;
+            out[j] = id >= 0 && live[id] != 0 ? map[id] : -1;
+        }
+    }
+    if (bad) atomicOr(p.err, HB_ERR_RECORDS);
 }
 
 // ---- extension (vsr_hnsw_extend): the per-edge distances of a graph that arrived without them.  One wave per (element, layer)
@@ -615,6 +817,78 @@ hipError_t vsr_hnsw_build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sor
                           : build_batch<false, ROWS_HALF>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
     return p.elem_row ? build_batch<true, ROWS_F32>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s)
                       : build_batch<false, ROWS_F32>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
+}
+
+// one repair batch of vsr_hnsw_vacuum: searches into the staging buffer, install, sort of the reverse edges, their application
+template <bool IND, int ROWS>
+static hipError_t vacuum_batch(HnswBuildParams& p, const HnswVacuumParams& v, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt,
+                               uint64_t* d_val_alt, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(p.rec_count, 0, sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(p.rec_key, 0xFF, (size_t) p.rec_cap * sizeof(uint64_t), s);
+    if (e != hipSuccess) return e;
+    const size_t lds1 = (size_t) p.lds_per_wave * p.wpb;
+    if (lds1 > 64 * 1024) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_vacuum_search_kernel<IND, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds1);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_vacuum_search_kernel<IND, ROWS>), dim3((p.count + p.wpb - 1) / p.wpb), dim3(64 * p.wpb), lds1, s, p, v);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(hnsw_vacuum_install_kernel, dim3((p.count + 3) / 4), dim3(256), 0, s, p, v);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (p.entry < 0) return hipSuccess;                                       // nobody else is left: the lists stay empty
+    hipcub::DoubleBuffer<uint64_t> keys(p.rec_key, d_key_alt), vals(p.rec_val, d_val_alt);
+    e = hipcub::DeviceRadixSort::SortPairs(d_sort_tmp, sort_tmp_bytes, keys, vals, (int) p.rec_cap, 0, HB_KEY_BITS, s);
+    if (e != hipSuccess) return e;
+    HnswBuildParams q = p;
+    q.rec_key = keys.Current();
+    q.rec_val = vals.Current();
+    const size_t lds2 = (size_t) 4 * HB_NBR * 32;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_vacuum_link_kernel<IND, ROWS>), dim3((p.rec_cap + 3) / 4), dim3(256), lds2, s, q, v.live);
+    return hipGetLastError();
+}
+
+hipError_t vsr_hnsw_vacuum_batch(HnswBuildParams& p, const HnswVacuumParams& v, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt,
+                                 uint64_t* d_val_alt, hipStream_t s)
+{
+    if (p.sparse || 2 * p.m > (uint32_t) HB_NBR || p.count == 0 || p.count > HB_BATCH_MAX) return hipErrorInvalidValue;
+    if (p.bits)
+        return p.elem_row ? vacuum_batch<true, ROWS_BIT>(p, v, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s)
+                          : vacuum_batch<false, ROWS_BIT>(p, v, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
+    if (p.halves)
+        return p.elem_row ? vacuum_batch<true, ROWS_HALF>(p, v, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s)
+                          : vacuum_batch<false, ROWS_HALF>(p, v, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
+    return p.elem_row ? vacuum_batch<true, ROWS_F32>(p, v, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s)
+                      : vacuum_batch<false, ROWS_F32>(p, v, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
+}
+
+size_t vsr_hnsw_vacuum_tmp_bytes(uint32_t n_elem)
+{
+    size_t a = 0, b = 0;
+    (void) hipcub::DeviceSelect::Flagged(nullptr, a, hipcub::CountingInputIterator<int32_t>(0), (const uint8_t*) nullptr, (int32_t*) nullptr,
+                                         (int32_t*) nullptr, (int) n_elem, (hipStream_t) 0);
+    (void) hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t*) nullptr, (int32_t*) nullptr, (int) n_elem, (hipStream_t) 0);
+    return std::max(a, b);
+}
+
+hipError_t vsr_hnsw_vacuum_mark(const HnswBuildParams& p, const int32_t* d_live, uint32_t n_elem, int32_t skip, uint8_t* d_flag, int32_t* d_list,
+                                int32_t* d_num, void* d_tmp, size_t tmp_bytes, hipStream_t s)
+{
+    hipLaunchKernelGGL(hnsw_vacuum_mark_kernel, dim3((n_elem + 255) / 256), dim3(256), 0, s, p, d_live, n_elem, skip, d_flag);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !d_list) return e;
+    return hipcub::DeviceSelect::Flagged(d_tmp, tmp_bytes, hipcub::CountingInputIterator<int32_t>(0), d_flag, d_list, d_num, (int) n_elem, s);
+}
+
+hipError_t vsr_hnsw_vacuum_renumber(const HnswBuildParams& p, const int32_t* d_live, int32_t* d_map, const int32_t* d_slot_map, uint32_t n_elem,
+                                    int32_t* d_new_nbr0, int32_t* d_new_up_nbr, uint32_t new_max_level, void* d_tmp, size_t tmp_bytes, hipStream_t s)
+{
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_live, d_map, (int) n_elem, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(hnsw_vacuum_renumber_kernel, dim3((n_elem + 3) / 4), dim3(256), 0, s, p, d_live, d_map, d_slot_map, n_elem, d_new_nbr0,
+                       d_new_up_nbr, new_max_level);
+    return hipGetLastError();
 }
 
 size_t vsr_hnsw_build_sort_bytes(uint32_t rec_cap)

@@ -560,18 +560,25 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
 // A sparse build also restarts, with a candidate array twice as long, when a layer search lost an unexpanded candidate as near as
 // the furthest of W (HB_ERR_CANDIDATES, vsr_hnsw_build.hip): pgvector's candidate heap has no bound, and rows without a common
 // index all have inner product 0, so such ties outgrow ef_construction + 2 m entries.
+static int hnsw_env_visited_slots(const char* who, uint32_t* slots)           // VSR_HNSW_BUILD_VISITED_SLOTS; unset: *slots stays
+{
+    if (const char* env = getenv("VSR_HNSW_BUILD_VISITED_SLOTS")) {
+        char* end = nullptr;
+        const long v = strtol(env, &end, 10);
+        if (end == env || *end != '\0' || v < 256 || v > 32768 || (v & (v - 1)) != 0)
+            return fail(VSR_ERR_INVALID, "%s: VSR_HNSW_BUILD_VISITED_SLOTS must be a power of two from 256 to 32768 (got \"%s\")", who, env);
+        *slots = (uint32_t) v;
+    }
+    return VSR_OK;
+}
+
 static int hnsw_build(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out,
                       const char* who, const HnswPrior* prior = nullptr)
 {
     uint32_t slots = 0;
-    if (const char* env = getenv("VSR_HNSW_BUILD_VISITED_SLOTS")) {
-        char* end = nullptr;
-        const long v = strtol(env, &end, 10);
-        if (end == env || *end != '\0' || v < 256 || v > 32768 || (v & (v - 1)) != 0) {
-            if (out) *out = nullptr;
-            return fail(VSR_ERR_INVALID, "%s: VSR_HNSW_BUILD_VISITED_SLOTS must be a power of two from 256 to 32768 (got \"%s\")", who, env);
-        }
-        slots = (uint32_t) v;
+    if (const int rc = hnsw_env_visited_slots(who, &slots)) {
+        if (out) *out = nullptr;
+        return rc;
     }
     uint32_t caps = (uint32_t) (ef_construction + 2 * m);
     for (;;) {
@@ -724,6 +731,419 @@ extern "C" int vsr_hnsw_extend(vsr_corpus* c, int m, int32_t n_elem, int32_t ent
         return hnsw_load(c, expect, expect == RowFormat::BIT ? metric : 0, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper,
                          max_level, out, who);
     return hnsw_build(c, expect, m, ef_construction, metric, seed, 0u, out, who, &pr);
+}
+
+// ---- VACUUM (hnswvacuum.c): delete rows from a graph, repair it on the GPU, squeeze the deleted elements out.
+// pass 1 on the host: the surviving TIDs, which elements live, the highest live element other than the entry (RemoveHeapTids'
+// scan: strict >, so the lowest id of the top level)
+struct HnswVacuumPlan {
+    std::vector<int32_t> live;               // [n_elem] 1: a heap TID is left
+    std::vector<int32_t> tcount, itids;      // the surviving TIDs (internal rows), in their old order, moved to the front; -1 padded
+    int32_t highest = -1, n_live = 0;
+    int64_t removed = 0, kept = 0;
+    bool identity = true;                    // element e is internal row e for every prior element: the direct kernels serve
+};
+
+// per-wave LDS of the repair's search kernel (hb_search_body, VAC): S and the flags, the three HB_NBR arrays, the visited table; the
+// selection's scratch lies over the table, so an entry of S costs 9 bytes and a graph's whole working set can be thousands long
+static size_t hnsw_vacuum_lds_per_wave(uint32_t caps, uint32_t slots)
+{
+    return ((size_t) caps * 8 + ((caps + 15) & ~15u) + (size_t) HB_NBR * 12 + (size_t) slots * 4 + 15) & ~(size_t) 15;
+}
+
+// One attempt with `slots` visited-table entries and `caps` candidate entries, from the caller's arrays.  *guard: as hnsw_build_once
+static int hnsw_vacuum_once(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, const HnswPrior& pr, const HnswVacuumPlan& pl,
+                            uint32_t slots, uint32_t caps, uint32_t batch_max, uint32_t* guard, vsr_hnsw_vacuum_stats* st, int32_t* out_elem_map,
+                            vsr_hnsw** out, const char* who)
+{
+    vsr_ctx* ctx = c->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t ne = (size_t) pr.n_elem, lm0 = (size_t) 2 * m;
+    const int32_t max_level = pr.max_level;
+    const size_t up_words = (size_t) std::max(pr.n_upper, 1) * max_level * m;
+    const uint32_t row_chunks = format_row_chunks(expect, c->dim);
+    std::vector<void*> work;                                                  // everything but the result's arrays
+    std::unique_ptr<vsr_hnsw> h(new vsr_hnsw());
+    h->corpus = c;
+    h->format = expect;
+    h->bit_metric = expect == RowFormat::BIT ? metric : 0;
+    h->m = m;
+    auto bail = [&](int rc) {
+        (void) hipStreamSynchronize(ctx->stream);
+        for (void* q : work) (void) hipFree(q);
+        vsr_hnsw_free(h.release());
+        return rc;
+    };
+#define HV_CHK(call)                                                                                         \
+    do {                                                                                                     \
+        hipError_t e_ = (call);                                                                              \
+        if (e_ != hipSuccess) return bail(fail(VSR_ERR_HIP, "%s: %s", who, hipGetErrorString(e_)));          \
+    } while (0)
+#define HV_ALLOC(ptr, bytes)                                                                                 \
+    do {                                                                                                     \
+        void* q_ = nullptr;                                                                                  \
+        HV_CHK(hipMalloc(&q_, std::max<size_t>((bytes), 16)));                                               \
+        work.push_back(q_);                                                                                  \
+        (ptr) = static_cast<std::remove_reference_t<decltype(ptr)>>(q_);                                     \
+    } while (0)
+    int32_t *w_level, *w_nbr0, *w_up_slot, *w_up_nbr, *w_live, *w_elem_row = nullptr, *w_up_owner, *w_list, *w_num, *w_map, *w_slot_map, *w_stage_n;
+    float *w_dist0, *w_up_dist, *w_stage_d;
+    uint8_t* w_flag;
+    HV_ALLOC(w_level, ne * 4);
+    HV_ALLOC(w_nbr0, ne * lm0 * 4);
+    HV_ALLOC(w_up_slot, ne * 4);
+    HV_ALLOC(w_up_nbr, up_words * 4);
+    HV_ALLOC(w_dist0, ne * lm0 * 4);
+    HV_ALLOC(w_up_dist, up_words * 4);
+    HV_ALLOC(w_live, ne * 4);
+    HV_ALLOC(w_up_owner, (size_t) std::max(pr.n_upper, 1) * 4);
+    HV_ALLOC(w_list, ne * 4);
+    HV_ALLOC(w_num, 16);                                                      // [0]: the repair list's length; [1], [2]: batches of one
+    HV_ALLOC(w_map, ne * 4);
+    HV_ALLOC(w_slot_map, (size_t) std::max(pr.n_upper, 1) * 4);
+    HV_ALLOC(w_flag, ne);
+    HV_CHK(hipMemsetAsync(w_up_nbr, 0xFF, up_words * 4, ctx->stream));
+    HV_CHK(hipMemsetAsync(w_dist0, 0, ne * lm0 * 4, ctx->stream));
+    HV_CHK(hipMemsetAsync(w_up_dist, 0, up_words * 4, ctx->stream));
+    HV_CHK(hipStreamSynchronize(ctx->stream));                                // the copies below are not on the stream
+    HV_CHK(hipMemcpy(w_level, pr.level, ne * 4, hipMemcpyHostToDevice));
+    HV_CHK(hipMemcpy(w_nbr0, pr.nbr0, ne * lm0 * 4, hipMemcpyHostToDevice));
+    HV_CHK(hipMemcpy(w_up_slot, pr.up_slot, ne * 4, hipMemcpyHostToDevice));
+    if (pr.n_upper > 0) {
+        HV_CHK(hipMemcpy(w_up_nbr, pr.up_nbr, (size_t) pr.n_upper * max_level * m * 4, hipMemcpyHostToDevice));
+        HV_CHK(hipMemcpy(w_up_owner, pr.up_owner.data(), (size_t) pr.n_upper * 4, hipMemcpyHostToDevice));
+    }
+    HV_CHK(hipMemcpy(w_live, pl.live.data(), ne * 4, hipMemcpyHostToDevice));
+    if (!pl.identity) {                                                       // a deleted element keeps its row for the whole repair
+        HV_ALLOC(w_elem_row, ne * 4);
+        HV_CHK(hipMemcpy(w_elem_row, pr.elem_row.data(), ne * 4, hipMemcpyHostToDevice));
+    }
+
+    HnswBuildParams bp{};
+    bp.rows = c->d_rows;
+    bp.stride4 = row_chunks;
+    bp.metric = metric == VSR_METRIC_L2 ? M_L2 : M_IP;
+    bp.halves = expect == RowFormat::HALF ? 1 : 0;
+    if (expect == RowFormat::BIT) {
+        bp.bits = 1;
+        bp.metric = metric == VSR_METRIC_JACCARD ? M_JACCARD : M_HAMMING;
+        bp.row_pop = c->d_norm2;
+    }
+    bp.m = (uint32_t) m;
+    bp.efc = (uint32_t) ef_construction + 1u;                                 // the repaired element counts towards its own beam
+    bp.max_level = (uint32_t) max_level;
+    bp.nbr0 = w_nbr0;
+    bp.dist0 = w_dist0;
+    bp.up_slot = w_up_slot;
+    bp.up_nbr = w_up_nbr;
+    bp.up_dist = w_up_dist;
+    bp.level = w_level;
+    bp.elem_row = w_elem_row;
+    bp.caps = caps;
+    bp.hash_slots = slots;
+    const size_t per = hnsw_vacuum_lds_per_wave(caps, slots);
+    if (per > HN_LDS_BUDGET)
+        return bail(fail(VSR_ERR_UNSUPPORTED, "%s: %u candidates with a visited table of %u entries do not fit the LDS", who, caps, slots));
+    bp.lds_per_wave = (uint32_t) per;
+    bp.wpb = (uint32_t) std::min<size_t>(4, HN_LDS_BUDGET / per);
+    bp.err = ctx->err_word();
+
+    HnswVacuumParams vp{};
+    const uint32_t stride = (uint32_t) (2 * m + max_level * m);
+    const uint64_t most = std::min<uint64_t>(batch_max, (uint64_t) std::max(pl.n_live, 1));
+    if (most * stride > 0x7FFFFFFFull) return bail(fail(VSR_ERR_UNSUPPORTED, "%s: a batch of %llu elements with m = %d has too many reverse edges", who, (unsigned long long) most, m));
+    const uint32_t rec_cap_max = (uint32_t) (most * stride);
+    uint64_t *d_key[2], *d_val[2];
+    uint32_t* d_cnt;
+    void* d_tmp;
+    const size_t tmp_bytes = std::max<size_t>({vsr_hnsw_build_sort_bytes(rec_cap_max), vsr_hnsw_build_sort_bytes(stride), vsr_hnsw_vacuum_tmp_bytes((uint32_t) ne), 256});
+    HV_ALLOC(d_key[0], (size_t) rec_cap_max * 8);
+    HV_ALLOC(d_key[1], (size_t) rec_cap_max * 8);
+    HV_ALLOC(d_val[0], (size_t) rec_cap_max * 8);
+    HV_ALLOC(d_val[1], (size_t) rec_cap_max * 8);
+    HV_ALLOC(d_cnt, 64);
+    HV_ALLOC(d_tmp, tmp_bytes);
+    HV_ALLOC(w_stage_n, (size_t) rec_cap_max * 4);
+    HV_ALLOC(w_stage_d, (size_t) rec_cap_max * 4);
+    bp.rec_count = d_cnt;
+    vp.live = w_live;
+    vp.stage_nbr = w_stage_n;
+    vp.stage_dist = w_stage_d;
+    vp.stage_stride = stride;
+
+    HV_CHK(vsr_hnsw_edge_distances(bp, (uint32_t) ne, w_up_owner, (uint32_t) pr.n_upper, ctx->stream));
+    int32_t nrep = 0, nbatch = 0;
+    // one repair batch: `count` elements at d_elems, searched from element `from` (-1: nobody is left, the lists become empty)
+    auto run_batch = [&](const int32_t* d_elems, uint32_t count, uint32_t rec_cap, int32_t from) -> hipError_t {
+        bp.entry = from;
+        bp.entry_level = from >= 0 ? pr.level[from] : -1;
+        bp.first = 0;
+        bp.count = count;
+        bp.rec_cap = rec_cap;
+        bp.rec_key = d_key[0];
+        bp.rec_val = d_val[0];
+        vp.elems = d_elems;
+        nrep += (int32_t) count;
+        ++nbatch;
+        return vsr_hnsw_vacuum_batch(bp, vp, d_tmp, tmp_bytes, d_key[1], d_val[1], ctx->stream);
+    };
+    auto rec_cap_of = [&](int32_t e) { return (uint32_t) (2 * m + pr.level[e] * m); };
+    // NeedsUpdated of one element, on the graph as the stream leaves it
+    auto needs = [&](int32_t e, bool* yes) -> hipError_t {
+        hipError_t e_ = vsr_hnsw_vacuum_mark(bp, w_live, (uint32_t) ne, -1, w_flag, nullptr, nullptr, d_tmp, tmp_bytes, ctx->stream);
+        if (e_ != hipSuccess) return e_;
+        if ((e_ = hipStreamSynchronize(ctx->stream)) != hipSuccess) return e_;
+        uint8_t f = 0;
+        e_ = hipMemcpy(&f, w_flag + e, 1, hipMemcpyDeviceToHost);
+        *yes = f != 0;
+        return e_;
+    };
+    // the entry phase (RepairGraphEntryPoint), batches of one
+    int32_t entry = pr.entry;
+    const int32_t hp = pl.highest;
+    const int32_t ones[2] = {hp, entry};
+    HV_CHK(hipMemcpy(w_num + 1, ones, sizeof ones, hipMemcpyHostToDevice));
+    if (hp >= 0) {
+        bool yes = false;
+        HV_CHK(needs(hp, &yes));
+        if (yes) HV_CHK(run_batch(w_num + 1, 1, rec_cap_of(hp), entry));      // from the entry as it is, deleted or not
+    }
+    if (pl.live[(size_t) entry] == 0) {
+        entry = hp;
+    } else {
+        bool yes = false;
+        HV_CHK(needs(entry, &yes));
+        if (yes) HV_CHK(run_batch(w_num + 2, 1, rec_cap_of(entry), hp));
+    }
+    // the main phase: the repair list once, after the entry phase
+    HV_CHK(vsr_hnsw_vacuum_mark(bp, w_live, (uint32_t) ne, entry, w_flag, w_list, w_num, d_tmp, tmp_bytes, ctx->stream));
+    HV_CHK(hipStreamSynchronize(ctx->stream));
+    int32_t n_list = 0;
+    HV_CHK(hipMemcpy(&n_list, w_num, 4, hipMemcpyDeviceToHost));
+    std::vector<int32_t> list((size_t) std::max(n_list, 1));
+    if (n_list > 0) HV_CHK(hipMemcpy(list.data(), w_list, (size_t) n_list * 4, hipMemcpyDeviceToHost));
+    // the guard word after the entry phase and after every batch: an attempt whose arrays are too short ends where that shows
+    uint32_t word = 0;
+    const uint32_t guard_bits = HB_ERR_VISITED | HB_ERR_RECORDS | HB_ERR_CANDIDATES;
+    HV_CHK(hipMemcpy(&word, bp.err, sizeof word, hipMemcpyDeviceToHost));
+    for (int32_t at = 0; at < n_list && !(word & guard_bits);) {
+        const uint32_t b = (uint32_t) std::min<int64_t>(batch_max, n_list - at);
+        uint64_t cap = 0;
+        for (uint32_t i = 0; i < b; ++i) cap += rec_cap_of(list[(size_t) at + i]);
+        HV_CHK(run_batch(w_list + at, b, (uint32_t) cap, entry));             // (cap <= rec_cap_max: b <= most, a level <= max_level)
+        at += (int32_t) b;
+        HV_CHK(hipStreamSynchronize(ctx->stream));
+        HV_CHK(hipMemcpy(&word, bp.err, sizeof word, hipMemcpyDeviceToHost));
+    }
+    if (word & guard_bits) {
+        *guard = word & guard_bits;
+        word &= ~guard_bits;
+        HV_CHK(hipMemcpy(bp.err, &word, sizeof word, hipMemcpyHostToDevice));
+        return bail(VSR_OK);
+    }
+
+    // pass 3: the compacted index.  Elements in ascending old id, upper slots in ascending old slot, the upper arrays at the new top
+    std::vector<int32_t> map(ne, -1), slot_map((size_t) std::max(pr.n_upper, 1), -1);
+    int32_t n_new = 0, n_upper_new = 0;
+    for (size_t e = 0; e < ne; ++e)
+        if (pl.live[e]) map[e] = n_new++;
+    for (int32_t s = 0; s < pr.n_upper; ++s)
+        if (pr.up_owner[(size_t) s] >= 0 && pl.live[(size_t) pr.up_owner[(size_t) s]]) slot_map[(size_t) s] = n_upper_new++;
+    const int32_t new_max_level = std::max(1, pr.level[entry]);
+    const size_t nn = (size_t) n_new, new_up_words = (size_t) std::max(n_upper_new, 1) * new_max_level * m;
+    std::vector<int32_t> level(nn), up_slot(nn), tcount(nn), erow(nn), itids(nn * 10);
+    for (size_t e = 0; e < ne; ++e) {
+        if (!pl.live[e]) continue;
+        const size_t k = (size_t) map[e];
+        level[k] = pr.level[e];
+        up_slot[k] = pr.up_slot[e] >= 0 ? slot_map[(size_t) pr.up_slot[e]] : -1;
+        tcount[k] = pl.tcount[e];
+        std::copy(pl.itids.begin() + e * 10, pl.itids.begin() + (e + 1) * 10, itids.begin() + k * 10);
+        erow[k] = itids[k * 10];
+    }
+    h->n_elem = n_new;
+    h->entry = map[(size_t) entry];
+    h->entry_level = pr.level[entry];
+    h->max_level = new_max_level;
+    h->n_upper = n_upper_new;
+    HV_CHK(hipMemcpy(w_slot_map, slot_map.data(), slot_map.size() * 4, hipMemcpyHostToDevice));
+    HV_CHK(hipMalloc(&h->d_nbr0, std::max<size_t>(nn * lm0 * 4, 4)));
+    HV_CHK(hipMalloc(&h->d_up_nbr, new_up_words * 4));
+    HV_CHK(hipMemsetAsync(h->d_nbr0, 0xFF, std::max<size_t>(nn * lm0 * 4, 4), ctx->stream));
+    HV_CHK(hipMemsetAsync(h->d_up_nbr, 0xFF, new_up_words * 4, ctx->stream));
+    HV_CHK(vsr_hnsw_vacuum_renumber(bp, w_live, w_map, w_slot_map, (uint32_t) ne, h->d_nbr0, h->d_up_nbr, (uint32_t) new_max_level, d_tmp, tmp_bytes,
+                                    ctx->stream));
+    HV_CHK(hipStreamSynchronize(ctx->stream));
+    HV_CHK(hipMemcpy(&word, bp.err, sizeof word, hipMemcpyDeviceToHost));
+    if (word & guard_bits) {                                                  // (HB_ERR_RECORDS: a live list still named a deleted element)
+        *guard = word & guard_bits;
+        word &= ~guard_bits;
+        HV_CHK(hipMemcpy(bp.err, &word, sizeof word, hipMemcpyHostToDevice));
+        return bail(VSR_OK);
+    }
+    // the device's scan and the host's must agree: the lists were renumbered by the one, the other arrays by the other
+    std::vector<int32_t> dmap(ne);
+    HV_CHK(hipMemcpy(dmap.data(), w_map, ne * 4, hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < ne; ++e)
+        if (pl.live[e] && dmap[e] != map[e]) return bail(fail(VSR_ERR_HIP, "%s: the element scan disagrees at element %zu", who, e));
+#undef HV_ALLOC
+#undef HV_CHK
+    for (void* q : work) (void) hipFree(q);
+    work.clear();
+    auto& up = upload_i32;
+    int rc = VSR_OK;
+    if ((rc = up(&h->d_elem_row, erow.data(), nn)) || (rc = up(&h->d_level, level.data(), nn)) || (rc = up(&h->d_up_slot, up_slot.data(), nn)) ||
+        (rc = up(&h->d_tid_count, tcount.data(), nn)) || (rc = up(&h->d_tids, itids.data(), nn * 10))) {
+        vsr_hnsw_free(h.release());
+        return rc;
+    }
+    if (out_elem_map) std::copy(map.begin(), map.end(), out_elem_map);
+    if (st) {
+        st->elements_repaired = nrep;
+        st->batches = nbatch;
+    }
+    c->hnsw_indexes.push_back(h.get());
+    *out = h.release();
+    return VSR_OK;
+}
+
+// VACUUM of an index after DELETE (include/vsrbac.h).  The ladders are the build's: a visited table twice as large, a candidate
+// array twice as long (or the longest that fits), every attempt from the caller's arrays.  Read at every call (development / tests):
+// VSR_HNSW_VACUUM_CAPS=n, the INITIAL candidate entries (ef_construction + 1 ..), VSR_HNSW_VACUUM_BATCH=n, the batch maximum
+// (1 .. 4096), and VSR_HNSW_BUILD_VISITED_SLOTS as for the build.
+extern "C" int vsr_hnsw_vacuum(vsr_corpus* c, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
+                               const int32_t* tid_count, const int64_t* tids, const int32_t* up_slot, const int32_t* up_nbr, int32_t n_upper,
+                               int32_t max_level, int ef_construction, int metric, const int64_t* dead_rows, int64_t n_dead, uint32_t flags,
+                               int32_t* out_elem_map, vsr_hnsw_vacuum_stats* out_stats, vsr_hnsw** out)
+{
+    const char* who = "vsr_hnsw_vacuum";
+    if (!c || !out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    if (c->format == RowFormat::SPARSE)
+        return fail(VSR_ERR_UNSUPPORTED,
+                    "%s: the graph of a sparsevec corpus cannot be vacuumed yet (the sparse build has no element -> row form): rebuild it with "
+                    "vsr_hnsw_build_sparse over the live rows", who);
+    if (flags != 0) return fail(VSR_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", who, flags);
+    const RowFormat expect = c->format;
+    int rc = hnsw_build_check(c, expect, m, ef_construction, metric, 0u, out, who);
+    if (rc) return rc;
+    if (n_dead < 0 || (n_dead > 0 && !dead_rows)) return fail(VSR_ERR_INVALID, "%s: bad dead_rows", who);
+    for (int64_t i = 0; i < n_dead; ++i)
+        if (dead_rows[i] < 0 || dead_rows[i] >= c->n)
+            return fail(VSR_ERR_INVALID, "%s: dead row %lld is outside [0, %lld)", who, (long long) dead_rows[i], (long long) c->n);
+    HnswPrior pr;
+    rc = hnsw_extend_prepare(c, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, pr, who);
+    if (rc) return rc;
+    vsr_hnsw_vacuum_stats st{};
+    const int bit_metric = expect == RowFormat::BIT ? metric : 0;
+    if (n_dead == 0 || n_elem == 0) {                                         // nothing to delete: the graph as it is
+        st.tuples_kept = pr.n0;
+        for (int32_t e = 0; out_elem_map && e < n_elem; ++e) out_elem_map[e] = e;
+        if (out_stats) *out_stats = st;
+        return hnsw_load(c, expect, bit_metric, m, n_elem, entry, level, nbr0, tid_count, tids, up_slot, up_nbr, n_upper, max_level, out, who);
+    }
+    // pass 1
+    const size_t ne = (size_t) n_elem;
+    HnswVacuumPlan pl;
+    {
+        std::vector<int32_t> inv((size_t) c->n, -1);
+        for (int64_t r = 0; r < c->n; ++r) inv[(size_t) c->h_orig[(size_t) r]] = (int32_t) r;
+        std::vector<uint8_t> dead((size_t) c->n, 0);
+        for (int64_t i = 0; i < n_dead; ++i) dead[(size_t) inv[(size_t) dead_rows[i]]] = 1;
+        pl.live.assign(ne, 0);
+        pl.tcount.assign(ne, 0);
+        pl.itids.assign(ne * 10, -1);
+        int32_t hl = -1;
+        for (size_t e = 0; e < ne; ++e) {
+            int k = 0;
+            for (int t = 0; t < tid_count[e]; ++t) {
+                const int32_t r = pr.itids[e * 10 + (size_t) t];
+                if (!dead[(size_t) r]) pl.itids[e * 10 + (size_t) k++] = r;
+            }
+            pl.tcount[e] = k;
+            pl.removed += tid_count[e] - k;
+            pl.kept += k;
+            pl.live[e] = k > 0;
+            pl.n_live += k > 0;
+            pl.identity = pl.identity && pr.elem_row[e] == (int32_t) e;
+            if (k > 0 && (int32_t) e != entry && level[e] > hl) {
+                pl.highest = (int32_t) e;
+                hl = level[e];
+            }
+        }
+    }
+    st.tuples_removed = pl.removed;
+    st.tuples_kept = pl.kept;
+    st.elements_removed = n_elem - pl.n_live;
+    if (pl.n_live == 0) {                                                     // everything is deleted: the empty index
+        for (int32_t e = 0; out_elem_map && e < n_elem; ++e) out_elem_map[e] = -1;
+        if (out_stats) *out_stats = st;
+        return hnsw_load(c, expect, bit_metric, m, 0, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, out, who);
+    }
+    // the knobs and the initial sizes.  Candidates: what the build holds, ef_construction + 1 + 2 m, over the live share, since
+    // W holds every deleted element met on the way to ef live ones; the result does not depend on it (HB_ERR_CANDIDATES)
+    uint32_t slots = 0;
+    if ((rc = hnsw_env_visited_slots(who, &slots))) return rc;
+    const bool slots_given = slots != 0;
+    if (slots == 0) {
+        slots = 4096;
+        while (slots < (uint32_t) ef_construction * 2u * (uint32_t) m * 2u && slots < 32768u) slots <<= 1;
+    }
+    auto env_int = [&](const char* name, long lo, long hi, long* v) -> int {
+        const char* env = getenv(name);
+        if (!env) return VSR_OK;
+        char* end = nullptr;
+        const long x = strtol(env, &end, 10);
+        if (end == env || *end != '\0' || x < lo || x > hi) return fail(VSR_ERR_INVALID, "%s: %s must be between %ld and %ld (got \"%s\")", who, name, lo, hi, env);
+        *v = x;
+        return VSR_OK;
+    };
+    // the longest candidate array that fits beside `s` visited slots (hnsw_vacuum_lds_per_wave: 9 bytes an entry), a multiple of 16
+    auto caps_fit = [&](uint32_t s) -> uint32_t {
+        const size_t fixed = (size_t) HB_NBR * 12 + (size_t) s * 4 + 64;
+        return HN_LDS_BUDGET > fixed ? (uint32_t) ((HN_LDS_BUDGET - fixed) / 9) & ~15u : 0u;
+    };
+    const uint32_t caps_min = (uint32_t) ef_construction + 1u;
+    long v = 0;
+    if ((rc = env_int("VSR_HNSW_VACUUM_CAPS", (long) caps_min, 1L << 20, &v))) return rc;
+    uint32_t caps;
+    if (v > 0) {
+        caps = (uint32_t) v;
+    } else {
+        const uint64_t base = (uint64_t) ef_construction + 1u + 2u * (uint64_t) m;
+        const uint64_t want = std::min<uint64_t>((base * (uint64_t) n_elem + (uint64_t) pl.n_live - 1) / (uint64_t) pl.n_live, (uint64_t) n_elem);
+        caps = (uint32_t) std::max<uint64_t>(base, std::min<uint64_t>((want + 15) & ~15ull, caps_fit(slots)));
+    }
+    // every candidate was visited first, so a table that fills at 3/4 should hold what the candidate array is sized for
+    while (!slots_given && v == 0 && slots < 32768u && (uint64_t) slots * 3u < (uint64_t) caps * 4u && hnsw_vacuum_lds_per_wave(caps, slots * 2u) <= HN_LDS_BUDGET)
+        slots *= 2u;
+    long batch = HB_BATCH_MAX;
+    if ((rc = env_int("VSR_HNSW_VACUUM_BATCH", 1, (long) HB_BATCH_MAX, &batch))) return rc;
+    for (;;) {
+        uint32_t guard = 0;
+        ++st.attempts;
+        rc = hnsw_vacuum_once(c, expect, m, ef_construction, metric, pr, pl, slots, caps, (uint32_t) batch, &guard, &st, out_elem_map, out, who);
+        if (rc != VSR_OK || guard == 0) {
+            if (rc == VSR_OK && out_stats) *out_stats = st;
+            return rc;
+        }
+        if (guard & HB_ERR_RECORDS)
+            return fail(VSR_ERR_UNSUPPORTED, "%s: the repair at ef_construction = %d with m = %d dropped reverse edges or left a list that names a "
+                        "deleted element: the graph would be incomplete", who, ef_construction, m);
+        const char* rebuild = "a graph this dead is to be rebuilt over its live rows (vsr_hnsw_build*)";
+        if (guard & HB_ERR_CANDIDATES) {
+            const uint32_t next = std::min(caps * 2u, caps_fit(slots));
+            if (next <= caps || hnsw_vacuum_lds_per_wave(next, slots) > HN_LDS_BUDGET)
+                return fail(VSR_ERR_UNSUPPORTED, "%s: a layer search of the repair holds more than %u candidates (%d of %d elements live) and no longer "
+                            "candidate array fits the LDS: %s", who, caps, pl.n_live, n_elem, rebuild);
+            caps = next;
+            if (!(guard & HB_ERR_VISITED)) continue;
+        }
+        if (slots >= 32768u || hnsw_vacuum_lds_per_wave(caps, slots * 2u) > HN_LDS_BUDGET)
+            return fail(VSR_ERR_UNSUPPORTED, "%s: a layer search of the repair fills its visited table of %u entries (%d of %d elements live) and no "
+                        "larger one fits the LDS: %s", who, slots, pl.n_live, n_elem, rebuild);
+        slots *= 2u;
+    }
 }
 
 // device memory of the graph arrays of an index (the corpus is counted by vsr_corpus_device_bytes); any index.  The row format

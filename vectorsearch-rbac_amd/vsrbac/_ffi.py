@@ -23,6 +23,11 @@ class Stats(C.Structure):
                 ("host_ms", C.c_double), ("host_wait_ms", C.c_double)]
 
 
+class HnswVacuumStats(C.Structure):          # vsr_hnsw_vacuum_stats
+    _fields_ = [("tuples_removed", C.c_int64), ("tuples_kept", C.c_int64), ("elements_removed", C.c_int32),
+                ("elements_repaired", C.c_int32), ("batches", C.c_int32), ("attempts", C.c_int32)]
+
+
 # every symbol include/vsrbac.h declares: name -> (restype, argtypes)
 _vp, _i, _i64, _i32 = C.c_void_p, C.c_int, C.c_int64, C.c_int32
 SYMBOLS = {
@@ -106,6 +111,8 @@ SYMBOLS = {
     "vsr_hnsw_build_ex": (_i, [_vp, _i, _i, _i, C.c_uint64, C.c_uint32, _vp]),
     "vsr_hnsw_extend": (_i, [_vp, _i, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i, _i, C.c_uint64, C.c_uint32,
                              C.POINTER(_vp)]),
+    "vsr_hnsw_vacuum": (_i, [_vp, _i, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i, _i, _vp, _i64, C.c_uint32, _vp,
+                             C.POINTER(HnswVacuumStats), C.POINTER(_vp)]),
     "vsr_hnsw_export_shape":(_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_hnsw_export": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vsr_hnsw_info": (_i, [_vp, _vp, _vp, _vp, _vp]),

@@ -593,6 +593,37 @@ class Corpus:
                                         int(ef_construction), _metric(metric), int(seed), 0, C.byref(h)))
         return HnswIndex(self, h)
 
+    def vacuum_hnsw(self, graph, dead_rows, ef_construction=64, metric=None):
+        """VACUUM after DELETE (vsr_hnsw_vacuum): `graph` is the dict HnswIndex.export() returns for a graph over this corpus,
+        `dead_rows` the row indices of this corpus that were deleted (duplicates allowed, rows no TID names ignored).  The rows
+        stay in this corpus: the repair walks through deleted elements.  Every live element that pointed at a deleted one, or
+        whose layer-0 list is not full, is repaired on the GPU with the build's search and selection; the deleted elements are
+        then squeezed out and the live ones renumbered in ascending old id.  fp32, halfvec and bit corpora; metric: None is
+        "l2", or "hamming" on a bit corpus.  Returns (HnswIndex, stats): stats has tuples_removed, tuples_kept,
+        elements_removed, elements_repaired, batches, attempts and "elem_map", the new id of every old element (-1: deleted).
+        No dead rows: the graph is loaded as it is.  Everything dead: an empty index whose searches return nothing.
+        Recipe to drop the rows from the corpus as well: vacuum, export() the result, formats.remap_hnsw_rows(export,
+        new_index_of_old_row), reload the corpus without the dead rows, load_hnsw(remapped) on it, free the old pair.
+        UPDATE is vacuum followed by extend_hnsw: remap onto a corpus of the live rows plus the new versions (the extension
+        inserts every row no TID names, so the dead rows must be gone from it) and extend there."""
+        if metric is None:
+            metric = "hamming" if self.is_bit else "l2"
+        a = lambda name, dt: np.ascontiguousarray(graph[name], dtype=dt)
+        level, nbr0, tc, tids = a("level", np.int32), a("nbr0", np.int32), a("tid_count", np.int32), a("tids", np.int64)
+        up_slot, up_nbr = a("up_slot", np.int32), a("up_nbr", np.int32)
+        n_upper = int((up_slot >= 0).sum())
+        dead = np.ascontiguousarray(np.asarray(dead_rows, dtype=np.int64).ravel())
+        elem_map = np.full(level.size, -1, dtype=np.int32)
+        st = _ffi.HnswVacuumStats()
+        h = C.c_void_p()
+        check(self._lib.vsr_hnsw_vacuum(self._h, int(graph["m"]), level.size, int(graph["entry"]), _ptr(level), _ptr(nbr0), _ptr(tc),
+                                        _ptr(tids), _ptr(up_slot), _ptr(up_nbr), n_upper, int(graph["max_level"]),
+                                        int(ef_construction), _metric(metric), _ptr(dead), dead.size, 0, _ptr(elem_map),
+                                        C.byref(st), C.byref(h)))
+        stats = {name: int(getattr(st, name)) for name, _ in st._fields_}
+        stats["elem_map"] = elem_map
+        return HnswIndex(self, h), stats
+
     def build_hnsw_bit(self, m=16, ef_construction=64, metric="hamming", seed=1, merge_duplicates=False):
         """CREATE INDEX ... USING hnsw (col bit_hamming_ops | bit_jaccard_ops) over this bit corpus (vsr_hnsw_build_bit):
         build_hnsw's batched insertion on the packed rows.  merge_duplicates: byte-identical rows share an element -- the
@@ -1103,6 +1134,13 @@ class HnswIndex:
         Corpus.extend_hnsw: the graph is kept, only the new rows are inserted.  This index and its corpus stay as they are: free
         the old pair once the new one serves."""
         return corpus.extend_hnsw(self.export(), ef_construction, metric, seed)
+
+    def vacuumed(self, dead_rows, ef_construction=64, metric=None):
+        """(HnswIndex, stats): this index without `dead_rows`, repaired and compacted -- Corpus.vacuum_hnsw over export().  The
+        rows stay in the corpus and this index stays as it is: free it once the new one serves.  To drop the rows from the
+        corpus too: export() the result, formats.remap_hnsw_rows, reload the corpus without the dead rows, load_hnsw, free
+        the old pair.  UPDATE is vacuum followed by extend_hnsw."""
+        return self.corpus.vacuum_hnsw(self.export(), dead_rows, ef_construction, metric)
 
     def search_device(self, d_queries, nq, k, ef_search, metric, filters, d_block, d_doc, d_rows, d_dist, d_counts,
                       d_visited=None):

@@ -497,3 +497,30 @@ def load_hnsw(path):
         graph = {name: np.ascontiguousarray(z[name], dtype=dt) for name, dt in _HNSW_ARRAYS}
         graph.update({name: int(z[name]) for name in _HNSW_SCALARS})
     return graph
+
+
+def remap_hnsw_rows(graph, new_index_of_old_row):
+    """Move an exported graph onto a corpus whose rows were renumbered: every heap TID t becomes new_index_of_old_row[t].
+    The step between Corpus.vacuum_hnsw and a corpus loaded without the dead rows: vacuum, export() the result,
+    remap_hnsw_rows(export, new_index_of_old_row), reload the corpus, Corpus.load_hnsw(remapped), free the old pair.
+    new_index_of_old_row: an integer array over the OLD corpus's rows, -1 for a row that is gone.  A TID that names such a
+    row, or a row outside the array, is a ValueError: the graph was not vacuumed of it.  Returns a new dict; the -1 padding of
+    `tids` past tid_count stays."""
+    new_of = np.asarray(new_index_of_old_row, dtype=np.int64).ravel()
+    tids = np.array(graph["tids"], dtype=np.int64, copy=True)
+    tc = np.asarray(graph["tid_count"], dtype=np.int64)
+    if tids.ndim != 2 or tids.shape[0] != tc.size:
+        raise ValueError("remap_hnsw_rows: tids must be [n_elem][10] beside tid_count [n_elem]")
+    used = np.arange(tids.shape[1])[None, :] < tc[:, None]
+    old = tids[used]
+    if old.size and (old.min() < 0 or old.max() >= new_of.size):
+        raise ValueError("remap_hnsw_rows: a heap TID names a row outside new_index_of_old_row")
+    new = new_of[old]
+    if new.size and new.min() < 0:
+        bad = int(old[np.argmin(new)])
+        raise ValueError(f"remap_hnsw_rows: row {bad} is named by a heap TID but has no new index (vacuum it first)")
+    tids[used] = new
+    tids[~used] = -1
+    out = dict(graph)
+    out["tids"] = tids
+    return out
