@@ -649,9 +649,15 @@ int vsr_hnsw_extend(vsr_corpus* corpus, int m, int32_t n_elem, int32_t entry, co
  *   - Refusals: those of vsr_hnsw_extend -- a sparse corpus (VSR_ERR_UNSUPPORTED, the message names sparsevec), a view corpus, the
  *     build's limits on m, ef_construction, metric and halfvec dimension, and its host checks of the prior graph (written through).
  *   - A search that cannot find ef_construction live elements admits every candidate, so the working set of a mostly deleted graph
- *     outgrows the kernel's arrays: the call then runs again with a visited table / candidate array twice as large, from the
- *     caller's arrays, and when nothing larger fits the LDS it is VSR_ERR_UNSUPPORTED (rebuild over the live rows), never a
- *     thinner graph.  The result does not depend on the initial sizes.
+ *     outgrows the kernel's arrays in the LDS: the call then runs again with a visited table / candidate array twice as large,
+ *     from the caller's arrays.  When nothing larger fits the LDS it runs once more in mixed form: the repairs that fit stay as
+ *     they are, and each repair that does not is redone from scratch with its candidates (pgvector's two heaps), its selection
+ *     scratch and an exact visited bitmap in a workspace in device memory, 28 bytes and one bit per element of the graph; a
+ *     bounded pool of such workspaces is shared by the repairs that need one.  That form cannot overflow, so what is left to fail
+ *     is the allocation of the pool (VSR_ERR_HIP).  The result depends neither on the initial sizes nor on which form a repair
+ *     ran in.  Environment, read at every call: VSR_HNSW_VACUUM_SPILL=0 restores the refusal where the ladders end
+ *     (VSR_ERR_UNSUPPORTED: rebuild over the live rows), =all runs every repair in the global-memory form; VSR_HNSW_VACUUM_LDS
+ *     and VSR_HNSW_VACUUM_SPILL_WAVES bound the LDS the sizing believes in and the pool.
  * To drop the deleted rows from the corpus too: export the result, remap its TIDs, load a corpus without them and vsr_hnsw_load.
  * UPDATE is vacuum followed by vsr_hnsw_extend.  The result is an ordinary index.  Synchronises. */
 typedef struct {
@@ -667,6 +673,9 @@ int vsr_hnsw_vacuum(vsr_corpus* corpus, int m, int32_t n_elem, int32_t entry, co
                     const int64_t* dead_rows, int64_t n_dead, uint32_t flags,
                     int32_t* out_elem_map /* [n_elem] new id or -1, may be NULL */, vsr_hnsw_vacuum_stats* out_stats /* may be NULL */,
                     vsr_hnsw** out);
+/* What the vacuum that made this index spilled: repairs run in the global-memory form, and the bytes of the workspace pool.
+ * 0 / 0 for an index any other call made. */
+int vsr_hnsw_vacuum_spill_info(const vsr_hnsw* index, int32_t* spilled_repairs, int64_t* workspace_bytes);
 /* Predicate-aware walk (off by default: pgvector filters what the index returns, hnswscan.c + the executor's RLS qual).  On:
  * the layer-0 search of later vsr_hnsw_search* calls applies the query's filter while it walks, ACORN-1 style -- the result
  * set and the candidate set hold permitted elements only, and an expansion also takes the permitted neighbours of its

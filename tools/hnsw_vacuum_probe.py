@@ -1,16 +1,19 @@
 """Cost of vacuuming an HNSW graph (vsr_hnsw_vacuum) against building it again over the live rows.
 
-The two shapes of tools/hnsw_extend_probe.py (120 000 x 128 fp32, 1M x 128 halfvec; m = 16, ef_construction = 64, L2), 10 % and 50 %
-of the rows deleted at random.  For each, alternately and --runs times after one warm-up of each call:
+The two shapes of tools/hnsw_extend_probe.py (120 000 x 128 fp32, 1M x 128 halfvec; m = 16, ef_construction = 64, L2), 10 %, 30 % and
+50 % of the rows deleted at random.  For each, alternately and --runs times after one warm-up of each call:
 
   (a) vsr_hnsw_vacuum of the exported graph of all rows -- the whole call: the host's validation and pass 1, the uploads, the
       edge-distance launch, the repair batches (every attempt, when the call restarts with larger arrays), the compaction;
   (b) vsr_hnsw_build* over a corpus of the live rows alone: existing code, the yardstick.
 
-Medians with min and max, the call's attempts and batches, and recall@10 at ef_search 40 of both graphs against the exact scan
-over the live rows.  Whether (a) beats (b) at 50 % is the open question; the record says which way it went.
+Medians with min and max, the call's attempts and batches, the repairs it ran in the global-memory form and the bytes of their
+workspace pool (HnswIndex.vacuum_spill_info), and recall@10 at ef_search 40 of both graphs against the exact scan over the live
+rows.  Whether (a) beats (b) at 50 % is the open question; the record says which way it went.
 
-    python tools/hnsw_vacuum_probe.py [--shapes f32 half] [--out profiles/hnsw_vacuum.json]
+    python tools/hnsw_vacuum_probe.py [--shapes f32 half] [--shares 10 30 50] [--out profiles/hnsw_vacuum.json]
+
+The legs of a shape that are not measured again (--shares) stay in the file as they are.
 
 Prints one JSON record and writes it to --out (an existing "build_vs_parent" entry, tools/hnsw_build_probe.py's comparison with the
 parent commit's library, is kept)."""
@@ -45,7 +48,7 @@ def recall(index, exact_rows, q, to_exact=None):
     return hit / (len(q) * K)
 
 
-def measure(ctx, shape, runs, seed):
+def measure(ctx, shape, runs, seed, shares, rec, save):
     import vsrbac
     from hnsw_extend_probe import rows_of
     x = rows_of(shape, seed)
@@ -59,9 +62,12 @@ def measure(ctx, shape, runs, seed):
     graph = idx.export()
     idx.free()
     print(f"{shape}: graph of {n} rows exported", file=sys.stderr, flush=True)
-    rec = {"rows": n, "dim": DIM, "format": "fp32" if shape == "f32" else "halfvec"}
-    for share in (10, 50):
-        dead = np.sort(rng.choice(n, n * share // 100, replace=False))
+    rec.update({"rows": n, "dim": DIM, "format": "fp32" if shape == "f32" else "halfvec"})
+    for share in (10, 30, 50):
+        # (10 and 50 draw what they always drew; 30 has a stream of its own)
+        dead = np.sort((rng if share != 30 else np.random.default_rng(seed + 30)).choice(n, n * share // 100, replace=False))
+        if share not in shares:
+            continue
         live = np.setdiff1d(np.arange(n), dead)
         part = load(x[live])
         exact = part.search(q, K, "l2").rows                   # live-corpus row indices
@@ -82,11 +88,13 @@ def measure(ctx, shape, runs, seed):
             b.free()
             b2.free()
             part.free()
+            save()
             continue
         new_of = np.full(n, -1, dtype=np.int64)
         new_of[live] = np.arange(len(live))
         r_vac = recall(v, exact, q, new_of)
         assert v.info()[0] == len(live)
+        spilled, ws_bytes = v.vacuum_spill_info()
         v.free()
         _, b = timed(lambda: build(part))
         r_build = recall(b, exact, q)
@@ -107,15 +115,17 @@ def measure(ctx, shape, runs, seed):
             "dead_rows": int(len(dead)), "vacuum_s": stats(t_vac), "rebuild_live_rows_s": stats(t_build),
             "vacuum_over_rebuild": statistics.median(t_vac) / statistics.median(t_build),
             "attempts_per_call": max(attempts), "batches": max(batches), "elements_repaired": st["elements_repaired"],
+            "spilled_repairs": spilled, "workspace_bytes": ws_bytes,
             f"recall_at_{K}_ef{EF}": {"vacuumed": r_vac, "rebuilt": r_build},
         }
+        save()                                                 # after every leg: the long ones come last
     full.free()
-    return rec
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--shapes", nargs="+", default=["f32", "half"], choices=["f32", "half"])
+    ap.add_argument("--shares", nargs="+", type=int, default=[10, 30, 50], choices=[10, 30, 50], help="per cent of the rows deleted")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--seed", type=int, default=20260117)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hnsw_vacuum.json"))
@@ -131,10 +141,13 @@ def main():
     ctx = vsrbac.Context(0)
     rec["device"] = ctx.device_info()["name"]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    for shape in args.shapes:
-        rec[shape] = measure(ctx, shape, args.runs, args.seed)
-        with open(args.out, "w") as f:                        # after every shape: the long one comes last
+
+    def save():
+        with open(args.out, "w") as f:
             f.write(json.dumps(rec, indent=1) + "\n")
+
+    for shape in args.shapes:
+        measure(ctx, shape, args.runs, args.seed, args.shares, rec.setdefault(shape, {}), save)
     ctx.close()
     print(json.dumps(rec))
 

@@ -58,7 +58,22 @@ struct HnswVacuumParams {
     int32_t*       stage_nbr = nullptr;      // [p.count][stage_stride] the new lists: layer 0 (2m), then layers 1 .. max_level (m each)
     float*         stage_dist = nullptr;     // their distances
     uint32_t       stage_stride = 0;         // 2m + max_level * m
+    // the spill form (hnsw_vacuum_search_spill_kernel): repairs whose working set is in a workspace in global memory
+    uint32_t*      spill_count = nullptr;    // mixed attempt: a repair of the LDS kernel that outgrows its arrays appends its batch index to
+    int32_t*       spill_list = nullptr;     // spill_list[p.count] and sets no guard bit; nullptr: the guard bits, as ever
+    unsigned char* spill_ws = nullptr;       // [spill_pool] workspaces of spill_ws_bytes each (hnsw_vacuum_spill_ws_bytes(spill_n))
+    uint64_t       spill_ws_bytes = 0;
+    uint32_t       spill_pool = 0;           // waves of the spill launch; wave w takes spilled repairs w, w + spill_pool, ..; 0: no launch
+    uint32_t       spill_n = 0;              // n_elem: what every array of a workspace holds
+    uint32_t       spill_all = 0;            // 1: every repair of the batch runs in the spill form and the LDS kernel is not launched
+    uint32_t*      spill_total = nullptr;    // += the repairs the spill launches ran
 };
+
+// one workspace of the spill form for a graph of n elements: C, W and T (8 bytes an element each), wd (4) and the visited bitmap
+inline size_t hnsw_vacuum_spill_ws_bytes(uint32_t n)
+{
+    return ((size_t) n * 28 + (((size_t) n + 31) / 32) * 4 + 15) & ~(size_t) 15;
+}
 
 // what the merging pre-pass (vsr_hnsw_dedup.hip) leaves: device arrays of n_elem entries, the caller's to hipFree
 struct HnswElemTable {
@@ -85,6 +100,8 @@ hipError_t vsr_hnsw_build_batch(vsr::HnswBuildParams& p, void* d_sort_tmp, size_
 size_t vsr_hnsw_build_sort_bytes(uint32_t rec_cap);
 // vsr_hnsw_vacuum.  One repair batch (p.count <= HB_BATCH_MAX elements, v.elems): the searches into v.stage_*, the install launch,
 // the sort and the link launch, all on s.  The selection's scratch lies over the visited table (hash_slots / 3 candidates).
+// With v.spill_pool > 0 the spill launch runs between the searches and the install: over the repairs the LDS launch listed
+// (v.spill_count / v.spill_list, the mixed attempt) or over all of them, the LDS launch left out (v.spill_all).
 hipError_t vsr_hnsw_vacuum_batch(vsr::HnswBuildParams& p, const vsr::HnswVacuumParams& v, void* d_sort_tmp, size_t sort_tmp_bytes,
                                  uint64_t* d_key_alt, uint64_t* d_val_alt, hipStream_t s);
 // scratch of the compaction and the scan below, for n_elem elements

@@ -84,6 +84,13 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_wave_barrier();
 }
 
+// global-memory stores of the wave visible to its later loads, and LDS as wave_sync (vsr_hnsw.h has the same for K4's discard array)
+__device__ __forceinline__ void wave_sync_global()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
 __device__ __forceinline__ int32_t* hb_list(const HnswBuildParams& p, uint32_t e, int lc, float** dist)
 {
     if (lc == 0) {
@@ -236,7 +243,8 @@ __device__ __forceinline__ int hb_select(const HnswBuildParams& p, const uint64_
 // and the element itself leave the candidates (RemoveElements); the new lists go to v.stage_* and not to the graph, which the
 // other waves of the batch are reading.  S can outgrow any bound here (a graph with few live elements admits everything), so the
 // loss check of the sparse build is on, and so is one for a W longer than S.
-template <bool IND, int ROWS, bool VAC>
+// MIXED (VAC only): the mixed attempt's form, see the end of the body
+template <bool IND, int ROWS, bool VAC, bool MIXED = false>
 __device__ __forceinline__ void hb_search_body(const HnswBuildParams& p, const HnswVacuumParams& v)
 {
     extern __shared__ __align__(16) unsigned char smem_all[];
@@ -300,6 +308,7 @@ __device__ __forceinline__ void hb_search_body(const HnswBuildParams& p, const H
     }
     if (p.entry < 0) return;                                                  // the very first element (VAC: nobody else is left)
 
+    constexpr bool defer = VAC && MIXED;                                      // mixed attempt: records wait until every layer is done
     bool overflow = false;
     uint32_t used = 0;
     auto clear_visited = [&]() {
@@ -472,23 +481,53 @@ __device__ __forceinline__ void hb_search_body(const HnswBuildParams& p, const H
         float* dl;
         int32_t* nl = own_list(lc, &dl);
         uint32_t base = 0;
-        if (lane == 0 && ns > 0) base = atomicAdd(p.rec_count, (uint32_t) ns);
+        if (lane == 0 && ns > 0 && !defer) base = atomicAdd(p.rec_count, (uint32_t) ns);
         base = (uint32_t) __shfl((int) base, 0);
         for (int j = lane; j < ns; j += 64) {
             const uint64_t key = C[sel[j]];
             nl[j] = (int32_t) (uint32_t) key;
             dl[j] = mono_to_float((uint32_t) (key >> 32));
-            if (base + (uint32_t) j < p.rec_cap) {
+            if (!defer && base + (uint32_t) j < p.rec_cap) {
                 // slots are claimed in wave arrival order; the sort key carries the index in the batch (< 4096 = 2^HB_SRC_BITS),
                 // so that a (layer, target) run comes out in ascending source element whatever the arrival order was
                 p.rec_key[base + j] = ((uint64_t) (uint32_t) lc << (32 + HB_SRC_BITS)) | ((uint64_t) (uint32_t) key << HB_SRC_BITS) | bi;
                 p.rec_val[base + j] = ((uint64_t) me << 32) | __float_as_uint(mono_to_float((uint32_t) (key >> 32)));
             }
         }
-        if (lane == 0 && ns > 0 && base + (uint32_t) ns > p.rec_cap) atomicOr(p.err, HB_ERR_RECORDS);   // (cannot happen: the host sizes rec_cap from the levels)
+        if (!defer && lane == 0 && ns > 0 && base + (uint32_t) ns > p.rec_cap) atomicOr(p.err, HB_ERR_RECORDS);   // (cannot happen: the host sizes rec_cap from the levels)
         if (lane == 0)
             for (uint32_t i = 0; i < count; ++i) X[i] = 0;                    // W is the next layer's entry set
         wave_sync();
+    }
+    if constexpr (defer) {
+        {
+            // mixed attempt: a repair that outgrew its arrays leaves no record and no guard bit, only its batch index -- the spill
+            // launch redoes it from scratch, staged lists included; one that fit emits the records of its staged lists now (each
+            // lane reads back what it stored itself; the lists are packed, so their lengths are the counts of the selections)
+            if (overflow || lost) {
+                if (lane == 0) v.spill_list[atomicAdd(v.spill_count, 1u)] = (int32_t) bi;
+                return;
+            }
+            for (int lc = my_level; lc >= 0; --lc) {
+                float* dl;
+                const int32_t* nl = own_list(lc, &dl);
+                const uint32_t lm = lc == 0 ? 2 * p.m : p.m;
+                uint32_t ns = 0;
+                for (uint32_t j0 = 0; j0 < lm; j0 += 64) ns += (uint32_t) __popcll(__ballot(j0 + (uint32_t) lane < lm && nl[j0 + (uint32_t) lane] >= 0));
+                if (ns == 0) continue;
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(p.rec_count, ns);
+                base = (uint32_t) __shfl((int) base, 0);
+                for (uint32_t j = (uint32_t) lane; j < ns; j += 64) {
+                    if (base + j < p.rec_cap) {
+                        p.rec_key[base + j] = ((uint64_t) (uint32_t) lc << (32 + HB_SRC_BITS)) | ((uint64_t) (uint32_t) nl[j] << HB_SRC_BITS) | bi;
+                        p.rec_val[base + j] = ((uint64_t) me << 32) | __float_as_uint(dl[j]);
+                    }
+                }
+                if (lane == 0 && base + ns > p.rec_cap) atomicOr(p.err, HB_ERR_RECORDS);
+            }
+            return;
+        }
     }
     if (overflow && lane == 0) atomicOr(p.err, HB_ERR_VISITED);
     if constexpr (ROWS == ROWS_SPARSE || VAC)
@@ -501,10 +540,240 @@ __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildP
     hb_search_body<IND, ROWS, false>(p, HnswVacuumParams{});
 }
 
-template <bool IND, int ROWS>
+template <bool IND, int ROWS, bool MIXED>
 __global__ __launch_bounds__(256) void hnsw_vacuum_search_kernel(const HnswBuildParams p, const HnswVacuumParams v)
 {
-    hb_search_body<IND, ROWS, true>(p, v);
+    hb_search_body<IND, ROWS, true, MIXED>(p, v);
+}
+
+// ---- the spill form of the repair (vsr_hnsw_vacuum): the algorithm of hb_search_body<.., VAC = true> with everything that grows
+// with the working set in a per-wave workspace in GLOBAL memory (HnswVacuumParams::spill_ws), for repairs whose working set no
+// LDS holds.  An element is visited once and pushed once in a layer search, so arrays of n_elem entries cannot overflow: this
+// form has no ladder and sets neither HB_ERR_VISITED nor HB_ERR_CANDIDATES.
+// The sorted array S of the LDS form is pgvector's two heaps here (hnswutils.c:813-976): C, a binary min-heap of everything pushed
+// and not yet expanded, and W, a binary max-heap of the nearest pushed - popped entries, both on (distance, id) keys, which are
+// distinct, so what a pop returns does not depend on the heaps' inner order.  "first open entry of S" is C's top, "S[wl - 1]" is
+// W's top, a live push beyond ef pops W.  A shifting insert into a sorted array of thousands of entries would cost count / 64
+// dependent round trips to memory per push; a heap operation costs at most log2(count), and only lane 0 touches the heaps, so they
+// need no ordering between lanes.  Between layers W is copied to C and C is sorted by the whole wave (bitonic, in place): a sorted
+// array is a min-heap, and it is W nearest first, which RemoveElements filters into T for hb_select.
+// Visited set: an exact bitmap of n_elem bits, set with atomicOr, cleared before every layer search -- so nothing of the previous
+// layer or of the previous repair in this workspace is left.  Stores of one lane that other lanes load (the copy, the sort, T)
+// are ordered with wave_sync_global(): wave_sync()'s wavefront scope orders LDS only.
+template <bool MAX>
+__device__ __forceinline__ void hs_heap_push(uint64_t* H, uint32_t& n, const uint64_t key)
+{
+    uint32_t i = n++;
+    while (i > 0) {
+        const uint32_t up = (i - 1) >> 1;
+        const uint64_t uk = H[up];
+        if (MAX ? uk >= key : uk <= key) break;
+        H[i] = uk;
+        i = up;
+    }
+    H[i] = key;
+}
+
+// removes the top (n >= 1)
+template <bool MAX>
+__device__ __forceinline__ void hs_heap_pop(uint64_t* H, uint32_t& n)
+{
+    const uint64_t key = H[--n];
+    uint32_t i = 0;
+    for (;;) {
+        uint32_t c = 2 * i + 1;
+        if (c >= n) break;
+        uint64_t ck = H[c];
+        if (c + 1 < n) {
+            const uint64_t c2 = H[c + 1];
+            if (MAX ? c2 > ck : c2 < ck) { ck = c2; ++c; }
+        }
+        if (MAX ? key >= ck : key <= ck) break;
+        H[i] = ck;
+        i = c;
+    }
+    H[i] = key;                                                               // (n == 0: H[0] again, harmless)
+}
+
+// one repair: batch element bi in workspace ws; nb, nd, sel: the wave's HB_NBR arrays in LDS
+template <bool IND, int ROWS>
+__device__ __forceinline__ void hb_spill_repair(const HnswBuildParams& p, const HnswVacuumParams& v, const uint32_t bi, unsigned char* ws,
+                                                int32_t* nb, float* nd, int32_t* sel, const int lane)
+{
+    const uint32_t n = v.spill_n, words = (n + 31u) / 32u;
+    uint64_t* Cq = reinterpret_cast<uint64_t*>(ws);                           // [n] min-heap: pushed, not expanded
+    uint64_t* Wq = Cq + n;                                                    // [n] max-heap: W
+    uint64_t* T = Wq + n;                                                     // [n] the selection's candidates
+    int32_t*  wd = reinterpret_cast<int32_t*>(T + n);                         // [n] its passed-over candidates
+    uint32_t* bm = reinterpret_cast<uint32_t*>(wd + n);                       // [words] visited
+    const uint32_t me = (uint32_t) v.elems[bi];
+    const float4* q = hb_row<IND>(p, me);
+    const int my_level = p.level[me];
+    int32_t* st_n = v.stage_nbr + (size_t) bi * v.stage_stride;
+    float* st_d = v.stage_dist + (size_t) bi * v.stage_stride;
+    for (int lc = 0; lc <= my_level; ++lc) {                                  // the element's staged lists start empty
+        const uint32_t at = lc == 0 ? 0u : (uint32_t) (lc + 1) * p.m, lm = lc == 0 ? 2 * p.m : p.m;
+        for (uint32_t j = (uint32_t) lane; j < lm; j += 64) { st_n[at + j] = -1; st_d[at + j] = 0.0f; }
+    }
+    if (p.entry < 0) return;                                                  // nobody else is left
+
+    uint32_t cn = 0, wn = 0;                                                  // entries of C and W (uniform: lane 0 changes them, then shares)
+    // HnswSearchLayer: on entry W holds the entry points and C the same keys, sorted; on exit W is the layer's result
+    auto search_layer = [&](int lc, uint32_t ef_) {
+        const uint32_t lm = lc == 0 ? 2 * p.m : p.m;
+        for (uint32_t i = (uint32_t) lane; i < words; i += 64) bm[i] = 0u;
+        wave_sync_global();
+        uint32_t live_pushed = 0;
+        for (uint32_t base = 0; base < cn; base += 64) {
+            const uint32_t i = base + (uint32_t) lane;
+            const uint32_t e = i < cn ? (uint32_t) Cq[i] : 0u;
+            if (i < cn) (void) atomicOr(&bm[e >> 5], 1u << (e & 31u));
+            live_pushed += (uint32_t) __popcll(__ballot(i < cn && v.live[e] != 0));
+        }
+        wave_sync_global();
+        for (;;) {
+            uint32_t ce = 0xFFFFFFFFu;
+            if (lane == 0 && cn > 0) {
+                const uint64_t ckey = Cq[0], fkey = Wq[0];
+                if (!(mono_to_float((uint32_t) (ckey >> 32)) > mono_to_float((uint32_t) (fkey >> 32)))) {
+                    ce = (uint32_t) ckey;
+                    hs_heap_pop<false>(Cq, cn);
+                }
+            }
+            ce = (uint32_t) __shfl((int) ce, 0);
+            if (ce == 0xFFFFFFFFu) break;                                     // (an element id is below 2^31)
+            cn = (uint32_t) __shfl((int) cn, 0);
+            float* dl;
+            const int32_t* nl = hb_list(p, ce, lc, &dl);
+            int cnt = 0;
+            for (uint32_t j0 = 0; j0 < lm; j0 += 64) {
+                const uint32_t j = j0 + (uint32_t) lane;
+                const int32_t my = j < lm ? nl[j] : -1;
+                bool fresh = false;
+                if (my >= 0) {
+                    const uint32_t bit = 1u << ((uint32_t) my & 31u);
+                    fresh = (atomicOr(&bm[(uint32_t) my >> 5], bit) & bit) == 0u;
+                }
+                const uint64_t fm = __ballot(fresh);
+                if (fresh) nb[cnt + __popcll(fm & ((1ull << lane) - 1ull))] = my;
+                cnt += __popcll(fm);
+                wave_sync();
+            }
+            if (cnt == 0) continue;
+            hb_distances<IND, ROWS>(p, q, nb, cnt, nd, lane);
+            if (lane == 0) {
+                for (int i = 0; i < cnt; ++i) {
+                    const uint32_t e = (uint32_t) nb[i];
+                    const float ed = nd[i];
+                    const bool always = live_pushed < ef_;
+                    const float fd = mono_to_float((uint32_t) (Wq[0] >> 32));
+                    if (!(ed < fd || always)) continue;
+                    const uint64_t key = make_key(ed, e);
+                    hs_heap_push<false>(Cq, cn, key);
+                    hs_heap_push<true>(Wq, wn, key);
+                    if (v.live[e] != 0 && ++live_pushed > ef_) hs_heap_pop<true>(Wq, wn);
+                }
+            }
+            cn = (uint32_t) __shfl((int) cn, 0);
+            wn = (uint32_t) __shfl((int) wn, 0);
+            live_pushed = (uint32_t) __shfl((int) live_pushed, 0);
+        }
+        // W becomes the next layer's entry set: C = W, sorted nearest first
+        wave_sync_global();
+        for (uint32_t i = (uint32_t) lane; i < wn; i += 64) Cq[i] = Wq[i];
+        cn = wn;
+        wave_sync_global();
+        uint32_t n2 = 1, lg = 0;
+        while (n2 < cn) { n2 <<= 1; ++lg; }
+        for (uint32_t ls = 1; ls <= lg; ++ls) {                               // bitonic: positions >= cn act as +inf and are never touched
+            const uint32_t size = 1u << ls, half = size >> 1;
+            for (uint32_t tt = (uint32_t) lane; tt < n2 / 2; tt += 64) {
+                const uint32_t i = ((tt >> (ls - 1)) << ls) + (tt & (half - 1)), j = i ^ (size - 1);
+                if (j < cn) {
+                    const uint64_t a = Cq[i], b = Cq[j];
+                    if (a > b) { Cq[i] = b; Cq[j] = a; }
+                }
+            }
+            wave_sync_global();
+            for (uint32_t ld = ls - 1; ld >= 1; --ld) {
+                const uint32_t stride = 1u << (ld - 1);
+                for (uint32_t tt = (uint32_t) lane; tt < n2 / 2; tt += 64) {
+                    const uint32_t i = ((tt >> (ld - 1)) << ld) + (tt & (stride - 1)), j = i + stride;
+                    if (j < cn) {
+                        const uint64_t a = Cq[i], b = Cq[j];
+                        if (a > b) { Cq[i] = b; Cq[j] = a; }
+                    }
+                }
+                wave_sync_global();
+            }
+        }
+    };
+
+    // HnswFindElementNeighbors, existing = true
+    if (lane == 0) nb[0] = p.entry;
+    wave_sync();
+    hb_distances<IND, ROWS>(p, q, nb, 1, nd, lane);
+    if (lane == 0) Cq[0] = Wq[0] = make_key(nd[0], (uint32_t) p.entry);
+    cn = wn = 1;
+    wave_sync_global();
+    for (int lc = p.entry_level; lc >= my_level + 1; --lc) search_layer(lc, 1);
+    for (int lc = my_level < p.entry_level ? my_level : p.entry_level; lc >= 0; --lc) {
+        search_layer(lc, p.efc);
+        const int lm = (int) (lc == 0 ? 2 * p.m : p.m);
+        int nc = 0;                                                           // RemoveElements: without the deleted ones and `me`, order kept
+        for (uint32_t base = 0; base < cn; base += 64) {
+            const uint32_t i = base + (uint32_t) lane;
+            const uint64_t kk = i < cn ? Cq[i] : 0;
+            const bool keep = i < cn && (uint32_t) kk != me && v.live[(uint32_t) kk] != 0;
+            const uint64_t km = __ballot(keep);
+            if (keep) T[(uint32_t) nc + (uint32_t) __popcll(km & ((1ull << lane) - 1ull))] = kk;
+            nc += __popcll(km);
+        }
+        wave_sync_global();
+        int pruned;
+        const int ns = hb_select<IND, ROWS>(p, T, nc, lm, sel, wd, nb, nd, &pruned, lane);
+        const uint32_t at = lc == 0 ? 0u : (uint32_t) (lc + 1) * p.m;
+        uint32_t base = 0;
+        if (lane == 0 && ns > 0) base = atomicAdd(p.rec_count, (uint32_t) ns);
+        base = (uint32_t) __shfl((int) base, 0);
+        for (int j = lane; j < ns; j += 64) {
+            const uint64_t key = T[sel[j]];
+            st_n[at + j] = (int32_t) (uint32_t) key;
+            st_d[at + j] = mono_to_float((uint32_t) (key >> 32));
+            if (base + (uint32_t) j < p.rec_cap) {
+                p.rec_key[base + j] = ((uint64_t) (uint32_t) lc << (32 + HB_SRC_BITS)) | ((uint64_t) (uint32_t) key << HB_SRC_BITS) | bi;
+                p.rec_val[base + j] = ((uint64_t) me << 32) | __float_as_uint(mono_to_float((uint32_t) (key >> 32)));
+            }
+        }
+        if (lane == 0 && ns > 0 && base + (uint32_t) ns > p.rec_cap) atomicOr(p.err, HB_ERR_RECORDS);
+        wave_sync();
+    }
+}
+
+// one wave per workspace: wave w redoes spilled repairs w, w + spill_pool, .. of the batch (a static stride: which workspace a repair
+// gets depends on the order the LDS launch listed them in, its result does not)
+template <bool IND, int ROWS>
+__global__ __launch_bounds__(256) void hnsw_vacuum_search_spill_kernel(const HnswBuildParams p, const HnswVacuumParams v)
+{
+    __shared__ __align__(16) int32_t nb_all[4][HB_NBR];
+    __shared__ __align__(16) float nd_all[4][HB_NBR];
+    __shared__ __align__(16) int32_t sel_all[4][HB_NBR];
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const uint32_t w = blockIdx.x * 4 + wave;
+    if (w >= v.spill_pool) return;                                            // (waves are independent: no workgroup barrier)
+    uint32_t todo = p.count;
+    if (!v.spill_all) {
+        todo = *v.spill_count;
+        if (todo > p.count) todo = p.count;
+    }
+    if (w == 0 && lane == 0 && todo > 0) atomicAdd(v.spill_total, todo);
+    unsigned char* ws = v.spill_ws + (size_t) w * v.spill_ws_bytes;
+    for (uint32_t t = w; t < todo; t += v.spill_pool) {
+        const uint32_t bi = v.spill_all ? t : (uint32_t) v.spill_list[t];
+        hb_spill_repair<IND, ROWS>(p, v, bi, ws, nb_all[wave], nd_all[wave], sel_all[wave], lane);
+        wave_sync_global();
+    }
 }
 
 // ---- phase 2: reverse edges, sorted by (layer, target, source): the wave of a run's first record applies the whole
@@ -829,12 +1098,25 @@ static hipError_t vacuum_batch(HnswBuildParams& p, const HnswVacuumParams& v, vo
     e = hipMemsetAsync(p.rec_key, 0xFF, (size_t) p.rec_cap * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
     const size_t lds1 = (size_t) p.lds_per_wave * p.wpb;
+    // the mixed attempt's searches are an instantiation of their own, so that the one every other attempt runs compiles as it did
+    const void* search = v.spill_count ? reinterpret_cast<const void*>(hnsw_vacuum_search_kernel<IND, ROWS, true>)
+                                       : reinterpret_cast<const void*>(hnsw_vacuum_search_kernel<IND, ROWS, false>);
     if (lds1 > 64 * 1024) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_vacuum_search_kernel<IND, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds1);
+        e = hipFuncSetAttribute(search, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds1);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_vacuum_search_kernel<IND, ROWS>), dim3((p.count + p.wpb - 1) / p.wpb), dim3(64 * p.wpb), lds1, s, p, v);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (v.spill_count && (e = hipMemsetAsync(v.spill_count, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
+    if (!v.spill_all) {
+        const dim3 grid((p.count + p.wpb - 1) / p.wpb), block(64 * p.wpb);
+        if (v.spill_count) hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_vacuum_search_kernel<IND, ROWS, true>), grid, block, lds1, s, p, v);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_vacuum_search_kernel<IND, ROWS, false>), grid, block, lds1, s, p, v);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if (v.spill_pool > 0) {                                                   // the repairs the launch above listed, or all of them: before the install
+        const uint32_t waves = std::min(v.spill_pool, p.count);               // (wave w >= count has nothing to do)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_vacuum_search_spill_kernel<IND, ROWS>), dim3((waves + 3) / 4), dim3(256), 0, s, p, v);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
     hipLaunchKernelGGL(hnsw_vacuum_install_kernel, dim3((p.count + 3) / 4), dim3(256), 0, s, p, v);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (p.entry < 0) return hipSuccess;                                       // nobody else is left: the lists stay empty
@@ -853,6 +1135,12 @@ hipError_t vsr_hnsw_vacuum_batch(HnswBuildParams& p, const HnswVacuumParams& v, 
                                  uint64_t* d_val_alt, hipStream_t s)
 {
     if (p.sparse || 2 * p.m > (uint32_t) HB_NBR || p.count == 0 || p.count > HB_BATCH_MAX) return hipErrorInvalidValue;
+    // the spill form: a pool with workspaces for this graph; the mixed attempt's list goes with a pool, `all` needs one
+    if (v.spill_pool > 0 && (!v.spill_ws || !v.spill_total || v.spill_n == 0 || v.spill_ws_bytes < vsr::hnsw_vacuum_spill_ws_bytes(v.spill_n)))
+        return hipErrorInvalidValue;
+    if ((v.spill_all != 0 && v.spill_pool == 0) || ((v.spill_count != nullptr) != (v.spill_pool > 0 && v.spill_all == 0)) ||
+        (v.spill_count && !v.spill_list))
+        return hipErrorInvalidValue;
     if (p.bits)
         return p.elem_row ? vacuum_batch<true, ROWS_BIT>(p, v, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s)
                           : vacuum_batch<false, ROWS_BIT>(p, v, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);

@@ -26,6 +26,8 @@ struct vsr_hnsw {
     PinBuf h_out, h_bm;
     int last_mode = -1;                              // visited form of the last launch (HnswVisited)
     int predicate_aware = 0;                         // vsr_hnsw_set_predicate_aware
+    int32_t vacuum_spilled = 0;                      // vsr_hnsw_vacuum: repairs run in the global-memory form; 0 for any other index
+    int64_t vacuum_ws_bytes = 0;                     // and the bytes of the workspace pool they ran in
 };
 
 extern "C" int vsr_hnsw_free(vsr_hnsw* h)
@@ -751,10 +753,21 @@ static size_t hnsw_vacuum_lds_per_wave(uint32_t caps, uint32_t slots)
     return ((size_t) caps * 8 + ((caps + 15) & ~15u) + (size_t) HB_NBR * 12 + (size_t) slots * 4 + 15) & ~(size_t) 15;
 }
 
+// how an attempt treats a repair that outgrows the LDS arrays (hnsw_vacuum_search_spill_kernel, vsr_hnsw_build.hip)
+enum { HV_SPILL_NONE = 0,                    // the guard bits: the caller's ladders
+       HV_SPILL_MIXED = 1,                   // such a repair is listed and redone in the global-memory form
+       HV_SPILL_ALL = 2 };                   // every repair runs in that form (VSR_HNSW_VACUUM_SPILL=all)
+constexpr uint32_t HV_SPILL_WAVES = 1024;    // cap of the workspace pool: four waves a CU
+struct HnswVacuumSpill {
+    int      mode = HV_SPILL_NONE;
+    size_t   lds_budget = HN_LDS_BUDGET;     // VSR_HNSW_VACUUM_LDS
+    uint32_t waves = HV_SPILL_WAVES;         // VSR_HNSW_VACUUM_SPILL_WAVES
+};
+
 // One attempt with `slots` visited-table entries and `caps` candidate entries, from the caller's arrays.  *guard: as hnsw_build_once
 static int hnsw_vacuum_once(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, const HnswPrior& pr, const HnswVacuumPlan& pl,
-                            uint32_t slots, uint32_t caps, uint32_t batch_max, uint32_t* guard, vsr_hnsw_vacuum_stats* st, int32_t* out_elem_map,
-                            vsr_hnsw** out, const char* who)
+                            uint32_t slots, uint32_t caps, uint32_t batch_max, const HnswVacuumSpill& sp, uint32_t* guard,
+                            vsr_hnsw_vacuum_stats* st, int32_t* out_elem_map, vsr_hnsw** out, const char* who)
 {
     vsr_ctx* ctx = c->ctx;
     HIPCHK(hipSetDevice(ctx->device));
@@ -842,10 +855,10 @@ static int hnsw_vacuum_once(vsr_corpus* c, RowFormat expect, int m, int ef_const
     bp.caps = caps;
     bp.hash_slots = slots;
     const size_t per = hnsw_vacuum_lds_per_wave(caps, slots);
-    if (per > HN_LDS_BUDGET)
+    if (per > sp.lds_budget)
         return bail(fail(VSR_ERR_UNSUPPORTED, "%s: %u candidates with a visited table of %u entries do not fit the LDS", who, caps, slots));
     bp.lds_per_wave = (uint32_t) per;
-    bp.wpb = (uint32_t) std::min<size_t>(4, HN_LDS_BUDGET / per);
+    bp.wpb = (uint32_t) std::min<size_t>(4, sp.lds_budget / per);
     bp.err = ctx->err_word();
 
     HnswVacuumParams vp{};
@@ -870,6 +883,30 @@ static int hnsw_vacuum_once(vsr_corpus* c, RowFormat expect, int m, int ef_const
     vp.stage_nbr = w_stage_n;
     vp.stage_dist = w_stage_d;
     vp.stage_stride = stride;
+    // the spill form's pool: one workspace a wave, as many as the largest batch has repairs, a quarter of the free device memory
+    // holds and the cap allows -- at least one, whose hipMalloc is then what can fail
+    int64_t ws_total = 0;
+    if (sp.mode != HV_SPILL_NONE) {
+        const size_t ws_bytes = hnsw_vacuum_spill_ws_bytes((uint32_t) ne);
+        size_t free_b = 0, total_b = 0;
+        HV_CHK(hipMemGetInfo(&free_b, &total_b));
+        const uint64_t pool = std::max<uint64_t>(1, std::min<uint64_t>({most, (uint64_t) sp.waves, (uint64_t) (free_b / 4 / ws_bytes)}));
+        uint32_t* w_spill;
+        HV_ALLOC(w_spill, 16);                                                // [0]: the batch's spill count, [1]: the call's total
+        HV_CHK(hipMemsetAsync(w_spill, 0, 16, ctx->stream));
+        HV_ALLOC(vp.spill_ws, (size_t) pool * ws_bytes);
+        vp.spill_ws_bytes = ws_bytes;
+        vp.spill_pool = (uint32_t) pool;
+        vp.spill_n = (uint32_t) ne;
+        vp.spill_total = w_spill + 1;
+        if (sp.mode == HV_SPILL_ALL) {
+            vp.spill_all = 1;
+        } else {
+            vp.spill_count = w_spill;
+            HV_ALLOC(vp.spill_list, (size_t) most * 4);
+        }
+        ws_total = (int64_t) (pool * ws_bytes);
+    }
 
     HV_CHK(vsr_hnsw_edge_distances(bp, (uint32_t) ne, w_up_owner, (uint32_t) pr.n_upper, ctx->stream));
     int32_t nrep = 0, nbatch = 0;
@@ -981,6 +1018,12 @@ static int hnsw_vacuum_once(vsr_corpus* c, RowFormat expect, int m, int ef_const
         HV_CHK(hipMemcpy(bp.err, &word, sizeof word, hipMemcpyHostToDevice));
         return bail(VSR_OK);
     }
+    if (vp.spill_total) {
+        uint32_t spilled = 0;
+        HV_CHK(hipMemcpy(&spilled, vp.spill_total, sizeof spilled, hipMemcpyDeviceToHost));
+        h->vacuum_spilled = (int32_t) spilled;
+        h->vacuum_ws_bytes = ws_total;
+    }
     // the device's scan and the host's must agree: the lists were renumbered by the one, the other arrays by the other
     std::vector<int32_t> dmap(ne);
     HV_CHK(hipMemcpy(dmap.data(), w_map, ne * 4, hipMemcpyDeviceToHost));
@@ -1008,7 +1051,8 @@ static int hnsw_vacuum_once(vsr_corpus* c, RowFormat expect, int m, int ef_const
 }
 
 // VACUUM of an index after DELETE (include/vsrbac.h).  The ladders are the build's: a visited table twice as large, a candidate
-// array twice as long (or the longest that fits), every attempt from the caller's arrays.  Read at every call (development / tests):
+// array twice as long (or the longest that fits), every attempt from the caller's arrays; where a ladder ends, one more attempt
+// in mixed form, whose overflowing repairs are redone in global memory (HnswVacuumSpill).  Read at every call (development / tests):
 // VSR_HNSW_VACUUM_CAPS=n, the INITIAL candidate entries (ef_construction + 1 ..), VSR_HNSW_VACUUM_BATCH=n, the batch maximum
 // (1 .. 4096), and VSR_HNSW_BUILD_VISITED_SLOTS as for the build.
 extern "C" int vsr_hnsw_vacuum(vsr_corpus* c, int m, int32_t n_elem, int32_t entry, const int32_t* level, const int32_t* nbr0,
@@ -1099,11 +1143,31 @@ extern "C" int vsr_hnsw_vacuum(vsr_corpus* c, int m, int32_t n_elem, int32_t ent
         return VSR_OK;
     };
     // the longest candidate array that fits beside `s` visited slots (hnsw_vacuum_lds_per_wave: 9 bytes an entry), a multiple of 16
+    const uint32_t caps_min = (uint32_t) ef_construction + 1u;
+    // the spill knobs.  VSR_HNSW_VACUUM_SPILL: unset / 1: a repair that outgrows the largest arrays the LDS holds is redone in the
+    // global-memory form (one mixed attempt where the ladders end); 0: never, the refusals as they were; all: every repair in that
+    // form from the first attempt.  VSR_HNSW_VACUUM_LDS=bytes: the LDS the sizing and the ladders believe in;
+    // VSR_HNSW_VACUUM_SPILL_WAVES=n: the cap of the workspace pool
+    HnswVacuumSpill sp;
+    int spill = 1;
+    if (const char* env = getenv("VSR_HNSW_VACUUM_SPILL")) {
+        if (!strcmp(env, "0")) spill = 0;
+        else if (!strcmp(env, "1")) spill = 1;
+        else if (!strcmp(env, "all")) spill = 2;
+        else return fail(VSR_ERR_INVALID, "%s: VSR_HNSW_VACUUM_SPILL must be 0, 1 or all (got \"%s\")", who, env);
+    }
+    long lds = 0, waves = HV_SPILL_WAVES;
+    if ((rc = env_int("VSR_HNSW_VACUUM_LDS", (long) hnsw_vacuum_lds_per_wave(caps_min, 256), (long) HN_LDS_BUDGET, &lds))) return rc;
+    if ((rc = env_int("VSR_HNSW_VACUUM_SPILL_WAVES", 1, 1L << 20, &waves))) return rc;
+    if (lds > 0) sp.lds_budget = (size_t) lds;
+    sp.waves = (uint32_t) waves;
+    const size_t budget = sp.lds_budget;
+    // a budget that was given may be below the default table: the largest table beside which caps_min candidates still fit
+    while (lds > 0 && !slots_given && slots > 256u && hnsw_vacuum_lds_per_wave(caps_min, slots) > budget) slots /= 2u;
     auto caps_fit = [&](uint32_t s) -> uint32_t {
         const size_t fixed = (size_t) HB_NBR * 12 + (size_t) s * 4 + 64;
-        return HN_LDS_BUDGET > fixed ? (uint32_t) ((HN_LDS_BUDGET - fixed) / 9) & ~15u : 0u;
+        return budget > fixed ? (uint32_t) ((budget - fixed) / 9) & ~15u : 0u;
     };
-    const uint32_t caps_min = (uint32_t) ef_construction + 1u;
     long v = 0;
     if ((rc = env_int("VSR_HNSW_VACUUM_CAPS", (long) caps_min, 1L << 20, &v))) return rc;
     uint32_t caps;
@@ -1113,16 +1177,25 @@ extern "C" int vsr_hnsw_vacuum(vsr_corpus* c, int m, int32_t n_elem, int32_t ent
         const uint64_t base = (uint64_t) ef_construction + 1u + 2u * (uint64_t) m;
         const uint64_t want = std::min<uint64_t>((base * (uint64_t) n_elem + (uint64_t) pl.n_live - 1) / (uint64_t) pl.n_live, (uint64_t) n_elem);
         caps = (uint32_t) std::max<uint64_t>(base, std::min<uint64_t>((want + 15) & ~15ull, caps_fit(slots)));
+        if (lds > 0 && hnsw_vacuum_lds_per_wave(caps, slots) > budget) caps = std::max(caps_min, caps_fit(slots));   // (a given budget below `base`)
     }
     // every candidate was visited first, so a table that fills at 3/4 should hold what the candidate array is sized for
-    while (!slots_given && v == 0 && slots < 32768u && (uint64_t) slots * 3u < (uint64_t) caps * 4u && hnsw_vacuum_lds_per_wave(caps, slots * 2u) <= HN_LDS_BUDGET)
+    while (!slots_given && v == 0 && slots < 32768u && (uint64_t) slots * 3u < (uint64_t) caps * 4u && hnsw_vacuum_lds_per_wave(caps, slots * 2u) <= budget)
         slots *= 2u;
     long batch = HB_BATCH_MAX;
     if ((rc = env_int("VSR_HNSW_VACUUM_BATCH", 1, (long) HB_BATCH_MAX, &batch))) return rc;
+    // where a ladder ends with spilling on, ONE more attempt at the sizes it has, in mixed form: the repairs that fit stay on the
+    // LDS kernel, the others are redone in the global-memory form, which cannot overflow
+    sp.mode = spill == 2 ? HV_SPILL_ALL : HV_SPILL_NONE;
+    auto go_mixed = [&]() -> bool {
+        if (spill != 1 || sp.mode != HV_SPILL_NONE) return false;
+        sp.mode = HV_SPILL_MIXED;
+        return true;
+    };
     for (;;) {
         uint32_t guard = 0;
         ++st.attempts;
-        rc = hnsw_vacuum_once(c, expect, m, ef_construction, metric, pr, pl, slots, caps, (uint32_t) batch, &guard, &st, out_elem_map, out, who);
+        rc = hnsw_vacuum_once(c, expect, m, ef_construction, metric, pr, pl, slots, caps, (uint32_t) batch, sp, &guard, &st, out_elem_map, out, who);
         if (rc != VSR_OK || guard == 0) {
             if (rc == VSR_OK && out_stats) *out_stats = st;
             return rc;
@@ -1133,17 +1206,29 @@ extern "C" int vsr_hnsw_vacuum(vsr_corpus* c, int m, int32_t n_elem, int32_t ent
         const char* rebuild = "a graph this dead is to be rebuilt over its live rows (vsr_hnsw_build*)";
         if (guard & HB_ERR_CANDIDATES) {
             const uint32_t next = std::min(caps * 2u, caps_fit(slots));
-            if (next <= caps || hnsw_vacuum_lds_per_wave(next, slots) > HN_LDS_BUDGET)
+            if (next <= caps || hnsw_vacuum_lds_per_wave(next, slots) > budget) {
+                if (go_mixed()) continue;
                 return fail(VSR_ERR_UNSUPPORTED, "%s: a layer search of the repair holds more than %u candidates (%d of %d elements live) and no longer "
                             "candidate array fits the LDS: %s", who, caps, pl.n_live, n_elem, rebuild);
+            }
             caps = next;
             if (!(guard & HB_ERR_VISITED)) continue;
         }
-        if (slots >= 32768u || hnsw_vacuum_lds_per_wave(caps, slots * 2u) > HN_LDS_BUDGET)
+        if (slots >= 32768u || hnsw_vacuum_lds_per_wave(caps, slots * 2u) > budget) {
+            if (go_mixed()) continue;
             return fail(VSR_ERR_UNSUPPORTED, "%s: a layer search of the repair fills its visited table of %u entries (%d of %d elements live) and no "
                         "larger one fits the LDS: %s", who, slots, pl.n_live, n_elem, rebuild);
+        }
         slots *= 2u;
     }
+}
+
+extern "C" int vsr_hnsw_vacuum_spill_info(const vsr_hnsw* h, int32_t* spilled_repairs, int64_t* workspace_bytes)
+{
+    if (!h) return fail(VSR_ERR_INVALID, "vsr_hnsw_vacuum_spill_info: index is NULL");
+    if (spilled_repairs) *spilled_repairs = h->vacuum_spilled;
+    if (workspace_bytes) *workspace_bytes = h->vacuum_ws_bytes;
+    return VSR_OK;
 }
 
 // device memory of the graph arrays of an index (the corpus is counted by vsr_corpus_device_bytes); any index.  The row format

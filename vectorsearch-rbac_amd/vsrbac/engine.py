@@ -1142,6 +1142,14 @@ class HnswIndex:
         the old pair.  UPDATE is vacuum followed by extend_hnsw."""
         return self.corpus.vacuum_hnsw(self.export(), dead_rows, ef_construction, metric)
 
+    def vacuum_spill_info(self):
+        """(spilled_repairs, workspace_bytes) of the vacuum that made this index (vsr_hnsw_vacuum_spill_info): the repairs whose
+        working set outgrew the LDS and ran in the global-memory form, and the bytes of the workspace pool they shared.
+        (0, 0) for an index any other call made."""
+        n, b = C.c_int32(), C.c_int64()
+        check(self._lib.vsr_hnsw_vacuum_spill_info(self._h, C.byref(n), C.byref(b)))
+        return int(n.value), int(b.value)
+
     def search_device(self, d_queries, nq, k, ef_search, metric, filters, d_block, d_doc, d_rows, d_dist, d_counts,
                       d_visited=None):
         """Device pointers (ints); ONE launch on the corpus context's stream, no synchronisation (vsr_hnsw_search_device)."""
