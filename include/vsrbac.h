@@ -673,6 +673,36 @@ int vsr_hnsw_vacuum(vsr_corpus* corpus, int m, int32_t n_elem, int32_t entry, co
                     const int64_t* dead_rows, int64_t n_dead, uint32_t flags,
                     int32_t* out_elem_map /* [n_elem] new id or -1, may be NULL */, vsr_hnsw_vacuum_stats* out_stats /* may be NULL */,
                     vsr_hnsw** out);
+/* The HNSW graphs of many row subsets of one corpus -- one index per role table or per dynamic partition -- built in ONE call, the
+ * vectors resident once.  The row format (fp32, halfvec or bit) comes from the corpus, as for vsr_hnsw_extend.
+ *   - Partition g is the caller rows part_rows[part_off[g] .. part_off[g + 1]); part_off[n_parts + 1] ascends from part_off[0] = 0.
+ *     Partitions may overlap each other (a document can belong to several roles), come in any order and be empty.  Within ONE
+ *     partition a row named twice, or a row outside [0, rows), is VSR_ERR_INVALID, the message naming the partition and the position.
+ *   - out[g] is an ordinary index over `corpus` (search, iterative search, predicate-aware walk, export, info, device_bytes) that
+ *     owns its arrays.  Its export equals, array for array, the export of vsr_hnsw_build / _half / _bit(m, ef_construction, metric,
+ *     seed) over a corpus holding only partition g's rows with their (document_id, block_id), the heap TIDs mapped through
+ *     part_rows: element e is the e-th row of the partition in internal (document_id, block_id) order; the level stream starts afresh
+ *     from `seed` for every partition; every partition follows the build's schedule from done = 0 and the build's entry-point rule;
+ *     every graph has its own max_level and its own upper-slot numbering.  An empty partition gives the index vsr_hnsw_load makes of
+ *     n_elem = 0.  n_parts = 0 succeeds and writes nothing.
+ *   - How: all partitions are built in one global element space by the build's kernels; a round serves the next batch of every
+ *     partition that has one due while the round's elements stay within 4096 (one search launch, one sort and one link launch per
+ *     round, where building the graphs one after the other takes those per batch and partition), and one last launch writes every
+ *     graph's own arrays.  The packing into rounds does not change any graph.  VSR_HNSW_FOREST_BATCH=<1..4096> (read at every call;
+ *     anything else: VSR_ERR_INVALID) lowers the cap, so that waiting can be exercised on small inputs; a batch larger than the cap
+ *     takes a round of its own.  A visited-table overflow in any graph restarts the whole call with twice the slots
+ *     (VSR_HNSW_BUILD_VISITED_SLOTS applies); dropped records are the build's refusal.
+ *   - metric, m, ef_construction, halfvec dimension, a view corpus: the rules and refusals of the matching build call.  A sparse
+ *     corpus: VSR_ERR_UNSUPPORTED, the message names sparsevec (the sparse build has no element -> row form).  flags must be 0:
+ *     VSR_HNSW_BUILD_MERGE_DUPLICATES is VSR_ERR_UNSUPPORTED, any other bit VSR_ERR_INVALID.
+ *   - On failure every index made so far is freed and every out[g] is NULL.  The session's guard word is left as it was found.
+ * Not covered: extending or vacuuming a partition graph in place (export it and use vsr_hnsw_extend / vsr_hnsw_vacuum), and searching
+ * several graphs in one launch.  Synchronises. */
+int vsr_hnsw_build_partitions(vsr_corpus* corpus, int n_parts,
+                              const int64_t* part_off  /* [n_parts + 1], ascending, part_off[0] = 0 */,
+                              const int64_t* part_rows /* [part_off[n_parts]] caller row indices */,
+                              int m, int ef_construction, int metric, uint64_t seed, uint32_t flags,
+                              vsr_hnsw** out /* [n_parts] */);
 /* What the vacuum that made this index spilled: repairs run in the global-memory form, and the bytes of the workspace pool.
  * 0 / 0 for an index any other call made. */
 int vsr_hnsw_vacuum_spill_info(const vsr_hnsw* index, int32_t* spilled_repairs, int64_t* workspace_bytes);

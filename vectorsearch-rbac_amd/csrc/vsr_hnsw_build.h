@@ -69,6 +69,23 @@ struct HnswVacuumParams {
     uint32_t*      spill_total = nullptr;    // += the repairs the spill launches ran
 };
 
+// vsr_hnsw_build_partitions: what the forest form of the search kernel takes beside HnswBuildParams (a second kernel argument, so
+// that the build's own launches keep theirs).  A round (vsr_hnsw_forest.h) is elems[0 .. p.count); the element of batch slot i
+// searches from entry[i], not from p.entry.  Elements are GLOBAL ids: every build array holds all partitions' graphs
+struct HnswForestParams {
+    const int32_t* elems = nullptr;          // [p.count] the round's elements, ascending
+    const int32_t* entry = nullptr;          // [p.count] the entry point of the element's graph when the round began; -1: none yet
+    const int32_t* entry_level = nullptr;    // [p.count] its level
+};
+
+// one graph of the forest, as the split launch writes it out: the arrays of a vsr_hnsw of its own
+struct HnswForestGraph {
+    int32_t *level = nullptr, *elem_row = nullptr, *nbr0 = nullptr, *up_slot = nullptr, *up_nbr = nullptr, *tid_count = nullptr, *tids = nullptr;
+    int32_t base = 0, n_elem = 0;            // global elements base .. base + n_elem - 1 (n_elem >= 1)
+    int32_t slot_base = 0;                   // its first upper slot in the global numbering (slots follow element order)
+    int32_t max_level = 1;                   // its own stride of the upper lists
+};
+
 // one workspace of the spill form for a graph of n elements: C, W and T (8 bytes an element each), wd (4) and the visited bitmap
 inline size_t hnsw_vacuum_spill_ws_bytes(uint32_t n)
 {
@@ -98,6 +115,14 @@ hipError_t vsr_hnsw_dedup_elements(const float4* rows, uint32_t n, uint32_t stri
 hipError_t vsr_hnsw_build_batch(vsr::HnswBuildParams& p, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt, uint64_t* d_val_alt,
                                 hipStream_t s);
 size_t vsr_hnsw_build_sort_bytes(uint32_t rec_cap);
+// vsr_hnsw_build_partitions.  One round (p.count <= HB_BATCH_MAX elements, f.elems): the forest searches, the sort and the link
+// launch, all on s.  p.elem_row is set (IND = true); p.first, p.entry and p.entry_level are not read.
+hipError_t vsr_hnsw_forest_round(vsr::HnswBuildParams& p, const vsr::HnswForestParams& f, void* d_sort_tmp, size_t sort_tmp_bytes,
+                                 uint64_t* d_key_alt, uint64_t* d_val_alt, hipStream_t s);
+// every graph's own arrays from the global ones (one launch on s): ids minus base, upper slots minus slot_base, upper lists at
+// the graph's max_level, one heap TID per element.  d_graphs[n_graphs]: the non-empty graphs, ascending base, covering 0 .. n_total - 1
+hipError_t vsr_hnsw_forest_split(const vsr::HnswBuildParams& p, const vsr::HnswForestGraph* d_graphs, uint32_t n_graphs, uint32_t n_total,
+                                 hipStream_t s);
 // vsr_hnsw_vacuum.  One repair batch (p.count <= HB_BATCH_MAX elements, v.elems): the searches into v.stage_*, the install launch,
 // the sort and the link launch, all on s.  The selection's scratch lies over the visited table (hash_slots / 3 candidates).
 // With v.spill_pool > 0 the spill launch runs between the searches and the install: over the repairs the LDS launch listed

@@ -57,6 +57,12 @@
 // before the first batch; elements reach their rows through elem_row whenever element != internal row (a merged prior graph, new
 // rows that sort between old ones).  fp32, halfvec and bit rows; tests/test_gpu_hnsw_extend.py.
 //
+// Partitions (vsr_hnsw_build_partitions): the graphs of many row subsets of one corpus, built in one global element space over one
+// set of build arrays.  A round (vsr_hnsw_forest.h) holds the next batch of every partition that has one due; its searches are
+// hnsw_forest_search_kernel -- the search body with the batch as a list and the entry point per batch slot -- and its sort and link
+// launch are the build's, which act on each graph as its own would because targets of different graphs are disjoint.
+// hnsw_forest_split_kernel then writes every graph's own arrays.  fp32, halfvec and bit rows; tests/test_gpu_hnsw_partitions.py.
+//
 // Parity definition (tests/test_gpu_index.py): recall@20 at ef_search = 40 against the exact scan >= pgvector's TAP
 // thresholds on its own case (10 000 x 3-d: 0.99; inner product 0.97), and within 0.01 of that serial build's recall on
 // the same rows; and (tests/test_gpu_hnsw_build_model.py) graph identity with the batched model, as above.
@@ -244,17 +250,28 @@ __device__ __forceinline__ int hb_select(const HnswBuildParams& p, const uint64_
 // other waves of the batch are reading.  S can outgrow any bound here (a graph with few live elements admits everything), so the
 // loss check of the sparse build is on, and so is one for a W longer than S.
 // MIXED (VAC only): the mixed attempt's form, see the end of the body
-template <bool IND, int ROWS, bool VAC, bool MIXED = false>
-__device__ __forceinline__ void hb_search_body(const HnswBuildParams& p, const HnswVacuumParams& v)
+// FOREST (vsr_hnsw_build_partitions; not with VAC): a round of many graphs that share the build arrays.  The batch is f.elems[],
+// and the entry point and its level are those of the element's own graph, f.entry[bi] / f.entry_level[bi], where the build reads
+// p.entry / p.entry_level.  A wave whose graph has no entry yet emits nothing, as the build's first element.  Nothing else differs:
+// the LDS carve-up is the build's
+template <bool IND, int ROWS, bool VAC, bool MIXED = false, bool FOREST = false>
+__device__ __forceinline__ void hb_search_body(const HnswBuildParams& p, const HnswVacuumParams& v, const HnswForestParams& f = HnswForestParams{})
 {
+    static_assert(!(VAC && FOREST), "the forest form is a build");
     extern __shared__ __align__(16) unsigned char smem_all[];
     const int lane = threadIdx.x & 63;
     const uint32_t wave = (uint32_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
     const uint32_t bi = blockIdx.x * p.wpb + wave;
     if (wave >= p.wpb || bi >= p.count) return;                               // (waves are independent: no workgroup barrier)
     uint32_t me_;
-    if constexpr (VAC) me_ = (uint32_t) v.elems[bi]; else me_ = p.first + bi;
+    if constexpr (VAC) me_ = (uint32_t) v.elems[bi]; else if constexpr (FOREST) me_ = (uint32_t) f.elems[bi]; else me_ = p.first + bi;
     const uint32_t me = me_;
+    int32_t entry_ = p.entry, entry_level_ = p.entry_level;
+    if constexpr (FOREST) {
+        entry_ = f.entry[bi];
+        entry_level_ = f.entry_level[bi];
+    }
+    const int32_t entry = entry_, entry_level = entry_level_;                 // the entry point this search starts from, and its level
     unsigned char* smem = smem_all + (size_t) wave * p.lds_per_wave;
     uint64_t* S = reinterpret_cast<uint64_t*>(smem);                          // [caps] candidates, sorted, nearest first
     uint8_t*  X = reinterpret_cast<uint8_t*>(S + p.caps);                     // [caps] expanded flags
@@ -306,7 +323,7 @@ __device__ __forceinline__ void hb_search_body(const HnswBuildParams& p, const H
         const uint32_t lm = lc == 0 ? 2 * p.m : p.m;
         for (uint32_t j = (uint32_t) lane; j < lm; j += 64) { nl[j] = -1; dl[j] = 0.0f; }
     }
-    if (p.entry < 0) return;                                                  // the very first element (VAC: nobody else is left)
+    if (entry < 0) return;                                                    // the very first element (VAC: nobody else is left)
 
     constexpr bool defer = VAC && MIXED;                                      // mixed attempt: records wait until every layer is done
     bool overflow = false;
@@ -442,17 +459,17 @@ __device__ __forceinline__ void hb_search_body(const HnswBuildParams& p, const H
     };
 
     // HnswFindElementNeighbors (hnswutils.c:1270-1346)
-    if (lane == 0) nb[0] = p.entry;
+    if (lane == 0) nb[0] = entry;
     wave_sync();
     hb_distances<IND, ROWS>(p, q, nb, 1, nd, lane, &left);
-    insert(make_key(nd[0], (uint32_t) p.entry));
-    for (int lc = p.entry_level; lc >= my_level + 1; --lc) {
+    insert(make_key(nd[0], (uint32_t) entry));
+    for (int lc = entry_level; lc >= my_level + 1; --lc) {
         search_layer(lc, 1);
         if (lane == 0)
             for (uint32_t i = 0; i < count; ++i) X[i] = 0;
         wave_sync();
     }
-    for (int lc = my_level < p.entry_level ? my_level : p.entry_level; lc >= 0; --lc) {
+    for (int lc = my_level < entry_level ? my_level : entry_level; lc >= 0; --lc) {
         search_layer(lc, p.efc);
         const int lm = (int) (lc == 0 ? 2 * p.m : p.m);
         int pruned;
@@ -538,6 +555,13 @@ template <bool IND, int ROWS>
 __global__ __launch_bounds__(256) void hnsw_build_search_kernel(const HnswBuildParams p)
 {
     hb_search_body<IND, ROWS, false>(p, HnswVacuumParams{});
+}
+
+// the forest form (vsr_hnsw_build_partitions): an instantiation of its own, so that the build's compiles as it did
+template <int ROWS>
+__global__ __launch_bounds__(256) void hnsw_forest_search_kernel(const HnswBuildParams p, const HnswForestParams f)
+{
+    hb_search_body<true, ROWS, false, false, true>(p, HnswVacuumParams{}, f);
 }
 
 template <bool IND, int ROWS, bool MIXED>
@@ -1009,6 +1033,45 @@ __global__ __launch_bounds__(256) void hnsw_edge_dist_kernel(const HnswBuildPara
     for (int j = lane; j < cnt; j += 64) dl[j] = mono_to_float(mono_bits(nd[j]));   // as a key carries it (-0 -> +0)
 }
 
+// ---- partitions (vsr_hnsw_build_partitions): every graph's own arrays out of the global ones.  One wave per global element e; its
+// graph is the last one whose base is <= e (graphs[] holds the non-empty graphs in ascending base).  Ids lose the graph's base,
+// upper slots its slot_base (slots were numbered in global element order, so a graph's are a run), the upper lists go from the
+// global stride p.max_level to the graph's own max_level (layers above an element's level hold -1 in both), and the element's
+// one heap TID is its row.  Waves are independent: no workgroup barrier ----
+__global__ __launch_bounds__(256) void hnsw_forest_split_kernel(const HnswBuildParams p, const HnswForestGraph* __restrict__ graphs,
+                                                                const uint32_t n_graphs, const uint32_t n_total)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t e = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (e >= n_total) return;
+    uint32_t lo = 0, hi = n_graphs;                                           // graphs[lo].base <= e < graphs[hi].base
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if ((uint32_t) graphs[mid].base <= e) lo = mid; else hi = mid;
+    }
+    const HnswForestGraph g = graphs[lo];
+    const uint32_t le = e - (uint32_t) g.base;
+    if (le >= (uint32_t) g.n_elem) return;                                    // (cannot happen: the graphs cover 0 .. n_total - 1)
+    const int32_t row = p.elem_row[e], slot = p.up_slot[e];
+    if (lane == 0) {
+        g.level[le] = p.level[e];
+        g.elem_row[le] = row;
+        g.up_slot[le] = slot >= 0 ? slot - g.slot_base : -1;
+        g.tid_count[le] = 1;
+    }
+    if (lane < HB_TIDS) g.tids[(size_t) le * HB_TIDS + lane] = lane == 0 ? row : -1;
+    for (uint32_t j = (uint32_t) lane; j < 2 * p.m; j += 64) {
+        const int32_t id = p.nbr0[(size_t) e * 2 * p.m + j];
+        g.nbr0[(size_t) le * 2 * p.m + j] = id >= 0 ? id - g.base : -1;
+    }
+    if (slot < 0) return;
+    const size_t from = (size_t) slot * p.max_level * p.m, to = (size_t) (slot - g.slot_base) * (uint32_t) g.max_level * p.m;
+    for (uint32_t j = (uint32_t) lane; j < (uint32_t) g.max_level * p.m; j += 64) {   // (g.max_level <= p.max_level)
+        const int32_t id = p.up_nbr[from + j];
+        g.up_nbr[to + j] = id >= 0 ? id - g.base : -1;
+    }
+}
+
 }  // namespace vsr
 
 using namespace vsr;
@@ -1086,6 +1149,53 @@ hipError_t vsr_hnsw_build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sor
                           : build_batch<false, ROWS_HALF>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
     return p.elem_row ? build_batch<true, ROWS_F32>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s)
                       : build_batch<false, ROWS_F32>(p, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
+}
+
+// one round of vsr_hnsw_build_partitions: build_batch with the forest searches.  No round is skipped for want of an entry point:
+// the graphs of a round are at different stages, and a wave without one emits no record
+template <int ROWS>
+static hipError_t forest_round(HnswBuildParams& p, const HnswForestParams& f, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt,
+                               uint64_t* d_val_alt, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(p.rec_count, 0, sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(p.rec_key, 0xFF, (size_t) p.rec_cap * sizeof(uint64_t), s);
+    if (e != hipSuccess) return e;
+    const size_t lds1 = (size_t) p.lds_per_wave * p.wpb;
+    if (lds1 > 64 * 1024) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_forest_search_kernel<ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds1);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_forest_search_kernel<ROWS>), dim3((p.count + p.wpb - 1) / p.wpb), dim3(64 * p.wpb), lds1, s, p, f);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipcub::DoubleBuffer<uint64_t> keys(p.rec_key, d_key_alt), vals(p.rec_val, d_val_alt);
+    e = hipcub::DeviceRadixSort::SortPairs(d_sort_tmp, sort_tmp_bytes, keys, vals, (int) p.rec_cap, 0, HB_KEY_BITS, s);
+    if (e != hipSuccess) return e;
+    HnswBuildParams q = p;
+    q.rec_key = keys.Current();
+    q.rec_val = vals.Current();
+    const size_t lds2 = (size_t) 4 * HB_NBR * 32;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_build_link_kernel<true, ROWS>), dim3((p.rec_cap + 3) / 4), dim3(256), lds2, s, q);
+    return hipGetLastError();
+}
+
+hipError_t vsr_hnsw_forest_round(HnswBuildParams& p, const HnswForestParams& f, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt,
+                                 uint64_t* d_val_alt, hipStream_t s)
+{
+    if (p.sparse || !p.elem_row || !f.elems || !f.entry || !f.entry_level || 2 * p.m > (uint32_t) HB_NBR || p.count == 0 ||
+        p.count > HB_BATCH_MAX || p.rec_cap == 0)
+        return hipErrorInvalidValue;
+    if (p.bits) return forest_round<ROWS_BIT>(p, f, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
+    if (p.halves) return forest_round<ROWS_HALF>(p, f, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
+    return forest_round<ROWS_F32>(p, f, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
+}
+
+hipError_t vsr_hnsw_forest_split(const HnswBuildParams& p, const HnswForestGraph* d_graphs, uint32_t n_graphs, uint32_t n_total, hipStream_t s)
+{
+    if (n_total == 0) return hipSuccess;
+    if (!d_graphs || n_graphs == 0 || !p.elem_row) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(hnsw_forest_split_kernel, dim3((n_total + 3) / 4), dim3(256), 0, s, p, d_graphs, n_graphs, n_total);
+    return hipGetLastError();
 }
 
 // one repair batch of vsr_hnsw_vacuum: searches into the staging buffer, install, sort of the reverse edges, their application

@@ -4,6 +4,7 @@
 #include "vsr_runtime.h"
 #include "vsr_hnsw.h"
 #include "vsr_hnsw_build.h"
+#include "vsr_hnsw_forest.h"
 #include "vsr_shortlist.h"
 
 #include <climits>
@@ -229,6 +230,32 @@ struct HnswPrior {
     bool identity = true;                    // element e is internal row e throughout: the direct kernels serve
 };
 
+// The build's levels: level = floor(-ln(u) * ml), ml = 1 / ln(m) (hnswutils.c:243), capped like HnswGetMaxLevel (hnsw.h:89), u from a
+// seeded xorshift64* stream (the serial CPU restatement draws the same stream).  One draw per inserted row
+struct HnswLevelStream {
+    uint64_t rs;
+    double ml;
+    int cap;
+    HnswLevelStream(uint64_t seed, int m) : rs(seed * 0x9E3779B97F4A7C15ULL + 0x1234567ULL), ml(1.0 / std::log((double) m))
+    {
+        cap = std::min((8192 - 24 - 8 - 4 - 4) / 6 / m - 2, 255);
+        if (!rs) rs = 1;
+        (void) next();
+    }
+    uint64_t next()
+    {
+        uint64_t x = rs;
+        x ^= x >> 12; x ^= x << 25; x ^= x >> 27;
+        rs = x;
+        return x * 0x2545F4914F6CDD1DULL;
+    }
+    int32_t level()
+    {
+        const double u = (double) (next() >> 11) * (1.0 / 9007199254740992.0);
+        return std::min((int) (-std::log(u) * ml), cap);
+    }
+};
+
 // what every build entry point asks of its corpus and arguments, in the order and words the build has always used
 static int hnsw_build_check(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, uint32_t flags, vsr_hnsw** out, const char* who)
 {
@@ -287,28 +314,13 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
     h->format = expect;
     h->bit_metric = expect == RowFormat::BIT ? metric : 0;
     h->m = m;
-    // levels: level = floor(-ln(u) * ml), ml = 1 / ln(m) (hnswutils.c:243), capped like HnswGetMaxLevel (hnsw.h:89)
-    int cap = (8192 - 24 - 8 - 4 - 4) / 6 / m - 2;
-    cap = std::min(cap, 255);
-    uint64_t rs = seed * 0x9E3779B97F4A7C15ULL + 0x1234567ULL;               // xorshift64* (the serial CPU restatement draws the same stream)
-    if (!rs) rs = 1;
-    auto next = [&]() {
-        uint64_t x = rs;
-        x ^= x >> 12; x ^= x << 25; x ^= x >> 27;
-        rs = x;
-        return x * 0x2545F4914F6CDD1DULL;
-    };
-    (void) next();
-    const double ml = 1.0 / std::log((double) m);
+    HnswLevelStream draws(seed, m);
     // per element: the prior graph's levels, then one draw per inserted row (merging: per row, then per element).  The i-th
     // inserted row takes draw n0 + i, so a prefix build extended with the build's seed draws what the one-shot build draws
     std::vector<int32_t> level((size_t) std::max<int64_t>(n_prior + n_new, 1), 0);
     if (n_prior > 0) std::copy(prior->level, prior->level + n_prior, level.begin());
-    for (int64_t r = 0; r < (prior ? prior->n0 : 0); ++r) (void) next();
-    for (int64_t r = 0; r < n_new; ++r) {
-        const double u = (double) (next() >> 11) * (1.0 / 9007199254740992.0);
-        level[(size_t) (n_prior + r)] = std::min((int) (-std::log(u) * ml), cap);
-    }
+    for (int64_t r = 0; r < (prior ? prior->n0 : 0); ++r) (void) draws.next();
+    for (int64_t r = 0; r < n_new; ++r) level[(size_t) (n_prior + r)] = draws.level();
     float *d_dist0 = nullptr, *d_up_dist = nullptr;
     uint64_t *d_key[2] = {nullptr, nullptr}, *d_val[2] = {nullptr, nullptr};
     uint32_t* d_cnt = nullptr;
@@ -630,6 +642,304 @@ extern "C" int vsr_hnsw_build_half(vsr_corpus* c, int m, int ef_construction, in
 extern "C" int vsr_hnsw_build_sparse(vsr_corpus* c, int m, int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out)
 {
     return hnsw_build(c, RowFormat::SPARSE, m, ef_construction, metric, seed, flags, out, "vsr_hnsw_build_sparse");
+}
+
+// ---- vsr_hnsw_build_partitions: the graphs of many row subsets in one global element space (vsr_hnsw_forest.h has the schedule,
+// vsr_hnsw_build.hip the forest form of the search kernel and the split launch)
+static_assert(HF_BATCH_MAX == HB_BATCH_MAX, "the forest's schedule is the build's");
+
+// what the host pass leaves for every attempt: the partitions as runs of one element space
+struct HnswForest {
+    int n_parts = 0;
+    std::vector<int64_t> base;               // [n_parts + 1] partition g owns elements base[g] .. base[g + 1] - 1
+    std::vector<int32_t> elem_row;           // [total] element -> internal row: a partition's rows in ascending internal order
+    std::vector<int32_t> level;              // [total] the build's level stream, started afresh for every partition
+    std::vector<int32_t> up_slot;            // [total] upper slots in global element order, -1 for level 0
+    std::vector<int32_t> slot_base, n_upper, max_level;   // [n_parts] a graph's first slot, its slots, its own max_level (>= 1)
+    int32_t g_upper = 0, g_max_level = 1;    // all slots / the stride of the global upper arrays
+    HnswForestPlan plan;
+};
+
+// One attempt with `slots` visited-table entries; *guard: as hnsw_build_once.  On success out[g] holds every index, registered
+static int hnsw_forest_once(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, const HnswForest& fo, uint32_t* slots_io,
+                            uint32_t* guard, vsr_hnsw** out, const char* who)
+{
+    vsr_ctx* ctx = c->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t total = (size_t) fo.base[(size_t) fo.n_parts];
+    const uint32_t row_chunks = format_row_chunks(expect, c->dim);
+    std::vector<std::unique_ptr<vsr_hnsw>> made((size_t) fo.n_parts);
+    std::vector<void*> scratch;                                               // every device allocation of the attempt but the indexes'
+    auto cleanup = [&]() {
+        for (void* q : scratch)
+            if (q) (void) hipFree(q);
+        scratch.clear();
+    };
+    auto bail = [&](int rc) {
+        (void) hipStreamSynchronize(ctx->stream);
+        cleanup();
+        for (auto& h : made)
+            if (h) vsr_hnsw_free(h.release());                                // (not registered yet: corpus stays nullptr until the end)
+        return rc;
+    };
+#define HF_CHK(call)                                                                                         \
+    do {                                                                                                     \
+        hipError_t e_ = (call);                                                                              \
+        if (e_ != hipSuccess) return bail(fail(VSR_ERR_HIP, "%s: %s", who, hipGetErrorString(e_)));          \
+    } while (0)
+    auto dev = [&](void** p, size_t bytes) -> hipError_t {
+        const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 4));
+        if (e == hipSuccess) scratch.push_back(*p);
+        return e;
+    };
+    // every index and its arrays first: an allocation that fails costs no GPU work.  An empty partition: what hnsw_load makes of n_elem = 0
+    std::vector<HnswForestGraph> graphs;
+    for (int g = 0; g < fo.n_parts; ++g) {
+        std::unique_ptr<vsr_hnsw> h(new vsr_hnsw());
+        const size_t ne = (size_t) (fo.base[(size_t) g + 1] - fo.base[(size_t) g]);
+        h->format = expect;
+        h->bit_metric = expect == RowFormat::BIT ? metric : 0;
+        h->m = m;
+        h->n_elem = (int32_t) ne;
+        h->max_level = fo.max_level[(size_t) g];
+        h->n_upper = fo.n_upper[(size_t) g];
+        const int32_t e = fo.plan.final_entry[(size_t) g];
+        h->entry = e >= 0 ? (int32_t) (e - fo.base[(size_t) g]) : -1;
+        h->entry_level = e >= 0 ? fo.level[(size_t) e] : -1;
+        made[(size_t) g] = std::move(h);
+        vsr_hnsw* hh = made[(size_t) g].get();
+        const size_t counts[7] = {ne, ne, ne * 2 * m, ne, (size_t) hh->n_upper * hh->max_level * m, ne, ne * 10};
+        int32_t** ptrs[7] = {&hh->d_elem_row, &hh->d_level, &hh->d_nbr0, &hh->d_up_slot, &hh->d_up_nbr, &hh->d_tid_count, &hh->d_tids};
+        for (int i = 0; i < 7; ++i) HF_CHK(hipMalloc(ptrs[i], std::max<size_t>(4, counts[i] * sizeof(int32_t))));
+        if (ne == 0) continue;
+        HnswForestGraph fg{};
+        fg.level = hh->d_level;
+        fg.elem_row = hh->d_elem_row;
+        fg.nbr0 = hh->d_nbr0;
+        fg.up_slot = hh->d_up_slot;
+        fg.up_nbr = hh->d_up_nbr;
+        fg.tid_count = hh->d_tid_count;
+        fg.tids = hh->d_tids;
+        fg.base = (int32_t) fo.base[(size_t) g];
+        fg.n_elem = (int32_t) ne;
+        fg.slot_base = fo.slot_base[(size_t) g];
+        fg.max_level = hh->max_level;
+        graphs.push_back(fg);
+    }
+    if (total > 0) {
+        int32_t *d_level = nullptr, *d_elem_row = nullptr, *d_up_slot = nullptr, *d_nbr0 = nullptr, *d_up_nbr = nullptr, *d_plan = nullptr;
+        float *d_dist0 = nullptr, *d_up_dist = nullptr;
+        uint64_t *d_key[2] = {nullptr, nullptr}, *d_val[2] = {nullptr, nullptr};
+        uint32_t* d_cnt = nullptr;
+        void* d_tmp = nullptr;
+        HnswForestGraph* d_graphs = nullptr;
+        const size_t up_words = (size_t) std::max(fo.g_upper, 1) * fo.g_max_level * m;
+        HF_CHK(dev((void**) &d_level, total * 4));
+        HF_CHK(dev((void**) &d_elem_row, total * 4));
+        HF_CHK(dev((void**) &d_up_slot, total * 4));
+        HF_CHK(dev((void**) &d_nbr0, total * 2 * m * 4));
+        HF_CHK(dev((void**) &d_dist0, total * 2 * m * 4));
+        HF_CHK(dev((void**) &d_up_nbr, up_words * 4));
+        HF_CHK(dev((void**) &d_up_dist, up_words * 4));
+        HF_CHK(dev((void**) &d_plan, total * 3 * 4));                         // the rounds' elements | entry points | their levels
+        HF_CHK(dev((void**) &d_graphs, graphs.size() * sizeof(HnswForestGraph)));
+        HF_CHK(hipMemcpy(d_level, fo.level.data(), total * 4, hipMemcpyHostToDevice));
+        HF_CHK(hipMemcpy(d_elem_row, fo.elem_row.data(), total * 4, hipMemcpyHostToDevice));
+        HF_CHK(hipMemcpy(d_up_slot, fo.up_slot.data(), total * 4, hipMemcpyHostToDevice));
+        HF_CHK(hipMemcpy(d_plan, fo.plan.elems.data(), total * 4, hipMemcpyHostToDevice));
+        HF_CHK(hipMemcpy(d_plan + total, fo.plan.entry.data(), total * 4, hipMemcpyHostToDevice));
+        HF_CHK(hipMemcpy(d_plan + 2 * total, fo.plan.entry_level.data(), total * 4, hipMemcpyHostToDevice));
+        HF_CHK(hipMemcpy(d_graphs, graphs.data(), graphs.size() * sizeof(HnswForestGraph), hipMemcpyHostToDevice));
+        HF_CHK(hipMemsetAsync(d_nbr0, 0xFF, total * 2 * m * 4, ctx->stream));
+        HF_CHK(hipMemsetAsync(d_up_nbr, 0xFF, up_words * 4, ctx->stream));
+        HF_CHK(hipMemsetAsync(d_dist0, 0, total * 2 * m * 4, ctx->stream));
+        HF_CHK(hipMemsetAsync(d_up_dist, 0, up_words * 4, ctx->stream));
+
+        HnswBuildParams bp{};
+        bp.rows = c->d_rows;
+        bp.stride4 = row_chunks;
+        bp.metric = metric == VSR_METRIC_L2 ? M_L2 : M_IP;
+        bp.halves = expect == RowFormat::HALF ? 1 : 0;
+        if (expect == RowFormat::BIT) {
+            bp.bits = 1;
+            bp.metric = metric == VSR_METRIC_JACCARD ? M_JACCARD : M_HAMMING;
+            bp.row_pop = c->d_norm2;
+        }
+        bp.m = (uint32_t) m;
+        bp.efc = (uint32_t) ef_construction;
+        bp.max_level = (uint32_t) fo.g_max_level;
+        bp.nbr0 = d_nbr0;
+        bp.dist0 = d_dist0;
+        bp.up_slot = d_up_slot;
+        bp.up_nbr = d_up_nbr;
+        bp.up_dist = d_up_dist;
+        bp.level = d_level;
+        bp.elem_row = d_elem_row;
+        bp.caps = (uint32_t) (ef_construction + 2 * m);
+        uint32_t slots = *slots_io;
+        if (slots == 0) {                                                     // the build's default
+            slots = 4096;
+            while (slots < (uint32_t) ef_construction * 2u * (uint32_t) m * 2u && slots < 32768u) slots <<= 1;
+            *slots_io = slots;
+        }
+        bp.hash_slots = slots;
+        const size_t per = hnsw_build_lds_per_wave(bp.caps, slots);
+        if (per > HN_LDS_BUDGET) return bail(fail(VSR_ERR_UNSUPPORTED, "%s: ef_construction = %d with m = %d does not fit the LDS", who, ef_construction, m));
+        bp.lds_per_wave = (uint32_t) per;
+        bp.wpb = (uint32_t) std::min<size_t>(4, HN_LDS_BUDGET / per);
+        bp.err = ctx->err_word();
+        uint32_t rec_cap_max = 1;
+        size_t tmp_bytes = 0;
+        {
+            std::vector<uint32_t> caps;                                       // the sort's scratch: the most any round's size asks for
+            for (const HnswForestRound& r : fo.plan.rounds) caps.push_back(r.rec_cap);
+            std::sort(caps.begin(), caps.end());
+            caps.erase(std::unique(caps.begin(), caps.end()), caps.end());
+            for (uint32_t cap : caps) tmp_bytes = std::max(tmp_bytes, vsr_hnsw_build_sort_bytes(cap));
+            if (!caps.empty()) rec_cap_max = std::max(rec_cap_max, caps.back());
+        }
+        for (int i = 0; i < 2; ++i) {
+            HF_CHK(dev((void**) &d_key[i], (size_t) rec_cap_max * 8));
+            HF_CHK(dev((void**) &d_val[i], (size_t) rec_cap_max * 8));
+        }
+        HF_CHK(dev((void**) &d_cnt, 64));
+        HF_CHK(dev(&d_tmp, std::max<size_t>(tmp_bytes, 256)));
+        bp.rec_count = d_cnt;
+        for (const HnswForestRound& r : fo.plan.rounds) {
+            HnswForestParams fp{};
+            fp.elems = d_plan + r.first_slot;
+            fp.entry = d_plan + total + r.first_slot;
+            fp.entry_level = d_plan + 2 * total + r.first_slot;
+            bp.count = r.count;
+            bp.rec_cap = r.rec_cap;
+            bp.rec_key = d_key[0];
+            bp.rec_val = d_val[0];
+            HF_CHK(vsr_hnsw_forest_round(bp, fp, d_tmp, tmp_bytes, d_key[1], d_val[1], ctx->stream));
+        }
+        HF_CHK(vsr_hnsw_forest_split(bp, d_graphs, (uint32_t) graphs.size(), (uint32_t) total, ctx->stream));
+        HF_CHK(hipStreamSynchronize(ctx->stream));
+        // the build's rule: never a thinner graph.  The bits are this call's and leave the session's guard word here
+        uint32_t word = 0;
+        HF_CHK(hipMemcpy(&word, bp.err, sizeof word, hipMemcpyDeviceToHost));
+        if (word & (HB_ERR_VISITED | HB_ERR_RECORDS | HB_ERR_CANDIDATES)) {
+            *guard = word & (HB_ERR_VISITED | HB_ERR_RECORDS | HB_ERR_CANDIDATES);
+            word &= ~(HB_ERR_VISITED | HB_ERR_RECORDS | HB_ERR_CANDIDATES);
+            HF_CHK(hipMemcpy(bp.err, &word, sizeof word, hipMemcpyHostToDevice));
+            return bail(VSR_OK);
+        }
+    }
+#undef HF_CHK
+    cleanup();
+    for (int g = 0; g < fo.n_parts; ++g) {
+        made[(size_t) g]->corpus = c;
+        c->hnsw_indexes.push_back(made[(size_t) g].get());
+        out[g] = made[(size_t) g].release();
+    }
+    return VSR_OK;
+}
+
+extern "C" int vsr_hnsw_build_partitions(vsr_corpus* c, int n_parts, const int64_t* part_off, const int64_t* part_rows, int m, int ef_construction,
+                                         int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out)
+{
+    const char* who = "vsr_hnsw_build_partitions";
+    if (out)
+        for (int g = 0; g < n_parts; ++g) out[g] = nullptr;
+    if (!c || n_parts < 0 || (n_parts > 0 && (!out || !part_off))) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
+    const RowFormat expect = c->format;
+    if (expect == RowFormat::SPARSE)
+        return fail(VSR_ERR_UNSUPPORTED,
+                    "%s: a sparsevec corpus is not supported (the sparse build has no element -> row form): build every partition's graph with "
+                    "vsr_hnsw_build_sparse over a corpus of its rows", who);
+    if (flags & VSR_HNSW_BUILD_MERGE_DUPLICATES)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: VSR_HNSW_BUILD_MERGE_DUPLICATES is not supported (every element of a partition graph is one row)", who);
+    {
+        vsr_hnsw* none = nullptr;
+        const int rc = hnsw_build_check(c, expect, m, ef_construction, metric, flags, &none, who);
+        if (rc) return rc;
+    }
+    uint32_t cap = HB_BATCH_MAX;
+    if (const char* env = getenv("VSR_HNSW_FOREST_BATCH")) {
+        char* end = nullptr;
+        const long v = strtol(env, &end, 10);
+        if (end == env || *end != '\0' || v < 1 || v > (long) HB_BATCH_MAX)
+            return fail(VSR_ERR_INVALID, "%s: VSR_HNSW_FOREST_BATCH must be a number from 1 to %u (got \"%s\")", who, HB_BATCH_MAX, env);
+        cap = (uint32_t) v;
+    }
+    uint32_t slots = 0;
+    if (const int rc = hnsw_env_visited_slots(who, &slots)) return rc;
+    if (n_parts == 0) return VSR_OK;
+    if (part_off[0] != 0) return fail(VSR_ERR_INVALID, "%s: part_off[0] is %lld, not 0", who, (long long) part_off[0]);
+    for (int g = 0; g < n_parts; ++g)
+        if (part_off[g + 1] < part_off[g])
+            return fail(VSR_ERR_INVALID, "%s: part_off does not ascend at partition %d (%lld after %lld)", who, g, (long long) part_off[g + 1],
+                        (long long) part_off[g]);
+    const int64_t total = part_off[n_parts];
+    if (total > 0 && !part_rows) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
+    if (total > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "%s: too many elements", who);
+
+    HnswForest fo;
+    fo.n_parts = n_parts;
+    fo.base.assign(part_off, part_off + n_parts + 1);
+    fo.elem_row.resize((size_t) total);
+    {
+        // caller rows -> internal rows; within a partition every row once (seen[row] = the partition that named it last, + 1)
+        std::vector<int32_t> inv((size_t) std::max<int64_t>(c->n, 1), -1), seen((size_t) std::max<int64_t>(c->n, 1), 0);
+        for (int64_t r = 0; r < c->n; ++r) inv[(size_t) c->h_orig[(size_t) r]] = (int32_t) r;
+        for (int g = 0; g < n_parts; ++g) {
+            for (int64_t i = part_off[g]; i < part_off[g + 1]; ++i) {
+                const int64_t row = part_rows[i];
+                if (row < 0 || row >= c->n)
+                    return fail(VSR_ERR_INVALID, "%s: partition %d, position %lld: row %lld is outside [0, %lld)", who, g, (long long) (i - part_off[g]),
+                                (long long) row, (long long) c->n);
+                if (seen[(size_t) row] == g + 1)
+                    return fail(VSR_ERR_INVALID, "%s: partition %d, position %lld: row %lld is named twice", who, g, (long long) (i - part_off[g]),
+                                (long long) row);
+                seen[(size_t) row] = g + 1;
+                fo.elem_row[(size_t) i] = inv[(size_t) row];
+            }
+            std::sort(fo.elem_row.begin() + part_off[g], fo.elem_row.begin() + part_off[g + 1]);   // the build's insertion order
+        }
+    }
+    // levels: the build's stream, drawn once as far as the largest partition needs and read from its start by each
+    {
+        int64_t longest = 0;
+        for (int g = 0; g < n_parts; ++g) longest = std::max(longest, part_off[g + 1] - part_off[g]);
+        HnswLevelStream stream(seed, m);
+        std::vector<int32_t> draws((size_t) longest);
+        for (int32_t& d : draws) d = stream.level();
+        fo.level.resize((size_t) total);
+        for (int g = 0; g < n_parts; ++g) std::copy(draws.begin(), draws.begin() + (part_off[g + 1] - part_off[g]), fo.level.begin() + part_off[g]);
+    }
+    fo.up_slot.assign((size_t) total, -1);
+    fo.slot_base.assign((size_t) n_parts, 0);
+    fo.n_upper.assign((size_t) n_parts, 0);
+    fo.max_level.assign((size_t) n_parts, 1);
+    for (int g = 0; g < n_parts; ++g) {
+        fo.slot_base[(size_t) g] = fo.g_upper;
+        for (int64_t e = part_off[g]; e < part_off[g + 1]; ++e)
+            if (fo.level[(size_t) e] >= 1) {
+                fo.up_slot[(size_t) e] = fo.g_upper++;
+                fo.max_level[(size_t) g] = std::max(fo.max_level[(size_t) g], fo.level[(size_t) e]);
+            }
+        fo.n_upper[(size_t) g] = fo.g_upper - fo.slot_base[(size_t) g];
+        fo.g_max_level = std::max(fo.g_max_level, fo.max_level[(size_t) g]);
+    }
+    if (!hnsw_forest_plan(n_parts, fo.base.data(), fo.level.data(), m, cap, fo.plan))
+        return fail(VSR_ERR_UNSUPPORTED, "%s: a round with m = %d has too many reverse edges", who, m);
+    for (;;) {
+        uint32_t guard = 0;
+        const int rc = hnsw_forest_once(c, expect, m, ef_construction, metric, fo, &slots, &guard, out, who);
+        if (rc != VSR_OK || guard == 0) return rc;
+        if (guard & HB_ERR_RECORDS)
+            return fail(VSR_ERR_UNSUPPORTED, "%s: reverse edges were dropped at ef_construction = %d with m = %d: the graph would be incomplete", who,
+                        ef_construction, m);
+        // HB_ERR_VISITED, in any graph: the whole call again, as hnsw_build
+        if (slots >= 32768u || hnsw_build_lds_per_wave((uint32_t) (ef_construction + 2 * m), slots * 2u) > HN_LDS_BUDGET)
+            return fail(VSR_ERR_UNSUPPORTED,
+                        "%s: a layer search at ef_construction = %d with m = %d fills its visited table of %u entries and no larger one fits the LDS",
+                        who, ef_construction, m, slots);
+        slots *= 2u;
+    }
 }
 
 // vsr_hnsw_extend's host pass over the caller's graph, before anything is uploaded.  The extension WRITES through these lists

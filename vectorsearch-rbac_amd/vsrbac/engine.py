@@ -568,6 +568,25 @@ class Corpus:
             check(self._lib.vsr_hnsw_build(self._h, int(m), int(ef_construction), _metric(metric), int(seed), C.byref(h)))
         return HnswIndex(self, h)
 
+    def build_hnsw_partitions(self, parts, m=16, ef_construction=64, metric=None, seed=1):
+        """One HNSW index per row subset -- a role table, a dynamic partition -- built in one call over this corpus, whose rows
+        stay resident once (vsr_hnsw_build_partitions).  `parts`: a sequence of row-index sequences of this corpus; they may
+        overlap, come in any order and be empty, but a partition names a row once.  Returns a list of HnswIndex, one per
+        partition, each the graph build_hnsw / build_hnsw_half / build_hnsw_bit (the row format is this corpus's) with the same
+        m, ef_construction, metric and seed makes of a corpus holding only that partition's rows, its heap TIDs being row indices
+        of THIS corpus.  metric: None is "l2", or "hamming" on a bit corpus, where it also becomes the indexes' opclass.  On an
+        error no index is left behind."""
+        if metric is None:
+            metric = "hamming" if self.is_bit else "l2"
+        rows = [np.ascontiguousarray(np.asarray(p, dtype=np.int64).ravel()) for p in parts]
+        off = np.zeros(len(rows) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([r.size for r in rows])
+        flat = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros(0, dtype=np.int64)
+        handles = (C.c_void_p * max(len(rows), 1))()
+        check(self._lib.vsr_hnsw_build_partitions(self._h, len(rows), _ptr(off), _ptr(flat), int(m), int(ef_construction),
+                                                  _metric(metric), int(seed), 0, handles))
+        return [HnswIndex(self, C.c_void_p(handles[g])) for g in range(len(rows))]
+
     def load_hnsw(self, graph):
         """HNSW graph over this corpus; `graph`: dict with m, entry, level, nbr0, tid_count, tids, up_slot, up_nbr,
         max_level (include/vsrbac.h, vsr_hnsw_load: what a dump of pgvector's in-memory build holds)."""

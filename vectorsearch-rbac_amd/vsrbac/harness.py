@@ -97,6 +97,7 @@ class Deployment:
         self.metric = metric
         self.corpus = ctx.load_corpus(rows, block_ids, doc_ids)
         self.corpus.load_rbac(user_roles, permissions)
+        self.doc_ids = None if doc_ids is None else np.asarray(doc_ids, dtype=np.int64).ravel()   # row -> document_id
         self.block_content = block_content          # optional: row index -> text (the table's block_content column)
         self.user_roles = {}
         for u, r in np.asarray(user_roles, dtype=np.int64).reshape(-1, 2):
@@ -160,6 +161,20 @@ class Deployment:
         self.comb_role_partitions = {tuple(sorted(int(r) for r in c)): [int(p) for p in ps]
                                      for c, ps in comb_role_partitions.items()}
         self._part_filters = {}
+
+    def build_partition_hnsw(self, partition_docs=None, m=16, ef_construction=64, metric=None, seed=1):
+        """One HNSW index per partition over the resident corpus, built in one call (Corpus.build_hnsw_partitions): the
+        reference's create_indexes_for_all_role_tables without a table per partition.  partition_docs: {partition_id:
+        [document_id, ...]} as load_partitions takes it (None: the partitions loaded); a partition's rows are the rows of its
+        documents.  Returns {partition_id: HnswIndex}, the caller's to free.  dynamic_partition_search does not go through
+        these graphs: it stays the exact scan."""
+        docs = self.partitions if partition_docs is None else partition_docs
+        if self.doc_ids is None:
+            raise ValueError("partitions are sets of documents: the deployment was loaded without doc_ids")
+        items = sorted(((int(p), np.asarray(d, dtype=np.int64).ravel()) for p, d in docs.items()), key=lambda t: t[0])
+        parts = [np.flatnonzero(np.isin(self.doc_ids, d)) for _, d in items]
+        metric = self.metric if metric is None else metric
+        return dict(zip([p for p, _ in items], self.corpus.build_hnsw_partitions(parts, m, ef_construction, metric, seed)))
 
     def _partition_filter(self, pid, user_id):
         """Pure partitions (every document visible to the combination) carry no per-row test; impure ones
