@@ -696,13 +696,63 @@ int vsr_hnsw_vacuum(vsr_corpus* corpus, int m, int32_t n_elem, int32_t entry, co
  *     corpus: VSR_ERR_UNSUPPORTED, the message names sparsevec (the sparse build has no element -> row form).  flags must be 0:
  *     VSR_HNSW_BUILD_MERGE_DUPLICATES is VSR_ERR_UNSUPPORTED, any other bit VSR_ERR_INVALID.
  *   - On failure every index made so far is freed and every out[g] is NULL.  The session's guard word is left as it was found.
- * Not covered: extending or vacuuming a partition graph in place (export it and use vsr_hnsw_extend / vsr_hnsw_vacuum), and searching
- * several graphs in one launch.  Synchronises. */
+ * Not covered: extending or vacuuming a partition graph in place (export it and use vsr_hnsw_extend / vsr_hnsw_vacuum).  The graphs of
+ * a query's partitions are searched as a set by vsr_hnsw_forest_search* below.  Synchronises. */
 int vsr_hnsw_build_partitions(vsr_corpus* corpus, int n_parts,
                               const int64_t* part_off  /* [n_parts + 1], ascending, part_off[0] = 0 */,
                               const int64_t* part_rows /* [part_off[n_parts]] caller row indices */,
                               int m, int ef_construction, int metric, uint64_t seed, uint32_t flags,
                               vsr_hnsw** out /* [n_parts] */);
+/* A FOREST: many indexes over ONE corpus (the graphs of vsr_hnsw_build_partitions, or any others) searched as a set -- what the
+ * reference's dynamic_partition_search does with the HNSW indexes of a user's role combination: search each, merge by distance, drop the
+ * rows several partitions hold, keep k.  Here: ONE search launch over all (query, graph) pairs of the call and ONE merge launch.
+ *   - vsr_hnsw_forest_open validates once: every index over the same corpus, of the same row format (fp32, halfvec or bit) and the same m,
+ *     bit indexes of the same opclass; a sparse index is VSR_ERR_UNSUPPORTED (the message names sparsevec), anything else
+ *     VSR_ERR_INVALID, the message naming the offending index.  n_indexes = 0 and empty graphs are allowed; an index may be named
+ *     twice.  The forest uploads one descriptor per graph and owns the scratch of its calls; the indexes stay the caller's and must
+ *     outlive the forest: vsr_hnsw_forest_free comes before vsr_hnsw_free of its indexes.
+ *   - A TASK is a (query, graph) pair: query i owns tasks q_off[i] .. q_off[i + 1] of q_graph (graph ids are positions in `indexes`).
+ *     q_off must be non-decreasing from 0 and every graph id within range (checked on the host: VSR_ERR_INVALID).  A query may have no
+ *     task (its count is 0) and may name a graph twice.
+ *   - The result of query i: the rows vsr_hnsw_search / vsr_hnsw_search_bit returns for that query, filter, k, ef_search and metric on
+ *     each of its graphs, put together, ordered by (the index's rank value, document_id, block_id), repeated rows dropped, the first k
+ *     kept.  Distances are reported as vsr_hnsw_search reports them; slots past the count hold -1 / +Inf.  filters: as vsr_hnsw_search,
+ *     one per QUERY (or NULL).  Predicate-aware walking is a property of the forest on this path (vsr_hnsw_forest_set_predicate_aware,
+ *     off by default); the indexes' own flags are not read.
+ *   - out_visited, [q_off[nq]], may be NULL: per TASK, what vsr_hnsw_search reports per query.
+ *   - A task whose LDS visited table overflows has no result.  The device forms then report count -1 for its query, never a partial
+ *     result; the host forms run exactly those tasks again with the global bitmap and merge again.  VSR_HNSW_VISITED applies as in
+ *     vsr_hnsw_search.
+ *   - The device forms take d_queries and the outputs in device memory, q_off / q_graph / filters in host memory, and enqueue on the
+ *     corpus context's stream: the task table's upload, (bit: one staging launch over the queries,) the search launch, the merge launch.
+ *     They wait only where vsr_hnsw_search_device does: for the previous call's pinned upload blocks.  Over an empty forest only
+ *     nq = 0 is answered (there is no context to enqueue on); the host forms answer count 0.
+ *   - VSR_HNSW_FOREST_MERGE_KEYS=<C> (read at every call): the key slots of the merge's LDS, a power of two from the smallest one
+ *     >= 2 k to 16384, anything else VSR_ERR_INVALID; default 2048, or the lower bound when that is larger.  It sets how many task lists
+ *     one merge pass takes and never changes a result.
+ * Out of scope: iterative scans over a forest, forests of sparse indexes, and forests that span GPUs. */
+typedef struct vsr_hnsw_forest vsr_hnsw_forest;
+int vsr_hnsw_forest_open(vsr_hnsw* const* indexes, int n_indexes, vsr_hnsw_forest** out);
+int vsr_hnsw_forest_free(vsr_hnsw_forest* forest);
+int vsr_hnsw_forest_set_predicate_aware(vsr_hnsw_forest* forest, int on);
+int vsr_hnsw_forest_search(vsr_hnsw_forest* forest, const float* queries, int nq, int dim, int k, int ef_search, int metric,
+                           const int64_t* q_off /* [nq + 1] */, const int32_t* q_graph /* [q_off[nq]] */,
+                           const vsr_filter* const* filters /* [nq] or NULL */,
+                           int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows, float* out_dist, int32_t* out_counts,
+                           int64_t* out_visited /* [q_off[nq]], per task, may be NULL */);
+int vsr_hnsw_forest_search_device(vsr_hnsw_forest* forest, const float* d_queries, int nq, int dim, int k, int ef_search, int metric,
+                                  const int64_t* q_off, const int32_t* q_graph, const vsr_filter* const* filters,
+                                  int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
+                                  int32_t* d_out_counts, int64_t* d_out_visited);
+/* ... over a forest of bit indexes: queries are packed bit strings of (dim + 7) / 8 bytes, metric the indexes' opclass */
+int vsr_hnsw_forest_search_bit(vsr_hnsw_forest* forest, const uint8_t* queries, int nq, int dim, int k, int ef_search, int metric,
+                               const int64_t* q_off, const int32_t* q_graph, const vsr_filter* const* filters,
+                               int64_t* out_block_ids, int32_t* out_doc_ids, int64_t* out_rows, float* out_dist, int32_t* out_counts,
+                               int64_t* out_visited);
+int vsr_hnsw_forest_search_bit_device(vsr_hnsw_forest* forest, const uint8_t* d_queries, int nq, int dim, int k, int ef_search, int metric,
+                                      const int64_t* q_off, const int32_t* q_graph, const vsr_filter* const* filters,
+                                      int64_t* d_out_block_ids, int32_t* d_out_doc_ids, int64_t* d_out_rows, float* d_out_dist,
+                                      int32_t* d_out_counts, int64_t* d_out_visited);
 /* What the vacuum that made this index spilled: repairs run in the global-memory form, and the bytes of the workspace pool.
  * 0 / 0 for an index any other call made. */
 int vsr_hnsw_vacuum_spill_info(const vsr_hnsw* index, int32_t* spilled_repairs, int64_t* workspace_bytes);

@@ -117,6 +117,31 @@ struct HnswParams {
     uint32_t        cap_d = 0;
 };
 
+// The forest kernels (vsr_hnsw_forest_search.h: hnsw_forest_search_kernel and its half / bit forms) take this beside HnswParams, as a
+// second kernel argument, so that the parameter block of the eight kernels below stays what it was.  One descriptor per graph of the
+// forest: the per-index fields of HnswParams.
+struct HnswGraphDesc {
+    uint32_t       n_elem = 0;
+    int32_t        entry = -1, entry_level = -1;
+    uint32_t       max_level = 0;
+    const int32_t* elem_row = nullptr;
+    const int32_t* nbr0 = nullptr;
+    const int32_t* up_slot = nullptr;
+    const int32_t* up_nbr = nullptr;
+    const int32_t* level = nullptr;
+    const int32_t* tid_count = nullptr;
+    const int32_t* tids = nullptr;
+};
+// A task is a (query, graph) pair; HnswParams::nq counts the launch's tasks.  The task's results are keys only: out_keys
+// [slot][k] = make_key(rank value, internal row), KEY_EMPTY past the count; out_count / out_status / out_visited [slot].
+struct HnswForestTasks {
+    const HnswGraphDesc* graphs = nullptr;   // [n_indexes]
+    const int32_t*       task_query = nullptr;   // [tasks] the query: its row, its popcount, its bitmap
+    const int32_t*       task_graph = nullptr;   // [tasks]
+    const int32_t*       task_slot = nullptr;    // [tasks] where the task's outputs go; nullptr: slot = task (a re-run names the slots
+                                                 // of the tasks it repeats; the global visited words are the launch's own, by task)
+};
+
 constexpr int HN_UPPER_VISITED = 1024;     // visited list of an upper-layer (ef = 1) search, in LDS
 constexpr int HN_NBR = 256;                // neighbour ids of one expansion (2m <= 200)
 
@@ -125,6 +150,19 @@ __device__ __forceinline__ void wave_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+}
+
+// What a search reports for a result whose rank value (the index distance) is d: written once for emit() below and for the merge
+// kernel of a forest search (vsr_hnsw_forest_search.h), the rule of vsr_exact.h -- arithmetic two kernels share has one definition.
+__device__ __forceinline__ float hnsw_reported_distance(int rows, int metric, float d)
+{
+    if (rows == ROWS_BIT) return d;                                          // <~> / <%>: the index distance is the operator's value
+    if (rows == ROWS_SPARSE && metric == M_L1) return d;                     // <+>: the index distance is the operator's value
+    if (metric == M_L2) return (float) sqrt((double) d);                     // l2_distance, vector.c:577
+    if (metric == M_IP) return d;                                            // <#> = negative inner product
+    double sim = -(double) d;                                                // unit rows: cosine distance = 1 - dot
+    if (sim > 1.0) sim = 1.0; else if (sim < -1.0) sim = -1.0;
+    return (float) (1.0 - sim);
 }
 
 constexpr int HN_HIST = 256;               // radix-select histogram of the iterative kernel (8-bit digits), in LDS
@@ -160,14 +198,32 @@ __device__ __forceinline__ void wave_sync_global()
 // stage (sparse_graph_distances, vsr_sparseops.h) gives a row 4, 16 or 64 lanes by the corpus's entry-count class.  Arithmetic:
 // K1s's (fp32 sum over the row's entries, double sum over the hits, the rest term of L2 and L1); ranked by squared L2, the L1 sum or
 // the negated inner product; reported as K4 reports, L1 as the sum itself.
-template <bool ITER, int ROWS = ROWS_F32>
-__device__ __forceinline__ void hnsw_search_body(const HnswParams p)
+//
+// FOREST (vsr_hnsw_forest_search.h): the wave serves one TASK, a (query, graph) pair of a forest of graphs over one corpus.  qi is
+// the task; the query's row, popcount and bitmap are taken by the query index qq, the graph fields of the wave's copy of the
+// parameters come from the graph's descriptor, the global visited words are the task's, and emission writes keys only (out_keys
+// [slot][k], make_key(rank value, internal row)): identities and reported distances are the merge kernel's.
+template <bool ITER, int ROWS = ROWS_F32, bool FOREST = false>
+__device__ __forceinline__ void hnsw_search_body(const HnswParams pk, const HnswForestTasks ft = HnswForestTasks{})
 {
+    static_assert(!FOREST || (!ITER && ROWS != ROWS_SPARSE), "forest search: the plain search over fp32, halfvec and bit rows");
     extern __shared__ __align__(16) unsigned char smem_all[];
     const int lane = threadIdx.x & 63;
     const uint32_t wave = (uint32_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
-    const uint32_t qi = blockIdx.x * p.qpb + wave;
-    if (wave >= p.qpb || qi >= p.nq) return;                                 // (waves are independent: no workgroup barrier below)
+    const uint32_t qi = blockIdx.x * pk.qpb + wave;
+    if (wave >= pk.qpb || qi >= pk.nq) return;                               // (waves are independent: no workgroup barrier below)
+    HnswParams p = pk;
+    uint32_t qq = qi;                        // the query whose row, popcount and bitmap the wave reads
+    uint32_t so = qi;                        // where its outputs go
+    if constexpr (FOREST) {
+        qq = (uint32_t) __builtin_amdgcn_readfirstlane(ft.task_query[qi]);
+        const uint32_t g = (uint32_t) __builtin_amdgcn_readfirstlane(ft.task_graph[qi]);
+        if (ft.task_slot) so = (uint32_t) __builtin_amdgcn_readfirstlane(ft.task_slot[qi]);
+        const HnswGraphDesc gd = ft.graphs[g];
+        p.n_elem = gd.n_elem; p.entry = gd.entry; p.entry_level = gd.entry_level; p.max_level = gd.max_level;
+        p.elem_row = gd.elem_row; p.nbr0 = gd.nbr0; p.up_slot = gd.up_slot; p.up_nbr = gd.up_nbr; p.level = gd.level;
+        p.tid_count = gd.tid_count; p.tids = gd.tids;
+    }
     unsigned char* smem = smem_all + (size_t) wave * p.lds_per_query;
     uint64_t* S = reinterpret_cast<uint64_t*>(smem);                         // [caps] sorted keys
     uint8_t*  X = reinterpret_cast<uint8_t*>(S + p.caps);                    // [caps] expanded flags
@@ -190,7 +246,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
         hist = lv;
         lv += HN_HIST;
     }
-    const float* q = p.queries + (size_t) qi * p.q_stride;
+    const float* q = p.queries + (size_t) qq * p.q_stride;
     uint32_t* gvis = p.vis_mode == VIS_GLOBAL ? p.visited + (size_t) qi * p.vis_words : nullptr;
     const int half = lane >> 5, hl = lane & 31;
     const uint32_t d4 = (p.dim + 3) / 4;
@@ -229,7 +285,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
         bit_g = bit_graph_lanes(p.stride4);
         const uint32_t gl = (uint32_t) lane & (bit_g - 1u);
         if (p.stride4 <= 64u && gl < p.stride4) qreg = reinterpret_cast<const uint4*>(q)[gl];
-        q_pop = p.q_pop[qi];
+        q_pop = p.q_pop[qq];
     }
     // ROWS_HALF: the same lane groups; the query rounded to binary16 once, this lane's chunk of it or the copy in LDS
     if constexpr (ROWS == ROWS_HALF) {
@@ -325,7 +381,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
         }
     };
 
-    const uint64_t* bm = p.bitmaps ? p.bitmaps[qi] : nullptr;
+    const uint64_t* bm = p.bitmaps ? p.bitmaps[qq] : nullptr;
     const bool pa = p.predicate_aware && bm != nullptr;
     // element e is permitted when one of its heap rows is
     auto permitted = [&](uint32_t e) -> bool {
@@ -566,7 +622,11 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
 
     auto write_empty = [&](uint32_t from) {
         for (uint32_t i = from + (uint32_t) lane; i < p.k; i += 64) {
-            const size_t o = (size_t) qi * p.k + i;
+            const size_t o = (size_t) so * p.k + i;
+            if constexpr (FOREST) {
+                p.out_keys[o] = KEY_EMPTY;
+                continue;
+            }
             p.out_block[o] = -1; p.out_doc[o] = -1;
             if (p.out_row) p.out_row[o] = -1;
             p.out_dist[o] = __builtin_inff();
@@ -574,11 +634,11 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
                 if (p.out_keys) p.out_keys[o] = KEY_EMPTY;
         }
     };
-    if (p.out_status && lane == 0) p.out_status[qi] = 0;
+    if (p.out_status && lane == 0) p.out_status[so] = 0;
     if (p.entry < 0) {
-        if (lane == 0) p.out_count[qi] = 0;
-        if constexpr (ITER)
-            if (p.out_visited && lane == 0) p.out_visited[qi] = 0;
+        if (lane == 0) p.out_count[so] = 0;
+        if constexpr (ITER || FOREST)
+            if (p.out_visited && lane == 0) p.out_visited[so] = 0;
         write_empty(0);
         return;
     }
@@ -595,17 +655,17 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
     }
     search_layer(0, p.ef, true);
     if constexpr (!ITER)
-        if (p.out_visited && lane == 0) p.out_visited[qi] = visited_l0;
+        if (p.out_visited && lane == 0) p.out_visited[so] = visited_l0;
     auto fail_query = [&]() {                                                // status 1: no result
         if (lane == 0) {
-            p.out_count[qi] = -1;
-            if (p.out_status) p.out_status[qi] = 1;
+            p.out_count[so] = -1;
+            if (p.out_status) p.out_status[so] = 1;
         }
         write_empty(0);
     };
     if (overflow) {                                                          // the visited table filled up (ITER: D did)
         if constexpr (ITER)
-            if (p.out_visited && lane == 0) p.out_visited[qi] = visited_l0;
+            if (p.out_visited && lane == 0) p.out_visited[so] = visited_l0;
         fail_query();
         return;
     }
@@ -647,25 +707,16 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
             if ((okmask >> t) & 1u) {
                 if (at < p.k) {
                     const uint32_t row = (uint32_t) p.tids[(size_t) e * 10 + (nt - 1 - t)];
-                    const size_t o = (size_t) qi * p.k + at;
+                    const size_t o = (size_t) so * p.k + at;
+                    if constexpr (FOREST) p.out_keys[o] = make_key(d, row);      // the merge kernel's input: nothing else
+                    else {
                     p.out_block[o] = p.block_ids[row];
                     p.out_doc[o] = p.doc_ids[row];
                     if (p.out_row) p.out_row[o] = p.orig_rows[row];
-                    float v;
-                    if constexpr (ROWS == ROWS_BIT) {                        // <~> / <%>: the index distance is the operator's value
-                        v = d;
+                    if constexpr (ROWS == ROWS_BIT)
                         if (p.out_keys) p.out_keys[o] = make_key(d, row + p.key_row_offset);
-                    } else
-                    if (ROWS == ROWS_SPARSE && p.metric == M_L1) v = d;      // <+>: the index distance is the operator's value
-                    else
-                    if (p.metric == M_L2) v = (float) sqrt((double) d);      // l2_distance, vector.c:577
-                    else if (p.metric == M_IP) v = d;                        // <#> = negative inner product
-                    else {                                                   // unit rows: cosine distance = 1 - dot
-                        double sim = -(double) d;
-                        if (sim > 1.0) sim = 1.0; else if (sim < -1.0) sim = -1.0;
-                        v = (float) (1.0 - sim);
+                    p.out_dist[o] = hnsw_reported_distance(ROWS, p.metric, d);
                     }
-                    p.out_dist[o] = v;
                 }
                 ++at;
             }
@@ -772,7 +823,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
             }
             emit(count);
         }
-        if (p.out_visited && lane == 0) p.out_visited[qi] = visited_l0;
+        if (p.out_visited && lane == 0) p.out_visited[so] = visited_l0;
         if (overflow) {
             fail_query();
             return;
@@ -780,7 +831,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswParams p)
     }
     if (out > p.k) out = p.k;
     write_empty(out);
-    if (lane == 0) p.out_count[qi] = (int32_t) out;
+    if (lane == 0) p.out_count[so] = (int32_t) out;
 }
 
 __global__ __launch_bounds__(256) void hnsw_search_kernel(const HnswParams p) { hnsw_search_body<false>(p); }

@@ -1,10 +1,12 @@
 // vsr_hnsw_rt.hip — K4 / K4b / K4h: HNSW graph load / build / search entry points, over fp32 corpora (vsr_hnsw_*), bit corpora
 // (vsr_hnsw_*_bit, vsr_hnsw_search_quantized*) and halfvec corpora (vsr_hnsw_load_half / vsr_hnsw_build_half, searched by the
-// float entry points).  The only unit that compiles vsr_hnsw.h's kernels.
+// float entry points), and the forest entry points that search many indexes of one corpus as a set (vsr_hnsw_forest_*).  The only
+// unit that compiles vsr_hnsw.h's and vsr_hnsw_forest_search.h's kernels.
 #include "vsr_runtime.h"
 #include "vsr_hnsw.h"
 #include "vsr_hnsw_build.h"
 #include "vsr_hnsw_forest.h"
+#include "vsr_hnsw_forest_search.h"
 #include "vsr_shortlist.h"
 
 #include <climits>
@@ -1671,15 +1673,14 @@ struct SparseCsr {
     uint32_t       max_nnz;
 };
 
-// One launch over queries resident in device memory, results into device arrays (out.keys: a bit index only, the raw keys of
-// the results); bitmaps: one device pointer per query (d_bm, may be nullptr).  d_status / d_vis are optional device arrays
-// (iterative: T).  The kernel is K4b when the index is over a bit corpus, K4h when it is over a halfvec corpus.
-static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const HnswQueries& qs, int nq, int k, int ef, int metric,
-                       const uint64_t* const* d_bm, bool force_global, const Outputs& out, int64_t* d_vis, int32_t* d_status,
-                       const HnswIterLaunch* iter = nullptr)
+// The parameter block of one launch over the index's graph: rows, queries, the graph arrays, the LDS plan (VSR_HNSW_VISITED applies)
+// and, where the plan asks for them, the global visited words of the launch's nq waves (cleared on the stream).  Results, status and
+// the guard word are the caller's to set.  (vsr_hnsw_forest_search*: h is the forest's own index object, whose n_elem is the
+// largest of the forest and whose graph arrays every wave replaces by its graph's, and nq counts tasks.)
+static int hnsw_params(vsr_hnsw* h, vsr_ctx* ctx, const HnswQueries& qs, int nq, int k, int ef, int metric, const uint64_t* const* d_bm,
+                       bool force_global, const HnswIterLaunch* iter, HnswParams& p)
 {
     vsr_corpus* c = h->corpus;
-    HnswParams p{};
     p.rows = c->d_rows;
     p.stride4 = format_row_chunks(h->format, c->dim);       // 16-byte chunks per row
     p.metric = metric;
@@ -1689,7 +1690,6 @@ static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const HnswQueries& qs, int nq,
         p.metric = h->bit_metric == VSR_METRIC_JACCARD ? M_JACCARD : M_HAMMING;
         p.row_pop = c->d_norm2;
         p.q_pop = qs.pop;
-        p.out_keys = out.keys;
         p.key_row_offset = (uint32_t) c->row_offset;
     }
     if (h->format == RowFormat::HALF) p.q_chunks = p.stride4 > 64u ? p.stride4 : 0u;   // K4h: rows past 64 chunks keep the query in LDS
@@ -1772,6 +1772,21 @@ static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const HnswQueries& qs, int nq,
         HIPCHK(hipMemsetAsync(h->d_vis.p, 0, (size_t) nq * p.vis_words * 4, ctx->stream));
         p.visited = h->d_vis.as<uint32_t>();
     }
+    return VSR_OK;
+}
+
+// One launch over queries resident in device memory, results into device arrays (out.keys: a bit index only, the raw keys of
+// the results); bitmaps: one device pointer per query (d_bm, may be nullptr).  d_status / d_vis are optional device arrays
+// (iterative: T).  The kernel is K4b when the index is over a bit corpus, K4h when it is over a halfvec corpus.
+static int hnsw_launch(vsr_hnsw* h, vsr_ctx* ctx, const HnswQueries& qs, int nq, int k, int ef, int metric,
+                       const uint64_t* const* d_bm, bool force_global, const Outputs& out, int64_t* d_vis, int32_t* d_status,
+                       const HnswIterLaunch* iter = nullptr)
+{
+    vsr_corpus* c = h->corpus;
+    HnswParams p{};
+    int rc = hnsw_params(h, ctx, qs, nq, k, ef, metric, d_bm, force_global, iter, p);
+    if (rc) return rc;
+    if (h->format == RowFormat::BIT) p.out_keys = out.keys;
     set_results(p, c, out);
     p.out_visited = d_vis;
     p.out_status = d_status;
@@ -2415,4 +2430,344 @@ extern "C" int vsr_hnsw_search_quantized(vsr_corpus* src, vsr_hnsw* h, const flo
     }
     rb.copy_out_all(hh, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr}, nullptr);
     return VSR_OK;
+}
+
+// ---- forest search: the partition graphs of a query in one search launch, merged on the GPU (vsr_hnsw_forest_search.h) ----
+struct vsr_hnsw_forest {
+    // The forest's own index object: no graph, registered with the corpus like any index.  It carries what the single-index entry
+    // points keep per index -- the row format and opclass the argument checks read, the shared m, the largest n_elem (the LDS plan), the
+    // forest's predicate-aware flag, the filter bitmaps, staged queries, visited words and result blocks of a call.  nullptr: an empty forest
+    vsr_hnsw* host = nullptr;
+    std::vector<vsr_hnsw*> indexes;
+    DevBuf d_graphs;                                 // one HnswGraphDesc per index
+    DevBuf d_tasks;                                  // a call's task table, task keys, counts, status words and visited counts
+    PinBuf h_tasks;
+};
+
+extern "C" int vsr_hnsw_forest_free(vsr_hnsw_forest* f)
+{
+    if (!f) return VSR_OK;
+    if (f->host) {
+        (void) hipSetDevice(f->host->corpus->ctx->device);
+        (void) vsr_hnsw_free(f->host);               // waits for the stream
+    }
+    delete f;
+    return VSR_OK;
+}
+
+extern "C" int vsr_hnsw_forest_open(vsr_hnsw* const* indexes, int n_indexes, vsr_hnsw_forest** out)
+{
+    const char* who = "vsr_hnsw_forest_open";
+    if (!out) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    if (n_indexes < 0 || (n_indexes > 0 && !indexes)) return fail(VSR_ERR_INVALID, "%s: %d indexes at %p", who, n_indexes, (const void*) indexes);
+    std::unique_ptr<vsr_hnsw_forest, int (*)(vsr_hnsw_forest*)> f(new vsr_hnsw_forest, vsr_hnsw_forest_free);
+    if (n_indexes == 0) {
+        *out = f.release();
+        return VSR_OK;
+    }
+    for (int g = 0; g < n_indexes; ++g) {
+        const vsr_hnsw* h = indexes[g];
+        const vsr_hnsw* h0 = indexes[0];
+        if (!h) return fail(VSR_ERR_INVALID, "%s: index %d is NULL", who, g);
+        if (h->format == RowFormat::SPARSE)
+            return fail(VSR_ERR_UNSUPPORTED, "%s: index %d is over a sparsevec corpus: a forest is searched over vector, halfvec or bit rows", who, g);
+        if (h->format != h0->format)
+            return fail(VSR_ERR_INVALID, "%s: index %d is over %s rows, index 0 over %s rows", who, g, format_name(h->format), format_name(h0->format));
+        if (h->corpus != h0->corpus) return fail(VSR_ERR_INVALID, "%s: index %d is over another corpus than index 0", who, g);
+        if (h->m != h0->m) return fail(VSR_ERR_INVALID, "%s: index %d has m = %d, index 0 has m = %d", who, g, h->m, h0->m);
+        if (h->format == RowFormat::BIT && h->bit_metric != h0->bit_metric)
+            return fail(VSR_ERR_INVALID, "%s: index %d was made for %s, index 0 for %s", who, g, bit_metric_name(h->bit_metric),
+                        bit_metric_name(h0->bit_metric));
+    }
+    vsr_corpus* c = indexes[0]->corpus;
+    HIPCHK(hipSetDevice(c->ctx->device));
+    std::unique_ptr<vsr_hnsw> host(new vsr_hnsw);
+    host->format = indexes[0]->format;
+    host->bit_metric = indexes[0]->bit_metric;
+    host->m = indexes[0]->m;
+    std::vector<HnswGraphDesc> desc((size_t) n_indexes);
+    for (int g = 0; g < n_indexes; ++g) {
+        const vsr_hnsw* h = indexes[g];
+        HnswGraphDesc& d = desc[(size_t) g];
+        d.n_elem = (uint32_t) h->n_elem;
+        d.entry = h->entry;
+        d.entry_level = h->entry_level;
+        d.max_level = (uint32_t) h->max_level;
+        d.elem_row = h->d_elem_row;
+        d.nbr0 = h->d_nbr0;
+        d.up_slot = h->d_up_slot;
+        d.up_nbr = h->d_up_nbr;
+        d.level = h->d_level;
+        d.tid_count = h->d_tid_count;
+        d.tids = h->d_tids;
+        host->n_elem = std::max(host->n_elem, h->n_elem);
+    }
+    int rc = f->d_graphs.reserve(desc.size() * sizeof(HnswGraphDesc));
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(f->d_graphs.p, desc.data(), desc.size() * sizeof(HnswGraphDesc), hipMemcpyHostToDevice));
+    f->indexes.assign(indexes, indexes + n_indexes);
+    host->corpus = c;
+    c->hnsw_indexes.push_back(host.get());
+    f->host = host.release();
+    *out = f.release();
+    return VSR_OK;
+}
+
+extern "C" int vsr_hnsw_forest_set_predicate_aware(vsr_hnsw_forest* f, int on)
+{
+    if (!f) return fail(VSR_ERR_INVALID, "vsr_hnsw_forest_set_predicate_aware: forest is NULL");
+    if (f->host) f->host->predicate_aware = on ? 1 : 0;
+    return VSR_OK;
+}
+
+// where a call's task arrays live in d_tasks; h_tasks mirrors the sections in front of o_keys (the upload, and a re-run's lists)
+struct ForestLayout {
+    size_t o_off, o_tq, o_tg, upload, o_redo, sec, o_keys, o_cnt, o_status, o_vis, total;
+    ForestLayout(int nq, size_t n_tasks, int k)
+    {
+        o_off = 0;
+        o_tq = align_up(((size_t) nq + 1) * 8, 256);
+        o_tg = align_up(o_tq + n_tasks * 4, 256);
+        upload = align_up(o_tg + n_tasks * 4, 256);
+        o_redo = upload;                                                     // a re-run's [query | graph | slot], `sec` bytes each
+        sec = align_up(n_tasks * 4, 256);
+        o_keys = o_redo + 3 * sec;
+        o_cnt = align_up(o_keys + n_tasks * (size_t) k * 8, 256);
+        o_status = align_up(o_cnt + n_tasks * 4, 256);
+        o_vis = align_up(o_status + n_tasks * 4, 256);                       // (status and visited: one copy back)
+        total = align_up(o_vis + n_tasks * 8, 256);
+    }
+};
+
+// VSR_HNSW_FOREST_MERGE_KEYS (read at every call)
+static int forest_merge_keys(const char* who, int k, uint32_t* cap)
+{
+    *cap = hnsw_merge_keys_default((uint32_t) k);
+    const char* env = getenv("VSR_HNSW_FOREST_MERGE_KEYS");
+    if (!env) return VSR_OK;
+    char* end = nullptr;
+    const unsigned long long v = strtoull(env, &end, 10);
+    if (!*env || *end || env[0] == '-' || !hnsw_merge_keys_ok((uint32_t) k, v))
+        return fail(VSR_ERR_INVALID, "%s: VSR_HNSW_FOREST_MERGE_KEYS must be a power of two from %u (the smallest >= 2 k) to %u (got \"%s\")", who,
+                    hnsw_merge_keys_min((uint32_t) k), HFS_MERGE_KEYS_MAX, env);
+    *cap = (uint32_t) v;
+    return VSR_OK;
+}
+
+// the search launch over n tasks listed at d_tq / d_tg (d_slot: a re-run's output slots, else nullptr)
+static int forest_search_launch(vsr_hnsw_forest* f, vsr_ctx* ctx, const HnswQueries& qs, bool any_filter, int n, const int32_t* d_tq,
+                                const int32_t* d_tg, const int32_t* d_slot, bool force_global, int k, int ef, int metric, const ForestLayout& lay,
+                                int64_t* d_visited)
+{
+    if (n == 0) return VSR_OK;
+    vsr_hnsw* h = f->host;
+    char* w = f->d_tasks.as<char>();
+    HnswParams p{};
+    int rc = hnsw_params(h, ctx, qs, n, k, ef, metric, any_filter ? h->d_bm.as<const uint64_t*>() : nullptr, force_global, nullptr, p);
+    if (rc) return rc;
+    p.key_row_offset = 0;
+    p.out_keys = reinterpret_cast<uint64_t*>(w + lay.o_keys);
+    p.out_count = reinterpret_cast<int32_t*>(w + lay.o_cnt);
+    p.out_status = reinterpret_cast<int32_t*>(w + lay.o_status);
+    p.out_visited = d_visited;
+    p.err = ctx->err_word();
+    HnswForestTasks ft{};
+    ft.graphs = f->d_graphs.as<const HnswGraphDesc>();
+    ft.task_query = d_tq;
+    ft.task_graph = d_tg;
+    ft.task_slot = d_slot;
+    HIPCHK(launch_hnsw_forest(h->format, p, ft, ctx->stream));
+    h->last_mode = p.vis_mode;
+    return VSR_OK;
+}
+
+static int forest_merge_launch(vsr_hnsw_forest* f, vsr_ctx* ctx, int nq, int k, uint32_t cap, int metric, const ForestLayout& lay, const Outputs& out)
+{
+    const vsr_hnsw* h = f->host;
+    char* w = f->d_tasks.as<char>();
+    HnswForestMergeParams mp{};
+    mp.q_off = reinterpret_cast<const int64_t*>(w + lay.o_off);
+    mp.task_keys = reinterpret_cast<const uint64_t*>(w + lay.o_keys);
+    mp.task_status = reinterpret_cast<const int32_t*>(w + lay.o_status);
+    mp.nq = (uint32_t) nq;
+    mp.k = (uint32_t) k;
+    mp.cap = cap;
+    mp.rows = h->format == RowFormat::BIT ? ROWS_BIT : h->format == RowFormat::HALF ? ROWS_HALF : ROWS_F32;
+    mp.metric = metric;
+    set_results(mp, h->corpus, out);
+    HIPCHK(launch_hnsw_forest_merge(mp, ctx->stream));
+    return VSR_OK;
+}
+
+// What every forest entry point checks; *n_tasks: the call's tasks, *cap: the merge's capacity
+static int forest_check(const HnswEntry& en, vsr_hnsw_forest* f, const void* queries, int nq, int dim, int k, int ef, int metric, const int64_t* q_off,
+                        const int32_t* q_graph, const vsr_filter* const* filters, size_t* n_tasks, uint32_t* cap)
+{
+    if (!f) return fail(VSR_ERR_INVALID, "%s: forest is NULL", en.who);
+    int rc;
+    if (f->host) {
+        if ((rc = hnsw_check(f->host, queries, nq, dim, k, ef, metric, filters, en.who, en.queries))) return rc;
+    } else if (nq < 0 || k < 1 || k > VSR_MAX_K)
+        return fail(VSR_ERR_INVALID, "%s: nq = %d, k = %d", en.who, nq, k);
+    char msg[160];
+    if (!hnsw_forest_check_tasks(nq, q_off, q_graph, (int) f->indexes.size(), msg, sizeof msg)) return fail(VSR_ERR_INVALID, "%s: %s", en.who, msg);
+    *n_tasks = (size_t) q_off[nq];
+    return forest_merge_keys(en.who, k, cap);
+}
+
+// queries resident at d_q: the task table's upload, the filters' bitmaps, (bit: the staging launch,) the search launch, the merge launch
+static int forest_enqueue(const HnswEntry& en, vsr_hnsw_forest* f, const void* d_q, int nq, int dim, int k, int ef, int metric, uint32_t cap,
+                          const int64_t* q_off, const int32_t* q_graph, const vsr_filter* const* filters, const ForestLayout& lay,
+                          const Outputs& out, int64_t* d_visited, HnswQueries& qs, bool& any_filter)
+{
+    vsr_hnsw* h = f->host;
+    vsr_ctx* ctx = h->corpus->ctx;
+    const size_t n_tasks = (size_t) q_off[nq];
+    int rc;
+    if (h->h_bm.p || f->h_tasks.p) HIPCHK(hipStreamSynchronize(ctx->stream));  // the pinned blocks of the previous call
+    if ((rc = f->d_tasks.reserve(lay.total))) return rc;
+    if ((rc = f->h_tasks.reserve(lay.o_keys))) return rc;
+    char* hp = f->h_tasks.as<char>();
+    char* w = f->d_tasks.as<char>();
+    memcpy(hp + lay.o_off, q_off, ((size_t) nq + 1) * 8);
+    int32_t* tq = reinterpret_cast<int32_t*>(hp + lay.o_tq);
+    for (int i = 0; i < nq; ++i)
+        for (int64_t t = q_off[i]; t < q_off[i + 1]; ++t) tq[t] = i;
+    if (n_tasks) memcpy(hp + lay.o_tg, q_graph, n_tasks * 4);
+    HIPCHK(hipMemcpyAsync(w, hp, lay.upload, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = hnsw_bitmaps(h, ctx, filters, nq, any_filter))) return rc;
+    if ((rc = en.resident(h, ctx, d_q, nq, dim, qs))) return rc;               // (bit: every QUERY staged once)
+    if ((rc = forest_search_launch(f, ctx, qs, any_filter, (int) n_tasks, reinterpret_cast<const int32_t*>(w + lay.o_tq),
+                                   reinterpret_cast<const int32_t*>(w + lay.o_tg), nullptr, false, k, ef, metric, lay, d_visited)))
+        return rc;
+    return forest_merge_launch(f, ctx, nq, k, cap, metric, lay, out);
+}
+
+// vsr_hnsw_forest_search_device / _bit_device: no synchronisation beyond the pinned blocks' reuse
+static int forest_search_device(const HnswEntry& en, vsr_hnsw_forest* f, const void* d_queries, int nq, int dim, int k, int ef, int metric,
+                                const int64_t* q_off, const int32_t* q_graph, const vsr_filter* const* filters, int64_t* d_blk, int32_t* d_doc,
+                                int64_t* d_row, float* d_dist, int32_t* d_cnt, int64_t* d_visited)
+{
+    size_t n_tasks = 0;
+    uint32_t cap = 0;
+    int rc = forest_check(en, f, d_queries, nq, dim, k, ef, metric, q_off, q_graph, filters, &n_tasks, &cap);
+    if (rc) return rc;
+    if (nq == 0) return VSR_OK;
+    if (!d_blk || !d_dist || !d_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", en.who);
+    if (!f->host) return fail(VSR_ERR_INVALID, "%s: an empty forest has no corpus, and so no stream to enqueue on (the host form answers)", en.who);
+    HIPCHK(hipSetDevice(f->host->corpus->ctx->device));
+    const ForestLayout lay(nq, n_tasks, k);
+    HnswQueries qs;
+    bool any_filter = false;
+    return forest_enqueue(en, f, d_queries, nq, dim, k, ef, metric, cap, q_off, q_graph, filters, lay, {d_blk, d_doc, d_row, d_dist, d_cnt, nullptr},
+                          d_visited, qs, any_filter);
+}
+
+// vsr_hnsw_forest_search / _bit: the device form over an upload of the queries, one copy back; the tasks whose LDS visited table
+// overflowed are run again with the global bitmap into their own slots, and every query is merged again
+static int forest_search_host(const HnswEntry& en, vsr_hnsw_forest* f, const void* queries, int nq, int dim, int k, int ef, int metric,
+                              const int64_t* q_off, const int32_t* q_graph, const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc,
+                              int64_t* out_row, float* out_dist, int32_t* out_cnt, int64_t* out_visited)
+{
+    size_t n_tasks = 0;
+    uint32_t cap = 0;
+    int rc = forest_check(en, f, queries, nq, dim, k, ef, metric, q_off, q_graph, filters, &n_tasks, &cap);
+    if (rc) return rc;
+    if (nq == 0) return VSR_OK;
+    if (!out_blk || !out_dist || !out_cnt) return fail(VSR_ERR_INVALID, "%s: output is NULL", en.who);
+    if (!f->host) {                                                          // an empty forest: no query has a task
+        for (size_t o = 0; o < (size_t) nq * k; ++o) {
+            out_blk[o] = -1;
+            if (out_doc) out_doc[o] = -1;
+            if (out_row) out_row[o] = -1;
+            out_dist[o] = INFINITY;
+        }
+        std::fill(out_cnt, out_cnt + nq, 0);
+        return VSR_OK;
+    }
+    vsr_hnsw* h = f->host;
+    if (h->format == RowFormat::HALF && (rc = half_query_range(queries, nq, dim))) return rc;
+    vsr_ctx* ctx = h->corpus->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    const ForestLayout lay(nq, n_tasks, k);
+    const ResultBlock rb(nq, k, false);
+    const size_t qbytes = en.bytes(dim), tail = lay.total - lay.o_status;     // [status | visited] of the tasks behind the results
+    if ((rc = h->d_q.reserve((size_t) nq * qbytes))) return rc;
+    if ((rc = h->d_out.reserve(rb.total))) return rc;
+    if ((rc = h->h_out.reserve(rb.total + tail))) return rc;
+    char* d = h->d_out.as<char>();
+    char* hh = h->h_out.as<char>();
+    HIPCHK(hipMemcpyAsync(h->d_q.p, queries, (size_t) nq * qbytes, hipMemcpyHostToDevice, ctx->stream));
+    HnswQueries qs;
+    bool any_filter = false;
+    if ((rc = f->d_tasks.reserve(lay.total))) return rc;                       // (forest_enqueue's own reservation then keeps the block)
+    char* w = f->d_tasks.as<char>();
+    int64_t* d_visited = reinterpret_cast<int64_t*>(w + lay.o_vis);
+    if ((rc = forest_enqueue(en, f, h->d_q.p, nq, dim, k, ef, metric, cap, q_off, q_graph, filters, lay, rb.arrays(d), d_visited, qs, any_filter)))
+        return rc;
+    const auto fetch = [&]() -> int {
+        HIPCHK(hipMemcpyAsync(hh, d, rb.total, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(hh + rb.total, w + lay.o_status, tail, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return VSR_OK;
+    };
+    if ((rc = fetch())) return rc;
+    const int32_t* status = reinterpret_cast<const int32_t*>(hh + rb.total);
+    std::vector<int32_t> redo;
+    for (size_t t = 0; t < n_tasks; ++t)
+        if (status[t]) redo.push_back((int32_t) t);
+    if (!redo.empty()) {
+        const size_t nr = redo.size(), sec4 = lay.sec / 4;
+        char* hp = f->h_tasks.as<char>();
+        const int32_t* tq = reinterpret_cast<const int32_t*>(hp + lay.o_tq);
+        int32_t* hr = reinterpret_cast<int32_t*>(hp + lay.o_redo);
+        for (size_t j = 0; j < nr; ++j) {
+            hr[j] = tq[redo[j]];
+            hr[sec4 + j] = q_graph[redo[j]];
+            hr[2 * sec4 + j] = redo[j];
+        }
+        HIPCHK(hipMemcpyAsync(w + lay.o_redo, hr, 3 * lay.sec, hipMemcpyHostToDevice, ctx->stream));
+        const int32_t* dr = reinterpret_cast<const int32_t*>(w + lay.o_redo);
+        if ((rc = forest_search_launch(f, ctx, qs, any_filter, (int) nr, dr, dr + sec4, dr + 2 * sec4, true, k, ef, metric, lay, d_visited)))
+            return rc;
+        // q_off went with the first upload and is still in place
+        if ((rc = forest_merge_launch(f, ctx, nq, k, cap, metric, lay, rb.arrays(d)))) return rc;
+        if ((rc = fetch())) return rc;
+    }
+    rb.copy_out_all(hh, {out_blk, out_doc, out_row, out_dist, out_cnt, nullptr}, nullptr);
+    if (out_visited && n_tasks) memcpy(out_visited, hh + rb.total + (lay.o_vis - lay.o_status), n_tasks * 8);
+    return VSR_OK;
+}
+
+extern "C" int vsr_hnsw_forest_search(vsr_hnsw_forest* f, const float* queries, int nq, int dim, int k, int ef, int metric, const int64_t* q_off,
+                                      const int32_t* q_graph, const vsr_filter* const* filters, int64_t* out_blk, int32_t* out_doc,
+                                      int64_t* out_row, float* out_dist, int32_t* out_cnt, int64_t* out_visited)
+{
+    return forest_search_host({"vsr_hnsw_forest_search", RowFormat::F32}, f, queries, nq, dim, k, ef, metric, q_off, q_graph, filters, out_blk,
+                              out_doc, out_row, out_dist, out_cnt, out_visited);
+}
+
+extern "C" int vsr_hnsw_forest_search_bit(vsr_hnsw_forest* f, const uint8_t* queries, int nq, int dim, int k, int ef, int metric,
+                                          const int64_t* q_off, const int32_t* q_graph, const vsr_filter* const* filters, int64_t* out_blk,
+                                          int32_t* out_doc, int64_t* out_row, float* out_dist, int32_t* out_cnt, int64_t* out_visited)
+{
+    return forest_search_host({"vsr_hnsw_forest_search_bit", RowFormat::BIT}, f, queries, nq, dim, k, ef, metric, q_off, q_graph, filters, out_blk,
+                              out_doc, out_row, out_dist, out_cnt, out_visited);
+}
+
+extern "C" int vsr_hnsw_forest_search_device(vsr_hnsw_forest* f, const float* d_queries, int nq, int dim, int k, int ef, int metric,
+                                             const int64_t* q_off, const int32_t* q_graph, const vsr_filter* const* filters, int64_t* d_blk,
+                                             int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt, int64_t* d_visited)
+{
+    return forest_search_device({"vsr_hnsw_forest_search_device", RowFormat::F32}, f, d_queries, nq, dim, k, ef, metric, q_off, q_graph, filters,
+                                d_blk, d_doc, d_row, d_dist, d_cnt, d_visited);
+}
+
+extern "C" int vsr_hnsw_forest_search_bit_device(vsr_hnsw_forest* f, const uint8_t* d_queries, int nq, int dim, int k, int ef, int metric,
+                                                 const int64_t* q_off, const int32_t* q_graph, const vsr_filter* const* filters, int64_t* d_blk,
+                                                 int32_t* d_doc, int64_t* d_row, float* d_dist, int32_t* d_cnt, int64_t* d_visited)
+{
+    return forest_search_device({"vsr_hnsw_forest_search_bit_device", RowFormat::BIT}, f, d_queries, nq, dim, k, ef, metric, q_off, q_graph, filters,
+                                d_blk, d_doc, d_row, d_dist, d_cnt, d_visited);
 }

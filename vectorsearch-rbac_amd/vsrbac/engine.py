@@ -587,6 +587,11 @@ class Corpus:
                                                   _metric(metric), int(seed), 0, handles))
         return [HnswIndex(self, C.c_void_p(handles[g])) for g in range(len(rows))]
 
+    def hnsw_forest(self, indexes):
+        """HnswForest over indexes of this corpus (the list build_hnsw_partitions returns, or any others of one row format and one
+        m): their graphs searched as a set, one search launch and one merge launch per call (vsr_hnsw_forest_open)."""
+        return HnswForest(indexes, corpus=self)
+
     def load_hnsw(self, graph):
         """HNSW graph over this corpus; `graph`: dict with m, entry, level, nbr0, tid_count, tids, up_slot, up_nbr,
         max_level (include/vsrbac.h, vsr_hnsw_load: what a dump of pgvector's in-memory build holds)."""
@@ -1341,3 +1346,106 @@ class HnswIndex:
                                                              int(max_scan_tuples), d_block, d_doc, d_rows, d_dist, d_counts,
                                                              d_tuples))
         return keep
+
+
+def _task_table(tasks, nq):
+    """(q_off int64 [nq + 1], q_graph int32 [q_off[nq]]) from one sequence of graph ids per query, or from a (q_off, q_graph) pair of
+    numpy arrays passed through as it is (the library checks it)."""
+    if isinstance(tasks, tuple) and len(tasks) == 2 and isinstance(tasks[0], np.ndarray):
+        off = np.ascontiguousarray(tasks[0], dtype=np.int64).reshape(-1)
+        if off.size != nq + 1:
+            raise ValueError("q_off has one entry per query and one more")
+        return off, np.ascontiguousarray(tasks[1], dtype=np.int32).reshape(-1)
+    if len(tasks) != nq:
+        raise ValueError("one sequence of graph ids per query")
+    lists = [np.asarray(t, dtype=np.int32).reshape(-1) for t in tasks]
+    off = np.zeros(nq + 1, dtype=np.int64)
+    np.cumsum([t.size for t in lists], out=off[1:])
+    flat = np.concatenate(lists) if lists else np.zeros(0, dtype=np.int32)
+    return off, np.ascontiguousarray(flat, dtype=np.int32)
+
+
+class HnswForest:
+    """Many HnswIndex over one corpus searched as a set (vsr_hnsw_forest_*): per query the graphs named in `tasks`, every
+    (query, graph) pair a wave of ONE search launch, the per-graph results merged on the GPU by (distance, document_id, block_id),
+    repeated rows dropped, the first k kept -- what HnswIndex.search on each graph plus a host merge gives.  `tasks`: one sequence
+    of graph ids (positions in `indexes`) per query, or a (q_off, q_graph) pair of arrays.  The forest keeps the indexes alive;
+    free() it before freeing them."""
+
+    def __init__(self, indexes, corpus=None):
+        self.indexes = list(indexes)
+        self.corpus = corpus if corpus is not None else (self.indexes[0].corpus if self.indexes else None)
+        self._lib = self.corpus._lib if self.corpus is not None else load_library()
+        arr = (C.c_void_p * max(len(self.indexes), 1))(*[h._h for h in self.indexes])
+        h = C.c_void_p()
+        check(self._lib.vsr_hnsw_forest_open(arr if self.indexes else None, len(self.indexes), C.byref(h)))
+        self._h = h
+
+    def free(self):
+        if getattr(self, "_h", None):
+            self._lib.vsr_hnsw_forest_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            if self.corpus is None or (self.corpus._h and self.corpus.ctx._h):
+                self.free()
+        except Exception:
+            pass
+
+    def set_predicate_aware(self, on=True):
+        """HnswIndex.set_predicate_aware for the searches of this forest (the indexes' own flags are not read)."""
+        check(self._lib.vsr_hnsw_forest_set_predicate_aware(self._h, 1 if on else 0))
+
+    def _filters(self, filters, nq):
+        return self.corpus._filter_array(filters, nq) if self.corpus is not None else (None, None)
+
+    def _host(self, fn, q, qdim, k, ef_search, metric, tasks, filters):
+        nq = q.shape[0]
+        off, graph = _task_table(tasks, nq)
+        farr, keep = self._filters(filters, nq)
+        kk = max(int(k), 1)
+        blk = np.full((nq, kk), -1, dtype=np.int64)
+        doc = np.full((nq, kk), -1, dtype=np.int32)
+        row = np.full((nq, kk), -1, dtype=np.int64)
+        dist = np.full((nq, kk), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.int32)
+        vis = np.zeros(max(int(off[-1]), 0), dtype=np.int64)
+        check(fn(self._h, _ptr(q), nq, qdim, int(k), int(ef_search), _metric(metric), _ptr(off), _ptr(graph), farr, _ptr(blk), _ptr(doc),
+                 _ptr(row), _ptr(dist), _ptr(cnt), _ptr(vis)))
+        del keep
+        return SearchResult(blk, doc, row, dist, cnt), vis
+
+    def search(self, queries, tasks, k, ef_search=40, metric="l2", filters=None):
+        """SearchResult plus the elements every TASK visited on layer 0, [q_off[nq]] (vsr_hnsw_forest_search)."""
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(queries, dtype=np.float32)))
+        return self._host(self._lib.vsr_hnsw_forest_search, q, q.shape[1], k, ef_search, metric, tasks, filters)
+
+    def search_bit(self, queries, tasks, k, ef_search=40, metric="hamming", filters=None, dim=None):
+        """search over a forest of bit indexes (vsr_hnsw_forest_search_bit): `queries` as HnswIndex.search_bit takes them."""
+        cdim = self.corpus.dim if self.corpus is not None else None
+        q, qdim = _packed_bits(queries, cdim if dim is None else dim, "search_bit")
+        return self._host(self._lib.vsr_hnsw_forest_search_bit, q, qdim, k, ef_search, metric, tasks, filters)
+
+    def _device(self, fn, d_queries, nq, dim, tasks, k, ef_search, metric, filters, d_block, d_doc, d_rows, d_dist, d_counts, d_visited):
+        off, graph = _task_table(tasks, nq)
+        farr, keep = self._filters(filters, nq)
+        check(fn(self._h, d_queries, nq, dim, int(k), int(ef_search), _metric(metric), _ptr(off), _ptr(graph), farr, d_block, d_doc,
+                 d_rows, d_dist, d_counts, d_visited))
+        return keep
+
+    def search_device(self, d_queries, nq, tasks, k, ef_search, metric, filters, d_block, d_doc, d_rows, d_dist, d_counts,
+                      d_visited=None):
+        """Device pointers (ints) for the queries and the outputs, `tasks` and `filters` on the host; one search launch and one
+        merge launch on the corpus context's stream, no synchronisation (vsr_hnsw_forest_search_device).  A query that owns a task
+        whose visited table overflowed reports count -1."""
+        return self._device(self._lib.vsr_hnsw_forest_search_device, d_queries, nq, self.corpus.dim if self.corpus is not None else 0, tasks,
+                            k, ef_search, metric, filters, d_block, d_doc, d_rows, d_dist, d_counts, d_visited)
+
+    def search_bit_device(self, d_queries, nq, tasks, k, ef_search, metric, filters, d_block, d_doc, d_rows, d_dist, d_counts,
+                          d_visited=None, dim=None):
+        """search_device over a forest of bit indexes: d_queries addresses nq x (dim + 7) // 8 packed bytes; one staging launch over
+        the queries in front of the two (vsr_hnsw_forest_search_bit_device)."""
+        cdim = self.corpus.dim if self.corpus is not None else 0
+        return self._device(self._lib.vsr_hnsw_forest_search_bit_device, d_queries, nq, cdim if dim is None else dim, tasks, k, ef_search,
+                            metric, filters, d_block, d_doc, d_rows, d_dist, d_counts, d_visited)

@@ -11,7 +11,9 @@ search functions over libvsrbac:
   search_documents_rls              controller/baseline/pg_row_security/row_level_security.py:98-160
   dynamic_partition_search          controller/dynamic_partition/search.py:31-111,347-364
 
-Every search is exact (recall 1.0): there is no ef_search / probes knob to trade recall for time.
+Every one of these three is exact (recall 1.0): there is no ef_search / probes knob to trade recall for time.  The reference's
+index route of the third -- one HNSW index per partition, searched per partition and merged -- is
+dynamic_partition_search_hnsw (and its batch form) over the graphs of build_partition_hnsw: approximate, with ef_search.
 """
 import json
 import time
@@ -106,6 +108,7 @@ class Deployment:
         self.comb_role_partitions = {}               # sorted role tuple -> [partition_id]
 
     def close(self):
+        self.close_partition_hnsw()
         self.corpus.free()
 
     # ---- result shaping --------------------------------------------------------------------
@@ -166,8 +169,8 @@ class Deployment:
         """One HNSW index per partition over the resident corpus, built in one call (Corpus.build_hnsw_partitions): the
         reference's create_indexes_for_all_role_tables without a table per partition.  partition_docs: {partition_id:
         [document_id, ...]} as load_partitions takes it (None: the partitions loaded); a partition's rows are the rows of its
-        documents.  Returns {partition_id: HnswIndex}, the caller's to free.  dynamic_partition_search does not go through
-        these graphs: it stays the exact scan."""
+        documents.  Returns {partition_id: HnswIndex}, the caller's to free.  use_partition_hnsw(graphs) makes them the graphs of
+        dynamic_partition_search_hnsw; dynamic_partition_search itself stays the exact scan."""
         docs = self.partitions if partition_docs is None else partition_docs
         if self.doc_ids is None:
             raise ValueError("partitions are sets of documents: the deployment was loaded without doc_ids")
@@ -208,6 +211,50 @@ class Deployment:
         for i in range(len(pids)):
             all_rows.extend(self._rows(res, i))
         return merge_results(all_rows, topk), secs
+
+    # ---- dynamic partitions through their HNSW graphs ------------------------------------------------
+    def use_partition_hnsw(self, graphs):
+        """graphs: {partition_id: HnswIndex} as build_partition_hnsw returns it.  Opens one HnswForest over them (the previous one
+        is freed); the indexes stay the caller's and must outlive the forest (close_partition_hnsw, or another use_partition_hnsw)."""
+        self.close_partition_hnsw()
+        pids = sorted(int(p) for p in graphs)
+        self._forest_slot = {p: i for i, p in enumerate(pids)}
+        self._forest = self.corpus.hnsw_forest([graphs[p] for p in pids])
+
+    def close_partition_hnsw(self):
+        if getattr(self, "_forest", None) is not None:
+            self._forest.free()
+        self._forest, self._forest_slot = None, {}
+
+    def dynamic_partition_search_hnsw_batch(self, user_ids, queries, topk=5, ef_search=40):
+        """Many users' queries in ONE forest call: query i is searched in the graph of every partition of user_ids[i]'s role
+        combination, under that user's BITMAP filter -- it admits every row of a pure partition and does the per-row test in an
+        impure one -- and the per-partition results are merged on the GPU as merge_results merges them (distance, then
+        (document_id, block_id); a row several partitions hold once).  Returns one list of the reference's 4-tuples per query."""
+        if getattr(self, "_forest", None) is None:
+            raise ValueError("no partition graphs: call use_partition_hnsw(build_partition_hnsw()) first")
+        qs = np.stack([parse_vector(q) for q in queries]) if len(queries) else np.zeros((0, self.corpus.dim), dtype=np.float32)
+        tasks, filters = [], []
+        for u in user_ids:
+            comb = tuple(sorted(self.user_roles.get(int(u), set())))
+            pids = sorted(set(self.comb_role_partitions.get(comb, [])))
+            missing = [p for p in pids if p not in self._forest_slot]
+            if missing:
+                raise ValueError(f"partitions {missing} have no graph in the forest")
+            tasks.append([self._forest_slot[p] for p in pids])
+            filters.append(self.corpus.filter_for_user(int(u), BITMAP))
+        if not len(user_ids):
+            return []
+        res, _ = self._forest.search(qs, tasks, topk, ef_search, self.metric, filters)
+        return [self._rows(res, i) for i in range(len(user_ids))]
+
+    def dynamic_partition_search_hnsw(self, user_id, query_vector, topk=5, statistics_type="sql", ef_search=40):
+        """dynamic_partition_search through the partitions' HNSW graphs (controller/dynamic_partition/search.py:31-111 with its
+        per-partition index scans): the batch form for one query.  Returns (rows, seconds); the graph search records no device
+        events, so both statistics types report the wall clock around the forest call."""
+        t = time.perf_counter()
+        rows = self.dynamic_partition_search_hnsw_batch([user_id], [query_vector], topk, ef_search)[0]
+        return rows, time.perf_counter() - t
 
     # ---- ground truth (exact scan; the reference's PostgreSQL seq-scan path, common_function.py:671-759) ----
     def ground_truth(self, user_id, query_vector, topk):
