@@ -601,7 +601,7 @@ void *orc_hnsw_build(int metric, const float *rows, int64_t n, int dim, int m, i
 }
 
 /* ---- the GPU's BATCHED build restated serially (vectorsearch-rbac_amd/csrc/vsr_hnsw_build.hip, the loop of hnsw_build in
- * vsr_hnsw_rt.hip).  Every piece is pgvector's, as above; what differs from orc_hnsw_build is the schedule:
+ * vsr_hnsw_build_rt.hip).  Every piece is pgvector's, as above; what differs from orc_hnsw_build is the schedule:
  *   elements   given by elem_row[n_elem] (element -> the row that holds its vector, ascending), with their heap TIDs; no
  *              opportunistic duplicate fold.  Levels: one draw per ROW in insertion order, an element takes its first row's.
  *   batches    max(1, min(done / 8, 4096, n_elem - done)) elements (batch_limit > 0: at most that many)

@@ -1,8 +1,8 @@
-"""What tests of vsr_hnsw_extend restate of the batched HNSW build (vsr_hnsw_rt.hip: hnsw_build_once): its batch schedule and its
+"""What tests of vsr_hnsw_extend restate of the batched HNSW build (vsr_hnsw_build_rt.hip: hnsw_build_once; vsr_hnsw_sizing.h): its batch schedule and its
 seeded level stream.  tests/test_hnsw_extend_cpu.py pins both to oracle.HnswIndex.batched before a GPU test leans on them."""
 import math
 
-BATCH_MAX = 4096                                          # HB_BATCH_MAX (vsr_hnsw_build.h)
+BATCH_MAX = 4096                                          # HB_BATCH_MAX (vsr_hnsw_sizing.h)
 _M64 = (1 << 64) - 1
 
 

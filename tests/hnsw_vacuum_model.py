@@ -19,7 +19,7 @@ import numpy as np
 
 from hnsw_iterative_model import rank_values
 
-BATCH_MAX = 4096                                          # HB_BATCH_MAX (vsr_hnsw_build.h)
+BATCH_MAX = 4096                                          # HB_BATCH_MAX (vsr_hnsw_sizing.h)
 
 
 class Graph:

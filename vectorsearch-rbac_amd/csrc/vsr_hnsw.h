@@ -56,6 +56,7 @@
 #include "vsr_bitops.h"
 #include "vsr_halfops.h"
 #include "vsr_sparseops.h"
+#include "vsr_hnsw_sizing.h"     // HN_LDS_BUDGET
 
 namespace vsr {
 
@@ -846,8 +847,6 @@ __global__ __launch_bounds__(256) void hnsw_half_iterative_kernel(const HnswPara
 // K4s: the search and the iterative scan over a sparse corpus
 __global__ __launch_bounds__(256) void hnsw_sparse_search_kernel(const HnswParams p) { hnsw_search_body<false, ROWS_SPARSE>(p); }
 __global__ __launch_bounds__(256) void hnsw_sparse_iterative_kernel(const HnswParams p) { hnsw_search_body<true, ROWS_SPARSE>(p); }
-
-constexpr size_t HN_LDS_BUDGET = 156 * 1024;   // of the CU's 160 KB (dynamic LDS of one workgroup)
 
 // (q_chunks: HnswParams::q_chunks, the rounded query of a K4h wave; 0 for every other kernel)
 inline size_t hnsw_lds_fixed(uint32_t caps, uint32_t q_chunks = 0)

@@ -1,21 +1,15 @@
-// vsr_hnsw_build.h -- parameters of the batched HNSW build (vsr_hnsw_build.hip), shared with the host loop in vsr_hnsw_rt.hip
+// vsr_hnsw_build.h -- parameters of the batched HNSW build (vsr_hnsw_build.hip), shared with the host loops in vsr_hnsw_build_rt.hip
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+#include "vsr_hnsw_sizing.h"               // HB_NBR, HB_BATCH_MAX, the HB_ERR_* guard-word bits
 
 namespace vsr {
 
-constexpr int HB_NBR = 256;                // neighbour ids of one expansion / one list (2m <= 200)
 constexpr int HB_TIDS = 10;                // heap TIDs of one element (HNSW_HEAPTIDS, hnsw.h:37)
-constexpr uint32_t HB_BATCH_MAX = 4096;    // elements of one batch
 constexpr int HB_SRC_BITS = 12;            // a reverse edge's sort key ends in its source's index in the batch (< HB_BATCH_MAX)
 constexpr int HB_KEY_BITS = 8 + 32 + HB_SRC_BITS;   // layer (<= 255) | target | source index: the bits the sort looks at
-constexpr uint32_t HB_ERR_VISITED = 16u;   // guard-word bit: a visited table filled up (hnsw_build restarts with a larger one)
-constexpr uint32_t HB_ERR_RECORDS = 32u;   // guard-word bit: reverse edges past rec_cap were dropped
-constexpr uint32_t HB_ERR_CANDIDATES = 64u;   // guard-word bit (sparse build): the candidate array dropped an unexpanded candidate as near as
-                                              // the furthest of W, which pgvector's unbounded heap would still expand (hnsw_build restarts
-                                              // with a longer array)
 
 struct HnswBuildParams {
     const float4*  rows = nullptr;           // corpus rows (internal order), zero padded to stride4 float4

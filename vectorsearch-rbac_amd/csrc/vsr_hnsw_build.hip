@@ -23,7 +23,7 @@
 // (CheckElementCloser's <=, keep-pruned-connections, which candidate counts as pruned, replace in place or append, and
 // SelectNeighbors returning a short candidate list as it came: furthest first).
 // A visited table that fills up ends the element's search early and sets HB_ERR_VISITED in the guard word; records past rec_cap
-// set HB_ERR_RECORDS.  hnsw_build (vsr_hnsw_rt.hip) reads the word after the last batch: it never returns such a graph.
+// set HB_ERR_RECORDS.  hnsw_build (vsr_hnsw_build_rt.hip) reads the word after the last batch: it never returns such a graph.
 // Levels come from the same seeded xorshift64* stream as the test suite's serial CPU restatement
 // (level = floor(-ln(u) / ln(m)), hnswutils.c:243), so both builds place the same elements on the same layers.
 // Identical vectors: pgvector folds a row whose vector equals a selected layer-0 neighbour's into that element's heap TIDs
@@ -988,7 +988,7 @@ __global__ __launch_bounds__(256) void hnsw_vacuum_renumber_kernel(const HnswBui
 // list of the prior graph: lists 0 .. n_prior - 1 are the layer-0 lists, the rest (slot, layer) pairs of the upper arrays, whose
 // owner comes from up_owner[slot] (-1: a slot no element names).  The ids go to the wave's LDS, hb_distances takes the owner's row
 // as the left operand, and the rank values land where phase 1 and the link kernel would have left them.  The host has bounded every
-// id the gather goes through (hnsw_extend_prepare, vsr_hnsw_rt.hip); waves are independent: no workgroup barrier ----
+// id the gather goes through (hnsw_extend_prepare, vsr_hnsw_build_rt.hip); waves are independent: no workgroup barrier ----
 template <bool IND, int ROWS>
 __global__ __launch_bounds__(256) void hnsw_edge_dist_kernel(const HnswBuildParams p, const uint32_t n_prior, const int32_t* __restrict__ up_owner,
                                                              const uint32_t n_upper_prior)
@@ -1100,7 +1100,7 @@ hipError_t vsr_hnsw_edge_distances(const HnswBuildParams& p, uint32_t n_prior, c
                       : edge_distances<false, ROWS_F32>(p, n_prior, d_up_owner, n_upper_prior, s);
 }
 
-// host side: see vsr_hnsw_rt.hip (vsr_hnsw_build) for the batch loop; these are the two launches and the sort of a batch
+// host side: see vsr_hnsw_build_rt.hip (vsr_hnsw_build) for the batch loop; these are the two launches and the sort of a batch
 template <bool IND, int ROWS>
 static hipError_t build_batch(HnswBuildParams& p, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt, uint64_t* d_val_alt, hipStream_t s)
 {

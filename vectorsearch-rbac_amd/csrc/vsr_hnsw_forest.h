@@ -1,8 +1,8 @@
-// vsr_hnsw_forest.h -- the schedule of vsr_hnsw_build_partitions (vsr_hnsw_rt.hip): the batches of many HNSW builds packed into
+// vsr_hnsw_forest.h -- the schedule of vsr_hnsw_build_partitions (vsr_hnsw_build_rt.hip): the batches of many HNSW builds packed into
 // shared rounds.  Plain C++, no HIP call: tests/test_hnsw_forest_cpu.py compiles this file alone with the host compiler.
 //
 // All partitions live in one global element space: partition g owns elements base[g] .. base[g + 1] - 1.  Every partition keeps
-// the build's own schedule (hnsw_build_once: a batch of max(1, min(done / 8, batch_max, left)) elements, done from 0) and the
+// the build's own schedule (hnsw_build_batch, vsr_hnsw_sizing.h: max(1, min(done / 8, batch_max, left)) elements, done from 0) and the
 // build's own entry-point rule (HnswUpdateGraphInMemory: after a batch, the first element above the entry's level takes over,
 // the first element of all when there is no entry yet).  A ROUND walks the unfinished partitions in ascending index and takes
 // each one's next batch while the round's elements stay within `cap`; a partition whose batch does not fit waits for the next
@@ -19,10 +19,9 @@
 #include <cstddef>
 #include <cstdint>
 #include <vector>
+#include "vsr_hnsw_sizing.h"                 // the build's batch rule and record capacity
 
 namespace vsr {
-
-constexpr uint32_t HF_BATCH_MAX = 4096;      // elements of one batch of the build (HB_BATCH_MAX, vsr_hnsw_build.h)
 
 struct HnswForestRound {
     uint64_t first_slot = 0;                 // where the round's elements begin in the slot arrays
@@ -39,14 +38,8 @@ struct HnswForestPlan {
     std::vector<int32_t> final_entry;        // [n_parts] global entry point of every finished graph, -1 for an empty partition
 };
 
-// the build's batch: what follows `done` inserted elements of n
-inline int64_t hnsw_forest_batch(int64_t done, int64_t n)
-{
-    return std::max<int64_t>(1, std::min<int64_t>({done / 8, (int64_t) HF_BATCH_MAX, n - done}));
-}
-
 // base[n_parts + 1]: ascending, base[0] = 0, base[n_parts] < 2^31; level[base[n_parts]]: the level of every global element;
-// cap: 1 .. HF_BATCH_MAX.  Returns false when a round's record capacity would pass 2^31 - 1 (the plan is then unusable).
+// cap: 1 .. HB_BATCH_MAX.  Returns false when a round's record capacity would pass 2^31 - 1 (the plan is then unusable).
 inline bool hnsw_forest_plan(int n_parts, const int64_t* base, const int32_t* level, int m, uint32_t cap, HnswForestPlan& plan)
 {
     const size_t total = n_parts > 0 ? (size_t) base[n_parts] : 0;
@@ -68,13 +61,13 @@ inline bool hnsw_forest_plan(int n_parts, const int64_t* base, const int32_t* le
         taken.clear();
         for (int g : open) {
             const int64_t n = base[g + 1] - base[g];
-            const int64_t b = hnsw_forest_batch(done[(size_t) g], n);
+            const int64_t b = hnsw_build_batch(done[(size_t) g], n);
             if (r.count > 0 && (uint64_t) r.count + (uint64_t) b > cap) continue;   // waits for the next round
             for (int64_t e = base[g] + done[(size_t) g]; e < base[g] + done[(size_t) g] + b; ++e) {
                 plan.elems.push_back((int32_t) e);
                 plan.entry.push_back(plan.final_entry[(size_t) g]);
                 plan.entry_level.push_back(ent_level[(size_t) g]);
-                rec += (uint64_t) (2 * m + level[(size_t) e] * m);
+                rec += hnsw_rec_cap(m, level[(size_t) e]);
             }
             r.count += (uint32_t) b;
             ++r.batches;
@@ -87,7 +80,7 @@ inline bool hnsw_forest_plan(int n_parts, const int64_t* base, const int32_t* le
         // the entry points move when the round is over: its elements did not see each other
         for (int g : taken) {
             const int64_t n = base[g + 1] - base[g];
-            const int64_t b = hnsw_forest_batch(done[(size_t) g], n);
+            const int64_t b = hnsw_build_batch(done[(size_t) g], n);
             for (int64_t e = base[g] + done[(size_t) g]; e < base[g] + done[(size_t) g] + b; ++e)
                 if (plan.final_entry[(size_t) g] < 0 || level[(size_t) e] > ent_level[(size_t) g]) {
                     plan.final_entry[(size_t) g] = (int32_t) e;
