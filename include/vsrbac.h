@@ -696,13 +696,50 @@ int vsr_hnsw_vacuum(vsr_corpus* corpus, int m, int32_t n_elem, int32_t entry, co
  *     corpus: VSR_ERR_UNSUPPORTED, the message names sparsevec (the sparse build has no element -> row form).  flags must be 0:
  *     VSR_HNSW_BUILD_MERGE_DUPLICATES is VSR_ERR_UNSUPPORTED, any other bit VSR_ERR_INVALID.
  *   - On failure every index made so far is freed and every out[g] is NULL.  The session's guard word is left as it was found.
- * Not covered: extending or vacuuming a partition graph in place (export it and use vsr_hnsw_extend / vsr_hnsw_vacuum).  The graphs of
- * a query's partitions are searched as a set by vsr_hnsw_forest_search* below.  Synchronises. */
+ * Not covered: vacuuming a partition graph in place (export it and use vsr_hnsw_vacuum).  New rows go into many partition graphs with
+ * vsr_hnsw_extend_partitions below.  The graphs of a query's partitions are searched as a set by vsr_hnsw_forest_search*.  Synchronises. */
 int vsr_hnsw_build_partitions(vsr_corpus* corpus, int n_parts,
                               const int64_t* part_off  /* [n_parts + 1], ascending, part_off[0] = 0 */,
                               const int64_t* part_rows /* [part_off[n_parts]] caller row indices */,
                               int m, int ef_construction, int metric, uint64_t seed, uint32_t flags,
                               vsr_hnsw** out /* [n_parts] */);
+/* vsr_hnsw_extend for many graphs over ONE resident corpus in one call: partition g's graph prior[g] takes the caller rows
+ * new_rows[new_off[g] .. new_off[g + 1]) -- a role was granted documents, new documents arrived -- and out[g] is the new index.
+ *   - prior[g] is any index over `corpus` (from vsr_hnsw_build_partitions, from this call, from vsr_hnsw_load*, ...); NULL or an index of
+ *     n_elem = 0 is the empty graph.  Two partitions may name one prior index.  The priors are read on the device, are not modified and
+ *     stay the caller's.  All priors share one m, which the call takes from them: when every prior[g] is NULL, m is not known and the
+ *     call is refused with VSR_ERR_INVALID (such graphs are vsr_hnsw_build_partitions').
+ *   - Partitions may share rows; within ONE partition a row named twice, or a row outside [0, rows), is VSR_ERR_INVALID naming the
+ *     partition and the position, and a new row that the prior graph already holds under a heap TID is VSR_ERR_INVALID naming the
+ *     partition and the row.
+ *   - out[g] is, array for array in its export, what vsr_hnsw_extend(ef_construction, metric, seed) makes of export(prior[g]) over a
+ *     corpus that holds only graph g's rows, old and new, with their (document_id, block_id), TIDs mapped there and back: prior
+ *     elements keep ids, TID lists, levels and upper slots; the new rows become elements n_elem + i in ascending internal
+ *     (document_id, block_id) order with one TID each; the i-th takes level draw n0 + i, n0 being the prior's heap TIDs; batches are the
+ *     build's from done = n_elem, with the build's entry-point rule; new upper slots continue after the prior ones and the upper
+ *     arrays are re-strided when the top level rises.  So priors that are vsr_hnsw_build_partitions graphs of prefixes ending at batch
+ *     boundaries, extended with the build's seed, give the graphs vsr_hnsw_build_partitions makes of the full partitions.
+ *     A partition without new rows gets an index whose export equals its prior's.  n_parts = 0 succeeds and writes nothing.
+ *   - How: the graphs that take rows are joined on the device into the global element space of vsr_hnsw_build_partitions, the prior
+ *     edges' distances are recomputed there, and the rounds, VSR_HNSW_FOREST_BATCH, VSR_HNSW_BUILD_VISITED_SLOTS and the restart (from
+ *     the priors, with twice the visited slots) are that call's.
+ *   - An index this library made (build, build_partitions, extend, extend_partitions, vacuum) is written through as it is.  Any other
+ *     prior that takes rows is first brought to the host and put through vsr_hnsw_extend's checks; a failure is VSR_ERR_INVALID naming
+ *     the partition, and nothing is launched.  The result of a partition WITHOUT new rows is a plain copy that nobody read: it counts as
+ *     made by this library only if its prior did, so the copy of a loaded index is checked like the loaded index when a later call gives
+ *     it rows.
+ *   - metric, ef_construction against m, halfvec dimension, a view corpus: the rules and refusals of vsr_hnsw_extend; on a bit corpus
+ *     metric must be the priors' opclass.  A sparse corpus: VSR_ERR_UNSUPPORTED, the message names sparsevec.  flags must be 0:
+ *     VSR_HNSW_BUILD_MERGE_DUPLICATES is VSR_ERR_UNSUPPORTED, any other bit VSR_ERR_INVALID.  A prior over another corpus, of another
+ *     row format, m or bit opclass: VSR_ERR_INVALID naming the partition.
+ *   - On failure every index made so far is freed and every out[g] is NULL.  The session's guard word is left as it was found.
+ * Not covered: vacuuming many partitions in one call, changing a prior in place, appending rows to the resident corpus.  Synchronises. */
+int vsr_hnsw_extend_partitions(vsr_corpus* corpus, int n_parts,
+                               vsr_hnsw* const* prior   /* [n_parts], an entry may be NULL */,
+                               const int64_t* new_off   /* [n_parts + 1], ascending from 0 */,
+                               const int64_t* new_rows  /* [new_off[n_parts]] caller row indices */,
+                               int ef_construction, int metric, uint64_t seed, uint32_t flags,
+                               vsr_hnsw** out           /* [n_parts] */);
 /* A FOREST: many indexes over ONE corpus (the graphs of vsr_hnsw_build_partitions, or any others) searched as a set -- what the
  * reference's dynamic_partition_search does with the HNSW indexes of a user's role combination: search each, merge by distance, drop the
  * rows several partitions hold, keep k.  Here: ONE search launch over all (query, graph) pairs of the call and ONE merge launch.

@@ -33,7 +33,7 @@ import numpy as np  # noqa: E402
 M, EFC, DIM = 16, 64, 128
 HBM_SPEC_BYTES_PER_S = 8e12
 NEW_SYMBOLS = ("vsr_hnsw_build_ex", "vsr_hnsw_export_shape", "vsr_hnsw_export", "vsr_hnsw_extend", "vsr_hnsw_vacuum",
-               "vsr_hnsw_vacuum_spill_info", "vsr_hnsw_build_partitions")
+               "vsr_hnsw_vacuum_spill_info", "vsr_hnsw_build_partitions", "vsr_hnsw_extend_partitions")
 
 
 def corpus_rows(n, kind, seed):

@@ -33,7 +33,7 @@ import numpy as np  # noqa: E402
 
 M, EFC, DIM = 16, 64, 128
 SHAPES = [(100, 10_000), (10, 100_000), (1000, 1000)]       # (partitions, rows each)
-NEW_SYMBOLS = ("vsr_hnsw_build_partitions",)                  # what the parent commit's library does not export
+NEW_SYMBOLS = ("vsr_hnsw_build_partitions", "vsr_hnsw_extend_partitions")   # what an older library given with --parent-lib may lack
 
 
 def corpus_rows(n, seed):

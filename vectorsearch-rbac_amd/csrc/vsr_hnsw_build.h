@@ -80,6 +80,27 @@ struct HnswForestGraph {
     int32_t max_level = 1;                   // its own stride of the upper lists
 };
 
+// vsr_hnsw_extend_partitions: the prior graph of forest graph i (d_priors[i] beside d_graphs[i]), the device arrays of the index it
+// lives in.  n_elem = 0: no prior graph, the pointers are not read
+struct HnswForestPrior {
+    const int32_t *level = nullptr, *elem_row = nullptr, *nbr0 = nullptr, *up_slot = nullptr, *up_nbr = nullptr, *tid_count = nullptr,
+                  *tids = nullptr;
+    int32_t n_elem = 0;                      // the graph's first n_elem elements are the prior's, in its numbering
+    int32_t n_upper = 0, max_level = 1;      // its upper slots (the graph's first n_upper) and the stride of its upper lists
+};
+// what the join launches write beside p.nbr0 / p.up_nbr: the per-element arrays p reads, the slot -> owner table of the edge-distance
+// launch, and two result words
+struct HnswForestJoin {
+    int32_t *level = nullptr, *elem_row = nullptr, *up_slot = nullptr;   // [n_total]; the new elements' entries are the host's
+    int32_t* up_owner = nullptr;             // [all upper slots], -1 filled by the caller
+    uint32_t n_rows = 0;                     // rows of the corpus: what an element's row and a heap TID are bounded by
+    uint32_t* bad = nullptr;                 // min over the graphs with a prior array that held a value outside its range of the graph's
+                                             // index (the element was joined as a level-0 element without edges; the caller throws the
+                                             // attempt away); all ones: none
+    unsigned long long* held = nullptr;      // min over the prior heap TIDs that name a new row of their graph of (graph index << 32) | row;
+                                             // all ones: none
+};
+
 // one workspace of the spill form for a graph of n elements: C, W and T (8 bytes an element each), wd (4) and the visited bitmap
 inline size_t hnsw_vacuum_spill_ws_bytes(uint32_t n)
 {
@@ -117,6 +138,15 @@ hipError_t vsr_hnsw_forest_round(vsr::HnswBuildParams& p, const vsr::HnswForestP
 // the graph's max_level, one heap TID per element.  d_graphs[n_graphs]: the non-empty graphs, ascending base, covering 0 .. n_total - 1
 hipError_t vsr_hnsw_forest_split(const vsr::HnswBuildParams& p, const vsr::HnswForestGraph* d_graphs, uint32_t n_graphs, uint32_t n_total,
                                  hipStream_t s);
+// vsr_hnsw_extend_partitions.  The inverse of the split, for the graphs that arrive (two launches on s): every prior graph's arrays
+// into the global ones -- ids plus base, upper slots plus slot_base, upper lists at the global stride p.max_level, j.up_owner --
+// and j.held.  The caller has filled p.nbr0 / p.up_nbr / j.up_owner with -1 and written the new elements' level, row (ascending within
+// a graph) and upper slot.  d_graphs[i].n_elem counts prior and new elements; the output pointers of d_graphs are not read
+hipError_t vsr_hnsw_forest_join(const vsr::HnswBuildParams& p, const vsr::HnswForestJoin& j, const vsr::HnswForestGraph* d_graphs,
+                                const vsr::HnswForestPrior* d_priors, uint32_t n_graphs, uint32_t n_total, hipStream_t s);
+// vsr_hnsw_forest_split for joined graphs: a prior element keeps the heap TIDs of d_priors, a new one holds its row alone
+hipError_t vsr_hnsw_forest_split_carry(const vsr::HnswBuildParams& p, const vsr::HnswForestGraph* d_graphs, const vsr::HnswForestPrior* d_priors,
+                                       uint32_t n_graphs, uint32_t n_total, hipStream_t s);
 // vsr_hnsw_vacuum.  One repair batch (p.count <= HB_BATCH_MAX elements, v.elems): the searches into v.stage_*, the install launch,
 // the sort and the link launch, all on s.  The selection's scratch lies over the visited table (hash_slots / 3 candidates).
 // With v.spill_pool > 0 the spill launch runs between the searches and the install: over the repairs the LDS launch listed

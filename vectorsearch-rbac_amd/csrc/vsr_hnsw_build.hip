@@ -63,6 +63,11 @@
 // launch are the build's, which act on each graph as its own would because targets of different graphs are disjoint.
 // hnsw_forest_split_kernel then writes every graph's own arrays.  fp32, halfvec and bit rows; tests/test_gpu_hnsw_partitions.py.
 //
+// Partitions that exist (vsr_hnsw_extend_partitions): the extension of many graphs in that element space.  hnsw_forest_join_kernel is
+// the split's inverse for the prior graphs, hnsw_forest_held_kernel looks every prior heap TID up among its graph's new rows,
+// hnsw_edge_dist_kernel runs over all elements, the rounds are the partition build's from done = the prior n_elem, and
+// hnsw_forest_split_kernel<true> carries the prior TID lists over.  tests/test_gpu_hnsw_extend_partitions.py.
+//
 // Parity definition (tests/test_gpu_index.py): recall@20 at ef_search = 40 against the exact scan >= pgvector's TAP
 // thresholds on its own case (10 000 x 3-d: 0.99; inner product 0.97), and within 0.01 of that serial build's recall on
 // the same rows; and (tests/test_gpu_hnsw_build_model.py) graph identity with the batched model, as above.
@@ -987,8 +992,11 @@ __global__ __launch_bounds__(256) void hnsw_vacuum_renumber_kernel(const HnswBui
 // ---- extension (vsr_hnsw_extend): the per-edge distances of a graph that arrived without them.  One wave per (element, layer)
 // list of the prior graph: lists 0 .. n_prior - 1 are the layer-0 lists, the rest (slot, layer) pairs of the upper arrays, whose
 // owner comes from up_owner[slot] (-1: a slot no element names).  The ids go to the wave's LDS, hb_distances takes the owner's row
-// as the left operand, and the rank values land where phase 1 and the link kernel would have left them.  The host has bounded every
-// id the gather goes through (hnsw_extend_prepare, vsr_hnsw_build_rt.hip); waves are independent: no workgroup barrier ----
+// as the left operand, and the rank values land where phase 1 and the link kernel would have left them.  Every id the gather goes
+// through has been bounded before this launch: by the host for arrays that came from a caller (hnsw_extend_prepare,
+// vsr_hnsw_build_rt.hip), by hnsw_forest_join_kernel for the prior indexes of vsr_hnsw_extend_partitions, which stay on the device
+// (ids into [base, base + n_elem) of their graph, rows into the corpus, slots into the graph's own).  Waves are independent: no
+// workgroup barrier ----
 template <bool IND, int ROWS>
 __global__ __launch_bounds__(256) void hnsw_edge_dist_kernel(const HnswBuildParams p, const uint32_t n_prior, const int32_t* __restrict__ up_owner,
                                                              const uint32_t n_upper_prior)
@@ -1037,9 +1045,12 @@ __global__ __launch_bounds__(256) void hnsw_edge_dist_kernel(const HnswBuildPara
 // graph is the last one whose base is <= e (graphs[] holds the non-empty graphs in ascending base).  Ids lose the graph's base,
 // upper slots its slot_base (slots were numbered in global element order, so a graph's are a run), the upper lists go from the
 // global stride p.max_level to the graph's own max_level (layers above an element's level hold -1 in both), and the element's
-// one heap TID is its row.  Waves are independent: no workgroup barrier ----
+// one heap TID is its row.  CARRY (vsr_hnsw_extend_partitions): the graph's first priors[].n_elem elements keep the heap TIDs of the
+// prior index, count and list; priors is not read without it.  Waves are independent: no workgroup barrier ----
+template <bool CARRY>
 __global__ __launch_bounds__(256) void hnsw_forest_split_kernel(const HnswBuildParams p, const HnswForestGraph* __restrict__ graphs,
-                                                                const uint32_t n_graphs, const uint32_t n_total)
+                                                                const uint32_t n_graphs, const uint32_t n_total,
+                                                                const HnswForestPrior* __restrict__ priors)
 {
     const int lane = threadIdx.x & 63;
     const uint32_t e = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1053,13 +1064,21 @@ __global__ __launch_bounds__(256) void hnsw_forest_split_kernel(const HnswBuildP
     const uint32_t le = e - (uint32_t) g.base;
     if (le >= (uint32_t) g.n_elem) return;                                    // (cannot happen: the graphs cover 0 .. n_total - 1)
     const int32_t row = p.elem_row[e], slot = p.up_slot[e];
+    int32_t tid_count = 1, tid = lane == 0 ? row : -1;
+    if (CARRY) {
+        const HnswForestPrior pr = priors[lo];
+        if (le < (uint32_t) pr.n_elem) {
+            tid_count = min(max(pr.tid_count[le], 1), HB_TIDS);
+            tid = lane < tid_count ? pr.tids[(size_t) le * HB_TIDS + lane] : -1;
+        }
+    }
     if (lane == 0) {
         g.level[le] = p.level[e];
         g.elem_row[le] = row;
         g.up_slot[le] = slot >= 0 ? slot - g.slot_base : -1;
-        g.tid_count[le] = 1;
+        g.tid_count[le] = tid_count;
     }
-    if (lane < HB_TIDS) g.tids[(size_t) le * HB_TIDS + lane] = lane == 0 ? row : -1;
+    if (lane < HB_TIDS) g.tids[(size_t) le * HB_TIDS + lane] = tid;
     for (uint32_t j = (uint32_t) lane; j < 2 * p.m; j += 64) {
         const int32_t id = p.nbr0[(size_t) e * 2 * p.m + j];
         g.nbr0[(size_t) le * 2 * p.m + j] = id >= 0 ? id - g.base : -1;
@@ -1069,6 +1088,93 @@ __global__ __launch_bounds__(256) void hnsw_forest_split_kernel(const HnswBuildP
     for (uint32_t j = (uint32_t) lane; j < (uint32_t) g.max_level * p.m; j += 64) {   // (g.max_level <= p.max_level)
         const int32_t id = p.up_nbr[from + j];
         g.up_nbr[to + j] = id >= 0 ? id - g.base : -1;
+    }
+}
+
+// the graph of global element e: the last one whose base is <= e (graphs[] ascends in base and covers 0 .. n_total - 1)
+__device__ __forceinline__ uint32_t hb_forest_graph_of(const HnswForestGraph* __restrict__ graphs, uint32_t n_graphs, uint32_t e)
+{
+    uint32_t lo = 0, hi = n_graphs;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if ((uint32_t) graphs[mid].base <= e) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// ---- partitions that exist already (vsr_hnsw_extend_partitions): the split's inverse.  One wave per global element e; only the
+// first priors[].n_elem elements of a graph have anything to bring, the rest are the rows to insert and were written by the host.
+// Ids gain the graph's base, upper slots its slot_base, the upper lists go from the prior's own stride to the global one (the
+// layers above it were filled with -1), and the slot's owner is noted for the edge-distance launch.  Every value read from a prior
+// array is bounded before it becomes an address, here or in a later launch: an element with a value out of range is joined as a
+// level-0 element of row 0 without edges and j.bad takes its graph's index.  Waves are independent: no workgroup barrier ----
+__global__ __launch_bounds__(256) void hnsw_forest_join_kernel(const HnswBuildParams p, const HnswForestJoin j,
+                                                               const HnswForestGraph* __restrict__ graphs,
+                                                               const HnswForestPrior* __restrict__ priors, const uint32_t n_graphs,
+                                                               const uint32_t n_total)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t e = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (e >= n_total) return;
+    const uint32_t gi = hb_forest_graph_of(graphs, n_graphs, e);
+    const HnswForestGraph g = graphs[gi];
+    const HnswForestPrior pr = priors[gi];
+    const uint32_t le = e - (uint32_t) g.base;
+    if (le >= (uint32_t) pr.n_elem || le >= (uint32_t) g.n_elem) return;
+    int32_t lev = pr.level[le], slot = pr.up_slot[le], row = pr.elem_row[le];
+    const bool ok = lev >= 0 && lev <= pr.max_level && (uint32_t) pr.max_level <= p.max_level && row >= 0 && (uint32_t) row < j.n_rows &&
+                    (lev >= 1 ? slot >= 0 && slot < pr.n_upper : slot == -1);
+    bool bad = !ok;
+    if (!ok) { lev = 0; slot = -1; row = 0; }
+    if (lane == 0) {
+        j.level[e] = lev;
+        j.elem_row[e] = row;
+        j.up_slot[e] = slot >= 0 ? slot + g.slot_base : -1;
+        if (slot >= 0) j.up_owner[slot + g.slot_base] = (int32_t) e;
+    }
+    if (ok) {
+        for (uint32_t i = (uint32_t) lane; i < 2 * p.m; i += 64) {
+            const int32_t id = pr.nbr0[(size_t) le * 2 * p.m + i];
+            bad |= id < -1 || id >= pr.n_elem;
+            p.nbr0[(size_t) e * 2 * p.m + i] = id >= 0 && id < pr.n_elem ? id + g.base : -1;
+        }
+        if (slot >= 0) {
+            const size_t from = (size_t) slot * (uint32_t) pr.max_level * p.m, to = (size_t) (slot + g.slot_base) * p.max_level * p.m;
+            for (uint32_t i = (uint32_t) lane; i < (uint32_t) pr.max_level * p.m; i += 64) {   // (pr.max_level <= p.max_level: checked above)
+                const int32_t id = pr.up_nbr[from + i];
+                bad |= id < -1 || id >= pr.n_elem;
+                p.up_nbr[to + i] = id >= 0 && id < pr.n_elem ? id + g.base : -1;
+            }
+        }
+    }
+    if (bad) atomicMin(j.bad, gi);
+}
+
+// "already held": one thread per prior element; each of its heap TIDs is looked up among the graph's new rows, which lie ascending in
+// p.elem_row behind the prior elements.  The least (graph, row) found stays in j.held
+__global__ __launch_bounds__(256) void hnsw_forest_held_kernel(const HnswBuildParams p, const HnswForestJoin j,
+                                                               const HnswForestGraph* __restrict__ graphs,
+                                                               const HnswForestPrior* __restrict__ priors, const uint32_t n_graphs,
+                                                               const uint32_t n_total)
+{
+    const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_total) return;
+    const uint32_t gi = hb_forest_graph_of(graphs, n_graphs, e);
+    const HnswForestGraph g = graphs[gi];
+    const HnswForestPrior pr = priors[gi];
+    const uint32_t le = e - (uint32_t) g.base;
+    if (le >= (uint32_t) pr.n_elem || le >= (uint32_t) g.n_elem) return;
+    const int32_t* fresh = p.elem_row + (size_t) g.base + (uint32_t) pr.n_elem;
+    const uint32_t n_fresh = (uint32_t) (g.n_elem - pr.n_elem);
+    const int cnt = min(max(pr.tid_count[le], 0), HB_TIDS);
+    for (int t = 0; t < cnt; ++t) {
+        const int32_t row = pr.tids[(size_t) le * HB_TIDS + t];
+        uint32_t lo = 0, hi = n_fresh;                                        // the first new row >= row
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (fresh[mid] < row) lo = mid + 1; else hi = mid;
+        }
+        if (lo < n_fresh && fresh[lo] == row && row >= 0) atomicMin(j.held, ((unsigned long long) gi << 32) | (uint32_t) row);
     }
 }
 
@@ -1194,7 +1300,32 @@ hipError_t vsr_hnsw_forest_split(const HnswBuildParams& p, const HnswForestGraph
 {
     if (n_total == 0) return hipSuccess;
     if (!d_graphs || n_graphs == 0 || !p.elem_row) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(hnsw_forest_split_kernel, dim3((n_total + 3) / 4), dim3(256), 0, s, p, d_graphs, n_graphs, n_total);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_forest_split_kernel<false>), dim3((n_total + 3) / 4), dim3(256), 0, s, p, d_graphs, n_graphs, n_total,
+                       (const HnswForestPrior*) nullptr);
+    return hipGetLastError();
+}
+
+hipError_t vsr_hnsw_forest_split_carry(const HnswBuildParams& p, const HnswForestGraph* d_graphs, const HnswForestPrior* d_priors, uint32_t n_graphs,
+                                       uint32_t n_total, hipStream_t s)
+{
+    if (n_total == 0) return hipSuccess;
+    if (!d_graphs || !d_priors || n_graphs == 0 || !p.elem_row) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_forest_split_kernel<true>), dim3((n_total + 3) / 4), dim3(256), 0, s, p, d_graphs, n_graphs, n_total,
+                       d_priors);
+    return hipGetLastError();
+}
+
+hipError_t vsr_hnsw_forest_join(const HnswBuildParams& p, const HnswForestJoin& j, const HnswForestGraph* d_graphs, const HnswForestPrior* d_priors,
+                                uint32_t n_graphs, uint32_t n_total, hipStream_t s)
+{
+    if (n_total == 0) return hipSuccess;
+    if (!d_graphs || !d_priors || n_graphs == 0 || !p.elem_row || !p.nbr0 || !p.up_nbr || !j.level || !j.elem_row || !j.up_slot || !j.up_owner ||
+        !j.bad || !j.held)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(hnsw_forest_join_kernel, dim3((n_total + 3) / 4), dim3(256), 0, s, p, j, d_graphs, d_priors, n_graphs, n_total);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(hnsw_forest_held_kernel, dim3((n_total + 255) / 256), dim3(256), 0, s, p, j, d_graphs, d_priors, n_graphs, n_total);
     return hipGetLastError();
 }
 

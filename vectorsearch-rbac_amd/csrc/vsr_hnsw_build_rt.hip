@@ -1,5 +1,5 @@
 // vsr_hnsw_build_rt.hip — the host side of everything that makes an HNSW graph on the GPU: vsr_hnsw_build / _ex / _bit / _half /
-// _sparse, vsr_hnsw_extend, vsr_hnsw_build_partitions and vsr_hnsw_vacuum.  No device code: the kernels are in vsr_hnsw_build.hip
+// _sparse, vsr_hnsw_extend, vsr_hnsw_build_partitions, vsr_hnsw_extend_partitions and vsr_hnsw_vacuum.  No device code: the kernels are in vsr_hnsw_build.hip
 // and vsr_hnsw_dedup.hip, what is decided without a GPU in vsr_hnsw_sizing.h and vsr_hnsw_forest.h, the index object and its load
 // in vsr_hnsw_index.h / vsr_hnsw_rt.hip.  Every call is attempts under a ladder: an attempt (hnsw_build_once, hnsw_forest_once,
 // hnsw_vacuum_once) runs the whole call from the caller's arrays with `slots` visited-table entries and `caps` candidates; when a
@@ -405,7 +405,7 @@ static int hnsw_build_once(vsr_corpus* c, RowFormat expect, int m, int ef_constr
             (rc = upload_i32(&h->d_tids, itids.data(), alloc * 10)))
             return rc;
     }
-    *out = hnsw_register(std::move(h));
+    *out = hnsw_register(std::move(h), 1);
     return VSR_OK;
 }
 
@@ -485,8 +485,97 @@ struct HnswForest {
     HnswForestPlan plan;
 };
 
+// the seven device arrays of an index under construction, sized by its n_elem, n_upper, max_level and m (at least 4 bytes each)
+static int hnsw_index_arrays(HnswAttempt& at, vsr_hnsw* hh, size_t counts[7] = nullptr)
+{
+    const size_t ne = (size_t) hh->n_elem, m = (size_t) hh->m;
+    const size_t want[7] = {ne, ne, ne * 2 * m, ne, (size_t) hh->n_upper * hh->max_level * m, ne, ne * 10};
+    int32_t** ptrs[7] = {&hh->d_elem_row, &hh->d_level, &hh->d_nbr0, &hh->d_up_slot, &hh->d_up_nbr, &hh->d_tid_count, &hh->d_tids};
+    for (int i = 0; i < 7; ++i) {
+        HNSW_TRY(hipMalloc(ptrs[i], std::max<size_t>(4, want[i] * sizeof(int32_t))));
+        if (counts) counts[i] = want[i];
+    }
+    return VSR_OK;
+}
+
+// the global element space of one attempt of a partition call (build or extend): the build arrays over all graphs, the plan's slot
+// arrays, the reverse edges' scratch and the kernels' parameters.  All of it is the attempt's scratch
+struct HnswForestSpace {
+    int32_t *level = nullptr, *elem_row = nullptr, *up_slot = nullptr, *nbr0 = nullptr, *up_nbr = nullptr;
+    int32_t* plan = nullptr;                 // [3][slots] the rounds' elements | entry points | their levels
+    float *dist0 = nullptr, *up_dist = nullptr;
+    size_t total = 0, slots = 0, up_slots = 1, up_words = 0;
+    HnswBuildParams bp{};
+    HnswRecScratch rs;
+};
+// allocates and fills the space of fo with *slots_io visited-table entries (0: the build's default, written back): the host's per-element
+// arrays uploaded, lists -1, distances 0 (behind the uploads, on the stream)
+static int hnsw_forest_space(HnswAttempt& at, vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, const HnswForest& fo,
+                             uint32_t* slots_io, HnswForestSpace& sp)
+{
+    vsr_ctx* ctx = c->ctx;
+    const size_t total = sp.total = (size_t) fo.base.back(), slots = sp.slots = fo.plan.elems.size();
+    sp.up_slots = (size_t) std::max(fo.g_upper, 1);
+    sp.up_words = sp.up_slots * fo.g_max_level * m;
+    HNSW_TRY(at.upload(&sp.level, fo.level.data(), total));
+    HNSW_TRY(at.upload(&sp.elem_row, fo.elem_row.data(), total));
+    HNSW_TRY(at.upload(&sp.up_slot, fo.up_slot.data(), total));
+    HNSW_TRY(at.alloc(&sp.nbr0, total * 2 * m));
+    HNSW_TRY(at.alloc(&sp.dist0, total * 2 * m));
+    HNSW_TRY(at.alloc(&sp.up_nbr, sp.up_words));
+    HNSW_TRY(at.alloc(&sp.up_dist, sp.up_words));
+    HNSW_TRY(at.alloc(&sp.plan, slots * 3));
+    HNSW_TRY(hipMemcpy(sp.plan, fo.plan.elems.data(), slots * 4, hipMemcpyHostToDevice));
+    HNSW_TRY(hipMemcpy(sp.plan + slots, fo.plan.entry.data(), slots * 4, hipMemcpyHostToDevice));
+    HNSW_TRY(hipMemcpy(sp.plan + 2 * slots, fo.plan.entry_level.data(), slots * 4, hipMemcpyHostToDevice));
+    HNSW_TRY(hipMemsetAsync(sp.nbr0, 0xFF, total * 2 * m * 4, ctx->stream));
+    HNSW_TRY(hipMemsetAsync(sp.up_nbr, 0xFF, sp.up_words * 4, ctx->stream));
+    HNSW_TRY(hipMemsetAsync(sp.dist0, 0, total * 2 * m * 4, ctx->stream));
+    HNSW_TRY(hipMemsetAsync(sp.up_dist, 0, sp.up_words * 4, ctx->stream));
+
+    HnswBuildParams& bp = sp.bp;
+    hnsw_row_params(bp, c, expect, metric);
+    bp.m = (uint32_t) m;
+    bp.efc = (uint32_t) ef_construction;
+    bp.max_level = (uint32_t) fo.g_max_level;
+    bp.nbr0 = sp.nbr0;
+    bp.dist0 = sp.dist0;
+    bp.up_slot = sp.up_slot;
+    bp.up_nbr = sp.up_nbr;
+    bp.up_dist = sp.up_dist;
+    bp.level = sp.level;
+    bp.elem_row = sp.elem_row;
+    bp.caps = (uint32_t) (ef_construction + 2 * m);
+    if (*slots_io == 0) *slots_io = hnsw_default_visited_slots(ef_construction, m);   // the build's default
+    bp.hash_slots = *slots_io;
+    if (!hnsw_lds_params(bp, HnswLadder{}))
+        return fail(VSR_ERR_UNSUPPORTED, "%s: ef_construction = %d with m = %d does not fit the LDS", at.who, ef_construction, m);
+    bp.err = ctx->err_word();
+    std::vector<uint32_t> rec_caps;
+    for (const HnswForestRound& r : fo.plan.rounds) rec_caps.push_back(r.rec_cap);
+    HNSW_TRY(hnsw_rec_scratch(at, rec_caps, 0, &sp.rs));
+    bp.rec_count = sp.rs.cnt;
+    return VSR_OK;
+}
+// the rounds of fo.plan over sp, on the stream
+static int hnsw_forest_rounds(HnswAttempt& at, const HnswForest& fo, HnswForestSpace& sp)
+{
+    for (const HnswForestRound& r : fo.plan.rounds) {
+        HnswForestParams fp{};
+        fp.elems = sp.plan + r.first_slot;
+        fp.entry = sp.plan + sp.slots + r.first_slot;
+        fp.entry_level = sp.plan + 2 * sp.slots + r.first_slot;
+        sp.bp.count = r.count;
+        sp.bp.rec_cap = r.rec_cap;
+        sp.bp.rec_key = sp.rs.key[0];
+        sp.bp.rec_val = sp.rs.val[0];
+        HNSW_TRY(vsr_hnsw_forest_round(sp.bp, fp, sp.rs.tmp, sp.rs.tmp_bytes, sp.rs.key[1], sp.rs.val[1], at.ctx->stream));
+    }
+    return VSR_OK;
+}
+
 // One attempt with *slots_io visited-table entries; *guard: as hnsw_build_once.  On success out[g] holds every index, registered.
-// Its own: the per-graph arrays, the rounds and the split
+// Its own: the per-graph arrays and the split
 static int hnsw_forest_once(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, const HnswForest& fo, uint32_t* slots_io,
                             uint32_t* guard, vsr_hnsw** out, const char* who)
 {
@@ -507,77 +596,82 @@ static int hnsw_forest_once(vsr_corpus* c, RowFormat expect, int m, int ef_const
         const int32_t e = fo.plan.final_entry[(size_t) g];
         hh->entry = e >= 0 ? (int32_t) (e - fo.base[(size_t) g]) : -1;
         hh->entry_level = e >= 0 ? fo.level[(size_t) e] : -1;
-        const size_t counts[7] = {ne, ne, ne * 2 * m, ne, (size_t) hh->n_upper * hh->max_level * m, ne, ne * 10};
-        int32_t** ptrs[7] = {&hh->d_elem_row, &hh->d_level, &hh->d_nbr0, &hh->d_up_slot, &hh->d_up_nbr, &hh->d_tid_count, &hh->d_tids};
-        for (int i = 0; i < 7; ++i) HNSW_TRY(hipMalloc(ptrs[i], std::max<size_t>(4, counts[i] * sizeof(int32_t))));
+        if (const int rc = hnsw_index_arrays(at, hh)) return rc;
         if (ne > 0)
             graphs.push_back({hh->d_level, hh->d_elem_row, hh->d_nbr0, hh->d_up_slot, hh->d_up_nbr, hh->d_tid_count, hh->d_tids,
                               (int32_t) fo.base[(size_t) g], (int32_t) ne, fo.slot_base[(size_t) g], hh->max_level});
     }
     if (total > 0) {
-        int32_t *d_level = nullptr, *d_elem_row = nullptr, *d_up_slot = nullptr, *d_nbr0 = nullptr, *d_up_nbr = nullptr, *d_plan = nullptr;
-        float *d_dist0 = nullptr, *d_up_dist = nullptr;
+        HnswForestSpace sp;
         HnswForestGraph* d_graphs = nullptr;
-        const size_t up_words = (size_t) std::max(fo.g_upper, 1) * fo.g_max_level * m;
-        HNSW_TRY(at.upload(&d_level, fo.level.data(), total));
-        HNSW_TRY(at.upload(&d_elem_row, fo.elem_row.data(), total));
-        HNSW_TRY(at.upload(&d_up_slot, fo.up_slot.data(), total));
+        if (const int rc = hnsw_forest_space(at, c, expect, m, ef_construction, metric, fo, slots_io, sp)) return rc;
         HNSW_TRY(at.upload(&d_graphs, graphs.data(), graphs.size()));
-        HNSW_TRY(at.alloc(&d_nbr0, total * 2 * m));
-        HNSW_TRY(at.alloc(&d_dist0, total * 2 * m));
-        HNSW_TRY(at.alloc(&d_up_nbr, up_words));
-        HNSW_TRY(at.alloc(&d_up_dist, up_words));
-        HNSW_TRY(at.alloc(&d_plan, total * 3));                               // the rounds' elements | entry points | their levels
-        HNSW_TRY(hipMemcpy(d_plan, fo.plan.elems.data(), total * 4, hipMemcpyHostToDevice));
-        HNSW_TRY(hipMemcpy(d_plan + total, fo.plan.entry.data(), total * 4, hipMemcpyHostToDevice));
-        HNSW_TRY(hipMemcpy(d_plan + 2 * total, fo.plan.entry_level.data(), total * 4, hipMemcpyHostToDevice));
-        HNSW_TRY(hipMemsetAsync(d_nbr0, 0xFF, total * 2 * m * 4, ctx->stream));
-        HNSW_TRY(hipMemsetAsync(d_up_nbr, 0xFF, up_words * 4, ctx->stream));
-        HNSW_TRY(hipMemsetAsync(d_dist0, 0, total * 2 * m * 4, ctx->stream));
-        HNSW_TRY(hipMemsetAsync(d_up_dist, 0, up_words * 4, ctx->stream));
-
-        HnswBuildParams bp{};
-        hnsw_row_params(bp, c, expect, metric);
-        bp.m = (uint32_t) m;
-        bp.efc = (uint32_t) ef_construction;
-        bp.max_level = (uint32_t) fo.g_max_level;
-        bp.nbr0 = d_nbr0;
-        bp.dist0 = d_dist0;
-        bp.up_slot = d_up_slot;
-        bp.up_nbr = d_up_nbr;
-        bp.up_dist = d_up_dist;
-        bp.level = d_level;
-        bp.elem_row = d_elem_row;
-        bp.caps = (uint32_t) (ef_construction + 2 * m);
-        if (*slots_io == 0) *slots_io = hnsw_default_visited_slots(ef_construction, m);   // the build's default
-        bp.hash_slots = *slots_io;
-        if (!hnsw_lds_params(bp, HnswLadder{}))
-            return fail(VSR_ERR_UNSUPPORTED, "%s: ef_construction = %d with m = %d does not fit the LDS", who, ef_construction, m);
-        bp.err = ctx->err_word();
-        std::vector<uint32_t> rec_caps;
-        for (const HnswForestRound& r : fo.plan.rounds) rec_caps.push_back(r.rec_cap);
-        HnswRecScratch rs;
-        HNSW_TRY(hnsw_rec_scratch(at, rec_caps, 0, &rs));
-        bp.rec_count = rs.cnt;
-        for (const HnswForestRound& r : fo.plan.rounds) {
-            HnswForestParams fp{};
-            fp.elems = d_plan + r.first_slot;
-            fp.entry = d_plan + total + r.first_slot;
-            fp.entry_level = d_plan + 2 * total + r.first_slot;
-            bp.count = r.count;
-            bp.rec_cap = r.rec_cap;
-            bp.rec_key = rs.key[0];
-            bp.rec_val = rs.val[0];
-            HNSW_TRY(vsr_hnsw_forest_round(bp, fp, rs.tmp, rs.tmp_bytes, rs.key[1], rs.val[1], ctx->stream));
-        }
-        HNSW_TRY(vsr_hnsw_forest_split(bp, d_graphs, (uint32_t) graphs.size(), (uint32_t) total, ctx->stream));
+        if (const int rc = hnsw_forest_rounds(at, fo, sp)) return rc;
+        HNSW_TRY(vsr_hnsw_forest_split(sp.bp, d_graphs, (uint32_t) graphs.size(), (uint32_t) total, ctx->stream));
         HNSW_TRY(hipStreamSynchronize(ctx->stream));
-        HNSW_TRY(hnsw_take_guard(bp.err, guard));                             // the build's rule: never a thinner graph
+        HNSW_TRY(hnsw_take_guard(sp.bp.err, guard));                          // the build's rule: never a thinner graph
         if (*guard) return VSR_OK;
     }
     at.free_all();
-    for (int g = 0; g < fo.n_parts; ++g) out[g] = hnsw_register(std::move(made[(size_t) g]));
+    for (int g = 0; g < fo.n_parts; ++g) out[g] = hnsw_register(std::move(made[(size_t) g]), 1);
     return VSR_OK;
+}
+
+// the partitions' row lists as both partition calls take them: `off` ascends from 0, a row is inside the corpus and named once within
+// its partition (seen[row] = the partition that named it last, + 1).  Leaves in `internal` the internal rows, every partition's
+// ascending: the build's insertion order.  off_name: what the caller's header calls `off`
+static int hnsw_partition_rows(const vsr_corpus* c, int n_parts, const int64_t* off, const int64_t* rows, const char* off_name, const char* who,
+                               std::vector<int32_t>& internal)
+{
+    if (off[0] != 0) return fail(VSR_ERR_INVALID, "%s: %s[0] is %lld, not 0", who, off_name, (long long) off[0]);
+    for (int g = 0; g < n_parts; ++g)
+        if (off[g + 1] < off[g])
+            return fail(VSR_ERR_INVALID, "%s: %s does not ascend at partition %d (%lld after %lld)", who, off_name, g, (long long) off[g + 1],
+                        (long long) off[g]);
+    const int64_t total = off[n_parts];
+    if (total > 0 && !rows) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
+    if (total > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "%s: too many elements", who);
+    internal.resize((size_t) total);
+    const std::vector<int32_t> inv = hnsw_row_map(c);
+    std::vector<int32_t> seen((size_t) std::max<int64_t>(c->n, 1), 0);
+    for (int g = 0; g < n_parts; ++g) {
+        for (int64_t i = off[g]; i < off[g + 1]; ++i) {
+            const int64_t row = rows[i];
+            if (row < 0 || row >= c->n)
+                return fail(VSR_ERR_INVALID, "%s: partition %d, position %lld: row %lld is outside [0, %lld)", who, g, (long long) (i - off[g]),
+                            (long long) row, (long long) c->n);
+            if (seen[(size_t) row] == g + 1)
+                return fail(VSR_ERR_INVALID, "%s: partition %d, position %lld: row %lld is named twice", who, g, (long long) (i - off[g]),
+                            (long long) row);
+            seen[(size_t) row] = g + 1;
+            internal[(size_t) i] = inv[(size_t) row];
+        }
+        std::sort(internal.begin() + off[g], internal.begin() + off[g + 1]);
+    }
+    return VSR_OK;
+}
+
+// the attempts of a partition call under the visited-table ladder: once(&slots, &guard) runs the whole call.  Dropped records apart,
+// a bit in any graph is the visited table's: the whole call again with twice the slots, as hnsw_build
+template <class Once>
+static int hnsw_forest_ladder(int m, int ef_construction, uint32_t slots, const char* who, Once once)
+{
+    uint32_t caps = (uint32_t) (ef_construction + 2 * m);
+    for (;;) {
+        uint32_t guard = 0;
+        const int rc = once(&slots, &guard);
+        if (rc != VSR_OK || guard == 0) return rc;
+        switch (hnsw_ladder_step(HnswLadder{}, (guard & HB_ERR_RECORDS) | HB_ERR_VISITED, &caps, &slots)) {
+        case HB_LADDER_RECORDS:
+            return fail(VSR_ERR_UNSUPPORTED, "%s: reverse edges were dropped at ef_construction = %d with m = %d: the graph would be incomplete", who,
+                        ef_construction, m);
+        case HB_LADDER_VISITED:
+            return fail(VSR_ERR_UNSUPPORTED,
+                        "%s: a layer search at ef_construction = %d with m = %d fills its visited table of %u entries and no larger one fits the LDS",
+                        who, ef_construction, m, slots);
+        default: break;
+        }
+    }
 }
 
 extern "C" int vsr_hnsw_build_partitions(vsr_corpus* c, int n_parts, const int64_t* part_off, const int64_t* part_rows, int m, int ef_construction,
@@ -601,38 +695,11 @@ extern "C" int vsr_hnsw_build_partitions(vsr_corpus* c, int n_parts, const int64
     uint32_t slots = 0;
     if (const int rc = hnsw_env_visited_slots(who, &slots)) return rc;
     if (n_parts == 0) return VSR_OK;
-    if (part_off[0] != 0) return fail(VSR_ERR_INVALID, "%s: part_off[0] is %lld, not 0", who, (long long) part_off[0]);
-    for (int g = 0; g < n_parts; ++g)
-        if (part_off[g + 1] < part_off[g])
-            return fail(VSR_ERR_INVALID, "%s: part_off does not ascend at partition %d (%lld after %lld)", who, g, (long long) part_off[g + 1],
-                        (long long) part_off[g]);
-    const int64_t total = part_off[n_parts];
-    if (total > 0 && !part_rows) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
-    if (total > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "%s: too many elements", who);
-
     HnswForest fo;
     fo.n_parts = n_parts;
+    if (const int rc = hnsw_partition_rows(c, n_parts, part_off, part_rows, "part_off", who, fo.elem_row)) return rc;
+    const int64_t total = part_off[n_parts];
     fo.base.assign(part_off, part_off + n_parts + 1);
-    fo.elem_row.resize((size_t) total);
-    {
-        // caller rows -> internal rows; within a partition every row once (seen[row] = the partition that named it last, + 1)
-        const std::vector<int32_t> inv = hnsw_row_map(c);
-        std::vector<int32_t> seen((size_t) std::max<int64_t>(c->n, 1), 0);
-        for (int g = 0; g < n_parts; ++g) {
-            for (int64_t i = part_off[g]; i < part_off[g + 1]; ++i) {
-                const int64_t row = part_rows[i];
-                if (row < 0 || row >= c->n)
-                    return fail(VSR_ERR_INVALID, "%s: partition %d, position %lld: row %lld is outside [0, %lld)", who, g, (long long) (i - part_off[g]),
-                                (long long) row, (long long) c->n);
-                if (seen[(size_t) row] == g + 1)
-                    return fail(VSR_ERR_INVALID, "%s: partition %d, position %lld: row %lld is named twice", who, g, (long long) (i - part_off[g]),
-                                (long long) row);
-                seen[(size_t) row] = g + 1;
-                fo.elem_row[(size_t) i] = inv[(size_t) row];
-            }
-            std::sort(fo.elem_row.begin() + part_off[g], fo.elem_row.begin() + part_off[g + 1]);   // the build's insertion order
-        }
-    }
     // levels: the build's stream, drawn once as far as the largest partition needs and read from its start by each
     int64_t longest = 0;
     for (int g = 0; g < n_parts; ++g) longest = std::max(longest, part_off[g + 1] - part_off[g]);
@@ -657,23 +724,9 @@ extern "C" int vsr_hnsw_build_partitions(vsr_corpus* c, int n_parts, const int64
     }
     if (!hnsw_forest_plan(n_parts, fo.base.data(), fo.level.data(), m, (uint32_t) cap, fo.plan))
         return fail(VSR_ERR_UNSUPPORTED, "%s: a round with m = %d has too many reverse edges", who, m);
-    uint32_t caps = (uint32_t) (ef_construction + 2 * m);
-    for (;;) {
-        uint32_t guard = 0;
-        const int rc = hnsw_forest_once(c, expect, m, ef_construction, metric, fo, &slots, &guard, out, who);
-        if (rc != VSR_OK || guard == 0) return rc;
-        // dropped records apart, a bit in any graph is the visited table's: the whole call again, as hnsw_build
-        switch (hnsw_ladder_step(HnswLadder{}, (guard & HB_ERR_RECORDS) | HB_ERR_VISITED, &caps, &slots)) {
-        case HB_LADDER_RECORDS:
-            return fail(VSR_ERR_UNSUPPORTED, "%s: reverse edges were dropped at ef_construction = %d with m = %d: the graph would be incomplete", who,
-                        ef_construction, m);
-        case HB_LADDER_VISITED:
-            return fail(VSR_ERR_UNSUPPORTED,
-                        "%s: a layer search at ef_construction = %d with m = %d fills its visited table of %u entries and no larger one fits the LDS",
-                        who, ef_construction, m, slots);
-        default: break;
-        }
-    }
+    return hnsw_forest_ladder(m, ef_construction, slots, who, [&](uint32_t* slots_io, uint32_t* guard) {
+        return hnsw_forest_once(c, expect, m, ef_construction, metric, fo, slots_io, guard, out, who);
+    });
 }
 
 // ---- vsr_hnsw_extend's host pass over the caller's graph, before anything is uploaded.  The extension WRITES through these lists
@@ -776,6 +829,280 @@ extern "C" int vsr_hnsw_extend(vsr_corpus* c, int m, int32_t n_elem, int32_t ent
     if (rc) return rc;
     if (pr.n_new == 0) return hnsw_load(c, expect, expect == RowFormat::BIT ? metric : 0, g, out, who);   // nothing to insert: the graph as it is
     return hnsw_build(c, expect, m, ef_construction, metric, seed, 0u, out, who, &pr);
+}
+
+// ---- vsr_hnsw_extend_partitions: vsr_hnsw_extend for many graphs over one corpus.  The graphs that take rows are joined on the device
+// into the global element space of vsr_hnsw_build_partitions (hnsw_forest_join_kernel), every graph's batches run in shared rounds from
+// done = its prior n_elem (hnsw_forest_plan_from), and the split writes every graph's own arrays with the prior TID lists carried over
+
+// what the host pass leaves for every attempt
+struct HnswForestExtend {
+    int n_parts = 0;
+    std::vector<const vsr_hnsw*> prior;      // [n_parts] nullptr: no prior graph (NULL, or n_elem = 0)
+    std::vector<int> active;                 // the partitions that take rows, ascending: graph i of the element space is active[i]
+    std::vector<int64_t> n_prior;            // [active] its prior elements
+    HnswForest fo;                           // the element space of the active graphs (fo.n_parts of them): graph i owns base[i] .. base[i + 1]
+                                             // - 1, prior elements first; elem_row / level / up_slot hold the new elements' entries, a prior
+                                             // element's are the join kernel's
+};
+
+// an index like h in arrays of its own (a partition that takes no rows); copies on the stream
+static int hnsw_clone_into(HnswAttempt& at, vsr_hnsw* to, const vsr_hnsw* h)
+{
+    if (h && h->n_elem > 0) {
+        to->n_elem = h->n_elem;
+        to->entry = h->entry;
+        to->entry_level = h->entry_level;
+        to->max_level = h->max_level;
+        to->n_upper = h->n_upper;
+    }
+    size_t counts[7];
+    if (const int rc = hnsw_index_arrays(at, to, counts)) return rc;
+    if (to->n_elem == 0) return VSR_OK;
+    int32_t* const ptrs[7] = {to->d_elem_row, to->d_level, to->d_nbr0, to->d_up_slot, to->d_up_nbr, to->d_tid_count, to->d_tids};
+    const int32_t* const from[7] = {h->d_elem_row, h->d_level, h->d_nbr0, h->d_up_slot, h->d_up_nbr, h->d_tid_count, h->d_tids};
+    for (int i = 0; i < 7; ++i)
+        if (counts[i] > 0) HNSW_TRY(hipMemcpyAsync(ptrs[i], from[i], counts[i] * sizeof(int32_t), hipMemcpyDeviceToDevice, at.ctx->stream));
+    return VSR_OK;
+}
+
+// One attempt with *slots_io visited-table entries; *guard: as hnsw_build_once.  On success out[g] holds every index, registered.
+static int hnsw_forest_extend_once(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, const HnswForestExtend& fx,
+                                   uint32_t* slots_io, uint32_t* guard, vsr_hnsw** out, const char* who)
+{
+    vsr_ctx* ctx = c->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    const HnswForest& fo = fx.fo;
+    const size_t n_graphs = fx.active.size(), total = (size_t) fo.base[n_graphs];
+    std::vector<HnswOwner> made((size_t) fx.n_parts);
+    std::vector<int> made_here((size_t) fx.n_parts, 1);
+    HnswAttempt at(ctx, who);
+    std::vector<HnswForestGraph> graphs;
+    std::vector<HnswForestPrior> priors;
+    size_t next = 0;                                                          // the next active partition
+    for (int g = 0; g < fx.n_parts; ++g) {
+        made[(size_t) g] = hnsw_new_index(c, expect, metric, m);
+        vsr_hnsw* hh = made[(size_t) g].get();
+        const vsr_hnsw* pr = fx.prior[(size_t) g];
+        if (next >= n_graphs || fx.active[next] != g) {
+            // nothing to insert: the prior graph as it is, unread -- so the copy is worth what the prior was worth (an empty one: nothing to doubt)
+            if (const int rc = hnsw_clone_into(at, hh, pr)) return rc;
+            made_here[(size_t) g] = pr ? pr->made_here : 1;
+            continue;
+        }
+        const size_t i = next++, ne = (size_t) (fo.base[i + 1] - fo.base[i]);
+        hh->n_elem = (int32_t) ne;
+        hh->max_level = fo.max_level[i];
+        hh->n_upper = fo.n_upper[i];
+        const int32_t e = fo.plan.final_entry[i];
+        hh->entry = (int32_t) (e - fo.base[i]);
+        hh->entry_level = e >= fo.base[i] + fx.n_prior[i] ? fo.level[(size_t) e] : pr->entry_level;   // a new element took over / the prior entry stays
+        if (const int rc = hnsw_index_arrays(at, hh)) return rc;
+        graphs.push_back({hh->d_level, hh->d_elem_row, hh->d_nbr0, hh->d_up_slot, hh->d_up_nbr, hh->d_tid_count, hh->d_tids, (int32_t) fo.base[i],
+                          (int32_t) ne, fo.slot_base[i], hh->max_level});
+        HnswForestPrior fp{};
+        if (pr) {
+            fp.level = pr->d_level; fp.elem_row = pr->d_elem_row; fp.nbr0 = pr->d_nbr0; fp.up_slot = pr->d_up_slot; fp.up_nbr = pr->d_up_nbr;
+            fp.tid_count = pr->d_tid_count; fp.tids = pr->d_tids;
+            fp.n_elem = pr->n_elem; fp.n_upper = pr->n_upper; fp.max_level = pr->max_level;
+        }
+        priors.push_back(fp);
+    }
+    if (total > 0) {
+        HnswForestSpace sp;
+        int32_t* d_up_owner = nullptr;
+        HnswForestGraph* d_graphs = nullptr;
+        HnswForestPrior* d_priors = nullptr;
+        unsigned long long* d_words = nullptr;                                // [0]: HnswForestJoin::held; [1]: bad (its low word)
+        if (const int rc = hnsw_forest_space(at, c, expect, m, ef_construction, metric, fo, slots_io, sp)) return rc;
+        HNSW_TRY(at.upload(&d_graphs, graphs.data(), graphs.size()));
+        HNSW_TRY(at.upload(&d_priors, priors.data(), priors.size()));
+        const unsigned long long words[2] = {~0ull, ~0ull};
+        HNSW_TRY(at.upload(&d_words, words, 2));
+        HNSW_TRY(at.alloc(&d_up_owner, sp.up_slots));
+        HNSW_TRY(hipMemsetAsync(d_up_owner, 0xFF, sp.up_slots * 4, ctx->stream));
+
+        // the prior graphs into the element space; what they say is read before anything is written through them
+        HnswForestJoin jn{};
+        jn.level = sp.level;
+        jn.elem_row = sp.elem_row;
+        jn.up_slot = sp.up_slot;
+        jn.up_owner = d_up_owner;
+        jn.n_rows = (uint32_t) c->n;
+        jn.held = d_words;
+        jn.bad = reinterpret_cast<uint32_t*>(d_words + 1);
+        HNSW_TRY(vsr_hnsw_forest_join(sp.bp, jn, d_graphs, d_priors, (uint32_t) graphs.size(), (uint32_t) total, ctx->stream));
+        HNSW_TRY(hipStreamSynchronize(ctx->stream));
+        unsigned long long got[2] = {~0ull, ~0ull};
+        HNSW_TRY(hipMemcpy(got, d_words, sizeof got, hipMemcpyDeviceToHost));
+        if ((uint32_t) got[1] != 0xFFFFFFFFu) {
+            const size_t i = (size_t) (uint32_t) got[1];
+            return fail(VSR_ERR_INVALID, "%s: partition %d: the prior index holds a level, row, upper slot or neighbour outside its range", who,
+                        i < n_graphs ? fx.active[i] : -1);
+        }
+        if (got[0] != ~0ull) {
+            const size_t i = (size_t) (got[0] >> 32), r = (size_t) (got[0] & 0xFFFFFFFFull);
+            if (i < n_graphs && r < (size_t) c->n)
+                return fail(VSR_ERR_INVALID, "%s: partition %d: new row %lld is under a heap TID of the prior graph already", who, fx.active[i],
+                            (long long) c->h_orig[r]);
+            return fail(VSR_ERR_INVALID, "%s: a new row is under a heap TID of a prior graph already", who);
+        }
+        // the distance of every prior edge (the new elements' lists are empty and return at once), then the rounds
+        HNSW_TRY(vsr_hnsw_edge_distances(sp.bp, (uint32_t) total, d_up_owner, (uint32_t) fo.g_upper, ctx->stream));
+        if (const int rc = hnsw_forest_rounds(at, fo, sp)) return rc;
+        HNSW_TRY(vsr_hnsw_forest_split_carry(sp.bp, d_graphs, d_priors, (uint32_t) graphs.size(), (uint32_t) total, ctx->stream));
+    }
+    HNSW_TRY(hipStreamSynchronize(ctx->stream));
+    if (total > 0) {
+        HNSW_TRY(hnsw_take_guard(ctx->err_word(), guard));                    // the build's rule: never a thinner graph
+        if (*guard) return VSR_OK;
+    }
+    at.free_all();
+    for (int g = 0; g < fx.n_parts; ++g) out[g] = hnsw_register(std::move(made[(size_t) g]), made_here[(size_t) g]);
+    return VSR_OK;
+}
+
+// a prior index this library did not make: its arrays to the host and through vsr_hnsw_extend's checks, before anything is launched
+static int hnsw_forest_check_prior(const vsr_corpus* c, const vsr_hnsw* h, int g, const char* who)
+{
+    const size_t ne = (size_t) h->n_elem, m = (size_t) h->m, up = (size_t) std::max(h->n_upper, 0) * (size_t) std::max(h->max_level, 1) * m;
+    std::vector<int32_t> level(ne), nbr0(ne * 2 * m), tid_count(ne), up_slot(ne), up_nbr(std::max<size_t>(up, 1)), itids(ne * 10);
+    std::vector<int64_t> tids(ne * 10, -1);
+    HIPCHK(hipMemcpy(level.data(), h->d_level, ne * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(nbr0.data(), h->d_nbr0, ne * 2 * m * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tid_count.data(), h->d_tid_count, ne * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(up_slot.data(), h->d_up_slot, ne * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(itids.data(), h->d_tids, ne * 10 * 4, hipMemcpyDeviceToHost));
+    if (up > 0) HIPCHK(hipMemcpy(up_nbr.data(), h->d_up_nbr, up * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < ne * 10; ++i)                                      // internal rows -> the caller's row indices
+        if (itids[i] >= 0 && (int64_t) itids[i] < c->n) tids[i] = c->h_orig[(size_t) itids[i]];
+    char name[96];
+    snprintf(name, sizeof name, "%s: partition %d: the prior index", who, g);
+    const HnswGraphView view{h->m, h->n_elem, h->entry, level.data(), nbr0.data(), tid_count.data(), tids.data(), up_slot.data(),
+                             up_nbr.data(), h->n_upper, h->max_level};
+    HnswPrior pr;
+    return hnsw_extend_prepare(c, view, pr, name);
+}
+
+extern "C" int vsr_hnsw_extend_partitions(vsr_corpus* c, int n_parts, vsr_hnsw* const* prior, const int64_t* new_off, const int64_t* new_rows,
+                                          int ef_construction, int metric, uint64_t seed, uint32_t flags, vsr_hnsw** out)
+{
+    const char* who = "vsr_hnsw_extend_partitions";
+    if (out)
+        for (int g = 0; g < n_parts; ++g) out[g] = nullptr;
+    if (!c || n_parts < 0 || (n_parts > 0 && (!out || !new_off || !prior))) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
+    const RowFormat expect = c->format;
+    if (expect == RowFormat::SPARSE)
+        return fail(VSR_ERR_UNSUPPORTED,
+                    "%s: a sparsevec corpus is not supported (the sparse build has no element -> row form): rebuild every partition's graph with "
+                    "vsr_hnsw_build_sparse over a corpus of its rows", who);
+    if (flags & VSR_HNSW_BUILD_MERGE_DUPLICATES)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: VSR_HNSW_BUILD_MERGE_DUPLICATES is not supported: an inserted row is never folded into an existing element", who);
+    if (flags) return fail(VSR_ERR_INVALID, "%s: unknown flag bits 0x%x", who, flags);
+    if (c->base) return fail(VSR_ERR_INVALID, "%s: the corpus is a view", who);
+    long cap = HB_BATCH_MAX;
+    if (const int rc = hnsw_env_int(who, "VSR_HNSW_FOREST_BATCH", 1, (long) HB_BATCH_MAX, false, "a number from", "to", &cap)) return rc;
+    uint32_t slots = 0;
+    if (const int rc = hnsw_env_visited_slots(who, &slots)) return rc;
+    if (n_parts == 0) return VSR_OK;
+    // m is the priors': the call has no m of its own, so at least one prior index must be there to say it
+    int m = 0;
+    for (int g = 0; g < n_parts; ++g) {
+        const vsr_hnsw* h = prior[g];
+        if (!h) continue;
+        if (h->corpus != c) return fail(VSR_ERR_INVALID, "%s: partition %d: the prior index is over another corpus", who, g);
+        if (h->format != expect) return fail(VSR_ERR_INVALID, "%s: partition %d: the prior index is of another row format than the corpus", who, g);
+        if (m == 0) m = h->m;
+        if (h->m != m) return fail(VSR_ERR_INVALID, "%s: partition %d: the prior index has m = %d, the ones before it m = %d", who, g, h->m, m);
+        if (expect == RowFormat::BIT && h->bit_metric != metric)
+            return fail(VSR_ERR_INVALID, "%s: partition %d: the prior index's opclass is metric %d, not %d", who, g, h->bit_metric, metric);
+    }
+    if (m == 0)
+        return fail(VSR_ERR_INVALID, "%s: every prior index is NULL, so m is not known: build the graphs with vsr_hnsw_build_partitions", who);
+    vsr_hnsw* none = nullptr;
+    if (const int rc = hnsw_build_check(c, expect, m, ef_construction, metric, flags, &none, who)) return rc;
+    if (c->n > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "%s: too many elements", who);
+    std::vector<int32_t> fresh;                                               // the new rows as internal rows, a partition's ascending
+    if (const int rc = hnsw_partition_rows(c, n_parts, new_off, new_rows, "new_off", who, fresh)) return rc;
+    HIPCHK(hipSetDevice(c->ctx->device));
+    // per prior index, once however many partitions name it: the checks of one this library did not make, and n0, its heap TIDs
+    HnswForestExtend fx;
+    fx.n_parts = n_parts;
+    HnswForest& fo = fx.fo;
+    fx.prior.assign((size_t) n_parts, nullptr);
+    std::map<const vsr_hnsw*, int64_t> n0_of;
+    std::vector<int32_t> counts;
+    int64_t most_draws = 0;
+    for (int g = 0; g < n_parts; ++g) {
+        const vsr_hnsw* h = prior[g];
+        if (!h || h->n_elem <= 0) continue;
+        fx.prior[(size_t) g] = h;
+        const int64_t n_new = new_off[g + 1] - new_off[g];
+        if (n_new == 0) continue;                                             // copied as it is: nothing is written through it
+        auto it = n0_of.find(h);
+        if (it == n0_of.end()) {
+            if (!h->made_here)
+                if (const int rc = hnsw_forest_check_prior(c, h, g, who)) return rc;
+            counts.resize((size_t) h->n_elem);
+            HIPCHK(hipMemcpy(counts.data(), h->d_tid_count, (size_t) h->n_elem * 4, hipMemcpyDeviceToHost));
+            int64_t n0 = 0;
+            for (int32_t t : counts) n0 += std::min(std::max(t, 0), (int32_t) HB_TIDS);
+            it = n0_of.emplace(h, n0).first;
+        }
+        most_draws = std::max(most_draws, it->second + n_new);
+    }
+    for (int g = 0; g < n_parts; ++g)
+        if (!fx.prior[(size_t) g]) most_draws = std::max(most_draws, new_off[g + 1] - new_off[g]);
+    // levels: the build's stream, drawn once as far as any partition reaches; the i-th new row of a graph takes draw n0 + i
+    HnswLevelStream stream(seed, m);
+    std::vector<int32_t> draws((size_t) most_draws);
+    for (int32_t& d : draws) d = stream.level();
+
+    fo.base.assign(1, 0);
+    std::vector<int64_t> start_done;
+    std::vector<int32_t> start_entry, start_entry_level;
+    for (int g = 0; g < n_parts; ++g) {
+        const int64_t n_new = new_off[g + 1] - new_off[g];
+        if (n_new == 0) continue;
+        const vsr_hnsw* h = fx.prior[(size_t) g];
+        const int64_t np = h ? h->n_elem : 0, b = fo.base.back();
+        if (b + np + n_new > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "%s: too many elements", who);
+        if (h && (h->entry < 0 || h->entry >= h->n_elem || h->max_level < 1 || h->n_upper < 0))
+            return fail(VSR_ERR_INVALID, "%s: partition %d: bad graph arrays", who, g);
+        fx.active.push_back(g);
+        fx.n_prior.push_back(np);
+        fo.base.push_back(b + np + n_new);
+        start_done.push_back(np);
+        start_entry.push_back(h ? (int32_t) (b + h->entry) : -1);
+        start_entry_level.push_back(h ? h->entry_level : -1);
+        fo.elem_row.resize((size_t) (b + np + n_new), 0);
+        fo.level.resize((size_t) (b + np + n_new), 0);
+        fo.up_slot.resize((size_t) (b + np + n_new), -1);
+        int32_t n_upper = h ? h->n_upper : 0, max_level = h ? h->max_level : 1;
+        fo.slot_base.push_back(fo.g_upper);
+        const int64_t n0 = h ? n0_of[h] : 0;
+        for (int64_t i = 0; i < n_new; ++i) {
+            const size_t e = (size_t) (b + np + i);
+            fo.elem_row[e] = fresh[(size_t) (new_off[g] + i)];
+            fo.level[e] = draws[(size_t) (n0 + i)];
+            if (fo.level[e] >= 1) {
+                fo.up_slot[e] = fo.g_upper + n_upper++;                       // new upper slots continue after the prior ones
+                max_level = std::max(max_level, fo.level[e]);
+            }
+        }
+        fo.n_upper.push_back(n_upper);
+        fo.max_level.push_back(max_level);
+        fo.g_upper += n_upper;
+        fo.g_max_level = std::max(fo.g_max_level, max_level);
+    }
+    fo.n_parts = (int) fx.active.size();
+    if (!hnsw_forest_plan_from((int) fx.active.size(), fo.base.data(), fo.level.data(), m, (uint32_t) cap, start_done.data(), start_entry.data(),
+                               start_entry_level.data(), fo.plan))
+        return fail(VSR_ERR_UNSUPPORTED, "%s: a round with m = %d has too many reverse edges", who, m);
+    // every attempt starts again from the priors, which no attempt has changed
+    return hnsw_forest_ladder(m, ef_construction, slots, who, [&](uint32_t* slots_io, uint32_t* guard) {
+        return hnsw_forest_extend_once(c, expect, m, ef_construction, metric, fx, slots_io, guard, out, who);
+    });
 }
 
 // ---- VACUUM (hnswvacuum.c): delete rows from a graph, repair it on the GPU, squeeze the deleted elements out.
@@ -1015,7 +1342,7 @@ static int hnsw_vacuum_once(vsr_corpus* c, RowFormat expect, int m, int ef_const
         st->elements_repaired = nrep;
         st->batches = nbatch;
     }
-    *out = hnsw_register(std::move(h));
+    *out = hnsw_register(std::move(h), 1);
     return VSR_OK;
 }
 

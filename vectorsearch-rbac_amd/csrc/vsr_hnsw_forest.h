@@ -1,5 +1,5 @@
-// vsr_hnsw_forest.h -- the schedule of vsr_hnsw_build_partitions (vsr_hnsw_build_rt.hip): the batches of many HNSW builds packed into
-// shared rounds.  Plain C++, no HIP call: tests/test_hnsw_forest_cpu.py compiles this file alone with the host compiler.
+// vsr_hnsw_forest.h -- the schedule of vsr_hnsw_build_partitions and vsr_hnsw_extend_partitions (vsr_hnsw_build_rt.hip): the batches of
+// many HNSW builds, or of many extensions, packed into shared rounds.  Plain C++, no HIP call: tests/test_hnsw_forest_cpu.py compiles this file alone with the host compiler.
 //
 // All partitions live in one global element space: partition g owns elements base[g] .. base[g + 1] - 1.  Every partition keeps
 // the build's own schedule (hnsw_build_batch, vsr_hnsw_sizing.h: max(1, min(done / 8, batch_max, left)) elements, done from 0) and the
@@ -38,11 +38,16 @@ struct HnswForestPlan {
     std::vector<int32_t> final_entry;        // [n_parts] global entry point of every finished graph, -1 for an empty partition
 };
 
-// base[n_parts + 1]: ascending, base[0] = 0, base[n_parts] < 2^31; level[base[n_parts]]: the level of every global element;
-// cap: 1 .. HB_BATCH_MAX.  Returns false when a round's record capacity would pass 2^31 - 1 (the plan is then unusable).
-inline bool hnsw_forest_plan(int n_parts, const int64_t* base, const int32_t* level, int m, uint32_t cap, HnswForestPlan& plan)
+// The plan of graphs that are partly there already (vsr_hnsw_extend_partitions): partition g's first start_done[g] elements are its
+// prior graph, whose entry point is the GLOBAL element start_entry[g] of level start_entry_level[g] (-1 / -1: no element yet); its
+// batches are the build's schedule from done = start_done[g], and only the elements behind the prior ones appear in the slots, so
+// plan.elems holds base[n_parts] minus the sum of start_done entries.  level[] is read for those elements alone.  A nullptr start
+// array stands for zeros (start_done) or -1 (the entry arrays).  The rest as hnsw_forest_plan, which is this plan from nothing.
+inline bool hnsw_forest_plan_from(int n_parts, const int64_t* base, const int32_t* level, int m, uint32_t cap, const int64_t* start_done,
+                                  const int32_t* start_entry, const int32_t* start_entry_level, HnswForestPlan& plan)
 {
-    const size_t total = n_parts > 0 ? (size_t) base[n_parts] : 0;
+    size_t total = 0;
+    for (int g = 0; g < n_parts; ++g) total += (size_t) std::max<int64_t>(base[g + 1] - base[g] - (start_done ? start_done[g] : 0), 0);
     plan = HnswForestPlan{};
     plan.elems.reserve(total);
     plan.entry.reserve(total);
@@ -51,8 +56,12 @@ inline bool hnsw_forest_plan(int n_parts, const int64_t* base, const int32_t* le
     std::vector<int64_t> done((size_t) std::max(n_parts, 0), 0);
     std::vector<int32_t> ent_level((size_t) std::max(n_parts, 0), -1);
     std::vector<int> open;                                                    // unfinished partitions, ascending
-    for (int g = 0; g < n_parts; ++g)
-        if (base[g + 1] > base[g]) open.push_back(g);
+    for (int g = 0; g < n_parts; ++g) {
+        if (start_done) done[(size_t) g] = start_done[g];
+        if (start_entry) plan.final_entry[(size_t) g] = start_entry[g];
+        if (start_entry_level) ent_level[(size_t) g] = start_entry_level[g];
+        if (base[g + 1] - base[g] > done[(size_t) g]) open.push_back(g);
+    }
     std::vector<int> taken;
     while (!open.empty()) {
         HnswForestRound r;
@@ -91,6 +100,13 @@ inline bool hnsw_forest_plan(int n_parts, const int64_t* base, const int32_t* le
         open.erase(std::remove_if(open.begin(), open.end(), [&](int g) { return done[(size_t) g] >= base[g + 1] - base[g]; }), open.end());
     }
     return true;
+}
+
+// base[n_parts + 1]: ascending, base[0] = 0, base[n_parts] < 2^31; level[base[n_parts]]: the level of every global element;
+// cap: 1 .. HB_BATCH_MAX.  Returns false when a round's record capacity would pass 2^31 - 1 (the plan is then unusable).
+inline bool hnsw_forest_plan(int n_parts, const int64_t* base, const int32_t* level, int m, uint32_t cap, HnswForestPlan& plan)
+{
+    return hnsw_forest_plan_from(n_parts, base, level, m, cap, nullptr, nullptr, nullptr, plan);
 }
 
 }  // namespace vsr

@@ -20,6 +20,11 @@ struct vsr_hnsw {
     int predicate_aware = 0;                         // vsr_hnsw_set_predicate_aware
     int32_t vacuum_spilled = 0;                      // vsr_hnsw_vacuum: repairs run in the global-memory form; 0 for any other index
     int64_t vacuum_ws_bytes = 0;                     // and the bytes of the workspace pool they ran in
+    int made_here = 0;                               // 1: this library made the graph (build, build_partitions, extend, vacuum, and
+                                                     // extend_partitions for a graph that took rows or whose prior had the flag), so its
+                                                     // lists are valid by construction and may be written through; 0: the arrays came from
+                                                     // a caller (vsr_hnsw_load*), checked for searching only -- a plain copy of such an index
+                                                     // (extend_partitions, no new rows) stays 0
 };
 
 namespace vsr {
@@ -48,9 +53,10 @@ inline HnswOwner hnsw_new_index(vsr_corpus* c, RowFormat expect, int metric, int
     h->m = m;
     return h;
 }
-// the finished index joins its corpus (vsr_hnsw_free takes it out) and becomes the caller's
-inline vsr_hnsw* hnsw_register(HnswOwner h)
+// the finished index joins its corpus (vsr_hnsw_free takes it out) and becomes the caller's.  made: vsr_hnsw::made_here
+inline vsr_hnsw* hnsw_register(HnswOwner h, int made = 0)
 {
+    h->made_here = made;
     h->corpus->hnsw_indexes.push_back(h.get());
     return h.release();
 }

@@ -114,6 +114,7 @@ SYMBOLS = {
     "vsr_hnsw_vacuum": (_i, [_vp, _i, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i, _i, _vp, _i64, C.c_uint32, _vp,
                              C.POINTER(HnswVacuumStats), C.POINTER(_vp)]),
     "vsr_hnsw_build_partitions": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, C.c_uint64, C.c_uint32, _vp]),
+    "vsr_hnsw_extend_partitions": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, C.c_uint64, C.c_uint32, _vp]),
     "vsr_hnsw_forest_open": (_i, [_vp, _i, C.POINTER(_vp)]),
     "vsr_hnsw_forest_free": (_i, [_vp]),
     "vsr_hnsw_forest_set_predicate_aware": (_i, [_vp, _i]),

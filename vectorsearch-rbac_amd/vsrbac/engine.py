@@ -587,6 +587,32 @@ class Corpus:
                                                   _metric(metric), int(seed), 0, handles))
         return [HnswIndex(self, C.c_void_p(handles[g])) for g in range(len(rows))]
 
+    def extend_hnsw_partitions(self, indexes, new_parts, ef_construction=64, metric=None, seed=1):
+        """extend_hnsw for many graphs of this corpus in one call (vsr_hnsw_extend_partitions): graph g, `indexes[g]`, takes the
+        rows `new_parts[g]` (row indices of this corpus; may be empty).  `indexes`: HnswIndex objects over this corpus -- what
+        build_hnsw_partitions or an earlier call of this method returned, or any others of one m -- or None for an empty graph; at
+        least one must be an index, because m is theirs.  Partitions may share rows and an index may be named twice; a row a graph
+        holds already is refused.  Returns a list of NEW HnswIndex, one per partition: each the graph extend_hnsw with the same
+        ef_construction, metric and seed makes of that graph alone over a corpus of its own rows.  The indexes passed in stay as
+        they are and stay the caller's to free.  metric: None is "l2", or "hamming" on a bit corpus, where it must be the indexes'
+        opclass.  On an error no index is left behind."""
+        if metric is None:
+            metric = "hamming" if self.is_bit else "l2"
+        if len(indexes) != len(new_parts):
+            raise ValueError(f"{len(indexes)} indexes but {len(new_parts)} row lists")
+        rows = [np.ascontiguousarray(np.asarray(p, dtype=np.int64).ravel()) for p in new_parts]
+        off = np.zeros(len(rows) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([r.size for r in rows])
+        flat = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros(0, dtype=np.int64)
+        for g, h in enumerate(indexes):
+            if h is not None and not getattr(h, "_h", None):
+                raise ValueError(f"indexes[{g}] has been freed")          # NULL would quietly mean an empty graph
+        prior = (C.c_void_p * max(len(rows), 1))(*[None if h is None else h._h for h in indexes])
+        handles = (C.c_void_p * max(len(rows), 1))()
+        check(self._lib.vsr_hnsw_extend_partitions(self._h, len(rows), prior, _ptr(off), _ptr(flat), int(ef_construction),
+                                                   _metric(metric), int(seed), 0, handles))
+        return [HnswIndex(self, C.c_void_p(handles[g])) for g in range(len(rows))]
+
     def hnsw_forest(self, indexes):
         """HnswForest over indexes of this corpus (the list build_hnsw_partitions returns, or any others of one row format and one
         m): their graphs searched as a set, one search launch and one merge launch per call (vsr_hnsw_forest_open)."""

@@ -179,6 +179,24 @@ class Deployment:
         metric = self.metric if metric is None else metric
         return dict(zip([p for p, _ in items], self.corpus.build_hnsw_partitions(parts, m, ef_construction, metric, seed)))
 
+    def extend_partition_hnsw(self, graphs, added_docs, ef_construction=64, metric=None, seed=1):
+        """New documents for partitions that have a graph, in one call (Corpus.extend_hnsw_partitions).  graphs: {partition_id:
+        HnswIndex} as build_partition_hnsw returns it; added_docs: {partition_id: [document_id, ...]}, documents of the resident
+        corpus that the partition's graph does not hold yet (a role was granted them, or they were loaded after the build); a
+        partition's new rows are the rows of those documents.  Returns {partition_id: HnswIndex} for the partitions named in
+        added_docs: NEW indexes, the old ones untouched.  The caller frees the indexes they replace and calls use_partition_hnsw
+        again with the updated dict; the partitions' document sets (load_partitions) are the caller's to update as well."""
+        if self.doc_ids is None:
+            raise ValueError("partitions are sets of documents: the deployment was loaded without doc_ids")
+        items = sorted(((int(p), np.asarray(d, dtype=np.int64).ravel()) for p, d in added_docs.items()), key=lambda t: t[0])
+        missing = [p for p, _ in items if p not in graphs]
+        if missing:
+            raise ValueError(f"partitions {missing} have no graph to extend")
+        parts = [np.flatnonzero(np.isin(self.doc_ids, d)) for _, d in items]
+        metric = self.metric if metric is None else metric
+        out = self.corpus.extend_hnsw_partitions([graphs[p] for p, _ in items], parts, ef_construction, metric, seed)
+        return dict(zip([p for p, _ in items], out))
+
     def _partition_filter(self, pid, user_id):
         """Pure partitions (every document visible to the combination) carry no per-row test; impure ones
         get the user's permission bits (load_result_to_database.py:590-624)."""
