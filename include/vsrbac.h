@@ -696,8 +696,8 @@ int vsr_hnsw_vacuum(vsr_corpus* corpus, int m, int32_t n_elem, int32_t entry, co
  *     corpus: VSR_ERR_UNSUPPORTED, the message names sparsevec (the sparse build has no element -> row form).  flags must be 0:
  *     VSR_HNSW_BUILD_MERGE_DUPLICATES is VSR_ERR_UNSUPPORTED, any other bit VSR_ERR_INVALID.
  *   - On failure every index made so far is freed and every out[g] is NULL.  The session's guard word is left as it was found.
- * Not covered: vacuuming a partition graph in place (export it and use vsr_hnsw_vacuum).  New rows go into many partition graphs with
- * vsr_hnsw_extend_partitions below.  The graphs of a query's partitions are searched as a set by vsr_hnsw_forest_search*.  Synchronises. */
+ * Not covered: vacuuming a partition graph in place.  New rows go into many partition graphs with vsr_hnsw_extend_partitions below,
+ * deleted rows leave them with vsr_hnsw_vacuum_partitions.  The graphs of a query's partitions are searched as a set by vsr_hnsw_forest_search*.  Synchronises. */
 int vsr_hnsw_build_partitions(vsr_corpus* corpus, int n_parts,
                               const int64_t* part_off  /* [n_parts + 1], ascending, part_off[0] = 0 */,
                               const int64_t* part_rows /* [part_off[n_parts]] caller row indices */,
@@ -733,13 +733,55 @@ int vsr_hnsw_build_partitions(vsr_corpus* corpus, int n_parts,
  *     VSR_HNSW_BUILD_MERGE_DUPLICATES is VSR_ERR_UNSUPPORTED, any other bit VSR_ERR_INVALID.  A prior over another corpus, of another
  *     row format, m or bit opclass: VSR_ERR_INVALID naming the partition.
  *   - On failure every index made so far is freed and every out[g] is NULL.  The session's guard word is left as it was found.
- * Not covered: vacuuming many partitions in one call, changing a prior in place, appending rows to the resident corpus.  Synchronises. */
+ * Rows leave many partition graphs with vsr_hnsw_vacuum_partitions below.  Not covered: changing a prior in place, appending rows to
+ * the resident corpus.  Synchronises. */
 int vsr_hnsw_extend_partitions(vsr_corpus* corpus, int n_parts,
                                vsr_hnsw* const* prior   /* [n_parts], an entry may be NULL */,
                                const int64_t* new_off   /* [n_parts + 1], ascending from 0 */,
                                const int64_t* new_rows  /* [new_off[n_parts]] caller row indices */,
                                int ef_construction, int metric, uint64_t seed, uint32_t flags,
                                vsr_hnsw** out           /* [n_parts] */);
+/* vsr_hnsw_vacuum for many graphs over ONE resident corpus in one call: partition g's graph prior[g] loses the caller rows
+ * dead_rows[dead_off[g] .. dead_off[g + 1]) -- a role lost documents, documents were deleted -- and out[g] is the new index.
+ *   - out[g] is, array for array in its export, what vsr_hnsw_vacuum(ef_construction, metric, flags) makes of export(prior[g]) with graph
+ *     g's dead rows over this corpus; out_elem_map (may be NULL) holds that call's element maps back to back in partition order, a slice
+ *     of prior[g]'s n_elem entries each (none for a NULL prior), and out_stats[g] (may be NULL) its stats, except `attempts`, which
+ *     is the call's own.  The rows stay in the corpus, so no row is renumbered.  The dead rows are per graph: a row dead in graph A may
+ *     be live in graph B.
+ *   - prior[g] is any index over `corpus`; the priors are read on the device, are not modified and stay the caller's; two partitions
+ *     may name one prior, with different dead rows.  All priors share one m, taken from them: when every prior[g] is NULL the call is
+ *     refused with VSR_ERR_INVALID.  A NULL prior or one of n_elem = 0 gives the empty index.  A partition without dead rows gets a
+ *     plain copy (vsr_hnsw_vacuum's n_dead = 0), which counts as made by this library only if its prior did.  A partition all of
+ *     whose TIDs die gives the empty index.
+ *   - A dead row named twice, or one that no TID of that graph names, is harmless, as in vsr_hnsw_vacuum; one outside [0, rows) is
+ *     VSR_ERR_INVALID, the message naming the partition and the position.
+ *   - An index this library made is taken as it is.  Any other prior that loses rows is first brought to the host and put through
+ *     vsr_hnsw_vacuum's checks; a failure is VSR_ERR_INVALID naming the partition, and nothing is launched.
+ *   - How: the graphs that lose rows are joined on the device into one global element space; pass 1 looks every heap TID up in its own
+ *     graph's dead rows, sorted (memory in proportion to the dead rows); every graph keeps exactly the batches vsr_hnsw_vacuum cuts for
+ *     it alone -- the entry phase first, then its repair list under VSR_HNSW_VACUUM_BATCH -- and a round serves the next due batch of
+ *     every graph while the round's elements stay within VSR_HNSW_FOREST_BATCH (default 4096; a larger batch takes a round of its
+ *     own): one repair launch, one install, one sort and one link launch per round.  One last launch compacts every graph into
+ *     arrays of its own.  The packing into rounds changes no graph.
+ *   - One launch has one candidate capacity and one visited table: the largest any graph of the call would start with alone;
+ *     VSR_HNSW_VACUUM_CAPS, VSR_HNSW_BUILD_VISITED_SLOTS and VSR_HNSW_VACUUM_LDS apply as in vsr_hnsw_vacuum, and no result depends on
+ *     them.  An overflow in any repair restarts the whole call from the priors at the next step of vsr_hnsw_vacuum's two ladders.
+ *     NOT covered: the global-memory (spill / mixed) form of a repair has no forest form.  Where the ladders end the call returns
+ *     VSR_ERR_UNSUPPORTED, the message naming the first partition whose repair overflowed: vacuum that graph alone with
+ *     vsr_hnsw_vacuum, which has the spill form.
+ *   - Refused in vsr_hnsw_extend_partitions' codes: a sparse corpus (VSR_ERR_UNSUPPORTED, the message names sparsevec), a view corpus,
+ *     VSR_HNSW_BUILD_MERGE_DUPLICATES (VSR_ERR_UNSUPPORTED), any other flag bit, a prior over another corpus or of another row format,
+ *     m or bit opclass (VSR_ERR_INVALID naming the partition), ef_construction against m, the halfvec dimension limit.
+ *   - On failure every index made so far is freed and every out[g] is NULL.  The session's guard word is left as it was found.
+ * Not covered: changing a prior in place, sparse graphs.  Synchronises. */
+int vsr_hnsw_vacuum_partitions(vsr_corpus* corpus, int n_parts,
+                               vsr_hnsw* const* prior      /* [n_parts], an entry may be NULL */,
+                               const int64_t* dead_off     /* [n_parts + 1], ascending from 0 */,
+                               const int64_t* dead_rows    /* [dead_off[n_parts]] caller row indices */,
+                               int ef_construction, int metric, uint32_t flags,
+                               int32_t* out_elem_map       /* may be NULL: the priors' n_elem values back to back, partition order */,
+                               vsr_hnsw_vacuum_stats* out_stats /* [n_parts], may be NULL */,
+                               vsr_hnsw** out              /* [n_parts] */);
 /* A FOREST: many indexes over ONE corpus (the graphs of vsr_hnsw_build_partitions, or any others) searched as a set -- what the
  * reference's dynamic_partition_search does with the HNSW indexes of a user's role combination: search each, merge by distance, drop the
  * rows several partitions hold, keep k.  Here: ONE search launch over all (query, graph) pairs of the call and ONE merge launch.

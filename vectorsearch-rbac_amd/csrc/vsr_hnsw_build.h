@@ -101,6 +101,33 @@ struct HnswForestJoin {
                                              // all ones: none
 };
 
+// vsr_hnsw_vacuum_partitions: what the forest form of the REPAIR takes beside HnswBuildParams, HnswVacuumParams (live and the staged
+// lists over GLOBAL ids, elems = the round) and HnswForestParams (the entry point per batch slot): a fourth kernel argument, so that
+// every other launch keeps its own.  A repair that outgrows its arrays sets the guard bits as ever and leaves its graph's index here
+struct HnswForestVacuumParams {
+    const int32_t* graph = nullptr;          // [p.count] the forest graph of the batch slot's element
+    uint32_t*      first_bad = nullptr;      // min over the graphs with a repair that overflowed; all ones: none
+};
+// what pass 1 of vsr_hnsw_vacuum_partitions (hnsw_forest_vacuum_mark_kernel) reads and leaves.  Graph i's dead rows are the INTERNAL
+// rows dead[dead_off[i] .. dead_off[i + 1]), ascending: memory in proportion to the dead rows, a binary search per heap TID
+struct HnswForestVacuumCount {
+    unsigned long long removed = 0, kept = 0;   // heap TIDs deleted / left
+    unsigned long long highest = 0;          // max over the live elements other than the entry of ((level + 1) << 32) | ~local id: the highest
+                                             // level's lowest id (RemoveHeapTids' scan); 0: none
+    uint32_t n_live = 0, n_upper = 0;        // elements with a TID left, and those of them with an upper slot
+    uint32_t entry_live = 0;                 // 1: the entry point is among them
+};
+struct HnswForestVacuumMark {
+    const int32_t* dead = nullptr;
+    const int64_t* dead_off = nullptr;       // [n_graphs + 1]
+    const int32_t* entry = nullptr;          // [n_graphs] the graph's entry point, a LOCAL id
+    int32_t* live = nullptr;                 // [n_total] 1: a heap TID is left
+    int32_t* tid_count = nullptr;            // [n_total] the surviving TIDs ..
+    int32_t* tids = nullptr;                 // [n_total][HB_TIDS] .. in their old order, moved to the front, -1 padded
+    int32_t* slot_live = nullptr;            // [all upper slots] 1: the slot's owner lives (zeroed by the caller)
+    HnswForestVacuumCount* count = nullptr;  // [n_graphs], zeroed by the caller
+};
+
 // one workspace of the spill form for a graph of n elements: C, W and T (8 bytes an element each), wd (4) and the visited bitmap
 inline size_t hnsw_vacuum_spill_ws_bytes(uint32_t n)
 {
@@ -162,6 +189,32 @@ hipError_t vsr_hnsw_vacuum_mark(const vsr::HnswBuildParams& p, const int32_t* d_
 hipError_t vsr_hnsw_vacuum_renumber(const vsr::HnswBuildParams& p, const int32_t* d_live, int32_t* d_map, const int32_t* d_slot_map,
                                     uint32_t n_elem, int32_t* d_new_nbr0, int32_t* d_new_up_nbr, uint32_t new_max_level, void* d_tmp,
                                     size_t tmp_bytes, hipStream_t s);
+// vsr_hnsw_vacuum_partitions, over the joined element space of vsr_hnsw_forest_join (d_graphs[i].n_elem = d_priors[i].n_elem).
+// Pass 1 for every graph (one launch on s): reads the PRIOR arrays, so it does not wait for the join
+hipError_t vsr_hnsw_forest_vacuum_mark(const vsr::HnswForestGraph* d_graphs, const vsr::HnswForestPrior* d_priors, uint32_t n_graphs,
+                                       uint32_t n_total, const vsr::HnswForestVacuumMark& mk, hipStream_t s);
+// NeedsUpdated (one launch on s).  d_list: d_flag[i] is that of element d_list[i] (-1: 0), n of them; nullptr: of element i, n =
+// n_total, 0 for a deleted element and for d_skip[its graph] (d_skip may be nullptr)
+hipError_t vsr_hnsw_forest_vacuum_needs(const vsr::HnswBuildParams& p, const int32_t* d_live, const int32_t* d_list, uint32_t n,
+                                        const vsr::HnswForestGraph* d_graphs, uint32_t n_graphs, const int32_t* d_skip, uint8_t* d_flag,
+                                        hipStream_t s);
+// One round (p.count <= HB_BATCH_MAX elements, v.elems = f.elems): the forest repairs into v.stage_*, the install launch, the sort
+// and the link launch, all on s.  The LDS form only: v's spill fields are not read
+hipError_t vsr_hnsw_forest_vacuum_round(vsr::HnswBuildParams& p, const vsr::HnswVacuumParams& v, const vsr::HnswForestParams& f,
+                                        const vsr::HnswForestVacuumParams& fv, void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt,
+                                        uint64_t* d_val_alt, hipStream_t s);
+// The compaction of every graph (one launch on s): d_map / d_slot_map are the exclusive sums of live[] / slot_live[] over the whole
+// space; a live element's new id is d_map[e] - d_map[its graph's base], its new slot likewise.  d_graphs[i]: the NEW arrays (nbr0 and
+// up_nbr filled with -1 by the caller), base / n_elem / slot_base the OLD ones, max_level the new stride.  mk: the surviving TIDs.
+// d_elem_map[n_total]: new local id or -1.  A live list that still names a deleted element sets HB_ERR_RECORDS
+hipError_t vsr_hnsw_forest_vacuum_split(const vsr::HnswBuildParams& p, const vsr::HnswForestVacuumMark& mk, const int32_t* d_map,
+                                        const int32_t* d_slot_map, const vsr::HnswForestGraph* d_graphs, uint32_t n_graphs, uint32_t n_total,
+                                        int32_t* d_elem_map, hipStream_t s);
+// d_out = exclusive sum of d_in[0 .. n) (tmp: vsr_hnsw_vacuum_tmp_bytes(n))
+hipError_t vsr_hnsw_exclusive_sum(const int32_t* d_in, int32_t* d_out, uint32_t n, void* d_tmp, size_t tmp_bytes, hipStream_t s);
+// d_list = the i in [0, n) with d_flag[i] != 0, ascending; *d_num of them (tmp: vsr_hnsw_vacuum_tmp_bytes(n))
+hipError_t vsr_hnsw_select_flagged(const uint8_t* d_flag, uint32_t n, int32_t* d_list, int32_t* d_num, void* d_tmp, size_t tmp_bytes,
+                                   hipStream_t s);
 // vsr_hnsw_extend: fills p.dist0 / p.up_dist for the lists of elements 0 .. n_prior - 1 from the ids p.nbr0 / p.up_nbr hold (one
 // launch on s, no synchronisation).  d_up_owner[n_upper_prior]: upper slot -> its element, -1 for a slot no element names.  Every
 // id in those lists is in [-1, n_prior), lists are packed, and a neighbour on layer lc has an upper slot: the caller checked.

@@ -68,6 +68,10 @@
 // hnsw_edge_dist_kernel runs over all elements, the rounds are the partition build's from done = the prior n_elem, and
 // hnsw_forest_split_kernel<true> carries the prior TID lists over.  tests/test_gpu_hnsw_extend_partitions.py.
 //
+// Vacuuming many graphs (vsr_hnsw_vacuum_partitions): the joined element space again.  hnsw_forest_vacuum_mark_kernel is pass 1 with
+// every graph's own dead rows, hnsw_forest_vacuum_search_kernel the repair with the entry point per batch slot, a round's install,
+// sort and link launch are the vacuum's, and hnsw_forest_vacuum_split_kernel renumbers and splits.  tests/test_gpu_hnsw_vacuum_partitions.py.
+//
 // Parity definition (tests/test_gpu_index.py): recall@20 at ef_search = 40 against the exact scan >= pgvector's TAP
 // thresholds on its own case (10 000 x 3-d: 0.99; inner product 0.97), and within 0.01 of that serial build's recall on
 // the same rows; and (tests/test_gpu_hnsw_build_model.py) graph identity with the batched model, as above.
@@ -255,14 +259,19 @@ __device__ __forceinline__ int hb_select(const HnswBuildParams& p, const uint64_
 // other waves of the batch are reading.  S can outgrow any bound here (a graph with few live elements admits everything), so the
 // loss check of the sparse build is on, and so is one for a W longer than S.
 // MIXED (VAC only): the mixed attempt's form, see the end of the body
-// FOREST (vsr_hnsw_build_partitions; not with VAC): a round of many graphs that share the build arrays.  The batch is f.elems[],
+// FOREST (vsr_hnsw_build_partitions): a round of many graphs that share the build arrays.  The batch is f.elems[],
 // and the entry point and its level are those of the element's own graph, f.entry[bi] / f.entry_level[bi], where the build reads
 // p.entry / p.entry_level.  A wave whose graph has no entry yet emits nothing, as the build's first element.  Nothing else differs:
 // the LDS carve-up is the build's
+// VAC and FOREST (vsr_hnsw_vacuum_partitions): a round of the repairs of many graphs.  The batch is v.elems[] (global ids, as v.live
+// and the staged lists are indexed), the entry point the graph's own as above -- a graph with no live element left has none and its
+// wave emits nothing -- and the carve-up, T / wd over the visited table and both loss checks are the repair's.  A repair that
+// outgrows its arrays also leaves its graph's index in fv.first_bad, so that the refusal where the ladders end can name it
 template <bool IND, int ROWS, bool VAC, bool MIXED = false, bool FOREST = false>
-__device__ __forceinline__ void hb_search_body(const HnswBuildParams& p, const HnswVacuumParams& v, const HnswForestParams& f = HnswForestParams{})
+__device__ __forceinline__ void hb_search_body(const HnswBuildParams& p, const HnswVacuumParams& v, const HnswForestParams& f = HnswForestParams{},
+                                               const HnswForestVacuumParams& fv = HnswForestVacuumParams{})
 {
-    static_assert(!(VAC && FOREST), "the forest form is a build");
+    static_assert(!(MIXED && FOREST), "the forest form of the repair has no mixed attempt");
     extern __shared__ __align__(16) unsigned char smem_all[];
     const int lane = threadIdx.x & 63;
     const uint32_t wave = (uint32_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
@@ -554,6 +563,8 @@ __device__ __forceinline__ void hb_search_body(const HnswBuildParams& p, const H
     if (overflow && lane == 0) atomicOr(p.err, HB_ERR_VISITED);
     if constexpr (ROWS == ROWS_SPARSE || VAC)
         if (lost && lane == 0) atomicOr(p.err, HB_ERR_CANDIDATES);
+    if constexpr (VAC && FOREST)
+        if ((overflow || lost) && lane == 0) atomicMin(fv.first_bad, (uint32_t) fv.graph[bi]);
 }
 
 template <bool IND, int ROWS>
@@ -573,6 +584,14 @@ template <bool IND, int ROWS, bool MIXED>
 __global__ __launch_bounds__(256) void hnsw_vacuum_search_kernel(const HnswBuildParams p, const HnswVacuumParams v)
 {
     hb_search_body<IND, ROWS, true, MIXED>(p, v);
+}
+
+// the forest form of the repair (vsr_hnsw_vacuum_partitions), element -> row form: an instantiation of its own, as the two above
+template <int ROWS>
+__global__ __launch_bounds__(256) void hnsw_forest_vacuum_search_kernel(const HnswBuildParams p, const HnswVacuumParams v, const HnswForestParams f,
+                                                                        const HnswForestVacuumParams fv)
+{
+    hb_search_body<true, ROWS, true, false, true>(p, v, f, fv);
 }
 
 // ---- the spill form of the repair (vsr_hnsw_vacuum): the algorithm of hb_search_body<.., VAC = true> with everything that grows
@@ -1178,6 +1197,167 @@ __global__ __launch_bounds__(256) void hnsw_forest_held_kernel(const HnswBuildPa
     }
 }
 
+// ---- vacuuming many graphs (vsr_hnsw_vacuum_partitions): the passes of vsr_hnsw_vacuum around the repair, over the joined element
+// space.  Pass 1, one thread per global element: each of its <= 10 heap TIDs is looked up in its OWN graph's dead rows (a row dead in
+// graph A may be live in graph B), the survivors are compacted to the front in their old order, and the graph's counters take the
+// element -- per wave where the wave lies within one graph, which is all but the waves on a graph boundary ----
+__global__ __launch_bounds__(256) void hnsw_forest_vacuum_mark_kernel(const HnswForestGraph* __restrict__ graphs,
+                                                                      const HnswForestPrior* __restrict__ priors, const uint32_t n_graphs,
+                                                                      const uint32_t n_total, const HnswForestVacuumMark mk)
+{
+    const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+    const bool in = e < n_total;
+    uint32_t gi = 0, removed = 0, kept = 0, upper = 0;
+    unsigned long long high = 0;
+    if (in) {
+        gi = hb_forest_graph_of(graphs, n_graphs, e);
+        const HnswForestGraph g = graphs[gi];
+        const HnswForestPrior pr = priors[gi];
+        const uint32_t le = e - (uint32_t) g.base;
+        if (le < (uint32_t) pr.n_elem && le < (uint32_t) g.n_elem) {
+            const int32_t* dead = mk.dead + mk.dead_off[gi];
+            const uint32_t n_dead = (uint32_t) (mk.dead_off[gi + 1] - mk.dead_off[gi]);
+            const int cnt = min(max(pr.tid_count[le], 0), HB_TIDS);
+            int32_t* out = mk.tids + (size_t) e * HB_TIDS;
+            for (int t = 0; t < cnt; ++t) {
+                const int32_t row = pr.tids[(size_t) le * HB_TIDS + t];
+                uint32_t lo = 0, hi = n_dead;                                 // the first dead row >= row
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (dead[mid] < row) lo = mid + 1; else hi = mid;
+                }
+                if (!(lo < n_dead && dead[lo] == row)) out[kept++] = row;
+            }
+            for (uint32_t t = kept; t < (uint32_t) HB_TIDS; ++t) out[t] = -1;
+            removed = (uint32_t) cnt - kept;
+            mk.tid_count[e] = (int32_t) kept;
+            mk.live[e] = kept > 0;
+            if (kept > 0) {
+                const int32_t slot = pr.up_slot[le];
+                if (slot >= 0 && slot < pr.n_upper) {
+                    mk.slot_live[slot + g.slot_base] = 1;
+                    upper = 1;
+                }
+                if ((int32_t) le != mk.entry[gi])
+                    high = ((unsigned long long) (uint32_t) (max(pr.level[le], 0) + 1) << 32) | (0xFFFFFFFFu - le);
+                else
+                    mk.count[gi].entry_live = 1u;                             // (one thread a graph)
+            }
+        }
+    }
+    const uint32_t g0 = (uint32_t) __shfl((int) gi, 0);
+    if (__all(in && gi == g0)) {                                              // one graph: the wave's sums, one lane's atomics
+        uint32_t live = kept > 0;
+        for (int mm = 32; mm >= 1; mm >>= 1) {
+            removed += __shfl_xor(removed, mm);
+            kept += __shfl_xor(kept, mm);
+            upper += __shfl_xor(upper, mm);
+            live += __shfl_xor(live, mm);
+            const unsigned long long o = __shfl_xor(high, mm);
+            high = o > high ? o : high;
+        }
+        if ((threadIdx.x & 63) == 0) {
+            HnswForestVacuumCount* c = mk.count + g0;
+            if (removed) atomicAdd(&c->removed, (unsigned long long) removed);
+            if (kept) atomicAdd(&c->kept, (unsigned long long) kept);
+            if (live) atomicAdd(&c->n_live, live);
+            if (upper) atomicAdd(&c->n_upper, upper);
+            if (high) atomicMax(&c->highest, high);
+        }
+    } else if (in) {
+        HnswForestVacuumCount* c = mk.count + gi;
+        if (removed) atomicAdd(&c->removed, (unsigned long long) removed);
+        if (kept) {
+            atomicAdd(&c->kept, (unsigned long long) kept);
+            atomicAdd(&c->n_live, 1u);
+        }
+        if (upper) atomicAdd(&c->n_upper, 1u);
+        if (high) atomicMax(&c->highest, high);
+    }
+}
+
+// NeedsUpdated (hnsw_vacuum_mark_kernel's test) over the forest.  list == nullptr: flag[e] for every global element e, 0 for a deleted
+// one and for skip[its graph], the entry point (skip == nullptr: nobody is skipped); else flag[i] for element list[i] (-1: 0), which
+// is how the entry phase asks about one element a graph.  One thread per flag
+__global__ __launch_bounds__(256) void hnsw_forest_vacuum_needs_kernel(const HnswBuildParams p, const int32_t* __restrict__ live,
+                                                                       const int32_t* __restrict__ list, const uint32_t n,
+                                                                       const HnswForestGraph* __restrict__ graphs, const uint32_t n_graphs,
+                                                                       const int32_t* __restrict__ skip, uint8_t* __restrict__ flag)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const int32_t e = list ? list[i] : (int32_t) i;
+    uint8_t f = 0;
+    if (e >= 0 && live[e] != 0 && !(skip && !list && skip[hb_forest_graph_of(graphs, n_graphs, (uint32_t) e)] == e)) {
+        const int my_level = p.level[e];
+        for (int lc = 0; lc <= my_level; ++lc) {
+            float* dl;
+            const int32_t* nl = hb_list(p, (uint32_t) e, lc, &dl);
+            const uint32_t lm = lc == 0 ? 2 * p.m : p.m;
+            uint32_t j = 0;
+            for (; j < lm; ++j) {
+                const int32_t id = nl[j];
+                if (id < 0) break;
+                if (live[id] == 0) f = 1;
+            }
+            if (lc == 0 && j < lm) f = 1;
+        }
+    }
+    flag[i] = f;
+}
+
+// pass 3 for every graph, hnsw_vacuum_renumber_kernel and the split in one: one wave per global element; a live one goes to its
+// graph's own arrays under its new id map[e] - map[base] (map: the exclusive sum of live[] over the whole space, so a graph's live
+// elements ascend in old id), its upper slot likewise through slot_map, its lists renumbered at the graph's NEW stride
+// g.max_level = max(1, level of the new entry), its surviving TIDs and the first survivor's row.  g's base / n_elem / slot_base are
+// the joined ones.  A list that still names a deleted element: HB_ERR_RECORDS, never a thinner list in silence.  No workgroup barrier
+__global__ __launch_bounds__(256) void hnsw_forest_vacuum_split_kernel(const HnswBuildParams p, const HnswForestVacuumMark mk,
+                                                                       const int32_t* __restrict__ map, const int32_t* __restrict__ slot_map,
+                                                                       const HnswForestGraph* __restrict__ graphs, const uint32_t n_graphs,
+                                                                       const uint32_t n_total, int32_t* __restrict__ elem_map)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t e = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (e >= n_total) return;
+    if (mk.live[e] == 0) {
+        if (lane == 0) elem_map[e] = -1;
+        return;
+    }
+    const HnswForestGraph g = graphs[hb_forest_graph_of(graphs, n_graphs, e)];
+    const int32_t first = map[g.base];
+    const uint32_t ne = (uint32_t) (map[e] - first);
+    const int32_t slot = p.up_slot[e];
+    const int32_t ns = slot >= 0 ? slot_map[slot] - slot_map[g.slot_base] : -1;
+    const int my_level = p.level[e];
+    if (lane == 0) {
+        elem_map[e] = (int32_t) ne;
+        g.level[ne] = my_level;
+        g.elem_row[ne] = mk.tids[(size_t) e * HB_TIDS];
+        g.up_slot[ne] = ns;
+        g.tid_count[ne] = mk.tid_count[e];
+    }
+    if (lane < HB_TIDS) g.tids[(size_t) ne * HB_TIDS + lane] = mk.tids[(size_t) e * HB_TIDS + lane];
+    bool bad = false;
+    for (uint32_t j = (uint32_t) lane; j < 2 * p.m; j += 64) {
+        const int32_t id = p.nbr0[(size_t) e * 2 * p.m + j];
+        const bool alive = id >= 0 && mk.live[id] != 0;
+        bad |= id >= 0 && !alive;
+        g.nbr0[(size_t) ne * 2 * p.m + j] = alive ? map[id] - first : -1;
+    }
+    if (ns >= 0) {
+        const size_t from = (size_t) slot * p.max_level * p.m, to = (size_t) ns * (uint32_t) g.max_level * p.m;
+        const uint32_t layers = min(min((uint32_t) my_level, (uint32_t) g.max_level), p.max_level);   // (my_level <= g.max_level: the new entry
+                                                                                                      // is on the top live level)
+        for (uint32_t j = (uint32_t) lane; j < layers * p.m; j += 64) {
+            const int32_t id = p.up_nbr[from + j];
+            const bool alive = id >= 0 && mk.live[id] != 0;
+            bad |= id >= 0 && !alive;
+            g.up_nbr[to + j] = alive ? map[id] - first : -1;
+        }
+    }
+    if (bad) atomicOr(p.err, HB_ERR_RECORDS);
+}
+
 }  // namespace vsr
 
 using namespace vsr;
@@ -1327,6 +1507,93 @@ hipError_t vsr_hnsw_forest_join(const HnswBuildParams& p, const HnswForestJoin& 
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(hnsw_forest_held_kernel, dim3((n_total + 255) / 256), dim3(256), 0, s, p, j, d_graphs, d_priors, n_graphs, n_total);
     return hipGetLastError();
+}
+
+hipError_t vsr_hnsw_forest_vacuum_mark(const HnswForestGraph* d_graphs, const HnswForestPrior* d_priors, uint32_t n_graphs, uint32_t n_total,
+                                       const HnswForestVacuumMark& mk, hipStream_t s)
+{
+    if (n_total == 0) return hipSuccess;
+    if (!d_graphs || !d_priors || n_graphs == 0 || !mk.dead || !mk.dead_off || !mk.entry || !mk.live || !mk.tid_count || !mk.tids || !mk.slot_live ||
+        !mk.count)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(hnsw_forest_vacuum_mark_kernel, dim3((n_total + 255) / 256), dim3(256), 0, s, d_graphs, d_priors, n_graphs, n_total, mk);
+    return hipGetLastError();
+}
+
+hipError_t vsr_hnsw_forest_vacuum_needs(const HnswBuildParams& p, const int32_t* d_live, const int32_t* d_list, uint32_t n,
+                                        const HnswForestGraph* d_graphs, uint32_t n_graphs, const int32_t* d_skip, uint8_t* d_flag, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    if (!d_live || !d_flag || !d_graphs || n_graphs == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(hnsw_forest_vacuum_needs_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p, d_live, d_list, n, d_graphs, n_graphs, d_skip,
+                       d_flag);
+    return hipGetLastError();
+}
+
+// one round of vsr_hnsw_vacuum_partitions: vacuum_batch with the forest repairs.  No round is cut short for want of an entry point:
+// a wave whose graph has none stages empty lists and emits no record, and the sort and the link launch act on each graph as its own
+// would, because targets of different graphs are disjoint and a graph's batch keeps its order in the source-index bits
+template <int ROWS>
+static hipError_t forest_vacuum_round(HnswBuildParams& p, const HnswVacuumParams& v, const HnswForestParams& f, const HnswForestVacuumParams& fv,
+                                      void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt, uint64_t* d_val_alt, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(p.rec_count, 0, sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(p.rec_key, 0xFF, (size_t) p.rec_cap * sizeof(uint64_t), s);
+    if (e != hipSuccess) return e;
+    const size_t lds1 = (size_t) p.lds_per_wave * p.wpb;
+    if (lds1 > 64 * 1024) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_forest_vacuum_search_kernel<ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int) lds1);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_forest_vacuum_search_kernel<ROWS>), dim3((p.count + p.wpb - 1) / p.wpb), dim3(64 * p.wpb), lds1, s, p, v,
+                       f, fv);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(hnsw_vacuum_install_kernel, dim3((p.count + 3) / 4), dim3(256), 0, s, p, v);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipcub::DoubleBuffer<uint64_t> keys(p.rec_key, d_key_alt), vals(p.rec_val, d_val_alt);
+    e = hipcub::DeviceRadixSort::SortPairs(d_sort_tmp, sort_tmp_bytes, keys, vals, (int) p.rec_cap, 0, HB_KEY_BITS, s);
+    if (e != hipSuccess) return e;
+    HnswBuildParams q = p;
+    q.rec_key = keys.Current();
+    q.rec_val = vals.Current();
+    const size_t lds2 = (size_t) 4 * HB_NBR * 32;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hnsw_vacuum_link_kernel<true, ROWS>), dim3((p.rec_cap + 3) / 4), dim3(256), lds2, s, q, v.live);
+    return hipGetLastError();
+}
+
+hipError_t vsr_hnsw_forest_vacuum_round(HnswBuildParams& p, const HnswVacuumParams& v, const HnswForestParams& f, const HnswForestVacuumParams& fv,
+                                        void* d_sort_tmp, size_t sort_tmp_bytes, uint64_t* d_key_alt, uint64_t* d_val_alt, hipStream_t s)
+{
+    if (p.sparse || !p.elem_row || !v.live || !v.elems || v.elems != f.elems || !v.stage_nbr || !v.stage_dist || !f.entry || !f.entry_level ||
+        !fv.graph || !fv.first_bad || 2 * p.m > (uint32_t) HB_NBR || p.count == 0 || p.count > HB_BATCH_MAX || p.rec_cap == 0 ||
+        (size_t) p.lds_per_wave * p.wpb > HN_LDS_BUDGET)
+        return hipErrorInvalidValue;
+    if (p.bits) return forest_vacuum_round<ROWS_BIT>(p, v, f, fv, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
+    if (p.halves) return forest_vacuum_round<ROWS_HALF>(p, v, f, fv, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
+    return forest_vacuum_round<ROWS_F32>(p, v, f, fv, d_sort_tmp, sort_tmp_bytes, d_key_alt, d_val_alt, s);
+}
+
+hipError_t vsr_hnsw_forest_vacuum_split(const HnswBuildParams& p, const HnswForestVacuumMark& mk, const int32_t* d_map, const int32_t* d_slot_map,
+                                        const HnswForestGraph* d_graphs, uint32_t n_graphs, uint32_t n_total, int32_t* d_elem_map, hipStream_t s)
+{
+    if (n_total == 0) return hipSuccess;
+    if (!d_graphs || n_graphs == 0 || !p.elem_row || !mk.live || !mk.tid_count || !mk.tids || !d_map || !d_slot_map || !d_elem_map)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(hnsw_forest_vacuum_split_kernel, dim3((n_total + 3) / 4), dim3(256), 0, s, p, mk, d_map, d_slot_map, d_graphs, n_graphs, n_total,
+                       d_elem_map);
+    return hipGetLastError();
+}
+
+hipError_t vsr_hnsw_exclusive_sum(const int32_t* d_in, int32_t* d_out, uint32_t n, void* d_tmp, size_t tmp_bytes, hipStream_t s)
+{
+    return n == 0 ? hipSuccess : hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_in, d_out, (int) n, s);
+}
+
+hipError_t vsr_hnsw_select_flagged(const uint8_t* d_flag, uint32_t n, int32_t* d_list, int32_t* d_num, void* d_tmp, size_t tmp_bytes, hipStream_t s)
+{
+    return hipcub::DeviceSelect::Flagged(d_tmp, tmp_bytes, hipcub::CountingInputIterator<int32_t>(0), d_flag, d_list, d_num, (int) n, s);
 }
 
 // one repair batch of vsr_hnsw_vacuum: searches into the staging buffer, install, sort of the reverse edges, their application

@@ -1,5 +1,5 @@
 // vsr_hnsw_build_rt.hip — the host side of everything that makes an HNSW graph on the GPU: vsr_hnsw_build / _ex / _bit / _half /
-// _sparse, vsr_hnsw_extend, vsr_hnsw_build_partitions, vsr_hnsw_extend_partitions and vsr_hnsw_vacuum.  No device code: the kernels are in vsr_hnsw_build.hip
+// _sparse, vsr_hnsw_extend, vsr_hnsw_build_partitions, vsr_hnsw_extend_partitions, vsr_hnsw_vacuum and vsr_hnsw_vacuum_partitions.  No device code: the kernels are in vsr_hnsw_build.hip
 // and vsr_hnsw_dedup.hip, what is decided without a GPU in vsr_hnsw_sizing.h and vsr_hnsw_forest.h, the index object and its load
 // in vsr_hnsw_index.h / vsr_hnsw_rt.hip.  Every call is attempts under a ladder: an attempt (hnsw_build_once, hnsw_forest_once,
 // hnsw_vacuum_once) runs the whole call from the caller's arrays with `slots` visited-table entries and `caps` candidates; when a
@@ -1127,6 +1127,64 @@ struct HnswVacuumSpill {
     uint32_t waves = HV_SPILL_WAVES;         // VSR_HNSW_VACUUM_SPILL_WAVES
 };
 
+// the knobs of a vacuum call (vsr_hnsw_vacuum, vsr_hnsw_vacuum_partitions), read at every call, in this order.
+// VSR_HNSW_BUILD_VISITED_SLOTS as for the build.  VSR_HNSW_VACUUM_SPILL: unset / 1: a repair that outgrows the largest arrays the LDS
+// holds is redone in the global-memory form (one mixed attempt where the ladders end); 0: never, the refusals as they were; all: every
+// repair in that form from the first attempt.  VSR_HNSW_VACUUM_LDS=bytes: the LDS the sizing and the ladders believe in;
+// VSR_HNSW_VACUUM_SPILL_WAVES=n: the cap of the workspace pool; VSR_HNSW_VACUUM_CAPS=n: the INITIAL candidate entries;
+// VSR_HNSW_VACUUM_BATCH=n: the batch maximum
+struct HnswVacuumKnobs {
+    uint32_t slots = 0;                      // 0: not given
+    int      spill = 1;                      // 0 / 1 / 2: all
+    long     lds = 0, waves = HV_SPILL_WAVES, caps = 0, batch = HB_BATCH_MAX;   // 0: not given (lds, caps)
+    size_t   budget = HN_LDS_BUDGET;         // lds, or the default
+};
+static int hnsw_vacuum_knobs(const char* who, int ef_construction, HnswVacuumKnobs& k)
+{
+    int rc;
+    if ((rc = hnsw_env_visited_slots(who, &k.slots))) return rc;
+    auto env_int = [&](const char* name, long lo, long hi, long* v) { return hnsw_env_int(who, name, lo, hi, false, "between", "and", v); };
+    const uint32_t caps_min = (uint32_t) ef_construction + 1u;
+    if (const char* env = getenv("VSR_HNSW_VACUUM_SPILL")) {
+        if (!strcmp(env, "0")) k.spill = 0;
+        else if (!strcmp(env, "1")) k.spill = 1;
+        else if (!strcmp(env, "all")) k.spill = 2;
+        else return fail(VSR_ERR_INVALID, "%s: VSR_HNSW_VACUUM_SPILL must be 0, 1 or all (got \"%s\")", who, env);
+    }
+    if ((rc = env_int("VSR_HNSW_VACUUM_LDS", (long) hnsw_vacuum_lds_per_wave(caps_min, 256), (long) HN_LDS_BUDGET, &k.lds))) return rc;
+    if ((rc = env_int("VSR_HNSW_VACUUM_SPILL_WAVES", 1, 1L << 20, &k.waves))) return rc;
+    if (k.lds > 0) k.budget = (size_t) k.lds;
+    if ((rc = env_int("VSR_HNSW_VACUUM_CAPS", (long) caps_min, 1L << 20, &k.caps))) return rc;
+    return env_int("VSR_HNSW_VACUUM_BATCH", 1, (long) HB_BATCH_MAX, &k.batch);
+}
+// the sizes the first attempt of a vacuum of n_elem elements, n_live >= 1 of them live, runs at.  Candidates: what the build holds,
+// ef_construction + 1 + 2 m, over the live share, since W holds every deleted element met on the way to ef live ones; the result does
+// not depend on it (HB_ERR_CANDIDATES)
+static void hnsw_vacuum_initial_sizes(const HnswVacuumKnobs& k, int ef_construction, int m, int64_t n_elem, int64_t n_live, uint32_t* caps_out,
+                                      uint32_t* slots_out)
+{
+    const bool slots_given = k.slots != 0;
+    uint32_t slots = slots_given ? k.slots : hnsw_default_visited_slots(ef_construction, m);
+    const uint32_t caps_min = (uint32_t) ef_construction + 1u;
+    const size_t budget = k.budget;
+    // a budget that was given may be below the default table: the largest table beside which caps_min candidates still fit
+    while (k.lds > 0 && !slots_given && slots > 256u && hnsw_vacuum_lds_per_wave(caps_min, slots) > budget) slots /= 2u;
+    uint32_t caps;
+    if (k.caps > 0) {
+        caps = (uint32_t) k.caps;
+    } else {
+        const uint64_t base = (uint64_t) ef_construction + 1u + 2u * (uint64_t) m;
+        const uint64_t want = std::min<uint64_t>((base * (uint64_t) n_elem + (uint64_t) n_live - 1) / (uint64_t) n_live, (uint64_t) n_elem);
+        caps = (uint32_t) std::max<uint64_t>(base, std::min<uint64_t>((want + 15) & ~15ull, hnsw_vacuum_caps_fit(budget, slots)));
+        if (k.lds > 0 && hnsw_vacuum_lds_per_wave(caps, slots) > budget) caps = std::max(caps_min, hnsw_vacuum_caps_fit(budget, slots));   // (a given budget below `base`)
+    }
+    // every candidate was visited first, so a table that fills at 3/4 should hold what the candidate array is sized for
+    while (!slots_given && k.caps == 0 && slots < HB_SLOTS_MAX && (uint64_t) slots * 3u < (uint64_t) caps * 4u && hnsw_vacuum_lds_per_wave(caps, slots * 2u) <= budget)
+        slots *= 2u;
+    *caps_out = caps;
+    *slots_out = slots;
+}
+
 // One attempt with `slots` visited-table entries and `caps` candidate entries, from the caller's arrays.  *guard: as hnsw_build_once.
 // Its own: the entry phase, the repair list and the compaction
 static int hnsw_vacuum_once(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, const HnswPrior& pr, const HnswVacuumPlan& pl,
@@ -1420,50 +1478,16 @@ extern "C" int vsr_hnsw_vacuum(vsr_corpus* c, int m, int32_t n_elem, int32_t ent
         if (out_stats) *out_stats = st;
         return hnsw_load(c, expect, bit_metric, HnswGraphView{m}, out, who);
     }
-    // the knobs and the initial sizes.  Candidates: what the build holds, ef_construction + 1 + 2 m, over the live share, since
-    // W holds every deleted element met on the way to ef live ones; the result does not depend on it (HB_ERR_CANDIDATES)
-    uint32_t slots = 0;
-    if ((rc = hnsw_env_visited_slots(who, &slots))) return rc;
-    const bool slots_given = slots != 0;
-    if (slots == 0) slots = hnsw_default_visited_slots(ef_construction, m);
-    auto env_int = [&](const char* name, long lo, long hi, long* v) { return hnsw_env_int(who, name, lo, hi, false, "between", "and", v); };
-    const uint32_t caps_min = (uint32_t) ef_construction + 1u;
-    // the spill knobs.  VSR_HNSW_VACUUM_SPILL: unset / 1: a repair that outgrows the largest arrays the LDS holds is redone in the
-    // global-memory form (one mixed attempt where the ladders end); 0: never, the refusals as they were; all: every repair in that
-    // form from the first attempt.  VSR_HNSW_VACUUM_LDS=bytes: the LDS the sizing and the ladders believe in;
-    // VSR_HNSW_VACUUM_SPILL_WAVES=n: the cap of the workspace pool
+    HnswVacuumKnobs kn;
+    if ((rc = hnsw_vacuum_knobs(who, ef_construction, kn))) return rc;
+    uint32_t slots = 0, caps = 0;
+    hnsw_vacuum_initial_sizes(kn, ef_construction, m, n_elem, pl.n_live, &caps, &slots);
     HnswVacuumSpill sp;
-    int spill = 1;
-    if (const char* env = getenv("VSR_HNSW_VACUUM_SPILL")) {
-        if (!strcmp(env, "0")) spill = 0;
-        else if (!strcmp(env, "1")) spill = 1;
-        else if (!strcmp(env, "all")) spill = 2;
-        else return fail(VSR_ERR_INVALID, "%s: VSR_HNSW_VACUUM_SPILL must be 0, 1 or all (got \"%s\")", who, env);
-    }
-    long lds = 0, waves = HV_SPILL_WAVES;
-    if ((rc = env_int("VSR_HNSW_VACUUM_LDS", (long) hnsw_vacuum_lds_per_wave(caps_min, 256), (long) HN_LDS_BUDGET, &lds))) return rc;
-    if ((rc = env_int("VSR_HNSW_VACUUM_SPILL_WAVES", 1, 1L << 20, &waves))) return rc;
-    if (lds > 0) sp.lds_budget = (size_t) lds;
-    sp.waves = (uint32_t) waves;
-    const size_t budget = sp.lds_budget;
-    // a budget that was given may be below the default table: the largest table beside which caps_min candidates still fit
-    while (lds > 0 && !slots_given && slots > 256u && hnsw_vacuum_lds_per_wave(caps_min, slots) > budget) slots /= 2u;
-    long v = 0;
-    if ((rc = env_int("VSR_HNSW_VACUUM_CAPS", (long) caps_min, 1L << 20, &v))) return rc;
-    uint32_t caps;
-    if (v > 0) {
-        caps = (uint32_t) v;
-    } else {
-        const uint64_t base = (uint64_t) ef_construction + 1u + 2u * (uint64_t) m;
-        const uint64_t want = std::min<uint64_t>((base * (uint64_t) n_elem + (uint64_t) pl.n_live - 1) / (uint64_t) pl.n_live, (uint64_t) n_elem);
-        caps = (uint32_t) std::max<uint64_t>(base, std::min<uint64_t>((want + 15) & ~15ull, hnsw_vacuum_caps_fit(budget, slots)));
-        if (lds > 0 && hnsw_vacuum_lds_per_wave(caps, slots) > budget) caps = std::max(caps_min, hnsw_vacuum_caps_fit(budget, slots));   // (a given budget below `base`)
-    }
-    // every candidate was visited first, so a table that fills at 3/4 should hold what the candidate array is sized for
-    while (!slots_given && v == 0 && slots < HB_SLOTS_MAX && (uint64_t) slots * 3u < (uint64_t) caps * 4u && hnsw_vacuum_lds_per_wave(caps, slots * 2u) <= budget)
-        slots *= 2u;
-    long batch = HB_BATCH_MAX;
-    if ((rc = env_int("VSR_HNSW_VACUUM_BATCH", 1, (long) HB_BATCH_MAX, &batch))) return rc;
+    sp.lds_budget = kn.budget;
+    sp.waves = (uint32_t) kn.waves;
+    const int spill = kn.spill;
+    const size_t budget = kn.budget;
+    const long batch = kn.batch;
     // where a ladder ends with spilling on, ONE more attempt at the sizes it has, in mixed form: the repairs that fit stay on the
     // LDS kernel, the others are redone in the global-memory form, which cannot overflow
     sp.mode = spill == 2 ? HV_SPILL_ALL : HV_SPILL_NONE;
@@ -1498,6 +1522,475 @@ extern "C" int vsr_hnsw_vacuum(vsr_corpus* c, int m, int32_t n_elem, int32_t ent
                         "larger one fits the LDS: %s", who, slots, pl.n_live, n_elem, rebuild);
         }
     }
+}
+
+// ---- vsr_hnsw_vacuum_partitions: vsr_hnsw_vacuum for many graphs over one corpus.  The graphs that lose rows are joined on the device
+// into one global element space (hnsw_forest_join_kernel), pass 1 runs there for all of them with each graph's own dead rows
+// (hnsw_forest_vacuum_mark_kernel), every graph's repair batches run in shared rounds (hnsw_forest_vacuum_plan: the entry phase step
+// by step, then the repair lists), and one launch compacts every graph into arrays of its own (hnsw_forest_vacuum_split_kernel)
+
+// what the host pass and pass 1 leave for every attempt.  The device arrays are the call's, not an attempt's: no attempt changes them
+struct HnswForestVacuum {
+    int n_parts = 0;
+    std::vector<const vsr_hnsw*> prior;      // [n_parts] nullptr: no prior graph (NULL, or n_elem = 0)
+    std::vector<int> active;                 // the partitions that name dead rows, ascending: graph i of the element space is active[i]
+    std::vector<int64_t> base;               // [active + 1] graph i owns elements base[i] .. base[i + 1] - 1, its prior's numbering
+    std::vector<int32_t> slot_base;          // [active] its first upper slot
+    int32_t g_upper = 0, g_max_level = 1;    // all slots / the stride of the global upper arrays
+    std::vector<HnswForestVacuumCount> count;   // [active] pass 1's counters
+    uint32_t cap = HB_BATCH_MAX, batch = HB_BATCH_MAX;   // VSR_HNSW_FOREST_BATCH, VSR_HNSW_VACUUM_BATCH
+    size_t budget = HN_LDS_BUDGET;
+    HnswForestVacuumMark mk{};               // live, the surviving TIDs, slot_live
+    int32_t *d_map = nullptr, *d_slot_map = nullptr;   // the exclusive sums of mk.live / mk.slot_live
+    HnswForestPrior* d_priors = nullptr;     // [active]
+    // the highest live element of graph i other than its entry (a GLOBAL id, -1: none) and its level
+    int32_t highest(size_t i) const { return count[i].highest ? (int32_t) (base[i] + (0xFFFFFFFFu - (uint32_t) count[i].highest)) : -1; }
+    int32_t highest_level(size_t i) const { return count[i].highest ? (int32_t) (count[i].highest >> 32) - 1 : -1; }
+};
+
+// One attempt with `slots` visited-table entries and `caps` candidates.  *guard: as hnsw_build_once, and *bad_part then names the first
+// partition with a repair that overflowed.  On success out[g] holds every index, registered, st (may be nullptr) the repairs and batches
+// of every partition and elem_map (may be nullptr) the new ids at elem_off[g]
+static int hnsw_forest_vacuum_once(vsr_corpus* c, RowFormat expect, int m, int ef_construction, int metric, const HnswForestVacuum& fv, uint32_t slots,
+                                   uint32_t caps, uint32_t* guard, int* bad_part, vsr_hnsw_vacuum_stats* st, int32_t* elem_map,
+                                   const std::vector<int64_t>& elem_off, vsr_hnsw** out, const char* who)
+{
+    vsr_ctx* ctx = c->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n_graphs = fv.active.size(), total = (size_t) fv.base[n_graphs];
+    std::vector<HnswOwner> made((size_t) fv.n_parts);
+    std::vector<int> made_here((size_t) fv.n_parts, 1);
+    HnswAttempt at(ctx, who);
+    std::vector<HnswForestGraph> graphs;
+    std::vector<int32_t> old_entry(n_graphs, -1), hp(n_graphs, -1), new_entry(n_graphs, -1);   // GLOBAL ids; new_entry: after the entry phase
+    std::vector<int32_t> rep(n_graphs, 0), nbatch(n_graphs, 0);
+    size_t next = 0;                                                          // the next active partition
+    for (int g = 0; g < fv.n_parts; ++g) {
+        made[(size_t) g] = hnsw_new_index(c, expect, metric, m);
+        vsr_hnsw* hh = made[(size_t) g].get();
+        const vsr_hnsw* pr = fv.prior[(size_t) g];
+        if (next >= n_graphs || fv.active[next] != g) {
+            // no dead rows: the prior graph as it is, unread (vsr_hnsw_extend_partitions' rule for what the copy is worth)
+            if (const int rc = hnsw_clone_into(at, hh, pr)) return rc;
+            made_here[(size_t) g] = pr ? pr->made_here : 1;
+            continue;
+        }
+        const size_t i = next++;
+        const HnswForestVacuumCount& cn = fv.count[i];
+        old_entry[i] = (int32_t) (fv.base[i] + pr->entry);
+        if (cn.n_live > 0) {                                                  // (else: everything is deleted, the empty index)
+            hp[i] = fv.highest(i);
+            new_entry[i] = cn.entry_live ? old_entry[i] : hp[i];              // a deleted entry is replaced by the highest element
+            hh->n_elem = (int32_t) cn.n_live;
+            hh->n_upper = (int32_t) cn.n_upper;
+            hh->entry_level = cn.entry_live ? pr->entry_level : fv.highest_level(i);
+            hh->max_level = std::max(1, hh->entry_level);
+        }
+        size_t counts[7];
+        if (const int rc = hnsw_index_arrays(at, hh, counts)) return rc;
+        HNSW_TRY(hipMemsetAsync(hh->d_nbr0, 0xFF, std::max<size_t>(4, counts[2] * 4), ctx->stream));
+        HNSW_TRY(hipMemsetAsync(hh->d_up_nbr, 0xFF, std::max<size_t>(4, counts[4] * 4), ctx->stream));
+        graphs.push_back({hh->d_level, hh->d_elem_row, hh->d_nbr0, hh->d_up_slot, hh->d_up_nbr, hh->d_tid_count, hh->d_tids, (int32_t) fv.base[i],
+                          pr->n_elem, fv.slot_base[i], hh->max_level});
+    }
+    std::vector<int32_t> new_id(std::max<size_t>(total, 1), -1);
+    if (total > 0) {
+        // the element space of the partition calls, at the repair's sizes (the repaired element counts towards its own beam)
+        HnswForest fo;
+        fo.n_parts = (int) n_graphs;
+        fo.base = fv.base;
+        fo.level.assign(total, 0);
+        fo.elem_row.assign(total, 0);
+        fo.up_slot.assign(total, -1);
+        fo.g_upper = fv.g_upper;
+        fo.g_max_level = fv.g_max_level;
+        HnswForestSpace sp;
+        uint32_t build_slots = 0;
+        if (const int rc = hnsw_forest_space(at, c, expect, m, ef_construction, metric, fo, &build_slots, sp)) return rc;
+        HnswBuildParams& bp = sp.bp;
+        bp.efc = (uint32_t) ef_construction + 1u;
+        bp.caps = caps;
+        bp.hash_slots = slots;
+        if (!hnsw_lds_params(bp, HnswLadder{true, 0, fv.budget}))
+            return fail(VSR_ERR_UNSUPPORTED, "%s: %u candidates with a visited table of %u entries do not fit the LDS", who, caps, slots);
+        const uint32_t stride = (uint32_t) hnsw_rec_cap(m, fv.g_max_level);
+        const uint64_t most = std::min<uint64_t>(std::max(fv.cap, fv.batch), total);   // a round's elements at most
+        if (most * stride > 0x7FFFFFFFull)
+            return fail(VSR_ERR_UNSUPPORTED, "%s: a round of %llu elements with m = %d has too many reverse edges", who, (unsigned long long) most, m);
+        HnswRecScratch rs;                                                    // tmp also serves the repair list's compaction
+        HNSW_TRY(hnsw_rec_scratch(at, {(uint32_t) (most * stride)}, std::max<size_t>(vsr_hnsw_vacuum_tmp_bytes((uint32_t) total), 256), &rs));
+        bp.rec_count = rs.cnt;
+        HnswVacuumParams vp{};
+        vp.live = fv.mk.live;
+        vp.stage_stride = stride;
+        HNSW_TRY(at.alloc(&vp.stage_nbr, (size_t) rs.rec_cap_max));
+        HNSW_TRY(at.alloc(&vp.stage_dist, (size_t) rs.rec_cap_max));
+        HnswForestGraph* d_graphs = nullptr;
+        int32_t *d_up_owner = nullptr, *d_ask = nullptr, *d_list = nullptr, *d_num = nullptr, *d_new_id = nullptr;
+        uint8_t* d_flag = nullptr;
+        unsigned long long* d_words = nullptr;                                // [0]: HnswForestJoin::held; [1]: bad (low word); [2]: first_bad (low word)
+        HNSW_TRY(at.upload(&d_graphs, graphs.data(), graphs.size()));
+        const unsigned long long words[3] = {~0ull, ~0ull, ~0ull};
+        HNSW_TRY(at.upload(&d_words, words, 3));
+        HNSW_TRY(at.alloc(&d_up_owner, sp.up_slots));
+        HNSW_TRY(at.alloc(&d_ask, n_graphs));
+        HNSW_TRY(at.alloc(&d_list, total));
+        HNSW_TRY(at.alloc(&d_num, 4));
+        HNSW_TRY(at.alloc(&d_new_id, total));
+        HNSW_TRY(at.alloc(&d_flag, std::max(total, n_graphs)));
+        HNSW_TRY(hipMemsetAsync(d_up_owner, 0xFF, sp.up_slots * 4, ctx->stream));
+        HnswForestVacuumParams fvp{};
+        fvp.first_bad = reinterpret_cast<uint32_t*>(d_words + 2);
+
+        // the prior graphs into the element space, then the distance of every edge: what the link launch's re-selection reads
+        HnswForestJoin jn{};
+        jn.level = sp.level;
+        jn.elem_row = sp.elem_row;
+        jn.up_slot = sp.up_slot;
+        jn.up_owner = d_up_owner;
+        jn.n_rows = (uint32_t) c->n;
+        jn.held = d_words;
+        jn.bad = reinterpret_cast<uint32_t*>(d_words + 1);
+        HNSW_TRY(vsr_hnsw_forest_join(bp, jn, d_graphs, fv.d_priors, (uint32_t) n_graphs, (uint32_t) total, ctx->stream));
+        HNSW_TRY(hipStreamSynchronize(ctx->stream));
+        unsigned long long got[2] = {~0ull, ~0ull};
+        HNSW_TRY(hipMemcpy(got, d_words, sizeof got, hipMemcpyDeviceToHost));
+        if ((uint32_t) got[1] != 0xFFFFFFFFu) {
+            const size_t i = (size_t) (uint32_t) got[1];
+            return fail(VSR_ERR_INVALID, "%s: partition %d: the prior index holds a level, row, upper slot or neighbour outside its range", who,
+                        i < n_graphs ? fv.active[i] : -1);
+        }
+        HNSW_TRY(vsr_hnsw_edge_distances(bp, (uint32_t) total, d_up_owner, (uint32_t) fv.g_upper, ctx->stream));
+        std::vector<int32_t> level(total);                                    // a round's record slots come from its elements' levels
+        HNSW_TRY(hipMemcpy(level.data(), sp.level, total * 4, hipMemcpyDeviceToHost));
+
+        // the guard word after every round: an attempt whose arrays are too short ends where that shows
+        auto guarded = [&]() -> int {
+            HNSW_TRY(hipStreamSynchronize(ctx->stream));
+            HNSW_TRY(hnsw_take_guard(bp.err, guard));
+            if (!*guard) return VSR_OK;
+            uint32_t first = 0xFFFFFFFFu;
+            HNSW_TRY(hipMemcpy(&first, fvp.first_bad, sizeof first, hipMemcpyDeviceToHost));
+            *bad_part = first < n_graphs ? fv.active[first] : -1;
+            return VSR_OK;
+        };
+        // the rounds of a plan; piece(pc, &elems, &from): the GLOBAL elements of a batch and the element they are searched from (-1:
+        // nobody is left, the lists become empty)
+        auto run = [&](const HnswVacuumRounds& plan, auto&& piece) -> int {
+            std::vector<int32_t> hs[4];                                       // slot -> element | entry point | its level | graph
+            for (const HnswVacuumPiece& pc : plan.pieces) {
+                const int32_t* elems = nullptr;
+                int32_t from = -1;
+                piece(pc, &elems, &from);
+                for (uint32_t k = 0; k < pc.count; ++k) {
+                    hs[0].push_back(elems[k]);
+                    hs[1].push_back(from);
+                    hs[2].push_back(from >= 0 ? level[(size_t) from] : -1);
+                    hs[3].push_back(pc.graph);
+                }
+                rep[(size_t) pc.graph] += (int32_t) pc.count;
+                ++nbatch[(size_t) pc.graph];
+            }
+            const size_t n = hs[0].size();
+            if (n == 0) return VSR_OK;
+            int32_t* d_slots = nullptr;
+            HNSW_TRY(at.alloc(&d_slots, 4 * n));
+            for (int a = 0; a < 4; ++a) HNSW_TRY(hipMemcpy(d_slots + a * n, hs[a].data(), n * 4, hipMemcpyHostToDevice));
+            size_t slot = 0;
+            for (size_t r = 0; r + 1 < plan.round_first.size() && !*guard; ++r) {
+                uint64_t count = 0, cap = 0;
+                for (size_t k = plan.round_first[r]; k < plan.round_first[r + 1]; ++k) count += plan.pieces[k].count;
+                for (size_t k = slot; k < slot + count; ++k) cap += hnsw_rec_cap(m, level[(size_t) hs[0][k]]);
+                const size_t need = vsr_hnsw_build_sort_bytes((uint32_t) cap);   // (cap <= rec_cap_max: count <= most, a level <= g_max_level)
+                if (need > rs.tmp_bytes) {
+                    HNSW_TRY(at.alloc(&rs.tmp, need));
+                    rs.tmp_bytes = need;
+                }
+                HnswForestParams fp{};
+                vp.elems = fp.elems = d_slots + slot;
+                fp.entry = d_slots + n + slot;
+                fp.entry_level = d_slots + 2 * n + slot;
+                fvp.graph = d_slots + 3 * n + slot;
+                bp.count = (uint32_t) count;
+                bp.rec_cap = (uint32_t) cap;
+                bp.rec_key = rs.key[0];
+                bp.rec_val = rs.val[0];
+                HNSW_TRY(vsr_hnsw_forest_vacuum_round(bp, vp, fp, fvp, rs.tmp, rs.tmp_bytes, rs.key[1], rs.val[1], ctx->stream));
+                if (const int rc = guarded()) return rc;
+                slot += count;
+            }
+            return VSR_OK;
+        };
+        // NeedsUpdated of one element a graph (-1: not asked), on the graph as the stream leaves it
+        std::vector<uint8_t> yes(n_graphs);
+        auto ask = [&](const std::vector<int32_t>& which, std::vector<int32_t>& due) -> int {
+            HNSW_TRY(hipMemcpy(d_ask, which.data(), n_graphs * 4, hipMemcpyHostToDevice));
+            HNSW_TRY(vsr_hnsw_forest_vacuum_needs(bp, fv.mk.live, d_ask, (uint32_t) n_graphs, d_graphs, (uint32_t) n_graphs, nullptr, d_flag, ctx->stream));
+            HNSW_TRY(hipStreamSynchronize(ctx->stream));
+            HNSW_TRY(hipMemcpy(yes.data(), d_flag, n_graphs, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < n_graphs; ++i) due[i] = yes[i] != 0;
+            return VSR_OK;
+        };
+        // the entry phase (RepairGraphEntryPoint) of every graph, batches of one: the highest element from the entry as it is, deleted
+        // or not; then a live entry from the highest element
+        HnswVacuumRounds plan;
+        std::vector<int32_t> due(n_graphs, 0), live_entry(n_graphs, -1);
+        if (const int rc = ask(hp, due)) return rc;
+        hnsw_forest_vacuum_plan((int) n_graphs, due.data(), nullptr, fv.batch, fv.cap, plan);
+        if (const int rc = run(plan, [&](const HnswVacuumPiece& pc, const int32_t** elems, int32_t* from) {
+                *elems = &hp[(size_t) pc.graph];
+                *from = old_entry[(size_t) pc.graph];
+            }))
+            return rc;
+        if (*guard) return VSR_OK;
+        for (size_t i = 0; i < n_graphs; ++i) live_entry[i] = fv.count[i].entry_live ? old_entry[i] : -1;
+        if (const int rc = ask(live_entry, due)) return rc;
+        hnsw_forest_vacuum_plan((int) n_graphs, due.data(), nullptr, fv.batch, fv.cap, plan);
+        if (const int rc = run(plan, [&](const HnswVacuumPiece& pc, const int32_t** elems, int32_t* from) {
+                *elems = &live_entry[(size_t) pc.graph];
+                *from = hp[(size_t) pc.graph];
+            }))
+            return rc;
+        if (*guard) return VSR_OK;
+        // the main phase: every graph's repair list once, after the entry phase.  The list ascends in global id, so a graph's is a run
+        HNSW_TRY(hipMemcpy(d_ask, new_entry.data(), n_graphs * 4, hipMemcpyHostToDevice));
+        HNSW_TRY(vsr_hnsw_forest_vacuum_needs(bp, fv.mk.live, nullptr, (uint32_t) total, d_graphs, (uint32_t) n_graphs, d_ask, d_flag, ctx->stream));
+        HNSW_TRY(vsr_hnsw_select_flagged(d_flag, (uint32_t) total, d_list, d_num, rs.tmp, rs.tmp_bytes, ctx->stream));
+        HNSW_TRY(hipStreamSynchronize(ctx->stream));
+        int32_t n_list = 0;
+        HNSW_TRY(hipMemcpy(&n_list, d_num, 4, hipMemcpyDeviceToHost));
+        std::vector<int32_t> list((size_t) std::max(n_list, 1));
+        if (n_list > 0) HNSW_TRY(hipMemcpy(list.data(), d_list, (size_t) n_list * 4, hipMemcpyDeviceToHost));
+        std::vector<int64_t> list_off(n_graphs + 1, 0), n_repair(n_graphs, 0);
+        for (size_t i = 0; i < n_graphs; ++i) {
+            list_off[i + 1] = std::lower_bound(list.begin(), list.begin() + n_list, (int32_t) fv.base[i + 1]) - list.begin();
+            n_repair[i] = list_off[i + 1] - list_off[i];
+        }
+        hnsw_forest_vacuum_plan((int) n_graphs, nullptr, n_repair.data(), fv.batch, fv.cap, plan);
+        if (const int rc = run(plan, [&](const HnswVacuumPiece& pc, const int32_t** elems, int32_t* from) {
+                *elems = list.data() + list_off[(size_t) pc.graph] + pc.first;
+                *from = new_entry[(size_t) pc.graph];
+            }))
+            return rc;
+        if (*guard) return VSR_OK;
+        // pass 3: every graph compacted into its own arrays
+        HNSW_TRY(vsr_hnsw_forest_vacuum_split(bp, fv.mk, fv.d_map, fv.d_slot_map, d_graphs, (uint32_t) n_graphs, (uint32_t) total, d_new_id, ctx->stream));
+        if (const int rc = guarded()) return rc;                              // (HB_ERR_RECORDS: a live list still named a deleted element)
+        if (*guard) return VSR_OK;
+        HNSW_TRY(hipMemcpy(new_id.data(), d_new_id, total * 4, hipMemcpyDeviceToHost));
+    }
+    HNSW_TRY(hipStreamSynchronize(ctx->stream));
+    at.free_all();
+    for (size_t i = 0; i < n_graphs; ++i) {
+        const int g = fv.active[i];
+        if (new_entry[i] >= 0) made[(size_t) g]->entry = new_id[(size_t) new_entry[i]];
+        if (st) {
+            st[g].elements_repaired = rep[i];
+            st[g].batches = nbatch[i];
+        }
+        if (elem_map) std::copy(new_id.begin() + fv.base[i], new_id.begin() + fv.base[i + 1], elem_map + elem_off[(size_t) g]);
+    }
+    for (int g = 0; g < fv.n_parts; ++g) out[g] = hnsw_register(std::move(made[(size_t) g]), made_here[(size_t) g]);
+    return VSR_OK;
+}
+
+// the attempts of vsr_hnsw_vacuum_partitions under vsr_hnsw_vacuum's two ladders, hnsw_forest_ladder's sibling: once(slots, caps,
+// &guard, &bad_part) runs the whole call from the priors.  The forest has no global-memory form of a repair: where a ladder ends the
+// call is refused, naming the first partition whose repair overflowed
+template <class Once>
+static int hnsw_forest_vacuum_ladder(size_t budget, uint32_t slots, uint32_t caps, const char* who, Once once)
+{
+    HnswLadder ladder{true, 0, budget};
+    const char* alone = "vacuum that graph alone with vsr_hnsw_vacuum, which redoes such a repair in device memory";
+    for (;;) {
+        uint32_t guard = 0;
+        int bad_part = -1;
+        const int rc = once(slots, caps, &guard, &bad_part);
+        if (rc != VSR_OK || guard == 0) return rc;
+        ladder.caps_ceiling = hnsw_vacuum_caps_fit(budget, slots);
+        switch (hnsw_ladder_step(ladder, guard, &caps, &slots)) {
+        case HB_LADDER_ON: break;
+        case HB_LADDER_RECORDS:
+            return fail(VSR_ERR_UNSUPPORTED, "%s: the repair dropped reverse edges or left a list that names a deleted element: the graphs would be "
+                        "incomplete", who);
+        case HB_LADDER_CANDIDATES:
+            return fail(VSR_ERR_UNSUPPORTED, "%s: partition %d: a layer search of the repair holds more than %u candidates and no longer candidate "
+                        "array fits the LDS: %s", who, bad_part, caps, alone);
+        case HB_LADDER_VISITED:
+            return fail(VSR_ERR_UNSUPPORTED, "%s: partition %d: a layer search of the repair fills its visited table of %u entries and no larger one "
+                        "fits the LDS: %s", who, bad_part, slots, alone);
+        }
+    }
+}
+
+extern "C" int vsr_hnsw_vacuum_partitions(vsr_corpus* c, int n_parts, vsr_hnsw* const* prior, const int64_t* dead_off, const int64_t* dead_rows,
+                                          int ef_construction, int metric, uint32_t flags, int32_t* out_elem_map,
+                                          vsr_hnsw_vacuum_stats* out_stats, vsr_hnsw** out)
+{
+    const char* who = "vsr_hnsw_vacuum_partitions";
+    if (out)
+        for (int g = 0; g < n_parts; ++g) out[g] = nullptr;
+    if (!c || n_parts < 0 || (n_parts > 0 && (!out || !dead_off || !prior))) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
+    const RowFormat expect = c->format;
+    if (expect == RowFormat::SPARSE)
+        return fail(VSR_ERR_UNSUPPORTED,
+                    "%s: a sparsevec corpus is not supported (the sparse build has no element -> row form): rebuild every partition's graph with "
+                    "vsr_hnsw_build_sparse over a corpus of its rows", who);
+    if (flags & VSR_HNSW_BUILD_MERGE_DUPLICATES)
+        return fail(VSR_ERR_UNSUPPORTED, "%s: VSR_HNSW_BUILD_MERGE_DUPLICATES is not supported: a vacuum folds no rows", who);
+    if (flags) return fail(VSR_ERR_INVALID, "%s: unknown flag bits 0x%x", who, flags);
+    if (c->base) return fail(VSR_ERR_INVALID, "%s: the corpus is a view", who);
+    HnswForestVacuum fv;
+    long cap = HB_BATCH_MAX;
+    if (const int rc = hnsw_env_int(who, "VSR_HNSW_FOREST_BATCH", 1, (long) HB_BATCH_MAX, false, "a number from", "to", &cap)) return rc;
+    fv.cap = (uint32_t) cap;
+    if (n_parts == 0) return VSR_OK;
+    // m is the priors', as in vsr_hnsw_extend_partitions
+    int m = 0;
+    for (int g = 0; g < n_parts; ++g) {
+        const vsr_hnsw* h = prior[g];
+        if (!h) continue;
+        if (h->corpus != c) return fail(VSR_ERR_INVALID, "%s: partition %d: the prior index is over another corpus", who, g);
+        if (h->format != expect) return fail(VSR_ERR_INVALID, "%s: partition %d: the prior index is of another row format than the corpus", who, g);
+        if (m == 0) m = h->m;
+        if (h->m != m) return fail(VSR_ERR_INVALID, "%s: partition %d: the prior index has m = %d, the ones before it m = %d", who, g, h->m, m);
+        if (expect == RowFormat::BIT && h->bit_metric != metric)
+            return fail(VSR_ERR_INVALID, "%s: partition %d: the prior index's opclass is metric %d, not %d", who, g, h->bit_metric, metric);
+    }
+    if (m == 0) return fail(VSR_ERR_INVALID, "%s: every prior index is NULL, so m is not known and there is nothing to vacuum", who);
+    vsr_hnsw* none = nullptr;
+    if (const int rc = hnsw_build_check(c, expect, m, ef_construction, metric, flags, &none, who)) return rc;
+    if (c->n > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "%s: too many elements", who);
+    HnswVacuumKnobs kn;
+    if (const int rc = hnsw_vacuum_knobs(who, ef_construction, kn)) return rc;
+    fv.batch = (uint32_t) kn.batch;
+    fv.budget = kn.budget;
+    // the dead rows: every graph's own, as internal rows, ascending.  A row named twice or one no TID names is harmless, as in vsr_hnsw_vacuum
+    if (dead_off[0] != 0) return fail(VSR_ERR_INVALID, "%s: dead_off[0] is %lld, not 0", who, (long long) dead_off[0]);
+    for (int g = 0; g < n_parts; ++g)
+        if (dead_off[g + 1] < dead_off[g])
+            return fail(VSR_ERR_INVALID, "%s: dead_off does not ascend at partition %d (%lld after %lld)", who, g, (long long) dead_off[g + 1],
+                        (long long) dead_off[g]);
+    if (dead_off[n_parts] > 0 && !dead_rows) return fail(VSR_ERR_INVALID, "%s: NULL argument", who);
+    if (dead_off[n_parts] > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "%s: too many dead rows", who);
+    const std::vector<int32_t> inv = hnsw_row_map(c);
+    for (int g = 0; g < n_parts; ++g)
+        for (int64_t i = dead_off[g]; i < dead_off[g + 1]; ++i)
+            if (dead_rows[i] < 0 || dead_rows[i] >= c->n)
+                return fail(VSR_ERR_INVALID, "%s: partition %d, position %lld: dead row %lld is outside [0, %lld)", who, g, (long long) (i - dead_off[g]),
+                            (long long) dead_rows[i], (long long) c->n);
+    HIPCHK(hipSetDevice(c->ctx->device));
+    fv.n_parts = n_parts;
+    fv.prior.assign((size_t) n_parts, nullptr);
+    fv.base.assign(1, 0);
+    std::vector<vsr_hnsw_vacuum_stats> stats((size_t) n_parts, vsr_hnsw_vacuum_stats{});
+    std::vector<int64_t> elem_off((size_t) n_parts + 1, 0), d_off(1, 0);
+    std::vector<int32_t> dead, entries, counts;
+    std::vector<HnswForestGraph> bare;
+    std::vector<HnswForestPrior> priors;
+    std::map<const vsr_hnsw*, int> checked;
+    for (int g = 0; g < n_parts; ++g) {
+        const vsr_hnsw* h = prior[g] && prior[g]->n_elem > 0 ? prior[g] : nullptr;
+        fv.prior[(size_t) g] = h;
+        elem_off[(size_t) g + 1] = elem_off[(size_t) g] + (h ? h->n_elem : 0);
+        if (!h) continue;                                                     // the empty index
+        if (dead_off[g + 1] == dead_off[g]) {                                 // a plain copy: its map is the identity, its TIDs all stay
+            counts.resize((size_t) h->n_elem);
+            HIPCHK(hipMemcpy(counts.data(), h->d_tid_count, (size_t) h->n_elem * 4, hipMemcpyDeviceToHost));
+            for (int32_t t : counts) stats[(size_t) g].tuples_kept += t;
+            for (int32_t e = 0; out_elem_map && e < h->n_elem; ++e) out_elem_map[elem_off[(size_t) g] + e] = e;
+            continue;
+        }
+        if (!h->made_here && !checked.count(h)) {
+            if (const int rc = hnsw_forest_check_prior(c, h, g, who)) return rc;
+            checked[h] = 1;
+        }
+        if (h->entry < 0 || h->entry >= h->n_elem || h->max_level < 1 || h->n_upper < 0)
+            return fail(VSR_ERR_INVALID, "%s: partition %d: bad graph arrays", who, g);
+        if (fv.base.back() + h->n_elem > 0x7FFFFFF0ll) return fail(VSR_ERR_UNSUPPORTED, "%s: too many elements", who);
+        fv.active.push_back(g);
+        HnswForestGraph bg{};
+        bg.base = (int32_t) fv.base.back();
+        bg.n_elem = h->n_elem;
+        bg.slot_base = fv.g_upper;
+        bare.push_back(bg);
+        HnswForestPrior fp{};
+        fp.level = h->d_level; fp.elem_row = h->d_elem_row; fp.nbr0 = h->d_nbr0; fp.up_slot = h->d_up_slot; fp.up_nbr = h->d_up_nbr;
+        fp.tid_count = h->d_tid_count; fp.tids = h->d_tids;
+        fp.n_elem = h->n_elem; fp.n_upper = h->n_upper; fp.max_level = h->max_level;
+        priors.push_back(fp);
+        entries.push_back(h->entry);
+        fv.slot_base.push_back(fv.g_upper);
+        fv.base.push_back(fv.base.back() + h->n_elem);
+        fv.g_upper += h->n_upper;
+        fv.g_max_level = std::max(fv.g_max_level, h->max_level);
+        for (int64_t i = dead_off[g]; i < dead_off[g + 1]; ++i) dead.push_back(inv[(size_t) dead_rows[i]]);
+        std::sort(dead.begin() + d_off.back(), dead.end());
+        d_off.push_back((int64_t) dead.size());
+    }
+    const size_t n_graphs = fv.active.size(), total = (size_t) fv.base.back();
+    // pass 1 on the device, once for all attempts: the surviving TIDs, which elements live, each graph's counters and the renumbering
+    HnswAttempt at(c->ctx, who);
+    uint32_t slots = 0, caps = 0;
+    if (n_graphs > 0) {
+        HnswForestGraph* d_bare = nullptr;
+        int32_t *d_dead = nullptr, *d_entry = nullptr;
+        int64_t* d_dead_off = nullptr;
+        unsigned char* d_tmp = nullptr;
+        const size_t up_slots = (size_t) std::max(fv.g_upper, 1), tmp_bytes = std::max<size_t>(vsr_hnsw_vacuum_tmp_bytes((uint32_t) std::max(total, up_slots)), 256);
+        HNSW_TRY(at.upload(&d_bare, bare.data(), n_graphs));
+        HNSW_TRY(at.upload(&fv.d_priors, priors.data(), n_graphs));
+        HNSW_TRY(at.upload(&d_dead, dead.data(), dead.size()));
+        HNSW_TRY(at.upload(&d_dead_off, d_off.data(), d_off.size()));
+        HNSW_TRY(at.upload(&d_entry, entries.data(), n_graphs));
+        HNSW_TRY(at.alloc(&fv.mk.live, total));
+        HNSW_TRY(at.alloc(&fv.mk.tid_count, total));
+        HNSW_TRY(at.alloc(&fv.mk.tids, total * HB_TIDS));
+        HNSW_TRY(at.alloc(&fv.mk.slot_live, up_slots));
+        HNSW_TRY(at.alloc(&fv.mk.count, n_graphs));
+        HNSW_TRY(at.alloc(&fv.d_map, total));
+        HNSW_TRY(at.alloc(&fv.d_slot_map, up_slots));
+        HNSW_TRY(at.alloc(&d_tmp, tmp_bytes));
+        fv.mk.dead = d_dead;
+        fv.mk.dead_off = d_dead_off;
+        fv.mk.entry = d_entry;
+        hipStream_t s = c->ctx->stream;
+        HNSW_TRY(hipMemsetAsync(fv.mk.slot_live, 0, up_slots * 4, s));
+        HNSW_TRY(hipMemsetAsync(fv.mk.count, 0, n_graphs * sizeof(HnswForestVacuumCount), s));
+        HNSW_TRY(vsr_hnsw_forest_vacuum_mark(d_bare, fv.d_priors, (uint32_t) n_graphs, (uint32_t) total, fv.mk, s));
+        HNSW_TRY(vsr_hnsw_exclusive_sum(fv.mk.live, fv.d_map, (uint32_t) total, d_tmp, tmp_bytes, s));
+        HNSW_TRY(vsr_hnsw_exclusive_sum(fv.mk.slot_live, fv.d_slot_map, (uint32_t) up_slots, d_tmp, tmp_bytes, s));
+        HNSW_TRY(hipStreamSynchronize(s));
+        fv.count.resize(n_graphs);
+        HNSW_TRY(hipMemcpy(fv.count.data(), fv.mk.count, n_graphs * sizeof(HnswForestVacuumCount), hipMemcpyDeviceToHost));
+        // one launch has one candidate capacity and one table: the largest any graph of the call would start with alone
+        for (size_t i = 0; i < n_graphs; ++i) {
+            const HnswForestVacuumCount& cn = fv.count[i];
+            vsr_hnsw_vacuum_stats& st = stats[(size_t) fv.active[i]];
+            st.tuples_removed = (int64_t) cn.removed;
+            st.tuples_kept = (int64_t) cn.kept;
+            st.elements_removed = priors[i].n_elem - (int32_t) cn.n_live;
+            if (cn.n_live == 0) continue;
+            uint32_t s1 = 0, c1 = 0;
+            hnsw_vacuum_initial_sizes(kn, ef_construction, m, priors[i].n_elem, cn.n_live, &c1, &s1);
+            caps = std::max(caps, c1);
+            slots = std::max(slots, s1);
+        }
+    }
+    const bool repairs = caps > 0;                                            // (else no graph has a live element to repair)
+    if (!repairs) hnsw_vacuum_initial_sizes(kn, ef_construction, m, 1, 1, &caps, &slots);
+    int attempts = 0;
+    const int rc = hnsw_forest_vacuum_ladder(fv.budget, slots, caps, who, [&](uint32_t slots_, uint32_t caps_, uint32_t* guard, int* bad_part) {
+        attempts += repairs;
+        return hnsw_forest_vacuum_once(c, expect, m, ef_construction, metric, fv, slots_, caps_, guard, bad_part, stats.data(), out_elem_map, elem_off,
+                                       out, who);
+    });
+    if (rc != VSR_OK) return rc;
+    for (int g = 0; out_stats && g < n_parts; ++g) {
+        out_stats[g] = stats[(size_t) g];
+        out_stats[g].attempts = attempts;
+    }
+    return VSR_OK;
 }
 
 extern "C" int vsr_hnsw_vacuum_spill_info(const vsr_hnsw* h, int32_t* spilled_repairs, int64_t* workspace_bytes)

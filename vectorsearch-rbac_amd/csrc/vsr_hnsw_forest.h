@@ -1,5 +1,6 @@
 // vsr_hnsw_forest.h -- the schedule of vsr_hnsw_build_partitions and vsr_hnsw_extend_partitions (vsr_hnsw_build_rt.hip): the batches of
-// many HNSW builds, or of many extensions, packed into shared rounds.  Plain C++, no HIP call: tests/test_hnsw_forest_cpu.py compiles this file alone with the host compiler.
+// many HNSW builds, or of many extensions, packed into shared rounds; at the end, the same for the repair batches of
+// vsr_hnsw_vacuum_partitions (hnsw_forest_vacuum_plan, tests/test_hnsw_forest_vacuum_cpu.py).  Plain C++, no HIP call: tests/test_hnsw_forest_cpu.py compiles this file alone with the host compiler.
 //
 // All partitions live in one global element space: partition g owns elements base[g] .. base[g + 1] - 1.  Every partition keeps
 // the build's own schedule (hnsw_build_batch, vsr_hnsw_sizing.h: max(1, min(done / 8, batch_max, left)) elements, done from 0) and the
@@ -107,6 +108,53 @@ inline bool hnsw_forest_plan_from(int n_parts, const int64_t* base, const int32_
 inline bool hnsw_forest_plan(int n_parts, const int64_t* base, const int32_t* level, int m, uint32_t cap, HnswForestPlan& plan)
 {
     return hnsw_forest_plan_from(n_parts, base, level, m, cap, nullptr, nullptr, nullptr, plan);
+}
+
+// The schedule of vsr_hnsw_vacuum_partitions: the repair batches of many vacuums packed into shared rounds.  Graph g keeps exactly the
+// batches vsr_hnsw_vacuum cuts for it alone: first n_entry[g] (0 .. 2) batches of ONE element, the entry phase's repairs that are due
+// (the highest live element, then the entry point), then its n_repair[g] listed elements in batches of min(batch_max, left).  A round
+// takes the next batch of every unfinished graph, in ascending graph, while its elements stay within cap; the first unfinished
+// graph's batch is taken even when it alone is larger, so a round holds one batch or several that sum to at most cap.  A batch is
+// never split and a graph has at most one batch in a round: its next batch reads the lists this one leaves.
+// The caller plans the entry phase step by step, as each step's need shows on the device (n_repair all zero), then the main phase.
+struct HnswVacuumPiece {
+    int32_t  graph = 0;
+    int32_t  entry_step = -1;                // 0 .. n_entry - 1: that batch of the entry phase; -1: a batch of the repair list
+    int64_t  first = 0;                      // a repair batch: where it begins in the graph's list
+    uint32_t count = 0;                      // its elements
+};
+struct HnswVacuumRounds {
+    std::vector<HnswVacuumPiece> pieces;     // round by round
+    std::vector<size_t> round_first;         // [rounds + 1] round r holds pieces round_first[r] .. round_first[r + 1] - 1
+};
+// n_entry (nullptr: zeros), n_repair (nullptr: zeros): [n_graphs]; batch_max, cap: 1 .. HB_BATCH_MAX
+inline void hnsw_forest_vacuum_plan(int n_graphs, const int32_t* n_entry, const int64_t* n_repair, uint32_t batch_max, uint32_t cap,
+                                    HnswVacuumRounds& plan)
+{
+    plan = HnswVacuumRounds{};
+    plan.round_first.push_back(0);
+    std::vector<int32_t> step((size_t) std::max(n_graphs, 0), 0);
+    std::vector<int64_t> done((size_t) std::max(n_graphs, 0), 0);
+    auto entries = [&](int g) { return n_entry ? n_entry[g] : 0; };
+    auto repairs = [&](int g) { return n_repair ? n_repair[g] : (int64_t) 0; };
+    std::vector<int> open;                                                    // unfinished graphs, ascending
+    for (int g = 0; g < n_graphs; ++g)
+        if (entries(g) > 0 || repairs(g) > 0) open.push_back(g);
+    while (!open.empty()) {
+        uint64_t count = 0;
+        for (int g : open) {
+            const bool in_entry = step[(size_t) g] < entries(g);
+            const int64_t b = in_entry ? 1 : std::min<int64_t>(batch_max, repairs(g) - done[(size_t) g]);
+            if (count > 0 && count + (uint64_t) b > cap) continue;             // waits for the next round
+            plan.pieces.push_back({g, in_entry ? step[(size_t) g] : -1, in_entry ? 0 : done[(size_t) g], (uint32_t) b});
+            if (in_entry) ++step[(size_t) g]; else done[(size_t) g] += b;
+            count += (uint64_t) b;
+            if (count >= cap) break;
+        }
+        plan.round_first.push_back(plan.pieces.size());
+        open.erase(std::remove_if(open.begin(), open.end(), [&](int g) { return step[(size_t) g] >= entries(g) && done[(size_t) g] >= repairs(g); }),
+                   open.end());
+    }
 }
 
 }  // namespace vsr

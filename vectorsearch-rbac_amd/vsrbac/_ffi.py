@@ -115,6 +115,7 @@ SYMBOLS = {
                              C.POINTER(HnswVacuumStats), C.POINTER(_vp)]),
     "vsr_hnsw_build_partitions": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, C.c_uint64, C.c_uint32, _vp]),
     "vsr_hnsw_extend_partitions": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, C.c_uint64, C.c_uint32, _vp]),
+    "vsr_hnsw_vacuum_partitions": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, C.c_uint32, _vp, _vp, _vp]),
     "vsr_hnsw_forest_open": (_i, [_vp, _i, C.POINTER(_vp)]),
     "vsr_hnsw_forest_free": (_i, [_vp]),
     "vsr_hnsw_forest_set_predicate_aware": (_i, [_vp, _i]),

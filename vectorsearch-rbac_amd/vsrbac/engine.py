@@ -613,6 +613,39 @@ class Corpus:
                                                    _metric(metric), int(seed), 0, handles))
         return [HnswIndex(self, C.c_void_p(handles[g])) for g in range(len(rows))]
 
+    def vacuum_hnsw_partitions(self, priors, dead_rows_per_partition, ef_construction=64, metric=None, flags=0):
+        """vacuum_hnsw for many graphs of this corpus in one call (vsr_hnsw_vacuum_partitions): graph g, `priors[g]`, loses the
+        rows `dead_rows_per_partition[g]` (row indices of this corpus; may be empty; duplicates and rows the graph does not hold
+        are ignored).  `priors`: HnswIndex objects over this corpus of one m, or None for an empty graph; at least one must be an
+        index.  The dead rows are per graph -- a row dead in one graph may stay in another -- and an index may be named twice.
+        Returns (indexes, elem_maps, stats): NEW HnswIndex objects, one per partition, each the graph vacuum_hnsw makes of that
+        graph's export alone; per partition the new id of every old element (-1: deleted; empty for None); per partition the
+        stats dict of vacuum_hnsw (attempts is the call's).  The priors stay as they are and stay the caller's to free.  A repair
+        whose working set no LDS holds is refused (VsrError names the partition): vacuum that graph alone with vacuum_hnsw.
+        metric: None is "l2", or "hamming" on a bit corpus.  On an error no index is left behind."""
+        if metric is None:
+            metric = "hamming" if self.is_bit else "l2"
+        if len(priors) != len(dead_rows_per_partition):
+            raise ValueError(f"{len(priors)} indexes but {len(dead_rows_per_partition)} row lists")
+        rows = [np.ascontiguousarray(np.asarray(p, dtype=np.int64).ravel()) for p in dead_rows_per_partition]
+        off = np.zeros(len(rows) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([r.size for r in rows])
+        flat = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros(0, dtype=np.int64)
+        for g, h in enumerate(priors):
+            if h is not None and not getattr(h, "_h", None):
+                raise ValueError(f"priors[{g}] has been freed")           # NULL would quietly mean an empty graph
+        sizes = [0 if h is None else h.info()[0] for h in priors]
+        elem_map = np.full(max(sum(sizes), 1), -1, dtype=np.int32)
+        st = (_ffi.HnswVacuumStats * max(len(rows), 1))()
+        prior = (C.c_void_p * max(len(rows), 1))(*[None if h is None else h._h for h in priors])
+        handles = (C.c_void_p * max(len(rows), 1))()
+        check(self._lib.vsr_hnsw_vacuum_partitions(self._h, len(rows), prior, _ptr(off), _ptr(flat), int(ef_construction),
+                                                   _metric(metric), int(flags), _ptr(elem_map), st, handles))
+        ends = np.cumsum([0] + sizes)
+        maps = [elem_map[ends[g]:ends[g + 1]].copy() for g in range(len(rows))]
+        stats = [{name: int(getattr(st[g], name)) for name, _ in _ffi.HnswVacuumStats._fields_} for g in range(len(rows))]
+        return [HnswIndex(self, C.c_void_p(handles[g])) for g in range(len(rows))], maps, stats
+
     def hnsw_forest(self, indexes):
         """HnswForest over indexes of this corpus (the list build_hnsw_partitions returns, or any others of one row format and one
         m): their graphs searched as a set, one search launch and one merge launch per call (vsr_hnsw_forest_open)."""

@@ -197,6 +197,35 @@ class Deployment:
         out = self.corpus.extend_hnsw_partitions([graphs[p] for p, _ in items], parts, ef_construction, metric, seed)
         return dict(zip([p for p, _ in items], out))
 
+    def vacuum_partition_hnsw(self, graphs, removed_docs=None, deleted_docs=(), ef_construction=64, metric=None):
+        """Documents leave partition graphs, in one call (Corpus.vacuum_hnsw_partitions).  graphs: {partition_id: HnswIndex};
+        removed_docs: {partition_id: [document_id, ...]}, documents a partition lost (a role lost them: they may stay in other
+        partitions); deleted_docs: documents deleted altogether, which leave every graph given.  A partition's dead rows are the
+        rows of those documents.  Returns ({partition_id: HnswIndex}, {partition_id: stats}) for the partitions that lose
+        anything: NEW indexes, which have taken the old ones' place in `graphs`; the old ones are freed, and when a forest is
+        in use (use_partition_hnsw) it is opened again over the updated `graphs`.  The partitions' document sets
+        (load_partitions) are the caller's to update."""
+        if self.doc_ids is None:
+            raise ValueError("partitions are sets of documents: the deployment was loaded without doc_ids")
+        gone = np.asarray(deleted_docs, dtype=np.int64).ravel()
+        lost = {int(p): np.asarray(d, dtype=np.int64).ravel() for p, d in (removed_docs or {}).items()}
+        missing = [p for p in lost if p not in graphs]
+        if missing:
+            raise ValueError(f"partitions {sorted(missing)} have no graph to vacuum")
+        pids = sorted(p for p in graphs if gone.size or lost.get(int(p), gone).size)
+        dead = [np.flatnonzero(np.isin(self.doc_ids, np.concatenate([lost.get(int(p), gone[:0]), gone]))) for p in pids]
+        metric = self.metric if metric is None else metric
+        new, _, stats = self.corpus.vacuum_hnsw_partitions([graphs[p] for p in pids], dead, ef_construction, metric)
+        in_use = getattr(self, "_forest", None) is not None
+        if in_use:
+            self.close_partition_hnsw()                                     # the forest must go before its indexes
+        for p, h in zip(pids, new):
+            graphs[p].free()
+            graphs[p] = h
+        if in_use:
+            self.use_partition_hnsw(graphs)
+        return dict(zip(pids, new)), dict(zip(pids, stats))
+
     def _partition_filter(self, pid, user_id):
         """Pure partitions (every document visible to the combination) carry no per-row test; impure ones
         get the user's permission bits (load_result_to_database.py:590-624)."""
