@@ -332,6 +332,12 @@ int vsr_search_device_exact(vsr_ctx* session, vsr_corpus* corpus, const float* d
 int vsr_set_query_hint(vsr_ctx* ctx, int u8_queries);
 int vsr_set_screening(vsr_ctx* ctx, int enable);           /* default: enabled; 0 also disables threshold seeding, so
                                                               searches of that context are exact and never flag */
+/* Bit corpora: enable != 0 runs the passes that two or more queries share -- vsr_search_bit*, stage 1 of vsr_search_quantized* --
+ * on the int8 matrix cores (K2b: popcount(row & query) as a dot product of the unpacked bits) instead of K1b.  Both kernels are
+ * exact and return the same rows, distances and counts.  Default: 0 (VSR_BIT_MFMA=1 at vsr_open sets it); takes effect from the
+ * context's next search; one-query passes, index views (vsr_ivf_search_bit*, vsr_ivf_search_quantized*) and corpora that are not
+ * bit corpora are not affected. */
+int vsr_set_bit_mfma(vsr_ctx* ctx, int enable);
 int vsr_screening_check(vsr_ctx* ctx, int64_t* flagged_total, int32_t* flags_last_call, int nq);
 
 /* merge n_parts per-shard results (layout [n_parts][nq][k], as all-gathered from vsr_search_device) into the

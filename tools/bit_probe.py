@@ -13,7 +13,14 @@ the call and the scan launch is what the other two and the launch overheads cost
 
     python tools/bit_probe.py OUT_DIR [--rows 10000000] [--queries 1000] [--reps 11]
 
-Writes OUT_DIR/bitvec.json and prints it."""
+Writes OUT_DIR/bitvec.json and prints it.
+
+    python tools/bit_probe.py OUT_DIR --mfma-ab [--ab-rows 1000000] [--queries 1000]
+
+runs instead the A/B leg of K2b (vsr_mfmab.h, Context.set_bit_mfma) against K1b: 1M x 768 bits quantized from clustered rows
+(the corpus of tools/hnsw_bit_probe.py), 1000 device-resident queries per call, k = 10, unfiltered and under the tree RBAC,
+both metrics; the switch is toggled in one resident process, a K1b window and a K2b window alternating, 9 windows each; the two
+kernels' outputs of the last windows are compared.  Writes OUT_DIR/bit_mfma.json."""
 import argparse
 import ctypes
 import json
@@ -31,9 +38,76 @@ import numpy as np  # noqa: E402
 K1_FP32_TB_PER_S = 5.65                                      # README: the brute-force fp32 kernel, 10M x 128
 
 
+def mfma_ab(args):
+    """K1b against K2b (Context.set_bit_mfma) in one resident process, the two timed alternately window by window."""
+    import torch
+    import vsrbac
+    from vsrbac.datasets import gaussian_corpus, tree_rbac
+
+    n, dim, nq, k, windows, calls = args.ab_rows, 768, args.queries, 10, 9, args.ab_calls
+    dev = torch.device("cuda", 0)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    rng = np.random.default_rng(args.seed)
+    centres, _, _ = gaussian_corpus(2000, dim, seed=args.seed + 1)       # the corpus of tools/hnsw_bit_probe.py
+    x, blk, doc = gaussian_corpus(n, dim, seed=args.seed)
+    x *= np.float32(0.6)
+    x += centres[rng.integers(0, 2000, n)]
+    q = x[rng.integers(0, n, nq)] + np.float32(0.3) * rng.standard_normal((nq, dim)).astype(np.float32)
+    ctx = vsrbac.Context(0)
+    packed = np.concatenate([ctx.binary_quantize(x[i:i + 100_000]) for i in range(0, n, 100_000)])
+    del x
+    bits = ctx.load_corpus_bit(packed, dim, blk, doc)
+    rbac = tree_rbac(num_users=1000, num_roles=100, num_docs=int(doc.max()), seed=args.seed)
+    bits.load_rbac(rbac.user_roles, rbac.permissions)
+    users = rng.integers(1, 1001, nq)
+    d_q = torch.from_numpy(ctx.binary_quantize(q)).to(dev)
+    out = {kind: {"blk": torch.zeros((nq, k), dtype=torch.int64, device=dev), "doc": torch.zeros((nq, k), dtype=torch.int32, device=dev),
+                  "row": torch.zeros((nq, k), dtype=torch.int64, device=dev), "dist": torch.zeros((nq, k), dtype=torch.float32, device=dev),
+                  "cnt": torch.zeros((nq,), dtype=torch.int32, device=dev)} for kind in ("K1b", "K2b")}
+    torch.cuda.synchronize()
+    report = {"device": ctx.device_info()["name"], "rows": n, "dim": dim, "queries": nq, "k": k, "windows": windows, "calls_per_window": calls,
+              "timing": "host clock around calls_per_window calls and a synchronise, device-resident queries and results; a K1b window "
+                        "and a K2b window alternate in one process; ms per call: median / min / max over the windows"}
+    for leg, fl in (("unfiltered", None), ("tree_rbac", bits.pack_filters([bits.filter_for_user(int(u), vsrbac.RANGES) for u in users]))):
+        for metric in ("hamming", "jaccard"):
+            ms, names = {"K1b": [], "K2b": []}, {}
+
+            def window(kind):
+                ctx.set_bit_mfma(kind == "K2b")
+                o = out[kind]
+                ctx.synchronize()
+                t = time.perf_counter()
+                for _ in range(calls):
+                    bits.search_bit_device(ptr(d_q), nq, k, metric, fl, ptr(o["blk"]), ptr(o["doc"]), ptr(o["row"]), ptr(o["dist"]), ptr(o["cnt"]))
+                ctx.synchronize()
+                names[kind] = ctx.last_scan_kernel()
+                return (time.perf_counter() - t) / calls * 1e3
+
+            for kind in ("K1b", "K2b"):
+                window(kind)                                   # warm-up: code objects, workspaces, cached filters
+            for _ in range(windows):
+                for kind in ("K1b", "K2b"):
+                    ms[kind].append(window(kind))
+            same = all(torch.equal(out["K1b"][f], out["K2b"][f]) for f in out["K1b"])
+            entry = {"results_equal": bool(same)}
+            for kind in ("K1b", "K2b"):
+                v = sorted(ms[kind])
+                entry[kind] = {"median_ms": round(v[len(v) // 2], 4), "min_ms": round(v[0], 4), "max_ms": round(v[-1], 4), "kernel": names[kind]}
+            entry["k2b_over_k1b"] = round(entry["K2b"]["median_ms"] / entry["K1b"]["median_ms"], 3)
+            report.setdefault(leg, {})[metric] = entry
+            print(json.dumps({leg: {metric: entry}}), flush=True)
+    with open(os.path.join(args.out_dir, "bit_mfma.json"), "w") as f:
+        json.dump(report, f, indent=1)
+        f.write("\n")
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("out_dir")
+    ap.add_argument("--mfma-ab", action="store_true", help="only the K1b / K2b A/B leg: writes OUT_DIR/bit_mfma.json")
+    ap.add_argument("--ab-rows", type=int, default=1_000_000)
+    ap.add_argument("--ab-calls", type=int, default=20, help="calls per window of the A/B leg")
     ap.add_argument("--rows", type=int, default=10_000_000)
     ap.add_argument("--queries", type=int, default=1000)
     ap.add_argument("--k", type=int, default=100)
@@ -47,6 +121,8 @@ def main():
     from vsrbac.datasets import sample_queries, tree_rbac
 
     os.makedirs(args.out_dir, exist_ok=True)
+    if args.mfma_ab:
+        return mfma_ab(args)
     k, nq, reps, n = args.k, args.queries, max(args.reps, 3), args.rows
     dev = torch.device("cuda", 0)
     ptr = lambda t: ctypes.c_void_p(t.data_ptr())

@@ -298,6 +298,7 @@ SparseLaunch launch_scans_l2, launch_scans_ip, launch_scans_cosine, launch_scans
 PassLaunch   launch_mq_l2, launch_mq_ip, launch_mq_cosine, launch_mq_l1;
 PassLaunch   launch_mfma_l2, launch_mfma_ip, launch_mfma_cosine;
 PassLaunch   launch_mfmah_l2, launch_mfmah_ip, launch_mfmah_cosine;                      // vsr_mfmah_*.hip
+PassLaunch   launch_mfmab_hamming, launch_mfmab_jaccard;                                 // vsr_mfmab_*.hip
 PassLaunch   launch_mfmaw_l2, launch_mfmaw_ip, launch_mfmaw_cosine;                      // vsr_mfmaw_*.hip
 PassLaunch   launch_gemm_l2, launch_gemm_ip, launch_gemm_cosine;                         // vsr_gemm_*.hip
 // one query per call over the int8 planes (vsr_scan8.h): K1's top-k and in-kernel merge, a quarter of the bytes per row
@@ -332,6 +333,18 @@ inline uint32_t mfma_cap_for_k(uint32_t kp)
     return cap;                    // sorted in the staging LDS: must stay <= 8192 keys (planner gate)
 }
 inline int mfma_qmax(uint32_t stride4) { (void) stride4; return 32; }
+// K2b (vsr_mfmab.h): K2's skeleton over a bit corpus, popcount(row & query) on the int8 matrix cores; exact, so no K5r
+// follows.  metric 4 Hamming / 5 Jaccard.  K2's cap (mfma_cap_for_k) and candidate buffers (p.cand); p.qmax 16 or 32
+hipError_t launch_mfmab(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s);
+constexpr size_t MFMAB_LDS_BUDGET = 80 * 1024;             // per workgroup: two fit a CU's 160 KiB
+inline size_t mfmab_lds_bytes(uint32_t cap, int nq)
+{
+    // no image of the rows: the sort buffer of a compaction, per wave 64 row indices + popcounts, the control words
+    return (size_t) cap * 8 + (size_t) 4 * 64 * 8 + (size_t) nq * 20 + 32;
+}
+// stages of 512 bits whose unpacked query fragments stay in registers (0: streamed), by the row's stages and the pass's
+// query groups: a stage and group is 32 VGPRs, and two groups of two stages spill
+inline uint32_t mfmab_nstr(uint32_t nstage, int ng) { return nstage == 1 || (nstage == 2 && ng == 1) ? nstage : 0u; }
 // K2w (vsr_mfmaw.h): GEMM-shaped shared passes for rows of <= 256 floats -- one 64-row tile staged per WORKGROUP and
 // multiplied against up to 64 (128 at d <= 128) queries whose B fragments live in the four waves' registers.
 constexpr uint32_t MW_PEND = 256;                       // survivors a wave parks in LDS between two flushes (vsr_mfmaw.h)

@@ -49,6 +49,7 @@ struct PlanScratch {
 
 struct Width {                               // what the kernel family and pass width stage decides
     bool     mq_ok, k2_ok, k2w_ok, k2g, i8wide;
+    bool     k2b_ok;                         // bit corpus: shared passes on K2b (vsr_mfmab.h)
     int      wq;                             // K2w / K2g: query columns of a workgroup
     int      qmax;                           // queries per pass
     uint32_t keep, keep_c;                   // screening survivors kept per query: fine planes, coarse planes
@@ -139,6 +140,8 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     // (a halfvec corpus has fp16 rows only: K1h or, under K2's gates, K2h -- K2 on the f16 matrix cores, vsr_mfmah.h; never
     // K1m, which reads fp32 rows, nor K2w / K2g / int8, which read planes it does not have)
     // (a bit corpus has packed bits only and an exact integer kernel, K1b: as with screening off, nothing else applies)
+    // (... or, switched on by vsr_set_bit_mfma, K2b for its shared passes: the int8 matrix cores on the unpacked bits, exact too.  Not a
+    // list-ordered view, whose keys go through the rank map: K3b and K3q's stage 1 stay on K1b)
     // (a sparse corpus has CSR rows only and an exact kernel, K1s: planned like a bit corpus; the call's table size bounds the pass)
     const bool f32 = c->format == RowFormat::F32, half = c->format == RowFormat::HALF;
     w.mq_ok = f32 && mq_supported(c->dim) && mq_qmax(c->dim) >= 4 && !ctx->no_mq;
@@ -168,7 +171,12 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     // 1.10 -> 1.39 ms
     if (w.wq > 64 && !w.k2g && !w.i8wide && !mostly_in_parts_over(gend, 64, true)) w.wq = 64;
     const int legacy_qb = ctx->max_qb_set ? ctx->max_qb : 16;
+    // K2b: 32 queries per pass, 16 when the LDS beside the sort buffer of that k holds the control words of 16 only, else K1b
+    const uint32_t k2b_cap = mfma_cap_for_k((uint32_t) in.k);
+    const int k2b_q = mfmab_lds_bytes(k2b_cap, 32) <= MFMAB_LDS_BUDGET ? 32 : mfmab_lds_bytes(k2b_cap, 16) <= MFMAB_LDS_BUDGET ? 16 : 0;
+    w.k2b_ok = c->format == RowFormat::BIT && ctx->bit_mfma && !c->d_rank && k2b_q > 0;
     if (w.k2w_ok) w.qmax = ctx->max_qb_set ? std::min(ctx->max_qb, w.wq) : w.wq;
+    else if (w.k2b_ok) w.qmax = ctx->max_qb_set ? std::min(ctx->max_qb, k2b_q) : k2b_q;
     else if (w.k2_ok) w.qmax = std::min(legacy_qb, mfma_qmax(c->stride4));
     else if (w.mq_ok) w.qmax = std::min(legacy_qb, mq_qmax(c->dim));
     else
@@ -237,11 +245,12 @@ void set_family(const PlanIn& in, const Width& w, uint32_t widest, Plan& plan)
     plan.k2 = plan.qi == 4 && w.k2_ok;
     plan.k2w = plan.k2 && w.k2w_ok;
     plan.mq = plan.qi == 4 && w.mq_ok && !plan.k2;
+    plan.k2b = plan.qi == 4 && w.k2b_ok;                    // exact: keep stays k, no K5r
     plan.keep = plan.k2 ? w.keep : (uint32_t) in.k;
     // K1s: a table that does not fit LDS beside one candidate list is read from global memory, and then qmax = QI
     plan.sparse_global = in.c->format == RowFormat::SPARSE && !scan_sparse_table_in_lds(in.ctx->sparse_slots, in.k);
     if (plan.k2w) plan.qmax = (uint32_t) w.wq;              // query slots per workgroup: one (long rows: two) 16-query groups per wave
-    else if (plan.k2) plan.qmax = plan.qmax > 16 ? 32 : 16;
+    else if (plan.k2 || plan.k2b) plan.qmax = plan.qmax > 16 ? 32 : 16;
     plan.int8 = plan.k2w && in.c->d_scr8 && in.metric == VSR_METRIC_L2 && in.ctx->int8_this_call;
     if (plan.int8) plan.keep = (uint32_t) std::max(in.k, 32);  // exact screening: no second half of survivors to re-rank
     plan.k2g = plan.k2w && w.k2g && !plan.int8;
@@ -433,7 +442,7 @@ void emit_groups(const PlanIn& in, bool i8wide, const LaunchSize& ls, PlanScratc
                                        ? (int64_t) ((__int128) p.rows * (__int128) c->sp_entries * 8 / std::max<int64_t>(c->n, 1))
                                        : p.rows * format_row_bytes(c->format, c->dim);
         plan.scan_bytes += rows_bytes + (g.bitmap ? (p.rows + 7) / 8 : 0) + (int64_t) p.q_count * in.k * 12 +
-                           (plan.k2 ? p.rows * 4 : 0);     // K2 also reads |row|^2
+                           (plan.k2 || plan.k2b ? p.rows * 4 : 0);     // K2 also reads |row|^2 (K2b: the popcounts)
     }
     plan.n_scan_lists = plan.n_partial;
     plan.n_launch = plan.n_blocks;
@@ -733,7 +742,7 @@ bool vsr::make_plan(const vsr_ctx* ctx, const vsr_corpus* c, int nq, int k, int 
         const bool thin = first_stride(in, plan) != ctx->sample_stride;
         const LaunchSize ls = size_launch(in, plan, s.passes);
         emit_groups(in, w.i8wide, ls, s, plan);
-        if (plan.k2 || plan.mq) map_blocks_to_xcds(s.lane, plan);
+        if (plan.k2 || plan.mq || plan.k2b) map_blocks_to_xcds(s.lane, plan);
         plan.walk = plan.walk && !plan.block_map.empty();
         if (plan.walk) build_walk_table(c->class_view.get(), plan);
         if (plan.k2w) {
@@ -779,6 +788,12 @@ std::string vsr::scan_kernel_name(const Plan& plan, const vsr_corpus* c, int met
                      plan.sparse_global ? "global" : "lds");
             break;
         case RowFormat::BIT:
+            if (plan.k2b) {
+                const int ng = plan.qmax > 16 ? 2 : 1;     // launch_mfmab_metric's choice
+                snprintf(buf, sizeof buf, "vsr::mfmab_scan_kernel<%s, NSTR=%u, NG=%d> (K2b, bit rows)", mname[metric],
+                         mfmab_nstr((c->stride4 + 3) / 4, ng), ng);
+                break;
+            }
             snprintf(buf, sizeof buf, "vsr::scanb_kernel<%s, LPR=%d, C=%d, R=%d, QI=%d> (K1b, bit rows)", mname[metric], c->shape.lpr,
                      c->shape.c, c->shape.r, plan.qi);
             break;

@@ -15,7 +15,7 @@
 // written at load, exact in fp32) and |query| from p.q_norm2 (staging), and evaluates bitutils.c:125-128 in double for the
 // lane that owns the finished row.  The ranking value is (float) of the operator's float8: a Hamming count <= 64000 is exact
 // in fp32, rounding a Jaccard value is monotone.  Nothing is screened: every result is exact by construction.
-// No matrix cores: CDNA4 has no 1-bit MFMA.
+// No matrix cores here: CDNA4 has no 1-bit MFMA (K2b, vsr_mfmab.h, runs shared passes on the int8 MFMA over unpacked bits; opt-in).
 // Not carried over from scan_kernel (this is a second kernel body: a fix to K1's top-k or overflow protocol belongs in both):
 // p.tau_init (no seeded thresholds), p.sample_stride (no sample pass) and p.fused (the one-query in-kernel merge, FusedTail, is
 // not instantiated here).  p.rank IS carried, by the VIEW instantiations (K3b, the list-ordered view of an IVFFlat index over a bit

@@ -170,6 +170,11 @@ class Context:
         halfvec corpus; K5r behind them).  False: exact kernels only (K1 / K1m, K1h), and no search of this context flags."""
         check(self._lib.vsr_set_screening(self._h, int(bool(enable))))
 
+    def set_bit_mfma(self, enable=True):
+        """Run the shared passes of this context's searches over bit corpora on the int8 matrix cores (K2b) instead of K1b.
+        Both are exact and return the same results.  Default off; one-query passes and index views stay on K1b."""
+        check(self._lib.vsr_set_bit_mfma(self._h, int(bool(enable))))
+
     def screening_check(self, nq=0):
         """(flagged queries since open, flags of the last vsr_search_device call).  Synchronises."""
         total = C.c_int64()
