@@ -338,6 +338,14 @@ int vsr_set_screening(vsr_ctx* ctx, int enable);           /* default: enabled; 
  * context's next search; one-query passes, index views (vsr_ivf_search_bit*, vsr_ivf_search_quantized*) and corpora that are not
  * bit corpora are not affected. */
 int vsr_set_bit_mfma(vsr_ctx* ctx, int enable);
+/* halfvec corpora: on != 0 runs the passes that two or more queries share -- vsr_search*, the list scans of vsr_ivf_search* over a
+ * half index -- on K2hw instead of K2h: a 64-row tile of the binary16 rows is staged once per workgroup and multiplied on the f16
+ * matrix cores against up to 64 queries per pass (K2h: 16 or 32 per wave-private tile), with threshold seeds from a sample pass
+ * and the exact re-rank on the half rows behind it.  Same screening keys, same error bound, same flag and re-run rules as K2h; the
+ * reported rows and distances are the exact kernels' either way.  Default: 0 (VSR_HALF_WIDE=1 at vsr_open sets it); takes effect
+ * from the context's next search; L1, one-query passes, rows shorter than 61 elements, a context with screening or seeding off
+ * and corpora that are not halfvec corpora are not affected. */
+int vsr_set_half_wide(vsr_ctx* ctx, int on);
 int vsr_screening_check(vsr_ctx* ctx, int64_t* flagged_total, int32_t* flags_last_call, int nq);
 
 /* merge n_parts per-shard results (layout [n_parts][nq][k], as all-gathered from vsr_search_device) into the

@@ -287,7 +287,7 @@ inline size_t scan_lds_bytes(uint32_t qmax, uint32_t cap, uint32_t stride4)
 hipError_t launch_scan(RowFormat f, const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s,
                        int sparse_lpr = 0, bool sparse_global_tab = false);
 // ... and the per-metric launchers behind the family launchers of this header (launch_scan, launch_mq, launch_mfma,
-// launch_mfmah, launch_mfmaw, launch_gemm): one translation unit per metric, for parallel builds
+// launch_mfmah, launch_mfmahw, launch_mfmaw, launch_gemm): one translation unit per metric, for parallel builds
 using ScanLaunch   = hipError_t(const ScanParams& p, int dim, int qi, uint32_t n_blocks, hipStream_t s);
 using SparseLaunch = hipError_t(const ScanParams& p, int lpr, int qi, bool global_tab, uint32_t n_blocks, hipStream_t s);
 using PassLaunch   = hipError_t(const ScanParams& p, uint32_t n_blocks, hipStream_t s);
@@ -298,6 +298,7 @@ SparseLaunch launch_scans_l2, launch_scans_ip, launch_scans_cosine, launch_scans
 PassLaunch   launch_mq_l2, launch_mq_ip, launch_mq_cosine, launch_mq_l1;
 PassLaunch   launch_mfma_l2, launch_mfma_ip, launch_mfma_cosine;
 PassLaunch   launch_mfmah_l2, launch_mfmah_ip, launch_mfmah_cosine;                      // vsr_mfmah_*.hip
+PassLaunch   launch_mfmahw_l2, launch_mfmahw_ip, launch_mfmahw_cosine;                   // vsr_mfmahw_*.hip
 PassLaunch   launch_mfmab_hamming, launch_mfmab_jaccard;                                 // vsr_mfmab_*.hip
 PassLaunch   launch_mfmaw_l2, launch_mfmaw_ip, launch_mfmaw_cosine;                      // vsr_mfmaw_*.hip
 PassLaunch   launch_gemm_l2, launch_gemm_ip, launch_gemm_cosine;                         // vsr_gemm_*.hip
@@ -362,6 +363,17 @@ inline bool mfmaw_supported(uint32_t stride4) { return stride4 >= 16 && stride4 
 // 2): 128, two groups per wave
 inline int  mfmaw_qmax(uint32_t pstride4, bool ho) { return pstride4 / 16 > (ho ? 2u : 3u) ? 128 : 64; }
 hipError_t launch_mfmaw(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s);
+// K2hw (vsr_mfmahw.h): K2w's work split over a halfvec corpus -- one 64-row tile of the resident binary16 rows staged per
+// WORKGROUP, f16 MFMA against up to 64 queries (p.q_scr: their binary16 image, as for K2h); K2w's candidate buffers, sample
+// pass and select_rerank_kernel.  Opt-in (vsr_ctx::half_wide).  lds_queries: rows of more than 2 stages (d > 256), whose
+// query chunks are staged beside the row tile
+constexpr int HW_RING = 4;                              // row-mapping ring (tiles): one tile ahead needs 3
+inline size_t mfmahw_lds_bytes(bool lds_queries)
+{
+    // two 64-row stage buffers of 16 chunks (+ two of the 64 query columns) + the row-mapping ring + per wave {value, row, column}[MW_PEND]
+    return (size_t) (lds_queries ? 4 : 2) * 64 * 16 * 16 + (size_t) HW_RING * 64 * 8 + (size_t) 4 * MW_PEND * 12;
+}
+hipError_t launch_mfmahw(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s);
 // K2g (vsr_gemm.h): long rows, passes of up to 256 queries, 256 x 256 tiles with both operands in LDS, ONE bf16 product
 // per element on the coarse planes (hi = bf16(x) only; rows padded to whole 64-element K-steps)
 constexpr uint32_t GM_QMAX = 256;

@@ -43,6 +43,11 @@ hipError_t launch_mfmah(const ScanParams& p, int metric, uint32_t n_blocks, hipS
     return launch_pass(by_metric(metric, launch_mfmah_l2, launch_mfmah_ip, launch_mfmah_cosine), p, n_blocks, s);
 }
 
+hipError_t launch_mfmahw(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s)
+{
+    return launch_pass(by_metric(metric, launch_mfmahw_l2, launch_mfmahw_ip, launch_mfmahw_cosine), p, n_blocks, s);
+}
+
 hipError_t launch_mfmab(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s)
 {
     return launch_pass(metric == 4 ? launch_mfmab_hamming : metric == 5 ? launch_mfmab_jaccard : nullptr, p, n_blocks, s);
@@ -1069,6 +1074,8 @@ __global__ __launch_bounds__(256) void rerank_kernel(const RerankParams p)
 
 // K2w: per query, the kp best of its candidate buffer (one wave, every key in registers, radix select) and then the
 // exact re-rank of those kp rows, in one launch.  A buffer that overflowed lost candidates: the query is flagged.
+// HALF (K2hw): the re-rank reads a halfvec corpus's rows
+template <bool HALF>
 __global__ __launch_bounds__(256) void select_rerank_kernel(const RerankParams p)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1090,7 +1097,7 @@ __global__ __launch_bounds__(256) void select_rerank_kernel(const RerankParams p
         if (lane == 0) s_worst = n >= p.kp ? kth : KEY_EMPTY;
     }
     __syncthreads();
-    rerank_body(p, slot, keys, np2, s_worst, cnt > p.capq || (p.qbad && p.qbad[slot]));
+    rerank_body<HALF>(p, slot, keys, np2, s_worst, cnt > p.capq || (p.qbad && p.qbad[slot]));
 }
 
 hipError_t launch_select_rerank(const RerankParams& p, uint32_t n_queries, hipStream_t s)
@@ -1098,7 +1105,8 @@ hipError_t launch_select_rerank(const RerankParams& p, uint32_t n_queries, hipSt
     if (p.capq != GQ_CAP || p.kp > GQ_MAX_KP) return hipErrorInvalidValue;
     uint32_t np2 = 2;
     while (np2 < p.kp) np2 <<= 1;
-    hipLaunchKernelGGL(select_rerank_kernel, dim3(n_queries), dim3(256), (size_t) np2 * sizeof(uint64_t), s, p);
+    if (p.rows_half) hipLaunchKernelGGL(select_rerank_kernel<true>, dim3(n_queries), dim3(256), (size_t) np2 * sizeof(uint64_t), s, p);
+    else hipLaunchKernelGGL(select_rerank_kernel<false>, dim3(n_queries), dim3(256), (size_t) np2 * sizeof(uint64_t), s, p);
     return hipGetLastError();
 }
 

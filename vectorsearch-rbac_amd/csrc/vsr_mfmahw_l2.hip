@@ -1,0 +1,11 @@
+// vsr_mfmahw_l2.hip — instantiates the K2hw kernels (workgroup-shared f16 MFMA passes over a halfvec corpus, vsr_mfmahw.h) for one metric.
+#include "vsr_mfmahw.h"
+
+namespace vsr {
+
+hipError_t launch_mfmahw_l2(const ScanParams& p, uint32_t n_blocks, hipStream_t s)
+{
+    return launch_mfmahw_metric<M_L2>(p, n_blocks, s);
+}
+
+}  // namespace vsr

@@ -16,6 +16,7 @@ struct PlanScalars {
     bool     mq = false;          // shared passes run on K1m (vsr_mq.h)
     bool     k2 = false;          // shared passes run on K2 / K2w (MFMA screening) + K5r
     bool     k2w = false;         // ... on K2w: workgroup-shared row tiles, up to 128 queries per pass (vsr_mfmaw.h)
+    bool     k2hw = false;        // ... on K2hw: K2w's work split over a halfvec corpus's own rows (vsr_mfmahw.h); implies k2w
     bool     int8 = false;        // ... on the corpus's int8 planes (L2, integer 0..255 rows and queries)
     bool     class_view = false;  // ... on the corpus's class view of the int8 planes (every pass a whole permission class)
     bool     walk = false;        // ... with the main launch's block_map rotated to where the launches in flight are reading (walk_table)

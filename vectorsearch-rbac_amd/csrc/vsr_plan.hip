@@ -50,6 +50,8 @@ struct PlanScratch {
 struct Width {                               // what the kernel family and pass width stage decides
     bool     mq_ok, k2_ok, k2w_ok, k2g, i8wide;
     bool     k2b_ok;                         // bit corpus: shared passes on K2b (vsr_mfmab.h)
+    bool     k2hw_ok;                        // halfvec corpus: shared passes on K2hw (vsr_mfmahw.h), planned as K2w's are
+    bool     wide() const { return k2w_ok || k2hw_ok; }   // one candidate buffer per query, sample pass, select + re-rank
     int      wq;                             // K2w / K2g: query columns of a workgroup
     int      qmax;                           // queries per pass
     uint32_t keep, keep_c;                   // screening survivors kept per query: fine planes, coarse planes
@@ -139,6 +141,7 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     Width w{};
     // (a halfvec corpus has fp16 rows only: K1h or, under K2's gates, K2h -- K2 on the f16 matrix cores, vsr_mfmah.h; never
     // K1m, which reads fp32 rows, nor K2w / K2g / int8, which read planes it does not have)
+    // (... or, switched on by vsr_set_half_wide, K2hw: K2w's work split and launch sequence over the half rows themselves)
     // (a bit corpus has packed bits only and an exact integer kernel, K1b: as with screening off, nothing else applies)
     // (... or, switched on by vsr_set_bit_mfma, K2b for its shared passes: the int8 matrix cores on the unpacked bits, exact too.  Not a
     // list-ordered view, whose keys go through the rank map: K3b and K3q's stage 1 stay on K1b)
@@ -150,8 +153,9 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     const bool k2_any = (f32 || (half && !ctx->no_half_mfma)) && allow_screening && ctx->screening && c->k2_safe && in.metric != VSR_METRIC_L1 &&
                         mq_supported(c->dim) && ctx->max_qb >= 16;
     w.k2w_ok = k2_any && f32 && allow_wide && c->d_scr && w.keep <= GQ_MAX_KP && !ctx->no_wide && ctx->seeding;
-    w.k2_ok = w.k2w_ok || (k2_any && mfma_cap_for_k(w.keep) <= 8192 && mfma_lds_bytes(c->stride4) <= 150 * 1024);
-    w.wq = mfmaw_qmax(c->pstride4, !c->scr_has_mid);
+    w.k2hw_ok = k2_any && half && ctx->half_wide && allow_wide && w.keep <= GQ_MAX_KP && ctx->seeding;
+    w.k2_ok = w.wide() || (k2_any && mfma_cap_for_k(w.keep) <= 8192 && mfma_lds_bytes(c->stride4) <= 150 * 1024);
+    w.wq = w.k2hw_ok ? 64 : mfmaw_qmax(c->pstride4, !c->scr_has_mid);   // (K2hw: one 16-query group per wave)
     // K2g (coarse planes, 256-query passes): when nearly all (part, query) items sit in parts seen by more than 128
     // queries -- unfiltered batches, a few big partitions -- and the coarser screen's larger survivor list fits
     w.keep_c = (uint32_t) std::max(4 * in.k, 128);
@@ -175,7 +179,7 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     const uint32_t k2b_cap = mfma_cap_for_k((uint32_t) in.k);
     const int k2b_q = mfmab_lds_bytes(k2b_cap, 32) <= MFMAB_LDS_BUDGET ? 32 : mfmab_lds_bytes(k2b_cap, 16) <= MFMAB_LDS_BUDGET ? 16 : 0;
     w.k2b_ok = c->format == RowFormat::BIT && ctx->bit_mfma && !c->d_rank && k2b_q > 0;
-    if (w.k2w_ok) w.qmax = ctx->max_qb_set ? std::min(ctx->max_qb, w.wq) : w.wq;
+    if (w.wide()) w.qmax = ctx->max_qb_set ? std::min(ctx->max_qb, w.wq) : w.wq;
     else if (w.k2b_ok) w.qmax = ctx->max_qb_set ? std::min(ctx->max_qb, k2b_q) : k2b_q;
     else if (w.k2_ok) w.qmax = std::min(legacy_qb, mfma_qmax(c->stride4));
     else if (w.mq_ok) w.qmax = std::min(legacy_qb, mq_qmax(c->dim));
@@ -184,7 +188,7 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
         case RowFormat::SPARSE: w.qmax = std::min(legacy_qb, scan_qmax_sparse(ctx->sparse_slots, in.k)); break;
         default:                w.qmax = std::min(legacy_qb, scan_qmax(c->format, c->dim, in.k));
         }
-    if (w.k2_ok && !w.k2w_ok && !ctx->max_qb_set && w.qmax >= 16 && c->stride4 > 64) {
+    if (w.k2_ok && !w.wide() && !ctx->max_qb_set && w.qmax >= 16 && c->stride4 > 64) {
         // long rows (d > 256): a pass costs mostly its row bytes, so two 16-query MFMA groups per pass (half the passes)
         // pay off -- but only when the query groups fill them (an unfiltered 1000-query batch: 17 % less time at
         // d = 768; role partitions with ~25 queries per class: 2.7x more, the second group would be mostly padding)
@@ -192,7 +196,7 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
                                         [](uint32_t cnt) { return (uint64_t) (cnt + 31) / 32 * 32; }, false);
         if (filled) w.qmax = std::min(32, mfma_qmax(c->stride4));
     }
-    w.qmax = w.k2w_ok ? std::max(16, w.qmax / 16 * 16) : w.qmax >= 4 ? w.qmax / 4 * 4 : 1;
+    w.qmax = w.wide() ? std::max(16, w.qmax / 16 * 16) : w.qmax >= 4 ? w.qmax / 4 * 4 : 1;
     return w;
 }
 
@@ -210,7 +214,7 @@ uint32_t cut_passes(const PlanIn& in, const Width& w, const std::vector<PassItem
         // K2w: a part seen by more queries than one pass holds is cut into equal passes (330 queries -> 3 x 110, not
         // 128 + 128 + 74), each a whole number of 16-query MFMA groups
         size_t per = (size_t) w.qmax;
-        if (w.k2w_ok && e - s > (size_t) w.qmax) {
+        if (w.wide() && e - s > (size_t) w.qmax) {
             const size_t n_pass = (e - s + (size_t) w.qmax - 1) / (size_t) w.qmax;
             per = std::min<size_t>((size_t) w.qmax, ((e - s + n_pass - 1) / n_pass + 15) / 16 * 16);
         }
@@ -226,7 +230,7 @@ uint32_t cut_passes(const PlanIn& in, const Width& w, const std::vector<PassItem
             // relative cost of a row of this pass: K2w passes are bound by the row stream up to ~3 query groups and by
             // the matrix pipe beyond (a 64-row tile costs 4 * groups * d/4 MFMAs), so fat passes get more workgroups
             const int64_t groups = (cnt + 15) / 16;
-            pd.cost = std::max<int64_t>(pd.rows, 1) * (w.k2w_ok ? std::max<int64_t>(32, 10 * groups) : 32);
+            pd.cost = std::max<int64_t>(pd.rows, 1) * (w.wide() ? std::max<int64_t>(32, 10 * groups) : 32);
             for (uint32_t i = 0; i < cnt; ++i) q_slots.push_back(items[b + i].slot);
             passes.push_back(pd);
             widest = std::max(widest, cnt);
@@ -243,7 +247,8 @@ void set_family(const PlanIn& in, const Width& w, uint32_t widest, Plan& plan)
     plan.qi = widest > 1 ? 4 : 1;
     plan.qmax = plan.qi == 1 ? 1 : (widest + 3) / 4 * 4;
     plan.k2 = plan.qi == 4 && w.k2_ok;
-    plan.k2w = plan.k2 && w.k2w_ok;
+    plan.k2w = plan.k2 && w.wide();
+    plan.k2hw = plan.k2w && w.k2hw_ok;
     plan.mq = plan.qi == 4 && w.mq_ok && !plan.k2;
     plan.k2b = plan.qi == 4 && w.k2b_ok;                    // exact: keep stays k, no K5r
     plan.keep = plan.k2 ? w.keep : (uint32_t) in.k;
@@ -764,7 +769,10 @@ std::string vsr::scan_kernel_name(const Plan& plan, const vsr_corpus* c, int met
     const uint32_t nstage = (c->stride4 + 15) / 16;
     if (plan.k2g)
         snprintf(buf, sizeof buf, "vsr::gemm_screen_kernel<%s, SAMPLE=false> (K2g, bf16 coarse planes)", mname[metric]);
-    else if (plan.k2w && plan.int8 && k2i)
+    else if (plan.k2hw) {
+        const uint32_t hstage = (c->stride4 / 2 + 15) / 16;    // launch_mfmahw_metric's choice
+        snprintf(buf, sizeof buf, "vsr::mfmahw_scan_kernel<%s, NSTR=%u, SAMPLE=false> (K2hw, f16 rows)", mname[metric], hstage <= 2 ? hstage : 0u);
+    } else if (plan.k2w && plan.int8 && k2i)
         snprintf(buf, sizeof buf, "vsr::i8_stream_kernel<NQG=4> (K2i, int8 planes, %s)", mname[metric]);
     else if (plan.k2w && plan.int8)
         snprintf(buf, sizeof buf, "vsr::mfma_wide_kernel<%s, NCH=1, SAMPLE=false, PL=int8> (K2w, int8 planes)", mname[metric]);

@@ -175,6 +175,11 @@ class Context:
         Both are exact and return the same results.  Default off; one-query passes and index views stay on K1b."""
         check(self._lib.vsr_set_bit_mfma(self._h, int(bool(enable))))
 
+    def set_half_wide(self, on=True):
+        """Run the shared passes of this context's searches over halfvec corpora and half IVFFlat indexes on K2hw (a row tile
+        staged once per workgroup for up to 64 queries) instead of K2h.  Same results; default off."""
+        check(self._lib.vsr_set_half_wide(self._h, int(bool(on))))
+
     def screening_check(self, nq=0):
         """(flagged queries since open, flags of the last vsr_search_device call).  Synchronises."""
         total = C.c_int64()
