@@ -338,6 +338,14 @@ int vsr_set_screening(vsr_ctx* ctx, int enable);           /* default: enabled; 
  * context's next search; one-query passes, index views (vsr_ivf_search_bit*, vsr_ivf_search_quantized*) and corpora that are not
  * bit corpora are not affected. */
 int vsr_set_bit_mfma(vsr_ctx* ctx, int enable);
+/* sparsevec corpora: enable != 0 runs the searches of vsr_search_sparse* in which some pass is shared by two or more queries on
+ * K1sm instead of K1s: the queries of a pass (up to 32, or 16, by what fits LDS) are merged into one table, so that a stored
+ * row entry is looked up once per pass instead of once per query.  Both kernels are exact: the same rows, distances and counts
+ * on integer-valued data, within 1e-4 on real-valued data (the sums run in another order).  Default: 0 (VSR_SPARSE_SHARED=1 at
+ * vsr_open sets it); takes effect from the context's next search; calls whose passes carry one query each, calls whose longest
+ * query is too long for the merged block (more than 32 non-zeros at k = 100) and corpora that are not sparse corpora are not
+ * affected. */
+int vsr_set_sparse_shared(vsr_ctx* ctx, int enable);
 /* halfvec corpora: on != 0 runs the passes that two or more queries share -- vsr_search*, the list scans of vsr_ivf_search* over a
  * half index -- on K2hw instead of K2h: a 64-row tile of the binary16 rows is staged once per workgroup and multiplied on the f16
  * matrix cores against up to 64 queries per pass (K2h: 16 or 32 per wave-private tile), with threshold seeds from a sample pass

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "vsr_bounds.h"
+#include "vsr_scansm_sizing.h"
 
 namespace vsr {
 
@@ -301,6 +302,7 @@ PassLaunch   launch_mfmah_l2, launch_mfmah_ip, launch_mfmah_cosine;             
 PassLaunch   launch_mfmahw_l2, launch_mfmahw_ip, launch_mfmahw_cosine;                   // vsr_mfmahw_*.hip
 PassLaunch   launch_mfmab_hamming, launch_mfmab_jaccard;                                 // vsr_mfmab_*.hip
 PassLaunch   launch_mfmaw_l2, launch_mfmaw_ip, launch_mfmaw_cosine;                      // vsr_mfmaw_*.hip
+PassLaunch   launch_scansm_l2, launch_scansm_ip, launch_scansm_cosine, launch_scansm_l1; // vsr_scansm_*.hip
 PassLaunch   launch_gemm_l2, launch_gemm_ip, launch_gemm_cosine;                         // vsr_gemm_*.hip
 // one query per call over the int8 planes (vsr_scan8.h): K1's top-k and in-kernel merge, a quarter of the bytes per row
 hipError_t launch_scan8_fused(const ScanParams& p, uint32_t dim, uint32_t* q8_bad_host, uint32_t n_blocks, hipStream_t s);
@@ -533,6 +535,10 @@ inline size_t scans_lds_bytes(uint32_t qmax, uint32_t cap, uint32_t lds_slots)
 {
     return (size_t) qmax * ((size_t) cap * 8 + 16 + (size_t) lds_slots * 8 + 8 + 4) + 16;
 }
+// K1sm (vsr_scansm.h): the shared passes of a sparse corpus with the pass's queries merged into one union table and a dense
+// block in LDS -- one probe per stored row entry instead of one per (entry, query); exact, K1s's values; K2b's cap
+// (mfma_cap_for_k), candidate buffers (p.cand) and block map.  p.qmax = QW, 16 or 32 (scansm_qw, vsr_scansm_sizing.h).  Opt-in
+hipError_t launch_scansm(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s);
 bool scan_sparse_table_in_lds(uint32_t slots, int k);     // one query's table fits beside its candidate list
 int  scan_qmax_sparse(uint32_t slots, int k);             // queries per pass: 1, or a multiple of 4 up to SCAN_QMAX (table in LDS); 4 or 1 (global)
 // sparsevec.c:803-1037 for n explicit pairs, one thread per pair, pgvector's sequential merge; out: the operator's float8

@@ -53,6 +53,11 @@ hipError_t launch_mfmab(const ScanParams& p, int metric, uint32_t n_blocks, hipS
     return launch_pass(metric == 4 ? launch_mfmab_hamming : metric == 5 ? launch_mfmab_jaccard : nullptr, p, n_blocks, s);
 }
 
+hipError_t launch_scansm(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s)
+{
+    return launch_pass(by_metric(metric, launch_scansm_l2, launch_scansm_ip, launch_scansm_cosine, launch_scansm_l1), p, n_blocks, s);
+}
+
 bool mq_supported(int dim) { return (dim + 3) / 4 >= 16; }
 
 int mq_qmax(int dim)

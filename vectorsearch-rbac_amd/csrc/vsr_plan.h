@@ -23,6 +23,7 @@ struct PlanScalars {
     uint32_t walk_n_pos = 0;      // 64-row units of the view
     uint32_t walk_shift = 0;      // walk_table's slice of a position p: p >> walk_shift
     bool     k2b = false;         // shared passes of a bit corpus run on K2b (vsr_mfmab.h): exact, K2's candidate buffers, no K5r
+    bool     k1sm = false;        // shared passes of a sparse corpus run on K1sm (vsr_scansm.h): exact, K2b's candidate buffers, qmax = QW
     bool     k2g = false;         // ... on K2g: long rows, 256-query passes, coarse planes (vsr_gemm.h); implies k2w
     bool     sparse_global = false;   // K1s (sparse corpus): the query tables stay in global memory (vsr_scans.h, GLOBAL_TAB)
     uint32_t keep = 0;            // partial list length kp (K2: 2k screening survivors; else k)

@@ -50,6 +50,7 @@ struct PlanScratch {
 struct Width {                               // what the kernel family and pass width stage decides
     bool     mq_ok, k2_ok, k2w_ok, k2g, i8wide;
     bool     k2b_ok;                         // bit corpus: shared passes on K2b (vsr_mfmab.h)
+    int      k1sm_qw;                        // sparse corpus: shared passes on K1sm (vsr_scansm.h) with this QW; 0: K1s
     bool     k2hw_ok;                        // halfvec corpus: shared passes on K2hw (vsr_mfmahw.h), planned as K2w's are
     bool     wide() const { return k2w_ok || k2hw_ok; }   // one candidate buffer per query, sample pass, select + re-rank
     int      wq;                             // K2w / K2g: query columns of a workgroup
@@ -146,6 +147,8 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     // (... or, switched on by vsr_set_bit_mfma, K2b for its shared passes: the int8 matrix cores on the unpacked bits, exact too.  Not a
     // list-ordered view, whose keys go through the rank map: K3b and K3q's stage 1 stay on K1b)
     // (a sparse corpus has CSR rows only and an exact kernel, K1s: planned like a bit corpus; the call's table size bounds the pass)
+    // (... or, switched on by vsr_set_sparse_shared, K1sm for its shared passes: QW = 32 queries per pass if the pass's query
+    // block fits K2b's LDS budget beside the sort buffer of that k, else 16, else K1s.  Not a view)
     const bool f32 = c->format == RowFormat::F32, half = c->format == RowFormat::HALF;
     w.mq_ok = f32 && mq_supported(c->dim) && mq_qmax(c->dim) >= 4 && !ctx->no_mq;
     // K2 / K2w: matrix-core screening keeps 2k (>= 32) candidates per query, K5r re-ranks them exactly
@@ -179,7 +182,10 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     const uint32_t k2b_cap = mfma_cap_for_k((uint32_t) in.k);
     const int k2b_q = mfmab_lds_bytes(k2b_cap, 32) <= MFMAB_LDS_BUDGET ? 32 : mfmab_lds_bytes(k2b_cap, 16) <= MFMAB_LDS_BUDGET ? 16 : 0;
     w.k2b_ok = c->format == RowFormat::BIT && ctx->bit_mfma && !c->d_rank && k2b_q > 0;
+    w.k1sm_qw = c->format == RowFormat::SPARSE && ctx->sparse_shared && !c->d_rank
+                    ? scansm_qw(ctx->sparse_slots, mfma_cap_for_k((uint32_t) in.k), ctx->max_qb_set ? ctx->max_qb : 32) : 0;
     if (w.wide()) w.qmax = ctx->max_qb_set ? std::min(ctx->max_qb, w.wq) : w.wq;
+    else if (w.k1sm_qw) w.qmax = w.k1sm_qw;
     else if (w.k2b_ok) w.qmax = ctx->max_qb_set ? std::min(ctx->max_qb, k2b_q) : k2b_q;
     else if (w.k2_ok) w.qmax = std::min(legacy_qb, mfma_qmax(c->stride4));
     else if (w.mq_ok) w.qmax = std::min(legacy_qb, mq_qmax(c->dim));
@@ -251,11 +257,13 @@ void set_family(const PlanIn& in, const Width& w, uint32_t widest, Plan& plan)
     plan.k2hw = plan.k2w && w.k2hw_ok;
     plan.mq = plan.qi == 4 && w.mq_ok && !plan.k2;
     plan.k2b = plan.qi == 4 && w.k2b_ok;                    // exact: keep stays k, no K5r
+    plan.k1sm = plan.qi == 4 && w.k1sm_qw > 0;              // exact: keep stays k
     plan.keep = plan.k2 ? w.keep : (uint32_t) in.k;
     // K1s: a table that does not fit LDS beside one candidate list is read from global memory, and then qmax = QI
     plan.sparse_global = in.c->format == RowFormat::SPARSE && !scan_sparse_table_in_lds(in.ctx->sparse_slots, in.k);
     if (plan.k2w) plan.qmax = (uint32_t) w.wq;              // query slots per workgroup: one (long rows: two) 16-query groups per wave
     else if (plan.k2 || plan.k2b) plan.qmax = plan.qmax > 16 ? 32 : 16;
+    else if (plan.k1sm) plan.qmax = (uint32_t) w.k1sm_qw;   // the instantiation: QW by what fits, not by the widest pass
     plan.int8 = plan.k2w && in.c->d_scr8 && in.metric == VSR_METRIC_L2 && in.ctx->int8_this_call;
     if (plan.int8) plan.keep = (uint32_t) std::max(in.k, 32);  // exact screening: no second half of survivors to re-rank
     plan.k2g = plan.k2w && w.k2g && !plan.int8;
@@ -747,7 +755,7 @@ bool vsr::make_plan(const vsr_ctx* ctx, const vsr_corpus* c, int nq, int k, int 
         const bool thin = first_stride(in, plan) != ctx->sample_stride;
         const LaunchSize ls = size_launch(in, plan, s.passes);
         emit_groups(in, w.i8wide, ls, s, plan);
-        if (plan.k2 || plan.mq || plan.k2b) map_blocks_to_xcds(s.lane, plan);
+        if (plan.k2 || plan.mq || plan.k2b || plan.k1sm) map_blocks_to_xcds(s.lane, plan);
         plan.walk = plan.walk && !plan.block_map.empty();
         if (plan.walk) build_walk_table(c->class_view.get(), plan);
         if (plan.k2w) {
@@ -792,6 +800,10 @@ std::string vsr::scan_kernel_name(const Plan& plan, const vsr_corpus* c, int met
     else
         switch (c->format) {
         case RowFormat::SPARSE:
+            if (plan.k1sm) {
+                snprintf(buf, sizeof buf, "vsr::scansm_kernel<%s, QW=%u> (K1sm, sparse rows)", mname[metric], plan.qmax);
+                break;
+            }
             snprintf(buf, sizeof buf, "vsr::scans_kernel<%s, LPR=%d, QI=%d, TAB=%s> (K1s, sparse rows)", mname[metric], c->shape.lpr, plan.qi,
                      plan.sparse_global ? "global" : "lds");
             break;

@@ -175,6 +175,12 @@ class Context:
         Both are exact and return the same results.  Default off; one-query passes and index views stay on K1b."""
         check(self._lib.vsr_set_bit_mfma(self._h, int(bool(enable))))
 
+    def set_sparse_shared(self, enable=True):
+        """Run the shared passes of this context's searches over sparse corpora on K1sm (the queries of a pass merged into one
+        table: one lookup per stored row entry and pass) instead of K1s.  Both are exact.  Default off; calls whose passes carry
+        one query each and calls whose longest query does not fit the merged block stay on K1s."""
+        check(self._lib.vsr_set_sparse_shared(self._h, int(bool(enable))))
+
     def set_half_wide(self, on=True):
         """Run the shared passes of this context's searches over halfvec corpora and half IVFFlat indexes on K2hw (a row tile
         staged once per workgroup for up to 64 queries) instead of K2h.  Same results; default off."""
