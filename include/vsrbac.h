@@ -354,6 +354,16 @@ int vsr_set_sparse_shared(vsr_ctx* ctx, int enable);
  * from the context's next search; L1, one-query passes, rows shorter than 61 elements, a context with screening or seeding off
  * and corpora that are not halfvec corpora are not affected. */
 int vsr_set_half_wide(vsr_ctx* ctx, int on);
+/* halfvec corpora with long rows: on != 0 runs the passes of vsr_search* that more than 128 queries share on K2gh: a GEMM-shaped
+ * kernel whose 256-row x 256-query tiles take both operands -- the corpus's own binary16 rows and the queries' binary16 image --
+ * through LDS to the f16 matrix cores, so a part seen by 1000 queries is walked 4 times (K2hw: 16, K2h: 32 or more).  No extra
+ * memory per corpus.  Same screening keys, error bound, threshold seeds, exact re-rank on the half rows and flag / re-run rules as
+ * K2hw; the reported rows and distances are the exact kernels' either way.  Independent of vsr_set_half_wide: a call the gate
+ * does not admit stays on K2hw or K2h, whichever that switch selects.  Default: 0 (VSR_HALF_GEMM=1 at vsr_open sets it); takes
+ * effect from the context's next search; L1, rows shorter than 225 elements, calls in which fewer than nine tenths of the (filter
+ * part, query) pairs sit in parts seen by more than 128 queries (small batches, role mixes), IVFFlat list scans, a context with
+ * screening or seeding off or a query-block limit set, and corpora that are not halfvec corpora are not affected. */
+int vsr_set_half_gemm(vsr_ctx* ctx, int on);
 int vsr_screening_check(vsr_ctx* ctx, int64_t* flagged_total, int32_t* flags_last_call, int nq);
 
 /* merge n_parts per-shard results (layout [n_parts][nq][k], as all-gathered from vsr_search_device) into the

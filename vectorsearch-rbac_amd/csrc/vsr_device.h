@@ -288,7 +288,7 @@ inline size_t scan_lds_bytes(uint32_t qmax, uint32_t cap, uint32_t stride4)
 hipError_t launch_scan(RowFormat f, const ScanParams& p, int metric, int dim, int qi, uint32_t n_blocks, hipStream_t s,
                        int sparse_lpr = 0, bool sparse_global_tab = false);
 // ... and the per-metric launchers behind the family launchers of this header (launch_scan, launch_mq, launch_mfma,
-// launch_mfmah, launch_mfmahw, launch_mfmaw, launch_gemm): one translation unit per metric, for parallel builds
+// launch_mfmah, launch_mfmahw, launch_gemmh, launch_mfmaw, launch_gemm): one translation unit per metric, for parallel builds
 using ScanLaunch   = hipError_t(const ScanParams& p, int dim, int qi, uint32_t n_blocks, hipStream_t s);
 using SparseLaunch = hipError_t(const ScanParams& p, int lpr, int qi, bool global_tab, uint32_t n_blocks, hipStream_t s);
 using PassLaunch   = hipError_t(const ScanParams& p, uint32_t n_blocks, hipStream_t s);
@@ -304,6 +304,7 @@ PassLaunch   launch_mfmab_hamming, launch_mfmab_jaccard;                        
 PassLaunch   launch_mfmaw_l2, launch_mfmaw_ip, launch_mfmaw_cosine;                      // vsr_mfmaw_*.hip
 PassLaunch   launch_scansm_l2, launch_scansm_ip, launch_scansm_cosine, launch_scansm_l1; // vsr_scansm_*.hip
 PassLaunch   launch_gemm_l2, launch_gemm_ip, launch_gemm_cosine;                         // vsr_gemm_*.hip
+PassLaunch   launch_gemmh_l2, launch_gemmh_ip, launch_gemmh_cosine;                      // vsr_gemmh_*.hip
 // one query per call over the int8 planes (vsr_scan8.h): K1's top-k and in-kernel merge, a quarter of the bytes per row
 hipError_t launch_scan8_fused(const ScanParams& p, uint32_t dim, uint32_t* q8_bad_host, uint32_t n_blocks, hipStream_t s);
 // K1m (vsr_mq.h): shared-pass kernel for 2..16 queries per pass; needs dim >= 61 (>= 16 float4 per row)
@@ -376,6 +377,12 @@ inline size_t mfmahw_lds_bytes(bool lds_queries)
     return (size_t) (lds_queries ? 4 : 2) * 64 * 16 * 16 + (size_t) HW_RING * 64 * 8 + (size_t) 4 * MW_PEND * 12;
 }
 hipError_t launch_mfmahw(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s);
+// K2gh (vsr_gemmh.h): K2g's 256 x 256 tiles over a halfvec corpus's own row-major rows, both operands through LDS, f16 MFMA
+// against up to 256 queries (p.q_scr: their binary16 image in rows of gemmh_q_chunks chunks, zero-padded to whole 32-element
+// K-steps).  Opt-in (vsr_ctx::half_gemm).  Its pipeline needs 8 K-steps per row: 29 chunks, d >= 225
+inline bool gemmh_supported(uint32_t row_chunks) { return row_chunks >= 29; }
+inline uint32_t gemmh_q_chunks(uint32_t row_chunks) { return (row_chunks + 3u) / 4u * 4u; }
+hipError_t launch_gemmh(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s);
 // K2g (vsr_gemm.h): long rows, passes of up to 256 queries, 256 x 256 tiles with both operands in LDS, ONE bf16 product
 // per element on the coarse planes (hi = bf16(x) only; rows padded to whole 64-element K-steps)
 constexpr uint32_t GM_QMAX = 256;
@@ -480,6 +487,7 @@ struct StageParams {
                                    // valid; q_dst receives nq x qfloats / 4 16-byte chunks, pad bits cleared; q_norm2 the popcounts
     uint32_t     q_half;           // halfvec corpus: every query element is rounded to binary16 and widened again (Float4ToHalf)
     _Float16*    q_h16;            // [nq][qfloats] the rounded queries as binary16 (K2h's B fragments), nullptr: not needed
+    uint32_t     q_h16_stride;     // halves per row of q_h16 when it is wider than qfloats (K2gh: zero-padded to whole K-steps); 0: qfloats
     float*       q_norm2;          // [nq]
     uint4*       q_scr;            // [nq][q plane stride] bf16 hi / mid planes of the padded queries (nullptr: not needed)
     uint32_t     pstride4;         // corpus plane stride

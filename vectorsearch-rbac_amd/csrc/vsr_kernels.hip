@@ -48,6 +48,11 @@ hipError_t launch_mfmahw(const ScanParams& p, int metric, uint32_t n_blocks, hip
     return launch_pass(by_metric(metric, launch_mfmahw_l2, launch_mfmahw_ip, launch_mfmahw_cosine), p, n_blocks, s);
 }
 
+hipError_t launch_gemmh(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s)
+{
+    return launch_pass(by_metric(metric, launch_gemmh_l2, launch_gemmh_ip, launch_gemmh_cosine), p, n_blocks, s);
+}
+
 hipError_t launch_mfmab(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s)
 {
     return launch_pass(metric == 4 ? launch_mfmab_hamming : metric == 5 ? launch_mfmab_jaccard : nullptr, p, n_blocks, s);
@@ -715,11 +720,14 @@ __global__ __launch_bounds__(256) void stage_kernel(const StageParams p)
     const uint32_t s = blockIdx.x;
     const float* src = p.q_src + (size_t) s * p.q_stride;
     float* dst = p.q_dst + (size_t) s * p.qfloats;
+    const uint32_t hstride = p.q_h16_stride ? p.q_h16_stride : p.qfloats;
     for (uint32_t j = (uint32_t) tid; j < p.qfloats; j += 256) {
         const float v = j < p.dim ? src[j] : 0.0f;
         dst[j] = p.q_half ? (float) (_Float16) v : v;        // what `$1::halfvec` holds (Float4ToHalf, halfutils.h:146-261)
-        if (p.q_h16) p.q_h16[(size_t) s * p.qfloats + j] = (_Float16) v;
+        if (p.q_h16) p.q_h16[(size_t) s * hstride + j] = (_Float16) v;
     }
+    if (p.q_h16)                                             // K2gh: the image's pad to whole K-steps
+        for (uint32_t j = p.qfloats + (uint32_t) tid; j < hstride; j += 256) p.q_h16[(size_t) s * hstride + j] = (_Float16) 0.0f;
     if (tid == 0) {
         p.flags[s] = 0;
         p.tau[s] = KEY_EMPTY;

@@ -17,6 +17,7 @@ struct PlanScalars {
     bool     k2 = false;          // shared passes run on K2 / K2w (MFMA screening) + K5r
     bool     k2w = false;         // ... on K2w: workgroup-shared row tiles, up to 128 queries per pass (vsr_mfmaw.h)
     bool     k2hw = false;        // ... on K2hw: K2w's work split over a halfvec corpus's own rows (vsr_mfmahw.h); implies k2w
+    bool     k2gh = false;        // ... on K2gh: K2g's 256-query GEMM tiles over a halfvec corpus's own long rows (vsr_gemmh.h); implies k2w
     bool     int8 = false;        // ... on the corpus's int8 planes (L2, integer 0..255 rows and queries)
     bool     class_view = false;  // ... on the corpus's class view of the int8 planes (every pass a whole permission class)
     bool     walk = false;        // ... with the main launch's block_map rotated to where the launches in flight are reading (walk_table)
@@ -65,7 +66,7 @@ struct Plan : PlanScalars {
     }
 };
 
-// Queries -> passes -> workgroups.  Returns false when the K2w / K2g plan it built cannot be seeded safely (the caller then
+// Queries -> passes -> workgroups.  Returns false when the K2w / K2g / K2gh plan it built cannot be seeded safely (the caller then
 // plans again with allow_gemm, then allow_wide, set to false).  Resets `plan` first.
 bool make_plan(const vsr_ctx* ctx, const vsr_corpus* c, int nq, int k, int metric, bool allow_screening, bool allow_wide,
                bool allow_gemm, const vsr_filter* const* filters, Plan& plan);

@@ -52,7 +52,8 @@ struct Width {                               // what the kernel family and pass 
     bool     k2b_ok;                         // bit corpus: shared passes on K2b (vsr_mfmab.h)
     int      k1sm_qw;                        // sparse corpus: shared passes on K1sm (vsr_scansm.h) with this QW; 0: K1s
     bool     k2hw_ok;                        // halfvec corpus: shared passes on K2hw (vsr_mfmahw.h), planned as K2w's are
-    bool     wide() const { return k2w_ok || k2hw_ok; }   // one candidate buffer per query, sample pass, select + re-rank
+    bool     k2gh;                           // halfvec corpus, long rows, parts seen by > 128 queries: 256-query passes on K2gh (vsr_gemmh.h)
+    bool     wide() const { return k2w_ok || k2hw_ok || k2gh; }   // one candidate buffer per query, sample pass, select + re-rank
     int      wq;                             // K2w / K2g: query columns of a workgroup
     int      qmax;                           // queries per pass
     uint32_t keep, keep_c;                   // screening survivors kept per query: fine planes, coarse planes
@@ -143,6 +144,7 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     // (a halfvec corpus has fp16 rows only: K1h or, under K2's gates, K2h -- K2 on the f16 matrix cores, vsr_mfmah.h; never
     // K1m, which reads fp32 rows, nor K2w / K2g / int8, which read planes it does not have)
     // (... or, switched on by vsr_set_half_wide, K2hw: K2w's work split and launch sequence over the half rows themselves)
+    // (... or, switched on by vsr_set_half_gemm, K2gh: K2g's tile, gate and launch geometry over the half rows, for rows of 225 elements up)
     // (a bit corpus has packed bits only and an exact integer kernel, K1b: as with screening off, nothing else applies)
     // (... or, switched on by vsr_set_bit_mfma, K2b for its shared passes: the int8 matrix cores on the unpacked bits, exact too.  Not a
     // list-ordered view, whose keys go through the rank map: K3b and K3q's stage 1 stay on K1b)
@@ -157,6 +159,11 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
                         mq_supported(c->dim) && ctx->max_qb >= 16;
     w.k2w_ok = k2_any && f32 && allow_wide && c->d_scr && w.keep <= GQ_MAX_KP && !ctx->no_wide && ctx->seeding;
     w.k2hw_ok = k2_any && half && ctx->half_wide && allow_wide && w.keep <= GQ_MAX_KP && ctx->seeding;
+    // K2gh: K2hw's conditions apart from its switch, K2g's gate (nearly all items in parts seen by more than 128 queries), rows
+    // long enough for the kernel's pipeline (8 K-steps of 32 elements: d >= 225), not a view (keys would go through the rank map).
+    // Nothing of the coarse planes: keep stays 2k.  A role mix stays on K2hw or K2h
+    w.k2gh = k2_any && half && ctx->half_gemm && allow_wide && allow_gemm && w.keep <= GQ_MAX_KP && ctx->seeding && !ctx->max_qb_set &&
+             !c->d_rank && gemmh_supported(format_row_chunks(c->format, c->dim)) && mostly_in_parts_over(gend, 128, false);
     w.k2_ok = w.wide() || (k2_any && mfma_cap_for_k(w.keep) <= 8192 && mfma_lds_bytes(c->stride4) <= 150 * 1024);
     w.wq = w.k2hw_ok ? 64 : mfmaw_qmax(c->pstride4, !c->scr_has_mid);   // (K2hw: one 16-query group per wave)
     // K2g (coarse planes, 256-query passes): when nearly all (part, query) items sit in parts seen by more than 128
@@ -164,7 +171,7 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     w.keep_c = (uint32_t) std::max(4 * in.k, 128);
     w.k2g = w.k2w_ok && allow_gemm && c->d_scr_c && !ctx->no_gemm && ctx->screen_level >= 2 && w.keep_c <= GQ_MAX_KP && !ctx->max_qb_set;
     w.k2g = w.k2g && mostly_in_parts_over(gend, 128, false);
-    if (w.k2g) w.wq = (int) GM_QMAX;
+    if (w.k2g || w.k2gh) w.wq = (int) GM_QMAX;
     // int8 planes on K2i: every wave holds the B fragments of the whole pass, and 128 columns fit its registers -- a class seen
     // by 330 queries is streamed 3 times instead of 6.  The sample launch (K2w's kernel: 64 columns) gets such a pass as two.
     // (measured on the headline step: 12 % fewer pass rows, but the 8-group instantiation -- 223 VGPRs, its candidate masks
@@ -176,7 +183,7 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     // where a pass has none) pay when nearly all (part, query) items sit in parts seen by more than 64 queries --
     // unfiltered batches: 1M x 768 x 1000 queries 9.9 -> 7.9 ms; a role mix (1000 users over 100 roles) would lose:
     // 1.10 -> 1.39 ms
-    if (w.wq > 64 && !w.k2g && !w.i8wide && !mostly_in_parts_over(gend, 64, true)) w.wq = 64;
+    if (w.wq > 64 && !w.k2g && !w.k2gh && !w.i8wide && !mostly_in_parts_over(gend, 64, true)) w.wq = 64;
     const int legacy_qb = ctx->max_qb_set ? ctx->max_qb : 16;
     // K2b: 32 queries per pass, 16 when the LDS beside the sort buffer of that k holds the control words of 16 only, else K1b
     const uint32_t k2b_cap = mfma_cap_for_k((uint32_t) in.k);
@@ -254,7 +261,8 @@ void set_family(const PlanIn& in, const Width& w, uint32_t widest, Plan& plan)
     plan.qmax = plan.qi == 1 ? 1 : (widest + 3) / 4 * 4;
     plan.k2 = plan.qi == 4 && w.k2_ok;
     plan.k2w = plan.k2 && w.wide();
-    plan.k2hw = plan.k2w && w.k2hw_ok;
+    plan.k2gh = plan.k2w && w.k2gh;
+    plan.k2hw = plan.k2w && w.k2hw_ok && !plan.k2gh;
     plan.mq = plan.qi == 4 && w.mq_ok && !plan.k2;
     plan.k2b = plan.qi == 4 && w.k2b_ok;                    // exact: keep stays k, no K5r
     plan.k1sm = plan.qi == 4 && w.k1sm_qw > 0;              // exact: keep stays k
@@ -380,7 +388,7 @@ LaunchSize size_launch(const PlanIn& in, const Plan& plan, const std::vector<Pas
         // K2w keeps 3 workgroups per CU resident and its passes differ a lot in cost per row: ~4 rounds of workgroups
         // even them out (10M rows, 1000 queries: main launch alone 0.97 -> 0.75 ms from 4 to 12 per CU)
         // (K2g: one 8-wave workgroup per CU; ~3 rounds, at least ~8 of its 256-row tiles per workgroup)
-        const int64_t want = plan.k2g ? std::min<int64_t>(total_rows / 2048, 3 * cus)
+        const int64_t want = plan.k2g || plan.k2gh ? std::min<int64_t>(total_rows / 2048, 3 * cus)
                            : plan.k2w ? std::min<int64_t>(total_rows / 4096, 12 * cus) : std::min<int64_t>(total_rows / 13000, 16 * cus);
         if (want > ls.budget) {
             ls.budget = want;
@@ -391,7 +399,7 @@ LaunchSize size_launch(const PlanIn& in, const Plan& plan, const std::vector<Pas
         // the sample launch visits every ss-th tile: a workgroup of it is all prologue and memory latency, so it gets ONE
         // resident round of workgroups (each then walks ~12 tiles instead of three rounds walking 4: 72 -> ~45 us on the
         // 10M-row corpus); launches that fit one round anyway (a shard) keep the main launch's workgroups
-        const int64_t slots = (plan.k2g ? 1 : plan.int8 ? 4 : 3) * cus * ctx->sample_rounds;   // (VSR_SAMPLE_ROUNDS: measurements only)
+        const int64_t slots = (plan.k2g || plan.k2gh ? 1 : plan.int8 ? 4 : 3) * cus * ctx->sample_rounds;   // (VSR_SAMPLE_ROUNDS: measurements only)
         ls.seed_div = (uint32_t) std::max<int64_t>(1, (ls.budget + slots - 1) / slots);
         // a thinner sample: fewer, not shorter, workgroups -- each still walks about as many stages of a longer range
         ls.seed_div = ls.seed_div * first_stride(in, plan) / ctx->sample_stride;
@@ -554,7 +562,8 @@ bool try_k2i_sample(const PlanIn& in, PlanScratch& s, Plan& plan)
 bool evaluate_stride(const PlanIn& in, uint32_t stride, PlanScratch& s, Plan& plan, bool& soft_thin)
 {
     const vsr_corpus* c = in.c;
-    const double tile_rows = plan.k2g ? 256.0 : 64.0;       // rows per workgroup tile of the kernel
+    const bool gemm_tile = plan.k2g || plan.k2gh;            // K2g's geometry: 256-row tiles, minima per 128-row wave-tile
+    const double tile_rows = gemm_tile ? 256.0 : 64.0;      // rows per workgroup tile of the kernel
     plan.sample_stride = stride;
     const double ss = stride;
     const double frac = densest_fraction(plan.groups_s, c->shape.rw, tile_rows, ss);
@@ -569,13 +578,13 @@ bool evaluate_stride(const PlanIn& in, uint32_t stride, PlanScratch& s, Plan& pl
         bool fine = false;
         for (uint32_t qi = 0; qi < gs.q_count; ++qi) {
             const double allowed = (double) allowed_rows(c, in.filter(plan.q_slots[gs.q_begin + qi]));
-            fine |= allowed / ((plan.k2g ? 128.0 : 64.0) * ss) < 4.0 * seed_m;
+            fine |= allowed / ((gemm_tile ? 128.0 : 64.0) * ss) < 4.0 * seed_m;
         }
         gs.partial_begin = fine ? 1u : 0u;                     // (K2w / K2g have no partial lists: the field carries the flag)
         double t64;
         const double sampled = sampled_tiles(gs, c->shape.rw, tile_rows, ss, t64);
         const uint32_t ngt = (gs.q_count + 15) / 16;
-        const double waves_per_col = plan.k2g ? 2.0 : ngt == 1 ? 4.0 : ngt == 2 ? 2.0 : 1.0;     // row split (vsr_mfmaw.h)
+        const double waves_per_col = gemm_tile ? 2.0 : ngt == 1 ? 4.0 : ngt == 2 ? 2.0 : 1.0;     // row split (vsr_mfmaw.h)
         const double entries_per_tile = waves_per_col * (fine ? 4.0 : 1.0);
         const double rows_per_entry = tile_rows / entries_per_tile;
         const double p_entry = std::min(1.0, s.gdens_s[gi] * rows_per_entry);    // a bitmap may leave an entry without rows
@@ -777,6 +786,8 @@ std::string vsr::scan_kernel_name(const Plan& plan, const vsr_corpus* c, int met
     const uint32_t nstage = (c->stride4 + 15) / 16;
     if (plan.k2g)
         snprintf(buf, sizeof buf, "vsr::gemm_screen_kernel<%s, SAMPLE=false> (K2g, bf16 coarse planes)", mname[metric]);
+    else if (plan.k2gh)
+        snprintf(buf, sizeof buf, "vsr::gemmh_screen_kernel<%s, SAMPLE=false> (K2gh, f16 rows)", mname[metric]);
     else if (plan.k2hw) {
         const uint32_t hstage = (c->stride4 / 2 + 15) / 16;    // launch_mfmahw_metric's choice
         snprintf(buf, sizeof buf, "vsr::mfmahw_scan_kernel<%s, NSTR=%u, SAMPLE=false> (K2hw, f16 rows)", mname[metric], hstage <= 2 ? hstage : 0u);

@@ -86,6 +86,7 @@ extern "C" int vsr_open(int device, vsr_ctx** out)
     if ((env = getenv("VSR_BIT_MFMA"))) ctx->bit_mfma = atoi(env) != 0;
     if ((env = getenv("VSR_SPARSE_SHARED"))) ctx->sparse_shared = atoi(env) != 0;
     if ((env = getenv("VSR_HALF_WIDE"))) ctx->half_wide = atoi(env) != 0;
+    if ((env = getenv("VSR_HALF_GEMM"))) ctx->half_gemm = atoi(env) != 0;
     if ((env = getenv("VSR_K2I"))) ctx->no_k2i = atoi(env) == 0;
     if ((env = getenv("VSR_FORCE_EPI"))) ctx->force_epi = atoi(env) != 0;
     if ((env = getenv("VSR_K2I_WIDE"))) ctx->k2i_wide = atoi(env) != 0;
@@ -846,6 +847,13 @@ extern "C" int vsr_set_half_wide(vsr_ctx* ctx, int on)
 {
     if (!ctx) return fail(VSR_ERR_INVALID, "vsr_set_half_wide: ctx is NULL");
     ctx->half_wide = on != 0;
+    return VSR_OK;
+}
+
+extern "C" int vsr_set_half_gemm(vsr_ctx* ctx, int on)
+{
+    if (!ctx) return fail(VSR_ERR_INVALID, "vsr_set_half_gemm: ctx is NULL");
+    ctx->half_gemm = on != 0;
     return VSR_OK;
 }
 

@@ -281,7 +281,9 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
     const size_t off_q8 = sb.add(plan.int8 ? (size_t) nq * 128 : 0);                      // int8 query planes, |q-128|^2, validity
     const size_t off_qn8 = sb.add(plan.int8 ? (size_t) nq * sizeof(float) : 0);
     const size_t off_qb = sb.add(plan.int8 ? (size_t) nq * sizeof(uint32_t) : 0);
-    const size_t off_qh = sb.add(plan.k2hw ? (size_t) nq * qfloats * sizeof(uint16_t) : 0);   // K2hw: the queries as binary16, its B operands
+    // K2hw / K2gh: the queries as binary16, their B operands (K2gh: every image zero-padded to whole K-steps)
+    const size_t qh_halves = plan.k2gh ? (size_t) gemmh_q_chunks(c->stride4 / 2) * 8 : qfloats;
+    const size_t off_qh = sb.add(plan.k2hw || plan.k2gh ? (size_t) nq * qh_halves * sizeof(uint16_t) : 0);
     const size_t off_g = sb.add(plan.groups);                                              // copied from here on
     const size_t off_gs = sb.add(plan.groups_s);
     const size_t off_qs = sb.add(plan.q_slots);
@@ -304,10 +306,11 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
     st.plane_ho = c->scr_has_mid ? 0u : 1u;
     st.qcnt = qcnt;
     st.scnt = scnt;
-    if (plan.k2hw) {                                        // a halfvec corpus has no planes: the rounded queries and their binary16 image
+    if (plan.k2hw || plan.k2gh) {                           // a halfvec corpus has no planes: the rounded queries and their binary16 image
         st.q_scr = nullptr;
         st.q_half = 1u;
         st.q_h16 = reinterpret_cast<_Float16*>(ds + off_qh);
+        st.q_h16_stride = plan.k2gh ? (uint32_t) qh_halves : 0u;
     }
     if (plan.k2g) {
         st.q_scr = nullptr;                                 // only the coarse planes are read
@@ -345,14 +348,17 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
             sp.n_rows = v->n_rows;
         }
     }
-    if (plan.k2hw) sp.q_scr = reinterpret_cast<const uint4*>(ds + off_qh);
+    if (plan.k2hw || plan.k2gh) sp.q_scr = reinterpret_cast<const uint4*>(ds + off_qh);
     if (plan.k2g) {
         sp.scr_c = c->d_scr_c;
         sp.q_scr_c = reinterpret_cast<const uint4*>(ds + off_qc);
         sp.cstride4 = c->cstride4;
     }
     auto launch_pass = [&](uint32_t blocks, hipStream_t s) {
-        return plan.k2g ? launch_gemm(sp, metric, blocks, s) : plan.k2hw ? launch_mfmahw(sp, metric, blocks, s) : launch_mfmaw(sp, metric, blocks, s);
+        return plan.k2g    ? launch_gemm(sp, metric, blocks, s)
+               : plan.k2gh ? launch_gemmh(sp, metric, blocks, s)
+               : plan.k2hw ? launch_mfmahw(sp, metric, blocks, s)
+                           : launch_mfmaw(sp, metric, blocks, s);
     };
     sp.q_slots = reinterpret_cast<const uint32_t*>(ds + off_qs);
 
@@ -442,7 +448,7 @@ int search_wide(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q)
     rr.qcand = ctx->d_cand.as<uint64_t>();
     rr.qcnt = qcnt;
     rr.capq = GQ_CAP;
-    rr.err_g = plan.k2g ? coarse_err_g(c->dim) : plan.k2hw ? half_err_g(c->dim) : plane_err_g(c->dim);   // K2hw: K2h's fp32 accumulation
+    rr.err_g = plan.k2g ? coarse_err_g(c->dim) : plan.k2hw || plan.k2gh ? half_err_g(c->dim) : plane_err_g(c->dim);   // K2hw / K2gh: K2h's fp32 accumulation
     rr.err_tight = plan.k2g ? 1u : 0u;
     rr.qbad = plan.int8 ? reinterpret_cast<const uint32_t*>(ds + off_qb) : nullptr;
     rr.exact_screen = plan.int8 ? 1u : 0u;
@@ -747,8 +753,8 @@ int search_impl(vsr_ctx* ctx, vsr_corpus* c, const Call& q, const vsr_filter* co
     if (q.sparse) ctx->sparse_slots = sparse_slots_for_nnz(q.sparse->max_nnz);
     static thread_local Plan plan;
     if (!make_plan(ctx, c, q.nq, q.k, q.metric, allow_screening, true, true, filters, plan)) {
-        // K2g could not be seeded safely: K2w; K2w neither: legacy shared passes
-        if (!plan.k2g || !make_plan(ctx, c, q.nq, q.k, q.metric, allow_screening, true, false, filters, plan))
+        // K2g could not be seeded safely: K2w (K2gh: K2hw or K2h); K2w neither: legacy shared passes
+        if (!(plan.k2g || plan.k2gh) || !make_plan(ctx, c, q.nq, q.k, q.metric, allow_screening, true, false, filters, plan))
             (void) make_plan(ctx, c, q.nq, q.k, q.metric, allow_screening, false, false, filters, plan);
     }
     ctx->last_coarse = plan.k2g;

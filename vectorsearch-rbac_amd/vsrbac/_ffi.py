@@ -76,6 +76,7 @@ SYMBOLS = {
     "vsr_set_bit_mfma": (_i, [_vp, _i]),
     "vsr_set_sparse_shared": (_i, [_vp, _i]),
     "vsr_set_half_wide": (_i, [_vp, _i]),
+    "vsr_set_half_gemm": (_i, [_vp, _i]),
     "vsr_set_query_hint": (_i, [_vp, _i]),
     "vsr_screening_check": (_i, [_vp, C.POINTER(_i64), _vp, _i]),
     "vsr_merge_topk_device": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -186,6 +186,12 @@ class Context:
         staged once per workgroup for up to 64 queries) instead of K2h.  Same results; default off."""
         check(self._lib.vsr_set_half_wide(self._h, int(bool(on))))
 
+    def set_half_gemm(self, on=True):
+        """Run the passes that more than 128 queries of a call share over a halfvec corpus with rows of 225 elements or more on
+        K2gh (256-row x 256-query f16 GEMM tiles over the rows themselves).  Independent of set_half_wide: calls the gate does
+        not admit stay on K2hw or K2h.  Same results; default off."""
+        check(self._lib.vsr_set_half_gemm(self._h, int(bool(on))))
+
     def screening_check(self, nq=0):
         """(flagged queries since open, flags of the last vsr_search_device call).  Synchronises."""
         total = C.c_int64()
