@@ -346,6 +346,14 @@ int vsr_set_bit_mfma(vsr_ctx* ctx, int enable);
  * query is too long for the merged block (more than 32 non-zeros at k = 100) and corpora that are not sparse corpora are not
  * affected. */
 int vsr_set_sparse_shared(vsr_ctx* ctx, int enable);
+/* sparsevec corpora: enable != 0 runs the searches of vsr_search_sparse* in which some pass is shared by two or more queries on
+ * K1sc: K1sm's pass with the merged queries kept compactly -- per distinct index a mask of the queries that hold it and the
+ * position of their packed values -- so that the block fits for 32 queries per pass up to 64 non-zeros in the call's longest
+ * query and for 16 up to 128 (at k = 100).  Exact, with K1sm's values.  Default: 0 (VSR_SPARSE_COMPACT=1 at vsr_open sets it);
+ * independent of vsr_set_sparse_shared; takes effect from the context's next search.  Calls whose passes carry one query each,
+ * calls with a longer query and corpora that are not sparse corpora run exactly as with this switch off (on K1sm if that
+ * switch is on and its block fits, else on K1s). */
+int vsr_set_sparse_compact(vsr_ctx* ctx, int enable);
 /* halfvec corpora: on != 0 runs the passes that two or more queries share -- vsr_search*, the list scans of vsr_ivf_search* over a
  * half index -- on K2hw instead of K2h: a 64-row tile of the binary16 rows is staged once per workgroup and multiplied on the f16
  * matrix cores against up to 64 queries per pass (K2h: 16 or 32 per wave-private tile), with threshold seeds from a sample pass

@@ -22,7 +22,13 @@ runs instead the A/B leg of K1sm (vsr_scansm.h, Context.set_sparse_shared) again
 queries of ~32 non-zeros cut at 32 (one longer query keeps the whole call on K1s), k = 100, <#> and <->, unfiltered and under the
 tree RBAC; a K1s window and a K1sm window alternate in one process, median [min, max] of 9 windows per kernel, and the two
 kernels' outputs of the last windows are compared query by query (real values: distances within 1e-4, and how many queries got
-the same rows).  Writes OUT_DIR/sparse_shared.json."""
+the same rows).  Writes OUT_DIR/sparse_shared.json.
+
+    python tools/sparse_probe.py OUT_DIR --compact-ab
+
+runs in the same way the two A/B comparisons of K1sc (vsr_scansc.h, Context.set_sparse_compact): queries of ~30 non-zeros cut at
+32, K1sm (QW = 16 there) against K1sc (QW = 32); queries of ~100 cut at 128, which K1sm does not serve, K1s against K1sc
+(QW = 16).  Writes OUT_DIR/sparse_compact.json."""
 import argparse
 import ctypes
 import json
@@ -57,13 +63,15 @@ def sparse_rows(rng, n, dim, mean_nnz):
     return indptr, idx.astype(np.int32), values
 
 
-def shared_ab(args):
-    """K1s against K1sm (Context.set_sparse_shared) in one resident process, the two timed alternately window by window."""
+def kernel_ab(args, out_name, comparisons):
+    """Two sparse scan kernels in one resident process, timed alternately window by window.  comparisons: (label, Poisson mean of the
+    queries' non-zeros, cut, kernel A, kernel B), a kernel being K1s, K1sm (Context.set_sparse_shared) or K1sc (set_sparse_compact);
+    the report has one section per label, or none at all for a single unlabelled comparison."""
     import torch
     import vsrbac
     from vsrbac.datasets import sample_queries, tree_rbac
 
-    n, dim, nq, k, windows, calls, cut = args.rows, args.dim, args.queries, args.k, 9, args.ab_calls, 32
+    n, dim, nq, k, windows, calls = args.rows, args.dim, args.queries, args.k, 9, args.ab_calls
     dev = torch.device("cuda", 0)
     ptr = lambda t: ctypes.c_void_p(t.data_ptr())
     rng = np.random.default_rng(args.seed)
@@ -72,30 +80,45 @@ def shared_ab(args):
     corpus = ctx.load_corpus_sparse(indptr, indices, values, dim, np.arange(n, dtype=np.int64), (np.arange(n) // 100 + 1).astype(np.int32))
     mean_row_nnz = round(float(np.diff(indptr).mean()), 2)
     del indices, values
-    q_ptr, q_idx, q_val = sparse_rows(rng, nq, dim, args.query_nnz)
-    keep = np.arange(q_idx.size) - np.repeat(q_ptr[:-1], np.diff(q_ptr)) < cut               # the first `cut` entries of every query
-    q_idx, q_val = q_idx[keep], q_val[keep]
-    q_ptr = np.concatenate([[0], np.cumsum(np.minimum(np.diff(q_ptr), cut))]).astype(np.int64)
-    max_nnz = int(np.diff(q_ptr).max())
-    d_ptr, d_idx, d_val = (torch.from_numpy(a).to(dev) for a in (q_ptr, q_idx, q_val))
     rbac = tree_rbac(num_users=1000, num_roles=100, num_docs=n // 100, seed=args.seed)
     corpus.load_rbac(rbac.user_roles, rbac.permissions)
     _, quser = sample_queries(nq, n, 1000, seed=args.seed)
-    out = {kind: {"blk": torch.zeros((nq, k), dtype=torch.int64, device=dev), "doc": torch.zeros((nq, k), dtype=torch.int32, device=dev),
-                  "row": torch.zeros((nq, k), dtype=torch.int64, device=dev), "dist": torch.zeros((nq, k), dtype=torch.float32, device=dev),
-                  "cnt": torch.zeros((nq,), dtype=torch.int32, device=dev)} for kind in ("K1s", "K1sm")}
-    torch.cuda.synchronize()
-    report = {"device": ctx.device_info()["name"], "rows": n, "dim": dim, "mean_row_nnz": mean_row_nnz, "queries": nq,
-              "mean_query_nnz": round(float(np.diff(q_ptr).mean()), 2), "max_query_nnz": max_nnz, "k": k, "windows": windows,
-              "calls_per_window": calls,
-              "timing": "host clock around calls_per_window calls and a synchronise, device-resident queries and results; a K1s window "
-                        "and a K1sm window alternate in one process; ms per call: median / min / max over the windows"}
-    for leg, fl in (("unfiltered", None), ("tree_rbac", corpus.pack_filters([corpus.filter_for_user(int(u), vsrbac.RANGES) for u in quser]))):
+    legs = (("unfiltered", None), ("tree_rbac", corpus.pack_filters([corpus.filter_for_user(int(u), vsrbac.RANGES) for u in quser])))
+    report = {"device": ctx.device_info()["name"], "rows": n, "dim": dim, "mean_row_nnz": mean_row_nnz, "queries": nq, "k": k,
+              "windows": windows, "calls_per_window": calls,
+              "timing": "host clock around calls_per_window calls and a synchronise, device-resident queries and results; a window of "
+                        "each kernel alternates in one process; ms per call: median / min / max over the windows"}
+    for label, query_nnz, cut, kind_a, kind_b in comparisons:
+        kinds = (kind_a, kind_b)
+        q_ptr, q_idx, q_val = sparse_rows(rng, nq, dim, query_nnz)
+        keep = np.arange(q_idx.size) - np.repeat(q_ptr[:-1], np.diff(q_ptr)) < cut           # the first `cut` entries of every query
+        q_idx, q_val = q_idx[keep], q_val[keep]
+        q_ptr = np.concatenate([[0], np.cumsum(np.minimum(np.diff(q_ptr), cut))]).astype(np.int64)
+        max_nnz = int(np.diff(q_ptr).max())
+        d_ptr, d_idx, d_val = (torch.from_numpy(a).to(dev) for a in (q_ptr, q_idx, q_val))
+        out = {kind: {"blk": torch.zeros((nq, k), dtype=torch.int64, device=dev), "doc": torch.zeros((nq, k), dtype=torch.int32, device=dev),
+                      "row": torch.zeros((nq, k), dtype=torch.int64, device=dev), "dist": torch.zeros((nq, k), dtype=torch.float32, device=dev),
+                      "cnt": torch.zeros((nq,), dtype=torch.int32, device=dev)} for kind in kinds}
+        torch.cuda.synchronize()
+        section = report.setdefault(label, {}) if label else report
+        section.update({"mean_query_nnz": round(float(np.diff(q_ptr).mean()), 2), "max_query_nnz": max_nnz})
+        ab_legs(ctx, corpus, legs, kinds, (d_ptr, d_idx, d_val), nq, max_nnz, k, windows, calls, out, ptr, section, label)
+    ctx.screening_check()                                      # raises if a staged query was refused
+    with open(os.path.join(args.out_dir, out_name), "w") as f:
+        json.dump(report, f, indent=1)
+        f.write("\n")
+    ctx.close()
+
+
+def ab_legs(ctx, corpus, legs, kinds, queries, nq, max_nnz, k, windows, calls, out, ptr, section, label):
+    d_ptr, d_idx, d_val = queries
+    for leg, fl in legs:
         for metric, op in (("ip", "<#>"), ("l2", "<->")):
-            ms, names = {"K1s": [], "K1sm": []}, {}
+            ms, names = {kind: [] for kind in kinds}, {}
 
             def window(kind):
                 ctx.set_sparse_shared(kind == "K1sm")
+                ctx.set_sparse_compact(kind == "K1sc")
                 o = out[kind]
                 ctx.synchronize()
                 t = time.perf_counter()
@@ -106,26 +129,23 @@ def shared_ab(args):
                 names[kind] = ctx.last_scan_kernel()
                 return (time.perf_counter() - t) / calls * 1e3
 
-            for kind in ("K1s", "K1sm"):
+            for kind in kinds:
                 window(kind)                                   # warm-up: code objects, workspaces, cached filters
             for _ in range(windows):
-                for kind in ("K1s", "K1sm"):
+                for kind in kinds:
                     ms[kind].append(window(kind))
-            a, b = ({f: t.cpu().numpy() for f, t in out[kind].items()} for kind in ("K1s", "K1sm"))
+            a, b = ({f: t.cpu().numpy() for f, t in out[kind].items()} for kind in kinds)
             entry = {"counts_equal": bool((a["cnt"] == b["cnt"]).all()),
                      "distances_within_1e-4": bool(np.allclose(a["dist"], b["dist"], rtol=1e-4, atol=1e-4)),
                      "queries_with_the_same_rows": int((a["row"] == b["row"]).all(axis=1).sum())}
-            for kind in ("K1s", "K1sm"):
+            for kind in kinds:
                 v = sorted(ms[kind])
                 entry[kind] = {"median_ms": round(v[len(v) // 2], 4), "min_ms": round(v[0], 4), "max_ms": round(v[-1], 4), "kernel": names[kind]}
-            entry["k1sm_over_k1s"] = round(entry["K1sm"]["median_ms"] / entry["K1s"]["median_ms"], 3)
-            report.setdefault(leg, {})[op] = entry
-            print(json.dumps({leg: {op: entry}}), flush=True)
-    ctx.screening_check()                                      # raises if a staged query was refused
-    with open(os.path.join(args.out_dir, "sparse_shared.json"), "w") as f:
-        json.dump(report, f, indent=1)
-        f.write("\n")
-    ctx.close()
+            entry[f"{kinds[1]}_over_{kinds[0]}".lower()] = round(entry[kinds[1]]["median_ms"] / entry[kinds[0]]["median_ms"], 3)
+            section.setdefault(leg, {})[op] = entry
+            print(json.dumps({label or "ab": {leg: {op: entry}}}), flush=True)
+    ctx.set_sparse_shared(False)
+    ctx.set_sparse_compact(False)
 
 
 def main():
@@ -141,11 +161,15 @@ def main():
     ap.add_argument("--singles", type=int, default=20, help="one-query calls per repetition of leg (a)")
     ap.add_argument("--seed", type=int, default=20251121)
     ap.add_argument("--shared-ab", action="store_true", help="only the K1s / K1sm A/B leg: writes OUT_DIR/sparse_shared.json")
+    ap.add_argument("--compact-ab", action="store_true", help="only the K1sm / K1sc and K1s / K1sc A/B legs: writes OUT_DIR/sparse_compact.json")
     ap.add_argument("--ab-calls", type=int, default=3, help="calls per window of the A/B leg")
     args = ap.parse_args()
-    if args.shared_ab:
+    if args.shared_ab or args.compact_ab:
         os.makedirs(args.out_dir, exist_ok=True)
-        return shared_ab(args)
+        if args.shared_ab:
+            return kernel_ab(args, "sparse_shared.json", [(None, args.query_nnz, 32, "K1s", "K1sm")])
+        return kernel_ab(args, "sparse_compact.json", [("short_queries_cut_at_32", 32, 32, "K1sm", "K1sc"),
+                                                       ("long_queries_cut_at_128", 100, 128, "K1s", "K1sc")])
 
     import torch
     import vsrbac

@@ -303,6 +303,7 @@ PassLaunch   launch_mfmahw_l2, launch_mfmahw_ip, launch_mfmahw_cosine;          
 PassLaunch   launch_mfmab_hamming, launch_mfmab_jaccard;                                 // vsr_mfmab_*.hip
 PassLaunch   launch_mfmaw_l2, launch_mfmaw_ip, launch_mfmaw_cosine;                      // vsr_mfmaw_*.hip
 PassLaunch   launch_scansm_l2, launch_scansm_ip, launch_scansm_cosine, launch_scansm_l1; // vsr_scansm_*.hip
+PassLaunch   launch_scansc_l2, launch_scansc_ip, launch_scansc_cosine, launch_scansc_l1; // vsr_scansc_*.hip
 PassLaunch   launch_gemm_l2, launch_gemm_ip, launch_gemm_cosine;                         // vsr_gemm_*.hip
 PassLaunch   launch_gemmh_l2, launch_gemmh_ip, launch_gemmh_cosine;                      // vsr_gemmh_*.hip
 // one query per call over the int8 planes (vsr_scan8.h): K1's top-k and in-kernel merge, a quarter of the bytes per row
@@ -547,6 +548,10 @@ inline size_t scans_lds_bytes(uint32_t qmax, uint32_t cap, uint32_t lds_slots)
 // block in LDS -- one probe per stored row entry instead of one per (entry, query); exact, K1s's values; K2b's cap
 // (mfma_cap_for_k), candidate buffers (p.cand) and block map.  p.qmax = QW, 16 or 32 (scansm_qw, vsr_scansm_sizing.h).  Opt-in
 hipError_t launch_scansm(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s);
+// K1sc (vsr_scansc.h): K1sm's pass over a compact query block -- a (mask, base) record per column and the packed values instead
+// of the dense block --, which fits QW = 32 up to 64 non-zeros and QW = 16 up to 128 at k = 100 (scansc_qw).  K1sm's values for a
+// given QW; the same cap, candidate buffers and block map.  Opt-in
+hipError_t launch_scansc(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s);
 bool scan_sparse_table_in_lds(uint32_t slots, int k);     // one query's table fits beside its candidate list
 int  scan_qmax_sparse(uint32_t slots, int k);             // queries per pass: 1, or a multiple of 4 up to SCAN_QMAX (table in LDS); 4 or 1 (global)
 // sparsevec.c:803-1037 for n explicit pairs, one thread per pair, pgvector's sequential merge; out: the operator's float8

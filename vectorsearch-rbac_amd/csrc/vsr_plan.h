@@ -25,8 +25,10 @@ struct PlanScalars {
     uint32_t walk_shift = 0;      // walk_table's slice of a position p: p >> walk_shift
     bool     k2b = false;         // shared passes of a bit corpus run on K2b (vsr_mfmab.h): exact, K2's candidate buffers, no K5r
     bool     k1sm = false;        // shared passes of a sparse corpus run on K1sm (vsr_scansm.h): exact, K2b's candidate buffers, qmax = QW
+    bool     k1sc = false;        // ... on K1sc (vsr_scansc.h): K1sm's pass over a compact query block, planned and launched as K1sm is; never both
     bool     k2g = false;         // ... on K2g: long rows, 256-query passes, coarse planes (vsr_gemm.h); implies k2w
     bool     sparse_global = false;   // K1s (sparse corpus): the query tables stay in global memory (vsr_scans.h, GLOBAL_TAB)
+    bool     sparse_merged() const { return k1sm || k1sc; }   // the queries of a pass share one union table
     uint32_t keep = 0;            // partial list length kp (K2: 2k screening survivors; else k)
     uint32_t rerank_base = 0;     // K2: first partial list holding the per-query screening survivors
     uint32_t n_scan_lists = 0;

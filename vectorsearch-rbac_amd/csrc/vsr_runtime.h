@@ -155,6 +155,7 @@ struct vsr_ctx {
     bool bit_mfma = false;         // vsr_set_bit_mfma / VSR_BIT_MFMA=1: shared passes over a bit corpus on K2b instead of K1b (opt-in)
     bool sparse_shared = false;    // vsr_set_sparse_shared / VSR_SPARSE_SHARED=1: shared passes over a sparse corpus on K1sm instead of K1s (opt-in)
     bool half_gemm = false;        // vsr_set_half_gemm / VSR_HALF_GEMM=1: 256-query passes over a halfvec corpus's long rows on K2gh (opt-in)
+    bool sparse_compact = false;   // vsr_set_sparse_compact / VSR_SPARSE_COMPACT=1: ... on K1sc, the compact block, where it fits (opt-in; ahead of K1sm)
     bool half_wide = false;        // vsr_set_half_wide / VSR_HALF_WIDE=1: shared passes over a halfvec corpus on K2hw instead of K2h (opt-in)
     bool no_half_mfma = false;     // VSR_NO_HALF_MFMA=1: shared passes over a halfvec corpus on K1h instead of K2h (A/B)
     bool no_k2i = true;            // VSR_K2I=1: the int8 main launch as K2i's per-wave streams instead of K2w's workgroup tiles (A/B;

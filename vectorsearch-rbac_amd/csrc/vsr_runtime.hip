@@ -85,6 +85,7 @@ extern "C" int vsr_open(int device, vsr_ctx** out)
     if ((env = getenv("VSR_NO_HALF_MFMA"))) ctx->no_half_mfma = atoi(env) != 0;
     if ((env = getenv("VSR_BIT_MFMA"))) ctx->bit_mfma = atoi(env) != 0;
     if ((env = getenv("VSR_SPARSE_SHARED"))) ctx->sparse_shared = atoi(env) != 0;
+    if ((env = getenv("VSR_SPARSE_COMPACT"))) ctx->sparse_compact = atoi(env) != 0;
     if ((env = getenv("VSR_HALF_WIDE"))) ctx->half_wide = atoi(env) != 0;
     if ((env = getenv("VSR_HALF_GEMM"))) ctx->half_gemm = atoi(env) != 0;
     if ((env = getenv("VSR_K2I"))) ctx->no_k2i = atoi(env) == 0;
@@ -833,6 +834,13 @@ extern "C" int vsr_set_sparse_shared(vsr_ctx* ctx, int enable)
 {
     if (!ctx) return fail(VSR_ERR_INVALID, "vsr_set_sparse_shared: ctx is NULL");
     ctx->sparse_shared = enable != 0;
+    return VSR_OK;
+}
+
+extern "C" int vsr_set_sparse_compact(vsr_ctx* ctx, int enable)
+{
+    if (!ctx) return fail(VSR_ERR_INVALID, "vsr_set_sparse_compact: ctx is NULL");
+    ctx->sparse_compact = enable != 0;
     return VSR_OK;
 }
 

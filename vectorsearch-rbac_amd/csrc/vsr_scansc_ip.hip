@@ -1,0 +1,11 @@
+// vsr_scansc_ip.hip — instantiates the K1sc kernels (shared passes over a sparse corpus, compact query block, vsr_scansc.h) for one metric.
+#include "vsr_scansc.h"
+
+namespace vsr {
+
+hipError_t launch_scansc_ip(const ScanParams& p, uint32_t n_blocks, hipStream_t s)
+{
+    return launch_scansc_metric<M_IP>(p, n_blocks, s);
+}
+
+}  // namespace vsr

@@ -39,4 +39,21 @@ inline int scansm_qw(uint32_t sp_slots, uint32_t cap, int max_qw)
     return 0;
 }
 
+// K1sc (vsr_scansc.h): the same pass over a compact block.  LDS of one workgroup: the sort buffer, the union table, one record
+// (mask, base: 8 bytes) per column, one fp32 per (query, non-zero) -- at most scansm_max_columns of either --, and the small
+// terms of scansm_lds_bytes.  Grows as qw x sp_slots where the dense block grows as qw^2 x sp_slots
+inline size_t scansc_lds_bytes(int qw, uint32_t sp_slots, uint32_t cap)
+{
+    return (size_t) cap * 8 + (size_t) scansm_union_slots(qw, sp_slots) * 8 + (size_t) scansm_max_columns(qw, sp_slots) * (8 + 4) +
+           (size_t) SM_WAVES * 16 + (size_t) qw * (16 + 8 + 4) + 32;
+}
+
+// queries per pass of K1sc: 32 if the compact block fits the budget, else 16, else 0 (the call is planned without K1sc)
+inline int scansc_qw(uint32_t sp_slots, uint32_t cap, int max_qw)
+{
+    if (max_qw >= 32 && scansc_lds_bytes(32, sp_slots, cap) <= SCANSM_LDS_BUDGET) return 32;
+    if (max_qw >= 16 && scansc_lds_bytes(16, sp_slots, cap) <= SCANSM_LDS_BUDGET) return 16;
+    return 0;
+}
+
 }  // namespace vsr

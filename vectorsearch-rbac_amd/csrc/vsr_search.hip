@@ -623,8 +623,8 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
         sp.sp_qtot = reinterpret_cast<const double*>(ds + off_qt);
     }
     sp.partial = ctx->d_partial.as<uint64_t>();
-    sp.cap = plan.k2 || plan.k2b || plan.k1sm ? mfma_cap_for_k(kp) : scan_cap_for_rw((int) kp, c->shape.rw);
-    if (plan.mq || plan.k2 || plan.k2b || plan.k1sm) {
+    sp.cap = plan.k2 || plan.k2b || plan.sparse_merged() ? mfma_cap_for_k(kp) : scan_cap_for_rw((int) kp, c->shape.rw);
+    if (plan.mq || plan.k2 || plan.k2b || plan.sparse_merged()) {
         RCCHK(ctx->d_cand.reserve(std::max<size_t>(8, (size_t) plan.n_scan_lists * cand_pitch(sp.cap) * sizeof(uint64_t))));
         sp.cand = ctx->d_cand.as<uint64_t>();
     }
@@ -692,6 +692,7 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
         else if (plan.mq) HIPCHK(launch_mq(sp, metric, launch_blocks, ctx->stream));
         else if (plan.k2b) HIPCHK(launch_mfmab(sp, metric, launch_blocks, ctx->stream));   // exact keys: K5 alone follows
         else if (plan.k1sm) HIPCHK(launch_scansm(sp, metric, launch_blocks, ctx->stream)); // exact keys too
+        else if (plan.k1sc) HIPCHK(launch_scansc(sp, metric, launch_blocks, ctx->stream)); // ... and the same ones
         else HIPCHK(launch_scan(c->format, sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream, c->shape.lpr, plan.sparse_global));
         HIPCHK(main.stop());
         ctx->last_kernel = scan_kernel_name(plan, c, metric);

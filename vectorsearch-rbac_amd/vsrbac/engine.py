@@ -181,6 +181,13 @@ class Context:
         one query each and calls whose longest query does not fit the merged block stay on K1s."""
         check(self._lib.vsr_set_sparse_shared(self._h, int(bool(enable))))
 
+    def set_sparse_compact(self, enable=True):
+        """Run the shared passes of this context's searches over sparse corpora on K1sc: K1sm's pass with the merged queries kept
+        compactly (a mask per index and the packed values), which serves queries of up to 128 non-zeros at k = 100 and 32 queries
+        per pass up to 64.  Exact, K1sm's values.  Default off and independent of set_sparse_shared; one-query calls and calls
+        with a longer query run as if it were off."""
+        check(self._lib.vsr_set_sparse_compact(self._h, int(bool(enable))))
+
     def set_half_wide(self, on=True):
         """Run the shared passes of this context's searches over halfvec corpora and half IVFFlat indexes on K2hw (a row tile
         staged once per workgroup for up to 64 queries) instead of K2h.  Same results; default off."""
