@@ -354,6 +354,22 @@ int vsr_set_sparse_shared(vsr_ctx* ctx, int enable);
  * calls with a longer query and corpora that are not sparse corpora run exactly as with this switch off (on K1sm if that
  * switch is on and its block fits, else on K1s). */
 int vsr_set_sparse_compact(vsr_ctx* ctx, int enable);
+/* sparsevec corpora: builds the inverted image of a corpus made by vsr_corpus_load_sparse, on the GPU, from its resident rows:
+ * the rows cut into row blocks of 512, and per block the distinct indices of its rows with their posting segments (row in
+ * block, value), plus sum a^2 and sum |a| of every row in double.  Device memory: 8 bytes per stored entry, 12 per (row block,
+ * distinct index) and per row block, 16 per row -- bounded by the stored entries whatever the dimension; counted by
+ * vsr_corpus_device_bytes, released by vsr_corpus_free.  About 24 bytes per stored entry more while it is built.  A second
+ * call returns VSR_OK and builds nothing.  VSR_ERR_UNSUPPORTED: not a sparse corpus, a view of another corpus, or 2^31-2
+ * stored entries and more. */
+int vsr_corpus_build_sparse_inverted(vsr_corpus* sparse_corpus);
+/* sparsevec corpora: enable != 0 runs the searches of vsr_search_sparse* over a corpus that has its inverted image on K1si: a
+ * query walks the posting segments of its own indices only, row block by row block, and what the other entries of a row add to
+ * a distance comes from the row's two sums.  Exact: the same filtered top-k contract, all four operators; distances within the
+ * library's 1e-4 of the other sparse kernels' (identical where the sums are exact).  Passes of up to 16 queries, one-query calls
+ * too.  Default: 0 (VSR_SPARSE_INVERTED=1 at vsr_open sets it); independent of vsr_set_sparse_shared and
+ * vsr_set_sparse_compact and ahead of both; takes effect from the context's next search.  A corpus without the image and a call
+ * whose longest query has more than 256 non-zeros run exactly as with this switch off. */
+int vsr_set_sparse_inverted(vsr_ctx* ctx, int enable);
 /* halfvec corpora: on != 0 runs the passes that two or more queries share -- vsr_search*, the list scans of vsr_ivf_search* over a
  * half index -- on K2hw instead of K2h: a 64-row tile of the binary16 rows is staged once per workgroup and multiplied on the f16
  * matrix cores against up to 64 queries per pass (K2h: 16 or 32 per wave-private tile), with threshold seeds from a sample pass

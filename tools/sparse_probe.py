@@ -28,7 +28,13 @@ the same rows).  Writes OUT_DIR/sparse_shared.json.
 
 runs in the same way the two A/B comparisons of K1sc (vsr_scansc.h, Context.set_sparse_compact): queries of ~30 non-zeros cut at
 32, K1sm (QW = 16 there) against K1sc (QW = 32); queries of ~100 cut at 128, which K1sm does not serve, K1s against K1sc
-(QW = 16).  Writes OUT_DIR/sparse_compact.json."""
+(QW = 16).  Writes OUT_DIR/sparse_compact.json.
+
+    python tools/sparse_probe.py OUT_DIR --inverted-ab
+
+builds the corpus's inverted image (Corpus.build_sparse_inverted: its bytes and build time are recorded) and runs, in the same
+way, K1si (vsr_scansi.h, Context.set_sparse_inverted) against K1sc at queries of ~30 non-zeros cut at 32 and of ~100 cut at 128,
+and against K1s with one query per call (the first of the ~30 non-zero queries).  Writes OUT_DIR/sparse_inverted.json."""
 import argparse
 import ctypes
 import json
@@ -66,6 +72,7 @@ def sparse_rows(rng, n, dim, mean_nnz):
 def kernel_ab(args, out_name, comparisons):
     """Two sparse scan kernels in one resident process, timed alternately window by window.  comparisons: (label, Poisson mean of the
     queries' non-zeros, cut, kernel A, kernel B), a kernel being K1s, K1sm (Context.set_sparse_shared) or K1sc (set_sparse_compact);
+    K1si (build_sparse_inverted + set_sparse_inverted); an optional sixth element gives the queries per call (default: all of them);
     the report has one section per label, or none at all for a single unlabelled comparison."""
     import torch
     import vsrbac
@@ -83,14 +90,22 @@ def kernel_ab(args, out_name, comparisons):
     rbac = tree_rbac(num_users=1000, num_roles=100, num_docs=n // 100, seed=args.seed)
     corpus.load_rbac(rbac.user_roles, rbac.permissions)
     _, quser = sample_queries(nq, n, 1000, seed=args.seed)
-    legs = (("unfiltered", None), ("tree_rbac", corpus.pack_filters([corpus.filter_for_user(int(u), vsrbac.RANGES) for u in quser])))
     report = {"device": ctx.device_info()["name"], "rows": n, "dim": dim, "mean_row_nnz": mean_row_nnz, "queries": nq, "k": k,
               "windows": windows, "calls_per_window": calls,
               "timing": "host clock around calls_per_window calls and a synchronise, device-resident queries and results; a window of "
                         "each kernel alternates in one process; ms per call: median / min / max over the windows"}
-    for label, query_nnz, cut, kind_a, kind_b in comparisons:
+    if any("K1si" in c[3:5] for c in comparisons):
+        before = corpus.device_bytes()
+        ctx.synchronize()
+        t = time.perf_counter()
+        corpus.build_sparse_inverted()
+        ctx.synchronize()
+        report["inverted_image"] = {"build_ms": round((time.perf_counter() - t) * 1e3, 2), "bytes": corpus.device_bytes() - before, "corpus_bytes": before}
+    all_nq = nq
+    for label, query_nnz, cut, kind_a, kind_b, *per_call in comparisons:
         kinds = (kind_a, kind_b)
-        q_ptr, q_idx, q_val = sparse_rows(rng, nq, dim, query_nnz)
+        nq = per_call[0] if per_call else all_nq
+        q_ptr, q_idx, q_val = sparse_rows(rng, all_nq, dim, query_nnz)
         keep = np.arange(q_idx.size) - np.repeat(q_ptr[:-1], np.diff(q_ptr)) < cut           # the first `cut` entries of every query
         q_idx, q_val = q_idx[keep], q_val[keep]
         q_ptr = np.concatenate([[0], np.cumsum(np.minimum(np.diff(q_ptr), cut))]).astype(np.int64)
@@ -101,7 +116,8 @@ def kernel_ab(args, out_name, comparisons):
                       "cnt": torch.zeros((nq,), dtype=torch.int32, device=dev)} for kind in kinds}
         torch.cuda.synchronize()
         section = report.setdefault(label, {}) if label else report
-        section.update({"mean_query_nnz": round(float(np.diff(q_ptr).mean()), 2), "max_query_nnz": max_nnz})
+        section.update({"mean_query_nnz": round(float(np.diff(q_ptr).mean()), 2), "max_query_nnz": max_nnz, "queries_per_call": nq})
+        legs = (("unfiltered", None), ("tree_rbac", corpus.pack_filters([corpus.filter_for_user(int(u), vsrbac.RANGES) for u in quser[:nq]])))
         ab_legs(ctx, corpus, legs, kinds, (d_ptr, d_idx, d_val), nq, max_nnz, k, windows, calls, out, ptr, section, label)
     ctx.screening_check()                                      # raises if a staged query was refused
     with open(os.path.join(args.out_dir, out_name), "w") as f:
@@ -119,6 +135,7 @@ def ab_legs(ctx, corpus, legs, kinds, queries, nq, max_nnz, k, windows, calls, o
             def window(kind):
                 ctx.set_sparse_shared(kind == "K1sm")
                 ctx.set_sparse_compact(kind == "K1sc")
+                ctx.set_sparse_inverted(kind == "K1si")
                 o = out[kind]
                 ctx.synchronize()
                 t = time.perf_counter()
@@ -146,6 +163,7 @@ def ab_legs(ctx, corpus, legs, kinds, queries, nq, max_nnz, k, windows, calls, o
             print(json.dumps({label or "ab": {leg: {op: entry}}}), flush=True)
     ctx.set_sparse_shared(False)
     ctx.set_sparse_compact(False)
+    ctx.set_sparse_inverted(False)
 
 
 def main():
@@ -162,10 +180,15 @@ def main():
     ap.add_argument("--seed", type=int, default=20251121)
     ap.add_argument("--shared-ab", action="store_true", help="only the K1s / K1sm A/B leg: writes OUT_DIR/sparse_shared.json")
     ap.add_argument("--compact-ab", action="store_true", help="only the K1sm / K1sc and K1s / K1sc A/B legs: writes OUT_DIR/sparse_compact.json")
+    ap.add_argument("--inverted-ab", action="store_true", help="only the K1sc / K1si and K1s / K1si (one query per call) A/B legs: writes OUT_DIR/sparse_inverted.json")
     ap.add_argument("--ab-calls", type=int, default=3, help="calls per window of the A/B leg")
     args = ap.parse_args()
-    if args.shared_ab or args.compact_ab:
+    if args.shared_ab or args.compact_ab or args.inverted_ab:
         os.makedirs(args.out_dir, exist_ok=True)
+        if args.inverted_ab:
+            return kernel_ab(args, "sparse_inverted.json", [("short_queries_cut_at_32", 32, 32, "K1sc", "K1si"),
+                                                            ("long_queries_cut_at_128", 100, 128, "K1sc", "K1si"),
+                                                            ("one_query_per_call", 32, 32, "K1s", "K1si", 1)])
         if args.shared_ab:
             return kernel_ab(args, "sparse_shared.json", [(None, args.query_nnz, 32, "K1s", "K1sm")])
         return kernel_ab(args, "sparse_compact.json", [("short_queries_cut_at_32", 32, 32, "K1sm", "K1sc"),

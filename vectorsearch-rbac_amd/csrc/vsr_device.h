@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "vsr_bounds.h"
 #include "vsr_scansm_sizing.h"
+#include "vsr_scansi_sizing.h"
 
 namespace vsr {
 
@@ -143,6 +144,14 @@ struct ScanParams {
     const uint2*     sp_tab;       // [n_slots][sp_slots] (index, value bits); empty slot: index SPARSE_EMPTY, value 0
     uint32_t         sp_slots;     // slots per table, a power of two >= 2
     const double*    sp_qtot;      // [n_slots][2] sum q^2, sum |q| of the staged query, in double
+    // K1si (vsr_scansi.h): the corpus's inverted image (SparseInverted, vsr_runtime.h), row blocks of SI_RB rows
+    const uint2*     si_post;      // [si_n_post] (row in block, value bits), ordered by (row block, index, row)
+    const uint32_t*  si_bterm;     // [si_n_terms] the distinct indices of every row block, ascending inside a block
+    const uint64_t*  si_boff;      // [si_n_terms + blocks] block b's segment j: si_post[si_boff[si_bbeg[b] + b + j] .. [.. + j + 1])
+    const uint32_t*  si_bbeg;      // [blocks + 1] block b's run of si_bterm: [si_bbeg[b], si_bbeg[b + 1])
+    const double*    si_a;         // [2][n_rows] sum a^2, then sum |a| of every row, in double, in entry order
+    uint64_t         si_n_post;
+    uint32_t         si_n_terms;
 };
 
 // Per query: which partial lists to merge and where to put the result.
@@ -304,6 +313,7 @@ PassLaunch   launch_mfmab_hamming, launch_mfmab_jaccard;                        
 PassLaunch   launch_mfmaw_l2, launch_mfmaw_ip, launch_mfmaw_cosine;                      // vsr_mfmaw_*.hip
 PassLaunch   launch_scansm_l2, launch_scansm_ip, launch_scansm_cosine, launch_scansm_l1; // vsr_scansm_*.hip
 PassLaunch   launch_scansc_l2, launch_scansc_ip, launch_scansc_cosine, launch_scansc_l1; // vsr_scansc_*.hip
+PassLaunch   launch_scansi_l2, launch_scansi_ip, launch_scansi_cosine, launch_scansi_l1; // vsr_scansi_*.hip
 PassLaunch   launch_gemm_l2, launch_gemm_ip, launch_gemm_cosine;                         // vsr_gemm_*.hip
 PassLaunch   launch_gemmh_l2, launch_gemmh_ip, launch_gemmh_cosine;                      // vsr_gemmh_*.hip
 // one query per call over the int8 planes (vsr_scan8.h): K1's top-k and in-kernel merge, a quarter of the bytes per row
@@ -552,6 +562,18 @@ hipError_t launch_scansm(const ScanParams& p, int metric, uint32_t n_blocks, hip
 // of the dense block --, which fits QW = 32 up to 64 non-zeros and QW = 16 up to 128 at k = 100 (scansc_qw).  K1sm's values for a
 // given QW; the same cap, candidate buffers and block map.  Opt-in
 hipError_t launch_scansc(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s);
+// K1si (vsr_scansi.h): the passes of a sparse corpus over its inverted image -- a wave per query walks the posting segments of
+// the query's own indices into LDS accumulators, row block by row block, and sweeps the block's tiles; exact, the model's values
+// on data whose sums are exact; K1sm's cap, candidate buffers and block map.  p.qmax = SI_QMAX (vsr_scansi_sizing.h).  Opt-in
+hipError_t launch_scansi(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s);
+// the image's build (vsr_sparse_inverted.hip): the arrays ScanParams::si_* name, allocated here, owned by the caller
+struct SparseInvertedArrays {
+    uint2* post = nullptr; uint32_t* bterm = nullptr; uint64_t* boff = nullptr; uint32_t* bbeg = nullptr; double* a = nullptr;
+    uint64_t n_post = 0;
+    uint32_t n_terms = 0, n_blocks = 0;
+};
+hipError_t build_sparse_inverted(const float4* rows, const uint64_t* sp_off, uint64_t entries, uint32_t n_rows, hipStream_t s,
+                                 SparseInvertedArrays* out);
 bool scan_sparse_table_in_lds(uint32_t slots, int k);     // one query's table fits beside its candidate list
 int  scan_qmax_sparse(uint32_t slots, int k);             // queries per pass: 1, or a multiple of 4 up to SCAN_QMAX (table in LDS); 4 or 1 (global)
 // sparsevec.c:803-1037 for n explicit pairs, one thread per pair, pgvector's sequential merge; out: the operator's float8

@@ -68,6 +68,11 @@ hipError_t launch_scansc(const ScanParams& p, int metric, uint32_t n_blocks, hip
     return launch_pass(by_metric(metric, launch_scansc_l2, launch_scansc_ip, launch_scansc_cosine, launch_scansc_l1), p, n_blocks, s);
 }
 
+hipError_t launch_scansi(const ScanParams& p, int metric, uint32_t n_blocks, hipStream_t s)
+{
+    return launch_pass(by_metric(metric, launch_scansi_l2, launch_scansi_ip, launch_scansi_cosine, launch_scansi_l1), p, n_blocks, s);
+}
+
 bool mq_supported(int dim) { return (dim + 3) / 4 >= 16; }
 
 int mq_qmax(int dim)

@@ -28,7 +28,8 @@ struct PlanScalars {
     bool     k1sc = false;        // ... on K1sc (vsr_scansc.h): K1sm's pass over a compact query block, planned and launched as K1sm is; never both
     bool     k2g = false;         // ... on K2g: long rows, 256-query passes, coarse planes (vsr_gemm.h); implies k2w
     bool     sparse_global = false;   // K1s (sparse corpus): the query tables stay in global memory (vsr_scans.h, GLOBAL_TAB)
-    bool     sparse_merged() const { return k1sm || k1sc; }   // the queries of a pass share one union table
+    bool     k1si = false;        // the passes of a sparse corpus, one-query passes too, run on K1si (vsr_scansi.h) over the inverted image: exact, qmax = SI_QMAX; never with the two above
+    bool     sparse_merged() const { return k1sm || k1sc || k1si; }   // a sparse kernel on K2b's cap, candidate buffers and block map
     uint32_t keep = 0;            // partial list length kp (K2: 2k screening survivors; else k)
     uint32_t rerank_base = 0;     // K2: first partial list holding the per-query screening survivors
     uint32_t n_scan_lists = 0;

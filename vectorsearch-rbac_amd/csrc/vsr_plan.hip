@@ -52,6 +52,7 @@ struct Width {                               // what the kernel family and pass 
     bool     k2b_ok;                         // bit corpus: shared passes on K2b (vsr_mfmab.h)
     int      k1sm_qw;                        // sparse corpus: shared passes on K1sm (vsr_scansm.h) with this QW; 0: K1s
     int      k1sc_qw;                        // ... on K1sc (vsr_scansc.h) with this QW, ahead of K1sm; 0: as without it
+    int      k1si_qw;                        // sparse corpus with its inverted image: every pass on K1si (vsr_scansi.h), this many queries each, ahead of both; 0: as without it
     bool     k2hw_ok;                        // halfvec corpus: shared passes on K2hw (vsr_mfmahw.h), planned as K2w's are
     bool     k2gh;                           // halfvec corpus, long rows, parts seen by > 128 queries: 256-query passes on K2gh (vsr_gemmh.h)
     bool     wide() const { return k2w_ok || k2hw_ok || k2gh; }   // one candidate buffer per query, sample pass, select + re-rank
@@ -154,6 +155,8 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     // block fits K2b's LDS budget beside the sort buffer of that k, else 16, else K1s.  Not a view)
     // (... or, switched on by vsr_set_sparse_compact, K1sc: the same pass over a compact block, QW by scansc_qw.  Where that is
     // 0 -- queries of more than 128 non-zeros at k = 100 -- the call is planned as if the switch were off)
+    // (... or, switched on by vsr_set_sparse_inverted over a corpus that has its inverted image, K1si: passes of up to SI_QMAX queries,
+    // one-query passes too, while the call's longest query has at most SI_MAX_TERMS non-zeros; else planned as if the switch were off)
     const bool f32 = c->format == RowFormat::F32, half = c->format == RowFormat::HALF;
     w.mq_ok = f32 && mq_supported(c->dim) && mq_qmax(c->dim) >= 4 && !ctx->no_mq;
     // K2 / K2w: matrix-core screening keeps 2k (>= 32) candidates per query, K5r re-ranks them exactly
@@ -193,10 +196,13 @@ Width choose_width(const PlanIn& in, const std::vector<uint32_t>& gend, bool all
     const int k2b_q = mfmab_lds_bytes(k2b_cap, 32) <= MFMAB_LDS_BUDGET ? 32 : mfmab_lds_bytes(k2b_cap, 16) <= MFMAB_LDS_BUDGET ? 16 : 0;
     w.k2b_ok = c->format == RowFormat::BIT && ctx->bit_mfma && !c->d_rank && k2b_q > 0;
     const bool sparse_base = c->format == RowFormat::SPARSE && !c->d_rank;
-    w.k1sc_qw = sparse_base && ctx->sparse_compact ? scansc_qw(ctx->sparse_slots, mfma_cap_for_k((uint32_t) in.k), ctx->max_qb_set ? ctx->max_qb : 32) : 0;
-    w.k1sm_qw = sparse_base && ctx->sparse_shared && !w.k1sc_qw
+    w.k1si_qw = sparse_base && ctx->sparse_inverted && c->sp_inverted && scansi_fits(ctx->sparse_slots, mfma_cap_for_k((uint32_t) in.k))
+                    ? (ctx->max_qb_set ? std::max(1, std::min(ctx->max_qb, SI_QMAX)) : SI_QMAX) : 0;
+    w.k1sc_qw = sparse_base && ctx->sparse_compact && !w.k1si_qw ? scansc_qw(ctx->sparse_slots, mfma_cap_for_k((uint32_t) in.k), ctx->max_qb_set ? ctx->max_qb : 32) : 0;
+    w.k1sm_qw = sparse_base && ctx->sparse_shared && !w.k1sc_qw && !w.k1si_qw
                     ? scansm_qw(ctx->sparse_slots, mfma_cap_for_k((uint32_t) in.k), ctx->max_qb_set ? ctx->max_qb : 32) : 0;
     if (w.wide()) w.qmax = ctx->max_qb_set ? std::min(ctx->max_qb, w.wq) : w.wq;
+    else if (w.k1si_qw) w.qmax = w.k1si_qw;
     else if (w.k1sc_qw) w.qmax = w.k1sc_qw;
     else if (w.k1sm_qw) w.qmax = w.k1sm_qw;
     else if (w.k2b_ok) w.qmax = ctx->max_qb_set ? std::min(ctx->max_qb, k2b_q) : k2b_q;
@@ -273,6 +279,7 @@ void set_family(const PlanIn& in, const Width& w, uint32_t widest, Plan& plan)
     plan.k2b = plan.qi == 4 && w.k2b_ok;                    // exact: keep stays k, no K5r
     plan.k1sm = plan.qi == 4 && w.k1sm_qw > 0;              // exact: keep stays k
     plan.k1sc = plan.qi == 4 && w.k1sc_qw > 0;              // exact too; k1sm_qw is 0 then
+    plan.k1si = w.k1si_qw > 0;                              // exact; whatever the widest pass: one query per wave and round
     plan.keep = plan.k2 ? w.keep : (uint32_t) in.k;
     // K1s: a table that does not fit LDS beside one candidate list is read from global memory, and then qmax = QI
     plan.sparse_global = in.c->format == RowFormat::SPARSE && !scan_sparse_table_in_lds(in.ctx->sparse_slots, in.k);
@@ -280,6 +287,7 @@ void set_family(const PlanIn& in, const Width& w, uint32_t widest, Plan& plan)
     else if (plan.k2 || plan.k2b) plan.qmax = plan.qmax > 16 ? 32 : 16;
     else if (plan.k1sm) plan.qmax = (uint32_t) w.k1sm_qw;   // the instantiation: QW by what fits, not by the widest pass
     else if (plan.k1sc) plan.qmax = (uint32_t) w.k1sc_qw;
+    else if (plan.k1si) plan.qmax = (uint32_t) SI_QMAX;     // the kernel's control words, not the widest pass
     plan.int8 = plan.k2w && in.c->d_scr8 && in.metric == VSR_METRIC_L2 && in.ctx->int8_this_call;
     if (plan.int8) plan.keep = (uint32_t) std::max(in.k, 32);  // exact screening: no second half of survivors to re-rank
     plan.k2g = plan.k2w && w.k2g && !plan.int8;
@@ -819,6 +827,10 @@ std::string vsr::scan_kernel_name(const Plan& plan, const vsr_corpus* c, int met
     else
         switch (c->format) {
         case RowFormat::SPARSE:
+            if (plan.k1si) {
+                snprintf(buf, sizeof buf, "vsr::scansi_kernel<%s> (K1si, sparse rows)", mname[metric]);
+                break;
+            }
             if (plan.k1sc) {
                 snprintf(buf, sizeof buf, "vsr::scansc_kernel<%s, QW=%u> (K1sc, sparse rows)", mname[metric], plan.qmax);
                 break;

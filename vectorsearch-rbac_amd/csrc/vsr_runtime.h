@@ -155,6 +155,7 @@ struct vsr_ctx {
     bool bit_mfma = false;         // vsr_set_bit_mfma / VSR_BIT_MFMA=1: shared passes over a bit corpus on K2b instead of K1b (opt-in)
     bool sparse_shared = false;    // vsr_set_sparse_shared / VSR_SPARSE_SHARED=1: shared passes over a sparse corpus on K1sm instead of K1s (opt-in)
     bool half_gemm = false;        // vsr_set_half_gemm / VSR_HALF_GEMM=1: 256-query passes over a halfvec corpus's long rows on K2gh (opt-in)
+    bool sparse_inverted = false;  // vsr_set_sparse_inverted / VSR_SPARSE_INVERTED=1: searches over a sparse corpus that has its inverted image on K1si (opt-in; ahead of K1sc and K1sm)
     bool sparse_compact = false;   // vsr_set_sparse_compact / VSR_SPARSE_COMPACT=1: ... on K1sc, the compact block, where it fits (opt-in; ahead of K1sm)
     bool half_wide = false;        // vsr_set_half_wide / VSR_HALF_WIDE=1: shared passes over a halfvec corpus on K2hw instead of K2h (opt-in)
     bool no_half_mfma = false;     // VSR_NO_HALF_MFMA=1: shared passes over a halfvec corpus on K1h instead of K2h (A/B)
@@ -245,6 +246,20 @@ struct ClassView {
     }
 };
 
+// The inverted image of a sparse corpus (vsr_corpus_build_sparse_inverted; vsr_sparse_inverted.hip builds it, K1si walks it):
+// sparse_inverted_bytes (vsr_scansi_sizing.h) of device memory, dropped with the corpus.
+struct SparseInverted {
+    vsr::SparseInvertedArrays a;
+    uint64_t rows = 0;
+    size_t bytes() const { return vsr::sparse_inverted_bytes(a.n_post, a.n_terms, rows); }
+    ~SparseInverted()
+    {
+        void* ptrs[] = {a.post, a.bterm, a.boff, a.bbeg, a.a};
+        for (void* p : ptrs)
+            if (p) (void) hipFree(p);
+    }
+};
+
 struct vsr_corpus {
     vsr_ctx*    ctx = nullptr;
     // identity of this corpus among all the process ever created: never reused, unlike the address.  A quantized corpus
@@ -267,6 +282,7 @@ struct vsr_corpus {
     RowFormat   format = RowFormat::F32;
     uint64_t*   d_sp_off = nullptr;
     uint64_t    sp_entries = 0;          // stored entries, pad entries included
+    std::unique_ptr<SparseInverted> sp_inverted;   // none: not built (K1si needs it)
     uint32_t    sp_max_nnz = 0;          // non-zeros of the longest row (the HNSW entry points take at most HNSW_MAX_NNZ = 1000)
     int64_t     row_offset = 0;
     KernelShape shape{};

@@ -86,6 +86,7 @@ extern "C" int vsr_open(int device, vsr_ctx** out)
     if ((env = getenv("VSR_BIT_MFMA"))) ctx->bit_mfma = atoi(env) != 0;
     if ((env = getenv("VSR_SPARSE_SHARED"))) ctx->sparse_shared = atoi(env) != 0;
     if ((env = getenv("VSR_SPARSE_COMPACT"))) ctx->sparse_compact = atoi(env) != 0;
+    if ((env = getenv("VSR_SPARSE_INVERTED"))) ctx->sparse_inverted = atoi(env) != 0;
     if ((env = getenv("VSR_HALF_WIDE"))) ctx->half_wide = atoi(env) != 0;
     if ((env = getenv("VSR_HALF_GEMM"))) ctx->half_gemm = atoi(env) != 0;
     if ((env = getenv("VSR_K2I"))) ctx->no_k2i = atoi(env) == 0;
@@ -601,6 +602,25 @@ extern "C" int vsr_corpus_load_sparse(vsr_ctx* ctx, const int64_t* indptr, const
 
 extern "C" int vsr_corpus_is_sparse(const vsr_corpus* c) { return c && c->format == RowFormat::SPARSE ? 1 : 0; }
 
+// the inverted image K1si walks, from the resident CSR rows (vsr_sparse_inverted.hip); a second call builds nothing
+extern "C" int vsr_corpus_build_sparse_inverted(vsr_corpus* c)
+{
+    const char* who = "vsr_corpus_build_sparse_inverted";
+    if (!c) return fail(VSR_ERR_INVALID, "%s: corpus is NULL", who);
+    if (c->format != RowFormat::SPARSE) return fail(VSR_ERR_UNSUPPORTED, "%s: not a sparse corpus (only vsr_corpus_load_sparse makes one)", who);
+    if (c->base || c->d_rank) return fail(VSR_ERR_UNSUPPORTED, "%s: a view of another corpus has no inverted image (build its base's)", who);
+    if (c->sp_inverted) return VSR_OK;
+    if (c->sp_entries + 1 >= 0x7FFFFFFFull) return fail(VSR_ERR_UNSUPPORTED, "%s: more than 2^31-2 stored entries", who);
+    vsr_ctx* ctx = c->ctx;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    std::unique_ptr<SparseInverted> im(new SparseInverted());
+    im->rows = (uint64_t) c->n;
+    HIPCHK(build_sparse_inverted(c->d_rows, c->d_sp_off, c->sp_entries, (uint32_t) c->n, ctx->stream, &im->a));
+    c->sp_inverted = std::move(im);
+    return VSR_OK;
+}
+
 // sparsevec.c:803-1037 for n explicit pairs (host CSR triples)
 extern "C" int vsr_sparse_pair_distances(vsr_ctx* ctx, int metric, const int64_t* a_indptr, const int32_t* a_indices,
                                          const float* a_values, const int64_t* b_indptr, const int32_t* b_indices,
@@ -794,7 +814,8 @@ extern "C" int64_t vsr_corpus_device_bytes(const vsr_corpus* c)
     if (!c) return 0;
     const size_t rows = (size_t) std::max<int64_t>(c->n, 1);
     if (c->format == RowFormat::SPARSE)                      // entries, row offsets, |row|^2
-        return (int64_t) ((size_t) c->sp_entries * 8 + 1024 + (rows + 1) * sizeof(uint64_t) + rows * sizeof(float));
+        return (int64_t) ((size_t) c->sp_entries * 8 + 1024 + (rows + 1) * sizeof(uint64_t) + rows * sizeof(float) +
+                          (c->sp_inverted ? c->sp_inverted->bytes() : 0));   // ... and the inverted image, once built
     size_t b = rows * format_row_chunks(c->format, c->dim) * 16 + 1024 + rows * sizeof(float);   // d_rows, d_norm2
     if (c->d_norm2_max) b += 64;
     if (c->d_scr) b += rows * (size_t) c->pstride4 * 16 + 1024;
@@ -841,6 +862,13 @@ extern "C" int vsr_set_sparse_compact(vsr_ctx* ctx, int enable)
 {
     if (!ctx) return fail(VSR_ERR_INVALID, "vsr_set_sparse_compact: ctx is NULL");
     ctx->sparse_compact = enable != 0;
+    return VSR_OK;
+}
+
+extern "C" int vsr_set_sparse_inverted(vsr_ctx* ctx, int enable)
+{
+    if (!ctx) return fail(VSR_ERR_INVALID, "vsr_set_sparse_inverted: ctx is NULL");
+    ctx->sparse_inverted = enable != 0;
     return VSR_OK;
 }
 

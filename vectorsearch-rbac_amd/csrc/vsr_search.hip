@@ -621,6 +621,16 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
         sp.sp_tab = reinterpret_cast<const uint2*>(ds);
         sp.sp_slots = sp_slots;
         sp.sp_qtot = reinterpret_cast<const double*>(ds + off_qt);
+        if (plan.k1si) {                                    // (planned only over a corpus that has the image)
+            const SparseInvertedArrays& im = c->sp_inverted->a;
+            sp.si_post = im.post;
+            sp.si_bterm = im.bterm;
+            sp.si_boff = im.boff;
+            sp.si_bbeg = im.bbeg;
+            sp.si_a = im.a;
+            sp.si_n_post = im.n_post;
+            sp.si_n_terms = im.n_terms;
+        }
     }
     sp.partial = ctx->d_partial.as<uint64_t>();
     sp.cap = plan.k2 || plan.k2b || plan.sparse_merged() ? mfma_cap_for_k(kp) : scan_cap_for_rw((int) kp, c->shape.rw);
@@ -693,6 +703,7 @@ int search_general(vsr_ctx* ctx, vsr_corpus* c, const Plan& plan, const Call& q,
         else if (plan.k2b) HIPCHK(launch_mfmab(sp, metric, launch_blocks, ctx->stream));   // exact keys: K5 alone follows
         else if (plan.k1sm) HIPCHK(launch_scansm(sp, metric, launch_blocks, ctx->stream)); // exact keys too
         else if (plan.k1sc) HIPCHK(launch_scansc(sp, metric, launch_blocks, ctx->stream)); // ... and the same ones
+        else if (plan.k1si) HIPCHK(launch_scansi(sp, metric, launch_blocks, ctx->stream)); // exact, from the inverted image
         else HIPCHK(launch_scan(c->format, sp, metric, c->dim, plan.qi, plan.n_blocks, ctx->stream, c->shape.lpr, plan.sparse_global));
         HIPCHK(main.stop());
         ctx->last_kernel = scan_kernel_name(plan, c, metric);

@@ -76,6 +76,8 @@ SYMBOLS = {
     "vsr_set_bit_mfma": (_i, [_vp, _i]),
     "vsr_set_sparse_shared": (_i, [_vp, _i]),
     "vsr_set_sparse_compact": (_i, [_vp, _i]),
+    "vsr_set_sparse_inverted": (_i, [_vp, _i]),
+    "vsr_corpus_build_sparse_inverted": (_i, [_vp]),
     "vsr_set_half_wide": (_i, [_vp, _i]),
     "vsr_set_half_gemm": (_i, [_vp, _i]),
     "vsr_set_query_hint": (_i, [_vp, _i]),

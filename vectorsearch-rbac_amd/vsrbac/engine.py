@@ -188,6 +188,13 @@ class Context:
         with a longer query run as if it were off."""
         check(self._lib.vsr_set_sparse_compact(self._h, int(bool(enable))))
 
+    def set_sparse_inverted(self, on=True):
+        """Run this context's searches over sparse corpora that have their inverted image (Corpus.build_sparse_inverted) on K1si:
+        a query reads the posting lists of its own indices only.  Exact; default off, independent of set_sparse_shared and
+        set_sparse_compact and ahead of both.  A corpus without the image and calls whose longest query has more than 256
+        non-zeros run as if it were off."""
+        check(self._lib.vsr_set_sparse_inverted(self._h, int(bool(on))))
+
     def set_half_wide(self, on=True):
         """Run the shared passes of this context's searches over halfvec corpora and half IVFFlat indexes on K2hw (a row tile
         staged once per workgroup for up to 64 queries) instead of K2h.  Same results; default off."""
@@ -762,6 +769,12 @@ class Corpus:
     def load_hnsw_half(self, graph):
         """load_hnsw over this halfvec corpus (vsr_hnsw_load_half): the graph kernels read the binary16 rows themselves."""
         return HnswIndex(self, graph, half=True)
+
+    def build_sparse_inverted(self):
+        """Build this sparse corpus's inverted image on the GPU (vsr_corpus_build_sparse_inverted): posting lists per block of
+        512 rows, 8 bytes per stored entry, 12 per (row block, distinct index) and row block, 16 per row -- device_bytes counts
+        it.  What Context.set_sparse_inverted searches; a second call builds nothing.  VsrError on a corpus that is not sparse."""
+        check(self._lib.vsr_corpus_build_sparse_inverted(self._h))
 
     def build_hnsw_sparse(self, m=16, ef_construction=64, metric="l2", seed=1, merge_duplicates=False):
         """CREATE INDEX ... USING hnsw (col sparsevec_l2_ops | sparsevec_ip_ops | sparsevec_cosine_ops | sparsevec_l1_ops) over
